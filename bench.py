@@ -1,15 +1,20 @@
 #!/usr/bin/env python3
 """bench.py — accepted tokens/s of the DFlash decode cycle on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Default workload (BASELINE.json configs[1]): Qwen3-8B-shaped target (36 layers) + 5-layer DFlash-b16
 draft, seeded random-init bf16 weights, one request per GPU, 1024 random prompt ids, block 16, temperature 0.  A *step*
 is one decode cycle: draft block forward + fused lm_head/argmax, target verify (NativeTarget: the same HIP kernels;
 `--hf-verify` sends it through the HF forward instead), posterior argmax + accept/commit.  `value` is that leg.
-The same line carries a `batch4` object: BASELINE configs[2]'s per-GPU leg — four requests per GPU as one ragged batch
-sharing every weight byte (dflash_amd.batch) — timed right after the headline with the same models, K steps as well.
+
+A plain run sets up, warms up, times the K steps and prints the line; `batch4`, `cpu_baseline` and `ttft_side` are null.
+`--full` adds what the headline does not need: the `batch4` object (BASELINE configs[2]'s per-GPU leg — four requests per
+GPU as one ragged batch sharing every weight byte, dflash_amd.batch — timed right after the headline with the same
+models, K steps as well), the CPU oracle baseline (`cpu_baseline`) and the target prefill / cycle 0 of a second request
+on warm code (`ttft_side`).  `--dump-outputs DIR` writes what the headline leg's last timed step handed its caller, as
+float64 / float32 .npy files (see dump_outputs); the inputs depend on the arguments only.
 
 Other workloads (builder-run lines, `--workload`):
   llama31-8b       BASELINE configs[3]: Llama-3.1-8B shapes (32 layers, FFN 14336, V 128256, llama3 RoPE), temperature
@@ -326,7 +331,10 @@ def single_leg(args, spec, rank, dev, target, draft, cfg, perm, meta):
                                          switch_margin=0.05, required_streak=2, cooldown_cycles=2, probe_interval=12,
                                          low_accept_threshold=0.35, low_accept_streak=2, adl_rho=0.30, adl_delta=2.0,
                                          adl_k_min=min(sched_c), adl_k_max=max(sched_c), adl_neighborhood=4)
-    for rep in range(2):   # rep 0 pays the one-off costs (code-object loads, allocator, HF lazy init): rep 1 is reported
+    # --full: rep 0 pays the one-off costs (code-object loads, allocator, HF lazy init), rep 1 is reported as ttft_side;
+    # a plain run needs one session only (its prefill and cycle 0 are setup either way)
+    ttft_side = None
+    for rep in range(2 if args.full else 1):
         s = DecodeSession(draft, target, prompt, mask_token_id=mask_id, max_new_tokens=need, max_block_size=bs,
                           stop_token_ids=None, temperature=T, draft_temperature=T if sched else 0.0, draft_token_hook=hook)
         torch.cuda.synchronize()
@@ -336,6 +344,8 @@ def single_leg(args, spec, rank, dev, target, draft, cfg, perm, meta):
         t_c0 = time.perf_counter()
         s.cycle(bs)                  # cycle 0: carries the one-off draft-context prefill of the prompt rows
         torch.cuda.synchronize()
+        if not rep:
+            continue
         hf_pf = args.hf_verify or args.hf_prefill or not getattr(target, "native_prefill", False)
         ttft_side = {"target_prefill_ms": 1e3 * (t_c0 - t_pf), "cycle0_ms": 1e3 * (time.perf_counter() - t_c0),
                      "note": "second request on warm code (outside the timed region): the target prefill runs "
@@ -407,12 +417,19 @@ def single_leg(args, spec, rank, dev, target, draft, cfg, perm, meta):
         if native:
             target.gu_events = (i % meta["layers"], gu_ev[j][0], gu_ev[j][1]) if (instr and not is_moe) else None
             target.moe_events = (i % meta["layers"], gu_ev[j][0], gu_ev[j][1], moe_log[j:j + 1]) if (instr and is_moe) else None
+        last_start = s.start
         tokens += step(instr, allow_graph=use_graph)
         if s.events:
             ev_all.append(s.events)
     torch.cuda.synchronize()
     barrier()
     dt = time.perf_counter() - t0
+    # what the last timed step handed its caller: the committed ids (the step's own ones are [last_start, start)) and
+    # the target's tapped hidden rows of its verify, the draft's context for the next cycle
+    outputs = {"output_ids": s.output_ids[0, :s.start].double().cpu().numpy(),
+               "last_step_ids": s.output_ids[0, last_start:s.start].double().cpu().numpy()}
+    if s.target_hidden is not None:
+        outputs["target_hidden"] = s.target_hidden[0].float().cpu().numpy()
     s.events, s.record_events = None, True
     host_enq = sum(a for a, _ in s.host_times) / max(1, len(s.host_times))
     host_wait = sum(b for _, b in s.host_times) / max(1, len(s.host_times))
@@ -479,7 +496,7 @@ def single_leg(args, spec, rank, dev, target, draft, cfg, perm, meta):
                   # (a run too short to see a run-ahead draft's event pair — it is collected one cycle later — has none)
                   "achieved_GBps": hot_bytes / (draft_ms * 1e-3) / 1e9 if draft_ms > 0 else None,
                   "frac_of_8TBps": hot_bytes / (draft_ms * 1e-3) / 1e9 / 8000.0 if draft_ms > 0 else None},
-        ttft_side=ttft_side,
+        ttft_side=ttft_side, outputs=outputs,
         host_side={"enqueue_ms_per_cycle": 1e3 * host_enq, "poll_wait_ms_per_cycle": 1e3 * host_wait,
                    "mode": ("hipGraph replay (two graphs per cycle); every --event-every-th cycle eager" if use_graph
                             else "eager launches"),
@@ -545,6 +562,7 @@ def batched_leg(args, rank, dev, draft, target, perm, cfg, meta, R):
     tokens = 0
     for i in range(args.steps):   # (phase marks on every --event-every-th cycle, as in the single-request leg)
         dec.events = {} if i % max(1, args.event_every) == 0 else None
+        last_start = list(dec.start)
         out = step(hook)
         if dec.events:
             ev_all.append(dec.events)
@@ -553,6 +571,15 @@ def batched_leg(args, rank, dev, draft, target, perm, cfg, meta, R):
     barrier()
     dt = time.perf_counter() - t0
     dec.events = None
+    # the committed ids of every request (row r: its first start[r] ids, -1 after them) and the ids of the last step
+    ids = dec.output_ids.double().cpu()
+    n, w = max(dec.start[:R]), max(dec.start[r] - last_start[r] for r in range(R))
+    outputs = {"output_ids": torch.full((R, n), -1.0, dtype=torch.float64),
+               "last_step_ids": torch.full((R, w), -1.0, dtype=torch.float64)}
+    for r in range(R):
+        outputs["output_ids"][r, :dec.start[r]] = ids[r, :dec.start[r]]
+        outputs["last_step_ids"][r, :dec.start[r] - last_start[r]] = ids[r, last_start[r]:dec.start[r]]
+    outputs = {k: v.numpy() for k, v in outputs.items()}
 
     def avg_ms(key):
         have = [e for e in ev_all if key in e and None not in e[key]]
@@ -585,7 +612,7 @@ def batched_leg(args, rank, dev, draft, target, perm, cfg, meta, R):
                   "algorithmic_bytes_per_cycle": hot_bytes,
                   "achieved_GBps": hot_bytes / (draft_ms * 1e-3) / 1e9 if draft_ms > 0 else None,
                   "frac_of_8TBps": hot_bytes / (draft_ms * 1e-3) / 1e9 / 8000.0 if draft_ms > 0 else None},
-        cycle_bytes=cyc_bytes, mode="hipGraph replay (three graphs per cycle)" if use_graph else "eager launches")
+        cycle_bytes=cyc_bytes, outputs=outputs, mode="hipGraph replay (three graphs per cycle)" if use_graph else "eager launches")
 
 
 def cpu_leg(args, spec, mean_tau):
@@ -662,6 +689,20 @@ def cpu_leg(args, spec, mean_tau):
                       f"build {build_s:.0f}s untimed"}
 
 
+def dump_outputs(path, outputs, rank):
+    """--dump-outputs: the arrays of the headline leg's last timed step as <path>/<name>.npy (rank r > 0: <name>_rank<r>.npy).
+    Token ids as float64 (exact), hidden rows as float32; well under 64 MB at every shape bench.py runs."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.nbytes for a in outputs.values())
+    if total > 64 << 20:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit 64 MB)")
+    for name, a in outputs.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(path, name + (f"_rank{rank}" if rank else "") + ".npy"), a)
+    log(f"[rank {rank}] outputs of the last timed step -> {path}: " + ", ".join(f"{k} {tuple(a.shape)}" for k, a in outputs.items()))
+
+
 def launch_ranks(n: int) -> int:
     """One fresh child process per GPU (RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* set, as torch.distributed.run would),
     started BEFORE this process makes any GPU call and never by re-exec'ing a process that did.  Rank 0 prints the
@@ -733,9 +774,9 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--requests-per-gpu", type=int, default=1,
                     help="R > 1: the HEADLINE becomes R requests per GPU as one ragged batch sharing the weight stream "
-                         "(BASELINE.json configs[2] uses 4); needs the native verify.  The default line carries that leg at "
+                         "(BASELINE.json configs[2] uses 4); needs the native verify.  A --full line carries that leg at "
                          "R = 4 as the `batch4` object anyway")
-    ap.add_argument("--no-batch4", action="store_true", help="skip the configs[2] leg (the `batch4` object) of the default line")
+    ap.add_argument("--no-batch4", action="store_true", help="skip the configs[2] leg (the `batch4` object) of a --full line")
     ap.add_argument("--eager", action="store_true",
                     help="~215 (N = 1) / ~300 (ragged batch) ctypes launches per cycle instead of hipGraph replays: same GPU time, "
                          "the host's share of a cycle is ~2.2 ms instead of ~0.2 ms (DESIGN.md section 5)")
@@ -752,6 +793,11 @@ def main():
     ap.add_argument("--selftest-cpu", action="store_true",
                     help="launcher plumbing only (tests/test_distributed_cpu.py): ranks rendezvous over gloo, run no "
                          "kernels and report value null; never a measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the `batch4` leg, the CPU oracle baseline and the warm-code ttft_side (a plain run "
+                         "times the headline leg only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline leg's last step computed as DIR/<name>.npy")
     args = ap.parse_args()
 
     if "RANK" not in os.environ and args.gpus > 1:
@@ -796,8 +842,10 @@ def main():
         res = batched_leg(args, rank, dev, draft, target, perm, cfg, meta, R)
     else:
         res = single_leg(args, spec, rank, dev, target, draft, cfg, perm, meta)
-        if args.workload == "qwen3-8b" and not args.no_batch4 and not args.hf_verify:
-            b4 = batched_leg(args, rank, dev, draft, target, perm, cfg, meta, 4)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res["outputs"], rank)
+    if R == 1 and args.full and args.workload == "qwen3-8b" and not args.no_batch4 and not args.hf_verify:
+        b4 = batched_leg(args, rank, dev, draft, target, perm, cfg, meta, 4)
 
     # ---- all timing is done: NOW the RCCL communicator (the world size it sees is the one reported) and the reductions
     from dflash_amd import distributed as D
@@ -832,7 +880,7 @@ def main():
                   "cycle_frac_of_8TBps": b4["cycle_bytes"] / (ms * 1e-3) / 8e12,
                   "roofline": b4["roofline"], "hot_path": b4["hot_path"], "mode": b4["mode"]}
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         try:
             if spec["kind"] != "qwen3":
                 raise RuntimeError("the CPU oracle's target is the dense Qwen3 stack: reported for the default workload only")

@@ -49,7 +49,7 @@ case "${1:-all}" in
     python3 -c "import json; d=json.loads(open('$O/r4_bench_qwen3_30b_a3b.json').read().strip().splitlines()[-1]); print(round(d['value'],1),'tok/s',round(d['ms_per_step'],4),'ms',d['lossless_fraction'],'tau',round(d['mean_acceptance_length'],2),'roofline frac',round(d['roofline']['frac'],3), d['used_block_sizes'])" ;;
   lines)   # the bench lines kept under profiles/ (un-profiled, replay where the workload allows it)
     cd "$R"
-    python3 bench.py > "$O/r4_bench_n1.json" 2> "$O/r4_bench_n1.err"; tail -c 300 "$O/r4_bench_n1.err"
+    python3 bench.py --full > "$O/r4_bench_n1.json" 2> "$O/r4_bench_n1.err"; tail -c 300 "$O/r4_bench_n1.err"
     python3 bench.py --no-cpu-baseline --workload llama31-8b > "$O/r4_bench_llama31_8b.json" 2> "$O/r4_bench_llama.err"
     python3 bench.py --no-cpu-baseline --workload qwen3-30b-a3b > "$O/r4_bench_qwen3_30b_a3b.json" 2> "$O/r4_bench_moe.err"
     python3 bench.py --no-cpu-baseline --steps 200 --warmup 8 > "$O/r4_bench_n1_200cycles.json" 2>/dev/null

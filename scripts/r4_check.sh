@@ -5,7 +5,7 @@ O=gpurun_out/r4check; mkdir -p $O
 python -m pytest tests/test_hip_batch.py tests/test_hip_kernels.py -x -q -m gpu 2>&1 | tail -4
 for m in 0 1 3 5; do echo "== ring rot=$m"; DFL_RING_ROT=$m SRC=frag python scripts/bench_gemm_batch.py gateup lm_head 2>&1 | grep -v -i "warn\|amdgpu.ids"; done
 echo "== slab"; DFL_BATCH_GEMM=slab SRC=frag python scripts/bench_gemm_batch.py gateup lm_head 2>&1 | grep -v -i "warn\|amdgpu.ids"
-python bench.py --no-cpu-baseline > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
+python bench.py --full --no-cpu-baseline > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
 python - <<'PY'
 import json
 d = json.load(open("gpurun_out/r4check/bench_default.json"))

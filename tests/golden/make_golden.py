@@ -8,6 +8,7 @@ outputs the reference computed for them.  `benchmark.py` /
 import; nothing on the measured path uses them.
 
     python tests/golden/make_golden.py
+    python tests/golden/make_golden.py draft_forward   # G1 + the G8 forward vectors alone, in a portable-CPU process
 
 Fixtures (SURVEY.md §8c list):
   G1 draft_forward_<cfg>.npz   multi-cycle DFlashDraftModel.forward with cache
@@ -20,6 +21,7 @@ Fixtures (SURVEY.md §8c list):
   G9 candidates.json           candidate builders + budget rule of benchmark_candidate_solutions.py
   G8 draft_forward_*_wide.npz, e2e_wide.json   block sizes 17..32 (forward vectors; loop runs at 20 / 24 / 32, policy)
 """
+import hashlib
 import json
 import os
 import sys
@@ -38,6 +40,17 @@ import torch
 
 import importlib.util  # noqa: E402
 
+import helpers as H  # noqa: E402
+
+if sys.argv[1:] == ["draft_forward"]:
+    # G1 / G8 forward vectors are pinned bit for bit on any host: CPU code paths common to every x86-64 machine
+    # (helpers.PORTABLE_CPU_ENV, read when torch starts: a fresh process with that environment computes them)
+    if any(os.environ.get(k) != v for k, v in H.PORTABLE_CPU_ENV.items()):
+        import subprocess
+        sys.exit(subprocess.run([sys.executable, *sys.argv], env={**os.environ, **H.PORTABLE_CPU_ENV}).returncode)
+    torch.backends.mkldnn.enabled = False
+    assert torch.backends.cpu.get_cpu_capability() == "DEFAULT"
+
 for name in ("loguru", "rich", "tqdm"):
     if importlib.util.find_spec(name) is None:
         m = types.ModuleType(name)
@@ -51,7 +64,6 @@ from model import DFlashDraftModel, sample as ref_sample  # noqa: E402  (referen
 import benchmark as ref_bench  # noqa: E402  (reference)
 import benchmark_dynamic_schedule as ref_dyn  # noqa: E402  (reference)
 
-import helpers as H  # noqa: E402
 from dflash_amd.config import DFlashConfig  # noqa: E402
 
 torch.set_num_threads(8)
@@ -95,18 +107,20 @@ def gen_draft_forward(tag, cfg, dtype, attn_impl, prompt_len, steps, seed):
     g = torch.Generator().manual_seed(seed)
     cache = DynamicCache()
     out = {"prompt_len": prompt_len, "steps": np.array(steps), "dtype": str(dtype), "attn_impl": attn_impl,
-           "w_checksum": float(sum(v.float().sum() for v in sd.values()))}
+           "w_checksum": float(sum(v.float().sum() for v in sd.values())), "seed": seed}
+    # the inputs are drawn again from the seed by the test (H.draft_forward_inputs); their digest is kept to show it
+    digest = hashlib.sha256()
     start = prompt_len
     ctx_rows = prompt_len
     with torch.inference_mode():
         for c, (bs, tau_next) in enumerate(steps):
-            th = (torch.randn(1, ctx_rows, cfg.fc_in, generator=g) * 1.5).to(dtype)
-            ne = (torch.randn(1, bs, cfg.hidden_size, generator=g) * 0.05).to(dtype)
+            th, ne = H.draft_forward_inputs(cfg, dtype, g, ctx_rows, bs)
+            digest.update(f32(th).tobytes() + f32(ne).tobytes())
             pos = torch.arange(cache.get_seq_length(), start + bs).unsqueeze(0)
             hid = model(target_hidden=th, noise_embedding=ne, position_ids=pos, past_key_values=cache,
                         use_cache=True, is_causal=False)
             cache.crop(start)
-            out[f"th{c}"], out[f"ne{c}"], out[f"hid{c}"] = f32(th), f32(ne), f32(hid)
+            out[f"hid{c}"] = f32(hid)
             out[f"start{c}"] = start
             start += tau_next
             ctx_rows = tau_next
@@ -114,6 +128,7 @@ def gen_draft_forward(tag, cfg, dtype, attn_impl, prompt_len, steps, seed):
         for li in (0, cfg.num_hidden_layers - 1):
             out[f"k_l{li}"] = f32(cache.layers[li].keys)
             out[f"v_l{li}"] = f32(cache.layers[li].values)
+    out["inputs_sha256"] = digest.hexdigest()
     np.savez_compressed(os.path.join(HERE, f"draft_forward_{tag}.npz"), **out)
     print("G1", tag, "done")
 
@@ -315,13 +330,15 @@ def gen_harness():
 
 
 # ---------------------------------------------------------------- G8: blocks wider than 16 rows
+# G8 (bs, tau_next): context rows of the next cycle go up to the block size
+WIDE_STEPS = [(24, 5), (20, 20), (32, 17), (17, 2), (24, 24), (16, 9)]
+
+
 def gen_wide():
     """Block sizes 17..32 (results.md:11-16 sweeps 20 and 24; the scheduler takes any candidate >= 2,
     benchmark_dynamic_schedule.py:44-51): G1-style forward vectors and G4-style loop runs."""
     tiny = H.tiny_cfg()
-    # (bs, tau_next): context rows of the next cycle go up to the block size
-    gen_draft_forward("tiny_bf16_sdpa_wide", tiny, torch.bfloat16, "sdpa", 40,
-                      [(24, 5), (20, 20), (32, 17), (17, 2), (24, 24), (16, 9)], 103)
+    # (the G8 forward vectors, draft_forward_tiny_bf16_sdpa_wide.npz, come from the draft_forward mode)
     cfg = tiny
     res = {}
     ref_bench.cuda_time = time.perf_counter
@@ -436,16 +453,21 @@ if __name__ == "__main__":
     if sys.argv[1:] == ["candidates"]:
         gen_candidates()
         sys.exit(0)
+    if sys.argv[1:] == ["draft_forward"]:
+        tiny, mid = H.tiny_cfg(), H.mid_cfg()
+        # (bs, tau_next): block size this cycle, tokens committed after it (= next cycle's ctx rows)
+        steps = [(16, 1), (16, 7), (16, 16), (12, 3), (8, 8), (16, 2)]
+        gen_draft_forward("tiny_f32_eager", tiny, torch.float32, "eager", 40, steps, 101)
+        gen_draft_forward("tiny_bf16_eager", tiny, torch.bfloat16, "eager", 40, steps, 101)
+        gen_draft_forward("tiny_bf16_sdpa", tiny, torch.bfloat16, "sdpa", 40, steps, 101)
+        gen_draft_forward("mid_bf16_sdpa", mid, torch.bfloat16, "sdpa", 300, steps, 102)
+        gen_draft_forward("tiny_bf16_sdpa_wide", tiny, torch.bfloat16, "sdpa", 40, WIDE_STEPS, 103)
+        sys.exit(0)
     if sys.argv[1:] == ["wide"]:     # later additions are generated alone: the round-1 fixtures stay byte-identical
         gen_wide()
         sys.exit(0)
-    tiny, mid = H.tiny_cfg(), H.mid_cfg()
-    # (bs, tau_next): block size this cycle, tokens committed after it (= next cycle's ctx rows)
-    steps = [(16, 1), (16, 7), (16, 16), (12, 3), (8, 8), (16, 2)]
-    gen_draft_forward("tiny_f32_eager", tiny, torch.float32, "eager", 40, steps, 101)
-    gen_draft_forward("tiny_bf16_eager", tiny, torch.bfloat16, "eager", 40, steps, 101)
-    gen_draft_forward("tiny_bf16_sdpa", tiny, torch.bfloat16, "sdpa", 40, steps, 101)
-    gen_draft_forward("mid_bf16_sdpa", mid, torch.bfloat16, "sdpa", 300, steps, 102)
+    import subprocess
+    subprocess.run([sys.executable, os.path.abspath(__file__), "draft_forward"], check=True)
     gen_argmax()
     gen_accept()
     gen_e2e()

@@ -31,6 +31,21 @@ from oracle.torch_target import TorchQwen3Target  # noqa: E402
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
+# The bit-exact draft-forward vectors (G1, G8) are computed, and checked, in a process whose CPU kernels take code paths
+# every x86-64 host shares: ATen's non-vectorised kernels, MKL's conditional-numerical-reproducibility branch and no
+# oneDNN (torch.backends.mkldnn off).  With the default dispatch the last bits follow the host's ISA and BLAS branch.
+# Read when torch starts, so they are set in the environment of a fresh process (see make_golden.py draft_forward).
+PORTABLE_CPU_ENV = {"ATEN_CPU_CAPABILITY": "default", "MKL_CBWR": "COMPATIBLE"}
+
+
+def draft_forward_inputs(cfg, dtype, g: torch.Generator, ctx_rows: int, bs: int):
+    """The target-hidden rows and noise embeddings of one G1/G8 cycle, drawn from g (generator and test alike).  Drawn in
+    float64: torch's fp32 normal sampler has ISA-specific vector paths, the fp64 one gives the same bits on every host."""
+    th = (torch.randn(1, ctx_rows, cfg.fc_in, generator=g, dtype=torch.float64) * 1.5).to(dtype)
+    ne = (torch.randn(1, bs, cfg.hidden_size, generator=g, dtype=torch.float64) * 0.05).to(dtype)
+    return th, ne
+
+
 # Smallest shape the HIP kernels accept (K multiple of 512, head_dim 128).
 TINY = dict(hidden_size=512, num_hidden_layers=2, num_attention_heads=4, num_key_value_heads=2, head_dim=128,
             intermediate_size=1024, vocab_size=2048, num_target_layers=6, block_size=16, rope_theta=1e6,

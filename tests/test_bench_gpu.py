@@ -23,8 +23,8 @@ def _run(args, env=None, timeout=420):
 def test_bench_line_contract_small():
     """A short run on 8 target layers: every key of the contract, the roofline object from live HIP events around the
     lm_head launch, losslessness of the scripted run — and the `batch4` object (BASELINE configs[2]'s per-GPU leg: four
-    requests per GPU as one ragged batch) timed behind the headline by the same command."""
-    d = _run(["--steps", "6", "--warmup", "1", "--target-layers", "8", "--no-cpu-baseline"])
+    requests per GPU as one ragged batch) timed behind the headline by the same --full command."""
+    d = _run(["--steps", "6", "--warmup", "1", "--target-layers", "8", "--no-cpu-baseline", "--full"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline", "batch4"):
         assert k in d, k
@@ -76,7 +76,31 @@ def test_two_rank_flow_rehearsed_on_one_gpu():
     127.0.0.1, barrier around the timed region, reduce the timing scalars and rank 0 prints the line with n_gpus = 2.
     Rehearsal mode (DFL_BENCH_SHARE_GPU=1): both ranks on cuda:0 over gloo — RCCL refuses two ranks on one device;
     the 8-GPU run itself is the driver's."""
-    d = _run(["--gpus", "2", "--steps", "4", "--warmup", "1", "--target-layers", "8"], env={"DFL_BENCH_SHARE_GPU": "1"})
+    d = _run(["--gpus", "2", "--steps", "4", "--warmup", "1", "--target-layers", "8", "--full"],
+             env={"DFL_BENCH_SHARE_GPU": "1"})
     assert d["n_gpus"] == 2 and d["config"]["parallelism"] == "dp2" and d["config"]["requests"] == 2
     assert d["lossless_fraction"] == 1.0 and "rehearsal" in d
-    assert d["cpu_baseline"] is None            # rank 0 at N = 1 only
+    assert d["cpu_baseline"] is None            # rank 0 at N = 1 only, --full or not
+
+
+def test_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) times the headline leg only, and --dump-outputs writes what its last timed step handed the
+    caller: float64 ids / float32 hidden rows, the same on a second run with the same arguments."""
+    import numpy as np
+    args = ["--steps", "5", "--warmup", "1", "--target-layers", "4"]
+    d = _run([*args, "--dump-outputs", str(tmp_path / "a")])
+    assert d["steps"] == 5 and d["ms_per_step"] > 0 and d["lossless_fraction"] == 1.0 and d["value"] > 0
+    assert d["batch4"] is None and d["cpu_baseline"] is None and d["ttft_side"] is None
+    a = {f.stem: np.load(f) for f in (tmp_path / "a").glob("*.npy")}
+    assert set(a) == {"output_ids", "last_step_ids", "target_hidden"}
+    assert a["output_ids"].dtype == a["last_step_ids"].dtype == np.float64 and a["target_hidden"].dtype == np.float32
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    ids, last = a["output_ids"], a["last_step_ids"]
+    assert ids.ndim == 1 and ids.size > 1024 and 1 <= last.size <= 16 and (ids[-last.size:] == last).all()
+    assert (ids == np.round(ids)).all() and ids.min() >= 0
+    th = a["target_hidden"]   # the verify's tapped rows: one per committed id of the step, the draft's 5 taps x 4096
+    assert th.shape == (last.size, 5 * 4096) and np.isfinite(th).all() and np.abs(th).max() > 0
+    _run([*args, "--dump-outputs", str(tmp_path / "b")])
+    b = {f.stem: np.load(f) for f in (tmp_path / "b").glob("*.npy")}
+    assert (b["output_ids"] == ids).all() and (b["last_step_ids"] == last).all()
+    np.testing.assert_allclose(b["target_hidden"], th, rtol=0, atol=1e-2 * float(np.abs(th).max()))

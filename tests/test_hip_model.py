@@ -38,10 +38,11 @@ def test_forward_matches_reference_vectors(tag, cfgf):
     cfg = cfgf()
     m = make_model(cfg)
     cache = m.new_cache(int(z["prompt_len"]) + 200)
+    g, ctx_rows = torch.Generator().manual_seed(int(z["seed"])), int(z["prompt_len"])   # the generator's inputs
     for c, (bs, tau_next) in enumerate(z["steps"].tolist()):
         start = int(z[f"start{c}"])
-        th = torch.from_numpy(z[f"th{c}"]).to(BF16).to(dev())
-        ne = torch.from_numpy(z[f"ne{c}"]).to(BF16).to(dev())
+        th, ne = (t.to(dev()) for t in H.draft_forward_inputs(cfg, BF16, g, ctx_rows, bs))
+        ctx_rows = tau_next
         pos = torch.arange(cache.get_seq_length(), start + bs, device=dev()).unsqueeze(0)
         hid = m(target_hidden=th, noise_embedding=ne, position_ids=pos, past_key_values=cache, use_cache=True,
                 is_causal=False)
