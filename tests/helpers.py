@@ -239,3 +239,31 @@ def assert_ids_match_where_safe(name: str, got_ids: torch.Tensor, ref_logits: to
     assert int(safe.sum()) >= min_safe, f"{name}: only {int(safe.sum())} margin-screened rows (need >= {min_safe})"
     assert torch.equal(got_ids[safe], ref_ids[safe]), f"{name}: ids differ on margin-screened rows"
     assert agree >= min_agree, f"{name}: id agreement {agree:.3f} < {min_agree}"
+
+
+# ---- ragged-batch kernel scaffolding (frag16 tiles, per-request length records) --------------
+def gen(seed: int) -> torch.Generator:
+    return torch.Generator().manual_seed(seed)
+
+
+def unfrag(frag: torch.Tensor, K: int) -> torch.Tensor:
+    """frag16 [K/8][16][8] (flat) -> the 16 rows [16, K]."""
+    return frag.view(K // 8, 16, 8).permute(1, 0, 2).reshape(16, K)
+
+
+def frag_of(x: torch.Tensor) -> torch.Tensor:
+    """x [MT, 16, K] bf16 on the GPU -> [MT, 16*K] frag16 tiles (dfl_pack_rows per tile)."""
+    from dflash_amd import ops
+    MT, _, K = x.shape
+    out = torch.empty(MT, 16 * K, dtype=torch.bfloat16, device=x.device)
+    for r in range(MT):
+        ops.pack_rows(x[r], 16, out[r])
+    return out
+
+
+def dyn_records(vals, MT: int, device) -> torch.Tensor:
+    """int32 [MT, 8] length records with (tau, bs) of request r in words 1, 2 (dflash_amd.ops.DYN_*)."""
+    d = torch.zeros(MT, 8, dtype=torch.int32)
+    for r, (tau, bs) in enumerate(vals):
+        d[r, 1], d[r, 2] = tau, bs
+    return d.to(device)

@@ -161,28 +161,11 @@ def test_batched_draft_and_verify_match_single_kernels():
 
 
 # ------------------------------------------------------------------ kernel level
-def _gen(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-def _unfrag(frag, K):
-    return frag.view(K // 8, 16, 8).permute(1, 0, 2).reshape(16, K)
-
-
-def _frag_of(x):  # x [MT, 16, K] bf16 cuda -> [MT, 16*K] frag16
-    from dflash_amd import ops
-    MT, _, K = x.shape
-    out = torch.empty(MT, 16 * K, dtype=BF16, device=x.device)
-    for r in range(MT):
-        ops.pack_rows(x[r], 16, out[r])
-    return out
+_gen, _unfrag, _frag_of = H.gen, H.unfrag, H.frag_of
 
 
 def _dyn(vals, MT):
-    d = torch.zeros(MT, 8, dtype=torch.int32)
-    for r, (tau, bs) in enumerate(vals):
-        d[r, 1], d[r, 2] = tau, bs
-    return d.to(dev())
+    return H.dyn_records(vals, MT, dev())
 
 
 @pytest.mark.parametrize("R,N,K", [(1, 64, 512), (2, 48, 4096), (3, 256, 4096), (4, 4096, 4096), (4, 512, 12288),
@@ -223,6 +206,8 @@ def test_gemm_resid_batch_exact_small_ints(R, N, K):
 
 @pytest.mark.parametrize("R,I,K", [(2, 64, 512), (4, 1024, 4096), (3, 12288 // 8, 4096)])
 def test_gemm_silu_mul_batch(R, I, K):
+    """Both sources: frag16 tiles reach the ring kernel (dfl_k_gemm_r, the default form), plain rows the slab kernel
+    (k_gemm_b, the fallback)."""
     from dflash_amd import ops
     MT = ops.batch_tiles(R)
     g = _gen(I + K + R)
@@ -230,29 +215,32 @@ def test_gemm_silu_mul_batch(R, I, K):
     up = (torch.randn(I, K, generator=g) * 0.05).to(BF16).to(dev())
     x = torch.randn(MT, 16, K, generator=g).to(BF16).to(dev())
     dyn = _dyn([(0, 16)] * MT, MT)
-    act = torch.zeros(MT, 16 * I, dtype=BF16, device=dev())
     act1 = torch.zeros(16 * I, dtype=BF16, device=dev())
     wp = ops.pack_weight_gateup(gate, up)
     ws = ops.gemm_batch_ws(2 * I, K, dev())
-    ops.gemm_silu_mul_batch(wp, ops.brows_plain(x, ops.DYN_BS), R, I, K, act, ws, dyn)
-    for r in range(R):
-        gb = (x[r].float() @ gate.float().T).to(BF16).float()
-        ub = (x[r].float() @ up.float().T).to(BF16).float()
-        want = (torch.nn.functional.silu(gb).to(BF16).float() * ub).to(BF16).float()
-        got = _unfrag(act[r], I).float()
-        d = (got - want).abs()
-        assert d.max() <= 2e-2 * want.abs().max() and d.mean() <= 2e-3 * want.abs().max()
-        # and against the single-request kernel (same rounding points, other summation order)
-        ops.gemm_silu_mul(wp, ops.rows_plain(x[r]), I, K, act1)
-        d1 = (got - _unfrag(act1, I).float()).abs()
-        assert d1.max() <= 2e-2 * want.abs().max()
+    for mode in ("frag", "rows"):
+        act = torch.zeros(MT, 16 * I, dtype=BF16, device=dev())
+        src = ops.brows_frag(_frag_of(x)) if mode == "frag" else ops.brows_plain(x, ops.DYN_BS)
+        ops.gemm_silu_mul_batch(wp, src, R, I, K, act, ws, dyn)
+        for r in range(R):
+            gb = (x[r].float() @ gate.float().T).to(BF16).float()
+            ub = (x[r].float() @ up.float().T).to(BF16).float()
+            want = (torch.nn.functional.silu(gb).to(BF16).float() * ub).to(BF16).float()
+            got = _unfrag(act[r], I).float()
+            d = (got - want).abs()
+            assert d.max() <= 2e-2 * want.abs().max() and d.mean() <= 2e-3 * want.abs().max(), (mode, r)
+            # and against the single-request kernel (same rounding points, other summation order)
+            ops.gemm_silu_mul(wp, ops.rows_plain(x[r]), I, K, act1)
+            d1 = (got - _unfrag(act1, I).float()).abs()
+            assert d1.max() <= 2e-2 * want.abs().max(), (mode, r)
 
 
 @pytest.mark.parametrize("R,V,K,row0", [(2, 2048, 512, 1), (4, 4096 + 16 * 7, 4096, 0), (3, 151936, 4096, 1)])
 def test_gemm_argmax_batch(R, V, K, row0):
     """Fused lm_head + argmax for R requests with different row counts: ids equal
     torch.argmax of the bf16 logits the same kernel materialises, and the logits equal
-    the fp32 reference within bf16 rounding."""
+    the fp32 reference within bf16 rounding.  Both sources: frag16 tiles reach the ring kernel
+    (dfl_k_gemm_r, the default form), plain rows the slab kernel (k_gemm_b, the fallback)."""
     from dflash_amd import ops
     MT = ops.batch_tiles(R)
     g = _gen(V + K)
@@ -262,17 +250,19 @@ def test_gemm_argmax_batch(R, V, K, row0):
     dyn = _dyn([(0, b) for b in bss], MT)
     wp = ops.pack_weight(w)
     ws = ops.gemm_batch_ws(V, K, dev())
-    ids = torch.full((MT, 16), -1, dtype=torch.int64, device=dev())
-    logits = torch.zeros(MT, 16, V, dtype=BF16, device=dev())
-    ops.gemm_argmax_batch(wp, ops.brows_plain(x, ops.DYN_BS), R, V, K, row0, 16 - row0, ws, ids, row0, dyn,
-                          nrows_dyn_word=ops.DYN_BS, logits=logits)
-    for r in range(R):
-        n = bss[r] - row0
-        ref = (x[r].float() @ w.float().T)[row0:bss[r]]
-        lg = logits[r, row0:bss[r]]
-        assert (lg.float() - ref).abs().max() <= 2e-2 * ref.abs().max()
-        assert torch.equal(ids[r, row0:row0 + n], torch.argmax(lg, dim=-1))
-        assert torch.all(ids[r, row0 + n:] == -1) and torch.all(ids[r, :row0] == -1)
+    for mode in ("frag", "rows"):
+        ids = torch.full((MT, 16), -1, dtype=torch.int64, device=dev())
+        logits = torch.zeros(MT, 16, V, dtype=BF16, device=dev())
+        src = ops.brows_frag(_frag_of(x)) if mode == "frag" else ops.brows_plain(x, ops.DYN_BS)
+        ops.gemm_argmax_batch(wp, src, R, V, K, row0, 16 - row0, ws, ids, row0, dyn, nrows_dyn_word=ops.DYN_BS,
+                              logits=logits)
+        for r in range(R):
+            n = bss[r] - row0
+            ref = (x[r].float() @ w.float().T)[row0:bss[r]]
+            lg = logits[r, row0:bss[r]]
+            assert (lg.float() - ref).abs().max() <= 2e-2 * ref.abs().max(), (mode, r)
+            assert torch.equal(ids[r, row0:row0 + n], torch.argmax(lg, dim=-1)), (mode, r)
+            assert torch.all(ids[r, row0 + n:] == -1) and torch.all(ids[r, :row0] == -1), (mode, r)
 
 
 def test_norm_frag_then_gemm_f32_batch():

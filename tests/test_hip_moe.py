@@ -701,3 +701,115 @@ def test_moe_target_one_copy_keep_hf_false():
     pa, _ = a.verify(block, P, ca)
     pb, _ = b.verify(block, P, cb)
     assert torch.equal(pa, pb)
+
+
+def _frag_rows(a):
+    """a [..., 16, I] bf16 rows -> [..., 16*I] frag16 ([I/8][16][8] per tile)."""
+    *lead, m, I = a.shape
+    return a.reshape(-1, m, I // 8, 8).permute(0, 2, 1, 3).reshape(*lead, m * I).contiguous()
+
+
+@pytest.mark.parametrize("nsplit,N", [(1, 2048), (2, 2048), (4, 2048), (4, 2064)],
+                         ids=["ns1-N2048-down<2,16>", "ns2-N2048-down<2,16>", "ns4-N2048-down<2,16>", "ns4-N2064-down<1,16>"])
+def test_moe_down_at_the_target_grid(nsplit, N):
+    """dfl_moe_down at the 30B-A3B expert geometry (128 experts, I 768, top-8 on 16 rows) with the expert shares NativeTarget
+    asks for (nsplit = 4, target.py) and 1 / 2, against the fp32 experts loop (Qwen3MoeExperts.forward: the routing-weighted
+    sum of act @ down^T); N % 32 != 0 takes the one-tile form k_moe_down<1, 16>.  Inactive experts' activations are NaN
+    (never read) and every output share is written."""
+    from dflash_amd import ops
+    E, I, top_k = 128, 768, 8
+    g = torch.Generator(device=dev()).manual_seed(N + nsplit)
+    dn = (torch.randn(E, N, I, generator=g, device=dev()) * 0.03).to(BF16)
+    a = torch.randn(E, 16, I, generator=g, device=dev()).to(BF16)
+    wt = torch.zeros(16, E, dtype=BF16, device=dev())
+    for m in range(16):
+        sel = torch.randperm(E - 8, generator=g, device=dev())[:top_k]          # the last 8 experts stay idle
+        wt[m, sel] = torch.rand(top_k, generator=g, device=dev()).to(BF16)
+    active = (wt != 0).any(dim=0)
+    k = int(active.sum())
+    lst = torch.zeros(E, dtype=torch.int32, device=dev())
+    lst[:k] = active.nonzero()[:, 0].to(torch.int32)
+    n = torch.tensor([k], dtype=torch.int32, device=dev())
+    act = _frag_rows(a)
+    act[~active] = float("nan")
+    dn_p = torch.stack([ops.pack_weight(dn[e].contiguous()) for e in range(E)])
+    out = torch.full((nsplit, 16, N), float("nan"), dtype=torch.float32, device=dev())
+    ops.moe_down(dn_p, act, wt, lst, n, E, N, I, nsplit, out)
+    assert torch.isfinite(out).all()
+    y = torch.einsum("emi,eni->emn", a.float(), dn.float())                  # every expert on every row, fp32
+    ref = (wt.float().T[:, :, None] * y).sum(0)
+    H.assert_close(f"moe_down nsplit {nsplit} N {N}", out.sum(0), ref)
+
+
+@pytest.mark.parametrize("K,with_norm,rows", [(2048, True, 16), (2048, False, 11), (4096, True, 11), (4096, False, 16)],
+                         ids=["K2048-router<4,true>", "K2048-router<4,false>", "K4096-router<8,true>", "K4096-router<8,false>"])
+def test_moe_router_against_torch(K, with_norm, rows):
+    """dfl_moe_router directly against torch (Qwen3MoeRMSNorm, the gate Linear in fp32, Qwen3MoeTopKRouter's softmax /
+    top-k / renormalise): normalised rows bit-equal, router logits within bf16 rounding of fp32, the routing equal to
+    torch's applied to the kernel's own bf16 logits (weights within a bf16 step: the kernel's exp differs from torch's
+    in the last fp32 bits), and equal to the fp32 routing on rows whose fp32 top-k margin exceeds the rounding."""
+    from dflash_amd import ops
+    E, top_k = 128, 8
+    g = torch.Generator(device=dev()).manual_seed(K + rows + with_norm)
+    rw = (torch.randn(E, K, generator=g, device=dev()) * 0.3).to(BF16)
+    wp = ops.pack_weight(rw)
+    nw = (1 + 0.1 * torch.randn(K, generator=g, device=dev())).to(BF16)
+    h = torch.randn(16, K, generator=g, device=dev()).to(BF16)
+    dyn = torch.zeros(8, dtype=torch.int32, device=dev())
+    ops.set_dyn(dyn, 0, 0, rows, 0)
+    ticket = torch.zeros(1, dtype=torch.int32, device=dev())
+    if with_norm:
+        hf = h.float()
+        xr = (nw.float() * (hf * torch.rsqrt(hf.pow(2).mean(-1, keepdim=True) + 1e-6)).to(BF16).float()).to(BF16)
+        xr[rows:] = 0
+        xn = torch.full((16 * K,), 3.0, dtype=BF16, device=dev())
+    else:
+        xr = h
+        xn = _frag_rows(h)
+    wt = torch.full((16, E), 7.0, dtype=BF16, device=dev())
+    active = torch.full((E,), 9, dtype=torch.int32, device=dev())
+    lst = torch.full((E,), -1, dtype=torch.int32, device=dev())
+    n = torch.zeros(1, dtype=torch.int32, device=dev())
+    rlog = torch.zeros(16, E, dtype=BF16, device=dev())
+    ops.moe_router(h=h if with_norm else None, norm_w=nw if with_norm else None, eps=1e-6, xn=xn, wp_router=wp, K=K, E=E,
+                   top_k=top_k, norm_topk=True, rlog=rlog, wt=wt, active=active, lst=lst, n_active=n, ticket=ticket, dyn=dyn,
+                   dyn_word=ops.DYN_BS)
+    torch.cuda.synchronize()
+    assert int(ticket) == 0
+    assert torch.equal(xn.view(K // 8, 16, 8).permute(1, 0, 2).reshape(16, K), xr)
+    ref32 = xr[:rows].float() @ rw.float().T
+    H.assert_close(f"moe router logits K {K}", rlog[:rows], ref32, max_rel=2 ** -7, mean_rel=2 ** -9)
+    # torch's routing of the kernel's bf16 logits
+    p = torch.softmax(rlog[:rows].float(), dim=-1)
+    v, i = torch.topk(p, top_k, dim=-1)
+    v = v / v.sum(dim=-1, keepdim=True)
+    wref = torch.zeros(rows, E, device=dev())
+    wref[torch.arange(rows, device=dev())[:, None], i] = v.to(BF16).float()
+    got = wt.float()
+    assert torch.equal(got[rows:], torch.zeros(16 - rows, E, device=dev()))
+    srt = p.sort(dim=-1, descending=True).values
+    clear = srt[:, top_k - 1] > srt[:, top_k]                 # the k-th and (k+1)-th differ: one correct selection
+    assert int(clear.sum()) >= rows // 2
+    for m in range(rows):
+        sel = got[m] != 0
+        # any row (bf16 logits can tie at the k-th place): a top-k of the kernel's logits, renormalised over itself
+        assert int(sel.sum()) == top_k and p[m][sel].min() >= p[m][~sel].max(), m
+        assert torch.allclose(got[m][sel], (p[m][sel] / p[m][sel].sum()).to(BF16).float(), rtol=2 ** -7, atol=1e-4), m
+        if clear[m]:
+            assert torch.equal(sel, wref[m] != 0), m
+            assert torch.allclose(got[m], wref[m], rtol=2 ** -7, atol=1e-4), m
+    act_ref = (got != 0).any(dim=0)
+    assert torch.equal(active != 0, act_ref)
+    k = int(n)
+    assert k == int(act_ref.sum()) and lst[:k].tolist() == act_ref.nonzero()[:, 0].tolist()
+    # the fp32 routing, where the fp32 k-th / (k+1)-th logit margin exceeds what bf16 rounding of the logits can close
+    s32 = ref32.sort(dim=-1, descending=True).values
+    safe = (s32[:, top_k - 1] - s32[:, top_k]) > 2 ** -6 * ref32.abs().max(dim=-1).values
+    sel32 = torch.zeros(rows, E, dtype=torch.bool, device=dev())
+    sel32[torch.arange(rows, device=dev())[:, None], ref32.topk(top_k, dim=-1).indices] = True
+    print(f"[parity] moe router K {K}: {int(clear.sum())}/{rows} rows with a clear bf16 selection, "
+          f"{int(safe.sum())}/{rows} with a clear fp32 one")
+    assert int(safe.sum()) >= 1
+    for m in range(rows):
+        if safe[m]:
+            assert torch.equal(got[m] != 0, sel32[m]), m
