@@ -178,6 +178,11 @@ inline bool fill_src(RowSrc &d, const dfl_rows *s, int K, const char *who) {
     dfl_set_error("%s: a normalised row source needs K <= 4096 (K=%d)", who, K);
     return false;
   }
+  // one partial per 16-column tile of K <= 4096: the prologue's 16 waves x 4 lane groups x 4 loads read 256 slots
+  if (ok && s->mode == 2 && s->nss > 256) {
+    dfl_set_error("%s: a normalised row source takes at most 256 partial sums of squares (nss=%d)", who, s->nss);
+    return false;
+  }
   return ok;
 }
 

@@ -324,8 +324,8 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &a) {
         nwv[mt] = *reinterpret_cast<const bf16x8 *>(nb + c * 16);
       }
       if (NORM && s.mode == 2) {  // uniform (a kernel argument); the loads inside are clamped, not guarded
-        // the nss partial sums of squares of a row are summed by the 16 waves together:
-        // wave w takes partials w, w+16, ... (four loads in flight per lane per 256)
+        // the nss <= 256 partial sums of squares of a row are summed by the 16 waves together:
+        // wave w takes partials w, w+16, ... (four loads in flight per lane)
         const int m = l & 15, part = l >> 4;
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -379,17 +379,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &a) {
           float v[4];
 #pragma unroll
           for (int u = 0; u < 4; ++u) v[u] = (w + 16 * (part + 4 * u)) < s.nss ? ssv[mt][u] : 0.f;
-          float t = (v[0] + v[1]) + (v[2] + v[3]);
-          for (int base = 256; base < s.nss; base += 256) {  // more than 256 partials: rare, late loads
-            float v2[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-              const int i = base + w + 16 * (part + 4 * u);
-              v2[u] = s.ss[(i < s.nss ? i : s.nss - 1) * 16 + m];
-              v2[u] = i < s.nss ? v2[u] : 0.f;
-            }
-            t += (v2[0] + v2[1]) + (v2[2] + v2[3]);
-          }
+          float t = (v[0] + v[1]) + (v[2] + v[3]);  // nss <= 256 (fill_src): the prologue's loads cover every partial
           t += __shfl_xor(t, 16, 64);
           t += __shfl_xor(t, 32, 64);
           if (part == 0) ssred[mt][w][m] = t;

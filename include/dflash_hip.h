@@ -63,7 +63,8 @@ extern "C" {
  *                   it builds its fragments: x = norm_w * bf16(h * rsqrt(sum_i ss[i][m] / K
  *                   + eps)) (Qwen3RMSNorm, tf:models/qwen3/modeling_qwen3.py:59-64), where
  *                   ss[nss][16] are partial sums of squares of each row left by the
- *                   producer (dfl_embed_rows: nss = 1; dfl_gemm_resid: nss = N/16).
+ *                   producer (dfl_embed_rows: nss = 1; dfl_gemm_resid: nss = N/16), 1 <= nss <= 256;
+ *                   K <= 4096.
  * Rows >= dyn[valid_word] (valid_word >= 0) are treated as zero. */
 typedef struct dfl_rows {
   const void *frag;
