@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # DFL_LIB_PATH: another build of the SAME library (a diagnostic -D build, an older revision for a same-box A/B)
 LIB_PATH = os.environ.get("DFL_LIB_PATH") or os.path.join(HERE, "lib", "libdflash_hip.so")
 
-_p, _i, _i64, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
+_p, _i, _i64, _f, _u64 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_uint64
 
 
 class Rows(C.Structure):
@@ -47,6 +47,8 @@ SIGNATURES = {
     "dfl_argmax_ws_bytes": (_i64, []),
     "dfl_gemm_argmax": (_i, [_p, _r, _i, _i, _i, _i, _p, _i, _p, _p, _i, _p, _p, _p]),
     "dfl_gemm_argmax_timed": (_i, [_p, _r, _i, _i, _i, _i, _p, _i, _p, _p, _i, _p, _p, _p, _p, _p]),
+    "dfl_gemm_sample": (_i, [_p, _r, _i, _i, _i, _i, _p, _i, _p, _p, _i, _p, _p, _u64, _f, _i, _p, _i, _i, _i, _p]),
+    "dfl_sample_rows": (_i, [_p, _i64, _i, _i, _u64, _f, _i, _i, _p, _i, _p, _p, _p]),
     "dfl_norm_pack": (_i, [_p, _i, _i64, _i, _i, _p, _p, _p, _p, _p, _i64, _p, _f, _p, _i, _p, _i, _p]),
     "dfl_qknorm_rope_append": (_i, [_p, _i, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _f, _p, _p, _i, _p, _p, _p, _i, _p,
                                     _i, _i, _p]),
@@ -105,6 +107,8 @@ SIGNATURES = {
     "dfl_gemm_silu_mul_batch": (_i, [_p, _rb, _i, _i, _i, _p, _i64, _p, _p, _p]),
     "dfl_gemm_resid_batch": (_i, [_p, _rb, _i, _i, _i, _p, _i64, _i64, _i, _p, _i64, _i64, _p, _i64, _p, _p, _p]),
     "dfl_gemm_argmax_batch": (_i, [_p, _rb, _i, _i, _i, _i, _i, _p, _i, _p, _p, _i64, _i, _p, _i64, _p]),
+    "dfl_gemm_sample_batch": (_i, [_p, _rb, _i, _i, _i, _i, _i, _p, _i, _p, _p, _i64, _i, _p, _i64, _p, _f, _i, _i, _i, _i,
+                                   _p]),
     "dfl_embed_rows_batch": (_i, [_p, _p, _i64, _i, _p, _i64, _i, _p, _i64, _p, _i, _p]),
     "dfl_norm_frag_batch": (_i, [_p, _i64, _i64, _i, _p, _i, _i64, _i, _p, _i64, _i64, _p, _f, _p, _i64, _i, _p, _i, _p]),
     "dfl_kv_append_batch": (_i, [_p, _i, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _p, _i64, _f, _p, _p, _i, _p, _p, _i,

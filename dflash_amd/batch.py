@@ -26,7 +26,7 @@ from typing import Callable, Optional, Sequence
 import torch
 
 from . import ops
-from .generate import _bf16_table, _taps, _trim, capture_graph, cuda_time
+from .generate import _bf16_table, _draw_rows, _taps, _trim, capture_graph, cuda_time, resolve_seed
 from .model import DFlashDraftModel
 from .target import NativeTarget
 from .utils import sample
@@ -51,15 +51,19 @@ class BatchedDecoder:
 
     def __init__(self, model: DFlashDraftModel, target: NativeTarget, n_requests: int, max_rows: int,
                  out_len: int, mask_token_id: int, stop_token_ids=None, max_splits: int = 32,
-                 temperature: float = 0.0, tiles_per_request: int = 1):
+                 temperature: float = 0.0, tiles_per_request: int = 1, sampler: str = "torch",
+                 draft_temperature: float = 0.0):
         if not isinstance(target, NativeTarget):
             raise TypeError("BatchedDecoder needs a dflash_amd.NativeTarget (see module docstring)")
         if tiles_per_request not in (1, 2):
             raise ValueError("tiles_per_request is 1 (blocks of <= 16 rows) or 2 (blocks of <= 32 rows)")
         if not 1 <= n_requests * tiles_per_request <= MAX_GROUP:
             raise ValueError(f"a group holds 1..{MAX_GROUP} sixteen-row tiles (requests x tiles_per_request)")
-        if tiles_per_request == 2 and temperature >= 1e-5:
-            raise NotImplementedError("blocks of more than 16 rows in the ragged batch are greedy (T = 0)")
+        if tiles_per_request == 2 and temperature >= 1e-5 and sampler != "device":
+            raise NotImplementedError("blocks of more than 16 rows in the ragged batch sample at T > 0 with sampler='device' only")
+        if draft_temperature >= 1e-5 and sampler != "device":
+            raise NotImplementedError("a sampled draft in the ragged batch needs sampler='device'")
+        resolve_seed(sampler, None, needed=False)   # (validates the name)
         if model.w is None:
             raise RuntimeError("draft weights not loaded")
         c, t = model.config, target
@@ -79,6 +83,10 @@ class BatchedDecoder:
         self.max_rows, self.out_len, self.mask_id = int(max_rows), int(out_len), int(mask_token_id)
         self.max_splits = max_splits
         self.temperature = float(temperature)
+        self.draft_temperature = float(draft_temperature)
+        # sampler="device": T > 0 draws are seeded on the device, one seed per request slot in a
+        # device array, so that a captured graph and a re-admitted slot keep working
+        self.sampler = sampler
         self._logits = None
         R, MT, H, I = self.R, self.MT, c.hidden_size, c.intermediate_size
         z = lambda *s, dt=BF16: torch.zeros(*s, dtype=dt, device=dev)  # noqa: E731
@@ -95,6 +103,7 @@ class BatchedDecoder:
         self.post = z(NREQ, self.BW, dt=I64)
         self.ids_tmp = z(MT, 16, dt=I64)      # TPR = 2: the draft's ids of every tile row (row 0 of tile 0 is not a draft token)
         self.result = z(MT, 4, dt=I32)
+        self.seeds = z(NREQ, dt=I64)
         self.output_ids = torch.full((NREQ, out_len), self.mask_id, dtype=I64, device=dev)
         self.stop_t = torch.tensor(stop_token_ids, dtype=I64, device=dev) if stop_token_ids else None
         # ---- draft scratch
@@ -162,11 +171,11 @@ class BatchedDecoder:
 
     # ------------------------------------------------------------------ admission
     @torch.inference_mode()
-    def admit(self, r: int, input_ids: torch.Tensor, temperature: float = 0.0) -> None:
+    def admit(self, r: int, input_ids: torch.Tensor, temperature: float = 0.0, seed: Optional[int] = None) -> None:
         """Prefill request r (model/dflash.py:218-229): target prefill through the wrapped
         model, K/V into the group cache, first token sampled, the prompt's context rows
         projected into the draft cache except the last <= 16, which become the first
-        cycle's context tile."""
+        cycle's context tile.  seed (sampler="device"): the request's seed (None: one from torch's RNG)."""
         m, t, c = self.model, self.target, self.cfg
         if input_ids.shape[0] != 1 or not input_ids.is_cuda:
             raise ValueError("admit: input_ids must be a [1, P] GPU tensor")
@@ -181,7 +190,12 @@ class BatchedDecoder:
         out = t.prefill(input_ids, tc, output_hidden_states=True, tap_layers=self.model.target_layer_ids)
         self.output_ids[r].fill_(self.mask_id)
         self.output_ids[r, :P] = input_ids[0]
-        first = sample(out.logits, temperature)
+        if self.sampler == "device" and (temperature >= 1e-5 or self.temperature >= 1e-5):
+            sd = resolve_seed("device", seed)
+            self.seeds[r] = ops.seed_i64(sd)
+            first = _draw_rows(out.logits[:, -1:], temperature, sd, P) if temperature >= 1e-5 else sample(out.logits, 0.0)
+        else:
+            first = sample(out.logits, temperature)
         self.output_ids[r, P:P + 1] = first[0]
         th = _taps(out.hidden_states, m.target_layer_ids)[0]          # [P, fc_in]
         n_tail = min(16, P)
@@ -295,7 +309,14 @@ class BatchedDecoder:
         m, c, d, s, R = self.model, self.cfg, self.d, self.src_d, self.NT
         ops.norm_frag_batch(d["h"], R, m.w["norm"], c.rms_norm_eps, d["xn"], self.dyn_tt, ops.DYN_BS,
                             part=d["part_h"], N=c.hidden_size, K=c.intermediate_size)  # last down_proj + final norm
-        if self.TPR == 1:
+        if self.draft_temperature >= 1e-5:   # sampled draft (policy loop): slot j of the block draws start + j
+            row0, out, off = (1, self.block, 1) if self.TPR == 1 else (0, self.ids_tmp, 0)
+            ops.gemm_sample_batch(self.lm_wp, s["xn"], R, c.vocab_size, c.hidden_size, row0, 16 - row0, self.gws, out, off,
+                                  self.dyn_tt, seeds=self.seeds, temperature=self.draft_temperature, stream=ops.RNG_DRAFT,
+                                  pos_word=ops.DYN_START, pos_add=0, tiles_per_req=self.TPR, nrows_dyn_word=ops.DYN_BS)
+            if self.TPR == 2:
+                self.block[:, 1:].copy_(self.ids_tmp.view(-1, self.BW)[:, 1:])
+        elif self.TPR == 1:
             ops.gemm_argmax_batch(self.lm_wp, s["xn"], R, c.vocab_size, c.hidden_size, 1, 15, self.gws, self.block, 1,
                                   self.dyn_tt, nrows_dyn_word=ops.DYN_BS)
         else:   # row 0 of a request's SECOND tile is a draft row: all 16 rows of every tile, row 0 of the block dropped here
@@ -376,6 +397,10 @@ class BatchedDecoder:
         if self.temperature < 1e-5:
             ops.gemm_argmax_batch(self.lm_wp, s["xn"], R, t.V, H, 0, 16, self.gws, self.post.view(-1, 16), 0, dyn_t,
                                   nrows_dyn_word=ops.DYN_BS)
+        elif self.sampler == "device":   # the seeded draw in the lm_head epilogue: tile j row m -> start + 16 j + m + 1
+            ops.gemm_sample_batch(self.lm_wp, s["xn"], R, t.V, H, 0, 16, self.gws, self.post.view(-1, 16), 0, dyn_t,
+                                  seeds=self.seeds, temperature=self.temperature, pos_word=ops.DYN_POS0, pos_add=1,
+                                  tiles_per_req=TPR, nrows_dyn_word=ops.DYN_BS)
         else:
             # T > 0 (model/utils.py:30-34): the same GEMM materialises the bf16 logits and the
             # reference's own softmax + torch.multinomial draws the posterior (caller's RNG stream;
@@ -494,15 +519,37 @@ class BatchedDecoder:
         return self.accept(launch=False)
 
 
+def _prompt_seeds(sampler: str, seed, n: int, sampling: bool) -> list:
+    """One seed per prompt: an int s gives prompt i the seed s + i; a sequence gives its own; None draws them."""
+    resolve_seed(sampler, None, needed=False)
+    if sampler != "device" or not sampling:
+        if seed is not None and sampler != "device":
+            raise ValueError("seed needs sampler='device' (sampler='torch' draws on the caller's torch RNG)")
+        return [None] * n
+    if seed is None:
+        return [resolve_seed("device", None) for _ in range(n)]
+    if isinstance(seed, int):
+        return [seed + i for i in range(n)]
+    seeds = [int(x) for x in seed]
+    if len(seeds) != n:
+        raise ValueError("one seed per prompt")
+    return seeds
+
+
 @torch.inference_mode()
 def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_ids: Sequence[torch.Tensor],
                           mask_token_id: int, max_new_tokens: int, block_size: int, stop_token_ids,
                           temperature: float = 0.0, draft_token_hook: Optional[Callable] = None,
-                          group_size: int = MAX_GROUP, hook_block_view: bool = False) -> list:
+                          group_size: int = MAX_GROUP, hook_block_view: bool = False, sampler: str = "torch",
+                          seed=None) -> list:
     """`dflash_generate` (benchmark.py:44-251) for a list of prompts: requests run in
     groups of `group_size` <= 4 (<= 2 with block sizes of 17..32 rows) that share the weight stream; returns one namespace per
     prompt with the fields of benchmark.py:242-251 (timing fields are the group's).
-    draft_token_hook(request_index, block, start, call)."""
+    draft_token_hook(request_index, block, start, call).
+    sampler="device": seeded draws on the device; seed is an int s (prompt i gets s + i), one seed
+    per prompt, or None (one per prompt from torch's RNG).  Request i then emits what dflash_generate(..., seed=its seed)
+    emits, however the group is formed."""
+    seeds = _prompt_seeds(sampler, seed, len(input_ids), temperature >= 1e-5)
     if not 1 <= block_size <= 32:
         raise NotImplementedError("the batched loop takes blocks of 1..16 rows (one tile per request) or 17..32 rows (two)")
     tpr = 1 if block_size <= 16 else 2      # blocks of 17..32 rows: a request takes two of the group's four tiles
@@ -516,10 +563,11 @@ def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_i
         max_len = [p.shape[1] + max_new_tokens for p in prompts]
         dec = BatchedDecoder(model, target, len(idx), max_rows=pmax + max_new_tokens + 3 * 16 * tpr,
                              out_len=pmax + max_new_tokens + 16 * tpr, mask_token_id=mask_token_id,
-                             stop_token_ids=stop_token_ids, temperature=temperature, tiles_per_request=tpr)
+                             stop_token_ids=stop_token_ids, temperature=temperature, tiles_per_request=tpr,
+                             sampler=sampler)
         t0 = cuda_time()
         for r, p in enumerate(prompts):
-            dec.admit(r, p, temperature)
+            dec.admit(r, p, temperature, seed=seeds[idx[r]])
         ttft = cuda_time() - t0
         taus = [[] for _ in idx]
         # (hook_block_view: the hook sees the block as the single-request loop hands it over, bs slots; default: the
@@ -567,16 +615,21 @@ def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_i
 def dflash_generate_policy_batch(*, model: DFlashDraftModel, target: NativeTarget, input_ids: Sequence[torch.Tensor],
                                  mask_token_id: int, max_new_tokens: int, stop_token_ids, temperature: float,
                                  schedulers: Sequence, draft_token_hook: Optional[Callable] = None,
-                                 group_size: int = MAX_GROUP) -> list:
+                                 group_size: int = MAX_GROUP, sampler: str = "torch", seed=None) -> list:
     """`dflash_generate_policy` (benchmark_dynamic_schedule.py:260-434) for a list of prompts, the requests of a group
     sharing the weight stream: every request has its OWN scheduler (schedulers[i], e.g. an EWMAPerformanceScheduler) and
     therefore its own block size per cycle — the kernels read each request's size from its length record, so a group
     may mix 8-, 12- and 16-row blocks in one pass over the weights.  Returns one namespace per prompt with the fields of
     :425-434.  The cycle time a scheduler is fed is the GROUP's cycle wall time (what its request actually waited).
     Block sizes <= 16 (one tile per request); T = 0 (the reference samples the draft with T too, :342 — a per-request
-    RNG stream over a shared launch has no counterpart in it): both raise NotImplementedError otherwise."""
-    if temperature >= 1e-5:
-        raise NotImplementedError("the batched policy loop is greedy; run T > 0 requests through dflash_generate_policy")
+    RNG stream over a shared launch has no counterpart in it): both raise NotImplementedError otherwise — except with
+    sampler="device" (seed as in dflash_generate_batch), whose per-request seeded draws of target AND draft are what
+    dflash_generate_policy(..., sampler="device") draws for that request."""
+    if temperature >= 1e-5 and sampler != "device":
+        raise NotImplementedError("the batched policy loop samples at T > 0 with sampler='device' only; or run the requests "
+                                  "through dflash_generate_policy")
+    seeds = _prompt_seeds(sampler, seed, len(input_ids), temperature >= 1e-5)
+    T = temperature if sampler == "device" else 0.0
     n = len(input_ids)
     if len(schedulers) != n:
         raise ValueError("one scheduler per prompt")
@@ -593,11 +646,11 @@ def dflash_generate_policy_batch(*, model: DFlashDraftModel, target: NativeTarge
         max_len = [p.shape[1] + max_new_tokens for p in prompts]
         dec = BatchedDecoder(model, target, len(idx), max_rows=pmax + max_new_tokens + 3 * 16,
                              out_len=pmax + max_new_tokens + 16, mask_token_id=mask_token_id,
-                             stop_token_ids=stop_token_ids, temperature=0.0)
+                             stop_token_ids=stop_token_ids, temperature=T, sampler=sampler, draft_temperature=T)
         stop_t = dec.stop_t
         t0 = cuda_time()
         for r, p in enumerate(prompts):
-            dec.admit(r, p, 0.0)
+            dec.admit(r, p, T, seed=seeds[idx[r]])
         ttft = cuda_time() - t0
         R = len(idx)
         taus, used, traces, cyc = [[] for _ in idx], [[] for _ in idx], [[] for _ in idx], [0] * R

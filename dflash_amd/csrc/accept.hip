@@ -2,8 +2,68 @@
 // target's posterior at T=0, model/utils.py:28-29) and the acceptance scan with
 // commit, bonus token, stop test and rollback bookkeeping (model/dflash.py:258-268).
 #include "dfl_common.h"
+#include "dfl_rng.h"
 
 namespace {
+
+// Seeded draw over materialised bf16 logits, one 1024-thread block per row: argmax_v fmaf(bf16 logit, invT, g) with the
+// noise of dfl_rng.h at position pos[r] (or pos0 + r), first index on ties — the same value the EPI_SAMPLE epilogue
+// of the lm_head GEMM compares, so both give the same ids.  margin_out (optional): perturbed top-1 minus top-2.
+__global__ __launch_bounds__(1024) void k_sample_rows(const bf16_t *__restrict__ logits, int64_t ld, int V, uint64_t seed,
+                                                     float inv_t, int rng_stream, int pos0, const int32_t *pos, int extra,
+                                                     int64_t *out_ids, float *margin_out) {
+  __shared__ float sv[16], s2[16];
+  __shared__ int si[16];
+  const int r = blockIdx.x;
+  const bf16_t *row = logits + (int64_t)r * ld;
+  const uint32_t p = (uint32_t)(pos ? pos[r] : pos0 + r);
+  float best = -INFINITY, second = -INFINITY;
+  int bi = 0x7fffffff;
+  for (int c = threadIdx.x; 4 * c < V; c += 1024) {  // one Philox call per 4 columns; columns ascend within a thread
+    uint32_t w[4];
+    dfl_rng_words(seed, (uint32_t)rng_stream, p, (uint32_t)(4 * c), (uint32_t)extra, w);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int v = 4 * c + j;
+      if (v < V) {
+        const float x = dfl_perturb_w(bf2f(row[v]), inv_t, w[j]);
+        if (x > best || bi == 0x7fffffff) {
+          second = best;
+          best = x;
+          bi = v;
+        } else {
+          second = fmaxf(second, x);
+        }
+      }
+    }
+  }
+  auto merge = [&](float ov, int oi, float os) {
+    const bool have = bi != 0x7fffffff, ohave = oi != 0x7fffffff;
+    second = fmaxf(second, os);
+    if (have && ohave) second = fmaxf(second, fminf(best, ov));
+    if (ohave && (!have || ov > best || (ov == best && oi < bi))) {
+      best = ov;
+      bi = oi;
+    }
+  };
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(best, o, 64), os = __shfl_xor(second, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    merge(ov, oi, os);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    sv[threadIdx.x >> 6] = best;
+    s2[threadIdx.x >> 6] = second;
+    si[threadIdx.x >> 6] = bi;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < 16; ++w) merge(sv[w], si[w], s2[w]);
+    out_ids[r] = (int64_t)bi;
+    if (margin_out) margin_out[r] = best - second;
+  }
+}
 
 // One 256-thread block per row.  torch.argmax returns the FIRST maximal index, so
 // the reduction is on (value desc, index asc).  Values are compared as fp32 (exact
@@ -208,6 +268,20 @@ extern "C" int dfl_argmax(const void *logits, int dtype, int rows, int64_t V, in
   else
     hipLaunchKernelGGL((k_argmax<float, 4>), dim3(rows), dim3(256), 0, (hipStream_t)stream, (const float *)logits, V, ids);
   DFL_CHECK_LAUNCH("dfl_argmax");
+  return DFL_OK;
+}
+
+extern "C" int dfl_sample_rows(const void *logits, int64_t ld, int rows, int V, uint64_t seed, float inv_t, int rng_stream,
+                               int pos0, const int32_t *pos, int extra, int64_t *out_ids, float *margin_out, void *stream) {
+  DFL_REQUIRE(logits && out_ids, "dfl_sample_rows: null pointer");
+  DFL_REQUIRE(rows >= 0 && V > 0 && ld >= V, "dfl_sample_rows: bad shape rows=%d V=%d ld=%lld", rows, V, (long long)ld);
+  DFL_REQUIRE(inv_t > 0.f && inv_t <= 1e5f, "dfl_sample_rows: inv_t=%g outside (0, 1e5]", (double)inv_t);
+  DFL_REQUIRE(rng_stream == (int)DFL_RNG_TARGET || rng_stream == (int)DFL_RNG_DRAFT, "dfl_sample_rows: unknown stream %d",
+              rng_stream);
+  if (rows == 0) return DFL_OK;
+  hipLaunchKernelGGL(k_sample_rows, dim3(rows), dim3(1024), 0, (hipStream_t)stream, (const bf16_t *)logits, ld, V, seed, inv_t,
+                     rng_stream, pos0, pos, extra, out_ids, margin_out);
+  DFL_CHECK_LAUNCH("dfl_sample_rows");
   return DFL_OK;
 }
 

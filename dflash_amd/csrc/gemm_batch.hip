@@ -799,6 +799,52 @@ extern "C" int dfl_gemm_argmax_batch(const void *wp, const dfl_rows_batch *x, in
   return DFL_OK;
 }
 
+// The seeded draw of dfl_gemm_sample for R <= 4 request tiles in one pass over the weights: the ring form with the
+// EPI_SAMPLE epilogue (gemm_ring.h).  No slab form: where the ring form does not apply this is an error, not a quiet
+// fall-back.
+extern "C" int dfl_gemm_sample_batch(const void *wp, const dfl_rows_batch *x, int R, int V, int K, int row0, int nrows,
+                                     const int32_t *dyn, int nrows_dyn_word, void *ws, int64_t *out_ids,
+                                     int64_t out_stride, int out_off, void *logits, int64_t logits_stride,
+                                     const int64_t *seeds, float inv_t, int rng_stream, int pos_word, int pos_add,
+                                     int tiles_per_req, void *stream) {
+  DFL_REQUIRE(wp && x && ws && out_ids && dyn && seeds, "dfl_gemm_sample_batch: null pointer");
+  DFL_REQUIRE(row0 >= 0 && nrows >= 0 && row0 + nrows <= 16, "dfl_gemm_sample_batch: rows [%d,%d) outside the tile", row0,
+              row0 + nrows);
+  DFL_REQUIRE(inv_t > 0.f && inv_t <= 1e5f, "dfl_gemm_sample_batch: inv_t=%g outside (0, 1e5]", (double)inv_t);
+  DFL_REQUIRE(rng_stream == (int)DFL_RNG_TARGET || rng_stream == (int)DFL_RNG_DRAFT,
+              "dfl_gemm_sample_batch: unknown stream %d", rng_stream);
+  DFL_REQUIRE(pos_word >= 0 && pos_word < DFL_DYN_WORDS && (tiles_per_req == 1 || tiles_per_req == 2) && R % tiles_per_req == 0,
+              "dfl_gemm_sample_batch: pos_word=%d / tiles_per_req=%d / R=%d", pos_word, tiles_per_req, R);
+  DFL_REQUIRE(use_ring() && ring_ok(x, K) && R >= 1 && R <= 4 && V > 0 && V % 16 == 0 && x->frag_stride % 8 == 0,
+              "dfl_gemm_sample_batch: needs the ring form (R <= 4 fragment sources, V %% 16 == 0, DFL_BATCH_GEMM not 'slab')");
+  GemmRArgs r{};
+  fill_ring(r, wp, x, V, K, dyn);
+  r.row0 = row0;
+  r.nrows = nrows;
+  r.nrows_word = nrows_dyn_word;
+  r.best_val = (float *)((char *)ws + WS_TICKETS);
+  r.best_idx = (int *)((char *)ws + WS_TICKETS + WS_CAND * sizeof(float));
+  r.logits = (bf16_t *)logits;
+  r.logits_stride = logits_stride;
+  r.N = V;
+  r.seeds = seeds;
+  r.inv_t = inv_t;
+  r.rng_stream = rng_stream;
+  r.pos_word = pos_word;
+  r.pos_add = pos_add;
+  r.tiles_per_req = tiles_per_req;
+  int gx = 0;
+  ring_plan(r, V / 16, 16, gx);
+  if (R <= 2)
+    launch_ring<2, 1, 1, 16, 2, EPI_SAMPLE>(r, gx, (hipStream_t)stream);
+  else
+    launch_ring<4, 1, 1, 16, 2, EPI_SAMPLE>(r, gx, (hipStream_t)stream);
+  hipLaunchKernelGGL(k_argmax_finish_b, dim3(16, R), dim3(64), 0, (hipStream_t)stream, r.best_val, r.best_idx, gx, mt_of(R),
+                     row0, nrows, dyn, nrows_dyn_word, out_ids, out_stride, out_off);
+  DFL_CHECK_LAUNCH("dfl_gemm_sample_batch");
+  return DFL_OK;
+}
+
 extern "C" int dfl_embed_rows_batch(const void *embed, const int64_t *ids, int64_t ids_stride, int R, void *h_out,
                                     int64_t h_stride, int H, float *ss_out, int64_t ss_stride, const int32_t *dyn,
                                     int dyn_word, void *stream) {

@@ -26,6 +26,7 @@
 // asm with their own lgkmcnt wait.
 #pragma once
 #include "gemm_rows.h"
+#include "dfl_rng.h"
 
 // (External linkage for the argument struct and the kernel template: hipFuncSetAttribute — more than 64 KB of dynamic
 // LDS — needs the kernel's address, and the host-side handle of a kernel with internal linkage is not emitted.)
@@ -61,6 +62,12 @@ struct GemmRArgs {
   int64_t ldtap, tap_stride;
   float *ss_out;  // optional [ntiles][16] per request: sum over the tile's 16 columns of the new rows' squares (next RMSNorm)
   int64_t ss_stride;
+  // EPI_SAMPLE (with the EPI_ARGMAX fields): tile mt is tile j = mt % tiles_per_req of request q = mt / tiles_per_req; its
+  // row m draws position base + pos_add + 16 j + m with base = dyn[mt][pos_word] and the seed seeds[q] (dfl_rng.h);
+  // the DRAFT stream takes extra = base (the block start), the TARGET stream extra = 0
+  const int64_t *seeds;
+  float inv_t;
+  int rng_stream, pos_word, pos_add, tiles_per_req;
 };
 
 namespace {
@@ -105,7 +112,7 @@ __global__ __launch_bounds__(NW * 64) void dfl_k_gemm_r(GemmRArgs a) {
     best[mt] = -INFINITY;
     bestn[mt] = 0x7fffffff;
     arg_rows[mt] = 0;
-    if (EPI == EPI_ARGMAX) {
+    if (EPI == EPI_ARGMAX || EPI == EPI_SAMPLE) {
       arg_rows[mt] = a.nrows;
       if (a.dyn && a.nrows_word >= 0) arg_rows[mt] = a.dyn[mt * DFL_DYN_WORDS + a.nrows_word] - a.row0;
     }
@@ -259,15 +266,23 @@ __global__ __launch_bounds__(NW * 64) void dfl_k_gemm_r(GemmRArgs a) {
           o[r] = f2bf(act * ub);
         }
         *reinterpret_cast<bf16x4 *>(a.act + mt * a.act_stride + ((size_t)(n0 >> 3) * 16 + fm) * 8 + (n0 & 7)) = o;
-      } else if (EPI == EPI_ARGMAX) {
+      } else if (EPI == EPI_ARGMAX || EPI == EPI_SAMPLE) {
         const bool live = (fm >= a.row0) && (fm < a.row0 + arg_rows[mt]);
         if (a.logits && live) {
           bf16x4 o = {f2bf(s[0]), f2bf(s[1]), f2bf(s[2]), f2bf(s[3])};
           *reinterpret_cast<bf16x4 *>(a.logits + mt * a.logits_stride + (size_t)fm * a.N + n0) = o;
         }
+        uint32_t wd[4] = {0u, 0u, 0u, 0u};
+        if (EPI == EPI_SAMPLE) {  // the thread's 4 columns are one column group: ONE Philox call covers them
+          const int q = mt / a.tiles_per_req, j = mt - q * a.tiles_per_req;
+          const int base = a.dyn[mt * DFL_DYN_WORDS + a.pos_word];
+          dfl_rng_words((uint64_t)a.seeds[q], (uint32_t)a.rng_stream, (uint32_t)(base + a.pos_add + 16 * j + fm),
+                        (uint32_t)n0, a.rng_stream == (int)DFL_RNG_DRAFT ? (uint32_t)base : 0u, wd);
+        }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const float vb = rbf(s[r]);  // lm_head output is bf16 before argmax (model/dflash.py:238,247); first maximum kept
+          float vb = rbf(s[r]);  // lm_head output is bf16 before argmax (model/dflash.py:238,247); first maximum kept
+          if (EPI == EPI_SAMPLE) vb = dfl_perturb_w(vb, a.inv_t, wd[r]);  // Gumbel-max (dfl_rng.h)
           if (live && (vb > best[mt] || (vb == best[mt] && n0 + r < bestn[mt]) || bestn[mt] == 0x7fffffff)) {
             best[mt] = vb;
             bestn[mt] = n0 + r;
@@ -348,7 +363,7 @@ __global__ __launch_bounds__(NW * 64) void dfl_k_gemm_r(GemmRArgs a) {
     }
   }
 
-  if (EPI == EPI_ARGMAX) {
+  if (EPI == EPI_ARGMAX || EPI == EPI_SAMPLE) {
     // the waves' candidates per (request, row) meet in LDS: ONE entry per workgroup goes out (the finish kernel scans
     // gridDim.x entries per row, not gridDim.x * NW: 30 us -> 5 us at 256 x 16)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (padding pieces past the last chunk still target the ring)

@@ -22,6 +22,7 @@
 // MFMA utilisation is a few percent by construction; the roofline is HBM: every launch
 // costs ~3.6 us + bytes / 6.5 TB/s (scripts/bench_gemm.py).
 #include "gemm_rows.h"
+#include "dfl_rng.h"
 
 namespace {
 
@@ -65,6 +66,17 @@ struct GemmArgs {
   float *ss_out;  // [ntiles][16] sum over the tile's 16 columns of h_new^2
 };
 
+// EPI_SAMPLE (which reads the EPI_ARGMAX fields of GemmArgs as well): row m draws position base + pos_add + m, base =
+// pos_dyn[pos_word] or pos_base; the DRAFT stream takes extra = base (the block start), the TARGET stream extra = 0.
+// A kernel argument of its own (k_gemm_s): GemmArgs, and with it the code of every other instantiation, is unchanged.
+struct SampleArgs {
+  uint64_t seed;
+  float inv_t;
+  int rng_stream;
+  const int32_t *pos_dyn;
+  int pos_word, pos_base, pos_add;
+};
+
 #ifdef DFL_GEMM_STAMPS  // diagnostic build only (scripts/dbg_gemm_stamps.py): 100 MHz wall stamps of workgroup 0,
 // and the start / first-item / end stamps of EVERY workgroup (is the tail a few late workgroups or all of them?)
 __device__ unsigned long long g_gstamps[8];
@@ -104,7 +116,7 @@ constexpr int gemm_fr(int MT, bool CHUNKED) { return CHUNKED ? 4 : (MT == 1 ? 8 
 // of its own rows (v_dot2c) instead of loading the producer's partials; waiting for the rows before the first weight
 // request; an 8-wave, three-buffer form of the K-chunked kernel.
 template <int MT, bool CHUNKED, int EPI, bool NORM>
-__device__ __forceinline__ void gemm_body(const GemmArgs &a) {
+__device__ __forceinline__ void gemm_body(const GemmArgs &a, const SampleArgs &sa) {
   GSTAMP(0);
   constexpr int FR = gemm_fr(MT, CHUNKED);
   // red[buf][wave][mt][256]: lane l owns floats 4l..4l+3 (its MFMA D regs)
@@ -170,6 +182,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &a) {
   float second = -INFINITY;  // runner-up VALUE as torch.topk(2) defines it: a tie with the best counts
   float gate_sum = 0.f;    // SILU: the pair's gate sum, kept across one position
   int arg_rows = 0;
+  int pos_row0 = 0, rng_extra = 0;  // EPI_SAMPLE: position drawn by tile row 0, counter word `extra`
 
   // chunked kernels: item (tile t, chunk c) = the wave's weights of that chunk AND its activation fragments.  Only the
   // REQUESTS are made here; the mask (rows beyond the valid count, k-steps beyond K) is applied in process(), right in
@@ -229,11 +242,17 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &a) {
           const int n = (t >> 1) * 16 + nl;
           a.act[((size_t)(n >> 3) * 16 + m) * 8 + (n & 7)] = f2bf(act * ub);
         }
-      } else if (EPI == EPI_ARGMAX) {
+      } else if (EPI == EPI_ARGMAX || EPI == EPI_SAMPLE) {
         const int n = t * 16 + nl;
-        const float vb = rbf(s);  // lm_head output is bf16 before argmax (model/dflash.py:238,247)
+        float vb = rbf(s);  // lm_head output is bf16 before argmax (model/dflash.py:238,247)
         const bool live = (m >= a.row0) && (m < a.row0 + arg_rows) && colok;
         if (a.logits && live) a.logits[(size_t)m * a.N + n] = f2bf(s);
+        if (EPI == EPI_SAMPLE) {  // Gumbel-max: the same running argmax over bf16(logit) * invT + g(seed, p, n)
+          uint32_t wd[4];
+          dfl_rng_words(sa.seed, (uint32_t)sa.rng_stream, (uint32_t)(pos_row0 + m), (uint32_t)n, (uint32_t)rng_extra, wd);
+          const int k = nl & 3;
+          vb = dfl_perturb_w(vb, sa.inv_t, k == 0 ? wd[0] : (k == 1 ? wd[1] : (k == 2 ? wd[2] : wd[3])));
+        }
         // n grows along the sequence for a fixed thread: strict '>' keeps the first maximum
         if (live && (vb > best || bestn == 0x7fffffff)) {
           second = best;
@@ -297,9 +316,14 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &a) {
   // with the vector loads — but through the same L2: requested behind the first weight burst they came back 5 - 9 us
   // later (the "rstd prologue" of round 2 was mostly this wait).  Asked for before any vector load they cost nothing.
   read_nv();
-  if (EPI == EPI_ARGMAX) {
+  if (EPI == EPI_ARGMAX || EPI == EPI_SAMPLE) {
     arg_rows = a.nrows;
     if (a.dyn && a.nrows_word >= 0) arg_rows = a.dyn[a.nrows_word] - a.row0;
+  }
+  if (EPI == EPI_SAMPLE) {
+    const int base = sa.pos_dyn ? sa.pos_dyn[sa.pos_word] : sa.pos_base;
+    pos_row0 = base + sa.pos_add;
+    rng_extra = sa.rng_stream == (int)DFL_RNG_DRAFT ? base : 0;
   }
   __builtin_amdgcn_sched_barrier(0);
   float rstd[MT];
@@ -443,7 +467,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &a) {
   }
 
   GSTAMP(5);
-  if (EPI == EPI_ARGMAX) {
+  if (EPI == EPI_ARGMAX || EPI == EPI_SAMPLE) {
     // the 16 threads of row m are consecutive lanes: shuffle down to lane nl == 0
     if (tid < 256) {
 #pragma unroll
@@ -468,7 +492,12 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &a) {
 
 template <int MT, bool CHUNKED, int EPI, bool NORM>
 __global__ __launch_bounds__(1024) void k_gemm(GemmArgs a) {
-  gemm_body<MT, CHUNKED, EPI, NORM>(a);
+  gemm_body<MT, CHUNKED, EPI, NORM>(a, SampleArgs{});
+}
+
+template <bool NORM>
+__global__ __launch_bounds__(1024) void k_gemm_s(GemmArgs a, SampleArgs sa) {
+  gemm_body<1, false, EPI_SAMPLE, NORM>(a, sa);
 }
 
 // the instantiation for this launch's row sources (a normalised source needs the NORM kernels)
@@ -721,7 +750,7 @@ extern "C" int64_t dfl_argmax_ws_bytes(void) { return 256 * 16 * (int64_t)(2 * s
 namespace {
 int gemm_argmax_impl(const void *wp, const dfl_rows *x, int V, int K, int row0, int nrows, const int32_t *dyn,
                      int nrows_dyn_word, void *ws, int64_t *out_ids, int out_off, void *logits, float *margin_out,
-                     hipEvent_t ev0, hipEvent_t ev1, void *stream) {
+                     hipEvent_t ev0, hipEvent_t ev1, void *stream, const SampleArgs *smp = nullptr) {
   DFL_REQUIRE(wp && ws && out_ids, "dfl_gemm_argmax: null pointer");
   DFL_REQUIRE(V > 0 && K > 0 && V % 16 == 0 && K % 32 == 0, "dfl_gemm_argmax: need V%%16==0, K%%32==0 (V=%d K=%d)", V, K);
   DFL_REQUIRE(row0 >= 0 && nrows >= 0 && row0 + nrows <= 16, "dfl_gemm_argmax: rows [%d,%d) outside the 16-row tile", row0,
@@ -747,7 +776,14 @@ int gemm_argmax_impl(const void *wp, const dfl_rows *x, int V, int K, int row0, 
   int gx = 0;
   plan_tiles(a, V / 16, true, gx);
   if (ev0) (void)hipEventRecord(ev0, (hipStream_t)stream);
-  launch_gemm<1, false, EPI_ARGMAX>(a, dim3(gx, 1), (hipStream_t)stream);
+  if (smp) {
+    if (a.src[0].mode == 2)
+      hipLaunchKernelGGL(k_gemm_s<true>, dim3(gx, 1), dim3(1024), 0, (hipStream_t)stream, a, *smp);
+    else
+      hipLaunchKernelGGL(k_gemm_s<false>, dim3(gx, 1), dim3(1024), 0, (hipStream_t)stream, a, *smp);
+  } else {
+    launch_gemm<1, false, EPI_ARGMAX>(a, dim3(gx, 1), (hipStream_t)stream);
+  }
   if (ev1) (void)hipEventRecord(ev1, (hipStream_t)stream);
   hipLaunchKernelGGL(k_argmax_finish, dim3(16), dim3(64), 0, (hipStream_t)stream, a.best_val, a.best_idx, a.best2_val, gx,
                      row0, nrows, dyn, nrows_dyn_word, out_ids, out_off, margin_out);
@@ -768,6 +804,21 @@ extern "C" int dfl_gemm_argmax_timed(const void *wp, const dfl_rows *x, int V, i
                                      void *logits, float *margin_out, void *ev_start, void *ev_end, void *stream) {
   return gemm_argmax_impl(wp, x, V, K, row0, nrows, dyn, nrows_dyn_word, ws, out_ids, out_off, logits, margin_out,
                           (hipEvent_t)ev_start, (hipEvent_t)ev_end, stream);
+}
+
+extern "C" int dfl_gemm_sample(const void *wp, const dfl_rows *x, int V, int K, int row0, int nrows, const int32_t *dyn,
+                               int nrows_dyn_word, void *ws, int64_t *out_ids, int out_off, void *logits, float *margin_out,
+                               uint64_t seed, float inv_t, int rng_stream, const int32_t *pos_dyn, int pos_word,
+                               int pos_base, int pos_add, void *stream) {
+  DFL_REQUIRE(wp && ws && out_ids, "dfl_gemm_sample: null pointer");
+  DFL_REQUIRE(inv_t > 0.f && inv_t <= 1e5f, "dfl_gemm_sample: inv_t=%g outside (0, 1e5]", (double)inv_t);
+  DFL_REQUIRE(rng_stream == (int)DFL_RNG_TARGET || rng_stream == (int)DFL_RNG_DRAFT, "dfl_gemm_sample: unknown stream %d",
+              rng_stream);
+  DFL_REQUIRE(!pos_dyn || (pos_word >= 0 && pos_word < DFL_DYN_WORDS), "dfl_gemm_sample: pos_word=%d outside the record",
+              pos_word);
+  const SampleArgs smp{seed, inv_t, rng_stream, pos_dyn, pos_word, pos_base, pos_add};
+  return gemm_argmax_impl(wp, x, V, K, row0, nrows, dyn, nrows_dyn_word, ws, out_ids, out_off, logits, margin_out, nullptr,
+                          nullptr, stream, &smp);
 }
 
 

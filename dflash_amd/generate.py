@@ -80,6 +80,32 @@ def _bf16_table(w, dev):
     return _TABLES[key]
 
 
+SAMPLERS = ("torch", "device")
+
+
+def resolve_seed(sampler: str, seed: Optional[int], needed: bool = True) -> Optional[int]:
+    """sampler="device" without a seed draws one from torch's default generator, so that torch.manual_seed still
+    governs reproducibility — only when a draw needs it (`needed`: T > 0), so a greedy run leaves the caller's RNG alone;
+    sampler="torch" takes no seed (it draws on the caller's torch RNG)."""
+    if sampler not in SAMPLERS:
+        raise ValueError(f"sampler={sampler!r}: one of {SAMPLERS}")
+    if sampler == "torch":
+        if seed is not None:
+            raise ValueError("seed needs sampler='device' (sampler='torch' draws on the caller's torch RNG)")
+        return None
+    if not needed:
+        return None if seed is None else int(seed) & 0xFFFFFFFFFFFFFFFF
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    return int(seed) & 0xFFFFFFFFFFFFFFFF
+
+
+def _draw_rows(logits: torch.Tensor, temperature: float, seed: int, pos0: int) -> torch.Tensor:
+    """The device sampler over materialised logits [1, T, V]: row j draws position pos0 + j (stream TARGET)."""
+    _, t, v = logits.shape
+    return ops.sample_rows(logits.reshape(t, v), seed=seed, temperature=temperature, pos0=pos0).view(1, t)
+
+
 def _trim(output_ids, max_length, mask_token_id, stop_token_ids, n_in):
     """model/dflash.py:269-275."""
     output_ids = output_ids[:, :max_length]
@@ -98,7 +124,7 @@ class DecodeSession:
 
     def __init__(self, model, target, input_ids: torch.Tensor, *, mask_token_id: int, max_new_tokens: int,
                  max_block_size: int, stop_token_ids, temperature: float, draft_temperature: float = 0.0,
-                 draft_token_hook: Optional[Callable] = None):
+                 draft_token_hook: Optional[Callable] = None, sampler: str = "torch", seed: Optional[int] = None):
         dev = model.device
         if not input_ids.is_cuda:
             raise RuntimeError("dflash_amd: input_ids must be on the GPU")
@@ -111,6 +137,14 @@ class DecodeSession:
         self.input_ids = input_ids
         self.mask_token_id, self.temperature = mask_token_id, temperature
         self.draft_temperature, self.hook = draft_temperature, draft_token_hook
+        # sampler="device": T > 0 draws are seeded Gumbel-max draws on the device — the target's in
+        # its lm_head epilogue (stream TARGET), the draft's likewise (stream DRAFT); None where a draw is greedy
+        self.sampler = sampler
+        self.seed = resolve_seed(sampler, seed, needed=temperature >= 1e-5 or draft_temperature >= 1e-5)
+        self._tseed = self.seed if (self.seed is not None and temperature >= 1e-5) else None
+        self._dseed = self.seed if (self.seed is not None and draft_temperature >= 1e-5) else None
+        # T > 0 cycles can be replayed only with the device sampler (the torch draw consumes host RNG state)
+        self.replay_sampling_ok = sampler == "device" or (temperature < 1e-5 and draft_temperature < 1e-5)
         self.stop_token_ids = stop_token_ids
         self.max_bs = max_block_size
         self.n_in = input_ids.shape[1]
@@ -171,7 +205,11 @@ class DecodeSession:
                               past_key_values=self.tcache, use_cache=True, logits_to_keep=1,
                               output_hidden_states=self.use_draft)
         self.output_ids[:, :self.n_in] = self.input_ids
-        self.output_ids[:, self.n_in:self.n_in + 1] = sample(out.logits, self.temperature)
+        if self._tseed is not None:   # the first new token draws position n_in
+            self.output_ids[:, self.n_in:self.n_in + 1] = _draw_rows(out.logits[:, -1:], self.temperature, self._tseed,
+                                                                     self.n_in)
+        else:
+            self.output_ids[:, self.n_in:self.n_in + 1] = sample(out.logits, self.temperature)
         if self.use_draft:
             self.target_hidden = _taps(out.hidden_states, self.model.target_layer_ids)
 
@@ -231,7 +269,8 @@ class DecodeSession:
                                 embed=self.embed_w, dyn_ready=ready)
             self._dyn_bs = None   # until the accept of this cycle has re-armed the record
             self._mark("lm_head", 0)
-            _draft_ids(m, hid, self.lm_wp, bs, blk, self.draft_temperature, self.draft_logits)
+            _draft_ids(m, hid, self.lm_wp, bs, blk, self.draft_temperature, self.draft_logits, seed=self._dseed,
+                       dyn=self.dcache.dyn, start=self.start)
             self._mark("lm_head", 1)
             if self.hook is not None:
                 self.hook(blk, self.start, self.hook_calls)
@@ -282,13 +321,16 @@ class DecodeSession:
             posterior, taps = self.target.verify(
                 blk[0], start, self.tcache, temperature=self.temperature,
                 tap_layers=self.model.target_layer_ids if (want_hidden and self.use_draft) else (),
-                taps_out=self.taps_buf)
+                taps_out=self.taps_buf, seed=self._tseed)
             self._mark("target", 1)
         else:
             out = self.target(blk, position_ids=self.position_ids[:, start:start + bs],
                               past_key_values=self.tcache, use_cache=True, output_hidden_states=want_hidden)
             self._mark("target", 1)
-            posterior = sample(out.logits, self.temperature)
+            if self._tseed is not None:   # verify row j predicts position start + j + 1
+                posterior = _draw_rows(out.logits, self.temperature, self._tseed, start + 1)
+            else:
+                posterior = sample(out.logits, self.temperature)
         # ---- accept scan + commit + bookkeeping on the device (:258-268)
         if not (bs > 1 and draft_steps == 1):
             # (after a cached draft forward the record already holds start = pos0 + tau: either draft_block's
@@ -305,10 +347,11 @@ class DecodeSession:
         # the record now holds the next draft forward's S / tau / pos0 / start — if that cycle was a cached draft cycle
         # on this record (bs > 1, one draft step) and keeps the block size
         self._dyn_bs = bs if (bs > 1 and draft_steps == 1 and self.use_draft) else None
-        # run-ahead: the next cycle's draft goes out now if it is certain to be a draft cycle of the same block size —
-        # no tail clamp even if every token of this block is accepted, no stop tokens to end the request early, a
-        # caller-driven block size (a scheduler picks the next size only after this cycle's result: `ahead_ok`)
-        if (ahead_ok and self.run_ahead and self._dyn_bs == bs and self.native and want_hidden and self.stop_t is None
+        # run-ahead: the next cycle's draft goes out now if it is likely to be a draft cycle of the same block size —
+        # no tail clamp even if every token of this block is accepted, no caller-driven block size (a scheduler picks the
+        # next size only after this cycle's result: `ahead_ok`).  A stop token committed by this cycle ends the request:
+        # its run-ahead draft is simply abandoned (it wrote scratch buffers and draft cache rows nobody reads again)
+        if (ahead_ok and self.run_ahead and self._dyn_bs == bs and self.native and want_hidden
                 and getattr(self.model, "attn_impl", "head") == "head"   # (the round-1 stage takes no device-driven lengths)
                 and not self.stop_always and self.draft_temperature < 1e-5 and bs <= 16
                 and start + 2 * bs <= self.max_length and start + self.max_bs + 16 + bs <= self.dcache.max_rows):
@@ -333,14 +376,15 @@ class DecodeSession:
             self.target_hidden = (taps[None, :tau] if self.native
                                   else _taps(out.hidden_states, self.model.target_layer_ids)[:, :tau, :])
         self.stopped = bool(self.stop_always or res[2])
-        return SimpleNamespace(tau=tau, bs=bs, start=start, stop=self.stopped)
+        return SimpleNamespace(tau=tau, bs=bs, start=start, stop=self.stopped, replayed=False)
 
     # ------------------------------------------------------------------ hipGraph replay of the steady-state cycle
     def _graph_ok(self, bs: int) -> bool:
-        """A cycle that can be replayed: fixed block size, T = 0, no stop ids, no tail clamp even if every token of this
-        block and the next is accepted, and the previous cycle left this cycle's draft enqueued (run-ahead)."""
+        """A cycle that can be replayed: fixed block size, T = 0 or the device sampler, stop ids unless the mask id is
+        one of them, no tail clamp even if every token of this block and the next is accepted, and the previous cycle
+        left this cycle's draft enqueued (run-ahead)."""
         if not (self.native and self.use_draft and bs == getattr(self, "_graph_bs", None) and self._ahead == bs
-                and self.stop_t is None and not self.stop_always and self.temperature < 1e-5
+                and not self.stop_always and self.replay_sampling_ok
                 and (self.events is None or not self.record_events)   # (a dict that only receives a run-ahead draft's pairs is fine)
                 and self.start + 2 * bs <= self.max_length and self.start + bs <= self._graph_bound):
             return False
@@ -365,9 +409,10 @@ class DecodeSession:
         record), so one capture serves every cycle; the attention launches size their key splits for the caches'
         capacity.  Call after at least one cycle(bs, ahead_ok=True).  The host then spends two graph launches and one poll
         per cycle instead of ~215 ctypes calls (VERDICT r2 next #9)."""
-        if not (self.native and self.use_draft and 2 <= bs <= 16 and self.temperature < 1e-5 and self.stop_t is None
+        if not (self.native and self.use_draft and 2 <= bs <= 16 and self.replay_sampling_ok and not self.stop_always
                 and self.draft_temperature < 1e-5 and self.target.attn_impl == "head" and not self.target.fuse_oproj):
-            raise ValueError("capture needs a NativeTarget ('head' attention), a draft, T = 0, no stop ids, 2 <= bs <= 16")
+            raise ValueError("capture needs a NativeTarget ('head' attention), a draft, T = 0 or sampler='device', a greedy "
+                             "draft, no mask id among the stop ids, 2 <= bs <= 16")
         if self._ahead != bs:
             raise RuntimeError("capture: run one cycle(bs, ahead_ok=True) first (the next draft must be in flight)")
         m, t = self.model, self.target
@@ -385,11 +430,11 @@ class DecodeSession:
         torch.cuda.synchronize(self.dev)
         tl = self.model.target_layer_ids
 
-        def verify_accept():
-            post, _ = t.verify(self.block[0, :bs], bound, self.tcache, temperature=0.0, tap_layers=tl,
-                               taps_out=self.taps_buf, dyn_lengths=True)
-            ops.accept_commit(self.block[0, :bs], post[0].contiguous(), bs, self.output_ids[0], self.dyn, None, self.result,
-                              rearm=(self.block[0], self.max_bs, self.mask_token_id), dyn_t=self.tcache.dyn)
+        def verify_accept():   # (a T > 0 draw takes its positions from the target record's POS0 word: fresh every replay)
+            post, _ = t.verify(self.block[0, :bs], bound, self.tcache, temperature=self.temperature, tap_layers=tl,
+                               taps_out=self.taps_buf, dyn_lengths=True, seed=self._tseed)
+            ops.accept_commit(self.block[0, :bs], post[0].contiguous(), bs, self.output_ids[0], self.dyn, self.stop_t,
+                              self.result, rearm=(self.block[0], self.max_bs, self.mask_token_id), dyn_t=self.tcache.dyn)
 
         def draft_next():
             hid = m.draft_block(self.dcache, th_rows=self.taps_buf[:16], tau=16, bs=bs, pos0=bound, block_ids=self.block[0],
@@ -448,7 +493,7 @@ class DecodeSession:
         self.tcache.crop(self.start)
         self.target_hidden = self.taps_buf[None, :tau]
         self.stopped = bool(res[2])
-        return SimpleNamespace(tau=tau, bs=bs, start=start, stop=self.stopped)
+        return SimpleNamespace(tau=tau, bs=bs, start=start, stop=self.stopped, replayed=True)
 
     # ------------------------------------------------------------------ hipGraph replay with a caller-chosen block size
     @torch.inference_mode()
@@ -459,10 +504,11 @@ class DecodeSession:
         own bookkeeping (two 64-thread launches) and replays the pair; there is no run-ahead draft, since the next block's
         size is only known once the scheduler has seen this cycle's result.  Call after at least one draft cycle."""
         sizes = sorted({int(b) for b in sizes})
-        if not (self.native and self.use_draft and sizes and 2 <= sizes[0] and sizes[-1] <= 16 and self.temperature < 1e-5
-                and self.stop_t is None and self.draft_temperature < 1e-5 and self.target.attn_impl == "head"
+        if not (self.native and self.use_draft and sizes and 2 <= sizes[0] and sizes[-1] <= 16 and self.replay_sampling_ok
+                and not self.stop_always and self.target.attn_impl == "head"
                 and not self.target.fuse_oproj and getattr(self.model, "attn_impl", "head") == "head"):
-            raise ValueError("capture_sizes needs a NativeTarget ('head' attention), a draft, T = 0, no stop ids, sizes in 2..16")
+            raise ValueError("capture_sizes needs a NativeTarget ('head' attention), a draft, T = 0 or sampler='device', no "
+                             "mask id among the stop ids, sizes in 2..16")
         if not self._armed:
             raise RuntimeError("capture_sizes: run one cycle first")
         m, t = self.model, self.target
@@ -475,16 +521,17 @@ class DecodeSession:
         tl = self.model.target_layer_ids
         graphs = {}
         for bs in sizes:
-            def draft_now(bs=bs):
+            def draft_now(bs=bs):   # (a sampled draft takes the block start from the draft record's START word)
                 hid = m.draft_block(self.dcache, th_rows=self.taps_buf[:16], tau=16, bs=bs, pos0=bound, block_ids=self.block[0],
                                     embed=self.embed_w, dyn_ready=True, s_bound=bound)
-                _draft_ids(m, hid, self.lm_wp, bs, self.block[:, :bs], 0.0, self.draft_logits)
+                _draft_ids(m, hid, self.lm_wp, bs, self.block[:, :bs], self.draft_temperature, self.draft_logits,
+                           seed=self._dseed, dyn=self.dcache.dyn)
 
             def verify_accept(bs=bs):
-                post, _ = t.verify(self.block[0, :bs], bound, self.tcache, temperature=0.0, tap_layers=tl,
-                                   taps_out=self.taps_buf, dyn_lengths=True)
-                ops.accept_commit(self.block[0, :bs], post[0].contiguous(), bs, self.output_ids[0], self.dyn, None, self.result,
-                                  rearm=(self.block[0], self.max_bs, self.mask_token_id), dyn_t=self.tcache.dyn)
+                post, _ = t.verify(self.block[0, :bs], bound, self.tcache, temperature=self.temperature, tap_layers=tl,
+                                   taps_out=self.taps_buf, dyn_lengths=True, seed=self._tseed)
+                ops.accept_commit(self.block[0, :bs], post[0].contiguous(), bs, self.output_ids[0], self.dyn, self.stop_t,
+                                  self.result, rearm=(self.block[0], self.max_bs, self.mask_token_id), dyn_t=self.tcache.dyn)
 
             graphs[bs] = (capture_graph(draft_now), capture_graph(verify_accept))
         self.tcache.crop(self.start)     # (verify's host-side bookkeeping ran with the bound)
@@ -495,7 +542,7 @@ class DecodeSession:
 
     def _sized_ok(self, bs: int) -> bool:
         g = getattr(self, "_sgraphs", None)
-        if not (g and bs in g and self._armed and self.stop_t is None and not self.stop_always
+        if not (g and bs in g and self._armed and not self.stop_always
                 and (self.events is None or not self.record_events) and self.target_hidden is not None
                 and self.target_hidden.shape[1] <= 16 and self.start + bs <= min(self.max_length, self._sgraph_bound)):
             return False
@@ -554,7 +601,7 @@ class DecodeSession:
         self.tcache.crop(self.start)
         self.target_hidden = self.taps_buf[None, :tau]
         self.stopped = bool(res[2])
-        return SimpleNamespace(tau=tau, bs=bs, start=start, stop=self.stopped)
+        return SimpleNamespace(tau=tau, bs=bs, start=start, stop=self.stopped, replayed=True)
 
     def finish(self) -> torch.Tensor:
         return _trim(self.output_ids, self.max_length, self.mask_token_id, self.stop_token_ids, self.n_in)
@@ -565,11 +612,11 @@ def run_decode(model, target, input_ids: torch.Tensor, *, mask_token_id: int, ma
                block_size: int, stop_token_ids, temperature: float, clamp_tail: bool,
                draft_steps: int = 1, collect_profile: bool = False, scheduler=None,
                draft_temperature: float = 0.0, draft_token_hook: Optional[Callable] = None,
-               max_block_size: Optional[int] = None) -> SimpleNamespace:
+               max_block_size: Optional[int] = None, sampler: str = "torch", seed: Optional[int] = None) -> SimpleNamespace:
     s = DecodeSession(model, target, input_ids, mask_token_id=mask_token_id, max_new_tokens=max_new_tokens,
                       max_block_size=max_block_size or block_size, stop_token_ids=stop_token_ids,
                       temperature=temperature, draft_temperature=draft_temperature,
-                      draft_token_hook=draft_token_hook)
+                      draft_token_hook=draft_token_hook, sampler=sampler, seed=seed)
     t_prefill = cuda_time()
     s.prefill()
     time_to_first_token = cuda_time() - t_prefill
@@ -579,7 +626,8 @@ def run_decode(model, target, input_ids: torch.Tensor, *, mask_token_id: int, ma
     draft_prefill = True
     use_graphs = os.environ.get("DFL_GRAPH", "1") != "0" and s.native and getattr(target, "attn_impl", "") == "head" \
         and not getattr(target, "fuse_oproj", False)
-    cyc = 0
+    cyc = replayed = 0
+    replayed_flags = []
     while s.start < s.max_length:
         cycle_t0 = cuda_time() if scheduler is not None else None
         if collect_profile:
@@ -610,10 +658,11 @@ def run_decode(model, target, input_ids: torch.Tensor, *, mask_token_id: int, ma
         gen_before = s.start - s.n_in
         start_idx = s.start
         # fixed-size loops replay their steady-state cycles from two hipGraphs (DecodeSession.capture): the host's share
-        # of a cycle drops from ~2.3 ms to ~0.2 ms at the same GPU time; DFL_GRAPH=0: eager launches
+        # of a cycle drops from ~2.3 ms to ~0.2 ms at the same GPU time; DFL_GRAPH=0: eager launches.
+        # Stop ids ride along in the captured accept launch; T > 0 needs the device sampler
         if (use_graphs and scheduler is None and draft_steps == 1 and not collect_profile and bs == block_size
-                and 2 <= bs <= 16 and want_hidden and not draft_prefill and s._ahead == bs and s.stop_t is None
-                and temperature < 1e-5 and draft_temperature < 1e-5):
+                and 2 <= bs <= 16 and want_hidden and not draft_prefill and s._ahead == bs and not s.stop_always
+                and s.replay_sampling_ok and draft_temperature < 1e-5):
             if getattr(s, "_graph_bs", None) is None and not getattr(s, "_graph_off", False):
                 try:
                     s.capture(bs)
@@ -625,7 +674,7 @@ def run_decode(model, target, input_ids: torch.Tensor, *, mask_token_id: int, ma
             # cycle N + 1, outside that cycle's [cycle0, cycle1] marks; benchmark.py:149-160 times each phase inside its
             # own cycle)
             if (use_graphs and scheduler is not None and draft_steps == 1 and not collect_profile and want_hidden
-                    and not draft_prefill and s.stop_t is None and temperature < 1e-5 and draft_temperature < 1e-5
+                    and not draft_prefill and not s.stop_always and s.replay_sampling_ok
                     and len(getattr(scheduler, "candidates", ())) > 0
                     and 2 <= min(scheduler.candidates) and max(scheduler.candidates) <= 16):
                 # the policy loop by replay: one pair of graphs per candidate size (DecodeSession.capture_sizes)
@@ -641,6 +690,8 @@ def run_decode(model, target, input_ids: torch.Tensor, *, mask_token_id: int, ma
         taus.append(r.tau)
         used_bs.append(bs)
         lgens.append(lg[0])
+        replayed += int(getattr(r, "replayed", False))
+        replayed_flags.append(bool(getattr(r, "replayed", False)))
         if scheduler is not None:
             cycle_s = cuda_time() - cycle_t0
             scheduler.update(tau=r.tau, cycle_s=cycle_s, effective_bs=bs, cycle_idx=cyc, l_gen=lg[0])
@@ -675,17 +726,26 @@ def run_decode(model, target, input_ids: torch.Tensor, *, mask_token_id: int, ma
                            time_to_first_token=time_to_first_token,
                            time_per_output_token=total_decode_time / max(1, num_output_tokens),
                            acceptance_lengths=taus, used_block_sizes=used_bs, l_gen=lgens,
-                           cycle_trace=cycle_trace, profile_summary=profile_summary)
+                           cycle_trace=cycle_trace, profile_summary=profile_summary, replayed_cycles=replayed,
+                           replayed_flags=replayed_flags,
+                           seed=s.seed)
 
 
-def _draft_ids(model, hid_frag, lm_wp, bs, blk, draft_temperature, keep_logits=None):
+def _draft_ids(model, hid_frag, lm_wp, bs, blk, draft_temperature, keep_logits=None, seed=None, dyn=None, start=None):
     """blk[0, 1:bs] <- draft tokens.  Greedy (every loop but the policy one at T>0):
     fused lm_head GEMM + argmax.  benchmark_dynamic_schedule.py:342 samples the draft
     with the temperature: then the logits are materialised by the same GEMM and the
     reference's softmax + multinomial is applied to them.  keep_logits (bf16 [16 * tiles, V]): the caller's
-    buffer for the materialised logits (the multi-candidate loop builds its candidates from them)."""
+    buffer for the materialised logits (the multi-candidate loop builds its candidates from them).
+    seed (sampler="device"): the seeded draw of the same GEMM's epilogue instead (stream DRAFT: slot j of the block that
+    starts at `start` draws position start + j, extra = start); dyn: the draft cache's record, whose START word holds
+    that start on the device (what a captured graph reads)."""
     if draft_temperature < 1e-5:
         model.draft_tokens(hid_frag, lm_wp, bs, blk[0], logits=keep_logits)
+        return
+    if seed is not None:
+        model.draft_tokens(hid_frag, lm_wp, bs, blk[0], logits=keep_logits,
+                           sample=dict(seed=seed, temperature=draft_temperature, dyn=dyn, start=start))
         return
     V = model.config.vocab_size
     logits = keep_logits
@@ -715,22 +775,28 @@ def _resolve_profile(cycle_trace, ttft, decode_wall):
 
 def dflash_generate(model, target, input_ids: torch.Tensor, mask_token_id: int, max_new_tokens: int,
                     block_size: int, stop_token_ids, temperature: float = 0.0, collect_profile: bool = False,
-                    draft_steps: int = 1, draft_token_hook=None) -> SimpleNamespace:
-    """benchmark.py:44-55 signature; returns the namespace of :242-251."""
+                    draft_steps: int = 1, draft_token_hook=None, sampler: str = "torch",
+                    seed: Optional[int] = None) -> SimpleNamespace:
+    """benchmark.py:44-55 signature; returns the namespace of :242-251 (+ replayed_cycles).
+    sampler="device": T > 0 draws are seeded on the device — the same seed gives the same tokens
+    however the request runs, and the cycles can be replayed from hipGraphs; seed=None draws one from torch's RNG."""
     if getattr(model, "wide_hidden", False):
         return _generate_wide_hidden(model, target, input_ids, mask_token_id, max_new_tokens, block_size, stop_token_ids,
-                                     temperature, collect_profile, draft_steps, draft_token_hook)
+                                     temperature, collect_profile, draft_steps, draft_token_hook, sampler, seed)
     r = run_decode(model, target, input_ids, mask_token_id=mask_token_id, max_new_tokens=max_new_tokens,
                    block_size=block_size, stop_token_ids=stop_token_ids, temperature=temperature, clamp_tail=True,
-                   draft_steps=draft_steps, collect_profile=collect_profile, draft_token_hook=draft_token_hook)
+                   draft_steps=draft_steps, collect_profile=collect_profile, draft_token_hook=draft_token_hook,
+                   sampler=sampler, seed=seed)
     return SimpleNamespace(output_ids=r.output_ids, num_input_tokens=r.num_input_tokens,
                            num_output_tokens=r.num_output_tokens, time_to_first_token=r.time_to_first_token,
                            time_per_output_token=r.time_per_output_token, acceptance_lengths=r.acceptance_lengths,
-                           cycle_trace=r.cycle_trace, profile_summary=r.profile_summary)
+                           cycle_trace=r.cycle_trace, profile_summary=r.profile_summary,
+                           replayed_cycles=r.replayed_cycles)
 
 
 def _generate_wide_hidden(model, target, input_ids, mask_token_id, max_new_tokens, block_size, stop_token_ids, temperature,
-                          collect_profile=False, draft_steps=1, draft_token_hook=None) -> SimpleNamespace:
+                          collect_profile=False, draft_steps=1, draft_token_hook=None, sampler="torch",
+                          seed=None) -> SimpleNamespace:
     """hidden_size > 4096: the request runs as a group of ONE through the ragged-batch kernels (their GEMMs cut K over
     workgroups; the single-request kernels keep a whole K = hidden row slice per workgroup).  Same loop semantics
     (benchmark.py:44-251, tail clamp included); no per-cycle profile, one draft step per cycle."""
@@ -743,13 +809,16 @@ def _generate_wide_hidden(model, target, input_ids, mask_token_id, max_new_token
         raise NotImplementedError("hidden_size > 4096: no per-cycle profile and one draft step per cycle")
     hook = (lambda r, blk, start, call: draft_token_hook(blk, start, call)) if draft_token_hook else None
     return dflash_generate_batch(model, target, [input_ids], mask_token_id, max_new_tokens, block_size, stop_token_ids,
-                                 temperature, draft_token_hook=hook, group_size=1, hook_block_view=True)[0]
+                                 temperature, draft_token_hook=hook, group_size=1, hook_block_view=True, sampler=sampler,
+                                 seed=None if seed is None else [seed])[0]
 
 
 def dflash_generate_policy(*, model, target, input_ids: torch.Tensor, mask_token_id: int, max_new_tokens: int,
                            stop_token_ids, temperature: float, fixed_block_size: Optional[int] = None,
-                           scheduler=None, draft_token_hook=None) -> SimpleNamespace:
-    """benchmark_dynamic_schedule.py:260-272 signature; returns the namespace of :425-434."""
+                           scheduler=None, draft_token_hook=None, sampler: str = "torch",
+                           seed: Optional[int] = None) -> SimpleNamespace:
+    """benchmark_dynamic_schedule.py:260-272 signature; returns the namespace of :425-434 (+ replayed_cycles).
+    sampler / seed: as dflash_generate; the draft's own T > 0 draw uses the same seed on a stream of its own."""
     if fixed_block_size is None and scheduler is None:
         raise ValueError("Either fixed_block_size or scheduler must be provided.")
     max_bs = fixed_block_size if fixed_block_size is not None else max(scheduler.candidates)
@@ -757,7 +826,7 @@ def dflash_generate_policy(*, model, target, input_ids: torch.Tensor, mask_token
     r = run_decode(model, target, input_ids, mask_token_id=mask_token_id, max_new_tokens=max_new_tokens,
                    block_size=max_bs, stop_token_ids=stop_token_ids, temperature=temperature, clamp_tail=True,
                    scheduler=sched, draft_temperature=temperature, max_block_size=max_bs,
-                   draft_token_hook=draft_token_hook)
+                   draft_token_hook=draft_token_hook, sampler=sampler, seed=seed)
     if fixed_block_size is not None:
         for row in r.cycle_trace:
             for k in ("tau_hat", "cycle_hat", "score_hat", "current_block_size", "adl_lgen_hat", "adl_lacc_hat",
@@ -766,7 +835,8 @@ def dflash_generate_policy(*, model, target, input_ids: torch.Tensor, mask_token
     return SimpleNamespace(output_ids=r.output_ids, num_input_tokens=r.num_input_tokens,
                            num_output_tokens=r.num_output_tokens, time_to_first_token=r.time_to_first_token,
                            time_per_output_token=r.time_per_output_token, acceptance_lengths=r.acceptance_lengths,
-                           used_block_sizes=r.used_block_sizes, cycle_trace=r.cycle_trace)
+                           used_block_sizes=r.used_block_sizes, cycle_trace=r.cycle_trace,
+                           replayed_cycles=r.replayed_cycles)
 
 
 class _Fixed:

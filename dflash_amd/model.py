@@ -501,20 +501,31 @@ class DFlashDraftModel:
         return WideRows(s["xn"], dyn2)
 
     def draft_tokens(self, hid_frag, lm_head_wp: torch.Tensor, bs: int, block_ids: torch.Tensor,
-                     logits: Optional[torch.Tensor] = None, margins: Optional[torch.Tensor] = None) -> None:
+                     logits: Optional[torch.Tensor] = None, margins: Optional[torch.Tensor] = None,
+                     sample: Optional[dict] = None) -> None:
         """block_ids[1:bs] <- argmax(lm_head(hidden[1:bs])) (model/dflash.py:238,245,247).
         hid_frag: what draft_block returned (one row source per 16-row tile; a single source = one tile).
         logits (bf16 [16 * tiles, V]) / margins (fp32 [>= bs]): margins[j] <- top-1 minus top-2 draft
         logit of block slot j >= 1, the reference's per-position confidence
-        (benchmark_candidate_solutions.py:296-302)."""
+        (benchmark_candidate_solutions.py:296-302).
+        sample (the device sampler): dict(seed, temperature, dyn, start) — slot j draws the seeded
+        stream-DRAFT noise of position start + j (extra = start), start from dyn's START word when dyn is given."""
         c, ws = self.config, self._workspace()
         if isinstance(hid_frag, WideRows):   # both tiles in one lm_head pass (ragged-batch GEMM, R = 2)
             if margins is not None:
                 raise NotImplementedError("top-2 margins are computed for blocks of <= 16 rows")
             ww = self._wide
+            if sample is not None and logits is None:   # (no sampled ring epilogue: the draw runs over the logits)
+                logits = torch.empty(32, c.vocab_size, dtype=BF16, device=self.device)
             ops.gemm_argmax_batch(lm_head_wp, hid_frag.src, 2, c.vocab_size, c.hidden_size, 0, 16, ww["gws"], ww["ids"], 0,
                                   hid_frag.dyn, nrows_dyn_word=ops.DYN_BS,
                                   logits=None if logits is None else logits.view(2, 16, c.vocab_size))
+            if sample is not None:
+                if sample.get("start") is None:
+                    raise ValueError("a sampled draft of more than 16 rows needs the block start on the host")
+                st = int(sample["start"])
+                ops.sample_rows(logits.view(-1, c.vocab_size)[:bs], seed=sample["seed"], temperature=sample["temperature"],
+                                pos0=st, stream=ops.RNG_DRAFT, extra=st, out=ww["ids"].view(-1)[:bs])
             block_ids[1:bs].copy_(ww["ids"].view(-1)[1:bs])
             return
         srcs = hid_frag if isinstance(hid_frag, (list, tuple)) else [hid_frag]
@@ -522,6 +533,16 @@ class DFlashDraftModel:
             row0 = 1 if t == 0 else 0
             nrows = min(bs - 16 * t, 16) - row0
             if nrows <= 0:
+                continue
+            if sample is not None:
+                dyn = sample.get("dyn")
+                if dyn is None and sample.get("start") is None:
+                    raise ValueError("a sampled draft needs the block start: a length record or the host value")
+                ops.gemm_sample(lm_head_wp, x, c.vocab_size, c.hidden_size, row0, nrows, ws["argmax_ws"], block_ids,
+                                16 * t + row0, seed=sample["seed"], temperature=sample["temperature"], stream=ops.RNG_DRAFT,
+                                pos_dyn=dyn, pos_word=ops.DYN_START, pos_base=int(sample.get("start") or 0),
+                                pos_add=16 * t, logits=None if logits is None else logits[16 * t:16 * t + 16],
+                                margins=margins)
                 continue
             ev = self.lm_head_events if t == 0 else None   # bench.py: the lm_head kernel itself between two events
             if ev is not None and self.lm_head_events_log is not None:
@@ -573,13 +594,15 @@ class DFlashDraftModel:
 
     @torch.inference_mode()
     def spec_generate(self, target, input_ids: torch.LongTensor, max_new_tokens: int, stop_token_ids,
-                      temperature: float, draft_token_hook=None) -> torch.LongTensor:
-        """model/dflash.py:192-277."""
+                      temperature: float, draft_token_hook=None, sampler: str = "torch",
+                      seed: Optional[int] = None) -> torch.LongTensor:
+        """model/dflash.py:192-277.  sampler / seed: as dflash_generate."""
         from .generate import _generate_wide_hidden, run_decode
         if self.wide_hidden:    # (ids are the same with or without the harness form's tail clamp)
             return _generate_wide_hidden(self, target, input_ids, self.mask_token_id, max_new_tokens, self.block_size,
-                                         stop_token_ids, temperature, draft_token_hook=draft_token_hook).output_ids
+                                         stop_token_ids, temperature, draft_token_hook=draft_token_hook, sampler=sampler,
+                                         seed=seed).output_ids
         r = run_decode(self, target, input_ids, mask_token_id=self.mask_token_id, max_new_tokens=max_new_tokens,
                        block_size=self.block_size, stop_token_ids=stop_token_ids, temperature=temperature,
-                       clamp_tail=False, draft_token_hook=draft_token_hook)
+                       clamp_tail=False, draft_token_hook=draft_token_hook, sampler=sampler, seed=seed)
         return r.output_ids

@@ -186,6 +186,52 @@ def gemm_argmax(wp, x, V: int, K: int, row0: int, nrows: int, ws, out_ids: torch
     check(lib().dfl_gemm_argmax(*args, _stream()), "dfl_gemm_argmax")
 
 
+RNG_TARGET, RNG_DRAFT = 0, 1   # noise streams of the seeded sampler (csrc/dfl_rng.h)
+
+
+def _seed64(seed: int) -> int:
+    return int(seed) & 0xFFFFFFFFFFFFFFFF
+
+
+def inv_temperature(temperature: float) -> float:
+    """float32(1 / T), computed on the host (the sampling contract)."""
+    import numpy as np
+    return float(np.float32(1.0 / float(temperature)))
+
+
+def gemm_sample(wp, x, V: int, K: int, row0: int, nrows: int, ws, out_ids: torch.Tensor, out_off: int = 0, *,
+                seed: int, temperature: float, stream: int = RNG_TARGET, pos_dyn=None, pos_word: int = DYN_POS0,
+                pos_base: int = 0, pos_add: int = 0, dyn=None, nrows_dyn_word: int = -1,
+                logits: Optional[torch.Tensor] = None, margins: Optional[torch.Tensor] = None) -> None:
+    """gemm_argmax with the seeded Gumbel-max draw at `temperature` (dfl_gemm_sample): tile row m draws position
+    (pos_dyn[pos_word] if pos_dyn is given, else pos_base) + pos_add + m."""
+    if logits is not None:
+        assert logits.numel() >= 16 * V
+    if margins is not None:
+        assert margins.numel() >= out_off + nrows
+    check(lib().dfl_gemm_sample(_p(wp, BF16, "wp"), _src(x).ref, V, K, row0, nrows, _p(dyn, I32, "dyn"), nrows_dyn_word,
+                                _p(ws), _p(out_ids, I64, "out_ids"), out_off, _p(logits, BF16, "logits"),
+                                _p(margins, F32, "margins"), _seed64(seed), inv_temperature(temperature), stream,
+                                _p(pos_dyn, I32, "pos_dyn"), pos_word, pos_base, pos_add, _stream()), "dfl_gemm_sample")
+
+
+def sample_rows(logits: torch.Tensor, *, seed: int, temperature: float, pos0: int = 0, positions=None,
+                stream: int = RNG_TARGET, extra: int = 0, out: Optional[torch.Tensor] = None,
+                margins: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The seeded draw over materialised bf16 logits [rows, V] (unit inner stride): row r draws position positions[r]
+    (int32) or pos0 + r.  Returns int64 ids [rows] (into `out` if given)."""
+    assert logits.dim() == 2 and logits.stride(1) == 1 and logits.is_cuda
+    if logits.dtype != BF16:
+        logits = logits.to(BF16)
+    rows, V = logits.shape
+    if out is None:
+        out = torch.empty(rows, dtype=I64, device=logits.device)
+    check(lib().dfl_sample_rows(logits.data_ptr(), logits.stride(0), rows, V, _seed64(seed), inv_temperature(temperature),
+                                stream, pos0, _p(positions, I32, "positions"), extra, _p(out, I64, "out"),
+                                _p(margins, F32, "margins"), _stream()), "dfl_sample_rows")
+    return out
+
+
 def gemm_resid(wp, x, N: int, K: int, h_io: torch.Tensor, *, add_residual: bool, ss_out=None, tap=None,
                dyn=None) -> None:
     """h_io [16, >=N] bf16 (unit inner stride) updated in place; tap: optional [16, *] view
@@ -608,6 +654,31 @@ def gemm_argmax_batch(wp, x: BatchRowSource, R: int, V: int, K: int, row0: int, 
     check(lib().dfl_gemm_argmax_batch(_p(wp, BF16, "wp"), x.ref, R, V, K, row0, nrows, _p(dyn, I32, "dyn"),
                                       nrows_dyn_word, _p(ws), out_ids.data_ptr(), out_ids.stride(0), out_off, lp, lst,
                                       _stream()), "dfl_gemm_argmax_batch")
+
+
+def seed_i64(seed: int) -> int:
+    """A 64-bit seed as the int64 a device seed array holds (same bits)."""
+    s = _seed64(seed)
+    return s - (1 << 64) if s >= (1 << 63) else s
+
+
+def gemm_sample_batch(wp, x: BatchRowSource, R: int, V: int, K: int, row0: int, nrows: int, ws,
+                      out_ids: torch.Tensor, out_off: int, dyn, *, seeds: torch.Tensor, temperature: float,
+                      stream: int = RNG_TARGET, pos_word: int = DYN_POS0, pos_add: int = 0, tiles_per_req: int = 1,
+                      nrows_dyn_word: int = -1, logits: Optional[torch.Tensor] = None) -> None:
+    """gemm_argmax_batch with the seeded draw (dfl_gemm_sample_batch): tile t (tile j = t % tiles_per_req of request
+    q = t // tiles_per_req) row m draws position dyn[t][pos_word] + pos_add + 16 j + m with seed seeds[q] (int64)."""
+    assert out_ids.dim() == 2 and out_ids.dtype == I64 and out_ids.stride(1) == 1
+    mt = batch_tiles(R)
+    assert dyn is not None and dyn.numel() >= 8 * mt and seeds.numel() >= mt // tiles_per_req
+    lp, lst = None, 0
+    if logits is not None:
+        assert logits.dim() == 3 and logits.shape[1] == 16 and logits.shape[2] == V and logits.is_contiguous()
+        lp, lst = _p(logits, BF16, "logits"), logits.stride(0)
+    check(lib().dfl_gemm_sample_batch(_p(wp, BF16, "wp"), x.ref, R, V, K, row0, nrows, _p(dyn, I32, "dyn"), nrows_dyn_word,
+                                      _p(ws), out_ids.data_ptr(), out_ids.stride(0), out_off, lp, lst,
+                                      _p(seeds, I64, "seeds"), inv_temperature(temperature), stream, pos_word, pos_add,
+                                      tiles_per_req, _stream()), "dfl_gemm_sample_batch")
 
 
 def embed_rows_batch(embed, ids: torch.Tensor, R: int, h_out: torch.Tensor, H: int, ss_out: torch.Tensor, dyn,

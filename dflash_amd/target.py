@@ -529,7 +529,7 @@ class NativeTarget:
         return 1
 
     # ---- the verify forward on the kernels
-    def _verify_wide(self, block_ids, start, cache, bs, tap_layers, taps, logits_out, temperature, cos, sin):
+    def _verify_wide(self, block_ids, start, cache, bs, tap_layers, taps, logits_out, temperature, cos, sin, seed=None):
         """Blocks of 17..32 rows in ONE pass over the weights: the two 16-row tiles go through the ragged-batch
         GEMMs (dfl_*_batch with R = 2: fp32 K-part sums of o_proj / down_proj, residual add + RMSNorm in
         dfl_norm_frag_batch) as if they were two requests, and through ONE attention launch with two query tiles on the
@@ -593,7 +593,11 @@ class NativeTarget:
             logits = torch.empty(32, self.V, dtype=BF16, device=self._dev)
         ops.gemm_argmax_batch(self.lm_wp, s["xn"], R, self.V, H, 0, 16, gws, post.view(2, 16), 0, dyn2,
                               nrows_dyn_word=ops.DYN_BS, logits=None if logits is None else logits.view(2, 16, self.V))
-        posterior = post[:bs].unsqueeze(0) if temperature < 1e-5 else sample(logits[:bs].unsqueeze(0), temperature)
+        if temperature >= 1e-5 and seed is not None:   # the seeded draw over the materialised rows: row j -> start + j + 1
+            ops.sample_rows(logits[:bs], seed=seed, temperature=temperature, pos0=start + 1, out=post[:bs])
+            posterior = post[:bs].unsqueeze(0)
+        else:
+            posterior = post[:bs].unsqueeze(0) if temperature < 1e-5 else sample(logits[:bs].unsqueeze(0), temperature)
         cache.length = start + bs
         return posterior, taps
 
@@ -606,7 +610,7 @@ class NativeTarget:
     @torch.inference_mode()
     def verify(self, block_ids: torch.Tensor, start: int, cache: TargetKVCache, *, tap_layers: Sequence[int] = (),
                temperature: float = 0.0, logits_out: Optional[torch.Tensor] = None,
-               taps_out: Optional[torch.Tensor] = None, dyn_lengths: bool = False):
+               taps_out: Optional[torch.Tensor] = None, dyn_lengths: bool = False, seed: Optional[int] = None):
         """block_ids int64 [bs] at positions start..start+bs-1 (cache rows alike), bs <= 32.
         Returns (posterior ids int64 [1, bs], taps bf16 [32, len(tap_layers)*H] or None).
         K/V of all bs rows are written; the caller crops to what it accepts.
@@ -617,7 +621,10 @@ class NativeTarget:
         tile of every single-request GEMM (wide_one_pass = False); both query tiles share the attention launch.
         dyn_lengths (bs <= 16, attention stage "head"): the launches take S / pos0 from the cache's device record alone
         (kept by dfl_accept_commit_rearm_t) — `start` is then only an upper bound that sizes the attention's key splits
-        and the RoPE table, and the sequence can be captured into a hipGraph (DecodeSession.capture)."""
+        and the RoPE table, and the sequence can be captured into a hipGraph (DecodeSession.capture).
+        seed (temperature > 0): the seeded Gumbel-max draw in the lm_head epilogue instead of softmax + multinomial —
+        row j draws position start + j + 1, start from the record's POS0 word under dyn_lengths (DESIGN.md section 8);
+        no logits are written unless logits_out is given."""
         bs = block_ids.numel()
         if self.wide_hidden:
             raise NotImplementedError("NativeTarget.verify: hidden > 4096 runs through the ragged-batch path "
@@ -659,7 +666,7 @@ class NativeTarget:
                 taps = self._taps[key]
         Ls, src = self.layers, self.src
         if len(tiles) == 2 and self.wide_one_pass and self.attn_impl == "head":
-            return self._verify_wide(block_ids, start, cache, bs, tap_layers, taps, logits_out, temperature, cos, sin)
+            return self._verify_wide(block_ids, start, cache, bs, tap_layers, taps, logits_out, temperature, cos, sin, seed)
         hrow = [ws["h"][16 * t:16 * t + 16] for t in range(2)]
         for t, dt in tiles:
             ops.embed_rows(self.embed, block_ids[16 * t:], hrow[t], H, ws["ss_emb"][16 * t:], dt, ops.DYN_BS)
@@ -718,9 +725,17 @@ class NativeTarget:
                 taps[:, j * H:(j + 1) * H].copy_(taps[:, sl[0] * H:(sl[0] + 1) * H])
         post = ws["post"]
         logits = logits_out
+        fin = src["xn1"] if prev_moe else src["final"]   # after an MoE layer the rows are final-normed already
+        if temperature >= 1e-5 and seed is not None:
+            for t, dt in tiles:   # tile t row m predicts position start + 16 t + m + 1
+                ops.gemm_sample(self.lm_wp, fin[t], self.V, H, 0, min(16, bs - 16 * t), ws["argmax_ws"], post, 16 * t,
+                                seed=seed, temperature=temperature, pos_dyn=dt if dyn_lengths else None,
+                                pos_word=ops.DYN_POS0, pos_base=start, pos_add=16 * t + 1, dyn=dt,
+                                logits=None if logits is None else logits[16 * t:16 * t + 16])
+            cache.length = start + bs
+            return post[:bs].unsqueeze(0), taps
         if temperature >= 1e-5:
             logits = torch.empty(16 * len(tiles), self.V, dtype=BF16, device=self._dev)
-        fin = src["xn1"] if prev_moe else src["final"]   # after an MoE layer the rows are final-normed already
         for t, dt in tiles:
             ops.gemm_argmax(self.lm_wp, fin[t], self.V, H, 0, min(16, bs - 16 * t), ws["argmax_ws"], post, 16 * t,
                             dyn=dt, logits=None if logits is None else logits[16 * t:16 * t + 16])

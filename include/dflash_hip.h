@@ -141,6 +141,17 @@ int dfl_gemm_argmax_timed(const void *wp, const dfl_rows *x, int V, int K, int r
                           int nrows_dyn_word, void *ws, int64_t *out_ids, int out_off, void *logits, float *margin_out,
                           void *ev_start, void *ev_end, void *stream);
 
+/* Seeded sampling at temperature T fused into the same lm_head GEMM (Gumbel-max):
+ *   ids[r] = argmax_n fmaf(bf16(x[r] . W[n]), inv_t, g(seed, rng_stream, p_r, n, extra)), first index on ties,
+ * inv_t = float32(1 / T), g the Gumbel noise of dfl_rng.h (Philox4x32-10, key = seed, counter = (n >> 2, p, extra,
+ * stream)).  Tile row m draws position p = base + pos_add + m with base = pos_dyn[pos_word] (a device length record, so
+ * a captured graph draws fresh positions on every replay) or, pos_dyn NULL, base = pos_base.  rng_stream 0 (TARGET):
+ * extra = 0; 1 (DRAFT): extra = base.  Everything else as dfl_gemm_argmax; margin_out is the perturbed top-2 gap. */
+int dfl_gemm_sample(const void *wp, const dfl_rows *x, int V, int K, int row0, int nrows, const int32_t *dyn,
+                    int nrows_dyn_word, void *ws, int64_t *out_ids, int out_off, void *logits, float *margin_out,
+                    uint64_t seed, float inv_t, int rng_stream, const int32_t *pos_dyn, int pos_word, int pos_base,
+                    int pos_add, void *stream);
+
 /* GEMM with the residual epilogue (o_proj / down_proj / fc, model/dflash.py:101,140,144,177):
  *   v = bf16(x W^T);  h_io[m][n] <- add_residual ? bf16(h_io[m][n] + v) : v;
  *   tap[m][n] <- the same value (optional: a tapped target layer, model/utils.py:16-25);
@@ -365,6 +376,12 @@ int dfl_moe_down(const void *wp_down, int64_t wp_expert_stride, const void *act_
  * dtype: 0 = bf16, 1 = fp32.  ids int64 [rows]. */
 int dfl_argmax(const void *logits, int dtype, int rows, int64_t V, int64_t *ids, void *stream);
 
+/* The draw of dfl_gemm_sample over materialised bf16 logits [rows][ld] (the first V columns): row r draws position
+ * pos[r] (pos int32, may be NULL: pos0 + r) with the given `extra` counter word.  Same value compared as the fused
+ * epilogue, so the same ids.  out_ids int64 [rows]; margin_out (optional) fp32 [rows]: perturbed top-1 minus top-2. */
+int dfl_sample_rows(const void *logits, int64_t ld, int rows, int V, uint64_t seed, float inv_t, int rng_stream, int pos0,
+                    const int32_t *pos, int extra, int64_t *out_ids, float *margin_out, void *stream);
+
 /* Acceptance scan + commit + bonus token + stop test + length bookkeeping in one
  * wavefront (model/dflash.py:258-268):
  *   acc = #leading i with block[i+1] == posterior[i]           (0..bs-1)
@@ -517,6 +534,15 @@ int dfl_gemm_resid_batch(const void *wp, const dfl_rows_batch *x, int R, int N, 
 int dfl_gemm_argmax_batch(const void *wp, const dfl_rows_batch *x, int R, int V, int K, int row0, int nrows,
                           const int32_t *dyn, int nrows_dyn_word, void *ws, int64_t *out_ids, int64_t out_stride,
                           int out_off, void *logits, int64_t logits_stride, void *stream);
+/* dfl_gemm_sample for R <= 4 request tiles on one pass over the weights (ring form, EPI_SAMPLE epilogue): tile t is tile
+ * j = t % tiles_per_req of request q = t / tiles_per_req; its row m draws position dyn[t][pos_word] + pos_add + 16 j + m
+ * with seed seeds[q] (int64, one per request slot: a captured batch graph and a re-admitted slot keep working).  dyn
+ * holds batch_tiles(R) records, seeds batch_tiles(R) / tiles_per_req entries.  No slab form: -22 where the ring form
+ * does not apply. */
+int dfl_gemm_sample_batch(const void *wp, const dfl_rows_batch *x, int R, int V, int K, int row0, int nrows,
+                          const int32_t *dyn, int nrows_dyn_word, void *ws, int64_t *out_ids, int64_t out_stride,
+                          int out_off, void *logits, int64_t logits_stride, const int64_t *seeds, float inv_t,
+                          int rng_stream, int pos_word, int pos_add, int tiles_per_req, void *stream);
 /* dfl_embed_rows for R requests: ids[r * ids_stride + m]. */
 int dfl_embed_rows_batch(const void *embed, const int64_t *ids, int64_t ids_stride, int R, void *h_out,
                          int64_t h_stride, int H, float *ss_out, int64_t ss_stride, const int32_t *dyn, int dyn_word,
