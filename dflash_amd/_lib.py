@@ -120,6 +120,8 @@ SIGNATURES = {
                                   _i64, _f, _i, _p, _i, _p, _i, _p, _i64, _p]),
     "dfl_accept_commit_batch": (_i, [_p, _i64, _p, _i64, _i, _p, _i64, _i64, _p, _p, _p, _i, _p, _p, _i64, _p]),
     "dfl_accept_commit_batch_t": (_i, [_p, _i64, _p, _i64, _i, _p, _i64, _i64, _p, _p, _p, _i, _p, _p, _i64, _i, _p, _p, _p]),
+    "dfl_admit_slot": (_i, [_i, _i, _p, _i, _p, _p, _i64, _i64, _p, _p, _i, _p, _p, _i64, _i, _p, _i, _p, _p, _i, _p, _i64,
+                            _i64, _p]),
 }
 
 _lib = None

@@ -162,6 +162,7 @@ class BatchedDecoder:
         self.events = None  # set to a dict to have cycle() record (start, end) event pairs per phase
         self._ahead, self._ahead_ev = False, None   # a run-ahead draft is in flight (cycle(ahead_ok=True))
         self.run_ahead = os.environ.get("DFL_RUN_AHEAD", "1") != "0"
+        self.graphs = None   # capture(): the three hipGraphs of a cycle
 
     def _mark(self, key, which):
         if self.events is not None:
@@ -170,13 +171,11 @@ class BatchedDecoder:
             self.events.setdefault(key, [None, None])[which] = e
 
     # ------------------------------------------------------------------ admission
-    @torch.inference_mode()
-    def admit(self, r: int, input_ids: torch.Tensor, temperature: float = 0.0, seed: Optional[int] = None) -> None:
-        """Prefill request r (model/dflash.py:218-229): target prefill through the wrapped
-        model, K/V into the group cache, first token sampled, the prompt's context rows
-        projected into the draft cache except the last <= 16, which become the first
-        cycle's context tile.  seed (sampler="device"): the request's seed (None: one from torch's RNG)."""
-        m, t, c = self.model, self.target, self.cfg
+    def _admit_prefill(self, r: int, input_ids: torch.Tensor, temperature: float, seed: Optional[int]):
+        """The launches both admissions share: target prefill into slot r's cache, the first token, the prompt's context
+        rows into the draft cache except the last <= 16.  Returns (P, first token [1, 1] on the device, tapped rows
+        [P, fc_in], the seed written for the slot or None)."""
+        m, t = self.model, self.target
         if input_ids.shape[0] != 1 or not input_ids.is_cuda:
             raise ValueError("admit: input_ids must be a [1, P] GPU tensor")
         P = input_ids.shape[1]
@@ -188,20 +187,32 @@ class BatchedDecoder:
             self.embed_w = _bf16_table(t.model.embed_tokens.weight, self.dev)
         tc = _View(self.tk[r], self.tv[r], None, self.max_rows)
         out = t.prefill(input_ids, tc, output_hidden_states=True, tap_layers=self.model.target_layer_ids)
-        self.output_ids[r].fill_(self.mask_id)
-        self.output_ids[r, :P] = input_ids[0]
+        sd = None
         if self.sampler == "device" and (temperature >= 1e-5 or self.temperature >= 1e-5):
             sd = resolve_seed("device", seed)
-            self.seeds[r] = ops.seed_i64(sd)
             first = _draw_rows(out.logits[:, -1:], temperature, sd, P) if temperature >= 1e-5 else sample(out.logits, 0.0)
         else:
             first = sample(out.logits, temperature)
-        self.output_ids[r, P:P + 1] = first[0]
         th = _taps(out.hidden_states, m.target_layer_ids)[0]          # [P, fc_in]
         n_tail = min(16, P)
         dc = _View(self.dk[r], self.dv[r], torch.zeros(8, dtype=I32, device=self.dev), self.max_rows)
         if P > n_tail:
             m.prefill_context(dc, th[:P - n_tail], 0)
+        return P, first, th, sd
+
+    @torch.inference_mode()
+    def admit(self, r: int, input_ids: torch.Tensor, temperature: float = 0.0, seed: Optional[int] = None) -> None:
+        """Prefill request r (model/dflash.py:218-229): target prefill through the wrapped
+        model, K/V into the group cache, first token sampled, the prompt's context rows
+        projected into the draft cache except the last <= 16, which become the first
+        cycle's context tile.  seed (sampler="device"): the request's seed (None: one from torch's RNG)."""
+        P, first, th, sd = self._admit_prefill(r, input_ids, temperature, seed)
+        self.output_ids[r].fill_(self.mask_id)
+        self.output_ids[r, :P] = input_ids[0]
+        if sd is not None:
+            self.seeds[r] = ops.seed_i64(sd)
+        self.output_ids[r, P:P + 1] = first[0]
+        n_tail = min(16, P)
         t0, BW = r * self.TPR, self.BW
         self.d["taps"][t0:t0 + self.TPR].zero_()
         self.d["taps"][t0, :n_tail] = th[P - n_tail:]      # (the tail rows fit the request's first tile)
@@ -215,6 +226,24 @@ class BatchedDecoder:
                 self.dyn_dt[t0 + j] = torch.tensor([S + 16 * j, n_tail if j == 0 else 0, 0, S + 16 * j, P, 0, 0, 0], dtype=I32)
                 self.dyn_tt[t0 + j] = torch.tensor([P, 0, 16, P, P, 0, 0, 0], dtype=I32)
         self.start[r], self.n_in[r], self.live[r], self.hook_calls[r], self.bs[r] = P, P, True, 0, BW
+
+    @torch.inference_mode()
+    def admit_fused(self, r: int, input_ids: torch.Tensor, temperature: float = 0.0, seed: Optional[int] = None) -> None:
+        """`admit` with the slot re-armed by ONE launch (dfl_admit_slot) instead of a dozen small writes: ids, first
+        token, block, context tile, both length records and the seed are written on the device from device-resident
+        inputs, so that after the prefill launches the admission reads nothing back and copies nothing from the host —
+        the other slots' cycle in flight is not waited for.  Leaves the device state `admit` leaves (and post / result
+        of the slot cleared).  Blocks of <= 16 rows (tiles_per_request = 1)."""
+        if self.TPR != 1:
+            raise NotImplementedError("admit_fused re-arms one 16-row tile per request; use admit() with tiles_per_request=2")
+        if not 0 <= r < self.R:
+            raise ValueError(f"admit_fused: slot {r} outside 0..{self.R - 1}")
+        P, first, th, sd = self._admit_prefill(r, input_ids, temperature, seed)
+        n_tail = min(16, P)
+        ops.admit_slot(r, input_ids[0].contiguous(), first.reshape(1), self.output_ids, self.block, self.post, self.result,
+                       th[P - n_tail:], self.d["taps"], self.dyn_d, self.dyn_t, self.BW, self.mask_id,
+                       seeds=self.seeds if sd is not None else None, seed=ops.seed_i64(sd) if sd is not None else 0)
+        self.start[r], self.n_in[r], self.live[r], self.hook_calls[r], self.bs[r] = P, P, True, 0, self.BW
 
     def park(self, r: int) -> None:
         """Request r is finished: its tile stays in the launches but does no work."""

@@ -356,3 +356,79 @@ extern "C" int dfl_accept_commit_batch_t(const int64_t *block_ids, int64_t blk_s
   DFL_CHECK_LAUNCH("dfl_accept_commit_batch_t");
   return DFL_OK;
 }
+
+// ---- slot admission (ragged batch): one launch re-arms slot r for a newly prefilled request ----------------------
+namespace {
+
+// Every record a decode cycle reads for slot r, written from device-resident inputs: the id row (prompt, first token,
+// mask), the block, the context tile (the prompt's last n_tail tapped rows, 16 bytes per lane, the rest zero), both
+// length records and the seed.  The first token is read from device memory: it never visits the host.
+__global__ __launch_bounds__(256) void k_admit_slot(int r, const int64_t *__restrict__ prompt_ids, int P,
+                                                    const int64_t *__restrict__ first_token, int64_t *output_ids,
+                                                    int64_t out_len, int64_t *block, int64_t *post, int blk_w, int32_t *result,
+                                                    const bf16_t *__restrict__ tail_rows, int64_t ld_tail, int n_tail,
+                                                    bf16_t *taps_tile, int fc_in, int32_t *dyn_d, int32_t *dyn_t, int bs,
+                                                    int64_t *seeds, int64_t seed, int64_t mask_id) {
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
+  const int vec_per_row = fc_in / 8;
+  const int64_t nvec = (int64_t)16 * vec_per_row;
+  for (int64_t v = tid; v < nvec; v += nthr) {
+    const int row = (int)(v / vec_per_row), col = (int)(v % vec_per_row);
+    u32x4 x = {0u, 0u, 0u, 0u};
+    if (row < n_tail) x = *reinterpret_cast<const u32x4 *>(tail_rows + (int64_t)row * ld_tail + 8 * col);
+    *reinterpret_cast<u32x4 *>(taps_tile + (int64_t)row * fc_in + 8 * col) = x;
+  }
+  const int64_t first = *first_token;
+  for (int64_t i = tid; i < out_len; i += nthr) output_ids[i] = i < P ? prompt_ids[i] : (i == P ? first : mask_id);
+  if (blockIdx.x != 0) return;
+  const int i = threadIdx.x;
+  if (i < blk_w) {
+    block[i] = i == 0 ? first : mask_id;
+    post[i] = 0;
+  }
+  if (i < 4) result[i] = 0;
+  if (i < DFL_DYN_WORDS) {
+    const int S = P - n_tail;
+    int d = 0, t = 0;
+    switch (i) {
+      case DFL_DYN_S: d = S, t = P; break;
+      case DFL_DYN_TAU: d = n_tail; break;
+      case DFL_DYN_BS: d = bs, t = bs; break;
+      case DFL_DYN_POS0: d = S, t = P; break;
+      case DFL_DYN_START: d = P, t = P; break;
+      default: break;   // DFL_DYN_STOP, DFL_DYN_CYCLE and the spare word: cleared
+    }
+    dyn_d[i] = d;
+    dyn_t[i] = t;
+  }
+  if (i == 0 && seeds) seeds[r] = seed;
+}
+
+}  // namespace
+
+extern "C" int dfl_admit_slot(int r, int n_slots, const int64_t *prompt_ids, int P, const int64_t *first_token,
+                              int64_t *output_ids, int64_t out_stride, int64_t out_len, int64_t *block, int64_t *post,
+                              int blk_w, int32_t *result, const void *tail_rows, int64_t ld_tail, int n_tail, void *taps,
+                              int fc_in, int32_t *dyn_d, int32_t *dyn_t, int bs, int64_t *seeds, int64_t seed,
+                              int64_t mask_id, void *stream) {
+  DFL_REQUIRE(n_slots >= 1 && r >= 0 && r < n_slots, "dfl_admit_slot: slot r=%d outside 0..%d", r, n_slots - 1);
+  DFL_REQUIRE(P >= 1 && (int64_t)P + 1 <= out_len && out_stride >= out_len,
+              "dfl_admit_slot: prompt of %d ids + first token does not fit out_len=%lld", P, (long long)out_len);
+  DFL_REQUIRE(n_tail >= 0 && n_tail <= 16 && n_tail <= P, "dfl_admit_slot: n_tail=%d outside 0..min(16, P)", n_tail);
+  DFL_REQUIRE(blk_w >= 1 && blk_w <= 64 && bs >= 0 && bs <= blk_w, "dfl_admit_slot: blk_w=%d bs=%d outside range", blk_w, bs);
+  DFL_REQUIRE(fc_in >= 8 && fc_in % 8 == 0 && ld_tail % 8 == 0 && (n_tail == 0 || ld_tail >= fc_in) &&
+                  (uintptr_t)tail_rows % 16 == 0 && (uintptr_t)taps % 16 == 0,
+              "dfl_admit_slot: tapped rows need fc_in %% 8 == 0 and 16-byte aligned rows (fc_in=%d ld=%lld)", fc_in,
+              (long long)ld_tail);
+  DFL_REQUIRE(prompt_ids && first_token && output_ids && block && post && result && taps && dyn_d && dyn_t,
+              "dfl_admit_slot: null pointer");
+  DFL_REQUIRE(n_tail == 0 || tail_rows, "dfl_admit_slot: null pointer (tail_rows with n_tail > 0)");
+  const int64_t work = (int64_t)16 * (fc_in / 8) > out_len ? (int64_t)16 * (fc_in / 8) : out_len;
+  const int grid = (int)((work + 255) / 256 < 128 ? (work + 255) / 256 : 128);
+  hipLaunchKernelGGL(k_admit_slot, dim3(grid), dim3(256), 0, (hipStream_t)stream, r, prompt_ids, P, first_token,
+                     output_ids + (int64_t)r * out_stride, out_len, block + (int64_t)r * blk_w, post + (int64_t)r * blk_w, blk_w,
+                     result + 4 * r, (const bf16_t *)tail_rows, ld_tail, n_tail, (bf16_t *)taps + (int64_t)r * 16 * fc_in, fc_in,
+                     dyn_d + r * DFL_DYN_WORDS, dyn_t + r * DFL_DYN_WORDS, bs, seeds, seed, mask_id);
+  DFL_CHECK_LAUNCH("dfl_admit_slot");
+  return DFL_OK;
+}

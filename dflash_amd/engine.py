@@ -1,0 +1,195 @@
+"""A ragged batch that stays full: `BatchEngine` owns ONE `BatchedDecoder` (one set of caches, workspaces and
+hipGraphs) for its whole life and re-admits the next queued prompt into a slot as soon as its request ends, instead of
+running static groups until their slowest request is done (`dflash_generate_batch`).  DESIGN.md section 9.
+
+Contract, the one `dflash_generate_batch` states: request i emits exactly what `dflash_generate(model, target,
+prompt_i, ..., max_new_tokens_i, ...)` emits — ids, acceptance lengths, token count — whichever slot it lands in,
+whenever it is admitted and whatever ran in that slot before; with sampler="device" at T > 0 under the terms of
+DESIGN.md section 8.  The scheduling decisions live in `dflash_amd.slots.SlotLoop` (pure Python)."""
+from __future__ import annotations
+
+import os
+from types import SimpleNamespace
+from typing import Callable, Optional, Sequence, Union
+
+import torch
+
+from .batch import MAX_GROUP, BatchedDecoder, _prompt_seeds
+from .generate import _trim, cuda_time
+from .slots import SlotLoop
+
+BLOCK_ROWS = 16   # rows of a slot's tile: the margins below are the ones dflash_generate_batch sizes its decoder with
+
+
+def check_fit(P: int, max_new_tokens: int, max_rows: int, out_len: int) -> None:
+    """ValueError unless a prompt of P ids with max_new_tokens fits a decoder of max_rows cache rows and out_len ids
+    (no torch, no GPU: `submit` calls it before anything is launched)."""
+    if P < 1 or max_new_tokens < 0:
+        raise ValueError("a request has a prompt of at least one id and max_new_tokens >= 0")
+    if P + max_new_tokens + 3 * BLOCK_ROWS > max_rows:
+        raise ValueError(f"request does not fit: P + max_new_tokens + {3 * BLOCK_ROWS} = "
+                         f"{P + max_new_tokens + 3 * BLOCK_ROWS} > max_rows = {max_rows}")
+    if P + max_new_tokens + BLOCK_ROWS > out_len:
+        raise ValueError(f"request does not fit: P + max_new_tokens + {BLOCK_ROWS} = "
+                         f"{P + max_new_tokens + BLOCK_ROWS} > out_len = {out_len}")
+
+
+class _DecoderDriver:
+    """The driver protocol of dflash_amd.slots over one BatchedDecoder.  It holds no reference to the engine or the
+    loop: an engine that goes out of scope is freed at once, graphs included, not by a later garbage collection —
+    which, if it ran inside another engine's capture, would destroy a hipGraph while a stream is capturing."""
+
+    def __init__(self, dec: BatchedDecoder, stats: dict, use_graph: bool, temperature: float, stop_token_ids):
+        self.dec, self.stats, self.use_graph = dec, stats, use_graph
+        self.temperature, self.stop_token_ids = temperature, stop_token_ids
+        self.hooks = [None] * dec.R
+        self.guard = None
+
+    def _captured_state(self) -> tuple:
+        """Addresses a captured launch reads that a prefill could in principle move."""
+        d, m, t = self.dec, self.dec.model, self.dec.target
+        return (m._rope[0].data_ptr(), m._rope[1].data_ptr(), t._rope[0].data_ptr(), t._rope[1].data_ptr(),
+                d.lm_wp.data_ptr(), d.embed_w.data_ptr(), t.embed.data_ptr())
+
+    def admit(self, slot: int, req) -> None:
+        p = req.payload
+        t0 = cuda_time()
+        ids = p.input_ids if p.input_ids.is_cuda else p.input_ids.to(self.dec.dev)
+        self.dec.admit_fused(slot, ids, self.temperature, seed=p.seed)
+        t1 = cuda_time()
+        p.ttft, p.t_admitted = t1 - t0, t1
+        self.stats["admit_s"] += t1 - t0
+        self.hooks[slot] = p.hook
+
+    def set_block_size(self, slot: int, bs: int) -> None:
+        self.dec.set_block_size(slot, bs)
+
+    def park(self, slot: int) -> None:
+        self.dec.park(slot)
+
+    def ahead_pending(self) -> bool:
+        return self.dec._ahead
+
+    def _hook(self, r: int, blk: torch.Tensor, start: int, call: int) -> None:
+        h = self.hooks[r]
+        if h is not None:
+            h(blk[:, :max(1, self.dec.bs[r])], start, call)
+
+    def cycle(self, ahead_ok: bool) -> list:
+        d = self.dec
+        hook = self._hook if any(h is not None for h in self.hooks) else None
+        if d.graphs is not None:
+            # (no admission of this engine can move them; a larger decoder on the same models can)
+            if self._captured_state() != self.guard:
+                raise RuntimeError("a buffer the captured graphs read has moved (RoPE table, lm_head, embedding)")
+            out = d.cycle_graph(hook)
+            self.stats["replayed_cycles"] += 1
+        else:
+            out = d.cycle(hook, ahead_ok=ahead_ok and not self.use_graph)
+            if self.use_graph:   # the one capture of the engine's life: every length is read from the device records
+                d.capture()
+                self.stats["captures"] += 1
+                self.guard = self._captured_state()
+        return [None if o is None else (o[0], d.start[r], o[1]) for r, o in enumerate(out)]
+
+    def retire(self, slot: int, req) -> None:
+        d, p = self.dec, req.payload
+        ids = _trim(d.output_ids[slot:slot + 1], req.max_len, d.mask_id, self.stop_token_ids, req.n_in).clone()
+        n_out = ids.shape[1] - req.n_in
+        decode_s = cuda_time() - p.t_admitted
+        self.hooks[slot] = None
+        p.result = SimpleNamespace(output_ids=ids, num_input_tokens=req.n_in, num_output_tokens=n_out,
+                                   time_to_first_token=p.ttft, time_per_output_token=decode_s / max(1, n_out),
+                                   acceptance_lengths=req.taus, cycle_trace=[], profile_summary=None,
+                                   request_id=req.rid, slot=slot, admitted_step=req.admitted_step,
+                                   finished_step=req.finished_step)
+
+
+class BatchEngine:
+    """submit() queues requests, step() runs one group cycle and refills free slots, run() drains the queue.
+
+    graph: None = replay unless DFL_GRAPH=0 (the rule of run_decode); True / False force it.  With replay the first
+    cycle runs eagerly, the decoder is captured ONCE and every later cycle of the engine's life is a replay, across
+    admissions.  A precondition of the capture that does not hold raises here, nothing is swallowed."""
+
+    def __init__(self, model, target, *, slots: int = MAX_GROUP, max_rows: int, out_len: int, mask_token_id: int,
+                 block_size: int = 16, stop_token_ids=None, temperature: float = 0.0, sampler: str = "torch",
+                 graph: Optional[bool] = None):
+        if not 1 <= block_size <= 32:
+            raise ValueError("block_size is 1..32")
+        if block_size > BLOCK_ROWS:
+            raise NotImplementedError("the engine takes blocks of 1..16 rows (one tile per request); blocks of 17..32 rows "
+                                      "run through dflash_generate_batch")
+        if not 1 <= slots <= MAX_GROUP:
+            raise ValueError(f"slots is 1..{MAX_GROUP}")
+        sampled_on_host = temperature >= 1e-5 and sampler != "device"
+        if graph is None:
+            graph = os.environ.get("DFL_GRAPH", "1") != "0" and not sampled_on_host
+        elif graph and sampled_on_host:
+            raise ValueError("graph=True at T > 0 needs sampler='device': torch.multinomial on the caller's RNG stream "
+                             "cannot be captured")
+        self.use_graph = bool(graph)
+        self.dec = BatchedDecoder(model, target, slots, max_rows=max_rows, out_len=out_len, mask_token_id=mask_token_id,
+                                  stop_token_ids=stop_token_ids, temperature=temperature, sampler=sampler)
+        self.stats = dict(group_cycles=0, live_slot_cycles=0, admissions=0, replayed_cycles=0, admit_s=0.0, captures=0,
+                          graph=self.use_graph)
+        driver = _DecoderDriver(self.dec, self.stats, self.use_graph, float(temperature), stop_token_ids)
+        stop_always = stop_token_ids is not None and mask_token_id in stop_token_ids
+        self.loop = SlotLoop(driver, slots, block_size, may_stop=stop_token_ids is not None, stop_always=stop_always,
+                             stats=self.stats)
+        self._pending: list = []   # results of requests finished since the last run()
+
+    def submit(self, input_ids: torch.Tensor, max_new_tokens: int, *, seed: Optional[int] = None,
+               draft_token_hook: Optional[Callable] = None) -> int:
+        """Queue a request; returns its id (ids count up in submission order).  draft_token_hook(block_view, start,
+        call): `call` counts from 0 at the request's admission; the view has the cycle's block size."""
+        if input_ids.dim() != 2 or input_ids.shape[0] != 1:
+            raise ValueError("submit: input_ids must be a [1, P] tensor")
+        check_fit(input_ids.shape[1], int(max_new_tokens), self.dec.max_rows, self.dec.out_len)
+        req = self.loop.submit(input_ids.shape[1], int(max_new_tokens),
+                               SimpleNamespace(input_ids=input_ids, seed=seed, hook=draft_token_hook, result=None,
+                                               ttft=0.0, t_admitted=0.0))
+        return req.rid
+
+    @torch.inference_mode()
+    def step(self) -> list:
+        """One group cycle; the result namespaces of the requests that finished on it."""
+        done = [r.payload.result for r in self.loop.step()]
+        self._pending.extend(done)
+        return done
+
+    @torch.inference_mode()
+    def run(self) -> list:
+        """Drain the queue.  Returns the results of every request finished since the last run(), in submission order."""
+        while not self.loop.idle:
+            self.step()
+        out, self._pending = sorted(self._pending, key=lambda r: r.request_id), []
+        return out
+
+
+@torch.inference_mode()
+def dflash_generate_stream(model, target, input_ids: Sequence[torch.Tensor], mask_token_id: int,
+                           max_new_tokens: Union[int, Sequence[int]], block_size: int, stop_token_ids,
+                           temperature: float = 0.0, *, slots: int = MAX_GROUP, draft_token_hook: Optional[Callable] = None,
+                           sampler: str = "torch", seed=None) -> list:
+    """`dflash_generate_batch` with slot refill: one namespace per prompt with the fields of benchmark.py:242-251, each
+    request emitting what its own `dflash_generate` run emits.  max_new_tokens: one int or one per prompt.
+    draft_token_hook(request_index, block_view, start, call).  seed as in dflash_generate_batch (an int s gives prompt i
+    the seed s + i).  time_to_first_token is the request's own admission; time_per_output_token its own decode wall
+    time, admission to last token, over its tokens."""
+    n = len(input_ids)
+    mnt = [int(max_new_tokens)] * n if isinstance(max_new_tokens, int) else [int(x) for x in max_new_tokens]
+    if len(mnt) != n:
+        raise ValueError("one max_new_tokens per prompt")
+    if block_size > BLOCK_ROWS:
+        raise NotImplementedError("dflash_generate_stream takes blocks of 1..16 rows; 17..32-row blocks run through "
+                                  "dflash_generate_batch")
+    seeds = _prompt_seeds(sampler, seed, n, temperature >= 1e-5)
+    need = max([p.shape[1] + k for p, k in zip(input_ids, mnt)] + [1])
+    eng = BatchEngine(model, target, slots=max(1, min(slots, max(n, 1))), max_rows=need + 3 * BLOCK_ROWS,
+                      out_len=need + BLOCK_ROWS, mask_token_id=mask_token_id, block_size=block_size,
+                      stop_token_ids=stop_token_ids, temperature=temperature, sampler=sampler)
+    for i, p in enumerate(input_ids):
+        hook = (lambda blk, start, call, i=i: draft_token_hook(i, blk, start, call)) if draft_token_hook else None
+        eng.submit(p, mnt[i], seed=seeds[i], draft_token_hook=hook)
+    return eng.run()

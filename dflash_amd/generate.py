@@ -16,6 +16,7 @@ target's hidden states and roll its cache back.
 """
 from __future__ import annotations
 
+import gc
 import os
 import time
 from types import SimpleNamespace
@@ -46,12 +47,22 @@ def capture_graph(fn) -> "torch.cuda.CUDAGraph":
     cur = torch.cuda.current_stream()
     side = torch.cuda.Stream()
     side.wait_stream(cur)
-    with torch.cuda.stream(side):
-        g.capture_begin()
-        try:
-            fn()
-        finally:
-            g.capture_end()
+    # No garbage collection while the stream captures: a collection that frees an unreachable hipGraph (a dropped
+    # session or decoder held in a reference cycle) destroys it inside the capture, which HIP refuses ("operation not
+    # permitted when stream is capturing") and torch turns into an abort.  torch.cuda.graph() collects before it begins
+    # for the same reason; pausing the collector for the ~300 launches of a capture needs no collection here.
+    gc_was_on = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.stream(side):
+            g.capture_begin()
+            try:
+                fn()
+            finally:
+                g.capture_end()
+    finally:
+        if gc_was_on:
+            gc.enable()
     cur.wait_stream(side)
     return g
 

@@ -782,6 +782,28 @@ def accept_commit_batch(block: torch.Tensor, posterior: torch.Tensor, R: int, ou
         int(rearm_mask_id) if rearm_mask_id is not None else 0, _stream()), "dfl_accept_commit_batch")
 
 
+def admit_slot(r: int, prompt_ids: torch.Tensor, first_token: torch.Tensor, output_ids: torch.Tensor, block: torch.Tensor,
+               post: torch.Tensor, result: torch.Tensor, tail_rows: torch.Tensor, taps: torch.Tensor, dyn_d: torch.Tensor,
+               dyn_t: torch.Tensor, bs: int, mask_id: int, seeds: Optional[torch.Tensor] = None, seed: int = 0) -> None:
+    """Re-arm request slot r of a ragged batch in one launch (dfl_admit_slot): prompt_ids int64 [P], first_token int64 [1]
+    (device), output_ids int64 [slots, n], block / post int64 [slots, w], result int32 [slots, 4], tail_rows bf16
+    [n_tail <= 16, fc_in] (the prompt's last tapped rows), taps bf16 [tiles, 16, fc_in], dyn_d / dyn_t int32 [slots, 8],
+    seeds int64 [slots] or None (the slot's seed is left alone)."""
+    n_slots = output_ids.shape[0]
+    assert prompt_ids.dim() == 1 and first_token.numel() == 1 and output_ids.dim() == 2 and tail_rows.dim() == 2
+    assert block.shape == post.shape and block.shape[0] >= n_slots and result.shape[0] >= n_slots and result.shape[1] == 4
+    assert taps.dim() == 3 and taps.shape[0] >= n_slots and taps.shape[1] == 16 and taps.shape[2] == tail_rows.shape[1]
+    assert dyn_d.shape[0] >= n_slots and dyn_t.shape[0] >= n_slots and dyn_d.shape[1] == 8 and dyn_t.shape[1] == 8
+    assert tail_rows.dtype == BF16 and tail_rows.is_cuda and tail_rows.stride(1) == 1
+    assert seeds is None or seeds.numel() >= n_slots
+    check(lib().dfl_admit_slot(
+        r, n_slots, _p(prompt_ids, I64, "prompt_ids"), prompt_ids.shape[0], _p(first_token, I64, "first_token"),
+        _p(output_ids, I64, "output_ids"), output_ids.stride(0), output_ids.shape[1], _p(block, I64, "block"),
+        _p(post, I64, "post"), block.shape[1], _p(result, I32, "result"), tail_rows.data_ptr(), tail_rows.stride(0),
+        tail_rows.shape[0], _p(taps, BF16, "taps"), taps.shape[2], _p(dyn_d, I32, "dyn_d"), _p(dyn_t, I32, "dyn_t"), bs,
+        _p(seeds, I64, "seeds"), int(seed), int(mask_id), _stream()), "dfl_admit_slot")
+
+
 # ---- target prefill (csrc/prefill.hip)
 def prefill_rows_padded(P: int) -> int:
     return lib().dfl_prefill_rows_padded(P)

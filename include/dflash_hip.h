@@ -615,6 +615,22 @@ int dfl_accept_commit_batch_t(const int64_t *block_ids, int64_t blk_stride, cons
                               int64_t *next_block, int64_t mask_id, int tiles_per_req, int32_t *dyn_d_tiles,
                               int32_t *dyn_t_tiles, void *stream);
 
+/* Slot admission of the ragged batch: ONE launch re-arms request slot r (0 <= r < n_slots) for a request whose prompt
+ * has just been prefilled, from device-resident inputs only (nothing is read back, nothing copied from the host):
+ *   output_ids[r][0..P) <- prompt_ids, [P] <- *first_token (a device int64), (P, out_len) <- mask_id
+ *   block[r] <- [*first_token, mask_id x (blk_w - 1)];  post[r], result[r] <- 0   (block / post: [n_slots][blk_w])
+ *   taps tile r (16 rows of fc_in bf16 at taps + r * 16 * fc_in) <- tail_rows[0..n_tail) (row stride ld_tail), rows
+ *     n_tail..15 zero: the prompt's last n_tail = min(16, P) tapped rows, the first cycle's context tile
+ *   dyn_d[r] <- {P - n_tail, n_tail, bs, P - n_tail, P, 0, 0, 0};  dyn_t[r] <- {P, 0, bs, P, P, 0, 0, 0}
+ *   seeds[r] <- seed  (seeds may be NULL: the slot's seed is left alone)
+ * Rows of the slot's KV caches past these lengths keep whatever the slot's previous request left: no launch reads them
+ * before the cycle that rewrites them.  fc_in % 8 == 0, rows 16-byte aligned.  DFL_EINVAL: null pointer, r outside
+ * 0..n_slots-1, P < 1 or P + 1 > out_len, n_tail outside 0..min(16, P), bs outside 0..blk_w. */
+int dfl_admit_slot(int r, int n_slots, const int64_t *prompt_ids, int P, const int64_t *first_token, int64_t *output_ids,
+                   int64_t out_stride, int64_t out_len, int64_t *block, int64_t *post, int blk_w, int32_t *result,
+                   const void *tail_rows, int64_t ld_tail, int n_tail, void *taps, int fc_in, int32_t *dyn_d,
+                   int32_t *dyn_t, int bs, int64_t *seeds, int64_t seed, int64_t mask_id, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
