@@ -16,7 +16,11 @@ LIB = os.path.join(LIBDIR, "libdflash_hip.so")
 SOURCES = ["dfl_common.hip", "gemm_skinny.hip", "gemm_batch.hip", "rows.hip", "attn_block.hip", "attn_head.hip", "accept.hip", "candidates.hip", "moe.hip", "prefill.hip"]
 HEADERS = [os.path.join(CSRC, "dfl_common.h"), os.path.join(CSRC, "dfl_rng.h"), os.path.join(CSRC, "gemm_rows.h"), os.path.join(CSRC, "gemm_ring.h"), os.path.join(CSRC, "moe_route.h"),
            os.path.join(HERE, "..", "include", "dflash_hip.h")]
-FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
+# kernarg preload: gfx950 delivers up to 14 leading scalar / pointer kernel arguments in SGPRs at wave start (the hot
+# kernels keep what their first memory request needs there: csrc/gemm_skinny.hip, "the head of the launch arguments").
+# The diagnostic builds under scripts/ compile with these flags too, so a stamped build measures the product's code.
+FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",
+         "-mllvm", "-amdgpu-kernarg-preload-count=14"]
 
 
 def _hipcc() -> str:

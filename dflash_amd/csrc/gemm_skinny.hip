@@ -27,7 +27,7 @@
 namespace {
 
 struct GemmArgs {
-  // what the first weight request needs comes first: one s_load of the head of the kernel-argument block
+  // (the kernels take the fields that their first requests need a second time, as flat leading arguments: GemmHead below)
   const bf16x8 *wp;  // packed weights [ntiles][KS][64]
   int KS;      // K / 32
   int ntiles;  // N / 16
@@ -37,6 +37,7 @@ struct GemmArgs {
   // 8-column halves, one per workgroup b < nhalf (tile ntiles + b/2, half b&1), as that workgroup's LAST item:
   // 384 tiles (qkv of an 8B model) are 1.5 tiles for each of 256 workgroups instead of 2 for each of 192
   int nhalf;
+  int gx;  // gridDim.x, as an argument: the built-in comes from the hidden arguments at the far end of the block
   const int32_t *dyn;
   RowSrc src[2];
   // EPI_F32
@@ -76,6 +77,95 @@ struct SampleArgs {
   const int32_t *pos_dyn;
   int pos_word, pos_base, pos_add;
 };
+
+// ---- the head of the launch arguments ---------------------------------------------------------------------------------
+// gfx950 delivers the first 14 dwords of the kernel-argument block in SGPRs at wave start (kernarg preload, build.py:
+// -amdgpu-kernarg-preload-count), but only leading scalar and pointer parameters, never a struct passed by value.  So the
+// kernels take, in FRONT of GemmArgs, a flat copy of everything that the instructions up to item 0's weight request
+// read (judged from the ISA: the row requests of src[0] come first, and they are in the same order-of-issue chain), and
+// overwrite the struct's fields with it: gemm_body then finds those values in registers and the first vector address
+// waits for no cold fetch of the argument block.  14 dwords are five pointers and four words, so the small fields share
+// one 64-bit word (HeadBits); gemm_head() builds the head from the finished GemmArgs and refuses a launch whose values
+// do not fit, so the two cannot drift.  src[1] (MT = 2) stays in the struct.
+struct HeadBits {
+  uint64_t KS : 17, nfr : 4, mode : 2, valid_word1 : 6 /* valid_word + 1 */, nrows_word1 : 6 /* nrows_word + 1 */, gx : 9,
+      nhalf : 9, nch_nss : 11 /* CHUNKED: nch; otherwise nss of a normalised src[0] */;
+};
+static_assert(sizeof(HeadBits) == 8, "HeadBits is one 64-bit kernel argument");
+struct GemmHead {
+  const bf16x8 *wp;
+  const void *x;  // src[0]: frag (mode 0) or rows (mode 1/2)
+  const float *ss;
+  const bf16_t *nw;
+  const int32_t *dyn;
+  uint64_t bits;
+  int ld, ntiles;
+};
+#define GEMM_HEAD_DWORDS 14  // tests/test_launch_args.py: the preload length the compiler must report for these kernels
+static_assert(sizeof(GemmHead) == 4 * GEMM_HEAD_DWORDS, "the head is what the hardware preloads: at most 14 dwords, no padding");
+#define GEMM_HEAD_PARAMS \
+  const bf16x8 *wp, const void *x, const float *ss, const bf16_t *nw, const int32_t *dyn, uint64_t bits, int ld, int ntiles
+#define GEMM_HEAD_NAMES wp, x, ss, nw, dyn, bits, ld, ntiles
+#define GEMM_HEAD_OF(h) (h).wp, (h).x, (h).ss, (h).nw, (h).dyn, (h).bits, (h).ld, (h).ntiles
+
+template <bool CHUNKED, bool NORM>
+__device__ __forceinline__ GemmArgs with_head(GemmArgs a, GEMM_HEAD_PARAMS) {
+  const HeadBits b = __builtin_bit_cast(HeadBits, bits);
+  a.wp = wp;
+  a.dyn = dyn;
+  a.ntiles = ntiles;
+  a.KS = (int)b.KS;
+  a.nfr = (int)b.nfr;
+  a.nhalf = (int)b.nhalf;
+  a.gx = (int)b.gx;
+  a.nch = CHUNKED ? (int)b.nch_nss : 1;
+  a.nrows_word = (int)b.nrows_word1 - 1;
+  RowSrc &s = a.src[0];
+  s.frag = reinterpret_cast<const bf16x8 *>(x);
+  s.rows = reinterpret_cast<const bf16_t *>(x);
+  s.ld = ld;
+  s.ss = ss;
+  s.nw = nw;
+  s.mode = (int)b.mode;
+  s.valid_word = (int)b.valid_word1 - 1;
+  if (NORM) s.nss = (int)b.nch_nss;
+  return a;
+}
+
+// host: the head of a finished GemmArgs (gx included)
+template <bool CHUNKED>
+bool gemm_head(GemmHead &h, const GemmArgs &a) {
+  const RowSrc &s = a.src[0];
+  HeadBits b{};
+  b.KS = a.KS;
+  b.nfr = a.nfr;
+  b.mode = s.mode;
+  b.valid_word1 = s.valid_word < 0 ? 0 : s.valid_word + 1;
+  b.nrows_word1 = a.nrows_word < 0 ? 0 : a.nrows_word + 1;
+  b.gx = a.gx;
+  b.nhalf = a.nhalf;
+  const int nch_nss = CHUNKED ? a.nch : (s.mode == 2 ? s.nss : 0);
+  b.nch_nss = nch_nss;
+  const int64_t ld = s.mode == 0 ? 0 : s.ld;  // (a fragment source has no row stride)
+  const bool fits = (int)b.KS == a.KS && (int)b.nfr == a.nfr && (int)b.mode == s.mode && (int)b.gx == a.gx &&
+                    (int)b.nhalf == a.nhalf && (int)b.nch_nss == nch_nss && (CHUNKED || a.nch == 1) && ld == (int)ld &&
+                    (int)b.valid_word1 == (s.valid_word < 0 ? 0 : s.valid_word + 1) &&
+                    (int)b.nrows_word1 == (a.nrows_word < 0 ? 0 : a.nrows_word + 1);
+  if (!fits) {
+    dfl_set_error("skinny GEMM: launch arguments outside the preloaded head's fields (K=%d, grid %d, ld=%lld)", a.KS * 32, a.gx,
+                  (long long)s.ld);
+    return false;
+  }
+  h.wp = a.wp;
+  h.x = s.mode == 0 ? (const void *)s.frag : (const void *)s.rows;
+  h.ss = s.ss;
+  h.nw = s.nw;
+  h.dyn = a.dyn;
+  h.bits = __builtin_bit_cast(uint64_t, b);
+  h.ld = (int)ld;
+  h.ntiles = a.ntiles;
+  return true;
+}
 
 #ifdef DFL_GEMM_STAMPS  // diagnostic build only (scripts/dbg_gemm_stamps.py): 100 MHz wall stamps of workgroup 0,
 // and the start / first-item / end stamps of EVERY workgroup (is the tail a few late workgroups or all of them?)
@@ -138,7 +228,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &a, const SampleArgs &s
   // SILU: the packed weight interleaves (gate tile p, up tile p) and the sequence walks
   // pairs p = bx, bx+G, ... as gate,up,gate,up: the finishing thread meets a pair's two
   // sums in consecutive positions.
-  const int stride = gridDim.x;
+  const int stride = a.gx;
   constexpr bool SILU = EPI == EPI_SILU || EPI == EPI_SILU_E;
   constexpr bool moe = EPI == EPI_SILU_E;  // the tile sequence comes from the active-expert list (dependent scalar loads)
   const int nwhole = (!SILU && (int)blockIdx.x < a.ntiles) ? (a.ntiles - 1 - (int)blockIdx.x) / stride + 1 : 0;  // whole tiles of this workgroup
@@ -316,10 +406,11 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &a, const SampleArgs &s
   // with the vector loads — but through the same L2: requested behind the first weight burst they came back 5 - 9 us
   // later (the "rstd prologue" of round 2 was mostly this wait).  Asked for before any vector load they cost nothing.
   read_nv();
-  if (EPI == EPI_ARGMAX || EPI == EPI_SAMPLE) {
-    arg_rows = a.nrows;
-    if (a.dyn && a.nrows_word >= 0) arg_rows = a.dyn[a.nrows_word] - a.row0;
-  }
+  // (only the REQUEST here: row0 / nrows are not in the head of the launch arguments, and arithmetic on the word would
+  // be a wait in front of the first vector request; arg_rows is settled below, behind item 0's weight request)
+  int arg_word = 0;
+  const bool arg_dyn = (EPI == EPI_ARGMAX || EPI == EPI_SAMPLE) && a.dyn && a.nrows_word >= 0;
+  if (arg_dyn) arg_word = a.dyn[a.nrows_word];
   if (EPI == EPI_SAMPLE) {
     const int base = sa.pos_dyn ? sa.pos_dyn[sa.pos_word] : sa.pos_base;
     pos_row0 = base + sa.pos_add;
@@ -438,6 +529,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &a, const SampleArgs &s
     GSTAMP(2);
   }
 
+  if (EPI == EPI_ARGMAX || EPI == EPI_SAMPLE) arg_rows = arg_dyn ? arg_word - a.row0 : a.nrows;
   GSTAMP(3);
   if (nitems > 0) {
     int j = 0, c = 0;  // current item
@@ -491,27 +583,31 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &a, const SampleArgs &s
 }
 
 template <int MT, bool CHUNKED, int EPI, bool NORM>
-__global__ __launch_bounds__(1024) void k_gemm(GemmArgs a) {
-  gemm_body<MT, CHUNKED, EPI, NORM>(a, SampleArgs{});
+__global__ __launch_bounds__(1024) void k_gemm(GEMM_HEAD_PARAMS, GemmArgs rest) {
+  gemm_body<MT, CHUNKED, EPI, NORM>(with_head<CHUNKED, NORM>(rest, GEMM_HEAD_NAMES), SampleArgs{});
 }
 
 template <bool NORM>
-__global__ __launch_bounds__(1024) void k_gemm_s(GemmArgs a, SampleArgs sa) {
-  gemm_body<1, false, EPI_SAMPLE, NORM>(a, sa);
+__global__ __launch_bounds__(1024) void k_gemm_s(GEMM_HEAD_PARAMS, GemmArgs rest, SampleArgs sa) {
+  gemm_body<1, false, EPI_SAMPLE, NORM>(with_head<false, NORM>(rest, GEMM_HEAD_NAMES), sa);
 }
 
 // the instantiation for this launch's row sources (a normalised source needs the NORM kernels)
 template <int MT, bool CHUNKED, int EPI>
-void launch_gemm(const GemmArgs &a, dim3 grid, hipStream_t stream) {
+bool launch_gemm(GemmArgs &a, dim3 grid, hipStream_t stream) {
   bool norm = false;
   for (int mt = 0; mt < MT; ++mt) norm |= a.src[mt].mode == 2;
+  a.gx = (int)grid.x;
+  GemmHead h;
+  if (!gemm_head<CHUNKED>(h, a)) return false;
   if constexpr (!CHUNKED) {  // (the chunked form takes no normalised source: its callers reject one)
     if (norm) {
-      hipLaunchKernelGGL((k_gemm<MT, false, EPI, true>), grid, dim3(1024), 0, stream, a);
-      return;
+      hipLaunchKernelGGL((k_gemm<MT, false, EPI, true>), grid, dim3(1024), 0, stream, GEMM_HEAD_OF(h), a);
+      return true;
     }
   }
-  hipLaunchKernelGGL((k_gemm<MT, CHUNKED, EPI, false>), grid, dim3(1024), 0, stream, a);
+  hipLaunchKernelGGL((k_gemm<MT, CHUNKED, EPI, false>), grid, dim3(1024), 0, stream, GEMM_HEAD_OF(h), a);
+  return true;
 }
 
 // Cross-workgroup finish of the fused argmax: one wave per row.  margin_out (optional):
@@ -683,10 +779,9 @@ extern "C" int dfl_gemm_f32(const void *wp, const dfl_rows *x0, const dfl_rows *
   int gx1 = 0;
   if (ksplit == 1) plan_tiles(a, N / 16, true, gx1);
   dim3 grid(ksplit == 1 ? gx1 : grid_x_for(a.ntiles, ksplit), ksplit);
-  if (mt == 1)
-    launch_gemm<1, false, EPI_F32>(a, grid, (hipStream_t)stream);
-  else
-    launch_gemm<2, false, EPI_F32>(a, grid, (hipStream_t)stream);
+  const bool ok = mt == 1 ? launch_gemm<1, false, EPI_F32>(a, grid, (hipStream_t)stream)
+                          : launch_gemm<2, false, EPI_F32>(a, grid, (hipStream_t)stream);
+  if (!ok) return DFL_EINVAL;
   DFL_CHECK_LAUNCH("dfl_gemm_f32");
   return DFL_OK;
 }
@@ -706,7 +801,7 @@ extern "C" int dfl_gemm_silu_mul(const void *wp_gateup, const dfl_rows *x, int I
   a.nfr = (KS + 15) / 16;
   a.nch = 1;
   a.act = (bf16_t *)act_frag;
-  launch_gemm<1, false, EPI_SILU>(a, dim3(grid_x_for(I / 16), 1), (hipStream_t)stream);
+  if (!launch_gemm<1, false, EPI_SILU>(a, dim3(grid_x_for(I / 16), 1), (hipStream_t)stream)) return DFL_EINVAL;
   DFL_CHECK_LAUNCH("dfl_gemm_silu_mul");
   return DFL_OK;
 }
@@ -740,7 +835,7 @@ extern "C" int dfl_gemm_silu_mul_experts(const void *wp_gateup, int64_t wp_exper
   a.elist = list;
   a.n_active = n_active;
   a.npp = I / 16;
-  launch_gemm<1, false, EPI_SILU_E>(a, dim3(256, 1), (hipStream_t)stream);
+  if (!launch_gemm<1, false, EPI_SILU_E>(a, dim3(256, 1), (hipStream_t)stream)) return DFL_EINVAL;
   DFL_CHECK_LAUNCH("dfl_gemm_silu_mul_experts");
   return DFL_OK;
 }
@@ -777,12 +872,15 @@ int gemm_argmax_impl(const void *wp, const dfl_rows *x, int V, int K, int row0, 
   plan_tiles(a, V / 16, true, gx);
   if (ev0) (void)hipEventRecord(ev0, (hipStream_t)stream);
   if (smp) {
+    a.gx = gx;
+    GemmHead h;
+    if (!gemm_head<false>(h, a)) return DFL_EINVAL;
     if (a.src[0].mode == 2)
-      hipLaunchKernelGGL(k_gemm_s<true>, dim3(gx, 1), dim3(1024), 0, (hipStream_t)stream, a, *smp);
+      hipLaunchKernelGGL(k_gemm_s<true>, dim3(gx, 1), dim3(1024), 0, (hipStream_t)stream, GEMM_HEAD_OF(h), a, *smp);
     else
-      hipLaunchKernelGGL(k_gemm_s<false>, dim3(gx, 1), dim3(1024), 0, (hipStream_t)stream, a, *smp);
+      hipLaunchKernelGGL(k_gemm_s<false>, dim3(gx, 1), dim3(1024), 0, (hipStream_t)stream, GEMM_HEAD_OF(h), a, *smp);
   } else {
-    launch_gemm<1, false, EPI_ARGMAX>(a, dim3(gx, 1), (hipStream_t)stream);
+    if (!launch_gemm<1, false, EPI_ARGMAX>(a, dim3(gx, 1), (hipStream_t)stream)) return DFL_EINVAL;
   }
   if (ev1) (void)hipEventRecord(ev1, (hipStream_t)stream);
   hipLaunchKernelGGL(k_argmax_finish, dim3(16), dim3(64), 0, (hipStream_t)stream, a.best_val, a.best_idx, a.best2_val, gx,
@@ -848,12 +946,12 @@ extern "C" int dfl_gemm_resid(const void *wp, const dfl_rows *x, int N, int K, v
   if (KS <= 16 * 8) {  // the whole K fits the 16 waves x 8 steps of one pass
     a.nfr = (KS + 15) / 16;
     a.nch = 1;
-    launch_gemm<1, false, EPI_RESID>(a, grid, (hipStream_t)stream);
+    if (!launch_gemm<1, false, EPI_RESID>(a, grid, (hipStream_t)stream)) return DFL_EINVAL;
   } else {  // walk K in chunks of 16 waves x 4 steps inside the workgroup
     DFL_REQUIRE(a.src[0].mode != 2, "dfl_gemm_resid: a normalised source needs K <= 4096");
     a.nfr = 4;
     a.nch = (KS + 63) / 64;  // 64 k-steps per chunk: 16 waves x 4
-    launch_gemm<1, true, EPI_RESID>(a, grid, (hipStream_t)stream);
+    if (!launch_gemm<1, true, EPI_RESID>(a, grid, (hipStream_t)stream)) return DFL_EINVAL;
   }
   DFL_CHECK_LAUNCH("dfl_gemm_resid");
   return DFL_OK;

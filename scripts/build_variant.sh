@@ -3,9 +3,10 @@
 #   scripts/build_variant.sh <out dir> [-DFLAG=..]...
 out=$1; shift
 mkdir -p "$out/obj"
+FLAGS=$(cd "$(dirname "$0")/.." && python3 -c "from dflash_amd.build import FLAGS; print(' '.join(FLAGS))")  # the product's flags
 cd "$(dirname "$0")/../dflash_amd/csrc"
 for f in *.hip; do
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wno-unused-function "$@" -c $f -o "$OLDPWD/$out/obj/${f%.hip}.o" &
+  /opt/rocm/bin/hipcc $FLAGS "$@" -c $f -o "$OLDPWD/$out/obj/${f%.hip}.o" &
 done
 wait
 cd "$OLDPWD"

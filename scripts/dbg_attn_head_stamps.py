@@ -9,6 +9,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from dflash_amd.build import FLAGS, _hipcc  # the product's compiler flags: the stamped build measures the product's code
 import torch
 
 out = os.path.join(ROOT, "gpurun_out", "dbg")
@@ -16,7 +17,7 @@ os.makedirs(out, exist_ok=True)
 so = os.path.join(out, "libdbg_head.so")
 src = [os.path.join(ROOT, "dflash_amd", "csrc", f) for f in ("attn_head.hip", "dfl_common.hip")]
 flags = [a for a in sys.argv[1:] if a.startswith("-D")]
-subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-shared", "-DDFL_ATTN_STAMPS",
+subprocess.run([_hipcc(), *FLAGS, "-shared", "-DDFL_ATTN_STAMPS",
                 *flags, "-o", so, *src], check=True)
 from dflash_amd import _lib, ops
 from dflash_amd.model import _rope_tables

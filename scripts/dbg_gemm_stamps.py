@@ -7,14 +7,17 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from dflash_amd.build import FLAGS, _hipcc  # the product's compiler flags: the stamped build measures the product's code
 import torch
 
 out = os.path.join(ROOT, "gpurun_out", "dbg")
 os.makedirs(out, exist_ok=True)
 so = os.path.join(out, "libdbg_gemm.so")
 src = [os.path.join(ROOT, "dflash_amd", "csrc", f) for f in ("gemm_skinny.hip", "dfl_common.hip", "rows.hip")]
-subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-shared", "-DDFL_GEMM_STAMPS",
-                "-o", so, *src], check=True)
+if os.environ.get("DFL_DBG_SO"):  # a stamped build made beforehand (another revision's, for a same-box A/B)
+    so = os.environ["DFL_DBG_SO"]
+else:
+    subprocess.run([_hipcc(), *FLAGS, "-shared", "-DDFL_GEMM_STAMPS", "-o", so, *src], check=True)
 from dflash_amd import _lib, ops
 dbg = C.CDLL(so)
 for n in ("dfl_gemm_f32", "dfl_gemm_resid", "dfl_gemm_silu_mul", "dfl_set_dyn"):

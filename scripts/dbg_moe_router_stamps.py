@@ -7,13 +7,14 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from dflash_amd.build import FLAGS, _hipcc  # the product's compiler flags: the stamped build measures the product's code
 import torch
 
 out = os.path.join(ROOT, "gpurun_out", "dbg")
 os.makedirs(out, exist_ok=True)
 so = os.path.join(out, "libdbg_moe.so")
 src = [os.path.join(ROOT, "dflash_amd", "csrc", f) for f in ("moe.hip", "dfl_common.hip")]
-subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-shared", "-DDFL_MOE_STAMPS",
+subprocess.run([_hipcc(), *FLAGS, "-shared", "-DDFL_MOE_STAMPS",
                 "-I", os.path.join(ROOT, "include"), "-o", so, *src], check=True)
 from dflash_amd import _lib, ops
 dbg = C.CDLL(so)
