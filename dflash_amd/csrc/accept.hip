@@ -204,7 +204,7 @@ __global__ __launch_bounds__(64) void k_accept_commit_b(const int64_t *block_ids
   int64_t tok = -1;
   if (i <= acc)
     tok = block_ids[i];
-  else if (i == acc + 1)
+  else if (i == acc + 1 && bs > 0)  // (an idle request has acc = -1: nothing of its rows is read)
     tok = posterior[acc];
   if (bs > 0 && i <= acc + 1 && start + i < output_len) output_ids[start + i] = tok;
   bool hit = false;

@@ -760,25 +760,38 @@ def attn_fused_batch(*, qkv, nsplit, split_stride, ld, q_col, k_col, v_col, R, n
 
 def accept_commit_batch(block: torch.Tensor, posterior: torch.Tensor, R: int, output_ids: torch.Tensor, dyn_d, dyn_t,
                         stop_ids, result: torch.Tensor, rearm_mask_id: Optional[int] = None, tiles_per_req: int = 1,
-                        dyn_d_tiles=None, dyn_t_tiles=None) -> None:
+                        dyn_d_tiles=None, dyn_t_tiles=None, next_block: Optional[torch.Tensor] = None,
+                        output_len: Optional[int] = None) -> None:
     """block/posterior int64 [requests, 16 * tiles_per_req]; output_ids int64 [requests, n]; result int32 [requests, 4];
-    tiles_per_req = 2: the per-tile records dyn_d_tiles / dyn_t_tiles are kept as well (dfl_accept_commit_batch_t)."""
+    tiles_per_req = 2: the per-tile records dyn_d_tiles / dyn_t_tiles are kept as well (dfl_accept_commit_batch_t).
+    rearm_mask_id: the next block is re-armed, in `block` itself or in next_block (same row stride as block).
+    output_len: ids per request the kernel may write (default: the whole row of output_ids)."""
     assert block.dim() == 2 and posterior.dim() == 2 and output_ids.dim() == 2
     n_stop = 0 if stop_ids is None else stop_ids.numel()
+    out_len = output_ids.shape[1] if output_len is None else int(output_len)
+    assert 0 <= out_len <= output_ids.shape[1]
+    nb = None
+    if rearm_mask_id is not None:
+        nb = block.data_ptr()
+        if next_block is not None:
+            assert next_block.dim() == 2 and next_block.stride(0) == block.stride(0) and next_block.shape[0] >= R
+            nb = _p(next_block, I64, "next_block")
+    else:
+        assert next_block is None, "next_block needs rearm_mask_id"
     if tiles_per_req != 1:
         check(lib().dfl_accept_commit_batch_t(
             _p(block, I64, "block"), block.stride(0), _p(posterior, I64, "posterior"), posterior.stride(0), R,
-            _p(output_ids, I64, "output_ids"), output_ids.stride(0), output_ids.shape[1], _p(dyn_d, I32, "dyn_d"),
+            _p(output_ids, I64, "output_ids"), output_ids.stride(0), out_len, _p(dyn_d, I32, "dyn_d"),
             _p(dyn_t, I32, "dyn_t"), _p(stop_ids, I64, "stop_ids") if n_stop else None, n_stop,
-            _p(result, I32, "result"), block.data_ptr() if rearm_mask_id is not None else None,
+            _p(result, I32, "result"), nb,
             int(rearm_mask_id) if rearm_mask_id is not None else 0, tiles_per_req, _p(dyn_d_tiles, I32, "dyn_d_tiles"),
             _p(dyn_t_tiles, I32, "dyn_t_tiles"), _stream()), "dfl_accept_commit_batch_t")
         return
     check(lib().dfl_accept_commit_batch(
         _p(block, I64, "block"), block.stride(0), _p(posterior, I64, "posterior"), posterior.stride(0), R,
-        _p(output_ids, I64, "output_ids"), output_ids.stride(0), output_ids.shape[1], _p(dyn_d, I32, "dyn_d"),
+        _p(output_ids, I64, "output_ids"), output_ids.stride(0), out_len, _p(dyn_d, I32, "dyn_d"),
         _p(dyn_t, I32, "dyn_t"), _p(stop_ids, I64, "stop_ids") if n_stop else None, n_stop,
-        _p(result, I32, "result"), block.data_ptr() if rearm_mask_id is not None else None,
+        _p(result, I32, "result"), nb,
         int(rearm_mask_id) if rearm_mask_id is not None else 0, _stream()), "dfl_accept_commit_batch")
 
 

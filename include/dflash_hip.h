@@ -92,12 +92,12 @@ int dfl_pack_weight_gateup(const void *gate, const void *up, void *wp, int I, in
 
 /* ---- per-cycle kernels ---- */
 
-/* dyn <- {S, tau, bs, pos0, start=pos0+tau, stop=0, cycle=0}. */
+/* dyn <- {S, tau, bs, pos0, start=pos0+tau, stop=0, cycle=0, 0}: all DFL_DYN_WORDS words, the spare one cleared. */
 int dfl_set_dyn(int32_t *dyn, int S, int tau, int bs, int pos0, void *stream);
 /* Blocks of 17..32 rows (results.md:11-16 sweeps 20 and 24; benchmark_dynamic_schedule.py:44-51 takes any
  * candidate >= 2) run as TWO 16-row tiles: every GEMM / embed launch is issued once per tile on rows 16 t ..
  * with the tile's own record.  dyn holds 2 x DFL_DYN_WORDS ints; record t gets
- * {S, clamp(tau - 16 t, 0, 16), clamp(bs - 16 t, 0, 16), pos0, start, 0, 0}. */
+ * {S, clamp(tau - 16 t, 0, 16), clamp(bs - 16 t, 0, 16), pos0, start = pos0 + tau (unclamped), 0, 0, 0}. */
 int dfl_set_dyn2(int32_t *dyn, int S, int tau, int bs, int pos0, void *stream);
 
 /* rows x K bf16 (row stride ldx elements) -> frag16; rows beyond n_valid zeroed.
@@ -596,9 +596,11 @@ int dfl_attn_fused_batch(const float *qkv, int nsplit, int64_t split_stride, int
 
 /* dfl_accept_commit for R requests, one wavefront each (model/dflash.py:258-268 per request).
  * bs is read from dyn_d.  Updates dyn_d (draft form: S <- start, tau <- acc+1, pos0 <- start,
- * start <- start+acc+1) and dyn_t (block form: S = pos0 = start = new start, tau = 0), the
- * latter read by the target verify and by the draft's block stage of the next cycle.
- * result int32 [R][4] = {acc, new_start, stop, cycle}.  A request with dyn_d bs == 0 is idle.
+ * start <- start+acc+1) and dyn_t (block form: S = pos0 = start = new start, tau = 0, bs / stop / cycle
+ * copied from dyn_d), the latter read by the target verify and by the draft's block stage of the next cycle;
+ * the spare word of both is left alone.
+ * result int32 [R][4] = {acc, new_start, stop, cycle}.  A request with dyn_d bs == 0 is idle: none of its rows
+ * is read and no word of its slot (ids, records, result, block) is written.
  * next_block (optional, may alias block_ids; same stride): re-armed for the next cycle as
  * [bonus token, mask_id x 15] = output_ids[new start .. +16) (model/dflash.py:235). */
 int dfl_accept_commit_batch(const int64_t *block_ids, int64_t blk_stride, const int64_t *posterior,
@@ -607,8 +609,10 @@ int dfl_accept_commit_batch(const int64_t *block_ids, int64_t blk_stride, const 
                             int64_t *next_block, int64_t mask_id, void *stream);
 /* The same for requests of tiles_per_req (1 or 2) 16-row tiles — blocks of up to 32 rows: besides the per-request records
  * it keeps one record per TILE for the per-tile launches (dyn_d_tiles: S / pos0 = start + 16 j, tau = the tile's share of
- * the acc + 1 context rows; dyn_t_tiles: block form with bs = the tile's share of the block rows); the re-armed block has
- * 16 * tiles_per_req slots. */
+ * the acc + 1 context rows, start = new start; dyn_t_tiles: block form with bs = the tile's share of the block rows); every
+ * other word of a tile record (dyn_d_tiles bs, stop, cycle, spare) is left as it was.  The re-armed block has
+ * 16 * tiles_per_req slots.  tiles_per_req = 1 with the per-request records passed as the tile records too leaves what
+ * dfl_accept_commit_batch leaves. */
 int dfl_accept_commit_batch_t(const int64_t *block_ids, int64_t blk_stride, const int64_t *posterior,
                               int64_t post_stride, int R, int64_t *output_ids, int64_t out_stride, int64_t output_len,
                               int32_t *dyn_d, int32_t *dyn_t, const int64_t *stop_ids, int n_stop, int32_t *result,

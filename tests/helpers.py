@@ -267,3 +267,10 @@ def dyn_records(vals, MT: int, device) -> torch.Tensor:
     for r, (tau, bs) in enumerate(vals):
         d[r, 1], d[r, 2] = tau, bs
     return d.to(device)
+
+
+def unpack_tiles(xf: torch.Tensor, P: int, K: int) -> torch.Tensor:
+    """Prefill frag16 row tiles [Pp/16][K/32][64][8] -> rows [P][K]: lane = (k % 32 // 8) * 16 + m."""
+    Pp = xf.numel() // K
+    t = xf.view(Pp // 16, K // 32, 4, 16, 8)            # [tile][k-step][kq][m][j]
+    return t.permute(0, 3, 1, 2, 4).reshape(Pp, K)[:P]

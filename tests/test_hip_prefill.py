@@ -16,11 +16,7 @@ def dev():
     return torch.device("cuda", 0)
 
 
-def _unpack_tiles(xf, P, K):
-    """frag16 row tiles [Pp/16][K/32][64][8] -> rows [P][K]: lane = (k % 32 // 8) * 16 + m."""
-    Pp = xf.numel() // K
-    t = xf.view(Pp // 16, K // 32, 4, 16, 8)            # [tile][k-step][kq][m][j]
-    return t.permute(0, 3, 1, 2, 4).reshape(Pp, K)[:P]
+_unpack_tiles = H.unpack_tiles
 
 
 @pytest.mark.parametrize("P,N,K", [(200, 256, 128), (128, 384, 320), (1, 128, 64), (300, 1280, 512)])
