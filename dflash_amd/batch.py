@@ -14,7 +14,7 @@ per-request preallocated KV caches, one device->host read of R x 4 ints.
 Needs the native target (`dflash_amd.NativeTarget`): the HF forward cannot take requests
 of different lengths without padding masks, which is exactly the cost this path removes.
 Sparse-MoE targets (round 3): attention and the dense projections run batched, the expert
-MLP per request (`BatchedDecoder._moe_mlp`).
+MLP per request (`NativeTarget.moe_mlp_tiles`).
 """
 from __future__ import annotations
 
@@ -29,6 +29,7 @@ from . import ops
 from .generate import _bf16_table, _draw_rows, _taps, _trim, capture_graph, cuda_time, resolve_seed
 from .model import DFlashDraftModel
 from .target import NativeTarget
+from .tile_stack import TileStack, gemm_ws
 from .utils import sample
 
 BF16, F32, I32, I64 = torch.bfloat16, torch.float32, torch.int32, torch.int64
@@ -110,47 +111,42 @@ class BatchedDecoder:
         self.nqkv_d = c.q_dim + 2 * c.kv_dim
         self.nkv_all = Ld * 2 * c.kv_dim
         ks = ops.batch_ksplit
-        self.d = dict(h=z(MT, 16, H), ctxh=z(MT, 16, H), ss_emb=z(MT, 16, dt=F32), xn=z(MT, 16 * H),
-                      attn=z(MT, 16 * c.q_dim), act=z(MT, 16 * I),
-                      part_qkv=z(ks(H) * MT * 16 * self.nqkv_d, dt=F32), part_kv=z(ks(H) * MT * 16 * self.nkv_all, dt=F32),
-                      part_h=z(max(ks(c.q_dim), ks(I)) * MT * 16 * H, dt=F32), taps=z(MT, 16, c.fc_in))
+        self.d = dict(ctxh=z(MT, 16, H), ss_emb=z(MT, 16, dt=F32),
+                      part_kv=z(ks(H) * MT * 16 * self.nkv_all, dt=F32), taps=z(MT, 16, c.fc_in))
         # context K/V weights of all layers as ONE packed weight: the k/v column tiles of each
         # layer's packed qkv, concatenated (tile-major layout: a plain cat of tile ranges)
         L = model.w["layers"]
         self.kv_all = torch.cat([lw["qkv"][c.q_dim * H:] for lw in L]).contiguous()
         self.k_norm_all = torch.stack([lw["k_norm"] for lw in L]).contiguous()
         # ---- target scratch
-        self.nqkv_t = t.nqkv
-        self.t = dict(h=z(MT, 16, H), ss_emb=z(MT, 16, dt=F32), xn=z(MT, 16 * H), attn=z(MT, 16 * t.q_dim),
-                      act=z(MT, 16 * t.I), part_qkv=z(ks(H) * MT * 16 * t.nqkv, dt=F32),
-                      part_h=z(max(ks(t.q_dim), ks(t.I), getattr(t, "moe_nsplit", 0) if getattr(t, "is_moe", False) else 0)
-                               * MT * 16 * H, dt=F32))
-        # ---- shared workspaces (launches are stream-ordered)
-        nmax = max(c.vocab_size, t.V, 2 * I, 2 * t.I, self.nqkv_d, t.nqkv)
-        kmax = max(H, I, t.I, c.fc_in, c.q_dim)
-        self.gws = torch.zeros(max(ops.lib().dfl_gemm_batch_ws_bytes(n, k) for n, k in
-                                   ((nmax, H), (H, kmax))), dtype=torch.uint8, device=dev)
-        # one per model: the arrival tickets sit behind the partials, whose size depends on n_q
-        self.aws_d = ops.attn_fused_batch_ws(MT, c.num_attention_heads, c.num_key_value_heads, max_splits, dev)
-        self.aws_t = ops.attn_fused_batch_ws(MT, t.n_q, t.n_kv, max_splits, dev)
-        # round 2: the attention stage on finished bf16 q/k/v rows (dfl_attn_head_batch); "fused" keeps the round-1 stage
-        self.attn_impl = getattr(model, "attn_impl", "head")
-        # round 4: the q/k/v projection leaves fp32 K-part sums and the attention launch sums them while it loads its rows
-        # (dfl_attn_head_batch_f32) — blocks of <= 16 rows, <= 2 K parts (hidden <= 4096); DFL_QKV_PARTS=0: the round-3 form
-        # (finished bf16 rows: slabs + ticket + combine inside the GEMM), kept as the second implementation
-        self.qkv_parts = (os.environ.get("DFL_QKV_PARTS", "1") != "0" and tiles_per_request == 1 and ops.batch_ksplit(H) <= 2)
-        self.hws_d = ops.attn_head_batch_ws(MT, c.num_attention_heads, max_splits, dev, q_tiles=TPR)
-        self.hws_t = ops.attn_head_batch_ws(MT, t.n_q, max_splits, dev, q_tiles=TPR)
-        if TPR == 2 and self.attn_impl != "head":
-            raise NotImplementedError("blocks of more than 16 rows need the 'head' attention stage")
-        self.d["xq"], self.t["xq"] = z(MT, 16, self.nqkv_d), z(MT, 16, t.nqkv)
-        # ---- row sources
+        self.t = dict(ss_emb=z(MT, 16, dt=F32))
+        # ---- shared workspace (launches are stream-ordered) and the two stacks: their rows, sums and row sources
         # (normalised operands come from dfl_norm_frag_batch: at 4 tiles the in-GEMM norm of the
         # single-request path, replicated in every workgroup, costs more than that launch)
-        d, tt = self.d, self.t
-        self.src_d = dict(taps=ops.brows_plain(d["taps"], ops.DYN_TAU), xn=ops.brows_frag(d["xn"]),
-                          attn=ops.brows_frag(d["attn"]), act=ops.brows_frag(d["act"]))
-        self.src_t = dict(xn=ops.brows_frag(tt["xn"]), attn=ops.brows_frag(tt["attn"]), act=ops.brows_frag(tt["act"]))
+        self.gws = gemm_ws(H, (c.vocab_size, t.V, 2 * I, 2 * t.I, self.nqkv_d, t.nqkv), (H, I, t.I, c.fc_in, c.q_dim), dev)
+        sd = TileStack(H=H, q_dim=c.q_dim, I=I, nqkv=self.nqkv_d, eps=c.rms_norm_eps, MT=MT, gws=self.gws, part_qkv=True)
+        st = TileStack(H=H, q_dim=t.q_dim, I=t.I, nqkv=t.nqkv, eps=t.eps, MT=MT, gws=self.gws, part_qkv=True,
+                       moe_nsplit=t.moe_nsplit if getattr(t, "is_moe", False) else 0)
+        self.src_taps = ops.brows_plain(self.d["taps"], ops.DYN_TAU)
+        # round 2: the attention stage on finished bf16 q/k/v rows (dfl_attn_head_batch); "fused" keeps the round-1 stage
+        self.attn_impl = getattr(model, "attn_impl", "head")
+        if TPR == 2 and self.attn_impl != "head":
+            raise NotImplementedError("blocks of more than 16 rows need the 'head' attention stage")
+        # round 4: the q/k/v projection leaves fp32 K-part sums and the attention launch sums them while it loads its rows
+        # (dfl_attn_head_batch_f32) — blocks of <= 16 rows, <= 2 K parts (hidden <= 4096); otherwise the round-3 form
+        # (finished bf16 rows: slabs + ticket + combine inside the GEMM)
+        self.qkv_parts = tiles_per_request == 1 and ops.batch_ksplit(H) <= 2
+        # what the attention launch of a model side takes (_attend); the workspaces are one per model: the arrival
+        # tickets sit behind the partials, whose size depends on n_q
+        self.side_d = SimpleNamespace(
+            stack=sd, q_dim=c.q_dim, kv_dim=c.kv_dim, n_q=c.num_attention_heads, n_kv=c.num_key_value_heads,
+            scale=c.head_dim ** -0.5, causal=False, k=self.dk, v=self.dv, rope=model._rope_tab,
+            aws=ops.attn_fused_batch_ws(MT, c.num_attention_heads, c.num_key_value_heads, max_splits, dev),
+            hws=ops.attn_head_batch_ws(MT, c.num_attention_heads, max_splits, dev, q_tiles=TPR))
+        self.side_t = SimpleNamespace(
+            stack=st, q_dim=t.q_dim, kv_dim=t.kv_dim, n_q=t.n_q, n_kv=t.n_kv, scale=128 ** -0.5, causal=True, k=self.tk,
+            v=self.tv, rope=t._rope_tab, aws=ops.attn_fused_batch_ws(MT, t.n_q, t.n_kv, max_splits, dev),
+            hws=ops.attn_head_batch_ws(MT, t.n_q, max_splits, dev, q_tiles=TPR))
         self.lm_wp = None
         self.embed_w = None
         # ---- host mirror of the lengths
@@ -276,68 +272,52 @@ class BatchedDecoder:
         self._draft_head()
         self._mark("lm_head", 1)
 
+    def _attend(self, sd, kvmax: int):
+        """The attention launch of one model side (side_d / side_t) as TileStack.run takes it, and the q/k/v form it
+        reads.  Per-request records (self.dyn_t) steer the 'head' stages, per-tile ones the fused stage."""
+        st, MT = sd.stack, self.MT
+        cos, sin = sd.rope(kvmax + 64)
+        kw = dict(q_col=0, k_col=sd.q_dim, v_col=sd.q_dim + sd.kv_dim, n_q=sd.n_q, n_kv=sd.n_kv, eps=st.eps, cos_tab=cos,
+                  sin_tab=sin, kcache=sd.k, vcache=sd.v, scale=sd.scale, causal=sd.causal, kv_len_max=kvmax,
+                  max_splits=self.max_splits, out_frag=st.attn)
+        nsp = ops.batch_ksplit(st.H)
+        if self.attn_impl != "head":
+            return "parts", lambda i, lw: ops.attn_fused_batch(
+                qkv=st.part_qkv, nsplit=nsp, split_stride=MT * 16 * st.nqkv, ld=st.nqkv, R=self.NT, q_norm_w=lw["q_norm"],
+                k_norm_w=lw["k_norm"], layer=i, dyn=self.dyn_tt, ws=sd.aws, **kw)
+        if self.qkv_parts:   # the parts meet in the attention launch's row loads (round 4)
+            return "parts", lambda i, lw: ops.attn_head_batch_f32(
+                qkv_parts=st.part_qkv, nparts=nsp, MT=MT, ld=st.nqkv, R=self.R, q_norm_w=lw["q_norm"],
+                k_norm_w=lw["k_norm"], layer=i, dyn=self.dyn_t, ws=sd.hws, **kw)
+        return "rows", lambda i, lw: ops.attn_head_batch(
+            xq=st.xq, R=self.R, q_norm_w=lw["q_norm"], k_norm_w=lw["k_norm"], layer=i, dyn=self.dyn_t, ws=sd.hws,
+            q_tiles=self.TPR, **kw)
+
     def _draft_body(self, kvmax: int) -> None:
-        m, c, d, s, MT = self.model, self.cfg, self.d, self.src_d, self.MT
-        R, RQ, TPR = self.NT, self.R, self.TPR     # R: 16-row tiles of the per-tile launches; RQ: requests (attention)
+        m, c, d, st, MT = self.model, self.cfg, self.d, self.side_d.stack, self.MT
+        R, TPR = self.NT, self.TPR                 # R: 16-row tiles of the per-tile launches
         dyn_d, dyn_t = self.dyn_dt, self.dyn_tt    # per-tile records (the per-request ones when TPR = 1)
-        H, I = c.hidden_size, c.intermediate_size
-        L = m.w["layers"]
+        H = c.hidden_size
         cos, sin = m._rope_tab(kvmax + 64)
-        ops.embed_rows_batch(self.embed_w, self.block.view(-1, 16), R, d["h"], H, d["ss_emb"], dyn_t, ops.DYN_BS)
+        ops.embed_rows_batch(self.embed_w, self.block.view(-1, 16), R, st.h, H, d["ss_emb"], dyn_t, ops.DYN_BS)
         # context rows: fc, then K/V of all layers appended to the draft caches
         eps = c.rms_norm_eps
-        ops.gemm_resid_batch(m.w["fc"], s["taps"], R, H, c.fc_in, d["ctxh"], add_residual=False, ws=self.gws,
+        ops.gemm_resid_batch(m.w["fc"], self.src_taps, R, H, c.fc_in, d["ctxh"], add_residual=False, ws=self.gws,
                              dyn=dyn_d)
-        ops.norm_frag_batch(d["ctxh"], R, m.w["hidden_norm"], eps, d["xn"], dyn_d, ops.DYN_TAU)
-        ops.gemm_f32_batch(self.kv_all, s["xn"], R, self.nkv_all, H, d["part_kv"], dyn_d)
-        nsp = ops.batch_ksplit(H)
-        ops.kv_append_batch(kv=d["part_kv"], nsplit=nsp, split_stride=MT * 16 * self.nkv_all, ld=self.nkv_all, k_col=0,
-                            v_col=c.kv_dim, col_layer_stride=2 * c.kv_dim, n_layers=c.num_hidden_layers, R=R,
-                            n_kv=c.num_key_value_heads, k_norm_w=self.k_norm_all, eps=c.rms_norm_eps, cos_tab=cos,
-                            sin_tab=sin, kcache=self.dk, vcache=self.dv, dyn=dyn_d, tiles_per_req=TPR)
-        # block rows.  o_proj / down_proj leave fp32 K-part sums; the residual add happens in the
-        # norm launch that follows (the parts meet at the launch boundary, not inside the GEMM)
-        pend = 0  # K of the GEMM whose sums are waiting in part_h (0: none)
-        for i, lw in enumerate(L):
-            ops.norm_frag_batch(d["h"], R, lw["ln1"], eps, d["xn"], dyn_t, ops.DYN_BS,
-                                part=d["part_h"] if pend else None, N=H, K=pend)
-            if self.attn_impl == "head" and self.qkv_parts:
-                # q/k/v as fp32 K-part sums; the parts meet in the attention launch's row loads (round 4)
-                ops.gemm_f32_batch(lw["qkv"], s["xn"], R, self.nqkv_d, H, d["part_qkv"], dyn_t)
-                ops.attn_head_batch_f32(qkv_parts=d["part_qkv"], nparts=nsp, MT=MT, ld=self.nqkv_d, q_col=0, k_col=c.q_dim,
-                                        v_col=c.q_dim + c.kv_dim, R=RQ, n_q=c.num_attention_heads,
-                                        n_kv=c.num_key_value_heads, q_norm_w=lw["q_norm"], k_norm_w=lw["k_norm"],
-                                        eps=c.rms_norm_eps, cos_tab=cos, sin_tab=sin, kcache=self.dk, vcache=self.dv, layer=i,
-                                        scale=c.head_dim ** -0.5, causal=False, dyn=self.dyn_t, kv_len_max=kvmax,
-                                        ws=self.hws_d, max_splits=self.max_splits, out_frag=d["attn"])
-            elif self.attn_impl == "head":
-                ops.gemm_resid_batch(lw["qkv"], s["xn"], R, self.nqkv_d, H, d["xq"], add_residual=False, ws=self.gws,
-                                     dyn=dyn_t)
-                ops.attn_head_batch(xq=d["xq"], q_col=0, k_col=c.q_dim, v_col=c.q_dim + c.kv_dim, R=RQ,
-                                    n_q=c.num_attention_heads, n_kv=c.num_key_value_heads, q_norm_w=lw["q_norm"],
-                                    k_norm_w=lw["k_norm"], eps=c.rms_norm_eps, cos_tab=cos, sin_tab=sin, kcache=self.dk,
-                                    vcache=self.dv, layer=i, scale=c.head_dim ** -0.5, causal=False, dyn=self.dyn_t,
-                                    kv_len_max=kvmax, ws=self.hws_d, max_splits=self.max_splits, out_frag=d["attn"],
-                                    q_tiles=TPR)
-            else:
-                ops.gemm_f32_batch(lw["qkv"], s["xn"], R, self.nqkv_d, H, d["part_qkv"], dyn_t)
-                ops.attn_fused_batch(qkv=d["part_qkv"], nsplit=nsp, split_stride=MT * 16 * self.nqkv_d, ld=self.nqkv_d,
-                                     q_col=0, k_col=c.q_dim, v_col=c.q_dim + c.kv_dim, R=R, n_q=c.num_attention_heads,
-                                     n_kv=c.num_key_value_heads, q_norm_w=lw["q_norm"], k_norm_w=lw["k_norm"],
-                                     eps=c.rms_norm_eps, cos_tab=cos, sin_tab=sin, kcache=self.dk, vcache=self.dv,
-                                     layer=i, scale=c.head_dim ** -0.5, causal=False, dyn=dyn_t, kv_len_max=kvmax,
-                                     ws=self.aws_d, max_splits=self.max_splits, out_frag=d["attn"])
-            ops.gemm_f32_batch(lw["o"], s["attn"], R, H, c.q_dim, d["part_h"], dyn_t)
-            ops.norm_frag_batch(d["h"], R, lw["ln2"], eps, d["xn"], dyn_t, ops.DYN_BS, part=d["part_h"], N=H,
-                                K=c.q_dim)
-            ops.gemm_silu_mul_batch(lw["gu"], s["xn"], R, I, H, d["act"], self.gws, dyn_t)
-            ops.gemm_f32_batch(lw["down"], s["act"], R, H, I, d["part_h"], dyn_t)
-            pend = I
+        ops.norm_frag_batch(d["ctxh"], R, m.w["hidden_norm"], eps, st.xn, dyn_d, ops.DYN_TAU)
+        ops.gemm_f32_batch(self.kv_all, st.src["xn"], R, self.nkv_all, H, d["part_kv"], dyn_d)
+        ops.kv_append_batch(kv=d["part_kv"], nsplit=ops.batch_ksplit(H), split_stride=MT * 16 * self.nkv_all,
+                            ld=self.nkv_all, k_col=0, v_col=c.kv_dim, col_layer_stride=2 * c.kv_dim,
+                            n_layers=c.num_hidden_layers, R=R, n_kv=c.num_key_value_heads, k_norm_w=self.k_norm_all,
+                            eps=c.rms_norm_eps, cos_tab=cos, sin_tab=sin, kcache=self.dk, vcache=self.dv, dyn=dyn_d,
+                            tiles_per_req=TPR)
+        qkv, attend = self._attend(self.side_d, kvmax)   # block rows
+        st.run(m.w["layers"], R, dyn_t, attend, qkv=qkv)
 
     def _draft_head(self) -> None:
-        m, c, d, s, R = self.model, self.cfg, self.d, self.src_d, self.NT
-        ops.norm_frag_batch(d["h"], R, m.w["norm"], c.rms_norm_eps, d["xn"], self.dyn_tt, ops.DYN_BS,
-                            part=d["part_h"], N=c.hidden_size, K=c.intermediate_size)  # last down_proj + final norm
+        m, c, R = self.model, self.cfg, self.NT
+        self.side_d.stack.finish(m.w["norm"])   # last down_proj + final norm
+        s = self.side_d.stack.src
         if self.draft_temperature >= 1e-5:   # sampled draft (policy loop): slot j of the block draws start + j
             row0, out, off = (1, self.block, 1) if self.TPR == 1 else (0, self.ids_tmp, 0)
             ops.gemm_sample_batch(self.lm_wp, s["xn"], R, c.vocab_size, c.hidden_size, row0, 16 - row0, self.gws, out, off,
@@ -356,73 +336,15 @@ class BatchedDecoder:
     def verify(self, kvmax: Optional[int] = None) -> None:
         """Target verify of every live request's block (model/dflash.py:249-257, T = 0):
         post[r] <- the target's greedy tokens, taps[r] <- the tapped layers' hidden rows."""
-        t, tt, s, R, MT, H = self.target, self.t, self.src_t, self.NT, self.MT, self.cfg.hidden_size
-        RQ, TPR, dyn_t = self.R, self.TPR, self.dyn_tt    # (R: tiles, RQ: requests, dyn_t: per-tile records, see _draft_body)
+        t, st, R, MT, H = self.target, self.side_t.stack, self.NT, self.MT, self.cfg.hidden_size
+        TPR, dyn_t, s = self.TPR, self.dyn_tt, st.src    # (R: tiles, dyn_t: per-tile records, see _draft_body)
         kvmax = kvmax or self._kv_len_max()
-        cos, sin = t._rope_tab(kvmax + 64)
-        taps = self.d["taps"]
-        tl = list(self.model.target_layer_ids)
-        if max(tl) >= t.L - 1:
-            raise NotImplementedError("tapping the last layer (post-norm state) is not supported")
-        nsp = ops.batch_ksplit(H)
-        ops.embed_rows_batch(t.embed, self.block.view(-1, 16), R, tt["h"], H, tt["ss_emb"], dyn_t, ops.DYN_BS)
-        pend, ptap, pdup = 0, None, ()  # K and tap view of the down_proj whose sums wait in part_h
-        slots = {}   # tapped layer -> its slots in the tap rows (build_target_layer_ids repeats layers for
-        for j, l in enumerate(tl):   # shallow targets: model/utils.py:16-25 concatenates the state twice)
-            slots.setdefault(l, []).append(j)
-
-        def spread(dups):   # the other slots of a repeated tap id get the same rows
-            for a, b in dups:
-                taps[:, :, b * H:(b + 1) * H].copy_(taps[:, :, a * H:(a + 1) * H])
-
-        self._pend_ns = None   # part count of the pending sums when they are expert shares, not K parts
-        for i, lw in enumerate(t.layers):
-            ops.norm_frag_batch(tt["h"], R, lw["ln1"], t.eps, tt["xn"], dyn_t, ops.DYN_BS,
-                                part=tt["part_h"] if pend else None, N=H, K=pend, tap=ptap, nsplit=self._pend_ns)
-            spread(pdup)
-            if self.attn_impl == "head" and self.qkv_parts:
-                ops.gemm_f32_batch(lw["qkv"], s["xn"], R, t.nqkv, H, tt["part_qkv"], dyn_t)
-                ops.attn_head_batch_f32(qkv_parts=tt["part_qkv"], nparts=nsp, MT=MT, ld=t.nqkv, q_col=0, k_col=t.q_dim,
-                                        v_col=t.q_dim + t.kv_dim, R=RQ, n_q=t.n_q, n_kv=t.n_kv, q_norm_w=lw["q_norm"],
-                                        k_norm_w=lw["k_norm"], eps=t.eps, cos_tab=cos, sin_tab=sin, kcache=self.tk,
-                                        vcache=self.tv, layer=i, scale=128 ** -0.5, causal=True, dyn=self.dyn_t,
-                                        kv_len_max=kvmax, ws=self.hws_t, max_splits=self.max_splits, out_frag=tt["attn"])
-            elif self.attn_impl == "head":
-                ops.gemm_resid_batch(lw["qkv"], s["xn"], R, t.nqkv, H, tt["xq"], add_residual=False, ws=self.gws,
-                                     dyn=dyn_t)
-                ops.attn_head_batch(xq=tt["xq"], q_col=0, k_col=t.q_dim, v_col=t.q_dim + t.kv_dim, R=RQ, n_q=t.n_q,
-                                    n_kv=t.n_kv, q_norm_w=lw["q_norm"], k_norm_w=lw["k_norm"], eps=t.eps, cos_tab=cos,
-                                    sin_tab=sin, kcache=self.tk, vcache=self.tv, layer=i, scale=128 ** -0.5, causal=True,
-                                    dyn=self.dyn_t, kv_len_max=kvmax, ws=self.hws_t, max_splits=self.max_splits,
-                                    out_frag=tt["attn"], q_tiles=TPR)
-            else:
-                ops.gemm_f32_batch(lw["qkv"], s["xn"], R, t.nqkv, H, tt["part_qkv"], dyn_t)
-                ops.attn_fused_batch(qkv=tt["part_qkv"], nsplit=nsp, split_stride=MT * 16 * t.nqkv, ld=t.nqkv, q_col=0,
-                                     k_col=t.q_dim, v_col=t.q_dim + t.kv_dim, R=R, n_q=t.n_q, n_kv=t.n_kv,
-                                     q_norm_w=lw["q_norm"], k_norm_w=lw["k_norm"], eps=t.eps, cos_tab=cos, sin_tab=sin,
-                                     kcache=self.tk, vcache=self.tv, layer=i, scale=128 ** -0.5, causal=True,
-                                     dyn=dyn_t, kv_len_max=kvmax, ws=self.aws_t,
-                                     max_splits=self.max_splits, out_frag=tt["attn"])
-            ops.gemm_f32_batch(lw["o"], s["attn"], R, H, t.q_dim, tt["part_h"], dyn_t)
-            ops.norm_frag_batch(tt["h"], R, lw["ln2"], t.eps, tt["xn"], dyn_t, ops.DYN_BS, part=tt["part_h"],
-                                N=H, K=t.q_dim)
-            pns = None
-            if "gu_e" in lw:   # sparse-MoE layer (Qwen3MoeSparseMoeBlock): the requests share attention and projections
-                pns = self._moe_mlp(lw)   # above; routing and expert weights are per request
-                pend = 1
-            else:
-                ops.gemm_silu_mul_batch(lw["gu"], s["xn"], R, t.I, H, tt["act"], self.gws, dyn_t)
-                ops.gemm_f32_batch(lw["down"], s["act"], R, H, t.I, tt["part_h"], dyn_t)
-                pend = t.I
-            # the layer's output (a tapped layer's hidden rows, model/utils.py:16-25) exists once the
-            # next norm launch has added these sums: it writes the tap
-            sl = slots.get(i, ())
-            ptap = taps[:, :, sl[0] * H:(sl[0] + 1) * H] if sl else None
-            pdup = [(sl[0], b) for b in sl[1:]]
-            self._pend_ns = pns
-        ops.norm_frag_batch(tt["h"], R, t.norm, t.eps, tt["xn"], dyn_t, ops.DYN_BS, part=tt["part_h"], N=H, K=pend,
-                            tap=ptap, nsplit=self._pend_ns)
-        spread(pdup)
+        ops.embed_rows_batch(t.embed, self.block.view(-1, 16), R, st.h, H, self.t["ss_emb"], dyn_t, ops.DYN_BS)
+        qkv, attend = self._attend(self.side_t, kvmax)
+        # (a sparse-MoE layer: the requests share attention and projections; routing and expert weights are per request)
+        st.run(t.layers, R, dyn_t, attend, qkv=qkv, taps=self.d["taps"], tap_layers=self.model.target_layer_ids,
+               moe=t.moe_mlp_tiles)
+        st.finish(t.norm)
         if self.temperature < 1e-5:
             ops.gemm_argmax_batch(self.lm_wp, s["xn"], R, t.V, H, 0, 16, self.gws, self.post.view(-1, 16), 0, dyn_t,
                                   nrows_dyn_word=ops.DYN_BS)
@@ -439,10 +361,6 @@ class BatchedDecoder:
             ops.gemm_argmax_batch(self.lm_wp, s["xn"], R, t.V, H, 0, 16, self.gws, self.post, 0, dyn_t,
                                   nrows_dyn_word=ops.DYN_BS, logits=self._logits)
             self.post[:R] = sample(self._logits[:R], self.temperature)
-
-    def _moe_mlp(self, lw: dict) -> int:
-        """Sparse-MoE MLP of one target layer for the requests of the group: NativeTarget.moe_mlp_tiles."""
-        return self.target.moe_mlp_tiles(lw, self.NT, self.MT, self.dyn_tt, self.t["xn"], self.t["part_h"])
 
     def _accept_launch(self) -> None:
         ops.accept_commit_batch(self.block, self.post, self.R, self.output_ids, self.dyn_d, self.dyn_t, self.stop_t,

@@ -27,6 +27,7 @@ import torch
 
 from . import ops
 from .generate import DecodeSession, _taps, cuda_time
+from .tile_stack import TileStack, gemm_ws
 from .utils import sample
 
 BF16, F32, I32, I64 = torch.bfloat16, torch.float32, torch.int32, torch.int64
@@ -216,22 +217,19 @@ class NativeCandidateVerifier:
         self.t, self.max_splits = t, max_splits
         dev = t.device
         z = lambda *s, dt=BF16: torch.zeros(*s, dtype=dt, device=dev)  # noqa: E731
-        H, ks = t.H, ops.batch_ksplit
+        H = t.H
         self.ids = z(MT, 16, dt=I64)
         self.dyn = z(MT, 8, dt=I32)
-        self.h, self.ss_emb = z(MT, 16, H), z(MT, 16, dt=F32)
-        self.xn, self.attn, self.act = z(MT, 16 * H), z(MT, 16 * t.q_dim), z(MT, 16 * t.I)
-        self.xq = z(MT, 16, t.nqkv)
-        self.part_h = z(max(ks(t.q_dim), ks(t.I), t.moe_nsplit if getattr(t, "is_moe", False) else 0) * MT * 16 * H, dt=F32)
-        nmax, kmax = max(t.V, 2 * t.I, t.nqkv), max(H, t.I, t.q_dim)
-        self.gws = torch.zeros(max(ops.lib().dfl_gemm_batch_ws_bytes(n, k) for n, k in ((nmax, H), (H, kmax))),
-                               dtype=torch.uint8, device=dev)
+        self.ss_emb = z(MT, 16, dt=F32)
+        self.stack = TileStack(H=H, q_dim=t.q_dim, I=t.I, nqkv=t.nqkv, eps=t.eps, MT=MT,
+                               gws=gemm_ws(H, (t.V, 2 * t.I, t.nqkv), (H, t.I, t.q_dim), dev),
+                               moe_nsplit=t.moe_nsplit if getattr(t, "is_moe", False) else 0)
+        self.part_h = self.stack.part_h
         self.head_ws = torch.zeros(MT * ops.lib().dfl_attn_head_ws_bytes(t.n_q, max_splits, 2), dtype=torch.uint8,
                                    device=dev)
         self.stage_k, self.stage_v = z(t.L, MT, t.n_kv, 32, 128), z(t.L, MT, t.n_kv, 32, 128)
         self.taps = z(MT, 16, max(1, n_taps) * H)
         self.post = z(MT, 16, dt=I64)
-        self.src = dict(xn=ops.brows_frag(self.xn), attn=ops.brows_frag(self.attn), act=ops.brows_frag(self.act))
 
     @torch.inference_mode()
     def verify(self, cands: torch.Tensor, start: int, cache, tap_layers: Sequence[int]) -> torch.Tensor:
@@ -247,50 +245,23 @@ class NativeCandidateVerifier:
             raise ValueError("target KV cache too small")
         if t.lm_wp is None:
             t.lm_wp = ops.pack_weight(t.lm_head.weight.detach().to(BF16).contiguous())
-        tl = list(tap_layers)
-        if tl and max(tl) >= t.L - 1:
-            raise NotImplementedError("tapping the last layer (post-norm state) is not supported")
         cos, sin = t._rope_tab(start + bs + 64)
         rec = [[start, 0, max(0, min(16, bs - 16 * (j % TPR))) if j < C * TPR else 0, start, start, 0, 0, 0] for j in range(MT)]
         self.dyn.copy_(torch.tensor(rec, dtype=I32))             # one record per TILE (valid rows of the tile)
         self.ids.view(-1, 16 * TPR)[:C, :bs].copy_(cands)
-        dyn, s, R = self.dyn, self.src, C * TPR
-        ops.embed_rows_batch(t.embed, self.ids, R, self.h, H, self.ss_emb, dyn, ops.DYN_BS)
-        slots = {}
-        for j, l in enumerate(tl):
-            slots.setdefault(l, []).append(j)
-        pend, ptap, pdup = 0, None, ()
+        dyn, st, R = self.dyn, self.stack, C * TPR
+        ops.embed_rows_batch(t.embed, self.ids, R, st.h, H, self.ss_emb, dyn, ops.DYN_BS)
 
-        def spread(dups):
-            for a, b in dups:
-                self.taps[:, :, b * H:(b + 1) * H].copy_(self.taps[:, :, a * H:(a + 1) * H])
-
-        pns = None   # share count of the pending sums when they are MoE expert shares, not K parts
-        for i, lw in enumerate(t.layers):
-            ops.norm_frag_batch(self.h, R, lw["ln1"], t.eps, self.xn, dyn, ops.DYN_BS,
-                                part=self.part_h if pend else None, N=H, K=pend, tap=ptap, nsplit=pns)
-            spread(pdup)
-            ops.gemm_resid_batch(lw["qkv"], s["xn"], R, t.nqkv, H, self.xq, add_residual=False, ws=self.gws, dyn=dyn)
-            ops.attn_head_cand(xq=self.xq[:R], q_col=0, k_col=t.q_dim, v_col=t.q_dim + t.kv_dim, n_q=t.n_q, n_kv=t.n_kv,
+        def attend(i, lw):
+            ops.attn_head_cand(xq=st.xq[:R], q_col=0, k_col=t.q_dim, v_col=t.q_dim + t.kv_dim, n_q=t.n_q, n_kv=t.n_kv,
                                q_norm_w=lw["q_norm"], k_norm_w=lw["k_norm"], eps=t.eps, cos_tab=cos, sin_tab=sin,
                                kcache=cache.k[i], vcache=cache.v[i], scale=128 ** -0.5, S=start, bs=bs,
-                               ws=self.head_ws, max_splits=self.max_splits, out_frag=self.attn,
+                               ws=self.head_ws, max_splits=self.max_splits, out_frag=st.attn,
                                k_out=self.stage_k[i], v_out=self.stage_v[i], q_tiles=TPR)
-            ops.gemm_f32_batch(lw["o"], s["attn"], R, H, t.q_dim, self.part_h, dyn)
-            ops.norm_frag_batch(self.h, R, lw["ln2"], t.eps, self.xn, dyn, ops.DYN_BS, part=self.part_h, N=H, K=t.q_dim)
-            if "gu_e" in lw:   # sparse-MoE layer: every candidate routes its own rows (round 3)
-                pns, pend = t.moe_mlp_tiles(lw, R, MT, dyn, self.xn, self.part_h), 1
-            else:
-                ops.gemm_silu_mul_batch(lw["gu"], s["xn"], R, t.I, H, self.act, self.gws, dyn)
-                ops.gemm_f32_batch(lw["down"], s["act"], R, H, t.I, self.part_h, dyn)
-                pns, pend = None, t.I
-            sl = slots.get(i, ())
-            ptap = self.taps[:, :, sl[0] * H:(sl[0] + 1) * H] if sl else None
-            pdup = [(sl[0], b) for b in sl[1:]]
-        ops.norm_frag_batch(self.h, R, t.norm, t.eps, self.xn, dyn, ops.DYN_BS, part=self.part_h, N=H, K=pend, tap=ptap,
-                            nsplit=pns)
-        spread(pdup)
-        ops.gemm_argmax_batch(t.lm_wp, s["xn"], R, t.V, H, 0, 16, self.gws, self.post, 0, dyn, nrows_dyn_word=ops.DYN_BS)
+
+        st.run(t.layers, R, dyn, attend, qkv="rows", taps=self.taps, tap_layers=tap_layers, moe=t.moe_mlp_tiles)
+        st.finish(t.norm)
+        ops.gemm_argmax_batch(t.lm_wp, st.src["xn"], R, t.V, H, 0, 16, st.gws, self.post, 0, dyn, nrows_dyn_word=ops.DYN_BS)
         return self.post.view(-1, 16 * TPR)[:C, :bs]
 
     def cand_taps(self, c: int, bs: int) -> torch.Tensor:

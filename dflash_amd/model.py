@@ -20,6 +20,7 @@ import torch
 
 from . import ops
 from .config import DFlashConfig
+from .tile_stack import TileStack, gemm_ws
 
 BF16 = torch.bfloat16
 
@@ -454,51 +455,39 @@ class DFlashDraftModel:
 
     def _draft_block_wide(self, cache, ws, S, tau, bs, pos0, block_ids, embed, noise, append, cos, sin) -> WideRows:
         """The block rows of a 17..32-row block in ONE pass over the layer weights: the two 16-row tiles go through the
-        ragged-batch GEMMs (R = 2: fp32 K-part sums of o_proj / down_proj, residual add + RMSNorm in
-        dfl_norm_frag_batch) and ONE attention launch with two query tiles (model/dflash.py:166-190)."""
+        ragged-batch GEMMs (tile_stack.TileStack, R = 2) and ONE attention launch per layer with two query tiles
+        (model/dflash.py:166-190)."""
         c, w, R = self.config, self.w, 2
-        H, I, eps = c.hidden_size, c.intermediate_size, c.rms_norm_eps
+        H, I = c.hidden_size, c.intermediate_size
         nqkv = c.q_dim + 2 * c.kv_dim
         if self._wide is None:
-            ks, d = ops.batch_ksplit, self.device
-            xn = torch.zeros(2, 16 * H, dtype=BF16, device=d)
-            nmax, kmax = max(c.vocab_size, 2 * I, nqkv), max(H, I, c.q_dim)
-            self._wide = dict(
-                xn=xn, ids=torch.zeros(2, 16, dtype=torch.int64, device=d),
-                part_h=torch.zeros(max(ks(c.q_dim), ks(I)) * 2 * 16 * H, dtype=torch.float32, device=d),
-                gws=torch.zeros(max(ops.lib().dfl_gemm_batch_ws_bytes(n, k) for n, k in ((nmax, H), (H, kmax))),
-                                dtype=torch.uint8, device=d),
-                src=dict(xn=ops.brows_frag(xn), attn=ops.brows_frag(ws["attn_frag"]), act=ops.brows_frag(ws["act_frag"])))
-        ww = self._wide
-        s, gws, part_h, xn = ww["src"], ww["gws"], ww["part_h"], ww["xn"]
+            self._wide = TileStack(H=H, q_dim=c.q_dim, I=I, nqkv=nqkv, eps=c.rms_norm_eps, MT=2,
+                                   gws=gemm_ws(H, (c.vocab_size, 2 * I, nqkv), (H, I, c.q_dim), self.device),
+                                   h=ws["h"].view(2, 16, H), attn=ws["attn_frag"], act=ws["act_frag"],
+                                   xq=ws["xq"].view(2, 16, nqkv))
+            self._wide_ids = torch.zeros(2, 16, dtype=torch.int64, device=self.device)
+        st = self._wide
         dyn2 = cache.dyn[:16].view(2, 8)
-        h3, xq3 = ws["h"].view(2, 16, H), ws["xq"].view(2, 16, nqkv)
         if noise is not None:   # public forward(): the caller embedded the block itself
             ws["h"][:bs].copy_(noise[:bs])
         else:
-            ww["ids"].view(-1)[:bs].copy_(block_ids[:bs])
-            ops.embed_rows_batch(embed, ww["ids"], R, h3, H, ws["ss_emb"].view(2, 16), dyn2, ops.DYN_BS)
-        pend = 0   # K of the GEMM whose fp32 sums wait in part_h (added by the next norm launch)
-        for i, lw in enumerate(w["layers"]):
-            ops.norm_frag_batch(h3, R, lw["ln1"], eps, xn, dyn2, ops.DYN_BS, part=part_h if pend else None, N=H, K=pend)
-            ops.gemm_resid_batch(lw["qkv"], s["xn"], R, nqkv, H, xq3, add_residual=False, ws=gws, dyn=dyn2)
+            self._wide_ids.view(-1)[:bs].copy_(block_ids[:bs])
+            ops.embed_rows_batch(embed, self._wide_ids, R, st.h, H, ws["ss_emb"].view(2, 16), dyn2, ops.DYN_BS)
+
+        def attend(i, lw):
             ops.attn_head(xq=ws["xq"], q_col=0, k_col=c.q_dim, v_col=c.q_dim + c.kv_dim,
                           xc=ws["xc"] if tau > 0 else None, ck_col=i * 2 * c.kv_dim, cv_col=i * 2 * c.kv_dim + c.kv_dim,
                           n_q=c.num_attention_heads, n_kv=c.num_key_value_heads, q_norm_w=lw["q_norm"],
-                          k_norm_w=lw["k_norm"], eps=eps, cos_tab=cos, sin_tab=sin, kcache=cache.k[i], vcache=cache.v[i],
-                          scale=c.head_dim ** -0.5, causal=False, S=S, tau=tau, bs=bs, pos0=pos0, ws=ws["head_ws"],
-                          max_splits=self.max_splits, out_frag=ws["attn_frag"], q_tiles=2,
+                          k_norm_w=lw["k_norm"], eps=c.rms_norm_eps, cos_tab=cos, sin_tab=sin, kcache=cache.k[i],
+                          vcache=cache.v[i], scale=c.head_dim ** -0.5, causal=False, S=S, tau=tau, bs=bs, pos0=pos0,
+                          ws=ws["head_ws"], max_splits=self.max_splits, out_frag=ws["attn_frag"], q_tiles=2,
                           out_tile_stride=ws["attn_frag"].stride(0))
-            ops.gemm_f32_batch(lw["o"], s["attn"], R, H, c.q_dim, part_h, dyn2)
-            ops.norm_frag_batch(h3, R, lw["ln2"], eps, xn, dyn2, ops.DYN_BS, part=part_h, N=H, K=c.q_dim)
-            ops.gemm_silu_mul_batch(lw["gu"], s["xn"], R, I, H, ws["act_frag"], gws, dyn2)
-            ops.gemm_f32_batch(lw["down"], s["act"], R, H, I, part_h, dyn2)
-            pend = I
-        # last down_proj's sums -> h (the rows forward() returns after its own norm), final norm -> frag16
-        ops.norm_frag_batch(h3, R, w["norm"], eps, xn, dyn2, ops.DYN_BS, part=part_h, N=H, K=pend)
+
+        st.run(w["layers"], R, dyn2, attend, qkv="rows")
+        st.finish(w["norm"])   # last down_proj's sums -> h (the rows forward() returns after its own norm), final norm -> frag16
         if append:
             cache.length = S + tau
-        return WideRows(s["xn"], dyn2)
+        return WideRows(st.src["xn"], dyn2)
 
     def draft_tokens(self, hid_frag, lm_head_wp: torch.Tensor, bs: int, block_ids: torch.Tensor,
                      logits: Optional[torch.Tensor] = None, margins: Optional[torch.Tensor] = None,
@@ -514,10 +503,10 @@ class DFlashDraftModel:
         if isinstance(hid_frag, WideRows):   # both tiles in one lm_head pass (ragged-batch GEMM, R = 2)
             if margins is not None:
                 raise NotImplementedError("top-2 margins are computed for blocks of <= 16 rows")
-            ww = self._wide
+            gws, ids = self._wide.gws, self._wide_ids
             if sample is not None and logits is None:   # (no sampled ring epilogue: the draw runs over the logits)
                 logits = torch.empty(32, c.vocab_size, dtype=BF16, device=self.device)
-            ops.gemm_argmax_batch(lm_head_wp, hid_frag.src, 2, c.vocab_size, c.hidden_size, 0, 16, ww["gws"], ww["ids"], 0,
+            ops.gemm_argmax_batch(lm_head_wp, hid_frag.src, 2, c.vocab_size, c.hidden_size, 0, 16, gws, ids, 0,
                                   hid_frag.dyn, nrows_dyn_word=ops.DYN_BS,
                                   logits=None if logits is None else logits.view(2, 16, c.vocab_size))
             if sample is not None:
@@ -525,8 +514,8 @@ class DFlashDraftModel:
                     raise ValueError("a sampled draft of more than 16 rows needs the block start on the host")
                 st = int(sample["start"])
                 ops.sample_rows(logits.view(-1, c.vocab_size)[:bs], seed=sample["seed"], temperature=sample["temperature"],
-                                pos0=st, stream=ops.RNG_DRAFT, extra=st, out=ww["ids"].view(-1)[:bs])
-            block_ids[1:bs].copy_(ww["ids"].view(-1)[1:bs])
+                                pos0=st, stream=ops.RNG_DRAFT, extra=st, out=ids.view(-1)[:bs])
+            block_ids[1:bs].copy_(ids.view(-1)[1:bs])
             return
         srcs = hid_frag if isinstance(hid_frag, (list, tuple)) else [hid_frag]
         for t, x in enumerate(srcs):

@@ -26,6 +26,7 @@ import torch
 
 from . import ops
 from .model import _rope_tables
+from .tile_stack import TileStack, gemm_ws
 from .utils import sample
 
 BF16 = torch.bfloat16
@@ -531,62 +532,31 @@ class NativeTarget:
     # ---- the verify forward on the kernels
     def _verify_wide(self, block_ids, start, cache, bs, tap_layers, taps, logits_out, temperature, cos, sin, seed=None):
         """Blocks of 17..32 rows in ONE pass over the weights: the two 16-row tiles go through the ragged-batch
-        GEMMs (dfl_*_batch with R = 2: fp32 K-part sums of o_proj / down_proj, residual add + RMSNorm in
-        dfl_norm_frag_batch) as if they were two requests, and through ONE attention launch with two query tiles on the
-        request's single cache.  Same lines as verify(): model/dflash.py:249-257."""
+        GEMMs (tile_stack.TileStack, R = 2) as if they were two requests, and through ONE attention launch per layer with
+        two query tiles on the request's single cache.  Same lines as verify(): model/dflash.py:249-257."""
         ws, H, R = self.ws, self.H, 2
         if self._wide is None:
-            ks, dev = ops.batch_ksplit, self._dev
-            xn = torch.zeros(2, 16 * H, dtype=BF16, device=dev)
-            nmax, kmax = max(self.V, 2 * self.I, self.nqkv), max(H, self.I, self.q_dim)
-            self._wide = dict(
-                xn=xn, ids=torch.zeros(2, 16, dtype=torch.int64, device=dev),
-                part_h=torch.zeros(max(ks(self.q_dim), ks(self.I), self.moe_nsplit if self.is_moe else 0) * 2 * 16 * H,
-                                   dtype=torch.float32, device=dev),
-                gws=torch.zeros(max(ops.lib().dfl_gemm_batch_ws_bytes(n, k) for n, k in ((nmax, H), (H, kmax))),
-                                dtype=torch.uint8, device=dev),
-                src=dict(xn=ops.brows_frag(xn), attn=ops.brows_frag(ws["attn"]), act=ops.brows_frag(ws["act"])))
-        ww = self._wide
-        s, gws, part_h, xn = ww["src"], ww["gws"], ww["part_h"], ww["xn"]
+            self._wide = TileStack(H=H, q_dim=self.q_dim, I=self.I, nqkv=self.nqkv, eps=self.eps, MT=2,
+                                   gws=gemm_ws(H, (self.V, 2 * self.I, self.nqkv), (H, self.I, self.q_dim), self._dev),
+                                   h=ws["h"].view(2, 16, H), attn=ws["attn"], act=ws["act"],
+                                   xq=ws["xq"].view(2, 16, self.nqkv), moe_nsplit=self.moe_nsplit if self.is_moe else 0)
+            self._wide_ids = torch.zeros(2, 16, dtype=torch.int64, device=self._dev)
+        st = self._wide
+        s, gws = st.src, st.gws
         dyn2 = cache.dyn[:16].view(2, 8)
-        h3, xq3 = ws["h"].view(2, 16, H), ws["xq"].view(2, 16, self.nqkv)
-        ww["ids"].view(-1)[:bs].copy_(block_ids[:bs])
-        ops.embed_rows_batch(self.embed, ww["ids"], R, h3, H, ws["ss_emb"].view(2, 16), dyn2, ops.DYN_BS)
-        tap3 = None if taps is None else taps.view(2, 16, taps.shape[1])
-        slots = {}
-        for j, l in enumerate(tap_layers):
-            slots.setdefault(l, []).append(j)
-        pend, ptap, pdup = 0, None, ()   # K and tap view of the down_proj whose sums wait in part_h
+        self._wide_ids.view(-1)[:bs].copy_(block_ids[:bs])
+        ops.embed_rows_batch(self.embed, self._wide_ids, R, st.h, H, ws["ss_emb"].view(2, 16), dyn2, ops.DYN_BS)
 
-        def spread(dups):   # the other slots of a repeated tap id get the same rows (model/utils.py:16-25)
-            for a, b in dups:
-                taps[:, b * H:(b + 1) * H].copy_(taps[:, a * H:(a + 1) * H])
-
-        pns = None   # share count of the pending sums when they are MoE expert shares, not K parts
-        for i, lw in enumerate(self.layers):
-            ops.norm_frag_batch(h3, R, lw["ln1"], self.eps, xn, dyn2, ops.DYN_BS, part=part_h if pend else None, N=H,
-                                K=pend, tap=ptap, nsplit=pns)
-            spread(pdup)
-            ops.gemm_resid_batch(lw["qkv"], s["xn"], R, self.nqkv, H, xq3, add_residual=False, ws=gws, dyn=dyn2)
+        def attend(i, lw):
             ops.attn_head(xq=ws["xq"], q_col=0, k_col=self.q_dim, v_col=self.q_dim + self.kv_dim, n_q=self.n_q,
                           n_kv=self.n_kv, q_norm_w=lw["q_norm"], k_norm_w=lw["k_norm"], eps=self.eps, cos_tab=cos,
                           sin_tab=sin, kcache=cache.k[i], vcache=cache.v[i], scale=128 ** -0.5, causal=True, S=start,
                           tau=0, bs=bs, pos0=start, ws=ws["head_ws"], max_splits=self.max_splits, out_frag=ws["attn"],
                           q_tiles=2, out_tile_stride=ws["attn"].stride(0))
-            ops.gemm_f32_batch(lw["o"], s["attn"], R, H, self.q_dim, part_h, dyn2)
-            ops.norm_frag_batch(h3, R, lw["ln2"], self.eps, xn, dyn2, ops.DYN_BS, part=part_h, N=H, K=self.q_dim)
-            if "gu_e" in lw:   # sparse-MoE layer: each of the two tiles routes its own rows (round 3)
-                pns, pend = self.moe_mlp_tiles(lw, R, 2, dyn2, xn, part_h), 1
-            else:
-                ops.gemm_silu_mul_batch(lw["gu"], s["xn"], R, self.I, H, ws["act"], gws, dyn2)
-                ops.gemm_f32_batch(lw["down"], s["act"], R, H, self.I, part_h, dyn2)
-                pns, pend = None, self.I
-            sl = slots.get(i, ())   # a tapped layer's rows exist once the next norm launch has added these sums
-            ptap = tap3[:, :, sl[0] * H:(sl[0] + 1) * H] if sl else None
-            pdup = [(sl[0], b) for b in sl[1:]]
-        ops.norm_frag_batch(h3, R, self.norm, self.eps, xn, dyn2, ops.DYN_BS, part=part_h, N=H, K=pend, tap=ptap,
-                            nsplit=pns)
-        spread(pdup)
+
+        st.run(self.layers, R, dyn2, attend, qkv="rows", taps=None if taps is None else taps.view(2, 16, -1),
+               tap_layers=tap_layers, moe=self.moe_mlp_tiles)
+        st.finish(self.norm)
         post = ws["post"]
         logits = logits_out
         if temperature >= 1e-5:
