@@ -514,7 +514,10 @@ typedef struct dfl_rows_batch {
 } dfl_rows_batch;
 
 int dfl_batch_tiles(int R);  /* 2 for R <= 2, else 4 */
-int dfl_batch_ksplit(int K); /* K parts of 2048 the batched GEMMs cut K into (grid.y) */
+/* K parts the batched GEMMs cut K into (grid.y): ceil(K / 2048), at most 16 (K <= 32768).  A part is NOT 2048 columns
+ * unless K is a multiple of it: the K / 32 k-steps are dealt evenly, part c covers the 8 * ceil(K / 32 / (8 * ksplit))
+ * k-steps from c times that many on (K = 2080: 1280 + 800 columns), the last part what is left. */
+int dfl_batch_ksplit(int K);
 /* workspace of the fused-epilogue batched GEMMs: arrival tickets (ZEROED once by the caller,
  * left zero by every launch), argmax candidates, fp32 partial tiles of the K parts */
 int64_t dfl_gemm_batch_ws_bytes(int N, int K);
@@ -552,7 +555,13 @@ int dfl_embed_rows_batch(const void *embed, const int64_t *ids, int64_t ids_stri
  * Qwen3RMSNorm, tf:models/qwen3/modeling_qwen3.py:59-64):
  *   h[r][m]   <- part ? bf16(h[r][m] + bf16(sum_{k<nsplit} part[k*part_split + (r*16+m)*ldp ..])) : h[r][m]
  *   tap[r][m] <- that row (optional: a tapped target layer, model/utils.py:16-25)
- *   frag[r]   <- norm_w * bf16(h * rstd);  rows >= dyn[r][dyn_word]: frag zeroed, h untouched.
+ *   frag[r]   <- norm_w * bf16(h * rstd);  rows >= dyn[r][dyn_word] (all 16 rows count when dyn is NULL): frag zeroed,
+ *                h AND tap untouched (a tap row keeps what it held), their part rows loaded but ignored (readable memory, any contents).
+ * The sum starts from an fp32 zero and takes the parts in the order k = 0, 1, ...; part k of request r's row m starts at
+ * part + k * part_split + (r * 16 + m) * ldp — for dfl_gemm_f32_batch's output part_split = dfl_batch_tiles(R) * 16 * N
+ * and ldp = N, whatever number of tile slots the caller's other buffers have.  Only the requests r < R are touched.
+ * H % 8 == 0, H <= 16384; ldh >= H, ldh % 8 == 0; ldp >= H, ldp % 4 == 0, nsplit >= 1 (with part); ldtap >= H,
+ * ldtap % 8 == 0 (with tap); frag_stride >= 16 * H, % 8 == 0; 1 <= R <= 4: DFL_EINVAL otherwise, nothing launched.
  * `part` = the fp32 K-part sums of the o_proj / down_proj GEMM just before it
  * (dfl_gemm_f32_batch): the parts meet at this launch boundary — the kernel reads every h row
  * anyway — instead of inside the GEMM.  The batched GEMMs read their normalised operand from
