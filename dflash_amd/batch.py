@@ -53,7 +53,7 @@ class BatchedDecoder:
     def __init__(self, model: DFlashDraftModel, target: NativeTarget, n_requests: int, max_rows: int,
                  out_len: int, mask_token_id: int, stop_token_ids=None, max_splits: int = 32,
                  temperature: float = 0.0, tiles_per_request: int = 1, sampler: str = "torch",
-                 draft_temperature: float = 0.0):
+                 draft_temperature: float = 0.0, filtering: bool = False):
         if not isinstance(target, NativeTarget):
             raise TypeError("BatchedDecoder needs a dflash_amd.NativeTarget (see module docstring)")
         if tiles_per_request not in (1, 2):
@@ -65,6 +65,9 @@ class BatchedDecoder:
         if draft_temperature >= 1e-5 and sampler != "device":
             raise NotImplementedError("a sampled draft in the ragged batch needs sampler='device'")
         resolve_seed(sampler, None, needed=False)   # (validates the name)
+        if filtering and temperature >= 1e-5 and sampler != "device":
+            raise ValueError("top_k / top_p at T > 0 need sampler='device' (sampler='torch' is the reference's unfiltered "
+                             "multinomial)")
         if model.w is None:
             raise RuntimeError("draft weights not loaded")
         c, t = model.config, target
@@ -105,6 +108,13 @@ class BatchedDecoder:
         self.ids_tmp = z(MT, 16, dt=I64)      # TPR = 2: the draft's ids of every tile row (row 0 of tile 0 is not a draft token)
         self.result = z(MT, 4, dt=I32)
         self.seeds = z(NREQ, dt=I64)
+        # filtering (fixed here: it fixes the captured launch sequence): the verify materialises its logits and
+        # dfl_sample_rows_nucleus draws under each slot's top_k / top_p (0 / 1.0: that slot's plain draw, same ids as the
+        # fused epilogue's); at T = 0 the argmax is always kept and the greedy path runs unchanged
+        self.filtering = bool(filtering) and self.temperature >= 1e-5
+        self.top_k, self.top_p = z(NREQ, dt=I32), torch.ones(NREQ, dtype=F32, device=dev)
+        if self.filtering:
+            self._logits = z(MT, 16, target.V)
         self.output_ids = torch.full((NREQ, out_len), self.mask_id, dtype=I64, device=dev)
         self.stop_t = torch.tensor(stop_token_ids, dtype=I64, device=dev) if stop_token_ids else None
         # ---- draft scratch
@@ -167,11 +177,17 @@ class BatchedDecoder:
             self.events.setdefault(key, [None, None])[which] = e
 
     # ------------------------------------------------------------------ admission
-    def _admit_prefill(self, r: int, input_ids: torch.Tensor, temperature: float, seed: Optional[int]):
+    def _admit_prefill(self, r: int, input_ids: torch.Tensor, temperature: float, seed: Optional[int], top_k=0,
+                       top_p=1.0):
         """The launches both admissions share: target prefill into slot r's cache, the first token, the prompt's context
         rows into the draft cache except the last <= 16.  Returns (P, first token [1, 1] on the device, tapped rows
         [P, fc_in], the seed written for the slot or None)."""
         m, t = self.model, self.target
+        flt = None
+        if ops.check_filter(top_k, top_p) and temperature >= 1e-5:
+            if not self.filtering:
+                raise ValueError("admit: top_k / top_p need a decoder built with filtering=True (and sampler='device')")
+            flt = dict(top_k=int(top_k), top_p=float(top_p))
         if input_ids.shape[0] != 1 or not input_ids.is_cuda:
             raise ValueError("admit: input_ids must be a [1, P] GPU tensor")
         P = input_ids.shape[1]
@@ -186,9 +202,13 @@ class BatchedDecoder:
         sd = None
         if self.sampler == "device" and (temperature >= 1e-5 or self.temperature >= 1e-5):
             sd = resolve_seed("device", seed)
-            first = _draw_rows(out.logits[:, -1:], temperature, sd, P) if temperature >= 1e-5 else sample(out.logits, 0.0)
+            first = (_draw_rows(out.logits[:, -1:], temperature, sd, P, flt) if temperature >= 1e-5
+                     else sample(out.logits, 0.0))
         else:
             first = sample(out.logits, temperature)
+        # the slot's filter, re-armed on every admission (0 / 1.0: off); two small fills, admissions are never captured
+        self.top_k[r:r + 1].fill_(flt["top_k"] if flt else 0)
+        self.top_p[r:r + 1].fill_(flt["top_p"] if flt else 1.0)
         th = _taps(out.hidden_states, m.target_layer_ids)[0]          # [P, fc_in]
         n_tail = min(16, P)
         dc = _View(self.dk[r], self.dv[r], torch.zeros(8, dtype=I32, device=self.dev), self.max_rows)
@@ -197,12 +217,14 @@ class BatchedDecoder:
         return P, first, th, sd
 
     @torch.inference_mode()
-    def admit(self, r: int, input_ids: torch.Tensor, temperature: float = 0.0, seed: Optional[int] = None) -> None:
+    def admit(self, r: int, input_ids: torch.Tensor, temperature: float = 0.0, seed: Optional[int] = None,
+              top_k: int = 0, top_p: float = 1.0) -> None:
         """Prefill request r (model/dflash.py:218-229): target prefill through the wrapped
         model, K/V into the group cache, first token sampled, the prompt's context rows
         projected into the draft cache except the last <= 16, which become the first
-        cycle's context tile.  seed (sampler="device"): the request's seed (None: one from torch's RNG)."""
-        P, first, th, sd = self._admit_prefill(r, input_ids, temperature, seed)
+        cycle's context tile.  seed (sampler="device"): the request's seed (None: one from torch's RNG).
+        top_k / top_p: the request's filter (a decoder built with filtering=True), written into the slot's device words."""
+        P, first, th, sd = self._admit_prefill(r, input_ids, temperature, seed, top_k, top_p)
         self.output_ids[r].fill_(self.mask_id)
         self.output_ids[r, :P] = input_ids[0]
         if sd is not None:
@@ -224,7 +246,8 @@ class BatchedDecoder:
         self.start[r], self.n_in[r], self.live[r], self.hook_calls[r], self.bs[r] = P, P, True, 0, BW
 
     @torch.inference_mode()
-    def admit_fused(self, r: int, input_ids: torch.Tensor, temperature: float = 0.0, seed: Optional[int] = None) -> None:
+    def admit_fused(self, r: int, input_ids: torch.Tensor, temperature: float = 0.0, seed: Optional[int] = None,
+                    top_k: int = 0, top_p: float = 1.0) -> None:
         """`admit` with the slot re-armed by ONE launch (dfl_admit_slot) instead of a dozen small writes: ids, first
         token, block, context tile, both length records and the seed are written on the device from device-resident
         inputs, so that after the prefill launches the admission reads nothing back and copies nothing from the host —
@@ -234,7 +257,7 @@ class BatchedDecoder:
             raise NotImplementedError("admit_fused re-arms one 16-row tile per request; use admit() with tiles_per_request=2")
         if not 0 <= r < self.R:
             raise ValueError(f"admit_fused: slot {r} outside 0..{self.R - 1}")
-        P, first, th, sd = self._admit_prefill(r, input_ids, temperature, seed)
+        P, first, th, sd = self._admit_prefill(r, input_ids, temperature, seed, top_k, top_p)
         n_tail = min(16, P)
         ops.admit_slot(r, input_ids[0].contiguous(), first.reshape(1), self.output_ids, self.block, self.post, self.result,
                        th[P - n_tail:], self.d["taps"], self.dyn_d, self.dyn_t, self.BW, self.mask_id,
@@ -348,6 +371,12 @@ class BatchedDecoder:
         if self.temperature < 1e-5:
             ops.gemm_argmax_batch(self.lm_wp, s["xn"], R, t.V, H, 0, 16, self.gws, self.post.view(-1, 16), 0, dyn_t,
                                   nrows_dyn_word=ops.DYN_BS)
+        elif self.filtering:   # materialise, then the filtered draw: tile j row m -> start + 16 j + m + 1
+            ops.gemm_argmax_batch(self.lm_wp, s["xn"], R, t.V, H, 0, 16, self.gws, self.post.view(-1, 16), 0, dyn_t,
+                                  nrows_dyn_word=ops.DYN_BS, logits=self._logits)
+            ops.sample_rows_nucleus(self._logits[:R], seed=self.seeds, top_k=self.top_k, top_p=self.top_p,
+                                    temperature=self.temperature, dyn=dyn_t, nrows_dyn_word=ops.DYN_BS,
+                                    pos_word=ops.DYN_POS0, pos_add=1, tiles_per_req=TPR, out=self.post.view(-1, 16))
         elif self.sampler == "device":   # the seeded draw in the lm_head epilogue: tile j row m -> start + 16 j + m + 1
             ops.gemm_sample_batch(self.lm_wp, s["xn"], R, t.V, H, 0, 16, self.gws, self.post.view(-1, 16), 0, dyn_t,
                                   seeds=self.seeds, temperature=self.temperature, pos_word=ops.DYN_POS0, pos_add=1,
@@ -483,20 +512,36 @@ def _prompt_seeds(sampler: str, seed, n: int, sampling: bool) -> list:
     return seeds
 
 
+def _prompt_filters(top_k, top_p, n: int, temperature: float, sampler: str):
+    """(top_k per prompt, top_p per prompt, whether any prompt filters a sampled draw) from scalars or sequences."""
+    ks = [top_k] * n if isinstance(top_k, int) else list(top_k)
+    ps = [top_p] * n if isinstance(top_p, (int, float)) else list(top_p)
+    if len(ks) != n or len(ps) != n:
+        raise ValueError("top_k / top_p: a scalar or one value per prompt")
+    on = [ops.check_filter(k, p) for k, p in zip(ks, ps)]
+    filtering = any(on) and temperature >= 1e-5
+    if filtering and sampler != "device":
+        raise ValueError("top_k / top_p at T > 0 need sampler='device' (sampler='torch' is the reference's unfiltered "
+                         "multinomial)")
+    return [int(k) for k in ks], [float(p) for p in ps], filtering
+
+
 @torch.inference_mode()
 def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_ids: Sequence[torch.Tensor],
                           mask_token_id: int, max_new_tokens: int, block_size: int, stop_token_ids,
                           temperature: float = 0.0, draft_token_hook: Optional[Callable] = None,
                           group_size: int = MAX_GROUP, hook_block_view: bool = False, sampler: str = "torch",
-                          seed=None) -> list:
+                          seed=None, top_k=0, top_p=1.0) -> list:
     """`dflash_generate` (benchmark.py:44-251) for a list of prompts: requests run in
     groups of `group_size` <= 4 (<= 2 with block sizes of 17..32 rows) that share the weight stream; returns one namespace per
     prompt with the fields of benchmark.py:242-251 (timing fields are the group's).
     draft_token_hook(request_index, block, start, call).
     sampler="device": seeded draws on the device; seed is an int s (prompt i gets s + i), one seed
     per prompt, or None (one per prompt from torch's RNG).  Request i then emits what dflash_generate(..., seed=its seed)
-    emits, however the group is formed."""
+    emits, however the group is formed.
+    top_k / top_p: a scalar, or one value per prompt (0 / 1.0: off), as in dflash_generate."""
     seeds = _prompt_seeds(sampler, seed, len(input_ids), temperature >= 1e-5)
+    top_ks, top_ps, filtering = _prompt_filters(top_k, top_p, len(input_ids), temperature, sampler)
     if not 1 <= block_size <= 32:
         raise NotImplementedError("the batched loop takes blocks of 1..16 rows (one tile per request) or 17..32 rows (two)")
     tpr = 1 if block_size <= 16 else 2      # blocks of 17..32 rows: a request takes two of the group's four tiles
@@ -511,10 +556,10 @@ def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_i
         dec = BatchedDecoder(model, target, len(idx), max_rows=pmax + max_new_tokens + 3 * 16 * tpr,
                              out_len=pmax + max_new_tokens + 16 * tpr, mask_token_id=mask_token_id,
                              stop_token_ids=stop_token_ids, temperature=temperature, tiles_per_request=tpr,
-                             sampler=sampler)
+                             sampler=sampler, filtering=filtering)
         t0 = cuda_time()
         for r, p in enumerate(prompts):
-            dec.admit(r, p, temperature, seed=seeds[idx[r]])
+            dec.admit(r, p, temperature, seed=seeds[idx[r]], top_k=top_ks[idx[r]], top_p=top_ps[idx[r]])
         ttft = cuda_time() - t0
         taus = [[] for _ in idx]
         # (hook_block_view: the hook sees the block as the single-request loop hands it over, bs slots; default: the

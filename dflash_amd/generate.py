@@ -111,10 +111,30 @@ def resolve_seed(sampler: str, seed: Optional[int], needed: bool = True) -> Opti
     return int(seed) & 0xFFFFFFFFFFFFFFFF
 
 
-def _draw_rows(logits: torch.Tensor, temperature: float, seed: int, pos0: int) -> torch.Tensor:
-    """The device sampler over materialised logits [1, T, V]: row j draws position pos0 + j (stream TARGET)."""
+def resolve_filter(top_k, top_p, temperature: float, sampler: str) -> Optional[dict]:
+    """Validate (top_k, top_p); the keywords of the filtered draw ("Filtered draw") if a filter is on
+    and the run samples, else None: at T = 0 the argmax is always kept, so the greedy path runs unchanged."""
+    on = ops.check_filter(top_k, top_p)
+    if not on or temperature < 1e-5:
+        return None
+    if sampler != "device":
+        raise ValueError("top_k / top_p at T > 0 need sampler='device' (sampler='torch' is the reference's unfiltered "
+                         "multinomial)")
+    return dict(top_k=int(top_k), top_p=float(top_p))
+
+
+def _draw_rows(logits: torch.Tensor, temperature: float, seed: int, pos0: int, flt: Optional[dict] = None) -> torch.Tensor:
+    """The device sampler over materialised logits [1, T, V]: row j draws position pos0 + j (stream TARGET); flt: the
+    top_k / top_p of the filtered draw, one launch per 16-row tile."""
     _, t, v = logits.shape
-    return ops.sample_rows(logits.reshape(t, v), seed=seed, temperature=temperature, pos0=pos0).view(1, t)
+    rows = logits.reshape(t, v)
+    if flt is None:
+        return ops.sample_rows(rows, seed=seed, temperature=temperature, pos0=pos0).view(1, t)
+    out = torch.empty(t, dtype=torch.long, device=logits.device)
+    for r0 in range(0, t, 16):
+        ops.sample_rows_nucleus(rows[r0:r0 + 16], seed=seed, temperature=temperature, pos_base=pos0 + r0, out=out[r0:r0 + 16],
+                                **flt)
+    return out.view(1, t)
 
 
 def _trim(output_ids, max_length, mask_token_id, stop_token_ids, n_in):
@@ -135,7 +155,8 @@ class DecodeSession:
 
     def __init__(self, model, target, input_ids: torch.Tensor, *, mask_token_id: int, max_new_tokens: int,
                  max_block_size: int, stop_token_ids, temperature: float, draft_temperature: float = 0.0,
-                 draft_token_hook: Optional[Callable] = None, sampler: str = "torch", seed: Optional[int] = None):
+                 draft_token_hook: Optional[Callable] = None, sampler: str = "torch", seed: Optional[int] = None,
+                 top_k: int = 0, top_p: float = 1.0):
         dev = model.device
         if not input_ids.is_cuda:
             raise RuntimeError("dflash_amd: input_ids must be on the GPU")
@@ -154,6 +175,10 @@ class DecodeSession:
         self.seed = resolve_seed(sampler, seed, needed=temperature >= 1e-5 or draft_temperature >= 1e-5)
         self._tseed = self.seed if (self.seed is not None and temperature >= 1e-5) else None
         self._dseed = self.seed if (self.seed is not None and draft_temperature >= 1e-5) else None
+        # top_k / top_p restrict the TARGET's draw (the draft's own draw stays unfiltered: the target's draw alone
+        # decides what is emitted); None: the fused unfiltered epilogue
+        self._filter = resolve_filter(top_k, top_p, temperature, sampler)
+        self._fkw = {} if self._filter is None else self._filter
         # T > 0 cycles can be replayed only with the device sampler (the torch draw consumes host RNG state)
         self.replay_sampling_ok = sampler == "device" or (temperature < 1e-5 and draft_temperature < 1e-5)
         self.stop_token_ids = stop_token_ids
@@ -218,7 +243,7 @@ class DecodeSession:
         self.output_ids[:, :self.n_in] = self.input_ids
         if self._tseed is not None:   # the first new token draws position n_in
             self.output_ids[:, self.n_in:self.n_in + 1] = _draw_rows(out.logits[:, -1:], self.temperature, self._tseed,
-                                                                     self.n_in)
+                                                                     self.n_in, self._filter)
         else:
             self.output_ids[:, self.n_in:self.n_in + 1] = sample(out.logits, self.temperature)
         if self.use_draft:
@@ -332,14 +357,14 @@ class DecodeSession:
             posterior, taps = self.target.verify(
                 blk[0], start, self.tcache, temperature=self.temperature,
                 tap_layers=self.model.target_layer_ids if (want_hidden and self.use_draft) else (),
-                taps_out=self.taps_buf, seed=self._tseed)
+                taps_out=self.taps_buf, seed=self._tseed, **self._fkw)
             self._mark("target", 1)
         else:
             out = self.target(blk, position_ids=self.position_ids[:, start:start + bs],
                               past_key_values=self.tcache, use_cache=True, output_hidden_states=want_hidden)
             self._mark("target", 1)
             if self._tseed is not None:   # verify row j predicts position start + j + 1
-                posterior = _draw_rows(out.logits, self.temperature, self._tseed, start + 1)
+                posterior = _draw_rows(out.logits, self.temperature, self._tseed, start + 1, self._filter)
             else:
                 posterior = sample(out.logits, self.temperature)
         # ---- accept scan + commit + bookkeeping on the device (:258-268)
@@ -443,7 +468,7 @@ class DecodeSession:
 
         def verify_accept():   # (a T > 0 draw takes its positions from the target record's POS0 word: fresh every replay)
             post, _ = t.verify(self.block[0, :bs], bound, self.tcache, temperature=self.temperature, tap_layers=tl,
-                               taps_out=self.taps_buf, dyn_lengths=True, seed=self._tseed)
+                               taps_out=self.taps_buf, dyn_lengths=True, seed=self._tseed, **self._fkw)
             ops.accept_commit(self.block[0, :bs], post[0].contiguous(), bs, self.output_ids[0], self.dyn, self.stop_t,
                               self.result, rearm=(self.block[0], self.max_bs, self.mask_token_id), dyn_t=self.tcache.dyn)
 
@@ -540,7 +565,7 @@ class DecodeSession:
 
             def verify_accept(bs=bs):
                 post, _ = t.verify(self.block[0, :bs], bound, self.tcache, temperature=self.temperature, tap_layers=tl,
-                                   taps_out=self.taps_buf, dyn_lengths=True, seed=self._tseed)
+                                   taps_out=self.taps_buf, dyn_lengths=True, seed=self._tseed, **self._fkw)
                 ops.accept_commit(self.block[0, :bs], post[0].contiguous(), bs, self.output_ids[0], self.dyn, self.stop_t,
                                   self.result, rearm=(self.block[0], self.max_bs, self.mask_token_id), dyn_t=self.tcache.dyn)
 
@@ -623,11 +648,12 @@ def run_decode(model, target, input_ids: torch.Tensor, *, mask_token_id: int, ma
                block_size: int, stop_token_ids, temperature: float, clamp_tail: bool,
                draft_steps: int = 1, collect_profile: bool = False, scheduler=None,
                draft_temperature: float = 0.0, draft_token_hook: Optional[Callable] = None,
-               max_block_size: Optional[int] = None, sampler: str = "torch", seed: Optional[int] = None) -> SimpleNamespace:
+               max_block_size: Optional[int] = None, sampler: str = "torch", seed: Optional[int] = None,
+               top_k: int = 0, top_p: float = 1.0) -> SimpleNamespace:
     s = DecodeSession(model, target, input_ids, mask_token_id=mask_token_id, max_new_tokens=max_new_tokens,
                       max_block_size=max_block_size or block_size, stop_token_ids=stop_token_ids,
                       temperature=temperature, draft_temperature=draft_temperature,
-                      draft_token_hook=draft_token_hook, sampler=sampler, seed=seed)
+                      draft_token_hook=draft_token_hook, sampler=sampler, seed=seed, top_k=top_k, top_p=top_p)
     t_prefill = cuda_time()
     s.prefill()
     time_to_first_token = cuda_time() - t_prefill
@@ -787,17 +813,18 @@ def _resolve_profile(cycle_trace, ttft, decode_wall):
 def dflash_generate(model, target, input_ids: torch.Tensor, mask_token_id: int, max_new_tokens: int,
                     block_size: int, stop_token_ids, temperature: float = 0.0, collect_profile: bool = False,
                     draft_steps: int = 1, draft_token_hook=None, sampler: str = "torch",
-                    seed: Optional[int] = None) -> SimpleNamespace:
+                    seed: Optional[int] = None, top_k: int = 0, top_p: float = 1.0) -> SimpleNamespace:
     """benchmark.py:44-55 signature; returns the namespace of :242-251 (+ replayed_cycles).
     sampler="device": T > 0 draws are seeded on the device — the same seed gives the same tokens
-    however the request runs, and the cycles can be replayed from hipGraphs; seed=None draws one from torch's RNG."""
+    however the request runs, and the cycles can be replayed from hipGraphs; seed=None draws one from torch's RNG.
+    top_k / top_p (0 / 1.0: off) restrict the target's seeded draw (section 8, "Filtered draw"); sampler="device" only."""
     if getattr(model, "wide_hidden", False):
         return _generate_wide_hidden(model, target, input_ids, mask_token_id, max_new_tokens, block_size, stop_token_ids,
-                                     temperature, collect_profile, draft_steps, draft_token_hook, sampler, seed)
+                                     temperature, collect_profile, draft_steps, draft_token_hook, sampler, seed, top_k, top_p)
     r = run_decode(model, target, input_ids, mask_token_id=mask_token_id, max_new_tokens=max_new_tokens,
                    block_size=block_size, stop_token_ids=stop_token_ids, temperature=temperature, clamp_tail=True,
                    draft_steps=draft_steps, collect_profile=collect_profile, draft_token_hook=draft_token_hook,
-                   sampler=sampler, seed=seed)
+                   sampler=sampler, seed=seed, top_k=top_k, top_p=top_p)
     return SimpleNamespace(output_ids=r.output_ids, num_input_tokens=r.num_input_tokens,
                            num_output_tokens=r.num_output_tokens, time_to_first_token=r.time_to_first_token,
                            time_per_output_token=r.time_per_output_token, acceptance_lengths=r.acceptance_lengths,
@@ -807,7 +834,7 @@ def dflash_generate(model, target, input_ids: torch.Tensor, mask_token_id: int, 
 
 def _generate_wide_hidden(model, target, input_ids, mask_token_id, max_new_tokens, block_size, stop_token_ids, temperature,
                           collect_profile=False, draft_steps=1, draft_token_hook=None, sampler="torch",
-                          seed=None) -> SimpleNamespace:
+                          seed=None, top_k=0, top_p=1.0) -> SimpleNamespace:
     """hidden_size > 4096: the request runs as a group of ONE through the ragged-batch kernels (their GEMMs cut K over
     workgroups; the single-request kernels keep a whole K = hidden row slice per workgroup).  Same loop semantics
     (benchmark.py:44-251, tail clamp included); no per-cycle profile, one draft step per cycle."""
@@ -821,15 +848,16 @@ def _generate_wide_hidden(model, target, input_ids, mask_token_id, max_new_token
     hook = (lambda r, blk, start, call: draft_token_hook(blk, start, call)) if draft_token_hook else None
     return dflash_generate_batch(model, target, [input_ids], mask_token_id, max_new_tokens, block_size, stop_token_ids,
                                  temperature, draft_token_hook=hook, group_size=1, hook_block_view=True, sampler=sampler,
-                                 seed=None if seed is None else [seed])[0]
+                                 seed=None if seed is None else [seed], top_k=top_k, top_p=top_p)[0]
 
 
 def dflash_generate_policy(*, model, target, input_ids: torch.Tensor, mask_token_id: int, max_new_tokens: int,
                            stop_token_ids, temperature: float, fixed_block_size: Optional[int] = None,
                            scheduler=None, draft_token_hook=None, sampler: str = "torch",
-                           seed: Optional[int] = None) -> SimpleNamespace:
+                           seed: Optional[int] = None, top_k: int = 0, top_p: float = 1.0) -> SimpleNamespace:
     """benchmark_dynamic_schedule.py:260-272 signature; returns the namespace of :425-434 (+ replayed_cycles).
-    sampler / seed: as dflash_generate; the draft's own T > 0 draw uses the same seed on a stream of its own."""
+    sampler / seed: as dflash_generate; the draft's own T > 0 draw uses the same seed on a stream of its own.
+    top_k / top_p: as dflash_generate (the target's draw; the draft's own draw stays unfiltered)."""
     if fixed_block_size is None and scheduler is None:
         raise ValueError("Either fixed_block_size or scheduler must be provided.")
     max_bs = fixed_block_size if fixed_block_size is not None else max(scheduler.candidates)
@@ -837,7 +865,7 @@ def dflash_generate_policy(*, model, target, input_ids: torch.Tensor, mask_token
     r = run_decode(model, target, input_ids, mask_token_id=mask_token_id, max_new_tokens=max_new_tokens,
                    block_size=max_bs, stop_token_ids=stop_token_ids, temperature=temperature, clamp_tail=True,
                    scheduler=sched, draft_temperature=temperature, max_block_size=max_bs,
-                   draft_token_hook=draft_token_hook, sampler=sampler, seed=seed)
+                   draft_token_hook=draft_token_hook, sampler=sampler, seed=seed, top_k=top_k, top_p=top_p)
     if fixed_block_size is not None:
         for row in r.cycle_trace:
             for k in ("tau_hat", "cycle_hat", "score_hat", "current_block_size", "adl_lgen_hat", "adl_lacc_hat",

@@ -232,6 +232,78 @@ def sample_rows(logits: torch.Tensor, *, seed: int, temperature: float, pos0: in
     return out
 
 
+def check_filter(top_k, top_p) -> bool:
+    """Validate one request's (top_k, top_p); True if either filter is on (top_k = 0 and top_p = 1.0 are "off")."""
+    if int(top_k) != top_k or int(top_k) < 0:
+        raise ValueError(f"dflash_amd: top_k must be an integer >= 0 (0 = off), got {top_k!r}")
+    if not (0.0 < float(top_p) <= 1.0):
+        raise ValueError(f"dflash_amd: top_p must be inside (0, 1] (1.0 = off), got {top_p!r}")
+    return int(top_k) > 0 or float(top_p) < 1.0
+
+
+def sample_rows_nucleus(logits: torch.Tensor, *, temperature: float, top_k=0, top_p=1.0, seed=0, row0: int = 0,
+                        nrows: Optional[int] = None, dyn=None, nrows_dyn_word: int = -1, pos_word: int = -1,
+                        pos_base: int = 0, positions=None, pos_add: int = 0, tiles_per_req: int = 1,
+                        stream: int = RNG_TARGET, extra: int = 0, out: Optional[torch.Tensor] = None, out_off: int = 0,
+                        thresholds: Optional[torch.Tensor] = None, kept: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The seeded draw under top-k / top-p (dfl_sample_rows_nucleus) over materialised bf16 logits
+    [rows <= 16, V] (one tile) or [tiles, 16, V], unit inner stride.
+    seed / top_k / top_p: a host value, or a device tensor (int64 / int32 / fp32) indexed by request slot
+    q = tile // tiles_per_req.  Tile t row m draws position positions[16 t + m] (int32 tensor), or
+    (dyn[t][pos_word] if pos_word >= 0 else pos_base) + pos_add + 16 (t % tiles_per_req) + m.  Rows of a tile:
+    row0 .. dyn[t][nrows_dyn_word] if nrows_dyn_word >= 0, else row0 .. row0 + nrows.
+    Returns int64 ids (`out` if given: [tiles, n] or, for one tile, [n]) at out[t, out_off + m - row0]; `thresholds`
+    (fp32) and `kept` (int32), shaped and indexed like out, receive the final threshold and the kept-set size."""
+    assert logits.dim() in (2, 3) and logits.stride(-1) == 1 and logits.is_cuda
+    if logits.dtype != BF16:
+        logits = logits.to(BF16)
+    if logits.dim() == 2:
+        assert logits.shape[0] <= 16, "one tile holds at most 16 rows"
+        tiles, tile_rows, tile_stride = 1, logits.shape[0], 16 * logits.stride(0)
+    else:
+        assert logits.shape[1] == 16
+        tiles, tile_rows, tile_stride = logits.shape[0], 16, logits.stride(0)
+    V, ld = logits.shape[-1], logits.stride(-2)
+    if nrows is None:
+        nrows = tile_rows - row0
+    assert 0 <= row0 and row0 + nrows <= tile_rows or nrows_dyn_word >= 0 and tile_rows == 16
+    n_out = 16 - row0 if nrows_dyn_word >= 0 else nrows
+    if out is None:
+        out = torch.empty((tiles, out_off + n_out) if logits.dim() == 3 else (out_off + n_out,), dtype=I64,
+                          device=logits.device)
+    out_stride = out.stride(0) if out.dim() == 2 else 0
+    for o, nm in ((out, "out"), (thresholds, "thresholds"), (kept, "kept")):
+        if o is not None:
+            assert o.dim() == out.dim() and o.stride(-1) == 1 and (o.dim() == 1 or o.stride(0) == out_stride), nm
+            assert o.shape[-1] >= out_off + n_out and (o.dim() == 1 and tiles == 1 or o.shape[0] >= tiles), nm
+    if positions is not None:
+        assert positions.numel() >= 16 * (tiles - 1) + row0 + n_out
+    if dyn is not None:
+        assert dyn.numel() >= 8 * tiles
+    slots = (tiles + tiles_per_req - 1) // tiles_per_req
+
+    def dev_or_host(v, dtype, name, host):
+        if torch.is_tensor(v):
+            assert v.numel() >= slots, name
+            return _p(v, dtype, name), host(0)
+        return None, host(v)
+
+    if not torch.is_tensor(top_k) or not torch.is_tensor(top_p):
+        check_filter(0 if torch.is_tensor(top_k) else top_k, 1.0 if torch.is_tensor(top_p) else top_p)
+    seeds_p, seed_v = dev_or_host(seed, I64, "seed", _seed64)
+    k_p, k_v = dev_or_host(top_k, I32, "top_k", int)
+    p_p, p_v = dev_or_host(top_p, F32, "top_p", float)
+    if p_p is not None:
+        p_v = 1.0
+    check(lib().dfl_sample_rows_nucleus(logits.data_ptr(), ld, tile_stride, tiles, V, row0, nrows, _p(dyn, I32, "dyn"),
+                                        nrows_dyn_word, pos_word, pos_base, _p(positions, I32, "positions"), pos_add,
+                                        tiles_per_req, seeds_p, seed_v, k_p, k_v, p_p, p_v,
+                                        inv_temperature(temperature), stream, extra, _p(out, I64, "out"), out_stride,
+                                        out_off, _p(thresholds, F32, "thresholds"), _p(kept, I32, "kept"), _stream()),
+          "dfl_sample_rows_nucleus")
+    return out
+
+
 def gemm_resid(wp, x, N: int, K: int, h_io: torch.Tensor, *, add_residual: bool, ss_out=None, tap=None,
                dyn=None) -> None:
     """h_io [16, >=N] bf16 (unit inner stride) updated in place; tap: optional [16, *] view

@@ -99,6 +99,7 @@ class NativeTarget:
         # single-request GEMMs once per 16-row tile (two passes; kept for A/B and as a second implementation for tests)
         self.wide_one_pass = True
         self._wide = None
+        self._nuc_logits = None   # bf16 [32, V], made on the first filtered verify (top_k / top_p)
         self.moe_pair_kernel = True   # MoE gate/up at K <= 2048 through dfl_moe_gate_up (False: the general kernel)
         self.moe_shared_pass = True   # three or four tiles (ragged batch, candidates): one pass over the experts they share
         self.moe_shared_min = 2       # tiles from which the shared pass is taken (30B-A3B layer: 2 tiles 291 -> 216 us, 4: 576 -> 241)
@@ -530,7 +531,14 @@ class NativeTarget:
         return 1
 
     # ---- the verify forward on the kernels
-    def _verify_wide(self, block_ids, start, cache, bs, tap_layers, taps, logits_out, temperature, cos, sin, seed=None):
+    def _nucleus_logits(self) -> torch.Tensor:
+        """bf16 [32, V]: where a filtered verify materialises its logits (kept: a captured cycle replays into it)."""
+        if self._nuc_logits is None:
+            self._nuc_logits = torch.zeros(32, self.V, dtype=BF16, device=self._dev)
+        return self._nuc_logits
+
+    def _verify_wide(self, block_ids, start, cache, bs, tap_layers, taps, logits_out, temperature, cos, sin, seed=None,
+                     flt=None):
         """Blocks of 17..32 rows in ONE pass over the weights: the two 16-row tiles go through the ragged-batch
         GEMMs (tile_stack.TileStack, R = 2) as if they were two requests, and through ONE attention launch per layer with
         two query tiles on the request's single cache.  Same lines as verify(): model/dflash.py:249-257."""
@@ -559,11 +567,18 @@ class NativeTarget:
         st.finish(self.norm)
         post = ws["post"]
         logits = logits_out
-        if temperature >= 1e-5:
+        if flt is not None and logits is None:
+            logits = self._nucleus_logits()
+        elif temperature >= 1e-5:
             logits = torch.empty(32, self.V, dtype=BF16, device=self._dev)
         ops.gemm_argmax_batch(self.lm_wp, s["xn"], R, self.V, H, 0, 16, gws, post.view(2, 16), 0, dyn2,
                               nrows_dyn_word=ops.DYN_BS, logits=None if logits is None else logits.view(2, 16, self.V))
-        if temperature >= 1e-5 and seed is not None:   # the seeded draw over the materialised rows: row j -> start + j + 1
+        if flt is not None:   # the filtered draw, host-position form: tile t row m -> start + 16 t + m + 1
+            ops.sample_rows_nucleus(logits.view(2, 16, self.V), seed=seed, temperature=temperature, dyn=dyn2,
+                                    nrows_dyn_word=ops.DYN_BS, pos_base=start, pos_add=1, tiles_per_req=2,
+                                    out=post.view(2, 16), **flt)
+            posterior = post[:bs].unsqueeze(0)
+        elif temperature >= 1e-5 and seed is not None:   # the seeded draw over the materialised rows: row j -> start + j + 1
             ops.sample_rows(logits[:bs], seed=seed, temperature=temperature, pos0=start + 1, out=post[:bs])
             posterior = post[:bs].unsqueeze(0)
         else:
@@ -580,7 +595,8 @@ class NativeTarget:
     @torch.inference_mode()
     def verify(self, block_ids: torch.Tensor, start: int, cache: TargetKVCache, *, tap_layers: Sequence[int] = (),
                temperature: float = 0.0, logits_out: Optional[torch.Tensor] = None,
-               taps_out: Optional[torch.Tensor] = None, dyn_lengths: bool = False, seed: Optional[int] = None):
+               taps_out: Optional[torch.Tensor] = None, dyn_lengths: bool = False, seed: Optional[int] = None,
+               top_k: int = 0, top_p: float = 1.0):
         """block_ids int64 [bs] at positions start..start+bs-1 (cache rows alike), bs <= 32.
         Returns (posterior ids int64 [1, bs], taps bf16 [32, len(tap_layers)*H] or None).
         K/V of all bs rows are written; the caller crops to what it accepts.
@@ -594,8 +610,15 @@ class NativeTarget:
         and the RoPE table, and the sequence can be captured into a hipGraph (DecodeSession.capture).
         seed (temperature > 0): the seeded Gumbel-max draw in the lm_head epilogue instead of softmax + multinomial —
         row j draws position start + j + 1, start from the record's POS0 word under dyn_lengths (DESIGN.md section 8);
-        no logits are written unless logits_out is given."""
+        no logits are written unless logits_out is given.
+        top_k / top_p (with seed, temperature > 0): the filtered draw (section 8, "Filtered draw") — the lm_head launch
+        materialises the block's logits and dfl_sample_rows_nucleus writes the posterior, positions as above."""
         bs = block_ids.numel()
+        flt = None
+        if ops.check_filter(top_k, top_p) and temperature >= 1e-5:
+            if seed is None:
+                raise ValueError("top_k / top_p at temperature > 0 need the seeded draw (seed=...)")
+            flt = dict(top_k=int(top_k), top_p=float(top_p))
         if self.wide_hidden:
             raise NotImplementedError("NativeTarget.verify: hidden > 4096 runs through the ragged-batch path "
                                       "(dflash_generate / dflash_generate_batch / BatchedDecoder)")
@@ -636,7 +659,8 @@ class NativeTarget:
                 taps = self._taps[key]
         Ls, src = self.layers, self.src
         if len(tiles) == 2 and self.wide_one_pass and self.attn_impl == "head":
-            return self._verify_wide(block_ids, start, cache, bs, tap_layers, taps, logits_out, temperature, cos, sin, seed)
+            return self._verify_wide(block_ids, start, cache, bs, tap_layers, taps, logits_out, temperature, cos, sin, seed,
+                                     flt)
         hrow = [ws["h"][16 * t:16 * t + 16] for t in range(2)]
         for t, dt in tiles:
             ops.embed_rows(self.embed, block_ids[16 * t:], hrow[t], H, ws["ss_emb"][16 * t:], dt, ops.DYN_BS)
@@ -696,6 +720,18 @@ class NativeTarget:
         post = ws["post"]
         logits = logits_out
         fin = src["xn1"] if prev_moe else src["final"]   # after an MoE layer the rows are final-normed already
+        if flt is not None:
+            if logits is None:
+                logits = self._nucleus_logits()
+            for t, dt in tiles:   # tile t row m predicts position start + 16 t + m + 1, start from the record when replayed
+                n = min(16, bs - 16 * t)
+                ops.gemm_argmax(self.lm_wp, fin[t], self.V, H, 0, n, ws["argmax_ws"], post, 16 * t, dyn=dt,
+                                logits=logits[16 * t:16 * t + 16])
+                ops.sample_rows_nucleus(logits[16 * t:16 * t + 16], seed=seed, temperature=temperature, nrows=n, dyn=dt,
+                                        pos_word=ops.DYN_POS0 if dyn_lengths else -1, pos_base=start, pos_add=16 * t + 1,
+                                        out=post[16 * t:16 * t + 16], **flt)
+            cache.length = start + bs
+            return post[:bs].unsqueeze(0), taps
         if temperature >= 1e-5 and seed is not None:
             for t, dt in tiles:   # tile t row m predicts position start + 16 t + m + 1
                 ops.gemm_sample(self.lm_wp, fin[t], self.V, H, 0, min(16, bs - 16 * t), ws["argmax_ws"], post, 16 * t,

@@ -382,6 +382,29 @@ int dfl_argmax(const void *logits, int dtype, int rows, int64_t V, int64_t *ids,
 int dfl_sample_rows(const void *logits, int64_t ld, int rows, int V, uint64_t seed, float inv_t, int rng_stream, int pos0,
                     const int32_t *pos, int extra, int64_t *out_ids, float *margin_out, void *stream);
 
+/* The seeded draw restricted by top-k and top-p ("Filtered draw") over materialised bf16 logits laid
+ * out as tiles [tiles][16][V] (row stride ld, tile stride tile_stride, in elements; V <= 155648).  Per row:
+ *   t_k = the top_k-th largest value (the row minimum if top_k == 0 or >= V);
+ *   t_p = the largest t with sum_{x >= t, x >= t_k} w >= top_p * sum_{x >= t_k} w, w = exp(inv_t (x - max));  top_p >= 1: t_k;
+ *   id  = argmax over {v : x_v >= max(t_k, t_p)} of fmaf(x_v, inv_t, noise of dfl_rng.h), lowest v on ties.
+ * Ties at a threshold are kept whole; with both filters off the ids are those of dfl_sample_rows.
+ * Rows: tile t takes rows row0 .. row0 + n, n = dyn[t][nrows_dyn_word] - row0 if nrows_dyn_word >= 0, else nrows (the
+ * convention of dfl_gemm_sample_batch); other rows are not written.  Tile t is tile j = t % tiles_per_req of request slot
+ * q = t / tiles_per_req.  Row m of it draws position
+ *   positions[16 t + m]                                         if positions != NULL (int32), else
+ *   (pos_word >= 0 ? dyn[t][pos_word] : pos_base) + pos_add + 16 j + m.
+ * The DRAFT stream with a record position takes that record word as its `extra` counter word; otherwise `extra`.
+ * seeds / top_k_dev / top_p_dev: device arrays (int64 / int32 / fp32) indexed by q, or NULL for the host value beside
+ * them; a device top_k < 0 or top_p outside (0, 1) reads as "off".  Everything a replayed launch needs is read by
+ * address.  out_ids[t * out_stride + out_off + (m - row0)]; thr_out (fp32: the final threshold) and kept_out (int32: the
+ * size of the kept set) are optional and indexed like out_ids. */
+int dfl_sample_rows_nucleus(const void *logits, int64_t ld, int64_t tile_stride, int tiles, int V, int row0, int nrows,
+                            const int32_t *dyn, int nrows_dyn_word, int pos_word, int pos_base, const int32_t *positions,
+                            int pos_add, int tiles_per_req, const int64_t *seeds, uint64_t seed, const int32_t *top_k_dev,
+                            int top_k, const float *top_p_dev, float top_p, float inv_t, int rng_stream, int extra,
+                            int64_t *out_ids, int64_t out_stride, int out_off, float *thr_out, int32_t *kept_out,
+                            void *stream);
+
 /* Acceptance scan + commit + bonus token + stop test + length bookkeeping in one
  * wavefront (model/dflash.py:258-268):
  *   acc = #leading i with block[i+1] == posterior[i]           (0..bs-1)

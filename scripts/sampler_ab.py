@@ -1,9 +1,12 @@
 """Same-box A/B of the two T > 0 samplers on BASELINE configs[3]'s workload (Llama-3.1-8B shapes, T = 0.7, prefix 1024,
 block 16, bench.py's scripted acceptance): sampler="torch" with eager cycles — what bench.py runs, its replay needs
-T < 1e-5 — against sampler="device" with the cycles replayed from hipGraphs.  The arms alternate,
+T < 1e-5 — against sampler="device" with the cycles replayed from hipGraphs; the arm
+"device_filtered" is the device arm with top_k=50, top_p=0.9 (the materialise + dfl_sample_rows_nucleus path; the plain
+device arm's launch sequence is the one from before that path existed).  The arms alternate,
 `--runs` timed runs each, on one set of models in one process; one JSON line per run, then a summary line.
 
     timeout -k 10 900 python scripts/sampler_ab.py --runs 3 --steps 48
+    timeout -k 10 900 python scripts/sampler_ab.py --runs 3 --steps 48 --arms device,device_filtered
 """
 from __future__ import annotations
 
@@ -37,10 +40,11 @@ def one_run(arm, draft, target, cfg, perm, V, P, steps, warmup, temperature, see
         if k + 1 < blk.shape[1]:
             blk[0, k + 1] = (G[start + k + 1] + 1) % (V - 1000)
 
-    device = arm == "device"
+    device = arm in ("device", "device_filtered")
+    flt = dict(top_k=50, top_p=0.9) if arm == "device_filtered" else {}
     s = DecodeSession(draft, target, prompt, mask_token_id=cfg.mask_token_id, max_new_tokens=need, max_block_size=bs,
                       stop_token_ids=None, temperature=temperature, draft_token_hook=hook,
-                      sampler="device" if device else "torch", seed=seed if device else None)
+                      sampler="device" if device else "torch", seed=seed if device else None, **flt)
     s.prefill()
     s.cycle(bs)
     for _ in range(1 + warmup):
