@@ -20,7 +20,7 @@ import gc
 import os
 import time
 from types import SimpleNamespace
-from typing import Callable, Optional
+from typing import Callable, NamedTuple, Optional
 
 import torch
 
@@ -65,6 +65,19 @@ def capture_graph(fn) -> "torch.cuda.CUDAGraph":
             gc.enable()
     cur.wait_stream(side)
     return g
+
+
+class GraphNotCovered(ValueError):
+    """capture / capture_sizes: this session, or the state it is in, is not one the graphs cover.  run_decode answers it
+    with eager cycles; anything else a capture raises is a failure and propagates."""
+
+
+class _Replay(NamedTuple):
+    """What a capture leaves behind, for the fixed-size form and for the caller-sized form alike."""
+    graphs: dict   # block size -> ([draft + lm_head] graph, [verify + accept] graph)
+    bound: int     # upper bound of S / start the captured launches were sized for
+    rope: tuple    # addresses of the draft model's and the target's RoPE tables at capture time
+    keep: tuple    # every tensor whose address sits in the launches and that the session does not own otherwise
 
 
 def _new_target_cache(target):
@@ -217,6 +230,9 @@ class DecodeSession:
         self._ahead = None
         self._ahead_ev = None
         self._armed = False   # True: the accept kernel has written the next cycle's block (bonus token + mask ids)
+        # hipGraph replay (capture / capture_sizes): one _Replay per form, None until captured or after a table moved
+        self._fixed = None    # one block size, the next cycle's draft running ahead (cycle_graph)
+        self._sized = None    # one pair of graphs per caller-chosen block size (cycle_sized)
         self.start = self.n_in
         self.target_hidden = None
         self.hook_calls = 0
@@ -274,20 +290,26 @@ class DecodeSession:
             ev[1].record()
         self._ahead, self._ahead_ev = bs, ev
 
+    def _call_hook(self, blk) -> None:
+        if self.hook is not None:
+            self.hook(blk, self.start, self.hook_calls)
+        self.hook_calls += 1
+
+    def _take_ahead(self, blk) -> None:
+        """This cycle's draft was enqueued behind the previous cycle's accept kernel: only the host's bookkeeping is left."""
+        self._ahead = None
+        self.dcache.length = self.start           # rows kept (S) + this cycle's context rows (tau) = the new start
+        self._dyn_bs = None
+        if self.events is not None and self._ahead_ev:   # its event pairs were recorded by the cycle that enqueued it
+            e = self._ahead_ev
+            self.events["draft"], self.events["lm_head"] = [e[0], e[1]], [e[2], e[3]]
+        self._call_hook(blk)
+
     def _draft(self, blk, bs, draft_steps):
         m = self.model
         ctx = self.target_hidden[0]
-        if draft_steps == 1 and self._ahead == bs:   # enqueued behind the previous cycle's accept kernel already
-            self._ahead = None
-            self.dcache.length = self.start           # rows kept (S) + this cycle's context rows (tau) = the new start
-            self._dyn_bs = None
-            if self.events is not None and self._ahead_ev:
-                e = self._ahead_ev
-                self.events["draft"], self.events["lm_head"] = [e[0], e[1]], [e[2], e[3]]
-            if self.hook is not None:
-                self.hook(blk, self.start, self.hook_calls)
-            self.hook_calls += 1
-            return
+        if draft_steps == 1 and self._ahead == bs:
+            return self._take_ahead(blk)
         # (a run-ahead draft of another block size is simply abandoned: it touched scratch buffers, the draft tokens of
         # the block and the draft cache rows this forward writes again — the length record is the accept kernel's)
         self._ahead = None
@@ -308,10 +330,7 @@ class DecodeSession:
             _draft_ids(m, hid, self.lm_wp, bs, blk, self.draft_temperature, self.draft_logits, seed=self._dseed,
                        dyn=self.dcache.dyn, start=self.start)
             self._mark("lm_head", 1)
-            if self.hook is not None:
-                self.hook(blk, self.start, self.hook_calls)
-            self.hook_calls += 1
-            return
+            return self._call_hook(blk)
         # benchmark.py:112-142: k full passes, each re-embedding the whole block, no draft
         # cache, positions rebuilt as [start-ctx_len, start+bs)
         ctx_len = ctx.shape[0]
@@ -325,9 +344,7 @@ class DecodeSession:
             hid = m.draft_block(tmp, th_rows=c2, tau=c2.shape[0], bs=bs, pos0=p0, block_ids=blk[0],
                                 embed=self.embed_w, append=False)
             _draft_ids(m, hid, self.lm_wp, bs, blk, 0.0)
-            if self.hook is not None:
-                self.hook(blk, self.start, self.hook_calls)
-            self.hook_calls += 1
+            self._call_hook(blk)
 
     @torch.inference_mode()
     def cycle(self, bs: int, *, draft_steps: int = 1, want_hidden: Optional[bool] = None,
@@ -374,11 +391,10 @@ class DecodeSession:
             # previous cycle's accept kernel did.  STOP is sticky and CYCLE keeps counting across steady-state cycles:
             # a stopped session is terminal, run_decode leaves the loop on it)
             ops.set_dyn(self.dyn, 0, 0, bs, start)  # start word = pos0 + tau = start
-        if self.poll_result:
-            self._res_np[3] = -1   # the cycle counter (>= 1 once written) is the kernel's LAST store, behind a release
+        self._arm_result()
         ops.accept_commit(blk[0], posterior[0].contiguous(), bs, self.output_ids[0], self.dyn, self.stop_t,
                           self.result, rearm=(self.block[0], self.max_bs, self.mask_token_id),
-                          dyn_t=self.tcache.dyn if (self.native and getattr(self, "_graph_bs", None)) else None)
+                          dyn_t=self.tcache.dyn if (self.native and self._fixed is not None) else None)
         self._armed = True
         # the record now holds the next draft forward's S / tau / pos0 / start — if that cycle was a cached draft cycle
         # on this record (bs > 1, one draft step) and keeps the block size
@@ -392,8 +408,23 @@ class DecodeSession:
                 and not self.stop_always and self.draft_temperature < 1e-5 and bs <= 16
                 and start + 2 * bs <= self.max_length and start + self.max_bs + 16 + bs <= self.dcache.max_rows):
             self._draft_ahead(bs)
+        res = self._await_result(t_call)
+        rows = None
+        if want_hidden and self.use_draft:
+            rows = taps if self.native else _taps(out.hidden_states, self.model.target_layer_ids)[0]
+        return self._commit(res, bs, start, rows, replayed=False)
+
+    # ------------------------------------------------------------------ the cycle's one device->host hand-over
+    def _arm_result(self) -> None:
+        # before the accept launch or its replay: the cycle counter (>= 1 once written) is the kernel's LAST store,
+        # behind a release
+        if self.poll_result:
+            self._res_np[3] = -1
+
+    def _await_result(self, t_call: float) -> list:
+        """After the cycle's last enqueue: wait for the accept result {acc, new start, stop, cycle} and return it."""
         t_enq = time.perf_counter() if self.host_times is not None else 0.0
-        if self.poll_result:   # the cycle's one device->host hand-over: pinned memory, polled on the word written last
+        if self.poll_result:   # pinned memory, polled on the word written last
             t0 = time.perf_counter()
             while self._res_np[3] == -1:
                 if time.perf_counter() - t0 > 0.05:   # a long verify: stop burning the core, block on the stream
@@ -405,35 +436,107 @@ class DecodeSession:
             res = self.result.tolist()  # device->host copy (synchronises the stream)
         if self.host_times is not None:   # host share of the cycle: launches enqueued, then waiting for the GPU
             self.host_times.append((t_enq - t_call, time.perf_counter() - t_enq))
+        return res
+
+    def _commit(self, res: list, bs: int, start: int, rows: Optional[torch.Tensor], replayed: bool) -> SimpleNamespace:
+        """The host's bookkeeping of an accepted block (model/dflash.py:258-268).  rows: the verify's tapped hidden rows
+        [>= tau, :], the next draft's context; None: the caller asked for none."""
         tau = res[0] + 1
         self.start = start + tau
         self.tcache.crop(self.start)
-        if want_hidden and self.use_draft:
-            self.target_hidden = (taps[None, :tau] if self.native
-                                  else _taps(out.hidden_states, self.model.target_layer_ids)[:, :tau, :])
-        self.stopped = bool(self.stop_always or res[2])
-        return SimpleNamespace(tau=tau, bs=bs, start=start, stop=self.stopped, replayed=False)
+        if rows is not None:
+            self.target_hidden = rows[None, :tau]
+        self.stopped = bool(self.stop_always or res[2])   # (a replayed session never has stop_always)
+        return SimpleNamespace(tau=tau, bs=bs, start=start, stop=self.stopped, replayed=replayed)
 
-    # ------------------------------------------------------------------ hipGraph replay of the steady-state cycle
-    def _graph_ok(self, bs: int) -> bool:
-        """A cycle that can be replayed: fixed block size, T = 0 or the device sampler, stop ids unless the mask id is
-        one of them, no tail clamp even if every token of this block and the next is accepted, and the previous cycle
-        left this cycle's draft enqueued (run-ahead)."""
-        if not (self.native and self.use_draft and bs == getattr(self, "_graph_bs", None) and self._ahead == bs
-                and not self.stop_always and self.replay_sampling_ok
-                and (self.events is None or not self.record_events)   # (a dict that only receives a run-ahead draft's pairs is fine)
-                and self.start + 2 * bs <= self.max_length and self.start + bs <= self._graph_bound):
-            return False
-        # The graphs hold RAW device pointers.  A shared draft model / NativeTarget replaces its RoPE table when another
-        # caller needs more positions (`_rope_tab`), and several sessions may interleave on one target: a replaced table
-        # means the captured launches would read freed (possibly reused) memory.  The session keeps the captured
-        # tensors alive (`_graph_keep`), so the replay stays memory-safe in any case; a differing pointer only says the
-        # owner has moved on to a larger table — its first rows are identical, the replay is still right, but the
-        # session re-captures at the next opportunity instead of pinning the old table for ever.
+    # ------------------------------------------------------------------ hipGraph replay: coverage and capture
+    def replay_uncovered(self, sizes, ahead: bool = False) -> Optional[str]:
+        """None if this session's cycles can be replayed from hipGraphs at every block size in `sizes`, else the reason
+        why not.  ahead: the fixed-size form (capture / cycle_graph), whose draft runs ahead of the accept result."""
+        sizes = sorted({int(b) for b in sizes})
+        if not self.native:
+            return "needs a NativeTarget"
+        if not self.use_draft:
+            return "needs a draft (block size > 1)"
+        if (self.target.attn_impl != "head" or self.target.fuse_oproj
+                or getattr(self.model, "attn_impl", "head") != "head"):
+            return "needs the plain 'head' attention stage on target and draft (the launches take device-driven lengths)"
+        if not self.replay_sampling_ok:
+            return "needs T = 0 or sampler='device' (the torch draw consumes host RNG state)"
+        if self.stop_always:
+            return "needs no mask id among the stop ids"
+        if not sizes or sizes[0] < 2 or sizes[-1] > 16:
+            return "needs block sizes in 2..16"
+        # The one asymmetry: the fixed form's draft is the NEXT cycle's, enqueued before the host has this cycle's result,
+        # and a run-ahead draft is only ever greedy (cycle() launches none at a draft temperature: capture()'s
+        # `_ahead == bs` could never hold).  The sized form drafts inside its own cycle, after the host has written the
+        # records, so its draft may sample (the draw takes the block start from the record's START word).
+        if ahead and self.draft_temperature >= 1e-5:
+            return "needs a greedy draft (the next cycle's draft runs ahead of the accept result)"
+        if self._replay_bound(sizes[-1]) < self.start:
+            return "the caches leave no room for a replayed cycle"
+        return None
+
+    def _replay_bound(self, top: int) -> int:
+        # upper bound of S / start for replays of up to `top` block rows: it sizes key splits and RoPE tables and must
+        # pass the launchers' capacity checks
+        return min(self.max_length, self.dcache.max_rows - 16 - top, self.tcache.max_rows - top)
+
+    def _capture_pairs(self, sizes, fixed: bool = False) -> _Replay:
+        """Per block size the graphs of [draft forward + lm_head] and [target verify + accept], every length from the
+        two device records the accept kernel keeps; `bound` stands in for S / start on the host side.  fixed: the one
+        size of capture(), whose accept kernel keeps the target cache's record from here on."""
+        m, t, tl = self.model, self.target, self.model.target_layer_ids
+        bound = self._replay_bound(max(sizes))
+        m._rope_tab(bound + 64 + 64)   # both tables long enough for every replayed cycle before an address is captured
+        t._rope_tab(bound + 64 + 64)
+        if fixed:   # the target cache's record: block form for the cycle about to run
+            ops.set_dyn2(self.tcache.dyn, self.start, 0, sizes[0], self.start)
+            self.tcache._dyn_bs = sizes[0]
+        torch.cuda.synchronize(self.dev)
+
+        def draft(bs):   # (a sampled draft takes the block start from the draft record's START word)
+            hid = m.draft_block(self.dcache, th_rows=self.taps_buf[:16], tau=16, bs=bs, pos0=bound, block_ids=self.block[0],
+                                embed=self.embed_w, dyn_ready=True, s_bound=bound)
+            _draft_ids(m, hid, self.lm_wp, bs, self.block[:, :bs], self.draft_temperature, self.draft_logits,
+                       seed=self._dseed, dyn=self.dcache.dyn)
+
+        def verify_accept(bs):   # (a T > 0 draw takes its positions from the target record's POS0 word: fresh every replay)
+            post, _ = t.verify(self.block[0, :bs], bound, self.tcache, temperature=self.temperature, tap_layers=tl,
+                               taps_out=self.taps_buf, dyn_lengths=True, seed=self._tseed, **self._fkw)
+            ops.accept_commit(self.block[0, :bs], post[0].contiguous(), bs, self.output_ids[0], self.dyn, self.stop_t,
+                              self.result, rearm=(self.block[0], self.max_bs, self.mask_token_id), dyn_t=self.tcache.dyn)
+
+        graphs = {bs: (capture_graph(lambda: draft(bs)), capture_graph(lambda: verify_accept(bs))) for bs in sizes}
+        # The graphs hold RAW device pointers: keep alive every tensor whose address they hold and that this session does
+        # not own through another attribute — the RoPE tables, the shared workspaces of draft model and target (ADVICE r3)
+        return _Replay(graphs, bound, (m._rope[0].data_ptr(), t._rope[0].data_ptr()),
+                       (m._rope, t._rope, getattr(m, "ws", None), getattr(t, "ws", None), getattr(t, "_taps", None),
+                        self.lm_wp, self.embed_w, getattr(t, "lm_wp", None)))
+
+    def _tables_moved(self, rec: _Replay) -> bool:
+        """A shared draft model / NativeTarget replaces its RoPE table when another caller needs more positions
+        (`_rope_tab`), and sessions may interleave on one target.  The record keeps the captured tensors alive, so a
+        replay stays memory-safe; a differing pointer only says the owner has moved on to a larger table (same first
+        rows): the caller drops the graphs, runs this cycle eagerly and captures again, not to pin the old table for ever."""
         m, t = self.model, self.target
-        if m._rope is None or t._rope is None or (m._rope[0].data_ptr(), t._rope[0].data_ptr()) != self._graph_rope:
-            self._graph_bs = None      # run_decode captures again on the next replayable cycle; this one runs eagerly
-            self._graphs, self._graph_keep = {}, None
+        return m._rope is None or t._rope is None or (m._rope[0].data_ptr(), t._rope[0].data_ptr()) != rec.rope
+
+    # ------------------------------------------------------------------ replay of the steady-state cycle, fixed block size
+    @property
+    def _graph_bs(self) -> Optional[int]:   # the block size capture() holds graphs for (its record's one key), or None
+        return next(iter(self._fixed.graphs)) if self._fixed is not None else None
+
+    def _graph_ok(self, bs: int) -> bool:
+        """A cycle that can be replayed: the captured block size, no tail clamp even if every token of this block and the
+        next is accepted, and the previous cycle left this cycle's draft enqueued (run-ahead)."""
+        r = self._fixed
+        if not (r is not None and bs in r.graphs and self._ahead == bs
+                and (self.events is None or not self.record_events)   # (a dict that only takes a run-ahead draft's pairs is fine)
+                and self.start + 2 * bs <= self.max_length and self.start + bs <= r.bound):
+            return False
+        if self._tables_moved(r):
+            self._fixed = None
             return False
         return True
 
@@ -444,48 +547,14 @@ class DecodeSession:
         accept kernel keeps (dfl_accept_commit_rearm_t: the draft cache's record and the target cache's block-form
         record), so one capture serves every cycle; the attention launches size their key splits for the caches'
         capacity.  Call after at least one cycle(bs, ahead_ok=True).  The host then spends two graph launches and one poll
-        per cycle instead of ~215 ctypes calls (VERDICT r2 next #9)."""
-        if not (self.native and self.use_draft and 2 <= bs <= 16 and self.replay_sampling_ok and not self.stop_always
-                and self.draft_temperature < 1e-5 and self.target.attn_impl == "head" and not self.target.fuse_oproj):
-            raise ValueError("capture needs a NativeTarget ('head' attention), a draft, T = 0 or sampler='device', a greedy "
-                             "draft, no mask id among the stop ids, 2 <= bs <= 16")
-        if self._ahead != bs:
-            raise RuntimeError("capture: run one cycle(bs, ahead_ok=True) first (the next draft must be in flight)")
-        m, t = self.model, self.target
-        # upper bounds of S / start for the replayed launches (they size key splits and RoPE tables, and must pass the
-        # launchers' capacity checks): a replayed cycle has start <= max_length - 2 bs (_graph_ok)
-        bound = min(self.max_length, self.dcache.max_rows - 16 - bs, self.tcache.max_rows - bs)
-        if bound < self.start:
-            raise RuntimeError("capture: the caches leave no room for a replayed cycle")
-        self._graph_bound = bound
-        m._rope_tab(bound + 64 + 64)
-        t._rope_tab(bound + 64 + 64)
-        # the target cache's record: block form for the cycle about to run (the accept kernel keeps it from here on)
-        ops.set_dyn2(self.tcache.dyn, self.start, 0, bs, self.start)
-        self.tcache._dyn_bs = bs
-        torch.cuda.synchronize(self.dev)
-        tl = self.model.target_layer_ids
-
-        def verify_accept():   # (a T > 0 draw takes its positions from the target record's POS0 word: fresh every replay)
-            post, _ = t.verify(self.block[0, :bs], bound, self.tcache, temperature=self.temperature, tap_layers=tl,
-                               taps_out=self.taps_buf, dyn_lengths=True, seed=self._tseed, **self._fkw)
-            ops.accept_commit(self.block[0, :bs], post[0].contiguous(), bs, self.output_ids[0], self.dyn, self.stop_t,
-                              self.result, rearm=(self.block[0], self.max_bs, self.mask_token_id), dyn_t=self.tcache.dyn)
-
-        def draft_next():
-            hid = m.draft_block(self.dcache, th_rows=self.taps_buf[:16], tau=16, bs=bs, pos0=bound, block_ids=self.block[0],
-                                embed=self.embed_w, dyn_ready=True, s_bound=bound)
-            _draft_ids(m, hid, self.lm_wp, bs, self.block[:, :bs], 0.0, self.draft_logits)
-
-        self._graphs = {}
-        for name, fn in (("verify", verify_accept), ("draft", draft_next)):
-            self._graphs[name] = capture_graph(fn)
-        self._graph_bs = bs
-        # every tensor whose address sits in the captured launches and that this session does not own through another
-        # attribute: the RoPE tables and the shared workspaces of the draft model and of the target (ADVICE r3)
-        self._graph_rope = (m._rope[0].data_ptr(), t._rope[0].data_ptr())
-        self._graph_keep = (m._rope, t._rope, getattr(m, "ws", None), getattr(t, "ws", None), getattr(t, "_taps", None),
-                            self.lm_wp, self.embed_w, getattr(t, "lm_wp", None))
+        per cycle instead of ~215 ctypes calls.  Raises GraphNotCovered for a session or a state
+        the graphs do not cover (replay_uncovered)."""
+        why = self.replay_uncovered((bs,), ahead=True)
+        if why is None and self._ahead != bs:
+            why = "run one cycle(bs, ahead_ok=True) first (the next draft must be in flight)"
+        if why is not None:
+            raise GraphNotCovered(f"capture: {why}")
+        self._fixed = self._capture_pairs((bs,), fixed=True)
 
     @torch.inference_mode()
     def cycle_graph(self, bs: int) -> SimpleNamespace:
@@ -495,41 +564,15 @@ class DecodeSession:
             return self.cycle(bs, ahead_ok=True)
         t_call = time.perf_counter() if self.host_times is not None else 0.0
         start = self.start
-        # the draft of THIS cycle is in flight already (run-ahead): host bookkeeping of _draft()
-        self._ahead = None
-        self.dcache.length = start
-        if self.events is not None and self._ahead_ev:   # its event pairs were recorded by the (eager) cycle that enqueued it
-            e = self._ahead_ev
-            self.events["draft"], self.events["lm_head"] = [e[0], e[1]], [e[2], e[3]]
-        if self.hook is not None:
-            self.hook(self.block[:, :bs], start, self.hook_calls)
-        self.hook_calls += 1
-        if self.poll_result:
-            self._res_np[3] = -1
-        self._graphs["verify"].replay()
+        self._take_ahead(self.block[:, :bs])   # the draft of THIS cycle is in flight already (run-ahead)
+        draft_next, verify = self._fixed.graphs[bs]
+        self._arm_result()
+        verify.replay()
         self._armed = True
         self._dyn_bs = bs
-        self._graphs["draft"].replay()          # the NEXT cycle's draft, behind the accept kernel
+        draft_next.replay()          # the NEXT cycle's draft, behind the accept kernel
         self._ahead, self._ahead_ev = bs, None
-        t_enq = time.perf_counter() if self.host_times is not None else 0.0
-        if self.poll_result:
-            t0 = time.perf_counter()
-            while self._res_np[3] == -1:
-                if time.perf_counter() - t0 > 0.05:
-                    torch.cuda.current_stream().synchronize()
-                    if self._res_np[3] == -1:
-                        raise RuntimeError("dfl_accept_commit: the result never arrived in host memory")
-            res = self._res_np.tolist()
-        else:
-            res = self.result.tolist()
-        if self.host_times is not None:
-            self.host_times.append((t_enq - t_call, time.perf_counter() - t_enq))
-        tau = res[0] + 1
-        self.start = start + tau
-        self.tcache.crop(self.start)
-        self.target_hidden = self.taps_buf[None, :tau]
-        self.stopped = bool(res[2])
-        return SimpleNamespace(tau=tau, bs=bs, start=start, stop=self.stopped, replayed=True)
+        return self._commit(self._await_result(t_call), bs, start, self.taps_buf, replayed=True)
 
     # ------------------------------------------------------------------ hipGraph replay with a caller-chosen block size
     @torch.inference_mode()
@@ -538,53 +581,25 @@ class DecodeSession:
         the policy loop of benchmark_dynamic_schedule.py:319-379: [draft forward + lm_head] and [target verify + accept],
         every launch taking its lengths from the two device records.  cycle_sized() writes those records from the host's
         own bookkeeping (two 64-thread launches) and replays the pair; there is no run-ahead draft, since the next block's
-        size is only known once the scheduler has seen this cycle's result.  Call after at least one draft cycle."""
+        size is only known once the scheduler has seen this cycle's result.  Call after at least one draft cycle.  Raises
+        GraphNotCovered for a session or a state the graphs do not cover (replay_uncovered)."""
         sizes = sorted({int(b) for b in sizes})
-        if not (self.native and self.use_draft and sizes and 2 <= sizes[0] and sizes[-1] <= 16 and self.replay_sampling_ok
-                and not self.stop_always and self.target.attn_impl == "head"
-                and not self.target.fuse_oproj and getattr(self.model, "attn_impl", "head") == "head"):
-            raise ValueError("capture_sizes needs a NativeTarget ('head' attention), a draft, T = 0 or sampler='device', no "
-                             "mask id among the stop ids, sizes in 2..16")
-        if not self._armed:
-            raise RuntimeError("capture_sizes: run one cycle first")
-        m, t = self.model, self.target
-        bound = min(self.max_length, self.dcache.max_rows - 16 - sizes[-1], self.tcache.max_rows - sizes[-1])
-        if bound < self.start:
-            raise RuntimeError("capture_sizes: the caches leave no room for a replayed cycle")
-        m._rope_tab(bound + 64 + 64)
-        t._rope_tab(bound + 64 + 64)
-        torch.cuda.synchronize(self.dev)
-        tl = self.model.target_layer_ids
-        graphs = {}
-        for bs in sizes:
-            def draft_now(bs=bs):   # (a sampled draft takes the block start from the draft record's START word)
-                hid = m.draft_block(self.dcache, th_rows=self.taps_buf[:16], tau=16, bs=bs, pos0=bound, block_ids=self.block[0],
-                                    embed=self.embed_w, dyn_ready=True, s_bound=bound)
-                _draft_ids(m, hid, self.lm_wp, bs, self.block[:, :bs], self.draft_temperature, self.draft_logits,
-                           seed=self._dseed, dyn=self.dcache.dyn)
-
-            def verify_accept(bs=bs):
-                post, _ = t.verify(self.block[0, :bs], bound, self.tcache, temperature=self.temperature, tap_layers=tl,
-                                   taps_out=self.taps_buf, dyn_lengths=True, seed=self._tseed, **self._fkw)
-                ops.accept_commit(self.block[0, :bs], post[0].contiguous(), bs, self.output_ids[0], self.dyn, self.stop_t,
-                                  self.result, rearm=(self.block[0], self.max_bs, self.mask_token_id), dyn_t=self.tcache.dyn)
-
-            graphs[bs] = (capture_graph(draft_now), capture_graph(verify_accept))
+        why = self.replay_uncovered(sizes)
+        if why is None and not self._armed:
+            why = "run one cycle first"
+        if why is not None:
+            raise GraphNotCovered(f"capture_sizes: {why}")
+        self._sized = self._capture_pairs(sizes)
         self.tcache.crop(self.start)     # (verify's host-side bookkeeping ran with the bound)
-        self._sgraphs, self._sgraph_bound = graphs, bound
-        self._sgraph_rope = (m._rope[0].data_ptr(), t._rope[0].data_ptr())
-        self._sgraph_keep = (m._rope, t._rope, getattr(m, "ws", None), getattr(t, "ws", None), getattr(t, "_taps", None),
-                             self.lm_wp, self.embed_w, getattr(t, "lm_wp", None))
 
     def _sized_ok(self, bs: int) -> bool:
-        g = getattr(self, "_sgraphs", None)
-        if not (g and bs in g and self._armed and not self.stop_always
+        r = self._sized
+        if not (r is not None and bs in r.graphs and self._armed
                 and (self.events is None or not self.record_events) and self.target_hidden is not None
-                and self.target_hidden.shape[1] <= 16 and self.start + bs <= min(self.max_length, self._sgraph_bound)):
+                and self.target_hidden.shape[1] <= 16 and self.start + bs <= min(self.max_length, r.bound)):
             return False
-        m, t = self.model, self.target
-        if m._rope is None or t._rope is None or (m._rope[0].data_ptr(), t._rope[0].data_ptr()) != self._sgraph_rope:
-            self._sgraphs = None         # a replaced RoPE table: the captured launches hold the old one's address
+        if self._tables_moved(r):
+            self._sized = None
             return False
         return True
 
@@ -604,40 +619,20 @@ class DecodeSession:
         ops.set_dyn2(self.tcache.dyn, start, 0, bs, start)
         self.tcache._dyn_bs = bs
         self._ahead = None
-        dg, vg = self._sgraphs[bs]
+        dg, vg = self._sized.graphs[bs]
         dg.replay()
         self.dcache.length = S + tau_c
         blk = self.block[:, :bs]
-        if self.hook is not None:
-            self.hook(blk, start, self.hook_calls)
-        self.hook_calls += 1
+        self._call_hook(blk)
         if after_draft is not None:
             after_draft(blk)
-        if self.poll_result:
-            self._res_np[3] = -1
+        self._arm_result()
         vg.replay()
         self._armed = True
         self._dyn_bs = bs
-        t_enq = time.perf_counter() if self.host_times is not None else 0.0
-        if self.poll_result:
-            t0 = time.perf_counter()
-            while self._res_np[3] == -1:
-                if time.perf_counter() - t0 > 0.05:
-                    torch.cuda.current_stream().synchronize()
-                    if self._res_np[3] == -1:
-                        raise RuntimeError("dfl_accept_commit: the result never arrived in host memory")
-            res = self._res_np.tolist()
-        else:
-            res = self.result.tolist()
-        if self.host_times is not None:
-            self.host_times.append((t_enq - t_call, time.perf_counter() - t_enq))
-        tau = res[0] + 1
-        self.start = start + tau
-        self.tcache.length = start + bs
-        self.tcache.crop(self.start)
-        self.target_hidden = self.taps_buf[None, :tau]
-        self.stopped = bool(res[2])
-        return SimpleNamespace(tau=tau, bs=bs, start=start, stop=self.stopped, replayed=True)
+        res = self._await_result(t_call)
+        self.tcache.length = start + bs   # (the replayed verify wrote bs rows; the host's counter follows before the crop)
+        return self._commit(res, bs, start, self.taps_buf, replayed=True)
 
     def finish(self) -> torch.Tensor:
         return _trim(self.output_ids, self.max_length, self.mask_token_id, self.stop_token_ids, self.n_in)
@@ -661,8 +656,11 @@ def run_decode(model, target, input_ids: torch.Tensor, *, mask_token_id: int, ma
     decode_start = cuda_time()
     taus, used_bs, cycle_trace, lgens = [], [], [], []
     draft_prefill = True
-    use_graphs = os.environ.get("DFL_GRAPH", "1") != "0" and s.native and getattr(target, "attn_impl", "") == "head" \
-        and not getattr(target, "fuse_oproj", False)
+    # Steady-state cycles are replayed from hipGraphs where the graphs cover the session (replay_uncovered: asked here
+    # and again by the capture, for the state it finds); DFL_GRAPH=0: eager launches.  GraphNotCovered from a capture
+    # means eager cycles for the rest of the request; any other error is a real failure and leaves this call
+    sizes = (block_size,) if scheduler is None else tuple(getattr(scheduler, "candidates", ()))
+    replay = os.environ.get("DFL_GRAPH", "1") != "0" and s.replay_uncovered(sizes, ahead=scheduler is None) is None
     cyc = replayed = 0
     replayed_flags = []
     while s.start < s.max_length:
@@ -695,40 +693,36 @@ def run_decode(model, target, input_ids: torch.Tensor, *, mask_token_id: int, ma
         gen_before = s.start - s.n_in
         start_idx = s.start
         # fixed-size loops replay their steady-state cycles from two hipGraphs (DecodeSession.capture): the host's share
-        # of a cycle drops from ~2.3 ms to ~0.2 ms at the same GPU time; DFL_GRAPH=0: eager launches.
-        # Stop ids ride along in the captured accept launch; T > 0 needs the device sampler
-        if (use_graphs and scheduler is None and draft_steps == 1 and not collect_profile and bs == block_size
-                and 2 <= bs <= 16 and want_hidden and not draft_prefill and s._ahead == bs and not s.stop_always
-                and s.replay_sampling_ok and draft_temperature < 1e-5):
-            if getattr(s, "_graph_bs", None) is None and not getattr(s, "_graph_off", False):
+        # of a cycle drops from ~2.3 ms to ~0.2 ms at the same GPU time.  Stop ids ride along in
+        # the captured accept launch; T > 0 needs the device sampler
+        per_cycle = replay and draft_steps == 1 and not collect_profile and want_hidden and not draft_prefill
+        if per_cycle and scheduler is None and bs == block_size and s._ahead == bs:
+            if s._graph_bs is None:
                 try:
                     s.capture(bs)
-                except (ValueError, RuntimeError):       # a session the graphs do not cover: eager cycles, as before
-                    s._graph_off = True
+                except GraphNotCovered:
+                    replay = False
             r = s.cycle_graph(bs)
+        elif per_cycle and scheduler is not None:
+            # the policy loop by replay: one pair of graphs per candidate size (DecodeSession.capture_sizes, which needs
+            # a cycle to have run: `not draft_prefill` says one has, and every cycle leaves the session armed)
+            if s._sized is None:
+                try:
+                    s.capture_sizes(sizes)
+                except GraphNotCovered:
+                    replay = False
+            r = s.cycle_sized(bs, after_draft=after_draft)
         else:
             # (collect_profile: no run-ahead draft — its event pairs would be recorded during cycle N and handed to
             # cycle N + 1, outside that cycle's [cycle0, cycle1] marks; benchmark.py:149-160 times each phase inside its
             # own cycle)
-            if (use_graphs and scheduler is not None and draft_steps == 1 and not collect_profile and want_hidden
-                    and not draft_prefill and not s.stop_always and s.replay_sampling_ok
-                    and len(getattr(scheduler, "candidates", ())) > 0
-                    and 2 <= min(scheduler.candidates) and max(scheduler.candidates) <= 16):
-                # the policy loop by replay: one pair of graphs per candidate size (DecodeSession.capture_sizes)
-                if getattr(s, "_sgraphs", None) is None and s._armed and not getattr(s, "_sgraphs_off", False):
-                    try:
-                        s.capture_sizes(scheduler.candidates)
-                    except (ValueError, RuntimeError):   # a session the graphs do not cover: eager cycles, as before
-                        s._sgraphs_off = True
-                r = s.cycle_sized(bs, after_draft=after_draft)
-            else:
-                r = s.cycle(bs, draft_steps=draft_steps, want_hidden=want_hidden, after_draft=after_draft,
-                            ahead_ok=scheduler is None and draft_steps == 1 and not collect_profile)
+            r = s.cycle(bs, draft_steps=draft_steps, want_hidden=want_hidden, after_draft=after_draft,
+                        ahead_ok=scheduler is None and draft_steps == 1 and not collect_profile)
         taus.append(r.tau)
         used_bs.append(bs)
         lgens.append(lg[0])
-        replayed += int(getattr(r, "replayed", False))
-        replayed_flags.append(bool(getattr(r, "replayed", False)))
+        replayed += int(r.replayed)
+        replayed_flags.append(r.replayed)
         if scheduler is not None:
             cycle_s = cuda_time() - cycle_t0
             scheduler.update(tau=r.tau, cycle_s=cycle_s, effective_bs=bs, cycle_idx=cyc, l_gen=lg[0])

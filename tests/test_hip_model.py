@@ -1098,6 +1098,7 @@ def test_generate_loop_with_graph_replay_env(monkeypatch):
         assert r.output_ids[0].tolist() == G[:33 + n_new].tolist(), mode
         runs[mode] = r
     assert runs["0"].acceptance_lengths == runs["1"].acceptance_lengths
+    assert runs["1"].replayed_cycles > 0 and runs["0"].replayed_cycles == 0
 
 
 class _ScriptedSizes:
@@ -1156,6 +1157,7 @@ def test_policy_loop_by_graph_replay_equals_the_eager_policy_loop(monkeypatch):
     a, b = runs["0"], runs["1"]
     assert a[0].acceptance_lengths == b[0].acceptance_lengths and a[0].used_block_sizes == b[0].used_block_sizes
     assert a[1].seen == b[1].seen and len(set(a[0].used_block_sizes)) >= 3
+    assert b[0].replayed_cycles > 0 and a[0].replayed_cycles == 0
 
 
 def test_cycle_sized_replays_and_falls_back():
@@ -1197,3 +1199,125 @@ def test_cycle_sized_replays_and_falls_back():
         i += 1
     assert s.finish()[0].tolist() == G[:29 + n_new].tolist()
     assert replayed >= 8, replayed
+
+
+def _replay_case(seed, n_prompt, n_new, plan):
+    """The tiny target with a known greedy walk G, a prompt, and the hook that scripts plan[call] agreeing draft tokens."""
+    from dflash_amd.synthetic import greedy_walk, impose_greedy_walk
+    hf = _tiny_hf()
+    perm = impose_greedy_walk(hf, seed=seed)
+    prompt = torch.randint(0, 2000, (1, n_prompt), generator=torch.Generator().manual_seed(seed)).to(dev())
+    G = greedy_walk(perm, prompt, n_new + 40).to(dev())
+
+    def hook(blk, start, call):
+        k = min(plan[call], blk.shape[1] - 1)
+        blk[0, 1:k + 1] = G[start + 1:start + k + 1]
+        if k + 1 < blk.shape[1]:
+            blk[0, k + 1] = (G[start + k + 1] + 1) % 2000
+    return hf, prompt, G, hook
+
+
+def test_fresh_session_has_its_replay_state():
+    """Every replay attribute exists from __init__ on: nothing is captured, nothing can be replayed, no AttributeError."""
+    from dflash_amd import NativeTarget
+    from dflash_amd.generate import DecodeSession
+    cfg = H.tiny_cfg()
+    hf, prompt, _, hook = _replay_case(7, 30, 48, H.make_plan(16, 16, 3))
+    s = DecodeSession(make_model(cfg), NativeTarget(hf), prompt, mask_token_id=cfg.mask_token_id, max_new_tokens=48,
+                      max_block_size=16, stop_token_ids=None, temperature=0.0, draft_token_hook=hook)
+    assert s._graph_bs is None
+    assert s._graph_ok(16) is False and s._sized_ok(16) is False
+    assert s.replay_uncovered((16,), ahead=True) is None and s.replay_uncovered((8, 16)) is None
+
+
+@pytest.mark.parametrize("case", ["torch_sampler_at_T", "mask_id_among_stop_ids"])
+def test_uncovered_session_raises_graph_not_covered(case):
+    """A session the graphs do not cover says why (replay_uncovered) and raises GraphNotCovered from both captures, with
+    every state precondition met (a cycle has run); dflash_generate runs such a request with eager cycles only."""
+    from dflash_amd import NativeTarget, dflash_generate
+    from dflash_amd.generate import DecodeSession, GraphNotCovered
+    cfg = H.tiny_cfg()
+    hf, prompt, _, hook = _replay_case(7, 30, 48, H.make_plan(64, 16, 3))
+    kw = (dict(stop_token_ids=None, temperature=0.7, sampler="torch") if case == "torch_sampler_at_T"
+          else dict(stop_token_ids=[cfg.mask_token_id], temperature=0.0))
+    m, nt = make_model(cfg), NativeTarget(hf)
+    s = DecodeSession(m, nt, prompt, mask_token_id=cfg.mask_token_id, max_new_tokens=48, max_block_size=16,
+                      draft_token_hook=hook, **kw)
+    s.prefill()
+    s.cycle(16, ahead_ok=True)
+    for sizes, ahead in (((16,), True), ((8, 16), False)):
+        why = s.replay_uncovered(sizes, ahead=ahead)
+        assert isinstance(why, str) and why, (sizes, why)
+    with pytest.raises(GraphNotCovered):
+        s.capture(16)
+    with pytest.raises(GraphNotCovered):
+        s.capture_sizes((8, 16))
+    assert s._graph_bs is None and not s._sized_ok(16)
+    if case == "torch_sampler_at_T":
+        r = dflash_generate(m, nt, prompt, cfg.mask_token_id, 48, 16, None, 0.7, draft_token_hook=hook, sampler="torch")
+        assert r.replayed_cycles == 0 and len(r.acceptance_lengths) > 0
+
+
+def test_capture_failure_other_than_coverage_propagates(monkeypatch):
+    """run_decode answers GraphNotCovered with eager cycles and nothing else: an error raised inside a capture (here a
+    host-side stub in place of capture_graph; no launch is made to fail) leaves dflash_generate as it is."""
+    import dflash_amd.generate as gen
+    from dflash_amd import NativeTarget, dflash_generate
+    cfg = H.tiny_cfg()
+    hf, prompt, _, hook = _replay_case(7, 30, 48, H.make_plan(64, 16, 3))
+
+    def boom(fn):
+        raise RuntimeError("boom")
+
+    monkeypatch.setenv("DFL_GRAPH", "1")
+    monkeypatch.setattr(gen, "capture_graph", boom)
+    with pytest.raises(RuntimeError, match="boom") as e:
+        dflash_generate(make_model(cfg), NativeTarget(hf), prompt, cfg.mask_token_id, 48, 16, None, 0.0,
+                        draft_token_hook=hook)
+    assert not isinstance(e.value, gen.GraphNotCovered)
+    torch.cuda.synchronize()
+
+
+def test_replay_forms_agree_under_both_result_modes(monkeypatch):
+    """The hand-over's two branches — pinned host memory polled on the cycle counter (DFL_HOST_RESULT=1, the default)
+    and a device buffer read with .tolist() (=0) — under cycle_graph and under cycle_sized: ids are the greedy walk and
+    the acceptance lengths are the same in both modes, with cycles really replayed in each."""
+    from dflash_amd import NativeTarget
+    from dflash_amd.generate import DecodeSession
+    cfg = H.tiny_cfg()
+    n_new = 40
+    plan = [0, 1, 2, 0, 1, 0, 3, 1] * 5   # short acceptances: several cycles start early enough to be replayed (_graph_ok)
+    hf, prompt, G, hook = _replay_case(11, 31, n_new, plan)
+    m, nt = make_model(cfg), NativeTarget(hf)
+
+    def run(form):
+        s = DecodeSession(m, nt, prompt, mask_token_id=cfg.mask_token_id, max_new_tokens=n_new, max_block_size=16,
+                          stop_token_ids=None, temperature=0.0, draft_token_hook=hook)
+        s.prefill()
+        taus, replayed, i = [], 0, 0
+        while s.start < s.max_length:
+            left = s.max_length - s.start
+            if form == "fixed":
+                if i == 2:
+                    s.capture(16)
+                bs = min(16, left)
+                r = s.cycle_graph(16) if (i >= 2 and bs == 16) else s.cycle(bs, ahead_ok=bs == 16)
+            else:
+                if i == 1:
+                    s.capture_sizes((8, 16))
+                bs = min((16, 8)[i % 2], left)
+                r = s.cycle_sized(bs) if i >= 1 else s.cycle(bs)
+            taus.append(r.tau)
+            replayed += int(r.replayed)
+            i += 1
+        assert s.finish()[0].tolist() == G[:31 + n_new].tolist(), form
+        return taus, replayed
+
+    runs = {}
+    for mode in ("1", "0"):
+        monkeypatch.setenv("DFL_HOST_RESULT", mode)
+        for form in ("fixed", "sized"):
+            taus, replayed = runs[mode, form] = run(form)
+            assert replayed >= 3, (mode, form, replayed)
+    for form in ("fixed", "sized"):
+        assert runs["0", form][0] == runs["1", form][0], form
