@@ -927,10 +927,26 @@ extern "C" int64_t dfl_attn_head_ws_bytes(int n_q, int max_splits, int q_tiles) 
   return (b + 15) / 16 * 16;   // per-candidate blocks of a multi-candidate launch stay 16-byte aligned
 }
 
+// Old-key split constants: the measured choice.  The head and o_proj pairs are swept at compile time by
+// scripts/dbg_attn_head_stamps.py / dbg_attn_oproj_stamps.py (-DDFL_ATTN_HEAD_TILES=... etc.).
+#ifndef DFL_ATTN_HEAD_TILES
+#define DFL_ATTN_HEAD_TILES 8  // 32-key tiles per split: a workgroup's 8 waves take one each per round
+#endif
+#ifndef DFL_ATTN_HEAD_WGS
+#define DFL_ATTN_HEAD_WGS 224  // workgroups per launch beyond which the splits grow instead
+#endif
+#ifndef DFL_ATTN_OPROJ_TILES
+#define DFL_ATTN_OPROJ_TILES 4
+#endif
+#ifndef DFL_ATTN_OPROJ_WGS
+#define DFL_ATTN_OPROJ_WGS 256  // with the o_proj tail: 4-wave workgroups, two per CU; 256 attention + H/16 o_proj workgroups fill the 512 slots
+#endif
+
 namespace {
-bool pair_ok_forced(int knob, bool has_tail, int q_tiles, int G, int bs) {
-  return knob == 1 && !has_tail && q_tiles == 1 && G % 2 == 0 && bs <= 16;
-}
+// several blocks per launch — requests of a ragged batch, candidates: ONE round of workgroups, 256; with 448 the
+// second half-round of a 4-request launch was a tail: 6.10 -> 5.99 ms per 4-request cycle
+constexpr int HEAD_WGS_MULTI = 256;
+static_assert(DFL_ATTN_HEAD_TILES >= 1 && DFL_ATTN_OPROJ_TILES >= 1, "tiles per split");
 
 // o_proj behind the attention stage in the same launch (dfl_attn_head_oproj)
 struct OprojTail {
@@ -979,33 +995,22 @@ int attn_head_launch(const void *xq, int64_t ldq, int q_col, int k_col, int v_co
   // (S here is the bound the caller sized the launch for when the lengths come from dyn).
   const int G = n_q / n_kv;
   const int nt = (S + 31) / 32;
-  // (DFL_ATTN_HEAD_TILES / DFL_ATTN_HEAD_WGS: tuning knobs read once from the environment, for
-  // scripts/dbg_attn_head_stamps.py; the defaults are the measured choice)
-  static const int knob_tiles = [] { const char *e = getenv("DFL_ATTN_HEAD_TILES"); return e ? atoi(e) : 8; }();
-  static const int knob_wgs = [] { const char *e = getenv("DFL_ATTN_HEAD_WGS"); return e ? atoi(e) : 224; }();
-  // (several blocks per launch — requests of a ragged batch, candidates: ONE round of workgroups, 256; with 448 the
-  // second half-round of a 4-request launch was a tail: 6.10 -> 5.99 ms per 4-request cycle)
-  static const int knob_wgsm = [] { const char *e = getenv("DFL_ATTN_HEAD_WGS_MULTI"); return e ? atoi(e) : 256; }();
-  static const int knob_wgs4 = [] { const char *e = getenv("DFL_ATTN_OPROJ_WGS"); return e ? atoi(e) : 256; }();
-  static const int knob_tiles4 = [] { const char *e = getenv("DFL_ATTN_OPROJ_TILES"); return e ? atoi(e) : 4; }();
-  // (with the o_proj tail: 4-wave workgroups, two per CU; 256 attention + H/16 o_proj workgroups fill the 512 slots)
-  const int tiles = tail ? (knob_tiles4 < 1 ? 1 : knob_tiles4) : (knob_tiles < 1 ? 1 : knob_tiles);
+  const int tiles = tail ? DFL_ATTN_OPROJ_TILES : DFL_ATTN_HEAD_TILES;
+  const int wgs = n_cand > 1 ? HEAD_WGS_MULTI : DFL_ATTN_HEAD_WGS;
   int ns_old = (nt + tiles - 1) / tiles;
-  int budget = (tail ? knob_wgs4 : (n_cand > 1 ? knob_wgsm : knob_wgs)) / (n_q * n_cand) - 1;
+  int budget = (tail ? DFL_ATTN_OPROJ_WGS : wgs) / (n_q * n_cand) - 1;
   budget = budget < 1 ? 1 : budget;
   ns_old = ns_old > budget ? budget : ns_old;
   // Head pairs (k_attn_head_pair): when the splits the budget allows would leave a wave more than one tile, two heads
-  // per workgroup halve the K/V pulled through L2 and double the splits.  DFL_ATTN_HEAD_PAIR=0/1 forces it off / on.
-  static const int knob_pair = [] { const char *e = getenv("DFL_ATTN_HEAD_PAIR"); return e ? atoi(e) : -1; }();
+  // per workgroup halve the K/V pulled through L2 and double the splits.
   // Measured on the 8B shapes (cycle, ms): S = 2048 4.28 -> 4.40 (worse), 4096 4.48 -> 4.49, 8192 4.78 -> 4.68: on from ~5k keys.
   // Several blocks per launch (requests of a ragged batch, candidates): the one round of workgroups leaves a single
   // old-key split per head from two requests on, i.e. ~4 tiles per wave at S = 1k — pairs on whenever the budget
   // leaves a wave more than one tile (round 3, same box: 4 requests 6.03 -> 5.81 ms per cycle, 3 requests 5.97 -> 5.69;
   // 2 requests 5.22 -> 5.29: from three blocks on).
-  bool pair = !tail && q_tiles == 1 && G % 2 == 0 && bs <= 16 && nt > tiles * ns_old && (nt > 160 || n_cand > 2);
-  if (knob_pair >= 0) pair = pair_ok_forced(knob_pair, tail != nullptr, q_tiles, G, bs);
+  const bool pair = !tail && q_tiles == 1 && G % 2 == 0 && bs <= 16 && nt > tiles * ns_old && (nt > 160 || n_cand > 2);
   if (pair) {
-    int budget2 = (n_cand > 1 ? knob_wgsm : knob_wgs) / ((n_q / 2) * n_cand) - 1;
+    int budget2 = wgs / ((n_q / 2) * n_cand) - 1;
     budget2 = budget2 < 1 ? 1 : budget2;
     ns_old = (nt + tiles - 1) / tiles;
     ns_old = ns_old > budget2 ? budget2 : ns_old;

@@ -485,16 +485,10 @@ constexpr int64_t WS_CAND = 256 * 16 * 4 * 16;                         // argmax
 constexpr int64_t WS_ARGMAX = WS_CAND * (int64_t)(sizeof(float) + sizeof(int));
 constexpr int64_t WS_HEAD = WS_TICKETS + WS_ARGMAX;
 
-// DFL_BATCH_GEMM=slab: the round-1..3 form (k_gemm_b: K cut over workgroups, fp32 slabs + ticket) for every batched
-// GEMM — A/B measurement and the second implementation the tests compare with.  Default: the ring form (gemm_ring.h)
-// where it applies (gate/up, lm_head from fragment sources).
-bool use_ring() {
-  static const bool v = [] {
-    const char *e = getenv("DFL_BATCH_GEMM");
-    return !(e && e[0] == 's');
-  }();
-  return v;
-}
+// Two forms of every fused batched GEMM.  The ring form (gemm_ring.h) runs gate/up and the lm_head where it applies:
+// fragment sources (mode 0) whose K fits whole k-steps (ring_ok).  The round-1..3 form (k_gemm_b: K cut over workgroups,
+// fp32 slabs + ticket) runs the small-N projections and every other source — the shape fallback, and the second
+// implementation the tests compare with (they reach it by passing plain-row sources).
 
 // workgroups, units per workgroup and pass, passes: every workgroup walks ceil(nunits / gx) units in passes of <= upp_max
 void ring_plan(GemmRArgs &a, int nunits, int upp_max, int &gx) {
@@ -505,41 +499,24 @@ void ring_plan(GemmRArgs &a, int nunits, int upp_max, int &gx) {
   a.upp = (per_wg + a.npass - 1) / a.npass;
 }
 
-template <int MT, int TPU, int KQ, int NW, int A, int EPI, int CK = 8>
-void launch_ring(const GemmRArgs &a, int gx, hipStream_t st, int gy = 1) {
-  constexpr int lds = ring_lds_bytes<MT, TPU, KQ, NW, A, CK>();
-  static bool attr_set = false;  // more than 64 KB of dynamic LDS needs the attribute (set once per instantiation)
-  void (*kern)(GemmRArgs) = dfl_k_gemm_r<MT, TPU, KQ, NW, A, EPI, CK>;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_set = true;
+// More than 64 KB of dynamic LDS needs the attribute: set once per instantiation (a function-local static: initialised
+// exactly once, whichever threads launch first).  False, with the error set, where it failed: nothing is launched.
+template <int MT, int TPU, int KQ, int NW, int A, int EPI>
+bool launch_ring(const char *who, const GemmRArgs &a, int gx, hipStream_t st) {
+  constexpr int lds = ring_lds_bytes<MT, TPU, KQ, NW, A>();
+  void (*kern)(GemmRArgs) = dfl_k_gemm_r<MT, TPU, KQ, NW, A, EPI>;
+  static const hipError_t attr =
+      hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  if (attr != hipSuccess) {
+    (void)hipGetLastError();  // (reported here, not by the next entry point's launch check)
+    dfl_set_error("%s: %d bytes of dynamic LDS refused: %s", who, lds, hipGetErrorString(attr));
+    return false;
   }
-  hipLaunchKernelGGL(kern, dim3(gx, gy), dim3(NW * 64), lds, st, a);
-}
-
-// DFL_RING_VARIANT=<n>: A/B knob for the lm_head launch (0: 8-k-step slots, two chunks ahead; 1: 16-k-step slots, one ahead)
-int ring_variant() {
-  static const int v = [] {
-    const char *e = getenv("DFL_RING_VARIANT");
-    return e ? atoi(e) : 0;
-  }();
-  return v;
-}
-
-// DFL_RING_ROT=m: workgroup b starts its K walk at chunk (b * m) % chunks.  Default 0 (every workgroup at chunk 0):
-// measured on one box, 4 tiles, gate/up 37.3 us at m = 0 against 39.8 / 38.9 / 39.5 at m = 1 / 3 / 5, lm_head 221 - 222 us
-// either way (profiles/r4_ring_microbench.txt) — HBM channel camping is not what limits the walk, and workgroups in
-// step share each activation chunk's L2 lines.
-int ring_rot() {
-  static const int v = [] {
-    const char *e = getenv("DFL_RING_ROT");
-    return e ? atoi(e) : 0;
-  }();
-  return v;
+  hipLaunchKernelGGL(kern, dim3(gx), dim3(NW * 64), lds, st, a);
+  return true;
 }
 
 void fill_ring(GemmRArgs &a, const void *wp, const dfl_rows_batch *x, int N, int K, const int32_t *dyn) {
-  a.rot_mul = ring_rot();
   a.wp = (const bf16x8 *)wp;
   a.xf = (const bf16x8 *)x->r0.frag;
   a.frag_stride8 = x->frag_stride / 8;
@@ -615,36 +592,11 @@ extern "C" int dfl_gemm_f32_batch(const void *wp, const dfl_rows_batch *x, int R
                                   const int32_t *dyn, void *stream) {
   GemmBArgs a{};
   DFL_REQUIRE(out, "dfl_gemm_f32_batch: null pointer");
-  // Ring form with K cut over grid.y (round 4, DFL_RING_F32=1; OFF by default): the same part count and output layout as
-  // k_gemm_b (the consumer adds dfl_batch_ksplit(K) parts), but a workgroup's 2048-wide K part of the activations streams
-  // through the LDS ring instead of being loaded into registers in front of the first MFMA.  Applies where a workgroup
-  // holds >= 6 tiles of a part (bytes in flight = tiles x look-ahead): down_proj (7 tiles x 6 parts).  MEASURED SLOWER
-  // there than the register-resident form: 23.8 against 22.7 us per launch, 5.25 against 5.11 ms per 4-request cycle
-  // (profiles/r4_batch4_ab.txt) — with a 2048-wide K part resident in registers the workgroup has ALL its activations
-  // after one burst and 3 x 64 KB weight items in flight; the ring holds 24 k-steps of look-ahead.  Kept as the measured
-  // variant; o_proj in four K parts on the same form was tried as well (12.0 against 11.9 us, and the norm launch
-  // behind it reads four parts: 5.23 against 5.16 ms) and removed.
-  static const int ring_f32 = [] { const char *e = getenv("DFL_RING_F32"); return e ? atoi(e) : 0; }();
-  {
-    const int ksplit = batch_ksplit(K), nt = N / 16;
-    const int gxm = 256 / ksplit > 0 ? 256 / ksplit : 1;
-    const int U = (nt + gxm - 1) / gxm;   // tiles per workgroup and part
-    if (ring_f32 && use_ring() && wp && ring_ok(x, K) && R >= 3 && R <= 4 && N % 16 == 0 && x->frag_stride % 8 == 0 && U >= 6 &&
-        U <= 8 && ksplit >= 2) {
-      GemmRArgs r{};
-      fill_ring(r, wp, x, N, K, dyn);
-      r.out = out;
-      r.ldo = N;
-      r.ksp = 8 * ((K / 32 + 8 * ksplit - 1) / (8 * ksplit));   // the k-steps of k_gemm_b's parts: 8 waves x nfr
-      r.nunits = nt;
-      r.npass = 1;
-      r.upp = U;
-      const int gx = (nt + U - 1) / U;
-      launch_ring<4, 1, 2, 16, 3, EPI_F32>(r, gx, (hipStream_t)stream, ksplit);
-      DFL_CHECK_LAUNCH("dfl_gemm_f32_batch");
-      return DFL_OK;
-    }
-  }
+  // (The register-resident form only.  The ring form with K cut over grid.y was measured slower on down_proj, 7 tiles x 6
+  // parts: 23.8 against 22.7 us per launch, 5.25 against 5.11 ms per 4-request cycle, profiles/r4_batch4_ab.txt — with a
+  // 2048-wide K part resident in registers the workgroup has all its activations after one burst and 3 x 64 KB weight
+  // items in flight; the ring holds 24 k-steps of look-ahead.  o_proj in four K parts likewise: 12.0 against 11.9 us,
+  // and the norm launch behind it reads four parts, 5.23 against 5.16 ms.)
   if (!fill_batch(a, wp, x, R, N, K, dyn, nullptr, "dfl_gemm_f32_batch")) return DFL_EINVAL;
   a.out = out;
   a.ldo = N;
@@ -660,7 +612,7 @@ extern "C" int dfl_gemm_silu_mul_batch(const void *wp_gateup, const dfl_rows_bat
   GemmBArgs a{};
   DFL_REQUIRE(act_frag && ws, "dfl_gemm_silu_mul_batch: null pointer");
   DFL_REQUIRE(act_stride >= 16 * (int64_t)I, "dfl_gemm_silu_mul_batch: act_stride < 16*I");
-  if (use_ring() && wp_gateup && ring_ok(x, K) && R >= 1 && R <= 4 && I > 0 && I % 16 == 0 && x->frag_stride % 8 == 0) {
+  if (wp_gateup && ring_ok(x, K) && R >= 1 && R <= 4 && I > 0 && I % 16 == 0 && x->frag_stride % 8 == 0) {
     // ring form: a wave owns a (gate, up) tile pair and a quarter of every K chunk; no K cut over workgroups
     GemmRArgs r{};
     fill_ring(r, wp_gateup, x, 2 * I, K, dyn);
@@ -670,21 +622,15 @@ extern "C" int dfl_gemm_silu_mul_batch(const void *wp_gateup, const dfl_rows_bat
     const int per_wg = (I / 16 + 255) / 256;
     const bool w16 = per_wg % 4 == 0 || per_wg > 6;  // units per pass: 3 (12 waves) or 4 (16 waves)
     ring_plan(r, I / 16, w16 ? 4 : 3, gx);
-    if (R <= 2) {
-      if (w16)
-        launch_ring<2, 2, 4, 16, 3, EPI_SILU>(r, gx, (hipStream_t)stream);
-      else
-        launch_ring<2, 2, 4, 12, 3, EPI_SILU>(r, gx, (hipStream_t)stream);
-    } else {
-      if (w16)
-        launch_ring<4, 2, 4, 16, 2, EPI_SILU>(r, gx, (hipStream_t)stream);
-      else if (ring_variant() & 2)   // A/B: four chunks ahead (160 KB of ring)
-        launch_ring<4, 2, 4, 12, 4, EPI_SILU>(r, gx, (hipStream_t)stream);
-      else if (ring_variant() & 4)   // A/B: three chunks ahead
-        launch_ring<4, 2, 4, 12, 3, EPI_SILU>(r, gx, (hipStream_t)stream);
-      else   // two chunks ahead (16 chunks at K = 4096: no padding iterations): in the cycle 35.0 us against 37.3 (three)
-        launch_ring<4, 2, 4, 12, 2, EPI_SILU>(r, gx, (hipStream_t)stream);
-    }
+    // look-ahead at 4 tiles: two chunks (16 chunks at K = 4096: no padding iterations), in the cycle 35.0 us against
+    // 37.3 at three; four chunks (160 KB of ring) were measured as well (profiles/r4_batch4_ab.txt)
+    const hipStream_t st = (hipStream_t)stream;
+    const char *who = "dfl_gemm_silu_mul_batch";
+    const bool ok = R <= 2 ? (w16 ? launch_ring<2, 2, 4, 16, 3, EPI_SILU>(who, r, gx, st)
+                                  : launch_ring<2, 2, 4, 12, 3, EPI_SILU>(who, r, gx, st))
+                           : (w16 ? launch_ring<4, 2, 4, 16, 2, EPI_SILU>(who, r, gx, st)
+                                  : launch_ring<4, 2, 4, 12, 2, EPI_SILU>(who, r, gx, st));
+    if (!ok) return DFL_ELAUNCH;
     DFL_CHECK_LAUNCH("dfl_gemm_silu_mul_batch");
     return DFL_OK;
   }
@@ -704,35 +650,9 @@ extern "C" int dfl_gemm_resid_batch(const void *wp, const dfl_rows_batch *x, int
   GemmBArgs a{};
   DFL_REQUIRE(h_io && ws, "dfl_gemm_resid_batch: null pointer");
   DFL_REQUIRE(ldh >= N && (!tap || ldtap >= N), "dfl_gemm_resid_batch: row strides shorter than N");
-  // DFL_RING_RESID=1|2 (A/B knob, default off): the ring form for the small-N projections too — finished sums, no K cut.
-  // What bounds it there is the ring itself: bytes of weights in flight = tiles per workgroup x look-ahead k-steps, and the
-  // look-ahead is capped by LDS (4 KiB of activations per k-step at 4 tiles): DESIGN.md section 6b.
-  static const int ring_resid = [] { const char *e = getenv("DFL_RING_RESID"); return e ? atoi(e) : 0; }();
-  if (ring_resid && use_ring() && wp && ring_ok(x, K) && R >= 3 && R <= 4 && !ss_out && N % 16 == 0 && K <= 4096 &&
-      x->frag_stride % 8 == 0) {
-    GemmRArgs r{};
-    fill_ring(r, wp, x, N, K, dyn);
-    r.h_io = (bf16_t *)h_io;
-    r.ldh = ldh;
-    r.h_stride = h_stride;
-    r.add_resid = add_residual ? 1 : 0;
-    r.tap = (bf16_t *)tap;
-    r.ldtap = ldtap;
-    r.tap_stride = tap_stride;
-    r.nunits = N / 16;
-    r.npass = 1;
-    if (ring_resid == 1) {  // 3 tiles per workgroup, 4 waves per tile
-      r.upp = 3;
-      const int gx = (r.nunits + 2) / 3;
-      launch_ring<4, 1, 4, 12, 4, EPI_RESID>(r, gx, (hipStream_t)stream);
-    } else {                // 2 tiles per workgroup, 8 waves per tile
-      r.upp = 2;
-      const int gx = (r.nunits + 1) / 2;
-      launch_ring<4, 1, 8, 16, 4, EPI_RESID>(r, gx, (hipStream_t)stream);
-    }
-    DFL_CHECK_LAUNCH("dfl_gemm_resid_batch");
-    return DFL_OK;
-  }
+  // (The register-resident form only.  What bounds the ring form at small N is the ring itself: bytes of weights in
+  // flight = tiles per workgroup x look-ahead k-steps, and the look-ahead is capped by LDS, 4 KiB of activations per
+  // k-step at 4 tiles: DESIGN.md section 6b.)
   if (!fill_batch(a, wp, x, R, N, K, dyn, ws, "dfl_gemm_resid_batch")) return DFL_EINVAL;
   a.h_io = (bf16_t *)h_io;
   a.ldh = ldh;
@@ -757,7 +677,7 @@ extern "C" int dfl_gemm_argmax_batch(const void *wp, const dfl_rows_batch *x, in
   DFL_REQUIRE(ws && out_ids, "dfl_gemm_argmax_batch: null pointer");
   DFL_REQUIRE(row0 >= 0 && nrows >= 0 && row0 + nrows <= 16, "dfl_gemm_argmax_batch: rows [%d,%d) outside the tile", row0,
               row0 + nrows);
-  if (use_ring() && wp && ring_ok(x, K) && R >= 1 && R <= 4 && V > 0 && V % 16 == 0 && x->frag_stride % 8 == 0) {
+  if (wp && ring_ok(x, K) && R >= 1 && R <= 4 && V > 0 && V % 16 == 0 && x->frag_stride % 8 == 0) {
     // ring form: a wave owns a column tile over the whole K, the workgroup walks its tiles in passes of <= 16
     GemmRArgs r{};
     fill_ring(r, wp, x, V, K, dyn);
@@ -771,12 +691,10 @@ extern "C" int dfl_gemm_argmax_batch(const void *wp, const dfl_rows_batch *x, in
     r.N = V;
     int gx = 0;
     ring_plan(r, V / 16, 16, gx);
-    if (R <= 2)
-      launch_ring<2, 1, 1, 16, 2, EPI_ARGMAX>(r, gx, (hipStream_t)stream);
-    else if (ring_variant() & 1)
-      launch_ring<4, 1, 1, 16, 1, EPI_ARGMAX, 16>(r, gx, (hipStream_t)stream);
-    else
-      launch_ring<4, 1, 1, 16, 2, EPI_ARGMAX>(r, gx, (hipStream_t)stream);
+    const char *who = "dfl_gemm_argmax_batch";
+    if (!(R <= 2 ? launch_ring<2, 1, 1, 16, 2, EPI_ARGMAX>(who, r, gx, (hipStream_t)stream)
+                 : launch_ring<4, 1, 1, 16, 2, EPI_ARGMAX>(who, r, gx, (hipStream_t)stream)))
+      return DFL_ELAUNCH;
     hipLaunchKernelGGL(k_argmax_finish_b, dim3(16, R), dim3(64), 0, (hipStream_t)stream, r.best_val, r.best_idx, gx,
                        mt_of(R), row0, nrows, dyn, nrows_dyn_word, out_ids, out_stride, out_off);
     DFL_CHECK_LAUNCH("dfl_gemm_argmax_batch");
@@ -815,8 +733,8 @@ extern "C" int dfl_gemm_sample_batch(const void *wp, const dfl_rows_batch *x, in
               "dfl_gemm_sample_batch: unknown stream %d", rng_stream);
   DFL_REQUIRE(pos_word >= 0 && pos_word < DFL_DYN_WORDS && (tiles_per_req == 1 || tiles_per_req == 2) && R % tiles_per_req == 0,
               "dfl_gemm_sample_batch: pos_word=%d / tiles_per_req=%d / R=%d", pos_word, tiles_per_req, R);
-  DFL_REQUIRE(use_ring() && ring_ok(x, K) && R >= 1 && R <= 4 && V > 0 && V % 16 == 0 && x->frag_stride % 8 == 0,
-              "dfl_gemm_sample_batch: needs the ring form (R <= 4 fragment sources, V %% 16 == 0, DFL_BATCH_GEMM not 'slab')");
+  DFL_REQUIRE(ring_ok(x, K) && R >= 1 && R <= 4 && V > 0 && V % 16 == 0 && x->frag_stride % 8 == 0,
+              "dfl_gemm_sample_batch: needs the ring form (R <= 4 fragment sources, V %% 16 == 0, K %% 32 == 0, K >= 256)");
   GemmRArgs r{};
   fill_ring(r, wp, x, V, K, dyn);
   r.row0 = row0;
@@ -835,10 +753,10 @@ extern "C" int dfl_gemm_sample_batch(const void *wp, const dfl_rows_batch *x, in
   r.tiles_per_req = tiles_per_req;
   int gx = 0;
   ring_plan(r, V / 16, 16, gx);
-  if (R <= 2)
-    launch_ring<2, 1, 1, 16, 2, EPI_SAMPLE>(r, gx, (hipStream_t)stream);
-  else
-    launch_ring<4, 1, 1, 16, 2, EPI_SAMPLE>(r, gx, (hipStream_t)stream);
+  const char *who = "dfl_gemm_sample_batch";
+  if (!(R <= 2 ? launch_ring<2, 1, 1, 16, 2, EPI_SAMPLE>(who, r, gx, (hipStream_t)stream)
+               : launch_ring<4, 1, 1, 16, 2, EPI_SAMPLE>(who, r, gx, (hipStream_t)stream)))
+    return DFL_ELAUNCH;
   hipLaunchKernelGGL(k_argmax_finish_b, dim3(16, R), dim3(64), 0, (hipStream_t)stream, r.best_val, r.best_idx, gx, mt_of(R),
                      row0, nrows, dyn, nrows_dyn_word, out_ids, out_stride, out_off);
   DFL_CHECK_LAUNCH("dfl_gemm_sample_batch");

@@ -49,19 +49,6 @@ struct GemmRArgs {
   bf16_t *logits;  // optional [16][N] per request
   int64_t logits_stride;
   int N;
-  // EPI_F32: out[(mt * 16 + m) * ldo + n]
-  float *out;
-  int ldo;
-  int rot_mul;  // workgroup b starts its K walk at chunk (b * rot_mul) % chunks (0: every workgroup at chunk 0)
-  int ksp;      // EPI_F32 with K cut over grid.y (0: no cut): k-steps per K part; part y writes out + y * MT * 16 * ldo
-  // EPI_RESID: h[r][m][n] <- bf16(sum) or bf16(h + bf16(sum)) (model/dflash.py:140,144), optional second copy (tap)
-  bf16_t *h_io;
-  int64_t ldh, h_stride;
-  int add_resid;
-  bf16_t *tap;
-  int64_t ldtap, tap_stride;
-  float *ss_out;  // optional [ntiles][16] per request: sum over the tile's 16 columns of the new rows' squares (next RMSNorm)
-  int64_t ss_stride;
   // EPI_SAMPLE (with the EPI_ARGMAX fields): tile mt is tile j = mt % tiles_per_req of request q = mt / tiles_per_req; its
   // row m draws position base + pos_add + 16 j + m with base = dyn[mt][pos_word] and the seed seeds[q] (dfl_rng.h);
   // the DRAFT stream takes extra = base (the block start), the TARGET stream extra = 0
@@ -77,15 +64,16 @@ typedef __attribute__((address_space(1))) void r_glb_void;
 constexpr int R_CK = 8;  // k-steps per ring slot
 }  // namespace
 
-// MT request tiles, TPU tiles per unit, KQ waves per unit (each takes CK / KQ k-steps of every chunk), NW waves per
-// workgroup, A chunks of look-ahead (weights in flight per wave: A * CK / KQ * TPU KiB; ring: A + 1 slots)
-template <int MT, int TPU, int KQ, int NW, int A, int EPI, int CK = 8>
+// MT request tiles, TPU tiles per unit, KQ waves per unit (each takes R_CK / KQ k-steps of every chunk), NW waves per
+// workgroup, A chunks of look-ahead (weights in flight per wave: A * R_CK / KQ * TPU KiB; ring: A + 1 slots)
+template <int MT, int TPU, int KQ, int NW, int A, int EPI>
 __global__ __launch_bounds__(NW * 64) void dfl_k_gemm_r(GemmRArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)  // the host pass needs the kernel's handle only; with this body it drops the instantiation (no diagnostic)
-  constexpr int KPC = CK / KQ, NS = A + 1;  // CK: k-steps per ring slot
+  constexpr int CK = R_CK, KPC = CK / KQ, NS = A + 1;
   constexpr int NPIECE = CK * MT;                 // 1 KiB pieces per chunk
   constexpr int SP = (NPIECE + NW - 1) / NW;      // pieces per wave and chunk (surplus: a duplicate of the last piece)
   constexpr int VMC = A * KPC * TPU + (A - 1) * SP;  // VMEM ops of a wave younger than its pieces of the chunk it is about to read
+  static_assert(EPI == EPI_SILU || EPI == EPI_ARGMAX || EPI == EPI_SAMPLE, "the ring form has these three epilogues");
   static_assert(CK % KQ == 0 && VMC < 64, "chunk split / vmcnt immediate");
   static_assert(NS * NPIECE * 1024 <= 160 * 1024, "ring exceeds LDS");
   static_assert(NW * TPU * MT * 1024 <= 160 * 1024 || KQ == 1, "the final KQ-way sum reuses the ring's LDS (ring_lds_bytes)");
@@ -96,11 +84,7 @@ __global__ __launch_bounds__(NW * 64) void dfl_k_gemm_r(GemmRArgs a) {
   const int l = tid & 63;
   const int fm = l & 15, fg = l >> 4;  // D layout: row m, columns 4 fg .. 4 fg + 3
   const int u = w / KQ, q = w - u * KQ;
-  // K range of this workgroup: the whole K, or (EPI_F32, grid.y parts: fp32 partial sums for a consumer that adds them —
-  // dfl_norm_frag_batch) k-steps [ks0, ks0 + KSl)
-  const int ks0 = a.ksp ? (int)blockIdx.y * a.ksp : 0;
-  const int KSl = a.ksp ? (a.KS - ks0 < a.ksp ? a.KS - ks0 : a.ksp) : a.KS;
-  const int nch = (KSl + CK - 1) / CK;
+  const int nch = (a.KS + CK - 1) / CK;  // every workgroup walks the whole K, chunk c at k-steps [c * CK, c * CK + CK)
   const int nit = (nch + A - 1) / A * A;  // chunk iterations, rounded up to the unroll (clipped weights: zeros)
   const unsigned ring_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)ring;
 
@@ -126,7 +110,7 @@ __global__ __launch_bounds__(NW * 64) void dfl_k_gemm_r(GemmRArgs a) {
   static_assert(NW % MT == 0, "a wave's pieces share a request");
   const int pmt = w % MT;
   const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<bf16x8 *>(a.xf + pmt * a.frag_stride8 + (size_t)ks0 * 64), 0, KSl * 1024, 0x00020000);
+      const_cast<bf16x8 *>(a.xf + pmt * a.frag_stride8), 0, a.KS * 1024, 0x00020000);
   int pks[SP], poff[SP];
 #pragma unroll
   for (int s = 0; s < SP; ++s) {
@@ -135,15 +119,12 @@ __global__ __launch_bounds__(NW * 64) void dfl_k_gemm_r(GemmRArgs a) {
     pks[s] = i / MT;
     poff[s] = i * 1024;
   }
-  // K is walked in chunks of CK k-steps; workgroup b starts at chunk (b * rot_mul) % nch and wraps: at one moment the
-  // 256 workgroups x <= 16 waves do NOT all ask HBM for the same offset inside their (128 KB-aligned) column tiles.
   // A pass runs nit >= nch iterations (the unroll's multiple): iterations >= nch are padding (k-steps past K: zeros).
-  const int rot = a.rot_mul ? (int)(((unsigned)blockIdx.x * (unsigned)a.rot_mul) % (unsigned)nch) : 0;
-  auto kchunk = [&](int c) {
-    int k = c + rot;
-    k = k >= nch ? k - nch : k;
-    return c < nch ? k : nch;
-  };
+  // (Every workgroup starts at chunk 0.  A start rotated by workgroup, (b * m) % chunks, was measured at 4 tiles: gate/up
+  // 37.3 us unrotated against 39.8 / 38.9 / 39.5 at m = 1 / 3 / 5, lm_head 221 - 222 us either way
+  // (profiles/r4_ring_microbench.txt) — HBM channel camping is not what limits the walk, and workgroups in step share
+  // each activation chunk's L2 lines.)
+  auto kchunk = [&](int c) { return c < nch ? c : nch; };
   int slot_w = 0, slot_r = 0;  // ring slots of the next stage() / the next chunk to compute (cycle 0 .. NS - 1)
   auto stage = [&](int kc) {   // data chunk kc -> the next ring slot
     const unsigned slot = ring_base + (unsigned)slot_w * (NPIECE * 1024);
@@ -158,8 +139,8 @@ __global__ __launch_bounds__(NW * 64) void dfl_k_gemm_r(GemmRArgs a) {
     g = (int)blockIdx.x + (p * a.upp + u) * (int)gridDim.x;
     const bool have = p < a.npass && u < a.upp && g < a.nunits;
 #pragma unroll
-    for (int tp = 0; tp < TPU; ++tp) base[tp] = a.wp + ((size_t)(have ? TPU * g + tp : 0) * a.KS + ks0) * 64;
-    bytes = have ? KSl * 1024 : 0;
+    for (int tp = 0; tp < TPU; ++tp) base[tp] = a.wp + (size_t)(have ? TPU * g + tp : 0) * a.KS * 64;
+    bytes = have ? a.KS * 1024 : 0;
   };
   bf16x8 wreg[A][KPC][TPU];
   // weights of data chunk kc for this wave: k-steps kc * CK + q * KPC + j of the unit's tiles
@@ -266,7 +247,7 @@ __global__ __launch_bounds__(NW * 64) void dfl_k_gemm_r(GemmRArgs a) {
           o[r] = f2bf(act * ub);
         }
         *reinterpret_cast<bf16x4 *>(a.act + mt * a.act_stride + ((size_t)(n0 >> 3) * 16 + fm) * 8 + (n0 & 7)) = o;
-      } else if (EPI == EPI_ARGMAX || EPI == EPI_SAMPLE) {
+      } else {  // EPI_ARGMAX, EPI_SAMPLE
         const bool live = (fm >= a.row0) && (fm < a.row0 + arg_rows[mt]);
         if (a.logits && live) {
           bf16x4 o = {f2bf(s[0]), f2bf(s[1]), f2bf(s[2]), f2bf(s[3])};
@@ -288,29 +269,6 @@ __global__ __launch_bounds__(NW * 64) void dfl_k_gemm_r(GemmRArgs a) {
             bestn[mt] = n0 + r;
           }
         }
-      } else if (EPI == EPI_RESID) {
-        bf16_t *hp = a.h_io + mt * a.h_stride + (int64_t)fm * a.ldh + n0;
-        bf16x4 o;
-        if (a.add_resid) {
-          const bf16x4 hv = *reinterpret_cast<const bf16x4 *>(hp);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) o[r] = f2bf(bf2f(hv[r]) + rbf(s[r]));
-        } else {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) o[r] = f2bf(s[r]);
-        }
-        *reinterpret_cast<bf16x4 *>(hp) = o;
-        if (a.tap) *reinterpret_cast<bf16x4 *>(a.tap + mt * a.tap_stride + (int64_t)fm * a.ldtap + n0) = o;
-        if (a.ss_out) {  // (uniform)
-          float q = 0.f;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) q += bf2f(o[r]) * bf2f(o[r]);
-          q += __shfl_xor(q, 16, 64);
-          q += __shfl_xor(q, 32, 64);
-          if (fg == 0) a.ss_out[mt * a.ss_stride + t_last * 16 + fm] = q;
-        }
-      } else {  // EPI_F32
-        *reinterpret_cast<f32x4 *>(a.out + ((size_t)(blockIdx.y * MT + mt) * 16 + fm) * a.ldo + n0) = s;
       }
     };
 
@@ -411,9 +369,9 @@ __global__ __launch_bounds__(NW * 64) void dfl_k_gemm_r(GemmRArgs a) {
 
 namespace {
 
-template <int MT, int TPU, int KQ, int NW, int A, int CK = 8>
+template <int MT, int TPU, int KQ, int NW, int A>
 constexpr int ring_lds_bytes() {
-  const int ring = (A + 1) * CK * MT * 1024, red = KQ > 1 ? NW * TPU * MT * 1024 : 0;
+  const int ring = (A + 1) * R_CK * MT * 1024, red = KQ > 1 ? NW * TPU * MT * 1024 : 0;
   return ring > red ? ring : red;
 }
 

@@ -712,9 +712,7 @@ static void plan_tiles(GemmArgs &a, int ntiles, bool allow_half, int &gx) {
   const int r = ntiles % 256;
   // (round 4) at most 128 tiles: ALL of them in halves, one per workgroup — twice the CUs stream half the bytes each
   // (o_proj / down_proj of a hidden-2048 model: 128 workgroups of one 16-column tile were half the chip).
-  // DFL_HALF_SMALL=0: whole tiles, the round-3 plan.
-  static const bool half_small = [] { const char *e = getenv("DFL_HALF_SMALL"); return !(e && e[0] == '0'); }();
-  if (allow_half && half_small && ntiles <= 128) {
+  if (allow_half && ntiles <= 128) {
     gx = 2 * ntiles;
     a.ntiles = 0;
     a.nhalf = 2 * ntiles;

@@ -612,11 +612,10 @@ extern "C" int dfl_moe_down(const void *wp_down, int64_t wp_expert_stride, const
   a.out = out;
   a.ldo = N;
   // Two column tiles per workgroup share an item's activation fragments (the caller asks for four shares, so that the
-  // grid stays at 256 workgroups for N = 2048); DFL_MOE_DOWN_CT=1: one tile per workgroup, the round-2/3 form
+  // grid stays at 256 workgroups for N = 2048); an odd tile count: one tile per workgroup, the round-2/3 form
   // (same box, BASELINE configs[4]'s cycle: one tile 6.44 - 6.45 ms, two 6.34, four tiles on 8 waves 6.37 - 6.38:
   // profiles/r4_moe_router_ab.txt)
-  static const int ct = [] { const char *e = getenv("DFL_MOE_DOWN_CT"); return e ? atoi(e) : 2; }();
-  if (ct == 2 && N % 32 == 0)
+  if (N % 32 == 0)
     hipLaunchKernelGGL((k_moe_down<2, 16>), dim3(N / 32, nsplit), dim3(1024), 0, (hipStream_t)stream, a);
   else
     hipLaunchKernelGGL((k_moe_down<1, 16>), dim3(N / 16, nsplit), dim3(1024), 0, (hipStream_t)stream, a);

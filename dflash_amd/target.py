@@ -18,7 +18,6 @@ loops of this package detect it and take the fast path instead:
 """
 from __future__ import annotations
 
-import os
 from types import SimpleNamespace
 from typing import Optional, Sequence
 
@@ -214,16 +213,16 @@ class NativeTarget:
         self.is_moe = any("gu_e" in lw for lw in self.layers)
         if self.is_moe:
             ep = (self.E + 15) // 16 * 16
-            # shares of the active experts (grid.y of dfl_moe_down): 4 with its two-tiles-per-workgroup form (the default)
-            self.moe_nsplit = 2 if (os.environ.get("DFL_MOE_DOWN_CT") == "1" or self.H % 32) else 4
+            # shares of the active experts (grid.y of dfl_moe_down): 4 with its two-tiles-per-workgroup form (H % 32 == 0)
+            self.moe_nsplit = 2 if self.H % 32 else 4
             self.ws.update(xn=z(NT, 16 * self.H), xn1=z(NT, 16 * self.H), rlog=z(NT, 16, ep), wt=z(NT, 16, self.E),
                            act_e=z(self.E, 16 * self.Ie), moe_part=z(self.moe_nsplit, 16, self.H, dt=torch.float32),
                            active=torch.zeros(self.E, dtype=torch.int32, device=dev),
                            elist=torch.zeros(self.E, dtype=torch.int32, device=dev),
                            n_active=torch.zeros(1, dtype=torch.int32, device=dev),
                            rticket=torch.zeros(1, dtype=torch.int32, device=dev))
-            # norm + gate Linear + routing as ONE launch (dfl_moe_router; DFL_MOE_ROUTER=split: the three launches)
-            self.moe_router_fused = (os.environ.get("DFL_MOE_ROUTER", "fused") != "split" and self.H <= 4096 and self.E % 2 == 0)
+            # norm + gate Linear + routing as ONE launch (dfl_moe_router); the three launches otherwise
+            self.moe_router_fused = self.H <= 4096 and self.E % 2 == 0
         ws, nt = self.ws, self.H // 16
         hs = [ws["h"][16 * t:16 * t + 16] for t in range(NT)]
         # row sources, one per tile: the consuming GEMM applies the RMSNorm itself (no norm launches)

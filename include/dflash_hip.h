@@ -11,8 +11,10 @@
  *
  * Conventions
  *  - every pointer is a DEVICE pointer into caller-owned memory (torch storage)
- *    unless named host_*; the library allocates nothing and keeps no state except
- *    the thread-local last-error string;
+ *    unless named host_*; the library allocates nothing, reads no environment
+ *    variable and keeps no state except the thread-local last-error string and,
+ *    per ring-GEMM kernel instantiation, the result of the one call that raises
+ *    its dynamic-LDS limit (made at its first launch, never changed after);
  *  - `stream` is a hipStream_t passed as void* (NULL = default stream); calls only
  *    enqueue work, never synchronise, and are capturable into a hipGraph;
  *  - return 0 on success, a negative DFL_E* code on a rejected argument or a

@@ -1,6 +1,7 @@
 """Diagnostic (GPU box): build attn_head.hip with -DDFL_ATTN_STAMPS into gpurun_out/dbg and print where a
 k_attn_head workgroup spends its time (100 MHz s_memrealtime stamps: first old-key split and the new-row split
-of kv head 0 / query head 0), for the split knobs given in the environment (DFL_ATTN_HEAD_TILES / _WGS).
+of kv head 0 / query head 0), for the split constants given in the environment (DFL_ATTN_HEAD_TILES / _WGS: compiled
+into this build with -D; unset: the product's values).
 K/V are cold (a 400 MB fill runs before every launch), as in the decode cycle."""
 import ctypes as C
 import os
@@ -16,7 +17,9 @@ out = os.path.join(ROOT, "gpurun_out", "dbg")
 os.makedirs(out, exist_ok=True)
 so = os.path.join(out, "libdbg_head.so")
 src = [os.path.join(ROOT, "dflash_amd", "csrc", f) for f in ("attn_head.hip", "dfl_common.hip")]
-flags = [a for a in sys.argv[1:] if a.startswith("-D")]
+KNOBS = {"DFL_ATTN_HEAD_TILES": "8", "DFL_ATTN_HEAD_WGS": "224"}
+KNOBS = {k: os.environ.get(k, d) for k, d in KNOBS.items()}
+flags = [f"-D{k}={v}" for k, v in KNOBS.items()] + [a for a in sys.argv[1:] if a.startswith("-D")]
 subprocess.run([_hipcc(), *FLAGS, "-shared", "-DDFL_ATTN_STAMPS",
                 *flags, "-o", so, *src], check=True)
 from dflash_amd import _lib, ops
@@ -61,5 +64,5 @@ for rep in range(5):
             d = [(t[i + 1] - t[i]) / 100.0 if t[i + 1] >= t[i] > 0 else float("nan") for i in range(7)]
             print(f"S={S} tau={tau} rep {rep} {label}: " + "  ".join(f"{n}={x_:.2f}" for n, x_ in zip(names[1:], d))
                   + f"  | total {(max(t) - t[0]) / 100.0:.2f} us")
-print(f"S={S} tau={tau} TILES={os.environ.get('DFL_ATTN_HEAD_TILES', '8')} WGS={os.environ.get('DFL_ATTN_HEAD_WGS', '224')}: "
+print(f"S={S} tau={tau} TILES={KNOBS['DFL_ATTN_HEAD_TILES']} WGS={KNOBS['DFL_ATTN_HEAD_WGS']}: "
       f"event-to-event {sorted(tot)[len(tot) // 2]:.1f} us (median of {len(tot)})")

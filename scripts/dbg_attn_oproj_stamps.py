@@ -1,7 +1,7 @@
 """Diagnostic (GPU box): build attn_head.hip with -DDFL_ATTN_STAMPS into gpurun_out/dbg and print the timeline of one
 k_attn_oproj launch (100 MHz s_memrealtime stamps): attention workgroup (kv head 0, query head 0) of the first old-key
 split and of the new-row split, and the first / last o_proj workgroup, all relative to the earliest stamp.
-Knobs: DFL_ATTN_OPROJ_WGS / DFL_ATTN_OPROJ_TILES (environment), S, TAU.  K/V and weights are cold (a 400 MB fill runs
+Knobs: DFL_ATTN_OPROJ_WGS / DFL_ATTN_OPROJ_TILES (environment: compiled into this build with -D), S, TAU.  K/V and weights are cold (a 400 MB fill runs
 before every launch), as in the decode cycle."""
 import ctypes as C
 import os
@@ -17,7 +17,9 @@ out = os.path.join(ROOT, "gpurun_out", "dbg")
 os.makedirs(out, exist_ok=True)
 so = os.path.join(out, "libdbg_oproj.so")
 src = [os.path.join(ROOT, "dflash_amd", "csrc", f) for f in ("attn_head.hip", "dfl_common.hip")]
-flags = [a for a in sys.argv[1:] if a.startswith("-D")]
+KNOBS = {"DFL_ATTN_OPROJ_WGS": "256", "DFL_ATTN_OPROJ_TILES": "4"}
+KNOBS = {k: os.environ.get(k, d) for k, d in KNOBS.items()}
+flags = [f"-D{k}={v}" for k, v in KNOBS.items()] + [a for a in sys.argv[1:] if a.startswith("-D")]
 subprocess.run([_hipcc(), *FLAGS, "-shared", "-DDFL_ATTN_STAMPS",
                 *flags, "-o", so, *src], check=True)
 from dflash_amd import _lib, ops
@@ -70,5 +72,5 @@ for rep in range(5):
         print(f"rep {rep}: latest ticket per key split: " + " ".join(f(am[i]) for i in range(15)) + f" | latest head-done signal {f(am[15])}")
         for j, lab in ((0, "first"), (1, "last ")):
             print(f"rep {rep}: o_proj {lab} [start issued landed heads-done mfma-done barrier end]: " + " ".join(f(os_[8 * j + i]) for i in range(7)))
-print(f"S={S} tau={tau} WGS={os.environ.get('DFL_ATTN_OPROJ_WGS', '256')} TILES={os.environ.get('DFL_ATTN_OPROJ_TILES', '4')}: "
+print(f"S={S} tau={tau} WGS={KNOBS['DFL_ATTN_OPROJ_WGS']} TILES={KNOBS['DFL_ATTN_OPROJ_TILES']}: "
       f"event-to-event {sorted(tot)[len(tot) // 2]:.1f} us (median of {len(tot)})")

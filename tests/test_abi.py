@@ -70,3 +70,14 @@ def test_product_never_imports_the_oracle():
         if fn.endswith(".py"):
             src = open(os.path.join(pkg, fn)).read()
             assert "oracle" not in src.replace("the oracle", ""), fn
+
+
+def test_library_reads_no_environment():
+    """The shipped library keeps no process state beyond what include/dflash_hip.h names: no source or header of it
+    calls getenv, and target.py picks the MoE launch forms by shape, not by a DFL_MOE_* variable."""
+    for d in (os.path.join(H.ROOT, "dflash_amd", "csrc"), os.path.join(H.ROOT, "include")):
+        files = sorted(os.listdir(d))
+        assert files, d
+        for fn in files:
+            assert "getenv" not in open(os.path.join(d, fn)).read(), fn
+    assert "DFL_MOE_" not in open(os.path.join(H.ROOT, "dflash_amd", "target.py")).read()
