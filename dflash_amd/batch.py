@@ -53,7 +53,7 @@ class BatchedDecoder:
     def __init__(self, model: DFlashDraftModel, target: NativeTarget, n_requests: int, max_rows: int,
                  out_len: int, mask_token_id: int, stop_token_ids=None, max_splits: int = 32,
                  temperature: float = 0.0, tiles_per_request: int = 1, sampler: str = "torch",
-                 draft_temperature: float = 0.0, filtering: bool = False):
+                 draft_temperature: float = 0.0, filtering: bool = False, request_temperature: bool = False):
         if not isinstance(target, NativeTarget):
             raise TypeError("BatchedDecoder needs a dflash_amd.NativeTarget (see module docstring)")
         if tiles_per_request not in (1, 2):
@@ -68,6 +68,9 @@ class BatchedDecoder:
         if filtering and temperature >= 1e-5 and sampler != "device":
             raise ValueError("top_k / top_p at T > 0 need sampler='device' (sampler='torch' is the reference's unfiltered "
                              "multinomial)")
+        if request_temperature and sampler != "device":
+            raise ValueError("request_temperature needs sampler='device': a slot's temperature is read by the seeded draw "
+                             "on the device")
         if model.w is None:
             raise RuntimeError("draft weights not loaded")
         c, t = model.config, target
@@ -111,7 +114,12 @@ class BatchedDecoder:
         # filtering (fixed here: it fixes the captured launch sequence): the verify materialises its logits and
         # dfl_sample_rows_nucleus draws under each slot's top_k / top_p (0 / 1.0: that slot's plain draw, same ids as the
         # fused epilogue's); at T = 0 the argmax is always kept and the greedy path runs unchanged
-        self.filtering = bool(filtering) and self.temperature >= 1e-5
+        # request_temperature (fixed here for the same reason): every slot draws at its own invT, read by address from
+        # inv_ts beside its seed; 0 is a greedy slot ("Per-request temperature").  `temperature` is
+        # then only the default of admit(): the verify runs the _t launch forms whatever it is.
+        self.request_temperature = bool(request_temperature)
+        self.inv_ts = z(NREQ, dt=F32) if self.request_temperature else None
+        self.filtering = bool(filtering) and (self.temperature >= 1e-5 or self.request_temperature)
         self.top_k, self.top_p = z(NREQ, dt=I32), torch.ones(NREQ, dtype=F32, device=dev)
         if self.filtering:
             self._logits = z(MT, 16, target.V)
@@ -209,6 +217,8 @@ class BatchedDecoder:
         # the slot's filter, re-armed on every admission (0 / 1.0: off); two small fills, admissions are never captured
         self.top_k[r:r + 1].fill_(flt["top_k"] if flt else 0)
         self.top_p[r:r + 1].fill_(flt["top_p"] if flt else 1.0)
+        if self.request_temperature:   # the slot's invT for every later token; 0: greedy
+            self.inv_ts[r:r + 1].fill_(ops.inv_temperature(temperature) if temperature >= 1e-5 else 0.0)
         th = _taps(out.hidden_states, m.target_layer_ids)[0]          # [P, fc_in]
         n_tail = min(16, P)
         dc = _View(self.dk[r], self.dv[r], torch.zeros(8, dtype=I32, device=self.dev), self.max_rows)
@@ -223,6 +233,8 @@ class BatchedDecoder:
         model, K/V into the group cache, first token sampled, the prompt's context rows
         projected into the draft cache except the last <= 16, which become the first
         cycle's context tile.  seed (sampler="device"): the request's seed (None: one from torch's RNG).
+        temperature: of the first token; of every later token too in a decoder built with request_temperature=True
+        (otherwise those are drawn at the decoder's).
         top_k / top_p: the request's filter (a decoder built with filtering=True), written into the slot's device words."""
         P, first, th, sd = self._admit_prefill(r, input_ids, temperature, seed, top_k, top_p)
         self.output_ids[r].fill_(self.mask_id)
@@ -368,7 +380,17 @@ class BatchedDecoder:
         st.run(t.layers, R, dyn_t, attend, qkv=qkv, taps=self.d["taps"], tap_layers=self.model.target_layer_ids,
                moe=t.moe_mlp_tiles)
         st.finish(t.norm)
-        if self.temperature < 1e-5:
+        if self.request_temperature and self.filtering:   # greedy slots keep the argmax ids the first launch wrote
+            ops.gemm_argmax_batch(self.lm_wp, s["xn"], R, t.V, H, 0, 16, self.gws, self.post.view(-1, 16), 0, dyn_t,
+                                  nrows_dyn_word=ops.DYN_BS, logits=self._logits)
+            ops.sample_rows_nucleus(self._logits[:R], seed=self.seeds, top_k=self.top_k, top_p=self.top_p,
+                                    inv_t=self.inv_ts, dyn=dyn_t, nrows_dyn_word=ops.DYN_BS, pos_word=ops.DYN_POS0,
+                                    pos_add=1, tiles_per_req=TPR, out=self.post.view(-1, 16))
+        elif self.request_temperature:   # the fused draw at each slot's own invT; a greedy slot takes the plain argmax
+            ops.gemm_sample_batch(self.lm_wp, s["xn"], R, t.V, H, 0, 16, self.gws, self.post.view(-1, 16), 0, dyn_t,
+                                  seeds=self.seeds, inv_ts=self.inv_ts, pos_word=ops.DYN_POS0, pos_add=1,
+                                  tiles_per_req=TPR, nrows_dyn_word=ops.DYN_BS)
+        elif self.temperature < 1e-5:
             ops.gemm_argmax_batch(self.lm_wp, s["xn"], R, t.V, H, 0, 16, self.gws, self.post.view(-1, 16), 0, dyn_t,
                                   nrows_dyn_word=ops.DYN_BS)
         elif self.filtering:   # materialise, then the filtered draw: tile j row m -> start + 16 j + m + 1
@@ -512,14 +534,31 @@ def _prompt_seeds(sampler: str, seed, n: int, sampling: bool) -> list:
     return seeds
 
 
-def _prompt_filters(top_k, top_p, n: int, temperature: float, sampler: str):
-    """(top_k per prompt, top_p per prompt, whether any prompt filters a sampled draw) from scalars or sequences."""
+def _prompt_temperatures(temperature, n: int, sampler: str):
+    """(temperature per prompt, whether the prompts need a decoder built with request_temperature=True) from one float or
+    one value per prompt.  A scalar or equal values run the single-temperature path; values that differ need
+    sampler='device'."""
+    if isinstance(temperature, (int, float)):
+        return [float(temperature)] * n, False
+    ts = [float(t) for t in temperature]
+    if len(ts) != n:
+        raise ValueError("temperature: one float or one value per prompt")
+    mixed = any(t != ts[0] for t in ts)
+    if mixed and sampler != "device":
+        raise ValueError("per-prompt temperatures that differ need sampler='device'")
+    return ts, mixed
+
+
+def _prompt_filters(top_k, top_p, n: int, temperature, sampler: str):
+    """(top_k per prompt, top_p per prompt, whether any prompt filters a sampled draw) from scalars or sequences;
+    temperature: one float, or the list _prompt_temperatures returns."""
     ks = [top_k] * n if isinstance(top_k, int) else list(top_k)
     ps = [top_p] * n if isinstance(top_p, (int, float)) else list(top_p)
     if len(ks) != n or len(ps) != n:
         raise ValueError("top_k / top_p: a scalar or one value per prompt")
     on = [ops.check_filter(k, p) for k, p in zip(ks, ps)]
-    filtering = any(on) and temperature >= 1e-5
+    ts = [temperature] * n if isinstance(temperature, (int, float)) else list(temperature)
+    filtering = any(o and t >= 1e-5 for o, t in zip(on, ts))
     if filtering and sampler != "device":
         raise ValueError("top_k / top_p at T > 0 need sampler='device' (sampler='torch' is the reference's unfiltered "
                          "multinomial)")
@@ -529,7 +568,7 @@ def _prompt_filters(top_k, top_p, n: int, temperature: float, sampler: str):
 @torch.inference_mode()
 def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_ids: Sequence[torch.Tensor],
                           mask_token_id: int, max_new_tokens: int, block_size: int, stop_token_ids,
-                          temperature: float = 0.0, draft_token_hook: Optional[Callable] = None,
+                          temperature=0.0, draft_token_hook: Optional[Callable] = None,
                           group_size: int = MAX_GROUP, hook_block_view: bool = False, sampler: str = "torch",
                           seed=None, top_k=0, top_p=1.0) -> list:
     """`dflash_generate` (benchmark.py:44-251) for a list of prompts: requests run in
@@ -539,9 +578,12 @@ def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_i
     sampler="device": seeded draws on the device; seed is an int s (prompt i gets s + i), one seed
     per prompt, or None (one per prompt from torch's RNG).  Request i then emits what dflash_generate(..., seed=its seed)
     emits, however the group is formed.
-    top_k / top_p: a scalar, or one value per prompt (0 / 1.0: off), as in dflash_generate."""
-    seeds = _prompt_seeds(sampler, seed, len(input_ids), temperature >= 1e-5)
-    top_ks, top_ps, filtering = _prompt_filters(top_k, top_p, len(input_ids), temperature, sampler)
+    top_k / top_p: a scalar, or one value per prompt (0 / 1.0: off), as in dflash_generate.
+    temperature: one float, or one value per prompt; values that differ need sampler="device" and run every group through
+    a decoder built with request_temperature=True ("Per-request temperature")."""
+    temps, per_request = _prompt_temperatures(temperature, len(input_ids), sampler)
+    seeds = _prompt_seeds(sampler, seed, len(input_ids), any(t >= 1e-5 for t in temps))
+    top_ks, top_ps, filtering = _prompt_filters(top_k, top_p, len(input_ids), temps, sampler)
     if not 1 <= block_size <= 32:
         raise NotImplementedError("the batched loop takes blocks of 1..16 rows (one tile per request) or 17..32 rows (two)")
     tpr = 1 if block_size <= 16 else 2      # blocks of 17..32 rows: a request takes two of the group's four tiles
@@ -555,11 +597,11 @@ def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_i
         max_len = [p.shape[1] + max_new_tokens for p in prompts]
         dec = BatchedDecoder(model, target, len(idx), max_rows=pmax + max_new_tokens + 3 * 16 * tpr,
                              out_len=pmax + max_new_tokens + 16 * tpr, mask_token_id=mask_token_id,
-                             stop_token_ids=stop_token_ids, temperature=temperature, tiles_per_request=tpr,
-                             sampler=sampler, filtering=filtering)
+                             stop_token_ids=stop_token_ids, temperature=max(temps[i] for i in idx), tiles_per_request=tpr,
+                             sampler=sampler, filtering=filtering, request_temperature=per_request)
         t0 = cuda_time()
         for r, p in enumerate(prompts):
-            dec.admit(r, p, temperature, seed=seeds[idx[r]], top_k=top_ks[idx[r]], top_p=top_ps[idx[r]])
+            dec.admit(r, p, temps[idx[r]], seed=seeds[idx[r]], top_k=top_ks[idx[r]], top_p=top_ps[idx[r]])
         ttft = cuda_time() - t0
         taus = [[] for _ in idx]
         # (hook_block_view: the hook sees the block as the single-request loop hands it over, bs slots; default: the

@@ -55,6 +55,9 @@ struct GemmRArgs {
   const int64_t *seeds;
   float inv_t;
   int rng_stream, pos_word, pos_add, tiles_per_req;
+  // EPI_SAMPLE_T (with the EPI_SAMPLE fields but inv_t): request slot q draws at invT = inv_ts[q]; a slot whose value is
+  // not > 0 (0, negative, NaN) takes the plain argmax of EPI_ARGMAX: no Philox call, no noise
+  const float *inv_ts;
 };
 
 namespace {
@@ -73,7 +76,8 @@ __global__ __launch_bounds__(NW * 64) void dfl_k_gemm_r(GemmRArgs a) {
   constexpr int NPIECE = CK * MT;                 // 1 KiB pieces per chunk
   constexpr int SP = (NPIECE + NW - 1) / NW;      // pieces per wave and chunk (surplus: a duplicate of the last piece)
   constexpr int VMC = A * KPC * TPU + (A - 1) * SP;  // VMEM ops of a wave younger than its pieces of the chunk it is about to read
-  static_assert(EPI == EPI_SILU || EPI == EPI_ARGMAX || EPI == EPI_SAMPLE, "the ring form has these three epilogues");
+  constexpr bool ARG = EPI == EPI_ARGMAX || EPI == EPI_SAMPLE || EPI == EPI_SAMPLE_T;  // a running (perturbed) argmax per row
+  static_assert(EPI == EPI_SILU || ARG, "the ring form has the SiLU epilogue and the three argmax ones");
   static_assert(CK % KQ == 0 && VMC < 64, "chunk split / vmcnt immediate");
   static_assert(NS * NPIECE * 1024 <= 160 * 1024, "ring exceeds LDS");
   static_assert(NW * TPU * MT * 1024 <= 160 * 1024 || KQ == 1, "the final KQ-way sum reuses the ring's LDS (ring_lds_bytes)");
@@ -96,7 +100,7 @@ __global__ __launch_bounds__(NW * 64) void dfl_k_gemm_r(GemmRArgs a) {
     best[mt] = -INFINITY;
     bestn[mt] = 0x7fffffff;
     arg_rows[mt] = 0;
-    if (EPI == EPI_ARGMAX || EPI == EPI_SAMPLE) {
+    if (ARG && EPI != EPI_SAMPLE_T) {  // (EPI_SAMPLE_T reads the count in its epilogue: four fewer SGPRs across the K walk)
       arg_rows[mt] = a.nrows;
       if (a.dyn && a.nrows_word >= 0) arg_rows[mt] = a.dyn[mt * DFL_DYN_WORDS + a.nrows_word] - a.row0;
     }
@@ -247,8 +251,13 @@ __global__ __launch_bounds__(NW * 64) void dfl_k_gemm_r(GemmRArgs a) {
           o[r] = f2bf(act * ub);
         }
         *reinterpret_cast<bf16x4 *>(a.act + mt * a.act_stride + ((size_t)(n0 >> 3) * 16 + fm) * 8 + (n0 & 7)) = o;
-      } else {  // EPI_ARGMAX, EPI_SAMPLE
-        const bool live = (fm >= a.row0) && (fm < a.row0 + arg_rows[mt]);
+      } else {  // EPI_ARGMAX, EPI_SAMPLE, EPI_SAMPLE_T
+        int nlive = arg_rows[mt];
+        if (EPI == EPI_SAMPLE_T) {
+          nlive = a.nrows;
+          if (a.dyn && a.nrows_word >= 0) nlive = a.dyn[mt * DFL_DYN_WORDS + a.nrows_word] - a.row0;
+        }
+        const bool live = (fm >= a.row0) && (fm < a.row0 + nlive);
         if (a.logits && live) {
           bf16x4 o = {f2bf(s[0]), f2bf(s[1]), f2bf(s[2]), f2bf(s[3])};
           *reinterpret_cast<bf16x4 *>(a.logits + mt * a.logits_stride + (size_t)fm * a.N + n0) = o;
@@ -260,9 +269,26 @@ __global__ __launch_bounds__(NW * 64) void dfl_k_gemm_r(GemmRArgs a) {
           dfl_rng_words((uint64_t)a.seeds[q], (uint32_t)a.rng_stream, (uint32_t)(base + a.pos_add + 16 * j + fm),
                         (uint32_t)n0, a.rng_stream == (int)DFL_RNG_DRAFT ? (uint32_t)base : 0u, wd);
         }
+        // EPI_SAMPLE_T: the same draw at the tile's own invT (wave-uniform: one scalar load per tile and pass, as the
+        // seed's) under a uniform branch; a greedy tile skips it whole and compares what EPI_ARGMAX compares
+        float pv[4] = {0.f, 0.f, 0.f, 0.f};
+        if (EPI == EPI_SAMPLE_T) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) pv[r] = rbf(s[r]);
+          const int q = mt >> (a.tiles_per_req - 1), j = mt & (a.tiles_per_req - 1);  // (tiles_per_req is 1 or 2)
+          const float inv_t = a.inv_ts[q];
+          if (inv_t > 0.f) {
+            const int base = a.dyn[mt * DFL_DYN_WORDS + a.pos_word];
+            dfl_rng_words((uint64_t)a.seeds[q], (uint32_t)a.rng_stream, (uint32_t)(base + a.pos_add + 16 * j + fm),
+                          (uint32_t)n0, a.rng_stream == (int)DFL_RNG_DRAFT ? (uint32_t)base : 0u, wd);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) pv[r] = dfl_perturb_w(pv[r], inv_t, wd[r]);
+          }
+        }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          float vb = rbf(s[r]);  // lm_head output is bf16 before argmax (model/dflash.py:238,247); first maximum kept
+          // lm_head output is bf16 before argmax (model/dflash.py:238,247); first maximum kept
+          float vb = EPI == EPI_SAMPLE_T ? pv[r] : rbf(s[r]);
           if (EPI == EPI_SAMPLE) vb = dfl_perturb_w(vb, a.inv_t, wd[r]);  // Gumbel-max (dfl_rng.h)
           if (live && (vb > best[mt] || (vb == best[mt] && n0 + r < bestn[mt]) || bestn[mt] == 0x7fffffff)) {
             best[mt] = vb;
@@ -321,7 +347,7 @@ __global__ __launch_bounds__(NW * 64) void dfl_k_gemm_r(GemmRArgs a) {
     }
   }
 
-  if (EPI == EPI_ARGMAX || EPI == EPI_SAMPLE) {
+  if (ARG) {
     // the waves' candidates per (request, row) meet in LDS: ONE entry per workgroup goes out (the finish kernel scans
     // gridDim.x entries per row, not gridDim.x * NW: 30 us -> 5 us at 256 x 16)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (padding pieces past the last chunk still target the ring)

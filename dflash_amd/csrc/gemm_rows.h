@@ -6,7 +6,8 @@
 namespace {
 
 enum { EPI_F32 = 0, EPI_SILU = 1, EPI_ARGMAX = 2, EPI_RESID = 3, EPI_SILU_E = 4 /* SILU over a list of active experts */,
-       EPI_SAMPLE = 5 /* EPI_ARGMAX over bf16(logit) * invT + Gumbel noise (dfl_rng.h) */ };
+       EPI_SAMPLE = 5 /* EPI_ARGMAX over bf16(logit) * invT + Gumbel noise (dfl_rng.h) */,
+       EPI_SAMPLE_T = 6 /* EPI_SAMPLE with invT per request slot from a device array; !(invT > 0): that slot's plain argmax */ };
 
 struct RowSrc {
   const bf16x8 *frag;  // mode 0: frag16 [KS][64]

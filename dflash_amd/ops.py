@@ -241,13 +241,16 @@ def check_filter(top_k, top_p) -> bool:
     return int(top_k) > 0 or float(top_p) < 1.0
 
 
-def sample_rows_nucleus(logits: torch.Tensor, *, temperature: float, top_k=0, top_p=1.0, seed=0, row0: int = 0,
+def sample_rows_nucleus(logits: torch.Tensor, *, temperature: Optional[float] = None, top_k=0, top_p=1.0, seed=0, row0: int = 0,
                         nrows: Optional[int] = None, dyn=None, nrows_dyn_word: int = -1, pos_word: int = -1,
                         pos_base: int = 0, positions=None, pos_add: int = 0, tiles_per_req: int = 1,
                         stream: int = RNG_TARGET, extra: int = 0, out: Optional[torch.Tensor] = None, out_off: int = 0,
-                        thresholds: Optional[torch.Tensor] = None, kept: Optional[torch.Tensor] = None) -> torch.Tensor:
+                        thresholds: Optional[torch.Tensor] = None, kept: Optional[torch.Tensor] = None,
+                        inv_t: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The seeded draw under top-k / top-p (dfl_sample_rows_nucleus) over materialised bf16 logits
     [rows <= 16, V] (one tile) or [tiles, 16, V], unit inner stride.
+    inv_t: a device fp32 tensor of invT per request slot (dfl_sample_rows_nucleus_t; `temperature` is then unused, pass
+    None): a slot whose value is not > 0 is greedy, its rows of out / thresholds / kept are not written.
     seed / top_k / top_p: a host value, or a device tensor (int64 / int32 / fp32) indexed by request slot
     q = tile // tiles_per_req.  Tile t row m draws position positions[16 t + m] (int32 tensor), or
     (dyn[t][pos_word] if pos_word >= 0 else pos_base) + pos_add + 16 (t % tiles_per_req) + m.  Rows of a tile:
@@ -295,6 +298,17 @@ def sample_rows_nucleus(logits: torch.Tensor, *, temperature: float, top_k=0, to
     p_p, p_v = dev_or_host(top_p, F32, "top_p", float)
     if p_p is not None:
         p_v = 1.0
+    if (temperature is None) == (inv_t is None):
+        raise ValueError("sample_rows_nucleus: give either temperature or inv_t")
+    if inv_t is not None:
+        assert inv_t.numel() >= slots, "inv_t"
+        check(lib().dfl_sample_rows_nucleus_t(logits.data_ptr(), ld, tile_stride, tiles, V, row0, nrows, _p(dyn, I32, "dyn"),
+                                              nrows_dyn_word, pos_word, pos_base, _p(positions, I32, "positions"), pos_add,
+                                              tiles_per_req, seeds_p, seed_v, k_p, k_v, p_p, p_v, _p(inv_t, F32, "inv_t"),
+                                              0.0, stream, extra, _p(out, I64, "out"), out_stride, out_off,
+                                              _p(thresholds, F32, "thresholds"), _p(kept, I32, "kept"), _stream()),
+              "dfl_sample_rows_nucleus_t")
+        return out
     check(lib().dfl_sample_rows_nucleus(logits.data_ptr(), ld, tile_stride, tiles, V, row0, nrows, _p(dyn, I32, "dyn"),
                                         nrows_dyn_word, pos_word, pos_base, _p(positions, I32, "positions"), pos_add,
                                         tiles_per_req, seeds_p, seed_v, k_p, k_v, p_p, p_v,
@@ -735,11 +749,16 @@ def seed_i64(seed: int) -> int:
 
 
 def gemm_sample_batch(wp, x: BatchRowSource, R: int, V: int, K: int, row0: int, nrows: int, ws,
-                      out_ids: torch.Tensor, out_off: int, dyn, *, seeds: torch.Tensor, temperature: float,
+                      out_ids: torch.Tensor, out_off: int, dyn, *, seeds: torch.Tensor, temperature: Optional[float] = None,
                       stream: int = RNG_TARGET, pos_word: int = DYN_POS0, pos_add: int = 0, tiles_per_req: int = 1,
-                      nrows_dyn_word: int = -1, logits: Optional[torch.Tensor] = None) -> None:
+                      nrows_dyn_word: int = -1, logits: Optional[torch.Tensor] = None,
+                      inv_ts: Optional[torch.Tensor] = None) -> None:
     """gemm_argmax_batch with the seeded draw (dfl_gemm_sample_batch): tile t (tile j = t % tiles_per_req of request
-    q = t // tiles_per_req) row m draws position dyn[t][pos_word] + pos_add + 16 j + m with seed seeds[q] (int64)."""
+    q = t // tiles_per_req) row m draws position dyn[t][pos_word] + pos_add + 16 j + m with seed seeds[q] (int64).
+    Either `temperature` (one host value for the launch) or inv_ts (dfl_gemm_sample_batch_t): a device fp32 tensor of
+    invT per request slot q, a slot whose value is not > 0 taking gemm_argmax_batch's plain argmax."""
+    if (temperature is None) == (inv_ts is None):
+        raise ValueError("gemm_sample_batch: give either temperature or inv_ts")
     assert out_ids.dim() == 2 and out_ids.dtype == I64 and out_ids.stride(1) == 1
     mt = batch_tiles(R)
     assert dyn is not None and dyn.numel() >= 8 * mt and seeds.numel() >= mt // tiles_per_req
@@ -747,6 +766,13 @@ def gemm_sample_batch(wp, x: BatchRowSource, R: int, V: int, K: int, row0: int, 
     if logits is not None:
         assert logits.dim() == 3 and logits.shape[1] == 16 and logits.shape[2] == V and logits.is_contiguous()
         lp, lst = _p(logits, BF16, "logits"), logits.stride(0)
+    if inv_ts is not None:
+        assert inv_ts.numel() >= mt // tiles_per_req, "inv_ts"
+        check(lib().dfl_gemm_sample_batch_t(_p(wp, BF16, "wp"), x.ref, R, V, K, row0, nrows, _p(dyn, I32, "dyn"),
+                                            nrows_dyn_word, _p(ws), out_ids.data_ptr(), out_ids.stride(0), out_off, lp, lst,
+                                            _p(seeds, I64, "seeds"), _p(inv_ts, F32, "inv_ts"), stream, pos_word, pos_add,
+                                            tiles_per_req, _stream()), "dfl_gemm_sample_batch_t")
+        return
     check(lib().dfl_gemm_sample_batch(_p(wp, BF16, "wp"), x.ref, R, V, K, row0, nrows, _p(dyn, I32, "dyn"), nrows_dyn_word,
                                       _p(ws), out_ids.data_ptr(), out_ids.stride(0), out_off, lp, lst,
                                       _p(seeds, I64, "seeds"), inv_temperature(temperature), stream, pos_word, pos_add,

@@ -406,6 +406,18 @@ int dfl_sample_rows_nucleus(const void *logits, int64_t ld, int64_t tile_stride,
                             int top_k, const float *top_p_dev, float top_p, float inv_t, int rng_stream, int extra,
                             int64_t *out_ids, int64_t out_stride, int out_off, float *thr_out, int32_t *kept_out,
                             void *stream);
+/* dfl_sample_rows_nucleus with invT per request slot: inv_t_dev is a device fp32 array indexed by q (NULL: the host inv_t,
+ * as with top_k_dev / top_k; a non-NULL array makes the host value unused and unchecked).  The slot's invT feeds both the
+ * masses exp(invT (x - max)) and the draw.  A slot whose value is not > 0 (0, negative, NaN) is GREEDY: its rows return at
+ * once and write nothing — out_ids, thr_out and kept_out keep what they held, the way rows past a tile's valid count do.
+ * In the filtering verify the dfl_gemm_argmax_batch launch in front has already written that slot's argmax ids (lowest
+ * index on ties) where this launch would write.  Device values are not validated: every bit pattern is defined. */
+int dfl_sample_rows_nucleus_t(const void *logits, int64_t ld, int64_t tile_stride, int tiles, int V, int row0, int nrows,
+                              const int32_t *dyn, int nrows_dyn_word, int pos_word, int pos_base, const int32_t *positions,
+                              int pos_add, int tiles_per_req, const int64_t *seeds, uint64_t seed, const int32_t *top_k_dev,
+                              int top_k, const float *top_p_dev, float top_p, const float *inv_t_dev, float inv_t,
+                              int rng_stream, int extra, int64_t *out_ids, int64_t out_stride, int out_off, float *thr_out,
+                              int32_t *kept_out, void *stream);
 
 /* Acceptance scan + commit + bonus token + stop test + length bookkeeping in one
  * wavefront (model/dflash.py:258-268):
@@ -571,6 +583,18 @@ int dfl_gemm_sample_batch(const void *wp, const dfl_rows_batch *x, int R, int V,
                           const int32_t *dyn, int nrows_dyn_word, void *ws, int64_t *out_ids, int64_t out_stride,
                           int out_off, void *logits, int64_t logits_stride, const int64_t *seeds, float inv_t,
                           int rng_stream, int pos_word, int pos_add, int tiles_per_req, void *stream);
+/* dfl_gemm_sample_batch with invT per request slot (EPI_SAMPLE_T epilogue): inv_ts is a device fp32 array of
+ * batch_tiles(R) / tiles_per_req entries, indexed by q like seeds, read by address on every launch (a replayed graph sees
+ * what an admission wrote).  Per slot:
+ *   inv_ts[q] > 0     sampled: argmax_v fmaf(bf16(logit_v), inv_ts[q], noise of dfl_rng.h) — dfl_gemm_sample_batch's draw
+ *                     at that slot's own invT (the host writes float32(1 / T));
+ *   otherwise         (0, negative, NaN) greedy: argmax_v bf16(logit_v), lowest v on ties, no Philox call and no noise —
+ *                     bit for bit the ids of dfl_gemm_argmax_batch on the same inputs.
+ * Device values are not validated.  -22 on a null pointer (inv_ts included) and wherever dfl_gemm_sample_batch returns it. */
+int dfl_gemm_sample_batch_t(const void *wp, const dfl_rows_batch *x, int R, int V, int K, int row0, int nrows,
+                            const int32_t *dyn, int nrows_dyn_word, void *ws, int64_t *out_ids, int64_t out_stride,
+                            int out_off, void *logits, int64_t logits_stride, const int64_t *seeds, const float *inv_ts,
+                            int rng_stream, int pos_word, int pos_add, int tiles_per_req, void *stream);
 /* dfl_embed_rows for R requests: ids[r * ids_stride + m]. */
 int dfl_embed_rows_batch(const void *embed, const int64_t *ids, int64_t ids_stride, int R, void *h_out,
                          int64_t h_stride, int H, float *ss_out, int64_t ss_stride, const int32_t *dyn, int dyn_word,
