@@ -45,14 +45,11 @@ SIGNATURES = {
     "dfl_gemm_resid": (_i, [_p, _r, _i, _i, _p, _i64, _i, _p, _i64, _p, _p, _p]),
     "dfl_embed_rows": (_i, [_p, _p, _p, _i, _p, _p, _i, _p]),
     "dfl_argmax_ws_bytes": (_i64, []),
-    "dfl_gemm_argmax": (_i, [_p, _r, _i, _i, _i, _i, _p, _i, _p, _p, _i, _p, _p, _p]),
-    "dfl_gemm_argmax_timed": (_i, [_p, _r, _i, _i, _i, _i, _p, _i, _p, _p, _i, _p, _p, _p, _p, _p]),
+    "dfl_gemm_argmax": (_i, [_p, _r, _i, _i, _i, _i, _p, _i, _p, _p, _i, _p, _p, _p, _p, _p]),
     "dfl_gemm_sample": (_i, [_p, _r, _i, _i, _i, _i, _p, _i, _p, _p, _i, _p, _p, _u64, _f, _i, _p, _i, _i, _i, _p]),
     "dfl_sample_rows": (_i, [_p, _i64, _i, _i, _u64, _f, _i, _i, _p, _i, _p, _p, _p]),
     "dfl_sample_rows_nucleus": (_i, [_p, _i64, _i64, _i, _i, _i, _i, _p, _i, _i, _i, _p, _i, _i, _p, _u64, _p, _i, _p, _f,
-                                     _f, _i, _i, _p, _i64, _i, _p, _p, _p]),
-    "dfl_sample_rows_nucleus_t": (_i, [_p, _i64, _i64, _i, _i, _i, _i, _p, _i, _i, _i, _p, _i, _i, _p, _u64, _p, _i, _p, _f,
-                                       _p, _f, _i, _i, _p, _i64, _i, _p, _p, _p]),
+                                     _p, _f, _i, _i, _p, _i64, _i, _p, _p, _p]),
     "dfl_norm_pack": (_i, [_p, _i, _i64, _i, _i, _p, _p, _p, _p, _p, _i64, _p, _f, _p, _i, _p, _i, _p]),
     "dfl_qknorm_rope_append": (_i, [_p, _i, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _f, _p, _p, _i, _p, _p, _p, _i, _p,
                                     _i, _i, _p]),
@@ -67,15 +64,11 @@ SIGNATURES = {
     "dfl_attn_head_oproj": (_i, [_p, _i64, _i, _i, _i, _p, _i64, _i, _i, _i, _i, _p, _p, _f, _p, _p, _i, _p, _p, _i, _f, _i,
                                  _p, _i, _i, _i, _i, _p, _i, _p, _p, _i, _p, _i64, _p, _p, _p]),
     "dfl_attn_head_cand": (_i, [_p, _i64, _i, _i, _i, _i, _i64, _i, _i, _p, _p, _f, _p, _p, _i, _p, _p, _i, _f, _i, _i,
-                                _p, _i, _p, _i64, _p, _p, _i64, _i, _p]),
-    "dfl_attn_head_cand_t": (_i, [_p, _i64, _i, _i, _i, _i, _i64, _i, _i, _p, _p, _f, _p, _p, _i, _p, _p, _i, _f, _i, _i,
-                                  _p, _i, _p, _i64, _i64, _i, _p, _p, _i64, _i, _p]),
-    "dfl_attn_head_batch": (_i, [_p, _i64, _i, _i, _i, _i, _i64, _i, _i, _p, _p, _f, _p, _p, _i, _p, _p, _i, _i64, _f, _i,
-                                 _p, _i, _p, _i, _p, _i64, _p]),
+                                _p, _i, _p, _i64, _i64, _i, _p, _p, _i64, _i, _p]),
     "dfl_attn_head_batch_f32": (_i, [_p, _i, _i64, _i64, _i, _i, _i, _i, _i64, _i, _i, _p, _p, _f, _p, _p, _i, _p, _p, _i, _i64, _f,
                                      _i, _p, _i, _p, _i, _p, _i64, _p]),
-    "dfl_attn_head_batch_t": (_i, [_p, _i64, _i, _i, _i, _i, _i64, _i, _i, _p, _p, _f, _p, _p, _i, _p, _p, _i, _i64, _f, _i,
-                                   _p, _i, _p, _i, _p, _i64, _i64, _i, _p]),
+    "dfl_attn_head_batch": (_i, [_p, _i64, _i, _i, _i, _i, _i64, _i, _i, _p, _p, _f, _p, _p, _i, _p, _p, _i, _i64, _f, _i,
+                                 _p, _i, _p, _i, _p, _i64, _i64, _i, _p]),
     "dfl_topk_rows": (_i, [_p, _i64, _i, _i, _i, _p, _p, _p, _p]),
     "dfl_candidate_select": (_i, [_p, _i64, _p, _i64, _p, _i, _i, _p, _i64, _p, _p, _i, _p, _p]),
     "dfl_moe_route": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _i, _p]),
@@ -84,9 +77,7 @@ SIGNATURES = {
     "dfl_moe_gate_up": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _p, _i, _p]),
     "dfl_moe_down": (_i, [_p, _i64, _p, _i64, _p, _p, _p, _i, _i, _i, _i, _p, _p]),
     "dfl_argmax": (_i, [_p, _i, _i, _i64, _p, _p]),
-    "dfl_accept_commit": (_i, [_p, _p, _i, _p, _i64, _p, _p, _i, _p, _p]),
-    "dfl_accept_commit_rearm": (_i, [_p, _p, _i, _p, _i64, _p, _p, _i, _p, _p, _i, _i64, _p]),
-    "dfl_accept_commit_rearm_t": (_i, [_p, _p, _i, _p, _i64, _p, _p, _i, _p, _p, _i, _i64, _p, _p]),
+    "dfl_accept_commit": (_i, [_p, _p, _i, _p, _i64, _p, _p, _i, _p, _p, _i, _i64, _p, _p]),
     # ---- target prefill
     "dfl_prefill_rows_padded": (_i64, [_i]),
     "dfl_prefill_gemm_rows": (_i, [_p, _p, _i, _i, _i, _p, _i64, _p]),
@@ -111,21 +102,16 @@ SIGNATURES = {
     "dfl_gemm_silu_mul_batch": (_i, [_p, _rb, _i, _i, _i, _p, _i64, _p, _p, _p]),
     "dfl_gemm_resid_batch": (_i, [_p, _rb, _i, _i, _i, _p, _i64, _i64, _i, _p, _i64, _i64, _p, _i64, _p, _p, _p]),
     "dfl_gemm_argmax_batch": (_i, [_p, _rb, _i, _i, _i, _i, _i, _p, _i, _p, _p, _i64, _i, _p, _i64, _p]),
-    "dfl_gemm_sample_batch": (_i, [_p, _rb, _i, _i, _i, _i, _i, _p, _i, _p, _p, _i64, _i, _p, _i64, _p, _f, _i, _i, _i, _i,
+    "dfl_gemm_sample_batch": (_i, [_p, _rb, _i, _i, _i, _i, _i, _p, _i, _p, _p, _i64, _i, _p, _i64, _p, _p, _f, _i, _i, _i, _i,
                                    _p]),
-    "dfl_gemm_sample_batch_t": (_i, [_p, _rb, _i, _i, _i, _i, _i, _p, _i, _p, _p, _i64, _i, _p, _i64, _p, _p, _i, _i, _i, _i,
-                                     _p]),
     "dfl_embed_rows_batch": (_i, [_p, _p, _i64, _i, _p, _i64, _i, _p, _i64, _p, _i, _p]),
     "dfl_norm_frag_batch": (_i, [_p, _i64, _i64, _i, _p, _i, _i64, _i, _p, _i64, _i64, _p, _f, _p, _i64, _i, _p, _i, _p]),
     "dfl_kv_append_batch": (_i, [_p, _i, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _p, _i64, _f, _p, _p, _i, _p, _p, _i,
-                                 _i64, _i64, _p, _p]),
-    "dfl_kv_append_batch_t": (_i, [_p, _i, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _p, _i64, _f, _p, _p, _i, _p, _p, _i,
-                                   _i64, _i64, _p, _i, _p]),
+                                 _i64, _i64, _p, _i, _p]),
     "dfl_attn_fused_batch_ws_bytes": (_i64, [_i, _i, _i, _i]),
     "dfl_attn_fused_batch": (_i, [_p, _i, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _f, _p, _p, _i, _p, _p, _i,
                                   _i64, _f, _i, _p, _i, _p, _i, _p, _i64, _p]),
-    "dfl_accept_commit_batch": (_i, [_p, _i64, _p, _i64, _i, _p, _i64, _i64, _p, _p, _p, _i, _p, _p, _i64, _p]),
-    "dfl_accept_commit_batch_t": (_i, [_p, _i64, _p, _i64, _i, _p, _i64, _i64, _p, _p, _p, _i, _p, _p, _i64, _i, _p, _p, _p]),
+    "dfl_accept_commit_batch": (_i, [_p, _i64, _p, _i64, _i, _p, _i64, _i64, _p, _p, _p, _i, _p, _p, _i64, _i, _p, _p, _p]),
     "dfl_admit_slot": (_i, [_i, _i, _p, _i, _p, _p, _i64, _i64, _p, _p, _i, _p, _p, _i64, _i, _p, _i, _p, _p, _i, _p, _i64,
                             _i64, _p]),
 }

@@ -80,7 +80,7 @@ class BatchedDecoder:
         # Blocks of 17..32 rows (benchmark.py's block-size sweep): a request takes TPR = 2 consecutive 16-row tiles of every
         # per-tile launch (GEMMs, norms, embedding, context K/V append), one cache, one slot of the attention / accept
         # launches.  Two kinds of length records then: per REQUEST (dyn_d / dyn_t: attention, accept) and per TILE (dyn_dt /
-        # dyn_tt: valid rows of each tile), both kept by dfl_accept_commit_batch_t.  TPR = 1: the same tensors.
+        # dyn_tt: valid rows of each tile), both kept by dfl_accept_commit_batch.  TPR = 1: the same tensors.
         self.TPR = TPR = tiles_per_request
         self.R, self.NT = n_requests, n_requests * TPR
         self.MT = ops.batch_tiles(self.NT)

@@ -285,75 +285,43 @@ extern "C" int dfl_sample_rows(const void *logits, int64_t ld, int rows, int V, 
   return DFL_OK;
 }
 
+// next_block == NULL: no re-arm (rearm_n / mask_id unused); dyn_t (optional) needs next_block.
 extern "C" int dfl_accept_commit(const int64_t *block_ids, const int64_t *posterior, int bs, int64_t *output_ids,
                                  int64_t output_len, int32_t *dyn, const int64_t *stop_ids, int n_stop,
-                                 int32_t *result, void *stream) {
+                                 int32_t *result, int64_t *next_block, int rearm_n, int64_t mask_id, int32_t *dyn_t,
+                                 void *stream) {
   DFL_REQUIRE(block_ids && posterior && output_ids && dyn, "dfl_accept_commit: null pointer");
+  DFL_REQUIRE(next_block || !dyn_t, "dfl_accept_commit: dyn_t is kept only together with the re-arm (next_block is null)");
   // lane acc + 1 <= bs writes the bonus token: bs = 64 would need a 65th lane
   DFL_REQUIRE(bs >= 1 && bs <= 63, "dfl_accept_commit: bs=%d outside 1..63", bs);
+  DFL_REQUIRE(!next_block || (rearm_n >= 1 && rearm_n <= 64), "dfl_accept_commit: rearm_n=%d outside 1..64", rearm_n);
   DFL_REQUIRE(n_stop == 0 || stop_ids, "dfl_accept_commit: n_stop>0 without stop_ids");
+  if (!next_block) rearm_n = 0, mask_id = 0;
   hipLaunchKernelGGL(k_accept_commit, dim3(1), dim3(64), 0, (hipStream_t)stream, block_ids, posterior, bs, output_ids,
-                     output_len, dyn, stop_ids, n_stop, result, (int64_t *)nullptr, 0, (int64_t)0, (int32_t *)nullptr);
+                     output_len, dyn, stop_ids, n_stop, result, next_block, rearm_n, mask_id, dyn_t);
   DFL_CHECK_LAUNCH("dfl_accept_commit");
   return DFL_OK;
 }
 
-extern "C" int dfl_accept_commit_rearm(const int64_t *block_ids, const int64_t *posterior, int bs, int64_t *output_ids,
-                                       int64_t output_len, int32_t *dyn, const int64_t *stop_ids, int n_stop,
-                                       int32_t *result, int64_t *next_block, int rearm_n, int64_t mask_id, void *stream) {
-  DFL_REQUIRE(block_ids && posterior && output_ids && dyn && next_block, "dfl_accept_commit_rearm: null pointer");
-  DFL_REQUIRE(bs >= 1 && bs <= 63 && rearm_n >= 1 && rearm_n <= 64, "dfl_accept_commit_rearm: bs=%d rearm_n=%d outside range", bs,
-              rearm_n);
-  DFL_REQUIRE(n_stop == 0 || stop_ids, "dfl_accept_commit_rearm: n_stop>0 without stop_ids");
-  hipLaunchKernelGGL(k_accept_commit, dim3(1), dim3(64), 0, (hipStream_t)stream, block_ids, posterior, bs, output_ids,
-                     output_len, dyn, stop_ids, n_stop, result, next_block, rearm_n, mask_id, (int32_t *)nullptr);
-  DFL_CHECK_LAUNCH("dfl_accept_commit_rearm");
-  return DFL_OK;
-}
-
-extern "C" int dfl_accept_commit_rearm_t(const int64_t *block_ids, const int64_t *posterior, int bs, int64_t *output_ids,
-                                         int64_t output_len, int32_t *dyn, const int64_t *stop_ids, int n_stop,
-                                         int32_t *result, int64_t *next_block, int rearm_n, int64_t mask_id, int32_t *dyn_t,
-                                         void *stream) {
-  DFL_REQUIRE(block_ids && posterior && output_ids && dyn && next_block && dyn_t, "dfl_accept_commit_rearm_t: null pointer");
-  DFL_REQUIRE(bs >= 1 && bs <= 63 && rearm_n >= 1 && rearm_n <= 64, "dfl_accept_commit_rearm_t: bs=%d rearm_n=%d outside range", bs,
-              rearm_n);
-  DFL_REQUIRE(n_stop == 0 || stop_ids, "dfl_accept_commit_rearm_t: n_stop>0 without stop_ids");
-  hipLaunchKernelGGL(k_accept_commit, dim3(1), dim3(64), 0, (hipStream_t)stream, block_ids, posterior, bs, output_ids,
-                     output_len, dyn, stop_ids, n_stop, result, next_block, rearm_n, mask_id, dyn_t);
-  DFL_CHECK_LAUNCH("dfl_accept_commit_rearm_t");
-  return DFL_OK;
-}
-
+// Tile records given (required for tiles_per_req == 2): the per-tile form, whose block holds 16 * tiles_per_req slots.
 extern "C" int dfl_accept_commit_batch(const int64_t *block_ids, int64_t blk_stride, const int64_t *posterior,
                                        int64_t post_stride, int R, int64_t *output_ids, int64_t out_stride,
                                        int64_t output_len, int32_t *dyn_d, int32_t *dyn_t, const int64_t *stop_ids,
-                                       int n_stop, int32_t *result, int64_t *next_block, int64_t mask_id,
-                                       void *stream) {
+                                       int n_stop, int32_t *result, int64_t *next_block, int64_t mask_id, int tiles_per_req,
+                                       int32_t *dyn_d_tiles, int32_t *dyn_t_tiles, void *stream) {
   DFL_REQUIRE(block_ids && posterior && output_ids && dyn_d && dyn_t, "dfl_accept_commit_batch: null pointer");
-  DFL_REQUIRE(R >= 1 && R <= 1024, "dfl_accept_commit_batch: R=%d outside 1..1024", R);
+  DFL_REQUIRE(R >= 1 && R <= 1024 && (tiles_per_req == 1 || tiles_per_req == 2),
+              "dfl_accept_commit_batch: R=%d tiles_per_req=%d outside range", R, tiles_per_req);
+  if (tiles_per_req == 2 || dyn_d_tiles || dyn_t_tiles) {
+    DFL_REQUIRE(dyn_d_tiles && dyn_t_tiles, "dfl_accept_commit_batch: null tile record");
+    DFL_REQUIRE(blk_stride >= 16 * tiles_per_req, "dfl_accept_commit_batch: blk_stride=%lld below the %d block slots",
+                (long long)blk_stride, 16 * tiles_per_req);
+  }
   DFL_REQUIRE(n_stop == 0 || stop_ids, "dfl_accept_commit_batch: n_stop>0 without stop_ids");
   hipLaunchKernelGGL(k_accept_commit_b, dim3(R), dim3(64), 0, (hipStream_t)stream, block_ids, blk_stride, posterior,
                      post_stride, output_ids, out_stride, output_len, dyn_d, dyn_t, stop_ids, n_stop, result, next_block,
-                     mask_id, 16, 1, (int32_t *)nullptr, (int32_t *)nullptr);
-  DFL_CHECK_LAUNCH("dfl_accept_commit_batch");
-  return DFL_OK;
-}
-
-extern "C" int dfl_accept_commit_batch_t(const int64_t *block_ids, int64_t blk_stride, const int64_t *posterior,
-                                         int64_t post_stride, int R, int64_t *output_ids, int64_t out_stride,
-                                         int64_t output_len, int32_t *dyn_d, int32_t *dyn_t, const int64_t *stop_ids,
-                                         int n_stop, int32_t *result, int64_t *next_block, int64_t mask_id, int tiles_per_req,
-                                         int32_t *dyn_d_tiles, int32_t *dyn_t_tiles, void *stream) {
-  DFL_REQUIRE(block_ids && posterior && output_ids && dyn_d && dyn_t && dyn_d_tiles && dyn_t_tiles,
-              "dfl_accept_commit_batch_t: null pointer");
-  DFL_REQUIRE(R >= 1 && R <= 1024 && (tiles_per_req == 1 || tiles_per_req == 2) && blk_stride >= 16 * tiles_per_req,
-              "dfl_accept_commit_batch_t: R=%d tiles_per_req=%d outside range", R, tiles_per_req);
-  DFL_REQUIRE(n_stop == 0 || stop_ids, "dfl_accept_commit_batch_t: n_stop>0 without stop_ids");
-  hipLaunchKernelGGL(k_accept_commit_b, dim3(R), dim3(64), 0, (hipStream_t)stream, block_ids, blk_stride, posterior,
-                     post_stride, output_ids, out_stride, output_len, dyn_d, dyn_t, stop_ids, n_stop, result, next_block,
                      mask_id, 16 * tiles_per_req, tiles_per_req, dyn_d_tiles, dyn_t_tiles);
-  DFL_CHECK_LAUNCH("dfl_accept_commit_batch_t");
+  DFL_CHECK_LAUNCH("dfl_accept_commit_batch");
   return DFL_OK;
 }
 

@@ -958,47 +958,82 @@ struct OprojTail {
   int32_t *sync;
 };
 
-int attn_head_launch(const void *xq, int64_t ldq, int q_col, int k_col, int v_col, const void *xc, int64_t ldc, int ck_col,
-                     int cv_col, int n_q, int n_kv, const void *q_norm_w, const void *k_norm_w, float eps,
-                     const void *cos_tab, const void *sin_tab, int max_pos, void *kcache, void *vcache, int cache_rows,
-                     float scale, int causal, const int32_t *dyn, int S, int tau, int bs, int pos0, int q_tiles, void *ws,
-                     int max_splits, void *out_frag, int64_t out_tile_stride, int n_cand, int64_t xq_cand_stride,
-                     int64_t out_cand_stride, void *k_out, void *v_out, int64_t kv_out_cand_stride, int out_rows,
-                     int dyn_cand_stride, int64_t cache_cand_stride, void *stream, const OprojTail *tail = nullptr,
-                     int nparts32 = 0, int64_t part_stride32 = 0) {
-  // nparts32 > 0: xq points at fp32 K-part sums (HeadAttnArgs::xq32; strides in floats)
-  DFL_REQUIRE(xq && cos_tab && sin_tab && kcache && vcache && out_frag && ws, "dfl_attn_head: null pointer");
-  DFL_REQUIRE(nparts32 >= 0 && nparts32 <= 2 && (nparts32 == 0 || (!tail && q_tiles == 1 && tau == 0 && !xc && part_stride32 % 4 == 0)),
+// What an entry point asks of attn_head_launch.  The defaults are a single block on the cache with one query tile:
+// an entry point names only the fields its form uses.
+struct HeadLaunch {
+  const void *xq = nullptr;  // block rows (nparts32 > 0: fp32 K-part sums, HeadAttnArgs::xq32, strides in floats)
+  int64_t ldq = 0;
+  int q_col = 0, k_col = 0, v_col = 0;
+  const void *xc = nullptr;  // context rows (the draft's single-request form only)
+  int64_t ldc = 0;
+  int ck_col = 0, cv_col = 0;
+  int n_q = 0, n_kv = 0;
+  const void *q_norm_w = nullptr, *k_norm_w = nullptr;
+  float eps = 0.f;
+  const void *cos_tab = nullptr, *sin_tab = nullptr;
+  int max_pos = 0;
+  void *kcache = nullptr, *vcache = nullptr;
+  int cache_rows = 0;
+  float scale = 0.f;
+  int causal = 0;
+  const int32_t *dyn = nullptr;  // null: the immediates below are the lengths; else S bounds dyn[S]
+  int S = 0, tau = 0, bs = 0, pos0 = 0;
+  int q_tiles = 1;
+  void *ws = nullptr;
+  int max_splits = 0;
+  void *out_frag = nullptr;
+  int64_t out_tile_stride = 0;
+  // several blocks per launch (grid.z): candidates on one cache, or the requests of a ragged batch
+  int n_cand = 1;
+  int64_t xq_cand_stride = 0, out_cand_stride = 0;
+  void *k_out = nullptr, *v_out = nullptr;  // K/V staging area of the candidates
+  int64_t kv_out_cand_stride = 0;
+  int out_rows = 0;
+  int dyn_cand_stride = 0;
+  int64_t cache_cand_stride = 0;
+  const OprojTail *tail = nullptr;
+  int nparts32 = 0;
+  int64_t part_stride32 = 0;
+  void *stream = nullptr;
+};
+
+int attn_head_launch(const HeadLaunch &L) {
+  DFL_REQUIRE(L.xq && L.cos_tab && L.sin_tab && L.kcache && L.vcache && L.out_frag && L.ws, "dfl_attn_head: null pointer");
+  DFL_REQUIRE(L.nparts32 >= 0 && L.nparts32 <= 2 &&
+                  (L.nparts32 == 0 || (!L.tail && L.q_tiles == 1 && L.tau == 0 && !L.xc && L.part_stride32 % 4 == 0)),
               "dfl_attn_head: the fp32-partials form takes 1 or 2 K parts, one query tile, no context rows");
-  DFL_REQUIRE((q_norm_w == nullptr) == (k_norm_w == nullptr), "dfl_attn_head: give both norm weights or neither");
-  DFL_REQUIRE(n_q > 0 && n_kv > 0 && n_q % n_kv == 0, "dfl_attn_head: bad head counts (n_q=%d n_kv=%d)", n_q, n_kv);
-  DFL_REQUIRE(q_tiles == 1 || q_tiles == 2, "dfl_attn_head: q_tiles must be 1 or 2");
-  DFL_REQUIRE(ldq > 0 && ldq % 8 == 0 && q_col >= 0 && k_col >= 0 && v_col >= 0 && q_col % 8 == 0 && k_col % 8 == 0 &&
-                  v_col % 8 == 0 && max_pos > 0,
+  DFL_REQUIRE((L.q_norm_w == nullptr) == (L.k_norm_w == nullptr), "dfl_attn_head: give both norm weights or neither");
+  DFL_REQUIRE(L.n_q > 0 && L.n_kv > 0 && L.n_q % L.n_kv == 0, "dfl_attn_head: bad head counts (n_q=%d n_kv=%d)", L.n_q, L.n_kv);
+  DFL_REQUIRE(L.q_tiles == 1 || L.q_tiles == 2, "dfl_attn_head: q_tiles must be 1 or 2");
+  DFL_REQUIRE(L.ldq > 0 && L.ldq % 8 == 0 && L.q_col >= 0 && L.k_col >= 0 && L.v_col >= 0 && L.q_col % 8 == 0 &&
+                  L.k_col % 8 == 0 && L.v_col % 8 == 0 && L.max_pos > 0,
               "dfl_attn_head: bad block-row layout");
-  DFL_REQUIRE(S >= 0 && tau >= 0 && tau <= 32 && bs >= 1 && bs <= 16 * q_tiles && tau + bs <= 64,
-              "dfl_attn_head: lengths S=%d tau=%d bs=%d outside the kernel's range (q_tiles=%d)", S, tau, bs, q_tiles);
-  DFL_REQUIRE(tau == 0 || (xc && ldc > 0 && ldc % 8 == 0 && ck_col >= 0 && cv_col >= 0 && ck_col % 8 == 0 && cv_col % 8 == 0),
+  DFL_REQUIRE(L.S >= 0 && L.tau >= 0 && L.tau <= 32 && L.bs >= 1 && L.bs <= 16 * L.q_tiles && L.tau + L.bs <= 64,
+              "dfl_attn_head: lengths S=%d tau=%d bs=%d outside the kernel's range (q_tiles=%d)", L.S, L.tau, L.bs, L.q_tiles);
+  DFL_REQUIRE(L.tau == 0 || (L.xc && L.ldc > 0 && L.ldc % 8 == 0 && L.ck_col >= 0 && L.cv_col >= 0 && L.ck_col % 8 == 0 &&
+                             L.cv_col % 8 == 0),
               "dfl_attn_head: context rows without a context source");
-  DFL_REQUIRE(S + (k_out ? 0 : tau + bs) <= cache_rows, "dfl_attn_head: S + tau + bs = %d exceeds cache_rows = %d", S + tau + bs,
-              cache_rows);
-  DFL_REQUIRE(max_splits >= 1 && out_tile_stride >= 0 && out_tile_stride % 8 == 0, "dfl_attn_head: bad max_splits / out_tile_stride");
-  DFL_REQUIRE(n_cand >= 1 && n_cand <= 64, "dfl_attn_head: n_cand outside 1..64");
-  DFL_REQUIRE(n_cand == 1 || (xq_cand_stride % 8 == 0 && out_cand_stride % 8 == 0 && cache_cand_stride % 8 == 0 &&
-                              ((k_out && v_out) || cache_cand_stride >= (int64_t)n_kv * cache_rows * 128)),
+  DFL_REQUIRE(L.S + (L.k_out ? 0 : L.tau + L.bs) <= L.cache_rows, "dfl_attn_head: S + tau + bs = %d exceeds cache_rows = %d",
+              L.S + L.tau + L.bs, L.cache_rows);
+  DFL_REQUIRE(L.max_splits >= 1 && L.out_tile_stride >= 0 && L.out_tile_stride % 8 == 0,
+              "dfl_attn_head: bad max_splits / out_tile_stride");
+  DFL_REQUIRE(L.n_cand >= 1 && L.n_cand <= 64, "dfl_attn_head: n_cand outside 1..64");
+  DFL_REQUIRE(L.n_cand == 1 || (L.xq_cand_stride % 8 == 0 && L.out_cand_stride % 8 == 0 && L.cache_cand_stride % 8 == 0 &&
+                              ((L.k_out && L.v_out) || L.cache_cand_stride >= (int64_t)L.n_kv * L.cache_rows * 128)),
               "dfl_attn_head: several blocks per launch need 8-element strides and either a K/V staging area "
               "(candidates on one cache) or a cache per request");
-  DFL_REQUIRE(!k_out == !v_out && (!k_out || (out_rows >= tau + bs && kv_out_cand_stride >= (int64_t)n_kv * out_rows * 128)),
+  DFL_REQUIRE(!L.k_out == !L.v_out &&
+                  (!L.k_out || (L.out_rows >= L.tau + L.bs && L.kv_out_cand_stride >= (int64_t)L.n_kv * L.out_rows * 128)),
               "dfl_attn_head: bad K/V staging area");
   // Old-key splits: a workgroup's 8 waves take one 32-key tile each per round, so up to 8 tiles
   // per split cost one round; beyond ~224 workgroups per launch the splits grow instead
   // (S here is the bound the caller sized the launch for when the lengths come from dyn).
-  const int G = n_q / n_kv;
-  const int nt = (S + 31) / 32;
-  const int tiles = tail ? DFL_ATTN_OPROJ_TILES : DFL_ATTN_HEAD_TILES;
-  const int wgs = n_cand > 1 ? HEAD_WGS_MULTI : DFL_ATTN_HEAD_WGS;
+  const int G = L.n_q / L.n_kv;
+  const int nt = (L.S + 31) / 32;
+  const int tiles = L.tail ? DFL_ATTN_OPROJ_TILES : DFL_ATTN_HEAD_TILES;
+  const int wgs = L.n_cand > 1 ? HEAD_WGS_MULTI : DFL_ATTN_HEAD_WGS;
   int ns_old = (nt + tiles - 1) / tiles;
-  int budget = (tail ? DFL_ATTN_OPROJ_WGS : wgs) / (n_q * n_cand) - 1;
+  int budget = (L.tail ? DFL_ATTN_OPROJ_WGS : wgs) / (L.n_q * L.n_cand) - 1;
   budget = budget < 1 ? 1 : budget;
   ns_old = ns_old > budget ? budget : ns_old;
   // Head pairs (k_attn_head_pair): when the splits the budget allows would leave a wave more than one tile, two heads
@@ -1008,67 +1043,67 @@ int attn_head_launch(const void *xq, int64_t ldq, int q_col, int k_col, int v_co
   // old-key split per head from two requests on, i.e. ~4 tiles per wave at S = 1k — pairs on whenever the budget
   // leaves a wave more than one tile (round 3, same box: 4 requests 6.03 -> 5.81 ms per cycle, 3 requests 5.97 -> 5.69;
   // 2 requests 5.22 -> 5.29: from three blocks on).
-  const bool pair = !tail && q_tiles == 1 && G % 2 == 0 && bs <= 16 && nt > tiles * ns_old && (nt > 160 || n_cand > 2);
+  const bool pair = !L.tail && L.q_tiles == 1 && G % 2 == 0 && L.bs <= 16 && nt > tiles * ns_old && (nt > 160 || L.n_cand > 2);
   if (pair) {
-    int budget2 = wgs / ((n_q / 2) * n_cand) - 1;
+    int budget2 = wgs / ((L.n_q / 2) * L.n_cand) - 1;
     budget2 = budget2 < 1 ? 1 : budget2;
     ns_old = (nt + tiles - 1) / tiles;
     ns_old = ns_old > budget2 ? budget2 : ns_old;
   }
-  ns_old = ns_old > max_splits - 1 ? max_splits - 1 : ns_old;
-  if (nt == 0 && !dyn) ns_old = 0;
+  ns_old = ns_old > L.max_splits - 1 ? L.max_splits - 1 : ns_old;
+  if (nt == 0 && !L.dyn) ns_old = 0;
   HeadAttnArgs a{};
-  a.xq = (const bf16_t *)xq;
-  a.ldq = ldq;
-  a.q_col = q_col;
-  a.k_col = k_col;
-  a.v_col = v_col;
-  a.xc = (const bf16_t *)xc;
-  a.ldc = ldc;
-  a.ck_col = ck_col;
-  a.cv_col = cv_col;
-  a.q_w = (const bf16_t *)q_norm_w;
-  a.k_w = (const bf16_t *)k_norm_w;
-  a.eps = eps;
-  a.cos_tab = (const bf16_t *)cos_tab;
-  a.sin_tab = (const bf16_t *)sin_tab;
-  a.max_pos = max_pos;
-  a.kc = (bf16_t *)kcache;
-  a.vc = (bf16_t *)vcache;
-  a.cache_rows = cache_rows;
-  a.n_q = n_q;
-  a.n_kv = n_kv;
+  a.xq = (const bf16_t *)L.xq;
+  a.ldq = L.ldq;
+  a.q_col = L.q_col;
+  a.k_col = L.k_col;
+  a.v_col = L.v_col;
+  a.xc = (const bf16_t *)L.xc;
+  a.ldc = L.ldc;
+  a.ck_col = L.ck_col;
+  a.cv_col = L.cv_col;
+  a.q_w = (const bf16_t *)L.q_norm_w;
+  a.k_w = (const bf16_t *)L.k_norm_w;
+  a.eps = L.eps;
+  a.cos_tab = (const bf16_t *)L.cos_tab;
+  a.sin_tab = (const bf16_t *)L.sin_tab;
+  a.max_pos = L.max_pos;
+  a.kc = (bf16_t *)L.kcache;
+  a.vc = (bf16_t *)L.vcache;
+  a.cache_rows = L.cache_rows;
+  a.n_q = L.n_q;
+  a.n_kv = L.n_kv;
   a.G = G;
-  a.scale_log2 = scale * 1.4426950408889634f;
-  a.causal = causal ? 1 : 0;
-  a.dyn = dyn;
-  a.S = S;
-  a.tau = tau;
-  a.bs = bs;
-  a.pos0 = pos0;
-  a.out_frag = (bf16x8 *)out_frag;
-  a.out_tile_stride = out_tile_stride / 8;
-  const int64_t rows = (int64_t)max_splits * n_q * q_tiles * 16;
-  a.o_part = (float *)ws;
-  a.ml_part = (float *)ws + rows * 128;
-  a.tickets = (int *)((float *)ws + rows * 130);
+  a.scale_log2 = L.scale * 1.4426950408889634f;
+  a.causal = L.causal ? 1 : 0;
+  a.dyn = L.dyn;
+  a.S = L.S;
+  a.tau = L.tau;
+  a.bs = L.bs;
+  a.pos0 = L.pos0;
+  a.out_frag = (bf16x8 *)L.out_frag;
+  a.out_tile_stride = L.out_tile_stride / 8;
+  const int64_t rows = (int64_t)L.max_splits * L.n_q * L.q_tiles * 16;
+  a.o_part = (float *)L.ws;
+  a.ml_part = (float *)L.ws + rows * 128;
+  a.tickets = (int *)((float *)L.ws + rows * 130);
   a.ns_old = ns_old;
-  a.xq_cand_stride = xq_cand_stride;
-  a.out_cand_stride = out_cand_stride / 8;
-  a.ws_cand_stride = dfl_attn_head_ws_bytes(n_q, max_splits, q_tiles) / 4;
-  a.k_out = (bf16_t *)k_out;
-  a.v_out = (bf16_t *)v_out;
-  a.kv_out_cand_stride = kv_out_cand_stride;
-  a.out_rows = out_rows;
-  a.dyn_cand_stride = dyn_cand_stride;
-  a.cache_cand_stride = cache_cand_stride;
-  const dim3 grid(n_kv, (pair ? G / 2 : G) * (ns_old + 1), n_cand);
-  hipStream_t st = (hipStream_t)stream;
-  if (nparts32 > 0) {
+  a.xq_cand_stride = L.xq_cand_stride;
+  a.out_cand_stride = L.out_cand_stride / 8;
+  a.ws_cand_stride = dfl_attn_head_ws_bytes(L.n_q, L.max_splits, L.q_tiles) / 4;
+  a.k_out = (bf16_t *)L.k_out;
+  a.v_out = (bf16_t *)L.v_out;
+  a.kv_out_cand_stride = L.kv_out_cand_stride;
+  a.out_rows = L.out_rows;
+  a.dyn_cand_stride = L.dyn_cand_stride;
+  a.cache_cand_stride = L.cache_cand_stride;
+  const dim3 grid(L.n_kv, (pair ? G / 2 : G) * (ns_old + 1), L.n_cand);
+  hipStream_t st = (hipStream_t)L.stream;
+  if (L.nparts32 > 0) {
     a.xq = nullptr;
-    a.xq32 = (const float *)xq;
-    a.nparts32 = nparts32;
-    a.part_stride32 = part_stride32;
+    a.xq32 = (const float *)L.xq;
+    a.nparts32 = L.nparts32;
+    a.part_stride32 = L.part_stride32;
     if (pair)
       hipLaunchKernelGGL(k_attn_head_pair32, grid, dim3(512), 0, st, a);
     else
@@ -1081,25 +1116,25 @@ int attn_head_launch(const void *xq, int64_t ldq, int q_col, int k_col, int v_co
     DFL_CHECK_LAUNCH("dfl_attn_head");
     return DFL_OK;
   }
-  if (tail) {
+  if (L.tail) {
     AttnOArgs p{};
     p.at = a;
-    p.n_attn = n_kv * G * (ns_old + 1);
-    p.wo = (const bf16x8 *)tail->wo;
-    p.KS = tail->q_dim / 32;
-    p.ntiles = tail->H / 16;
-    p.h_io = (bf16_t *)tail->h_io;
-    p.ldh = tail->ldh;
-    p.ss_out = tail->ss_out;
-    p.done = tail->sync;
-    p.o_done = tail->sync + 1024;
-    p.fail = tail->sync + 1025;
-    p.done_target = n_q;
+    p.n_attn = L.n_kv * G * (ns_old + 1);
+    p.wo = (const bf16x8 *)L.tail->wo;
+    p.KS = L.tail->q_dim / 32;
+    p.ntiles = L.tail->H / 16;
+    p.h_io = (bf16_t *)L.tail->h_io;
+    p.ldh = L.tail->ldh;
+    p.ss_out = L.tail->ss_out;
+    p.done = L.tail->sync;
+    p.o_done = L.tail->sync + 1024;
+    p.fail = L.tail->sync + 1025;
+    p.done_target = L.n_q;
     hipLaunchKernelGGL(k_attn_oproj, dim3(p.n_attn + p.ntiles), dim3(256), 0, st, p);
     DFL_CHECK_LAUNCH("dfl_attn_head_oproj");
     return DFL_OK;
   }
-  if (q_tiles == 1)
+  if (L.q_tiles == 1)
     hipLaunchKernelGGL(k_attn_head<1>, grid, dim3(512), 0, st, a);
   else
     hipLaunchKernelGGL(k_attn_head<2>, grid, dim3(512), 0, st, a);
@@ -1114,9 +1149,15 @@ extern "C" int dfl_attn_head(const void *xq, int64_t ldq, int q_col, int k_col, 
                              void *vcache, int cache_rows, float scale, int causal, const int32_t *dyn, int S, int tau,
                              int bs, int pos0, int q_tiles, void *ws, int max_splits, void *out_frag,
                              int64_t out_tile_stride, void *stream) {
-  return attn_head_launch(xq, ldq, q_col, k_col, v_col, xc, ldc, ck_col, cv_col, n_q, n_kv, q_norm_w, k_norm_w, eps, cos_tab,
-                          sin_tab, max_pos, kcache, vcache, cache_rows, scale, causal, dyn, S, tau, bs, pos0, q_tiles, ws,
-                          max_splits, out_frag, out_tile_stride, 1, 0, 0, nullptr, nullptr, 0, 0, 0, 0, stream);
+  HeadLaunch L;
+  L.xq = xq, L.xc = xc, L.ldc = ldc, L.ck_col = ck_col, L.cv_col = cv_col;
+  L.ldq = ldq, L.q_col = q_col, L.k_col = k_col, L.v_col = v_col;
+  L.n_q = n_q, L.n_kv = n_kv, L.q_norm_w = q_norm_w, L.k_norm_w = k_norm_w, L.eps = eps;
+  L.cos_tab = cos_tab, L.sin_tab = sin_tab, L.max_pos = max_pos;
+  L.kcache = kcache, L.vcache = vcache, L.cache_rows = cache_rows, L.scale = scale, L.causal = causal;
+  L.dyn = dyn, L.S = S, L.tau = tau, L.bs = bs, L.pos0 = pos0, L.q_tiles = q_tiles;
+  L.ws = ws, L.max_splits = max_splits, L.out_frag = out_frag, L.out_tile_stride = out_tile_stride, L.stream = stream;
+  return attn_head_launch(L);
 }
 
 extern "C" int dfl_attn_head_oproj(const void *xq, int64_t ldq, int q_col, int k_col, int v_col, const void *xc, int64_t ldc,
@@ -1130,69 +1171,64 @@ extern "C" int dfl_attn_head_oproj(const void *xq, int64_t ldq, int q_col, int k
               "dfl_attn_head_oproj: H=%d q_dim=%d tau=%d bs=%d outside the kernel's range (q_dim <= 4096, tau + bs <= 32)", H,
               n_q * 128, tau, bs);
   const OprojTail tail{wo_packed, n_q * 128, H, h_io, ldh, ss_out, sync};
-  return attn_head_launch(xq, ldq, q_col, k_col, v_col, xc, ldc, ck_col, cv_col, n_q, n_kv, q_norm_w, k_norm_w, eps, cos_tab,
-                          sin_tab, max_pos, kcache, vcache, cache_rows, scale, causal, dyn, S, tau, bs, pos0, 1, ws, max_splits,
-                          attn_frag, 0, 1, 0, 0, nullptr, nullptr, 0, 0, 0, 0, stream, &tail);
+  HeadLaunch L;
+  L.xq = xq, L.xc = xc, L.ldc = ldc, L.ck_col = ck_col, L.cv_col = cv_col;
+  L.ldq = ldq, L.q_col = q_col, L.k_col = k_col, L.v_col = v_col;
+  L.n_q = n_q, L.n_kv = n_kv, L.q_norm_w = q_norm_w, L.k_norm_w = k_norm_w, L.eps = eps;
+  L.cos_tab = cos_tab, L.sin_tab = sin_tab, L.max_pos = max_pos;
+  L.kcache = kcache, L.vcache = vcache, L.cache_rows = cache_rows, L.scale = scale, L.causal = causal;
+  L.dyn = dyn, L.S = S, L.tau = tau, L.bs = bs, L.pos0 = pos0;
+  L.ws = ws, L.max_splits = max_splits, L.out_frag = attn_frag, L.tail = &tail, L.stream = stream;
+  return attn_head_launch(L);
 }
 
+// Candidate c = q_tiles consecutive 16-row tiles of xq / out_frag (blocks of 17..32 rows: two); staging rows 0..bs-1.
+// Causal, no context rows, the lengths are the immediates S and bs.
 extern "C" int dfl_attn_head_cand(const void *xq, int64_t ldq, int q_col, int k_col, int v_col, int n_cand,
                                   int64_t xq_cand_stride, int n_q, int n_kv, const void *q_norm_w, const void *k_norm_w,
                                   float eps, const void *cos_tab, const void *sin_tab, int max_pos, const void *kcache,
                                   const void *vcache, int cache_rows, float scale, int S, int bs, void *ws, int max_splits,
-                                  void *out_frag, int64_t out_cand_stride, void *k_out, void *v_out,
-                                  int64_t kv_out_cand_stride, int out_rows, void *stream) {
+                                  void *out_frag, int64_t out_cand_stride, int64_t out_tile_stride, int q_tiles, void *k_out,
+                                  void *v_out, int64_t kv_out_cand_stride, int out_rows, void *stream) {
   DFL_REQUIRE(n_cand >= 1 && k_out && v_out, "dfl_attn_head_cand: needs the K/V staging area");
-  return attn_head_launch(xq, ldq, q_col, k_col, v_col, nullptr, 0, 0, 0, n_q, n_kv, q_norm_w, k_norm_w, eps, cos_tab, sin_tab,
-                          max_pos, const_cast<void *>(kcache), const_cast<void *>(vcache), cache_rows, scale, 1, nullptr, S, 0,
-                          bs, S, 1, ws, max_splits, out_frag, 0, n_cand, xq_cand_stride, out_cand_stride, k_out, v_out,
-                          kv_out_cand_stride, out_rows, 0, 0, stream);
+  DFL_REQUIRE(q_tiles == 1 || q_tiles == 2, "dfl_attn_head_cand: q_tiles must be 1 or 2");
+  HeadLaunch L;
+  L.xq = xq;
+  L.ldq = ldq, L.q_col = q_col, L.k_col = k_col, L.v_col = v_col;
+  L.n_q = n_q, L.n_kv = n_kv, L.q_norm_w = q_norm_w, L.k_norm_w = k_norm_w, L.eps = eps;
+  L.cos_tab = cos_tab, L.sin_tab = sin_tab, L.max_pos = max_pos;
+  L.kcache = const_cast<void *>(kcache), L.vcache = const_cast<void *>(vcache), L.cache_rows = cache_rows;
+  L.scale = scale, L.causal = 1, L.S = S, L.bs = bs, L.pos0 = S, L.q_tiles = q_tiles;
+  L.ws = ws, L.max_splits = max_splits, L.out_frag = out_frag, L.out_tile_stride = out_tile_stride;
+  L.n_cand = n_cand, L.xq_cand_stride = xq_cand_stride, L.out_cand_stride = out_cand_stride;
+  L.k_out = k_out, L.v_out = v_out, L.kv_out_cand_stride = kv_out_cand_stride, L.out_rows = out_rows, L.stream = stream;
+  return attn_head_launch(L);
 }
 
+// Request r = q_tiles consecutive 16-row tiles of xq / out_frag (strides per request; blocks of 17..32 rows: two), one
+// cache, one length record whose bs counts both tiles.
 extern "C" int dfl_attn_head_batch(const void *xq, int64_t ldq, int q_col, int k_col, int v_col, int R, int64_t xq_req_stride,
                                    int n_q, int n_kv, const void *q_norm_w, const void *k_norm_w, float eps,
                                    const void *cos_tab, const void *sin_tab, int max_pos, void *kcache, void *vcache,
                                    int cache_rows, int64_t cache_req_stride, float scale, int causal, const int32_t *dyn,
                                    int kv_len_max, void *ws, int max_splits, void *out_frag, int64_t out_req_stride,
-                                   void *stream) {
+                                   int64_t out_tile_stride, int q_tiles, void *stream) {
   DFL_REQUIRE(dyn, "dfl_attn_head_batch: the requests' lengths come from dyn (R records)");
-  DFL_REQUIRE(kv_len_max >= 16 && kv_len_max <= cache_rows, "dfl_attn_head_batch: kv_len_max=%d outside 16..cache_rows", kv_len_max);
-  // lengths from the device records (block form: tau = 0, bs <= 16); kv_len_max - 16 bounds every request's S
-  return attn_head_launch(xq, ldq, q_col, k_col, v_col, nullptr, 0, 0, 0, n_q, n_kv, q_norm_w, k_norm_w, eps, cos_tab, sin_tab,
-                          max_pos, kcache, vcache, cache_rows, scale, causal, dyn, kv_len_max - 16, 0, 16, 0, 1, ws, max_splits,
-                          out_frag, 0, R, xq_req_stride, out_req_stride, nullptr, nullptr, 0, 0, DFL_DYN_WORDS, cache_req_stride,
-                          stream);
-}
-
-// Blocks of 17..32 rows in the ragged batch: request r = TWO consecutive 16-row tiles of xq / out_frag (strides per
-// request), one cache, one length record (bs = 17..32 counts both tiles).
-extern "C" int dfl_attn_head_batch_t(const void *xq, int64_t ldq, int q_col, int k_col, int v_col, int R, int64_t xq_req_stride,
-                                     int n_q, int n_kv, const void *q_norm_w, const void *k_norm_w, float eps,
-                                     const void *cos_tab, const void *sin_tab, int max_pos, void *kcache, void *vcache,
-                                     int cache_rows, int64_t cache_req_stride, float scale, int causal, const int32_t *dyn,
-                                     int kv_len_max, void *ws, int max_splits, void *out_frag, int64_t out_req_stride,
-                                     int64_t out_tile_stride, int q_tiles, void *stream) {
-  DFL_REQUIRE(dyn, "dfl_attn_head_batch_t: the requests' lengths come from dyn (R records)");
-  DFL_REQUIRE(q_tiles == 1 || q_tiles == 2, "dfl_attn_head_batch_t: q_tiles must be 1 or 2");
-  DFL_REQUIRE(kv_len_max >= 16 * q_tiles && kv_len_max <= cache_rows, "dfl_attn_head_batch_t: kv_len_max=%d outside range", kv_len_max);
-  return attn_head_launch(xq, ldq, q_col, k_col, v_col, nullptr, 0, 0, 0, n_q, n_kv, q_norm_w, k_norm_w, eps, cos_tab, sin_tab,
-                          max_pos, kcache, vcache, cache_rows, scale, causal, dyn, kv_len_max - 16 * q_tiles, 0, 16 * q_tiles, 0,
-                          q_tiles, ws, max_splits, out_frag, out_tile_stride, R, xq_req_stride, out_req_stride, nullptr, nullptr, 0,
-                          0, DFL_DYN_WORDS, cache_req_stride, stream);
-}
-
-// Candidate blocks of 17..32 rows: candidate c = TWO consecutive 16-row tiles of xq / out_frag; staging rows 0..bs-1.
-extern "C" int dfl_attn_head_cand_t(const void *xq, int64_t ldq, int q_col, int k_col, int v_col, int n_cand,
-                                    int64_t xq_cand_stride, int n_q, int n_kv, const void *q_norm_w, const void *k_norm_w,
-                                    float eps, const void *cos_tab, const void *sin_tab, int max_pos, const void *kcache,
-                                    const void *vcache, int cache_rows, float scale, int S, int bs, void *ws, int max_splits,
-                                    void *out_frag, int64_t out_cand_stride, int64_t out_tile_stride, int q_tiles, void *k_out,
-                                    void *v_out, int64_t kv_out_cand_stride, int out_rows, void *stream) {
-  DFL_REQUIRE(n_cand >= 1 && k_out && v_out, "dfl_attn_head_cand_t: needs the K/V staging area");
-  DFL_REQUIRE(q_tiles == 1 || q_tiles == 2, "dfl_attn_head_cand_t: q_tiles must be 1 or 2");
-  return attn_head_launch(xq, ldq, q_col, k_col, v_col, nullptr, 0, 0, 0, n_q, n_kv, q_norm_w, k_norm_w, eps, cos_tab, sin_tab,
-                          max_pos, const_cast<void *>(kcache), const_cast<void *>(vcache), cache_rows, scale, 1, nullptr, S, 0,
-                          bs, S, q_tiles, ws, max_splits, out_frag, out_tile_stride, n_cand, xq_cand_stride, out_cand_stride, k_out,
-                          v_out, kv_out_cand_stride, out_rows, 0, 0, stream);
+  DFL_REQUIRE(q_tiles == 1 || q_tiles == 2, "dfl_attn_head_batch: q_tiles must be 1 or 2");
+  DFL_REQUIRE(kv_len_max >= 16 * q_tiles && kv_len_max <= cache_rows,
+              "dfl_attn_head_batch: kv_len_max=%d outside %d..cache_rows", kv_len_max, 16 * q_tiles);
+  // lengths from the device records (block form: tau = 0, bs <= 16 * q_tiles); kv_len_max - 16 * q_tiles bounds every S
+  HeadLaunch L;
+  L.xq = xq;
+  L.ldq = ldq, L.q_col = q_col, L.k_col = k_col, L.v_col = v_col;
+  L.n_q = n_q, L.n_kv = n_kv, L.q_norm_w = q_norm_w, L.k_norm_w = k_norm_w, L.eps = eps;
+  L.cos_tab = cos_tab, L.sin_tab = sin_tab, L.max_pos = max_pos;
+  L.kcache = kcache, L.vcache = vcache, L.cache_rows = cache_rows, L.scale = scale, L.causal = causal;
+  L.dyn = dyn, L.S = kv_len_max - 16 * q_tiles, L.bs = 16 * q_tiles, L.q_tiles = q_tiles;
+  L.ws = ws, L.max_splits = max_splits, L.out_frag = out_frag, L.out_tile_stride = out_tile_stride;
+  L.n_cand = R, L.xq_cand_stride = xq_req_stride, L.out_cand_stride = out_req_stride;
+  L.dyn_cand_stride = DFL_DYN_WORDS, L.cache_cand_stride = cache_req_stride, L.stream = stream;
+  return attn_head_launch(L);
 }
 
 // dfl_attn_head_batch on the fp32 K-PART SUMS of the qkv projection (dfl_gemm_f32_batch's output: [part][R tiles x 16
@@ -1209,8 +1245,15 @@ extern "C" int dfl_attn_head_batch_f32(const float *xq_parts, int nparts, int64_
   DFL_REQUIRE(nparts == 1 || nparts == 2, "dfl_attn_head_batch_f32: 1 or 2 K parts (got %d)", nparts);
   DFL_REQUIRE(kv_len_max >= 16 && kv_len_max <= cache_rows, "dfl_attn_head_batch_f32: kv_len_max=%d outside 16..cache_rows",
               kv_len_max);
-  return attn_head_launch(xq_parts, ldq, q_col, k_col, v_col, nullptr, 0, 0, 0, n_q, n_kv, q_norm_w, k_norm_w, eps, cos_tab,
-                          sin_tab, max_pos, kcache, vcache, cache_rows, scale, causal, dyn, kv_len_max - 16, 0, 16, 0, 1, ws,
-                          max_splits, out_frag, 0, R, xq_req_stride, out_req_stride, nullptr, nullptr, 0, 0, DFL_DYN_WORDS,
-                          cache_req_stride, stream, nullptr, nparts, part_stride);
+  HeadLaunch L;
+  L.xq = xq_parts, L.nparts32 = nparts, L.part_stride32 = part_stride;
+  L.ldq = ldq, L.q_col = q_col, L.k_col = k_col, L.v_col = v_col;
+  L.n_q = n_q, L.n_kv = n_kv, L.q_norm_w = q_norm_w, L.k_norm_w = k_norm_w, L.eps = eps;
+  L.cos_tab = cos_tab, L.sin_tab = sin_tab, L.max_pos = max_pos;
+  L.kcache = kcache, L.vcache = vcache, L.cache_rows = cache_rows, L.scale = scale, L.causal = causal;
+  L.dyn = dyn, L.S = kv_len_max - 16, L.bs = 16;
+  L.ws = ws, L.max_splits = max_splits, L.out_frag = out_frag;
+  L.n_cand = R, L.xq_cand_stride = xq_req_stride, L.out_cand_stride = out_req_stride;
+  L.dyn_cand_stride = DFL_DYN_WORDS, L.cache_cand_stride = cache_req_stride, L.stream = stream;
+  return attn_head_launch(L);
 }

@@ -669,6 +669,26 @@ extern "C" int dfl_gemm_resid_batch(const void *wp, const dfl_rows_batch *x, int
   return DFL_OK;
 }
 
+namespace {
+// What the ring forms of the lm_head epilogues (argmax, seeded draw) share: the rows, the candidate buffers in ws, the
+// optional logits and the plan over the V / 16 column tiles.  Returns grid.x.
+int fill_ring_rows(GemmRArgs &r, const void *wp, const dfl_rows_batch *x, int V, int K, const int32_t *dyn, int row0,
+                   int nrows, int nrows_dyn_word, void *ws, void *logits, int64_t logits_stride) {
+  fill_ring(r, wp, x, V, K, dyn);
+  r.row0 = row0;
+  r.nrows = nrows;
+  r.nrows_word = nrows_dyn_word;
+  r.best_val = (float *)((char *)ws + WS_TICKETS);
+  r.best_idx = (int *)((char *)ws + WS_TICKETS + WS_CAND * sizeof(float));
+  r.logits = (bf16_t *)logits;
+  r.logits_stride = logits_stride;
+  r.N = V;
+  int gx = 0;
+  ring_plan(r, V / 16, 16, gx);
+  return gx;
+}
+}  // namespace
+
 extern "C" int dfl_gemm_argmax_batch(const void *wp, const dfl_rows_batch *x, int R, int V, int K, int row0, int nrows,
                                      const int32_t *dyn, int nrows_dyn_word, void *ws, int64_t *out_ids,
                                      int64_t out_stride, int out_off, void *logits, int64_t logits_stride,
@@ -680,17 +700,7 @@ extern "C" int dfl_gemm_argmax_batch(const void *wp, const dfl_rows_batch *x, in
   if (wp && ring_ok(x, K) && R >= 1 && R <= 4 && V > 0 && V % 16 == 0 && x->frag_stride % 8 == 0) {
     // ring form: a wave owns a column tile over the whole K, the workgroup walks its tiles in passes of <= 16
     GemmRArgs r{};
-    fill_ring(r, wp, x, V, K, dyn);
-    r.row0 = row0;
-    r.nrows = nrows;
-    r.nrows_word = nrows_dyn_word;
-    r.best_val = (float *)((char *)ws + WS_TICKETS);
-    r.best_idx = (int *)((char *)ws + WS_TICKETS + WS_CAND * sizeof(float));
-    r.logits = (bf16_t *)logits;
-    r.logits_stride = logits_stride;
-    r.N = V;
-    int gx = 0;
-    ring_plan(r, V / 16, 16, gx);
+    const int gx = fill_ring_rows(r, wp, x, V, K, dyn, row0, nrows, nrows_dyn_word, ws, logits, logits_stride);
     const char *who = "dfl_gemm_argmax_batch";
     if (!(R <= 2 ? launch_ring<2, 1, 1, 16, 2, EPI_ARGMAX>(who, r, gx, (hipStream_t)stream)
                  : launch_ring<4, 1, 1, 16, 2, EPI_ARGMAX>(who, r, gx, (hipStream_t)stream)))
@@ -720,39 +730,32 @@ extern "C" int dfl_gemm_argmax_batch(const void *wp, const dfl_rows_batch *x, in
 // The seeded draw of dfl_gemm_sample for R <= 4 request tiles in one pass over the weights: the ring form with the
 // EPI_SAMPLE epilogue (gemm_ring.h), or with EPI_SAMPLE_T where invT comes per request slot from the device array
 // inv_ts.  No slab form: where the ring form does not apply this is an error, not a quiet fall-back.
-namespace {
-
-int sample_batch(const char *who, const void *wp, const dfl_rows_batch *x, int R, int V, int K, int row0, int nrows,
-                 const int32_t *dyn, int nrows_dyn_word, void *ws, int64_t *out_ids, int64_t out_stride, int out_off,
-                 void *logits, int64_t logits_stride, const int64_t *seeds, const float *inv_ts, float inv_t, int rng_stream,
-                 int pos_word, int pos_add, int tiles_per_req, void *stream) {
-  DFL_REQUIRE(row0 >= 0 && nrows >= 0 && row0 + nrows <= 16, "%s: rows [%d,%d) outside the tile", who, row0, row0 + nrows);
+extern "C" int dfl_gemm_sample_batch(const void *wp, const dfl_rows_batch *x, int R, int V, int K, int row0, int nrows,
+                                     const int32_t *dyn, int nrows_dyn_word, void *ws, int64_t *out_ids,
+                                     int64_t out_stride, int out_off, void *logits, int64_t logits_stride,
+                                     const int64_t *seeds, const float *inv_ts, float inv_t, int rng_stream, int pos_word,
+                                     int pos_add, int tiles_per_req, void *stream) {
+  DFL_REQUIRE(wp && x && ws && out_ids && dyn && seeds, "dfl_gemm_sample_batch: null pointer");
+  DFL_REQUIRE(row0 >= 0 && nrows >= 0 && row0 + nrows <= 16, "dfl_gemm_sample_batch: rows [%d,%d) outside the tile", row0,
+              row0 + nrows);
   // (the values of inv_ts are not validated: every bit pattern is defined, !(invT > 0) is the greedy slot)
-  DFL_REQUIRE(inv_ts || (inv_t > 0.f && inv_t <= 1e5f), "%s: inv_t=%g outside (0, 1e5]", who, (double)inv_t);
-  DFL_REQUIRE(rng_stream == (int)DFL_RNG_TARGET || rng_stream == (int)DFL_RNG_DRAFT, "%s: unknown stream %d", who, rng_stream);
+  DFL_REQUIRE(inv_ts || (inv_t > 0.f && inv_t <= 1e5f), "dfl_gemm_sample_batch: inv_t=%g outside (0, 1e5]", (double)inv_t);
+  DFL_REQUIRE(rng_stream == (int)DFL_RNG_TARGET || rng_stream == (int)DFL_RNG_DRAFT,
+              "dfl_gemm_sample_batch: unknown stream %d", rng_stream);
   DFL_REQUIRE(pos_word >= 0 && pos_word < DFL_DYN_WORDS && (tiles_per_req == 1 || tiles_per_req == 2) && R % tiles_per_req == 0,
-              "%s: pos_word=%d / tiles_per_req=%d / R=%d", who, pos_word, tiles_per_req, R);
+              "dfl_gemm_sample_batch: pos_word=%d / tiles_per_req=%d / R=%d", pos_word, tiles_per_req, R);
   DFL_REQUIRE(ring_ok(x, K) && R >= 1 && R <= 4 && V > 0 && V % 16 == 0 && x->frag_stride % 8 == 0,
-              "%s: needs the ring form (R <= 4 fragment sources, V %% 16 == 0, K %% 32 == 0, K >= 256)", who);
+              "dfl_gemm_sample_batch: needs the ring form (R <= 4 fragment sources, V %% 16 == 0, K %% 32 == 0, K >= 256)");
   GemmRArgs r{};
-  fill_ring(r, wp, x, V, K, dyn);
-  r.row0 = row0;
-  r.nrows = nrows;
-  r.nrows_word = nrows_dyn_word;
-  r.best_val = (float *)((char *)ws + WS_TICKETS);
-  r.best_idx = (int *)((char *)ws + WS_TICKETS + WS_CAND * sizeof(float));
-  r.logits = (bf16_t *)logits;
-  r.logits_stride = logits_stride;
-  r.N = V;
+  const int gx = fill_ring_rows(r, wp, x, V, K, dyn, row0, nrows, nrows_dyn_word, ws, logits, logits_stride);
   r.seeds = seeds;
-  r.inv_t = inv_t;
+  r.inv_t = inv_ts ? 0.f : inv_t;
   r.inv_ts = inv_ts;
   r.rng_stream = rng_stream;
   r.pos_word = pos_word;
   r.pos_add = pos_add;
   r.tiles_per_req = tiles_per_req;
-  int gx = 0;
-  ring_plan(r, V / 16, 16, gx);
+  const char *who = "dfl_gemm_sample_batch";
   const hipStream_t st = (hipStream_t)stream;
   const bool ok = inv_ts ? (R <= 2 ? launch_ring<2, 1, 1, 16, 2, EPI_SAMPLE_T>(who, r, gx, st)
                                    : launch_ring<4, 1, 1, 16, 2, EPI_SAMPLE_T>(who, r, gx, st))
@@ -761,32 +764,8 @@ int sample_batch(const char *who, const void *wp, const dfl_rows_batch *x, int R
   if (!ok) return DFL_ELAUNCH;
   hipLaunchKernelGGL(k_argmax_finish_b, dim3(16, R), dim3(64), 0, st, r.best_val, r.best_idx, gx, mt_of(R), row0, nrows, dyn,
                      nrows_dyn_word, out_ids, out_stride, out_off);
-  DFL_CHECK_LAUNCH(who);
+  DFL_CHECK_LAUNCH("dfl_gemm_sample_batch");
   return DFL_OK;
-}
-
-}  // namespace
-
-extern "C" int dfl_gemm_sample_batch(const void *wp, const dfl_rows_batch *x, int R, int V, int K, int row0, int nrows,
-                                     const int32_t *dyn, int nrows_dyn_word, void *ws, int64_t *out_ids,
-                                     int64_t out_stride, int out_off, void *logits, int64_t logits_stride,
-                                     const int64_t *seeds, float inv_t, int rng_stream, int pos_word, int pos_add,
-                                     int tiles_per_req, void *stream) {
-  DFL_REQUIRE(wp && x && ws && out_ids && dyn && seeds, "dfl_gemm_sample_batch: null pointer");
-  return sample_batch("dfl_gemm_sample_batch", wp, x, R, V, K, row0, nrows, dyn, nrows_dyn_word, ws, out_ids, out_stride,
-                      out_off, logits, logits_stride, seeds, nullptr, inv_t, rng_stream, pos_word, pos_add, tiles_per_req,
-                      stream);
-}
-
-extern "C" int dfl_gemm_sample_batch_t(const void *wp, const dfl_rows_batch *x, int R, int V, int K, int row0, int nrows,
-                                       const int32_t *dyn, int nrows_dyn_word, void *ws, int64_t *out_ids,
-                                       int64_t out_stride, int out_off, void *logits, int64_t logits_stride,
-                                       const int64_t *seeds, const float *inv_ts, int rng_stream, int pos_word,
-                                       int pos_add, int tiles_per_req, void *stream) {
-  DFL_REQUIRE(wp && x && ws && out_ids && dyn && seeds && inv_ts, "dfl_gemm_sample_batch_t: null pointer");
-  return sample_batch("dfl_gemm_sample_batch_t", wp, x, R, V, K, row0, nrows, dyn, nrows_dyn_word, ws, out_ids, out_stride,
-                      out_off, logits, logits_stride, seeds, inv_ts, 0.f, rng_stream, pos_word, pos_add, tiles_per_req,
-                      stream);
 }
 
 extern "C" int dfl_embed_rows_batch(const void *embed, const int64_t *ids, int64_t ids_stride, int R, void *h_out,

@@ -890,14 +890,7 @@ int gemm_argmax_impl(const void *wp, const dfl_rows *x, int V, int K, int row0, 
 
 extern "C" int dfl_gemm_argmax(const void *wp, const dfl_rows *x, int V, int K, int row0, int nrows,
                                const int32_t *dyn, int nrows_dyn_word, void *ws, int64_t *out_ids, int out_off,
-                               void *logits, float *margin_out, void *stream) {
-  return gemm_argmax_impl(wp, x, V, K, row0, nrows, dyn, nrows_dyn_word, ws, out_ids, out_off, logits, margin_out, nullptr,
-                          nullptr, stream);
-}
-
-extern "C" int dfl_gemm_argmax_timed(const void *wp, const dfl_rows *x, int V, int K, int row0, int nrows,
-                                     const int32_t *dyn, int nrows_dyn_word, void *ws, int64_t *out_ids, int out_off,
-                                     void *logits, float *margin_out, void *ev_start, void *ev_end, void *stream) {
+                               void *logits, float *margin_out, void *ev_start, void *ev_end, void *stream) {
   return gemm_argmax_impl(wp, x, V, K, row0, nrows, dyn, nrows_dyn_word, ws, out_ids, out_off, logits, margin_out,
                           (hipEvent_t)ev_start, (hipEvent_t)ev_end, stream);
 }

@@ -367,26 +367,28 @@ __global__ __launch_bounds__(NUC_NT) void k_sample_rows_nucleus(NucArgs a) {
 
 }  // namespace
 
-namespace {
-
-int nucleus_launch(const char *who, const void *logits, int64_t ld, int64_t tile_stride, int tiles, int V, int row0, int nrows,
-                   const int32_t *dyn, int nrows_dyn_word, int pos_word, int pos_base, const int32_t *positions, int pos_add,
-                   int tiles_per_req, const int64_t *seeds, uint64_t seed, const int32_t *top_k_dev, int top_k,
-                   const float *top_p_dev, float top_p, const float *inv_t_dev, float inv_t, int rng_stream, int extra,
-                   int64_t *out_ids, int64_t out_stride, int out_off, float *thr_out, int32_t *kept_out, void *stream) {
-  DFL_REQUIRE(logits && out_ids, "%s: null pointer", who);
+extern "C" int dfl_sample_rows_nucleus(const void *logits, int64_t ld, int64_t tile_stride, int tiles, int V, int row0,
+                                       int nrows, const int32_t *dyn, int nrows_dyn_word, int pos_word, int pos_base,
+                                       const int32_t *positions, int pos_add, int tiles_per_req, const int64_t *seeds,
+                                       uint64_t seed, const int32_t *top_k_dev, int top_k, const float *top_p_dev,
+                                       float top_p, const float *inv_t_dev, float inv_t, int rng_stream, int extra,
+                                       int64_t *out_ids, int64_t out_stride, int out_off, float *thr_out,
+                                       int32_t *kept_out, void *stream) {
+  DFL_REQUIRE(logits && out_ids, "dfl_sample_rows_nucleus: null pointer");
   DFL_REQUIRE(tiles >= 0 && V > 0 && V <= NUC_VMAX && ld >= V && (tiles <= 1 || tile_stride >= 16 * ld),
-              "%s: bad shape tiles=%d V=%d (at most %d) ld=%lld tile_stride=%lld", who, tiles, V, NUC_VMAX, (long long)ld,
-              (long long)tile_stride);
-  DFL_REQUIRE(row0 >= 0 && nrows >= 0 && row0 + nrows <= 16, "%s: rows [%d,%d) outside the tile", who, row0, row0 + nrows);
+              "dfl_sample_rows_nucleus: bad shape tiles=%d V=%d (at most %d) ld=%lld tile_stride=%lld", tiles, V, NUC_VMAX,
+              (long long)ld, (long long)tile_stride);
+  DFL_REQUIRE(row0 >= 0 && nrows >= 0 && row0 + nrows <= 16, "dfl_sample_rows_nucleus: rows [%d,%d) outside the tile", row0,
+              row0 + nrows);
   DFL_REQUIRE(nrows_dyn_word < DFL_DYN_WORDS && pos_word < DFL_DYN_WORDS && ((nrows_dyn_word < 0 && pos_word < 0) || dyn),
-              "%s: nrows_dyn_word=%d / pos_word=%d need a record inside dyn", who, nrows_dyn_word, pos_word);
-  DFL_REQUIRE(tiles_per_req == 1 || tiles_per_req == 2, "%s: tiles_per_req=%d", who, tiles_per_req);
-  DFL_REQUIRE(top_k_dev || top_k >= 0, "%s: top_k=%d is negative", who, top_k);
-  DFL_REQUIRE(top_p_dev || (top_p > 0.f && top_p <= 1.f), "%s: top_p=%g outside (0, 1]", who, (double)top_p);
+              "dfl_sample_rows_nucleus: nrows_dyn_word=%d / pos_word=%d need a record inside dyn", nrows_dyn_word, pos_word);
+  DFL_REQUIRE(tiles_per_req == 1 || tiles_per_req == 2, "dfl_sample_rows_nucleus: tiles_per_req=%d", tiles_per_req);
+  DFL_REQUIRE(top_k_dev || top_k >= 0, "dfl_sample_rows_nucleus: top_k=%d is negative", top_k);
+  DFL_REQUIRE(top_p_dev || (top_p > 0.f && top_p <= 1.f), "dfl_sample_rows_nucleus: top_p=%g outside (0, 1]", (double)top_p);
   // (device values are not validated: !(invT > 0) is the greedy slot)
-  DFL_REQUIRE(inv_t_dev || (inv_t > 0.f && inv_t <= 1e5f), "%s: inv_t=%g outside (0, 1e5]", who, (double)inv_t);
-  DFL_REQUIRE(rng_stream == (int)DFL_RNG_TARGET || rng_stream == (int)DFL_RNG_DRAFT, "%s: unknown stream %d", who, rng_stream);
+  DFL_REQUIRE(inv_t_dev || (inv_t > 0.f && inv_t <= 1e5f), "dfl_sample_rows_nucleus: inv_t=%g outside (0, 1e5]", (double)inv_t);
+  DFL_REQUIRE(rng_stream == (int)DFL_RNG_TARGET || rng_stream == (int)DFL_RNG_DRAFT,
+              "dfl_sample_rows_nucleus: unknown stream %d", rng_stream);
   if (tiles == 0 || (nrows == 0 && nrows_dyn_word < 0)) return DFL_OK;
   NucArgs a{(const bf16_t *)logits, ld,    tile_stride, V,         row0,  nrows, dyn,       nrows_dyn_word, pos_word,
             pos_base,               positions, pos_add, tiles_per_req, seeds, seed,  top_k_dev, top_k,          top_p_dev,
@@ -394,31 +396,6 @@ int nucleus_launch(const char *who, const void *logits, int64_t ld, int64_t tile
             inv_t_dev};
   hipLaunchKernelGGL(k_sample_rows_nucleus, dim3(nrows_dyn_word >= 0 ? 16 - row0 : nrows, tiles), dim3(NUC_NT), 0,
                      (hipStream_t)stream, a);
-  DFL_CHECK_LAUNCH(who);
+  DFL_CHECK_LAUNCH("dfl_sample_rows_nucleus");
   return DFL_OK;
-}
-
-}  // namespace
-
-extern "C" int dfl_sample_rows_nucleus(const void *logits, int64_t ld, int64_t tile_stride, int tiles, int V, int row0,
-                                       int nrows, const int32_t *dyn, int nrows_dyn_word, int pos_word, int pos_base,
-                                       const int32_t *positions, int pos_add, int tiles_per_req, const int64_t *seeds,
-                                       uint64_t seed, const int32_t *top_k_dev, int top_k, const float *top_p_dev,
-                                       float top_p, float inv_t, int rng_stream, int extra, int64_t *out_ids,
-                                       int64_t out_stride, int out_off, float *thr_out, int32_t *kept_out, void *stream) {
-  return nucleus_launch("dfl_sample_rows_nucleus", logits, ld, tile_stride, tiles, V, row0, nrows, dyn, nrows_dyn_word, pos_word,
-                        pos_base, positions, pos_add, tiles_per_req, seeds, seed, top_k_dev, top_k, top_p_dev, top_p, nullptr,
-                        inv_t, rng_stream, extra, out_ids, out_stride, out_off, thr_out, kept_out, stream);
-}
-
-extern "C" int dfl_sample_rows_nucleus_t(const void *logits, int64_t ld, int64_t tile_stride, int tiles, int V, int row0,
-                                         int nrows, const int32_t *dyn, int nrows_dyn_word, int pos_word, int pos_base,
-                                         const int32_t *positions, int pos_add, int tiles_per_req, const int64_t *seeds,
-                                         uint64_t seed, const int32_t *top_k_dev, int top_k, const float *top_p_dev,
-                                         float top_p, const float *inv_t_dev, float inv_t, int rng_stream, int extra,
-                                         int64_t *out_ids, int64_t out_stride, int out_off, float *thr_out,
-                                         int32_t *kept_out, void *stream) {
-  return nucleus_launch("dfl_sample_rows_nucleus_t", logits, ld, tile_stride, tiles, V, row0, nrows, dyn, nrows_dyn_word,
-                        pos_word, pos_base, positions, pos_add, tiles_per_req, seeds, seed, top_k_dev, top_k, top_p_dev, top_p,
-                        inv_t_dev, inv_t, rng_stream, extra, out_ids, out_stride, out_off, thr_out, kept_out, stream);
 }

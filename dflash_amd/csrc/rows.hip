@@ -351,7 +351,7 @@ extern "C" int dfl_qknorm_rope_append(const float *qkv, int nsplit, int64_t spli
 }
 
 /* see include/dflash_hip.h */
-static int kv_append_batch_impl(const float *kv, int nsplit, int64_t split_stride, int ld, int k_col, int v_col,
+extern "C" int dfl_kv_append_batch(const float *kv, int nsplit, int64_t split_stride, int ld, int k_col, int v_col,
                                    int col_layer_stride, int n_layers, int R, int req_rows, int n_kv,
                                    const void *k_norm_w, int64_t kw_layer_stride, float eps, const void *cos_tab,
                                    const void *sin_tab, int max_pos, void *kcache, void *vcache, int cache_rows,
@@ -369,26 +369,4 @@ static int kv_append_batch_impl(const float *kv, int nsplit, int64_t split_strid
   hipLaunchKernelGGL(k_qknorm_rope, dim3((items + 3) / 4, R, n_layers), dim3(256), 0, (hipStream_t)stream, a);
   DFL_CHECK_LAUNCH("dfl_kv_append_batch");
   return DFL_OK;
-}
-
-extern "C" int dfl_kv_append_batch(const float *kv, int nsplit, int64_t split_stride, int ld, int k_col, int v_col,
-                                   int col_layer_stride, int n_layers, int R, int req_rows, int n_kv,
-                                   const void *k_norm_w, int64_t kw_layer_stride, float eps, const void *cos_tab,
-                                   const void *sin_tab, int max_pos, void *kcache, void *vcache, int cache_rows,
-                                   int64_t cache_req_stride, int64_t cache_layer_stride, const int32_t *dyn,
-                                   void *stream) {
-  return kv_append_batch_impl(kv, nsplit, split_stride, ld, k_col, v_col, col_layer_stride, n_layers, R, req_rows, n_kv, k_norm_w,
-                              kw_layer_stride, eps, cos_tab, sin_tab, max_pos, kcache, vcache, cache_rows, cache_req_stride,
-                              cache_layer_stride, dyn, 1, stream);
-}
-
-extern "C" int dfl_kv_append_batch_t(const float *kv, int nsplit, int64_t split_stride, int ld, int k_col, int v_col,
-                                     int col_layer_stride, int n_layers, int n_tiles, int req_rows, int n_kv,
-                                     const void *k_norm_w, int64_t kw_layer_stride, float eps, const void *cos_tab,
-                                     const void *sin_tab, int max_pos, void *kcache, void *vcache, int cache_rows,
-                                     int64_t cache_req_stride, int64_t cache_layer_stride, const int32_t *dyn_tiles,
-                                     int tiles_per_req, void *stream) {
-  return kv_append_batch_impl(kv, nsplit, split_stride, ld, k_col, v_col, col_layer_stride, n_layers, n_tiles, req_rows, n_kv,
-                              k_norm_w, kw_layer_stride, eps, cos_tab, sin_tab, max_pos, kcache, vcache, cache_rows,
-                              cache_req_stride, cache_layer_stride, dyn_tiles, tiles_per_req, stream);
 }

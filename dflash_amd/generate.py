@@ -354,7 +354,7 @@ class DecodeSession:
         t_call = time.perf_counter() if self.host_times is not None else 0.0
         start = self.start
         blk = self.block[:, :bs]
-        if not self._armed:   # model/dflash.py:235; afterwards dfl_accept_commit_rearm leaves the same ids in self.block
+        if not self._armed:   # model/dflash.py:235; afterwards dfl_accept_commit (re-arming) leaves the same ids in self.block
             blk.copy_(self.output_ids[:, start:start + bs])
         if bs > 1:
             ahead = draft_steps == 1 and self._ahead == bs
@@ -544,7 +544,7 @@ class DecodeSession:
     def capture(self, bs: int) -> None:
         """Capture the steady-state cycle of block size bs (2..16) into two hipGraphs: [target verify + accept] and
         [draft forward + lm_head of the NEXT cycle].  Every length the launches need is in the device records the
-        accept kernel keeps (dfl_accept_commit_rearm_t: the draft cache's record and the target cache's block-form
+        accept kernel keeps (dfl_accept_commit with dyn_t: the draft cache's record and the target cache's block-form
         record), so one capture serves every cycle; the attention launches size their key splits for the caches'
         capacity.  Call after at least one cycle(bs, ahead_ok=True).  The host then spends two graph launches and one poll
         per cycle instead of ~215 ctypes calls.  Raises GraphNotCovered for a session or a state

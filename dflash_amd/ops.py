@@ -172,18 +172,15 @@ def gemm_argmax(wp, x, V: int, K: int, row0: int, nrows: int, ws, out_ids: torch
                 margins: Optional[torch.Tensor] = None, events=None) -> None:
     """margins: optional fp32 tensor indexed like out_ids: top-1 minus top-2 logit per row.
     events: (start, end) torch.cuda.Event pair (enable_timing, already recorded once so that their handles exist),
-    recorded right around the GEMM launch itself (dfl_gemm_argmax_timed)."""
+    recorded right around the GEMM launch itself."""
     if logits is not None:
         assert logits.numel() >= 16 * V
     if margins is not None:
         assert margins.numel() >= out_off + nrows
-    args = (_p(wp, BF16, "wp"), _src(x).ref, V, K, row0, nrows, _p(dyn, I32, "dyn"), nrows_dyn_word, _p(ws),
-            _p(out_ids, I64, "out_ids"), out_off, _p(logits, BF16, "logits"), _p(margins, F32, "margins"))
-    if events is not None:
-        check(lib().dfl_gemm_argmax_timed(*args, events[0].cuda_event, events[1].cuda_event, _stream()),
-              "dfl_gemm_argmax_timed")
-        return
-    check(lib().dfl_gemm_argmax(*args, _stream()), "dfl_gemm_argmax")
+    ev_start, ev_end = (None, None) if events is None else (events[0].cuda_event, events[1].cuda_event)
+    check(lib().dfl_gemm_argmax(_p(wp, BF16, "wp"), _src(x).ref, V, K, row0, nrows, _p(dyn, I32, "dyn"), nrows_dyn_word,
+                                _p(ws), _p(out_ids, I64, "out_ids"), out_off, _p(logits, BF16, "logits"),
+                                _p(margins, F32, "margins"), ev_start, ev_end, _stream()), "dfl_gemm_argmax")
 
 
 RNG_TARGET, RNG_DRAFT = 0, 1   # noise streams of the seeded sampler (csrc/dfl_rng.h)
@@ -249,8 +246,8 @@ def sample_rows_nucleus(logits: torch.Tensor, *, temperature: Optional[float] = 
                         inv_t: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The seeded draw under top-k / top-p (dfl_sample_rows_nucleus) over materialised bf16 logits
     [rows <= 16, V] (one tile) or [tiles, 16, V], unit inner stride.
-    inv_t: a device fp32 tensor of invT per request slot (dfl_sample_rows_nucleus_t; `temperature` is then unused, pass
-    None): a slot whose value is not > 0 is greedy, its rows of out / thresholds / kept are not written.
+    inv_t: a device fp32 tensor of invT per request slot (`temperature` is then unused, pass None): a slot whose value is
+    not > 0 is greedy, its rows of out / thresholds / kept are not written.
     seed / top_k / top_p: a host value, or a device tensor (int64 / int32 / fp32) indexed by request slot
     q = tile // tiles_per_req.  Tile t row m draws position positions[16 t + m] (int32 tensor), or
     (dyn[t][pos_word] if pos_word >= 0 else pos_base) + pos_add + 16 (t % tiles_per_req) + m.  Rows of a tile:
@@ -302,19 +299,12 @@ def sample_rows_nucleus(logits: torch.Tensor, *, temperature: Optional[float] = 
         raise ValueError("sample_rows_nucleus: give either temperature or inv_t")
     if inv_t is not None:
         assert inv_t.numel() >= slots, "inv_t"
-        check(lib().dfl_sample_rows_nucleus_t(logits.data_ptr(), ld, tile_stride, tiles, V, row0, nrows, _p(dyn, I32, "dyn"),
-                                              nrows_dyn_word, pos_word, pos_base, _p(positions, I32, "positions"), pos_add,
-                                              tiles_per_req, seeds_p, seed_v, k_p, k_v, p_p, p_v, _p(inv_t, F32, "inv_t"),
-                                              0.0, stream, extra, _p(out, I64, "out"), out_stride, out_off,
-                                              _p(thresholds, F32, "thresholds"), _p(kept, I32, "kept"), _stream()),
-              "dfl_sample_rows_nucleus_t")
-        return out
     check(lib().dfl_sample_rows_nucleus(logits.data_ptr(), ld, tile_stride, tiles, V, row0, nrows, _p(dyn, I32, "dyn"),
                                         nrows_dyn_word, pos_word, pos_base, _p(positions, I32, "positions"), pos_add,
-                                        tiles_per_req, seeds_p, seed_v, k_p, k_v, p_p, p_v,
-                                        inv_temperature(temperature), stream, extra, _p(out, I64, "out"), out_stride,
-                                        out_off, _p(thresholds, F32, "thresholds"), _p(kept, I32, "kept"), _stream()),
-          "dfl_sample_rows_nucleus")
+                                        tiles_per_req, seeds_p, seed_v, k_p, k_v, p_p, p_v, _p(inv_t, F32, "inv_t"),
+                                        0.0 if inv_t is not None else inv_temperature(temperature), stream, extra,
+                                        _p(out, I64, "out"), out_stride, out_off, _p(thresholds, F32, "thresholds"),
+                                        _p(kept, I32, "kept"), _stream()), "dfl_sample_rows_nucleus")
     return out
 
 
@@ -457,23 +447,15 @@ def attn_head_cand(*, xq: torch.Tensor, q_col: int, k_col: int, v_col: int, n_q:
     assert k_out.shape == v_out.shape and k_out.dim() == 4 and k_out.shape[3] == 128 and k_out.is_contiguous()
     assert v_out.is_contiguous() and k_out.shape[0] * q_tiles >= xq.shape[0] and k_out.shape[1] == n_kv
     assert kcache.shape == vcache.shape and kcache.dim() == 3 and kcache.shape[2] == 128
-    if q_tiles != 1:
-        assert xq.shape[0] % q_tiles == 0 and k_out.shape[2] >= bs
-        check(lib().dfl_attn_head_cand_t(
-            xq.data_ptr(), xq.stride(1), q_col, k_col, v_col, xq.shape[0] // q_tiles, q_tiles * xq.stride(0), n_q, n_kv,
-            _p(q_norm_w, BF16, "q_norm_w"), _p(k_norm_w, BF16, "k_norm_w"), eps, _p(cos_tab, BF16, "cos"),
-            _p(sin_tab, BF16, "sin"), cos_tab.shape[0], _p(kcache, BF16, "kcache"), _p(vcache, BF16, "vcache"),
-            kcache.shape[1], scale, S, bs, _p(ws), max_splits, _p(out_frag, BF16, "out_frag"), q_tiles * out_frag.stride(0),
-            out_frag.stride(0), q_tiles, _p(k_out, BF16, "k_out"), _p(v_out, BF16, "v_out"), k_out.stride(0), k_out.shape[2],
-            _stream()), "dfl_attn_head_cand_t")
-        return
+    assert q_tiles == 1 or (xq.shape[0] % q_tiles == 0 and k_out.shape[2] >= bs)
+    # one tile per candidate: no tile stride (the kernel's arguments are those of the single-tile form)
     check(lib().dfl_attn_head_cand(
-        xq.data_ptr(), xq.stride(1), q_col, k_col, v_col, xq.shape[0], xq.stride(0), n_q, n_kv,
+        xq.data_ptr(), xq.stride(1), q_col, k_col, v_col, xq.shape[0] // q_tiles, q_tiles * xq.stride(0), n_q, n_kv,
         _p(q_norm_w, BF16, "q_norm_w"), _p(k_norm_w, BF16, "k_norm_w"), eps, _p(cos_tab, BF16, "cos"),
         _p(sin_tab, BF16, "sin"), cos_tab.shape[0], _p(kcache, BF16, "kcache"), _p(vcache, BF16, "vcache"),
-        kcache.shape[1], scale, S, bs, _p(ws), max_splits, _p(out_frag, BF16, "out_frag"), out_frag.stride(0),
-        _p(k_out, BF16, "k_out"), _p(v_out, BF16, "v_out"), k_out.stride(0), k_out.shape[2], _stream()),
-        "dfl_attn_head_cand")
+        kcache.shape[1], scale, S, bs, _p(ws), max_splits, _p(out_frag, BF16, "out_frag"), q_tiles * out_frag.stride(0),
+        out_frag.stride(0) if q_tiles != 1 else 0, q_tiles, _p(k_out, BF16, "k_out"), _p(v_out, BF16, "v_out"),
+        k_out.stride(0), k_out.shape[2], _stream()), "dfl_attn_head_cand")
 
 
 def attn_head_batch_ws(R: int, n_q: int, max_splits: int, device, q_tiles: int = 1) -> torch.Tensor:
@@ -490,20 +472,12 @@ def attn_head_batch(*, xq: torch.Tensor, q_col: int, k_col: int, v_col: int, R: 
     assert kcache.shape == vcache.shape and kcache.dim() == 5 and kcache.shape[4] == 128 and kcache.is_contiguous()
     assert out_frag.dim() == 2 and out_frag.is_contiguous()
     kc, vc = kcache[0, layer], vcache[0, layer]
-    if q_tiles != 1:
-        check(lib().dfl_attn_head_batch_t(
-            xq.data_ptr(), xq.stride(1), q_col, k_col, v_col, R, q_tiles * xq.stride(0), n_q, n_kv,
-            _p(q_norm_w, BF16, "q_norm_w"), _p(k_norm_w, BF16, "k_norm_w"), eps, _p(cos_tab, BF16, "cos"),
-            _p(sin_tab, BF16, "sin"), cos_tab.shape[0], kc.data_ptr(), vc.data_ptr(), kcache.shape[3], kcache.stride(0), scale,
-            int(causal), _p(dyn, I32, "dyn"), kv_len_max, _p(ws), max_splits, _p(out_frag, BF16, "out_frag"),
-            q_tiles * out_frag.stride(0), out_frag.stride(0), q_tiles, _stream()), "dfl_attn_head_batch_t")
-        return
     check(lib().dfl_attn_head_batch(
-        xq.data_ptr(), xq.stride(1), q_col, k_col, v_col, R, xq.stride(0), n_q, n_kv, _p(q_norm_w, BF16, "q_norm_w"),
-        _p(k_norm_w, BF16, "k_norm_w"), eps, _p(cos_tab, BF16, "cos"), _p(sin_tab, BF16, "sin"), cos_tab.shape[0],
-        kc.data_ptr(), vc.data_ptr(), kcache.shape[3], kcache.stride(0), scale, int(causal), _p(dyn, I32, "dyn"),
-        kv_len_max, _p(ws), max_splits, _p(out_frag, BF16, "out_frag"), out_frag.stride(0), _stream()),
-        "dfl_attn_head_batch")
+        xq.data_ptr(), xq.stride(1), q_col, k_col, v_col, R, q_tiles * xq.stride(0), n_q, n_kv,
+        _p(q_norm_w, BF16, "q_norm_w"), _p(k_norm_w, BF16, "k_norm_w"), eps, _p(cos_tab, BF16, "cos"),
+        _p(sin_tab, BF16, "sin"), cos_tab.shape[0], kc.data_ptr(), vc.data_ptr(), kcache.shape[3], kcache.stride(0), scale,
+        int(causal), _p(dyn, I32, "dyn"), kv_len_max, _p(ws), max_splits, _p(out_frag, BF16, "out_frag"),
+        q_tiles * out_frag.stride(0), out_frag.stride(0) if q_tiles != 1 else 0, q_tiles, _stream()), "dfl_attn_head_batch")
 
 
 def attn_head_batch_f32(*, qkv_parts: torch.Tensor, nparts: int, MT: int, ld: int, q_col: int, k_col: int, v_col: int, R: int,
@@ -623,7 +597,8 @@ def argmax(logits: torch.Tensor) -> torch.Tensor:
 def accept_commit(block_ids, posterior, bs: int, output_ids, dyn, stop_ids=None, result=None, rearm=None, dyn_t=None) -> None:
     """result: int32[4] on the GPU, or PINNED host memory (the kernel stores the four words with one 16-byte store, a
     CPU thread may poll them).  rearm = (next_block int64 tensor, n, mask_id): the next cycle's block is written by
-    the kernel (dfl_accept_commit_rearm)."""
+    the kernel; dyn_t: the next verify's block-form record is kept on the device too (graph replay).  dyn_t without
+    rearm is an error (the library refuses it): the record is kept by the re-arming launch only."""
     n_stop = 0 if stop_ids is None else stop_ids.numel()
     rp = None
     if result is not None:
@@ -634,19 +609,12 @@ def accept_commit(block_ids, posterior, bs: int, output_ids, dyn, stop_ids=None,
             if not result.is_pinned():
                 raise RuntimeError("dflash_amd: a host-side result buffer must be pinned memory")
             rp = result.data_ptr()
-    common = (_p(block_ids, I64, "block_ids"), _p(posterior, I64, "posterior"), bs, _p(output_ids, I64, "output_ids"),
-              output_ids.numel(), _p(dyn, I32, "dyn"), _p(stop_ids, I64, "stop_ids") if n_stop else None, n_stop, rp)
-    if rearm is not None:
-        nb, n, mask_id = rearm
-        assert nb.numel() >= n
-        if dyn_t is not None:    # the next verify's block-form record kept on the device too (graph replay)
-            check(lib().dfl_accept_commit_rearm_t(*common, _p(nb, I64, "next_block"), int(n), int(mask_id),
-                                                  _p(dyn_t, I32, "dyn_t"), _stream()), "dfl_accept_commit_rearm_t")
-            return
-        check(lib().dfl_accept_commit_rearm(*common, _p(nb, I64, "next_block"), int(n), int(mask_id), _stream()),
-              "dfl_accept_commit_rearm")
-        return
-    check(lib().dfl_accept_commit(*common, _stream()), "dfl_accept_commit")
+    nb, n, mask_id = (None, 0, 0) if rearm is None else rearm
+    assert nb is None or nb.numel() >= n
+    check(lib().dfl_accept_commit(_p(block_ids, I64, "block_ids"), _p(posterior, I64, "posterior"), bs,
+                                  _p(output_ids, I64, "output_ids"), output_ids.numel(), _p(dyn, I32, "dyn"),
+                                  _p(stop_ids, I64, "stop_ids") if n_stop else None, n_stop, rp, _p(nb, I64, "next_block"),
+                                  int(n), int(mask_id), _p(dyn_t, I32, "dyn_t"), _stream()), "dfl_accept_commit")
 
 
 # ---- ragged batch of requests (include/dflash_hip.h, second half) ---------------------------
@@ -755,8 +723,8 @@ def gemm_sample_batch(wp, x: BatchRowSource, R: int, V: int, K: int, row0: int, 
                       inv_ts: Optional[torch.Tensor] = None) -> None:
     """gemm_argmax_batch with the seeded draw (dfl_gemm_sample_batch): tile t (tile j = t % tiles_per_req of request
     q = t // tiles_per_req) row m draws position dyn[t][pos_word] + pos_add + 16 j + m with seed seeds[q] (int64).
-    Either `temperature` (one host value for the launch) or inv_ts (dfl_gemm_sample_batch_t): a device fp32 tensor of
-    invT per request slot q, a slot whose value is not > 0 taking gemm_argmax_batch's plain argmax."""
+    Either `temperature` (one host value for the launch) or inv_ts: a device fp32 tensor of invT per request slot q, a
+    slot whose value is not > 0 taking gemm_argmax_batch's plain argmax."""
     if (temperature is None) == (inv_ts is None):
         raise ValueError("gemm_sample_batch: give either temperature or inv_ts")
     assert out_ids.dim() == 2 and out_ids.dtype == I64 and out_ids.stride(1) == 1
@@ -768,15 +736,11 @@ def gemm_sample_batch(wp, x: BatchRowSource, R: int, V: int, K: int, row0: int, 
         lp, lst = _p(logits, BF16, "logits"), logits.stride(0)
     if inv_ts is not None:
         assert inv_ts.numel() >= mt // tiles_per_req, "inv_ts"
-        check(lib().dfl_gemm_sample_batch_t(_p(wp, BF16, "wp"), x.ref, R, V, K, row0, nrows, _p(dyn, I32, "dyn"),
-                                            nrows_dyn_word, _p(ws), out_ids.data_ptr(), out_ids.stride(0), out_off, lp, lst,
-                                            _p(seeds, I64, "seeds"), _p(inv_ts, F32, "inv_ts"), stream, pos_word, pos_add,
-                                            tiles_per_req, _stream()), "dfl_gemm_sample_batch_t")
-        return
     check(lib().dfl_gemm_sample_batch(_p(wp, BF16, "wp"), x.ref, R, V, K, row0, nrows, _p(dyn, I32, "dyn"), nrows_dyn_word,
                                       _p(ws), out_ids.data_ptr(), out_ids.stride(0), out_off, lp, lst,
-                                      _p(seeds, I64, "seeds"), inv_temperature(temperature), stream, pos_word, pos_add,
-                                      tiles_per_req, _stream()), "dfl_gemm_sample_batch")
+                                      _p(seeds, I64, "seeds"), _p(inv_ts, F32, "inv_ts"),
+                                      0.0 if inv_ts is not None else inv_temperature(temperature), stream, pos_word,
+                                      pos_add, tiles_per_req, _stream()), "dfl_gemm_sample_batch")
 
 
 def embed_rows_batch(embed, ids: torch.Tensor, R: int, h_out: torch.Tensor, H: int, ss_out: torch.Tensor, dyn,
@@ -822,18 +786,12 @@ def kv_append_batch(*, kv, nsplit, split_stride, ld, k_col, v_col, col_layer_str
     else:
         assert kcache.dim() == 5
         rows, req_stride, layer_stride = kcache.shape[3], kcache.stride(0), kcache.stride(1)
-    if tiles_per_req != 1:    # R counts tiles, dyn holds one record per tile, tiles_per_req tiles share a request's cache
-        check(lib().dfl_kv_append_batch_t(
-            _p(kv, F32, "kv"), nsplit, split_stride, ld, k_col, v_col, col_layer_stride, n_layers, R, 16, n_kv,
-            _p(k_norm_w, BF16, "k_norm_w"), 128, eps, _p(cos_tab, BF16, "cos"), _p(sin_tab, BF16, "sin"),
-            cos_tab.shape[0], _p(kcache, BF16, "kcache"), _p(vcache, BF16, "vcache"), rows,
-            req_stride, layer_stride, _p(dyn, I32, "dyn"), tiles_per_req, _stream()), "dfl_kv_append_batch_t")
-        return
+    # R counts tiles, dyn holds one record per tile, tiles_per_req tiles share a request's cache
     check(lib().dfl_kv_append_batch(
         _p(kv, F32, "kv"), nsplit, split_stride, ld, k_col, v_col, col_layer_stride, n_layers, R, 16, n_kv,
         _p(k_norm_w, BF16, "k_norm_w"), 128, eps, _p(cos_tab, BF16, "cos"), _p(sin_tab, BF16, "sin"),
         cos_tab.shape[0], _p(kcache, BF16, "kcache"), _p(vcache, BF16, "vcache"), rows,
-        req_stride, layer_stride, _p(dyn, I32, "dyn"), _stream()), "dfl_kv_append_batch")
+        req_stride, layer_stride, _p(dyn, I32, "dyn"), tiles_per_req, _stream()), "dfl_kv_append_batch")
 
 
 def attn_fused_batch_ws(R: int, n_q: int, n_kv: int, max_splits: int, device) -> torch.Tensor:
@@ -861,7 +819,8 @@ def accept_commit_batch(block: torch.Tensor, posterior: torch.Tensor, R: int, ou
                         dyn_d_tiles=None, dyn_t_tiles=None, next_block: Optional[torch.Tensor] = None,
                         output_len: Optional[int] = None) -> None:
     """block/posterior int64 [requests, 16 * tiles_per_req]; output_ids int64 [requests, n]; result int32 [requests, 4];
-    tiles_per_req = 2: the per-tile records dyn_d_tiles / dyn_t_tiles are kept as well (dfl_accept_commit_batch_t).
+    tiles_per_req = 2: the per-tile records dyn_d_tiles / dyn_t_tiles are kept as well (with one tile per request they are not
+    handed over: they may be the per-request records themselves).
     rearm_mask_id: the next block is re-armed, in `block` itself or in next_block (same row stride as block).
     output_len: ids per request the kernel may write (default: the whole row of output_ids)."""
     assert block.dim() == 2 and posterior.dim() == 2 and output_ids.dim() == 2
@@ -876,21 +835,14 @@ def accept_commit_batch(block: torch.Tensor, posterior: torch.Tensor, R: int, ou
             nb = _p(next_block, I64, "next_block")
     else:
         assert next_block is None, "next_block needs rearm_mask_id"
-    if tiles_per_req != 1:
-        check(lib().dfl_accept_commit_batch_t(
-            _p(block, I64, "block"), block.stride(0), _p(posterior, I64, "posterior"), posterior.stride(0), R,
-            _p(output_ids, I64, "output_ids"), output_ids.stride(0), out_len, _p(dyn_d, I32, "dyn_d"),
-            _p(dyn_t, I32, "dyn_t"), _p(stop_ids, I64, "stop_ids") if n_stop else None, n_stop,
-            _p(result, I32, "result"), nb,
-            int(rearm_mask_id) if rearm_mask_id is not None else 0, tiles_per_req, _p(dyn_d_tiles, I32, "dyn_d_tiles"),
-            _p(dyn_t_tiles, I32, "dyn_t_tiles"), _stream()), "dfl_accept_commit_batch_t")
-        return
+    tiled = tiles_per_req != 1
     check(lib().dfl_accept_commit_batch(
         _p(block, I64, "block"), block.stride(0), _p(posterior, I64, "posterior"), posterior.stride(0), R,
         _p(output_ids, I64, "output_ids"), output_ids.stride(0), out_len, _p(dyn_d, I32, "dyn_d"),
         _p(dyn_t, I32, "dyn_t"), _p(stop_ids, I64, "stop_ids") if n_stop else None, n_stop,
-        _p(result, I32, "result"), nb,
-        int(rearm_mask_id) if rearm_mask_id is not None else 0, _stream()), "dfl_accept_commit_batch")
+        _p(result, I32, "result"), nb, int(rearm_mask_id) if rearm_mask_id is not None else 0, tiles_per_req,
+        _p(dyn_d_tiles, I32, "dyn_d_tiles") if tiled else None, _p(dyn_t_tiles, I32, "dyn_t_tiles") if tiled else None,
+        _stream()), "dfl_accept_commit_batch")
 
 
 def admit_slot(r: int, prompt_ids: torch.Tensor, first_token: torch.Tensor, output_ids: torch.Tensor, block: torch.Tensor,

@@ -605,7 +605,7 @@ class NativeTarget:
         weights through the ragged-batch GEMMs (`_verify_wide`; an MoE layer's expert MLP per tile), or one launch per
         tile of every single-request GEMM (wide_one_pass = False); both query tiles share the attention launch.
         dyn_lengths (bs <= 16, attention stage "head"): the launches take S / pos0 from the cache's device record alone
-        (kept by dfl_accept_commit_rearm_t) — `start` is then only an upper bound that sizes the attention's key splits
+        (kept by dfl_accept_commit, dyn_t) — `start` is then only an upper bound that sizes the attention's key splits
         and the RoPE table, and the sequence can be captured into a hipGraph (DecodeSession.capture).
         seed (temperature > 0): the seeded Gumbel-max draw in the lm_head epilogue instead of softmax + multinomial —
         row j draws position start + j + 1, start from the record's POS0 word under dyn_lengths (DESIGN.md section 8);

@@ -31,6 +31,10 @@
  *    cache length before this cycle, context rows, block rows, absolute position
  *    of the first context row.  Kernels read lengths from it so that one captured
  *    graph serves every cycle.
+ *
+ * One entry point per operation: dfl_gemm_argmax, dfl_sample_rows_nucleus, dfl_attn_head_cand, dfl_attn_head_batch,
+ * dfl_accept_commit, dfl_gemm_sample_batch, dfl_kv_append_batch and dfl_accept_commit_batch each took over the arguments
+ * of their former `_t` / `_timed` / `_rearm` twins (optional ones are nullable or have a neutral value, said at each).
  */
 #ifndef DFLASH_HIP_H
 #define DFLASH_HIP_H
@@ -132,16 +136,13 @@ int dfl_gemm_silu_mul(const void *wp_gateup, const dfl_rows *x, int I, int K, vo
  * margin_out (optional, fp32, same indexing as out_ids): top-1 minus top-2 bf16 logit of the
  * row, the reference's confidence statistic (benchmark_candidate_solutions.py:296-302,
  * torch.topk(2) values: an exact tie gives 0) — the per-position confidence comes with the
- * unmask at no extra pass over the logits. */
+ * unmask at no extra pass over the logits.
+ * ev_start / ev_end (each optional): hipEvent_t recorded on `stream` right before and right after the GEMM launch (the
+ * argmax finish launch comes behind ev_end): bench.py times the lm_head kernel itself with them (roofline.achieved). */
 int64_t dfl_argmax_ws_bytes(void);
 int dfl_gemm_argmax(const void *wp, const dfl_rows *x, int V, int K, int row0, int nrows, const int32_t *dyn,
                     int nrows_dyn_word, void *ws, int64_t *out_ids, int out_off, void *logits, float *margin_out,
-                    void *stream);
-/* The same, with two hipEvent_t recorded on `stream` right before and right after the GEMM launch (the argmax finish
- * launch comes behind ev_end): bench.py times the lm_head kernel itself with them (roofline.achieved). */
-int dfl_gemm_argmax_timed(const void *wp, const dfl_rows *x, int V, int K, int row0, int nrows, const int32_t *dyn,
-                          int nrows_dyn_word, void *ws, int64_t *out_ids, int out_off, void *logits, float *margin_out,
-                          void *ev_start, void *ev_end, void *stream);
+                    void *ev_start, void *ev_end, void *stream);
 
 /* Seeded sampling at temperature T fused into the same lm_head GEMM (Gumbel-max):
  *   ids[r] = argmax_n fmaf(bf16(x[r] . W[n]), inv_t, g(seed, rng_stream, p_r, n, extra)), first index on ties,
@@ -266,36 +267,34 @@ int dfl_attn_head_oproj(const void *xq, int64_t ldq, int q_col, int k_col, int v
 /* ---- multi-candidate verify (benchmark_candidate_solutions.py) ----
  * Several drafts of ONE block are verified against ONE cached prefix and the best is kept (:570-618).
  *
- * dfl_attn_head_cand: dfl_attn_head (causal, no context rows, q_tiles = 1) for n_cand candidate blocks in one launch
+ * dfl_attn_head_cand: dfl_attn_head (causal, no context rows) for n_cand candidate blocks in one launch
  * (grid.z = candidate): candidate c's block rows at xq + c * xq_cand_stride elements, its frag16 output at out_frag +
  * c * out_cand_stride elements; every candidate attends the same cached rows [0, S) plus ITS OWN bs new rows, which go
  * not to the cache but to the staging area k_out / v_out [c][n_kv][out_rows][128] (rows 0..bs-1) — the reference clones
  * and batch-repeats the whole DynamicCache instead (:76-81, :572-575) and selects the winner's copy (:604-608); here the
- * caller copies the winner's bs rows into the cache.  ws: n_cand * dfl_attn_head_ws_bytes(n_q, max_splits, 1), zeroed. */
+ * caller copies the winner's bs rows into the cache.  q_tiles = 2 (candidate blocks of 17..32 rows): candidate c = two
+ * consecutive 16-row tiles of xq and of out_frag, out_tile_stride elements apart (q_tiles = 1: pass 0).
+ * ws: n_cand * dfl_attn_head_ws_bytes(n_q, max_splits, q_tiles) bytes, zeroed. */
 int dfl_attn_head_cand(const void *xq, int64_t ldq, int q_col, int k_col, int v_col, int n_cand, int64_t xq_cand_stride,
                        int n_q, int n_kv, const void *q_norm_w, const void *k_norm_w, float eps, const void *cos_tab,
                        const void *sin_tab, int max_pos, const void *kcache, const void *vcache, int cache_rows,
                        float scale, int S, int bs, void *ws, int max_splits, void *out_frag, int64_t out_cand_stride,
-                       void *k_out, void *v_out, int64_t kv_out_cand_stride, int out_rows, void *stream);
-/* The same for candidate blocks of 17..32 rows (q_tiles = 2): candidate c = two consecutive 16-row tiles of xq and of
- * out_frag (out_tile_stride elements apart); ws: n_cand * dfl_attn_head_ws_bytes(n_q, max_splits, q_tiles) bytes. */
-int dfl_attn_head_cand_t(const void *xq, int64_t ldq, int q_col, int k_col, int v_col, int n_cand, int64_t xq_cand_stride,
-                         int n_q, int n_kv, const void *q_norm_w, const void *k_norm_w, float eps, const void *cos_tab,
-                         const void *sin_tab, int max_pos, const void *kcache, const void *vcache, int cache_rows,
-                         float scale, int S, int bs, void *ws, int max_splits, void *out_frag, int64_t out_cand_stride,
-                         int64_t out_tile_stride, int q_tiles, void *k_out, void *v_out, int64_t kv_out_cand_stride,
-                         int out_rows, void *stream);
+                       int64_t out_tile_stride, int q_tiles, void *k_out, void *v_out, int64_t kv_out_cand_stride,
+                       int out_rows, void *stream);
 
 /* dfl_attn_head for the R requests of a ragged batch in one launch (grid.z = request; replaces dfl_attn_fused_batch):
  * request r's block rows at xq + r * xq_req_stride, its lengths at dyn + r * DFL_DYN_WORDS (block form: the context rows
  * are cached already, dyn tau == 0), its cache at + r * cache_req_stride, its frag16 output at + r * out_req_stride.
- * kv_len_max bounds S + 16 over the requests (it sizes the key splits).  ws: R * dfl_attn_head_ws_bytes(n_q, max_splits,
- * 1) bytes, zeroed once. */
+ * kv_len_max bounds S + 16 * q_tiles over the requests (it sizes the key splits).  q_tiles = 2 (blocks of 17..32 rows;
+ * benchmark.py's block-size sweep, results.md:11-16, with several requests per GPU): request r is TWO consecutive 16-row
+ * tiles of xq and of out_frag (out_tile_stride elements apart; q_tiles = 1: pass 0), one cache and one length record whose
+ * bs counts both tiles.  ws: R * dfl_attn_head_ws_bytes(n_q, max_splits, q_tiles) bytes, zeroed once. */
 int dfl_attn_head_batch(const void *xq, int64_t ldq, int q_col, int k_col, int v_col, int R, int64_t xq_req_stride, int n_q,
                         int n_kv, const void *q_norm_w, const void *k_norm_w, float eps, const void *cos_tab,
                         const void *sin_tab, int max_pos, void *kcache, void *vcache, int cache_rows,
                         int64_t cache_req_stride, float scale, int causal, const int32_t *dyn, int kv_len_max, void *ws,
-                        int max_splits, void *out_frag, int64_t out_req_stride, void *stream);
+                        int max_splits, void *out_frag, int64_t out_req_stride, int64_t out_tile_stride, int q_tiles,
+                        void *stream);
 /* dfl_attn_head_batch on the fp32 K-PART SUMS of the q/k/v projection (dfl_gemm_f32_batch's output) instead of finished
  * bf16 rows (model/dflash.py:70-76: a q/k/v value is the Linear's bf16 output = bf16(part 0 + part 1)): request r's rows of
  * part k at xq_parts + k * part_stride + r * xq_req_stride floats, row stride ldq floats; nparts = dfl_batch_ksplit(hidden)
@@ -307,15 +306,6 @@ int dfl_attn_head_batch_f32(const float *xq_parts, int nparts, int64_t part_stri
                             void *kcache, void *vcache, int cache_rows, int64_t cache_req_stride, float scale, int causal,
                             const int32_t *dyn, int kv_len_max, void *ws, int max_splits, void *out_frag,
                             int64_t out_req_stride, void *stream);
-/* The same for blocks of 17..32 rows (q_tiles = 2; benchmark.py's block-size sweep, results.md:11-16, with several requests
- * per GPU): request r is TWO consecutive 16-row tiles of xq and of out_frag (out_tile_stride elements apart), one cache and
- * one length record whose bs counts both tiles.  ws: R * dfl_attn_head_ws_bytes(n_q, max_splits, q_tiles) bytes. */
-int dfl_attn_head_batch_t(const void *xq, int64_t ldq, int q_col, int k_col, int v_col, int R, int64_t xq_req_stride, int n_q,
-                          int n_kv, const void *q_norm_w, const void *k_norm_w, float eps, const void *cos_tab,
-                          const void *sin_tab, int max_pos, void *kcache, void *vcache, int cache_rows,
-                          int64_t cache_req_stride, float scale, int causal, const int32_t *dyn, int kv_len_max, void *ws,
-                          int max_splits, void *out_frag, int64_t out_req_stride, int64_t out_tile_stride, int q_tiles,
-                          void *stream);
 
 /* Per row of bf16 logits [rows][ld] (rows <= 64): the k <= 8 largest values with their indices, ordered (value
  * descending, index ascending) — out_val fp32 [rows][8], out_idx int32 [rows][8] — and the row's log-sum-exp (fp32).
@@ -399,25 +389,19 @@ int dfl_sample_rows(const void *logits, int64_t ld, int rows, int V, uint64_t se
  * seeds / top_k_dev / top_p_dev: device arrays (int64 / int32 / fp32) indexed by q, or NULL for the host value beside
  * them; a device top_k < 0 or top_p outside (0, 1) reads as "off".  Everything a replayed launch needs is read by
  * address.  out_ids[t * out_stride + out_off + (m - row0)]; thr_out (fp32: the final threshold) and kept_out (int32: the
- * size of the kept set) are optional and indexed like out_ids. */
+ * size of the kept set) are optional and indexed like out_ids.
+ * invT: inv_t_dev is a device fp32 array indexed by q (NULL: the host inv_t, as with top_k_dev / top_k; a non-NULL array
+ * makes the host value unused and unchecked).  The slot's invT feeds both the masses exp(invT (x - max)) and the draw.  A
+ * slot whose value is not > 0 (0, negative, NaN) is GREEDY: its rows return at once and write nothing — out_ids, thr_out
+ * and kept_out keep what they held, the way rows past a tile's valid count do.  In the filtering verify the
+ * dfl_gemm_argmax_batch launch in front has already written that slot's argmax ids (lowest index on ties) where this
+ * launch would write.  Device values are not validated: every bit pattern is defined. */
 int dfl_sample_rows_nucleus(const void *logits, int64_t ld, int64_t tile_stride, int tiles, int V, int row0, int nrows,
                             const int32_t *dyn, int nrows_dyn_word, int pos_word, int pos_base, const int32_t *positions,
                             int pos_add, int tiles_per_req, const int64_t *seeds, uint64_t seed, const int32_t *top_k_dev,
-                            int top_k, const float *top_p_dev, float top_p, float inv_t, int rng_stream, int extra,
-                            int64_t *out_ids, int64_t out_stride, int out_off, float *thr_out, int32_t *kept_out,
-                            void *stream);
-/* dfl_sample_rows_nucleus with invT per request slot: inv_t_dev is a device fp32 array indexed by q (NULL: the host inv_t,
- * as with top_k_dev / top_k; a non-NULL array makes the host value unused and unchecked).  The slot's invT feeds both the
- * masses exp(invT (x - max)) and the draw.  A slot whose value is not > 0 (0, negative, NaN) is GREEDY: its rows return at
- * once and write nothing — out_ids, thr_out and kept_out keep what they held, the way rows past a tile's valid count do.
- * In the filtering verify the dfl_gemm_argmax_batch launch in front has already written that slot's argmax ids (lowest
- * index on ties) where this launch would write.  Device values are not validated: every bit pattern is defined. */
-int dfl_sample_rows_nucleus_t(const void *logits, int64_t ld, int64_t tile_stride, int tiles, int V, int row0, int nrows,
-                              const int32_t *dyn, int nrows_dyn_word, int pos_word, int pos_base, const int32_t *positions,
-                              int pos_add, int tiles_per_req, const int64_t *seeds, uint64_t seed, const int32_t *top_k_dev,
-                              int top_k, const float *top_p_dev, float top_p, const float *inv_t_dev, float inv_t,
-                              int rng_stream, int extra, int64_t *out_ids, int64_t out_stride, int out_off, float *thr_out,
-                              int32_t *kept_out, void *stream);
+                            int top_k, const float *top_p_dev, float top_p, const float *inv_t_dev, float inv_t,
+                            int rng_stream, int extra, int64_t *out_ids, int64_t out_stride, int out_off, float *thr_out,
+                            int32_t *kept_out, void *stream);
 
 /* Acceptance scan + commit + bonus token + stop test + length bookkeeping in one
  * wavefront (model/dflash.py:258-268):
@@ -427,23 +411,17 @@ int dfl_sample_rows_nucleus_t(const void *logits, int64_t ld, int64_t tile_strid
  *        among the acc+2 tokens just written
  * result (int32[4], may be pinned host memory mapped to the device): {acc, new_start, stop, cycle}; words 0..2 are
  * stored first, the cycle counter (>= 1) last behind a system-scope release: a polling host waits for word 3 to change
- * and reads the others afterwards. */
+ * and reads the others afterwards.
+ * next_block != NULL: the next cycle's block is RE-ARMED on the device as well (model/dflash.py:235: block =
+ * output_ids[:, start:start+bs] = the token just committed at the new start followed by mask ids): next_block[0] <-
+ * posterior[acc], next_block[1 .. rearm_n-1] <- mask_id, 1 <= rearm_n <= 64 (next_block may be block_ids itself).  NULL:
+ * no re-arm, rearm_n / mask_id unused.
+ * dyn_t != NULL (needs next_block): the block-form length record of the NEXT target verify is maintained too (S = POS0 =
+ * START = new start, TAU = 0; its BS word is left alone): with it a steady-state cycle needs no host-side length at all —
+ * verify and accept can be replayed from a hipGraph (DecodeSession.capture). */
 int dfl_accept_commit(const int64_t *block_ids, const int64_t *posterior, int bs, int64_t *output_ids,
                       int64_t output_len, int32_t *dyn, const int64_t *stop_ids, int n_stop, int32_t *result,
-                      void *stream);
-
-/* dfl_accept_commit that also RE-ARMS the next cycle's block on the device (model/dflash.py:235: block =
- * output_ids[:, start:start+bs] = the token just committed at the new start followed by mask ids):
- * next_block[0] <- posterior[acc], next_block[1 .. rearm_n-1] <- mask_id (next_block may be block_ids itself). */
-int dfl_accept_commit_rearm(const int64_t *block_ids, const int64_t *posterior, int bs, int64_t *output_ids,
-                            int64_t output_len, int32_t *dyn, const int64_t *stop_ids, int n_stop, int32_t *result,
-                            int64_t *next_block, int rearm_n, int64_t mask_id, void *stream);
-/* The same, and the block-form length record of the NEXT target verify maintained on the device as well (dyn_t:
- * S = POS0 = START = new start, TAU = 0; its BS word is left alone): with it a steady-state cycle needs no host-side length
- * at all — verify and accept can be replayed from a hipGraph (DecodeSession.capture). */
-int dfl_accept_commit_rearm_t(const int64_t *block_ids, const int64_t *posterior, int bs, int64_t *output_ids,
-                              int64_t output_len, int32_t *dyn, const int64_t *stop_ids, int n_stop, int32_t *result,
-                              int64_t *next_block, int rearm_n, int64_t mask_id, int32_t *dyn_t, void *stream);
+                      int64_t *next_block, int rearm_n, int64_t mask_id, int32_t *dyn_t, void *stream);
 
 /* ======================================================================================
  * Target PREFILL on the kernels (model/dflash.py:218-225: target(input_ids, ..., output_hidden_states=True) over the
@@ -578,23 +556,19 @@ int dfl_gemm_argmax_batch(const void *wp, const dfl_rows_batch *x, int R, int V,
  * j = t % tiles_per_req of request q = t / tiles_per_req; its row m draws position dyn[t][pos_word] + pos_add + 16 j + m
  * with seed seeds[q] (int64, one per request slot: a captured batch graph and a re-admitted slot keep working).  dyn
  * holds batch_tiles(R) records, seeds batch_tiles(R) / tiles_per_req entries.  No slab form: -22 where the ring form
- * does not apply. */
-int dfl_gemm_sample_batch(const void *wp, const dfl_rows_batch *x, int R, int V, int K, int row0, int nrows,
-                          const int32_t *dyn, int nrows_dyn_word, void *ws, int64_t *out_ids, int64_t out_stride,
-                          int out_off, void *logits, int64_t logits_stride, const int64_t *seeds, float inv_t,
-                          int rng_stream, int pos_word, int pos_add, int tiles_per_req, void *stream);
-/* dfl_gemm_sample_batch with invT per request slot (EPI_SAMPLE_T epilogue): inv_ts is a device fp32 array of
- * batch_tiles(R) / tiles_per_req entries, indexed by q like seeds, read by address on every launch (a replayed graph sees
- * what an admission wrote).  Per slot:
- *   inv_ts[q] > 0     sampled: argmax_v fmaf(bf16(logit_v), inv_ts[q], noise of dfl_rng.h) — dfl_gemm_sample_batch's draw
- *                     at that slot's own invT (the host writes float32(1 / T));
+ * does not apply.
+ * inv_ts == NULL: every slot draws at the host inv_t (in (0, 1e5]).  inv_ts != NULL (EPI_SAMPLE_T epilogue; inv_t unused):
+ * a device fp32 array of batch_tiles(R) / tiles_per_req entries, indexed by q like seeds, read by address on every launch
+ * (a replayed graph sees what an admission wrote).  Per slot:
+ *   inv_ts[q] > 0     sampled: argmax_v fmaf(bf16(logit_v), inv_ts[q], noise of dfl_rng.h) — the draw at that slot's own
+ *                     invT (the host writes float32(1 / T));
  *   otherwise         (0, negative, NaN) greedy: argmax_v bf16(logit_v), lowest v on ties, no Philox call and no noise —
  *                     bit for bit the ids of dfl_gemm_argmax_batch on the same inputs.
- * Device values are not validated.  -22 on a null pointer (inv_ts included) and wherever dfl_gemm_sample_batch returns it. */
-int dfl_gemm_sample_batch_t(const void *wp, const dfl_rows_batch *x, int R, int V, int K, int row0, int nrows,
-                            const int32_t *dyn, int nrows_dyn_word, void *ws, int64_t *out_ids, int64_t out_stride,
-                            int out_off, void *logits, int64_t logits_stride, const int64_t *seeds, const float *inv_ts,
-                            int rng_stream, int pos_word, int pos_add, int tiles_per_req, void *stream);
+ * Device values are not validated. */
+int dfl_gemm_sample_batch(const void *wp, const dfl_rows_batch *x, int R, int V, int K, int row0, int nrows,
+                          const int32_t *dyn, int nrows_dyn_word, void *ws, int64_t *out_ids, int64_t out_stride,
+                          int out_off, void *logits, int64_t logits_stride, const int64_t *seeds, const float *inv_ts,
+                          float inv_t, int rng_stream, int pos_word, int pos_add, int tiles_per_req, void *stream);
 /* dfl_embed_rows for R requests: ids[r * ids_stride + m]. */
 int dfl_embed_rows_batch(const void *embed, const int64_t *ids, int64_t ids_stride, int R, void *h_out,
                          int64_t h_stride, int H, float *ss_out, int64_t ss_stride, const int32_t *dyn, int dyn_word,
@@ -626,19 +600,14 @@ int dfl_norm_frag_batch(void *h, int64_t h_stride, int64_t ldh, int R, const flo
  * of the n_layers layers (layer i's k columns at k_col + i * col_layer_stride, v alike);
  * k_norm + RoPE (position pos0 + row) -> caches at rows S + row, row < dyn tau.  The block
  * stage that follows then sees them as cached rows (lengths in block form, see
- * dfl_accept_commit_batch). */
+ * dfl_accept_commit_batch).  R counts 16-row TILES with one length record each, tiles_per_req (>= 1) consecutive tiles
+ * sharing one request's cache: 1 for blocks of <= 16 rows; 2 for the context rows of requests that run 17..32-row blocks
+ * (up to 32 accepted rows per cycle). */
 int dfl_kv_append_batch(const float *kv, int nsplit, int64_t split_stride, int ld, int k_col, int v_col,
                         int col_layer_stride, int n_layers, int R, int req_rows, int n_kv, const void *k_norm_w,
                         int64_t kw_layer_stride, float eps, const void *cos_tab, const void *sin_tab, int max_pos,
                         void *kcache, void *vcache, int cache_rows, int64_t cache_req_stride,
-                        int64_t cache_layer_stride, const int32_t *dyn, void *stream);
-/* The same over n_tiles 16-row TILES with one length record each (dyn_tiles), tiles_per_req consecutive tiles sharing one
- * request's cache: the context rows of requests that run 17..32-row blocks (up to 32 accepted rows per cycle). */
-int dfl_kv_append_batch_t(const float *kv, int nsplit, int64_t split_stride, int ld, int k_col, int v_col,
-                          int col_layer_stride, int n_layers, int n_tiles, int req_rows, int n_kv, const void *k_norm_w,
-                          int64_t kw_layer_stride, float eps, const void *cos_tab, const void *sin_tab, int max_pos,
-                          void *kcache, void *vcache, int cache_rows, int64_t cache_req_stride,
-                          int64_t cache_layer_stride, const int32_t *dyn_tiles, int tiles_per_req, void *stream);
+                        int64_t cache_layer_stride, const int32_t *dyn, int tiles_per_req, void *stream);
 
 /* dfl_attn_fused for R requests (grid.z = request): request r's block rows at partial-buffer
  * rows blk_row0 + r * req_rows, cache at + r * cache_req_stride, frag16 output at
@@ -660,22 +629,18 @@ int dfl_attn_fused_batch(const float *qkv, int nsplit, int64_t split_stride, int
  * result int32 [R][4] = {acc, new_start, stop, cycle}.  A request with dyn_d bs == 0 is idle: none of its rows
  * is read and no word of its slot (ids, records, result, block) is written.
  * next_block (optional, may alias block_ids; same stride): re-armed for the next cycle as
- * [bonus token, mask_id x 15] = output_ids[new start .. +16) (model/dflash.py:235). */
+ * [bonus token, mask_id x (16 * tiles_per_req - 1)] = output_ids[new start .. ) (model/dflash.py:235).
+ * Requests of tiles_per_req (1 or 2) 16-row tiles — 2: blocks of up to 32 rows.  With dyn_d_tiles / dyn_t_tiles (both or
+ * neither; required for tiles_per_req = 2; blk_stride >= 16 * tiles_per_req) one record per TILE is kept for the per-tile
+ * launches besides the per-request records (dyn_d_tiles: S / pos0 = start + 16 j, tau = the tile's share of the acc + 1
+ * context rows, start = new start; dyn_t_tiles: block form with bs = the tile's share of the block rows); every other
+ * word of a tile record (dyn_d_tiles bs, stop, cycle, spare) is left as it was.  tiles_per_req = 1 with the per-request
+ * records passed as the tile records too leaves what NULL tile records leave. */
 int dfl_accept_commit_batch(const int64_t *block_ids, int64_t blk_stride, const int64_t *posterior,
                             int64_t post_stride, int R, int64_t *output_ids, int64_t out_stride, int64_t output_len,
                             int32_t *dyn_d, int32_t *dyn_t, const int64_t *stop_ids, int n_stop, int32_t *result,
-                            int64_t *next_block, int64_t mask_id, void *stream);
-/* The same for requests of tiles_per_req (1 or 2) 16-row tiles — blocks of up to 32 rows: besides the per-request records
- * it keeps one record per TILE for the per-tile launches (dyn_d_tiles: S / pos0 = start + 16 j, tau = the tile's share of
- * the acc + 1 context rows, start = new start; dyn_t_tiles: block form with bs = the tile's share of the block rows); every
- * other word of a tile record (dyn_d_tiles bs, stop, cycle, spare) is left as it was.  The re-armed block has
- * 16 * tiles_per_req slots.  tiles_per_req = 1 with the per-request records passed as the tile records too leaves what
- * dfl_accept_commit_batch leaves. */
-int dfl_accept_commit_batch_t(const int64_t *block_ids, int64_t blk_stride, const int64_t *posterior,
-                              int64_t post_stride, int R, int64_t *output_ids, int64_t out_stride, int64_t output_len,
-                              int32_t *dyn_d, int32_t *dyn_t, const int64_t *stop_ids, int n_stop, int32_t *result,
-                              int64_t *next_block, int64_t mask_id, int tiles_per_req, int32_t *dyn_d_tiles,
-                              int32_t *dyn_t_tiles, void *stream);
+                            int64_t *next_block, int64_t mask_id, int tiles_per_req, int32_t *dyn_d_tiles,
+                            int32_t *dyn_t_tiles, void *stream);
 
 /* Slot admission of the ragged batch: ONE launch re-arms request slot r (0 <= r < n_slots) for a request whose prompt
  * has just been prefilled, from device-resident inputs only (nothing is read back, nothing copied from the host):

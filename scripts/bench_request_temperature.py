@@ -1,8 +1,8 @@
 """Cost of the per-request temperature ("Per-request temperature"), one process, arms alternating.
 
-  lm_head   the ring-form lm_head at four request tiles, K = 4096, V = 151936 / 128256: dfl_gemm_sample_batch_t with
+  lm_head   the ring-form lm_head at four request tiles, K = 4096, V = 151936 / 128256: dfl_gemm_sample_batch (inv_ts given) with
             (i) uniform sampled inv_ts, (ii) mixed (sampled, greedy, sampled, greedy), (iii) all greedy, against
-            dfl_gemm_sample_batch and dfl_gemm_argmax_batch; median of 10 blocks of 50 launches (GEMM plus finish kernel),
+            dfl_gemm_sample_batch at one host invT and dfl_gemm_argmax_batch; median of 10 blocks of 50 launches (GEMM plus finish kernel),
             the order of the arms rotating from block to block, and each arm's own spread over its blocks
   cycle     scripts/stream_ab.py's steady four-request cycle on Qwen3-8B shapes, every request at T = 0.7 with
             sampler="device": an engine built with request_temperature=True against one built without it

@@ -35,7 +35,7 @@ def rearm(row, bonus, mask_id, n):
         row[i] = bonus if i == 0 else mask_id
 
 
-# ---- single form (dfl_accept_commit, _rearm, _rearm_t) ---------------------------------------------------------
+# ---- single form (dfl_accept_commit: plain, re-arm, dyn_t) ------------------------------------------------------
 def single_dyn(dyn, start, acc, hit):
     dyn[S], dyn[TAU], dyn[POS0], dyn[START] = start, acc + 1, start, start + acc + 1
     dyn[STOP] |= int(hit)
@@ -90,7 +90,7 @@ def tile_records(dd, dt, j, start, bs, acc):
 
 def batch_cycle(R, block, post, out, out_len, dyn_d, dyn_t, stops, result=None, next_block=None, mask_id=0,
                 tiles_per_req=1, dyn_dt=None, dyn_tt=None):
-    """One dfl_accept_commit_batch (dyn_dt None) or dfl_accept_commit_batch_t launch over requests 0..R-1.  block, post,
+    """One dfl_accept_commit_batch launch (dyn_dt None: no tile records) over requests 0..R-1.  block, post,
     out, next_block: lists of rows; dyn_*: lists of records (dyn_dt / dyn_tt: tiles_per_req per request; they may be
     dyn_d / dyn_t themselves at tiles_per_req = 1, as the batched decoder passes them).  bs = dyn_d[r][BS]; a request
     with bs == 0 is idle: no word of its slot changes.  Returns the accepted lengths (None for idle requests)."""

@@ -44,7 +44,8 @@ def test_batch_entry_points_validate_without_gpu():
     assert h.dfl_batch_ksplit(4096) == 2 and h.dfl_batch_ksplit(12288) == 6 and h.dfl_batch_ksplit(512) == 1
     assert h.dfl_gemm_batch_ws_bytes(4096, 4096) > 2 * 256 * 4 * 1024
     assert h.dfl_gemm_f32_batch(None, None, 2, 16, 32, None, None, None) == -22
-    assert h.dfl_accept_commit_batch(None, 16, None, 16, 1, None, 1, 1, None, None, None, 0, None, None, 0, None) == -22
+    assert h.dfl_accept_commit_batch(None, 16, None, 16, 1, None, 1, 1, None, None, None, 0, None, None, 0, 1, None, None,
+                                     None) == -22
 
 
 def test_argument_validation_needs_no_gpu():
@@ -53,7 +54,58 @@ def test_argument_validation_needs_no_gpu():
     assert h.dfl_pack_weight(None, None, 16, 32, None) == -22
     assert b"null" in h.dfl_last_error()
     assert h.dfl_gemm_f32(1, None, None, 3, 16, 32, 1, 1, None, None) == -22
-    assert h.dfl_accept_commit(1, 1, 0, 1, 4, 1, None, 0, None, None) == -22
+    assert h.dfl_accept_commit(1, 1, 0, 1, 4, 1, None, 0, None, None, 0, 0, None, None) == -22
+
+
+def test_no_entry_point_has_a_twin():
+    """One entry point per operation: no declared name is another declared name plus _t or _timed."""
+    names = set(_declared())
+    twins = sorted(n for n in names for suffix in ("_t", "_timed") if n.endswith(suffix) and n[:-len(suffix)] in names)
+    assert not twins, twins
+
+
+def test_folded_entry_points_keep_the_conditional_checks():
+    """What only the wider form of a folded entry point required is still required, for that form alone: each call is
+    refused with -22 and the entry point's own name in the text.  Small integers stand for pointers: nothing launches."""
+    import ctypes as C
+    from dflash_amd import _lib
+    h = _lib.lib()
+
+    def refused(name, *args):
+        assert getattr(h, name)(*args) == -22, name
+        assert (name + ":").encode() in h.dfl_last_error(), (name, h.dfl_last_error())
+
+    # dyn_t without the re-arm it belongs to
+    refused("dfl_accept_commit", 16, 16, 4, 16, 64, 16, None, 0, None, None, 0, 0, 16, None)
+    assert b"dyn_t" in h.dfl_last_error()
+    # two tiles per request need both tile records; three tiles do not exist
+    batch = (16, 32, 16, 32, 2, 16, 64, 64, 16, 16, None, 0, 16, None, 0)
+    refused("dfl_accept_commit_batch", *batch, 2, None, 16, None)
+    assert b"tile record" in h.dfl_last_error()
+    refused("dfl_accept_commit_batch", *batch, 2, 16, None, None)
+    assert b"tile record" in h.dfl_last_error()
+    refused("dfl_accept_commit_batch", *batch, 3, 16, 16, None)
+    assert b"tiles_per_req=3" in h.dfl_last_error()
+    # q_tiles = 3
+    refused("dfl_attn_head_batch", 16, 1024, 0, 512, 768, 2, 16384, 4, 2, None, None, 1e-6, 16, 16, 4096, 16, 16, 1024,
+            1 << 20, 0.088, 0, 16, 512, 16, 8, 16, 8192, 8192, 3, None)
+    assert b"q_tiles" in h.dfl_last_error()
+    refused("dfl_attn_head_cand", 16, 1024, 0, 512, 768, 2, 16384, 4, 2, None, None, 1e-6, 16, 16, 4096, 16, 16, 1024,
+            0.088, 100, 16, 16, 8, 16, 8192, 8192, 3, 16, 16, 1 << 16, 32, None)
+    assert b"q_tiles" in h.dfl_last_error()
+    # no per-slot 1/T array: the host value is the temperature, and 0 is none
+    x = _lib.RowsBatch()
+    x.r0.frag, x.r0.mode, x.frag_stride = 16, 0, 4096 * 16
+    refused("dfl_gemm_sample_batch", 16, C.byref(x), 2, 64, 256, 0, 16, 16, 2, 16, 16, 16, 0, None, 0, 16, None, 0.0, 0, 3,
+            1, 1, None)
+    assert b"inv_t" in h.dfl_last_error()
+    refused("dfl_sample_rows_nucleus", 16, 64, 1024, 1, 64, 0, 16, None, -1, -1, 0, None, 0, 1, None, 1, None, 0, None,
+            1.0, None, 0.0, 0, 0, 16, 16, 0, None, None, None)
+    assert b"inv_t" in h.dfl_last_error()
+    # tiles that share a cache: at least one
+    refused("dfl_kv_append_batch", 16, 1, 4096, 256, 0, 128, 256, 1, 2, 16, 2, None, 128, 1e-6, 16, 16, 4096, 16, 16,
+            1024, 1 << 20, 1 << 18, 16, 0, None)
+    assert b"batch shape" in h.dfl_last_error()
 
 
 def test_product_has_no_cpu_path():

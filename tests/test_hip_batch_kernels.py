@@ -395,7 +395,7 @@ ATTN_BF16 = [("draft", "bench", 1), ("target", "ragged", 1), ("moe", "r2", 1), (
                               for h, n, t in ATTN_BF16])
 def test_attn_head_batch_against_reference(heads, lens_name, q_tiles):
     """dfl_attn_head_batch on finished bf16 q/k/v rows against the same reference; q_tiles = 2 is the two-tile form
-    (blocks of 17..32 rows, dfl_attn_head_batch_t)."""
+    (blocks of 17..32 rows, q_tiles = 2)."""
     _attn_case("bf16", heads, lens_name, 1, seed=17 * q_tiles + len(lens_name), q_tiles=q_tiles)
 
 
@@ -462,7 +462,7 @@ def test_kv_append_batch_against_oracle(R):
 
 def test_kv_append_batch_shared_cache_and_two_tiles_per_request():
     """The 4-D form (ONE request's cache, consecutive 16-row tiles of its context, each with its own S / pos0: the
-    large-M context prefill) and tiles_per_req = 2 (two tiles per request cache, dfl_kv_append_batch_t)."""
+    large-M context prefill) and tiles_per_req = 2 (two tiles per request cache)."""
     from dflash_amd import ops
     L, n_kv, rows = 5, 8, 300
     # 4-D: 5 tiles of one request, the last one partial

@@ -719,7 +719,7 @@ def test_accept_commit_golden(ops):
 
 
 def test_accept_commit_rearm_and_pinned_result_golden(ops):
-    """The reference's accept cases (G3) through dfl_accept_commit_rearm with the result in PINNED host memory: same
+    """The reference's accept cases (G3) through dfl_accept_commit (re-arming) with the result in PINNED host memory: same
     acceptance, commit and bookkeeping; the block buffer then holds the next cycle's block (the token committed at the
     new start followed by mask ids, model/dflash.py:235) — re-armed in place, wider than the block just accepted."""
     MASK = 151669

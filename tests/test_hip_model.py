@@ -970,7 +970,7 @@ def test_wide_context_prefill_equals_group_prefill(P):
 def test_graph_replayed_cycles_equal_eager_cycles():
     """DecodeSession.capture / cycle_graph: the steady-state cycle replayed from two hipGraphs —
     [verify + accept], [the next cycle's draft + lm_head], every length from the device records the accept kernel keeps
-    (dfl_accept_commit_rearm_t) — commits the same ids with the same acceptance lengths as eager cycles, including an
+    (dfl_accept_commit with dyn_t) — commits the same ids with the same acceptance lengths as eager cycles, including an
     eager cycle in the middle (its accept keeps the target's record too) and the eager tail."""
     from dflash_amd import NativeTarget
     from dflash_amd.generate import DecodeSession

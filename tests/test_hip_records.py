@@ -94,9 +94,9 @@ class Batch:
         hd = ht = None
         if tiled:
             (hd, gd), (ht, gt) = self.tiles("d"), self.tiles("t")
-        if tiled and self.tpr == 1:      # the wrapper sends one tile per request to dfl_accept_commit_batch: call the _t form
+        if tiled and self.tpr == 1:      # the wrapper hands over no tile records for one tile per request: call the library
             L = ops.lib()
-            rc = L.dfl_accept_commit_batch_t(
+            rc = L.dfl_accept_commit_batch(
                 g["block"].data_ptr(), g["block"].stride(0), g["post"].data_ptr(), g["post"].stride(0), R,
                 g["out"].data_ptr(), g["out"].stride(0), self.out_len, g["dyn_d"].data_ptr(), g["dyn_t"].data_ptr(),
                 st.data_ptr() if stops else None, len(stops), g["result"].data_ptr(),
@@ -149,7 +149,7 @@ def test_accept_commit_batch_one_cycle(ops, R, blk_stride, post_stride, rearm):
             b.check(f"R={R} bs={bss} acc={want}")
 
 
-# ---- b. dfl_accept_commit_batch_t ---------------------------------------------------------------------------------
+# ---- b. dfl_accept_commit_batch, tiled -----------------------------------------------------------------------------
 @pytest.mark.parametrize("blk_stride,post_stride,rearm", [(32, 32, "inplace"), (40, 48, "separate")])
 def test_accept_commit_batch_t_two_tiles(ops, blk_stride, post_stride, rearm):
     """Blocks of 17..32 rows, a wide slot running a short tail block (bs 16, 5: tile 1's shares are 0) and an idle slot,
@@ -173,8 +173,8 @@ def test_accept_commit_batch_t_two_tiles(ops, blk_stride, post_stride, rearm):
 
 
 def test_accept_commit_batch_t_one_tile_equals_batch(ops):
-    """tiles_per_req = 1 through the _t entry point with the per-tile pointers being the per-request records, as the
-    batched decoder holds them: exactly what dfl_accept_commit_batch leaves."""
+    """tiles_per_req = 1 with the per-tile pointers being the per-request records, as the batched decoder holds them:
+    exactly what dfl_accept_commit_batch leaves without tile records."""
     for kind in range(4):
         pairs = []
         for tiled in (False, True):
@@ -258,7 +258,7 @@ def test_stop_ids_batch_and_single(ops, which, idx, n_stop, hit):
 
 # ---- e. single form (also used by c) ------------------------------------------------------------------------------
 class Single:
-    """One request through dfl_accept_commit / _rearm / _rearm_t: the records sit inside 24-word sentinel buffers
+    """One request through dfl_accept_commit (plain / re-arm / re-arm with dyn_t): the records sit inside 24-word sentinel buffers
     (dyn at word 8, result at word 4), block / posterior / ids in buffers wider than bs and output_len."""
 
     def __init__(self, bs, acc, start, out_len, base=1000, width=72):

@@ -1,5 +1,5 @@
 """Per-request temperature at the kernel level ("Per-request temperature"): the ring-form lm_head
-with invT read per request slot (dfl_gemm_sample_batch_t) and the filtered draw with the same (dfl_sample_rows_nucleus_t).
+with invT read per request slot (dfl_gemm_sample_batch with inv_ts) and the filtered draw with the same (dfl_sample_rows_nucleus with inv_t_dev).
 A sampled slot draws what dfl_gemm_sample_batch / dfl_sample_rows draw at that slot's own T; a greedy slot (invT not > 0)
 emits the ids of dfl_gemm_argmax_batch, respectively writes nothing."""
 import numpy as np

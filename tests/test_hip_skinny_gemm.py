@@ -400,6 +400,29 @@ def test_gemm_argmax_normed_exact(ops, V):
     assert torch.equal(ids[:15], _first_argmax(ref2[1:].float())) and int(ids[15]) == -7
 
 
+@pytest.mark.gpu
+def test_gemm_argmax_events(ops):
+    """The optional event pair of dfl_gemm_argmax (what bench.py times the lm_head kernel with): one 16-row tile,
+    K = 256, V = 320.  With and without `events=` the ids are the same (and the first maximum of torch's exact logits);
+    both events are recorded on the stream, start before end."""
+    V, K = 320, 256
+    w = _small_ints((V, K), _cuda_gen(3))
+    x = _small_ints((16, K), _cuda_gen(4))
+    wp, src, ws = ops.pack_weight(w), ops.rows_frag(_frag(x)), ops.argmax_ws(dev())
+    start, end = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+    end.record()                      # recorded once so that their handles exist: in the WRONG order, work in between,
+    torch.mm(w.float(), w.float().T)  # so that a launch that left them alone would not pass below
+    start.record()
+    plain = torch.full((16,), -7, dtype=torch.int64, device=dev())
+    timed = torch.full((16,), -7, dtype=torch.int64, device=dev())
+    ops.gemm_argmax(wp, src, V, K, 0, 16, ws, plain)
+    ops.gemm_argmax(wp, src, V, K, 0, 16, ws, timed, events=(start, end))
+    torch.cuda.synchronize()
+    assert torch.equal(plain, timed)
+    assert torch.equal(plain, _first_argmax((x.float() @ w.float().T).to(BF16).float()))
+    assert start.query() and end.query() and start.elapsed_time(end) >= 0
+
+
 # ---------------------------------------------------------------- the normalised source
 @pytest.mark.gpu
 @pytest.mark.parametrize("nss", [1, 128, 256], ids=lambda n: f"nss{n}")

@@ -65,7 +65,7 @@ def test_entry_point_validates_without_a_gpu():
              positions=None, padd=0, tpr=1, seeds=None, seed=1, kdev=None, k=0, pdev=None, p=1.0, inv_t=1.0, stream=0,
              extra=0, out=1, ostride=16, ooff=0, thr=None, kept=None):
         return h.dfl_sample_rows_nucleus(logits, ld, tstride, tiles, V, row0, nrows, dyn, nword, pword, pbase, positions,
-                                         padd, tpr, seeds, seed, kdev, k, pdev, p, inv_t, stream, extra, out, ostride,
+                                         padd, tpr, seeds, seed, kdev, k, pdev, p, None, inv_t, stream, extra, out, ostride,
                                          ooff, thr, kept, None)
 
     assert call(tiles=0) == 0                       # nothing to do: no launch

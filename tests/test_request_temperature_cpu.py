@@ -1,5 +1,5 @@
 """No-GPU parts of the per-request temperature ("Per-request temperature"): argument validation of
-the two _t entry points, the helper that reads a temperature per prompt, and the scheduler handing each request's value
+the two entry points that take 1/T per request slot, the helper that reads a temperature per prompt, and the scheduler handing each request's value
 to the driver's admit."""
 import ctypes
 
@@ -13,16 +13,18 @@ def test_gemm_sample_batch_t_validates_without_a_gpu():
     x.r0.frag, x.r0.mode, x.frag_stride = 16, 0, 4096 * 16   # a fragment source; never dereferenced: validation only
 
     def call(wp=16, xs=x, R=2, V=64, K=256, row0=0, nrows=16, dyn=16, ws=16, out=16, seeds=16, inv_ts=16, stream=0,
-             pos_word=3, tpr=1):
-        return h.dfl_gemm_sample_batch_t(wp, ctypes.byref(xs) if xs is not None else None, R, V, K, row0, nrows, dyn, 2, ws,
-                                         out, 16, 0, None, 0, seeds, inv_ts, stream, pos_word, 1, tpr, None)
+             inv_t=0.0, pos_word=3, tpr=1):
+        return h.dfl_gemm_sample_batch(wp, ctypes.byref(xs) if xs is not None else None, R, V, K, row0, nrows, dyn, 2, ws,
+                                       out, 16, 0, None, 0, seeds, inv_ts, inv_t, stream, pos_word, 1, tpr, None)
 
-    assert h.dfl_gemm_sample_batch_t(None, None, 2, 64, 256, 0, 16, None, 2, None, None, 16, 0, None, 0, None, None, 0, 3, 1,
-                                     1, None) == -22 and b"null" in h.dfl_last_error()
-    for name in ("wp", "xs", "dyn", "ws", "out", "seeds", "inv_ts"):
+    assert h.dfl_gemm_sample_batch(None, None, 2, 64, 256, 0, 16, None, 2, None, None, 16, 0, None, 0, None, None, 0.0, 0, 3,
+                                   1, 1, None) == -22 and b"null" in h.dfl_last_error()
+    for name in ("wp", "xs", "dyn", "ws", "out", "seeds"):
         assert call(**{name: None}) == -22, name
-        assert b"dfl_gemm_sample_batch_t: null" in h.dfl_last_error(), name
-    # the checks dfl_gemm_sample_batch makes, and -22 where the ring form does not apply
+        assert b"dfl_gemm_sample_batch: null" in h.dfl_last_error(), name
+    # no per-slot array: the host inv_t (0 here) is the temperature and is range-checked
+    assert call(inv_ts=None) == -22 and b"dfl_gemm_sample_batch: inv_t" in h.dfl_last_error()
+    # the other checks, and -22 where the ring form does not apply
     assert call(row0=4, nrows=13) == -22 and b"rows" in h.dfl_last_error()
     assert call(stream=2) == -22 and b"stream" in h.dfl_last_error()
     assert call(pos_word=8) == -22 and call(tpr=3) == -22 and call(R=3, tpr=2) == -22
@@ -38,15 +40,15 @@ def test_sample_rows_nucleus_t_validates_without_a_gpu():
     h = _lib.lib()
 
     def call(logits=16, ld=64, tiles=1, V=64, row0=0, nrows=16, tpr=1, k=0, p=1.0, inv_dev=16, inv_t=0.0, stream=0, out=16):
-        return h.dfl_sample_rows_nucleus_t(logits, ld, 1024, tiles, V, row0, nrows, None, -1, -1, 0, None, 0, tpr, None, 1,
-                                           None, k, None, p, inv_dev, inv_t, stream, 0, out, 16, 0, None, None, None)
+        return h.dfl_sample_rows_nucleus(logits, ld, 1024, tiles, V, row0, nrows, None, -1, -1, 0, None, 0, tpr, None, 1,
+                                         None, k, None, p, inv_dev, inv_t, stream, 0, out, 16, 0, None, None, None)
 
     assert call(tiles=0) == 0                                   # nothing to do: no launch; the host inv_t is not read
-    assert call(logits=None) == -22 and b"dfl_sample_rows_nucleus_t: null" in h.dfl_last_error()
+    assert call(logits=None) == -22 and b"dfl_sample_rows_nucleus: null" in h.dfl_last_error()
     assert call(out=None) == -22 and b"null" in h.dfl_last_error()
     assert call(p=0.0) == -22 and b"top_p" in h.dfl_last_error()
     assert call(k=-1) == -22 and call(stream=2) == -22 and call(tpr=3) == -22 and call(row0=4, nrows=13) == -22
-    # without a device array the host value is the temperature, validated as dfl_sample_rows_nucleus validates it
+    # without a device array the host value is the temperature, range-checked
     for it in (0.0, -1.0, 2e5, float("nan")):
         assert call(inv_dev=None, inv_t=it, tiles=0) == -22 and b"inv_t" in h.dfl_last_error(), it
     assert call(inv_dev=None, inv_t=1.0, tiles=0) == 0
