@@ -323,7 +323,8 @@ def _attn_case(form, heads, lens_name, nparts, seed, q_tiles=1):
     qw = (1 + 0.1 * torch.randn(128, generator=g, device=dev())).to(BF16)
     kw = (1 + 0.1 * torch.randn(128, generator=g, device=dev())).to(BF16)
     cos, sin = _rope_tables(128, 1e6, rows + 64, dev())
-    ws = ops.attn_head_batch_ws(QS, n_q, MAX_SPLITS, dev(), q_tiles=q_tiles)
+    ws = (ops.attn_fused_batch_ws(QS, n_q, n_kv, MAX_SPLITS, dev()) if form == "fused"
+          else ops.attn_head_batch_ws(QS, n_q, MAX_SPLITS, dev(), q_tiles=q_tiles))
     runs = ((lens, bss), (tuple(max(0, s - 37 * (i + 1)) for i, s in enumerate(lens))[::-1], bss[::-1]))
     for run, (lens, bss) in enumerate(runs):
         kc0 = torch.randn(QS, L, n_kv, rows, 128, generator=g, device=dev()).to(BF16)
@@ -341,6 +342,8 @@ def _attn_case(form, heads, lens_name, nparts, seed, q_tiles=1):
                       dyn=dyn, kv_len_max=kvmax, ws=ws, max_splits=MAX_SPLITS, out_frag=out)
         if form == "f32":
             ops.attn_head_batch_f32(qkv_parts=parts, nparts=nparts, MT=QS, ld=ld, **common)
+        elif form == "fused":   # per-tile records (one 16-row tile per request here), as batch.py's _attend passes them
+            ops.attn_fused_batch(qkv=parts, nsplit=nparts, split_stride=QS * 16 * ld, ld=ld, **common)
         else:
             ops.attn_head_batch(xq=lin.reshape(QS * q_tiles, 16, ld).contiguous(), q_tiles=q_tiles, **common)
         torch.cuda.synchronize()
@@ -397,6 +400,16 @@ def test_attn_head_batch_against_reference(heads, lens_name, q_tiles):
     """dfl_attn_head_batch on finished bf16 q/k/v rows against the same reference; q_tiles = 2 is the two-tile form
     (blocks of 17..32 rows, q_tiles = 2)."""
     _attn_case("bf16", heads, lens_name, 1, seed=17 * q_tiles + len(lens_name), q_tiles=q_tiles)
+
+
+ATTN_FUSED = [("draft", "bench", 2), ("target", "ragged", 2), ("moe", "r2", 1), ("target", "r3", 2), ("draft", "long", 1)]
+
+
+@pytest.mark.parametrize("heads,lens_name,nparts", ATTN_FUSED, ids=[f"{h}-{n}-p{p}" for h, n, p in ATTN_FUSED])
+def test_attn_fused_batch_against_reference(heads, lens_name, nparts):
+    """dfl_attn_fused_batch (the batch's attention stage when attn_impl != "head") on the fp32 K parts, against the same
+    reference and with the same bars as the head forms above; GQA groups 4 and 8, ragged lengths including 0."""
+    _attn_case("fused", heads, lens_name, nparts, seed=1000 + 10 * list(LENS).index(lens_name) + nparts)
 
 
 # ---------------------------------------------------------------- dfl_kv_append_batch / _t (rows.hip)
