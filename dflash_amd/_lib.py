@@ -44,6 +44,12 @@ SIGNATURES = {
     "dfl_gemm_silu_mul": (_i, [_p, _r, _i, _i, _p, _p, _p]),
     "dfl_gemm_resid": (_i, [_p, _r, _i, _i, _p, _i64, _i, _p, _i64, _p, _p, _p]),
     "dfl_embed_rows": (_i, [_p, _p, _p, _i, _p, _p, _i, _p]),
+    # ---- fp8 (e4m3) weight streaming: the scale vector follows the packed weight
+    "dfl_pack_weight_fp8": (_i, [_p, _p, _i, _i, _p]),
+    "dfl_pack_weight_gateup_fp8": (_i, [_p, _p, _p, _i, _i, _p]),
+    "dfl_gemm_resid_fp8": (_i, [_p, _p, _r, _i, _i, _p, _i64, _i, _p, _i64, _p, _p, _p]),
+    "dfl_gemm_silu_mul_fp8": (_i, [_p, _p, _r, _i, _i, _p, _p, _p]),
+    "dfl_gemm_argmax_fp8": (_i, [_p, _p, _r, _i, _i, _i, _i, _p, _i, _p, _p, _i, _p, _p, _p, _p, _p]),
     "dfl_argmax_ws_bytes": (_i64, []),
     "dfl_gemm_argmax": (_i, [_p, _r, _i, _i, _i, _i, _p, _i, _p, _p, _i, _p, _p, _p, _p, _p]),
     "dfl_gemm_sample": (_i, [_p, _r, _i, _i, _i, _i, _p, _i, _p, _p, _i, _p, _p, _u64, _f, _i, _p, _i, _i, _i, _p]),

@@ -42,6 +42,39 @@ __device__ __forceinline__ void load_ksteps(bf16x8 (&wr)[NF], const bf16x8 *firs
     wr[f] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(r, voff + (f & 3) * 1024, (f >> 2) * 4096, AUX));
 }
 
+// ---- W8: weights stored as OCP e4m3 codes (one byte each), converted to bf16 in registers (exact) ----
+// Packed layout [N/16][K/64][64 lanes][16 B]: lane l (column l & 15, kq = l >> 4) holds the 8 codes of k-step 2j
+// (k = 64j + 8kq ..) in bytes 0-7 and those of k-step 2j+1 (k = 64j + 32 + 8kq ..) in bytes 8-15, so one 16-byte load
+// per lane is still one contiguous 1 KiB wave request and carries TWO MFMA A-fragments.
+// The W8 form of load_ksteps: the wave's NF k-steps (NF even) as NF/2 loads; `nf` (k-steps of the wave's share, even)
+// clips the descriptor at nf * 512 bytes.  The raw 16-byte words stay in flight as they are (half the registers of the
+// bf16 form); w8_frag turns one into the fragment of k-step f right in front of its MFMA.
+template <int NF, int AUX = 2>
+__device__ __forceinline__ void load_ksteps_w8(bf16x8 (&wr)[NF / 2], const bf16x8 *first, int nf, int l, int half = -1) {
+  static_assert(NF % 2 == 0, "W8: a wave's share is a whole number of k-step pairs");
+  load_ksteps<NF / 2, AUX>(wr, first, nf >> 1, l, half);
+}
+
+// the 8 e4m3 codes in half `hi` (0: bytes 0-7, 1: bytes 8-15) of one 16-byte word -> bf16x8
+__device__ __forceinline__ bf16x8 w8_frag(bf16x8 raw, int hi) {
+  const u32x4 q = __builtin_bit_cast(u32x4, raw);
+  const uint32_t d0 = hi ? q[2] : q[0], d1 = hi ? q[3] : q[1];
+  const bf16x2 a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d0, 1.0f, false);
+  const bf16x2 b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d0, 1.0f, true);
+  const bf16x2 c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d1, 1.0f, false);
+  const bf16x2 d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d1, 1.0f, true);
+  return (bf16x8){a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
+}
+
+// fragment of k-step f of an item's weight registers: bf16 words as loaded, or converted from e4m3
+template <bool W8, int NW>
+__device__ __forceinline__ bf16x8 weight_frag(const bf16x8 (&wr)[NW], int f) {
+  if constexpr (W8)
+    return w8_frag(wr[f >> 1], f & 1);
+  else
+    return wr[f];
+}
+
 // sum over the 16 lanes of a DPP row, result in each of them
 __device__ __forceinline__ float row_sum16(float v) {
   v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));

@@ -19,6 +19,8 @@
 //     running bf16 argmax (lm_head) / residual add -> h, taps, sums of squares;
 //   * K beyond 16 waves x 8 steps: either grid.y partials, or (CHUNKED) the workgroup
 //     loops over K chunks itself so that the epilogue sees finished sums.
+//   * W8 (k_gemm_w8, the draft's optional fp8 weights): the same kernel over e4m3 codes, one byte per weight, two
+//     k-steps per 16-byte word, converted to bf16 in registers; one fp32 scale per output row on the fp32 sum.
 // MFMA utilisation is a few percent by construction; the roofline is HBM: every launch
 // costs ~3.6 us + bytes / 6.5 TB/s (scripts/bench_gemm.py).
 #include "gemm_rows.h"
@@ -65,6 +67,9 @@ struct GemmArgs {
   bf16_t *tap;  // optional second copy of the new rows, row stride ldtap
   int64_t ldtap;
   float *ss_out;  // [ntiles][16] sum over the tile's 16 columns of h_new^2
+  // W8 kernels (k_gemm_w8): wp holds e4m3 codes (gemm_rows.h, W8); wscale[16 t + nl] multiplies the fp32 K-sum of
+  // packed tile t, column nl, before the epilogue's first rounding.  Last, so that no other field moves.
+  const float *wscale;
 };
 
 // EPI_SAMPLE (which reads the EPI_ARGMAX fields of GemmArgs as well): row m draws position base + pos_add + m, base =
@@ -205,10 +210,14 @@ constexpr int gemm_fr(int MT, bool CHUNKED) { return CHUNKED ? 4 : (MT == 1 ? 8 
 // commits dc953f3 and 5c920f1): item 1's weights requested in the prologue as well; the workgroup summing the squares
 // of its own rows (v_dot2c) instead of loading the producer's partials; waiting for the rows before the first weight
 // request; an 8-wave, three-buffer form of the K-chunked kernel.
-template <int MT, bool CHUNKED, int EPI, bool NORM>
+// W8: the weights are e4m3 codes, two k-steps per 16-byte word (gemm_rows.h): half as many loads per item, each word
+// converted into two fragments in front of its MFMAs; the finishing thread's scale is requested WITH the item's weights.
+// Everything else (masks, the half-tile lane rule, the LDS meeting, the tile plan) is the bf16 form's.
+template <int MT, bool CHUNKED, int EPI, bool NORM, bool W8 = false>
 __device__ __forceinline__ void gemm_body(const GemmArgs &a, const SampleArgs &sa) {
   GSTAMP(0);
   constexpr int FR = gemm_fr(MT, CHUNKED);
+  constexpr int NW = W8 ? FR / 2 : FR;  // 16-byte weight words per item and lane
   // red[buf][wave][mt][256]: lane l owns floats 4l..4l+3 (its MFMA D regs)
   __shared__ float red[2][16][MT][256];
   __shared__ float ssred[NORM ? MT : 1][16][16];
@@ -242,7 +251,8 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &a, const SampleArgs &s
     return 2 * p + (j & 1);
   };
 
-  bf16x8 wA[FR], wB[FR];
+  bf16x8 wA[NW], wB[NW];
+  float scA = 1.f, scB = 1.f;  // W8: the scale of this thread's column (tid & 15) of the item in wA / wB
   bf16x8 xA[MT][FR], xB[MT][FR];
   bf16x8 xr[MT][FR];  // activations of the (single) chunk stay in registers for the launch
 
@@ -292,8 +302,19 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &a, const SampleArgs &s
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) issue_x<FR, false>(a.src[mt], ks, l, nv[mt], xb[mt], wv[mt]);  // no mode 2 here
   };
-  auto load_item = [&](bf16x8(&wr)[FR], bf16x8(&xb)[MT][FR], int t, int c, int half) {
-    load_ksteps<FR>(wr, a.wp + ((size_t)t * a.KS + ks0_of(c)) * 64, nf_of(c), l, half);
+  // W8: the wave's k-steps ks0 .. ks0 + nf of tile t (nf = 0: nothing is fetched) and, WITH that request, the scale of
+  // this thread's column — not behind the K loop: a dependent load at the tail of a one-tile launch is ~1 us
+  auto load_w8 = [&](bf16x8(&wr)[NW], float &sc, int t, int ks0, int nf, int half) {
+    if constexpr (W8) {
+      load_ksteps_w8<FR>(wr, a.wp + ((size_t)t * (a.KS >> 1) + (ks0 >> 1)) * 64, nf, l, half);
+      sc = a.wscale[(size_t)t * 16 + (tid & 15)];
+    }
+  };
+  auto load_item = [&](bf16x8(&wr)[NW], float &sc, bf16x8(&xb)[MT][FR], int t, int c, int half) {
+    if constexpr (W8)
+      load_w8(wr, sc, t, ks0_of(c), nf_of(c), half);
+    else
+      load_ksteps<FR>(wr, a.wp + ((size_t)t * a.KS + ks0_of(c)) * 64, nf_of(c), l, half);
     if (CHUNKED) load_item_x(xb, c);  // the weights first (HBM), the activation fragments (L2) behind them
   };
 
@@ -303,7 +324,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &a, const SampleArgs &s
   constexpr bool PREF = EPI == EPI_RESID && !NORM;
   bf16_t resid0 = (bf16_t)0.f;
 
-  auto finish = [&](int t, int pos) {
+  auto finish = [&](int t, int pos, float wsc) {
     const int buf = pos & 1;
     const int hf = half_of(pos);  // a half tile: the other 8 columns belong to the neighbouring workgroup
 #pragma unroll
@@ -318,6 +339,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &a, const SampleArgs &s
       float s = 0.f;
 #pragma unroll
       for (int ww = 0; ww < 16; ++ww) s += red[buf][ww][mt][idx];
+      if (W8) s *= wsc;  // the row's scale on the fp32 K-sum, in front of every rounding point below
       const bool colok = hf < 0 || (nl >> 3) == hf;
       if (EPI == EPI_F32) {
         if (colok) a.out[((size_t)(blockIdx.y * MT + mt) * 16 + m) * a.ldo + t * 16 + nl] = s;
@@ -369,7 +391,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &a, const SampleArgs &s
     }
   };
 
-  auto process = [&](bf16x8(&wr)[FR], bf16x8(&xb)[MT][FR], int t, int c, int pos) {
+  auto process = [&](bf16x8(&wr)[NW], float wsc, bf16x8(&xb)[MT][FR], int t, int c, int pos) {
     if (!CHUNKED || c == 0) {
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) acc[mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -384,9 +406,9 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &a, const SampleArgs &s
           const bool keep = ks0c + f < a.KS && (a.src[mt].mode == 0 || (l & 15) < nv[mt]);
           xv = keep ? xb[mt][f] : (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
         }
-        acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wr[f], xv, acc[mt], 0, 0, 0);
+        acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(weight_frag<W8>(wr, f), xv, acc[mt], 0, 0, 0);
       }
-    if (!CHUNKED || c == a.nch - 1) finish(t, pos);
+    if (!CHUNKED || c == a.nch - 1) finish(t, pos, wsc);
   };
 
   // item 0 of this workgroup (F32 / ARGMAX / RESID): whole tile blockIdx.x, or — a launch cut entirely in halves
@@ -474,7 +496,9 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &a, const SampleArgs &s
     // load_ksteps clips at the wave's share through the buffer descriptor instead (zero weights, no traffic), and
     // activations past the share are zero as well.  (The expert list of an MoE launch is a dependent scalar load: that
     // launch asks for its first weights once it knows the tile.)
-    if (!moe)
+    if constexpr (W8)
+      load_w8(wA, scA, SILU ? 2 * (int)blockIdx.x : first_tile, ks0_of(0), first_live ? nf0 : 0, first_half);
+    else if (!moe)
       load_ksteps<FR>(wA, a.wp + ((size_t)(SILU ? 2 * blockIdx.x : first_tile) * a.KS + ks0_of(0)) * 64,
                       first_live ? nf0 : 0, l, first_half);
     else if (nitems > 0)
@@ -520,7 +544,9 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &a, const SampleArgs &s
     }
   } else {
     // chunked kernels build their activation fragments per item: item 0's behind the weights already requested
-    if (nitems > 0 || !moe)
+    if constexpr (W8)
+      load_w8(wA, scA, first_tile, ks0_of(0), first_live ? nf0 : 0, first_half);
+    else if (nitems > 0 || !moe)
       load_ksteps<FR>(wA, a.wp + ((size_t)first_tile * a.KS + ks0_of(0)) * 64, first_live ? nf0 : 0, l, first_half);
     GSTAMP(6);
     load_item_x(xA, 0);
@@ -541,8 +567,8 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &a, const SampleArgs &s
       }
       // (requesting unconditionally — a zero-length dummy past the last item, so that hipcc can count the loads in
       // flight — was tried twice in this 16-wave kernel, rounds 2 and 3: 20.4 -> 20.8 us on down_proj; not kept)
-      if (i + 1 < nitems) load_item(wB, xB, tile_of(jn), cn, half_of(jn));
-      process(wA, xA, tile_of(j), c, j);
+      if (i + 1 < nitems) load_item(wB, scB, xB, tile_of(jn), cn, half_of(jn));
+      process(wA, scA, xA, tile_of(j), c, j);
       if (i == 0) GSTAMP(4);
       if (i + 1 >= nitems) break;
       int j2 = jn, c2 = cn + 1;  // item i+2
@@ -550,8 +576,8 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &a, const SampleArgs &s
         c2 = 0;
         ++j2;
       }
-      if (i + 2 < nitems) load_item(wA, xA, tile_of(j2), c2, half_of(j2));
-      process(wB, xB, tile_of(jn), cn, jn);
+      if (i + 2 < nitems) load_item(wA, scA, xA, tile_of(j2), c2, half_of(j2));
+      process(wB, scB, xB, tile_of(jn), cn, jn);
       if (i + 2 >= nitems) break;
       j = j2;
       c = c2;
@@ -587,19 +613,41 @@ __global__ __launch_bounds__(1024) void k_gemm(GEMM_HEAD_PARAMS, GemmArgs rest) 
   gemm_body<MT, CHUNKED, EPI, NORM>(with_head<CHUNKED, NORM>(rest, GEMM_HEAD_NAMES), SampleArgs{});
 }
 
+// the W8 form (e4m3 weights, gemm_body): a name of its own, so that the bf16 kernels keep theirs
+template <bool CHUNKED, int EPI, bool NORM>
+__global__ __launch_bounds__(1024) void k_gemm_w8(GEMM_HEAD_PARAMS, GemmArgs rest) {
+  gemm_body<1, CHUNKED, EPI, NORM, true>(with_head<CHUNKED, NORM>(rest, GEMM_HEAD_NAMES), SampleArgs{});
+}
+
 template <bool NORM>
 __global__ __launch_bounds__(1024) void k_gemm_s(GEMM_HEAD_PARAMS, GemmArgs rest, SampleArgs sa) {
   gemm_body<1, false, EPI_SAMPLE, NORM>(with_head<false, NORM>(rest, GEMM_HEAD_NAMES), sa);
 }
 
 // the instantiation for this launch's row sources (a normalised source needs the NORM kernels)
-template <int MT, bool CHUNKED, int EPI>
+template <int MT, bool CHUNKED, int EPI, bool W8 = false>
 bool launch_gemm(GemmArgs &a, dim3 grid, hipStream_t stream) {
   bool norm = false;
   for (int mt = 0; mt < MT; ++mt) norm |= a.src[mt].mode == 2;
   a.gx = (int)grid.x;
   GemmHead h;
   if (!gemm_head<CHUNKED>(h, a)) return false;
+  if constexpr (W8) {
+    static_assert(MT == 1, "the W8 kernels take one 16-row tile");
+    if (!a.wscale || a.KS % 2 || a.nfr % 2) {  // whole k-step pairs: per tile and per wave
+      dfl_set_error("skinny GEMM (fp8): needs a scale vector, K %% 64 == 0 and an even share per wave (K=%d, nfr=%d)",
+                    a.KS * 32, a.nfr);
+      return false;
+    }
+    if constexpr (!CHUNKED) {
+      if (norm) {
+        hipLaunchKernelGGL((k_gemm_w8<false, EPI, true>), grid, dim3(1024), 0, stream, GEMM_HEAD_OF(h), a);
+        return true;
+      }
+    }
+    hipLaunchKernelGGL((k_gemm_w8<CHUNKED, EPI, false>), grid, dim3(1024), 0, stream, GEMM_HEAD_OF(h), a);
+    return true;
+  }
   if constexpr (!CHUNKED) {  // (the chunked form takes no normalised source: its callers reject one)
     if (norm) {
       hipLaunchKernelGGL((k_gemm<MT, false, EPI, true>), grid, dim3(1024), 0, stream, GEMM_HEAD_OF(h), a);
@@ -665,6 +713,24 @@ __global__ void k_pack_weight(const bf16x8 *__restrict__ w, bf16x8 *__restrict__
     const size_t src = row * (size_t)(KS * 4) + (size_t)ks * 4 + (l >> 4);  // in 16-B units
     const size_t dt = t * tile_mul + tile_add;
     wp[(dt * KS + ks) * 64 + l] = w[src];
+  }
+}
+
+// The W8 layout (gemm_rows.h): a byte permutation of row-major e4m3 codes q [N][K].  Out word c = ((t*KP + j)*64 + l),
+// KP = K / 64: bytes 0-7 from q[t*16 + (l&15)][64j + 8(l>>4) ..], bytes 8-15 from 32 columns further on.
+__global__ void k_pack_weight_fp8(const uint2 *__restrict__ q, uint4 *__restrict__ wp, int ntiles, int KP, int tile_mul,
+                                  int tile_add) {
+  const size_t total = (size_t)ntiles * KP * 64;
+  for (size_t c = blockIdx.x * (size_t)blockDim.x + threadIdx.x; c < total; c += (size_t)gridDim.x * blockDim.x) {
+    const int l = c & 63;
+    const size_t tj = c >> 6;
+    const int j = tj % KP;
+    const size_t t = tj / KP;
+    const size_t row = t * 16 + (l & 15);
+    const size_t src = row * (size_t)(KP * 8) + (size_t)j * 8 + (l >> 4);  // in 8-byte units
+    const uint2 lo = q[src], hi = q[src + 4];
+    const size_t dt = t * tile_mul + tile_add;
+    wp[(dt * KP + j) * 64 + l] = make_uint4(lo.x, lo.y, hi.x, hi.y);
   }
 }
 
@@ -744,6 +810,27 @@ extern "C" int dfl_pack_weight_gateup(const void *gate, const void *up, void *wp
   return DFL_OK;
 }
 
+extern "C" int dfl_pack_weight_fp8(const void *q, void *wp8, int N, int K, void *stream) {
+  DFL_REQUIRE(q && wp8, "dfl_pack_weight_fp8: null pointer");
+  DFL_REQUIRE(N > 0 && K > 0 && N % 16 == 0 && K % 64 == 0, "dfl_pack_weight_fp8: need N%%16==0, K%%64==0 (N=%d K=%d)", N, K);
+  hipLaunchKernelGGL(k_pack_weight_fp8, dim3(2048), dim3(256), 0, (hipStream_t)stream, (const uint2 *)q, (uint4 *)wp8,
+                     N / 16, K / 64, 1, 0);
+  DFL_CHECK_LAUNCH("dfl_pack_weight_fp8");
+  return DFL_OK;
+}
+
+extern "C" int dfl_pack_weight_gateup_fp8(const void *gate_q, const void *up_q, void *wp8, int I, int K, void *stream) {
+  DFL_REQUIRE(gate_q && up_q && wp8, "dfl_pack_weight_gateup_fp8: null pointer");
+  DFL_REQUIRE(I > 0 && K > 0 && I % 16 == 0 && K % 64 == 0, "dfl_pack_weight_gateup_fp8: need I%%16==0, K%%64==0 (I=%d K=%d)", I,
+              K);
+  hipLaunchKernelGGL(k_pack_weight_fp8, dim3(2048), dim3(256), 0, (hipStream_t)stream, (const uint2 *)gate_q, (uint4 *)wp8,
+                     I / 16, K / 64, 2, 0);
+  hipLaunchKernelGGL(k_pack_weight_fp8, dim3(2048), dim3(256), 0, (hipStream_t)stream, (const uint2 *)up_q, (uint4 *)wp8,
+                     I / 16, K / 64, 2, 1);
+  DFL_CHECK_LAUNCH("dfl_pack_weight_gateup_fp8");
+  return DFL_OK;
+}
+
 extern "C" int dfl_embed_rows(const void *embed, const int64_t *ids, void *h_out, int H, float *ss_out,
                               const int32_t *dyn, int dyn_word, void *stream) {
   DFL_REQUIRE(embed && ids && h_out && ss_out, "dfl_embed_rows: null pointer");
@@ -784,24 +871,41 @@ extern "C" int dfl_gemm_f32(const void *wp, const dfl_rows *x0, const dfl_rows *
   return DFL_OK;
 }
 
-extern "C" int dfl_gemm_silu_mul(const void *wp_gateup, const dfl_rows *x, int I, int K, void *act_frag,
-                                 const int32_t *dyn, void *stream) {
-  DFL_REQUIRE(wp_gateup && act_frag, "dfl_gemm_silu_mul: null pointer");
-  DFL_REQUIRE(I > 0 && K > 0 && I % 16 == 0 && K % 32 == 0, "dfl_gemm_silu_mul: need I%%16==0, K%%32==0");
+// The fp8 entry points share their bf16 siblings' bodies: W8 = the weights are e4m3 codes in the W8 layout with one
+// fp32 scale per packed row (`wscale`), K % 64 == 0, and every wave's share (nfr) is rounded up to whole k-step pairs.
+namespace {
+template <bool W8>
+int gemm_silu_mul_impl(const char *who, const void *wp_gateup, const float *wscale, const dfl_rows *x, int I, int K,
+                       void *act_frag, const int32_t *dyn, void *stream) {
+  DFL_REQUIRE(wp_gateup && act_frag && (!W8 || wscale), "%s: null pointer", who);
+  DFL_REQUIRE(I > 0 && K > 0 && I % 16 == 0 && K % (W8 ? 64 : 32) == 0, "%s: need I%%16==0, K%%%d==0", who, W8 ? 64 : 32);
   const int KS = K / 32;
-  DFL_REQUIRE(KS <= 16 * 8, "dfl_gemm_silu_mul: K=%d needs a K split, which the fused activation cannot take", K);
+  DFL_REQUIRE(KS <= 16 * 8, "%s: K=%d needs a K split, which the fused activation cannot take", who, K);
   GemmArgs a{};
-  if (!fill_src(a.src[0], x, K, "dfl_gemm_silu_mul")) return DFL_EINVAL;
+  if (!fill_src(a.src[0], x, K, who)) return DFL_EINVAL;
   a.wp = (const bf16x8 *)wp_gateup;
+  a.wscale = wscale;
   a.dyn = dyn;
   a.KS = KS;
   a.ntiles = 2 * (I / 16);
   a.nfr = (KS + 15) / 16;
+  if (W8) a.nfr += a.nfr & 1;
   a.nch = 1;
   a.act = (bf16_t *)act_frag;
-  if (!launch_gemm<1, false, EPI_SILU>(a, dim3(grid_x_for(I / 16), 1), (hipStream_t)stream)) return DFL_EINVAL;
-  DFL_CHECK_LAUNCH("dfl_gemm_silu_mul");
+  if (!launch_gemm<1, false, EPI_SILU, W8>(a, dim3(grid_x_for(I / 16), 1), (hipStream_t)stream)) return DFL_EINVAL;
+  DFL_CHECK_LAUNCH(who);
   return DFL_OK;
+}
+}  // namespace
+
+extern "C" int dfl_gemm_silu_mul(const void *wp_gateup, const dfl_rows *x, int I, int K, void *act_frag,
+                                 const int32_t *dyn, void *stream) {
+  return gemm_silu_mul_impl<false>("dfl_gemm_silu_mul", wp_gateup, nullptr, x, I, K, act_frag, dyn, stream);
+}
+
+extern "C" int dfl_gemm_silu_mul_fp8(const void *wp_gateup, const float *wscale, const dfl_rows *x, int I, int K,
+                                     void *act_frag, const int32_t *dyn, void *stream) {
+  return gemm_silu_mul_impl<true>("dfl_gemm_silu_mul_fp8", wp_gateup, wscale, x, I, K, act_frag, dyn, stream);
 }
 
 // One launch for the gate/up projection of EVERY active expert of a sparse-MoE layer (Qwen3-MoE:
@@ -843,9 +947,12 @@ extern "C" int64_t dfl_argmax_ws_bytes(void) { return 256 * 16 * (int64_t)(2 * s
 namespace {
 int gemm_argmax_impl(const void *wp, const dfl_rows *x, int V, int K, int row0, int nrows, const int32_t *dyn,
                      int nrows_dyn_word, void *ws, int64_t *out_ids, int out_off, void *logits, float *margin_out,
-                     hipEvent_t ev0, hipEvent_t ev1, void *stream, const SampleArgs *smp = nullptr) {
-  DFL_REQUIRE(wp && ws && out_ids, "dfl_gemm_argmax: null pointer");
-  DFL_REQUIRE(V > 0 && K > 0 && V % 16 == 0 && K % 32 == 0, "dfl_gemm_argmax: need V%%16==0, K%%32==0 (V=%d K=%d)", V, K);
+                     hipEvent_t ev0, hipEvent_t ev1, void *stream, const SampleArgs *smp = nullptr,
+                     const float *wscale = nullptr, bool w8 = false) {
+  const char *who = w8 ? "dfl_gemm_argmax_fp8" : "dfl_gemm_argmax";
+  DFL_REQUIRE(wp && ws && out_ids && (!w8 || wscale), "%s: null pointer", who);
+  DFL_REQUIRE(V > 0 && K > 0 && V % 16 == 0 && K % (w8 ? 64 : 32) == 0, "%s: need V%%16==0, K%%%d==0 (V=%d K=%d)", who,
+              w8 ? 64 : 32, V, K);
   DFL_REQUIRE(row0 >= 0 && nrows >= 0 && row0 + nrows <= 16, "dfl_gemm_argmax: rows [%d,%d) outside the 16-row tile", row0,
               row0 + nrows);
   const int KS = K / 32;
@@ -857,6 +964,8 @@ int gemm_argmax_impl(const void *wp, const dfl_rows *x, int V, int K, int row0, 
   a.KS = KS;
   a.ntiles = V / 16;
   a.nfr = (KS + 15) / 16;
+  if (w8) a.nfr += a.nfr & 1;
+  a.wscale = wscale;
   a.nch = 1;
   a.row0 = row0;
   a.nrows = nrows;
@@ -877,6 +986,8 @@ int gemm_argmax_impl(const void *wp, const dfl_rows *x, int V, int K, int row0, 
       hipLaunchKernelGGL(k_gemm_s<true>, dim3(gx, 1), dim3(1024), 0, (hipStream_t)stream, GEMM_HEAD_OF(h), a, *smp);
     else
       hipLaunchKernelGGL(k_gemm_s<false>, dim3(gx, 1), dim3(1024), 0, (hipStream_t)stream, GEMM_HEAD_OF(h), a, *smp);
+  } else if (w8) {
+    if (!launch_gemm<1, false, EPI_ARGMAX, true>(a, dim3(gx, 1), (hipStream_t)stream)) return DFL_EINVAL;
   } else {
     if (!launch_gemm<1, false, EPI_ARGMAX>(a, dim3(gx, 1), (hipStream_t)stream)) return DFL_EINVAL;
   }
@@ -895,6 +1006,13 @@ extern "C" int dfl_gemm_argmax(const void *wp, const dfl_rows *x, int V, int K, 
                           (hipEvent_t)ev_start, (hipEvent_t)ev_end, stream);
 }
 
+extern "C" int dfl_gemm_argmax_fp8(const void *wp, const float *wscale, const dfl_rows *x, int V, int K, int row0, int nrows,
+                                   const int32_t *dyn, int nrows_dyn_word, void *ws, int64_t *out_ids, int out_off,
+                                   void *logits, float *margin_out, void *ev_start, void *ev_end, void *stream) {
+  return gemm_argmax_impl(wp, x, V, K, row0, nrows, dyn, nrows_dyn_word, ws, out_ids, out_off, logits, margin_out,
+                          (hipEvent_t)ev_start, (hipEvent_t)ev_end, stream, nullptr, wscale, true);
+}
+
 extern "C" int dfl_gemm_sample(const void *wp, const dfl_rows *x, int V, int K, int row0, int nrows, const int32_t *dyn,
                                int nrows_dyn_word, void *ws, int64_t *out_ids, int out_off, void *logits, float *margin_out,
                                uint64_t seed, float inv_t, int rng_stream, const int32_t *pos_dyn, int pos_word,
@@ -911,16 +1029,20 @@ extern "C" int dfl_gemm_sample(const void *wp, const dfl_rows *x, int V, int K, 
 }
 
 
-extern "C" int dfl_gemm_resid(const void *wp, const dfl_rows *x, int N, int K, void *h_io, int64_t ldh,
-                              int add_residual, void *tap, int64_t ldtap, float *ss_out, const int32_t *dyn,
-                              void *stream) {
-  DFL_REQUIRE(wp && h_io, "dfl_gemm_resid: null pointer");
-  DFL_REQUIRE(N > 0 && K > 0 && N % 16 == 0 && K % 32 == 0, "dfl_gemm_resid: need N%%16==0, K%%32==0 (N=%d K=%d)", N, K);
-  DFL_REQUIRE(ldh >= N && (!tap || ldtap >= N), "dfl_gemm_resid: row strides shorter than N");
+namespace {
+template <bool W8>
+int gemm_resid_impl(const char *who, const void *wp, const float *wscale, const dfl_rows *x, int N, int K, void *h_io,
+                    int64_t ldh, int add_residual, void *tap, int64_t ldtap, float *ss_out, const int32_t *dyn,
+                    void *stream) {
+  DFL_REQUIRE(wp && h_io && (!W8 || wscale), "%s: null pointer", who);
+  DFL_REQUIRE(N > 0 && K > 0 && N % 16 == 0 && K % (W8 ? 64 : 32) == 0, "%s: need N%%16==0, K%%%d==0 (N=%d K=%d)", who,
+              W8 ? 64 : 32, N, K);
+  DFL_REQUIRE(ldh >= N && (!tap || ldtap >= N), "%s: row strides shorter than N", who);
   const int KS = K / 32;
   GemmArgs a{};
-  if (!fill_src(a.src[0], x, K, "dfl_gemm_resid")) return DFL_EINVAL;
+  if (!fill_src(a.src[0], x, K, who)) return DFL_EINVAL;
   a.wp = (const bf16x8 *)wp;
+  a.wscale = wscale;
   a.dyn = dyn;
   a.KS = KS;
   a.ntiles = N / 16;
@@ -936,14 +1058,30 @@ extern "C" int dfl_gemm_resid(const void *wp, const dfl_rows *x, int N, int K, v
   const dim3 grid(gx, 1);
   if (KS <= 16 * 8) {  // the whole K fits the 16 waves x 8 steps of one pass
     a.nfr = (KS + 15) / 16;
+    if (W8) a.nfr += a.nfr & 1;
     a.nch = 1;
-    if (!launch_gemm<1, false, EPI_RESID>(a, grid, (hipStream_t)stream)) return DFL_EINVAL;
+    if (!launch_gemm<1, false, EPI_RESID, W8>(a, grid, (hipStream_t)stream)) return DFL_EINVAL;
   } else {  // walk K in chunks of 16 waves x 4 steps inside the workgroup
-    DFL_REQUIRE(a.src[0].mode != 2, "dfl_gemm_resid: a normalised source needs K <= 4096");
+    DFL_REQUIRE(a.src[0].mode != 2, "%s: a normalised source needs K <= 4096", who);
     a.nfr = 4;
     a.nch = (KS + 63) / 64;  // 64 k-steps per chunk: 16 waves x 4
-    if (!launch_gemm<1, true, EPI_RESID>(a, grid, (hipStream_t)stream)) return DFL_EINVAL;
+    if (!launch_gemm<1, true, EPI_RESID, W8>(a, grid, (hipStream_t)stream)) return DFL_EINVAL;
   }
-  DFL_CHECK_LAUNCH("dfl_gemm_resid");
+  DFL_CHECK_LAUNCH(who);
   return DFL_OK;
+}
+}  // namespace
+
+extern "C" int dfl_gemm_resid(const void *wp, const dfl_rows *x, int N, int K, void *h_io, int64_t ldh,
+                              int add_residual, void *tap, int64_t ldtap, float *ss_out, const int32_t *dyn,
+                              void *stream) {
+  return gemm_resid_impl<false>("dfl_gemm_resid", wp, nullptr, x, N, K, h_io, ldh, add_residual, tap, ldtap, ss_out, dyn,
+                                stream);
+}
+
+extern "C" int dfl_gemm_resid_fp8(const void *wp, const float *wscale, const dfl_rows *x, int N, int K, void *h_io,
+                                  int64_t ldh, int add_residual, void *tap, int64_t ldtap, float *ss_out,
+                                  const int32_t *dyn, void *stream) {
+  return gemm_resid_impl<true>("dfl_gemm_resid_fp8", wp, wscale, x, N, K, h_io, ldh, add_residual, tap, ldtap, ss_out, dyn,
+                               stream);
 }

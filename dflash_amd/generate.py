@@ -211,6 +211,9 @@ class DecodeSession:
         self.lm_wp = model.packed_lm_head(target.lm_head) if self.use_draft else None
         if self.native and self.lm_wp is not None:
             target.share_lm_head(self.lm_wp)  # one packed copy serves draft unmask and target posterior
+        # an fp8 draft model: the DRAFT's greedy unmask streams an e4m3 copy of the lm_head (the target keeps the bf16 one)
+        self.lm_wp8 = (model.packed_lm_head_fp8(target.lm_head)
+                       if self.use_draft and getattr(model, "w8", None) is not None else None)
         self.stop_t = torch.tensor(stop_token_ids, dtype=torch.long, device=dev) if stop_token_ids else None
         # the reference scans the whole buffer, mask slots included (model/dflash.py:265-268)
         self.stop_always = stop_token_ids is not None and mask_token_id in stop_token_ids
@@ -271,6 +274,10 @@ class DecodeSession:
             e.record()
             self.events.setdefault(key, [None, None])[which] = e
 
+    def _lm8(self):
+        """The e4m3 lm_head for the draft's greedy unmask, or None (a bf16 model, or fp8_stream switched off)."""
+        return self.lm_wp8 if self.model.fp8_stream else None
+
     def _draft_ahead(self, bs) -> None:
         """The draft forward of the cycle AFTER the one whose accept kernel has just been enqueued (model/dflash.py:237-247
         of the next loop iteration): lengths from the device record, context rows = the verify's tap buffer (valid count
@@ -284,7 +291,7 @@ class DecodeSession:
                             block_ids=self.block[0], embed=self.embed_w, dyn_ready=True, s_bound=self.start + self.max_bs)
         if ev:
             ev[2].record()
-        _draft_ids(m, hid, self.lm_wp, bs, self.block[:, :bs], 0.0, self.draft_logits)
+        _draft_ids(m, hid, self.lm_wp, bs, self.block[:, :bs], 0.0, self.draft_logits, lm_wp8=self._lm8())
         if ev:
             ev[3].record()
             ev[1].record()
@@ -328,7 +335,7 @@ class DecodeSession:
             self._dyn_bs = None   # until the accept of this cycle has re-armed the record
             self._mark("lm_head", 0)
             _draft_ids(m, hid, self.lm_wp, bs, blk, self.draft_temperature, self.draft_logits, seed=self._dseed,
-                       dyn=self.dcache.dyn, start=self.start)
+                       dyn=self.dcache.dyn, start=self.start, lm_wp8=self._lm8())
             self._mark("lm_head", 1)
             return self._call_hook(blk)
         # benchmark.py:112-142: k full passes, each re-embedding the whole block, no draft
@@ -343,7 +350,7 @@ class DecodeSession:
                 c2, p0 = ctx[ctx_len - 16:], p0 + ctx_len - 16
             hid = m.draft_block(tmp, th_rows=c2, tau=c2.shape[0], bs=bs, pos0=p0, block_ids=blk[0],
                                 embed=self.embed_w, append=False)
-            _draft_ids(m, hid, self.lm_wp, bs, blk, 0.0)
+            _draft_ids(m, hid, self.lm_wp, bs, blk, 0.0, lm_wp8=self._lm8())
             self._call_hook(blk)
 
     @torch.inference_mode()
@@ -499,7 +506,7 @@ class DecodeSession:
             hid = m.draft_block(self.dcache, th_rows=self.taps_buf[:16], tau=16, bs=bs, pos0=bound, block_ids=self.block[0],
                                 embed=self.embed_w, dyn_ready=True, s_bound=bound)
             _draft_ids(m, hid, self.lm_wp, bs, self.block[:, :bs], self.draft_temperature, self.draft_logits,
-                       seed=self._dseed, dyn=self.dcache.dyn)
+                       seed=self._dseed, dyn=self.dcache.dyn, lm_wp8=self._lm8())
 
         def verify_accept(bs):   # (a T > 0 draw takes its positions from the target record's POS0 word: fresh every replay)
             post, _ = t.verify(self.block[0, :bs], bound, self.tcache, temperature=self.temperature, tap_layers=tl,
@@ -512,7 +519,7 @@ class DecodeSession:
         # not own through another attribute — the RoPE tables, the shared workspaces of draft model and target
         return _Replay(graphs, bound, (m._rope[0].data_ptr(), t._rope[0].data_ptr()),
                        (m._rope, t._rope, getattr(m, "ws", None), getattr(t, "ws", None), getattr(t, "_taps", None),
-                        self.lm_wp, self.embed_w, getattr(t, "lm_wp", None)))
+                        self.lm_wp, self.lm_wp8, self.embed_w, getattr(t, "lm_wp", None)))
 
     def _tables_moved(self, rec: _Replay) -> bool:
         """A shared draft model / NativeTarget replaces its RoPE table when another caller needs more positions
@@ -762,7 +769,8 @@ def run_decode(model, target, input_ids: torch.Tensor, *, mask_token_id: int, ma
                            seed=s.seed)
 
 
-def _draft_ids(model, hid_frag, lm_wp, bs, blk, draft_temperature, keep_logits=None, seed=None, dyn=None, start=None):
+def _draft_ids(model, hid_frag, lm_wp, bs, blk, draft_temperature, keep_logits=None, seed=None, dyn=None, start=None,
+               lm_wp8=None):
     """blk[0, 1:bs] <- draft tokens.  Greedy (every loop but the policy one at T>0):
     fused lm_head GEMM + argmax.  benchmark_dynamic_schedule.py:342 samples the draft
     with the temperature: then the logits are materialised by the same GEMM and the
@@ -770,9 +778,13 @@ def _draft_ids(model, hid_frag, lm_wp, bs, blk, draft_temperature, keep_logits=N
     buffer for the materialised logits (the multi-candidate loop builds its candidates from them).
     seed (sampler="device"): the seeded draw of the same GEMM's epilogue instead (stream DRAFT: slot j of the block that
     starts at `start` draws position start + j, extra = start); dyn: the draft cache's record, whose START word holds
-    that start on the device (what a captured graph reads)."""
+    that start on the device (what a captured graph reads).
+    lm_wp8 (an fp8 draft model): the e4m3 lm_head, taken by the greedy unmask of a block of <= 16 rows; a sampled
+    draft and a wide block keep the bf16 copy."""
     if draft_temperature < 1e-5:
-        model.draft_tokens(hid_frag, lm_wp, bs, blk[0], logits=keep_logits)
+        from .model import WideRows
+        wp = lm_wp8 if (lm_wp8 is not None and not isinstance(hid_frag, WideRows) and bs <= 16) else lm_wp
+        model.draft_tokens(hid_frag, wp, bs, blk[0], logits=keep_logits)
         return
     if seed is not None:
         model.draft_tokens(hid_frag, lm_wp, bs, blk[0], logits=keep_logits,

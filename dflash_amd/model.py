@@ -72,8 +72,20 @@ class WideRows:
         return self.tiles
 
 
+WEIGHT_FORMATS = ("bf16", "fp8_e4m3")
+
+
 class DFlashDraftModel:
-    def __init__(self, config, device=None):
+    def __init__(self, config, device=None, weight_format: str = "bf16"):
+        """weight_format: "bf16" (default), or "fp8_e4m3": every Linear weight of the draft is quantised at load time
+        to OCP e4m3 codes with one power-of-two scale per output row (ops.quantize_fp8_rows) — ONE quantised model:
+        `self.w` then holds the dequantised values (exact in bf16) for every path without an fp8 kernel, `self.w8` the
+        codes, which the single-request draft forward of a block of <= 16 rows streams at one byte per weight
+        (DESIGN.md section 10).  The target is never quantised, so committed tokens stay the target's own; what the
+        quantisation does to the acceptance length of a trained checkpoint is NOT measured — hence off by default."""
+        if weight_format not in WEIGHT_FORMATS:
+            raise ValueError(f"weight_format must be one of {WEIGHT_FORMATS}, got {weight_format!r}")
+        self.weight_format = weight_format
         self.config = DFlashConfig.from_any(config)
         c = self.config
         if c.head_dim != 128:
@@ -89,9 +101,15 @@ class DFlashDraftModel:
         self.target_layer_ids = list(c.target_layer_ids)
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.dtype = BF16
+        if weight_format == "fp8_e4m3" and any(k % 64 for k in (c.hidden_size, c.intermediate_size, c.fc_in, c.q_dim)):
+            raise NotImplementedError("fp8_e4m3 weights need hidden, intermediate, fc input and q widths % 64 == 0")
         self.w: Optional[dict] = None
+        self.w8: Optional[dict] = None   # fp8_e4m3: ops.Fp8Weight twins of the matrices in self.w (same keys)
+        # fp8_e4m3 only: False = run everything on the dequantised bf16 copy (the second implementation the tests compare)
+        self.fp8_stream = True
         self._ws = None
         self._lm_head_cache = {}
+        self._lm_head_cache8 = {}
         self._rope = None
         # "head": dfl_attn_head on finished bf16 q/k/v rows (round 2); "fused": round-1 stage on fp32 partials
         self.attn_impl = "head"
@@ -126,39 +144,72 @@ class DFlashDraftModel:
         def dev(name):
             return sd[name].to(device=self.device, dtype=BF16).contiguous()
 
-        w = {"fc": ops.pack_weight(dev("fc.weight")), "hidden_norm": dev("hidden_norm.weight"),
+        fp8 = self.weight_format == "fp8_e4m3"
+        w8 = {"layers": []} if fp8 else None
+
+        def mat(name, store, key):
+            """A Linear weight on the device: as loaded, or (fp8) its dequantised values, the codes packed into `store`."""
+            m = dev(name)
+            if not fp8:
+                return m
+            q, sc = ops.quantize_fp8_rows(m)
+            store[key] = (q, sc)
+            return ops.dequantize_fp8_rows(q, sc)
+
+        top8 = {}
+        w = {"fc": ops.pack_weight(mat("fc.weight", top8, "fc")), "hidden_norm": dev("hidden_norm.weight"),
              "norm": dev("norm.weight"), "layers": []}
+        if fp8:
+            w8["fc"] = ops.pack_weight_fp8(*top8.pop("fc"))
         for i in range(c.num_hidden_layers):
             p = f"layers.{i}."
-            qkv = torch.cat([dev(p + "self_attn.q_proj.weight"), dev(p + "self_attn.k_proj.weight"),
-                             dev(p + "self_attn.v_proj.weight")], dim=0)
+            l8 = {}
+            qkv = torch.cat([mat(p + "self_attn.q_proj.weight", l8, "q"), mat(p + "self_attn.k_proj.weight", l8, "k"),
+                             mat(p + "self_attn.v_proj.weight", l8, "v")], dim=0)
+            gate, up = mat(p + "mlp.gate_proj.weight", l8, "gate"), mat(p + "mlp.up_proj.weight", l8, "up")
+            o, down = mat(p + "self_attn.o_proj.weight", l8, "o"), mat(p + "mlp.down_proj.weight", l8, "down")
+            if fp8:
+                w8["layers"].append({
+                    "qkv": ops.pack_weight_fp8(torch.cat([l8[k][0] for k in "qkv"]), torch.cat([l8[k][1] for k in "qkv"])),
+                    "o": ops.pack_weight_fp8(*l8["o"]),
+                    "gu": ops.pack_weight_gateup_fp8(*l8["gate"], *l8["up"]),
+                    "down": ops.pack_weight_fp8(*l8["down"]),
+                })
+            del l8
             w["layers"].append({
                 "qkv": ops.pack_weight(qkv),
-                "o": ops.pack_weight(dev(p + "self_attn.o_proj.weight")),
-                "gu": ops.pack_weight_gateup(dev(p + "mlp.gate_proj.weight"), dev(p + "mlp.up_proj.weight")),
-                "down": ops.pack_weight(dev(p + "mlp.down_proj.weight")),
+                "o": ops.pack_weight(o),
+                "gu": ops.pack_weight_gateup(gate, up),
+                "down": ops.pack_weight(down),
                 "q_norm": dev(p + "self_attn.q_norm.weight"), "k_norm": dev(p + "self_attn.k_norm.weight"),
                 "ln1": dev(p + "input_layernorm.weight"), "ln2": dev(p + "post_attention_layernorm.weight"),
             })
-            del qkv
+            del qkv, gate, up, o, down
         # context K/V weights of ALL layers as one packed weight (tile-major layout: the k/v column tiles of
         # each layer's packed qkv, concatenated): the context rows' K/V of every layer depend only on the
         # context rows, so one GEMM per cycle produces them all (model/dflash.py:73-78, context half)
         w["kv_all"] = torch.cat([lw["qkv"][c.q_dim * c.hidden_size:] for lw in w["layers"]]).contiguous()
         w["k_norm_all"] = torch.stack([lw["k_norm"] for lw in w["layers"]]).contiguous()
+        if fp8:   # the k/v column tiles of each layer's packed codes are a plain slice too, and so are their scales
+            nkv2 = 2 * c.kv_dim
+            w8["kv_all"] = ops.Fp8Weight(
+                torch.cat([l8["qkv"].wp[c.q_dim * c.hidden_size:] for l8 in w8["layers"]]).contiguous(),
+                torch.cat([l8["qkv"].scale[c.q_dim:] for l8 in w8["layers"]]).contiguous(),
+                c.num_hidden_layers * nkv2, c.hidden_size)
         torch.cuda.synchronize(self.device)
         self.w = w
+        self.w8 = w8
         self._ws = None  # row sources point at the weights: rebuild with them
         return self
 
     @classmethod
-    def from_pretrained(cls, path: str, device=None, **_):
+    def from_pretrained(cls, path: str, device=None, weight_format: str = "bf16", **_):
         """HF checkpoint directory: config.json (+ block_size / num_target_layers /
-        dflash_config, model/dflash.py:157,162-163) and *.safetensors shards."""
+        dflash_config, model/dflash.py:157,162-163) and *.safetensors shards.  weight_format: as the constructor's."""
         from safetensors.torch import load_file
         with open(os.path.join(path, "config.json")) as f:
             cfg = json.load(f)
-        model = cls(cfg, device=device)
+        model = cls(cfg, device=device, weight_format=weight_format)
         sd = {}
         for fn in sorted(os.listdir(path)):
             if fn.endswith(".safetensors"):
@@ -238,6 +289,23 @@ class DFlashDraftModel:
             self._lm_head_cache.clear()
             self._lm_head_cache[key] = ops.pack_weight(wt.detach().to(device=self.device, dtype=BF16).contiguous())
         return self._lm_head_cache[key]
+
+    def packed_lm_head_fp8(self, lm_head) -> ops.Fp8Weight:
+        """The target's lm_head weight quantised to e4m3 rows and packed for streaming (the DRAFT's greedy unmask only:
+        the target keeps its bf16 copy); cached per weight tensor as packed_lm_head."""
+        wt = lm_head.weight if hasattr(lm_head, "weight") else lm_head
+        key = (wt.data_ptr(), tuple(wt.shape), wt._version)
+        if key not in self._lm_head_cache8:
+            self._lm_head_cache8.clear()
+            q, sc = ops.quantize_fp8_rows(wt.detach().to(device=self.device, dtype=BF16).contiguous())
+            self._lm_head_cache8[key] = ops.pack_weight_fp8(q, sc)
+        return self._lm_head_cache8[key]
+
+    def streams_fp8(self, bs: int) -> bool:
+        """Whether draft_block streams the e4m3 codes for a block of `bs` rows: an fp8 model, one 16-row tile, the head
+        attention stage, o_proj not fused.  Every other path computes the same quantised model from self.w."""
+        return (self.w8 is not None and self.fp8_stream and bs <= 16 and self.attn_impl == "head" and not self.fuse_oproj
+                and not self.wide_hidden)
 
     # ------------------------------------------------------------------ kernels
     def _ctx_rows(self, th_rows: torch.Tensor, n: int, dyn, dyn_word: Optional[int]):
@@ -374,6 +442,7 @@ class DFlashDraftModel:
         draft).  th_rows then holds 16 rows (the valid count is the record's tau), tau / pos0 are upper bounds,
         s_bound bounds S (it sizes the attention's key splits) and the host-side cache length is left to the caller."""
         c, ws, w = self.config, self._workspace(), self.w
+        ww = self.w8 if self.streams_fp8(bs) else w   # the matrices this forward streams (norm weights stay in w)
         if bs < 1 or bs > 32 or tau < 0 or tau > 16:
             raise ValueError(f"bs={bs} / tau={tau}: the kernels take 1..32 block rows and 0..16 context rows")
         head = self.attn_impl == "head"
@@ -397,10 +466,10 @@ class DFlashDraftModel:
         tiles = [(t, cache.dyn[8 * t:8 * t + 8]) for t in range((bs + 15) // 16)]
         if tau > 0:
             # fc straight off the tap rows; hidden_norm is applied by each layer's qkv GEMM (:177)
-            ops.gemm_resid(w["fc"], ops.rows_plain(th_rows, ops.DYN_TAU), H, c.fc_in, ws["ctxh"], add_residual=False,
+            ops.gemm_resid(ww["fc"], ops.rows_plain(th_rows, ops.DYN_TAU), H, c.fc_in, ws["ctxh"], add_residual=False,
                            ss_out=ws["ss_ctx"], dyn=dyn)
         if head and tau > 0:   # K/V Linear outputs of the context rows, all layers, one pass over 84 MB
-            ops.gemm_resid(w["kv_all"], src["ctx"], c.num_hidden_layers * 2 * c.kv_dim, H, ws["xc"], add_residual=False,
+            ops.gemm_resid(ww["kv_all"], src["ctx"], c.num_hidden_layers * 2 * c.kv_dim, H, ws["xc"], add_residual=False,
                            dyn=dyn)
         L = w["layers"]
         if len(tiles) == 2 and self.wide_one_pass and head:
@@ -414,10 +483,11 @@ class DFlashDraftModel:
         hrow = [ws["h"][16 * t:16 * t + 16] for t in range(2)]
         fuse_o = self.fuse_oproj and head and len(tiles) == 1 and c.q_dim <= 4096
         for i, lw in enumerate(L):
+            lm = ww["layers"][i]   # the layer's matrices: lw's own, or their e4m3 twins
             x1 = src["ln1_first"] if i == 0 else src["ln1"][i]
             if head:
                 for t, dt in tiles:
-                    ops.gemm_resid(lw["qkv"], x1[t], nqkv, H, ws["xq"][16 * t:], add_residual=False, dyn=dt)
+                    ops.gemm_resid(lm["qkv"], x1[t], nqkv, H, ws["xq"][16 * t:], add_residual=False, dyn=dt)
                 kw = dict(xq=ws["xq"], q_col=0, k_col=c.q_dim, v_col=c.q_dim + c.kv_dim,
                           xc=ws["xc"] if tau > 0 else None, ck_col=i * 2 * c.kv_dim,
                           cv_col=i * 2 * c.kv_dim + c.kv_dim, n_q=c.num_attention_heads,
@@ -442,12 +512,12 @@ class DFlashDraftModel:
                                ws=ws["attn_ws"], max_splits=self.max_splits, out_frag=ws["attn_frag"][0])
             for t, dt in tiles:
                 if not fuse_o:
-                    ops.gemm_resid(lw["o"], src["attn"][t], H, c.q_dim, hrow[t], add_residual=True, ss_out=ws["ss_h"][t],
+                    ops.gemm_resid(lm["o"], src["attn"][t], H, c.q_dim, hrow[t], add_residual=True, ss_out=ws["ss_h"][t],
                                    dyn=dt)
             for t, dt in tiles:
-                ops.gemm_silu_mul(lw["gu"], src["ln2"][i][t], I, H, ws["act_frag"][t], dt)
+                ops.gemm_silu_mul(lm["gu"], src["ln2"][i][t], I, H, ws["act_frag"][t], dt)
             for t, dt in tiles:
-                ops.gemm_resid(lw["down"], src["act"][t], H, I, hrow[t], add_residual=True, ss_out=ws["ss_h"][t],
+                ops.gemm_resid(lm["down"], src["act"][t], H, I, hrow[t], add_residual=True, ss_out=ws["ss_h"][t],
                                dyn=dt)
         if append and not ahead:
             cache.length = S + tau

@@ -5,7 +5,7 @@ raw pointers.  Everything raises on a non-CUDA tensor — there is no host path.
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -47,6 +47,99 @@ def pack_weight_gateup(gate: torch.Tensor, up: torch.Tensor) -> torch.Tensor:
     check(lib().dfl_pack_weight_gateup(_p(gate, BF16, "gate"), _p(up, BF16, "up"), _p(out), i, k, _stream()),
           "dfl_pack_weight_gateup")
     return out
+
+
+# ---- fp8 (OCP e4m3fn) weights: one byte per weight, one power-of-two scale per output row ----
+U8 = torch.uint8
+FP8_MAX = 448.0   # largest finite e4m3fn value
+
+
+class Fp8Weight(NamedTuple):
+    """A packed e4m3 weight (pack_weight_fp8 / pack_weight_gateup_fp8) and its fp32 scales in packed tile order.
+    gemm_resid / gemm_silu_mul / gemm_argmax take one in place of a packed bf16 weight."""
+    wp: torch.Tensor      # uint8 [N * K], layout [N/16][K/64][64 lanes][16 B]
+    scale: torch.Tensor   # fp32 [N]
+    N: int
+    K: int
+
+
+_fp8_cast_on_device = {}
+
+
+def fp8_cast_on_device(device) -> bool:
+    """Whether this torch build casts fp32 -> float8_e4m3fn on `device` as the host does (probed once per device over
+    every rounding boundary of the format: all midpoints between neighbouring codes and the codes themselves)."""
+    device = torch.device(device)
+    if device.type == "cpu":
+        return True
+    key = str(device)
+    if key not in _fp8_cast_on_device:
+        codes = torch.arange(256, dtype=U8)
+        v = codes.view(torch.float8_e4m3fn).float()
+        v = v[torch.isfinite(v)].sort().values
+        probe = torch.cat([v, (v[1:] + v[:-1]) / 2])
+        try:
+            got = probe.to(device).to(torch.float8_e4m3fn).view(U8).cpu()
+            ok = bool(torch.equal(got, probe.to(torch.float8_e4m3fn).view(U8)))
+        except (RuntimeError, TypeError, NotImplementedError):
+            ok = False
+        _fp8_cast_on_device[key] = ok
+    return _fp8_cast_on_device[key]
+
+
+def quantize_fp8_rows(w: torch.Tensor):
+    """[N, K] weight -> (q uint8 [N, K] e4m3fn codes, scale fp32 [N]): scale[n] = 2^ceil(log2(amax_n / 448)) (1 for an
+    all-zero row), q = round-to-nearest-even of clamp(w / scale, +-448).  w / scale is exact (a power of two), the cast
+    never sees a value beyond 448 and so never yields NaN, and q * scale is exactly representable in bf16.
+    Runs on w's device; a torch build whose device cast to float8_e4m3fn is missing or differs quantises on the host."""
+    assert w.dim() == 2
+    dev = w.device
+    if not fp8_cast_on_device(dev):
+        q, scale = quantize_fp8_rows(w.cpu())
+        return q.to(dev), scale.to(dev)
+    wf = w.detach().float()
+    amax = wf.abs().amax(dim=1)
+    m, e = torch.frexp(amax / FP8_MAX)                 # amax / 448 = m * 2^e, m in [0.5, 1)
+    e = torch.where(m == 0.5, e - 1, e)                # ceil(log2(.)): an exact power of two is its own ceiling
+    scale = torch.ldexp(torch.ones_like(amax), e)
+    scale = torch.where(amax / scale > FP8_MAX, scale * 2, scale)   # (a quotient rounded down onto a power of two)
+    scale = torch.where(amax == 0, torch.ones_like(scale), scale)
+    x = (wf / scale[:, None]).clamp_(-FP8_MAX, FP8_MAX)
+    q = x.to(torch.float8_e4m3fn).view(U8)
+    return q.contiguous(), scale.contiguous()
+
+
+def dequantize_fp8_rows(q: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """q * scale as bf16 [N, K] (exact for quantize_fp8_rows' output)."""
+    return (q.view(torch.float8_e4m3fn).float() * scale[:, None].float()).to(BF16)
+
+
+def pack_weight_fp8(q: torch.Tensor, scale: torch.Tensor) -> Fp8Weight:
+    """q uint8 [N, K] e4m3 codes (row-major), scale fp32 [N] -> Fp8Weight.  N % 16 == 0, K % 64 == 0."""
+    n, k = q.shape
+    assert scale.numel() == n
+    out = torch.empty(n * k, dtype=U8, device=q.device)
+    check(lib().dfl_pack_weight_fp8(_p(q, U8, "q"), _p(out), n, k, _stream()), "dfl_pack_weight_fp8")
+    return Fp8Weight(out, scale.to(device=q.device, dtype=F32).contiguous(), n, k)
+
+
+def pack_weight_gateup_fp8(gate_q: torch.Tensor, gate_scale: torch.Tensor, up_q: torch.Tensor,
+                           up_scale: torch.Tensor) -> Fp8Weight:
+    """gate / up codes [I, K] and scales [I] -> one Fp8Weight of 2I rows, tiles (and scales, 16 at a time) interleaved
+    (gate tile p, up tile p) as pack_weight_gateup."""
+    i, k = gate_q.shape
+    assert up_q.shape == gate_q.shape and gate_scale.numel() == i and up_scale.numel() == i
+    out = torch.empty(2 * i * k, dtype=U8, device=gate_q.device)
+    check(lib().dfl_pack_weight_gateup_fp8(_p(gate_q, U8, "gate_q"), _p(up_q, U8, "up_q"), _p(out), i, k, _stream()),
+          "dfl_pack_weight_gateup_fp8")
+    sc = torch.stack([gate_scale.to(F32).view(i // 16, 16), up_scale.to(F32).view(i // 16, 16)], dim=1)
+    return Fp8Weight(out, sc.reshape(-1).to(gate_q.device).contiguous(), 2 * i, k)
+
+
+def _fp8(wp: Fp8Weight, N: int, K: int, name: str):
+    if (wp.N, wp.K) != (N, K):
+        raise ValueError(f"dflash_amd: {name} is an fp8 weight of {wp.N} x {wp.K}, the launch asks for {N} x {K}")
+    return _p(wp.wp, U8, name), _p(wp.scale, F32, name + ".scale")
 
 
 # ---- per-cycle ------------------------------------------------------------------
@@ -159,6 +252,10 @@ def pick_ksplit(N: int, K: int, mt: int) -> int:
 
 def gemm_silu_mul(wp_gu, x, I: int, K: int, act_frag: torch.Tensor, dyn=None) -> None:
     assert act_frag.numel() >= 16 * I
+    if isinstance(wp_gu, Fp8Weight):
+        check(lib().dfl_gemm_silu_mul_fp8(*_fp8(wp_gu, 2 * I, K, "wp_gu"), _src(x).ref, I, K, _p(act_frag, BF16, "act"),
+                                          _p(dyn, I32, "dyn"), _stream()), "dfl_gemm_silu_mul_fp8")
+        return
     check(lib().dfl_gemm_silu_mul(_p(wp_gu, BF16, "wp_gu"), _src(x).ref, I, K, _p(act_frag, BF16, "act"),
                                   _p(dyn, I32, "dyn"), _stream()), "dfl_gemm_silu_mul")
 
@@ -178,6 +275,12 @@ def gemm_argmax(wp, x, V: int, K: int, row0: int, nrows: int, ws, out_ids: torch
     if margins is not None:
         assert margins.numel() >= out_off + nrows
     ev_start, ev_end = (None, None) if events is None else (events[0].cuda_event, events[1].cuda_event)
+    if isinstance(wp, Fp8Weight):
+        check(lib().dfl_gemm_argmax_fp8(*_fp8(wp, V, K, "wp"), _src(x).ref, V, K, row0, nrows, _p(dyn, I32, "dyn"),
+                                        nrows_dyn_word, _p(ws), _p(out_ids, I64, "out_ids"), out_off,
+                                        _p(logits, BF16, "logits"), _p(margins, F32, "margins"), ev_start, ev_end,
+                                        _stream()), "dfl_gemm_argmax_fp8")
+        return
     check(lib().dfl_gemm_argmax(_p(wp, BF16, "wp"), _src(x).ref, V, K, row0, nrows, _p(dyn, I32, "dyn"), nrows_dyn_word,
                                 _p(ws), _p(out_ids, I64, "out_ids"), out_off, _p(logits, BF16, "logits"),
                                 _p(margins, F32, "margins"), ev_start, ev_end, _stream()), "dfl_gemm_argmax")
@@ -319,6 +422,11 @@ def gemm_resid(wp, x, N: int, K: int, h_io: torch.Tensor, *, add_residual: bool,
         tp, ldt = tap.data_ptr(), tap.stride(0)
     if ss_out is not None:
         assert ss_out.numel() >= N
+    if isinstance(wp, Fp8Weight):
+        check(lib().dfl_gemm_resid_fp8(*_fp8(wp, N, K, "wp"), _src(x).ref, N, K, h_io.data_ptr(), h_io.stride(0),
+                                       int(add_residual), tp, ldt, _p(ss_out, F32, "ss_out"), _p(dyn, I32, "dyn"),
+                                       _stream()), "dfl_gemm_resid_fp8")
+        return
     check(lib().dfl_gemm_resid(_p(wp, BF16, "wp"), _src(x).ref, N, K, h_io.data_ptr(), h_io.stride(0),
                                int(add_residual), tp, ldt, _p(ss_out, F32, "ss_out"), _p(dyn, I32, "dyn"), _stream()),
           "dfl_gemm_resid")

@@ -164,6 +164,29 @@ int dfl_gemm_sample(const void *wp, const dfl_rows *x, int V, int K, int row0, i
 int dfl_gemm_resid(const void *wp, const dfl_rows *x, int N, int K, void *h_io, int64_t ldh, int add_residual,
                    void *tap, int64_t ldtap, float *ss_out, const int32_t *dyn, void *stream);
 
+/* ---- FP8 (OCP e4m3fn) weight streaming, weight-only (W8A16) ----
+ * The weight is stored as one e4m3 code per element plus one fp32 scale per output row; the kernels convert the codes
+ * to bf16 in registers (exact), run the same bf16 MFMA on the same bf16 activations, and multiply the fp32 K-sum by
+ * the row's scale before the epilogue's first rounding: Linear output = bf16(sum_k x[m][k] * q[n][k] * scale[n]).
+ * Packed layout [N/16][K/64][64 lanes][16 B]: lane l (column 16 t + (l & 15), kq = l >> 4) holds the 8 codes of
+ * k = 64 j + 8 kq .. in bytes 0-7 and those of k = 64 j + 32 + 8 kq .. in bytes 8-15.  K % 64 == 0.
+ * wscale: fp32 [N] in PACKED tile order: wscale[16 t + nl] belongs to column nl of packed tile t — row order for
+ * dfl_pack_weight_fp8, (gate tile p, up tile p) interleaved for dfl_pack_weight_gateup_fp8.  Any fp32 multiplier is
+ * taken; a code of 0x7f / 0xff is NaN.  Everything else is the bf16 sibling's contract, argument for argument. */
+/* q [N][K] uint8 row-major e4m3 codes -> wp8 (N * K bytes). */
+int dfl_pack_weight_fp8(const void *q, void *wp8, int N, int K, void *stream);
+/* gate_q / up_q [I][K] codes -> one packed weight of 2I rows, tiles interleaved as dfl_pack_weight_gateup. */
+int dfl_pack_weight_gateup_fp8(const void *gate_q, const void *up_q, void *wp8, int I, int K, void *stream);
+int dfl_gemm_resid_fp8(const void *wp, const float *wscale, const dfl_rows *x, int N, int K, void *h_io, int64_t ldh,
+                       int add_residual, void *tap, int64_t ldtap, float *ss_out, const int32_t *dyn, void *stream);
+/* gate and up sums are scaled separately, each before its bf16 rounding. */
+int dfl_gemm_silu_mul_fp8(const void *wp_gateup, const float *wscale, const dfl_rows *x, int I, int K, void *act_frag,
+                          const int32_t *dyn, void *stream);
+/* ids, logits and margins over bf16(sum * scale). */
+int dfl_gemm_argmax_fp8(const void *wp, const float *wscale, const dfl_rows *x, int V, int K, int row0, int nrows,
+                        const int32_t *dyn, int nrows_dyn_word, void *ws, int64_t *out_ids, int out_off, void *logits,
+                        float *margin_out, void *ev_start, void *ev_end, void *stream);
+
 /* h_out[m] = embed[ids[m]] for m < dyn[dyn_word] (model/dflash.py:237) and ss_out[m] =
  * sum of squares of that row (one partial per row: nss = 1 for the next GEMM). */
 int dfl_embed_rows(const void *embed, const int64_t *ids, void *h_out, int H, float *ss_out, const int32_t *dyn,
