@@ -108,6 +108,10 @@ SIGNATURES = {
     "dfl_gemm_silu_mul_batch": (_i, [_p, _rb, _i, _i, _i, _p, _i64, _p, _p, _p]),
     "dfl_gemm_resid_batch": (_i, [_p, _rb, _i, _i, _i, _p, _i64, _i64, _i, _p, _i64, _i64, _p, _i64, _p, _p, _p]),
     "dfl_gemm_argmax_batch": (_i, [_p, _rb, _i, _i, _i, _i, _i, _p, _i, _p, _p, _i64, _i, _p, _i64, _p]),
+    # fp8 (e4m3) weights in the ragged batch: the siblings' lists with the scale vector behind the packed weight
+    "dfl_gemm_f32_batch_fp8": (_i, [_p, _p, _rb, _i, _i, _i, _p, _p, _p]),
+    "dfl_gemm_silu_mul_batch_fp8": (_i, [_p, _p, _rb, _i, _i, _i, _p, _i64, _p, _p, _p]),
+    "dfl_gemm_argmax_batch_fp8": (_i, [_p, _p, _rb, _i, _i, _i, _i, _i, _p, _i, _p, _p, _i64, _i, _p, _i64, _p]),
     "dfl_gemm_sample_batch": (_i, [_p, _rb, _i, _i, _i, _i, _i, _p, _i, _p, _p, _i64, _i, _p, _i64, _p, _p, _f, _i, _i, _i, _i,
                                    _p]),
     "dfl_embed_rows_batch": (_i, [_p, _p, _i64, _i, _p, _i64, _i, _p, _i64, _p, _i, _p]),

@@ -166,6 +166,7 @@ class BatchedDecoder:
             v=self.tv, rope=t._rope_tab, aws=ops.attn_fused_batch_ws(MT, t.n_q, t.n_kv, max_splits, dev),
             hws=ops.attn_head_batch_ws(MT, t.n_q, max_splits, dev, q_tiles=TPR))
         self.lm_wp = None
+        self.lm_wp8 = None
         self.embed_w = None
         # ---- host mirror of the lengths
         self.start = [0] * R
@@ -183,6 +184,15 @@ class BatchedDecoder:
             e = torch.cuda.Event(enable_timing=True)
             e.record()
             self.events.setdefault(key, [None, None])[which] = e
+
+    def _lm8(self):
+        """The e4m3 lm_head of the greedy draft head, or None where the draft does not stream its codes; packed on first
+        use (0.6 GB at 8B shapes: not for a model that never reads it)."""
+        if not self.model.streams_fp8_tiles():
+            return None
+        if self.lm_wp8 is None:
+            self.lm_wp8 = self.model.packed_lm_head_fp8(self.target.lm_head)
+        return self.lm_wp8
 
     # ------------------------------------------------------------------ admission
     def _admit_prefill(self, r: int, input_ids: torch.Tensor, temperature: float, seed: Optional[int], top_k=0,
@@ -204,6 +214,8 @@ class BatchedDecoder:
         if self.lm_wp is None:
             self.lm_wp = m.packed_lm_head(t.lm_head)
             t.share_lm_head(self.lm_wp)
+            # an fp8 draft that streams: its greedy unmask takes an e4m3 copy of the lm_head (the target keeps the bf16 one)
+            self._lm8()
             self.embed_w = _bf16_table(t.model.embed_tokens.weight, self.dev)
         tc = _View(self.tk[r], self.tv[r], None, self.max_rows)
         out = t.prefill(input_ids, tc, output_hidden_states=True, tap_layers=self.model.target_layer_ids)
@@ -340,14 +352,17 @@ class BatchedDecoder:
         ops.gemm_resid_batch(m.w["fc"], self.src_taps, R, H, c.fc_in, d["ctxh"], add_residual=False, ws=self.gws,
                              dyn=dyn_d)
         ops.norm_frag_batch(d["ctxh"], R, m.w["hidden_norm"], eps, st.xn, dyn_d, ops.DYN_TAU)
-        ops.gemm_f32_batch(self.kv_all, st.src["xn"], R, self.nkv_all, H, d["part_kv"], dyn_d)
+        # an fp8 draft: the context K/V weights and the layers' gate/up, o, down — and q/k/v where
+        # it leaves K parts — stream their e4m3 codes; fc (a plain-row source) reads the dequantised copy
+        fp8 = m.streams_fp8_tiles()
+        ops.gemm_f32_batch(m.w8["kv_all"] if fp8 else self.kv_all, st.src["xn"], R, self.nkv_all, H, d["part_kv"], dyn_d)
         ops.kv_append_batch(kv=d["part_kv"], nsplit=ops.batch_ksplit(H), split_stride=MT * 16 * self.nkv_all,
                             ld=self.nkv_all, k_col=0, v_col=c.kv_dim, col_layer_stride=2 * c.kv_dim,
                             n_layers=c.num_hidden_layers, R=R, n_kv=c.num_key_value_heads, k_norm_w=self.k_norm_all,
                             eps=c.rms_norm_eps, cos_tab=cos, sin_tab=sin, kcache=self.dk, vcache=self.dv, dyn=dyn_d,
                             tiles_per_req=TPR)
         qkv, attend = self._attend(self.side_d, kvmax)   # block rows
-        st.run(m.w["layers"], R, dyn_t, attend, qkv=qkv)
+        st.run(m.tile_layers(qkv_parts=qkv == "parts"), R, dyn_t, attend, qkv=qkv)
 
     def _draft_head(self) -> None:
         m, c, R = self.model, self.cfg, self.NT
@@ -361,10 +376,12 @@ class BatchedDecoder:
             if self.TPR == 2:
                 self.block[:, 1:].copy_(self.ids_tmp.view(-1, self.BW)[:, 1:])
         elif self.TPR == 1:
-            ops.gemm_argmax_batch(self.lm_wp, s["xn"], R, c.vocab_size, c.hidden_size, 1, 15, self.gws, self.block, 1,
+            lm = self._lm8() or self.lm_wp
+            ops.gemm_argmax_batch(lm, s["xn"], R, c.vocab_size, c.hidden_size, 1, 15, self.gws, self.block, 1,
                                   self.dyn_tt, nrows_dyn_word=ops.DYN_BS)
         else:   # row 0 of a request's SECOND tile is a draft row: all 16 rows of every tile, row 0 of the block dropped here
-            ops.gemm_argmax_batch(self.lm_wp, s["xn"], R, c.vocab_size, c.hidden_size, 0, 16, self.gws, self.ids_tmp, 0,
+            lm = self._lm8() or self.lm_wp
+            ops.gemm_argmax_batch(lm, s["xn"], R, c.vocab_size, c.hidden_size, 0, 16, self.gws, self.ids_tmp, 0,
                                   self.dyn_tt, nrows_dyn_word=ops.DYN_BS)
             self.block[:, 1:].copy_(self.ids_tmp.view(-1, self.BW)[:, 1:])
 

@@ -49,6 +49,8 @@ struct GemmBArgs {
   int64_t ldtap, tap_stride;
   float *ss_out;  // [ntiles][16] per request
   int64_t ss_out_stride;
+  // W8 (EPI_F32; wp: e4m3 codes [ntiles][KS / 2][64 lanes][16 B]): fp32 scale per column, 64-byte aligned
+  const float *wscale;
 };
 
 // NW waves split the workgroup's K part; each keeps FR k-steps of every request's tile in
@@ -68,9 +70,16 @@ struct GemmBArgs {
 // 1.0-2.6 TB/s) — then drain, barrier, one relaxed agent-scope ticket.  The last part to
 // arrive acquires (L1 invalidate only) and ALL its waves combine the slabs, 8 (tile, request)
 // items per wave in flight, in a fixed part order.
-template <int MT, int EPI>
+//
+// W8 (EPI_F32 only): the weight items are e4m3 codes, FR / 2 loads of k-step pairs kept as raw
+// words (the three rotating buffers take half the registers) and converted in front of their MFMAs; nfr is even.  The
+// finishing wave multiplies the part's sums by the columns' scales in front of the store: EVERY K part is scaled, so
+// the launch that sums the parts later (norm, attention, K/V append) is untouched.
+template <int MT, int EPI, bool W8 = false>
 __global__ __launch_bounds__(512) void k_gemm_b(GemmBArgs a) {
   constexpr int FR = 8, NW = 8;
+  constexpr int WR = W8 ? FR / 2 : FR;  // registers (16 B per lane) of a weight item
+  static_assert(!W8 || EPI == EPI_F32, "W8: the K-part form only");
   constexpr int TPU = EPI == EPI_SILU ? 2 : 1;  // tiles per epilogue unit (SILU: gate + up)
   // MT = 4 lives at the 256-VGPR limit in its main loop (128 activations + 96 weights + 16
   // accumulators): the epilogue code is kept out of that loop — even a single K part goes
@@ -118,8 +127,11 @@ __global__ __launch_bounds__(512) void k_gemm_b(GemmBArgs a) {
   // right after loading it: `s_waitcnt vmcnt(0); scratch_store` in the main loop, which
   // serialises the whole prefetch ring.
   // (live = false: a dummy request — empty descriptor, zeros, no traffic — see the main loop)
-  auto load_item = [&](bf16x8(&wr)[FR], int t, bool live = true) {
-    load_ksteps<FR>(wr, a.wp + ((size_t)t * a.KS + ks0) * 64, live ? nf0 : 0, l);
+  auto load_item = [&](bf16x8(&wr)[WR], int t, bool live = true) {
+    if constexpr (W8)
+      load_ksteps_w8<FR>(wr, a.wp + ((size_t)t * a.KS + ks0) * 32, live ? nf0 : 0, l);
+    else
+      load_ksteps<FR>(wr, a.wp + ((size_t)t * a.KS + ks0) * 64, live ? nf0 : 0, l);
   };
 
   // ---- prologue: the first two weight items leave for HBM, then this wave's K slice of every
@@ -127,7 +139,7 @@ __global__ __launch_bounds__(512) void k_gemm_b(GemmBArgs a) {
   // activations go SECOND here: at 4 tiles they are 256 KB per workgroup, and asking for them
   // first delays the weight stream by more than it saves (6.47 -> 6.69 ms per 4-request cycle).
   bf16x8 xr[MT][FR];
-  bf16x8 wA[FR], wB[FR], wC[FR];
+  bf16x8 wA[WR], wB[WR], wC[WR];
   if (nseq > 0) load_item(wA, tile_of(0));
   if (nseq > 1) load_item(wB, tile_of(1));
   {
@@ -210,14 +222,23 @@ __global__ __launch_bounds__(512) void k_gemm_b(GemmBArgs a) {
   auto slab_off = [&](int k, int t, int mt) -> int { return ((((k * a.ntiles + t) * MT + mt) * 256) + 4 * l) * 4; };
 
   f32x4 acc[MT];
-  auto process = [&](bf16x8(&wr)[FR], int t, int pos) {
+  auto process = [&](bf16x8(&wr)[WR], int t, int pos) {
+    // W8: the tile's 16 scales by a scalar load (tile_scales: no VMEM operation, so the weight items in flight are not
+    // waited for).  hipcc places it in the finishing branch behind the barrier, where the finishing wave sits out its
+    // latency once per item.  Issuing it by inline asm in front of the MFMAs and waiting behind them was measured 0.1 -
+    // 1.5 us per launch faster (profiles/fp8_batch_ab.txt, section 6) and is NOT done: between the two asm statements
+    // the compiler would not know that the registers are pending, and a copy or spill there would read stale values.
+    f32x16 sc;
+    if constexpr (W8) sc = tile_scales(a.wscale, t);
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) acc[mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int f = 0; f < FR; ++f)  // k-steps past the wave's share: zero weights and zero activations
+    for (int f = 0; f < FR; ++f) {  // k-steps past the wave's share: zero weights and zero activations
+      const bf16x8 wf = weight_frag<W8>(wr, f);
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt)
-        acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wr[f], xr[mt][f], acc[mt], 0, 0, 0);
+        acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, xr[mt][f], acc[mt], 0, 0, 0);
+    }
     const int buf = pos & 1;
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) *reinterpret_cast<f32x4 *>(&red[buf][w][mt][l * 4]) = acc[mt];
@@ -226,6 +247,7 @@ __global__ __launch_bounds__(512) void k_gemm_b(GemmBArgs a) {
       f32x4 s = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int ww = 0; ww < NW; ++ww) s += *reinterpret_cast<const f32x4 *>(&red[buf][ww][w][l * 4]);
+      if constexpr (W8) s *= lane_scales(sc, fg);
       if (EPI == EPI_F32) {
         *reinterpret_cast<f32x4 *>(a.out + ((size_t)(ky * MT + w) * 16 + fm) * a.ldo + t * 16 + 4 * fg) = s;
       } else if (nky > 1 || !INLINE_EPI) {
@@ -501,10 +523,10 @@ void ring_plan(GemmRArgs &a, int nunits, int upp_max, int &gx) {
 
 // More than 64 KB of dynamic LDS needs the attribute: set once per instantiation (a function-local static: initialised
 // exactly once, whichever threads launch first).  False, with the error set, where it failed: nothing is launched.
-template <int MT, int TPU, int KQ, int NW, int A, int EPI>
+template <int MT, int TPU, int KQ, int NW, int A, int EPI, bool W8 = false>
 bool launch_ring(const char *who, const GemmRArgs &a, int gx, hipStream_t st) {
   constexpr int lds = ring_lds_bytes<MT, TPU, KQ, NW, A>();
-  void (*kern)(GemmRArgs) = dfl_k_gemm_r<MT, TPU, KQ, NW, A, EPI>;
+  void (*kern)(GemmRArgs) = dfl_k_gemm_r<MT, TPU, KQ, NW, A, EPI, W8>;
   static const hipError_t attr =
       hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   if (attr != hipSuccess) {
@@ -524,6 +546,11 @@ void fill_ring(GemmRArgs &a, const void *wp, const dfl_rows_batch *x, int N, int
   a.ntiles = N / 16;
   a.dyn = dyn;
 }
+
+// Look-ahead A (chunks of 8 k-steps) of the W8 ring forms: their bf16 siblings' values.  Half the bytes per chunk leave
+// LDS and vmcnt room for a deeper ring; deeper ones were measured and are not faster (DESIGN.md section 10,
+// profiles/fp8_batch_ab.txt section 5).
+constexpr int W8_A_SILU2 = 3, W8_A_SILU4 = 2, W8_A_ARGMAX2 = 2, W8_A_ARGMAX4 = 2;
 
 int batch_ksplit(int K) { return (K / 32 + 63) / 64; }
 int mt_of(int R) { return R <= 2 ? 2 : 4; }
@@ -570,13 +597,40 @@ bool fill_batch(GemmBArgs &a, const void *wp, const dfl_rows_batch *x, int R, in
   return true;
 }
 
-template <int EPI>
+template <int EPI, bool W8 = false>
 void launch_b(int R, dim3 grid, hipStream_t st, const GemmBArgs &a) {
   // MT is the compiled tile count: R = 3 runs as 4 with an empty fourth request, R = 1 as 2
   if (R <= 2)
-    hipLaunchKernelGGL((k_gemm_b<2, EPI>), grid, dim3(512), 0, st, a);
+    hipLaunchKernelGGL((k_gemm_b<2, EPI, W8>), grid, dim3(512), 0, st, a);
   else
-    hipLaunchKernelGGL((k_gemm_b<4, EPI>), grid, dim3(512), 0, st, a);
+    hipLaunchKernelGGL((k_gemm_b<4, EPI, W8>), grid, dim3(512), 0, st, a);
+}
+
+// What the three fp8 entry points refuse before anything else: the scale vector, and the K the packed e4m3 layout and
+// the kernels' shares take.
+bool fp8_batch_ok(const char *who, const void *wp, const float *wscale, const dfl_rows_batch *x, int R, int N, int K) {
+  if (!wp || !wscale || !x) {
+    dfl_set_error("%s: null pointer (weight, scale or row source)", who);
+    return false;
+  }
+  if ((uintptr_t)wscale % 64) {
+    dfl_set_error("%s: the scale vector must be 64-byte aligned", who);
+    return false;
+  }
+  if (R < 1 || R > 4 || N <= 0 || N % 16 || K < 256 || K % 64) {
+    dfl_set_error("%s: need 1 <= R <= 4, N%%16==0, K%%64==0, K >= 256 (R=%d N=%d K=%d)", who, R, N, K);
+    return false;
+  }
+  return true;
+}
+
+// ... and the two ring ones: they have no slab form
+bool fp8_ring_ok(const char *who, const dfl_rows_batch *x, int K) {
+  if (!ring_ok(x, K) || x->frag_stride % 8) {
+    dfl_set_error("%s: needs the ring form: frag16 row sources (mode 0) with frag_stride %% 8 == 0; there is no slab form", who);
+    return false;
+  }
+  return true;
 }
 
 }  // namespace
@@ -603,6 +657,23 @@ extern "C" int dfl_gemm_f32_batch(const void *wp, const dfl_rows_batch *x, int R
   const int ksplit = batch_ksplit(K);
   launch_b<EPI_F32>(R, dim3(grid_x_for(a.ntiles, ksplit), ksplit), (hipStream_t)stream, a);
   DFL_CHECK_LAUNCH("dfl_gemm_f32_batch");
+  return DFL_OK;
+}
+
+extern "C" int dfl_gemm_f32_batch_fp8(const void *wp8, const float *wscale, const dfl_rows_batch *x, int R, int N, int K,
+                                      float *out, const int32_t *dyn, void *stream) {
+  GemmBArgs a{};
+  const char *who = "dfl_gemm_f32_batch_fp8";
+  DFL_REQUIRE(out, "dfl_gemm_f32_batch_fp8: null pointer");
+  if (!fp8_batch_ok(who, wp8, wscale, x, R, N, K)) return DFL_EINVAL;
+  if (!fill_batch(a, wp8, x, R, N, K, dyn, nullptr, who)) return DFL_EINVAL;
+  a.nfr = (a.nfr + 1) & ~1;  // a wave's share is a whole number of k-step pairs (8 waves x nfr still cover the K part)
+  a.wscale = wscale;
+  a.out = out;
+  a.ldo = N;
+  const int ksplit = batch_ksplit(K);
+  launch_b<EPI_F32, true>(R, dim3(grid_x_for(a.ntiles, ksplit), ksplit), (hipStream_t)stream, a);
+  DFL_CHECK_LAUNCH("dfl_gemm_f32_batch_fp8");
   return DFL_OK;
 }
 
@@ -640,6 +711,34 @@ extern "C" int dfl_gemm_silu_mul_batch(const void *wp_gateup, const dfl_rows_bat
   const int ksplit = batch_ksplit(K);
   launch_b<EPI_SILU>(R, dim3(grid_x_for(I / 16, ksplit), ksplit), (hipStream_t)stream, a);
   DFL_CHECK_LAUNCH("dfl_gemm_silu_mul_batch");
+  return DFL_OK;
+}
+
+// The ring form over e4m3 codes; the look-ahead A of each form: DESIGN.md section 10, "The batch forms".
+extern "C" int dfl_gemm_silu_mul_batch_fp8(const void *wp8_gateup, const float *wscale, const dfl_rows_batch *x, int R,
+                                           int I, int K, void *act_frag, int64_t act_stride, void *ws,
+                                           const int32_t *dyn, void *stream) {
+  const char *who = "dfl_gemm_silu_mul_batch_fp8";
+  (void)ws;  // (the sibling's slab form needs it; kept so that the two take the same arguments)
+  DFL_REQUIRE(act_frag, "dfl_gemm_silu_mul_batch_fp8: null pointer");
+  if (!fp8_batch_ok(who, wp8_gateup, wscale, x, R, I, K) || !fp8_ring_ok(who, x, K)) return DFL_EINVAL;
+  DFL_REQUIRE(act_stride >= 16 * (int64_t)I, "dfl_gemm_silu_mul_batch_fp8: act_stride < 16*I");
+  GemmRArgs r{};
+  fill_ring(r, wp8_gateup, x, 2 * I, K, dyn);
+  r.wscale = wscale;
+  r.act = (bf16_t *)act_frag;
+  r.act_stride = act_stride;
+  int gx = 0;
+  const int per_wg = (I / 16 + 255) / 256;
+  const bool w16 = per_wg % 4 == 0 || per_wg > 6;  // as the bf16 sibling: the same waves take the same k-steps
+  ring_plan(r, I / 16, w16 ? 4 : 3, gx);
+  const hipStream_t st = (hipStream_t)stream;
+  const bool ok = R <= 2 ? (w16 ? launch_ring<2, 2, 4, 16, W8_A_SILU2, EPI_SILU, true>(who, r, gx, st)
+                                : launch_ring<2, 2, 4, 12, W8_A_SILU2, EPI_SILU, true>(who, r, gx, st))
+                         : (w16 ? launch_ring<4, 2, 4, 16, W8_A_SILU4, EPI_SILU, true>(who, r, gx, st)
+                                : launch_ring<4, 2, 4, 12, W8_A_SILU4, EPI_SILU, true>(who, r, gx, st));
+  if (!ok) return DFL_ELAUNCH;
+  DFL_CHECK_LAUNCH("dfl_gemm_silu_mul_batch_fp8");
   return DFL_OK;
 }
 
@@ -724,6 +823,27 @@ extern "C" int dfl_gemm_argmax_batch(const void *wp, const dfl_rows_batch *x, in
   hipLaunchKernelGGL(k_argmax_finish_b, dim3(16, R), dim3(64), 0, (hipStream_t)stream, a.best_val, a.best_idx, gx * 8,
                      mt_of(R), row0, nrows, dyn, nrows_dyn_word, out_ids, out_stride, out_off);
   DFL_CHECK_LAUNCH("dfl_gemm_argmax_batch");
+  return DFL_OK;
+}
+
+extern "C" int dfl_gemm_argmax_batch_fp8(const void *wp8, const float *wscale, const dfl_rows_batch *x, int R, int V,
+                                         int K, int row0, int nrows, const int32_t *dyn, int nrows_dyn_word, void *ws,
+                                         int64_t *out_ids, int64_t out_stride, int out_off, void *logits,
+                                         int64_t logits_stride, void *stream) {
+  const char *who = "dfl_gemm_argmax_batch_fp8";
+  DFL_REQUIRE(ws && out_ids, "dfl_gemm_argmax_batch_fp8: null pointer");
+  DFL_REQUIRE(row0 >= 0 && nrows >= 0 && row0 + nrows <= 16, "dfl_gemm_argmax_batch_fp8: rows [%d,%d) outside the tile",
+              row0, row0 + nrows);
+  if (!fp8_batch_ok(who, wp8, wscale, x, R, V, K) || !fp8_ring_ok(who, x, K)) return DFL_EINVAL;
+  GemmRArgs r{};
+  const int gx = fill_ring_rows(r, wp8, x, V, K, dyn, row0, nrows, nrows_dyn_word, ws, logits, logits_stride);
+  r.wscale = wscale;
+  if (!(R <= 2 ? launch_ring<2, 1, 1, 16, W8_A_ARGMAX2, EPI_ARGMAX, true>(who, r, gx, (hipStream_t)stream)
+               : launch_ring<4, 1, 1, 16, W8_A_ARGMAX4, EPI_ARGMAX, true>(who, r, gx, (hipStream_t)stream)))
+    return DFL_ELAUNCH;
+  hipLaunchKernelGGL(k_argmax_finish_b, dim3(16, R), dim3(64), 0, (hipStream_t)stream, r.best_val, r.best_idx, gx,
+                     mt_of(R), row0, nrows, dyn, nrows_dyn_word, out_ids, out_stride, out_off);
+  DFL_CHECK_LAUNCH("dfl_gemm_argmax_batch_fp8");
   return DFL_OK;
 }
 

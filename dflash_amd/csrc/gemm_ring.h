@@ -58,6 +58,8 @@ struct GemmRArgs {
   // EPI_SAMPLE_T (with the EPI_SAMPLE fields but inv_t): request slot q draws at invT = inv_ts[q]; a slot whose value is
   // not > 0 (0, negative, NaN) takes the plain argmax of EPI_ARGMAX: no Philox call, no noise
   const float *inv_ts;
+  // W8 (wp: e4m3 codes [ntiles][KS / 2][64 lanes][16 B]): fp32 scale per column in packed tile order, 64-byte aligned
+  const float *wscale;
 };
 
 namespace {
@@ -69,13 +71,20 @@ constexpr int R_CK = 8;  // k-steps per ring slot
 
 // MT request tiles, TPU tiles per unit, KQ waves per unit (each takes R_CK / KQ k-steps of every chunk), NW waves per
 // workgroup, A chunks of look-ahead (weights in flight per wave: A * R_CK / KQ * TPU KiB; ring: A + 1 slots)
-template <int MT, int TPU, int KQ, int NW, int A, int EPI>
+// W8: the weights are e4m3 codes, one 16-byte word per lane carrying the k-steps 2j and 2j + 1
+// (gemm_rows.h).  A wave's share of a chunk — KPC k-steps from kc * 8 + q * KPC, a whole number of aligned pairs — is
+// KPC / 2 loads, kept as raw words and converted in front of each of the two MFMAs a word feeds; the finished fp32 sums
+// are multiplied by the columns' scales in front of the epilogue's first rounding.  Half the loads per chunk: VMC below.
+template <int MT, int TPU, int KQ, int NW, int A, int EPI, bool W8 = false>
 __global__ __launch_bounds__(NW * 64) void dfl_k_gemm_r(GemmRArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)  // the host pass needs the kernel's handle only; with this body it drops the instantiation (no diagnostic)
   constexpr int CK = R_CK, KPC = CK / KQ, NS = A + 1;
   constexpr int NPIECE = CK * MT;                 // 1 KiB pieces per chunk
   constexpr int SP = (NPIECE + NW - 1) / NW;      // pieces per wave and chunk (surplus: a duplicate of the last piece)
-  constexpr int VMC = A * KPC * TPU + (A - 1) * SP;  // VMEM ops of a wave younger than its pieces of the chunk it is about to read
+  constexpr int WPC = W8 ? KPC / 2 : KPC;         // weight loads per chunk and tile (W8: one word per k-step pair)
+  constexpr int VMC = A * WPC * TPU + (A - 1) * SP;  // VMEM ops of a wave younger than its pieces of the chunk it is about to read
+  static_assert(!W8 || (KPC % 2 == 0 && (EPI == EPI_SILU || EPI == EPI_ARGMAX)), "W8: k-step pairs; SiLU and argmax only");
+  static_assert(!W8 || KQ == 1 || MT <= KQ, "W8: a wave finishes at most one (unit, request) item: upp * MT <= NW");
   constexpr bool ARG = EPI == EPI_ARGMAX || EPI == EPI_SAMPLE || EPI == EPI_SAMPLE_T;  // a running (perturbed) argmax per row
   static_assert(EPI == EPI_SILU || ARG, "the ring form has the SiLU epilogue and the three argmax ones");
   static_assert(CK % KQ == 0 && VMC < 64, "chunk split / vmcnt immediate");
@@ -143,22 +152,34 @@ __global__ __launch_bounds__(NW * 64) void dfl_k_gemm_r(GemmRArgs a) {
     g = (int)blockIdx.x + (p * a.upp + u) * (int)gridDim.x;
     const bool have = p < a.npass && u < a.upp && g < a.nunits;
 #pragma unroll
-    for (int tp = 0; tp < TPU; ++tp) base[tp] = a.wp + (size_t)(have ? TPU * g + tp : 0) * a.KS * 64;
-    bytes = have ? a.KS * 1024 : 0;
+    for (int tp = 0; tp < TPU; ++tp) base[tp] = a.wp + (size_t)(have ? TPU * g + tp : 0) * a.KS * (W8 ? 32 : 64);
+    bytes = have ? a.KS * (W8 ? 512 : 1024) : 0;
   };
-  bf16x8 wreg[A][KPC][TPU];
-  // weights of data chunk kc for this wave: k-steps kc * CK + q * KPC + j of the unit's tiles
+  // W8: the scales of the tiles whose sums this wave FINISHES in pass p — its own unit's (KQ = 1), or those of the item
+  // (unit slot w / MT, request w % MT) it takes after the KQ-way sum — 16 per tile by one scalar load (gemm_rows.h:
+  // no VMEM operation, the counts above stand), requested right behind the pass's first weights (in front of them the
+  // scalar wait for a descriptor word would wait for the scales too)
+  auto scales_of = [&](int p, f32x16(&sc)[TPU]) {
+    const int uu = KQ == 1 ? u : w / MT;
+    const int g = (int)blockIdx.x + (p * a.upp + uu) * (int)gridDim.x;
+    const bool have = p < a.npass && (KQ == 1 ? u < a.upp : w < a.upp * MT) && g < a.nunits;
+#pragma unroll
+    for (int tp = 0; tp < TPU; ++tp) sc[tp] = tile_scales(a.wscale, have ? TPU * g + tp : 0);
+  };
+  f32x16 scur[TPU], snxt[TPU];
+  bf16x8 wreg[A][WPC][TPU];
+  // weights of data chunk kc for this wave: k-steps kc * CK + q * KPC + j of the unit's tiles (W8: the pair j)
   auto wload1 = [&](bf16x8(&dst)[TPU], const bf16x8 *const(&base)[TPU], int bytes, int kc, int j) {
-    const int soff = (kc * CK + q * KPC + j) * 1024;
+    const int soff = W8 ? ((kc * CK + q * KPC) / 2 + j) * 1024 : (kc * CK + q * KPC + j) * 1024;
 #pragma unroll
     for (int tp = 0; tp < TPU; ++tp) {
       const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16x8 *>(base[tp]), 0, bytes, 0x00020000);
       dst[tp] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(wr, l * 16, soff, 2));
     }
   };
-  auto wload = [&](bf16x8(&dst)[KPC][TPU], const bf16x8 *const(&base)[TPU], int bytes, int kc) {
+  auto wload = [&](bf16x8(&dst)[WPC][TPU], const bf16x8 *const(&base)[TPU], int bytes, int kc) {
 #pragma unroll
-    for (int j = 0; j < KPC; ++j) wload1(dst[j], base, bytes, kc, j);
+    for (int j = 0; j < WPC; ++j) wload1(dst[j], base, bytes, kc, j);
   };
 
   const bf16x8 *wcur[TPU], *wnxt[TPU];
@@ -172,9 +193,11 @@ __global__ __launch_bounds__(NW * 64) void dfl_k_gemm_r(GemmRArgs a) {
     wload(wreg[c], wcur, bcur, kchunk(c));
     __builtin_amdgcn_sched_barrier(0);
   }
+  if constexpr (W8) scales_of(0, scur);
 
   for (int p = 0; p < a.npass; ++p) {
     unit_of(CONT ? p + 1 : a.npass, wnxt, bnxt, gnxt);  // (not CONT: nothing is requested across a pass boundary)
+    if constexpr (W8 && CONT) scales_of(p + 1, snxt);   // with the next pass's weights, not behind this K walk
     f32x4 acc[TPU][MT];
 #pragma unroll
     for (int tp = 0; tp < TPU; ++tp)
@@ -224,16 +247,31 @@ __global__ __launch_bounds__(NW * 64) void dfl_k_gemm_r(GemmRArgs a) {
           } else {
             asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(b[0]) : "v"(rd + j * MT * 1024) : "memory");
           }
+          if constexpr (W8) {
 #pragma unroll
-          for (int tp = 0; tp < TPU; ++tp)
+            for (int tp = 0; tp < TPU; ++tp) {
+              const bf16x8 wf = w8_frag(wreg[ca][j >> 1][tp], j & 1);
 #pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-              acc[tp][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wreg[ca][j][tp], b[mt], acc[tp][mt], 0, 0, 0);
-          // the registers just consumed take the same k-step of the chunk A ahead at once (past K: clipped, zeros, no
-          // traffic): the wave keeps A chunks of weights in flight all the time, not A - 1 while it computes
-          __builtin_amdgcn_sched_barrier(0);
-          wload1(wreg[ca][j], wsel, bsel, kcn, j);
-          __builtin_amdgcn_sched_barrier(0);
+              for (int mt = 0; mt < MT; ++mt)
+                acc[tp][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, b[mt], acc[tp][mt], 0, 0, 0);
+            }
+            if (j & 1) {  // both k-steps of the word are consumed: it takes the same pair of the chunk A ahead
+              __builtin_amdgcn_sched_barrier(0);
+              wload1(wreg[ca][j >> 1], wsel, bsel, kcn, j >> 1);
+              __builtin_amdgcn_sched_barrier(0);
+            }
+          } else {
+#pragma unroll
+            for (int tp = 0; tp < TPU; ++tp)
+#pragma unroll
+              for (int mt = 0; mt < MT; ++mt)
+                acc[tp][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wreg[ca][j][tp], b[mt], acc[tp][mt], 0, 0, 0);
+            // the registers just consumed take the same k-step of the chunk A ahead at once (past K: clipped, zeros, no
+            // traffic): the wave keeps A chunks of weights in flight all the time, not A - 1 while it computes
+            __builtin_amdgcn_sched_barrier(0);
+            wload1(wreg[ca][j], wsel, bsel, kcn, j);
+            __builtin_amdgcn_sched_barrier(0);
+          }
         }
       }
     }
@@ -300,8 +338,14 @@ __global__ __launch_bounds__(NW * 64) void dfl_k_gemm_r(GemmRArgs a) {
 
     if constexpr (KQ == 1) {
       if (bcur) {  // (the wave has a unit in this pass)
+        if constexpr (W8) {  // sum * scale, in front of every rounding of the epilogue
+          const f32x4 sl = lane_scales(scur[TPU - 1], fg), s0 = lane_scales(scur[0], fg);
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt) epilogue(TPU * gcur + TPU - 1, mt, acc[TPU - 1][mt], acc[0][mt]);
+          for (int mt = 0; mt < MT; ++mt) epilogue(TPU * gcur + TPU - 1, mt, acc[TPU - 1][mt] * sl, acc[0][mt] * s0);
+        } else {
+#pragma unroll
+          for (int mt = 0; mt < MT; ++mt) epilogue(TPU * gcur + TPU - 1, mt, acc[TPU - 1][mt], acc[0][mt]);
+        }
       }
     } else {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (padding pieces past the last chunk still target the ring)
@@ -324,6 +368,7 @@ __global__ __launch_bounds__(NW * 64) void dfl_k_gemm_r(GemmRArgs a) {
 #pragma unroll
           for (int qq = 0; qq < KQ; ++qq)  // fixed order: deterministic sums
             s[tp] += *reinterpret_cast<const f32x4 *>(&red[(((uu * KQ + qq) * TPU + tp) * MT + mt) * 256 + l * 4]);
+          if constexpr (W8) s[tp] *= lane_scales(scur[tp], fg);  // behind the KQ-way sum (it == w: scales_of's item)
         }
         epilogue(TPU * gg + TPU - 1, mt, s[TPU - 1], s[0]);
       }
@@ -334,6 +379,10 @@ __global__ __launch_bounds__(NW * 64) void dfl_k_gemm_r(GemmRArgs a) {
     for (int tp = 0; tp < TPU; ++tp) wcur[tp] = wnxt[tp];
     bcur = bnxt;
     gcur = gnxt;
+    if constexpr (W8 && CONT) {
+#pragma unroll
+      for (int tp = 0; tp < TPU; ++tp) scur[tp] = snxt[tp];
+    }
     if (!CONT && p + 1 < a.npass) {  // the ring was reused for the sums: a prologue of its own
       unit_of(p + 1, wcur, bcur, gcur);
       slot_r = slot_w;
@@ -344,6 +393,7 @@ __global__ __launch_bounds__(NW * 64) void dfl_k_gemm_r(GemmRArgs a) {
         wload(wreg[c], wcur, bcur, kchunk(c));
         __builtin_amdgcn_sched_barrier(0);
       }
+      if constexpr (W8) scales_of(p + 1, scur);
     }
   }
 

@@ -75,6 +75,22 @@ __device__ __forceinline__ bf16x8 weight_frag(const bf16x8 (&wr)[NW], int f) {
     return wr[f];
 }
 
+// The 16 fp32 scales of packed tile t (wscale + 16 t, 64-byte aligned) by ONE scalar load: the address is wave-uniform
+// and the pointer is read through the constant address space, so no VMEM operation is issued — the ragged-batch ring
+// kernel counts its vector loads by vmcnt immediates, and the register-resident one would wait for its weight items in
+// flight behind a vector load.  lane_scales picks the four of the lane's columns 4 fg .. 4 fg + 3 (MFMA D layout).
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+__device__ __forceinline__ f32x16 tile_scales(const float *wscale, int t) {
+  typedef const __attribute__((address_space(4))) f32x16 *cptr;
+  return *(cptr)(uintptr_t)(wscale + (size_t)__builtin_amdgcn_readfirstlane(t) * 16);
+}
+__device__ __forceinline__ f32x4 lane_scales(const f32x16 &s, int fg) {
+  f32x4 o;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) o[r] = fg == 0 ? s[r] : fg == 1 ? s[4 + r] : fg == 2 ? s[8 + r] : s[12 + r];
+  return o;
+}
+
 // sum over the 16 lanes of a DPP row, result in each of them
 __device__ __forceinline__ float row_sum16(float v) {
   v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));

@@ -50,7 +50,8 @@ class _DecoderDriver:
         """Addresses a captured launch reads that a prefill could in principle move."""
         d, m, t = self.dec, self.dec.model, self.dec.target
         return (m._rope[0].data_ptr(), m._rope[1].data_ptr(), t._rope[0].data_ptr(), t._rope[1].data_ptr(),
-                d.lm_wp.data_ptr(), d.embed_w.data_ptr(), t.embed.data_ptr())
+                d.lm_wp.data_ptr(), d.lm_wp8.wp.data_ptr() if d.lm_wp8 is not None else 0, d.embed_w.data_ptr(),
+                t.embed.data_ptr())
 
     def admit(self, slot: int, req) -> None:
         p = req.payload

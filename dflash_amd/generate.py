@@ -779,11 +779,12 @@ def _draft_ids(model, hid_frag, lm_wp, bs, blk, draft_temperature, keep_logits=N
     seed (sampler="device"): the seeded draw of the same GEMM's epilogue instead (stream DRAFT: slot j of the block that
     starts at `start` draws position start + j, extra = start); dyn: the draft cache's record, whose START word holds
     that start on the device (what a captured graph reads).
-    lm_wp8 (an fp8 draft model): the e4m3 lm_head, taken by the greedy unmask of a block of <= 16 rows; a sampled
-    draft and a wide block keep the bf16 copy."""
+    lm_wp8 (an fp8 draft model): the e4m3 lm_head, taken by the greedy unmask — of a block of <= 16 rows, or of a
+    17..32-row block that went through the tile stack; a sampled draft keeps the bf16 copy."""
     if draft_temperature < 1e-5:
         from .model import WideRows
-        wp = lm_wp8 if (lm_wp8 is not None and not isinstance(hid_frag, WideRows) and bs <= 16) else lm_wp
+        wide = isinstance(hid_frag, WideRows)   # (both tiles in one ragged-batch lm_head pass)
+        wp = lm_wp8 if lm_wp8 is not None and (model.streams_fp8_tiles() if wide else bs <= 16) else lm_wp
         model.draft_tokens(hid_frag, wp, bs, blk[0], logits=keep_logits)
         return
     if seed is not None:

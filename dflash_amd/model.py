@@ -80,8 +80,8 @@ class DFlashDraftModel:
         """weight_format: "bf16" (default), or "fp8_e4m3": every Linear weight of the draft is quantised at load time
         to OCP e4m3 codes with one power-of-two scale per output row (ops.quantize_fp8_rows) — ONE quantised model:
         `self.w` then holds the dequantised values (exact in bf16) for every path without an fp8 kernel, `self.w8` the
-        codes, which the single-request draft forward of a block of <= 16 rows streams at one byte per weight
-        (DESIGN.md section 10).  The target is never quantised, so committed tokens stay the target's own; what the
+        codes, which the draft forward streams at one byte per weight: a single request's block, the ragged batch and
+        the engine.  The target is never quantised, so committed tokens stay the target's own; what the
         quantisation does to the acceptance length of a trained checkpoint is NOT measured — hence off by default."""
         if weight_format not in WEIGHT_FORMATS:
             raise ValueError(f"weight_format must be one of {WEIGHT_FORMATS}, got {weight_format!r}")
@@ -110,6 +110,7 @@ class DFlashDraftModel:
         self._ws = None
         self._lm_head_cache = {}
         self._lm_head_cache8 = {}
+        self._tile_layers = {}   # tile_layers(): qkv_parts -> layer dicts with the e4m3 twins
         self._rope = None
         # "head": dfl_attn_head on finished bf16 q/k/v rows (round 2); "fused": round-1 stage on fp32 partials
         self.attn_impl = "head"
@@ -199,6 +200,7 @@ class DFlashDraftModel:
         torch.cuda.synchronize(self.device)
         self.w = w
         self.w8 = w8
+        self._tile_layers = {}
         self._ws = None  # row sources point at the weights: rebuild with them
         return self
 
@@ -306,6 +308,24 @@ class DFlashDraftModel:
         attention stage, o_proj not fused.  Every other path computes the same quantised model from self.w."""
         return (self.w8 is not None and self.fp8_stream and bs <= 16 and self.attn_impl == "head" and not self.fuse_oproj
                 and not self.wide_hidden)
+
+    def streams_fp8_tiles(self) -> bool:
+        """Whether the tile-stack paths — the ragged batch and engine (batch.py), a 17..32-row block
+        (_draft_block_wide) — stream the e4m3 codes: an fp8 model, fp8_stream, the head attention stage.  There the
+        gate/up, o_proj, down_proj, context K/V and greedy lm_head launches take the codes, and q/k/v where it leaves
+        K parts; fc, q/k/v as finished rows and a sampled lm_head read self.w."""
+        return self.w8 is not None and self.fp8_stream and self.attn_impl == "head"
+
+    def tile_layers(self, qkv_parts: bool) -> list:
+        """The layer dicts TileStack.run takes: self.w's, with gu / o / down — and qkv, where the caller runs
+        qkv="parts" — replaced by their e4m3 twins when streams_fp8_tiles()."""
+        if not self.streams_fp8_tiles():
+            return self.w["layers"]
+        if qkv_parts not in self._tile_layers:   # (built once per loaded state dict)
+            keys = ("gu", "o", "down") + (("qkv",) if qkv_parts else ())
+            self._tile_layers[qkv_parts] = [{**lw, **{k: l8[k] for k in keys}}
+                                            for lw, l8 in zip(self.w["layers"], self.w8["layers"])]
+        return self._tile_layers[qkv_parts]
 
     # ------------------------------------------------------------------ kernels
     def _ctx_rows(self, th_rows: torch.Tensor, n: int, dyn, dyn_word: Optional[int]):
@@ -553,7 +573,7 @@ class DFlashDraftModel:
                           ws=ws["head_ws"], max_splits=self.max_splits, out_frag=ws["attn_frag"], q_tiles=2,
                           out_tile_stride=ws["attn_frag"].stride(0))
 
-        st.run(w["layers"], R, dyn2, attend, qkv="rows")
+        st.run(self.tile_layers(qkv_parts=False), R, dyn2, attend, qkv="rows")
         st.finish(w["norm"])   # last down_proj's sums -> h (the rows forward() returns after its own norm), final norm -> frag16
         if append:
             cache.length = S + tau
@@ -564,6 +584,7 @@ class DFlashDraftModel:
                      sample: Optional[dict] = None) -> None:
         """block_ids[1:bs] <- argmax(lm_head(hidden[1:bs])) (model/dflash.py:238,245,247).
         hid_frag: what draft_block returned (one row source per 16-row tile; a single source = one tile).
+        lm_head_wp: the packed bf16 lm_head, or (greedy only: sample is None) an ops.Fp8Weight of it.
         logits (bf16 [16 * tiles, V]) / margins (fp32 [>= bs]): margins[j] <- top-1 minus top-2 draft
         logit of block slot j >= 1, the reference's per-position confidence
         (benchmark_candidate_solutions.py:296-302).
@@ -574,6 +595,8 @@ class DFlashDraftModel:
             if margins is not None:
                 raise NotImplementedError("top-2 margins are computed for blocks of <= 16 rows")
             gws, ids = self._wide.gws, self._wide_ids
+            if sample is not None and isinstance(lm_head_wp, ops.Fp8Weight):
+                raise ValueError("a sampled draft takes the bf16 lm_head")
             if sample is not None and logits is None:   # (no sampled ring epilogue: the draw runs over the logits)
                 logits = torch.empty(32, c.vocab_size, dtype=BF16, device=self.device)
             ops.gemm_argmax_batch(lm_head_wp, hid_frag.src, 2, c.vocab_size, c.hidden_size, 0, 16, gws, ids, 0,

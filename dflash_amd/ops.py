@@ -777,12 +777,21 @@ def gemm_batch_ws(N: int, K: int, device) -> torch.Tensor:
 
 def gemm_f32_batch(wp, x: BatchRowSource, R: int, N: int, K: int, out: torch.Tensor, dyn) -> None:
     assert out.numel() >= batch_ksplit(K) * batch_tiles(R) * 16 * N
+    if isinstance(wp, Fp8Weight):   # every K part comes out scaled: the launch that sums them takes it as it is
+        check(lib().dfl_gemm_f32_batch_fp8(*_fp8(wp, N, K, "wp"), x.ref, R, N, K, _p(out, F32, "out"), _p(dyn, I32, "dyn"),
+                                           _stream()), "dfl_gemm_f32_batch_fp8")
+        return
     check(lib().dfl_gemm_f32_batch(_p(wp, BF16, "wp"), x.ref, R, N, K, _p(out, F32, "out"), _p(dyn, I32, "dyn"),
                                    _stream()), "dfl_gemm_f32_batch")
 
 
 def gemm_silu_mul_batch(wp_gu, x: BatchRowSource, R: int, I: int, K: int, act: torch.Tensor, ws, dyn) -> None:
     assert act.dim() == 2 and act.shape[1] >= 16 * I and act.shape[0] >= batch_tiles(R)
+    if isinstance(wp_gu, Fp8Weight):   # the ring form only: a plain-row source is an error, not a fall-back
+        check(lib().dfl_gemm_silu_mul_batch_fp8(*_fp8(wp_gu, 2 * I, K, "wp_gu"), x.ref, R, I, K, _p(act, BF16, "act"),
+                                                act.stride(0), _p(ws), _p(dyn, I32, "dyn"), _stream()),
+              "dfl_gemm_silu_mul_batch_fp8")
+        return
     check(lib().dfl_gemm_silu_mul_batch(_p(wp_gu, BF16, "wp_gu"), x.ref, R, I, K, _p(act, BF16, "act"), act.stride(0),
                                         _p(ws), _p(dyn, I32, "dyn"), _stream()), "dfl_gemm_silu_mul_batch")
 
@@ -813,6 +822,11 @@ def gemm_argmax_batch(wp, x: BatchRowSource, R: int, V: int, K: int, row0: int, 
     if logits is not None:
         assert logits.dim() == 3 and logits.shape[1] == 16 and logits.shape[2] == V and logits.is_contiguous()
         lp, lst = _p(logits, BF16, "logits"), logits.stride(0)
+    if isinstance(wp, Fp8Weight):   # the ring form only, as above
+        check(lib().dfl_gemm_argmax_batch_fp8(*_fp8(wp, V, K, "wp"), x.ref, R, V, K, row0, nrows, _p(dyn, I32, "dyn"),
+                                              nrows_dyn_word, _p(ws), out_ids.data_ptr(), out_ids.stride(0), out_off, lp,
+                                              lst, _stream()), "dfl_gemm_argmax_batch_fp8")
+        return
     check(lib().dfl_gemm_argmax_batch(_p(wp, BF16, "wp"), x.ref, R, V, K, row0, nrows, _p(dyn, I32, "dyn"),
                                       nrows_dyn_word, _p(ws), out_ids.data_ptr(), out_ids.stride(0), out_off, lp, lst,
                                       _stream()), "dfl_gemm_argmax_batch")

@@ -592,6 +592,21 @@ int dfl_gemm_sample_batch(const void *wp, const dfl_rows_batch *x, int R, int V,
                           const int32_t *dyn, int nrows_dyn_word, void *ws, int64_t *out_ids, int64_t out_stride,
                           int out_off, void *logits, int64_t logits_stride, const int64_t *seeds, const float *inv_ts,
                           float inv_t, int rng_stream, int pos_word, int pos_add, int tiles_per_req, void *stream);
+/* ---- FP8 (e4m3) weights in the ragged batch ("The batch forms") ----
+ * The three launches below with the weight as e4m3 codes (dfl_pack_weight_fp8 / dfl_pack_weight_gateup_fp8) and its
+ * fp32 scales in packed tile order (64-byte aligned) in front; everything else is the bf16 sibling's contract, argument
+ * for argument.  The sums are multiplied by the columns' scales in front of the sibling's first rounding: gate and up
+ * separately, logits and argmax over bf16(sum * scale), and EVERY K part of dfl_gemm_f32_batch_fp8's output (the launch
+ * that sums the parts is untouched).  K % 64 == 0, K >= 256.
+ * dfl_gemm_silu_mul_batch_fp8 and dfl_gemm_argmax_batch_fp8 are the ring form and have no slab form: -22 for a source
+ * that is not frag16 (mode 0).  Never a quiet fall-back to the bf16 kernels. */
+int dfl_gemm_f32_batch_fp8(const void *wp8, const float *wscale, const dfl_rows_batch *x, int R, int N, int K, float *out,
+                           const int32_t *dyn, void *stream);
+int dfl_gemm_silu_mul_batch_fp8(const void *wp8_gateup, const float *wscale, const dfl_rows_batch *x, int R, int I, int K,
+                                void *act_frag, int64_t act_stride, void *ws, const int32_t *dyn, void *stream);
+int dfl_gemm_argmax_batch_fp8(const void *wp8, const float *wscale, const dfl_rows_batch *x, int R, int V, int K, int row0,
+                              int nrows, const int32_t *dyn, int nrows_dyn_word, void *ws, int64_t *out_ids,
+                              int64_t out_stride, int out_off, void *logits, int64_t logits_stride, void *stream);
 /* dfl_embed_rows for R requests: ids[r * ids_stride + m]. */
 int dfl_embed_rows_batch(const void *embed, const int64_t *ids, int64_t ids_stride, int R, void *h_out,
                          int64_t h_stride, int H, float *ss_out, int64_t ss_stride, const int32_t *dyn, int dyn_word,
