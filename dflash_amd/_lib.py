@@ -50,6 +50,7 @@ SIGNATURES = {
     "dfl_gemm_resid_fp8": (_i, [_p, _p, _r, _i, _i, _p, _i64, _i, _p, _i64, _p, _p, _p]),
     "dfl_gemm_silu_mul_fp8": (_i, [_p, _p, _r, _i, _i, _p, _p, _p]),
     "dfl_gemm_argmax_fp8": (_i, [_p, _p, _r, _i, _i, _i, _i, _p, _i, _p, _p, _i, _p, _p, _p, _p, _p]),
+    "dfl_gemm_sample_fp8": (_i, [_p, _p, _r, _i, _i, _i, _i, _p, _i, _p, _p, _i, _p, _p, _u64, _f, _i, _p, _i, _i, _i, _p]),
     "dfl_argmax_ws_bytes": (_i64, []),
     "dfl_gemm_argmax": (_i, [_p, _r, _i, _i, _i, _i, _p, _i, _p, _p, _i, _p, _p, _p, _p, _p]),
     "dfl_gemm_sample": (_i, [_p, _r, _i, _i, _i, _i, _p, _i, _p, _p, _i, _p, _p, _u64, _f, _i, _p, _i, _i, _i, _p]),
@@ -112,6 +113,8 @@ SIGNATURES = {
     "dfl_gemm_f32_batch_fp8": (_i, [_p, _p, _rb, _i, _i, _i, _p, _p, _p]),
     "dfl_gemm_silu_mul_batch_fp8": (_i, [_p, _p, _rb, _i, _i, _i, _p, _i64, _p, _p, _p]),
     "dfl_gemm_argmax_batch_fp8": (_i, [_p, _p, _rb, _i, _i, _i, _i, _i, _p, _i, _p, _p, _i64, _i, _p, _i64, _p]),
+    "dfl_gemm_sample_batch_fp8": (_i, [_p, _p, _rb, _i, _i, _i, _i, _i, _p, _i, _p, _p, _i64, _i, _p, _i64, _p, _p, _f, _i, _i,
+                                        _i, _i, _p]),
     "dfl_gemm_sample_batch": (_i, [_p, _rb, _i, _i, _i, _i, _i, _p, _i, _p, _p, _i64, _i, _p, _i64, _p, _p, _f, _i, _i, _i, _i,
                                    _p]),
     "dfl_embed_rows_batch": (_i, [_p, _p, _i64, _i, _p, _i64, _i, _p, _i64, _p, _i, _p]),

@@ -190,9 +190,13 @@ class BatchedDecoder:
         use (0.6 GB at 8B shapes: not for a model that never reads it)."""
         if not self.model.streams_fp8_tiles():
             return None
-        if self.lm_wp8 is None:
-            self.lm_wp8 = self.model.packed_lm_head_fp8(self.target.lm_head)
+        if self.lm_wp8 is None:   # (an fp8 target's own codes where it has them: one e4m3 copy serves both)
+            self.lm_wp8 = getattr(self.target, "lm_wp8", None) or self.model.packed_lm_head_fp8(self.target.lm_head)
         return self.lm_wp8
+
+    def _t_head(self):
+        """The verify's lm_head: an fp8 target that streams takes its e4m3 codes, else the shared packed bf16 copy."""
+        return self.target.lm_wp8 if self.target.streams_fp8_tiles() else self.lm_wp
 
     # ------------------------------------------------------------------ admission
     def _admit_prefill(self, r: int, input_ids: torch.Tensor, temperature: float, seed: Optional[int], top_k=0,
@@ -214,7 +218,8 @@ class BatchedDecoder:
         if self.lm_wp is None:
             self.lm_wp = m.packed_lm_head(t.lm_head)
             t.share_lm_head(self.lm_wp)
-            # an fp8 draft that streams: its greedy unmask takes an e4m3 copy of the lm_head (the target keeps the bf16 one)
+            # an fp8 draft that streams: its greedy unmask takes an e4m3 copy of the lm_head (an fp8 target's own codes,
+            # else packed here beside the bf16 one the target keeps)
             self._lm8()
             self.embed_w = _bf16_table(t.model.embed_tokens.weight, self.dev)
         tc = _View(self.tk[r], self.tv[r], None, self.max_rows)
@@ -394,30 +399,33 @@ class BatchedDecoder:
         ops.embed_rows_batch(t.embed, self.block.view(-1, 16), R, st.h, H, self.t["ss_emb"], dyn_t, ops.DYN_BS)
         qkv, attend = self._attend(self.side_t, kvmax)
         # (a sparse-MoE layer: the requests share attention and projections; routing and expert weights are per request)
-        st.run(t.layers, R, dyn_t, attend, qkv=qkv, taps=self.d["taps"], tap_layers=self.model.target_layer_ids,
-               moe=t.moe_mlp_tiles)
+        # (an fp8 target, DESIGN.md section 10 "The target": o, gate/up, down — and q/k/v where it leaves K parts — and
+        # every head below stream its e4m3 codes; q/k/v as finished rows reads the dequantised copy)
+        st.run(t.tile_layers(qkv_parts=qkv == "parts"), R, dyn_t, attend, qkv=qkv, taps=self.d["taps"],
+               tap_layers=self.model.target_layer_ids, moe=t.moe_mlp_tiles)
         st.finish(t.norm)
+        lm = self._t_head()
         if self.request_temperature and self.filtering:   # greedy slots keep the argmax ids the first launch wrote
-            ops.gemm_argmax_batch(self.lm_wp, s["xn"], R, t.V, H, 0, 16, self.gws, self.post.view(-1, 16), 0, dyn_t,
+            ops.gemm_argmax_batch(lm, s["xn"], R, t.V, H, 0, 16, self.gws, self.post.view(-1, 16), 0, dyn_t,
                                   nrows_dyn_word=ops.DYN_BS, logits=self._logits)
             ops.sample_rows_nucleus(self._logits[:R], seed=self.seeds, top_k=self.top_k, top_p=self.top_p,
                                     inv_t=self.inv_ts, dyn=dyn_t, nrows_dyn_word=ops.DYN_BS, pos_word=ops.DYN_POS0,
                                     pos_add=1, tiles_per_req=TPR, out=self.post.view(-1, 16))
         elif self.request_temperature:   # the fused draw at each slot's own invT; a greedy slot takes the plain argmax
-            ops.gemm_sample_batch(self.lm_wp, s["xn"], R, t.V, H, 0, 16, self.gws, self.post.view(-1, 16), 0, dyn_t,
+            ops.gemm_sample_batch(lm, s["xn"], R, t.V, H, 0, 16, self.gws, self.post.view(-1, 16), 0, dyn_t,
                                   seeds=self.seeds, inv_ts=self.inv_ts, pos_word=ops.DYN_POS0, pos_add=1,
                                   tiles_per_req=TPR, nrows_dyn_word=ops.DYN_BS)
         elif self.temperature < 1e-5:
-            ops.gemm_argmax_batch(self.lm_wp, s["xn"], R, t.V, H, 0, 16, self.gws, self.post.view(-1, 16), 0, dyn_t,
+            ops.gemm_argmax_batch(lm, s["xn"], R, t.V, H, 0, 16, self.gws, self.post.view(-1, 16), 0, dyn_t,
                                   nrows_dyn_word=ops.DYN_BS)
         elif self.filtering:   # materialise, then the filtered draw: tile j row m -> start + 16 j + m + 1
-            ops.gemm_argmax_batch(self.lm_wp, s["xn"], R, t.V, H, 0, 16, self.gws, self.post.view(-1, 16), 0, dyn_t,
+            ops.gemm_argmax_batch(lm, s["xn"], R, t.V, H, 0, 16, self.gws, self.post.view(-1, 16), 0, dyn_t,
                                   nrows_dyn_word=ops.DYN_BS, logits=self._logits)
             ops.sample_rows_nucleus(self._logits[:R], seed=self.seeds, top_k=self.top_k, top_p=self.top_p,
                                     temperature=self.temperature, dyn=dyn_t, nrows_dyn_word=ops.DYN_BS,
                                     pos_word=ops.DYN_POS0, pos_add=1, tiles_per_req=TPR, out=self.post.view(-1, 16))
         elif self.sampler == "device":   # the seeded draw in the lm_head epilogue: tile j row m -> start + 16 j + m + 1
-            ops.gemm_sample_batch(self.lm_wp, s["xn"], R, t.V, H, 0, 16, self.gws, self.post.view(-1, 16), 0, dyn_t,
+            ops.gemm_sample_batch(lm, s["xn"], R, t.V, H, 0, 16, self.gws, self.post.view(-1, 16), 0, dyn_t,
                                   seeds=self.seeds, temperature=self.temperature, pos_word=ops.DYN_POS0, pos_add=1,
                                   tiles_per_req=TPR, nrows_dyn_word=ops.DYN_BS)
         else:
@@ -426,7 +434,7 @@ class BatchedDecoder:
             # one draw over all requests' rows, so the stream differs from R sequential runs)
             if self._logits is None:
                 self._logits = torch.zeros(MT, 16, t.V, dtype=BF16, device=self.dev)
-            ops.gemm_argmax_batch(self.lm_wp, s["xn"], R, t.V, H, 0, 16, self.gws, self.post, 0, dyn_t,
+            ops.gemm_argmax_batch(lm, s["xn"], R, t.V, H, 0, 16, self.gws, self.post, 0, dyn_t,
                                   nrows_dyn_word=ops.DYN_BS, logits=self._logits)
             self.post[:R] = sample(self._logits[:R], self.temperature)
 

@@ -551,6 +551,7 @@ void fill_ring(GemmRArgs &a, const void *wp, const dfl_rows_batch *x, int N, int
 // LDS and vmcnt room for a deeper ring; deeper ones were measured and are not faster (DESIGN.md section 10,
 // profiles/fp8_batch_ab.txt section 5).
 constexpr int W8_A_SILU2 = 3, W8_A_SILU4 = 2, W8_A_ARGMAX2 = 2, W8_A_ARGMAX4 = 2;
+constexpr int W8_A_SAMPLE2 = 2, W8_A_SAMPLE4 = 2;  // (dfl_gemm_sample_batch: A = 2 at both tile counts, both epilogues)
 
 int batch_ksplit(int K) { return (K / 32 + 63) / 64; }
 int mt_of(int R) { return R <= 2 ? 2 : 4; }
@@ -885,6 +886,45 @@ extern "C" int dfl_gemm_sample_batch(const void *wp, const dfl_rows_batch *x, in
   hipLaunchKernelGGL(k_argmax_finish_b, dim3(16, R), dim3(64), 0, st, r.best_val, r.best_idx, gx, mt_of(R), row0, nrows, dyn,
                      nrows_dyn_word, out_ids, out_stride, out_off);
   DFL_CHECK_LAUNCH("dfl_gemm_sample_batch");
+  return DFL_OK;
+}
+
+// ... with an e4m3 lm_head: the W8 ring form with the same two epilogues, the columns' scales on the finished fp32 sums
+// in front of the rounding that the perturbation follows.  Refuses what the ring cannot take (no slab form, no fall-back).
+extern "C" int dfl_gemm_sample_batch_fp8(const void *wp8, const float *wscale, const dfl_rows_batch *x, int R, int V,
+                                         int K, int row0, int nrows, const int32_t *dyn, int nrows_dyn_word, void *ws,
+                                         int64_t *out_ids, int64_t out_stride, int out_off, void *logits,
+                                         int64_t logits_stride, const int64_t *seeds, const float *inv_ts, float inv_t,
+                                         int rng_stream, int pos_word, int pos_add, int tiles_per_req, void *stream) {
+  const char *who = "dfl_gemm_sample_batch_fp8";
+  DFL_REQUIRE(ws && out_ids && dyn && seeds, "dfl_gemm_sample_batch_fp8: null pointer");
+  DFL_REQUIRE(row0 >= 0 && nrows >= 0 && row0 + nrows <= 16, "dfl_gemm_sample_batch_fp8: rows [%d,%d) outside the tile", row0,
+              row0 + nrows);
+  DFL_REQUIRE(inv_ts || (inv_t > 0.f && inv_t <= 1e5f), "dfl_gemm_sample_batch_fp8: inv_t=%g outside (0, 1e5]", (double)inv_t);
+  DFL_REQUIRE(rng_stream == (int)DFL_RNG_TARGET || rng_stream == (int)DFL_RNG_DRAFT,
+              "dfl_gemm_sample_batch_fp8: unknown stream %d", rng_stream);
+  if (!fp8_batch_ok(who, wp8, wscale, x, R, V, K) || !fp8_ring_ok(who, x, K)) return DFL_EINVAL;
+  DFL_REQUIRE(pos_word >= 0 && pos_word < DFL_DYN_WORDS && (tiles_per_req == 1 || tiles_per_req == 2) && R % tiles_per_req == 0,
+              "dfl_gemm_sample_batch_fp8: pos_word=%d / tiles_per_req=%d / R=%d", pos_word, tiles_per_req, R);
+  GemmRArgs r{};
+  const int gx = fill_ring_rows(r, wp8, x, V, K, dyn, row0, nrows, nrows_dyn_word, ws, logits, logits_stride);
+  r.wscale = wscale;
+  r.seeds = seeds;
+  r.inv_t = inv_ts ? 0.f : inv_t;
+  r.inv_ts = inv_ts;
+  r.rng_stream = rng_stream;
+  r.pos_word = pos_word;
+  r.pos_add = pos_add;
+  r.tiles_per_req = tiles_per_req;
+  const hipStream_t st = (hipStream_t)stream;
+  const bool ok = inv_ts ? (R <= 2 ? launch_ring<2, 1, 1, 16, W8_A_SAMPLE2, EPI_SAMPLE_T, true>(who, r, gx, st)
+                                   : launch_ring<4, 1, 1, 16, W8_A_SAMPLE4, EPI_SAMPLE_T, true>(who, r, gx, st))
+                         : (R <= 2 ? launch_ring<2, 1, 1, 16, W8_A_SAMPLE2, EPI_SAMPLE, true>(who, r, gx, st)
+                                   : launch_ring<4, 1, 1, 16, W8_A_SAMPLE4, EPI_SAMPLE, true>(who, r, gx, st));
+  if (!ok) return DFL_ELAUNCH;
+  hipLaunchKernelGGL(k_argmax_finish_b, dim3(16, R), dim3(64), 0, st, r.best_val, r.best_idx, gx, mt_of(R), row0, nrows, dyn,
+                     nrows_dyn_word, out_ids, out_stride, out_off);
+  DFL_CHECK_LAUNCH("dfl_gemm_sample_batch_fp8");
   return DFL_OK;
 }
 

@@ -83,7 +83,7 @@ __global__ __launch_bounds__(NW * 64) void dfl_k_gemm_r(GemmRArgs a) {
   constexpr int SP = (NPIECE + NW - 1) / NW;      // pieces per wave and chunk (surplus: a duplicate of the last piece)
   constexpr int WPC = W8 ? KPC / 2 : KPC;         // weight loads per chunk and tile (W8: one word per k-step pair)
   constexpr int VMC = A * WPC * TPU + (A - 1) * SP;  // VMEM ops of a wave younger than its pieces of the chunk it is about to read
-  static_assert(!W8 || (KPC % 2 == 0 && (EPI == EPI_SILU || EPI == EPI_ARGMAX)), "W8: k-step pairs; SiLU and argmax only");
+  static_assert(!W8 || KPC % 2 == 0, "W8: a wave's share of a chunk is whole k-step pairs");
   static_assert(!W8 || KQ == 1 || MT <= KQ, "W8: a wave finishes at most one (unit, request) item: upp * MT <= NW");
   constexpr bool ARG = EPI == EPI_ARGMAX || EPI == EPI_SAMPLE || EPI == EPI_SAMPLE_T;  // a running (perturbed) argmax per row
   static_assert(EPI == EPI_SILU || ARG, "the ring form has the SiLU epilogue and the three argmax ones");

@@ -624,6 +624,12 @@ __global__ __launch_bounds__(1024) void k_gemm_s(GEMM_HEAD_PARAMS, GemmArgs rest
   gemm_body<1, false, EPI_SAMPLE, NORM>(with_head<false, NORM>(rest, GEMM_HEAD_NAMES), sa);
 }
 
+// ... and its W8 form (dfl_gemm_sample_fp8): the scale on the fp32 sum, the perturbation on bf16(sum * scale)
+template <bool NORM>
+__global__ __launch_bounds__(1024) void k_gemm_s_w8(GEMM_HEAD_PARAMS, GemmArgs rest, SampleArgs sa) {
+  gemm_body<1, false, EPI_SAMPLE, NORM, true>(with_head<false, NORM>(rest, GEMM_HEAD_NAMES), sa);
+}
+
 // the instantiation for this launch's row sources (a normalised source needs the NORM kernels)
 template <int MT, bool CHUNKED, int EPI, bool W8 = false>
 bool launch_gemm(GemmArgs &a, dim3 grid, hipStream_t stream) {
@@ -949,7 +955,7 @@ int gemm_argmax_impl(const void *wp, const dfl_rows *x, int V, int K, int row0, 
                      int nrows_dyn_word, void *ws, int64_t *out_ids, int out_off, void *logits, float *margin_out,
                      hipEvent_t ev0, hipEvent_t ev1, void *stream, const SampleArgs *smp = nullptr,
                      const float *wscale = nullptr, bool w8 = false) {
-  const char *who = w8 ? "dfl_gemm_argmax_fp8" : "dfl_gemm_argmax";
+  const char *who = w8 ? (smp ? "dfl_gemm_sample_fp8" : "dfl_gemm_argmax_fp8") : "dfl_gemm_argmax";
   DFL_REQUIRE(wp && ws && out_ids && (!w8 || wscale), "%s: null pointer", who);
   DFL_REQUIRE(V > 0 && K > 0 && V % 16 == 0 && K % (w8 ? 64 : 32) == 0, "%s: need V%%16==0, K%%%d==0 (V=%d K=%d)", who,
               w8 ? 64 : 32, V, K);
@@ -982,7 +988,12 @@ int gemm_argmax_impl(const void *wp, const dfl_rows *x, int V, int K, int row0, 
     a.gx = gx;
     GemmHead h;
     if (!gemm_head<false>(h, a)) return DFL_EINVAL;
-    if (a.src[0].mode == 2)
+    if (w8) {  // (K % 64 and the scale vector are checked above; nfr is even: whole k-step pairs per wave)
+      if (a.src[0].mode == 2)
+        hipLaunchKernelGGL(k_gemm_s_w8<true>, dim3(gx, 1), dim3(1024), 0, (hipStream_t)stream, GEMM_HEAD_OF(h), a, *smp);
+      else
+        hipLaunchKernelGGL(k_gemm_s_w8<false>, dim3(gx, 1), dim3(1024), 0, (hipStream_t)stream, GEMM_HEAD_OF(h), a, *smp);
+    } else if (a.src[0].mode == 2)
       hipLaunchKernelGGL(k_gemm_s<true>, dim3(gx, 1), dim3(1024), 0, (hipStream_t)stream, GEMM_HEAD_OF(h), a, *smp);
     else
       hipLaunchKernelGGL(k_gemm_s<false>, dim3(gx, 1), dim3(1024), 0, (hipStream_t)stream, GEMM_HEAD_OF(h), a, *smp);
@@ -1026,6 +1037,21 @@ extern "C" int dfl_gemm_sample(const void *wp, const dfl_rows *x, int V, int K, 
   const SampleArgs smp{seed, inv_t, rng_stream, pos_dyn, pos_word, pos_base, pos_add};
   return gemm_argmax_impl(wp, x, V, K, row0, nrows, dyn, nrows_dyn_word, ws, out_ids, out_off, logits, margin_out, nullptr,
                           nullptr, stream, &smp);
+}
+
+extern "C" int dfl_gemm_sample_fp8(const void *wp8, const float *wscale, const dfl_rows *x, int V, int K, int row0, int nrows,
+                                   const int32_t *dyn, int nrows_dyn_word, void *ws, int64_t *out_ids, int out_off,
+                                   void *logits, float *margin_out, uint64_t seed, float inv_t, int rng_stream,
+                                   const int32_t *pos_dyn, int pos_word, int pos_base, int pos_add, void *stream) {
+  DFL_REQUIRE(wp8 && wscale && ws && out_ids, "dfl_gemm_sample_fp8: null pointer");
+  DFL_REQUIRE(inv_t > 0.f && inv_t <= 1e5f, "dfl_gemm_sample_fp8: inv_t=%g outside (0, 1e5]", (double)inv_t);
+  DFL_REQUIRE(rng_stream == (int)DFL_RNG_TARGET || rng_stream == (int)DFL_RNG_DRAFT, "dfl_gemm_sample_fp8: unknown stream %d",
+              rng_stream);
+  DFL_REQUIRE(!pos_dyn || (pos_word >= 0 && pos_word < DFL_DYN_WORDS), "dfl_gemm_sample_fp8: pos_word=%d outside the record",
+              pos_word);
+  const SampleArgs smp{seed, inv_t, rng_stream, pos_dyn, pos_word, pos_base, pos_add};
+  return gemm_argmax_impl(wp8, x, V, K, row0, nrows, dyn, nrows_dyn_word, ws, out_ids, out_off, logits, margin_out, nullptr,
+                          nullptr, stream, &smp, wscale, true);
 }
 
 

@@ -51,7 +51,7 @@ class _DecoderDriver:
         d, m, t = self.dec, self.dec.model, self.dec.target
         return (m._rope[0].data_ptr(), m._rope[1].data_ptr(), t._rope[0].data_ptr(), t._rope[1].data_ptr(),
                 d.lm_wp.data_ptr(), d.lm_wp8.wp.data_ptr() if d.lm_wp8 is not None else 0, d.embed_w.data_ptr(),
-                t.embed.data_ptr())
+                t.embed.data_ptr()) + tuple(x.data_ptr() for x in t.fp8_tensors())   # (an fp8 target's codes and scales)
 
     def admit(self, slot: int, req) -> None:
         p = req.payload

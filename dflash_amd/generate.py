@@ -211,9 +211,13 @@ class DecodeSession:
         self.lm_wp = model.packed_lm_head(target.lm_head) if self.use_draft else None
         if self.native and self.lm_wp is not None:
             target.share_lm_head(self.lm_wp)  # one packed copy serves draft unmask and target posterior
-        # an fp8 draft model: the DRAFT's greedy unmask streams an e4m3 copy of the lm_head (the target keeps the bf16 one)
-        self.lm_wp8 = (model.packed_lm_head_fp8(target.lm_head)
-                       if self.use_draft and getattr(model, "w8", None) is not None else None)
+        # an fp8 draft model: the DRAFT's greedy unmask streams an e4m3 copy of the lm_head — the fp8 target's own codes
+        # where it has them (ONE e4m3 copy serves both), else packed here (a bf16 target keeps its bf16 one)
+        self.lm_wp8 = None
+        if self.use_draft and getattr(model, "w8", None) is not None:
+            self.lm_wp8 = getattr(target, "lm_wp8", None) if self.native else None
+            if self.lm_wp8 is None:
+                self.lm_wp8 = model.packed_lm_head_fp8(target.lm_head)
         self.stop_t = torch.tensor(stop_token_ids, dtype=torch.long, device=dev) if stop_token_ids else None
         # the reference scans the whole buffer, mask slots included (model/dflash.py:265-268)
         self.stop_always = stop_token_ids is not None and mask_token_id in stop_token_ids
@@ -519,7 +523,8 @@ class DecodeSession:
         # not own through another attribute — the RoPE tables, the shared workspaces of draft model and target
         return _Replay(graphs, bound, (m._rope[0].data_ptr(), t._rope[0].data_ptr()),
                        (m._rope, t._rope, getattr(m, "ws", None), getattr(t, "ws", None), getattr(t, "_taps", None),
-                        self.lm_wp, self.lm_wp8, self.embed_w, getattr(t, "lm_wp", None)))
+                        self.lm_wp, self.lm_wp8, self.embed_w, getattr(t, "lm_wp", None),
+                        t.fp8_tensors() if self.native else ()))   # (an fp8 target's codes and scale vectors)
 
     def _tables_moved(self, rec: _Replay) -> bool:
         """A shared draft model / NativeTarget replaces its RoPE table when another caller needs more positions

@@ -81,8 +81,9 @@ class DFlashDraftModel:
         to OCP e4m3 codes with one power-of-two scale per output row (ops.quantize_fp8_rows) — ONE quantised model:
         `self.w` then holds the dequantised values (exact in bf16) for every path without an fp8 kernel, `self.w8` the
         codes, which the draft forward streams at one byte per weight: a single request's block, the ragged batch and
-        the engine.  The target is never quantised, so committed tokens stay the target's own; what the
-        quantisation does to the acceptance length of a trained checkpoint is NOT measured — hence off by default."""
+        the engine.  The draft's format never touches the target, so committed tokens stay the target's
+        own (a target may be quantised on its own: NativeTarget(weight_format=...)); what the quantisation does to the
+        acceptance length of a trained checkpoint is NOT measured — hence off by default."""
         if weight_format not in WEIGHT_FORMATS:
             raise ValueError(f"weight_format must be one of {WEIGHT_FORMATS}, got {weight_format!r}")
         self.weight_format = weight_format

@@ -304,11 +304,19 @@ def gemm_sample(wp, x, V: int, K: int, row0: int, nrows: int, ws, out_ids: torch
                 pos_base: int = 0, pos_add: int = 0, dyn=None, nrows_dyn_word: int = -1,
                 logits: Optional[torch.Tensor] = None, margins: Optional[torch.Tensor] = None) -> None:
     """gemm_argmax with the seeded Gumbel-max draw at `temperature` (dfl_gemm_sample): tile row m draws position
-    (pos_dyn[pos_word] if pos_dyn is given, else pos_base) + pos_add + m."""
+    (pos_dyn[pos_word] if pos_dyn is given, else pos_base) + pos_add + m.  wp: packed bf16, or an Fp8Weight
+    (dfl_gemm_sample_fp8: the draw over bf16(sum * scale))."""
     if logits is not None:
         assert logits.numel() >= 16 * V
     if margins is not None:
         assert margins.numel() >= out_off + nrows
+    if isinstance(wp, Fp8Weight):
+        check(lib().dfl_gemm_sample_fp8(*_fp8(wp, V, K, "wp"), _src(x).ref, V, K, row0, nrows, _p(dyn, I32, "dyn"),
+                                        nrows_dyn_word, _p(ws), _p(out_ids, I64, "out_ids"), out_off,
+                                        _p(logits, BF16, "logits"), _p(margins, F32, "margins"), _seed64(seed),
+                                        inv_temperature(temperature), stream, _p(pos_dyn, I32, "pos_dyn"), pos_word,
+                                        pos_base, pos_add, _stream()), "dfl_gemm_sample_fp8")
+        return
     check(lib().dfl_gemm_sample(_p(wp, BF16, "wp"), _src(x).ref, V, K, row0, nrows, _p(dyn, I32, "dyn"), nrows_dyn_word,
                                 _p(ws), _p(out_ids, I64, "out_ids"), out_off, _p(logits, BF16, "logits"),
                                 _p(margins, F32, "margins"), _seed64(seed), inv_temperature(temperature), stream,
@@ -858,6 +866,13 @@ def gemm_sample_batch(wp, x: BatchRowSource, R: int, V: int, K: int, row0: int, 
         lp, lst = _p(logits, BF16, "logits"), logits.stride(0)
     if inv_ts is not None:
         assert inv_ts.numel() >= mt // tiles_per_req, "inv_ts"
+    if isinstance(wp, Fp8Weight):   # the ring form only, as gemm_argmax_batch's
+        check(lib().dfl_gemm_sample_batch_fp8(*_fp8(wp, V, K, "wp"), x.ref, R, V, K, row0, nrows, _p(dyn, I32, "dyn"),
+                                              nrows_dyn_word, _p(ws), out_ids.data_ptr(), out_ids.stride(0), out_off, lp,
+                                              lst, _p(seeds, I64, "seeds"), _p(inv_ts, F32, "inv_ts"),
+                                              0.0 if inv_ts is not None else inv_temperature(temperature), stream,
+                                              pos_word, pos_add, tiles_per_req, _stream()), "dfl_gemm_sample_batch_fp8")
+        return
     check(lib().dfl_gemm_sample_batch(_p(wp, BF16, "wp"), x.ref, R, V, K, row0, nrows, _p(dyn, I32, "dyn"), nrows_dyn_word,
                                       _p(ws), out_ids.data_ptr(), out_ids.stride(0), out_off, lp, lst,
                                       _p(seeds, I64, "seeds"), _p(inv_ts, F32, "inv_ts"),

@@ -24,7 +24,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import ops
-from .model import _rope_tables
+from .model import WEIGHT_FORMATS, _rope_tables
 from .tile_stack import TileStack, gemm_ws
 from .utils import sample
 
@@ -78,8 +78,18 @@ class _Weight:
 
 class NativeTarget:
     def __init__(self, hf_model, max_splits: int = 32, attn_impl: str = "head", keep_hf: bool = True,
-                 prefill: str = "native"):
-        """attn_impl: "head" = dfl_attn_head on finished bf16 q/k/v rows (round 2, default); "fused" = the
+                 prefill: str = "native", weight_format: str = "bf16"):
+        """weight_format: "bf16" (default), or "fp8_e4m3": every Linear weight of the target — q/k/v, o_proj, gate, up and
+        down of every layer, and the lm_head — is quantised here to OCP e4m3 codes with one power-of-two scale per output
+        row (ops.quantize_fp8_rows; W8A16, weight-only).  The quantised target IS the model: THE CALLER'S hf_model IS
+        MODIFIED — its Linear weights are overwritten in place with q * scale (with tied embeddings the embedding table
+        then holds the dequantised head), so that `target.hf`, prefill="hf", `target.lm_head.weight`, share_lm_head and
+        the native prefill all see the same model.  `self.layers` is the packed bf16 copy of q * scale (every path
+        without an fp8 kernel), `self.layers8` / `self.lm_wp8` the codes, which the verify streams at one byte per
+        weight ("The target").  Norm weights and the embedding gather stay bf16.  What weight-only
+        e4m3 does to a real checkpoint's outputs, or to the acceptance length of a draft trained on the bf16 target, is
+        NOT measured — hence off by default.
+        attn_impl: "head" = dfl_attn_head on finished bf16 q/k/v rows (round 2, default); "fused" = the
         round-1 stage (fp32 K-split partials -> dfl_attn_fused), kept for A/B measurement and as a second
         implementation the tests compare against.
         prefill: "native" (round 3, default where the shapes allow: dense target, projection widths % 128) = the prompt
@@ -98,13 +108,21 @@ class NativeTarget:
         # single-request GEMMs once per 16-row tile (two passes; kept for A/B and as a second implementation for tests)
         self.wide_one_pass = True
         self._wide = None
+        self._wide_seed = None    # int64 [1]: the seed of an fp8 target's sampled wide head (dfl_gemm_sample_batch_fp8)
         self._nuc_logits = None   # bf16 [32, V], made on the first filtered verify (top_k / top_p)
         self.moe_pair_kernel = True   # MoE gate/up at K <= 2048 through dfl_moe_gate_up (False: the general kernel)
         self.moe_shared_pass = True   # three or four tiles (ragged batch, candidates): one pass over the experts they share
         self.moe_shared_min = 2       # tiles from which the shared pass is taken (30B-A3B layer: 2 tiles 291 -> 216 us, 4: 576 -> 241)
         self._moe_sh = None
         cfg = hf_model.config
-        self.check_config(cfg)   # (before anything touches the device: a rejected architecture never launches a kernel)
+        self.check_config(cfg, weight_format)   # (before anything touches the device: a rejected architecture never launches a kernel)
+        self.weight_format = weight_format
+        fp8 = weight_format == "fp8_e4m3"
+        # fp8_e4m3 only: False = the bf16 kernels on the dequantised copy (the second implementation the tests compare)
+        self.fp8_stream = True
+        self.layers8 = [] if fp8 else None   # per layer: ops.Fp8Weight twins of qkv / o / gu / down in self.layers
+        self.lm_wp8 = None                   # the e4m3 lm_head (ops.Fp8Weight)
+        self._tile_layers = {}               # tile_layers(): qkv_parts -> layer dicts with the e4m3 twins
         self.hf = hf_model
         self.model = hf_model.model
         self.lm_head = hf_model.lm_head
@@ -153,13 +171,31 @@ class NativeTarget:
         def w(name):
             return sd[name].detach().to(device=dev, dtype=BF16).contiguous()
 
+        def mat(name, store, key):
+            """A Linear weight: as loaded, or (fp8) its dequantised values q * scale — written back over the wrapped
+            model's own tensor — with the codes and scales kept in `store`."""
+            m = w(name)
+            if not fp8:
+                return m
+            q, sc = ops.quantize_fp8_rows(m)
+            store[key] = (q, sc)
+            m = ops.dequantize_fp8_rows(q, sc)
+            with torch.no_grad():
+                sd[name].copy_(m)   # (the state dict's tensors are the parameters' storage; exact in any float dtype)
+            return m
+
+        if fp8:   # the head first: with tied embeddings self.embed, read below, is then the dequantised head
+            h8 = {}
+            mat("lm_head.weight", h8, "lm")
+            self.lm_wp8 = ops.pack_weight_fp8(*h8.pop("lm"))
         self.layers = []
         for i in range(self.L):
             p = f"model.layers.{i}."
-            qkv = torch.cat([w(p + "self_attn.q_proj.weight"), w(p + "self_attn.k_proj.weight"),
-                             w(p + "self_attn.v_proj.weight")], dim=0)
+            l8 = {}
+            qkv = torch.cat([mat(p + "self_attn.q_proj.weight", l8, "q"), mat(p + "self_attn.k_proj.weight", l8, "k"),
+                             mat(p + "self_attn.v_proj.weight", l8, "v")], dim=0)
             has_qk = (p + "self_attn.q_norm.weight") in sd
-            lw = {"qkv": ops.pack_weight(qkv), "o": ops.pack_weight(w(p + "self_attn.o_proj.weight")),
+            lw = {"qkv": ops.pack_weight(qkv), "o": ops.pack_weight(mat(p + "self_attn.o_proj.weight", l8, "o")),
                   "q_norm": w(p + "self_attn.q_norm.weight") if has_qk else None,
                   "k_norm": w(p + "self_attn.k_norm.weight") if has_qk else None,
                   "ln1": w(p + "input_layernorm.weight"), "ln2": w(p + "post_attention_layernorm.weight")}
@@ -187,10 +223,19 @@ class NativeTarget:
                     lw["router_p"] = lw["router"]
                 del gup, dwn, rw
             else:
-                lw["gu"] = ops.pack_weight_gateup(w(p + "mlp.gate_proj.weight"), w(p + "mlp.up_proj.weight"))
-                lw["down"] = ops.pack_weight(w(p + "mlp.down_proj.weight"))
+                lw["gu"] = ops.pack_weight_gateup(mat(p + "mlp.gate_proj.weight", l8, "gate"),
+                                                  mat(p + "mlp.up_proj.weight", l8, "up"))
+                lw["down"] = ops.pack_weight(mat(p + "mlp.down_proj.weight", l8, "down"))
+            if fp8:
+                if "gate" not in l8:
+                    raise NotImplementedError("NativeTarget: fp8_e4m3 needs dense MLP layers")
+                self.layers8.append({
+                    "qkv": ops.pack_weight_fp8(torch.cat([l8[k][0] for k in "qkv"]), torch.cat([l8[k][1] for k in "qkv"])),
+                    "o": ops.pack_weight_fp8(*l8["o"]),
+                    "gu": ops.pack_weight_gateup_fp8(*l8["gate"], *l8["up"]),
+                    "down": ops.pack_weight_fp8(*l8["down"])})
             self.layers.append(lw)
-            del qkv
+            del qkv, l8
         self.norm = w("model.norm.weight")
         self.embed = w("model.embed_tokens.weight")
         self.lm_wp = None  # set by share_lm_head() or packed on first use
@@ -262,10 +307,14 @@ class NativeTarget:
         torch.cuda.synchronize(dev)
 
     @staticmethod
-    def check_config(cfg) -> None:
+    def check_config(cfg, weight_format: str = "bf16") -> None:
         """Architectures the kernels do not cover are rejected loudly, before any launch (the reference is shape-agnostic:
         model/dflash.py:36,42-56 take head_dim, attention_bias and sliding_window from the config; no BASELINE config
-        needs them): head_dim != 128, biased projections, sliding-window attention layers."""
+        needs them): head_dim != 128, biased projections, sliding-window attention layers.  weight_format: an unknown
+        one is a ValueError; "fp8_e4m3" refuses a sparse-MoE target (the expert kernels have no W8 form) and hidden,
+        intermediate or q widths that are not multiples of 64 (the packed e4m3 layout holds k-step pairs)."""
+        if weight_format not in WEIGHT_FORMATS:
+            raise ValueError(f"NativeTarget: weight_format must be one of {WEIGHT_FORMATS}, got {weight_format!r}")
         n_q = cfg.num_attention_heads
         hd = getattr(cfg, "head_dim", None) or cfg.hidden_size // n_q
         if hd != 128:
@@ -275,6 +324,15 @@ class NativeTarget:
         lt = getattr(cfg, "layer_types", None) or ()
         if any(t == "sliding_attention" for t in lt) and getattr(cfg, "sliding_window", None):
             raise NotImplementedError("NativeTarget: sliding-window attention layers are not supported; keep the HF target")
+        if weight_format == "fp8_e4m3":
+            if getattr(cfg, "num_experts", 0) or getattr(cfg, "num_local_experts", 0):
+                raise NotImplementedError("NativeTarget: fp8_e4m3 weights are not supported for sparse-MoE targets (the "
+                                          "expert kernels have no e4m3 form); use weight_format='bf16'")
+            widths = dict(hidden_size=cfg.hidden_size, intermediate_size=cfg.intermediate_size, q_width=n_q * hd)
+            bad = {k: v for k, v in widths.items() if v % 64}
+            if bad:
+                raise NotImplementedError(f"NativeTarget: fp8_e4m3 weights need hidden, intermediate and q widths % 64 == 0 "
+                                          f"(got {bad})")
 
     # ---- HF-compatible surface (the reference loop can still drive the wrapped model)
     @property
@@ -288,6 +346,44 @@ class NativeTarget:
 
     def share_lm_head(self, packed: torch.Tensor) -> None:
         self.lm_wp = packed
+
+    def streams_fp8(self, bs: int = 16) -> bool:
+        """Whether verify() streams the e4m3 codes for a block of `bs` rows: an fp8 target, fp8_stream, the head
+        attention stage; one 16-row tile with o_proj not fused, or 17..32 rows in one pass (_verify_wide).  Every other
+        path computes the same quantised model from self.layers / self.lm_wp."""
+        if self.layers8 is None or not self.fp8_stream or self.attn_impl != "head" or self.wide_hidden:
+            return False
+        return (not self.fuse_oproj) if bs <= 16 else self.wide_one_pass
+
+    def streams_fp8_tiles(self) -> bool:
+        """The same for the tile-stack paths — _verify_wide, the ragged batch and engine (batch.py; hidden > 4096 runs
+        there as a group of one): gate/up, o_proj, down_proj and the lm_head take the codes, and q/k/v where it leaves K
+        parts; q/k/v as finished rows reads self.layers.  Widths under 256 (toy models) run the
+        bf16 kernels on the dequantised copy: the batch W8 forms refuse K < 256."""
+        return (self.layers8 is not None and self.fp8_stream and self.attn_impl == "head"
+                and min(self.H, self.I, self.q_dim) >= 256)   # (the ring and K-part W8 forms take K >= 256)
+
+    def tile_layers(self, qkv_parts: bool) -> list:
+        """The layer dicts TileStack.run takes: self.layers, with gu / o / down — and qkv, where the caller runs
+        qkv="parts" — replaced by their e4m3 twins when streams_fp8_tiles()."""
+        if not self.streams_fp8_tiles():
+            return self.layers
+        if qkv_parts not in self._tile_layers:
+            keys = ("gu", "o", "down") + (("qkv",) if qkv_parts else ())
+            self._tile_layers[qkv_parts] = [{**lw, **{k: l8[k] for k in keys}} for lw, l8 in zip(self.layers, self.layers8)]
+        return self._tile_layers[qkv_parts]
+
+    def fp8_tensors(self) -> tuple:
+        """Every e4m3 code tensor and scale vector of an fp8 target (empty for bf16): what a captured graph of the verify
+        holds raw pointers to (DecodeSession's keep-alive tuple, the engine's capture key)."""
+        if self.layers8 is None:
+            return ()
+        ws = [w8 for l8 in self.layers8 for w8 in l8.values()] + [self.lm_wp8]
+        return tuple(t for w8 in ws for t in (w8.wp, w8.scale))
+
+    def tile_head(self):
+        """The lm_head of the tile-stack paths: the e4m3 codes when streams_fp8_tiles(), else the packed bf16 copy."""
+        return self.lm_wp8 if self.streams_fp8_tiles() else self.lm_wp
 
     def new_cache(self, max_rows: Optional[int] = None) -> TargetKVCache:
         if max_rows is None:
@@ -561,17 +657,32 @@ class NativeTarget:
                           tau=0, bs=bs, pos0=start, ws=ws["head_ws"], max_splits=self.max_splits, out_frag=ws["attn"],
                           q_tiles=2, out_tile_stride=ws["attn"].stride(0))
 
-        st.run(self.layers, R, dyn2, attend, qkv="rows", taps=None if taps is None else taps.view(2, 16, -1),
-               tap_layers=tap_layers, moe=self.moe_mlp_tiles)
+        st.run(self.tile_layers(qkv_parts=False), R, dyn2, attend, qkv="rows",
+               taps=None if taps is None else taps.view(2, 16, -1), tap_layers=tap_layers, moe=self.moe_mlp_tiles)
         st.finish(self.norm)
         post = ws["post"]
+        if flt is None and temperature >= 1e-5 and seed is not None and self.streams_fp8_tiles():
+            # an fp8 target: the seeded draw in the e4m3 ring head's epilogue (tile j row m -> POS0 + 16 j + m + 1; the
+            # record is rewritten here: verify() rewrites it only when the block size changes, and POS0 must be this
+            # cycle's `start`) — the ids of sample_rows over the same launch's logits
+            ops.set_dyn2(cache.dyn, start, 0, bs, start)
+            if self._wide_seed is None:
+                self._wide_seed = torch.zeros(1, dtype=torch.int64, device=self._dev)
+            self._wide_seed.fill_(ops.seed_i64(seed))
+            ops.gemm_sample_batch(self.lm_wp8, s["xn"], R, self.V, H, 0, 16, gws, post.view(2, 16), 0, dyn2,
+                                  seeds=self._wide_seed, temperature=temperature, pos_word=ops.DYN_POS0, pos_add=1,
+                                  tiles_per_req=2, nrows_dyn_word=ops.DYN_BS,
+                                  logits=None if logits_out is None else logits_out.view(2, 16, self.V))
+            cache.length = start + bs
+            return post[:bs].unsqueeze(0), taps
         logits = logits_out
         if flt is not None and logits is None:
             logits = self._nucleus_logits()
         elif temperature >= 1e-5:
             logits = torch.empty(32, self.V, dtype=BF16, device=self._dev)
-        ops.gemm_argmax_batch(self.lm_wp, s["xn"], R, self.V, H, 0, 16, gws, post.view(2, 16), 0, dyn2,
-                              nrows_dyn_word=ops.DYN_BS, logits=None if logits is None else logits.view(2, 16, self.V))
+        lv = None if logits is None else logits.view(2, 16, self.V)
+        ops.gemm_argmax_batch(self.tile_head(), s["xn"], R, self.V, H, 0, 16, gws, post.view(2, 16), 0, dyn2,
+                              nrows_dyn_word=ops.DYN_BS, logits=lv)
         if flt is not None:   # the filtered draw, host-position form: tile t row m -> start + 16 t + m + 1
             ops.sample_rows_nucleus(logits.view(2, 16, self.V), seed=seed, temperature=temperature, dyn=dyn2,
                                     nrows_dyn_word=ops.DYN_BS, pos_base=start, pos_add=1, tiles_per_req=2,
@@ -657,6 +768,9 @@ class NativeTarget:
                     self._taps[key] = torch.zeros(32, key * H, dtype=BF16, device=self._dev)
                 taps = self._taps[key]
         Ls, src = self.layers, self.src
+        w8 = self.streams_fp8(bs)
+        Lm = self.layers8 if w8 else Ls   # the matrices this verify streams: the layers' own, or their e4m3 twins
+        head = self.lm_wp8 if w8 else self.lm_wp
         if len(tiles) == 2 and self.wide_one_pass and self.attn_impl == "head":
             return self._verify_wide(block_ids, start, cache, bs, tap_layers, taps, logits_out, temperature, cos, sin, seed,
                                      flt)
@@ -666,12 +780,13 @@ class NativeTarget:
         fuse_o = self.fuse_oproj and self.attn_impl == "head" and len(tiles) == 1 and self.q_dim <= 4096
         prev_moe = False   # an MoE layer leaves its successor's input already normalised (frag16 in ws["xn1"])
         for i, lw in enumerate(Ls):
+            lm = Lm[i]
             x1 = src["xn1"] if prev_moe else src["ln1"][i]
             if self.attn_impl == "head":
                 # q/k/v as finished bf16 Linear outputs (no K split: 192 workgroups x 2 column tiles), then
                 # one launch: q/k-norm + RoPE + append + causal attention + split merge
                 for t, dt in tiles:
-                    ops.gemm_resid(lw["qkv"], x1[t], self.nqkv, H, ws["xq"][16 * t:], add_residual=False, dyn=dt)
+                    ops.gemm_resid(lm["qkv"], x1[t], self.nqkv, H, ws["xq"][16 * t:], add_residual=False, dyn=dt)
                 kw = dict(xq=ws["xq"], q_col=0, k_col=self.q_dim, v_col=self.q_dim + self.kv_dim, n_q=self.n_q,
                           n_kv=self.n_kv, q_norm_w=lw["q_norm"], k_norm_w=lw["k_norm"], eps=self.eps, cos_tab=cos,
                           sin_tab=sin, kcache=cache.k[i], vcache=cache.v[i], scale=128 ** -0.5, causal=True,
@@ -694,7 +809,7 @@ class NativeTarget:
                 if not fuse_o:
                     # (an MoE block normalises its rows itself — dfl_moe_router: no partial sums of squares wanted, and
                     # without them a narrow o_proj may run in half tiles on twice the workgroups)
-                    ops.gemm_resid(lw["o"], src["attn"][t], H, self.q_dim, hrow[t], add_residual=True,
+                    ops.gemm_resid(lm["o"], src["attn"][t], H, self.q_dim, hrow[t], add_residual=True,
                                    ss_out=None if "gu_e" in lw else ws["ss_h"][t], dyn=dt)
             # every slot j with tap_layers[j] == i: build_target_layer_ids repeats layers for shallow
             # targets and the reference concatenates the same state twice (model/utils.py:16-25)
@@ -707,12 +822,12 @@ class NativeTarget:
                 if gev is not None:       # bench.py: this layer's gate/up launch between two events on the launch stream
                     gev[1].record()
                 for t, dt in tiles:
-                    ops.gemm_silu_mul(lw["gu"], src["ln2"][i][t], self.I, H, ws["act"][t], dt)
+                    ops.gemm_silu_mul(lm["gu"], src["ln2"][i][t], self.I, H, ws["act"][t], dt)
                 if gev is not None:
                     gev[2].record()
                 for t, dt in tiles:
                     tap = taps[16 * t:16 * t + 16, sl[0] * H:(sl[0] + 1) * H] if sl else None
-                    ops.gemm_resid(lw["down"], src["act"][t], H, self.I, hrow[t], add_residual=True,
+                    ops.gemm_resid(lm["down"], src["act"][t], H, self.I, hrow[t], add_residual=True,
                                    ss_out=ws["ss_h"][t], tap=tap, dyn=dt)
             for j in sl[1:]:
                 taps[:, j * H:(j + 1) * H].copy_(taps[:, sl[0] * H:(sl[0] + 1) * H])
@@ -724,7 +839,7 @@ class NativeTarget:
                 logits = self._nucleus_logits()
             for t, dt in tiles:   # tile t row m predicts position start + 16 t + m + 1, start from the record when replayed
                 n = min(16, bs - 16 * t)
-                ops.gemm_argmax(self.lm_wp, fin[t], self.V, H, 0, n, ws["argmax_ws"], post, 16 * t, dyn=dt,
+                ops.gemm_argmax(head, fin[t], self.V, H, 0, n, ws["argmax_ws"], post, 16 * t, dyn=dt,
                                 logits=logits[16 * t:16 * t + 16])
                 ops.sample_rows_nucleus(logits[16 * t:16 * t + 16], seed=seed, temperature=temperature, nrows=n, dyn=dt,
                                         pos_word=ops.DYN_POS0 if dyn_lengths else -1, pos_base=start, pos_add=16 * t + 1,
@@ -733,7 +848,7 @@ class NativeTarget:
             return post[:bs].unsqueeze(0), taps
         if temperature >= 1e-5 and seed is not None:
             for t, dt in tiles:   # tile t row m predicts position start + 16 t + m + 1
-                ops.gemm_sample(self.lm_wp, fin[t], self.V, H, 0, min(16, bs - 16 * t), ws["argmax_ws"], post, 16 * t,
+                ops.gemm_sample(head, fin[t], self.V, H, 0, min(16, bs - 16 * t), ws["argmax_ws"], post, 16 * t,
                                 seed=seed, temperature=temperature, pos_dyn=dt if dyn_lengths else None,
                                 pos_word=ops.DYN_POS0, pos_base=start, pos_add=16 * t + 1, dyn=dt,
                                 logits=None if logits is None else logits[16 * t:16 * t + 16])
@@ -742,7 +857,7 @@ class NativeTarget:
         if temperature >= 1e-5:
             logits = torch.empty(16 * len(tiles), self.V, dtype=BF16, device=self._dev)
         for t, dt in tiles:
-            ops.gemm_argmax(self.lm_wp, fin[t], self.V, H, 0, min(16, bs - 16 * t), ws["argmax_ws"], post, 16 * t,
+            ops.gemm_argmax(head, fin[t], self.V, H, 0, min(16, bs - 16 * t), ws["argmax_ws"], post, 16 * t,
                             dyn=dt, logits=None if logits is None else logits[16 * t:16 * t + 16])
         if temperature < 1e-5:
             posterior = post[:bs].unsqueeze(0)

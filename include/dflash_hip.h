@@ -186,6 +186,13 @@ int dfl_gemm_silu_mul_fp8(const void *wp_gateup, const float *wscale, const dfl_
 int dfl_gemm_argmax_fp8(const void *wp, const float *wscale, const dfl_rows *x, int V, int K, int row0, int nrows,
                         const int32_t *dyn, int nrows_dyn_word, void *ws, int64_t *out_ids, int out_off, void *logits,
                         float *margin_out, void *ev_start, void *ev_end, void *stream);
+/* dfl_gemm_sample with an e4m3 lm_head: the draw perturbs bf16(sum * scale[n]) — the logit dfl_gemm_argmax_fp8
+ * materialises — so ids, logits and margins are those of the two-step draw over these logits.  Positions, streams and
+ * every other argument as dfl_gemm_sample. */
+int dfl_gemm_sample_fp8(const void *wp8, const float *wscale, const dfl_rows *x, int V, int K, int row0, int nrows,
+                        const int32_t *dyn, int nrows_dyn_word, void *ws, int64_t *out_ids, int out_off, void *logits,
+                        float *margin_out, uint64_t seed, float inv_t, int rng_stream, const int32_t *pos_dyn,
+                        int pos_word, int pos_base, int pos_add, void *stream);
 
 /* h_out[m] = embed[ids[m]] for m < dyn[dyn_word] (model/dflash.py:237) and ss_out[m] =
  * sum of squares of that row (one partial per row: nss = 1 for the next GEMM). */
@@ -598,8 +605,9 @@ int dfl_gemm_sample_batch(const void *wp, const dfl_rows_batch *x, int R, int V,
  * for argument.  The sums are multiplied by the columns' scales in front of the sibling's first rounding: gate and up
  * separately, logits and argmax over bf16(sum * scale), and EVERY K part of dfl_gemm_f32_batch_fp8's output (the launch
  * that sums the parts is untouched).  K % 64 == 0, K >= 256.
- * dfl_gemm_silu_mul_batch_fp8 and dfl_gemm_argmax_batch_fp8 are the ring form and have no slab form: -22 for a source
- * that is not frag16 (mode 0).  Never a quiet fall-back to the bf16 kernels. */
+ * dfl_gemm_silu_mul_batch_fp8, dfl_gemm_argmax_batch_fp8 and dfl_gemm_sample_batch_fp8 are the ring form and have no
+ * slab form: -22 for a source that is not frag16 (mode 0).  Never a quiet fall-back to the bf16 kernels.
+ * dfl_gemm_sample_batch_fp8: both epilogues of dfl_gemm_sample_batch (inv_ts NULL or not) over bf16(sum * scale). */
 int dfl_gemm_f32_batch_fp8(const void *wp8, const float *wscale, const dfl_rows_batch *x, int R, int N, int K, float *out,
                            const int32_t *dyn, void *stream);
 int dfl_gemm_silu_mul_batch_fp8(const void *wp8_gateup, const float *wscale, const dfl_rows_batch *x, int R, int I, int K,
@@ -607,6 +615,11 @@ int dfl_gemm_silu_mul_batch_fp8(const void *wp8_gateup, const float *wscale, con
 int dfl_gemm_argmax_batch_fp8(const void *wp8, const float *wscale, const dfl_rows_batch *x, int R, int V, int K, int row0,
                               int nrows, const int32_t *dyn, int nrows_dyn_word, void *ws, int64_t *out_ids,
                               int64_t out_stride, int out_off, void *logits, int64_t logits_stride, void *stream);
+int dfl_gemm_sample_batch_fp8(const void *wp8, const float *wscale, const dfl_rows_batch *x, int R, int V, int K, int row0,
+                              int nrows, const int32_t *dyn, int nrows_dyn_word, void *ws, int64_t *out_ids,
+                              int64_t out_stride, int out_off, void *logits, int64_t logits_stride, const int64_t *seeds,
+                              const float *inv_ts, float inv_t, int rng_stream, int pos_word, int pos_add,
+                              int tiles_per_req, void *stream);
 /* dfl_embed_rows for R requests: ids[r * ids_stride + m]. */
 int dfl_embed_rows_batch(const void *embed, const int64_t *ids, int64_t ids_stride, int R, void *h_out,
                          int64_t h_stride, int H, float *ss_out, int64_t ss_stride, const int32_t *dyn, int dyn_word,
