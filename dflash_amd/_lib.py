@@ -83,6 +83,9 @@ SIGNATURES = {
     "dfl_gemm_silu_mul_experts": (_i, [_p, _i64, _r, _i, _i, _i, _p, _i64, _p, _p, _p, _p]),
     "dfl_moe_gate_up": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _p, _i, _p]),
     "dfl_moe_down": (_i, [_p, _i64, _p, _i64, _p, _p, _p, _i, _i, _i, _i, _p, _p]),
+    # the two expert launches on e4m3 codes: the scale vector follows the packed weight (and its stride)
+    "dfl_moe_gate_up_fp8": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _i, _p]),
+    "dfl_moe_down_fp8": (_i, [_p, _i64, _p, _p, _i64, _p, _p, _p, _i, _i, _i, _i, _p, _p]),
     "dfl_argmax": (_i, [_p, _i, _i, _i64, _p, _p]),
     "dfl_accept_commit": (_i, [_p, _p, _i, _p, _i64, _p, _p, _i, _p, _p, _i, _i64, _p, _p]),
     # ---- target prefill

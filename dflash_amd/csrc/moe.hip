@@ -15,6 +15,7 @@
 #include "moe_route.h"
 #include <limits.h>
 #include <stdlib.h>
+#include <type_traits>
 
 namespace {
 
@@ -342,12 +343,24 @@ struct MoeDownArgs {
   float *out;           // [nsplit][16][ldo]
   int ldo;
 };
+// W8: wd holds e4m3 codes ([E][ntiles][KSe/2][64 lanes][16 B], gemm_rows.h; wd_stride in 16-byte units all the same) and
+// wscale [E][16 ntiles] the fp32 scale of every output column.  A struct of its own, so that the bf16 kernels' launch
+// arguments — and with them their instruction streams — stay as they were.
+struct MoeDownArgs8 : MoeDownArgs {
+  const float *wscale;
+};
 
 // CT: column tiles per workgroup.  With CT = 1 every workgroup re-reads every expert's activations (24 KB per expert
 // at I = 768: as many bytes from L2 as weight bytes from HBM); CT = 2 shares an item's activation fragments between two
 // column tiles.
-template <int CT, int NW>
-__global__ __launch_bounds__(NW * 64) void k_moe_down(MoeDownArgs a) {
+// W8 (dfl_moe_down_fp8): the item's 4 k-steps of a column tile arrive as TWO 16-byte loads of codes that stay in
+// flight as they are (half the registers per buffer) and are converted right in front of each MFMA (w8_frag); the
+// same k-steps in the same order as the bf16 form, so with power-of-two scales the launch is bit-equal to the bf16
+// one on q * scale.  The four scales of the lane's columns (MFMA D layout: 4 (L >> 4) .. + 3) are one 16-byte vector
+// load requested WITH the item, in front of its weights — a wave's loads return in order, so it lands first and no wave
+// waits for it behind weights; a scalar load in consume() would be a dependent round trip per item.
+template <int CT, int NW, bool W8>
+__global__ __launch_bounds__(NW * 64) void k_moe_down(std::conditional_t<W8, MoeDownArgs8, MoeDownArgs> a) {
   __shared__ float red[NW][CT][256];
   const int tid = threadIdx.x;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6), l = tid & 63;
@@ -364,12 +377,14 @@ __global__ __launch_bounds__(NW * 64) void k_moe_down(MoeDownArgs a) {
   f32x4 total[CT];
 #pragma unroll
   for (int c = 0; c < CT; ++c) total[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  bf16x8 wA[CT][4], xA[4], wB[CT][4], xB[4];
+  constexpr int WR = W8 ? 2 : 4;  // weight registers (16 bytes each) per column tile of an item
+  bf16x8 wA[CT][WR], xA[4], wB[CT][WR], xB[4];
   bf16_t rA = 0, rB = 0;  // (kept as loaded: converting at the load would make the wave wait for it there)
+  f32x4 sA[W8 ? CT : 1], sB[W8 ? CT : 1];  // W8: the scales of the lane's four columns of each tile
   // Every request in the loop is UNCONDITIONAL — past the wave's last item a dummy (empty descriptors: zeros, no
   // traffic): behind `if (more) issue` hipcc cannot count the loads in flight and waits vmcnt(0) before the MFMAs of
   // the current item, i.e. for the item it has just requested.
-  auto issue = [&](bf16x8(&wv)[CT][4], bf16x8(&xv)[4], bf16_t &wr, int it) {
+  auto issue = [&](bf16x8(&wv)[CT][WR], bf16x8(&xv)[4], bf16_t &wr, f32x4(&sc)[W8 ? CT : 1], int it) {
     const bool live = it < nitems;
     it = live ? it : nitems - 1;
     const int e = a.list[p0 + it / cpe], ks0 = (it % cpe) * 4;
@@ -377,33 +392,46 @@ __global__ __launch_bounds__(NW * 64) void k_moe_down(MoeDownArgs a) {
     // (scalar: a clamp compiled to v_med3 puts the buffer descriptors in VGPRs and every load into a waterfall loop)
     nf = __builtin_amdgcn_readfirstlane(live ? (nf > 4 ? 4 : nf) : 0);
     wr = a.wt[(int64_t)(l & 15) * a.E + e];  // the routing weight of this lane's row; first: loads return in order
+    if constexpr (W8) {
+#pragma unroll
+      for (int c = 0; c < CT; ++c)
+        sc[c] = *reinterpret_cast<const f32x4 *>(a.wscale + ((int64_t)e * a.ntiles + t0 + c) * 16 + 4 * (l >> 4));
+    }
     load_ksteps<4, 0>(xv, a.act + e * a.act_stride + (size_t)ks0 * 64, nf, l);  // re-read by every column group: L2
 #pragma unroll
-    for (int c = 0; c < CT; ++c)
-      load_ksteps<4>(wv[c], a.wd + e * a.wd_stride + ((size_t)(t0 + c) * a.KSe + ks0) * 64, nf, l);  // past nf: zero fragments
+    for (int c = 0; c < CT; ++c) {
+      if constexpr (W8)  // (KSe and ks0 even: k-step pairs)
+        load_ksteps_w8<4>(wv[c], a.wd + e * a.wd_stride + ((size_t)(t0 + c) * (a.KSe >> 1) + (ks0 >> 1)) * 64, nf, l);
+      else
+        load_ksteps<4>(wv[c], a.wd + e * a.wd_stride + ((size_t)(t0 + c) * a.KSe + ks0) * 64, nf, l);  // past nf: zero fragments
+    }
   };
-  auto consume = [&](const bf16x8(&wv)[CT][4], const bf16x8(&xv)[4], bf16_t wraw) {
+  auto consume = [&](const bf16x8(&wv)[CT][WR], const bf16x8(&xv)[4], bf16_t wraw, const f32x4(&sc)[W8 ? CT : 1]) {
     const float wr = bf2f(wraw);
 #pragma unroll
     for (int c = 0; c < CT; ++c) {
       f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int f = 0; f < 4; ++f) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wv[c][f], xv[f], acc, 0, 0, 0);
+      for (int f = 0; f < 4; ++f)
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(weight_frag<W8, WR>(wv[c], f), xv[f], acc, 0, 0, 0);
       // D layout: lane L, register r = output column 4 (L >> 4) + r of row L & 15
-      total[c] += acc * wr;
+      if constexpr (W8)  // the scale on the product FIRST (exact for a power of two): `x * wr` then meets the running sum
+        total[c] += (acc * sc[c]) * wr;  // exactly as in the bf16 form, whether or not hipcc contracts it into an fma
+      else
+        total[c] += acc * wr;
     }
   };
   int it = w;
   if (it < nitems) {
-    issue(wA, xA, rA, it);
+    issue(wA, xA, rA, sA, it);
     for (; it < nitems; it += 2 * NW) {
-      issue(wB, xB, rB, it + NW);
+      issue(wB, xB, rB, sB, it + NW);
       __builtin_amdgcn_sched_barrier(0);  // (or hipcc sinks the requests below the current item's waits and MFMAs)
-      consume(wA, xA, rA);
+      consume(wA, xA, rA, sA);
       __builtin_amdgcn_sched_barrier(0);
-      issue(wA, xA, rA, it + 2 * NW);
+      issue(wA, xA, rA, sA, it + 2 * NW);
       __builtin_amdgcn_sched_barrier(0);
-      if (it + NW < nitems) consume(wB, xB, rB);
+      if (it + NW < nitems) consume(wB, xB, rB, sB);
       __builtin_amdgcn_sched_barrier(0);
     }
   }
@@ -434,42 +462,66 @@ struct MoeGuArgs {
   int KS, npp;           // K / 32 (<= 64), I / 16
   bf16_t *act;           // [E][16 * I] frag16 per expert
 };
+// W8: wp holds e4m3 codes, [E][2*npp tiles][KS/2][64 lanes][16 B] (gemm_rows.h), wscale [E][2*npp][16] the fp32 scale of
+// every gate / up row in that tile order.  (A struct of its own: the bf16 kernel's launch arguments stay as they were.)
+struct MoeGuArgs8 : MoeGuArgs {
+  const float *wscale;
+};
 
-__global__ __launch_bounds__(1024) void k_moe_gate_up(MoeGuArgs a) {
+// W8 (dfl_moe_gate_up_fp8): a wave's 4 k-steps of the gate tile and of the up tile arrive as 2 + 2 16-byte loads of
+// codes, kept raw in flight (half the registers per buffer) and converted in front of each MFMA; same k-steps per wave,
+// same order, so with power-of-two scales the launch is bit-equal to the bf16 one on q * scale.  The scales: every
+// lane requests the two of column l & 15 (gate, up) WITH the item and IN FRONT of its weights — loads return in order,
+// so they land first and cost no wait; the finishing thread (row tid >> 4, column tid & 15 = l & 15) then has its own
+// pair in registers at the epilogue.  A scalar load (tile_scales) would have to be issued per item behind the dependent
+// scalar load of the expert list and be selected 16 ways per thread; requested in the epilogue it is a round trip per
+// item at the launch's tail.
+template <bool W8>
+__global__ __launch_bounds__(1024) void k_moe_gate_up(std::conditional_t<W8, MoeGuArgs8, MoeGuArgs> a) {
   __shared__ float red[2][16][2][256];
   const int tid = threadIdx.x;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6), l = tid & 63;
   int nfw = a.KS - 4 * w;
   nfw = __builtin_amdgcn_readfirstlane(nfw < 0 ? 0 : (nfw > 4 ? 4 : nfw));
   const int nitems = a.n_active[0] * a.npp;
-  const int64_t tile = (int64_t)a.KS * 64, expert = 2 * a.npp * tile;   // bf16x8 units
-  bf16x8 gA[4], uA[4], gB[4], uB[4], xr[4];
+  constexpr int WR = W8 ? 2 : 4;  // weight registers (16 bytes each) per tile of an item
+  const int64_t tile = (int64_t)(W8 ? a.KS >> 1 : a.KS) * 64, expert = 2 * a.npp * tile;   // 16-byte units
+  bf16x8 gA[WR], uA[WR], gB[WR], uB[WR], xr[4];
+  float sgA = 0.f, suA = 0.f, sgB = 0.f, suB = 0.f;  // W8: the scales of this lane's gate / up column
   // (every request unconditional, a dummy past the end: see k_moe_down)
-  auto issue = [&](bf16x8(&g)[4], bf16x8(&u)[4], int it) {
+  auto issue = [&](bf16x8(&g)[WR], bf16x8(&u)[WR], float &sg, float &su, int it) {
     const bool live = it < nitems;
     it = live ? it : nitems - 1;
     const int e = a.list[it / a.npp], p = it % a.npp;
-    const bf16x8 *base = a.wp + e * expert + 2 * p * tile + 4 * w * 64;
+    const bf16x8 *base = a.wp + e * expert + 2 * p * tile + WR * w * 64;
     const int nf = __builtin_amdgcn_readfirstlane(live ? nfw : 0);
-    load_ksteps<4>(g, base, nf, l);
-    load_ksteps<4>(u, base + tile, nf, l);
+    if constexpr (W8) {
+      const float *sp = a.wscale + ((int64_t)e * a.npp + p) * 32 + (l & 15);
+      sg = sp[0];
+      su = sp[16];
+      load_ksteps_w8<4>(g, base, nf, l);
+      load_ksteps_w8<4>(u, base + tile, nf, l);
+    } else {
+      load_ksteps<4>(g, base, nf, l);
+      load_ksteps<4>(u, base + tile, nf, l);
+    }
   };
   int it = blockIdx.x;
   if (it >= nitems) return;
   load_ksteps<4, 0>(xr, a.xfrag + 4 * w * 64, nfw, l);   // activations first: a wave's loads return in issue order
-  issue(gA, uA, it);
+  issue(gA, uA, sgA, suA, it);
   const int nv = (a.dyn && a.valid_word >= 0) ? a.dyn[a.valid_word] : 16;
   if ((l & 15) >= nv) {
 #pragma unroll
     for (int f = 0; f < 4; ++f) xr[f] = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
   }
   int pos = 0;
-  auto consume = [&](const bf16x8(&g)[4], const bf16x8(&u)[4], int itc) {
+  auto consume = [&](const bf16x8(&g)[WR], const bf16x8(&u)[WR], float scg, float scu, int itc) {
     f32x4 ag = {0.f, 0.f, 0.f, 0.f}, au = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int f = 0; f < 4; ++f) ag = __builtin_amdgcn_mfma_f32_16x16x32_bf16(g[f], xr[f], ag, 0, 0, 0);
+    for (int f = 0; f < 4; ++f) ag = __builtin_amdgcn_mfma_f32_16x16x32_bf16(weight_frag<W8, WR>(g, f), xr[f], ag, 0, 0, 0);
 #pragma unroll
-    for (int f = 0; f < 4; ++f) au = __builtin_amdgcn_mfma_f32_16x16x32_bf16(u[f], xr[f], au, 0, 0, 0);
+    for (int f = 0; f < 4; ++f) au = __builtin_amdgcn_mfma_f32_16x16x32_bf16(weight_frag<W8, WR>(u, f), xr[f], au, 0, 0, 0);
     const int buf = pos & 1;
     ++pos;
     *reinterpret_cast<f32x4 *>(&red[buf][w][0][l * 4]) = ag;
@@ -484,6 +536,10 @@ __global__ __launch_bounds__(1024) void k_moe_gate_up(MoeGuArgs a) {
         sg += red[buf][ww][0][idx];
         su += red[buf][ww][1][idx];
       }
+      if constexpr (W8) {  // the rows' scales on the fp32 K-sums, in front of the rounding point
+        sg *= scg;
+        su *= scu;
+      }
       const float gb = rbf(sg), ub = rbf(su);   // the Linears' bf16 outputs
       const float act = rbf(gb / (1.f + __expf(-gb)));
       const int e = a.list[itc / a.npp], n = (itc % a.npp) * 16 + nl;
@@ -492,26 +548,38 @@ __global__ __launch_bounds__(1024) void k_moe_gate_up(MoeGuArgs a) {
   };
   const int G = gridDim.x;
   for (; it < nitems; it += 2 * G) {
-    issue(gB, uB, it + G);
+    issue(gB, uB, sgB, suB, it + G);
     __builtin_amdgcn_sched_barrier(0);
-    consume(gA, uA, it);
+    consume(gA, uA, sgA, suA, it);
     __builtin_amdgcn_sched_barrier(0);
-    issue(gA, uA, it + 2 * G);
+    issue(gA, uA, sgA, suA, it + 2 * G);
     __builtin_amdgcn_sched_barrier(0);
-    if (it + G < nitems) consume(gB, uB, it + G);
+    if (it + G < nitems) consume(gB, uB, sgB, suB, it + G);
     __builtin_amdgcn_sched_barrier(0);
   }
 }
 
 }  // namespace
 
-extern "C" int dfl_moe_gate_up(const void *wp_gateup, const void *x_frag, int E, int I, int K, void *act_frag,
-                               const int32_t *list, const int32_t *n_active, const int32_t *dyn, int valid_word,
-                               void *stream) {
-  DFL_REQUIRE(wp_gateup && x_frag && act_frag && list && n_active, "dfl_moe_gate_up: null pointer");
+namespace {
+// 64-byte alignment of a scale vector: a tile's 16 scales are one aligned line (gemm_rows.h, tile_scales' contract;
+// the expert kernels read them by 4- and 16-byte vector loads)
+inline bool scales_aligned(const float *p) { return ((uintptr_t)p & 63) == 0; }
+
+template <bool W8>
+int moe_gate_up_impl(const char *who, const void *wp_gateup, const float *wscale, const void *x_frag, int E, int I, int K,
+                     void *act_frag, const int32_t *list, const int32_t *n_active, const int32_t *dyn, int valid_word,
+                     void *stream) {
+  DFL_REQUIRE(wp_gateup && x_frag && act_frag && list && n_active, "%s: null pointer", who);
   DFL_REQUIRE(E >= 1 && E <= 1024 && I > 0 && I % 16 == 0 && K > 0 && K % 32 == 0 && K <= 2048,
-              "dfl_moe_gate_up: E=%d I=%d K=%d outside range (K <= 2048; larger K: dfl_gemm_silu_mul_experts)", E, I, K);
-  MoeGuArgs a{};
+              "%s: E=%d I=%d K=%d outside range (K <= 2048; larger K: dfl_gemm_silu_mul_experts)", who, E, I, K);
+  std::conditional_t<W8, MoeGuArgs8, MoeGuArgs> a{};
+  if constexpr (W8) {
+    DFL_REQUIRE(K % 64 == 0, "%s: K=%d is not a multiple of 64 (the e4m3 layout holds k-step pairs)", who, K);
+    DFL_REQUIRE(wscale, "%s: null scale vector", who);
+    DFL_REQUIRE(scales_aligned(wscale), "%s: the scale vector must be 64-byte aligned", who);
+    a.wscale = wscale;
+  }
   a.wp = (const bf16x8 *)wp_gateup;
   a.xfrag = (const bf16x8 *)x_frag;
   a.list = list;
@@ -521,9 +589,24 @@ extern "C" int dfl_moe_gate_up(const void *wp_gateup, const void *x_frag, int E,
   a.KS = K / 32;
   a.npp = I / 16;
   a.act = (bf16_t *)act_frag;
-  hipLaunchKernelGGL(k_moe_gate_up, dim3(256), dim3(1024), 0, (hipStream_t)stream, a);
-  DFL_CHECK_LAUNCH("dfl_moe_gate_up");
+  hipLaunchKernelGGL(k_moe_gate_up<W8>, dim3(256), dim3(1024), 0, (hipStream_t)stream, a);
+  DFL_CHECK_LAUNCH(who);
   return DFL_OK;
+}
+}  // namespace
+
+extern "C" int dfl_moe_gate_up(const void *wp_gateup, const void *x_frag, int E, int I, int K, void *act_frag,
+                               const int32_t *list, const int32_t *n_active, const int32_t *dyn, int valid_word,
+                               void *stream) {
+  return moe_gate_up_impl<false>("dfl_moe_gate_up", wp_gateup, nullptr, x_frag, E, I, K, act_frag, list, n_active, dyn,
+                                 valid_word, stream);
+}
+
+extern "C" int dfl_moe_gate_up_fp8(const void *wp8_gateup, const float *wscale, const void *x_frag, int E, int I, int K,
+                                   void *act_frag, const int32_t *list, const int32_t *n_active, const int32_t *dyn,
+                                   int valid_word, void *stream) {
+  return moe_gate_up_impl<true>("dfl_moe_gate_up_fp8", wp8_gateup, wscale, x_frag, E, I, K, act_frag, list, n_active, dyn,
+                                valid_word, stream);
 }
 
 extern "C" int dfl_moe_route(const void *logits, int ld, int E, int top_k, int norm_topk, void *wt, int32_t *active,
@@ -590,17 +673,27 @@ extern "C" int dfl_debug_read_router_stamps(unsigned long long *host_out) {
 }
 #endif
 
-extern "C" int dfl_moe_down(const void *wp_down, int64_t wp_expert_stride, const void *act_frag, int64_t act_expert_stride,
-                            const void *wt, const int32_t *list, const int32_t *n_active, int E, int N, int I, int nsplit,
-                            float *out, void *stream) {
-  DFL_REQUIRE(wp_down && act_frag && wt && list && n_active && out, "dfl_moe_down: null pointer");
-  DFL_REQUIRE(E >= 1 && N > 0 && I > 0 && N % 16 == 0 && I % 32 == 0 && nsplit >= 1 && nsplit <= 16, "dfl_moe_down: bad shape");
-  DFL_REQUIRE(wp_expert_stride >= (int64_t)N * I && wp_expert_stride % 8 == 0 && act_expert_stride >= (int64_t)16 * I &&
+namespace {
+// wp_expert_stride: bf16 elements (bf16) or bytes of codes (W8) between experts — 16-byte units either way once divided
+template <bool W8>
+int moe_down_impl(const char *who, const void *wp_down, int64_t wp_expert_stride, const float *wscale, const void *act_frag,
+                  int64_t act_expert_stride, const void *wt, const int32_t *list, const int32_t *n_active, int E, int N,
+                  int I, int nsplit, float *out, void *stream) {
+  DFL_REQUIRE(wp_down && act_frag && wt && list && n_active && out, "%s: null pointer", who);
+  DFL_REQUIRE(E >= 1 && N > 0 && I > 0 && N % 16 == 0 && I % 32 == 0 && nsplit >= 1 && nsplit <= 16, "%s: bad shape", who);
+  constexpr int UNIT = W8 ? 16 : 8;  // stride units per 16 bytes
+  DFL_REQUIRE(wp_expert_stride >= (int64_t)N * I && wp_expert_stride % UNIT == 0 && act_expert_stride >= (int64_t)16 * I &&
                   act_expert_stride % 8 == 0,
-              "dfl_moe_down: expert strides too short");
-  MoeDownArgs a{};
+              "%s: expert strides too short", who);
+  std::conditional_t<W8, MoeDownArgs8, MoeDownArgs> a{};
+  if constexpr (W8) {
+    DFL_REQUIRE(I % 64 == 0, "%s: I=%d is not a multiple of 64 (the e4m3 layout holds k-step pairs)", who, I);
+    DFL_REQUIRE(wscale, "%s: null scale vector", who);
+    DFL_REQUIRE(scales_aligned(wscale), "%s: the scale vector must be 64-byte aligned", who);
+    a.wscale = wscale;
+  }
   a.wd = (const bf16x8 *)wp_down;
-  a.wd_stride = wp_expert_stride / 8;
+  a.wd_stride = wp_expert_stride / UNIT;
   a.act = (const bf16x8 *)act_frag;
   a.act_stride = act_expert_stride / 8;
   a.wt = (const bf16_t *)wt;
@@ -616,9 +709,24 @@ extern "C" int dfl_moe_down(const void *wp_down, int64_t wp_expert_stride, const
   // (same box, BASELINE configs[4]'s cycle: one tile 6.44 - 6.45 ms, two 6.34, four tiles on 8 waves 6.37 - 6.38:
   // profiles/r4_moe_router_ab.txt)
   if (N % 32 == 0)
-    hipLaunchKernelGGL((k_moe_down<2, 16>), dim3(N / 32, nsplit), dim3(1024), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL((k_moe_down<2, 16, W8>), dim3(N / 32, nsplit), dim3(1024), 0, (hipStream_t)stream, a);
   else
-    hipLaunchKernelGGL((k_moe_down<1, 16>), dim3(N / 16, nsplit), dim3(1024), 0, (hipStream_t)stream, a);
-  DFL_CHECK_LAUNCH("dfl_moe_down");
+    hipLaunchKernelGGL((k_moe_down<1, 16, W8>), dim3(N / 16, nsplit), dim3(1024), 0, (hipStream_t)stream, a);
+  DFL_CHECK_LAUNCH(who);
   return DFL_OK;
+}
+}  // namespace
+
+extern "C" int dfl_moe_down(const void *wp_down, int64_t wp_expert_stride, const void *act_frag, int64_t act_expert_stride,
+                            const void *wt, const int32_t *list, const int32_t *n_active, int E, int N, int I, int nsplit,
+                            float *out, void *stream) {
+  return moe_down_impl<false>("dfl_moe_down", wp_down, wp_expert_stride, nullptr, act_frag, act_expert_stride, wt, list,
+                              n_active, E, N, I, nsplit, out, stream);
+}
+
+extern "C" int dfl_moe_down_fp8(const void *wp8_down, int64_t wp_expert_stride, const float *wscale, const void *act_frag,
+                                int64_t act_expert_stride, const void *wt, const int32_t *list, const int32_t *n_active,
+                                int E, int N, int I, int nsplit, float *out, void *stream) {
+  return moe_down_impl<true>("dfl_moe_down_fp8", wp8_down, wp_expert_stride, wscale, act_frag, act_expert_stride, wt, list,
+                             n_active, E, N, I, nsplit, out, stream);
 }

@@ -136,6 +136,35 @@ def pack_weight_gateup_fp8(gate_q: torch.Tensor, gate_scale: torch.Tensor, up_q:
     return Fp8Weight(out, sc.reshape(-1).to(gate_q.device).contiguous(), 2 * i, k)
 
 
+class Fp8Experts(NamedTuple):
+    """One MoE layer's expert weights of one kind as e4m3 codes (pack_experts_fp8): expert e's packed codes in row e.
+    moe_gate_up / moe_down take one in place of the packed bf16 [E, .] tensor."""
+    wp: torch.Tensor      # uint8 [E, N * K]: per expert pack_weight_gateup_fp8's (gate/up, N = 2I) or pack_weight_fp8's layout
+    scale: torch.Tensor   # fp32 [E, N], in that layout's tile order
+    E: int
+    N: int                # output rows per expert: 2 * I (gate/up) or the hidden width (down)
+    K: int
+
+
+def pack_experts_fp8(q: torch.Tensor, scale: torch.Tensor, gateup: bool) -> Fp8Experts:
+    """q uint8 [E, N, K] codes and scale fp32 [E, N] (quantize_fp8_rows of the [E * N, K] view) -> Fp8Experts.
+    gateup: N = 2I with rows 0 .. I-1 the gate and I .. 2I-1 the up projection (HF's fused gate_up_proj), packed with
+    their tiles interleaved; else a plain [N, K] weight per expert (down_proj).  One expert at a time, as the bf16 path."""
+    e, n, k = q.shape
+    assert scale.shape == (e, n) and q.dtype == U8
+    wp = torch.empty(e, n * k, dtype=U8, device=q.device)
+    sc = torch.empty(e, n, dtype=F32, device=q.device)
+    for j in range(e):
+        if gateup:
+            i = n // 2
+            w8 = pack_weight_gateup_fp8(q[j, :i].contiguous(), scale[j, :i], q[j, i:].contiguous(), scale[j, i:])
+        else:
+            w8 = pack_weight_fp8(q[j].contiguous(), scale[j])
+        wp[j].copy_(w8.wp)
+        sc[j].copy_(w8.scale)
+    return Fp8Experts(wp, sc, e, n, k)
+
+
 def _fp8(wp: Fp8Weight, N: int, K: int, name: str):
     if (wp.N, wp.K) != (N, K):
         raise ValueError(f"dflash_amd: {name} is an fp8 weight of {wp.N} x {wp.K}, the launch asks for {N} x {K}")
@@ -680,7 +709,18 @@ def gemm_silu_mul_experts(wp_gu: torch.Tensor, x, E: int, I: int, K: int, act: t
 
 def moe_gate_up(wp_gu: torch.Tensor, x_frag: torch.Tensor, E: int, I: int, K: int, act: torch.Tensor, lst: torch.Tensor,
                 n_active: torch.Tensor, dyn=None, valid_word: int = -1) -> None:
-    """gemm_silu_mul_experts for K <= 2048 from frag16 rows: one LDS meeting per (gate, up) tile pair."""
+    """gemm_silu_mul_experts for K <= 2048 from frag16 rows: one LDS meeting per (gate, up) tile pair.  wp_gu: packed
+    bf16 [E, 2*I*K], or an Fp8Experts (dfl_moe_gate_up_fp8)."""
+    assert act.dim() == 2 and act.is_contiguous() and act.shape[1] == 16 * I and x_frag.numel() >= 16 * K
+    if isinstance(wp_gu, Fp8Experts):
+        if (wp_gu.E, wp_gu.N, wp_gu.K) != (E, 2 * I, K):
+            raise ValueError(f"dflash_amd: wp_gu holds fp8 experts of {wp_gu.E} x {wp_gu.N} x {wp_gu.K}, the launch asks "
+                             f"for {E} x {2 * I} x {K}")
+        check(lib().dfl_moe_gate_up_fp8(_p(wp_gu.wp, U8, "wp_gu"), _p(wp_gu.scale, F32, "wp_gu.scale"),
+                                        _p(x_frag, BF16, "x_frag"), E, I, K, _p(act, BF16, "act"), _p(lst, I32, "list"),
+                                        _p(n_active, I32, "n_active"), _p(dyn, I32, "dyn"), valid_word, _stream()),
+              "dfl_moe_gate_up_fp8")
+        return
     assert wp_gu.dim() == 2 and wp_gu.is_contiguous() and wp_gu.shape[1] == 2 * I * K
     assert act.dim() == 2 and act.is_contiguous() and act.shape[1] == 16 * I and x_frag.numel() >= 16 * K
     check(lib().dfl_moe_gate_up(_p(wp_gu, BF16, "wp_gu"), _p(x_frag, BF16, "x_frag"), E, I, K, _p(act, BF16, "act"),
@@ -690,9 +730,19 @@ def moe_gate_up(wp_gu: torch.Tensor, x_frag: torch.Tensor, E: int, I: int, K: in
 
 def moe_down(wp_down: torch.Tensor, act: torch.Tensor, wt: torch.Tensor, lst: torch.Tensor, n_active: torch.Tensor, E: int,
              N: int, I: int, nsplit: int, out: torch.Tensor) -> None:
-    """wp_down bf16 [E, N*I] packed per expert; out fp32 [nsplit, 16, N]."""
-    assert wp_down.dim() == 2 and wp_down.is_contiguous() and act.dim() == 2 and act.is_contiguous()
+    """wp_down bf16 [E, N*I] packed per expert, or an Fp8Experts (dfl_moe_down_fp8); out fp32 [nsplit, 16, N]."""
+    assert act.dim() == 2 and act.is_contiguous()
     assert out.dtype == F32 and out.is_contiguous() and out.numel() >= nsplit * 16 * N
+    if isinstance(wp_down, Fp8Experts):
+        if (wp_down.E, wp_down.N, wp_down.K) != (E, N, I):
+            raise ValueError(f"dflash_amd: wp_down holds fp8 experts of {wp_down.E} x {wp_down.N} x {wp_down.K}, the launch "
+                             f"asks for {E} x {N} x {I}")
+        check(lib().dfl_moe_down_fp8(_p(wp_down.wp, U8, "wp_down"), wp_down.wp.stride(0), _p(wp_down.scale, F32, "wp_down.scale"),
+                                     _p(act, BF16, "act"), act.stride(0), _p(wt, BF16, "wt"), _p(lst, I32, "list"),
+                                     _p(n_active, I32, "n_active"), E, N, I, nsplit, _p(out, F32, "out"), _stream()),
+              "dfl_moe_down_fp8")
+        return
+    assert wp_down.dim() == 2 and wp_down.is_contiguous()
     check(lib().dfl_moe_down(_p(wp_down, BF16, "wp_down"), wp_down.stride(0), _p(act, BF16, "act"), act.stride(0),
                              _p(wt, BF16, "wt"), _p(lst, I32, "list"), _p(n_active, I32, "n_active"), E, N, I, nsplit,
                              _p(out, F32, "out"), _stream()), "dfl_moe_down")

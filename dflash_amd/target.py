@@ -78,7 +78,7 @@ class _Weight:
 
 class NativeTarget:
     def __init__(self, hf_model, max_splits: int = 32, attn_impl: str = "head", keep_hf: bool = True,
-                 prefill: str = "native", weight_format: str = "bf16"):
+                 prefill: str = "native", weight_format: str = "bf16", expert_format: str = "bf16"):
         """weight_format: "bf16" (default), or "fp8_e4m3": every Linear weight of the target — q/k/v, o_proj, gate, up and
         down of every layer, and the lm_head — is quantised here to OCP e4m3 codes with one power-of-two scale per output
         row (ops.quantize_fp8_rows; W8A16, weight-only).  The quantised target IS the model: THE CALLER'S hf_model IS
@@ -89,6 +89,16 @@ class NativeTarget:
         weight ("The target").  Norm weights and the embedding gather stay bf16.  What weight-only
         e4m3 does to a real checkpoint's outputs, or to the acceptance length of a draft trained on the bf16 target, is
         NOT measured — hence off by default.
+        expert_format: "bf16" (default), or "fp8_e4m3" for a sparse-MoE target (weight_format stays "bf16": at the MoE
+        targets' hidden widths the dense projections are at their launch floors; the bytes are the experts'): every MoE
+        layer's mlp.experts.gate_up_proj ([E, 2I, H] as E * 2I rows of H) and mlp.experts.down_proj ([E, H, I] as E * H
+        rows of I) is quantised the same way, one power-of-two scale per output row.  Again the quantised target IS the
+        model and THE CALLER'S hf_model IS MODIFIED: both expert tensors are overwritten in place with q * scale before
+        anything is packed.  Router, norms, attention projections, dense layers (mlp_only_layers) and the lm_head stay
+        bf16.  lw["gu_e"] / lw["down_e"] stay the packed bf16 copy of q * scale (the experts cost 1.5 x their bf16 bytes);
+        `self.experts8[i]` holds layer i's codes and scales (ops.Fp8Experts; None for a dense layer), which the <= 16-row
+        verify and the per-tile expert branch stream while `self.expert_stream` is True ("The
+        experts").  What weight-only e4m3 does to a real MoE checkpoint's routing and outputs is NOT measured.
         attn_impl: "head" = dfl_attn_head on finished bf16 q/k/v rows (round 2, default); "fused" = the
         round-1 stage (fp32 K-split partials -> dfl_attn_fused), kept for A/B measurement and as a second
         implementation the tests compare against.
@@ -115,9 +125,14 @@ class NativeTarget:
         self.moe_shared_min = 2       # tiles from which the shared pass is taken (30B-A3B layer: 2 tiles 291 -> 216 us, 4: 576 -> 241)
         self._moe_sh = None
         cfg = hf_model.config
-        self.check_config(cfg, weight_format)   # (before anything touches the device: a rejected architecture never launches a kernel)
+        self.check_config(cfg, weight_format, expert_format)   # (before anything touches the device: a rejected architecture never launches a kernel)
         self.weight_format = weight_format
+        self.expert_format = expert_format
         fp8 = weight_format == "fp8_e4m3"
+        e8 = expert_format == "fp8_e4m3"
+        # fp8 experts only: False = the bf16 expert kernels on the dequantised copy (the second implementation the tests compare)
+        self.expert_stream = True
+        self.experts8 = [] if e8 else None   # per layer: {"gu_e", "down_e"} ops.Fp8Experts twins, None for a dense layer
         # fp8_e4m3 only: False = the bf16 kernels on the dequantised copy (the second implementation the tests compare)
         self.fp8_stream = True
         self.layers8 = [] if fp8 else None   # per layer: ops.Fp8Weight twins of qkv / o / gu / down in self.layers
@@ -207,6 +222,17 @@ class NativeTarget:
                 Ie = self.Ie
                 if gup.shape != (self.E, 2 * Ie, self.H) or dwn.shape != (self.E, self.H, Ie):
                     raise ValueError(f"layer {i}: unexpected expert tensor shapes {tuple(gup.shape)} {tuple(dwn.shape)}")
+                if e8:   # codes + scales per output row; the model's own tensors and what is packed below become q * scale
+                    x8 = {}
+                    for key, name, t in (("gu_e", "mlp.experts.gate_up_proj", gup), ("down_e", "mlp.experts.down_proj", dwn)):
+                        q, sc = ops.quantize_fp8_rows(t.view(-1, t.shape[2]))
+                        t.copy_(ops.dequantize_fp8_rows(q, sc).view_as(t))
+                        with torch.no_grad():
+                            sd[p + name].copy_(t)
+                        x8[key] = ops.pack_experts_fp8(q.view(t.shape), sc.view(t.shape[:2]), gateup=key == "gu_e")
+                        del q, sc
+                    self.experts8.append(x8)
+                    lw["gu_e8"], lw["down_e8"] = x8["gu_e"], x8["down_e"]   # (the layer dict is what moe_mlp_tiles is handed)
                 lw["gu_e"] = torch.stack([ops.pack_weight_gateup(gup[e, :Ie].contiguous(), gup[e, Ie:].contiguous())
                                           for e in range(self.E)])
                 lw["down_e"] = torch.stack([ops.pack_weight(dwn[e].contiguous()) for e in range(self.E)])
@@ -226,6 +252,8 @@ class NativeTarget:
                 lw["gu"] = ops.pack_weight_gateup(mat(p + "mlp.gate_proj.weight", l8, "gate"),
                                                   mat(p + "mlp.up_proj.weight", l8, "up"))
                 lw["down"] = ops.pack_weight(mat(p + "mlp.down_proj.weight", l8, "down"))
+                if e8:
+                    self.experts8.append(None)
             if fp8:
                 if "gate" not in l8:
                     raise NotImplementedError("NativeTarget: fp8_e4m3 needs dense MLP layers")
@@ -307,14 +335,18 @@ class NativeTarget:
         torch.cuda.synchronize(dev)
 
     @staticmethod
-    def check_config(cfg, weight_format: str = "bf16") -> None:
+    def check_config(cfg, weight_format: str = "bf16", expert_format: str = "bf16") -> None:
         """Architectures the kernels do not cover are rejected loudly, before any launch (the reference is shape-agnostic:
         model/dflash.py:36,42-56 take head_dim, attention_bias and sliding_window from the config; no BASELINE config
         needs them): head_dim != 128, biased projections, sliding-window attention layers.  weight_format: an unknown
-        one is a ValueError; "fp8_e4m3" refuses a sparse-MoE target (the expert kernels have no W8 form) and hidden,
-        intermediate or q widths that are not multiples of 64 (the packed e4m3 layout holds k-step pairs)."""
+        one is a ValueError; "fp8_e4m3" refuses a sparse-MoE target (its experts take expert_format instead) and hidden,
+        intermediate or q widths that are not multiples of 64 (the packed e4m3 layout holds k-step pairs).
+        expert_format: an unknown one is a ValueError; "fp8_e4m3" needs a sparse-MoE config (num_experts) whose hidden_size
+        and moe_intermediate_size are multiples of 64."""
         if weight_format not in WEIGHT_FORMATS:
             raise ValueError(f"NativeTarget: weight_format must be one of {WEIGHT_FORMATS}, got {weight_format!r}")
+        if expert_format not in WEIGHT_FORMATS:
+            raise ValueError(f"NativeTarget: expert_format must be one of {WEIGHT_FORMATS}, got {expert_format!r}")
         n_q = cfg.num_attention_heads
         hd = getattr(cfg, "head_dim", None) or cfg.hidden_size // n_q
         if hd != 128:
@@ -332,6 +364,15 @@ class NativeTarget:
             bad = {k: v for k, v in widths.items() if v % 64}
             if bad:
                 raise NotImplementedError(f"NativeTarget: fp8_e4m3 weights need hidden, intermediate and q widths % 64 == 0 "
+                                          f"(got {bad})")
+        if expert_format == "fp8_e4m3":
+            if not getattr(cfg, "num_experts", 0):
+                raise NotImplementedError("NativeTarget: expert_format='fp8_e4m3' needs a sparse-MoE target (Qwen3-MoE expert "
+                                          "layout); a dense target takes weight_format='fp8_e4m3'")
+            widths = dict(hidden_size=cfg.hidden_size, moe_intermediate_size=getattr(cfg, "moe_intermediate_size", 0))
+            bad = {k: v for k, v in widths.items() if not v or v % 64}
+            if bad:
+                raise NotImplementedError(f"NativeTarget: fp8_e4m3 experts need hidden and moe_intermediate widths % 64 == 0 "
                                           f"(got {bad})")
 
     # ---- HF-compatible surface (the reference loop can still drive the wrapped model)
@@ -374,12 +415,23 @@ class NativeTarget:
         return self._tile_layers[qkv_parts]
 
     def fp8_tensors(self) -> tuple:
-        """Every e4m3 code tensor and scale vector of an fp8 target (empty for bf16): what a captured graph of the verify
-        holds raw pointers to (DecodeSession's keep-alive tuple, the engine's capture key)."""
-        if self.layers8 is None:
-            return ()
-        ws = [w8 for l8 in self.layers8 for w8 in l8.values()] + [self.lm_wp8]
+        """Every e4m3 code tensor and scale vector of an fp8 target and of fp8 experts (empty for bf16): what a captured
+        graph of the verify holds raw pointers to (DecodeSession's keep-alive tuple, the engine's capture key)."""
+        ws = []
+        if self.layers8 is not None:
+            ws += [w8 for l8 in self.layers8 for w8 in l8.values()] + [self.lm_wp8]
+        if self.experts8 is not None:
+            ws += [x8 for l8 in self.experts8 if l8 is not None for x8 in l8.values()]
         return tuple(t for w8 in ws for t in (w8.wp, w8.scale))
+
+    def expert_weights(self, lw: dict) -> tuple:
+        """(gate/up, down) weights of an MoE layer (its dict in self.layers) for the two expert launches on <= 16 rows:
+        the e4m3 codes (ops.Fp8Experts) of an fp8-expert target while expert_stream is set — gate/up only where the pair
+        kernel runs (hidden <= 2048, moe_pair_kernel): dfl_gemm_silu_mul_experts has no W8 form — else the packed bf16
+        copy."""
+        if "gu_e8" not in lw or not self.expert_stream:
+            return lw["gu_e"], lw["down_e"]
+        return (lw["gu_e8"] if (self.H <= 2048 and self.moe_pair_kernel) else lw["gu_e"]), lw["down_e8"]
 
     def tile_head(self):
         """The lm_head of the tile-stack paths: the e4m3 codes when streams_fp8_tiles(), else the packed bf16 copy."""
@@ -520,6 +572,7 @@ class NativeTarget:
         projections as fp32 K-part sums, then residual add + tap + the NEXT stage's RMSNorm in one row-wise launch."""
         ws, H, E = self.ws, self.H, self.E
         nxt = self.layers[i + 1]["ln1"] if i + 1 < self.L else self.norm
+        gu_e, down_e = self.expert_weights(lw)   # (fp8 experts: the codes where the launch has a W8 form)
         for t, dt in tiles:
             if self.moe_router_fused:
                 ops.moe_router(h=hrow[t], norm_w=lw["ln2"], eps=self.eps, xn=ws["xn"][t], wp_router=lw["router"], K=H, E=E,
@@ -539,7 +592,7 @@ class NativeTarget:
             if mev is not None:
                 mev[1].record()
             if H <= 2048 and self.moe_pair_kernel:   # one LDS meeting per (gate, up) tile pair: 64 KB tiles at K = 2048
-                ops.moe_gate_up(lw["gu_e"], ws["xn"][t], E, self.Ie, H, ws["act_e"], ws["elist"], ws["n_active"], dyn=dt,
+                ops.moe_gate_up(gu_e, ws["xn"][t], E, self.Ie, H, ws["act_e"], ws["elist"], ws["n_active"], dyn=dt,
                                 valid_word=ops.DYN_BS)
             else:
                 ops.gemm_silu_mul_experts(lw["gu_e"], self.src["xn"][t], E, self.Ie, H, ws["act_e"], ws["elist"],
@@ -547,7 +600,7 @@ class NativeTarget:
             if mev is not None:
                 mev[2].record()
                 mev[3].copy_(ws["n_active"])
-            ops.moe_down(lw["down_e"], ws["act_e"], ws["wt"][t], ws["elist"], ws["n_active"], E, H, self.Ie,
+            ops.moe_down(down_e, ws["act_e"], ws["wt"][t], ws["elist"], ws["n_active"], E, H, self.Ie,
                          self.moe_nsplit, ws["moe_part"])
             tap = taps[16 * t:16 * t + 16, sl[0] * H:(sl[0] + 1) * H] if sl else None
             ops.norm_pack(norm_w=nxt, frag=ws["xn1"][t], H=H, eps=self.eps, part=ws["moe_part"], nsplit=self.moe_nsplit,
@@ -574,6 +627,7 @@ class NativeTarget:
         if mt > MT:
             raise ValueError(f"moe_mlp_tiles: {R} tiles need {mt} tile slots, the buffers have {MT}")
         pv = part[:ns * mt * 16 * H].view(ns, mt * 16, H)
+        gu_e, down_e = self.expert_weights(lw)   # (fp8 experts: the codes; the shared pass above reads the bf16 copy)
         for r in range(R):
             dt, x = dyn[r], xn[r]
             if self.moe_router_fused:   # gate Linear + routing in one launch on the tile's normalised fragments
@@ -586,12 +640,12 @@ class NativeTarget:
                 ops.moe_route(w["rlog"][0], self.E, self.top_k, self.norm_topk, w["wt"][0], w["active"], w["elist"],
                               w["n_active"], dyn=dt, dyn_word=ops.DYN_BS)
             if H <= 2048 and self.moe_pair_kernel:
-                ops.moe_gate_up(lw["gu_e"], x, self.E, self.Ie, H, w["act_e"], w["elist"], w["n_active"], dyn=dt,
+                ops.moe_gate_up(gu_e, x, self.E, self.Ie, H, w["act_e"], w["elist"], w["n_active"], dyn=dt,
                                 valid_word=ops.DYN_BS)
             else:
                 ops.gemm_silu_mul_experts(lw["gu_e"], ops.rows_frag(x), self.E, self.Ie, H, w["act_e"], w["elist"],
                                           w["n_active"], dyn=dt)
-            ops.moe_down(lw["down_e"], w["act_e"], w["wt"][0], w["elist"], w["n_active"], self.E, H, self.Ie, ns,
+            ops.moe_down(down_e, w["act_e"], w["wt"][0], w["elist"], w["n_active"], self.E, H, self.Ie, ns,
                          w["moe_part"])
             pv[:, r * 16:(r + 1) * 16].copy_(w["moe_part"])
         return ns

@@ -393,6 +393,20 @@ int dfl_moe_gate_up(const void *wp_gateup, const void *x_frag, int E, int I, int
 int dfl_moe_down(const void *wp_down, int64_t wp_expert_stride, const void *act_frag, int64_t act_expert_stride,
                  const void *wt, const int32_t *list, const int32_t *n_active, int E, int N, int I, int nsplit, float *out,
                  void *stream);
+/* The two expert launches on e4m3 codes (W8A16; one fp32 scale per output row, read only): the same items, the same
+ * k-steps per wave in the same order, the fp32 sums multiplied by the row's scale in front of the first rounding point —
+ * with power-of-two scales bit-equal to the bf16 launch on q * scale.
+ *  dfl_moe_gate_up_fp8: wp8_gateup = the experts' codes back to back, each 2*I*K bytes in dfl_pack_weight_gateup_fp8's
+ *    layout; wscale fp32 [E][2*I] in that layout's tile order (gate tile p's 16 scales, then up tile p's).
+ *    K % 64 == 0, K <= 2048; wscale non-null and 64-byte aligned.
+ *  dfl_moe_down_fp8: wp8_down = expert e's codes (dfl_pack_weight_fp8 of its [N][I] weight) at wp8_down + e *
+ *    wp_expert_stride BYTES (>= N*I, % 16 == 0); wscale fp32 [E][N].  I % 64 == 0; wscale non-null and 64-byte aligned.
+ * Anything else is DFL_EINVAL with a message and no launch. */
+int dfl_moe_gate_up_fp8(const void *wp8_gateup, const float *wscale, const void *x_frag, int E, int I, int K, void *act_frag,
+                        const int32_t *list, const int32_t *n_active, const int32_t *dyn, int valid_word, void *stream);
+int dfl_moe_down_fp8(const void *wp8_down, int64_t wp_expert_stride, const float *wscale, const void *act_frag,
+                     int64_t act_expert_stride, const void *wt, const int32_t *list, const int32_t *n_active, int E, int N,
+                     int I, int nsplit, float *out, void *stream);
 
 /* First-max-index argmax over the last axis (model/utils.py:28-29).
  * dtype: 0 = bf16, 1 = fp32.  ids int64 [rows]. */
