@@ -77,8 +77,10 @@ __device__ __forceinline__ void route_row(const bf16_t *logits_row, int E, int t
     sel_v[r] = bv;
     sel_i[r] = bi;
     tot += bv;
+    // taken: BELOW the rounds' starting value -1, so that route_better never picks it again (at -1 it tied with the
+    // start and won on its index: a NaN row took expert 0 in every round after the first, tests/test_hip_prefill_forms.py)
 #pragma unroll
     for (int j = 0; j < 4; ++j)
-      if (l + 64 * j == bi) p[j] = -1.f;  // taken
+      if (l + 64 * j == bi) p[j] = -2.f;
   }
 }
