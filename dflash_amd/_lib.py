@@ -31,6 +31,16 @@ class RowsBatch(C.Structure):
 
 _rb = C.POINTER(RowsBatch)
 
+W_BF16, W_E4M3 = 0, 1   # DFL_W_BF16, DFL_W_E4M3
+
+
+class Weight(C.Structure):
+    """dfl_weight of include/dflash_hip.h: every launch that has an e4m3 form takes one in place of the packed weight."""
+    _fields_ = [("wp", C.c_void_p), ("scale", C.c_void_p), ("format", C.c_int32)]
+
+
+_w = C.POINTER(Weight)
+
 # name -> (restype, argtypes); mirrors include/dflash_hip.h one to one
 SIGNATURES = {
     "dfl_version": (_i, []),
@@ -41,19 +51,15 @@ SIGNATURES = {
     "dfl_set_dyn2": (_i, [_p, _i, _i, _i, _i, _p]),
     "dfl_pack_rows": (_i, [_p, _i64, _i, _i, _p, _p, _i, _p]),
     "dfl_gemm_f32": (_i, [_p, _r, _r, _i, _i, _i, _i, _p, _p, _p]),
-    "dfl_gemm_silu_mul": (_i, [_p, _r, _i, _i, _p, _p, _p]),
-    "dfl_gemm_resid": (_i, [_p, _r, _i, _i, _p, _i64, _i, _p, _i64, _p, _p, _p]),
+    "dfl_gemm_silu_mul": (_i, [_w, _r, _i, _i, _p, _p, _p]),
+    "dfl_gemm_resid": (_i, [_w, _r, _i, _i, _p, _i64, _i, _p, _i64, _p, _p, _p]),
     "dfl_embed_rows": (_i, [_p, _p, _p, _i, _p, _p, _i, _p]),
-    # ---- fp8 (e4m3) weight streaming: the scale vector follows the packed weight
+    # ---- fp8 (e4m3) weights: the packers (a launch takes the codes and their scales as a Weight)
     "dfl_pack_weight_fp8": (_i, [_p, _p, _i, _i, _p]),
     "dfl_pack_weight_gateup_fp8": (_i, [_p, _p, _p, _i, _i, _p]),
-    "dfl_gemm_resid_fp8": (_i, [_p, _p, _r, _i, _i, _p, _i64, _i, _p, _i64, _p, _p, _p]),
-    "dfl_gemm_silu_mul_fp8": (_i, [_p, _p, _r, _i, _i, _p, _p, _p]),
-    "dfl_gemm_argmax_fp8": (_i, [_p, _p, _r, _i, _i, _i, _i, _p, _i, _p, _p, _i, _p, _p, _p, _p, _p]),
-    "dfl_gemm_sample_fp8": (_i, [_p, _p, _r, _i, _i, _i, _i, _p, _i, _p, _p, _i, _p, _p, _u64, _f, _i, _p, _i, _i, _i, _p]),
     "dfl_argmax_ws_bytes": (_i64, []),
-    "dfl_gemm_argmax": (_i, [_p, _r, _i, _i, _i, _i, _p, _i, _p, _p, _i, _p, _p, _p, _p, _p]),
-    "dfl_gemm_sample": (_i, [_p, _r, _i, _i, _i, _i, _p, _i, _p, _p, _i, _p, _p, _u64, _f, _i, _p, _i, _i, _i, _p]),
+    "dfl_gemm_argmax": (_i, [_w, _r, _i, _i, _i, _i, _p, _i, _p, _p, _i, _p, _p, _p, _p, _p]),
+    "dfl_gemm_sample": (_i, [_w, _r, _i, _i, _i, _i, _p, _i, _p, _p, _i, _p, _p, _u64, _f, _i, _p, _i, _i, _i, _p]),
     "dfl_sample_rows": (_i, [_p, _i64, _i, _i, _u64, _f, _i, _i, _p, _i, _p, _p, _p]),
     "dfl_sample_rows_nucleus": (_i, [_p, _i64, _i64, _i, _i, _i, _i, _p, _i, _i, _i, _p, _i, _i, _p, _u64, _p, _i, _p, _f,
                                      _p, _f, _i, _i, _p, _i64, _i, _p, _p, _p]),
@@ -81,11 +87,8 @@ SIGNATURES = {
     "dfl_moe_route": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _i, _p]),
     "dfl_moe_router": (_i, [_p, _i64, _p, _f, _p, _p, _i, _i, _i, _i, _p, _i, _p, _p, _p, _p, _p, _i, _p, _p]),
     "dfl_gemm_silu_mul_experts": (_i, [_p, _i64, _r, _i, _i, _i, _p, _i64, _p, _p, _p, _p]),
-    "dfl_moe_gate_up": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _p, _i, _p]),
-    "dfl_moe_down": (_i, [_p, _i64, _p, _i64, _p, _p, _p, _i, _i, _i, _i, _p, _p]),
-    # the two expert launches on e4m3 codes: the scale vector follows the packed weight (and its stride)
-    "dfl_moe_gate_up_fp8": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _i, _p]),
-    "dfl_moe_down_fp8": (_i, [_p, _i64, _p, _p, _i64, _p, _p, _p, _i, _i, _i, _i, _p, _p]),
+    "dfl_moe_gate_up": (_i, [_w, _p, _i, _i, _i, _p, _p, _p, _p, _i, _p]),
+    "dfl_moe_down": (_i, [_w, _i64, _p, _i64, _p, _p, _p, _i, _i, _i, _i, _p, _p]),
     "dfl_argmax": (_i, [_p, _i, _i, _i64, _p, _p]),
     "dfl_accept_commit": (_i, [_p, _p, _i, _p, _i64, _p, _p, _i, _p, _p, _i, _i64, _p, _p]),
     # ---- target prefill
@@ -108,17 +111,11 @@ SIGNATURES = {
     "dfl_batch_tiles": (_i, [_i]),
     "dfl_batch_ksplit": (_i, [_i]),
     "dfl_gemm_batch_ws_bytes": (_i64, [_i, _i]),
-    "dfl_gemm_f32_batch": (_i, [_p, _rb, _i, _i, _i, _p, _p, _p]),
-    "dfl_gemm_silu_mul_batch": (_i, [_p, _rb, _i, _i, _i, _p, _i64, _p, _p, _p]),
+    "dfl_gemm_f32_batch": (_i, [_w, _rb, _i, _i, _i, _p, _p, _p]),
+    "dfl_gemm_silu_mul_batch": (_i, [_w, _rb, _i, _i, _i, _p, _i64, _p, _p, _p]),
     "dfl_gemm_resid_batch": (_i, [_p, _rb, _i, _i, _i, _p, _i64, _i64, _i, _p, _i64, _i64, _p, _i64, _p, _p, _p]),
-    "dfl_gemm_argmax_batch": (_i, [_p, _rb, _i, _i, _i, _i, _i, _p, _i, _p, _p, _i64, _i, _p, _i64, _p]),
-    # fp8 (e4m3) weights in the ragged batch: the siblings' lists with the scale vector behind the packed weight
-    "dfl_gemm_f32_batch_fp8": (_i, [_p, _p, _rb, _i, _i, _i, _p, _p, _p]),
-    "dfl_gemm_silu_mul_batch_fp8": (_i, [_p, _p, _rb, _i, _i, _i, _p, _i64, _p, _p, _p]),
-    "dfl_gemm_argmax_batch_fp8": (_i, [_p, _p, _rb, _i, _i, _i, _i, _i, _p, _i, _p, _p, _i64, _i, _p, _i64, _p]),
-    "dfl_gemm_sample_batch_fp8": (_i, [_p, _p, _rb, _i, _i, _i, _i, _i, _p, _i, _p, _p, _i64, _i, _p, _i64, _p, _p, _f, _i, _i,
-                                        _i, _i, _p]),
-    "dfl_gemm_sample_batch": (_i, [_p, _rb, _i, _i, _i, _i, _i, _p, _i, _p, _p, _i64, _i, _p, _i64, _p, _p, _f, _i, _i, _i, _i,
+    "dfl_gemm_argmax_batch": (_i, [_w, _rb, _i, _i, _i, _i, _i, _p, _i, _p, _p, _i64, _i, _p, _i64, _p]),
+    "dfl_gemm_sample_batch": (_i, [_w, _rb, _i, _i, _i, _i, _i, _p, _i, _p, _p, _i64, _i, _p, _i64, _p, _p, _f, _i, _i, _i, _i,
                                    _p]),
     "dfl_embed_rows_batch": (_i, [_p, _p, _i64, _i, _p, _i64, _i, _p, _i64, _p, _i, _p]),
     "dfl_norm_frag_batch": (_i, [_p, _i64, _i64, _i, _p, _i, _i64, _i, _p, _i64, _i64, _p, _f, _p, _i64, _i, _p, _i, _p]),

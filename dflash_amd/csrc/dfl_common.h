@@ -36,6 +36,21 @@ void dfl_set_error(const char *fmt, ...);
     }                                                                      \
   } while (0)
 
+// What every entry point that takes a dfl_weight refuses first (dflash_hip.h): no descriptor, a format that is neither of
+// the two, a bf16 weight with a scale vector.  (e4m3 codes WITHOUT one are refused where each entry point checks its
+// pointers.)  After it, w->format == DFL_W_E4M3 selects the W8 instantiation.
+inline bool weight_ok(const char *who, const dfl_weight *w) {
+  if (!w)
+    dfl_set_error("%s: null weight descriptor", who);
+  else if (w->format != DFL_W_BF16 && w->format != DFL_W_E4M3)
+    dfl_set_error("%s: unknown weight format %d (DFL_W_BF16 = 0, DFL_W_E4M3 = 1)", who, w->format);
+  else if (w->format == DFL_W_BF16 && w->scale)
+    dfl_set_error("%s: a bf16 weight takes no scale vector (format DFL_W_BF16 with a non-null scale)", who);
+  else
+    return true;
+  return false;
+}
+
 // ---- device helpers ---------------------------------------------------------
 // Round-to-nearest-even fp32 -> bf16 via the hardware convert (keeps NaN a NaN).
 __device__ __forceinline__ bf16_t f2bf(float x) { return (bf16_t)x; }

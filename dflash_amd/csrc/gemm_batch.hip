@@ -538,8 +538,9 @@ bool launch_ring(const char *who, const GemmRArgs &a, int gx, hipStream_t st) {
   return true;
 }
 
-void fill_ring(GemmRArgs &a, const void *wp, const dfl_rows_batch *x, int N, int K, const int32_t *dyn) {
-  a.wp = (const bf16x8 *)wp;
+void fill_ring(GemmRArgs &a, const dfl_weight *w, const dfl_rows_batch *x, int N, int K, const int32_t *dyn) {
+  a.wp = (const bf16x8 *)w->wp;
+  a.wscale = w->scale;
   a.xf = (const bf16x8 *)x->r0.frag;
   a.frag_stride8 = x->frag_stride / 8;
   a.KS = K / 32;
@@ -607,14 +608,14 @@ void launch_b(int R, dim3 grid, hipStream_t st, const GemmBArgs &a) {
     hipLaunchKernelGGL((k_gemm_b<4, EPI, W8>), grid, dim3(512), 0, st, a);
 }
 
-// What the three fp8 entry points refuse before anything else: the scale vector, and the K the packed e4m3 layout and
-// the kernels' shares take.
-bool fp8_batch_ok(const char *who, const void *wp, const float *wscale, const dfl_rows_batch *x, int R, int N, int K) {
-  if (!wp || !wscale || !x) {
+// What the e4m3 form of an entry point refuses before anything else of its own: the scale vector, and the K the packed
+// e4m3 layout and the kernels' shares take.
+bool fp8_batch_ok(const char *who, const dfl_weight *w, const dfl_rows_batch *x, int R, int N, int K) {
+  if (!w->wp || !w->scale || !x) {
     dfl_set_error("%s: null pointer (weight, scale or row source)", who);
     return false;
   }
-  if ((uintptr_t)wscale % 64) {
+  if ((uintptr_t)w->scale % 64) {
     dfl_set_error("%s: the scale vector must be 64-byte aligned", who);
     return false;
   }
@@ -625,7 +626,7 @@ bool fp8_batch_ok(const char *who, const void *wp, const float *wscale, const df
   return true;
 }
 
-// ... and the two ring ones: they have no slab form
+// ... and the ring ones: on e4m3 codes they have no slab form
 bool fp8_ring_ok(const char *who, const dfl_rows_batch *x, int K) {
   if (!ring_ok(x, K) || x->frag_stride % 8) {
     dfl_set_error("%s: needs the ring form: frag16 row sources (mode 0) with frag_stride %% 8 == 0; there is no slab form", who);
@@ -643,103 +644,81 @@ extern "C" int64_t dfl_gemm_batch_ws_bytes(int N, int K) {
   return WS_HEAD + (int64_t)batch_ksplit(K) * (N / 16) * 4 * 256 * sizeof(float);
 }
 
-extern "C" int dfl_gemm_f32_batch(const void *wp, const dfl_rows_batch *x, int R, int N, int K, float *out,
+extern "C" int dfl_gemm_f32_batch(const dfl_weight *w, const dfl_rows_batch *x, int R, int N, int K, float *out,
                                   const int32_t *dyn, void *stream) {
+  const char *who = "dfl_gemm_f32_batch";
   GemmBArgs a{};
-  DFL_REQUIRE(out, "dfl_gemm_f32_batch: null pointer");
+  if (!weight_ok(who, w)) return DFL_EINVAL;
+  const bool w8 = w->format == DFL_W_E4M3;
+  DFL_REQUIRE(out, "%s: null pointer", who);
   // (The register-resident form only.  The ring form with K cut over grid.y was measured slower on down_proj, 7 tiles x 6
   // parts: 23.8 against 22.7 us per launch, 5.25 against 5.11 ms per 4-request cycle, profiles/r4_batch4_ab.txt — with a
   // 2048-wide K part resident in registers the workgroup has all its activations after one burst and 3 x 64 KB weight
   // items in flight; the ring holds 24 k-steps of look-ahead.  o_proj in four K parts likewise: 12.0 against 11.9 us,
   // and the norm launch behind it reads four parts, 5.23 against 5.16 ms.)
-  if (!fill_batch(a, wp, x, R, N, K, dyn, nullptr, "dfl_gemm_f32_batch")) return DFL_EINVAL;
+  if (w8 && !fp8_batch_ok(who, w, x, R, N, K)) return DFL_EINVAL;
+  if (!fill_batch(a, w->wp, x, R, N, K, dyn, nullptr, who)) return DFL_EINVAL;
+  if (w8) a.nfr = (a.nfr + 1) & ~1;  // a wave's share is a whole number of k-step pairs (8 waves x nfr still cover the K part)
+  a.wscale = w->scale;
   a.out = out;
   a.ldo = N;
   const int ksplit = batch_ksplit(K);
-  launch_b<EPI_F32>(R, dim3(grid_x_for(a.ntiles, ksplit), ksplit), (hipStream_t)stream, a);
-  DFL_CHECK_LAUNCH("dfl_gemm_f32_batch");
+  const dim3 grid(grid_x_for(a.ntiles, ksplit), ksplit);
+  if (!w8)
+    launch_b<EPI_F32>(R, grid, (hipStream_t)stream, a);
+  else
+    launch_b<EPI_F32, true>(R, grid, (hipStream_t)stream, a);
+  DFL_CHECK_LAUNCH(who);
   return DFL_OK;
 }
 
-extern "C" int dfl_gemm_f32_batch_fp8(const void *wp8, const float *wscale, const dfl_rows_batch *x, int R, int N, int K,
-                                      float *out, const int32_t *dyn, void *stream) {
-  GemmBArgs a{};
-  const char *who = "dfl_gemm_f32_batch_fp8";
-  DFL_REQUIRE(out, "dfl_gemm_f32_batch_fp8: null pointer");
-  if (!fp8_batch_ok(who, wp8, wscale, x, R, N, K)) return DFL_EINVAL;
-  if (!fill_batch(a, wp8, x, R, N, K, dyn, nullptr, who)) return DFL_EINVAL;
-  a.nfr = (a.nfr + 1) & ~1;  // a wave's share is a whole number of k-step pairs (8 waves x nfr still cover the K part)
-  a.wscale = wscale;
-  a.out = out;
-  a.ldo = N;
-  const int ksplit = batch_ksplit(K);
-  launch_b<EPI_F32, true>(R, dim3(grid_x_for(a.ntiles, ksplit), ksplit), (hipStream_t)stream, a);
-  DFL_CHECK_LAUNCH("dfl_gemm_f32_batch_fp8");
-  return DFL_OK;
-}
-
-extern "C" int dfl_gemm_silu_mul_batch(const void *wp_gateup, const dfl_rows_batch *x, int R, int I, int K,
+// e4m3 codes run in the ring form only (an error where it does not apply); the look-ahead A of each form: DESIGN.md
+// section 10, "The batch forms".
+extern "C" int dfl_gemm_silu_mul_batch(const dfl_weight *w_gateup, const dfl_rows_batch *x, int R, int I, int K,
                                        void *act_frag, int64_t act_stride, void *ws, const int32_t *dyn,
                                        void *stream) {
+  const char *who = "dfl_gemm_silu_mul_batch";
   GemmBArgs a{};
-  DFL_REQUIRE(act_frag && ws, "dfl_gemm_silu_mul_batch: null pointer");
-  DFL_REQUIRE(act_stride >= 16 * (int64_t)I, "dfl_gemm_silu_mul_batch: act_stride < 16*I");
-  if (wp_gateup && ring_ok(x, K) && R >= 1 && R <= 4 && I > 0 && I % 16 == 0 && x->frag_stride % 8 == 0) {
-    // ring form: a wave owns a (gate, up) tile pair and a quarter of every K chunk; no K cut over workgroups
-    GemmRArgs r{};
-    fill_ring(r, wp_gateup, x, 2 * I, K, dyn);
+  if (!weight_ok(who, w_gateup)) return DFL_EINVAL;
+  const bool w8 = w_gateup->format == DFL_W_E4M3;
+  DFL_REQUIRE(act_frag && (w8 || ws), "%s: null pointer", who);  // (ws is the slab form's: the e4m3 ring takes none)
+  if (w8 && (!fp8_batch_ok(who, w_gateup, x, R, I, K) || !fp8_ring_ok(who, x, K))) return DFL_EINVAL;
+  DFL_REQUIRE(act_stride >= 16 * (int64_t)I, "%s: act_stride < 16*I", who);
+  const bool ring = w8 || (w_gateup->wp && ring_ok(x, K) && R >= 1 && R <= 4 && I > 0 && I % 16 == 0 && x->frag_stride % 8 == 0);
+  const hipStream_t st = (hipStream_t)stream;
+  GemmRArgs r{};
+  int gx = 0;
+  bool w16 = false, ok = true;
+  if (ring) {  // a wave owns a (gate, up) tile pair and a quarter of every K chunk; no K cut over workgroups
+    fill_ring(r, w_gateup, x, 2 * I, K, dyn);
     r.act = (bf16_t *)act_frag;
     r.act_stride = act_stride;
-    int gx = 0;
     const int per_wg = (I / 16 + 255) / 256;
-    const bool w16 = per_wg % 4 == 0 || per_wg > 6;  // units per pass: 3 (12 waves) or 4 (16 waves)
-    ring_plan(r, I / 16, w16 ? 4 : 3, gx);
-    // look-ahead at 4 tiles: two chunks (16 chunks at K = 4096: no padding iterations), in the cycle 35.0 us against
-    // 37.3 at three; four chunks (160 KB of ring) were measured as well (profiles/r4_batch4_ab.txt)
-    const hipStream_t st = (hipStream_t)stream;
-    const char *who = "dfl_gemm_silu_mul_batch";
-    const bool ok = R <= 2 ? (w16 ? launch_ring<2, 2, 4, 16, 3, EPI_SILU>(who, r, gx, st)
-                                  : launch_ring<2, 2, 4, 12, 3, EPI_SILU>(who, r, gx, st))
-                           : (w16 ? launch_ring<4, 2, 4, 16, 2, EPI_SILU>(who, r, gx, st)
-                                  : launch_ring<4, 2, 4, 12, 2, EPI_SILU>(who, r, gx, st));
-    if (!ok) return DFL_ELAUNCH;
-    DFL_CHECK_LAUNCH("dfl_gemm_silu_mul_batch");
-    return DFL_OK;
+    w16 = per_wg % 4 == 0 || per_wg > 6;  // units per pass: 3 (12 waves) or 4 (16 waves): the same waves take the same
+    ring_plan(r, I / 16, w16 ? 4 : 3, gx);  // k-steps in both formats
   }
-  if (!fill_batch(a, wp_gateup, x, R, 2 * I, K, dyn, ws, "dfl_gemm_silu_mul_batch")) return DFL_EINVAL;
-  a.act = (bf16_t *)act_frag;
-  a.act_stride = act_stride;
-  const int ksplit = batch_ksplit(K);
-  launch_b<EPI_SILU>(R, dim3(grid_x_for(I / 16, ksplit), ksplit), (hipStream_t)stream, a);
-  DFL_CHECK_LAUNCH("dfl_gemm_silu_mul_batch");
-  return DFL_OK;
-}
-
-// The ring form over e4m3 codes; the look-ahead A of each form: DESIGN.md section 10, "The batch forms".
-extern "C" int dfl_gemm_silu_mul_batch_fp8(const void *wp8_gateup, const float *wscale, const dfl_rows_batch *x, int R,
-                                           int I, int K, void *act_frag, int64_t act_stride, void *ws,
-                                           const int32_t *dyn, void *stream) {
-  const char *who = "dfl_gemm_silu_mul_batch_fp8";
-  (void)ws;  // (the sibling's slab form needs it; kept so that the two take the same arguments)
-  DFL_REQUIRE(act_frag, "dfl_gemm_silu_mul_batch_fp8: null pointer");
-  if (!fp8_batch_ok(who, wp8_gateup, wscale, x, R, I, K) || !fp8_ring_ok(who, x, K)) return DFL_EINVAL;
-  DFL_REQUIRE(act_stride >= 16 * (int64_t)I, "dfl_gemm_silu_mul_batch_fp8: act_stride < 16*I");
-  GemmRArgs r{};
-  fill_ring(r, wp8_gateup, x, 2 * I, K, dyn);
-  r.wscale = wscale;
-  r.act = (bf16_t *)act_frag;
-  r.act_stride = act_stride;
-  int gx = 0;
-  const int per_wg = (I / 16 + 255) / 256;
-  const bool w16 = per_wg % 4 == 0 || per_wg > 6;  // as the bf16 sibling: the same waves take the same k-steps
-  ring_plan(r, I / 16, w16 ? 4 : 3, gx);
-  const hipStream_t st = (hipStream_t)stream;
-  const bool ok = R <= 2 ? (w16 ? launch_ring<2, 2, 4, 16, W8_A_SILU2, EPI_SILU, true>(who, r, gx, st)
-                                : launch_ring<2, 2, 4, 12, W8_A_SILU2, EPI_SILU, true>(who, r, gx, st))
-                         : (w16 ? launch_ring<4, 2, 4, 16, W8_A_SILU4, EPI_SILU, true>(who, r, gx, st)
-                                : launch_ring<4, 2, 4, 12, W8_A_SILU4, EPI_SILU, true>(who, r, gx, st));
+  // look-ahead at 4 tiles: two chunks (16 chunks at K = 4096: no padding iterations), in the cycle 35.0 us against
+  // 37.3 at three; four chunks (160 KB of ring) were measured as well (profiles/r4_batch4_ab.txt)
+  // (three forms, in the order their kernels stand in the code object: bf16 ring, bf16 slab, e4m3 ring)
+  if (ring && !w8) {
+    ok = R <= 2 ? (w16 ? launch_ring<2, 2, 4, 16, 3, EPI_SILU>(who, r, gx, st)
+                       : launch_ring<2, 2, 4, 12, 3, EPI_SILU>(who, r, gx, st))
+                : (w16 ? launch_ring<4, 2, 4, 16, 2, EPI_SILU>(who, r, gx, st)
+                       : launch_ring<4, 2, 4, 12, 2, EPI_SILU>(who, r, gx, st));
+  } else if (!ring) {  // slab form (bf16 only)
+    if (!fill_batch(a, w_gateup->wp, x, R, 2 * I, K, dyn, ws, who)) return DFL_EINVAL;
+    a.act = (bf16_t *)act_frag;
+    a.act_stride = act_stride;
+    const int ksplit = batch_ksplit(K);
+    launch_b<EPI_SILU>(R, dim3(grid_x_for(I / 16, ksplit), ksplit), st, a);
+  } else {
+    ok = R <= 2 ? (w16 ? launch_ring<2, 2, 4, 16, W8_A_SILU2, EPI_SILU, true>(who, r, gx, st)
+                       : launch_ring<2, 2, 4, 12, W8_A_SILU2, EPI_SILU, true>(who, r, gx, st))
+                : (w16 ? launch_ring<4, 2, 4, 16, W8_A_SILU4, EPI_SILU, true>(who, r, gx, st)
+                       : launch_ring<4, 2, 4, 12, W8_A_SILU4, EPI_SILU, true>(who, r, gx, st));
+  }
   if (!ok) return DFL_ELAUNCH;
-  DFL_CHECK_LAUNCH("dfl_gemm_silu_mul_batch_fp8");
+  DFL_CHECK_LAUNCH(who);
   return DFL_OK;
 }
 
@@ -772,9 +751,9 @@ extern "C" int dfl_gemm_resid_batch(const void *wp, const dfl_rows_batch *x, int
 namespace {
 // What the ring forms of the lm_head epilogues (argmax, seeded draw) share: the rows, the candidate buffers in ws, the
 // optional logits and the plan over the V / 16 column tiles.  Returns grid.x.
-int fill_ring_rows(GemmRArgs &r, const void *wp, const dfl_rows_batch *x, int V, int K, const int32_t *dyn, int row0,
+int fill_ring_rows(GemmRArgs &r, const dfl_weight *w, const dfl_rows_batch *x, int V, int K, const int32_t *dyn, int row0,
                    int nrows, int nrows_dyn_word, void *ws, void *logits, int64_t logits_stride) {
-  fill_ring(r, wp, x, V, K, dyn);
+  fill_ring(r, w, x, V, K, dyn);
   r.row0 = row0;
   r.nrows = nrows;
   r.nrows_word = nrows_dyn_word;
@@ -789,126 +768,76 @@ int fill_ring_rows(GemmRArgs &r, const void *wp, const dfl_rows_batch *x, int V,
 }
 }  // namespace
 
-extern "C" int dfl_gemm_argmax_batch(const void *wp, const dfl_rows_batch *x, int R, int V, int K, int row0, int nrows,
+extern "C" int dfl_gemm_argmax_batch(const dfl_weight *w, const dfl_rows_batch *x, int R, int V, int K, int row0, int nrows,
                                      const int32_t *dyn, int nrows_dyn_word, void *ws, int64_t *out_ids,
                                      int64_t out_stride, int out_off, void *logits, int64_t logits_stride,
                                      void *stream) {
+  const char *who = "dfl_gemm_argmax_batch";
   GemmBArgs a{};
-  DFL_REQUIRE(ws && out_ids, "dfl_gemm_argmax_batch: null pointer");
-  DFL_REQUIRE(row0 >= 0 && nrows >= 0 && row0 + nrows <= 16, "dfl_gemm_argmax_batch: rows [%d,%d) outside the tile", row0,
-              row0 + nrows);
-  if (wp && ring_ok(x, K) && R >= 1 && R <= 4 && V > 0 && V % 16 == 0 && x->frag_stride % 8 == 0) {
-    // ring form: a wave owns a column tile over the whole K, the workgroup walks its tiles in passes of <= 16
-    GemmRArgs r{};
-    const int gx = fill_ring_rows(r, wp, x, V, K, dyn, row0, nrows, nrows_dyn_word, ws, logits, logits_stride);
-    const char *who = "dfl_gemm_argmax_batch";
-    if (!(R <= 2 ? launch_ring<2, 1, 1, 16, 2, EPI_ARGMAX>(who, r, gx, (hipStream_t)stream)
-                 : launch_ring<4, 1, 1, 16, 2, EPI_ARGMAX>(who, r, gx, (hipStream_t)stream)))
-      return DFL_ELAUNCH;
-    hipLaunchKernelGGL(k_argmax_finish_b, dim3(16, R), dim3(64), 0, (hipStream_t)stream, r.best_val, r.best_idx, gx,
-                       mt_of(R), row0, nrows, dyn, nrows_dyn_word, out_ids, out_stride, out_off);
-    DFL_CHECK_LAUNCH("dfl_gemm_argmax_batch");
-    return DFL_OK;
-  }
-  if (!fill_batch(a, wp, x, R, V, K, dyn, ws, "dfl_gemm_argmax_batch")) return DFL_EINVAL;
-  a.row0 = row0;
-  a.nrows = nrows;
-  a.nrows_word = nrows_dyn_word;
-  a.logits = (bf16_t *)logits;
-  a.logits_stride = logits_stride;
-  a.N = V;
-  const int ksplit = batch_ksplit(K);
-  const int gx = grid_x_for(a.ntiles, ksplit);
-  launch_b<EPI_ARGMAX>(R, dim3(gx, ksplit), (hipStream_t)stream, a);
-  // candidates per (column group, wave): only the finishing workgroup of a group writes them
-  hipLaunchKernelGGL(k_argmax_finish_b, dim3(16, R), dim3(64), 0, (hipStream_t)stream, a.best_val, a.best_idx, gx * 8,
-                     mt_of(R), row0, nrows, dyn, nrows_dyn_word, out_ids, out_stride, out_off);
-  DFL_CHECK_LAUNCH("dfl_gemm_argmax_batch");
-  return DFL_OK;
-}
-
-extern "C" int dfl_gemm_argmax_batch_fp8(const void *wp8, const float *wscale, const dfl_rows_batch *x, int R, int V,
-                                         int K, int row0, int nrows, const int32_t *dyn, int nrows_dyn_word, void *ws,
-                                         int64_t *out_ids, int64_t out_stride, int out_off, void *logits,
-                                         int64_t logits_stride, void *stream) {
-  const char *who = "dfl_gemm_argmax_batch_fp8";
-  DFL_REQUIRE(ws && out_ids, "dfl_gemm_argmax_batch_fp8: null pointer");
-  DFL_REQUIRE(row0 >= 0 && nrows >= 0 && row0 + nrows <= 16, "dfl_gemm_argmax_batch_fp8: rows [%d,%d) outside the tile",
-              row0, row0 + nrows);
-  if (!fp8_batch_ok(who, wp8, wscale, x, R, V, K) || !fp8_ring_ok(who, x, K)) return DFL_EINVAL;
+  if (!weight_ok(who, w)) return DFL_EINVAL;
+  const bool w8 = w->format == DFL_W_E4M3;
+  DFL_REQUIRE(ws && out_ids, "%s: null pointer", who);
+  DFL_REQUIRE(row0 >= 0 && nrows >= 0 && row0 + nrows <= 16, "%s: rows [%d,%d) outside the tile", who, row0, row0 + nrows);
+  if (w8 && (!fp8_batch_ok(who, w, x, R, V, K) || !fp8_ring_ok(who, x, K))) return DFL_EINVAL;
+  const bool ring = w8 || (w->wp && ring_ok(x, K) && R >= 1 && R <= 4 && V > 0 && V % 16 == 0 && x->frag_stride % 8 == 0);
+  const hipStream_t st = (hipStream_t)stream;
   GemmRArgs r{};
-  const int gx = fill_ring_rows(r, wp8, x, V, K, dyn, row0, nrows, nrows_dyn_word, ws, logits, logits_stride);
-  r.wscale = wscale;
-  if (!(R <= 2 ? launch_ring<2, 1, 1, 16, W8_A_ARGMAX2, EPI_ARGMAX, true>(who, r, gx, (hipStream_t)stream)
-               : launch_ring<4, 1, 1, 16, W8_A_ARGMAX4, EPI_ARGMAX, true>(who, r, gx, (hipStream_t)stream)))
-    return DFL_ELAUNCH;
-  hipLaunchKernelGGL(k_argmax_finish_b, dim3(16, R), dim3(64), 0, (hipStream_t)stream, r.best_val, r.best_idx, gx,
-                     mt_of(R), row0, nrows, dyn, nrows_dyn_word, out_ids, out_stride, out_off);
-  DFL_CHECK_LAUNCH("dfl_gemm_argmax_batch_fp8");
+  // ring form: a wave owns a column tile over the whole K, the workgroup walks its tiles in passes of <= 16
+  int gx = ring ? fill_ring_rows(r, w, x, V, K, dyn, row0, nrows, nrows_dyn_word, ws, logits, logits_stride) : 0;
+  int ncand = gx;  // candidates per row and request for the finish: one per ring workgroup
+  bool ok = true;
+  // (three forms, as in dfl_gemm_silu_mul_batch: bf16 ring, bf16 slab, e4m3 ring)
+  if (ring && !w8) {
+    ok = R <= 2 ? launch_ring<2, 1, 1, 16, 2, EPI_ARGMAX>(who, r, gx, st) : launch_ring<4, 1, 1, 16, 2, EPI_ARGMAX>(who, r, gx, st);
+  } else if (!ring) {  // slab form (bf16 only)
+    if (!fill_batch(a, w->wp, x, R, V, K, dyn, ws, who)) return DFL_EINVAL;
+    a.row0 = row0;
+    a.nrows = nrows;
+    a.nrows_word = nrows_dyn_word;
+    a.logits = (bf16_t *)logits;
+    a.logits_stride = logits_stride;
+    a.N = V;
+    const int ksplit = batch_ksplit(K);
+    gx = grid_x_for(a.ntiles, ksplit);
+    launch_b<EPI_ARGMAX>(R, dim3(gx, ksplit), st, a);
+    ncand = gx * 8;  // per (column group, wave): only the finishing workgroup of a group writes them
+  } else {
+    ok = R <= 2 ? launch_ring<2, 1, 1, 16, W8_A_ARGMAX2, EPI_ARGMAX, true>(who, r, gx, st)
+                : launch_ring<4, 1, 1, 16, W8_A_ARGMAX4, EPI_ARGMAX, true>(who, r, gx, st);
+  }
+  if (!ok) return DFL_ELAUNCH;
+  hipLaunchKernelGGL(k_argmax_finish_b, dim3(16, R), dim3(64), 0, st, ring ? r.best_val : a.best_val,
+                     ring ? r.best_idx : a.best_idx, ncand, mt_of(R), row0, nrows, dyn, nrows_dyn_word, out_ids, out_stride,
+                     out_off);
+  DFL_CHECK_LAUNCH(who);
   return DFL_OK;
 }
 
 // The seeded draw of dfl_gemm_sample for R <= 4 request tiles in one pass over the weights: the ring form with the
 // EPI_SAMPLE epilogue (gemm_ring.h), or with EPI_SAMPLE_T where invT comes per request slot from the device array
-// inv_ts.  No slab form: where the ring form does not apply this is an error, not a quiet fall-back.
-extern "C" int dfl_gemm_sample_batch(const void *wp, const dfl_rows_batch *x, int R, int V, int K, int row0, int nrows,
+// inv_ts.  No slab form in either format: where the ring form does not apply this is an error, not a quiet fall-back.
+// e4m3: the columns' scales on the finished fp32 sums, in front of the rounding that the perturbation follows.
+extern "C" int dfl_gemm_sample_batch(const dfl_weight *w, const dfl_rows_batch *x, int R, int V, int K, int row0, int nrows,
                                      const int32_t *dyn, int nrows_dyn_word, void *ws, int64_t *out_ids,
                                      int64_t out_stride, int out_off, void *logits, int64_t logits_stride,
                                      const int64_t *seeds, const float *inv_ts, float inv_t, int rng_stream, int pos_word,
                                      int pos_add, int tiles_per_req, void *stream) {
-  DFL_REQUIRE(wp && x && ws && out_ids && dyn && seeds, "dfl_gemm_sample_batch: null pointer");
-  DFL_REQUIRE(row0 >= 0 && nrows >= 0 && row0 + nrows <= 16, "dfl_gemm_sample_batch: rows [%d,%d) outside the tile", row0,
-              row0 + nrows);
-  // (the values of inv_ts are not validated: every bit pattern is defined, !(invT > 0) is the greedy slot)
-  DFL_REQUIRE(inv_ts || (inv_t > 0.f && inv_t <= 1e5f), "dfl_gemm_sample_batch: inv_t=%g outside (0, 1e5]", (double)inv_t);
-  DFL_REQUIRE(rng_stream == (int)DFL_RNG_TARGET || rng_stream == (int)DFL_RNG_DRAFT,
-              "dfl_gemm_sample_batch: unknown stream %d", rng_stream);
-  DFL_REQUIRE(pos_word >= 0 && pos_word < DFL_DYN_WORDS && (tiles_per_req == 1 || tiles_per_req == 2) && R % tiles_per_req == 0,
-              "dfl_gemm_sample_batch: pos_word=%d / tiles_per_req=%d / R=%d", pos_word, tiles_per_req, R);
-  DFL_REQUIRE(ring_ok(x, K) && R >= 1 && R <= 4 && V > 0 && V % 16 == 0 && x->frag_stride % 8 == 0,
-              "dfl_gemm_sample_batch: needs the ring form (R <= 4 fragment sources, V %% 16 == 0, K %% 32 == 0, K >= 256)");
-  GemmRArgs r{};
-  const int gx = fill_ring_rows(r, wp, x, V, K, dyn, row0, nrows, nrows_dyn_word, ws, logits, logits_stride);
-  r.seeds = seeds;
-  r.inv_t = inv_ts ? 0.f : inv_t;
-  r.inv_ts = inv_ts;
-  r.rng_stream = rng_stream;
-  r.pos_word = pos_word;
-  r.pos_add = pos_add;
-  r.tiles_per_req = tiles_per_req;
   const char *who = "dfl_gemm_sample_batch";
-  const hipStream_t st = (hipStream_t)stream;
-  const bool ok = inv_ts ? (R <= 2 ? launch_ring<2, 1, 1, 16, 2, EPI_SAMPLE_T>(who, r, gx, st)
-                                   : launch_ring<4, 1, 1, 16, 2, EPI_SAMPLE_T>(who, r, gx, st))
-                         : (R <= 2 ? launch_ring<2, 1, 1, 16, 2, EPI_SAMPLE>(who, r, gx, st)
-                                   : launch_ring<4, 1, 1, 16, 2, EPI_SAMPLE>(who, r, gx, st));
-  if (!ok) return DFL_ELAUNCH;
-  hipLaunchKernelGGL(k_argmax_finish_b, dim3(16, R), dim3(64), 0, st, r.best_val, r.best_idx, gx, mt_of(R), row0, nrows, dyn,
-                     nrows_dyn_word, out_ids, out_stride, out_off);
-  DFL_CHECK_LAUNCH("dfl_gemm_sample_batch");
-  return DFL_OK;
-}
-
-// ... with an e4m3 lm_head: the W8 ring form with the same two epilogues, the columns' scales on the finished fp32 sums
-// in front of the rounding that the perturbation follows.  Refuses what the ring cannot take (no slab form, no fall-back).
-extern "C" int dfl_gemm_sample_batch_fp8(const void *wp8, const float *wscale, const dfl_rows_batch *x, int R, int V,
-                                         int K, int row0, int nrows, const int32_t *dyn, int nrows_dyn_word, void *ws,
-                                         int64_t *out_ids, int64_t out_stride, int out_off, void *logits,
-                                         int64_t logits_stride, const int64_t *seeds, const float *inv_ts, float inv_t,
-                                         int rng_stream, int pos_word, int pos_add, int tiles_per_req, void *stream) {
-  const char *who = "dfl_gemm_sample_batch_fp8";
-  DFL_REQUIRE(ws && out_ids && dyn && seeds, "dfl_gemm_sample_batch_fp8: null pointer");
-  DFL_REQUIRE(row0 >= 0 && nrows >= 0 && row0 + nrows <= 16, "dfl_gemm_sample_batch_fp8: rows [%d,%d) outside the tile", row0,
-              row0 + nrows);
-  DFL_REQUIRE(inv_ts || (inv_t > 0.f && inv_t <= 1e5f), "dfl_gemm_sample_batch_fp8: inv_t=%g outside (0, 1e5]", (double)inv_t);
-  DFL_REQUIRE(rng_stream == (int)DFL_RNG_TARGET || rng_stream == (int)DFL_RNG_DRAFT,
-              "dfl_gemm_sample_batch_fp8: unknown stream %d", rng_stream);
-  if (!fp8_batch_ok(who, wp8, wscale, x, R, V, K) || !fp8_ring_ok(who, x, K)) return DFL_EINVAL;
+  if (!weight_ok(who, w)) return DFL_EINVAL;
+  const bool w8 = w->format == DFL_W_E4M3;
+  // (e4m3: a null weight or row source is fp8_batch_ok's refusal, below)
+  DFL_REQUIRE((w8 || (w->wp && x)) && ws && out_ids && dyn && seeds, "%s: null pointer", who);
+  DFL_REQUIRE(row0 >= 0 && nrows >= 0 && row0 + nrows <= 16, "%s: rows [%d,%d) outside the tile", who, row0, row0 + nrows);
+  // (the values of inv_ts are not validated: every bit pattern is defined, !(invT > 0) is the greedy slot)
+  DFL_REQUIRE(inv_ts || (inv_t > 0.f && inv_t <= 1e5f), "%s: inv_t=%g outside (0, 1e5]", who, (double)inv_t);
+  DFL_REQUIRE(rng_stream == (int)DFL_RNG_TARGET || rng_stream == (int)DFL_RNG_DRAFT, "%s: unknown stream %d", who, rng_stream);
+  if (w8 && (!fp8_batch_ok(who, w, x, R, V, K) || !fp8_ring_ok(who, x, K))) return DFL_EINVAL;
   DFL_REQUIRE(pos_word >= 0 && pos_word < DFL_DYN_WORDS && (tiles_per_req == 1 || tiles_per_req == 2) && R % tiles_per_req == 0,
-              "dfl_gemm_sample_batch_fp8: pos_word=%d / tiles_per_req=%d / R=%d", pos_word, tiles_per_req, R);
+              "%s: pos_word=%d / tiles_per_req=%d / R=%d", who, pos_word, tiles_per_req, R);
+  DFL_REQUIRE(w8 || (ring_ok(x, K) && R >= 1 && R <= 4 && V > 0 && V % 16 == 0 && x->frag_stride % 8 == 0),
+              "%s: needs the ring form (R <= 4 fragment sources, V %% 16 == 0, K %% 32 == 0, K >= 256)", who);
   GemmRArgs r{};
-  const int gx = fill_ring_rows(r, wp8, x, V, K, dyn, row0, nrows, nrows_dyn_word, ws, logits, logits_stride);
-  r.wscale = wscale;
+  const int gx = fill_ring_rows(r, w, x, V, K, dyn, row0, nrows, nrows_dyn_word, ws, logits, logits_stride);
   r.seeds = seeds;
   r.inv_t = inv_ts ? 0.f : inv_t;
   r.inv_ts = inv_ts;
@@ -917,14 +846,21 @@ extern "C" int dfl_gemm_sample_batch_fp8(const void *wp8, const float *wscale, c
   r.pos_add = pos_add;
   r.tiles_per_req = tiles_per_req;
   const hipStream_t st = (hipStream_t)stream;
-  const bool ok = inv_ts ? (R <= 2 ? launch_ring<2, 1, 1, 16, W8_A_SAMPLE2, EPI_SAMPLE_T, true>(who, r, gx, st)
-                                   : launch_ring<4, 1, 1, 16, W8_A_SAMPLE4, EPI_SAMPLE_T, true>(who, r, gx, st))
-                         : (R <= 2 ? launch_ring<2, 1, 1, 16, W8_A_SAMPLE2, EPI_SAMPLE, true>(who, r, gx, st)
-                                   : launch_ring<4, 1, 1, 16, W8_A_SAMPLE4, EPI_SAMPLE, true>(who, r, gx, st));
+  bool ok;
+  if (!w8)
+    ok = inv_ts ? (R <= 2 ? launch_ring<2, 1, 1, 16, 2, EPI_SAMPLE_T>(who, r, gx, st)
+                          : launch_ring<4, 1, 1, 16, 2, EPI_SAMPLE_T>(who, r, gx, st))
+                : (R <= 2 ? launch_ring<2, 1, 1, 16, 2, EPI_SAMPLE>(who, r, gx, st)
+                          : launch_ring<4, 1, 1, 16, 2, EPI_SAMPLE>(who, r, gx, st));
+  else
+    ok = inv_ts ? (R <= 2 ? launch_ring<2, 1, 1, 16, W8_A_SAMPLE2, EPI_SAMPLE_T, true>(who, r, gx, st)
+                          : launch_ring<4, 1, 1, 16, W8_A_SAMPLE4, EPI_SAMPLE_T, true>(who, r, gx, st))
+                : (R <= 2 ? launch_ring<2, 1, 1, 16, W8_A_SAMPLE2, EPI_SAMPLE, true>(who, r, gx, st)
+                          : launch_ring<4, 1, 1, 16, W8_A_SAMPLE4, EPI_SAMPLE, true>(who, r, gx, st));
   if (!ok) return DFL_ELAUNCH;
   hipLaunchKernelGGL(k_argmax_finish_b, dim3(16, R), dim3(64), 0, st, r.best_val, r.best_idx, gx, mt_of(R), row0, nrows, dyn,
                      nrows_dyn_word, out_ids, out_stride, out_off);
-  DFL_CHECK_LAUNCH("dfl_gemm_sample_batch_fp8");
+  DFL_CHECK_LAUNCH(who);
   return DFL_OK;
 }
 

@@ -624,7 +624,7 @@ __global__ __launch_bounds__(1024) void k_gemm_s(GEMM_HEAD_PARAMS, GemmArgs rest
   gemm_body<1, false, EPI_SAMPLE, NORM>(with_head<false, NORM>(rest, GEMM_HEAD_NAMES), sa);
 }
 
-// ... and its W8 form (dfl_gemm_sample_fp8): the scale on the fp32 sum, the perturbation on bf16(sum * scale)
+// ... and its W8 form (dfl_gemm_sample on e4m3 codes): the scale on the fp32 sum, the perturbation on bf16(sum * scale)
 template <bool NORM>
 __global__ __launch_bounds__(1024) void k_gemm_s_w8(GEMM_HEAD_PARAMS, GemmArgs rest, SampleArgs sa) {
   gemm_body<1, false, EPI_SAMPLE, NORM, true>(with_head<false, NORM>(rest, GEMM_HEAD_NAMES), sa);
@@ -877,20 +877,21 @@ extern "C" int dfl_gemm_f32(const void *wp, const dfl_rows *x0, const dfl_rows *
   return DFL_OK;
 }
 
-// The fp8 entry points share their bf16 siblings' bodies: W8 = the weights are e4m3 codes in the W8 layout with one
-// fp32 scale per packed row (`wscale`), K % 64 == 0, and every wave's share (nfr) is rounded up to whole k-step pairs.
+// The entry points that take a dfl_weight: one body for both formats.  W8 = the weights are e4m3 codes in the W8 layout
+// with one fp32 scale per packed row (w->scale), K % 64 == 0, and every wave's share (nfr) is rounded up to whole k-step
+// pairs.
 namespace {
 template <bool W8>
-int gemm_silu_mul_impl(const char *who, const void *wp_gateup, const float *wscale, const dfl_rows *x, int I, int K,
-                       void *act_frag, const int32_t *dyn, void *stream) {
-  DFL_REQUIRE(wp_gateup && act_frag && (!W8 || wscale), "%s: null pointer", who);
+int gemm_silu_mul_impl(const char *who, const dfl_weight *w, const dfl_rows *x, int I, int K, void *act_frag,
+                       const int32_t *dyn, void *stream) {
+  DFL_REQUIRE(w->wp && act_frag && (!W8 || w->scale), "%s: null pointer", who);
   DFL_REQUIRE(I > 0 && K > 0 && I % 16 == 0 && K % (W8 ? 64 : 32) == 0, "%s: need I%%16==0, K%%%d==0", who, W8 ? 64 : 32);
   const int KS = K / 32;
   DFL_REQUIRE(KS <= 16 * 8, "%s: K=%d needs a K split, which the fused activation cannot take", who, K);
   GemmArgs a{};
   if (!fill_src(a.src[0], x, K, who)) return DFL_EINVAL;
-  a.wp = (const bf16x8 *)wp_gateup;
-  a.wscale = wscale;
+  a.wp = (const bf16x8 *)w->wp;
+  a.wscale = w->scale;
   a.dyn = dyn;
   a.KS = KS;
   a.ntiles = 2 * (I / 16);
@@ -904,14 +905,12 @@ int gemm_silu_mul_impl(const char *who, const void *wp_gateup, const float *wsca
 }
 }  // namespace
 
-extern "C" int dfl_gemm_silu_mul(const void *wp_gateup, const dfl_rows *x, int I, int K, void *act_frag,
+extern "C" int dfl_gemm_silu_mul(const dfl_weight *w_gateup, const dfl_rows *x, int I, int K, void *act_frag,
                                  const int32_t *dyn, void *stream) {
-  return gemm_silu_mul_impl<false>("dfl_gemm_silu_mul", wp_gateup, nullptr, x, I, K, act_frag, dyn, stream);
-}
-
-extern "C" int dfl_gemm_silu_mul_fp8(const void *wp_gateup, const float *wscale, const dfl_rows *x, int I, int K,
-                                     void *act_frag, const int32_t *dyn, void *stream) {
-  return gemm_silu_mul_impl<true>("dfl_gemm_silu_mul_fp8", wp_gateup, wscale, x, I, K, act_frag, dyn, stream);
+  const char *who = "dfl_gemm_silu_mul";
+  if (!weight_ok(who, w_gateup)) return DFL_EINVAL;
+  return w_gateup->format == DFL_W_BF16 ? gemm_silu_mul_impl<false>(who, w_gateup, x, I, K, act_frag, dyn, stream)
+                                        : gemm_silu_mul_impl<true>(who, w_gateup, x, I, K, act_frag, dyn, stream);
 }
 
 // One launch for the gate/up projection of EVERY active expert of a sparse-MoE layer (Qwen3-MoE:
@@ -951,27 +950,27 @@ extern "C" int dfl_gemm_silu_mul_experts(const void *wp_gateup, int64_t wp_exper
 extern "C" int64_t dfl_argmax_ws_bytes(void) { return 256 * 16 * (int64_t)(2 * sizeof(float) + sizeof(int)); }
 
 namespace {
-int gemm_argmax_impl(const void *wp, const dfl_rows *x, int V, int K, int row0, int nrows, const int32_t *dyn,
-                     int nrows_dyn_word, void *ws, int64_t *out_ids, int out_off, void *logits, float *margin_out,
-                     hipEvent_t ev0, hipEvent_t ev1, void *stream, const SampleArgs *smp = nullptr,
-                     const float *wscale = nullptr, bool w8 = false) {
-  const char *who = w8 ? (smp ? "dfl_gemm_sample_fp8" : "dfl_gemm_argmax_fp8") : "dfl_gemm_argmax";
-  DFL_REQUIRE(wp && ws && out_ids && (!w8 || wscale), "%s: null pointer", who);
+// who: dfl_gemm_argmax, or dfl_gemm_sample with its draw in smp; w has passed weight_ok
+int gemm_argmax_impl(const char *who, const dfl_weight *w, const dfl_rows *x, int V, int K, int row0, int nrows,
+                     const int32_t *dyn, int nrows_dyn_word, void *ws, int64_t *out_ids, int out_off, void *logits,
+                     float *margin_out, hipEvent_t ev0, hipEvent_t ev1, void *stream, const SampleArgs *smp = nullptr) {
+  const bool w8 = w->format == DFL_W_E4M3;
+  DFL_REQUIRE(w->wp && ws && out_ids && (!w8 || w->scale), "%s: null pointer", who);
   DFL_REQUIRE(V > 0 && K > 0 && V % 16 == 0 && K % (w8 ? 64 : 32) == 0, "%s: need V%%16==0, K%%%d==0 (V=%d K=%d)", who,
               w8 ? 64 : 32, V, K);
-  DFL_REQUIRE(row0 >= 0 && nrows >= 0 && row0 + nrows <= 16, "dfl_gemm_argmax: rows [%d,%d) outside the 16-row tile", row0,
+  DFL_REQUIRE(row0 >= 0 && nrows >= 0 && row0 + nrows <= 16, "%s: rows [%d,%d) outside the 16-row tile", who, row0,
               row0 + nrows);
   const int KS = K / 32;
-  DFL_REQUIRE(KS <= 16 * 8, "dfl_gemm_argmax: K=%d exceeds 4096 (argmax needs finished sums)", K);
+  DFL_REQUIRE(KS <= 16 * 8, "%s: K=%d exceeds 4096 (argmax needs finished sums)", who, K);
   GemmArgs a{};
-  if (!fill_src(a.src[0], x, K, "dfl_gemm_argmax")) return DFL_EINVAL;
-  a.wp = (const bf16x8 *)wp;
+  if (!fill_src(a.src[0], x, K, who)) return DFL_EINVAL;
+  a.wp = (const bf16x8 *)w->wp;
   a.dyn = dyn;
   a.KS = KS;
   a.ntiles = V / 16;
   a.nfr = (KS + 15) / 16;
   if (w8) a.nfr += a.nfr & 1;
-  a.wscale = wscale;
+  a.wscale = w->scale;
   a.nch = 1;
   a.row0 = row0;
   a.nrows = nrows;
@@ -1005,70 +1004,50 @@ int gemm_argmax_impl(const void *wp, const dfl_rows *x, int V, int K, int row0, 
   if (ev1) (void)hipEventRecord(ev1, (hipStream_t)stream);
   hipLaunchKernelGGL(k_argmax_finish, dim3(16), dim3(64), 0, (hipStream_t)stream, a.best_val, a.best_idx, a.best2_val, gx,
                      row0, nrows, dyn, nrows_dyn_word, out_ids, out_off, margin_out);
-  DFL_CHECK_LAUNCH("dfl_gemm_argmax");
+  DFL_CHECK_LAUNCH(who);
   return DFL_OK;
 }
 }  // namespace
 
-extern "C" int dfl_gemm_argmax(const void *wp, const dfl_rows *x, int V, int K, int row0, int nrows,
+extern "C" int dfl_gemm_argmax(const dfl_weight *w, const dfl_rows *x, int V, int K, int row0, int nrows,
                                const int32_t *dyn, int nrows_dyn_word, void *ws, int64_t *out_ids, int out_off,
                                void *logits, float *margin_out, void *ev_start, void *ev_end, void *stream) {
-  return gemm_argmax_impl(wp, x, V, K, row0, nrows, dyn, nrows_dyn_word, ws, out_ids, out_off, logits, margin_out,
+  const char *who = "dfl_gemm_argmax";
+  if (!weight_ok(who, w)) return DFL_EINVAL;
+  return gemm_argmax_impl(who, w, x, V, K, row0, nrows, dyn, nrows_dyn_word, ws, out_ids, out_off, logits, margin_out,
                           (hipEvent_t)ev_start, (hipEvent_t)ev_end, stream);
 }
 
-extern "C" int dfl_gemm_argmax_fp8(const void *wp, const float *wscale, const dfl_rows *x, int V, int K, int row0, int nrows,
-                                   const int32_t *dyn, int nrows_dyn_word, void *ws, int64_t *out_ids, int out_off,
-                                   void *logits, float *margin_out, void *ev_start, void *ev_end, void *stream) {
-  return gemm_argmax_impl(wp, x, V, K, row0, nrows, dyn, nrows_dyn_word, ws, out_ids, out_off, logits, margin_out,
-                          (hipEvent_t)ev_start, (hipEvent_t)ev_end, stream, nullptr, wscale, true);
-}
-
-extern "C" int dfl_gemm_sample(const void *wp, const dfl_rows *x, int V, int K, int row0, int nrows, const int32_t *dyn,
-                               int nrows_dyn_word, void *ws, int64_t *out_ids, int out_off, void *logits, float *margin_out,
-                               uint64_t seed, float inv_t, int rng_stream, const int32_t *pos_dyn, int pos_word,
-                               int pos_base, int pos_add, void *stream) {
-  DFL_REQUIRE(wp && ws && out_ids, "dfl_gemm_sample: null pointer");
-  DFL_REQUIRE(inv_t > 0.f && inv_t <= 1e5f, "dfl_gemm_sample: inv_t=%g outside (0, 1e5]", (double)inv_t);
-  DFL_REQUIRE(rng_stream == (int)DFL_RNG_TARGET || rng_stream == (int)DFL_RNG_DRAFT, "dfl_gemm_sample: unknown stream %d",
+extern "C" int dfl_gemm_sample(const dfl_weight *w, const dfl_rows *x, int V, int K, int row0, int nrows,
+                               const int32_t *dyn, int nrows_dyn_word, void *ws, int64_t *out_ids, int out_off,
+                               void *logits, float *margin_out, uint64_t seed, float inv_t, int rng_stream,
+                               const int32_t *pos_dyn, int pos_word, int pos_base, int pos_add, void *stream) {
+  const char *who = "dfl_gemm_sample";
+  if (!weight_ok(who, w)) return DFL_EINVAL;
+  DFL_REQUIRE(w->wp && (w->format == DFL_W_BF16 || w->scale) && ws && out_ids, "%s: null pointer", who);
+  DFL_REQUIRE(inv_t > 0.f && inv_t <= 1e5f, "%s: inv_t=%g outside (0, 1e5]", who, (double)inv_t);
+  DFL_REQUIRE(rng_stream == (int)DFL_RNG_TARGET || rng_stream == (int)DFL_RNG_DRAFT, "%s: unknown stream %d", who,
               rng_stream);
-  DFL_REQUIRE(!pos_dyn || (pos_word >= 0 && pos_word < DFL_DYN_WORDS), "dfl_gemm_sample: pos_word=%d outside the record",
-              pos_word);
+  DFL_REQUIRE(!pos_dyn || (pos_word >= 0 && pos_word < DFL_DYN_WORDS), "%s: pos_word=%d outside the record", who, pos_word);
   const SampleArgs smp{seed, inv_t, rng_stream, pos_dyn, pos_word, pos_base, pos_add};
-  return gemm_argmax_impl(wp, x, V, K, row0, nrows, dyn, nrows_dyn_word, ws, out_ids, out_off, logits, margin_out, nullptr,
-                          nullptr, stream, &smp);
-}
-
-extern "C" int dfl_gemm_sample_fp8(const void *wp8, const float *wscale, const dfl_rows *x, int V, int K, int row0, int nrows,
-                                   const int32_t *dyn, int nrows_dyn_word, void *ws, int64_t *out_ids, int out_off,
-                                   void *logits, float *margin_out, uint64_t seed, float inv_t, int rng_stream,
-                                   const int32_t *pos_dyn, int pos_word, int pos_base, int pos_add, void *stream) {
-  DFL_REQUIRE(wp8 && wscale && ws && out_ids, "dfl_gemm_sample_fp8: null pointer");
-  DFL_REQUIRE(inv_t > 0.f && inv_t <= 1e5f, "dfl_gemm_sample_fp8: inv_t=%g outside (0, 1e5]", (double)inv_t);
-  DFL_REQUIRE(rng_stream == (int)DFL_RNG_TARGET || rng_stream == (int)DFL_RNG_DRAFT, "dfl_gemm_sample_fp8: unknown stream %d",
-              rng_stream);
-  DFL_REQUIRE(!pos_dyn || (pos_word >= 0 && pos_word < DFL_DYN_WORDS), "dfl_gemm_sample_fp8: pos_word=%d outside the record",
-              pos_word);
-  const SampleArgs smp{seed, inv_t, rng_stream, pos_dyn, pos_word, pos_base, pos_add};
-  return gemm_argmax_impl(wp8, x, V, K, row0, nrows, dyn, nrows_dyn_word, ws, out_ids, out_off, logits, margin_out, nullptr,
-                          nullptr, stream, &smp, wscale, true);
+  return gemm_argmax_impl(who, w, x, V, K, row0, nrows, dyn, nrows_dyn_word, ws, out_ids, out_off, logits, margin_out,
+                          nullptr, nullptr, stream, &smp);
 }
 
 
 namespace {
 template <bool W8>
-int gemm_resid_impl(const char *who, const void *wp, const float *wscale, const dfl_rows *x, int N, int K, void *h_io,
-                    int64_t ldh, int add_residual, void *tap, int64_t ldtap, float *ss_out, const int32_t *dyn,
-                    void *stream) {
-  DFL_REQUIRE(wp && h_io && (!W8 || wscale), "%s: null pointer", who);
+int gemm_resid_impl(const char *who, const dfl_weight *w, const dfl_rows *x, int N, int K, void *h_io, int64_t ldh,
+                    int add_residual, void *tap, int64_t ldtap, float *ss_out, const int32_t *dyn, void *stream) {
+  DFL_REQUIRE(w->wp && h_io && (!W8 || w->scale), "%s: null pointer", who);
   DFL_REQUIRE(N > 0 && K > 0 && N % 16 == 0 && K % (W8 ? 64 : 32) == 0, "%s: need N%%16==0, K%%%d==0 (N=%d K=%d)", who,
               W8 ? 64 : 32, N, K);
   DFL_REQUIRE(ldh >= N && (!tap || ldtap >= N), "%s: row strides shorter than N", who);
   const int KS = K / 32;
   GemmArgs a{};
   if (!fill_src(a.src[0], x, K, who)) return DFL_EINVAL;
-  a.wp = (const bf16x8 *)wp;
-  a.wscale = wscale;
+  a.wp = (const bf16x8 *)w->wp;
+  a.wscale = w->scale;
   a.dyn = dyn;
   a.KS = KS;
   a.ntiles = N / 16;
@@ -1098,16 +1077,12 @@ int gemm_resid_impl(const char *who, const void *wp, const float *wscale, const 
 }
 }  // namespace
 
-extern "C" int dfl_gemm_resid(const void *wp, const dfl_rows *x, int N, int K, void *h_io, int64_t ldh,
+extern "C" int dfl_gemm_resid(const dfl_weight *w, const dfl_rows *x, int N, int K, void *h_io, int64_t ldh,
                               int add_residual, void *tap, int64_t ldtap, float *ss_out, const int32_t *dyn,
                               void *stream) {
-  return gemm_resid_impl<false>("dfl_gemm_resid", wp, nullptr, x, N, K, h_io, ldh, add_residual, tap, ldtap, ss_out, dyn,
-                                stream);
-}
-
-extern "C" int dfl_gemm_resid_fp8(const void *wp, const float *wscale, const dfl_rows *x, int N, int K, void *h_io,
-                                  int64_t ldh, int add_residual, void *tap, int64_t ldtap, float *ss_out,
-                                  const int32_t *dyn, void *stream) {
-  return gemm_resid_impl<true>("dfl_gemm_resid_fp8", wp, wscale, x, N, K, h_io, ldh, add_residual, tap, ldtap, ss_out, dyn,
-                               stream);
+  const char *who = "dfl_gemm_resid";
+  if (!weight_ok(who, w)) return DFL_EINVAL;
+  return w->format == DFL_W_BF16
+             ? gemm_resid_impl<false>(who, w, x, N, K, h_io, ldh, add_residual, tap, ldtap, ss_out, dyn, stream)
+             : gemm_resid_impl<true>(who, w, x, N, K, h_io, ldh, add_residual, tap, ldtap, ss_out, dyn, stream);
 }

@@ -353,7 +353,7 @@ struct MoeDownArgs8 : MoeDownArgs {
 // CT: column tiles per workgroup.  With CT = 1 every workgroup re-reads every expert's activations (24 KB per expert
 // at I = 768: as many bytes from L2 as weight bytes from HBM); CT = 2 shares an item's activation fragments between two
 // column tiles.
-// W8 (dfl_moe_down_fp8): the item's 4 k-steps of a column tile arrive as TWO 16-byte loads of codes that stay in
+// W8 (dfl_moe_down on e4m3 codes): the item's 4 k-steps of a column tile arrive as TWO 16-byte loads of codes that stay in
 // flight as they are (half the registers per buffer) and are converted right in front of each MFMA (w8_frag); the
 // same k-steps in the same order as the bf16 form, so with power-of-two scales the launch is bit-equal to the bf16
 // one on q * scale.  The four scales of the lane's columns (MFMA D layout: 4 (L >> 4) .. + 3) are one 16-byte vector
@@ -468,7 +468,7 @@ struct MoeGuArgs8 : MoeGuArgs {
   const float *wscale;
 };
 
-// W8 (dfl_moe_gate_up_fp8): a wave's 4 k-steps of the gate tile and of the up tile arrive as 2 + 2 16-byte loads of
+// W8 (dfl_moe_gate_up on e4m3 codes): a wave's 4 k-steps of the gate tile and of the up tile arrive as 2 + 2 16-byte loads of
 // codes, kept raw in flight (half the registers per buffer) and converted in front of each MFMA; same k-steps per wave,
 // same order, so with power-of-two scales the launch is bit-equal to the bf16 one on q * scale.  The scales: every
 // lane requests the two of column l & 15 (gate, up) WITH the item and IN FRONT of its weights — loads return in order,
@@ -567,20 +567,19 @@ namespace {
 inline bool scales_aligned(const float *p) { return ((uintptr_t)p & 63) == 0; }
 
 template <bool W8>
-int moe_gate_up_impl(const char *who, const void *wp_gateup, const float *wscale, const void *x_frag, int E, int I, int K,
-                     void *act_frag, const int32_t *list, const int32_t *n_active, const int32_t *dyn, int valid_word,
-                     void *stream) {
-  DFL_REQUIRE(wp_gateup && x_frag && act_frag && list && n_active, "%s: null pointer", who);
+int moe_gate_up_impl(const char *who, const dfl_weight *w, const void *x_frag, int E, int I, int K, void *act_frag,
+                     const int32_t *list, const int32_t *n_active, const int32_t *dyn, int valid_word, void *stream) {
+  DFL_REQUIRE(w->wp && x_frag && act_frag && list && n_active, "%s: null pointer", who);
   DFL_REQUIRE(E >= 1 && E <= 1024 && I > 0 && I % 16 == 0 && K > 0 && K % 32 == 0 && K <= 2048,
               "%s: E=%d I=%d K=%d outside range (K <= 2048; larger K: dfl_gemm_silu_mul_experts)", who, E, I, K);
   std::conditional_t<W8, MoeGuArgs8, MoeGuArgs> a{};
   if constexpr (W8) {
     DFL_REQUIRE(K % 64 == 0, "%s: K=%d is not a multiple of 64 (the e4m3 layout holds k-step pairs)", who, K);
-    DFL_REQUIRE(wscale, "%s: null scale vector", who);
-    DFL_REQUIRE(scales_aligned(wscale), "%s: the scale vector must be 64-byte aligned", who);
-    a.wscale = wscale;
+    DFL_REQUIRE(w->scale, "%s: null scale vector", who);
+    DFL_REQUIRE(scales_aligned(w->scale), "%s: the scale vector must be 64-byte aligned", who);
+    a.wscale = w->scale;
   }
-  a.wp = (const bf16x8 *)wp_gateup;
+  a.wp = (const bf16x8 *)w->wp;
   a.xfrag = (const bf16x8 *)x_frag;
   a.list = list;
   a.n_active = n_active;
@@ -595,18 +594,14 @@ int moe_gate_up_impl(const char *who, const void *wp_gateup, const float *wscale
 }
 }  // namespace
 
-extern "C" int dfl_moe_gate_up(const void *wp_gateup, const void *x_frag, int E, int I, int K, void *act_frag,
+extern "C" int dfl_moe_gate_up(const dfl_weight *w_gateup, const void *x_frag, int E, int I, int K, void *act_frag,
                                const int32_t *list, const int32_t *n_active, const int32_t *dyn, int valid_word,
                                void *stream) {
-  return moe_gate_up_impl<false>("dfl_moe_gate_up", wp_gateup, nullptr, x_frag, E, I, K, act_frag, list, n_active, dyn,
-                                 valid_word, stream);
-}
-
-extern "C" int dfl_moe_gate_up_fp8(const void *wp8_gateup, const float *wscale, const void *x_frag, int E, int I, int K,
-                                   void *act_frag, const int32_t *list, const int32_t *n_active, const int32_t *dyn,
-                                   int valid_word, void *stream) {
-  return moe_gate_up_impl<true>("dfl_moe_gate_up_fp8", wp8_gateup, wscale, x_frag, E, I, K, act_frag, list, n_active, dyn,
-                                valid_word, stream);
+  const char *who = "dfl_moe_gate_up";
+  if (!weight_ok(who, w_gateup)) return DFL_EINVAL;
+  return w_gateup->format == DFL_W_BF16
+             ? moe_gate_up_impl<false>(who, w_gateup, x_frag, E, I, K, act_frag, list, n_active, dyn, valid_word, stream)
+             : moe_gate_up_impl<true>(who, w_gateup, x_frag, E, I, K, act_frag, list, n_active, dyn, valid_word, stream);
 }
 
 extern "C" int dfl_moe_route(const void *logits, int ld, int E, int top_k, int norm_topk, void *wt, int32_t *active,
@@ -676,10 +671,10 @@ extern "C" int dfl_debug_read_router_stamps(unsigned long long *host_out) {
 namespace {
 // wp_expert_stride: bf16 elements (bf16) or bytes of codes (W8) between experts — 16-byte units either way once divided
 template <bool W8>
-int moe_down_impl(const char *who, const void *wp_down, int64_t wp_expert_stride, const float *wscale, const void *act_frag,
+int moe_down_impl(const char *who, const dfl_weight *w, int64_t wp_expert_stride, const void *act_frag,
                   int64_t act_expert_stride, const void *wt, const int32_t *list, const int32_t *n_active, int E, int N,
                   int I, int nsplit, float *out, void *stream) {
-  DFL_REQUIRE(wp_down && act_frag && wt && list && n_active && out, "%s: null pointer", who);
+  DFL_REQUIRE(w->wp && act_frag && wt && list && n_active && out, "%s: null pointer", who);
   DFL_REQUIRE(E >= 1 && N > 0 && I > 0 && N % 16 == 0 && I % 32 == 0 && nsplit >= 1 && nsplit <= 16, "%s: bad shape", who);
   constexpr int UNIT = W8 ? 16 : 8;  // stride units per 16 bytes
   DFL_REQUIRE(wp_expert_stride >= (int64_t)N * I && wp_expert_stride % UNIT == 0 && act_expert_stride >= (int64_t)16 * I &&
@@ -688,11 +683,11 @@ int moe_down_impl(const char *who, const void *wp_down, int64_t wp_expert_stride
   std::conditional_t<W8, MoeDownArgs8, MoeDownArgs> a{};
   if constexpr (W8) {
     DFL_REQUIRE(I % 64 == 0, "%s: I=%d is not a multiple of 64 (the e4m3 layout holds k-step pairs)", who, I);
-    DFL_REQUIRE(wscale, "%s: null scale vector", who);
-    DFL_REQUIRE(scales_aligned(wscale), "%s: the scale vector must be 64-byte aligned", who);
-    a.wscale = wscale;
+    DFL_REQUIRE(w->scale, "%s: null scale vector", who);
+    DFL_REQUIRE(scales_aligned(w->scale), "%s: the scale vector must be 64-byte aligned", who);
+    a.wscale = w->scale;
   }
-  a.wd = (const bf16x8 *)wp_down;
+  a.wd = (const bf16x8 *)w->wp;
   a.wd_stride = wp_expert_stride / UNIT;
   a.act = (const bf16x8 *)act_frag;
   a.act_stride = act_expert_stride / 8;
@@ -717,16 +712,13 @@ int moe_down_impl(const char *who, const void *wp_down, int64_t wp_expert_stride
 }
 }  // namespace
 
-extern "C" int dfl_moe_down(const void *wp_down, int64_t wp_expert_stride, const void *act_frag, int64_t act_expert_stride,
-                            const void *wt, const int32_t *list, const int32_t *n_active, int E, int N, int I, int nsplit,
-                            float *out, void *stream) {
-  return moe_down_impl<false>("dfl_moe_down", wp_down, wp_expert_stride, nullptr, act_frag, act_expert_stride, wt, list,
-                              n_active, E, N, I, nsplit, out, stream);
-}
-
-extern "C" int dfl_moe_down_fp8(const void *wp8_down, int64_t wp_expert_stride, const float *wscale, const void *act_frag,
-                                int64_t act_expert_stride, const void *wt, const int32_t *list, const int32_t *n_active,
-                                int E, int N, int I, int nsplit, float *out, void *stream) {
-  return moe_down_impl<true>("dfl_moe_down_fp8", wp8_down, wp_expert_stride, wscale, act_frag, act_expert_stride, wt, list,
-                             n_active, E, N, I, nsplit, out, stream);
+extern "C" int dfl_moe_down(const dfl_weight *w_down, int64_t wp_expert_stride, const void *act_frag,
+                            int64_t act_expert_stride, const void *wt, const int32_t *list, const int32_t *n_active, int E,
+                            int N, int I, int nsplit, float *out, void *stream) {
+  const char *who = "dfl_moe_down";
+  if (!weight_ok(who, w_down)) return DFL_EINVAL;
+  return w_down->format == DFL_W_BF16 ? moe_down_impl<false>(who, w_down, wp_expert_stride, act_frag, act_expert_stride, wt,
+                                                             list, n_active, E, N, I, nsplit, out, stream)
+                                      : moe_down_impl<true>(who, w_down, wp_expert_stride, act_frag, act_expert_stride, wt,
+                                                            list, n_active, E, N, I, nsplit, out, stream);
 }

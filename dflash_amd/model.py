@@ -152,11 +152,9 @@ class DFlashDraftModel:
         def mat(name, store, key):
             """A Linear weight on the device: as loaded, or (fp8) its dequantised values, the codes packed into `store`."""
             m = dev(name)
-            if not fp8:
-                return m
-            q, sc = ops.quantize_fp8_rows(m)
-            store[key] = (q, sc)
-            return ops.dequantize_fp8_rows(q, sc)
+            if fp8:
+                m, store[key] = ops.quantize_keep_fp8(m)
+            return m
 
         top8 = {}
         w = {"fc": ops.pack_weight(mat("fc.weight", top8, "fc")), "hidden_norm": dev("hidden_norm.weight"),
@@ -171,12 +169,7 @@ class DFlashDraftModel:
             gate, up = mat(p + "mlp.gate_proj.weight", l8, "gate"), mat(p + "mlp.up_proj.weight", l8, "up")
             o, down = mat(p + "self_attn.o_proj.weight", l8, "o"), mat(p + "mlp.down_proj.weight", l8, "down")
             if fp8:
-                w8["layers"].append({
-                    "qkv": ops.pack_weight_fp8(torch.cat([l8[k][0] for k in "qkv"]), torch.cat([l8[k][1] for k in "qkv"])),
-                    "o": ops.pack_weight_fp8(*l8["o"]),
-                    "gu": ops.pack_weight_gateup_fp8(*l8["gate"], *l8["up"]),
-                    "down": ops.pack_weight_fp8(*l8["down"]),
-                })
+                w8["layers"].append(ops.pack_layer_fp8(l8))
             del l8
             w["layers"].append({
                 "qkv": ops.pack_weight(qkv),
@@ -322,11 +315,7 @@ class DFlashDraftModel:
         qkv="parts" — replaced by their e4m3 twins when streams_fp8_tiles()."""
         if not self.streams_fp8_tiles():
             return self.w["layers"]
-        if qkv_parts not in self._tile_layers:   # (built once per loaded state dict)
-            keys = ("gu", "o", "down") + (("qkv",) if qkv_parts else ())
-            self._tile_layers[qkv_parts] = [{**lw, **{k: l8[k] for k in keys}}
-                                            for lw, l8 in zip(self.w["layers"], self.w8["layers"])]
-        return self._tile_layers[qkv_parts]
+        return ops.tile_layers(self.w["layers"], self.w8["layers"], qkv_parts, self._tile_layers)
 
     # ------------------------------------------------------------------ kernels
     def _ctx_rows(self, th_rows: torch.Tensor, n: int, dyn, dyn_word: Optional[int]):

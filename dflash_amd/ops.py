@@ -9,7 +9,7 @@ from typing import NamedTuple, Optional
 
 import torch
 
-from ._lib import Rows, check, lib
+from ._lib import W_BF16, W_E4M3, Rows, Weight, check, lib
 
 BF16, F32, I32, I64 = torch.bfloat16, torch.float32, torch.int32, torch.int64
 DYN_S, DYN_TAU, DYN_BS, DYN_POS0, DYN_START, DYN_STOP, DYN_CYCLE = range(7)
@@ -165,10 +165,50 @@ def pack_experts_fp8(q: torch.Tensor, scale: torch.Tensor, gateup: bool) -> Fp8E
     return Fp8Experts(wp, sc, e, n, k)
 
 
-def _fp8(wp: Fp8Weight, N: int, K: int, name: str):
+def quantize_keep_fp8(m: torch.Tensor):
+    """The load step of an fp8 model for one Linear weight [N, K]: (q * scale as bf16 — what the bf16 kernels and the
+    rest of the model compute with —, (q, scale) for pack_weight_fp8 / pack_layer_fp8)."""
+    q, sc = quantize_fp8_rows(m)
+    return dequantize_fp8_rows(q, sc), (q, sc)
+
+
+def pack_layer_fp8(l8: dict) -> dict:
+    """A dense layer's (codes, scales) by projection — q, k, v, o, gate, up, down — -> its four Fp8Weights, laid out as
+    the layer's packed bf16 weights are: q/k/v as one matrix, gate/up interleaved."""
+    return {"qkv": pack_weight_fp8(torch.cat([l8[k][0] for k in "qkv"]), torch.cat([l8[k][1] for k in "qkv"])),
+            "o": pack_weight_fp8(*l8["o"]), "gu": pack_weight_gateup_fp8(*l8["gate"], *l8["up"]),
+            "down": pack_weight_fp8(*l8["down"])}
+
+
+def tile_layers(layers: list, layers8: list, qkv_parts: bool, cache: dict) -> list:
+    """The layer dicts TileStack.run takes where it streams e4m3 codes: `layers` with gu / o / down — and qkv, where the
+    caller runs qkv="parts" — replaced by their twins in layers8.  Built once per form and kept in `cache`."""
+    if qkv_parts not in cache:
+        keys = ("gu", "o", "down") + (("qkv",) if qkv_parts else ())
+        cache[qkv_parts] = [{**lw, **{k: l8[k] for k in keys}} for lw, l8 in zip(layers, layers8)]
+    return cache[qkv_parts]
+
+
+def _w(wp, N: int, K: int, name: str) -> Weight:
+    """The dfl_weight of a launch: a packed bf16 tensor, or an Fp8Weight of the launch's N x K.  Read on the host during
+    the call only; the caller's references keep the tensors alive."""
+    if not isinstance(wp, Fp8Weight):
+        return Weight(_p(wp, BF16, name), None, W_BF16)
     if (wp.N, wp.K) != (N, K):
         raise ValueError(f"dflash_amd: {name} is an fp8 weight of {wp.N} x {wp.K}, the launch asks for {N} x {K}")
-    return _p(wp.wp, U8, name), _p(wp.scale, F32, name + ".scale")
+    return Weight(_p(wp.wp, U8, name), _p(wp.scale, F32, name + ".scale"), W_E4M3)
+
+
+def _we(wp, E: int, N: int, K: int, name: str):
+    """_w for one MoE layer's experts: packed bf16 [E, .] or an Fp8Experts of E x N x K.  Returns the descriptor and the
+    tensor whose rows are the experts (its stride(0): bf16 elements, or bytes of codes, between them)."""
+    if not isinstance(wp, Fp8Experts):
+        assert wp.dim() == 2 and wp.is_contiguous()
+        return Weight(_p(wp, BF16, name), None, W_BF16), wp
+    if (wp.E, wp.N, wp.K) != (E, N, K):
+        raise ValueError(f"dflash_amd: {name} holds fp8 experts of {wp.E} x {wp.N} x {wp.K}, the launch asks for "
+                         f"{E} x {N} x {K}")
+    return Weight(_p(wp.wp, U8, name), _p(wp.scale, F32, name + ".scale"), W_E4M3), wp.wp
 
 
 # ---- per-cycle ------------------------------------------------------------------
@@ -281,11 +321,7 @@ def pick_ksplit(N: int, K: int, mt: int) -> int:
 
 def gemm_silu_mul(wp_gu, x, I: int, K: int, act_frag: torch.Tensor, dyn=None) -> None:
     assert act_frag.numel() >= 16 * I
-    if isinstance(wp_gu, Fp8Weight):
-        check(lib().dfl_gemm_silu_mul_fp8(*_fp8(wp_gu, 2 * I, K, "wp_gu"), _src(x).ref, I, K, _p(act_frag, BF16, "act"),
-                                          _p(dyn, I32, "dyn"), _stream()), "dfl_gemm_silu_mul_fp8")
-        return
-    check(lib().dfl_gemm_silu_mul(_p(wp_gu, BF16, "wp_gu"), _src(x).ref, I, K, _p(act_frag, BF16, "act"),
+    check(lib().dfl_gemm_silu_mul(_w(wp_gu, 2 * I, K, "wp_gu"), _src(x).ref, I, K, _p(act_frag, BF16, "act"),
                                   _p(dyn, I32, "dyn"), _stream()), "dfl_gemm_silu_mul")
 
 
@@ -304,13 +340,7 @@ def gemm_argmax(wp, x, V: int, K: int, row0: int, nrows: int, ws, out_ids: torch
     if margins is not None:
         assert margins.numel() >= out_off + nrows
     ev_start, ev_end = (None, None) if events is None else (events[0].cuda_event, events[1].cuda_event)
-    if isinstance(wp, Fp8Weight):
-        check(lib().dfl_gemm_argmax_fp8(*_fp8(wp, V, K, "wp"), _src(x).ref, V, K, row0, nrows, _p(dyn, I32, "dyn"),
-                                        nrows_dyn_word, _p(ws), _p(out_ids, I64, "out_ids"), out_off,
-                                        _p(logits, BF16, "logits"), _p(margins, F32, "margins"), ev_start, ev_end,
-                                        _stream()), "dfl_gemm_argmax_fp8")
-        return
-    check(lib().dfl_gemm_argmax(_p(wp, BF16, "wp"), _src(x).ref, V, K, row0, nrows, _p(dyn, I32, "dyn"), nrows_dyn_word,
+    check(lib().dfl_gemm_argmax(_w(wp, V, K, "wp"), _src(x).ref, V, K, row0, nrows, _p(dyn, I32, "dyn"), nrows_dyn_word,
                                 _p(ws), _p(out_ids, I64, "out_ids"), out_off, _p(logits, BF16, "logits"),
                                 _p(margins, F32, "margins"), ev_start, ev_end, _stream()), "dfl_gemm_argmax")
 
@@ -334,19 +364,12 @@ def gemm_sample(wp, x, V: int, K: int, row0: int, nrows: int, ws, out_ids: torch
                 logits: Optional[torch.Tensor] = None, margins: Optional[torch.Tensor] = None) -> None:
     """gemm_argmax with the seeded Gumbel-max draw at `temperature` (dfl_gemm_sample): tile row m draws position
     (pos_dyn[pos_word] if pos_dyn is given, else pos_base) + pos_add + m.  wp: packed bf16, or an Fp8Weight
-    (dfl_gemm_sample_fp8: the draw over bf16(sum * scale))."""
+    (the draw over bf16(sum * scale))."""
     if logits is not None:
         assert logits.numel() >= 16 * V
     if margins is not None:
         assert margins.numel() >= out_off + nrows
-    if isinstance(wp, Fp8Weight):
-        check(lib().dfl_gemm_sample_fp8(*_fp8(wp, V, K, "wp"), _src(x).ref, V, K, row0, nrows, _p(dyn, I32, "dyn"),
-                                        nrows_dyn_word, _p(ws), _p(out_ids, I64, "out_ids"), out_off,
-                                        _p(logits, BF16, "logits"), _p(margins, F32, "margins"), _seed64(seed),
-                                        inv_temperature(temperature), stream, _p(pos_dyn, I32, "pos_dyn"), pos_word,
-                                        pos_base, pos_add, _stream()), "dfl_gemm_sample_fp8")
-        return
-    check(lib().dfl_gemm_sample(_p(wp, BF16, "wp"), _src(x).ref, V, K, row0, nrows, _p(dyn, I32, "dyn"), nrows_dyn_word,
+    check(lib().dfl_gemm_sample(_w(wp, V, K, "wp"), _src(x).ref, V, K, row0, nrows, _p(dyn, I32, "dyn"), nrows_dyn_word,
                                 _p(ws), _p(out_ids, I64, "out_ids"), out_off, _p(logits, BF16, "logits"),
                                 _p(margins, F32, "margins"), _seed64(seed), inv_temperature(temperature), stream,
                                 _p(pos_dyn, I32, "pos_dyn"), pos_word, pos_base, pos_add, _stream()), "dfl_gemm_sample")
@@ -459,12 +482,7 @@ def gemm_resid(wp, x, N: int, K: int, h_io: torch.Tensor, *, add_residual: bool,
         tp, ldt = tap.data_ptr(), tap.stride(0)
     if ss_out is not None:
         assert ss_out.numel() >= N
-    if isinstance(wp, Fp8Weight):
-        check(lib().dfl_gemm_resid_fp8(*_fp8(wp, N, K, "wp"), _src(x).ref, N, K, h_io.data_ptr(), h_io.stride(0),
-                                       int(add_residual), tp, ldt, _p(ss_out, F32, "ss_out"), _p(dyn, I32, "dyn"),
-                                       _stream()), "dfl_gemm_resid_fp8")
-        return
-    check(lib().dfl_gemm_resid(_p(wp, BF16, "wp"), _src(x).ref, N, K, h_io.data_ptr(), h_io.stride(0),
+    check(lib().dfl_gemm_resid(_w(wp, N, K, "wp"), _src(x).ref, N, K, h_io.data_ptr(), h_io.stride(0),
                                int(add_residual), tp, ldt, _p(ss_out, F32, "ss_out"), _p(dyn, I32, "dyn"), _stream()),
           "dfl_gemm_resid")
 
@@ -710,42 +728,24 @@ def gemm_silu_mul_experts(wp_gu: torch.Tensor, x, E: int, I: int, K: int, act: t
 def moe_gate_up(wp_gu: torch.Tensor, x_frag: torch.Tensor, E: int, I: int, K: int, act: torch.Tensor, lst: torch.Tensor,
                 n_active: torch.Tensor, dyn=None, valid_word: int = -1) -> None:
     """gemm_silu_mul_experts for K <= 2048 from frag16 rows: one LDS meeting per (gate, up) tile pair.  wp_gu: packed
-    bf16 [E, 2*I*K], or an Fp8Experts (dfl_moe_gate_up_fp8)."""
+    bf16 [E, 2*I*K], or an Fp8Experts."""
     assert act.dim() == 2 and act.is_contiguous() and act.shape[1] == 16 * I and x_frag.numel() >= 16 * K
-    if isinstance(wp_gu, Fp8Experts):
-        if (wp_gu.E, wp_gu.N, wp_gu.K) != (E, 2 * I, K):
-            raise ValueError(f"dflash_amd: wp_gu holds fp8 experts of {wp_gu.E} x {wp_gu.N} x {wp_gu.K}, the launch asks "
-                             f"for {E} x {2 * I} x {K}")
-        check(lib().dfl_moe_gate_up_fp8(_p(wp_gu.wp, U8, "wp_gu"), _p(wp_gu.scale, F32, "wp_gu.scale"),
-                                        _p(x_frag, BF16, "x_frag"), E, I, K, _p(act, BF16, "act"), _p(lst, I32, "list"),
-                                        _p(n_active, I32, "n_active"), _p(dyn, I32, "dyn"), valid_word, _stream()),
-              "dfl_moe_gate_up_fp8")
-        return
-    assert wp_gu.dim() == 2 and wp_gu.is_contiguous() and wp_gu.shape[1] == 2 * I * K
-    assert act.dim() == 2 and act.is_contiguous() and act.shape[1] == 16 * I and x_frag.numel() >= 16 * K
-    check(lib().dfl_moe_gate_up(_p(wp_gu, BF16, "wp_gu"), _p(x_frag, BF16, "x_frag"), E, I, K, _p(act, BF16, "act"),
-                                _p(lst, I32, "list"), _p(n_active, I32, "n_active"), _p(dyn, I32, "dyn"), valid_word,
-                                _stream()), "dfl_moe_gate_up")
+    w, rows = _we(wp_gu, E, 2 * I, K, "wp_gu")
+    assert rows.shape[1] == 2 * I * K
+    check(lib().dfl_moe_gate_up(w, _p(x_frag, BF16, "x_frag"), E, I, K, _p(act, BF16, "act"), _p(lst, I32, "list"),
+                                _p(n_active, I32, "n_active"), _p(dyn, I32, "dyn"), valid_word, _stream()),
+          "dfl_moe_gate_up")
 
 
 def moe_down(wp_down: torch.Tensor, act: torch.Tensor, wt: torch.Tensor, lst: torch.Tensor, n_active: torch.Tensor, E: int,
              N: int, I: int, nsplit: int, out: torch.Tensor) -> None:
-    """wp_down bf16 [E, N*I] packed per expert, or an Fp8Experts (dfl_moe_down_fp8); out fp32 [nsplit, 16, N]."""
+    """wp_down bf16 [E, N*I] packed per expert, or an Fp8Experts; out fp32 [nsplit, 16, N]."""
     assert act.dim() == 2 and act.is_contiguous()
     assert out.dtype == F32 and out.is_contiguous() and out.numel() >= nsplit * 16 * N
-    if isinstance(wp_down, Fp8Experts):
-        if (wp_down.E, wp_down.N, wp_down.K) != (E, N, I):
-            raise ValueError(f"dflash_amd: wp_down holds fp8 experts of {wp_down.E} x {wp_down.N} x {wp_down.K}, the launch "
-                             f"asks for {E} x {N} x {I}")
-        check(lib().dfl_moe_down_fp8(_p(wp_down.wp, U8, "wp_down"), wp_down.wp.stride(0), _p(wp_down.scale, F32, "wp_down.scale"),
-                                     _p(act, BF16, "act"), act.stride(0), _p(wt, BF16, "wt"), _p(lst, I32, "list"),
-                                     _p(n_active, I32, "n_active"), E, N, I, nsplit, _p(out, F32, "out"), _stream()),
-              "dfl_moe_down_fp8")
-        return
-    assert wp_down.dim() == 2 and wp_down.is_contiguous()
-    check(lib().dfl_moe_down(_p(wp_down, BF16, "wp_down"), wp_down.stride(0), _p(act, BF16, "act"), act.stride(0),
-                             _p(wt, BF16, "wt"), _p(lst, I32, "list"), _p(n_active, I32, "n_active"), E, N, I, nsplit,
-                             _p(out, F32, "out"), _stream()), "dfl_moe_down")
+    w, rows = _we(wp_down, E, N, I, "wp_down")
+    check(lib().dfl_moe_down(w, rows.stride(0), _p(act, BF16, "act"), act.stride(0), _p(wt, BF16, "wt"),
+                             _p(lst, I32, "list"), _p(n_active, I32, "n_active"), E, N, I, nsplit, _p(out, F32, "out"),
+                             _stream()), "dfl_moe_down")
 
 
 def argmax(logits: torch.Tensor) -> torch.Tensor:
@@ -835,22 +835,15 @@ def gemm_batch_ws(N: int, K: int, device) -> torch.Tensor:
 
 def gemm_f32_batch(wp, x: BatchRowSource, R: int, N: int, K: int, out: torch.Tensor, dyn) -> None:
     assert out.numel() >= batch_ksplit(K) * batch_tiles(R) * 16 * N
-    if isinstance(wp, Fp8Weight):   # every K part comes out scaled: the launch that sums them takes it as it is
-        check(lib().dfl_gemm_f32_batch_fp8(*_fp8(wp, N, K, "wp"), x.ref, R, N, K, _p(out, F32, "out"), _p(dyn, I32, "dyn"),
-                                           _stream()), "dfl_gemm_f32_batch_fp8")
-        return
-    check(lib().dfl_gemm_f32_batch(_p(wp, BF16, "wp"), x.ref, R, N, K, _p(out, F32, "out"), _p(dyn, I32, "dyn"),
+    # (an Fp8Weight: every K part comes out scaled, the launch that sums them takes it as it is)
+    check(lib().dfl_gemm_f32_batch(_w(wp, N, K, "wp"), x.ref, R, N, K, _p(out, F32, "out"), _p(dyn, I32, "dyn"),
                                    _stream()), "dfl_gemm_f32_batch")
 
 
 def gemm_silu_mul_batch(wp_gu, x: BatchRowSource, R: int, I: int, K: int, act: torch.Tensor, ws, dyn) -> None:
     assert act.dim() == 2 and act.shape[1] >= 16 * I and act.shape[0] >= batch_tiles(R)
-    if isinstance(wp_gu, Fp8Weight):   # the ring form only: a plain-row source is an error, not a fall-back
-        check(lib().dfl_gemm_silu_mul_batch_fp8(*_fp8(wp_gu, 2 * I, K, "wp_gu"), x.ref, R, I, K, _p(act, BF16, "act"),
-                                                act.stride(0), _p(ws), _p(dyn, I32, "dyn"), _stream()),
-              "dfl_gemm_silu_mul_batch_fp8")
-        return
-    check(lib().dfl_gemm_silu_mul_batch(_p(wp_gu, BF16, "wp_gu"), x.ref, R, I, K, _p(act, BF16, "act"), act.stride(0),
+    # (an Fp8Weight runs the ring form only, here and in the two below: a plain-row source is an error, not a fall-back)
+    check(lib().dfl_gemm_silu_mul_batch(_w(wp_gu, 2 * I, K, "wp_gu"), x.ref, R, I, K, _p(act, BF16, "act"), act.stride(0),
                                         _p(ws), _p(dyn, I32, "dyn"), _stream()), "dfl_gemm_silu_mul_batch")
 
 
@@ -880,12 +873,7 @@ def gemm_argmax_batch(wp, x: BatchRowSource, R: int, V: int, K: int, row0: int, 
     if logits is not None:
         assert logits.dim() == 3 and logits.shape[1] == 16 and logits.shape[2] == V and logits.is_contiguous()
         lp, lst = _p(logits, BF16, "logits"), logits.stride(0)
-    if isinstance(wp, Fp8Weight):   # the ring form only, as above
-        check(lib().dfl_gemm_argmax_batch_fp8(*_fp8(wp, V, K, "wp"), x.ref, R, V, K, row0, nrows, _p(dyn, I32, "dyn"),
-                                              nrows_dyn_word, _p(ws), out_ids.data_ptr(), out_ids.stride(0), out_off, lp,
-                                              lst, _stream()), "dfl_gemm_argmax_batch_fp8")
-        return
-    check(lib().dfl_gemm_argmax_batch(_p(wp, BF16, "wp"), x.ref, R, V, K, row0, nrows, _p(dyn, I32, "dyn"),
+    check(lib().dfl_gemm_argmax_batch(_w(wp, V, K, "wp"), x.ref, R, V, K, row0, nrows, _p(dyn, I32, "dyn"),
                                       nrows_dyn_word, _p(ws), out_ids.data_ptr(), out_ids.stride(0), out_off, lp, lst,
                                       _stream()), "dfl_gemm_argmax_batch")
 
@@ -916,14 +904,7 @@ def gemm_sample_batch(wp, x: BatchRowSource, R: int, V: int, K: int, row0: int, 
         lp, lst = _p(logits, BF16, "logits"), logits.stride(0)
     if inv_ts is not None:
         assert inv_ts.numel() >= mt // tiles_per_req, "inv_ts"
-    if isinstance(wp, Fp8Weight):   # the ring form only, as gemm_argmax_batch's
-        check(lib().dfl_gemm_sample_batch_fp8(*_fp8(wp, V, K, "wp"), x.ref, R, V, K, row0, nrows, _p(dyn, I32, "dyn"),
-                                              nrows_dyn_word, _p(ws), out_ids.data_ptr(), out_ids.stride(0), out_off, lp,
-                                              lst, _p(seeds, I64, "seeds"), _p(inv_ts, F32, "inv_ts"),
-                                              0.0 if inv_ts is not None else inv_temperature(temperature), stream,
-                                              pos_word, pos_add, tiles_per_req, _stream()), "dfl_gemm_sample_batch_fp8")
-        return
-    check(lib().dfl_gemm_sample_batch(_p(wp, BF16, "wp"), x.ref, R, V, K, row0, nrows, _p(dyn, I32, "dyn"), nrows_dyn_word,
+    check(lib().dfl_gemm_sample_batch(_w(wp, V, K, "wp"), x.ref, R, V, K, row0, nrows, _p(dyn, I32, "dyn"), nrows_dyn_word,
                                       _p(ws), out_ids.data_ptr(), out_ids.stride(0), out_off, lp, lst,
                                       _p(seeds, I64, "seeds"), _p(inv_ts, F32, "inv_ts"),
                                       0.0 if inv_ts is not None else inv_temperature(temperature), stream, pos_word,

@@ -118,7 +118,7 @@ class NativeTarget:
         # single-request GEMMs once per 16-row tile (two passes; kept for A/B and as a second implementation for tests)
         self.wide_one_pass = True
         self._wide = None
-        self._wide_seed = None    # int64 [1]: the seed of an fp8 target's sampled wide head (dfl_gemm_sample_batch_fp8)
+        self._wide_seed = None    # int64 [1]: the seed of an fp8 target's sampled wide head (dfl_gemm_sample_batch on e4m3 codes)
         self._nuc_logits = None   # bf16 [32, V], made on the first filtered verify (top_k / top_p)
         self.moe_pair_kernel = True   # MoE gate/up at K <= 2048 through dfl_moe_gate_up (False: the general kernel)
         self.moe_shared_pass = True   # three or four tiles (ragged batch, candidates): one pass over the experts they share
@@ -190,13 +190,10 @@ class NativeTarget:
             """A Linear weight: as loaded, or (fp8) its dequantised values q * scale — written back over the wrapped
             model's own tensor — with the codes and scales kept in `store`."""
             m = w(name)
-            if not fp8:
-                return m
-            q, sc = ops.quantize_fp8_rows(m)
-            store[key] = (q, sc)
-            m = ops.dequantize_fp8_rows(q, sc)
-            with torch.no_grad():
-                sd[name].copy_(m)   # (the state dict's tensors are the parameters' storage; exact in any float dtype)
+            if fp8:
+                m, store[key] = ops.quantize_keep_fp8(m)
+                with torch.no_grad():
+                    sd[name].copy_(m)   # (the state dict's tensors are the parameters' storage; exact in any float dtype)
             return m
 
         if fp8:   # the head first: with tied embeddings self.embed, read below, is then the dequantised head
@@ -257,11 +254,7 @@ class NativeTarget:
             if fp8:
                 if "gate" not in l8:
                     raise NotImplementedError("NativeTarget: fp8_e4m3 needs dense MLP layers")
-                self.layers8.append({
-                    "qkv": ops.pack_weight_fp8(torch.cat([l8[k][0] for k in "qkv"]), torch.cat([l8[k][1] for k in "qkv"])),
-                    "o": ops.pack_weight_fp8(*l8["o"]),
-                    "gu": ops.pack_weight_gateup_fp8(*l8["gate"], *l8["up"]),
-                    "down": ops.pack_weight_fp8(*l8["down"])})
+                self.layers8.append(ops.pack_layer_fp8(l8))
             self.layers.append(lw)
             del qkv, l8
         self.norm = w("model.norm.weight")
@@ -409,10 +402,7 @@ class NativeTarget:
         qkv="parts" — replaced by their e4m3 twins when streams_fp8_tiles()."""
         if not self.streams_fp8_tiles():
             return self.layers
-        if qkv_parts not in self._tile_layers:
-            keys = ("gu", "o", "down") + (("qkv",) if qkv_parts else ())
-            self._tile_layers[qkv_parts] = [{**lw, **{k: l8[k] for k in keys}} for lw, l8 in zip(self.layers, self.layers8)]
-        return self._tile_layers[qkv_parts]
+        return ops.tile_layers(self.layers, self.layers8, qkv_parts, self._tile_layers)
 
     def fp8_tensors(self) -> tuple:
         """Every e4m3 code tensor and scale vector of an fp8 target and of fp8 experts (empty for bf16): what a captured

@@ -34,7 +34,8 @@
  *
  * One entry point per operation: dfl_gemm_argmax, dfl_sample_rows_nucleus, dfl_attn_head_cand, dfl_attn_head_batch,
  * dfl_accept_commit, dfl_gemm_sample_batch, dfl_kv_append_batch and dfl_accept_commit_batch each took over the arguments
- * of their former `_t` / `_timed` / `_rearm` twins (optional ones are nullable or have a neutral value, said at each).
+ * of their former `_t` / `_timed` / `_rearm` twins (optional ones are nullable or have a neutral value, said at each),
+ * and the ten launches that have an e4m3 form take the matrix as a dfl_weight in place of a former `_fp8` twin.
  */
 #ifndef DFLASH_HIP_H
 #define DFLASH_HIP_H
@@ -84,6 +85,26 @@ typedef struct dfl_rows {
   int32_t mode;
 } dfl_rows;
 
+/* What the matrix of a launch is (dfl_rows says where the activations come from).  An entry point takes one exactly when
+ * it has an e4m3 form; the others take the packed bf16 weight as `const void *wp`.
+ * ---- FP8 (OCP e4m3fn) weight streaming, weight-only (W8A16) ----
+ * The weight is stored as one e4m3 code per element plus one fp32 scale per output row; the kernels convert the codes
+ * to bf16 in registers (exact), run the same bf16 MFMA on the same bf16 activations, and multiply the fp32 K-sum by
+ * the row's scale before the epilogue's first rounding: Linear output = bf16(sum_k x[m][k] * q[n][k] * scale[n]).
+ * Packed layout [N/16][K/64][64 lanes][16 B]: lane l (column 16 t + (l & 15), kq = l >> 4) holds the 8 codes of
+ * k = 64 j + 8 kq .. in bytes 0-7 and those of k = 64 j + 32 + 8 kq .. in bytes 8-15.  K % 64 == 0.
+ * scale: fp32 [N] in PACKED tile order: scale[16 t + nl] belongs to column nl of packed tile t — row order for
+ * dfl_pack_weight_fp8, (gate tile p, up tile p) interleaved for dfl_pack_weight_gateup_fp8.  Any fp32 multiplier is
+ * taken; a code of 0x7f / 0xff is NaN.  Everything else of a launch is the same contract in both formats, argument for
+ * argument; what the e4m3 form narrows is said at each entry point.
+ * DFL_EINVAL: a null descriptor, a format other than the two, DFL_W_BF16 with a scale, DFL_W_E4M3 without one. */
+enum { DFL_W_BF16 = 0, DFL_W_E4M3 = 1 };
+typedef struct dfl_weight {
+  const void *wp;      /* packed weight: dfl_pack_weight[_gateup] (bf16) or dfl_pack_weight[_gateup]_fp8 (codes) */
+  const float *scale;  /* DFL_W_E4M3: fp32 scale per packed row, in packed tile order; DFL_W_BF16: must be NULL */
+  int32_t format;
+} dfl_weight;
+
 int dfl_version(void);
 const char *dfl_last_error(void);
 
@@ -95,6 +116,10 @@ int dfl_pack_weight(const void *w, void *wp, int N, int K, void *stream);
  * interleaved (gate tile t, up tile t) so SiLU(gate)*up fuses into the GEMM
  * epilogue (tf:models/qwen3/modeling_qwen3.py:81-83). */
 int dfl_pack_weight_gateup(const void *gate, const void *up, void *wp, int I, int K, void *stream);
+/* The same two for e4m3 codes (dfl_weight): q [N][K] uint8 row-major -> wp8 (N * K bytes); gate_q / up_q [I][K] -> one
+ * packed weight of 2I rows, tiles interleaved as dfl_pack_weight_gateup.  N%16==0 / I%16==0, K%64==0. */
+int dfl_pack_weight_fp8(const void *q, void *wp8, int N, int K, void *stream);
+int dfl_pack_weight_gateup_fp8(const void *gate_q, const void *up_q, void *wp8, int I, int K, void *stream);
 
 /* ---- per-cycle kernels ---- */
 
@@ -122,9 +147,10 @@ int dfl_gemm_f32(const void *wp, const dfl_rows *x0, const dfl_rows *x1, int mt,
                  const int32_t *dyn, void *stream);
 
 /* act = bf16(silu(bf16(x Wg^T))) * bf16(x Wu^T) written as frag16 [I/8][16][8]
- * (tf:...modeling_qwen3.py:82 inner expression).  wp from dfl_pack_weight_gateup.
- * K/32 <= 128 (no K split: the activation needs the finished sums). */
-int dfl_gemm_silu_mul(const void *wp_gateup, const dfl_rows *x, int I, int K, void *act_frag, const int32_t *dyn,
+ * (tf:...modeling_qwen3.py:82 inner expression).  w_gateup from dfl_pack_weight_gateup[_fp8].
+ * K/32 <= 128 (no K split: the activation needs the finished sums).  e4m3: gate and up sums are scaled separately,
+ * each before its bf16 rounding. */
+int dfl_gemm_silu_mul(const dfl_weight *w_gateup, const dfl_rows *x, int I, int K, void *act_frag, const int32_t *dyn,
                       void *stream);
 
 /* lm_head GEMM fused with the greedy unmask: ids[r] = argmax_n bf16(x[r] . W[n])
@@ -138,9 +164,10 @@ int dfl_gemm_silu_mul(const void *wp_gateup, const dfl_rows *x, int I, int K, vo
  * torch.topk(2) values: an exact tie gives 0) — the per-position confidence comes with the
  * unmask at no extra pass over the logits.
  * ev_start / ev_end (each optional): hipEvent_t recorded on `stream` right before and right after the GEMM launch (the
- * argmax finish launch comes behind ev_end): bench.py times the lm_head kernel itself with them (roofline.achieved). */
+ * argmax finish launch comes behind ev_end): bench.py times the lm_head kernel itself with them (roofline.achieved).
+ * e4m3: ids, logits and margins over bf16(sum * scale). */
 int64_t dfl_argmax_ws_bytes(void);
-int dfl_gemm_argmax(const void *wp, const dfl_rows *x, int V, int K, int row0, int nrows, const int32_t *dyn,
+int dfl_gemm_argmax(const dfl_weight *w, const dfl_rows *x, int V, int K, int row0, int nrows, const int32_t *dyn,
                     int nrows_dyn_word, void *ws, int64_t *out_ids, int out_off, void *logits, float *margin_out,
                     void *ev_start, void *ev_end, void *stream);
 
@@ -149,8 +176,9 @@ int dfl_gemm_argmax(const void *wp, const dfl_rows *x, int V, int K, int row0, i
  * inv_t = float32(1 / T), g the Gumbel noise of dfl_rng.h (Philox4x32-10, key = seed, counter = (n >> 2, p, extra,
  * stream)).  Tile row m draws position p = base + pos_add + m with base = pos_dyn[pos_word] (a device length record, so
  * a captured graph draws fresh positions on every replay) or, pos_dyn NULL, base = pos_base.  rng_stream 0 (TARGET):
- * extra = 0; 1 (DRAFT): extra = base.  Everything else as dfl_gemm_argmax; margin_out is the perturbed top-2 gap. */
-int dfl_gemm_sample(const void *wp, const dfl_rows *x, int V, int K, int row0, int nrows, const int32_t *dyn,
+ * extra = 0; 1 (DRAFT): extra = base.  Everything else as dfl_gemm_argmax; margin_out is the perturbed top-2 gap.
+ * e4m3: the draw perturbs bf16(sum * scale[n]), the logit dfl_gemm_argmax materialises for the same weight. */
+int dfl_gemm_sample(const dfl_weight *w, const dfl_rows *x, int V, int K, int row0, int nrows, const int32_t *dyn,
                     int nrows_dyn_word, void *ws, int64_t *out_ids, int out_off, void *logits, float *margin_out,
                     uint64_t seed, float inv_t, int rng_stream, const int32_t *pos_dyn, int pos_word, int pos_base,
                     int pos_add, void *stream);
@@ -161,38 +189,8 @@ int dfl_gemm_sample(const void *wp, const dfl_rows *x, int V, int K, int row0, i
  *   ss_out[n/16][m] <- sum over the tile's 16 columns of h_new^2 (optional; feeds the
  *   mode-2 row source of the next GEMM, so the RMSNorm is no launch of its own).
  * Any K: beyond 4096 the workgroup walks K in chunks itself (x must then be mode 0/1). */
-int dfl_gemm_resid(const void *wp, const dfl_rows *x, int N, int K, void *h_io, int64_t ldh, int add_residual,
+int dfl_gemm_resid(const dfl_weight *w, const dfl_rows *x, int N, int K, void *h_io, int64_t ldh, int add_residual,
                    void *tap, int64_t ldtap, float *ss_out, const int32_t *dyn, void *stream);
-
-/* ---- FP8 (OCP e4m3fn) weight streaming, weight-only (W8A16) ----
- * The weight is stored as one e4m3 code per element plus one fp32 scale per output row; the kernels convert the codes
- * to bf16 in registers (exact), run the same bf16 MFMA on the same bf16 activations, and multiply the fp32 K-sum by
- * the row's scale before the epilogue's first rounding: Linear output = bf16(sum_k x[m][k] * q[n][k] * scale[n]).
- * Packed layout [N/16][K/64][64 lanes][16 B]: lane l (column 16 t + (l & 15), kq = l >> 4) holds the 8 codes of
- * k = 64 j + 8 kq .. in bytes 0-7 and those of k = 64 j + 32 + 8 kq .. in bytes 8-15.  K % 64 == 0.
- * wscale: fp32 [N] in PACKED tile order: wscale[16 t + nl] belongs to column nl of packed tile t — row order for
- * dfl_pack_weight_fp8, (gate tile p, up tile p) interleaved for dfl_pack_weight_gateup_fp8.  Any fp32 multiplier is
- * taken; a code of 0x7f / 0xff is NaN.  Everything else is the bf16 sibling's contract, argument for argument. */
-/* q [N][K] uint8 row-major e4m3 codes -> wp8 (N * K bytes). */
-int dfl_pack_weight_fp8(const void *q, void *wp8, int N, int K, void *stream);
-/* gate_q / up_q [I][K] codes -> one packed weight of 2I rows, tiles interleaved as dfl_pack_weight_gateup. */
-int dfl_pack_weight_gateup_fp8(const void *gate_q, const void *up_q, void *wp8, int I, int K, void *stream);
-int dfl_gemm_resid_fp8(const void *wp, const float *wscale, const dfl_rows *x, int N, int K, void *h_io, int64_t ldh,
-                       int add_residual, void *tap, int64_t ldtap, float *ss_out, const int32_t *dyn, void *stream);
-/* gate and up sums are scaled separately, each before its bf16 rounding. */
-int dfl_gemm_silu_mul_fp8(const void *wp_gateup, const float *wscale, const dfl_rows *x, int I, int K, void *act_frag,
-                          const int32_t *dyn, void *stream);
-/* ids, logits and margins over bf16(sum * scale). */
-int dfl_gemm_argmax_fp8(const void *wp, const float *wscale, const dfl_rows *x, int V, int K, int row0, int nrows,
-                        const int32_t *dyn, int nrows_dyn_word, void *ws, int64_t *out_ids, int out_off, void *logits,
-                        float *margin_out, void *ev_start, void *ev_end, void *stream);
-/* dfl_gemm_sample with an e4m3 lm_head: the draw perturbs bf16(sum * scale[n]) — the logit dfl_gemm_argmax_fp8
- * materialises — so ids, logits and margins are those of the two-step draw over these logits.  Positions, streams and
- * every other argument as dfl_gemm_sample. */
-int dfl_gemm_sample_fp8(const void *wp8, const float *wscale, const dfl_rows *x, int V, int K, int row0, int nrows,
-                        const int32_t *dyn, int nrows_dyn_word, void *ws, int64_t *out_ids, int out_off, void *logits,
-                        float *margin_out, uint64_t seed, float inv_t, int rng_stream, const int32_t *pos_dyn,
-                        int pos_word, int pos_base, int pos_add, void *stream);
 
 /* h_out[m] = embed[ids[m]] for m < dyn[dyn_word] (model/dflash.py:237) and ss_out[m] =
  * sum of squares of that row (one partial per row: nss = 1 for the next GEMM). */
@@ -387,26 +385,19 @@ int dfl_gemm_silu_mul_experts(const void *wp_gateup, int64_t wp_expert_stride, c
 /* dfl_gemm_silu_mul_experts for K <= 2048 and frag16 rows (x_frag: [K/32][64] fragments): an item is the (gate, up)
  * tile PAIR of an active expert, the 16 waves of a workgroup meet once per pair (at K = 2048 a tile is 64 KB and the
  * per-tile meeting of the general kernel weighs twice what it does at K = 4096).  Same results, same layouts; rows
- * >= dyn[valid_word] count as zero (valid_word < 0 or dyn NULL: all 16). */
-int dfl_moe_gate_up(const void *wp_gateup, const void *x_frag, int E, int I, int K, void *act_frag, const int32_t *list,
+ * >= dyn[valid_word] count as zero (valid_word < 0 or dyn NULL: all 16).
+ * e4m3 (both launches; one fp32 scale per output row, read only): the same items, the same k-steps per wave in the same
+ * order, the fp32 sums multiplied by the row's scale in front of the first rounding point — with power-of-two scales
+ * bit-equal to the bf16 launch on q * scale.  The scales must be 64-byte aligned.
+ *  dfl_moe_gate_up: the experts' codes back to back, each 2*I*K bytes in dfl_pack_weight_gateup_fp8's layout; scale fp32
+ *    [E][2*I] in that layout's tile order (gate tile p's 16 scales, then up tile p's).  K % 64 == 0.
+ *  dfl_moe_down: expert e's codes (dfl_pack_weight_fp8 of its [N][I] weight) at wp + e * wp_expert_stride BYTES (>= N*I,
+ *    % 16 == 0); scale fp32 [E][N].  I % 64 == 0. */
+int dfl_moe_gate_up(const dfl_weight *w_gateup, const void *x_frag, int E, int I, int K, void *act_frag, const int32_t *list,
                     const int32_t *n_active, const int32_t *dyn, int valid_word, void *stream);
-int dfl_moe_down(const void *wp_down, int64_t wp_expert_stride, const void *act_frag, int64_t act_expert_stride,
+int dfl_moe_down(const dfl_weight *w_down, int64_t wp_expert_stride, const void *act_frag, int64_t act_expert_stride,
                  const void *wt, const int32_t *list, const int32_t *n_active, int E, int N, int I, int nsplit, float *out,
                  void *stream);
-/* The two expert launches on e4m3 codes (W8A16; one fp32 scale per output row, read only): the same items, the same
- * k-steps per wave in the same order, the fp32 sums multiplied by the row's scale in front of the first rounding point —
- * with power-of-two scales bit-equal to the bf16 launch on q * scale.
- *  dfl_moe_gate_up_fp8: wp8_gateup = the experts' codes back to back, each 2*I*K bytes in dfl_pack_weight_gateup_fp8's
- *    layout; wscale fp32 [E][2*I] in that layout's tile order (gate tile p's 16 scales, then up tile p's).
- *    K % 64 == 0, K <= 2048; wscale non-null and 64-byte aligned.
- *  dfl_moe_down_fp8: wp8_down = expert e's codes (dfl_pack_weight_fp8 of its [N][I] weight) at wp8_down + e *
- *    wp_expert_stride BYTES (>= N*I, % 16 == 0); wscale fp32 [E][N].  I % 64 == 0; wscale non-null and 64-byte aligned.
- * Anything else is DFL_EINVAL with a message and no launch. */
-int dfl_moe_gate_up_fp8(const void *wp8_gateup, const float *wscale, const void *x_frag, int E, int I, int K, void *act_frag,
-                        const int32_t *list, const int32_t *n_active, const int32_t *dyn, int valid_word, void *stream);
-int dfl_moe_down_fp8(const void *wp8_down, int64_t wp_expert_stride, const float *wscale, const void *act_frag,
-                     int64_t act_expert_stride, const void *wt, const int32_t *list, const int32_t *n_active, int E, int N,
-                     int I, int nsplit, float *out, void *stream);
 
 /* First-max-index argmax over the last axis (model/utils.py:28-29).
  * dtype: 0 = bf16, 1 = fp32.  ids int64 [rows]. */
@@ -581,19 +572,25 @@ int dfl_batch_ksplit(int K);
  * left zero by every launch), argmax candidates, fp32 partial tiles of the K parts */
 int64_t dfl_gemm_batch_ws_bytes(int N, int K);
 
+/* e4m3 weights in the batched GEMMs that take a dfl_weight ("The batch forms"): scales 64-byte
+ * aligned, K % 64 == 0, K >= 256.  The sums are multiplied by the columns' scales in front of the bf16 form's first
+ * rounding: gate and up separately, logits and argmax over bf16(sum * scale), and EVERY K part of dfl_gemm_f32_batch's
+ * output (the launch that sums the parts is untouched).  dfl_gemm_silu_mul_batch, dfl_gemm_argmax_batch and
+ * dfl_gemm_sample_batch run e4m3 in the ring form only: -22 for a source that is not frag16 (mode 0), never a quiet
+ * fall-back to the slab form or to the bf16 kernels. */
 /* dfl_gemm_f32 for R requests: out[c][r*16+m][n], c < dfl_batch_ksplit(K) partial sums
  * (out holds ksplit * dfl_batch_tiles(R) * 16 * N floats). */
-int dfl_gemm_f32_batch(const void *wp, const dfl_rows_batch *x, int R, int N, int K, float *out, const int32_t *dyn,
+int dfl_gemm_f32_batch(const dfl_weight *w, const dfl_rows_batch *x, int R, int N, int K, float *out, const int32_t *dyn,
                        void *stream);
 /* dfl_gemm_silu_mul for R requests; request r's frag16 output at act_frag + r * act_stride. */
-int dfl_gemm_silu_mul_batch(const void *wp_gateup, const dfl_rows_batch *x, int R, int I, int K, void *act_frag,
+int dfl_gemm_silu_mul_batch(const dfl_weight *w_gateup, const dfl_rows_batch *x, int R, int I, int K, void *act_frag,
                             int64_t act_stride, void *ws, const int32_t *dyn, void *stream);
 /* dfl_gemm_resid for R requests (h_io, tap, ss_out advance by their strides per request). */
 int dfl_gemm_resid_batch(const void *wp, const dfl_rows_batch *x, int R, int N, int K, void *h_io, int64_t ldh,
                          int64_t h_stride, int add_residual, void *tap, int64_t ldtap, int64_t tap_stride,
                          float *ss_out, int64_t ss_stride, void *ws, const int32_t *dyn, void *stream);
 /* dfl_gemm_argmax for R requests: out_ids[r * out_stride + out_off + (row - row0)]. */
-int dfl_gemm_argmax_batch(const void *wp, const dfl_rows_batch *x, int R, int V, int K, int row0, int nrows,
+int dfl_gemm_argmax_batch(const dfl_weight *w, const dfl_rows_batch *x, int R, int V, int K, int row0, int nrows,
                           const int32_t *dyn, int nrows_dyn_word, void *ws, int64_t *out_ids, int64_t out_stride,
                           int out_off, void *logits, int64_t logits_stride, void *stream);
 /* dfl_gemm_sample for R <= 4 request tiles on one pass over the weights (ring form, EPI_SAMPLE epilogue): tile t is tile
@@ -609,31 +606,10 @@ int dfl_gemm_argmax_batch(const void *wp, const dfl_rows_batch *x, int R, int V,
  *   otherwise         (0, negative, NaN) greedy: argmax_v bf16(logit_v), lowest v on ties, no Philox call and no noise —
  *                     bit for bit the ids of dfl_gemm_argmax_batch on the same inputs.
  * Device values are not validated. */
-int dfl_gemm_sample_batch(const void *wp, const dfl_rows_batch *x, int R, int V, int K, int row0, int nrows,
+int dfl_gemm_sample_batch(const dfl_weight *w, const dfl_rows_batch *x, int R, int V, int K, int row0, int nrows,
                           const int32_t *dyn, int nrows_dyn_word, void *ws, int64_t *out_ids, int64_t out_stride,
                           int out_off, void *logits, int64_t logits_stride, const int64_t *seeds, const float *inv_ts,
                           float inv_t, int rng_stream, int pos_word, int pos_add, int tiles_per_req, void *stream);
-/* ---- FP8 (e4m3) weights in the ragged batch ("The batch forms") ----
- * The three launches below with the weight as e4m3 codes (dfl_pack_weight_fp8 / dfl_pack_weight_gateup_fp8) and its
- * fp32 scales in packed tile order (64-byte aligned) in front; everything else is the bf16 sibling's contract, argument
- * for argument.  The sums are multiplied by the columns' scales in front of the sibling's first rounding: gate and up
- * separately, logits and argmax over bf16(sum * scale), and EVERY K part of dfl_gemm_f32_batch_fp8's output (the launch
- * that sums the parts is untouched).  K % 64 == 0, K >= 256.
- * dfl_gemm_silu_mul_batch_fp8, dfl_gemm_argmax_batch_fp8 and dfl_gemm_sample_batch_fp8 are the ring form and have no
- * slab form: -22 for a source that is not frag16 (mode 0).  Never a quiet fall-back to the bf16 kernels.
- * dfl_gemm_sample_batch_fp8: both epilogues of dfl_gemm_sample_batch (inv_ts NULL or not) over bf16(sum * scale). */
-int dfl_gemm_f32_batch_fp8(const void *wp8, const float *wscale, const dfl_rows_batch *x, int R, int N, int K, float *out,
-                           const int32_t *dyn, void *stream);
-int dfl_gemm_silu_mul_batch_fp8(const void *wp8_gateup, const float *wscale, const dfl_rows_batch *x, int R, int I, int K,
-                                void *act_frag, int64_t act_stride, void *ws, const int32_t *dyn, void *stream);
-int dfl_gemm_argmax_batch_fp8(const void *wp8, const float *wscale, const dfl_rows_batch *x, int R, int V, int K, int row0,
-                              int nrows, const int32_t *dyn, int nrows_dyn_word, void *ws, int64_t *out_ids,
-                              int64_t out_stride, int out_off, void *logits, int64_t logits_stride, void *stream);
-int dfl_gemm_sample_batch_fp8(const void *wp8, const float *wscale, const dfl_rows_batch *x, int R, int V, int K, int row0,
-                              int nrows, const int32_t *dyn, int nrows_dyn_word, void *ws, int64_t *out_ids,
-                              int64_t out_stride, int out_off, void *logits, int64_t logits_stride, const int64_t *seeds,
-                              const float *inv_ts, float inv_t, int rng_stream, int pos_word, int pos_add,
-                              int tiles_per_req, void *stream);
 /* dfl_embed_rows for R requests: ids[r * ids_stride + m]. */
 int dfl_embed_rows_batch(const void *embed, const int64_t *ids, int64_t ids_stride, int R, void *h_out,
                          int64_t h_stride, int H, float *ss_out, int64_t ss_stride, const int32_t *dyn, int dyn_word,

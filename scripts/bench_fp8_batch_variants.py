@@ -23,7 +23,7 @@ from dflash_amd import _lib, ops  # noqa: E402
 
 BF16, F32 = torch.bfloat16, torch.float32
 H, I, V, L, Q, KV = 4096, 12288, 151936, 5, 4096, 1024
-NAMES = ("dfl_gemm_f32_batch_fp8", "dfl_gemm_silu_mul_batch_fp8", "dfl_gemm_argmax_batch_fp8", "dfl_last_error")
+NAMES = ("dfl_gemm_f32_batch", "dfl_gemm_silu_mul_batch", "dfl_gemm_argmax_batch", "dfl_last_error")
 
 
 def load(path):
@@ -72,15 +72,15 @@ def main():
                   for _ in range(n_buf)]
 
             def launch(h, i):
-                w, sc = ws[i]
+                w = _lib.Weight(ws[i][0].data_ptr(), ws[i][1].data_ptr(), _lib.W_E4M3)
                 if gemm == "gate_up":
-                    rc = h.dfl_gemm_silu_mul_batch_fp8(w.data_ptr(), sc.data_ptr(), x.ref, R, I, K, act.data_ptr(), act.stride(0),
-                                                       gws.data_ptr(), dyn.data_ptr(), st)
+                    rc = h.dfl_gemm_silu_mul_batch(w, x.ref, R, I, K, act.data_ptr(), act.stride(0), gws.data_ptr(),
+                                                   dyn.data_ptr(), st)
                 elif gemm == "lm_head":
-                    rc = h.dfl_gemm_argmax_batch_fp8(w.data_ptr(), sc.data_ptr(), x.ref, R, V, K, 1, 15, dyn.data_ptr(),
-                                                     ops.DYN_BS, gws.data_ptr(), ids.data_ptr(), ids.stride(0), 1, None, 0, st)
+                    rc = h.dfl_gemm_argmax_batch(w, x.ref, R, V, K, 1, 15, dyn.data_ptr(), ops.DYN_BS, gws.data_ptr(),
+                                                 ids.data_ptr(), ids.stride(0), 1, None, 0, st)
                 else:
-                    rc = h.dfl_gemm_f32_batch_fp8(w.data_ptr(), sc.data_ptr(), x.ref, R, N, K, part.data_ptr(), dyn.data_ptr(), st)
+                    rc = h.dfl_gemm_f32_batch(w, x.ref, R, N, K, part.data_ptr(), dyn.data_ptr(), st)
                 assert rc == 0, h.dfl_last_error()
 
             for h in libs.values():          # warm-up of each build

@@ -75,6 +75,12 @@ def run(label, fn):
 
 
 S = torch.cuda.current_stream().cuda_stream
+
+
+def bf(t):
+    return _lib.Weight(t.data_ptr(), None, _lib.W_BF16)
+
+
 wq = torch.randn(6144 * H // 2, device=dev).view(BF16)[:6144 * H].contiguous()
 part = torch.empty(2 * 16 * 6144, device=dev)
 run("qkv f32 normed ksplit2", lambda: dbg.dfl_gemm_f32(wq.data_ptr(), normed.ref, None, 1, 6144, H, 2, part.data_ptr(), dyn.data_ptr(), S))
@@ -82,10 +88,10 @@ run("qkv f32 frag   ksplit2", lambda: dbg.dfl_gemm_f32(wq.data_ptr(), fragH.ref,
 wo = torch.randn(H * H // 2, device=dev).view(BF16)[:H * H].contiguous()
 hh = torch.zeros(16, H, device=dev, dtype=BF16)
 sso = torch.zeros(H, device=dev)
-run("o resid frag", lambda: dbg.dfl_gemm_resid(wo.data_ptr(), fragH.ref, H, H, hh.data_ptr(), H, 1, None, 0, sso.data_ptr(), dyn.data_ptr(), S))
+run("o resid frag", lambda: dbg.dfl_gemm_resid(bf(wo), fragH.ref, H, H, hh.data_ptr(), H, 1, None, 0, sso.data_ptr(), dyn.data_ptr(), S))
 wg = torch.randn(2 * I * H // 2, device=dev).view(BF16)[:2 * I * H].contiguous()
 act = torch.empty(16 * I, device=dev, dtype=BF16)
-run("gate/up silu normed", lambda: dbg.dfl_gemm_silu_mul(wg.data_ptr(), normed.ref, I, H, act.data_ptr(), dyn.data_ptr(), S))
-run("gate/up silu frag", lambda: dbg.dfl_gemm_silu_mul(wg.data_ptr(), fragH.ref, I, H, act.data_ptr(), dyn.data_ptr(), S))
+run("gate/up silu normed", lambda: dbg.dfl_gemm_silu_mul(bf(wg), normed.ref, I, H, act.data_ptr(), dyn.data_ptr(), S))
+run("gate/up silu frag", lambda: dbg.dfl_gemm_silu_mul(bf(wg), fragH.ref, I, H, act.data_ptr(), dyn.data_ptr(), S))
 wd = torch.randn(H * I // 2, device=dev).view(BF16)[:H * I].contiguous()
-run("down resid frag (chunked)", lambda: dbg.dfl_gemm_resid(wd.data_ptr(), fragI.ref, H, I, hh.data_ptr(), H, 1, None, 0, sso.data_ptr(), dyn.data_ptr(), S))
+run("down resid frag (chunked)", lambda: dbg.dfl_gemm_resid(bf(wd), fragI.ref, H, I, hh.data_ptr(), H, 1, None, 0, sso.data_ptr(), dyn.data_ptr(), S))

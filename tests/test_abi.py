@@ -58,9 +58,14 @@ def test_argument_validation_needs_no_gpu():
 
 
 def test_no_entry_point_has_a_twin():
-    """One entry point per operation: no declared name is another declared name plus _t or _timed."""
+    """One entry point per operation: no declared name is another declared name plus _t, _timed or _fp8 — a launch
+    takes its weight's format in a dfl_weight.  The two packers are the exception: packing e4m3 codes is a separate
+    operation on another element type, and nothing about it is chosen at launch."""
     names = set(_declared())
-    twins = sorted(n for n in names for suffix in ("_t", "_timed") if n.endswith(suffix) and n[:-len(suffix)] in names)
+    packers = {"dfl_pack_weight_fp8", "dfl_pack_weight_gateup_fp8"}
+    assert packers <= names
+    twins = sorted(n for n in names - packers for suffix in ("_t", "_timed", "_fp8")
+                   if n.endswith(suffix) and n[:-len(suffix)] in names)
     assert not twins, twins
 
 
@@ -96,7 +101,7 @@ def test_folded_entry_points_keep_the_conditional_checks():
     # no per-slot 1/T array: the host value is the temperature, and 0 is none
     x = _lib.RowsBatch()
     x.r0.frag, x.r0.mode, x.frag_stride = 16, 0, 4096 * 16
-    refused("dfl_gemm_sample_batch", 16, C.byref(x), 2, 64, 256, 0, 16, 16, 2, 16, 16, 16, 0, None, 0, 16, None, 0.0, 0, 3,
+    refused("dfl_gemm_sample_batch", _lib.Weight(16, None, _lib.W_BF16), C.byref(x), 2, 64, 256, 0, 16, 16, 2, 16, 16, 16, 0, None, 0, 16, None, 0.0, 0, 3,
             1, 1, None)
     assert b"inv_t" in h.dfl_last_error()
     refused("dfl_sample_rows_nucleus", 16, 64, 1024, 1, 64, 0, 16, None, -1, -1, 0, None, 0, 1, None, 1, None, 0, None,
@@ -106,6 +111,20 @@ def test_folded_entry_points_keep_the_conditional_checks():
     refused("dfl_kv_append_batch", 16, 1, 4096, 256, 0, 128, 256, 1, 2, 16, 2, None, 128, 1e-6, 16, 16, 4096, 16, 16,
             1024, 1 << 20, 1 << 18, 16, 0, None)
     assert b"batch shape" in h.dfl_last_error()
+    # the weight descriptor, on a single-request and a batch entry point: a format that is neither of the two, e4m3
+    # codes without their scales, a bf16 weight with a scale vector, no descriptor at all
+    rows = _lib.Rows()
+    rows.frag, rows.mode, rows.valid_word = 16, 0, -1
+    for name, rest in (("dfl_gemm_resid", (C.byref(rows), 16, 64, 16, 16, 0, None, 0, None, None, None)),
+                       ("dfl_gemm_f32_batch", (C.byref(x), 2, 64, 256, 16, None, None))):
+        refused(name, _lib.Weight(4096, 4096, 2), *rest)
+        assert b"format 2" in h.dfl_last_error()
+        refused(name, _lib.Weight(4096, None, _lib.W_E4M3), *rest)
+        assert b"null" in h.dfl_last_error()
+        refused(name, _lib.Weight(4096, 4096, _lib.W_BF16), *rest)
+        assert b"no scale" in h.dfl_last_error()
+        refused(name, None, *rest)
+        assert b"descriptor" in h.dfl_last_error()
 
 
 def test_product_has_no_cpu_path():

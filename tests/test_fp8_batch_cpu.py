@@ -1,10 +1,11 @@
 """FP8 (e4m3) draft weights in the ragged batch, the parts that need no GPU ("The batch forms"):
-the three entry points' argument validation, and the host form rules behind the cases of test_hip_fp8_batch.py."""
+the three entry points' argument validation on a Weight(wp, scale, W_E4M3) descriptor, and the host form rules behind the
+cases of test_hip_fp8_batch.py."""
 import ctypes as C
 
 import fp8_batch_cases as FC
 
-NAMES = ("dfl_gemm_f32_batch_fp8", "dfl_gemm_silu_mul_batch_fp8", "dfl_gemm_argmax_batch_fp8")
+NAMES = ("dfl_gemm_f32_batch", "dfl_gemm_silu_mul_batch", "dfl_gemm_argmax_batch")
 P = 4096   # stands for a device pointer (64-byte aligned); nothing is launched
 
 
@@ -20,12 +21,14 @@ def _source(mode):
 
 
 def _call(h, name, wp, sc, x, R, N, K):
+    from dflash_amd import _lib
     xr = C.byref(x) if x is not None else None
-    if name == "dfl_gemm_f32_batch_fp8":
-        return h.dfl_gemm_f32_batch_fp8(wp, sc, xr, R, N, K, P, None, None)
-    if name == "dfl_gemm_silu_mul_batch_fp8":
-        return h.dfl_gemm_silu_mul_batch_fp8(wp, sc, xr, R, N, K, P, 16 * N, P, None, None)
-    return h.dfl_gemm_argmax_batch_fp8(wp, sc, xr, R, N, K, 1, 15, None, -1, P, P, 16, 1, None, 0, None)
+    w = _lib.Weight(wp, sc, _lib.W_E4M3)
+    if name == "dfl_gemm_f32_batch":
+        return h.dfl_gemm_f32_batch(w, xr, R, N, K, P, None, None)
+    if name == "dfl_gemm_silu_mul_batch":
+        return h.dfl_gemm_silu_mul_batch(w, xr, R, N, K, P, 16 * N, P, None, None)
+    return h.dfl_gemm_argmax_batch(w, xr, R, N, K, 1, 15, None, -1, P, P, 16, 1, None, 0, None)
 
 
 def test_fp8_batch_entry_points_validate_without_gpu():
@@ -56,10 +59,11 @@ def test_fp8_batch_entry_points_validate_without_gpu():
 
 
 def test_fp8_batch_signatures_mirror_their_siblings():
+    """One name per launch: the e4m3 form is the same entry point with the format in its weight descriptor."""
     from dflash_amd import _lib
     for name in NAMES:
-        a, b = _lib.SIGNATURES[name[:-4]][1], _lib.SIGNATURES[name][1]
-        assert b == [a[0], _lib._p] + a[1:], name
+        assert _lib.SIGNATURES[name][1][0] is C.POINTER(_lib.Weight), name
+        assert name + "_fp8" not in _lib.SIGNATURES, name
 
 
 def test_gpu_cases_reach_every_form():

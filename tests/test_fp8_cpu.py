@@ -1,5 +1,5 @@
 """FP8 (e4m3) draft weights, the parts that need no GPU: the row quantiser's contract and the new entry points'
-argument validation."""
+argument validation.  The launches take the codes as a Weight(wp, scale, W_E4M3) descriptor."""
 import ctypes as C
 import os
 import re
@@ -10,8 +10,7 @@ import torch
 import helpers as H
 
 BF16 = torch.bfloat16
-FP8_ENTRY_POINTS = ["dfl_pack_weight_fp8", "dfl_pack_weight_gateup_fp8", "dfl_gemm_resid_fp8", "dfl_gemm_silu_mul_fp8",
-                    "dfl_gemm_argmax_fp8"]
+FP8_PACKERS = ["dfl_pack_weight_fp8", "dfl_pack_weight_gateup_fp8"]
 
 
 def _rows():
@@ -76,15 +75,15 @@ def test_fp8_entry_points_are_declared_bound_and_exported():
     from dflash_amd import _lib
     names = _declared()
     handle = _lib.lib()
-    for n in FP8_ENTRY_POINTS:
+    for n in FP8_PACKERS + ["dfl_gemm_resid", "dfl_gemm_silu_mul", "dfl_gemm_argmax"]:
         assert n in names, f"{n} missing from include/dflash_hip.h"
         assert n in _lib.SIGNATURES, f"{n} missing from SIGNATURES"
         assert isinstance(getattr(handle, n), C._CFuncPtr)
-    # the bf16 siblings' parameter lists with the scale vector behind the packed weight
+    # one launch name per operation: the weight's format travels in the descriptor that takes the packed weight's place
     for n in ("dfl_gemm_resid", "dfl_gemm_silu_mul", "dfl_gemm_argmax"):
-        a, b = _lib.SIGNATURES[n][1], _lib.SIGNATURES[n + "_fp8"][1]
-        assert b == [a[0], _lib._p] + a[1:], n
-    for n in ("dfl_pack_weight", "dfl_pack_weight_gateup"):
+        assert _lib.SIGNATURES[n][1][0] is C.POINTER(_lib.Weight), n
+        assert n + "_fp8" not in names and n + "_fp8" not in _lib.SIGNATURES, n
+    for n in ("dfl_pack_weight", "dfl_pack_weight_gateup"):   # the packers stay: another element type, nothing chosen at launch
         assert _lib.SIGNATURES[n] == _lib.SIGNATURES[n + "_fp8"]
 
 
@@ -97,6 +96,9 @@ def test_fp8_entry_points_validate_without_gpu():
     x.frag, x.mode, x.valid_word = 16, 0, -1
     xr = C.byref(x)
 
+    def w8(wp, scale):
+        return _lib.Weight(wp, scale, _lib.W_E4M3)
+
     def refused(name, *args, text=None):
         assert getattr(h, name)(*args) == -22, (name, args)
         err = h.dfl_last_error()
@@ -108,17 +110,17 @@ def test_fp8_entry_points_validate_without_gpu():
         p = None if text == b"null" else 16
         refused("dfl_pack_weight_fp8", p, 16, N, K, None, text=text)
         refused("dfl_pack_weight_gateup_fp8", 16, p, 16, N, K, None, text=text)
-        refused("dfl_gemm_resid_fp8", 16, p, xr, N, K, 16, N, 0, None, 0, None, None, None, text=text)
-        refused("dfl_gemm_silu_mul_fp8", 16, p, xr, N, K, 16, None, None, text=text)
-        refused("dfl_gemm_argmax_fp8", 16, p, xr, N, K, 0, 16, None, -1, 16, 16, 0, None, None, None, None, None, text=text)
+        refused("dfl_gemm_resid", w8(16, p), xr, N, K, 16, N, 0, None, 0, None, None, None, text=text)
+        refused("dfl_gemm_silu_mul", w8(16, p), xr, N, K, 16, None, None, text=text)
+        refused("dfl_gemm_argmax", w8(16, p), xr, N, K, 0, 16, None, -1, 16, 16, 0, None, None, None, None, None, text=text)
     # a missing weight / output pointer, and a missing row source
-    refused("dfl_gemm_resid_fp8", None, 16, xr, 16, 64, 16, 16, 0, None, 0, None, None, None, text=b"null")
-    refused("dfl_gemm_resid_fp8", 16, 16, xr, 16, 64, None, 16, 0, None, 0, None, None, None, text=b"null")
-    refused("dfl_gemm_resid_fp8", 16, 16, None, 16, 64, 16, 16, 0, None, 0, None, None, None, text=b"null")
-    refused("dfl_gemm_silu_mul_fp8", 16, 16, xr, 16, 64, None, None, None, text=b"null")
-    refused("dfl_gemm_argmax_fp8", 16, 16, xr, 16, 64, 0, 16, None, -1, None, 16, 0, None, None, None, None, None, text=b"null")
+    refused("dfl_gemm_resid", w8(None, 16), xr, 16, 64, 16, 16, 0, None, 0, None, None, None, text=b"null")
+    refused("dfl_gemm_resid", w8(16, 16), xr, 16, 64, None, 16, 0, None, 0, None, None, None, text=b"null")
+    refused("dfl_gemm_resid", w8(16, 16), None, 16, 64, 16, 16, 0, None, 0, None, None, None, text=b"null")
+    refused("dfl_gemm_silu_mul", w8(16, 16), xr, 16, 64, None, None, None, text=b"null")
+    refused("dfl_gemm_argmax", w8(16, 16), xr, 16, 64, 0, 16, None, -1, None, 16, 0, None, None, None, None, None, text=b"null")
     # a normalised source beyond K = 4096 (the chunked form takes none), as the bf16 sibling
-    assert h.dfl_gemm_silu_mul_fp8(16, 16, xr, 16, 8192, 16, None, None) == -22
+    assert h.dfl_gemm_silu_mul(w8(16, 16), xr, 16, 8192, 16, None, None) == -22
 
 
 def test_weight_format_is_validated():

@@ -80,13 +80,12 @@ def test_expert_fp8_entry_points_are_declared_bound_and_exported():
     txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(H.ROOT, "include", "dflash_hip.h")).read(), flags=re.S)
     names = set(re.findall(r"\b(dfl_[a-z0-9_]+)\s*\(", txt))
     handle = _lib.lib()
-    for n in ("dfl_moe_gate_up_fp8", "dfl_moe_down_fp8"):
+    for n in ("dfl_moe_gate_up", "dfl_moe_down"):
         assert n in names and n in _lib.SIGNATURES and isinstance(getattr(handle, n), C._CFuncPtr), n
         assert len(_lib.SIGNATURES[n][1]) == _header_arity(txt, n), n
-    a, b = _lib.SIGNATURES["dfl_moe_gate_up"][1], _lib.SIGNATURES["dfl_moe_gate_up_fp8"][1]
-    assert b == [a[0], _lib._p] + a[1:]             # the scale vector behind the packed weight
-    a, b = _lib.SIGNATURES["dfl_moe_down"][1], _lib.SIGNATURES["dfl_moe_down_fp8"][1]
-    assert b == a[:2] + [_lib._p] + a[2:]           # ... and behind its stride
+        # the experts' codes and scales arrive in the weight descriptor: one name per launch
+        assert _lib.SIGNATURES[n][1][0] is C.POINTER(_lib.Weight), n
+        assert n + "_fp8" not in names and n + "_fp8" not in _lib.SIGNATURES, n
     assert handle.dfl_version() == 1
     assert re.search(r"#define\s+DFL_ABI_VERSION\s+1\b", txt)
 
@@ -104,33 +103,36 @@ def test_expert_fp8_entry_points_validate_without_gpu():
         if text:
             assert text in err, (name, err)
 
-    # dfl_moe_gate_up_fp8(wp8, wscale, x_frag, E, I, K, act, list, n_active, dyn, valid_word, stream)
-    def gu(wp=64, sc=64, x=64, E=8, I=64, K=512, act=64, lst=64, n=64):
-        return (wp, sc, x, E, I, K, act, lst, n, None, -1, None)
-    refused("dfl_moe_gate_up_fp8", *gu(K=96), text=b"multiple of 64")
-    refused("dfl_moe_gate_up_fp8", *gu(K=1056), text=b"multiple of 64")
-    refused("dfl_moe_gate_up_fp8", *gu(K=2112), text=b"K <= 2048")
-    refused("dfl_moe_gate_up_fp8", *gu(K=4096), text=b"K <= 2048")
-    refused("dfl_moe_gate_up_fp8", *gu(sc=None), text=b"null scale")
-    refused("dfl_moe_gate_up_fp8", *gu(sc=64 + 4), text=b"64-byte aligned")
-    refused("dfl_moe_gate_up_fp8", *gu(wp=None), text=b"null")
-    refused("dfl_moe_gate_up_fp8", *gu(lst=None), text=b"null")
-    refused("dfl_moe_gate_up_fp8", *gu(I=40))
+    def w8(wp, sc):
+        return _lib.Weight(wp, sc, _lib.W_E4M3)
 
-    # dfl_moe_down_fp8(wp8, stride_bytes, wscale, act, act_stride, wt, list, n_active, E, N, I, nsplit, out, stream)
+    # dfl_moe_gate_up({wp8, wscale, e4m3}, x_frag, E, I, K, act, list, n_active, dyn, valid_word, stream)
+    def gu(wp=64, sc=64, x=64, E=8, I=64, K=512, act=64, lst=64, n=64):
+        return (w8(wp, sc), x, E, I, K, act, lst, n, None, -1, None)
+    refused("dfl_moe_gate_up", *gu(K=96), text=b"multiple of 64")
+    refused("dfl_moe_gate_up", *gu(K=1056), text=b"multiple of 64")
+    refused("dfl_moe_gate_up", *gu(K=2112), text=b"K <= 2048")
+    refused("dfl_moe_gate_up", *gu(K=4096), text=b"K <= 2048")
+    refused("dfl_moe_gate_up", *gu(sc=None), text=b"null scale")
+    refused("dfl_moe_gate_up", *gu(sc=64 + 4), text=b"64-byte aligned")
+    refused("dfl_moe_gate_up", *gu(wp=None), text=b"null")
+    refused("dfl_moe_gate_up", *gu(lst=None), text=b"null")
+    refused("dfl_moe_gate_up", *gu(I=40))
+
+    # dfl_moe_down({wp8, wscale, e4m3}, stride_bytes, act, act_stride, wt, list, n_active, E, N, I, nsplit, out, stream)
     def dn(wp=64, stride=None, sc=64, act=64, astride=None, E=8, N=64, I=128, nsplit=4, out=64):
-        return (wp, N * I if stride is None else stride, sc, act, 16 * I if astride is None else astride, 64, 64, 64, E, N, I,
+        return (w8(wp, sc), N * I if stride is None else stride, act, 16 * I if astride is None else astride, 64, 64, 64, E, N, I,
                 nsplit, out, None)
-    refused("dfl_moe_down_fp8", *dn(I=96), text=b"multiple of 64")
-    refused("dfl_moe_down_fp8", *dn(I=32), text=b"multiple of 64")
-    refused("dfl_moe_down_fp8", *dn(sc=None), text=b"null scale")
-    refused("dfl_moe_down_fp8", *dn(sc=64 + 4), text=b"64-byte aligned")
-    refused("dfl_moe_down_fp8", *dn(stride=64 * 128 - 16), text=b"strides")     # bytes of codes: shorter than N * I
-    refused("dfl_moe_down_fp8", *dn(stride=64 * 128 + 8), text=b"strides")      # no whole 16-byte words
-    refused("dfl_moe_down_fp8", *dn(astride=16 * 128 - 8), text=b"strides")
-    refused("dfl_moe_down_fp8", *dn(out=None), text=b"null")
-    refused("dfl_moe_down_fp8", *dn(nsplit=17))
-    refused("dfl_moe_down_fp8", *dn(N=72))
+    refused("dfl_moe_down", *dn(I=96), text=b"multiple of 64")
+    refused("dfl_moe_down", *dn(I=32), text=b"multiple of 64")
+    refused("dfl_moe_down", *dn(sc=None), text=b"null scale")
+    refused("dfl_moe_down", *dn(sc=64 + 4), text=b"64-byte aligned")
+    refused("dfl_moe_down", *dn(stride=64 * 128 - 16), text=b"strides")     # bytes of codes: shorter than N * I
+    refused("dfl_moe_down", *dn(stride=64 * 128 + 8), text=b"strides")      # no whole 16-byte words
+    refused("dfl_moe_down", *dn(astride=16 * 128 - 8), text=b"strides")
+    refused("dfl_moe_down", *dn(out=None), text=b"null")
+    refused("dfl_moe_down", *dn(nsplit=17))
+    refused("dfl_moe_down", *dn(N=72))
 
 
 # ---------------------------------------------------------------------------------------------- the quantiser

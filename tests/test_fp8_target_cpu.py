@@ -96,18 +96,21 @@ def test_constructor_refuses_before_any_device_work():
 
 
 # ---------------------------------------------------------------------------------------------- the C ABI
-NEW = ("dfl_gemm_sample_fp8", "dfl_gemm_sample_batch_fp8")
+SAMPLED = ("dfl_gemm_sample", "dfl_gemm_sample_batch")
+PACKERS = {"dfl_pack_weight_fp8", "dfl_pack_weight_gateup_fp8"}   # another element type, nothing chosen at launch
 
 
-def test_sampled_fp8_entry_points_are_declared_bound_and_exported():
+def test_sampled_entry_points_take_a_descriptor_and_no_fp8_launch_is_declared():
     from dflash_amd import _lib
     txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(H.ROOT, "include", "dflash_hip.h")).read(), flags=re.S)
     names = set(re.findall(r"\b(dfl_[a-z0-9_]+)\s*\(", txt))
     handle = _lib.lib()
-    for n in NEW:
+    for n in SAMPLED:
         assert n in names and n in _lib.SIGNATURES and isinstance(getattr(handle, n), C._CFuncPtr), n
-        a, b = _lib.SIGNATURES[n[:-4]][1], _lib.SIGNATURES[n][1]
-        assert b == [a[0], _lib._p] + a[1:], n      # the sibling's list, the scale vector behind the packed weight
+        assert _lib.SIGNATURES[n][1][0] is C.POINTER(_lib.Weight), n     # the e4m3 lm_head arrives in the descriptor
+        assert re.search(r"\b" + n + r"\s*\(\s*const\s+dfl_weight\s*\*", txt), n
+    assert {n for n in names | set(_lib.SIGNATURES) if n.endswith("_fp8")} == PACKERS
+    assert not any(hasattr(handle, n + "_fp8") for n in SAMPLED)
     assert handle.dfl_version() == 1
     assert re.search(r"#define\s+DFL_ABI_VERSION\s+1\b", txt)
 
@@ -129,46 +132,49 @@ def test_sampled_fp8_entry_points_validate_without_gpu():
             assert text in err, (name, err)
 
     f = C.c_float
-    # ---- dfl_gemm_sample_fp8(wp8, wscale, x, V, K, row0, nrows, dyn, word, ws, ids, off, logits, margins, seed, inv_t,
-    #                          stream, pos_dyn, pos_word, pos_base, pos_add, hip stream)
-    def one(wp=64, sc=64, V=64, K=512, row0=0, nrows=16, ws=64, ids=64, inv_t=1.4, stream=0, pos_dyn=None, pos_word=3):
-        return (wp, sc, C.byref(x), V, K, row0, nrows, None, -1, ws, ids, 0, None, None, 5, f(inv_t), stream, pos_dyn,
-                pos_word, 0, 1, None)
-    refused("dfl_gemm_sample_fp8", *one(wp=None), text=b"null")
-    refused("dfl_gemm_sample_fp8", *one(sc=None), text=b"null")
-    refused("dfl_gemm_sample_fp8", *one(ids=None), text=b"null")
-    refused("dfl_gemm_sample_fp8", *one(K=544), text=b"K%64")
-    refused("dfl_gemm_sample_fp8", *one(V=72), text=b"%16")
-    refused("dfl_gemm_sample_fp8", *one(inv_t=0.0), text=b"inv_t")
-    refused("dfl_gemm_sample_fp8", *one(stream=2), text=b"stream")
-    refused("dfl_gemm_sample_fp8", *one(pos_dyn=64, pos_word=8), text=b"pos_word")
-    assert h.dfl_gemm_sample_fp8(*one(row0=4, nrows=13)) == -22
-    assert h.dfl_gemm_sample_fp8(*one(K=8192)) == -22          # beyond 4096: the head needs finished sums
 
-    # ---- dfl_gemm_sample_batch_fp8(wp8, wscale, x, R, V, K, row0, nrows, dyn, word, ws, ids, stride, off, logits,
-    #                                lstride, seeds, inv_ts, inv_t, stream, pos_word, pos_add, tiles_per_req, hip stream)
+    def w8(wp, sc):
+        return _lib.Weight(wp, sc, _lib.W_E4M3)
+    # ---- dfl_gemm_sample({wp8, wscale, e4m3}, x, V, K, row0, nrows, dyn, word, ws, ids, off, logits, margins, seed, inv_t,
+    #                      stream, pos_dyn, pos_word, pos_base, pos_add, hip stream)
+    def one(wp=64, sc=64, V=64, K=512, row0=0, nrows=16, ws=64, ids=64, inv_t=1.4, stream=0, pos_dyn=None, pos_word=3):
+        return (w8(wp, sc), C.byref(x), V, K, row0, nrows, None, -1, ws, ids, 0, None, None, 5, f(inv_t), stream, pos_dyn,
+                pos_word, 0, 1, None)
+    refused("dfl_gemm_sample", *one(wp=None), text=b"null")
+    refused("dfl_gemm_sample", *one(sc=None), text=b"null")
+    refused("dfl_gemm_sample", *one(ids=None), text=b"null")
+    refused("dfl_gemm_sample", *one(K=544), text=b"K%64")
+    refused("dfl_gemm_sample", *one(V=72), text=b"%16")
+    refused("dfl_gemm_sample", *one(inv_t=0.0), text=b"inv_t")
+    refused("dfl_gemm_sample", *one(stream=2), text=b"stream")
+    refused("dfl_gemm_sample", *one(pos_dyn=64, pos_word=8), text=b"pos_word")
+    assert h.dfl_gemm_sample(*one(row0=4, nrows=13)) == -22
+    assert h.dfl_gemm_sample(*one(K=8192)) == -22          # beyond 4096: the head needs finished sums
+
+    # ---- dfl_gemm_sample_batch({wp8, wscale, e4m3}, x, R, V, K, row0, nrows, dyn, word, ws, ids, stride, off, logits,
+    #                            lstride, seeds, inv_ts, inv_t, stream, pos_word, pos_add, tiles_per_req, hip stream)
     def ring(wp=64, sc=64, src=xb, R=2, V=64, K=512, dyn=64, seeds=64, inv_ts=None, inv_t=1.4, stream=0, pos_word=3, tpr=1):
-        return (wp, sc, C.byref(src) if src is not None else None, R, V, K, 0, 16, dyn, 2, 64, 64, 16, 0, None, 0, seeds,
+        return (w8(wp, sc), C.byref(src) if src is not None else None, R, V, K, 0, 16, dyn, 2, 64, 64, 16, 0, None, 0, seeds,
                 inv_ts, f(inv_t), stream, pos_word, 1, tpr, None)
-    refused("dfl_gemm_sample_batch_fp8", *ring(wp=None), text=b"null")
-    refused("dfl_gemm_sample_batch_fp8", *ring(sc=None), text=b"null")
-    refused("dfl_gemm_sample_batch_fp8", *ring(src=None), text=b"null")
-    refused("dfl_gemm_sample_batch_fp8", *ring(seeds=None), text=b"null")
-    refused("dfl_gemm_sample_batch_fp8", *ring(dyn=None), text=b"null")
-    refused("dfl_gemm_sample_batch_fp8", *ring(sc=68), text=b"64-byte aligned")
-    refused("dfl_gemm_sample_batch_fp8", *ring(K=288), text=b"K%64")
-    refused("dfl_gemm_sample_batch_fp8", *ring(K=192), text=b"K >= 256")
-    refused("dfl_gemm_sample_batch_fp8", *ring(R=0), text=b"R")
-    refused("dfl_gemm_sample_batch_fp8", *ring(R=5), text=b"R")
-    refused("dfl_gemm_sample_batch_fp8", *ring(V=72), text=b"%16")
-    refused("dfl_gemm_sample_batch_fp8", *ring(inv_t=0.0), text=b"inv_t")
-    refused("dfl_gemm_sample_batch_fp8", *ring(stream=3), text=b"stream")
-    refused("dfl_gemm_sample_batch_fp8", *ring(tpr=3), text=b"tiles_per_req")
-    refused("dfl_gemm_sample_batch_fp8", *ring(R=3, tpr=2), text=b"tiles_per_req")
+    refused("dfl_gemm_sample_batch", *ring(wp=None), text=b"null")
+    refused("dfl_gemm_sample_batch", *ring(sc=None), text=b"null")
+    refused("dfl_gemm_sample_batch", *ring(src=None), text=b"null")
+    refused("dfl_gemm_sample_batch", *ring(seeds=None), text=b"null")
+    refused("dfl_gemm_sample_batch", *ring(dyn=None), text=b"null")
+    refused("dfl_gemm_sample_batch", *ring(sc=68), text=b"64-byte aligned")
+    refused("dfl_gemm_sample_batch", *ring(K=288), text=b"K%64")
+    refused("dfl_gemm_sample_batch", *ring(K=192), text=b"K >= 256")
+    refused("dfl_gemm_sample_batch", *ring(R=0), text=b"R")
+    refused("dfl_gemm_sample_batch", *ring(R=5), text=b"R")
+    refused("dfl_gemm_sample_batch", *ring(V=72), text=b"%16")
+    refused("dfl_gemm_sample_batch", *ring(inv_t=0.0), text=b"inv_t")
+    refused("dfl_gemm_sample_batch", *ring(stream=3), text=b"stream")
+    refused("dfl_gemm_sample_batch", *ring(tpr=3), text=b"tiles_per_req")
+    refused("dfl_gemm_sample_batch", *ring(R=3, tpr=2), text=b"tiles_per_req")
     rows = _lib.Rows()                      # plain rows (mode 1): the ring takes frag16 only, and there is no slab form
     rows.rows, rows.ld, rows.mode, rows.valid_word = 64, 512, 1, -1
     pb = _lib.RowsBatch()
     pb.r0, pb.rows_stride = rows, 16 * 512
-    refused("dfl_gemm_sample_batch_fp8", *ring(src=pb), text=b"ring form")
+    refused("dfl_gemm_sample_batch", *ring(src=pb), text=b"ring form")
     xb.frag_stride = 16 * 512 + 4           # a fragment stride that is no multiple of 8
-    refused("dfl_gemm_sample_batch_fp8", *ring(), text=b"ring form")
+    refused("dfl_gemm_sample_batch", *ring(), text=b"ring form")

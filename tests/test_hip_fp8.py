@@ -52,7 +52,7 @@ def int_weight(ops, N, K, g, lo=-8, hi=8):
 # ------------------------------------------------------------------ 3. every code
 def test_every_e4m3_code_converts_exactly(ops):
     """A [16, 64] weight whose 1024 entries run through all 254 finite e4m3 codes (subnormals and both zeros included),
-    scale 1, one-hot activation rows selecting 16 k's per launch: the logits of dfl_gemm_argmax_fp8 are the codes'
+    scale 1, one-hot activation rows selecting 16 k's per launch: the logits of dfl_gemm_argmax (e4m3) are the codes'
     values in bf16, bit for bit — the conversion and the byte layout.  (Code 0x80: the K-sum of +0 products and one -0
     is +0 in IEEE arithmetic, so a zero is compared as a zero, every other value by its bits.)"""
     finite = torch.tensor([c for c in range(256) if (c & 0x7F) != 0x7F], dtype=torch.uint8)

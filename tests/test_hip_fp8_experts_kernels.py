@@ -1,4 +1,4 @@
-"""The two expert launches on e4m3 codes — dfl_moe_gate_up_fp8 and dfl_moe_down_fp8 (csrc/moe.hip, k_moe_gate_up<true>,
+"""The two expert launches on e4m3 codes — dfl_moe_gate_up and dfl_moe_down with an e4m3 descriptor (csrc/moe.hip, k_moe_gate_up<true>,
 k_moe_down<CT, 16, true>) — against their bf16 siblings on the dequantised weights (bit for bit) and against exact
 arithmetic in torch ("The experts").
 
@@ -78,7 +78,7 @@ GU_IDS = ["one-pair-K64", "KS34-11rows", "576-items", "30b-a3b-routed"]
 
 @pytest.mark.parametrize("E,I,K,nact,rows", GU_SHAPES, ids=GU_IDS)
 def test_moe_gate_up_fp8(E, I, K, nact, rows):
-    """dfl_moe_gate_up_fp8 at: one pair where only wave 0 has k-steps (a single 16-byte load); KS = 34 (wave 8 holds
+    """dfl_moe_gate_up (e4m3) at: one pair where only wave 0 has k-steps (a single 16-byte load); KS = 34 (wave 8 holds
     two k-steps, waves 9..15 none) with 11 valid rows through `dyn`; 576 items > 2 x 256 workgroups (both buffers, the
     loop's second trip); the 30B-A3B geometry routed by dfl_moe_route on tie-free logits.
     (a) power-of-two scales: bit-equal to ops.moe_gate_up on the packed dequantised weights (module docstring).
@@ -174,7 +174,7 @@ DOWN_IDS = ["ns1-N2048-two-tile", "ns4-N2048-two-tile", "ns4-N2064-one-tile", "n
 
 @pytest.mark.parametrize("nsplit,N,I,n_on", DOWN_SHAPES, ids=DOWN_IDS)
 def test_moe_down_fp8(nsplit, N, I, n_on):
-    """dfl_moe_down_fp8 at E 128 with top-8 on 16 rows and the last 8 experts idle: the two-tile form (N % 32 == 0) under
+    """dfl_moe_down (e4m3) at E 128 with top-8 on 16 rows and the last 8 experts idle: the two-tile form (N % 32 == 0) under
     1 and 4 shares, the one-tile form (N = 2064), one chunk of two k-steps (I = 64), KSe = 26 (the last chunk two
     k-steps), and 3 active experts under 4 shares (one share is empty and must still be written as zeros).
     (a) power-of-two scales: every share of `out` bit-equal to ops.moe_down on the dequantised weights.

@@ -1,6 +1,7 @@
-"""The sampled lm_head with e4m3 weights on the GPU ("The target"): dfl_gemm_sample_fp8 against
-torch on exact operands, against dfl_gemm_argmax_fp8's logits and against the two-step draw over them;
-dfl_gemm_sample_batch_fp8 (the ring form, both epilogues) bit for bit against its bf16 sibling on the dequantised copy
+"""The sampled lm_head with e4m3 weights on the GPU ("The target"): dfl_gemm_sample on e4m3 codes
+against torch on exact operands, against dfl_gemm_argmax's logits on the same codes and against the two-step draw over
+them; dfl_gemm_sample_batch on e4m3 codes (the ring form, both epilogues) bit for bit against the bf16 form on the
+dequantised copy
 and against the two-step draw, and what it refuses."""
 import ctypes as C
 
@@ -27,7 +28,7 @@ def _codes(w):
     return q.view(torch.uint8).contiguous()
 
 
-# ---------------------------------------------------------------------------------------------- dfl_gemm_sample_fp8
+# ---------------------------------------------------------------------------------------------- dfl_gemm_sample on e4m3 codes
 def _int_case(V, K, normed):
     """Weights in [-8, 8] (exact in e4m3) and one of SCALES by row (all four inside every tile): with activations that are
     multiples of 1/4 of magnitude <= 4 every K-sum is an integer number of quarters below 2^18 and its product with a
@@ -58,7 +59,7 @@ def _int_case(V, K, normed):
 @pytest.mark.parametrize("normed", [False, True], ids=["plain", "normed"])
 @pytest.mark.parametrize("V,K", [(2048, 512), (4208, 1024)])
 def test_gemm_sample_fp8_exact_ints(V, K, normed):
-    """The materialised logits are torch's bf16(sum * scale) and dfl_gemm_argmax_fp8's, bit for bit; the ids are
+    """The materialised logits are torch's bf16(sum * scale) and dfl_gemm_argmax's on the same codes, bit for bit; the ids are
     dfl_sample_rows' over those logits, with positions from a device record and from pos_base; rows outside
     [row0, row0 + nrows) are not written, neither ids nor logits."""
     from dflash_amd import ops
@@ -109,7 +110,7 @@ def test_gemm_sample_fp8_draft_stream_and_margins():
 def test_gemm_sample_fp8_full_vocabulary():
     """(V 151936, K 4096), random data quantised by quantize_fp8_rows: every workgroup and merge pass of the real head.
     The fused draw equals the two-step draw over the launch's own logits bit for bit, the logits equal
-    dfl_gemm_argmax_fp8's, and the launch that writes no logits draws the same ids."""
+    dfl_gemm_argmax's on the same codes, and the launch that writes no logits draws the same ids."""
     from dflash_amd import ops
     V, K = 151936, 4096
     gd = torch.Generator(device=dev()).manual_seed(19)
@@ -139,7 +140,7 @@ def test_gemm_sample_fp8_full_vocabulary():
         assert float((ids[1:] != ids_arg[1:]).float().mean()) > 0.5   # (random logits at T = 0.7: draws, not the argmax)
 
 
-# ---------------------------------------------------------------------------------------- dfl_gemm_sample_batch_fp8
+# ---------------------------------------------------------------------------------------- dfl_gemm_sample_batch on e4m3 codes
 V_B = 4208
 RING_CASES = [(1, 1), (3, 1), (4, 1), (4, 2)]
 SEEDS = [3, 2 ** 63 + 5, 77, 1 << 40]
@@ -195,7 +196,7 @@ def _ring_launch(wp, c, K, R, tpr, rec, seeds, with_logits=True, **temp):
 @pytest.mark.parametrize("K", [512, 4096])
 @pytest.mark.parametrize("R,tpr", RING_CASES)
 def test_ring_sample_fp8_equals_the_bf16_ring_and_the_two_step_draw(R, tpr, K, per_request):
-    """dfl_gemm_sample_batch_fp8 against dfl_gemm_sample_batch on the dequantised copy: ids and logits bit for bit.
+    """dfl_gemm_sample_batch on e4m3 codes against dfl_gemm_sample_batch on the dequantised copy: ids and logits bit for bit.
     Derivable, as for the argmax ring (test_ring_argmax_fp8_equals_the_bf16_ring_on_the_copy): the lm_head forms have
     KQ = 1, so in both a wave owns a column tile and walks ALL k-steps of K in ascending order through the same MFMA
     (the W8 form converts a code to the bf16 value q exactly; chunks past K are zeros in both); its fp32 sum is then
@@ -203,7 +204,7 @@ def test_ring_sample_fp8_equals_the_bf16_ring_and_the_two_step_draw(R, tpr, K, p
     fp32 rounding (random normal data: no subnormals) — and the multiplication by the scale in front of the epilogue
     restores the same bits, which the same epilogue rounds, perturbs and compares.  V = 4208 = 263 tiles: more than one
     pass per workgroup and a last pass with idle waves.  Then the ids against dfl_sample_rows over the launch's own
-    logits (a greedy slot: dfl_gemm_argmax_batch_fp8's ids), rows past a tile's count and tiles past R unwritten, and
+    logits (a greedy slot: dfl_gemm_argmax_batch's ids on the same codes), rows past a tile's count and tiles past R unwritten, and
     the launch without logits draws the same ids."""
     from dflash_amd import ops
     c = _ring_case(K)
@@ -252,11 +253,11 @@ def test_ring_sample_fp8_refusals_launch_nothing():
         ops.gemm_sample_batch(wp, x, R, V_B, Kk, 0, 16, c["gws"], ids, 0, rec, seeds=seeds, temperature=T,
                               pos_word=ops.DYN_POS0, pos_add=1, tiles_per_req=1, nrows_dyn_word=ops.DYN_BS)
 
-    with pytest.raises(_lib.DFlashHipError, match="dfl_gemm_sample_batch_fp8.*ring form"):
+    with pytest.raises(_lib.DFlashHipError, match="dfl_gemm_sample_batch:.*ring form"):
         call(w8, ops.brows_plain(c["x"][:2].contiguous()), 2, K)
     for Kk in (288, 192):    # K % 64 != 0; K < 256 (the buffers are never read: refused on the numbers alone)
         fake = ops.Fp8Weight(w8.wp, w8.scale, V_B, Kk)
-        with pytest.raises(_lib.DFlashHipError, match="dfl_gemm_sample_batch_fp8.*K"):
+        with pytest.raises(_lib.DFlashHipError, match="dfl_gemm_sample_batch:.*K"):
             call(fake, good, 2, Kk)
     for R in (0, 5):
         with pytest.raises((_lib.DFlashHipError, AssertionError)):
@@ -264,16 +265,16 @@ def test_ring_sample_fp8_refusals_launch_nothing():
     pad = torch.zeros(V_B + 16, dtype=torch.float32, device=dev())
     off = next(i for i in range(1, 16) if pad[i:].data_ptr() % 64)
     pad[off:off + V_B] = w8.scale
-    with pytest.raises(_lib.DFlashHipError, match="dfl_gemm_sample_batch_fp8.*64-byte aligned"):
+    with pytest.raises(_lib.DFlashHipError, match="dfl_gemm_sample_batch:.*64-byte aligned"):
         call(ops.Fp8Weight(w8.wp, pad[off:off + V_B], V_B, K), good, 2, K)
     # a null scale vector, and R out of range, through the C ABI itself
     h = _lib.lib()
-    args = lambda scale, R: (w8.wp.data_ptr(), scale, good.ref, R, V_B, K, 0, 16, rec.data_ptr(), ops.DYN_BS,  # noqa: E731
+    args = lambda scale, R: (_lib.Weight(w8.wp.data_ptr(), scale, _lib.W_E4M3), good.ref, R, V_B, K, 0, 16, rec.data_ptr(), ops.DYN_BS,  # noqa: E731
                              c["gws"].data_ptr(), ids.data_ptr(), 16, 0, None, 0, seeds.data_ptr(), None,
                              C.c_float(1.0 / T), 0, ops.DYN_POS0, 1, 1, None)
     for scale, R in ((None, 2), (w8.scale.data_ptr(), 0), (w8.scale.data_ptr(), 5)):
-        assert h.dfl_gemm_sample_batch_fp8(*args(scale, R)) == -22
-        assert b"dfl_gemm_sample_batch_fp8" in h.dfl_last_error()
+        assert h.dfl_gemm_sample_batch(*args(scale, R)) == -22
+        assert b"dfl_gemm_sample_batch:" in h.dfl_last_error()
     torch.cuda.synchronize()
     assert torch.all(ids == -1)
     call(w8, good, 2, K)     # and the same arguments, valid: it launches

@@ -14,8 +14,8 @@ def test_gemm_sample_batch_t_validates_without_a_gpu():
 
     def call(wp=16, xs=x, R=2, V=64, K=256, row0=0, nrows=16, dyn=16, ws=16, out=16, seeds=16, inv_ts=16, stream=0,
              inv_t=0.0, pos_word=3, tpr=1):
-        return h.dfl_gemm_sample_batch(wp, ctypes.byref(xs) if xs is not None else None, R, V, K, row0, nrows, dyn, 2, ws,
-                                       out, 16, 0, None, 0, seeds, inv_ts, inv_t, stream, pos_word, 1, tpr, None)
+        return h.dfl_gemm_sample_batch(_lib.Weight(wp, None, _lib.W_BF16), ctypes.byref(xs) if xs is not None else None,
+                                       R, V, K, row0, nrows, dyn, 2, ws, out, 16, 0, None, 0, seeds, inv_ts, inv_t, stream, pos_word, 1, tpr, None)
 
     assert h.dfl_gemm_sample_batch(None, None, 2, 64, 256, 0, 16, None, 2, None, None, 16, 0, None, 0, None, None, 0.0, 0, 3,
                                    1, 1, None) == -22 and b"null" in h.dfl_last_error()

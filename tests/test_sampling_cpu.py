@@ -69,4 +69,4 @@ def test_sampling_entry_points_validate_without_gpu():
     assert h.dfl_sample_rows(1, 16, 1, 16, 1, 1.0, 7, 0, None, 0, 1, None, None) == -22   # unknown stream
     assert h.dfl_gemm_sample(None, None, 16, 32, 0, 16, None, -1, None, None, 0, None, None, 1, 1.0, 0, None, 3, 0, 0,
                              None) == -22
-    assert h.dfl_gemm_sample(1, None, 16, 32, 0, 16, None, -1, 1, 1, 0, None, None, 1, -1.0, 0, None, 3, 0, 0, None) == -22
+    assert h.dfl_gemm_sample(_lib.Weight(1, None, _lib.W_BF16), None, 16, 32, 0, 16, None, -1, 1, 1, 0, None, None, 1, -1.0, 0, None, 3, 0, 0, None) == -22
