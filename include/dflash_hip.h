@@ -224,7 +224,12 @@ int dfl_norm_pack(const float *part, int nsplit, int64_t part_split, int ldp, in
  * NULL skips the per-head norms (Llama-style attention).
  * ctx_rows_override >= 0: that many context rows instead of dyn tau and no block
  * rows — the draft-cache prefill of the prompt's context in 16-row groups, with
- * row_base = index of the group's first row. */
+ * row_base = index of the group's first row (the record's tau and bs are then ignored).
+ * Edges: a position >= max_pos rotates with table row max_pos - 1 (clamped, no read past the
+ * tables); a K/V row whose cache row S + rel is >= cache_rows is silently not stored (q_out
+ * is still written; dfl_kv_append_batch runs the same kernel).  The position clamp holds at
+ * every norm + RoPE site below that takes max_pos (dfl_attn_fused, dfl_attn_head and its
+ * forms, the _batch forms). */
 int dfl_qknorm_rope_append(const float *qkv, int nsplit, int64_t split_stride, int ld, int q_col, int k_col,
                            int v_col, int ctx_row0, int blk_row0, int n_q, int n_kv, const void *q_norm_w,
                            const void *k_norm_w, float eps, const void *cos_tab, const void *sin_tab, int max_pos,
@@ -481,7 +486,8 @@ int dfl_prefill_gemm_resid(const void *wp, const void *x_frag, int P, int N, int
 int dfl_prefill_gemm_silu(const void *wp_gateup, const void *x_frag, int P, int I, int K, void *act_frag, void *stream);
 
 /* Rows h [P][H] (bf16, row stride ldh) -> Qwen3RMSNorm (tf:modeling_qwen3.py:59-64; norm_w NULL: none) -> frag16 row
- * tiles of H columns; all dfl_prefill_rows_padded(P) / 16 tiles are written (zero fragments beyond row P). */
+ * tiles of H columns; all dfl_prefill_rows_padded(P) / 16 tiles are written (zero fragments beyond row P).
+ * H % 32 == 0 and H <= 8192 (a wave keeps its row in registers): a wider H returns DFL_EINVAL and launches nothing. */
 int dfl_prefill_norm_pack(const void *h, int64_t ldh, int P, int H, const void *norm_w, float eps, void *x_frag,
                           void *stream);
 /* rows [P][K] (row stride ld) -> frag16 row tiles of K columns, any K % 32 == 0 (the draft's fc operand: K = 5 H tapped
@@ -490,7 +496,8 @@ int dfl_prefill_pack_rows(const void *rows, int64_t ld, int P, int K, void *x_fr
 
 /* Per-head q/k RMSNorm (weights may be NULL: Llama) + RoPE at positions pos0 + row over the P rows of a bf16 q/k/v row
  * buffer (row stride ld): q is rewritten in place, k (normed, rotated) and v go to cache rows row0 + row of
- * kcache / vcache [n_kv][cache_rows][128].  cos/sin: bf16 [max_pos][64]. */
+ * kcache / vcache [n_kv][cache_rows][128].  cos/sin: bf16 [max_pos][64]; a position >= max_pos rotates with table row
+ * max_pos - 1 (clamped).  row0 + P <= cache_rows is required (DFL_EINVAL otherwise): no row is ever dropped here. */
 int dfl_prefill_qk_rope(void *qkv_rows, int64_t ld, int P, int q_col, int k_col, int v_col, int n_q, int n_kv,
                         const void *q_norm_w, const void *k_norm_w, float eps, const void *cos_tab, const void *sin_tab,
                         int max_pos, int pos0, void *kcache, void *vcache, int cache_rows, int row0, void *stream);
