@@ -107,6 +107,8 @@ SIGNATURES = {
     "dfl_prefill_moe_gemm_silu": (_i, [_p, _i64, _p, _p, _p, _i, _i, _i, _p, _i, _p, _p, _p]),
     "dfl_prefill_moe_gemm_down": (_i, [_p, _i64, _p, _p, _p, _i, _i, _i, _p, _p, _i, _p]),
     "dfl_prefill_moe_combine": (_i, [_p, _p, _i, _i, _i, _p, _i64, _p, _i64, _p, _p]),
+    "dfl_moe_grouped_gate_up": (_i, [_w, _i64, _p, _p, _p, _i, _i, _i, _p, _i, _p, _p, _p]),
+    "dfl_moe_grouped_down": (_i, [_w, _i64, _p, _p, _p, _i, _i, _i, _p, _p, _i, _p]),
     # ---- ragged batch of requests
     "dfl_batch_tiles": (_i, [_i]),
     "dfl_batch_ksplit": (_i, [_i]),

@@ -17,6 +17,8 @@
 #include "gemm_rows.h"
 #include "moe_route.h"
 
+#include <type_traits>
+
 namespace {
 
 enum { PEPI_ROWS = 0, PEPI_RESID = 1, PEPI_SILU = 2, PEPI_SCALE32 = 3 };
@@ -41,14 +43,21 @@ struct PGemmArgs {
   const float *row_w;       // [gathered row]
   int64_t ld32;
 };
+// W8 (the grouped form on e4m3 codes): wp holds an expert's codes, [ntiles][KS/2][64 lanes][16 B] (gemm_rows.h),
+// w_expert_stride counts 16-byte units of codes, wscale [E][ntiles * 16] is the fp32 scale of every output row in packed
+// tile order.  (A struct of its own: the bf16 kernels' launch arguments stay as they were.)
+struct PGemmArgs8 : PGemmArgs {
+  const float *wscale;
+};
 
 typedef __attribute__((address_space(3))) void lds_void;
 typedef const __attribute__((address_space(1))) void glb_void;
 
 // The epilogues of k_pgemm for one wave: acc[i][j] = n tile nb * 8 + wn * 4 + i x row tile tile0 + wm * MW + j.
-template <int EPI, int MW, bool GRP>
+// W8: sc[i] = the scales of the lane's four columns of n tile i, put on the fp32 sums in front of the first rounding point.
+template <int EPI, int MW, bool GRP, bool W8 = false>
 __device__ __forceinline__ void pgemm_epilogue(const PGemmArgs &a, f32x4 (&acc)[4][MW], int nb, int wn, int wm, int tile0, int ntl,
-                                               int l) {
+                                               int l, const f32x4 (&sc)[4]) {
   // D layout (A = W rows n, B = x^T columns m): lane L, register r = column 4 (L >> 4) + r of the n tile, row L & 15
   const int fm = l & 15, fg = l >> 4;
 #pragma unroll
@@ -64,7 +73,12 @@ __device__ __forceinline__ void pgemm_epilogue(const PGemmArgs &a, f32x4 (&acc)[
         bf16x4 o;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const float gb = rbf(acc[2 * q][j][r]), ub = rbf(acc[2 * q + 1][j][r]);
+          float sg = acc[2 * q][j][r], su = acc[2 * q + 1][j][r];
+          if constexpr (W8) {  // (the packed tile order interleaves the gate and up scales like the weights)
+            sg *= sc[2 * q][r];
+            su *= sc[2 * q + 1][r];
+          }
+          const float gb = rbf(sg), ub = rbf(su);
           const float act = rbf(gb / (1.f + __expf(-gb)));
           o[r] = f2bf(act * ub);
         }
@@ -78,7 +92,12 @@ __device__ __forceinline__ void pgemm_epilogue(const PGemmArgs &a, f32x4 (&acc)[
         const int n0 = (nb * 8 + wn * 4 + i) * 16 + 4 * fg;
         f32x4 o;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) o[r] = rw * acc[i][j][r];
+        for (int r = 0; r < 4; ++r) {
+          if constexpr (W8)  // the scale on the product FIRST, as in k_moe_down<.., true> (exact for a power of two)
+            o[r] = rw * (acc[i][j][r] * sc[i][r]);
+          else
+            o[r] = rw * acc[i][j][r];
+        }
         *reinterpret_cast<f32x4 *>(a.out32 + (int64_t)m * a.ld32 + n0) = o;
       }
     } else {
@@ -112,19 +131,30 @@ __device__ __forceinline__ void pgemm_epilogue(const PGemmArgs &a, f32x4 (&acc)[
 // (Tried for the grouped form and dropped, commit history: rings of their own for the two operands — five 16 KB weight
 // stages from HBM and three activation stages from L2, fed by different waves so that the in-order vmcnt of a wave
 // tracks one ring, ONE workgroup per CU: 607 us per 30B-A3B layer against 449 for this kernel with two workgroups per CU.)
-template <int EPI, int MW, int NST, bool GRP = false>
-__global__ __launch_bounds__(256) void k_pgemm(PGemmArgs a) {
+// W8 (grouped SILU / SCALE32 only: the shared MoE pass of a verify on e4m3 expert codes): a column tile's 64-deep K step
+// is ONE 1 KiB fragment of codes carrying both k-steps (gemm_rows.h), staged by the same LDS-DMA as it is: a stage holds
+// 8 weight slots (column tile) instead of 16 (column tile, k-step), the activation slots follow from slot 8, and a wave
+// issues PER = 4 or 6 LDS-DMA instructions per stage (the counted waits follow).  One ds_read_b128 per column tile and K
+// step; w8_frag converts right in front of the MFMAs of each k-step — the same k-steps in the same order into every
+// accumulator as the bf16 form, so with power-of-two scales the launch is bit-equal to the bf16 one on q * scale.  The
+// lane's 4 x 4 scales are four 16-byte vector loads requested in FRONT of the first stage (a wave's loads return in
+// order: they have landed before the first counted wait is over, and no request sits between stages).
+template <int EPI, int MW, int NST, bool GRP = false, bool W8 = false>
+__global__ __launch_bounds__(256) void k_pgemm(std::conditional_t<W8, PGemmArgs8, PGemmArgs> a) {
+  static_assert(!W8 || (GRP && (EPI == PEPI_SILU || EPI == PEPI_SCALE32)), "W8: the grouped expert GEMMs only");
   constexpr int MB = 2 * MW;  // row tiles per block
-  constexpr int PER = (16 + 2 * MB) / 4;  // LDS-DMA instructions per wave and stage
-  static_assert(PER == 8 || PER == 6, "vmcnt immediates below");
+  constexpr int WS = W8 ? 8 : 16;  // weight slots per stage
+  constexpr int PER = (WS + 2 * MB) / 4;  // LDS-DMA instructions per wave and stage
+  static_assert(PER == 8 || PER == 6 || PER == 4, "vmcnt immediates below");
   static_assert(NST == 2 || NST == 3, "stage counts measured");
-  __shared__ bf16x8 lds[NST][16 + 2 * MB][64];  // [stage][slot: 0..15 = W (n tile, k-step), 16.. = X (m tile, k-step)][lane]
+  // [stage][slot: 0..15 = W (n tile, k-step), 16.. = X (m tile, k-step)][lane]; W8: 0..7 = W (n tile), 8.. = X
+  __shared__ bf16x8 lds[NST][WS + 2 * MB][64];
   const int tid = threadIdx.x;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l = tid & 63;
   const int nbx = a.ntiles >> 3, nby = a.mtiles / MB;
   // column block / row block of this workgroup: the nby row blocks of a column block are 8 apart in blockIdx
-  int nb, mb = 0, tile0 = 0, ntl = MB;
+  int nb, mb = 0, tile0 = 0, ntl = MB, expert = 0;
   const bf16x8 *wbase = a.wp;
   if (GRP) {
     // the column blocks of an item share blockIdx % 8, i.e. an XCD and its L2: the item's gathered rows leave HBM once
@@ -133,7 +163,8 @@ __global__ __launch_bounds__(256) void k_pgemm(PGemmArgs a) {
     const int seq = blockIdx.x >> 3, item = (seq / nbx) * 8 + (blockIdx.x & 7);
     nb = seq % nbx;
     if (item >= *a.n_items) return;  // (uniform: the grid is sized for the worst case)
-    wbase += (int64_t)a.items[3 * item] * a.w_expert_stride;
+    expert = a.items[3 * item];
+    wbase += (int64_t)expert * a.w_expert_stride;
     tile0 = a.items[3 * item + 1];
     ntl = a.items[3 * item + 2];
   } else {
@@ -166,21 +197,34 @@ __global__ __launch_bounds__(256) void k_pgemm(PGemmArgs a) {
       if (m >= 0) xsrc[q] = ((int64_t)(m >> 4) * a.KS) * 64 + (l >> 4) * 16 + (m & 15);
     }
   }
-  // stage kt -> buffer: 16 weight fragments + 2 MB activation fragments of 1 KiB, dealt round-robin to the 4 waves
+  // stage kt -> buffer: 16 (W8: 8) weight fragments + 2 MB activation fragments of 1 KiB, dealt round-robin to the 4 waves
   auto stage = [&](int kt, int buf) {
 #pragma unroll
-    for (int i = 0; i < (16 + 2 * MB) / 4; ++i) {
+    for (int i = 0; i < (WS + 2 * MB) / 4; ++i) {
       const int slot = i * 4 + w;  // wave-uniform
-      const int s16 = slot < 16 ? slot : slot - 16;  // fragment of its operand: (tile s16 >> 1, k-step s16 & 1)
-      const bf16x8 *src = (slot < 16 ? wbase + ((size_t)(nb * 8 + (s16 >> 1)) * a.KS + kt * 2 + (s16 & 1)) * 64
-                                     : a.xf + ((size_t)tile_of(s16 >> 1) * a.KS + kt * 2 + (s16 & 1)) * 64) + l;
-      if (GRP && i >= 4 && a.src_row) {
-        const int64_t o = xsrc[i >= 4 ? i - 4 : 0];
+      const int s16 = slot < WS ? slot : slot - WS;  // fragment of its operand: (tile s16 >> 1, k-step s16 & 1)
+      const bf16x8 *src;
+      if constexpr (W8)  // a weight slot is column tile s16 whole: [KT] fragments of 1 KiB per tile
+        src = (slot < WS ? wbase + ((size_t)(nb * 8 + s16) * KT + kt) * 64
+                         : a.xf + ((size_t)tile_of(s16 >> 1) * a.KS + kt * 2 + (s16 & 1)) * 64) + l;
+      else
+        src = (slot < 16 ? wbase + ((size_t)(nb * 8 + (s16 >> 1)) * a.KS + kt * 2 + (s16 & 1)) * 64
+                         : a.xf + ((size_t)tile_of(s16 >> 1) * a.KS + kt * 2 + (s16 & 1)) * 64) + l;
+      // (the activation slots start at i = WS / 4: slot - WS = 4 (i - WS / 4) + w, the tile and k-step xsrc was built for)
+      if (GRP && i >= WS / 4 && a.src_row) {
+        const int64_t o = xsrc[i >= WS / 4 ? i - WS / 4 : 0];
         src = o < 0 ? a.zeros + l : a.xf + o + (kt * 2 + (w & 1)) * 64;
       }
       __builtin_amdgcn_global_load_lds((glb_void *)src, (lds_void *)&lds[buf][slot][0], 16, 0, 0);
     }
   };
+
+  f32x4 wsc[4];  // W8: the scales of the lane's columns 4 (l >> 4) .. + 3 of its four column tiles
+  if constexpr (W8) {
+    const float *sp = a.wscale + ((int64_t)expert * a.ntiles + nb * 8 + wn * 4) * 16 + 4 * (l >> 4);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) wsc[i] = *reinterpret_cast<const f32x4 *>(sp + i * 16);
+  }
 
   f32x4 acc[4][MW];
 #pragma unroll
@@ -198,7 +242,8 @@ __global__ __launch_bounds__(256) void k_pgemm(PGemmArgs a) {
     const int later = KT - 1 - kt;
     if (NST >= 3 && later >= 1) {
       if (PER == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+      else if (PER == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
     } else {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
@@ -207,13 +252,23 @@ __global__ __launch_bounds__(256) void k_pgemm(PGemmArgs a) {
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     if (kt + NST - 1 < KT) stage(kt + NST - 1, buf == 0 ? NST - 1 : buf - 1);  // into the buffer of iteration kt - 1
+    bf16x8 raw[4];  // W8: the codes of the wave's four column tiles, both k-steps of this K step
+    if constexpr (W8) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) raw[i] = lds[buf][wn * 4 + i][l];
+    }
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
       bf16x8 af[4], bq[MW];
 #pragma unroll
-      for (int i = 0; i < 4; ++i) af[i] = lds[buf][(wn * 4 + i) * 2 + ks][l];
+      for (int i = 0; i < 4; ++i) {
+        if constexpr (W8)
+          af[i] = w8_frag(raw[i], ks);
+        else
+          af[i] = lds[buf][(wn * 4 + i) * 2 + ks][l];
+      }
 #pragma unroll
-      for (int j = 0; j < MW; ++j) bq[j] = lds[buf][16 + (wm * MW + j) * 2 + ks][l];
+      for (int j = 0; j < MW; ++j) bq[j] = lds[buf][WS + (wm * MW + j) * 2 + ks][l];
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -222,7 +277,7 @@ __global__ __launch_bounds__(256) void k_pgemm(PGemmArgs a) {
     buf = buf == NST - 1 ? 0 : buf + 1;
   }
 
-  pgemm_epilogue<EPI, MW, GRP>(a, acc, nb, wn, wm, tile0, ntl, l);
+  pgemm_epilogue<EPI, MW, GRP, W8>(a, acc, nb, wn, wm, tile0, ntl, l, wsc);
 }
 
 // rows [P][H] -> (RMSNorm) -> frag16 row tiles.  One WAVE per row (grid = row tiles x 4, four rows per workgroup): the
@@ -889,46 +944,113 @@ extern "C" int dfl_prefill_moe_gather(const void *x_frag, int P, int H, int top_
   return DFL_OK;
 }
 
+// The two grouped expert GEMMs, one implementation behind both their entry points (dfl_prefill_moe_gemm_* on a packed
+// bf16 pointer, dfl_moe_grouped_* on a dfl_weight).  W8: codes and scales, the stride in bytes of codes.
+namespace {
+inline bool scales_aligned(const float *p) { return ((uintptr_t)p & 63) == 0; }  // a tile's 16 scales: one aligned line
+
+template <bool W8>
+int grouped_gate_up_impl(const char *who, const void *wp, const float *wscale, int64_t w_expert_stride, const void *xg,
+                         const int32_t *items, const int32_t *n_items, int max_items, int I, int K, void *act_g,
+                         int rows_per_item, const int32_t *src_row, const void *zeros_1k, void *stream) {
+  std::conditional_t<W8, PGemmArgs8, PGemmArgs> a{};
+  DFL_REQUIRE(!src_row == !zeros_1k, "%s: src_row and zeros_1k come together", who);
+  a.src_row = src_row;
+  a.zeros = (const bf16x8 *)zeros_1k;
+  DFL_REQUIRE(rows_per_item == 64 || rows_per_item == 128, "%s: rows_per_item must be 64 or 128", who);
+  DFL_REQUIRE(act_g && I > 0 && I % 64 == 0, "%s: need I%%64==0", who);
+  if (!pmoe_gemm_fill(a, wp, w_expert_stride, xg, items, n_items, max_items, 2 * I, K, who)) return DFL_EINVAL;
+  a.act = (bf16x8 *)act_g;
+  a.KSo = I / 32;
+  if constexpr (W8) {
+    a.w_expert_stride = w_expert_stride / 16;
+    a.wscale = wscale;
+  }
+  const dim3 grid((max_items + 7) / 8 * 8 * (a.ntiles / 8));
+  if (rows_per_item == 128)
+    hipLaunchKernelGGL((k_pgemm<PEPI_SILU, 4, 2, true, W8>), grid, dim3(256), 0, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL((k_pgemm<PEPI_SILU, 2, 3, true, W8>), grid, dim3(256), 0, (hipStream_t)stream, a);
+  DFL_CHECK_LAUNCH(who);
+  return DFL_OK;
+}
+
+template <bool W8>
+int grouped_down_impl(const char *who, const void *wp, const float *wscale, int64_t w_expert_stride, const void *act_g,
+                      const int32_t *items, const int32_t *n_items, int max_items, int H, int I, const float *row_w,
+                      float *out32, int rows_per_item, void *stream) {
+  std::conditional_t<W8, PGemmArgs8, PGemmArgs> a{};
+  DFL_REQUIRE(rows_per_item == 64 || rows_per_item == 128, "%s: rows_per_item must be 64 or 128", who);
+  DFL_REQUIRE(row_w && out32, "%s: null pointer", who);
+  if (!pmoe_gemm_fill(a, wp, w_expert_stride, act_g, items, n_items, max_items, H, I, who)) return DFL_EINVAL;
+  a.row_w = row_w;
+  a.out32 = out32;
+  a.ld32 = H;
+  if constexpr (W8) {
+    a.w_expert_stride = w_expert_stride / 16;
+    a.wscale = wscale;
+  }
+  const dim3 grid((max_items + 7) / 8 * 8 * (a.ntiles / 8));
+  if (rows_per_item == 128)
+    hipLaunchKernelGGL((k_pgemm<PEPI_SCALE32, 4, 2, true, W8>), grid, dim3(256), 0, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL((k_pgemm<PEPI_SCALE32, 2, 3, true, W8>), grid, dim3(256), 0, (hipStream_t)stream, a);
+  DFL_CHECK_LAUNCH(who);
+  return DFL_OK;
+}
+
+// what a dfl_weight entry point of the grouped GEMMs refuses before anything else: the descriptor errors, then e4m3 codes
+// without scales or with scales off a 64-byte line
+inline bool grouped_weight_ok(const char *who, const dfl_weight *w) {
+  if (!weight_ok(who, w)) return false;
+  if (w->format == DFL_W_E4M3 && !w->scale) {
+    dfl_set_error("%s: null scale vector (format DFL_W_E4M3)", who);
+    return false;
+  }
+  if (w->format == DFL_W_E4M3 && !scales_aligned(w->scale)) {
+    dfl_set_error("%s: the scale vector must be 64-byte aligned", who);
+    return false;
+  }
+  return true;
+}
+}  // namespace
+
 extern "C" int dfl_prefill_moe_gemm_silu(const void *wp_gateup_e, int64_t w_expert_stride, const void *xg, const int32_t *items,
                                          const int32_t *n_items, int max_items, int I, int K, void *act_g, int rows_per_item,
                                          const int32_t *src_row, const void *zeros_1k, void *stream) {
-  PGemmArgs a{};
-  DFL_REQUIRE(!src_row == !zeros_1k, "dfl_prefill_moe_gemm_silu: src_row and zeros_1k come together");
-  a.src_row = src_row;
-  a.zeros = (const bf16x8 *)zeros_1k;
-  DFL_REQUIRE(rows_per_item == 64 || rows_per_item == 128, "dfl_prefill_moe_gemm_silu: rows_per_item must be 64 or 128");
-  DFL_REQUIRE(act_g && I > 0 && I % 64 == 0, "dfl_prefill_moe_gemm_silu: need I%%64==0");
-  if (!pmoe_gemm_fill(a, wp_gateup_e, w_expert_stride, xg, items, n_items, max_items, 2 * I, K, "dfl_prefill_moe_gemm_silu"))
-    return DFL_EINVAL;
-  a.act = (bf16x8 *)act_g;
-  a.KSo = I / 32;
-  const dim3 grid((max_items + 7) / 8 * 8 * (a.ntiles / 8));
-  if (rows_per_item == 128)
-    hipLaunchKernelGGL((k_pgemm<PEPI_SILU, 4, 2, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL((k_pgemm<PEPI_SILU, 2, 3, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
-  DFL_CHECK_LAUNCH("dfl_prefill_moe_gemm_silu");
-  return DFL_OK;
+  return grouped_gate_up_impl<false>("dfl_prefill_moe_gemm_silu", wp_gateup_e, nullptr, w_expert_stride, xg, items, n_items,
+                                     max_items, I, K, act_g, rows_per_item, src_row, zeros_1k, stream);
 }
 
 extern "C" int dfl_prefill_moe_gemm_down(const void *wp_down_e, int64_t w_expert_stride, const void *act_g, const int32_t *items,
                                          const int32_t *n_items, int max_items, int H, int I, const float *row_w, float *out32,
                                          int rows_per_item, void *stream) {
-  PGemmArgs a{};
-  DFL_REQUIRE(rows_per_item == 64 || rows_per_item == 128, "dfl_prefill_moe_gemm_down: rows_per_item must be 64 or 128");
-  DFL_REQUIRE(row_w && out32, "dfl_prefill_moe_gemm_down: null pointer");
-  if (!pmoe_gemm_fill(a, wp_down_e, w_expert_stride, act_g, items, n_items, max_items, H, I, "dfl_prefill_moe_gemm_down"))
-    return DFL_EINVAL;
-  a.row_w = row_w;
-  a.out32 = out32;
-  a.ld32 = H;
-  const dim3 grid((max_items + 7) / 8 * 8 * (a.ntiles / 8));
-  if (rows_per_item == 128)
-    hipLaunchKernelGGL((k_pgemm<PEPI_SCALE32, 4, 2, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL((k_pgemm<PEPI_SCALE32, 2, 3, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
-  DFL_CHECK_LAUNCH("dfl_prefill_moe_gemm_down");
-  return DFL_OK;
+  return grouped_down_impl<false>("dfl_prefill_moe_gemm_down", wp_down_e, nullptr, w_expert_stride, act_g, items, n_items,
+                                  max_items, H, I, row_w, out32, rows_per_item, stream);
+}
+
+extern "C" int dfl_moe_grouped_gate_up(const dfl_weight *w_gateup_e, int64_t w_expert_stride, const void *xg,
+                                       const int32_t *items, const int32_t *n_items, int max_items, int I, int K, void *act_g,
+                                       int rows_per_item, const int32_t *src_row, const void *zeros_1k, void *stream) {
+  const char *who = "dfl_moe_grouped_gate_up";
+  if (!grouped_weight_ok(who, w_gateup_e)) return DFL_EINVAL;
+  return w_gateup_e->format == DFL_W_BF16
+             ? grouped_gate_up_impl<false>(who, w_gateup_e->wp, nullptr, w_expert_stride, xg, items, n_items, max_items, I, K,
+                                           act_g, rows_per_item, src_row, zeros_1k, stream)
+             : grouped_gate_up_impl<true>(who, w_gateup_e->wp, w_gateup_e->scale, w_expert_stride, xg, items, n_items,
+                                          max_items, I, K, act_g, rows_per_item, src_row, zeros_1k, stream);
+}
+
+extern "C" int dfl_moe_grouped_down(const dfl_weight *w_down_e, int64_t w_expert_stride, const void *act_g, const int32_t *items,
+                                    const int32_t *n_items, int max_items, int H, int I, const float *row_w, float *out32,
+                                    int rows_per_item, void *stream) {
+  const char *who = "dfl_moe_grouped_down";
+  if (!grouped_weight_ok(who, w_down_e)) return DFL_EINVAL;
+  return w_down_e->format == DFL_W_BF16
+             ? grouped_down_impl<false>(who, w_down_e->wp, nullptr, w_expert_stride, act_g, items, n_items, max_items, H, I,
+                                        row_w, out32, rows_per_item, stream)
+             : grouped_down_impl<true>(who, w_down_e->wp, w_down_e->scale, w_expert_stride, act_g, items, n_items, max_items,
+                                       H, I, row_w, out32, rows_per_item, stream);
 }
 
 extern "C" int dfl_prefill_moe_combine(const float *out32, const int32_t *posmap, int P, int H, int top_k, void *h_io,

@@ -138,7 +138,7 @@ def pack_weight_gateup_fp8(gate_q: torch.Tensor, gate_scale: torch.Tensor, up_q:
 
 class Fp8Experts(NamedTuple):
     """One MoE layer's expert weights of one kind as e4m3 codes (pack_experts_fp8): expert e's packed codes in row e.
-    moe_gate_up / moe_down take one in place of the packed bf16 [E, .] tensor."""
+    moe_gate_up / moe_down and moe_grouped_gate_up / moe_grouped_down take one in place of the packed bf16 [E, .] tensor."""
     wp: torch.Tensor      # uint8 [E, N * K]: per expert pack_weight_gateup_fp8's (gate/up, N = 2I) or pack_weight_fp8's layout
     scale: torch.Tensor   # fp32 [E, N], in that layout's tile order
     E: int
@@ -1119,6 +1119,33 @@ def prefill_moe_route(rlog: torch.Tensor, P: int, sc: dict, norm_topk: bool = Tr
                                       sc["posmap"].data_ptr(), sc["src_row"].data_ptr(), sc["row_w"].data_ptr(),
                                       sc["rows_per_item"], _stream()),
           "dfl_prefill_moe_route")
+
+
+def moe_grouped_gate_up(wp_gu, x_frag: torch.Tensor, sc: dict, K: int, *, gather: bool) -> None:
+    """The grouped gate/up + SiLU launch over the work list in the scratch `sc` (prefill_moe_route): act_g <- silu(x Wg_e^T)
+    * (x Wu_e^T) per item.  wp_gu: packed bf16 [E, 2*I*K], or an Fp8Experts (dfl_moe_grouped_gate_up's e4m3 form: any K,
+    unlike moe_gate_up).  gather: x_frag holds the UNGATHERED row tiles and the gather happens in the kernel's addresses
+    (src_row); else x_frag is the gathered copy (sc["xg"])."""
+    E, I = sc["E"], sc["I"]
+    w, rows = _we(wp_gu, E, 2 * I, K, "wp_gu")
+    assert rows.shape == (E, 2 * I * K) and x_frag.is_cuda and x_frag.dtype == BF16
+    check(lib().dfl_moe_grouped_gate_up(w, rows.stride(0), x_frag.data_ptr(), _p(sc["items"], I32, "items"),
+                                        _p(sc["n_items"], I32, "n_items"), sc["max_items"], I, K, _p(sc["act_g"], BF16, "act_g"),
+                                        sc["rows_per_item"], _p(sc["src_row"], I32, "src_row") if gather else None,
+                                        _p(sc["zeros"], BF16, "zeros") if gather else None, _stream()),
+          "dfl_moe_grouped_gate_up")
+
+
+def moe_grouped_down(wp_down, sc: dict, N: int) -> None:
+    """The grouped down projection over the same work list: out32[gathered row] <- row_w * (act_g Wd_e^T), fp32.
+    wp_down: packed bf16 [E, N*I], or an Fp8Experts."""
+    E, I = sc["E"], sc["I"]
+    w, rows = _we(wp_down, E, N, I, "wp_down")
+    assert rows.shape == (E, N * I) and sc["out32"].shape[1] == N
+    check(lib().dfl_moe_grouped_down(w, rows.stride(0), _p(sc["act_g"], BF16, "act_g"), _p(sc["items"], I32, "items"),
+                                     _p(sc["n_items"], I32, "n_items"), sc["max_items"], N, I, _p(sc["row_w"], F32, "row_w"),
+                                     _p(sc["out32"], F32, "out32"), sc["rows_per_item"], _stream()),
+          "dfl_moe_grouped_down")
 
 
 def prefill_moe_mlp(router_wp, gu_e, down_e, x_frag, P: int, H: int, I: int, E: int, top_k: int, norm_topk: bool,

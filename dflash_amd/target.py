@@ -97,8 +97,8 @@ class NativeTarget:
         anything is packed.  Router, norms, attention projections, dense layers (mlp_only_layers) and the lm_head stay
         bf16.  lw["gu_e"] / lw["down_e"] stay the packed bf16 copy of q * scale (the experts cost 1.5 x their bf16 bytes);
         `self.experts8[i]` holds layer i's codes and scales (ops.Fp8Experts; None for a dense layer), which the <= 16-row
-        verify and the per-tile expert branch stream while `self.expert_stream` is True ("The
-        experts").  What weight-only e4m3 does to a real MoE checkpoint's routing and outputs is NOT measured.
+        verify, the per-tile expert branch and the shared pass over 2..4 tiles stream while `self.expert_stream` is True
+        ("The experts"; the native MoE prefill reads the copy).  What weight-only e4m3 does to a real MoE checkpoint's routing and outputs is NOT measured.
         attn_impl: "head" = dfl_attn_head on finished bf16 q/k/v rows (round 2, default); "fused" = the
         round-1 stage (fp32 K-split partials -> dfl_attn_fused), kept for A/B measurement and as a second
         implementation the tests compare against.
@@ -617,7 +617,7 @@ class NativeTarget:
         if mt > MT:
             raise ValueError(f"moe_mlp_tiles: {R} tiles need {mt} tile slots, the buffers have {MT}")
         pv = part[:ns * mt * 16 * H].view(ns, mt * 16, H)
-        gu_e, down_e = self.expert_weights(lw)   # (fp8 experts: the codes; the shared pass above reads the bf16 copy)
+        gu_e, down_e = self.expert_weights(lw)   # (fp8 experts: the codes, as the shared pass above)
         for r in range(R):
             dt, x = dyn[r], xn[r]
             if self.moe_router_fused:   # gate Linear + routing in one launch on the tile's normalised fragments
@@ -645,6 +645,7 @@ class NativeTarget:
         gathered like prompt rows (dfl_prefill_moe_*, csrc/prefill.hip), so that an expert several tiles picked is
         streamed once (four tiles of 16 rows x top-8 touch nearly all of 128 experts: one pass over them instead of four
         over ~80 each).  Same rounding points as the per-tile kernels; the rows' fp32 sums land as ONE share in `part`.
+        An fp8-expert target streams the codes here too while expert_stream is set (ops.moe_grouped_gate_up / _down).
         Rows beyond a tile's valid count are routed too (zero fragments) and ignored by the norm launch that follows."""
         H, P = self.H, R * 16
         if self._moe_sh is None:
@@ -657,14 +658,11 @@ class NativeTarget:
         ops.gemm_resid_batch(lw["router_p"], ops.brows_frag(xn), R, sh["rlog"].shape[2], H, sh["rlog"], add_residual=False,
                              ws=sh["gws"], dyn=dyn)
         ops.prefill_moe_route(sh["rlog"].view(64, -1), P, sc, self.norm_topk)
-        gu, dn = lw["gu_e"], lw["down_e"]
-        ops.check(L.dfl_prefill_moe_gemm_silu(gu.data_ptr(), gu.stride(0), xn.data_ptr(), sc["items"].data_ptr(),
-                                              sc["n_items"].data_ptr(), sc["max_items"], self.Ie, H, sc["act_g"].data_ptr(),
-                                              sc["rows_per_item"], sc["src_row"].data_ptr(), sc["zeros"].data_ptr(), st),
-                  "dfl_prefill_moe_gemm_silu")
-        ops.check(L.dfl_prefill_moe_gemm_down(dn.data_ptr(), dn.stride(0), sc["act_g"].data_ptr(), sc["items"].data_ptr(),
-                                              sc["n_items"].data_ptr(), sc["max_items"], H, self.Ie, sc["row_w"].data_ptr(),
-                                              sc["out32"].data_ptr(), sc["rows_per_item"], st), "dfl_prefill_moe_gemm_down")
+        # fp8 experts: both grouped launches stream the codes (the grouped form has no K <= 2048 limit, so gate/up too at
+        # any hidden width); else, or with expert_stream off, the packed bf16 copy
+        e8 = "gu_e8" in lw and self.expert_stream
+        ops.moe_grouped_gate_up(lw["gu_e8"] if e8 else lw["gu_e"], xn, sc, H, gather=True)
+        ops.moe_grouped_down(lw["down_e8"] if e8 else lw["down_e"], sc, H)
         ops.check(L.dfl_prefill_moe_combine(sc["out32"].data_ptr(), sc["posmap"].data_ptr(), P, H, self.top_k, None, 0, None, 0,
                                             part.data_ptr(), st), "dfl_prefill_moe_combine")
         return 1

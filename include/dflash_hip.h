@@ -548,6 +548,24 @@ int dfl_prefill_moe_gemm_down(const void *wp_down_e, int64_t w_expert_stride, co
                               int rows_per_item, void *stream);
 int dfl_prefill_moe_combine(const float *out32, const int32_t *posmap, int P, int H, int top_k, void *h_io, int64_t ldh,
                             void *tap, int64_t ldtap, float *sum_out, void *stream);
+/* The two grouped expert GEMMs with the experts' weights as a dfl_weight: what the shared MoE pass of a verify over 2..4
+ * tiles launches ("The experts"); every other argument is dfl_prefill_moe_gemm_silu's / _down's.
+ * DFL_W_BF16: exactly the launch of dfl_prefill_moe_gemm_silu / _down (those two are this implementation on a bare bf16
+ * pointer).  DFL_W_E4M3: expert e's codes at wp + e * w_expert_stride BYTES in dfl_pack_weight_gateup_fp8's (gate/up,
+ * N = 2*I rows) or dfl_pack_weight_fp8's (down, N = H rows) layout, scale fp32 [E][N] in that layout's tile order (N floats
+ * per expert, 64-byte aligned).  The codes are staged to LDS as they are and converted in front of each MFMA: the same
+ * k-steps in the same order into every accumulator, the fp32 sums multiplied by the row's scale in front of the first
+ * rounding point (gate/up: before the bf16 rounding of the two Linears' outputs; down: row_w * (sum * scale)) — with
+ * power-of-two scales bit-equal to the bf16 launch on q * scale.
+ * w_expert_stride: elements of the weight's format between experts; it must be N * K.  N % 128 == 0, K % 64 == 0,
+ * rows_per_item 64 or 128, src_row and zeros_1k together or neither; DFL_EINVAL, nothing launched, on any of these, on
+ * the descriptor errors of dfl_weight and on scales that are not 64-byte aligned. */
+int dfl_moe_grouped_gate_up(const dfl_weight *w_gateup_e, int64_t w_expert_stride, const void *xg, const int32_t *items,
+                            const int32_t *n_items, int max_items, int I, int K, void *act_g, int rows_per_item,
+                            const int32_t *src_row, const void *zeros_1k, void *stream);
+int dfl_moe_grouped_down(const dfl_weight *w_down_e, int64_t w_expert_stride, const void *act_g, const int32_t *items,
+                         const int32_t *n_items, int max_items, int H, int I, const float *row_w, float *out32,
+                         int rows_per_item, void *stream);
 
 /* ======================================================================================
  * Ragged batch of requests on one GPU (BASELINE.json configs[2]; SURVEY.md §8e: "within a
