@@ -75,6 +75,89 @@ __device__ __forceinline__ bf16x8 weight_frag(const bf16x8 (&wr)[NW], int f) {
     return wr[f];
 }
 
+// ---- W13: bf16 weights stored losslessly in 13 bits (DFL_W_BF16X13, dflash_hip.h) ----
+// A bf16 is L = bits[7:0] (e0, m6..m0) and H = bits[15:8] (s, e7..e1).  Per packed 16-column tile, hb = max(0, max(H & 0x7f)
+// - 15); a weight keeps L, its sign and a 4-bit code c: c = 0 <=> (H & 0x7f) == 0, c = 1..15 <=> (H & 0x7f) == hb + c.
+// Unit of the layout: a QUAD of four k-steps of one tile, 3328 bytes = four lane-linear planes
+//   L0 [64 lanes][16 B]  L bytes of k-step 0 (bytes 0-7: elements 0..7) and k-step 1 (bytes 8-15)
+//   L1 [64 lanes][16 B]  the same of k-steps 2 and 3
+//   NB [64 lanes][16 B]  dword f = the codes of k-step f: byte b = c[b] | c[b + 4] << 4
+//   SG [64 lanes][ 4 B]  bit 8 b + r = the sign of element 4 (r & 1) + b of k-step r >> 1
+// with lane l = (column l & 15, kq = l >> 4) as in the bf16 form, so the half-tile lane rule carries over.  A tile is
+// K / 128 quads back to back; a wave's share is nfr / 4 of them (nfr = 4 or 8: K = 2048 or 4096), so the descriptor
+// clips at whole quads, and a clipped read (all bits zero) decodes to +0 as the bf16 form's does.
+// Behind the quads of all tiles: meta [ntiles][16 waves] of {hb, patch} dword pairs, read by a scalar load.  patch:
+// bit 31 valid, 30:28 k-step of the wave's share, 27:22 lane, 21:19 element, 15:0 the bf16 itself — the one nonzero
+// weight of that (tile, wave) item that lies below the window (its stored code is 0).
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+#define W13_QUAD_BYTES 3328
+struct W13Extra {
+  uint32_t sg[2];  // the SG words of the item's two quads
+  u32x2 meta;      // {hb, patch} of the item's (tile, wave)
+};
+
+// the wave's nq (0..2) quads starting at `first`, six 16-byte and two 4-byte requests, all through one descriptor
+template <int AUX = 2>
+__device__ __forceinline__ void load_quads_w13(bf16x8 (&wr)[6], uint32_t (&sg)[2], const char *first, int nq, int l,
+                                               int half = -1) {
+  const __amdgpu_buffer_rsrc_t r =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(first), 0, (nq < 0 ? 0 : nq) * W13_QUAD_BYTES, 0x00020000);
+  const bool mine = half < 0 || ((l >> 3) & 1) == half;
+  const int voff = mine ? l * 16 : 0x40000000, voff4 = mine ? l * 4 : 0x40000000;
+  // Order of issue: a wave's loads return in order, and k-step f needs its SG word, its NB word and one L word.  The two
+  // small SG requests go first and NB in front of L0 / L1, so that the first decode waits for four requests, not eight.
+#pragma unroll
+  for (int q = 0; q < 2; ++q) sg[q] = __builtin_amdgcn_raw_buffer_load_b32(r, voff4 + 3072, q * W13_QUAD_BYTES, AUX);
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+#pragma unroll
+    for (int p = 2; p < 5; ++p)  // NB, L0, L1
+      wr[3 * q + p % 3] =
+          __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(r, voff + (p % 3) * 1024, q * W13_QUAD_BYTES, AUX));
+  }
+}
+
+// {hb, patch} of (tile t, wave w): wave-uniform address, constant address space -> one scalar load, no VMEM operation
+__device__ __forceinline__ u32x2 w13_meta(const u32x2 *meta, int t, int w) {
+  typedef const __attribute__((address_space(4))) u32x2 *cptr;
+  return *(cptr)(uintptr_t)(meta + (size_t)__builtin_amdgcn_readfirstlane(t) * 16 + w);
+}
+
+// four H bytes from four codes (one per byte) and the SG word: (c ? hb + c : 0) | sign << 7
+__device__ __forceinline__ uint32_t w13_high(uint32_t c, uint32_t sgw, int r, u16x2 hb2) {
+  const uint32_t nz = ((c + 0x0f0f0f0fu) >> 4) & 0x01010101u;  // 1 in every byte whose code is not 0
+  const u16x2 e = __builtin_bit_cast(u16x2, nz) * hb2 + __builtin_bit_cast(u16x2, c);  // bytes stay below 128: no carry
+  return __builtin_bit_cast(uint32_t, e) | ((sgw << (7 - r)) & 0x80808080u);
+}
+
+// the fragment of k-step f (0..7) of an item, decoded right in front of its MFMA
+__device__ __forceinline__ bf16x8 w13_frag(const bf16x8 (&wr)[6], const W13Extra &ex, int f, int l) {
+  const int q = f >> 2, ff = f & 3;
+  const u32x4 lw = __builtin_bit_cast(u32x4, wr[3 * q + (ff >> 1)]);
+  const uint32_t la = (ff & 1) ? lw[2] : lw[0], lb = (ff & 1) ? lw[3] : lw[1];
+  const uint32_t n = __builtin_bit_cast(u32x4, wr[3 * q + 2])[ff];
+  const uint32_t hb = __builtin_amdgcn_readfirstlane(ex.meta[0]) & 0x7f, pw = __builtin_amdgcn_readfirstlane(ex.meta[1]);
+  const u16x2 hb2 = {(unsigned short)hb, (unsigned short)hb};
+  const uint32_t ha = w13_high(n & 0x0f0f0f0fu, ex.sg[q], 2 * ff, hb2);
+  const uint32_t hh = w13_high((n >> 4) & 0x0f0f0f0fu, ex.sg[q], 2 * ff + 1, hb2);
+  u32x4 o;
+  o[0] = __builtin_amdgcn_perm(ha, la, 0x05010400u);  // L0 H0 L1 H1
+  o[1] = __builtin_amdgcn_perm(ha, la, 0x07030602u);  // L2 H2 L3 H3
+  o[2] = __builtin_amdgcn_perm(hh, lb, 0x05010400u);
+  o[3] = __builtin_amdgcn_perm(hh, lb, 0x07030602u);
+  if ((pw >> 28) == (8u | (uint32_t)f)) {  // wave-uniform: the item's one exception sits in this k-step
+    const int pl = (pw >> 22) & 63, el = (pw >> 19) & 7;
+    const uint32_t raw = pw & 0xffffu;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+      const uint32_t nd = (el & 1) ? (o[d] & 0xffffu) | (raw << 16) : (o[d] & 0xffff0000u) | raw;
+      o[d] = (l == pl && (el >> 1) == d) ? nd : o[d];
+    }
+  }
+  return __builtin_bit_cast(bf16x8, o);
+}
+
 // The 16 fp32 scales of packed tile t (wscale + 16 t, 64-byte aligned) by ONE scalar load: the address is wave-uniform
 // and the pointer is read through the constant address space, so no VMEM operation is issued — the ragged-batch ring
 // kernel counts its vector loads by vmcnt immediates, and the register-resident one would wait for its weight items in

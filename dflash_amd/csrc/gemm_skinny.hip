@@ -69,6 +69,7 @@ struct GemmArgs {
   float *ss_out;  // [ntiles][16] sum over the tile's 16 columns of h_new^2
   // W8 kernels (k_gemm_w8): wp holds e4m3 codes (gemm_rows.h, W8); wscale[16 t + nl] multiplies the fp32 K-sum of
   // packed tile t, column nl, before the epilogue's first rounding.  Last, so that no other field moves.
+  // W13 kernels (k_gemm_w13): wp holds the 13-bit quads and wscale points at the {base, patch} pairs behind them.
   const float *wscale;
 };
 
@@ -213,11 +214,15 @@ constexpr int gemm_fr(int MT, bool CHUNKED) { return CHUNKED ? 4 : (MT == 1 ? 8 
 // W8: the weights are e4m3 codes, two k-steps per 16-byte word (gemm_rows.h): half as many loads per item, each word
 // converted into two fragments in front of its MFMAs; the finishing thread's scale is requested WITH the item's weights.
 // Everything else (masks, the half-tile lane rule, the LDS meeting, the tile plan) is the bf16 form's.
-template <int MT, bool CHUNKED, int EPI, bool NORM, bool W8 = false>
+// W13: the weights are the lossless 13-bit form of bf16 (gemm_rows.h): an item is two quads of four k-steps, six 16-byte and
+// two 4-byte words per lane instead of eight 16-byte ones, decoded into the SAME fragments in front of the MFMAs; the
+// tile's base and the item's patch word come by a scalar load issued with the item's request.  MT = 1, not chunked.
+template <int MT, bool CHUNKED, int EPI, bool NORM, bool W8 = false, bool W13 = false>
 __device__ __forceinline__ void gemm_body(const GemmArgs &a, const SampleArgs &sa) {
   GSTAMP(0);
+  static_assert(!W13 || (MT == 1 && !CHUNKED && !W8), "W13: the single-tile, single-pass bf16 kernels only");
   constexpr int FR = gemm_fr(MT, CHUNKED);
-  constexpr int NW = W8 ? FR / 2 : FR;  // 16-byte weight words per item and lane
+  constexpr int NW = W13 ? 6 : (W8 ? FR / 2 : FR);  // 16-byte weight words per item and lane
   // red[buf][wave][mt][256]: lane l owns floats 4l..4l+3 (its MFMA D regs)
   __shared__ float red[2][16][MT][256];
   __shared__ float ssred[NORM ? MT : 1][16][16];
@@ -253,6 +258,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &a, const SampleArgs &s
 
   bf16x8 wA[NW], wB[NW];
   float scA = 1.f, scB = 1.f;  // W8: the scale of this thread's column (tid & 15) of the item in wA / wB
+  W13Extra exA{}, exB{};       // W13: the item's sign words and its {base, patch} pair
   bf16x8 xA[MT][FR], xB[MT][FR];
   bf16x8 xr[MT][FR];  // activations of the (single) chunk stay in registers for the launch
 
@@ -310,8 +316,18 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &a, const SampleArgs &s
       sc = a.wscale[(size_t)t * 16 + (tid & 15)];
     }
   };
-  auto load_item = [&](bf16x8(&wr)[NW], float &sc, bf16x8(&xb)[MT][FR], int t, int c, int half) {
-    if constexpr (W8)
+  // W13: (K is 2048 or 4096, so ks0 and nf are whole quads) the meta pair WITH the request, as the W8 scale
+  auto load_w13 = [&](bf16x8(&wr)[NW], W13Extra &ex, int t, int ks0, int nf, int half) {
+    if constexpr (W13) {
+      const char *base = reinterpret_cast<const char *>(a.wp);
+      load_quads_w13(wr, ex.sg, base + ((size_t)t * (a.KS >> 2) + (ks0 >> 2)) * W13_QUAD_BYTES, nf >> 2, l, half);
+      ex.meta = w13_meta(reinterpret_cast<const u32x2 *>(a.wscale), nf > 0 ? t : 0, w);  // (nothing fetched: any valid pair)
+    }
+  };
+  auto load_item = [&](bf16x8(&wr)[NW], float &sc, W13Extra &ex, bf16x8(&xb)[MT][FR], int t, int c, int half) {
+    if constexpr (W13)
+      load_w13(wr, ex, t, ks0_of(c), nf_of(c), half);
+    else if constexpr (W8)
       load_w8(wr, sc, t, ks0_of(c), nf_of(c), half);
     else
       load_ksteps<FR>(wr, a.wp + ((size_t)t * a.KS + ks0_of(c)) * 64, nf_of(c), l, half);
@@ -391,7 +407,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &a, const SampleArgs &s
     }
   };
 
-  auto process = [&](bf16x8(&wr)[NW], float wsc, bf16x8(&xb)[MT][FR], int t, int c, int pos) {
+  auto process = [&](bf16x8(&wr)[NW], float wsc, const W13Extra &ex, bf16x8(&xb)[MT][FR], int t, int c, int pos) {
     if (!CHUNKED || c == 0) {
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) acc[mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -406,7 +422,12 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &a, const SampleArgs &s
           const bool keep = ks0c + f < a.KS && (a.src[mt].mode == 0 || (l & 15) < nv[mt]);
           xv = keep ? xb[mt][f] : (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
         }
-        acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(weight_frag<W8>(wr, f), xv, acc[mt], 0, 0, 0);
+        bf16x8 wf;
+        if constexpr (W13)
+          wf = w13_frag(wr, ex, f, l);
+        else
+          wf = weight_frag<W8>(wr, f);
+        acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, xv, acc[mt], 0, 0, 0);
       }
     if (!CHUNKED || c == a.nch - 1) finish(t, pos, wsc);
   };
@@ -496,7 +517,9 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &a, const SampleArgs &s
     // load_ksteps clips at the wave's share through the buffer descriptor instead (zero weights, no traffic), and
     // activations past the share are zero as well.  (The expert list of an MoE launch is a dependent scalar load: that
     // launch asks for its first weights once it knows the tile.)
-    if constexpr (W8)
+    if constexpr (W13)
+      load_w13(wA, exA, SILU ? 2 * (int)blockIdx.x : first_tile, ks0_of(0), first_live ? nf0 : 0, first_half);
+    else if constexpr (W8)
       load_w8(wA, scA, SILU ? 2 * (int)blockIdx.x : first_tile, ks0_of(0), first_live ? nf0 : 0, first_half);
     else if (!moe)
       load_ksteps<FR>(wA, a.wp + ((size_t)(SILU ? 2 * blockIdx.x : first_tile) * a.KS + ks0_of(0)) * 64,
@@ -546,6 +569,8 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &a, const SampleArgs &s
     // chunked kernels build their activation fragments per item: item 0's behind the weights already requested
     if constexpr (W8)
       load_w8(wA, scA, first_tile, ks0_of(0), first_live ? nf0 : 0, first_half);
+    else if constexpr (W13)
+      ;  // (no chunked W13 form: the static_assert above)
     else if (nitems > 0 || !moe)
       load_ksteps<FR>(wA, a.wp + ((size_t)first_tile * a.KS + ks0_of(0)) * 64, first_live ? nf0 : 0, l, first_half);
     GSTAMP(6);
@@ -567,8 +592,8 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &a, const SampleArgs &s
       }
       // (requesting unconditionally — a zero-length dummy past the last item, so that hipcc can count the loads in
       // flight — was tried twice in this 16-wave kernel, rounds 2 and 3: 20.4 -> 20.8 us on down_proj; not kept)
-      if (i + 1 < nitems) load_item(wB, scB, xB, tile_of(jn), cn, half_of(jn));
-      process(wA, scA, xA, tile_of(j), c, j);
+      if (i + 1 < nitems) load_item(wB, scB, exB, xB, tile_of(jn), cn, half_of(jn));
+      process(wA, scA, exA, xA, tile_of(j), c, j);
       if (i == 0) GSTAMP(4);
       if (i + 1 >= nitems) break;
       int j2 = jn, c2 = cn + 1;  // item i+2
@@ -576,8 +601,8 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &a, const SampleArgs &s
         c2 = 0;
         ++j2;
       }
-      if (i + 2 < nitems) load_item(wA, scA, xA, tile_of(j2), c2, half_of(j2));
-      process(wB, scB, xB, tile_of(jn), cn, jn);
+      if (i + 2 < nitems) load_item(wA, scA, exA, xA, tile_of(j2), c2, half_of(j2));
+      process(wB, scB, exB, xB, tile_of(jn), cn, jn);
       if (i + 2 >= nitems) break;
       j = j2;
       c = c2;
@@ -617,6 +642,12 @@ __global__ __launch_bounds__(1024) void k_gemm(GEMM_HEAD_PARAMS, GemmArgs rest) 
 template <bool CHUNKED, int EPI, bool NORM>
 __global__ __launch_bounds__(1024) void k_gemm_w8(GEMM_HEAD_PARAMS, GemmArgs rest) {
   gemm_body<1, CHUNKED, EPI, NORM, true>(with_head<CHUNKED, NORM>(rest, GEMM_HEAD_NAMES), SampleArgs{});
+}
+
+// the W13 form (lossless 13-bit bf16, gemm_body): gate/up + SiLU and lm_head + argmax, the two launches it pays for
+template <int EPI, bool NORM>
+__global__ __launch_bounds__(1024) void k_gemm_w13(GEMM_HEAD_PARAMS, GemmArgs rest) {
+  gemm_body<1, false, EPI, NORM, false, true>(with_head<false, NORM>(rest, GEMM_HEAD_NAMES), SampleArgs{});
 }
 
 template <bool NORM>
@@ -661,6 +692,33 @@ bool launch_gemm(GemmArgs &a, dim3 grid, hipStream_t stream) {
     }
   }
   hipLaunchKernelGGL((k_gemm<MT, CHUNKED, EPI, false>), grid, dim3(1024), 0, stream, GEMM_HEAD_OF(h), a);
+  return true;
+}
+
+// Bytes of a DFL_W_BF16X13 weight of N x K (dflash_hip.h): the quads of all tiles, then the {base, patch} pairs
+static int64_t w13_quads_bytes(int N, int K) { return (int64_t)(N / 16) * (K / 128) * W13_QUAD_BYTES; }
+
+// The W13 launch of dfl_gemm_silu_mul / dfl_gemm_argmax.  The layout covers whole quads per wave: K = 2048 (nfr = 4) or
+// 4096 (nfr = 8); a.wp is the weight's first byte, N its packed rows.
+template <int EPI>
+bool launch_gemm_w13(const char *who, GemmArgs &a, const dfl_weight *w, int N, dim3 grid, hipStream_t stream) {
+  if (w->scale) {
+    dfl_set_error("%s: a DFL_W_BF16X13 weight takes no scale vector (the bases and patch words follow the codes)", who);
+    return false;
+  }
+  if (a.KS % 64 || a.nfr % 4 || a.nfr * 16 != a.KS) {
+    dfl_set_error("%s: DFL_W_BF16X13 covers K = 2048 and K = 4096 only (whole quads of four k-steps per wave; K=%d, %d k-steps "
+                  "per wave)", who, a.KS * 32, a.nfr);
+    return false;
+  }
+  a.wscale = reinterpret_cast<const float *>(reinterpret_cast<const char *>(w->wp) + w13_quads_bytes(N, a.KS * 32));
+  a.gx = (int)grid.x;
+  GemmHead h;
+  if (!gemm_head<false>(h, a)) return false;
+  if (a.src[0].mode == 2)
+    hipLaunchKernelGGL((k_gemm_w13<EPI, true>), grid, dim3(1024), 0, stream, GEMM_HEAD_OF(h), a);
+  else
+    hipLaunchKernelGGL((k_gemm_w13<EPI, false>), grid, dim3(1024), 0, stream, GEMM_HEAD_OF(h), a);
   return true;
 }
 
@@ -881,7 +939,7 @@ extern "C" int dfl_gemm_f32(const void *wp, const dfl_rows *x0, const dfl_rows *
 // with one fp32 scale per packed row (w->scale), K % 64 == 0, and every wave's share (nfr) is rounded up to whole k-step
 // pairs.
 namespace {
-template <bool W8>
+template <bool W8, bool W13 = false>
 int gemm_silu_mul_impl(const char *who, const dfl_weight *w, const dfl_rows *x, int I, int K, void *act_frag,
                        const int32_t *dyn, void *stream) {
   DFL_REQUIRE(w->wp && act_frag && (!W8 || w->scale), "%s: null pointer", who);
@@ -899,7 +957,11 @@ int gemm_silu_mul_impl(const char *who, const dfl_weight *w, const dfl_rows *x, 
   if (W8) a.nfr += a.nfr & 1;
   a.nch = 1;
   a.act = (bf16_t *)act_frag;
-  if (!launch_gemm<1, false, EPI_SILU, W8>(a, dim3(grid_x_for(I / 16), 1), (hipStream_t)stream)) return DFL_EINVAL;
+  if constexpr (W13) {
+    if (!launch_gemm_w13<EPI_SILU>(who, a, w, 2 * I, dim3(grid_x_for(I / 16), 1), (hipStream_t)stream)) return DFL_EINVAL;
+  } else if (!launch_gemm<1, false, EPI_SILU, W8>(a, dim3(grid_x_for(I / 16), 1), (hipStream_t)stream)) {
+    return DFL_EINVAL;
+  }
   DFL_CHECK_LAUNCH(who);
   return DFL_OK;
 }
@@ -908,6 +970,8 @@ int gemm_silu_mul_impl(const char *who, const dfl_weight *w, const dfl_rows *x, 
 extern "C" int dfl_gemm_silu_mul(const dfl_weight *w_gateup, const dfl_rows *x, int I, int K, void *act_frag,
                                  const int32_t *dyn, void *stream) {
   const char *who = "dfl_gemm_silu_mul";
+  if (w_gateup && w_gateup->format == DFL_W_BF16X13)  // (weight_ok knows the two formats every entry point takes)
+    return gemm_silu_mul_impl<false, true>(who, w_gateup, x, I, K, act_frag, dyn, stream);
   if (!weight_ok(who, w_gateup)) return DFL_EINVAL;
   return w_gateup->format == DFL_W_BF16 ? gemm_silu_mul_impl<false>(who, w_gateup, x, I, K, act_frag, dyn, stream)
                                         : gemm_silu_mul_impl<true>(who, w_gateup, x, I, K, act_frag, dyn, stream);
@@ -954,7 +1018,7 @@ namespace {
 int gemm_argmax_impl(const char *who, const dfl_weight *w, const dfl_rows *x, int V, int K, int row0, int nrows,
                      const int32_t *dyn, int nrows_dyn_word, void *ws, int64_t *out_ids, int out_off, void *logits,
                      float *margin_out, hipEvent_t ev0, hipEvent_t ev1, void *stream, const SampleArgs *smp = nullptr) {
-  const bool w8 = w->format == DFL_W_E4M3;
+  const bool w8 = w->format == DFL_W_E4M3, w13 = w->format == DFL_W_BF16X13;
   DFL_REQUIRE(w->wp && ws && out_ids && (!w8 || w->scale), "%s: null pointer", who);
   DFL_REQUIRE(V > 0 && K > 0 && V % 16 == 0 && K % (w8 ? 64 : 32) == 0, "%s: need V%%16==0, K%%%d==0 (V=%d K=%d)", who,
               w8 ? 64 : 32, V, K);
@@ -996,6 +1060,8 @@ int gemm_argmax_impl(const char *who, const dfl_weight *w, const dfl_rows *x, in
       hipLaunchKernelGGL(k_gemm_s<true>, dim3(gx, 1), dim3(1024), 0, (hipStream_t)stream, GEMM_HEAD_OF(h), a, *smp);
     else
       hipLaunchKernelGGL(k_gemm_s<false>, dim3(gx, 1), dim3(1024), 0, (hipStream_t)stream, GEMM_HEAD_OF(h), a, *smp);
+  } else if (w13) {
+    if (!launch_gemm_w13<EPI_ARGMAX>(who, a, w, V, dim3(gx, 1), (hipStream_t)stream)) return DFL_EINVAL;
   } else if (w8) {
     if (!launch_gemm<1, false, EPI_ARGMAX, true>(a, dim3(gx, 1), (hipStream_t)stream)) return DFL_EINVAL;
   } else {
@@ -1013,7 +1079,7 @@ extern "C" int dfl_gemm_argmax(const dfl_weight *w, const dfl_rows *x, int V, in
                                const int32_t *dyn, int nrows_dyn_word, void *ws, int64_t *out_ids, int out_off,
                                void *logits, float *margin_out, void *ev_start, void *ev_end, void *stream) {
   const char *who = "dfl_gemm_argmax";
-  if (!weight_ok(who, w)) return DFL_EINVAL;
+  if (!(w && w->format == DFL_W_BF16X13) && !weight_ok(who, w)) return DFL_EINVAL;
   return gemm_argmax_impl(who, w, x, V, K, row0, nrows, dyn, nrows_dyn_word, ws, out_ids, out_off, logits, margin_out,
                           (hipEvent_t)ev_start, (hipEvent_t)ev_end, stream);
 }

@@ -76,8 +76,12 @@ WEIGHT_FORMATS = ("bf16", "fp8_e4m3")
 
 
 class DFlashDraftModel:
-    def __init__(self, config, device=None, weight_format: str = "bf16"):
-        """weight_format: "bf16" (default), or "fp8_e4m3": every Linear weight of the draft is quantised at load time
+    def __init__(self, config, device=None, weight_format: str = "bf16", stream_format: str = "auto"):
+        """stream_format: "auto" (default): a bf16 model streams gate/up and the lm_head of a single request's block of
+        <= 16 rows from a lossless 13-bit copy (ops.pack_weight_bf16x13) wherever the layout covers
+        the shape (hidden 2048 or 4096) and the packer takes the matrix — same bits out, 13/16 of the bytes in; the plain
+        packed weights stay resident for every other path.  "bf16": plain packed bf16 everywhere.
+        weight_format: "bf16" (default), or "fp8_e4m3": every Linear weight of the draft is quantised at load time
         to OCP e4m3 codes with one power-of-two scale per output row (ops.quantize_fp8_rows) — ONE quantised model:
         `self.w` then holds the dequantised values (exact in bf16) for every path without an fp8 kernel, `self.w8` the
         codes, which the draft forward streams at one byte per weight: a single request's block, the ragged batch and
@@ -87,6 +91,8 @@ class DFlashDraftModel:
         if weight_format not in WEIGHT_FORMATS:
             raise ValueError(f"weight_format must be one of {WEIGHT_FORMATS}, got {weight_format!r}")
         self.weight_format = weight_format
+        self.x13 = ops.check_stream_format(stream_format) and weight_format == "bf16"
+        self.stream_format = stream_format
         self.config = DFlashConfig.from_any(config)
         c = self.config
         if c.head_dim != 128:
@@ -105,6 +111,7 @@ class DFlashDraftModel:
         if weight_format == "fp8_e4m3" and any(k % 64 for k in (c.hidden_size, c.intermediate_size, c.fc_in, c.q_dim)):
             raise NotImplementedError("fp8_e4m3 weights need hidden, intermediate, fc input and q widths % 64 == 0")
         self.w: Optional[dict] = None
+        self.gu13: list = []             # stream_format="auto": per layer, the 13-bit twin of w["layers"][i]["gu"] or None
         self.w8: Optional[dict] = None   # fp8_e4m3: ops.Fp8Weight twins of the matrices in self.w (same keys)
         # fp8_e4m3 only: False = run everything on the dequantised bf16 copy (the second implementation the tests compare)
         self.fp8_stream = True
@@ -161,6 +168,7 @@ class DFlashDraftModel:
              "norm": dev("norm.weight"), "layers": []}
         if fp8:
             w8["fc"] = ops.pack_weight_fp8(*top8.pop("fc"))
+        gu13 = []
         for i in range(c.num_hidden_layers):
             p = f"layers.{i}."
             l8 = {}
@@ -179,6 +187,9 @@ class DFlashDraftModel:
                 "q_norm": dev(p + "self_attn.q_norm.weight"), "k_norm": dev(p + "self_attn.k_norm.weight"),
                 "ln1": dev(p + "input_layernorm.weight"), "ln2": dev(p + "post_attention_layernorm.weight"),
             })
+            # the 13-bit twin of gate/up per layer, or None where plain bf16 stays (ops.bf16x13_twin)
+            gu13.append(ops.bf16x13_twin(w["layers"][-1]["gu"], 2 * c.intermediate_size, c.hidden_size, "gateup")
+                        if self.x13 else None)
             del qkv, gate, up, o, down
         # context K/V weights of ALL layers as one packed weight (tile-major layout: the k/v column tiles of
         # each layer's packed qkv, concatenated): the context rows' K/V of every layer depend only on the
@@ -194,18 +205,19 @@ class DFlashDraftModel:
         torch.cuda.synchronize(self.device)
         self.w = w
         self.w8 = w8
+        self.gu13 = gu13
         self._tile_layers = {}
         self._ws = None  # row sources point at the weights: rebuild with them
         return self
 
     @classmethod
-    def from_pretrained(cls, path: str, device=None, weight_format: str = "bf16", **_):
+    def from_pretrained(cls, path: str, device=None, weight_format: str = "bf16", stream_format: str = "auto", **_):
         """HF checkpoint directory: config.json (+ block_size / num_target_layers /
-        dflash_config, model/dflash.py:157,162-163) and *.safetensors shards.  weight_format: as the constructor's."""
+        dflash_config, model/dflash.py:157,162-163) and *.safetensors shards.  weight_format, stream_format: as the constructor's."""
         from safetensors.torch import load_file
         with open(os.path.join(path, "config.json")) as f:
             cfg = json.load(f)
-        model = cls(cfg, device=device, weight_format=weight_format)
+        model = cls(cfg, device=device, weight_format=weight_format, stream_format=stream_format)
         sd = {}
         for fn in sorted(os.listdir(path)):
             if fn.endswith(".safetensors"):
@@ -284,6 +296,8 @@ class DFlashDraftModel:
         if key not in self._lm_head_cache:
             self._lm_head_cache.clear()
             self._lm_head_cache[key] = ops.pack_weight(wt.detach().to(device=self.device, dtype=BF16).contiguous())
+            if self.x13:   # its 13-bit twin now, at load, not inside the first cycle (draft_tokens finds it by the tensor)
+                ops.bf16x13_twin(self._lm_head_cache[key], wt.shape[0], wt.shape[1], "lm_head")
         return self._lm_head_cache[key]
 
     def packed_lm_head_fp8(self, lm_head) -> ops.Fp8Weight:
@@ -524,8 +538,9 @@ class DFlashDraftModel:
                 if not fuse_o:
                     ops.gemm_resid(lm["o"], src["attn"][t], H, c.q_dim, hrow[t], add_residual=True, ss_out=ws["ss_h"][t],
                                    dyn=dt)
+            gu = lm["gu"] if ww is not w or self.gu13[i] is None else self.gu13[i]
             for t, dt in tiles:
-                ops.gemm_silu_mul(lm["gu"], src["ln2"][i][t], I, H, ws["act_frag"][t], dt)
+                ops.gemm_silu_mul(gu, src["ln2"][i][t], I, H, ws["act_frag"][t], dt)
             for t, dt in tiles:
                 ops.gemm_resid(lm["down"], src["act"][t], H, I, hrow[t], add_residual=True, ss_out=ws["ss_h"][t],
                                dyn=dt)
@@ -574,7 +589,8 @@ class DFlashDraftModel:
                      sample: Optional[dict] = None) -> None:
         """block_ids[1:bs] <- argmax(lm_head(hidden[1:bs])) (model/dflash.py:238,245,247).
         hid_frag: what draft_block returned (one row source per 16-row tile; a single source = one tile).
-        lm_head_wp: the packed bf16 lm_head, or (greedy only: sample is None) an ops.Fp8Weight of it.
+        lm_head_wp: the packed bf16 lm_head, or (greedy only: sample is None) an ops.Fp8Weight of it.  A bf16 head's
+        single-tile argmax launch streams its 13-bit twin where stream_format="auto" has one (shared with the target).
         logits (bf16 [16 * tiles, V]) / margins (fp32 [>= bs]): margins[j] <- top-1 minus top-2 draft
         logit of block slot j >= 1, the reference's per-position confidence
         (benchmark_candidate_solutions.py:296-302).
@@ -619,7 +635,10 @@ class DFlashDraftModel:
             ev = self.lm_head_events if t == 0 else None   # bench.py: the lm_head kernel itself between two events
             if ev is not None and self.lm_head_events_log is not None:
                 self.lm_head_events_log.append(ev)
-            ops.gemm_argmax(lm_head_wp, x, c.vocab_size, c.hidden_size, row0, nrows, ws["argmax_ws"], block_ids,
+            head = lm_head_wp
+            if self.x13 and isinstance(head, torch.Tensor):
+                head = ops.bf16x13_twin(head, c.vocab_size, c.hidden_size, "lm_head") or head
+            ops.gemm_argmax(head, x, c.vocab_size, c.hidden_size, row0, nrows, ws["argmax_ws"], block_ids,
                             16 * t + row0, logits=None if logits is None else logits[16 * t:16 * t + 16],
                             margins=margins, events=ev)
 

@@ -9,7 +9,7 @@ from typing import NamedTuple, Optional
 
 import torch
 
-from ._lib import W_BF16, W_E4M3, Rows, Weight, check, lib
+from ._lib import W_BF16, W_BF16X13, W_E4M3, Rows, Weight, check, lib
 
 BF16, F32, I32, I64 = torch.bfloat16, torch.float32, torch.int32, torch.int64
 DYN_S, DYN_TAU, DYN_BS, DYN_POS0, DYN_START, DYN_STOP, DYN_CYCLE = range(7)
@@ -189,9 +189,125 @@ def tile_layers(layers: list, layers8: list, qkv_parts: bool, cache: dict) -> li
     return cache[qkv_parts]
 
 
+# ---- bf16x13: the packed bf16 weight in 13 bits per element, losslessly ----
+X13_QUAD_BYTES = 3328   # four k-steps of one 16-column tile: L0, L1, NB (1024 B each) and SG (256 B); csrc/gemm_rows.h
+STREAM_FORMATS = ("auto", "bf16")
+# Which matrix kinds stream_format="auto" packs: each kept only where its slowest repeat beat the plain form's fastest
+# (profiles/bf16x13_ab.txt, part 1)
+X13_KINDS = {"gateup": True, "lm_head": True}
+
+
+class Bf16x13Weight(NamedTuple):
+    """A packed bf16 weight re-coded by pack_weight_bf16x13: gemm_silu_mul / gemm_argmax take one in place of the packed
+    bf16 tensor and compute the same bits from 13/16 of the bytes."""
+    data: torch.Tensor    # uint8: [N/16][K/128] quads of X13_QUAD_BYTES, then int32 [N/16][16][2] {base, patch}
+    N: int
+    K: int
+
+
+def bf16x13_covers(N: int, K: int) -> bool:
+    """The layout holds whole quads of four k-steps per wave: 16 waves x 4 or x 8 k-steps."""
+    return N > 0 and N % 16 == 0 and K in (2048, 4096)
+
+
+def pack_weight_bf16x13(wp: torch.Tensor, N: int, K: int, tiles_per_pass: int = 256):
+    """wp: the packed bf16 weight of N x K (pack_weight, or pack_weight_gateup with N = 2I: its tiles are already
+    interleaved, and every packed tile — a gate tile, an up tile — gets a base of its own).
+    Returns (Bf16x13Weight or None, report).  Per packed tile hb = max(0, max(H & 0x7f) - 15) with H the bf16's high
+    byte; an element keeps its low byte, its sign and a code c (0: H & 0x7f == 0; 1..15: H & 0x7f == hb + c).  A nonzero
+    element below the window (H & 0x7f in 1..hb) is an exception: ONE per (tile, wave) item is carried exactly in that
+    item's patch word; a second one refuses the matrix (None: the caller keeps plain bf16).  report = {"items": (tile,
+    wave) items, "patched": items with a patch word, "refused": items with two or more exceptions}.
+    Plain tensor ops on wp's device (CPU included), `tiles_per_pass` tiles at a time; runs once at load."""
+    if not bf16x13_covers(N, K):
+        raise ValueError(f"dflash_amd: bf16x13 covers K = 2048 or 4096 and N % 16 == 0 (N={N} K={K})")
+    if wp.dtype != BF16 or wp.numel() != N * K:
+        raise ValueError("dflash_amd: pack_weight_bf16x13 takes the packed bf16 weight of N * K elements")
+    nt, KS, dev = N // 16, K // 32, wp.device
+    nfr, Q = KS // 16, KS // 4
+    src = wp.view(torch.int16).view(nt, KS, 64, 8)
+    qbytes = nt * Q * X13_QUAD_BYTES
+    data = torch.empty(qbytes + nt * 16 * 8, dtype=U8, device=dev)
+    quads, meta = data[:qbytes].view(nt, Q, X13_QUAD_BYTES), data[qbytes:].view(I32).view(nt, 16, 2)
+    rsh = torch.arange(8, dtype=I32, device=dev).view(1, 1, 4, 1, 2, 1)   # r = 2 f + g
+    patched = refused = 0
+    for t0 in range(0, nt, tiles_per_pass):
+        wi = src[t0:t0 + tiles_per_pass].to(I32) & 0xffff
+        T = wi.shape[0]
+        lo, h7, sign = (wi & 0xff).to(U8), (wi >> 8) & 0x7f, wi >> 15
+        hb = (h7.amax(dim=(1, 2, 3)) - 15).clamp_(min=0)
+        c = h7 - hb.view(T, 1, 1, 1)
+        exc = (h7 != 0) & (c < 1)
+        c = torch.where(c < 1, torch.zeros_like(c), c)             # (h7 == 0 lies below hb + 1 as well)
+        # exceptions per (tile, wave) item: wave w owns k-steps w * nfr .. of the tile
+        ex = exc.view(T, 16, nfr * 512)
+        cnt = ex.sum(dim=2)
+        refused += int((cnt > 1).sum())
+        patched += int((cnt == 1).sum())
+        idx = ex.to(I32).argmax(dim=2)                             # (the first one: the only one where cnt == 1)
+        raw = wi.view(T, 16, nfr * 512).gather(2, idx.unsqueeze(2)).squeeze(2)
+        word = ((8 + idx // 512) << 28) | (((idx // 8) % 64) << 22) | ((idx % 8) << 19) | raw      # int64
+        word = torch.where(cnt == 1, word - (1 << 32), torch.zeros_like(word)).to(I32)             # bit 31: the sign
+        meta[t0:t0 + T, :, 0] = hb.to(I32).view(T, 1)
+        meta[t0:t0 + T, :, 1] = word
+        lq = lo.view(T, Q, 4, 64, 8)
+        cq = c.view(T, Q, 4, 64, 8)
+        nb = (cq[..., :4] | (cq[..., 4:] << 4)).to(U8)              # byte b = c[b] | c[b + 4] << 4
+        sg = (sign.view(T, Q, 4, 64, 2, 4) << rsh).sum(dim=(2, 4)).to(U8)   # [T, Q, 64, 4]: bit r of byte b
+        out = quads[t0:t0 + T]
+        out[:, :, 0:1024] = lq[:, :, 0:2].permute(0, 1, 3, 2, 4).reshape(T, Q, 1024)
+        out[:, :, 1024:2048] = lq[:, :, 2:4].permute(0, 1, 3, 2, 4).reshape(T, Q, 1024)
+        out[:, :, 2048:3072] = nb.permute(0, 1, 3, 2, 4).reshape(T, Q, 1024)
+        out[:, :, 3072:3328] = sg.reshape(T, Q, 256)
+    report = {"items": nt * 16, "patched": patched, "refused": refused}
+    if refused:
+        return None, report
+    return Bf16x13Weight(data, N, K), report
+
+
+_x13_twins = {}   # data_ptr of a packed bf16 tensor -> (weak reference to it, N, K, its Bf16x13Weight or None, report)
+
+
+def bf16x13_twin(wp: torch.Tensor, N: int, K: int, kind: str):
+    """The 13-bit twin stream_format="auto" streams in place of the packed bf16 tensor `wp`, or None where plain bf16
+    stays: a kind the measurement did not keep (X13_KINDS), a shape the layout does not cover, a matrix the packer refused.
+    Packed once per tensor — draft and target share one lm_head twin as they share the packed head — and kept while the
+    tensor lives."""
+    import weakref
+    if not X13_KINDS[kind] or not bf16x13_covers(N, K):
+        return None
+    key = wp.data_ptr()
+    hit = _x13_twins.get(key)
+    if hit is None or hit[0]() is not wp or hit[1:3] != (N, K):
+        for k in [k for k, v in _x13_twins.items() if v[0]() is None]:
+            del _x13_twins[k]
+        twin, report = pack_weight_bf16x13(wp, N, K)
+        hit = _x13_twins[key] = (weakref.ref(wp), N, K, twin, report)
+    return hit[3]
+
+
+def bf16x13_report() -> dict:
+    """What the live twins came to: matrices packed, matrices kept as plain bf16 because the packer refused them, and the
+    patched / refused (tile, wave) items over all of them."""
+    live = [v for v in _x13_twins.values() if v[0]() is not None]
+    return {"packed": sum(v[3] is not None for v in live), "kept_bf16": sum(v[3] is None for v in live),
+            "patched_items": sum(v[4]["patched"] for v in live), "refused_items": sum(v[4]["refused"] for v in live)}
+
+
+def check_stream_format(stream_format: str) -> bool:
+    """True for "auto" (the 13-bit twins where they apply), False for "bf16"."""
+    if stream_format not in STREAM_FORMATS:
+        raise ValueError(f"stream_format must be one of {STREAM_FORMATS}, got {stream_format!r}")
+    return stream_format == "auto"
+
+
 def _w(wp, N: int, K: int, name: str) -> Weight:
-    """The dfl_weight of a launch: a packed bf16 tensor, or an Fp8Weight of the launch's N x K.  Read on the host during
-    the call only; the caller's references keep the tensors alive."""
+    """The dfl_weight of a launch: a packed bf16 tensor, or an Fp8Weight / a Bf16x13Weight of the launch's N x K.  Read
+    on the host during the call only; the caller's references keep the tensors alive."""
+    if isinstance(wp, Bf16x13Weight):
+        if (wp.N, wp.K) != (N, K):
+            raise ValueError(f"dflash_amd: {name} is a bf16x13 weight of {wp.N} x {wp.K}, the launch asks for {N} x {K}")
+        return Weight(_p(wp.data, U8, name), None, W_BF16X13)
     if not isinstance(wp, Fp8Weight):
         return Weight(_p(wp, BF16, name), None, W_BF16)
     if (wp.N, wp.K) != (N, K):

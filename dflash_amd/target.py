@@ -78,8 +78,14 @@ class _Weight:
 
 class NativeTarget:
     def __init__(self, hf_model, max_splits: int = 32, attn_impl: str = "head", keep_hf: bool = True,
-                 prefill: str = "native", weight_format: str = "bf16", expert_format: str = "bf16"):
-        """weight_format: "bf16" (default), or "fp8_e4m3": every Linear weight of the target — q/k/v, o_proj, gate, up and
+                 prefill: str = "native", weight_format: str = "bf16", expert_format: str = "bf16",
+                 stream_format: str = "auto"):
+        """stream_format: "auto" (default): a bf16 target's verify of <= 16 block rows streams each dense layer's gate/up
+        and, at temperature 0, the lm_head from a lossless 13-bit copy (ops.pack_weight_bf16x13)
+        wherever the layout covers the shape (hidden 2048 or 4096) and the packer takes the matrix: the same bits out,
+        13/16 of the bytes in.  The plain packed weights stay resident for every other path (prefill, wide blocks, the
+        ragged batch, sampled heads): 13/16 of gate/up and lm_head more memory.  "bf16": plain packed bf16 everywhere.
+        weight_format: "bf16" (default), or "fp8_e4m3": every Linear weight of the target — q/k/v, o_proj, gate, up and
         down of every layer, and the lm_head — is quantised here to OCP e4m3 codes with one power-of-two scale per output
         row (ops.quantize_fp8_rows; W8A16, weight-only).  The quantised target IS the model: THE CALLER'S hf_model IS
         MODIFIED — its Linear weights are overwritten in place with q * scale (with tied embeddings the embedding table
@@ -106,6 +112,8 @@ class NativeTarget:
         through the MFMA GEMMs of csrc/prefill.hip on the same packed weights; "hf" = through the wrapped model.
         keep_hf = False: the wrapped model is dropped after packing (ONE copy of the layers' weights in memory; the
         caller must drop its own reference too); needs the native prefill."""
+        self.x13 = ops.check_stream_format(stream_format) and weight_format == "bf16"
+        self.stream_format = stream_format
         if attn_impl not in ("head", "fused"):
             raise ValueError("attn_impl must be 'head' or 'fused'")
         if prefill not in ("native", "hf"):
@@ -201,9 +209,10 @@ class NativeTarget:
             mat("lm_head.weight", h8, "lm")
             self.lm_wp8 = ops.pack_weight_fp8(*h8.pop("lm"))
         self.layers = []
+        self.gu13 = []   # stream_format="auto": per layer, the 13-bit twin of a dense layer's gate/up or None
         for i in range(self.L):
             p = f"model.layers.{i}."
-            l8 = {}
+            l8, gu13 = {}, None
             qkv = torch.cat([mat(p + "self_attn.q_proj.weight", l8, "q"), mat(p + "self_attn.k_proj.weight", l8, "k"),
                              mat(p + "self_attn.v_proj.weight", l8, "v")], dim=0)
             has_qk = (p + "self_attn.q_norm.weight") in sd
@@ -249,6 +258,8 @@ class NativeTarget:
                 lw["gu"] = ops.pack_weight_gateup(mat(p + "mlp.gate_proj.weight", l8, "gate"),
                                                   mat(p + "mlp.up_proj.weight", l8, "up"))
                 lw["down"] = ops.pack_weight(mat(p + "mlp.down_proj.weight", l8, "down"))
+                if self.x13:   # the 13-bit twin, or None where plain bf16 stays (ops.bf16x13_twin)
+                    gu13 = ops.bf16x13_twin(lw["gu"], 2 * self.I, self.H, "gateup")
                 if e8:
                     self.experts8.append(None)
             if fp8:
@@ -256,6 +267,7 @@ class NativeTarget:
                     raise NotImplementedError("NativeTarget: fp8_e4m3 needs dense MLP layers")
                 self.layers8.append(ops.pack_layer_fp8(l8))
             self.layers.append(lw)
+            self.gu13.append(gu13)
             del qkv, l8
         self.norm = w("model.norm.weight")
         self.embed = w("model.embed_tokens.weight")
@@ -315,6 +327,7 @@ class NativeTarget:
                 raise NotImplementedError("NativeTarget(keep_hf=False) needs the native prefill (widths % 128, FFN widths % 64)")
             if self.lm_wp is None:
                 self.lm_wp = ops.pack_weight(self.lm_head.weight.detach().to(BF16).contiguous())
+                self._head_twin()
             self.hf = None
             self.model = SimpleNamespace(embed_tokens=_Weight(self.embed), rotary_emb=self._rotary)
             self.lm_head = _Weight(self.lm_head.weight.detach())
@@ -380,6 +393,13 @@ class NativeTarget:
 
     def share_lm_head(self, packed: torch.Tensor) -> None:
         self.lm_wp = packed
+        self._head_twin()
+
+    def _head_twin(self) -> None:
+        """stream_format="auto": the packed head's 13-bit twin at load, not inside the first verify (one per packed
+        tensor: a head shared with the draft has one twin)."""
+        if self.x13 and self.lm_wp is not None:
+            ops.bf16x13_twin(self.lm_wp, self.V, self.H, "lm_head")
 
     def streams_fp8(self, bs: int = 16) -> bool:
         """Whether verify() streams the e4m3 codes for a block of `bs` rows: an fp8 target, fp8_stream, the head
@@ -813,6 +833,7 @@ class NativeTarget:
         w8 = self.streams_fp8(bs)
         Lm = self.layers8 if w8 else Ls   # the matrices this verify streams: the layers' own, or their e4m3 twins
         head = self.lm_wp8 if w8 else self.lm_wp
+        x13 = self.x13 and not w8
         if len(tiles) == 2 and self.wide_one_pass and self.attn_impl == "head":
             return self._verify_wide(block_ids, start, cache, bs, tap_layers, taps, logits_out, temperature, cos, sin, seed,
                                      flt)
@@ -863,8 +884,9 @@ class NativeTarget:
                 gev = self.gu_events if (self.gu_events is not None and self.gu_events[0] == i) else None
                 if gev is not None:       # bench.py: this layer's gate/up launch between two events on the launch stream
                     gev[1].record()
+                gu = self.gu13[i] if x13 and self.gu13[i] is not None else lm["gu"]
                 for t, dt in tiles:
-                    ops.gemm_silu_mul(lm["gu"], src["ln2"][i][t], self.I, H, ws["act"][t], dt)
+                    ops.gemm_silu_mul(gu, src["ln2"][i][t], self.I, H, ws["act"][t], dt)
                 if gev is not None:
                     gev[2].record()
                 for t, dt in tiles:
@@ -898,6 +920,8 @@ class NativeTarget:
             return post[:bs].unsqueeze(0), taps
         if temperature >= 1e-5:
             logits = torch.empty(16 * len(tiles), self.V, dtype=BF16, device=self._dev)
+        elif x13:   # the greedy posterior: the head's 13-bit twin (the draft's, where DecodeSession shares the packed head)
+            head = ops.bf16x13_twin(head, self.V, H, "lm_head") or head
         for t, dt in tiles:
             ops.gemm_argmax(head, fin[t], self.V, H, 0, min(16, bs - 16 * t), ws["argmax_ws"], post, 16 * t,
                             dyn=dt, logits=None if logits is None else logits[16 * t:16 * t + 16])

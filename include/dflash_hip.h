@@ -97,8 +97,24 @@ typedef struct dfl_rows {
  * dfl_pack_weight_fp8, (gate tile p, up tile p) interleaved for dfl_pack_weight_gateup_fp8.  Any fp32 multiplier is
  * taken; a code of 0x7f / 0xff is NaN.  Everything else of a launch is the same contract in both formats, argument for
  * argument; what the e4m3 form narrows is said at each entry point.
- * DFL_EINVAL: a null descriptor, a format other than the two, DFL_W_BF16 with a scale, DFL_W_E4M3 without one. */
-enum { DFL_W_BF16 = 0, DFL_W_E4M3 = 1 };
+ * DFL_EINVAL: a null descriptor, a format other than the two, DFL_W_BF16 with a scale, DFL_W_E4M3 without one.
+ * ---- DFL_W_BF16X13: the packed bf16 weight in 13 bits per element, losslessly ----
+ * Taken by dfl_gemm_silu_mul and dfl_gemm_argmax ONLY, at K = 2048 or K = 4096; every other entry point refuses it as an
+ * unknown format.  Same results as DFL_W_BF16 on the same matrix, bit for bit: the kernels rebuild the bf16 fragments in
+ * registers from 13/16 of the bytes.  A bf16 is L = bits[7:0] and H = bits[15:8].  Per packed 16-column tile the base is
+ * hb = max(0, max(H & 0x7f) - 15); an element keeps L, its sign and a 4-bit code c: c = 0 <=> (H & 0x7f) == 0 (+-0,
+ * denormals, exponent 1: L is kept), c = 1..15 <=> (H & 0x7f) == hb + c.  All-zero bits decode to +0.
+ * wp points at ONE buffer (scale must be NULL): the quads of all packed tiles, then the meta pairs.
+ *   quad = four k-steps of one tile, 3328 bytes: L0 [64 lanes][16 B] (L of k-step 0, elements 0..7, then of k-step 1),
+ *     L1 (k-steps 2, 3), NB [64][16 B] (dword f = codes of k-step f: byte b = c[b] | c[b + 4] << 4), SG [64][4 B] (bit
+ *     8 b + r = sign of element 4 (r & 1) + b of k-step r >> 1); lane l = column l & 15, k group l >> 4 as in the packed
+ *     bf16 layout.  Tile t holds K / 128 quads at byte (t * K / 128) * 3328; tiles in dfl_pack_weight[_gateup] order.
+ *   meta = uint32 [N / 16][16 waves][2] at byte (N / 16) * (K / 128) * 3328: {hb, patch}.  Wave w of the kernel owns k-steps
+ *     w * K / 512 .. of a tile.  patch: bit 31 valid, 30:28 k-step within the wave's share, 27:22 lane, 21:19 element,
+ *     15:0 the bf16 itself: the ONE nonzero element of that (tile, wave) item below the window (stored with c = 0).  A
+ *     matrix with two such elements in one item has no BF16X13 form and stays DFL_W_BF16.
+ * The packer is dflash_amd.ops.pack_weight_bf16x13 (tensor ops over the packed bf16 weight, once at load). */
+enum { DFL_W_BF16 = 0, DFL_W_E4M3 = 1, DFL_W_BF16X13 = 2 };
 typedef struct dfl_weight {
   const void *wp;      /* packed weight: dfl_pack_weight[_gateup] (bf16) or dfl_pack_weight[_gateup]_fp8 (codes) */
   const float *scale;  /* DFL_W_E4M3: fp32 scale per packed row, in packed tile order; DFL_W_BF16: must be NULL */
@@ -149,7 +165,8 @@ int dfl_gemm_f32(const void *wp, const dfl_rows *x0, const dfl_rows *x1, int mt,
 /* act = bf16(silu(bf16(x Wg^T))) * bf16(x Wu^T) written as frag16 [I/8][16][8]
  * (tf:...modeling_qwen3.py:82 inner expression).  w_gateup from dfl_pack_weight_gateup[_fp8].
  * K/32 <= 128 (no K split: the activation needs the finished sums).  e4m3: gate and up sums are scaled separately,
- * each before its bf16 rounding. */
+ * each before its bf16 rounding.  DFL_W_BF16X13 (of the dfl_pack_weight_gateup layout, N = 2 I): K = 2048 or 4096, scale
+ * NULL; anything else is refused by name.  Same bits as DFL_W_BF16. */
 int dfl_gemm_silu_mul(const dfl_weight *w_gateup, const dfl_rows *x, int I, int K, void *act_frag, const int32_t *dyn,
                       void *stream);
 
@@ -165,7 +182,8 @@ int dfl_gemm_silu_mul(const dfl_weight *w_gateup, const dfl_rows *x, int I, int 
  * unmask at no extra pass over the logits.
  * ev_start / ev_end (each optional): hipEvent_t recorded on `stream` right before and right after the GEMM launch (the
  * argmax finish launch comes behind ev_end): bench.py times the lm_head kernel itself with them (roofline.achieved).
- * e4m3: ids, logits and margins over bf16(sum * scale). */
+ * e4m3: ids, logits and margins over bf16(sum * scale).  DFL_W_BF16X13: K = 2048 or 4096, scale NULL; same bits as
+ * DFL_W_BF16 (dfl_gemm_sample does not take it). */
 int64_t dfl_argmax_ws_bytes(void);
 int dfl_gemm_argmax(const dfl_weight *w, const dfl_rows *x, int V, int K, int row0, int nrows, const int32_t *dyn,
                     int nrows_dyn_word, void *ws, int64_t *out_ids, int out_off, void *logits, float *margin_out,
