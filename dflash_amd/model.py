@@ -20,6 +20,7 @@ import torch
 
 from . import ops
 from .config import DFlashConfig
+from .row_stack import RowStack
 from .tile_stack import TileStack, gemm_ws
 
 BF16 = torch.bfloat16
@@ -116,9 +117,11 @@ class DFlashDraftModel:
         # fp8_e4m3 only: False = run everything on the dequantised bf16 copy (the second implementation the tests compare)
         self.fp8_stream = True
         self._ws = None
+        self.rows: Optional[RowStack] = None   # the block's layer stack on the single-request kernels (made with _ws)
         self._lm_head_cache = {}
         self._lm_head_cache8 = {}
         self._tile_layers = {}   # tile_layers(): qkv_parts -> layer dicts with the e4m3 twins
+        self._row_layers = {}    # row_layers(): streams e4m3 -> layer dicts with the e4m3 / 13-bit twins
         self._rope = None
         # "head": dfl_attn_head on finished bf16 q/k/v rows (round 2); "fused": round-1 stage on fp32 partials
         self.attn_impl = "head"
@@ -207,7 +210,8 @@ class DFlashDraftModel:
         self.w8 = w8
         self.gu13 = gu13
         self._tile_layers = {}
-        self._ws = None  # row sources point at the weights: rebuild with them
+        self._row_layers = {}
+        self._ws = self.rows = None  # row sources point at the weights: rebuild with them
         return self
 
     @classmethod
@@ -240,42 +244,27 @@ class DFlashDraftModel:
             npart = max(self.ks_fc * 16 * H, self.ks_qkv * 32 * nqkv, self.ks_o * 16 * H, self.ks_down * 16 * H,
                         self.ks_kv * 16 * 2 * c.kv_dim)
             self.max_splits = 32
-            NT = 2  # block rows as up to two 16-row tiles (block sizes 17..32)
+            L = self.w["layers"]
+            # the block rows' buffers and row sources (pointers are fixed until the weights are reloaded)
+            self.rows = RowStack(H=H, q_dim=c.q_dim, kv_dim=c.kv_dim, I=I, nqkv=nqkv, n_q=c.num_attention_heads,
+                                 n_kv=c.num_key_value_heads, eps=c.rms_norm_eps, max_splits=self.max_splits, device=d,
+                                 ln1=[lw["ln1"] for lw in L], ln2=[lw["ln2"] for lw in L], norm=self.w["norm"])
             self._ws = dict(
                 th_frag=torch.zeros(16 * c.fc_in, dtype=BF16, device=d),
                 ctx_frag=torch.zeros(16 * H, dtype=BF16, device=d),
-                xn_frag=torch.zeros(NT, 16 * H, dtype=BF16, device=d),
-                attn_frag=torch.zeros(NT, 16 * c.q_dim, dtype=BF16, device=d),
-                act_frag=torch.zeros(NT, 16 * I, dtype=BF16, device=d),
-                h=torch.zeros(16 * NT, H, dtype=BF16, device=d),
+                xn_frag=torch.zeros(2, 16 * H, dtype=BF16, device=d),
                 ctxh=torch.zeros(16, H, dtype=BF16, device=d),
-                ss_emb=torch.zeros(16 * NT, dtype=torch.float32, device=d),
-                ss_h=torch.zeros(NT, H, dtype=torch.float32, device=d),       # per tile [H/16 tiles][16 rows]
                 ss_ctx=torch.zeros(H, dtype=torch.float32, device=d),
-                q_rot=torch.zeros(c.num_attention_heads, 16, 128, dtype=BF16, device=d),
                 part=torch.zeros(npart, dtype=torch.float32, device=d),
                 attn_ws=ops.attn_fused_ws(c.num_attention_heads, c.num_key_value_heads, self.max_splits, d),
                 argmax_ws=ops.argmax_ws(d),
-                ids16=torch.zeros(16, dtype=torch.int64, device=d),
-                xq=torch.zeros(16 * NT, nqkv, dtype=BF16, device=d),
                 xc=torch.zeros(16, c.num_hidden_layers * 2 * c.kv_dim, dtype=BF16, device=d),
-                head_ws=ops.attn_head_ws(c.num_attention_heads, self.max_splits, NT, d),
-                sync=torch.zeros(ops.ATTN_OPROJ_SYNC_WORDS, dtype=torch.int32, device=d),
+                sync=self.rows.sync,
             )
-            # row sources of the fused pipeline (pointers are fixed for the model's lifetime), one per block tile:
-            # the GEMM that consumes a normalised activation applies the RMSNorm itself
-            ws, eps, nt = self._ws, c.rms_norm_eps, H // 16
-            L = self.w["layers"]
-            hs = [ws["h"][16 * t:16 * t + 16] for t in range(NT)]
-            self._src = dict(
-                ctx=ops.rows_normed(ws["ctxh"], ws["ss_ctx"], nt, self.w["hidden_norm"], eps, ops.DYN_TAU),
-                ln1_first=[ops.rows_normed(hs[t], ws["ss_emb"][16 * t:], 1, L[0]["ln1"], eps, ops.DYN_BS) for t in range(NT)],
-                ln1=[[ops.rows_normed(hs[t], ws["ss_h"][t], nt, lw["ln1"], eps, ops.DYN_BS) for t in range(NT)] for lw in L],
-                ln2=[[ops.rows_normed(hs[t], ws["ss_h"][t], nt, lw["ln2"], eps, ops.DYN_BS) for t in range(NT)] for lw in L],
-                final=[ops.rows_normed(hs[t], ws["ss_h"][t], nt, self.w["norm"], eps, ops.DYN_BS) for t in range(NT)],
-                attn=[ops.rows_frag(ws["attn_frag"][t]) for t in range(NT)],
-                act=[ops.rows_frag(ws["act_frag"][t]) for t in range(NT)],
-            )
+            ws = self._ws
+            # the stack's sources, and the context rows': hidden_norm is applied by the GEMM that reads them
+            self._src = dict(self.rows.src, ctx=ops.rows_normed(ws["ctxh"], ws["ss_ctx"], H // 16, self.w["hidden_norm"],
+                                                                 c.rms_norm_eps, ops.DYN_TAU))
         return self._ws
 
     def _rope_tab(self, need: int):
@@ -330,6 +319,12 @@ class DFlashDraftModel:
         if not self.streams_fp8_tiles():
             return self.w["layers"]
         return ops.tile_layers(self.w["layers"], self.w8["layers"], qkv_parts, self._tile_layers)
+
+    def row_layers(self, bs: int) -> list:
+        """The layer dicts RowStack.run takes for a block of `bs` rows: self.w's, with the four matrices replaced by
+        their e4m3 twins when streams_fp8(bs), else gate/up by its 13-bit twin where the layer has one (gu13)."""
+        fp8 = self.streams_fp8(bs)
+        return ops.row_layers(self.w["layers"], self.w8["layers"] if fp8 else None, self.gu13, fp8, self._row_layers)
 
     # ------------------------------------------------------------------ kernels
     def _ctx_rows(self, th_rows: torch.Tensor, n: int, dyn, dyn_word: Optional[int]):
@@ -444,9 +439,8 @@ class DFlashDraftModel:
 
     def raise_if_failed(self) -> None:
         """fuse_oproj only: a dfl_attn_head_oproj launch whose o_proj workgroups gave up waiting (2 ms) leaves a flag."""
-        if self.fuse_oproj and self._ws is not None and int(self._ws["sync"][ops.ATTN_OPROJ_FAIL_WORD]) != 0:
-            self._ws["sync"].zero_()
-            raise RuntimeError("dfl_attn_head_oproj: an o_proj workgroup gave up waiting for the attention stage")
+        if self.fuse_oproj and self.rows is not None:
+            self.rows.raise_if_failed()
 
     def draft_block(self, cache: DFlashKVCache, *, th_rows: Optional[torch.Tensor], tau: int, bs: int, pos0: int,
                     block_ids: Optional[torch.Tensor] = None, embed: Optional[torch.Tensor] = None,
@@ -465,8 +459,7 @@ class DFlashDraftModel:
         loop enqueues this forward BEFORE the host knows the previous cycle's acceptance length (generate.py, run-ahead
         draft).  th_rows then holds 16 rows (the valid count is the record's tau), tau / pos0 are upper bounds,
         s_bound bounds S (it sizes the attention's key splits) and the host-side cache length is left to the caller."""
-        c, ws, w = self.config, self._workspace(), self.w
-        ww = self.w8 if self.streams_fp8(bs) else w   # the matrices this forward streams (norm weights stay in w)
+        c, ws, w, rs = self.config, self._workspace(), self.w, self.rows
         if bs < 1 or bs > 32 or tau < 0 or tau > 16:
             raise ValueError(f"bs={bs} / tau={tau}: the kernels take 1..32 block rows and 0..16 context rows")
         head = self.attn_impl == "head"
@@ -478,7 +471,7 @@ class DFlashDraftModel:
         S = int(s_bound) if ahead else cache.length
         if S + tau + bs > cache.max_rows:
             raise ValueError("draft KV cache too small")
-        H, I = c.hidden_size, c.intermediate_size
+        H = c.hidden_size
         nqkv = c.q_dim + 2 * c.kv_dim
         cos, sin = self._rope_tab(pos0 + tau + bs + 64)
         src = self._src
@@ -488,95 +481,68 @@ class DFlashDraftModel:
             ops.set_dyn2(cache.dyn, S, tau, bs, pos0)
         dyn = cache.dyn[:8]
         tiles = [(t, cache.dyn[8 * t:8 * t + 8]) for t in range((bs + 15) // 16)]
+        top = self.w8 if self.streams_fp8(bs) else w   # fc and kv_all, the matrices outside the layers: as row_layers(bs)
         if tau > 0:
             # fc straight off the tap rows; hidden_norm is applied by each layer's qkv GEMM (:177)
-            ops.gemm_resid(ww["fc"], ops.rows_plain(th_rows, ops.DYN_TAU), H, c.fc_in, ws["ctxh"], add_residual=False,
+            ops.gemm_resid(top["fc"], ops.rows_plain(th_rows, ops.DYN_TAU), H, c.fc_in, ws["ctxh"], add_residual=False,
                            ss_out=ws["ss_ctx"], dyn=dyn)
         if head and tau > 0:   # K/V Linear outputs of the context rows, all layers, one pass over 84 MB
-            ops.gemm_resid(ww["kv_all"], src["ctx"], c.num_hidden_layers * 2 * c.kv_dim, H, ws["xc"], add_residual=False,
+            ops.gemm_resid(top["kv_all"], src["ctx"], c.num_hidden_layers * 2 * c.kv_dim, H, ws["xc"], add_residual=False,
                            dyn=dyn)
-        L = w["layers"]
         if len(tiles) == 2 and self.wide_one_pass and head:
             return self._draft_block_wide(cache, ws, S, tau, bs, pos0, block_ids, embed, noise, append, cos, sin)
         if noise is not None:  # public forward(): the caller embedded the block itself
-            ws["h"][:bs].copy_(noise[:bs])
-            ws["ss_emb"][:bs].copy_(noise[:bs].float().pow(2).sum(-1))
+            rs.h[:bs].copy_(noise[:bs])
+            rs.ss_emb[:bs].copy_(noise[:bs].float().pow(2).sum(-1))
         else:
             for t, dt in tiles:
-                ops.embed_rows(embed, block_ids[16 * t:], ws["h"][16 * t:], H, ws["ss_emb"][16 * t:], dt, ops.DYN_BS)
-        hrow = [ws["h"][16 * t:16 * t + 16] for t in range(2)]
-        fuse_o = self.fuse_oproj and head and len(tiles) == 1 and c.q_dim <= 4096
-        for i, lw in enumerate(L):
-            lm = ww["layers"][i]   # the layer's matrices: lw's own, or their e4m3 twins
-            x1 = src["ln1_first"] if i == 0 else src["ln1"][i]
-            if head:
-                for t, dt in tiles:
-                    ops.gemm_resid(lm["qkv"], x1[t], nqkv, H, ws["xq"][16 * t:], add_residual=False, dyn=dt)
-                kw = dict(xq=ws["xq"], q_col=0, k_col=c.q_dim, v_col=c.q_dim + c.kv_dim,
-                          xc=ws["xc"] if tau > 0 else None, ck_col=i * 2 * c.kv_dim,
-                          cv_col=i * 2 * c.kv_dim + c.kv_dim, n_q=c.num_attention_heads,
-                          n_kv=c.num_key_value_heads, q_norm_w=lw["q_norm"], k_norm_w=lw["k_norm"],
-                          eps=c.rms_norm_eps, cos_tab=cos, sin_tab=sin, kcache=cache.k[i], vcache=cache.v[i],
-                          scale=c.head_dim ** -0.5, causal=False, S=S, tau=tau, bs=bs, pos0=pos0,
-                          ws=ws["head_ws"], max_splits=self.max_splits, dyn=dyn if ahead else None)
-                if fuse_o:
-                    ops.attn_head_oproj(**kw, attn_frag=ws["attn_frag"][0], wo=lw["o"], H=H, h_io=hrow[0],
-                                        ss_out=ws["ss_h"][0], sync=ws["sync"])
-                else:
-                    ops.attn_head(**kw, out_frag=ws["attn_frag"], q_tiles=len(tiles),
-                                  out_tile_stride=ws["attn_frag"].stride(0))
-            else:
-                ops.gemm_f32(lw["qkv"], src["ctx"], x1[0], 2, nqkv, H, self.ks_qkv, ws["part"], dyn)
-                # one launch: q/k-norm + RoPE + KV append + attention + split merge
-                ops.attn_fused(qkv=ws["part"], nsplit=self.ks_qkv, split_stride=32 * nqkv, ld=nqkv, q_col=0,
-                               k_col=c.q_dim, v_col=c.q_dim + c.kv_dim, ctx_row0=0, blk_row0=16,
-                               n_q=c.num_attention_heads, n_kv=c.num_key_value_heads, q_norm_w=lw["q_norm"],
-                               k_norm_w=lw["k_norm"], eps=c.rms_norm_eps, cos_tab=cos, sin_tab=sin, kcache=cache.k[i],
-                               vcache=cache.v[i], dyn=dyn, scale=c.head_dim ** -0.5, kv_len_max=S + tau + bs,
-                               ws=ws["attn_ws"], max_splits=self.max_splits, out_frag=ws["attn_frag"][0])
-            for t, dt in tiles:
-                if not fuse_o:
-                    ops.gemm_resid(lm["o"], src["attn"][t], H, c.q_dim, hrow[t], add_residual=True, ss_out=ws["ss_h"][t],
-                                   dyn=dt)
-            gu = lm["gu"] if ww is not w or self.gu13[i] is None else self.gu13[i]
-            for t, dt in tiles:
-                ops.gemm_silu_mul(gu, src["ln2"][i][t], I, H, ws["act_frag"][t], dt)
-            for t, dt in tiles:
-                ops.gemm_resid(lm["down"], src["act"][t], H, I, hrow[t], add_residual=True, ss_out=ws["ss_h"][t],
-                               dyn=dt)
+                ops.embed_rows(embed, block_ids[16 * t:], rs.h[16 * t:], H, rs.ss_emb[16 * t:], dt, ops.DYN_BS)
+
+        def attend(i, lw, x1):   # attn_impl="fused": context and block rows' q/k/v as fp32 K parts (mt = 2), then one
+            # launch: q/k-norm + RoPE + KV append + attention + split merge
+            ops.gemm_f32(lw["qkv"], src["ctx"], x1[0], 2, nqkv, H, self.ks_qkv, ws["part"], dyn)
+            ops.attn_fused(qkv=ws["part"], nsplit=self.ks_qkv, split_stride=32 * nqkv, ld=nqkv, q_col=0,
+                           k_col=c.q_dim, v_col=c.q_dim + c.kv_dim, ctx_row0=0, blk_row0=16,
+                           n_q=c.num_attention_heads, n_kv=c.num_key_value_heads, q_norm_w=lw["q_norm"],
+                           k_norm_w=lw["k_norm"], eps=c.rms_norm_eps, cos_tab=cos, sin_tab=sin, kcache=cache.k[i],
+                           vcache=cache.v[i], dyn=dyn, scale=c.head_dim ** -0.5, kv_len_max=S + tau + bs,
+                           ws=ws["attn_ws"], max_splits=self.max_splits, out_frag=rs.attn[0])
+
+        final = rs.run(self.row_layers(bs), tiles, bs=bs, fuse_oproj=self.fuse_oproj, attend=None if head else attend,
+                       attn=dict(cos_tab=cos, sin_tab=sin, kcache=cache.k, vcache=cache.v, causal=False, S=S, tau=tau,
+                                 pos0=pos0, dyn=dyn if ahead else None, xc=ws["xc"] if tau > 0 else None))
         if append and not ahead:
             cache.length = S + tau
-        return src["final"][:len(tiles)]
+        return final
 
     def _draft_block_wide(self, cache, ws, S, tau, bs, pos0, block_ids, embed, noise, append, cos, sin) -> WideRows:
         """The block rows of a 17..32-row block in ONE pass over the layer weights: the two 16-row tiles go through the
         ragged-batch GEMMs (tile_stack.TileStack, R = 2) and ONE attention launch per layer with two query tiles
         (model/dflash.py:166-190)."""
-        c, w, R = self.config, self.w, 2
+        c, w, rs, R = self.config, self.w, self.rows, 2
         H, I = c.hidden_size, c.intermediate_size
         nqkv = c.q_dim + 2 * c.kv_dim
         if self._wide is None:
             self._wide = TileStack(H=H, q_dim=c.q_dim, I=I, nqkv=nqkv, eps=c.rms_norm_eps, MT=2,
                                    gws=gemm_ws(H, (c.vocab_size, 2 * I, nqkv), (H, I, c.q_dim), self.device),
-                                   h=ws["h"].view(2, 16, H), attn=ws["attn_frag"], act=ws["act_frag"],
-                                   xq=ws["xq"].view(2, 16, nqkv))
+                                   h=rs.h.view(2, 16, H), attn=rs.attn, act=rs.act, xq=rs.xq.view(2, 16, nqkv))
             self._wide_ids = torch.zeros(2, 16, dtype=torch.int64, device=self.device)
         st = self._wide
         dyn2 = cache.dyn[:16].view(2, 8)
         if noise is not None:   # public forward(): the caller embedded the block itself
-            ws["h"][:bs].copy_(noise[:bs])
+            rs.h[:bs].copy_(noise[:bs])
         else:
             self._wide_ids.view(-1)[:bs].copy_(block_ids[:bs])
-            ops.embed_rows_batch(embed, self._wide_ids, R, st.h, H, ws["ss_emb"].view(2, 16), dyn2, ops.DYN_BS)
+            ops.embed_rows_batch(embed, self._wide_ids, R, st.h, H, rs.ss_emb.view(2, 16), dyn2, ops.DYN_BS)
 
         def attend(i, lw):
-            ops.attn_head(xq=ws["xq"], q_col=0, k_col=c.q_dim, v_col=c.q_dim + c.kv_dim,
+            ops.attn_head(xq=rs.xq, q_col=0, k_col=c.q_dim, v_col=c.q_dim + c.kv_dim,
                           xc=ws["xc"] if tau > 0 else None, ck_col=i * 2 * c.kv_dim, cv_col=i * 2 * c.kv_dim + c.kv_dim,
                           n_q=c.num_attention_heads, n_kv=c.num_key_value_heads, q_norm_w=lw["q_norm"],
                           k_norm_w=lw["k_norm"], eps=c.rms_norm_eps, cos_tab=cos, sin_tab=sin, kcache=cache.k[i],
                           vcache=cache.v[i], scale=c.head_dim ** -0.5, causal=False, S=S, tau=tau, bs=bs, pos0=pos0,
-                          ws=ws["head_ws"], max_splits=self.max_splits, out_frag=ws["attn_frag"], q_tiles=2,
-                          out_tile_stride=ws["attn_frag"].stride(0))
+                          ws=rs.head_ws, max_splits=self.max_splits, out_frag=rs.attn, q_tiles=2,
+                          out_tile_stride=rs.attn.stride(0))
 
         st.run(self.tile_layers(qkv_parts=False), R, dyn2, attend, qkv="rows")
         st.finish(w["norm"])   # last down_proj's sums -> h (the rows forward() returns after its own norm), final norm -> frag16
@@ -677,7 +643,7 @@ class DFlashDraftModel:
         out = []
         for t in range(len(frag)):
             ops.norm_pack(norm_w=self.w["norm"], frag=ws["xn_frag"][t], H=H, eps=c.rms_norm_eps,
-                          resid_in=ws["h"][16 * t:16 * t + 16], dyn=cache.dyn[8 * t:8 * t + 8], dyn_word=ops.DYN_BS)
+                          resid_in=self.rows.h_tiles[t], dyn=cache.dyn[8 * t:8 * t + 8], dyn_word=ops.DYN_BS)
             out.append(ws["xn_frag"][t].view(H // 8, 16, 8).permute(1, 0, 2).reshape(16, H))
         return torch.cat(out)[:q_len].unsqueeze(0).clone()
 

@@ -189,6 +189,18 @@ def tile_layers(layers: list, layers8: list, qkv_parts: bool, cache: dict) -> li
     return cache[qkv_parts]
 
 
+def row_layers(layers: list, layers8, gu13: list, fp8: bool, cache: dict) -> list:
+    """The layer dicts RowStack.run takes — the one format choice of the single-request path.  fp8: `layers` with qkv / o /
+    gu / down replaced by their e4m3 twins in layers8; else with gu replaced by its 13-bit twin where gu13[i] is not None
+    (a layer without one, an MoE layer among them, passes through as it is).  Built once per form and kept in `cache`."""
+    if fp8 not in cache:
+        if fp8:
+            cache[fp8] = [{**lw, **{k: l8[k] for k in ("qkv", "o", "gu", "down")}} for lw, l8 in zip(layers, layers8)]
+        else:
+            cache[fp8] = [lw if g is None else {**lw, "gu": g} for lw, g in zip(layers, gu13)]
+    return cache[fp8]
+
+
 # ---- bf16x13: the packed bf16 weight in 13 bits per element, losslessly (DESIGN.md section 11) ----
 X13_QUAD_BYTES = 3328   # four k-steps of one 16-column tile: L0, L1, NB (1024 B each) and SG (256 B); csrc/gemm_rows.h
 STREAM_FORMATS = ("auto", "bf16")

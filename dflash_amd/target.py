@@ -25,6 +25,7 @@ import torch
 
 from . import ops
 from .model import WEIGHT_FORMATS, _rope_tables
+from .row_stack import RowStack
 from .tile_stack import TileStack, gemm_ws
 from .utils import sample
 
@@ -146,6 +147,7 @@ class NativeTarget:
         self.layers8 = [] if fp8 else None   # per layer: ops.Fp8Weight twins of qkv / o / gu / down in self.layers
         self.lm_wp8 = None                   # the e4m3 lm_head (ops.Fp8Weight)
         self._tile_layers = {}               # tile_layers(): qkv_parts -> layer dicts with the e4m3 twins
+        self._row_layers = {}                # row_layers(): streams e4m3 -> layer dicts with the e4m3 / 13-bit twins
         self.hf = hf_model
         self.model = hf_model.model
         self.lm_head = hf_model.lm_head
@@ -281,12 +283,12 @@ class NativeTarget:
         npart = max(self.ks_qkv * 16 * self.nqkv, self.ks_o * 16 * self.H, self.ks_down * 16 * self.H)
         z = lambda *s, dt=BF16: torch.zeros(*s, dtype=dt, device=dev)  # noqa: E731
         NT = 2  # block rows as up to two 16-row tiles (blocks of 17..32 rows: one GEMM launch per tile)
-        self.ws = dict(attn=z(NT, 16 * self.q_dim), act=z(NT, 16 * self.I), h=z(16 * NT, self.H),
-                       ss_emb=z(16 * NT, dt=torch.float32), ss_h=z(NT, self.H, dt=torch.float32),
-                       q=z(self.n_q, 16, 128), part=z(npart, dt=torch.float32),
-                       attn_ws=ops.attn_fused_ws(self.n_q, self.n_kv, max_splits, dev), argmax_ws=ops.argmax_ws(dev),
-                       xq=z(16 * NT, self.nqkv), head_ws=ops.attn_head_ws(self.n_q, max_splits, NT, dev),
-                       sync=torch.zeros(ops.ATTN_OPROJ_SYNC_WORDS, dtype=torch.int32, device=dev),
+        # the block rows' buffers and row sources, and the verify's layer sequence on the single-request kernels
+        self.rows = RowStack(H=self.H, q_dim=self.q_dim, kv_dim=self.kv_dim, I=self.I, nqkv=self.nqkv, n_q=self.n_q,
+                             n_kv=self.n_kv, eps=self.eps, max_splits=max_splits, device=dev,
+                             ln1=[lw["ln1"] for lw in self.layers], ln2=[lw["ln2"] for lw in self.layers], norm=self.norm)
+        self.ws = dict(part=z(npart, dt=torch.float32), attn_ws=ops.attn_fused_ws(self.n_q, self.n_kv, max_splits, dev),
+                       argmax_ws=ops.argmax_ws(dev), sync=self.rows.sync,
                        post=torch.zeros(16 * NT, dtype=torch.int64, device=dev))
         self.is_moe = any("gu_e" in lw for lw in self.layers)
         if self.is_moe:
@@ -301,20 +303,9 @@ class NativeTarget:
                            rticket=torch.zeros(1, dtype=torch.int32, device=dev))
             # norm + gate Linear + routing as ONE launch (dfl_moe_router); the three launches otherwise
             self.moe_router_fused = self.H <= 4096 and self.E % 2 == 0
-        ws, nt = self.ws, self.H // 16
-        hs = [ws["h"][16 * t:16 * t + 16] for t in range(NT)]
-        # row sources, one per tile: the consuming GEMM applies the RMSNorm itself (no norm launches)
-        self.src = dict(
-            ln1=[[ops.rows_normed(hs[t], ws["ss_emb"][16 * t:] if i == 0 else ws["ss_h"][t], 1 if i == 0 else nt,
-                                  lw["ln1"], self.eps, ops.DYN_BS) for t in range(NT)]
-                 for i, lw in enumerate(self.layers)],
-            ln2=[[ops.rows_normed(hs[t], ws["ss_h"][t], nt, lw["ln2"], self.eps, ops.DYN_BS) for t in range(NT)]
-                 for lw in self.layers],
-            final=[ops.rows_normed(hs[t], ws["ss_h"][t], nt, self.norm, self.eps, ops.DYN_BS) for t in range(NT)],
-            attn=[ops.rows_frag(ws["attn"][t]) for t in range(NT)], act=[ops.rows_frag(ws["act"][t]) for t in range(NT)])
+        self.src = {}
         if self.is_moe:   # MoE layers hand their successor ready-normalised rows (the residual add + norm launch after the experts)
-            self.src["xn"] = [ops.rows_frag(ws["xn"][t]) for t in range(NT)]
-            self.src["xn1"] = [ops.rows_frag(ws["xn1"][t]) for t in range(NT)]
+            self.src = {k: [ops.rows_frag(self.ws[k][t]) for t in range(NT)] for k in ("xn", "xn1")}
         q_dim, kv_dim = self.n_q * 128, self.n_kv * 128
         self._pf = self._pf_moe = None
         dense_ok = all("gu_e" in lw for lw in self.layers) or self.I % 64 == 0   # (a dense MLP layer needs I % 64)
@@ -423,6 +414,11 @@ class NativeTarget:
         if not self.streams_fp8_tiles():
             return self.layers
         return ops.tile_layers(self.layers, self.layers8, qkv_parts, self._tile_layers)
+
+    def row_layers(self, bs: int) -> list:
+        """The layer dicts RowStack.run takes for a block of `bs` rows: self.layers, with the four matrices replaced by
+        their e4m3 twins when streams_fp8(bs), else a dense layer's gate/up by its 13-bit twin where it has one (gu13)."""
+        return ops.row_layers(self.layers, self.layers8, self.gu13, self.streams_fp8(bs), self._row_layers)
 
     def fp8_tensors(self) -> tuple:
         """Every e4m3 code tensor and scale vector of an fp8 target and of fp8 experts (empty for bf16): what a captured
@@ -576,10 +572,11 @@ class NativeTarget:
         cache.length = P
         return out
 
-    def _moe_mlp(self, i: int, lw: dict, tiles, hrow, taps, sl) -> None:
+    def _moe_mlp(self, i: int, lw: dict, tiles, hrow, taps, sl) -> list:
         """Qwen3MoeSparseMoeBlock of layer i on the block rows (tf:models/qwen3_moe/modeling_qwen3_moe.py): norm, router
         GEMM, softmax/top-k/renormalise, gate/up of every active expert in one launch, the routing-weighted down
-        projections as fp32 K-part sums, then residual add + tap + the NEXT stage's RMSNorm in one row-wise launch."""
+        projections as fp32 K-part sums, then residual add + tap + the NEXT stage's RMSNorm in one row-wise launch.
+        Returns the row sources of those normalised rows (RowStack.run's `moe`)."""
         ws, H, E = self.ws, self.H, self.E
         nxt = self.layers[i + 1]["ln1"] if i + 1 < self.L else self.norm
         gu_e, down_e = self.expert_weights(lw)   # (fp8 experts: the codes where the launch has a W8 form)
@@ -616,6 +613,7 @@ class NativeTarget:
             ops.norm_pack(norm_w=nxt, frag=ws["xn1"][t], H=H, eps=self.eps, part=ws["moe_part"], nsplit=self.moe_nsplit,
                           part_split=16 * H, ldp=H, resid_in=hrow[t], h_out=hrow[t], h_out2=tap,
                           ld2=taps.stride(0) if tap is not None else 0, dyn=dt, dyn_word=ops.DYN_BS)
+        return self.src["xn1"]
 
     def moe_mlp_tiles(self, lw: dict, R: int, MT: int, dyn: torch.Tensor, xn: torch.Tensor, part: torch.Tensor) -> int:
         """Qwen3MoeSparseMoeBlock (tf:models/qwen3_moe/modeling_qwen3_moe.py) of one layer for R 16-row tiles that went
@@ -699,25 +697,25 @@ class NativeTarget:
         """Blocks of 17..32 rows in ONE pass over the weights: the two 16-row tiles go through the ragged-batch
         GEMMs (tile_stack.TileStack, R = 2) as if they were two requests, and through ONE attention launch per layer with
         two query tiles on the request's single cache.  Same lines as verify(): model/dflash.py:249-257."""
-        ws, H, R = self.ws, self.H, 2
+        ws, rs, H, R = self.ws, self.rows, self.H, 2
         if self._wide is None:
             self._wide = TileStack(H=H, q_dim=self.q_dim, I=self.I, nqkv=self.nqkv, eps=self.eps, MT=2,
                                    gws=gemm_ws(H, (self.V, 2 * self.I, self.nqkv), (H, self.I, self.q_dim), self._dev),
-                                   h=ws["h"].view(2, 16, H), attn=ws["attn"], act=ws["act"],
-                                   xq=ws["xq"].view(2, 16, self.nqkv), moe_nsplit=self.moe_nsplit if self.is_moe else 0)
+                                   h=rs.h.view(2, 16, H), attn=rs.attn, act=rs.act,
+                                   xq=rs.xq.view(2, 16, self.nqkv), moe_nsplit=self.moe_nsplit if self.is_moe else 0)
             self._wide_ids = torch.zeros(2, 16, dtype=torch.int64, device=self._dev)
         st = self._wide
         s, gws = st.src, st.gws
         dyn2 = cache.dyn[:16].view(2, 8)
         self._wide_ids.view(-1)[:bs].copy_(block_ids[:bs])
-        ops.embed_rows_batch(self.embed, self._wide_ids, R, st.h, H, ws["ss_emb"].view(2, 16), dyn2, ops.DYN_BS)
+        ops.embed_rows_batch(self.embed, self._wide_ids, R, st.h, H, rs.ss_emb.view(2, 16), dyn2, ops.DYN_BS)
 
         def attend(i, lw):
-            ops.attn_head(xq=ws["xq"], q_col=0, k_col=self.q_dim, v_col=self.q_dim + self.kv_dim, n_q=self.n_q,
+            ops.attn_head(xq=rs.xq, q_col=0, k_col=self.q_dim, v_col=self.q_dim + self.kv_dim, n_q=self.n_q,
                           n_kv=self.n_kv, q_norm_w=lw["q_norm"], k_norm_w=lw["k_norm"], eps=self.eps, cos_tab=cos,
                           sin_tab=sin, kcache=cache.k[i], vcache=cache.v[i], scale=128 ** -0.5, causal=True, S=start,
-                          tau=0, bs=bs, pos0=start, ws=ws["head_ws"], max_splits=self.max_splits, out_frag=ws["attn"],
-                          q_tiles=2, out_tile_stride=ws["attn"].stride(0))
+                          tau=0, bs=bs, pos0=start, ws=rs.head_ws, max_splits=self.max_splits, out_frag=rs.attn,
+                          q_tiles=2, out_tile_stride=rs.attn.stride(0))
 
         st.run(self.tile_layers(qkv_parts=False), R, dyn2, attend, qkv="rows",
                taps=None if taps is None else taps.view(2, 16, -1), tap_layers=tap_layers, moe=self.moe_mlp_tiles)
@@ -760,9 +758,8 @@ class NativeTarget:
 
     def raise_if_failed(self) -> None:
         """fuse_oproj only: a dfl_attn_head_oproj launch whose o_proj workgroups gave up waiting (2 ms) leaves a flag."""
-        if self.fuse_oproj and int(self.ws["sync"][ops.ATTN_OPROJ_FAIL_WORD]) != 0:
-            self.ws["sync"].zero_()
-            raise RuntimeError("dfl_attn_head_oproj: an o_proj workgroup gave up waiting for the attention stage")
+        if self.fuse_oproj:
+            self.rows.raise_if_failed()
 
     @torch.inference_mode()
     def verify(self, block_ids: torch.Tensor, start: int, cache: TargetKVCache, *, tap_layers: Sequence[int] = (),
@@ -829,75 +826,32 @@ class NativeTarget:
                 if key not in self._taps:
                     self._taps[key] = torch.zeros(32, key * H, dtype=BF16, device=self._dev)
                 taps = self._taps[key]
-        Ls, src = self.layers, self.src
         w8 = self.streams_fp8(bs)
-        Lm = self.layers8 if w8 else Ls   # the matrices this verify streams: the layers' own, or their e4m3 twins
         head = self.lm_wp8 if w8 else self.lm_wp
-        x13 = self.x13 and not w8
         if len(tiles) == 2 and self.wide_one_pass and self.attn_impl == "head":
             return self._verify_wide(block_ids, start, cache, bs, tap_layers, taps, logits_out, temperature, cos, sin, seed,
                                      flt)
-        hrow = [ws["h"][16 * t:16 * t + 16] for t in range(2)]
+        rs = self.rows
         for t, dt in tiles:
-            ops.embed_rows(self.embed, block_ids[16 * t:], hrow[t], H, ws["ss_emb"][16 * t:], dt, ops.DYN_BS)
-        fuse_o = self.fuse_oproj and self.attn_impl == "head" and len(tiles) == 1 and self.q_dim <= 4096
-        prev_moe = False   # an MoE layer leaves its successor's input already normalised (frag16 in ws["xn1"])
-        for i, lw in enumerate(Ls):
-            lm = Lm[i]
-            x1 = src["xn1"] if prev_moe else src["ln1"][i]
-            if self.attn_impl == "head":
-                # q/k/v as finished bf16 Linear outputs (no K split: 192 workgroups x 2 column tiles), then
-                # one launch: q/k-norm + RoPE + append + causal attention + split merge
-                for t, dt in tiles:
-                    ops.gemm_resid(lm["qkv"], x1[t], self.nqkv, H, ws["xq"][16 * t:], add_residual=False, dyn=dt)
-                kw = dict(xq=ws["xq"], q_col=0, k_col=self.q_dim, v_col=self.q_dim + self.kv_dim, n_q=self.n_q,
-                          n_kv=self.n_kv, q_norm_w=lw["q_norm"], k_norm_w=lw["k_norm"], eps=self.eps, cos_tab=cos,
-                          sin_tab=sin, kcache=cache.k[i], vcache=cache.v[i], scale=128 ** -0.5, causal=True,
-                          S=start, tau=0, bs=bs, pos0=start, ws=ws["head_ws"], max_splits=self.max_splits,
-                          dyn=dyn if dyn_lengths else None)
-                if fuse_o:
-                    ops.attn_head_oproj(**kw, attn_frag=ws["attn"][0], wo=lw["o"], H=H, h_io=hrow[0],
-                                        ss_out=ws["ss_h"][0], sync=ws["sync"])
-                else:
-                    ops.attn_head(**kw, out_frag=ws["attn"], q_tiles=len(tiles), out_tile_stride=ws["attn"].stride(0))
-            else:
-                ops.gemm_f32(lw["qkv"], x1[0], None, 1, self.nqkv, H, self.ks_qkv, ws["part"], dyn)
-                ops.attn_fused(qkv=ws["part"], nsplit=self.ks_qkv, split_stride=16 * self.nqkv, ld=self.nqkv, q_col=0,
-                               k_col=self.q_dim, v_col=self.q_dim + self.kv_dim, ctx_row0=0, blk_row0=0, n_q=self.n_q,
-                               n_kv=self.n_kv, q_norm_w=lw["q_norm"], k_norm_w=lw["k_norm"], eps=self.eps,
-                               cos_tab=cos, sin_tab=sin, kcache=cache.k[i], vcache=cache.v[i], dyn=dyn,
-                               scale=128 ** -0.5, kv_len_max=start + bs, ws=ws["attn_ws"],
-                               max_splits=self.max_splits, out_frag=ws["attn"][0], causal=True)
-            for t, dt in tiles:
-                if not fuse_o:
-                    # (an MoE block normalises its rows itself — dfl_moe_router: no partial sums of squares wanted, and
-                    # without them a narrow o_proj may run in half tiles on twice the workgroups)
-                    ops.gemm_resid(lm["o"], src["attn"][t], H, self.q_dim, hrow[t], add_residual=True,
-                                   ss_out=None if "gu_e" in lw else ws["ss_h"][t], dyn=dt)
-            # every slot j with tap_layers[j] == i: build_target_layer_ids repeats layers for shallow
-            # targets and the reference concatenates the same state twice (model/utils.py:16-25)
-            sl = [j for j, l in enumerate(tap_layers) if l == i]
-            prev_moe = "gu_e" in lw
-            if prev_moe:
-                self._moe_mlp(i, lw, tiles, hrow, taps, sl)
-            else:
-                gev = self.gu_events if (self.gu_events is not None and self.gu_events[0] == i) else None
-                if gev is not None:       # bench.py: this layer's gate/up launch between two events on the launch stream
-                    gev[1].record()
-                gu = self.gu13[i] if x13 and self.gu13[i] is not None else lm["gu"]
-                for t, dt in tiles:
-                    ops.gemm_silu_mul(gu, src["ln2"][i][t], self.I, H, ws["act"][t], dt)
-                if gev is not None:
-                    gev[2].record()
-                for t, dt in tiles:
-                    tap = taps[16 * t:16 * t + 16, sl[0] * H:(sl[0] + 1) * H] if sl else None
-                    ops.gemm_resid(lm["down"], src["act"][t], H, self.I, hrow[t], add_residual=True,
-                                   ss_out=ws["ss_h"][t], tap=tap, dyn=dt)
-            for j in sl[1:]:
-                taps[:, j * H:(j + 1) * H].copy_(taps[:, sl[0] * H:(sl[0] + 1) * H])
+            ops.embed_rows(self.embed, block_ids[16 * t:], rs.h_tiles[t], H, rs.ss_emb[16 * t:], dt, ops.DYN_BS)
+
+        def attend(i, lw, x1):   # attn_impl="fused": the block rows' q/k/v as fp32 K parts (mt = 1), then the round-1 stage
+            ops.gemm_f32(lw["qkv"], x1[0], None, 1, self.nqkv, H, self.ks_qkv, ws["part"], dyn)
+            ops.attn_fused(qkv=ws["part"], nsplit=self.ks_qkv, split_stride=16 * self.nqkv, ld=self.nqkv, q_col=0,
+                           k_col=self.q_dim, v_col=self.q_dim + self.kv_dim, ctx_row0=0, blk_row0=0, n_q=self.n_q,
+                           n_kv=self.n_kv, q_norm_w=lw["q_norm"], k_norm_w=lw["k_norm"], eps=self.eps,
+                           cos_tab=cos, sin_tab=sin, kcache=cache.k[i], vcache=cache.v[i], dyn=dyn,
+                           scale=128 ** -0.5, kv_len_max=start + bs, ws=ws["attn_ws"],
+                           max_splits=self.max_splits, out_frag=rs.attn[0], causal=True)
+
+        # fin: the final-normed rows' sources (after an MoE layer the rows are final-normed already)
+        fin = rs.run(self.row_layers(bs), tiles, bs=bs, fuse_oproj=self.fuse_oproj,
+                     attend=None if self.attn_impl == "head" else attend,
+                     attn=dict(cos_tab=cos, sin_tab=sin, kcache=cache.k, vcache=cache.v, causal=True, S=start, tau=0,
+                               pos0=start, dyn=dyn if dyn_lengths else None),
+                     taps=taps, tap_layers=tap_layers, moe=self._moe_mlp, gu_events=self.gu_events)
         post = ws["post"]
         logits = logits_out
-        fin = src["xn1"] if prev_moe else src["final"]   # after an MoE layer the rows are final-normed already
         if flt is not None:
             if logits is None:
                 logits = self._nucleus_logits()
@@ -920,7 +874,7 @@ class NativeTarget:
             return post[:bs].unsqueeze(0), taps
         if temperature >= 1e-5:
             logits = torch.empty(16 * len(tiles), self.V, dtype=BF16, device=self._dev)
-        elif x13:   # the greedy posterior: the head's 13-bit twin (the draft's, where DecodeSession shares the packed head)
+        elif self.x13 and not w8:   # the greedy posterior: the head's 13-bit twin (the draft's, where DecodeSession shares the packed head)
             head = ops.bf16x13_twin(head, self.V, H, "lm_head") or head
         for t, dt in tiles:
             ops.gemm_argmax(head, fin[t], self.V, H, 0, min(16, bs - 16 * t), ws["argmax_ws"], post, 16 * t,

@@ -1,4 +1,6 @@
-"""`TileStack` — a decoder stack over 16-row tiles on the ragged-batch kernels, the one place the layer sequence lives.
+"""`TileStack` — a decoder stack over 16-row tiles on the ragged-batch kernels, the one place THIS kernel family's layer
+sequence lives.  There are two stacks, one per family: a single request's block on the skinny kernels (one tile, or two
+in two passes) runs through row_stack.RowStack, whose partial-sum and norm protocol is another.
 
 Every caller that pushes several 16-row tiles through a stack in ONE pass over the weights runs it through here: the
 requests of a ragged batch (draft and target side, batch.py), the two tiles of a 17..32-row block (model.py,
