@@ -1,5 +1,6 @@
 """The lossless 13-bit bf16 weight stream (DFL_W_BF16X13) without a GPU: the packer against a
-NumPy decoder written from the format's description, the entry points' refusals, and the auto -> bf16 fall-back."""
+NumPy decoder written from the format's description, the entry points' refusals, the auto -> bf16 fall-back, and the
+packer's account of every matrix the GPU tests stream (tests/bf16x13_cases.py)."""
 import ctypes as C
 
 import numpy as np
@@ -112,6 +113,92 @@ def test_one_below_window_element_is_patched_exactly():
         w[3, 0] = from_bits(low)                                       # tile 0, wave 0, first k-step, lane 3, element 0
         rep = roundtrip(to_packed(w), 32, K)
         assert rep["patched"] == 2 and rep["refused"] == 0
+
+
+def _generated_cases():
+    import bf16x13_cases as X
+    return ([("argmax", V, K, ext) for V, K in X.ARGMAX_SHAPES for ext in (False, True)]
+            + [("silu", I, K, False) for I, K in X.SILU_SHAPES])
+
+
+@pytest.mark.parametrize("kind,n,K,extreme", _generated_cases())
+def test_generated_cases_are_in_format_by_the_packers_account(kind, n, K, extreme):
+    """What keeps the GPU tests over tests/bf16x13_cases.py honest: every matrix they stream is in format by the PACKER's
+    account — nothing refused, exactly the planted patches, each patch word naming the planted (k-step, lane, element,
+    bits) — it decodes back bit for bit, its tiles have many bases, the items a workgroup walks one after the other have
+    different ones, and the planted patches cover the classes the kernel's decode distinguishes."""
+    import bf16x13_cases as X
+    from dflash_amd import ops
+    case = X.argmax_case(n, K, extreme) if kind == "argmax" else X.silu_case(n, K)
+    N, nfr = case.N, K // 512
+    wp = to_packed(case.w)
+    w13, rep = ops.pack_weight_bf16x13(wp, N, K)
+    assert w13 is not None and rep["refused"] == 0, rep
+    assert rep["patched"] == len(case.patches) == 16 * len(case.patch_tiles), rep
+    data = w13.data.numpy()
+    assert np.array_equal(decode(data, N, K).reshape(-1), bits(wp)), "the 13-bit form does not reproduce the weight"
+    meta = data[N // 16 * (K // 128) * QUAD:].view(np.uint32).reshape(N // 16, 16, 2)
+    hb = meta[:, 0, 0].astype(int)
+    assert len(set(hb.tolist())) >= 5 + 2 * extreme, sorted(set(hb.tolist()))
+    assert hb[X.ZERO_TILE] == 0 and (not extreme or (hb[X.TOP_TILE] == 112 and hb[X.DEEP_TILE] == 0))
+    wb = bits(case.w)
+    for r, c, v in case.edges:
+        assert wb[r, c] == v
+    # the patch words against the table
+    assert int((meta[:, :, 1] >> 31).sum()) == len(case.patches)
+    for p in case.patches:
+        pw = int(meta[p.tile, p.wave, 1])
+        assert (pw >> 31, (pw >> 28) & 7, (pw >> 22) & 63, (pw >> 19) & 7, pw & 0xffff) == (1, p.kstep, p.lane, p.element, p.bits)
+        assert wb[p.row, p.col] == p.bits and (p.row, p.col) == (16 * p.tile + (p.lane & 15),
+                                                                 (p.wave * nfr + p.kstep) * 32 + (p.lane >> 4) * 8 + p.element)
+        assert 1 <= (p.bits >> 8) & 0x7f <= hb[p.tile] and p.bits & 0x7fff, "not a nonzero element below the window"
+    # the classes
+    P = case.patches
+    assert {p.kstep for p in P} == set(range(nfr)) and {p.element for p in P} == set(range(8))
+    assert {0, 63} <= {p.lane for p in P} and {(p.lane >> 3) & 1 for p in P} == {0, 1}
+    assert {0, 15} <= {p.wave for p in P} and len({p.wave for p in P} - {0, 15}) >= 2
+    assert {p.bits >> 15 for p in P} == {0, 1}
+    plan = X.plan_argmax(n) if kind == "argmax" else X.plan_silu(n)
+    ptiles = set(case.patch_tiles)
+    longest = max(len(items) for items in plan)
+    for pos in range(longest):     # a patched tile at every position of a workgroup's sequence: first, second, third ...
+        assert any(len(items) > pos and items[pos][0] in ptiles for items in plan), pos
+    for items in plan:
+        if all(t in ptiles for t, _ in items):      # the workgroups the patches sit in: a base per item
+            assert all(hb[a[0]] != hb[b[0]] for a, b in zip(items, items[1:])), items
+    differ = sum(all(hb[a[0]] != hb[b[0]] for a, b in zip(items, items[1:])) for items in plan)
+    assert differ >= 0.8 * len(plan)
+    halved = {t for items in plan for t, half in items if half >= 0}
+    for t in halved & ptiles:                        # a halved tile: patches in both halves
+        assert {(p.lane >> 3) & 1 for p in P if p.tile == t} == {0, 1}
+    if kind == "argmax" and n != 8192:
+        assert halved & ptiles
+    if kind == "silu":
+        assert {p.tile & 1 for p in P} == {0, 1}     # gate tiles and up tiles
+        assert hb[0] != hb[1]
+
+
+def test_model_helpers_of_the_generated_cases():
+    """What the mixed-model session test does to a model's gate/up: tile shifts leave the matrix in format with a base
+    per tile (and are undone exactly by the down columns' powers); plant_refusal makes the packer refuse it."""
+    import bf16x13_cases as X
+    from dflash_amd import ops
+    K = 2048
+    gate, up, down = rand_w(112, K, 9), rand_w(112, K, 10), rand_w(64, 112, 11)
+    g0, u0, d0 = gate.clone(), up.clone(), down.clone()
+    X.apply_tile_shifts(gate, up, down)
+    s = torch.tensor(X.SHIFTS, dtype=torch.float64)
+    t = torch.arange(112) // 16 * 2
+    assert torch.equal(gate.double(), g0.double() * torch.exp2(s[t % 7]).view(-1, 1))
+    assert torch.equal(up.double(), u0.double() * torch.exp2(s[(t + 1) % 7]).view(-1, 1))
+    assert torch.equal(down.double(), d0.double() * torch.exp2(-s[t % 7] - s[(t + 1) % 7]).view(1, -1))
+    w13, rep = ops.pack_weight_bf16x13(to_packed_gateup(gate, up), 224, K)
+    assert w13 is not None and rep == {"items": 224, "patched": 0, "refused": 0}
+    meta = w13.data.numpy()[224 // 16 * (K // 128) * QUAD:].view(np.uint32).reshape(14, 16, 2)
+    assert len(set(meta[:, 0, 0].tolist())) >= 5 and all(meta[t, 0, 0] != meta[t + 1, 0, 0] for t in range(13))
+    X.plant_refusal(gate, 4, 3)
+    w13, rep = ops.pack_weight_bf16x13(to_packed_gateup(gate, up), 224, K)
+    assert w13 is None and rep == {"items": 224, "patched": 0, "refused": 1}
 
 
 def test_two_below_window_elements_in_one_item_refuse_the_matrix():
