@@ -118,6 +118,19 @@ __device__ __forceinline__ void load_quads_w13(bf16x8 (&wr)[6], uint32_t (&sg)[2
   }
 }
 
+// ONE quad (nq = 0 or 1) at `first` through a descriptor of its own, for the kernels whose item is one quad per tile
+// (k_moe_gate_up at K = 2048: a gate and an up quad): the 4-byte SG request, then NB, L0, L1 as above — a tile's first
+// decode waits for three requests, and nothing of a second quad is ever asked for.  wr: {L0, L1, NB}.
+template <int AUX = 2>
+__device__ __forceinline__ void load_quads_w13(bf16x8 (&wr)[3], uint32_t &sg, const char *first, int nq, int l) {
+  const __amdgpu_buffer_rsrc_t r =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(first), 0, (nq < 0 ? 0 : nq) * W13_QUAD_BYTES, 0x00020000);
+  sg = __builtin_amdgcn_raw_buffer_load_b32(r, l * 4 + 3072, 0, AUX);
+#pragma unroll
+  for (int p = 2; p < 5; ++p)  // NB, L0, L1
+    wr[p % 3] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(r, l * 16 + (p % 3) * 1024, 0, AUX));
+}
+
 // {hb, patch} of (tile t, wave w): wave-uniform address, constant address space -> one scalar load, no VMEM operation
 __device__ __forceinline__ u32x2 w13_meta(const u32x2 *meta, int t, int w) {
   typedef const __attribute__((address_space(4))) u32x2 *cptr;
@@ -131,16 +144,17 @@ __device__ __forceinline__ uint32_t w13_high(uint32_t c, uint32_t sgw, int r, u1
   return __builtin_bit_cast(uint32_t, e) | ((sgw << (7 - r)) & 0x80808080u);
 }
 
-// the fragment of k-step f (0..7) of an item, decoded right in front of its MFMA
-__device__ __forceinline__ bf16x8 w13_frag(const bf16x8 (&wr)[6], const W13Extra &ex, int f, int l) {
-  const int q = f >> 2, ff = f & 3;
-  const u32x4 lw = __builtin_bit_cast(u32x4, wr[3 * q + (ff >> 1)]);
+// the fragment of k-step f (0..7) of the wave's share, decoded right in front of its MFMA: k-step f & 3 of the quad whose
+// L0 or L1 word (the one that holds it) is lq, whose NB word is nq and whose SG word is sgw; meta = the item's {hb, patch}
+__device__ __forceinline__ bf16x8 w13_frag(bf16x8 lq, bf16x8 nq, uint32_t sgw, u32x2 meta, int f, int l) {
+  const int ff = f & 3;
+  const u32x4 lw = __builtin_bit_cast(u32x4, lq);
   const uint32_t la = (ff & 1) ? lw[2] : lw[0], lb = (ff & 1) ? lw[3] : lw[1];
-  const uint32_t n = __builtin_bit_cast(u32x4, wr[3 * q + 2])[ff];
-  const uint32_t hb = __builtin_amdgcn_readfirstlane(ex.meta[0]) & 0x7f, pw = __builtin_amdgcn_readfirstlane(ex.meta[1]);
+  const uint32_t n = __builtin_bit_cast(u32x4, nq)[ff];
+  const uint32_t hb = __builtin_amdgcn_readfirstlane(meta[0]) & 0x7f, pw = __builtin_amdgcn_readfirstlane(meta[1]);
   const u16x2 hb2 = {(unsigned short)hb, (unsigned short)hb};
-  const uint32_t ha = w13_high(n & 0x0f0f0f0fu, ex.sg[q], 2 * ff, hb2);
-  const uint32_t hh = w13_high((n >> 4) & 0x0f0f0f0fu, ex.sg[q], 2 * ff + 1, hb2);
+  const uint32_t ha = w13_high(n & 0x0f0f0f0fu, sgw, 2 * ff, hb2);
+  const uint32_t hh = w13_high((n >> 4) & 0x0f0f0f0fu, sgw, 2 * ff + 1, hb2);
   u32x4 o;
   o[0] = __builtin_amdgcn_perm(ha, la, 0x05010400u);  // L0 H0 L1 H1
   o[1] = __builtin_amdgcn_perm(ha, la, 0x07030602u);  // L2 H2 L3 H3
@@ -156,6 +170,15 @@ __device__ __forceinline__ bf16x8 w13_frag(const bf16x8 (&wr)[6], const W13Extra
     }
   }
   return __builtin_bit_cast(bf16x8, o);
+}
+// ... of a two-quad item (f = 0..7)
+__device__ __forceinline__ bf16x8 w13_frag(const bf16x8 (&wr)[6], const W13Extra &ex, int f, int l) {
+  const int q = f >> 2;
+  return w13_frag(wr[3 * q + ((f & 3) >> 1)], wr[3 * q + 2], ex.sg[q], ex.meta, f, l);
+}
+// ... of a one-quad item (f = 0..3)
+__device__ __forceinline__ bf16x8 w13_frag(const bf16x8 (&wr)[3], uint32_t sgw, u32x2 meta, int f, int l) {
+  return w13_frag(wr[f >> 1], wr[2], sgw, meta, f, l);
 }
 
 // The 16 fp32 scales of packed tile t (wscale + 16 t, 64-byte aligned) by ONE scalar load: the address is wave-uniform

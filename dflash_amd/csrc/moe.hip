@@ -467,6 +467,17 @@ struct MoeGuArgs {
 struct MoeGuArgs8 : MoeGuArgs {
   const float *wscale;
 };
+// W13: wp holds the 13-bit quads of the experts' gate/up weights as ONE tall matrix of E * 2*npp tiles (gemm_rows.h), meta
+// the [tiles][16 waves] {base, patch} pairs behind them.  (Again a struct of its own.)
+struct MoeGuArgs13 : MoeGuArgs {
+  const u32x2 *meta;
+};
+// what an item of the W13 form holds beside its six 16-byte words: the SG words of its gate and up quad (VGPRs) and the
+// two {base, patch} pairs (wave-uniform: SGPRs)
+struct W13Pair {
+  uint32_t sg[2];
+  u32x2 meta[2];
+};
 
 // W8 (dfl_moe_gate_up on e4m3 codes): a wave's 4 k-steps of the gate tile and of the up tile arrive as 2 + 2 16-byte loads of
 // codes, kept raw in flight (half the registers per buffer) and converted in front of each MFMA; same k-steps per wave,
@@ -476,26 +487,46 @@ struct MoeGuArgs8 : MoeGuArgs {
 // pair in registers at the epilogue.  A scalar load (tile_scales) would have to be issued per item behind the dependent
 // scalar load of the expert list and be selected 16 ways per thread; requested in the epilogue it is a round trip per
 // item at the launch's tail.
-template <bool W8>
-__global__ __launch_bounds__(1024) void k_moe_gate_up(std::conditional_t<W8, MoeGuArgs8, MoeGuArgs> a) {
+// W13 (dfl_moe_gate_up on the lossless 13-bit form, K = 2048): wave w's four k-steps of a tile are exactly quad w of that
+// tile, so an item is ONE quad of the gate tile and one of the up tile — per tile and lane a 4-byte SG request and three
+// 16-byte ones (load_quads_w13's one-quad form), 13 VGPRs in flight per tile where the bf16 form has 16.  The two {base,
+// patch} pairs of (tile, wave w) are wave-uniform: scalar loads through the constant address space (w13_meta), issued
+// WITH the item — behind the same dependent scalar load of list[] its weight addresses wait for — and held in SGPRs
+// beside the buffers; w13_frag rebuilds the bf16 form's fragment of each k-step in front of its MFMA and applies the
+// patch under a scalar compare on the held word, so a launch without exceptions pays the compares only.  Same
+// fragments, same MFMAs in the same order, same meeting and epilogue: the bf16 launch's bits.  A dead item clips both
+// descriptors to zero quads; its meta loads read the last live item's pairs, which nothing uses.
+template <bool W8, bool W13 = false>
+__global__ __launch_bounds__(1024) void k_moe_gate_up(
+    std::conditional_t<W13, MoeGuArgs13, std::conditional_t<W8, MoeGuArgs8, MoeGuArgs>> a) {
+  static_assert(!(W8 && W13), "one weight format per instantiation");
   __shared__ float red[2][16][2][256];
   const int tid = threadIdx.x;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6), l = tid & 63;
   int nfw = a.KS - 4 * w;
   nfw = __builtin_amdgcn_readfirstlane(nfw < 0 ? 0 : (nfw > 4 ? 4 : nfw));
   const int nitems = a.n_active[0] * a.npp;
-  constexpr int WR = W8 ? 2 : 4;  // weight registers (16 bytes each) per tile of an item
-  const int64_t tile = (int64_t)(W8 ? a.KS >> 1 : a.KS) * 64, expert = 2 * a.npp * tile;   // 16-byte units
+  constexpr int WR = W13 ? 3 : (W8 ? 2 : 4);  // weight registers (16 bytes each) per tile of an item
+  // 16-byte units per tile and per expert (W13: a tile is KS / 4 quads of 208 units, and the wave's quad is number w)
+  const int64_t tile = W13 ? (int64_t)(a.KS >> 2) * (W13_QUAD_BYTES / 16) : (int64_t)(W8 ? a.KS >> 1 : a.KS) * 64;
+  const int64_t expert = 2 * a.npp * tile;
   bf16x8 gA[WR], uA[WR], gB[WR], uB[WR], xr[4];
   float sgA = 0.f, suA = 0.f, sgB = 0.f, suB = 0.f;  // W8: the scales of this lane's gate / up column
+  W13Pair exA{}, exB{};                              // W13: the item's sign words and {base, patch} pairs
   // (every request unconditional, a dummy past the end: see k_moe_down)
-  auto issue = [&](bf16x8(&g)[WR], bf16x8(&u)[WR], float &sg, float &su, int it) {
+  auto issue = [&](bf16x8(&g)[WR], bf16x8(&u)[WR], float &sg, float &su, W13Pair &ex, int it) {
     const bool live = it < nitems;
     it = live ? it : nitems - 1;
     const int e = a.list[it / a.npp], p = it % a.npp;
-    const bf16x8 *base = a.wp + e * expert + 2 * p * tile + WR * w * 64;
+    const bf16x8 *base = a.wp + e * expert + 2 * p * tile + (W13 ? W13_QUAD_BYTES / 16 : WR * 64) * w;
     const int nf = __builtin_amdgcn_readfirstlane(live ? nfw : 0);
-    if constexpr (W8) {
+    if constexpr (W13) {
+      const int t = (e * a.npp + p) * 2;  // the gate tile of the tall matrix; the up tile is t + 1
+      ex.meta[0] = w13_meta(a.meta, t, w);
+      ex.meta[1] = w13_meta(a.meta, t + 1, w);
+      load_quads_w13(g, ex.sg[0], reinterpret_cast<const char *>(base), nf >> 2, l);
+      load_quads_w13(u, ex.sg[1], reinterpret_cast<const char *>(base + tile), nf >> 2, l);
+    } else if constexpr (W8) {
       const float *sp = a.wscale + ((int64_t)e * a.npp + p) * 32 + (l & 15);
       sg = sp[0];
       su = sp[16];
@@ -509,19 +540,28 @@ __global__ __launch_bounds__(1024) void k_moe_gate_up(std::conditional_t<W8, Moe
   int it = blockIdx.x;
   if (it >= nitems) return;
   load_ksteps<4, 0>(xr, a.xfrag + 4 * w * 64, nfw, l);   // activations first: a wave's loads return in issue order
-  issue(gA, uA, sgA, suA, it);
+  issue(gA, uA, sgA, suA, exA, it);
   const int nv = (a.dyn && a.valid_word >= 0) ? a.dyn[a.valid_word] : 16;
   if ((l & 15) >= nv) {
 #pragma unroll
     for (int f = 0; f < 4; ++f) xr[f] = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
   }
   int pos = 0;
-  auto consume = [&](const bf16x8(&g)[WR], const bf16x8(&u)[WR], float scg, float scu, int itc) {
+  auto consume = [&](const bf16x8(&g)[WR], const bf16x8(&u)[WR], float scg, float scu, const W13Pair &ex, int itc) {
     f32x4 ag = {0.f, 0.f, 0.f, 0.f}, au = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (W13) {
 #pragma unroll
-    for (int f = 0; f < 4; ++f) ag = __builtin_amdgcn_mfma_f32_16x16x32_bf16(weight_frag<W8, WR>(g, f), xr[f], ag, 0, 0, 0);
+      for (int f = 0; f < 4; ++f)
+        ag = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w13_frag(g, ex.sg[0], ex.meta[0], f, l), xr[f], ag, 0, 0, 0);
 #pragma unroll
-    for (int f = 0; f < 4; ++f) au = __builtin_amdgcn_mfma_f32_16x16x32_bf16(weight_frag<W8, WR>(u, f), xr[f], au, 0, 0, 0);
+      for (int f = 0; f < 4; ++f)
+        au = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w13_frag(u, ex.sg[1], ex.meta[1], f, l), xr[f], au, 0, 0, 0);
+    } else {
+#pragma unroll
+      for (int f = 0; f < 4; ++f) ag = __builtin_amdgcn_mfma_f32_16x16x32_bf16(weight_frag<W8, WR>(g, f), xr[f], ag, 0, 0, 0);
+#pragma unroll
+      for (int f = 0; f < 4; ++f) au = __builtin_amdgcn_mfma_f32_16x16x32_bf16(weight_frag<W8, WR>(u, f), xr[f], au, 0, 0, 0);
+    }
     const int buf = pos & 1;
     ++pos;
     *reinterpret_cast<f32x4 *>(&red[buf][w][0][l * 4]) = ag;
@@ -548,13 +588,13 @@ __global__ __launch_bounds__(1024) void k_moe_gate_up(std::conditional_t<W8, Moe
   };
   const int G = gridDim.x;
   for (; it < nitems; it += 2 * G) {
-    issue(gB, uB, sgB, suB, it + G);
+    issue(gB, uB, sgB, suB, exB, it + G);
     __builtin_amdgcn_sched_barrier(0);
-    consume(gA, uA, sgA, suA, it);
+    consume(gA, uA, sgA, suA, exA, it);
     __builtin_amdgcn_sched_barrier(0);
-    issue(gA, uA, sgA, suA, it + 2 * G);
+    issue(gA, uA, sgA, suA, exA, it + 2 * G);
     __builtin_amdgcn_sched_barrier(0);
-    if (it + G < nitems) consume(gB, uB, sgB, suB, it + G);
+    if (it + G < nitems) consume(gB, uB, sgB, suB, exB, it + G);
     __builtin_amdgcn_sched_barrier(0);
   }
 }
@@ -566,13 +606,22 @@ namespace {
 // the expert kernels read them by 4- and 16-byte vector loads)
 inline bool scales_aligned(const float *p) { return ((uintptr_t)p & 63) == 0; }
 
-template <bool W8>
+template <bool W8, bool W13 = false>
 int moe_gate_up_impl(const char *who, const dfl_weight *w, const void *x_frag, int E, int I, int K, void *act_frag,
                      const int32_t *list, const int32_t *n_active, const int32_t *dyn, int valid_word, void *stream) {
+  if constexpr (W13) {
+    DFL_REQUIRE(!w->scale, "%s: a DFL_W_BF16X13 weight takes no scale vector (the bases and patch words follow the codes)", who);
+    DFL_REQUIRE(K == 2048, "%s: DFL_W_BF16X13 covers K = 2048 only here (a wave's share of a tile is one quad of four k-steps; K=%d)",
+                who, K);
+  }
   DFL_REQUIRE(w->wp && x_frag && act_frag && list && n_active, "%s: null pointer", who);
   DFL_REQUIRE(E >= 1 && E <= 1024 && I > 0 && I % 16 == 0 && K > 0 && K % 32 == 0 && K <= 2048,
               "%s: E=%d I=%d K=%d outside range (K <= 2048; larger K: dfl_gemm_silu_mul_experts)", who, E, I, K);
-  std::conditional_t<W8, MoeGuArgs8, MoeGuArgs> a{};
+  std::conditional_t<W13, MoeGuArgs13, std::conditional_t<W8, MoeGuArgs8, MoeGuArgs>> a{};
+  if constexpr (W13) {  // the meta pairs lie behind the quads of all E * 2I / 16 tiles, as k_gemm_w13 finds them
+    const int64_t quads = (int64_t)E * (2 * I / 16) * (K / 128);
+    a.meta = reinterpret_cast<const u32x2 *>(reinterpret_cast<const char *>(w->wp) + quads * W13_QUAD_BYTES);
+  }
   if constexpr (W8) {
     DFL_REQUIRE(K % 64 == 0, "%s: K=%d is not a multiple of 64 (the e4m3 layout holds k-step pairs)", who, K);
     DFL_REQUIRE(w->scale, "%s: null scale vector", who);
@@ -588,7 +637,7 @@ int moe_gate_up_impl(const char *who, const dfl_weight *w, const void *x_frag, i
   a.KS = K / 32;
   a.npp = I / 16;
   a.act = (bf16_t *)act_frag;
-  hipLaunchKernelGGL(k_moe_gate_up<W8>, dim3(256), dim3(1024), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL((k_moe_gate_up<W8, W13>), dim3(256), dim3(1024), 0, (hipStream_t)stream, a);
   DFL_CHECK_LAUNCH(who);
   return DFL_OK;
 }
@@ -598,6 +647,8 @@ extern "C" int dfl_moe_gate_up(const dfl_weight *w_gateup, const void *x_frag, i
                                const int32_t *list, const int32_t *n_active, const int32_t *dyn, int valid_word,
                                void *stream) {
   const char *who = "dfl_moe_gate_up";
+  if (w_gateup && w_gateup->format == DFL_W_BF16X13)  // (weight_ok knows the two formats every entry point takes)
+    return moe_gate_up_impl<false, true>(who, w_gateup, x_frag, E, I, K, act_frag, list, n_active, dyn, valid_word, stream);
   if (!weight_ok(who, w_gateup)) return DFL_EINVAL;
   return w_gateup->format == DFL_W_BF16
              ? moe_gate_up_impl<false>(who, w_gateup, x_frag, E, I, K, act_frag, list, n_active, dyn, valid_word, stream)

@@ -205,13 +205,15 @@ def row_layers(layers: list, layers8, gu13: list, fp8: bool, cache: dict) -> lis
 X13_QUAD_BYTES = 3328   # four k-steps of one 16-column tile: L0, L1, NB (1024 B each) and SG (256 B); csrc/gemm_rows.h
 STREAM_FORMATS = ("auto", "bf16")
 # Which matrix kinds stream_format="auto" packs: each kept only where its slowest repeat beat the plain form's fastest
-# (profiles/bf16x13_ab.txt, part 1)
-X13_KINDS = {"gateup": True, "lm_head": True}
+# (profiles/bf16x13_ab.txt, part 1); "experts_gateup" — an MoE layer's experts as one tall matrix, dfl_moe_gate_up — by
+# the same rule at 46 AND at 80 active experts (profiles/bf16x13_experts_ab.txt, part 1: 40.6 < 45.6 us, 63.5 < 74.9 us)
+X13_KINDS = {"gateup": True, "lm_head": True, "experts_gateup": True}
 
 
 class Bf16x13Weight(NamedTuple):
-    """A packed bf16 weight re-coded by pack_weight_bf16x13: gemm_silu_mul / gemm_argmax take one in place of the packed
-    bf16 tensor and compute the same bits from 13/16 of the bytes."""
+    """A packed bf16 weight re-coded by pack_weight_bf16x13: gemm_silu_mul / gemm_argmax — and moe_gate_up, for an MoE
+    layer's experts as one tall matrix — take one in place of the packed bf16 tensor and compute the same bits from
+    13/16 of the bytes."""
     data: torch.Tensor    # uint8: [N/16][K/128] quads of X13_QUAD_BYTES, then int32 [N/16][16][2] {base, patch}
     N: int
     K: int
@@ -856,10 +858,14 @@ def gemm_silu_mul_experts(wp_gu: torch.Tensor, x, E: int, I: int, K: int, act: t
 def moe_gate_up(wp_gu: torch.Tensor, x_frag: torch.Tensor, E: int, I: int, K: int, act: torch.Tensor, lst: torch.Tensor,
                 n_active: torch.Tensor, dyn=None, valid_word: int = -1) -> None:
     """gemm_silu_mul_experts for K <= 2048 from frag16 rows: one LDS meeting per (gate, up) tile pair.  wp_gu: packed
-    bf16 [E, 2*I*K], or an Fp8Experts."""
+    bf16 [E, 2*I*K], an Fp8Experts, or (K = 2048) the Bf16x13Weight of that packed tensor as ONE matrix of E * 2I x K
+    (pack_weight_bf16x13: the experts' tiles back to back) — the same bits as the packed tensor gives."""
     assert act.dim() == 2 and act.is_contiguous() and act.shape[1] == 16 * I and x_frag.numel() >= 16 * K
-    w, rows = _we(wp_gu, E, 2 * I, K, "wp_gu")
-    assert rows.shape[1] == 2 * I * K
+    if isinstance(wp_gu, Bf16x13Weight):
+        w = _w(wp_gu, E * 2 * I, K, "wp_gu")
+    else:
+        w, rows = _we(wp_gu, E, 2 * I, K, "wp_gu")
+        assert rows.shape[1] == 2 * I * K
     check(lib().dfl_moe_gate_up(w, _p(x_frag, BF16, "x_frag"), E, I, K, _p(act, BF16, "act"), _p(lst, I32, "list"),
                                 _p(n_active, I32, "n_active"), _p(dyn, I32, "dyn"), valid_word, _stream()),
           "dfl_moe_gate_up")

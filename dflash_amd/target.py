@@ -85,7 +85,12 @@ class NativeTarget:
         and, at temperature 0, the lm_head from a lossless 13-bit copy (ops.pack_weight_bf16x13)
         wherever the layout covers the shape (hidden 2048 or 4096) and the packer takes the matrix: the same bits out,
         13/16 of the bytes in.  The plain packed weights stay resident for every other path (prefill, wide blocks, the
-        ragged batch, sampled heads): 13/16 of gate/up and lm_head more memory.  "bf16": plain packed bf16 everywhere.
+        ragged batch, sampled heads): 13/16 of gate/up and lm_head more memory.  A sparse-MoE target with bf16 experts at
+        hidden 2048 streams its experts' gate/up the same way (dfl_moe_gate_up on the twin of each MoE layer's tall
+        E * 2I x H matrix, lw["gu_e13"]: the verify of <= 16 rows and the per-tile expert branch of moe_mlp_tiles; the
+        shared pass over 2..4 tiles, prefill and an fp8-expert target read the plain copy; a layer whose matrix the packer
+        refused stays bf16).  That costs 13/16 of the gate/up expert bytes on top: at 30B-A3B about 31 GB beside 58 GB of
+        weights ("The experts").  "bf16": plain packed bf16 everywhere.
         weight_format: "bf16" (default), or "fp8_e4m3": every Linear weight of the target — q/k/v, o_proj, gate, up and
         down of every layer, and the lm_head — is quantised here to OCP e4m3 codes with one power-of-two scale per output
         row (ops.quantize_fp8_rows; W8A16, weight-only).  The quantised target IS the model: THE CALLER'S hf_model IS
@@ -244,6 +249,10 @@ class NativeTarget:
                 lw["gu_e"] = torch.stack([ops.pack_weight_gateup(gup[e, :Ie].contiguous(), gup[e, Ie:].contiguous())
                                           for e in range(self.E)])
                 lw["down_e"] = torch.stack([ops.pack_weight(dwn[e].contiguous()) for e in range(self.E)])
+                if self.x13 and not e8 and self.H == 2048:   # the experts' gate/up as ONE tall matrix in 13 bits
+                    g13 = ops.bf16x13_twin(lw["gu_e"], self.E * 2 * Ie, self.H, "experts_gateup")
+                    if g13 is not None:   # (None: the kind is off or the packer refused the matrix — plain bf16 stays)
+                        lw["gu_e13"] = g13   # (held by the layer dict: a captured verify reads it for the target's lifetime)
                 ep = (self.E + 15) // 16 * 16               # router rows padded to whole column tiles (never routed to)
                 rw = torch.zeros(ep, self.H, dtype=BF16, device=dev)
                 rw[:self.E] = w(p + "mlp.gate.weight")
@@ -434,10 +443,12 @@ class NativeTarget:
         """(gate/up, down) weights of an MoE layer (its dict in self.layers) for the two expert launches on <= 16 rows:
         the e4m3 codes (ops.Fp8Experts) of an fp8-expert target while expert_stream is set — gate/up only where the pair
         kernel runs (hidden <= 2048, moe_pair_kernel): dfl_gemm_silu_mul_experts has no W8 form — else the packed bf16
-        copy."""
+        copy; of a bf16 target under stream_format="auto", gate/up is the layer's 13-bit twin (lw["gu_e13"], hidden 2048)
+        where the pair kernel runs and the packer took the matrix: the same bits from 13/16 of the bytes."""
+        pair = self.H <= 2048 and self.moe_pair_kernel
         if "gu_e8" not in lw or not self.expert_stream:
-            return lw["gu_e"], lw["down_e"]
-        return (lw["gu_e8"] if (self.H <= 2048 and self.moe_pair_kernel) else lw["gu_e"]), lw["down_e8"]
+            return (lw["gu_e13"] if (pair and "gu_e13" in lw) else lw["gu_e"]), lw["down_e"]
+        return (lw["gu_e8"] if pair else lw["gu_e"]), lw["down_e8"]
 
     def tile_head(self):
         """The lm_head of the tile-stack paths: the e4m3 codes when streams_fp8_tiles(), else the packed bf16 copy."""

@@ -99,8 +99,8 @@ typedef struct dfl_rows {
  * argument; what the e4m3 form narrows is said at each entry point.
  * DFL_EINVAL: a null descriptor, a format other than the two, DFL_W_BF16 with a scale, DFL_W_E4M3 without one.
  * ---- DFL_W_BF16X13: the packed bf16 weight in 13 bits per element, losslessly ----
- * Taken by dfl_gemm_silu_mul and dfl_gemm_argmax ONLY, at K = 2048 or K = 4096; every other entry point refuses it as an
- * unknown format.  Same results as DFL_W_BF16 on the same matrix, bit for bit: the kernels rebuild the bf16 fragments in
+ * Taken by dfl_gemm_silu_mul and dfl_gemm_argmax at K = 2048 or K = 4096 and by dfl_moe_gate_up at K = 2048 ONLY; every
+ * other entry point refuses it as an unknown format. Same results as DFL_W_BF16 on the same matrix, bit for bit: the kernels rebuild the bf16 fragments in
  * registers from 13/16 of the bytes.  A bf16 is L = bits[7:0] and H = bits[15:8].  Per packed 16-column tile the base is
  * hb = max(0, max(H & 0x7f) - 15); an element keeps L, its sign and a 4-bit code c: c = 0 <=> (H & 0x7f) == 0 (+-0,
  * denormals, exponent 1: L is kept), c = 1..15 <=> (H & 0x7f) == hb + c.  All-zero bits decode to +0.
@@ -415,7 +415,13 @@ int dfl_gemm_silu_mul_experts(const void *wp_gateup, int64_t wp_expert_stride, c
  *  dfl_moe_gate_up: the experts' codes back to back, each 2*I*K bytes in dfl_pack_weight_gateup_fp8's layout; scale fp32
  *    [E][2*I] in that layout's tile order (gate tile p's 16 scales, then up tile p's).  K % 64 == 0.
  *  dfl_moe_down: expert e's codes (dfl_pack_weight_fp8 of its [N][I] weight) at wp + e * wp_expert_stride BYTES (>= N*I,
- *    % 16 == 0); scale fp32 [E][N].  I % 64 == 0. */
+ *    % 16 == 0); scale fp32 [E][N].  I % 64 == 0.
+ * DFL_W_BF16X13 (dfl_moe_gate_up only; dfl_moe_down refuses it: its K = I is not the layout's): K = 2048, scale NULL.  wp
+ * is the 13-bit form of the experts' packed gate/up weights taken as ONE matrix of N = E * 2*I rows (dflash_amd.ops.
+ * pack_weight_bf16x13 of the [E][2*I*K] tensor as it stands): the quads of all E * 2*I / 16 tiles, expert after expert
+ * in dfl_pack_weight_gateup order, then the {base, patch} pairs of all tiles.  Wave w's four k-steps of a tile are quad
+ * w of that tile, so an item streams one quad of the gate tile and one of the up tile and rebuilds the bf16 form's
+ * fragments in registers: the same bits as the DFL_W_BF16 launch on the same weights, from 13/16 of the bytes. */
 int dfl_moe_gate_up(const dfl_weight *w_gateup, const void *x_frag, int E, int I, int K, void *act_frag, const int32_t *list,
                     const int32_t *n_active, const int32_t *dyn, int valid_word, void *stream);
 int dfl_moe_down(const dfl_weight *w_down, int64_t wp_expert_stride, const void *act_frag, int64_t act_expert_stride,
