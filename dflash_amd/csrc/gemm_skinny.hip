@@ -216,13 +216,18 @@ constexpr int gemm_fr(int MT, bool CHUNKED) { return CHUNKED ? 4 : (MT == 1 ? 8 
 // Everything else (masks, the half-tile lane rule, the LDS meeting, the tile plan) is the bf16 form's.
 // W13: the weights are the lossless 13-bit form of bf16 (gemm_rows.h): an item is two quads of four k-steps, six 16-byte and
 // two 4-byte words per lane instead of eight 16-byte ones, decoded into the SAME fragments in front of the MFMAs; the
-// tile's base and the item's patch word come by a scalar load issued with the item's request.  MT = 1, not chunked.
+// tile's base and the item's patch word come by a scalar load issued with the item's request.  MT = 1.
+// W13 && CHUNKED (k_gemm_w13c; K a multiple of 2048 above 4096, so every chunk is whole): in chunk c wave w owns k-steps
+// (16 c + w) * 4 .. + 3 — quad 16 c + w of the tile.  An item is that ONE quad (the request of k_moe_gate_up: SG, NB, L0,
+// L1; 13 VGPRs in flight against 16), its meta pair is pair (t * nch + c) * 16 + w, and the chunk's activation fragments
+// go behind the quad as in the bf16 form.
 template <int MT, bool CHUNKED, int EPI, bool NORM, bool W8 = false, bool W13 = false>
 __device__ __forceinline__ void gemm_body(const GemmArgs &a, const SampleArgs &sa) {
   GSTAMP(0);
-  static_assert(!W13 || (MT == 1 && !CHUNKED && !W8), "W13: the single-tile, single-pass bf16 kernels only");
+  static_assert(!W13 || (MT == 1 && !W8), "W13: the single-tile bf16 kernels only");
+  static_assert(!W13 || !CHUNKED || (EPI == EPI_RESID && !NORM), "W13, K-chunked: the residual launch only");
   constexpr int FR = gemm_fr(MT, CHUNKED);
-  constexpr int NW = W13 ? 6 : (W8 ? FR / 2 : FR);  // 16-byte weight words per item and lane
+  constexpr int NW = W13 ? (CHUNKED ? 3 : 6) : (W8 ? FR / 2 : FR);  // 16-byte weight words per item and lane
   // red[buf][wave][mt][256]: lane l owns floats 4l..4l+3 (its MFMA D regs)
   __shared__ float red[2][16][MT][256];
   __shared__ float ssred[NORM ? MT : 1][16][16];
@@ -317,8 +322,13 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &a, const SampleArgs &s
     }
   };
   // W13: (K is 2048 or 4096, so ks0 and nf are whole quads) the meta pair WITH the request, as the W8 scale
-  auto load_w13 = [&](bf16x8(&wr)[NW], W13Extra &ex, int t, int ks0, int nf, int half) {
-    if constexpr (W13) {
+  // chunked: the one quad of (tile t, chunk c), whole tiles only, and the pair of (t * nch + c, wave)
+  auto load_w13 = [&](bf16x8(&wr)[NW], W13Extra &ex, int t, int ks0, int nf, int half, int c = 0) {
+    if constexpr (W13 && CHUNKED) {
+      const char *base = reinterpret_cast<const char *>(a.wp);
+      load_quads_w13(wr, ex.sg[0], base + ((size_t)t * (a.KS >> 2) + (ks0 >> 2)) * W13_QUAD_BYTES, nf >> 2, l);
+      ex.meta = w13_meta(reinterpret_cast<const u32x2 *>(a.wscale), nf > 0 ? t * a.nch + c : 0, w);
+    } else if constexpr (W13) {
       const char *base = reinterpret_cast<const char *>(a.wp);
       load_quads_w13(wr, ex.sg, base + ((size_t)t * (a.KS >> 2) + (ks0 >> 2)) * W13_QUAD_BYTES, nf >> 2, l, half);
       ex.meta = w13_meta(reinterpret_cast<const u32x2 *>(a.wscale), nf > 0 ? t : 0, w);  // (nothing fetched: any valid pair)
@@ -326,7 +336,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &a, const SampleArgs &s
   };
   auto load_item = [&](bf16x8(&wr)[NW], float &sc, W13Extra &ex, bf16x8(&xb)[MT][FR], int t, int c, int half) {
     if constexpr (W13)
-      load_w13(wr, ex, t, ks0_of(c), nf_of(c), half);
+      load_w13(wr, ex, t, ks0_of(c), nf_of(c), half, c);
     else if constexpr (W8)
       load_w8(wr, sc, t, ks0_of(c), nf_of(c), half);
     else
@@ -423,7 +433,9 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &a, const SampleArgs &s
           xv = keep ? xb[mt][f] : (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
         }
         bf16x8 wf;
-        if constexpr (W13)
+        if constexpr (W13 && CHUNKED)
+          wf = w13_frag(wr, ex.sg[0], ex.meta, f, l);
+        else if constexpr (W13)
           wf = w13_frag(wr, ex, f, l);
         else
           wf = weight_frag<W8>(wr, f);
@@ -570,7 +582,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &a, const SampleArgs &s
     if constexpr (W8)
       load_w8(wA, scA, first_tile, ks0_of(0), first_live ? nf0 : 0, first_half);
     else if constexpr (W13)
-      ;  // (no chunked W13 form: the static_assert above)
+      load_w13(wA, exA, first_tile, ks0_of(0), first_live ? nf0 : 0, first_half, 0);
     else if (nitems > 0 || !moe)
       load_ksteps<FR>(wA, a.wp + ((size_t)first_tile * a.KS + ks0_of(0)) * 64, first_live ? nf0 : 0, l, first_half);
     GSTAMP(6);
@@ -648,6 +660,12 @@ __global__ __launch_bounds__(1024) void k_gemm_w8(GEMM_HEAD_PARAMS, GemmArgs res
 template <int EPI, bool NORM>
 __global__ __launch_bounds__(1024) void k_gemm_w13(GEMM_HEAD_PARAMS, GemmArgs rest) {
   gemm_body<1, false, EPI, NORM, false, true>(with_head<false, NORM>(rest, GEMM_HEAD_NAMES), SampleArgs{});
+}
+
+// ... and its K-chunked form (down_proj, fc: K a multiple of 2048 above 4096), one quad per item
+template <int EPI>
+__global__ __launch_bounds__(1024) void k_gemm_w13c(GEMM_HEAD_PARAMS, GemmArgs rest) {
+  gemm_body<1, true, EPI, false, false, true>(with_head<true, false>(rest, GEMM_HEAD_NAMES), SampleArgs{});
 }
 
 template <bool NORM>
@@ -1102,7 +1120,7 @@ extern "C" int dfl_gemm_sample(const dfl_weight *w, const dfl_rows *x, int V, in
 
 
 namespace {
-template <bool W8>
+template <bool W8, bool W13 = false>
 int gemm_resid_impl(const char *who, const dfl_weight *w, const dfl_rows *x, int N, int K, void *h_io, int64_t ldh,
                     int add_residual, void *tap, int64_t ldtap, float *ss_out, const int32_t *dyn, void *stream) {
   DFL_REQUIRE(w->wp && h_io && (!W8 || w->scale), "%s: null pointer", who);
@@ -1136,7 +1154,15 @@ int gemm_resid_impl(const char *who, const dfl_weight *w, const dfl_rows *x, int
     DFL_REQUIRE(a.src[0].mode != 2, "%s: a normalised source needs K <= 4096", who);
     a.nfr = 4;
     a.nch = (KS + 63) / 64;  // 64 k-steps per chunk: 16 waves x 4
-    if (!launch_gemm<1, true, EPI_RESID, W8>(a, grid, (hipStream_t)stream)) return DFL_EINVAL;
+    if constexpr (W13) {  // (dfl_gemm_resid: K is a whole number of chunks, no scale; whole tiles only — KS > 128 above)
+      a.wscale = reinterpret_cast<const float *>(reinterpret_cast<const char *>(w->wp) + w13_quads_bytes(N, K));
+      a.gx = (int)grid.x;
+      GemmHead h;
+      if (!gemm_head<true>(h, a)) return DFL_EINVAL;
+      hipLaunchKernelGGL((k_gemm_w13c<EPI_RESID>), grid, dim3(1024), 0, (hipStream_t)stream, GEMM_HEAD_OF(h), a);
+    } else if (!launch_gemm<1, true, EPI_RESID, W8>(a, grid, (hipStream_t)stream)) {
+      return DFL_EINVAL;
+    }
   }
   DFL_CHECK_LAUNCH(who);
   return DFL_OK;
@@ -1147,6 +1173,11 @@ extern "C" int dfl_gemm_resid(const dfl_weight *w, const dfl_rows *x, int N, int
                               int add_residual, void *tap, int64_t ldtap, float *ss_out, const int32_t *dyn,
                               void *stream) {
   const char *who = "dfl_gemm_resid";
+  // the 13-bit form where its K-chunked layout covers the launch; any other K falls through to weight_ok's refusal
+  if (w && w->format == DFL_W_BF16X13 && K > 4096 && K % 2048 == 0) {
+    DFL_REQUIRE(!w->scale, "%s: a DFL_W_BF16X13 weight takes no scale vector (the bases and patch words follow the codes)", who);
+    return gemm_resid_impl<false, true>(who, w, x, N, K, h_io, ldh, add_residual, tap, ldtap, ss_out, dyn, stream);
+  }
   if (!weight_ok(who, w)) return DFL_EINVAL;
   return w->format == DFL_W_BF16
              ? gemm_resid_impl<false>(who, w, x, N, K, h_io, ldh, add_residual, tap, ldtap, ss_out, dyn, stream)

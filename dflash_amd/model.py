@@ -113,6 +113,8 @@ class DFlashDraftModel:
             raise NotImplementedError("fp8_e4m3 weights need hidden, intermediate, fc input and q widths % 64 == 0")
         self.w: Optional[dict] = None
         self.gu13: list = []             # stream_format="auto": per layer, the 13-bit twin of w["layers"][i]["gu"] or None
+        self.down13: list = []           # ... and of w["layers"][i]["down"]
+        self.fc13 = None                 # ... and of w["fc"]
         self.w8: Optional[dict] = None   # fp8_e4m3: ops.Fp8Weight twins of the matrices in self.w (same keys)
         # fp8_e4m3 only: False = run everything on the dequantised bf16 copy (the second implementation the tests compare)
         self.fp8_stream = True
@@ -171,7 +173,7 @@ class DFlashDraftModel:
              "norm": dev("norm.weight"), "layers": []}
         if fp8:
             w8["fc"] = ops.pack_weight_fp8(*top8.pop("fc"))
-        gu13 = []
+        gu13, down13 = [], []
         for i in range(c.num_hidden_layers):
             p = f"layers.{i}."
             l8 = {}
@@ -193,6 +195,8 @@ class DFlashDraftModel:
             # the 13-bit twin of gate/up per layer, or None where plain bf16 stays (ops.bf16x13_twin)
             gu13.append(ops.bf16x13_twin(w["layers"][-1]["gu"], 2 * c.intermediate_size, c.hidden_size, "gateup")
                         if self.x13 else None)
+            down13.append(ops.bf16x13_twin(w["layers"][-1]["down"], c.hidden_size, c.intermediate_size, "down")
+                          if self.x13 else None)
             del qkv, gate, up, o, down
         # context K/V weights of ALL layers as one packed weight (tile-major layout: the k/v column tiles of
         # each layer's packed qkv, concatenated): the context rows' K/V of every layer depend only on the
@@ -208,7 +212,9 @@ class DFlashDraftModel:
         torch.cuda.synchronize(self.device)
         self.w = w
         self.w8 = w8
-        self.gu13 = gu13
+        self.gu13, self.down13 = gu13, down13
+        # fc's 13-bit twin for the <= 16-row block (draft_block), or None where plain bf16 stays
+        self.fc13 = ops.bf16x13_twin(w["fc"], c.hidden_size, c.fc_in, "fc") if self.x13 else None
         self._tile_layers = {}
         self._row_layers = {}
         self._ws = self.rows = None  # row sources point at the weights: rebuild with them
@@ -322,9 +328,11 @@ class DFlashDraftModel:
 
     def row_layers(self, bs: int) -> list:
         """The layer dicts RowStack.run takes for a block of `bs` rows: self.w's, with the four matrices replaced by
-        their e4m3 twins when streams_fp8(bs), else gate/up by its 13-bit twin where the layer has one (gu13)."""
+        their e4m3 twins when streams_fp8(bs), else gate/up and down by their 13-bit twins where the layer has them
+        (gu13, down13)."""
         fp8 = self.streams_fp8(bs)
-        return ops.row_layers(self.w["layers"], self.w8["layers"] if fp8 else None, self.gu13, fp8, self._row_layers)
+        return ops.row_layers(self.w["layers"], self.w8["layers"] if fp8 else None, self.gu13, fp8, self._row_layers,
+                              getattr(self, "down13", None))
 
     # ------------------------------------------------------------------ kernels
     def _ctx_rows(self, th_rows: torch.Tensor, n: int, dyn, dyn_word: Optional[int]):
@@ -484,7 +492,10 @@ class DFlashDraftModel:
         top = self.w8 if self.streams_fp8(bs) else w   # fc and kv_all, the matrices outside the layers: as row_layers(bs)
         if tau > 0:
             # fc straight off the tap rows; hidden_norm is applied by each layer's qkv GEMM (:177)
-            ops.gemm_resid(top["fc"], ops.rows_plain(th_rows, ops.DYN_TAU), H, c.fc_in, ws["ctxh"], add_residual=False,
+            fc = top["fc"]
+            if top is w and bs <= 16 and getattr(self, "fc13", None) is not None:
+                fc = self.fc13
+            ops.gemm_resid(fc, ops.rows_plain(th_rows, ops.DYN_TAU), H, c.fc_in, ws["ctxh"], add_residual=False,
                            ss_out=ws["ss_ctx"], dyn=dyn)
         if head and tau > 0:   # K/V Linear outputs of the context rows, all layers, one pass over 84 MB
             ops.gemm_resid(top["kv_all"], src["ctx"], c.num_hidden_layers * 2 * c.kv_dim, H, ws["xc"], add_residual=False,

@@ -189,15 +189,18 @@ def tile_layers(layers: list, layers8: list, qkv_parts: bool, cache: dict) -> li
     return cache[qkv_parts]
 
 
-def row_layers(layers: list, layers8, gu13: list, fp8: bool, cache: dict) -> list:
+def row_layers(layers: list, layers8, gu13: list, fp8: bool, cache: dict, down13=None) -> list:
     """The layer dicts RowStack.run takes — the one format choice of the single-request path.  fp8: `layers` with qkv / o /
-    gu / down replaced by their e4m3 twins in layers8; else with gu replaced by its 13-bit twin where gu13[i] is not None
-    (a layer without one, an MoE layer among them, passes through as it is).  Built once per form and kept in `cache`."""
+    gu / down replaced by their e4m3 twins in layers8; else with gu / down replaced by their 13-bit twins where gu13[i] /
+    down13[i] is not None (a layer with neither, an MoE layer among them, passes through as it is).  Built once per form
+    and kept in `cache`."""
     if fp8 not in cache:
         if fp8:
             cache[fp8] = [{**lw, **{k: l8[k] for k in ("qkv", "o", "gu", "down")}} for lw, l8 in zip(layers, layers8)]
         else:
-            cache[fp8] = [lw if g is None else {**lw, "gu": g} for lw, g in zip(layers, gu13)]
+            twins = [{k: v for k, v in (("gu", g), ("down", d)) if v is not None}
+                     for g, d in zip(gu13, down13 or [None] * len(layers))]
+            cache[fp8] = [{**lw, **tw} if tw else lw for lw, tw in zip(layers, twins)]
     return cache[fp8]
 
 
@@ -206,22 +209,25 @@ X13_QUAD_BYTES = 3328   # four k-steps of one 16-column tile: L0, L1, NB (1024 B
 STREAM_FORMATS = ("auto", "bf16")
 # Which matrix kinds stream_format="auto" packs: each kept only where its slowest repeat beat the plain form's fastest
 # (profiles/bf16x13_ab.txt, part 1); "experts_gateup" — an MoE layer's experts as one tall matrix, dfl_moe_gate_up — by
-# the same rule at 46 AND at 80 active experts (profiles/bf16x13_experts_ab.txt, part 1: 40.6 < 45.6 us, 63.5 < 74.9 us)
-X13_KINDS = {"gateup": True, "lm_head": True, "experts_gateup": True}
+# the same rule at 46 AND at 80 active experts (profiles/bf16x13_experts_ab.txt, part 1: 40.6 < 45.6 us, 63.5 < 74.9 us);
+# "down" and "fc" — the K-chunked form of gemm_resid, K a multiple of 2048 above 4096 — by profiles/bf16x13_down_ab.txt,
+# part 1: down kept at 4096 x 12288, 4096 x 14336 and 2048 x 6144; fc (4096 x 20480: 0.99 x, the spreads overlap) NOT kept
+X13_KINDS = {"gateup": True, "lm_head": True, "experts_gateup": True, "down": True, "fc": False}
 
 
 class Bf16x13Weight(NamedTuple):
-    """A packed bf16 weight re-coded by pack_weight_bf16x13: gemm_silu_mul / gemm_argmax — and moe_gate_up, for an MoE
-    layer's experts as one tall matrix — take one in place of the packed bf16 tensor and compute the same bits from
-    13/16 of the bytes."""
-    data: torch.Tensor    # uint8: [N/16][K/128] quads of X13_QUAD_BYTES, then int32 [N/16][16][2] {base, patch}
+    """A packed bf16 weight re-coded by pack_weight_bf16x13: gemm_silu_mul / gemm_argmax (K = 2048 or 4096), gemm_resid
+    (K a multiple of 2048 above 4096) — and moe_gate_up, for an MoE layer's experts as one tall matrix — take one in
+    place of the packed bf16 tensor and compute the same bits from 13/16 of the bytes."""
+    data: torch.Tensor    # uint8: [N/16][K/128] quads of X13_QUAD_BYTES, then int32 [N/16][items per tile][2] {base, patch}
     N: int
     K: int
 
 
 def bf16x13_covers(N: int, K: int) -> bool:
-    """The layout holds whole quads of four k-steps per wave: 16 waves x 4 or x 8 k-steps."""
-    return N > 0 and N % 16 == 0 and K in (2048, 4096)
+    """The layout holds whole quads of four k-steps per wave: 16 waves x 4 or x 8 k-steps in one pass, or — the K-chunked
+    form of gemm_resid — whole chunks of 16 waves x 4 k-steps above that."""
+    return N > 0 and N % 16 == 0 and (K in (2048, 4096) or (K > 4096 and K % 2048 == 0))
 
 
 def pack_weight_bf16x13(wp: torch.Tensor, N: int, K: int, tiles_per_pass: int = 256):
@@ -229,20 +235,24 @@ def pack_weight_bf16x13(wp: torch.Tensor, N: int, K: int, tiles_per_pass: int = 
     interleaved, and every packed tile — a gate tile, an up tile — gets a base of its own).
     Returns (Bf16x13Weight or None, report).  Per packed tile hb = max(0, max(H & 0x7f) - 15) with H the bf16's high
     byte; an element keeps its low byte, its sign and a code c (0: H & 0x7f == 0; 1..15: H & 0x7f == hb + c).  A nonzero
-    element below the window (H & 0x7f in 1..hb) is an exception: ONE per (tile, wave) item is carried exactly in that
-    item's patch word; a second one refuses the matrix (None: the caller keeps plain bf16).  report = {"items": (tile,
-    wave) items, "patched": items with a patch word, "refused": items with two or more exceptions}.
+    element below the window (H & 0x7f in 1..hb) is an exception: ONE per item is carried exactly in that item's patch
+    word; a second one refuses the matrix (None: the caller keeps plain bf16).  An item is what one wave holds in flight
+    at a time: (tile, wave) — K / 16 elements per column — at K <= 4096, and (tile, chunk, wave) — one quad — in the
+    K-chunked form above that; its meta pair is pair (tile * nch + chunk) * 16 + wave, nch = K / 2048 chunks (1 at
+    K <= 4096).  report = {"items": items, "patched": items with a patch word, "refused": items with two or more
+    exceptions}.
     Plain tensor ops on wp's device (CPU included), `tiles_per_pass` tiles at a time; runs once at load."""
     if not bf16x13_covers(N, K):
-        raise ValueError(f"dflash_amd: bf16x13 covers K = 2048 or 4096 and N % 16 == 0 (N={N} K={K})")
+        raise ValueError(f"dflash_amd: bf16x13 covers K = 2048, 4096 or a multiple of 2048 above, and N % 16 == 0 (N={N} K={K})")
     if wp.dtype != BF16 or wp.numel() != N * K:
         raise ValueError("dflash_amd: pack_weight_bf16x13 takes the packed bf16 weight of N * K elements")
     nt, KS, dev = N // 16, K // 32, wp.device
-    nfr, Q = KS // 16, KS // 4
+    Q = KS // 4
+    nit, isz = (16, KS // 16 * 512) if K <= 4096 else (Q, 4 * 512)   # items per tile, elements per item
     src = wp.view(torch.int16).view(nt, KS, 64, 8)
     qbytes = nt * Q * X13_QUAD_BYTES
-    data = torch.empty(qbytes + nt * 16 * 8, dtype=U8, device=dev)
-    quads, meta = data[:qbytes].view(nt, Q, X13_QUAD_BYTES), data[qbytes:].view(I32).view(nt, 16, 2)
+    data = torch.empty(qbytes + nt * nit * 8, dtype=U8, device=dev)
+    quads, meta = data[:qbytes].view(nt, Q, X13_QUAD_BYTES), data[qbytes:].view(I32).view(nt, nit, 2)
     rsh = torch.arange(8, dtype=I32, device=dev).view(1, 1, 4, 1, 2, 1)   # r = 2 f + g
     patched = refused = 0
     for t0 in range(0, nt, tiles_per_pass):
@@ -253,13 +263,13 @@ def pack_weight_bf16x13(wp: torch.Tensor, N: int, K: int, tiles_per_pass: int = 
         c = h7 - hb.view(T, 1, 1, 1)
         exc = (h7 != 0) & (c < 1)
         c = torch.where(c < 1, torch.zeros_like(c), c)             # (h7 == 0 lies below hb + 1 as well)
-        # exceptions per (tile, wave) item: wave w owns k-steps w * nfr .. of the tile
-        ex = exc.view(T, 16, nfr * 512)
+        # exceptions per item: item i of a tile owns its k-steps i * isz / 512 ..
+        ex = exc.view(T, nit, isz)
         cnt = ex.sum(dim=2)
         refused += int((cnt > 1).sum())
         patched += int((cnt == 1).sum())
         idx = ex.to(I32).argmax(dim=2)                             # (the first one: the only one where cnt == 1)
-        raw = wi.view(T, 16, nfr * 512).gather(2, idx.unsqueeze(2)).squeeze(2)
+        raw = wi.view(T, nit, isz).gather(2, idx.unsqueeze(2)).squeeze(2)
         word = ((8 + idx // 512) << 28) | (((idx // 8) % 64) << 22) | ((idx % 8) << 19) | raw      # int64
         word = torch.where(cnt == 1, word - (1 << 32), torch.zeros_like(word)).to(I32)             # bit 31: the sign
         meta[t0:t0 + T, :, 0] = hb.to(I32).view(T, 1)
@@ -273,7 +283,7 @@ def pack_weight_bf16x13(wp: torch.Tensor, N: int, K: int, tiles_per_pass: int = 
         out[:, :, 1024:2048] = lq[:, :, 2:4].permute(0, 1, 3, 2, 4).reshape(T, Q, 1024)
         out[:, :, 2048:3072] = nb.permute(0, 1, 3, 2, 4).reshape(T, Q, 1024)
         out[:, :, 3072:3328] = sg.reshape(T, Q, 256)
-    report = {"items": nt * 16, "patched": patched, "refused": refused}
+    report = {"items": nt * nit, "patched": patched, "refused": refused}
     if refused:
         return None, report
     return Bf16x13Weight(data, N, K), report
@@ -289,6 +299,8 @@ def bf16x13_twin(wp: torch.Tensor, N: int, K: int, kind: str):
     tensor lives."""
     import weakref
     if not X13_KINDS[kind] or not bf16x13_covers(N, K):
+        return None
+    if kind in ("down", "fc") and K <= 4096:   # gemm_resid takes the K-chunked form only (dfl_gemm_resid)
         return None
     key = wp.data_ptr()
     hit = _x13_twins.get(key)

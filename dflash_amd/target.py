@@ -217,9 +217,10 @@ class NativeTarget:
             self.lm_wp8 = ops.pack_weight_fp8(*h8.pop("lm"))
         self.layers = []
         self.gu13 = []   # stream_format="auto": per layer, the 13-bit twin of a dense layer's gate/up or None
+        self.down13 = []   # ... and of its down_proj (the K-chunked form: intermediate size a multiple of 2048 above 4096)
         for i in range(self.L):
             p = f"model.layers.{i}."
-            l8, gu13 = {}, None
+            l8, gu13, down13 = {}, None, None
             qkv = torch.cat([mat(p + "self_attn.q_proj.weight", l8, "q"), mat(p + "self_attn.k_proj.weight", l8, "k"),
                              mat(p + "self_attn.v_proj.weight", l8, "v")], dim=0)
             has_qk = (p + "self_attn.q_norm.weight") in sd
@@ -271,6 +272,7 @@ class NativeTarget:
                 lw["down"] = ops.pack_weight(mat(p + "mlp.down_proj.weight", l8, "down"))
                 if self.x13:   # the 13-bit twin, or None where plain bf16 stays (ops.bf16x13_twin)
                     gu13 = ops.bf16x13_twin(lw["gu"], 2 * self.I, self.H, "gateup")
+                    down13 = ops.bf16x13_twin(lw["down"], self.H, self.I, "down")
                 if e8:
                     self.experts8.append(None)
             if fp8:
@@ -279,6 +281,7 @@ class NativeTarget:
                 self.layers8.append(ops.pack_layer_fp8(l8))
             self.layers.append(lw)
             self.gu13.append(gu13)
+            self.down13.append(down13)
             del qkv, l8
         self.norm = w("model.norm.weight")
         self.embed = w("model.embed_tokens.weight")
@@ -426,8 +429,9 @@ class NativeTarget:
 
     def row_layers(self, bs: int) -> list:
         """The layer dicts RowStack.run takes for a block of `bs` rows: self.layers, with the four matrices replaced by
-        their e4m3 twins when streams_fp8(bs), else a dense layer's gate/up by its 13-bit twin where it has one (gu13)."""
-        return ops.row_layers(self.layers, self.layers8, self.gu13, self.streams_fp8(bs), self._row_layers)
+        their e4m3 twins when streams_fp8(bs), else a dense layer's gate/up and down by their 13-bit twins where it has
+        them (gu13, down13)."""
+        return ops.row_layers(self.layers, self.layers8, self.gu13, self.streams_fp8(bs), self._row_layers, self.down13)
 
     def fp8_tensors(self) -> tuple:
         """Every e4m3 code tensor and scale vector of an fp8 target and of fp8 experts (empty for bf16): what a captured

@@ -99,8 +99,9 @@ typedef struct dfl_rows {
  * argument; what the e4m3 form narrows is said at each entry point.
  * DFL_EINVAL: a null descriptor, a format other than the two, DFL_W_BF16 with a scale, DFL_W_E4M3 without one.
  * ---- DFL_W_BF16X13: the packed bf16 weight in 13 bits per element, losslessly ----
- * Taken by dfl_gemm_silu_mul and dfl_gemm_argmax at K = 2048 or K = 4096 and by dfl_moe_gate_up at K = 2048 ONLY; every
- * other entry point refuses it as an unknown format. Same results as DFL_W_BF16 on the same matrix, bit for bit: the kernels rebuild the bf16 fragments in
+ * Taken by dfl_gemm_silu_mul and dfl_gemm_argmax at K = 2048 or K = 4096, by dfl_moe_gate_up at K = 2048 and by
+ * dfl_gemm_resid at K a multiple of 2048 ABOVE 4096 (the K-chunked form below) ONLY; every other entry point, and
+ * dfl_gemm_resid at any other K, refuses it as an unknown format. Same results as DFL_W_BF16 on the same matrix, bit for bit: the kernels rebuild the bf16 fragments in
  * registers from 13/16 of the bytes.  A bf16 is L = bits[7:0] and H = bits[15:8].  Per packed 16-column tile the base is
  * hb = max(0, max(H & 0x7f) - 15); an element keeps L, its sign and a 4-bit code c: c = 0 <=> (H & 0x7f) == 0 (+-0,
  * denormals, exponent 1: L is kept), c = 1..15 <=> (H & 0x7f) == hb + c.  All-zero bits decode to +0.
@@ -113,6 +114,10 @@ typedef struct dfl_rows {
  *     w * K / 512 .. of a tile.  patch: bit 31 valid, 30:28 k-step within the wave's share, 27:22 lane, 21:19 element,
  *     15:0 the bf16 itself: the ONE nonzero element of that (tile, wave) item below the window (stored with c = 0).  A
  *     matrix with two such elements in one item has no BF16X13 form and stays DFL_W_BF16.
+ *   K > 4096 (K % 2048 == 0; dfl_gemm_resid): the quads as above; the kernel walks K in nch = K / 2048 chunks and in
+ *     chunk c wave w owns k-steps (16 c + w) * 4 .. + 3 — quad 16 c + w of the tile — so an ITEM is (tile, chunk, wave),
+ *     one quad.  meta = uint32 [N / 16][nch][16][2]: the pair of (t, c, w) at index (t * nch + c) * 16 + w (nch = 1 gives
+ *     the formula above), the base repeated per (chunk, wave), the patch word's k-step field 0..3.
  * The packer is dflash_amd.ops.pack_weight_bf16x13 (tensor ops over the packed bf16 weight, once at load). */
 enum { DFL_W_BF16 = 0, DFL_W_E4M3 = 1, DFL_W_BF16X13 = 2 };
 typedef struct dfl_weight {
@@ -206,7 +211,8 @@ int dfl_gemm_sample(const dfl_weight *w, const dfl_rows *x, int V, int K, int ro
  *   tap[m][n] <- the same value (optional: a tapped target layer, model/utils.py:16-25);
  *   ss_out[n/16][m] <- sum over the tile's 16 columns of h_new^2 (optional; feeds the
  *   mode-2 row source of the next GEMM, so the RMSNorm is no launch of its own).
- * Any K: beyond 4096 the workgroup walks K in chunks itself (x must then be mode 0/1). */
+ * Any K: beyond 4096 the workgroup walks K in chunks itself (x must then be mode 0/1).
+ * DFL_W_BF16X13: K > 4096 and K % 2048 == 0 only (the K-chunked form), scale NULL; same bits as DFL_W_BF16. */
 int dfl_gemm_resid(const dfl_weight *w, const dfl_rows *x, int N, int K, void *h_io, int64_t ldh, int add_residual,
                    void *tap, int64_t ldtap, float *ss_out, const int32_t *dyn, void *stream);
 
