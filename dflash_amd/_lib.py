@@ -63,6 +63,8 @@ SIGNATURES = {
     "dfl_sample_rows": (_i, [_p, _i64, _i, _i, _u64, _f, _i, _i, _p, _i, _p, _p, _p]),
     "dfl_sample_rows_nucleus": (_i, [_p, _i64, _i64, _i, _i, _i, _i, _p, _i, _i, _i, _p, _i, _i, _p, _u64, _p, _i, _p, _f,
                                      _p, _f, _i, _i, _p, _i64, _i, _p, _p, _p]),
+    "dfl_logprob_rows": (_i, [_p, _i64, _i64, _i, _i, _i, _i, _p, _i, _i, _i, _i, _i, _p, _i64, _i, _i, _p, _p, _p, _i64, _i,
+                              _p]),
     "dfl_norm_pack": (_i, [_p, _i, _i64, _i, _i, _p, _p, _p, _p, _p, _i64, _p, _f, _p, _i, _p, _i, _p]),
     "dfl_qknorm_rope_append": (_i, [_p, _i, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _f, _p, _p, _i, _p, _p, _p, _i, _p,
                                     _i, _i, _p]),

@@ -26,7 +26,8 @@ from typing import Callable, Optional, Sequence
 import torch
 
 from . import ops
-from .generate import _bf16_table, _draw_rows, _taps, _trim, capture_graph, cuda_time, resolve_seed
+from .generate import (NO_LOGPROBS, _bf16_table, _draw_rows, _kept_cols, _taps, _trim, capture_graph, cuda_time,
+                       logprob_fields, resolve_seed)
 from .model import DFlashDraftModel
 from .target import NativeTarget
 from .tile_stack import TileStack, gemm_ws
@@ -53,7 +54,12 @@ class BatchedDecoder:
     def __init__(self, model: DFlashDraftModel, target: NativeTarget, n_requests: int, max_rows: int,
                  out_len: int, mask_token_id: int, stop_token_ids=None, max_splits: int = 32,
                  temperature: float = 0.0, tiles_per_request: int = 1, sampler: str = "torch",
-                 draft_temperature: float = 0.0, filtering: bool = False, request_temperature: bool = False):
+                 draft_temperature: float = 0.0, filtering: bool = False, request_temperature: bool = False,
+                 logprobs: Optional[int] = None):
+        """logprobs = N (None: off; fixed here, it fixes the captured launch sequence): every verify materialises its
+        logits and dfl_logprob_rows scatters the log-probability of each committed token, and the top N alternatives, to
+        the token's position in the slot's row of self.lp."""
+        logprobs = ops.check_logprobs(logprobs)
         if not isinstance(target, NativeTarget):
             raise TypeError("BatchedDecoder needs a dflash_amd.NativeTarget (see module docstring)")
         if tiles_per_request not in (1, 2):
@@ -121,7 +127,8 @@ class BatchedDecoder:
         self.inv_ts = z(NREQ, dt=F32) if self.request_temperature else None
         self.filtering = bool(filtering) and (self.temperature >= 1e-5 or self.request_temperature)
         self.top_k, self.top_p = z(NREQ, dt=I32), torch.ones(NREQ, dtype=F32, device=dev)
-        if self.filtering:
+        self.lp = ops.logprob_sink(NREQ, out_len, logprobs, dev) if logprobs is not None else None
+        if self.filtering or self.lp is not None:
             self._logits = z(MT, 16, target.V)
         self.output_ids = torch.full((NREQ, out_len), self.mask_id, dtype=I64, device=dev)
         self.stop_t = torch.tensor(stop_token_ids, dtype=I64, device=dev) if stop_token_ids else None
@@ -231,6 +238,9 @@ class BatchedDecoder:
                      else sample(out.logits, 0.0))
         else:
             first = sample(out.logits, temperature)
+        if self.lp is not None:   # the first token's value, from the prompt's last-row logits: nothing is read back
+            sink = SimpleNamespace(**{**vars(self.lp), "slot": r})
+            ops.logprob_rows(out.logits[0, -1:].to(BF16).contiguous(), first.reshape(1), sink, pos_base=P)
         # the slot's filter, re-armed on every admission (0 / 1.0: off); two small fills, admissions are never captured
         self.top_k[r:r + 1].fill_(flt["top_k"] if flt else 0)
         self.top_p[r:r + 1].fill_(flt["top_p"] if flt else 1.0)
@@ -405,6 +415,7 @@ class BatchedDecoder:
                tap_layers=self.model.target_layer_ids, moe=t.moe_mlp_tiles)
         st.finish(t.norm)
         lm = self._t_head()
+        lg = self._logits if self.lp is not None else None   # logprobs: every head below materialises its logits
         if self.request_temperature and self.filtering:   # greedy slots keep the argmax ids the first launch wrote
             ops.gemm_argmax_batch(lm, s["xn"], R, t.V, H, 0, 16, self.gws, self.post.view(-1, 16), 0, dyn_t,
                                   nrows_dyn_word=ops.DYN_BS, logits=self._logits)
@@ -414,10 +425,10 @@ class BatchedDecoder:
         elif self.request_temperature:   # the fused draw at each slot's own invT; a greedy slot takes the plain argmax
             ops.gemm_sample_batch(lm, s["xn"], R, t.V, H, 0, 16, self.gws, self.post.view(-1, 16), 0, dyn_t,
                                   seeds=self.seeds, inv_ts=self.inv_ts, pos_word=ops.DYN_POS0, pos_add=1,
-                                  tiles_per_req=TPR, nrows_dyn_word=ops.DYN_BS)
+                                  tiles_per_req=TPR, nrows_dyn_word=ops.DYN_BS, logits=lg)
         elif self.temperature < 1e-5:
             ops.gemm_argmax_batch(lm, s["xn"], R, t.V, H, 0, 16, self.gws, self.post.view(-1, 16), 0, dyn_t,
-                                  nrows_dyn_word=ops.DYN_BS)
+                                  nrows_dyn_word=ops.DYN_BS, logits=lg)
         elif self.filtering:   # materialise, then the filtered draw: tile j row m -> start + 16 j + m + 1
             ops.gemm_argmax_batch(lm, s["xn"], R, t.V, H, 0, 16, self.gws, self.post.view(-1, 16), 0, dyn_t,
                                   nrows_dyn_word=ops.DYN_BS, logits=self._logits)
@@ -427,7 +438,7 @@ class BatchedDecoder:
         elif self.sampler == "device":   # the seeded draw in the lm_head epilogue: tile j row m -> start + 16 j + m + 1
             ops.gemm_sample_batch(lm, s["xn"], R, t.V, H, 0, 16, self.gws, self.post.view(-1, 16), 0, dyn_t,
                                   seeds=self.seeds, temperature=self.temperature, pos_word=ops.DYN_POS0, pos_add=1,
-                                  tiles_per_req=TPR, nrows_dyn_word=ops.DYN_BS)
+                                  tiles_per_req=TPR, nrows_dyn_word=ops.DYN_BS, logits=lg)
         else:
             # T > 0 (model/utils.py:30-34): the same GEMM materialises the bf16 logits and the
             # reference's own softmax + torch.multinomial draws the posterior (caller's RNG stream;
@@ -437,6 +448,10 @@ class BatchedDecoder:
             ops.gemm_argmax_batch(lm, s["xn"], R, t.V, H, 0, 16, self.gws, self.post, 0, dyn_t,
                                   nrows_dyn_word=ops.DYN_BS, logits=self._logits)
             self.post[:R] = sample(self._logits[:R], self.temperature)
+        if self.lp is not None:   # behind whichever branch wrote the posterior, before the accept launch moves POS0:
+            # tile j row m of a slot commits (if accepted) at position POS0 + 16 j + m + 1
+            ops.logprob_rows(self._logits[:R], self.post.view(-1, 16), self.lp, dyn=dyn_t, nrows_dyn_word=ops.DYN_BS,
+                             pos_word=ops.DYN_POS0, pos_add=1, tiles_per_req=TPR)
 
     def _accept_launch(self) -> None:
         ops.accept_commit_batch(self.block, self.post, self.R, self.output_ids, self.dyn_d, self.dyn_t, self.stop_t,
@@ -595,7 +610,7 @@ def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_i
                           mask_token_id: int, max_new_tokens: int, block_size: int, stop_token_ids,
                           temperature=0.0, draft_token_hook: Optional[Callable] = None,
                           group_size: int = MAX_GROUP, hook_block_view: bool = False, sampler: str = "torch",
-                          seed=None, top_k=0, top_p=1.0) -> list:
+                          seed=None, top_k=0, top_p=1.0, logprobs: Optional[int] = None) -> list:
     """`dflash_generate` (benchmark.py:44-251) for a list of prompts: requests run in
     groups of `group_size` <= 4 (<= 2 with block sizes of 17..32 rows) that share the weight stream; returns one namespace per
     prompt with the fields of benchmark.py:242-251 (timing fields are the group's).
@@ -605,7 +620,9 @@ def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_i
     emits, however the group is formed.
     top_k / top_p: a scalar, or one value per prompt (0 / 1.0: off), as in dflash_generate.
     temperature: one float, or one value per prompt; values that differ need sampler="device" and run every group through
-    a decoder built with request_temperature=True ("Per-request temperature")."""
+    a decoder built with request_temperature=True ("Per-request temperature").
+    logprobs: as dflash_generate, for every prompt (the fields logprobs / top_logprob_ids / top_logprobs; None when off)."""
+    logprobs = ops.check_logprobs(logprobs)
     temps, per_request = _prompt_temperatures(temperature, len(input_ids), sampler)
     seeds = _prompt_seeds(sampler, seed, len(input_ids), any(t >= 1e-5 for t in temps))
     top_ks, top_ps, filtering = _prompt_filters(top_k, top_p, len(input_ids), temps, sampler)
@@ -623,7 +640,7 @@ def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_i
         dec = BatchedDecoder(model, target, len(idx), max_rows=pmax + max_new_tokens + 3 * 16 * tpr,
                              out_len=pmax + max_new_tokens + 16 * tpr, mask_token_id=mask_token_id,
                              stop_token_ids=stop_token_ids, temperature=max(temps[i] for i in idx), tiles_per_request=tpr,
-                             sampler=sampler, filtering=filtering, request_temperature=per_request)
+                             sampler=sampler, filtering=filtering, request_temperature=per_request, logprobs=logprobs)
         t0 = cuda_time()
         for r, p in enumerate(prompts):
             dec.admit(r, p, temps[idx[r]], seed=seeds[idx[r]], top_k=top_ks[idx[r]], top_p=top_ps[idx[r]])
@@ -663,9 +680,11 @@ def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_i
         for r, i in enumerate(idx):
             ids = _trim(dec.output_ids[r:r + 1], max_len[r], mask_token_id, stop_token_ids, dec.n_in[r])
             n_out = ids.shape[1] - dec.n_in[r]
+            lpf = NO_LOGPROBS if dec.lp is None else logprob_fields(
+                dec.lp, r, _kept_cols(dec.output_ids[r:r + 1], max_len[r], mask_token_id, stop_token_ids, dec.n_in[r])[dec.n_in[r]:])
             results[i] = SimpleNamespace(output_ids=ids.clone(), num_input_tokens=dec.n_in[r], num_output_tokens=n_out,
                                          time_to_first_token=ttft, time_per_output_token=decode_s / max(1, n_out),
-                                         acceptance_lengths=taus[r], cycle_trace=[], profile_summary=None)
+                                         acceptance_lengths=taus[r], cycle_trace=[], profile_summary=None, **lpf)
         del dec
     return results
 

@@ -16,7 +16,7 @@ import torch
 
 from . import ops
 from .batch import MAX_GROUP, BatchedDecoder, _prompt_filters, _prompt_seeds, _prompt_temperatures
-from .generate import _trim, cuda_time
+from .generate import NO_LOGPROBS, _kept_cols, _trim, cuda_time, logprob_fields
 from .slots import SlotLoop
 
 BLOCK_ROWS = 16   # rows of a slot's tile: the margins below are the ones dflash_generate_batch sizes its decoder with
@@ -100,11 +100,15 @@ class _DecoderDriver:
         n_out = ids.shape[1] - req.n_in
         decode_s = cuda_time() - p.t_admitted
         self.hooks[slot] = None
+        # logprobs: the positions the ids keep, [n_in, n_in + n_out) of the slot's row — each written by THIS request (its
+        # admission, then the cycle that committed the position), so nothing of the slot's previous request shows
+        lpf = NO_LOGPROBS if d.lp is None else logprob_fields(
+            d.lp, slot, _kept_cols(d.output_ids[slot:slot + 1], req.max_len, d.mask_id, self.stop_token_ids, req.n_in)[req.n_in:])
         p.result = SimpleNamespace(output_ids=ids, num_input_tokens=req.n_in, num_output_tokens=n_out,
                                    time_to_first_token=p.ttft, time_per_output_token=decode_s / max(1, n_out),
                                    acceptance_lengths=req.taus, cycle_trace=[], profile_summary=None,
                                    request_id=req.rid, slot=slot, admitted_step=req.admitted_step,
-                                   finished_step=req.finished_step)
+                                   finished_step=req.finished_step, **lpf)
 
 
 class BatchEngine:
@@ -118,8 +122,11 @@ class BatchEngine:
 
     def __init__(self, model, target, *, slots: int = MAX_GROUP, max_rows: int, out_len: int, mask_token_id: int,
                  block_size: int = 16, stop_token_ids=None, temperature: float = 0.0, sampler: str = "torch",
-                 graph: Optional[bool] = None, filtering: bool = False, request_temperature: bool = False):
-        """filtering: requests may carry top_k / top_p (submit); fixed here because it fixes the captured launch sequence
+                 graph: Optional[bool] = None, filtering: bool = False, request_temperature: bool = False,
+                 logprobs: Optional[int] = None):
+        """logprobs = N (None: off): every result carries logprobs / top_logprob_ids / top_logprobs as dflash_generate
+        returns them; fixed here, one capture per engine — there is no per-request switch.
+        filtering: requests may carry top_k / top_p (submit); fixed here because it fixes the captured launch sequence
         ("Filtered draw").  Unfiltered requests of such an engine emit the same ids.
         request_temperature: requests may carry their own temperature (submit), greedy and sampled ones sharing the
         weight pass and the one capture; fixed here for the same reason, needs sampler='device' (DESIGN.md section 8,
@@ -140,7 +147,7 @@ class BatchEngine:
         self.use_graph = bool(graph)
         self.dec = BatchedDecoder(model, target, slots, max_rows=max_rows, out_len=out_len, mask_token_id=mask_token_id,
                                   stop_token_ids=stop_token_ids, temperature=temperature, sampler=sampler,
-                                  filtering=filtering, request_temperature=request_temperature)
+                                  filtering=filtering, request_temperature=request_temperature, logprobs=logprobs)
         self.filtering, self.temperature = bool(filtering), float(temperature)
         self.request_temperature = bool(request_temperature)
         self.stats = dict(group_cycles=0, live_slot_cycles=0, admissions=0, replayed_cycles=0, admit_s=0.0, captures=0,
@@ -195,14 +202,15 @@ class BatchEngine:
 def dflash_generate_stream(model, target, input_ids: Sequence[torch.Tensor], mask_token_id: int,
                            max_new_tokens: Union[int, Sequence[int]], block_size: int, stop_token_ids,
                            temperature=0.0, *, slots: int = MAX_GROUP, draft_token_hook: Optional[Callable] = None,
-                           sampler: str = "torch", seed=None, top_k=0, top_p=1.0) -> list:
+                           sampler: str = "torch", seed=None, top_k=0, top_p=1.0,
+                           logprobs: Optional[int] = None) -> list:
     """`dflash_generate_batch` with slot refill: one namespace per prompt with the fields of benchmark.py:242-251, each
     request emitting what its own `dflash_generate` run emits.  max_new_tokens: one int or one per prompt.
     draft_token_hook(request_index, block_view, start, call).  seed as in dflash_generate_batch (an int s gives prompt i
     the seed s + i).  time_to_first_token is the request's own admission; time_per_output_token its own decode wall
     time, admission to last token, over its tokens.  top_k / top_p: a scalar or one value per prompt.
     temperature: one float, or one value per prompt (values that differ: sampler="device", an engine built with
-    request_temperature=True)."""
+    request_temperature=True).  logprobs: as dflash_generate, for every prompt."""
     n = len(input_ids)
     mnt = [int(max_new_tokens)] * n if isinstance(max_new_tokens, int) else [int(x) for x in max_new_tokens]
     if len(mnt) != n:
@@ -217,7 +225,7 @@ def dflash_generate_stream(model, target, input_ids: Sequence[torch.Tensor], mas
     eng = BatchEngine(model, target, slots=max(1, min(slots, max(n, 1))), max_rows=need + 3 * BLOCK_ROWS,
                       out_len=need + BLOCK_ROWS, mask_token_id=mask_token_id, block_size=block_size,
                       stop_token_ids=stop_token_ids, temperature=max(temps, default=0.0), sampler=sampler, filtering=filtering,
-                      request_temperature=per_request)
+                      request_temperature=per_request, logprobs=logprobs)
     for i, p in enumerate(input_ids):
         hook = (lambda blk, start, call, i=i: draft_token_hook(i, blk, start, call)) if draft_token_hook else None
         eng.submit(p, mnt[i], seed=seeds[i], draft_token_hook=hook, top_k=top_ks[i], top_p=top_ps[i],

@@ -162,6 +162,30 @@ def _trim(output_ids, max_length, mask_token_id, stop_token_ids, n_in):
     return output_ids
 
 
+def _kept_cols(output_ids, max_length, mask_token_id, stop_token_ids, n_in):
+    """The columns of output_ids that _trim keeps, as indices: what trims a per-position buffer exactly as the ids."""
+    cols = (output_ids[0, :max_length] != mask_token_id).nonzero(as_tuple=True)[0]
+    if stop_token_ids is not None:
+        st = torch.tensor(stop_token_ids, device=output_ids.device)
+        idx = torch.isin(output_ids[0, cols][n_in:], st).nonzero(as_tuple=True)[0]
+        if idx.numel() > 0:
+            cols = cols[: n_in + idx[0] + 1]
+    return cols
+
+
+def logprob_fields(sink, row: int, cols: torch.Tensor) -> dict:
+    """The three result fields of a request whose generated tokens sit at positions `cols` of the sink's row: logprobs
+    fp32 [n], top_logprob_ids int64 [n, N], top_logprobs fp32 [n, N] (N = 0: empty second axis)."""
+    n, N = cols.numel(), sink.n_top
+    dev = sink.lp.device
+    return dict(logprobs=sink.lp[row, cols].clone(),
+                top_logprob_ids=sink.top_ids[row, cols].clone() if N else torch.empty(n, 0, dtype=torch.long, device=dev),
+                top_logprobs=sink.top_lp[row, cols].clone() if N else torch.empty(n, 0, dtype=torch.float32, device=dev))
+
+
+NO_LOGPROBS = dict(logprobs=None, top_logprob_ids=None, top_logprobs=None)
+
+
 class DecodeSession:
     """State of one request between cycles (what the reference keeps in local
     variables of its while-loop, model/dflash.py:206-233)."""
@@ -169,7 +193,13 @@ class DecodeSession:
     def __init__(self, model, target, input_ids: torch.Tensor, *, mask_token_id: int, max_new_tokens: int,
                  max_block_size: int, stop_token_ids, temperature: float, draft_temperature: float = 0.0,
                  draft_token_hook: Optional[Callable] = None, sampler: str = "torch", seed: Optional[int] = None,
-                 top_k: int = 0, top_p: float = 1.0):
+                 top_k: int = 0, top_p: float = 1.0, logprobs: Optional[int] = None):
+        from .target import NativeTarget
+        # logprobs = N (None: off): per position of output_ids the log-probability of the committed token and the top N
+        # alternatives, scattered there by dfl_logprob_rows behind every verify's posterior
+        self.logprobs = ops.check_logprobs(logprobs)
+        if self.logprobs is not None and not isinstance(target, NativeTarget):
+            raise ValueError("logprobs needs a dflash_amd.NativeTarget (the kernel reads the verify's materialised logits)")
         dev = model.device
         if not input_ids.is_cuda:
             raise RuntimeError("dflash_amd: input_ids must be on the GPU")
@@ -200,8 +230,9 @@ class DecodeSession:
         self.max_length = self.n_in + max_new_tokens
         self.output_ids = torch.full((1, self.max_length + self.max_bs), mask_token_id, dtype=torch.long, device=dev)
         self.position_ids = torch.arange(self.output_ids.shape[1], device=dev).unsqueeze(0)
-        from .target import NativeTarget
         self.native = isinstance(target, NativeTarget)
+        self.lp = (ops.logprob_sink(1, self.output_ids.shape[1], self.logprobs, dev) if self.logprobs is not None else None)
+        self._lpkw = {} if self.lp is None else dict(logprobs=self.lp)
         self.tcache = (target.new_cache(self.max_length + 2 * self.max_bs) if self.native
                        else _new_target_cache(target))
         self.use_draft = self.max_bs > 1
@@ -269,6 +300,9 @@ class DecodeSession:
                                                                      self.n_in, self._filter)
         else:
             self.output_ids[:, self.n_in:self.n_in + 1] = sample(out.logits, self.temperature)
+        if self.lp is not None:   # the first new token, from the prompt's last-row logits
+            ops.logprob_rows(out.logits[0, -1:].to(torch.bfloat16).contiguous(), self.output_ids[0, self.n_in:self.n_in + 1],
+                             self.lp, pos_base=self.n_in)
         if self.use_draft:
             self.target_hidden = _taps(out.hidden_states, self.model.target_layer_ids)
 
@@ -385,7 +419,7 @@ class DecodeSession:
             posterior, taps = self.target.verify(
                 blk[0], start, self.tcache, temperature=self.temperature,
                 tap_layers=self.model.target_layer_ids if (want_hidden and self.use_draft) else (),
-                taps_out=self.taps_buf, seed=self._tseed, **self._fkw)
+                taps_out=self.taps_buf, seed=self._tseed, **self._fkw, **self._lpkw)
             self._mark("target", 1)
         else:
             out = self.target(blk, position_ids=self.position_ids[:, start:start + bs],
@@ -514,7 +548,7 @@ class DecodeSession:
 
         def verify_accept(bs):   # (a T > 0 draw takes its positions from the target record's POS0 word: fresh every replay)
             post, _ = t.verify(self.block[0, :bs], bound, self.tcache, temperature=self.temperature, tap_layers=tl,
-                               taps_out=self.taps_buf, dyn_lengths=True, seed=self._tseed, **self._fkw)
+                               taps_out=self.taps_buf, dyn_lengths=True, seed=self._tseed, **self._fkw, **self._lpkw)
             ops.accept_commit(self.block[0, :bs], post[0].contiguous(), bs, self.output_ids[0], self.dyn, self.stop_t,
                               self.result, rearm=(self.block[0], self.max_bs, self.mask_token_id), dyn_t=self.tcache.dyn)
 
@@ -524,7 +558,8 @@ class DecodeSession:
         return _Replay(graphs, bound, (m._rope[0].data_ptr(), t._rope[0].data_ptr()),
                        (m._rope, t._rope, getattr(m, "ws", None), getattr(t, "ws", None), getattr(t, "_taps", None),
                         self.lm_wp, self.lm_wp8, self.embed_w, getattr(t, "lm_wp", None),
-                        t.fp8_tensors() if self.native else ()))   # (an fp8 target's codes and scale vectors)
+                        t.fp8_tensors() if self.native else (),    # (an fp8 target's codes and scale vectors)
+                        getattr(t, "_nuc_logits", None)))          # (the logits a filtered or logprobs verify materialises)
 
     def _tables_moved(self, rec: _Replay) -> bool:
         """A shared draft model / NativeTarget replaces its RoPE table when another caller needs more positions
@@ -649,6 +684,14 @@ class DecodeSession:
     def finish(self) -> torch.Tensor:
         return _trim(self.output_ids, self.max_length, self.mask_token_id, self.stop_token_ids, self.n_in)
 
+    def finish_logprobs(self) -> dict:
+        """The result fields logprobs / top_logprob_ids / top_logprobs, trimmed exactly as finish() trims the ids (all
+        None with logprobs off)."""
+        if self.lp is None:
+            return dict(NO_LOGPROBS)
+        cols = _kept_cols(self.output_ids, self.max_length, self.mask_token_id, self.stop_token_ids, self.n_in)
+        return logprob_fields(self.lp, 0, cols[self.n_in:])
+
 
 @torch.inference_mode()
 def run_decode(model, target, input_ids: torch.Tensor, *, mask_token_id: int, max_new_tokens: int,
@@ -656,11 +699,12 @@ def run_decode(model, target, input_ids: torch.Tensor, *, mask_token_id: int, ma
                draft_steps: int = 1, collect_profile: bool = False, scheduler=None,
                draft_temperature: float = 0.0, draft_token_hook: Optional[Callable] = None,
                max_block_size: Optional[int] = None, sampler: str = "torch", seed: Optional[int] = None,
-               top_k: int = 0, top_p: float = 1.0) -> SimpleNamespace:
+               top_k: int = 0, top_p: float = 1.0, logprobs: Optional[int] = None) -> SimpleNamespace:
     s = DecodeSession(model, target, input_ids, mask_token_id=mask_token_id, max_new_tokens=max_new_tokens,
                       max_block_size=max_block_size or block_size, stop_token_ids=stop_token_ids,
                       temperature=temperature, draft_temperature=draft_temperature,
-                      draft_token_hook=draft_token_hook, sampler=sampler, seed=seed, top_k=top_k, top_p=top_p)
+                      draft_token_hook=draft_token_hook, sampler=sampler, seed=seed, top_k=top_k, top_p=top_p,
+                      logprobs=logprobs)
     t_prefill = cuda_time()
     s.prefill()
     time_to_first_token = cuda_time() - t_prefill
@@ -771,7 +815,7 @@ def run_decode(model, target, input_ids: torch.Tensor, *, mask_token_id: int, ma
                            acceptance_lengths=taus, used_block_sizes=used_bs, l_gen=lgens,
                            cycle_trace=cycle_trace, profile_summary=profile_summary, replayed_cycles=replayed,
                            replayed_flags=replayed_flags,
-                           seed=s.seed)
+                           seed=s.seed, **s.finish_logprobs())
 
 
 def _draft_ids(model, hid_frag, lm_wp, bs, blk, draft_temperature, keep_logits=None, seed=None, dyn=None, start=None,
@@ -825,28 +869,35 @@ def _resolve_profile(cycle_trace, ttft, decode_wall):
 def dflash_generate(model, target, input_ids: torch.Tensor, mask_token_id: int, max_new_tokens: int,
                     block_size: int, stop_token_ids, temperature: float = 0.0, collect_profile: bool = False,
                     draft_steps: int = 1, draft_token_hook=None, sampler: str = "torch",
-                    seed: Optional[int] = None, top_k: int = 0, top_p: float = 1.0) -> SimpleNamespace:
+                    seed: Optional[int] = None, top_k: int = 0, top_p: float = 1.0,
+                    logprobs: Optional[int] = None) -> SimpleNamespace:
     """benchmark.py:44-55 signature; returns the namespace of :242-251 (+ replayed_cycles).
+    logprobs (None: off; needs a NativeTarget): 0 adds the field `logprobs` fp32 [num_output_tokens], the
+    log-probability of every generated token under the target's RAW distribution (log_softmax of its logits at T = 1,
+    unfiltered, whatever temperature and filter drew the token); 1..8 add `top_logprob_ids` / `top_logprobs`
+    [num_output_tokens, N], the N most likely tokens at each position.  Off: the fields are None.
     sampler="device": T > 0 draws are seeded on the device — the same seed gives the same tokens
     however the request runs, and the cycles can be replayed from hipGraphs; seed=None draws one from torch's RNG.
     top_k / top_p (0 / 1.0: off) restrict the target's seeded draw (section 8, "Filtered draw"); sampler="device" only."""
     if getattr(model, "wide_hidden", False):
         return _generate_wide_hidden(model, target, input_ids, mask_token_id, max_new_tokens, block_size, stop_token_ids,
-                                     temperature, collect_profile, draft_steps, draft_token_hook, sampler, seed, top_k, top_p)
+                                     temperature, collect_profile, draft_steps, draft_token_hook, sampler, seed, top_k, top_p,
+                                     logprobs)
     r = run_decode(model, target, input_ids, mask_token_id=mask_token_id, max_new_tokens=max_new_tokens,
                    block_size=block_size, stop_token_ids=stop_token_ids, temperature=temperature, clamp_tail=True,
                    draft_steps=draft_steps, collect_profile=collect_profile, draft_token_hook=draft_token_hook,
-                   sampler=sampler, seed=seed, top_k=top_k, top_p=top_p)
+                   sampler=sampler, seed=seed, top_k=top_k, top_p=top_p, logprobs=logprobs)
     return SimpleNamespace(output_ids=r.output_ids, num_input_tokens=r.num_input_tokens,
                            num_output_tokens=r.num_output_tokens, time_to_first_token=r.time_to_first_token,
                            time_per_output_token=r.time_per_output_token, acceptance_lengths=r.acceptance_lengths,
                            cycle_trace=r.cycle_trace, profile_summary=r.profile_summary,
-                           replayed_cycles=r.replayed_cycles)
+                           replayed_cycles=r.replayed_cycles, logprobs=r.logprobs, top_logprob_ids=r.top_logprob_ids,
+                           top_logprobs=r.top_logprobs)
 
 
 def _generate_wide_hidden(model, target, input_ids, mask_token_id, max_new_tokens, block_size, stop_token_ids, temperature,
                           collect_profile=False, draft_steps=1, draft_token_hook=None, sampler="torch",
-                          seed=None, top_k=0, top_p=1.0) -> SimpleNamespace:
+                          seed=None, top_k=0, top_p=1.0, logprobs=None) -> SimpleNamespace:
     """hidden_size > 4096: the request runs as a group of ONE through the ragged-batch kernels (their GEMMs cut K over
     workgroups; the single-request kernels keep a whole K = hidden row slice per workgroup).  Same loop semantics
     (benchmark.py:44-251, tail clamp included); no per-cycle profile, one draft step per cycle."""
@@ -860,14 +911,16 @@ def _generate_wide_hidden(model, target, input_ids, mask_token_id, max_new_token
     hook = (lambda r, blk, start, call: draft_token_hook(blk, start, call)) if draft_token_hook else None
     return dflash_generate_batch(model, target, [input_ids], mask_token_id, max_new_tokens, block_size, stop_token_ids,
                                  temperature, draft_token_hook=hook, group_size=1, hook_block_view=True, sampler=sampler,
-                                 seed=None if seed is None else [seed], top_k=top_k, top_p=top_p)[0]
+                                 seed=None if seed is None else [seed], top_k=top_k, top_p=top_p, logprobs=logprobs)[0]
 
 
 def dflash_generate_policy(*, model, target, input_ids: torch.Tensor, mask_token_id: int, max_new_tokens: int,
                            stop_token_ids, temperature: float, fixed_block_size: Optional[int] = None,
                            scheduler=None, draft_token_hook=None, sampler: str = "torch",
-                           seed: Optional[int] = None, top_k: int = 0, top_p: float = 1.0) -> SimpleNamespace:
+                           seed: Optional[int] = None, top_k: int = 0, top_p: float = 1.0,
+                           logprobs: Optional[int] = None) -> SimpleNamespace:
     """benchmark_dynamic_schedule.py:260-272 signature; returns the namespace of :425-434 (+ replayed_cycles).
+    logprobs: as dflash_generate (the fields logprobs / top_logprob_ids / top_logprobs; None when off).
     sampler / seed: as dflash_generate; the draft's own T > 0 draw uses the same seed on a stream of its own.
     top_k / top_p: as dflash_generate (the target's draw; the draft's own draw stays unfiltered)."""
     if fixed_block_size is None and scheduler is None:
@@ -877,7 +930,8 @@ def dflash_generate_policy(*, model, target, input_ids: torch.Tensor, mask_token
     r = run_decode(model, target, input_ids, mask_token_id=mask_token_id, max_new_tokens=max_new_tokens,
                    block_size=max_bs, stop_token_ids=stop_token_ids, temperature=temperature, clamp_tail=True,
                    scheduler=sched, draft_temperature=temperature, max_block_size=max_bs,
-                   draft_token_hook=draft_token_hook, sampler=sampler, seed=seed, top_k=top_k, top_p=top_p)
+                   draft_token_hook=draft_token_hook, sampler=sampler, seed=seed, top_k=top_k, top_p=top_p,
+                   logprobs=logprobs)
     if fixed_block_size is not None:
         for row in r.cycle_trace:
             for k in ("tau_hat", "cycle_hat", "score_hat", "current_block_size", "adl_lgen_hat", "adl_lacc_hat",
@@ -887,7 +941,8 @@ def dflash_generate_policy(*, model, target, input_ids: torch.Tensor, mask_token
                            num_output_tokens=r.num_output_tokens, time_to_first_token=r.time_to_first_token,
                            time_per_output_token=r.time_per_output_token, acceptance_lengths=r.acceptance_lengths,
                            used_block_sizes=r.used_block_sizes, cycle_trace=r.cycle_trace,
-                           replayed_cycles=r.replayed_cycles)
+                           replayed_cycles=r.replayed_cycles, logprobs=r.logprobs, top_logprob_ids=r.top_logprob_ids,
+                           top_logprobs=r.top_logprobs)
 
 
 class _Fixed:

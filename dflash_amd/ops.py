@@ -5,6 +5,7 @@ raw pointers.  Everything raises on a non-CUDA tensor — there is no host path.
 """
 from __future__ import annotations
 
+from types import SimpleNamespace
 from typing import NamedTuple, Optional
 
 import torch
@@ -611,6 +612,72 @@ def sample_rows_nucleus(logits: torch.Tensor, *, temperature: Optional[float] = 
                                         _p(out, I64, "out"), out_stride, out_off, _p(thresholds, F32, "thresholds"),
                                         _p(kept, I32, "kept"), _stream()), "dfl_sample_rows_nucleus")
     return out
+
+
+MAX_TOP_LOGPROBS = 8
+
+
+def check_logprobs(logprobs) -> Optional[int]:
+    """Validate a `logprobs` keyword: None (off), 0 (the chosen token only) or 1..8 (that many alternatives too)."""
+    if logprobs is None:
+        return None
+    if isinstance(logprobs, bool) or int(logprobs) != logprobs or not 0 <= int(logprobs) <= MAX_TOP_LOGPROBS:
+        raise ValueError(f"dflash_amd: logprobs must be None or an integer 0..{MAX_TOP_LOGPROBS}, got {logprobs!r}")
+    return int(logprobs)
+
+
+def logprob_sink(slots: int, length: int, n_top: int, device) -> SimpleNamespace:
+    """The buffers dfl_logprob_rows scatters into by position, one row of `length` positions per request slot: lp fp32
+    [slots, length], and for n_top > 0 top_ids int64 / top_lp fp32 [slots, length, n_top] (else None).  `slot`: the row
+    a single-request verify writes.  Unwritten positions hold NaN / -1."""
+    n_top = check_logprobs(n_top)
+    lp = torch.full((slots, length), float("nan"), dtype=F32, device=device)
+    top_ids = torch.full((slots, length, n_top), -1, dtype=I64, device=device) if n_top else None
+    top_lp = torch.full((slots, length, n_top), float("nan"), dtype=F32, device=device) if n_top else None
+    return SimpleNamespace(lp=lp, top_ids=top_ids, top_lp=top_lp, n_top=n_top, slot=0)
+
+
+def logprob_rows(logits: torch.Tensor, ids: torch.Tensor, sink, *, ids_off: int = 0, row0: int = 0,
+                 nrows: Optional[int] = None, dyn=None, nrows_dyn_word: int = -1, pos_word: int = -1, pos_base: int = 0,
+                 pos_add: int = 0, tiles_per_req: int = 1) -> None:
+    """Log-probabilities of the ids a verify commits (dfl_logprob_rows) over materialised bf16
+    logits [rows <= 16, V] (one tile) or [tiles, 16, V], unit inner stride: log_softmax of the raw logits, at T = 1 and
+    unfiltered.  ids int64: [tiles, n] or, for one tile, [n]; tile t row m takes ids[t, ids_off + m - row0].  Rows of a
+    tile as in sample_rows_nucleus.  Tile t (tile j = t % tiles_per_req of slot q = t // tiles_per_req) row m writes at
+    position (dyn[t][pos_word] if pos_word >= 0 else pos_base) + pos_add + 16 j + m of the sink's row sink.slot + q:
+    sink.lp, and sink.top_ids / sink.top_lp when sink.n_top > 0 (logprob_sink); positions outside a row are dropped."""
+    assert logits.dim() in (2, 3) and logits.stride(-1) == 1 and logits.is_cuda and logits.dtype == BF16
+    if logits.dim() == 2:
+        assert logits.shape[0] <= 16, "one tile holds at most 16 rows"
+        tiles, tile_rows, tile_stride = 1, logits.shape[0], 16 * logits.stride(0)
+    else:
+        assert logits.shape[1] == 16
+        tiles, tile_rows, tile_stride = logits.shape[0], 16, logits.stride(0)
+    V, ld = logits.shape[-1], logits.stride(-2)
+    if nrows is None:
+        nrows = tile_rows - row0
+    assert 0 <= row0 and row0 + nrows <= tile_rows or nrows_dyn_word >= 0 and tile_rows == 16
+    n_ids = 16 - row0 if nrows_dyn_word >= 0 else nrows
+    assert ids.dim() in (1, 2) and ids.stride(-1) == 1 and ids.shape[-1] >= ids_off + n_ids, "ids"
+    assert ids.dim() == 2 and ids.shape[0] >= tiles or tiles == 1, "ids"
+    ids_stride = ids.stride(0) if ids.dim() == 2 else 0
+    if dyn is not None:
+        assert dyn.numel() >= 8 * tiles
+    slots = (tiles + tiles_per_req - 1) // tiles_per_req
+    lp, n_top = sink.lp, sink.n_top
+    assert lp.dim() == 2 and lp.is_contiguous() and 0 <= sink.slot and sink.slot + slots <= lp.shape[0], "sink.lp"
+    length = lp.shape[1]
+    tid = tlp = None
+    if n_top:
+        for o in (sink.top_ids, sink.top_lp):
+            assert o is not None and o.shape == (lp.shape[0], length, n_top) and o.is_contiguous(), "sink.top_ids / top_lp"
+        tid, tlp = sink.top_ids[sink.slot:], sink.top_lp[sink.slot:]
+    if ids.dtype != I64 or not ids.is_cuda:
+        raise TypeError("dflash_amd: ids must be an int64 GPU tensor")
+    check(lib().dfl_logprob_rows(logits.data_ptr(), ld, tile_stride, tiles, V, row0, nrows, _p(dyn, I32, "dyn"),
+                                 nrows_dyn_word, pos_word, pos_base, pos_add, tiles_per_req, ids.data_ptr(), ids_stride,
+                                 ids_off, n_top, _p(lp[sink.slot:], F32, "sink.lp"), _p(tid, I64, "sink.top_ids"),
+                                 _p(tlp, F32, "sink.top_lp"), length, length, _stream()), "dfl_logprob_rows")
 
 
 def gemm_resid(wp, x, N: int, K: int, h_io: torch.Tensor, *, add_residual: bool, ss_out=None, tap=None,

@@ -708,7 +708,7 @@ class NativeTarget:
         return self._nuc_logits
 
     def _verify_wide(self, block_ids, start, cache, bs, tap_layers, taps, logits_out, temperature, cos, sin, seed=None,
-                     flt=None):
+                     flt=None, logprobs=None):
         """Blocks of 17..32 rows in ONE pass over the weights: the two 16-row tiles go through the ragged-batch
         GEMMs (tile_stack.TileStack, R = 2) as if they were two requests, and through ONE attention launch per layer with
         two query tiles on the request's single cache.  Same lines as verify(): model/dflash.py:249-257."""
@@ -736,6 +736,13 @@ class NativeTarget:
                taps=None if taps is None else taps.view(2, 16, -1), tap_layers=tap_layers, moe=self.moe_mlp_tiles)
         st.finish(self.norm)
         post = ws["post"]
+        if logprobs is not None and logits_out is None:   # the head launch below materialises the block's logits
+            logits_out = self._nucleus_logits()
+
+        def lp_rows(logits, ids):   # tile j row m -> position start + 16 j + m + 1, both tiles of the one request
+            ops.logprob_rows(logits.view(2, 16, self.V), ids.view(2, 16), logprobs, dyn=dyn2, nrows_dyn_word=ops.DYN_BS,
+                             pos_base=start, pos_add=1, tiles_per_req=2)
+
         if flt is None and temperature >= 1e-5 and seed is not None and self.streams_fp8_tiles():
             # an fp8 target: the seeded draw in the e4m3 ring head's epilogue (tile j row m -> POS0 + 16 j + m + 1; the
             # record is rewritten here: verify() rewrites it only when the block size changes, and POS0 must be this
@@ -748,6 +755,8 @@ class NativeTarget:
                                   seeds=self._wide_seed, temperature=temperature, pos_word=ops.DYN_POS0, pos_add=1,
                                   tiles_per_req=2, nrows_dyn_word=ops.DYN_BS,
                                   logits=None if logits_out is None else logits_out.view(2, 16, self.V))
+            if logprobs is not None:
+                lp_rows(logits_out, post)
             cache.length = start + bs
             return post[:bs].unsqueeze(0), taps
         logits = logits_out
@@ -768,6 +777,12 @@ class NativeTarget:
             posterior = post[:bs].unsqueeze(0)
         else:
             posterior = post[:bs].unsqueeze(0) if temperature < 1e-5 else sample(logits[:bs].unsqueeze(0), temperature)
+        if logprobs is not None:
+            ids = post
+            if posterior.data_ptr() != post.data_ptr():   # the host draw: its ids, padded to the two tiles
+                ids = torch.zeros(32, dtype=torch.int64, device=self._dev)
+                ids[:bs] = posterior[0]
+            lp_rows(logits, ids)
         cache.length = start + bs
         return posterior, taps
 
@@ -780,7 +795,7 @@ class NativeTarget:
     def verify(self, block_ids: torch.Tensor, start: int, cache: TargetKVCache, *, tap_layers: Sequence[int] = (),
                temperature: float = 0.0, logits_out: Optional[torch.Tensor] = None,
                taps_out: Optional[torch.Tensor] = None, dyn_lengths: bool = False, seed: Optional[int] = None,
-               top_k: int = 0, top_p: float = 1.0):
+               top_k: int = 0, top_p: float = 1.0, logprobs=None):
         """block_ids int64 [bs] at positions start..start+bs-1 (cache rows alike), bs <= 32.
         Returns (posterior ids int64 [1, bs], taps bf16 [32, len(tap_layers)*H] or None).
         K/V of all bs rows are written; the caller crops to what it accepts.
@@ -796,7 +811,12 @@ class NativeTarget:
         row j draws position start + j + 1, start from the record's POS0 word under dyn_lengths (DESIGN.md section 8);
         no logits are written unless logits_out is given.
         top_k / top_p (with seed, temperature > 0): the filtered draw (section 8, "Filtered draw") — the lm_head launch
-        materialises the block's logits and dfl_sample_rows_nucleus writes the posterior, positions as above."""
+        materialises the block's logits and dfl_sample_rows_nucleus writes the posterior, positions as above.
+        logprobs: an ops.logprob_sink (None: off, and nothing here changes).  The head launch then materialises the
+        block's logits — into logits_out or the target's own buffer — and dfl_logprob_rows, behind whichever launch wrote
+        the posterior, scatters log_softmax(raw logits)[posterior[j]] (T = 1, unfiltered, whatever drew the token) and
+        the sink's n_top alternatives to position start + j + 1 of the sink's row `slot`; start
+        from the record's POS0 word under dyn_lengths."""
         bs = block_ids.numel()
         flt = None
         if ops.check_filter(top_k, top_p) and temperature >= 1e-5:
@@ -845,7 +865,7 @@ class NativeTarget:
         head = self.lm_wp8 if w8 else self.lm_wp
         if len(tiles) == 2 and self.wide_one_pass and self.attn_impl == "head":
             return self._verify_wide(block_ids, start, cache, bs, tap_layers, taps, logits_out, temperature, cos, sin, seed,
-                                     flt)
+                                     flt, logprobs)
         rs = self.rows
         for t, dt in tiles:
             ops.embed_rows(self.embed, block_ids[16 * t:], rs.h_tiles[t], H, rs.ss_emb[16 * t:], dt, ops.DYN_BS)
@@ -867,6 +887,14 @@ class NativeTarget:
                      taps=taps, tap_layers=tap_layers, moe=self._moe_mlp, gu_events=self.gu_events)
         post = ws["post"]
         logits = logits_out
+        if logprobs is not None and logits is None and (flt is not None or seed is not None or temperature < 1e-5):
+            logits = self._nucleus_logits()   # (the host draw below materialises into a buffer of its own)
+
+        def lp_rows(ids):   # behind the launches that wrote the posterior: tile t row m -> position start + 16 t + m + 1
+            for t, dt in tiles:
+                ops.logprob_rows(logits[16 * t:16 * t + 16], ids[16 * t:], logprobs, nrows=min(16, bs - 16 * t), dyn=dt,
+                                 pos_word=ops.DYN_POS0 if dyn_lengths else -1, pos_base=start, pos_add=16 * t + 1)
+
         if flt is not None:
             if logits is None:
                 logits = self._nucleus_logits()
@@ -877,6 +905,8 @@ class NativeTarget:
                 ops.sample_rows_nucleus(logits[16 * t:16 * t + 16], seed=seed, temperature=temperature, nrows=n, dyn=dt,
                                         pos_word=ops.DYN_POS0 if dyn_lengths else -1, pos_base=start, pos_add=16 * t + 1,
                                         out=post[16 * t:16 * t + 16], **flt)
+            if logprobs is not None:
+                lp_rows(post)
             cache.length = start + bs
             return post[:bs].unsqueeze(0), taps
         if temperature >= 1e-5 and seed is not None:
@@ -885,6 +915,8 @@ class NativeTarget:
                                 seed=seed, temperature=temperature, pos_dyn=dt if dyn_lengths else None,
                                 pos_word=ops.DYN_POS0, pos_base=start, pos_add=16 * t + 1, dyn=dt,
                                 logits=None if logits is None else logits[16 * t:16 * t + 16])
+            if logprobs is not None:
+                lp_rows(post)
             cache.length = start + bs
             return post[:bs].unsqueeze(0), taps
         if temperature >= 1e-5:
@@ -898,5 +930,7 @@ class NativeTarget:
             posterior = post[:bs].unsqueeze(0)
         else:
             posterior = sample(logits[:bs].unsqueeze(0), temperature)
+        if logprobs is not None:
+            lp_rows(posterior[0].contiguous())
         cache.length = start + bs
         return posterior, taps

@@ -473,6 +473,32 @@ int dfl_sample_rows_nucleus(const void *logits, int64_t ld, int64_t tile_stride,
                             int rng_stream, int extra, int64_t *out_ids, int64_t out_stride, int out_off, float *thr_out,
                             int32_t *kept_out, void *stream);
 
+/* Log-probabilities of the tokens a verify commits, and optionally of the top alternatives at each position (DESIGN.md
+ * section 12), over materialised bf16 logits laid out as tiles [tiles][16][V] — layout, rows and tiles exactly as
+ * dfl_sample_rows_nucleus takes them (ld, tile_stride in elements, V <= 155648; row0 / nrows or dyn[t][nrows_dyn_word];
+ * tile t = tile j = t % tiles_per_req of request slot q = t / tiles_per_req; rows past a tile's valid count write nothing).
+ * The numbers are of the RAW distribution: log_softmax of the logits as the head produced them, at T = 1 and unfiltered,
+ * whatever temperature, top-k or top-p chose the token.  Per row, in fp32:
+ *   lse = max + log(sum exp(x - max)), max over the FINITE values; -inf, +inf and NaN entries contribute 0 (a row without
+ *         a finite value has lse = -inf).  The sum has one fixed order (per thread in column order, the wave's butterfly,
+ *         the 16 wave sums in wave order): the same logits give the same bits on every run.
+ *   lp  = x[id] - lse, id = ids[t * ids_stride + ids_off + (m - row0)] (int64: the out_ids indexing of the sampling
+ *         launches).  An id outside [0, V) writes NaN and reads nothing out of the row.
+ *   top : the n_top (0..8) columns first in the order (value descending, column ascending), as column ids (int64) and
+ *         x - lse.  -0 and +0 are one value; a NaN sorts above +inf (sign clear) or below -inf (sign set), so every bit
+ *         pattern has a place.  V < n_top: the entries past V are id -1 and NaN.  n_top = 0: the outputs may be NULL.
+ * Outputs are scattered by POSITION: row m of tile t writes at
+ *   pos = (pos_word >= 0 ? dyn[t][pos_word] : pos_base) + pos_add + 16 j + m     (the position rule of the filtered draw)
+ * into lp_out[q * lp_stride + pos] and top_ids_out / top_lp_out[(q * lp_stride + pos) * n_top + i]; pos < 0 or
+ * pos >= lp_len writes nothing.  Verify row j of a cycle starting at `start` predicts position start + j + 1, and the
+ * token committed there is always posterior[j]; a later cycle rewrites every position past its own start, so each
+ * committed position keeps the value of the cycle that committed it.  Launch it behind the last launch that writes the
+ * posterior and BEFORE the accept launch, which advances the records the positions are read from. */
+int dfl_logprob_rows(const void *logits, int64_t ld, int64_t tile_stride, int tiles, int V, int row0, int nrows,
+                     const int32_t *dyn, int nrows_dyn_word, int pos_word, int pos_base, int pos_add, int tiles_per_req,
+                     const int64_t *ids, int64_t ids_stride, int ids_off, int n_top, float *lp_out, int64_t *top_ids_out,
+                     float *top_lp_out, int64_t lp_stride, int lp_len, void *stream);
+
 /* Acceptance scan + commit + bonus token + stop test + length bookkeeping in one
  * wavefront (model/dflash.py:258-268):
  *   acc = #leading i with block[i+1] == posterior[i]           (0..bs-1)
