@@ -55,11 +55,20 @@ class BatchedDecoder:
                  out_len: int, mask_token_id: int, stop_token_ids=None, max_splits: int = 32,
                  temperature: float = 0.0, tiles_per_request: int = 1, sampler: str = "torch",
                  draft_temperature: float = 0.0, filtering: bool = False, request_temperature: bool = False,
-                 logprobs: Optional[int] = None):
+                 logprobs: Optional[int] = None, penalties: bool = False):
         """logprobs = N (None: off; fixed here, it fixes the captured launch sequence): every verify materialises its
         logits and dfl_logprob_rows scatters the log-probability of each committed token, and the top N alternatives, to
-        the token's position in the slot's row of self.lp."""
+        the token's position in the slot's row of self.lp.
+        penalties (fixed here for the same reason): requests may carry repetition / presence / frequency penalties
+        (admit); every verify materialises its logits, dfl_penalty_rows writes each slot's penalised rows and their
+        argmax, the draw runs over the penalised rows, and dfl_penalty_count keeps the slots' table rows behind the
+        accept launch.  A slot with neutral values gets the ids of a decoder built without it."""
         logprobs = ops.check_logprobs(logprobs)
+        if penalties and tiles_per_request != 1:
+            raise NotImplementedError("penalties take blocks of <= 16 rows (tiles_per_request = 1)")
+        if penalties and temperature >= 1e-5 and sampler != "device":
+            raise ValueError("penalties at T > 0 need sampler='device' (sampler='torch' is the reference's multinomial over "
+                             "the raw logits)")
         if not isinstance(target, NativeTarget):
             raise TypeError("BatchedDecoder needs a dflash_amd.NativeTarget (see module docstring)")
         if tiles_per_request not in (1, 2):
@@ -128,7 +137,14 @@ class BatchedDecoder:
         self.filtering = bool(filtering) and (self.temperature >= 1e-5 or self.request_temperature)
         self.top_k, self.top_p = z(NREQ, dt=I32), torch.ones(NREQ, dtype=F32, device=dev)
         self.lp = ops.logprob_sink(NREQ, out_len, logprobs, dev) if logprobs is not None else None
-        if self.filtering or self.lp is not None:
+        # penalties: one table row per request slot (bit 31: seen in the prompt, bits 0..30: occurrences in the output),
+        # the slots' three values beside their seeds, and the buffer of the penalised rows (the raw ones stay for logprobs)
+        self.penalties = bool(penalties)
+        if self.penalties:
+            self.pen_table = ops.penalty_state(NREQ, target.V, dev)
+            self.pen_r, self.pen_a, self.pen_f = torch.ones(NREQ, dtype=F32, device=dev), z(NREQ, dt=F32), z(NREQ, dt=F32)
+            self._pen_logits = z(MT, 16, target.V)
+        if self.filtering or self.lp is not None or self.penalties:
             self._logits = z(MT, 16, target.V)
         self.output_ids = torch.full((NREQ, out_len), self.mask_id, dtype=I64, device=dev)
         self.stop_t = torch.tensor(stop_token_ids, dtype=I64, device=dev) if stop_token_ids else None
@@ -207,11 +223,16 @@ class BatchedDecoder:
 
     # ------------------------------------------------------------------ admission
     def _admit_prefill(self, r: int, input_ids: torch.Tensor, temperature: float, seed: Optional[int], top_k=0,
-                       top_p=1.0):
+                       top_p=1.0, penalties=(1.0, 0.0, 0.0)):
         """The launches both admissions share: target prefill into slot r's cache, the first token, the prompt's context
         rows into the draft cache except the last <= 16.  Returns (P, first token [1, 1] on the device, tapped rows
         [P, fc_in], the seed written for the slot or None)."""
         m, t = self.model, self.target
+        pen = ops.check_penalties(*penalties)
+        if pen is not None and not self.penalties:
+            raise ValueError("admit: penalties need a decoder built with penalties=True")
+        if pen is not None and temperature >= 1e-5 and self.sampler != "device":
+            raise ValueError("admit: penalties at T > 0 need sampler='device'")
         flt = None
         if ops.check_filter(top_k, top_p) and temperature >= 1e-5:
             if not self.filtering:
@@ -231,13 +252,26 @@ class BatchedDecoder:
             self.embed_w = _bf16_table(t.model.embed_tokens.weight, self.dev)
         tc = _View(self.tk[r], self.tv[r], None, self.max_rows)
         out = t.prefill(input_ids, tc, output_hidden_states=True, tap_layers=self.model.target_layer_ids)
+        first_logits = out.logits[:, -1:]
+        if self.penalties:   # the slot's table row starts from the prompt alone, whatever ran in the slot before; the
+            # first token comes from the prompt's last row penalised by it (no block in front of it)
+            pr, pa, pf = pen or (1.0, 0.0, 0.0)
+            tab = self.pen_table[r:r + 1]
+            ops.penalty_count(tab, input_ids, lo=0, hi=P, as_prompt=True, clear=True)
+            first_logits = ops.penalty_rows(out.logits[0, -1:].to(BF16).contiguous(), tab, repetition_penalty=pr,
+                                            presence_penalty=pa, frequency_penalty=pf).unsqueeze(0)
         sd = None
         if self.sampler == "device" and (temperature >= 1e-5 or self.temperature >= 1e-5):
             sd = resolve_seed("device", seed)
-            first = (_draw_rows(out.logits[:, -1:], temperature, sd, P, flt) if temperature >= 1e-5
-                     else sample(out.logits, 0.0))
+            first = (_draw_rows(first_logits, temperature, sd, P, flt) if temperature >= 1e-5
+                     else sample(first_logits, 0.0))
         else:
-            first = sample(out.logits, temperature)
+            first = sample(first_logits, temperature)
+        if self.penalties:   # the first token is output; the slot's three values, re-armed on every admission
+            ops.penalty_count(tab, first.reshape(1, 1), lo=0, hi=1)
+            self.pen_r[r:r + 1].fill_(pr)
+            self.pen_a[r:r + 1].fill_(pa)
+            self.pen_f[r:r + 1].fill_(pf)
         if self.lp is not None:   # the first token's value, from the prompt's last-row logits: nothing is read back
             sink = SimpleNamespace(**{**vars(self.lp), "slot": r})
             ops.logprob_rows(out.logits[0, -1:].to(BF16).contiguous(), first.reshape(1), sink, pos_base=P)
@@ -255,15 +289,19 @@ class BatchedDecoder:
 
     @torch.inference_mode()
     def admit(self, r: int, input_ids: torch.Tensor, temperature: float = 0.0, seed: Optional[int] = None,
-              top_k: int = 0, top_p: float = 1.0) -> None:
+              top_k: int = 0, top_p: float = 1.0, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
+              frequency_penalty: float = 0.0) -> None:
         """Prefill request r (model/dflash.py:218-229): target prefill through the wrapped
         model, K/V into the group cache, first token sampled, the prompt's context rows
         projected into the draft cache except the last <= 16, which become the first
         cycle's context tile.  seed (sampler="device"): the request's seed (None: one from torch's RNG).
         temperature: of the first token; of every later token too in a decoder built with request_temperature=True
         (otherwise those are drawn at the decoder's).
-        top_k / top_p: the request's filter (a decoder built with filtering=True), written into the slot's device words."""
-        P, first, th, sd = self._admit_prefill(r, input_ids, temperature, seed, top_k, top_p)
+        top_k / top_p: the request's filter (a decoder built with filtering=True), written into the slot's device words.
+        repetition_penalty / presence_penalty / frequency_penalty: the request's penalties (a decoder built with
+        penalties=True), likewise; the slot's table row is cleared and re-counted from this prompt."""
+        P, first, th, sd = self._admit_prefill(r, input_ids, temperature, seed, top_k, top_p,
+                                               (repetition_penalty, presence_penalty, frequency_penalty))
         self.output_ids[r].fill_(self.mask_id)
         self.output_ids[r, :P] = input_ids[0]
         if sd is not None:
@@ -286,7 +324,8 @@ class BatchedDecoder:
 
     @torch.inference_mode()
     def admit_fused(self, r: int, input_ids: torch.Tensor, temperature: float = 0.0, seed: Optional[int] = None,
-                    top_k: int = 0, top_p: float = 1.0) -> None:
+                    top_k: int = 0, top_p: float = 1.0, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
+                    frequency_penalty: float = 0.0) -> None:
         """`admit` with the slot re-armed by ONE launch (dfl_admit_slot) instead of a dozen small writes: ids, first
         token, block, context tile, both length records and the seed are written on the device from device-resident
         inputs, so that after the prefill launches the admission reads nothing back and copies nothing from the host —
@@ -296,7 +335,8 @@ class BatchedDecoder:
             raise NotImplementedError("admit_fused re-arms one 16-row tile per request; use admit() with tiles_per_request=2")
         if not 0 <= r < self.R:
             raise ValueError(f"admit_fused: slot {r} outside 0..{self.R - 1}")
-        P, first, th, sd = self._admit_prefill(r, input_ids, temperature, seed, top_k, top_p)
+        P, first, th, sd = self._admit_prefill(r, input_ids, temperature, seed, top_k, top_p,
+                                               (repetition_penalty, presence_penalty, frequency_penalty))
         n_tail = min(16, P)
         ops.admit_slot(r, input_ids[0].contiguous(), first.reshape(1), self.output_ids, self.block, self.post, self.result,
                        th[P - n_tail:], self.d["taps"], self.dyn_d, self.dyn_t, self.BW, self.mask_id,
@@ -416,7 +456,19 @@ class BatchedDecoder:
         st.finish(t.norm)
         lm = self._t_head()
         lg = self._logits if self.lp is not None else None   # logprobs: every head below materialises its logits
-        if self.request_temperature and self.filtering:   # greedy slots keep the argmax ids the first launch wrote
+        if self.penalties:   # materialise; each slot's penalised rows and their argmax (what a greedy slot keeps); the
+            # draw over the penalised rows at the slot's seed / top_k / top_p / invT; logprobs below read the raw rows
+            ops.gemm_argmax_batch(lm, s["xn"], R, t.V, H, 0, 16, self.gws, self.post.view(-1, 16), 0, dyn_t,
+                                  nrows_dyn_word=ops.DYN_BS, logits=self._logits)
+            ops.penalty_rows(self._logits[:R], self.pen_table, repetition_penalty=self.pen_r, presence_penalty=self.pen_a,
+                             frequency_penalty=self.pen_f, block=self.block, out=self._pen_logits[:R], dyn=dyn_t,
+                             nrows_dyn_word=ops.DYN_BS, out_ids=self.post.view(-1, 16))
+            if self.request_temperature or self.temperature >= 1e-5:
+                tkw = dict(inv_t=self.inv_ts) if self.request_temperature else dict(temperature=self.temperature)
+                ops.sample_rows_nucleus(self._pen_logits[:R], seed=self.seeds, top_k=self.top_k, top_p=self.top_p,
+                                        dyn=dyn_t, nrows_dyn_word=ops.DYN_BS, pos_word=ops.DYN_POS0, pos_add=1,
+                                        tiles_per_req=TPR, out=self.post.view(-1, 16), **tkw)
+        elif self.request_temperature and self.filtering:   # greedy slots keep the argmax ids the first launch wrote
             ops.gemm_argmax_batch(lm, s["xn"], R, t.V, H, 0, 16, self.gws, self.post.view(-1, 16), 0, dyn_t,
                                   nrows_dyn_word=ops.DYN_BS, logits=self._logits)
             ops.sample_rows_nucleus(self._logits[:R], seed=self.seeds, top_k=self.top_k, top_p=self.top_p,
@@ -457,6 +509,9 @@ class BatchedDecoder:
         ops.accept_commit_batch(self.block, self.post, self.R, self.output_ids, self.dyn_d, self.dyn_t, self.stop_t,
                                 self.result, rearm_mask_id=self.mask_id, tiles_per_req=self.TPR,
                                 dyn_d_tiles=self.dyn_dt, dyn_t_tiles=self.dyn_tt)
+        if self.penalties:   # what the launch committed, output_ids(S, START] of each live slot; a parked slot is idle
+            ops.penalty_count(self.pen_table[:self.R], self.output_ids, dyn=self.dyn_d, lo_word=ops.DYN_S,
+                              hi_word=ops.DYN_START, lo=1, hi=1)
 
     def accept(self, launch: bool = True) -> list:
         """Acceptance scan + commit + rollback bookkeeping of all requests (:258-268) and
@@ -605,12 +660,25 @@ def _prompt_filters(top_k, top_p, n: int, temperature, sampler: str):
     return [int(k) for k in ks], [float(p) for p in ps], filtering
 
 
+def _prompt_penalties(repetition_penalty, presence_penalty, frequency_penalty, n: int):
+    """((r, a, f) per prompt, whether any prompt is not neutral) from scalars or one value per prompt."""
+    cols = []
+    for v in (repetition_penalty, presence_penalty, frequency_penalty):
+        col = [float(v)] * n if isinstance(v, (int, float)) else [float(x) for x in v]
+        if len(col) != n:
+            raise ValueError("repetition_penalty / presence_penalty / frequency_penalty: a scalar or one value per prompt")
+        cols.append(col)
+    pens = list(zip(*cols))
+    return pens, any(ops.check_penalties(*p) is not None for p in pens)
+
+
 @torch.inference_mode()
 def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_ids: Sequence[torch.Tensor],
                           mask_token_id: int, max_new_tokens: int, block_size: int, stop_token_ids,
                           temperature=0.0, draft_token_hook: Optional[Callable] = None,
                           group_size: int = MAX_GROUP, hook_block_view: bool = False, sampler: str = "torch",
-                          seed=None, top_k=0, top_p=1.0, logprobs: Optional[int] = None) -> list:
+                          seed=None, top_k=0, top_p=1.0, logprobs: Optional[int] = None, repetition_penalty=1.0,
+                          presence_penalty=0.0, frequency_penalty=0.0) -> list:
     """`dflash_generate` (benchmark.py:44-251) for a list of prompts: requests run in
     groups of `group_size` <= 4 (<= 2 with block sizes of 17..32 rows) that share the weight stream; returns one namespace per
     prompt with the fields of benchmark.py:242-251 (timing fields are the group's).
@@ -621,13 +689,18 @@ def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_i
     top_k / top_p: a scalar, or one value per prompt (0 / 1.0: off), as in dflash_generate.
     temperature: one float, or one value per prompt; values that differ need sampler="device" and run every group through
     a decoder built with request_temperature=True ("Per-request temperature").
-    logprobs: as dflash_generate, for every prompt (the fields logprobs / top_logprob_ids / top_logprobs; None when off)."""
+    logprobs: as dflash_generate, for every prompt (the fields logprobs / top_logprob_ids / top_logprobs; None when off).
+    repetition_penalty / presence_penalty / frequency_penalty: as dflash_generate; a scalar, or one value per prompt.
+    The decoders are built with penalties=True when any prompt is not neutral (blocks of <= 16 rows)."""
     logprobs = ops.check_logprobs(logprobs)
+    pens, penalties = _prompt_penalties(repetition_penalty, presence_penalty, frequency_penalty, len(input_ids))
     temps, per_request = _prompt_temperatures(temperature, len(input_ids), sampler)
     seeds = _prompt_seeds(sampler, seed, len(input_ids), any(t >= 1e-5 for t in temps))
     top_ks, top_ps, filtering = _prompt_filters(top_k, top_p, len(input_ids), temps, sampler)
     if not 1 <= block_size <= 32:
         raise NotImplementedError("the batched loop takes blocks of 1..16 rows (one tile per request) or 17..32 rows (two)")
+    if penalties and block_size > 16:
+        raise NotImplementedError("penalties take blocks of <= 16 rows")
     tpr = 1 if block_size <= 16 else 2      # blocks of 17..32 rows: a request takes two of the group's four tiles
     group_size = min(group_size, MAX_GROUP // tpr)
     n = len(input_ids)
@@ -640,10 +713,13 @@ def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_i
         dec = BatchedDecoder(model, target, len(idx), max_rows=pmax + max_new_tokens + 3 * 16 * tpr,
                              out_len=pmax + max_new_tokens + 16 * tpr, mask_token_id=mask_token_id,
                              stop_token_ids=stop_token_ids, temperature=max(temps[i] for i in idx), tiles_per_request=tpr,
-                             sampler=sampler, filtering=filtering, request_temperature=per_request, logprobs=logprobs)
+                             sampler=sampler, filtering=filtering, request_temperature=per_request, logprobs=logprobs,
+                             penalties=penalties)
         t0 = cuda_time()
         for r, p in enumerate(prompts):
-            dec.admit(r, p, temps[idx[r]], seed=seeds[idx[r]], top_k=top_ks[idx[r]], top_p=top_ps[idx[r]])
+            pr, pa, pf = pens[idx[r]]
+            dec.admit(r, p, temps[idx[r]], seed=seeds[idx[r]], top_k=top_ks[idx[r]], top_p=top_ps[idx[r]],
+                      repetition_penalty=pr, presence_penalty=pa, frequency_penalty=pf)
         ttft = cuda_time() - t0
         taus = [[] for _ in idx]
         # (hook_block_view: the hook sees the block as the single-request loop hands it over, bs slots; default: the

@@ -193,8 +193,20 @@ class DecodeSession:
     def __init__(self, model, target, input_ids: torch.Tensor, *, mask_token_id: int, max_new_tokens: int,
                  max_block_size: int, stop_token_ids, temperature: float, draft_temperature: float = 0.0,
                  draft_token_hook: Optional[Callable] = None, sampler: str = "torch", seed: Optional[int] = None,
-                 top_k: int = 0, top_p: float = 1.0, logprobs: Optional[int] = None):
+                 top_k: int = 0, top_p: float = 1.0, logprobs: Optional[int] = None, repetition_penalty: float = 1.0,
+                 presence_penalty: float = 0.0, frequency_penalty: float = 0.0):
         from .target import NativeTarget
+        # repetition / presence / frequency penalties on the TARGET's rows; all three neutral:
+        # None, and every launch below is the one enqueued without the keywords
+        pen = ops.check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
+        if pen is not None:
+            if not isinstance(target, NativeTarget):
+                raise ValueError("penalties need a dflash_amd.NativeTarget (the kernel reads the verify's materialised logits)")
+            if temperature >= 1e-5 and sampler != "device":
+                raise ValueError("penalties at T > 0 need sampler='device' (sampler='torch' is the reference's multinomial "
+                                 "over the raw logits)")
+            if int(max_block_size) > 16:
+                raise NotImplementedError("penalties take blocks of <= 16 rows (the 17..32-row verify is not covered)")
         # logprobs = N (None: off): per position of output_ids the log-probability of the committed token and the top N
         # alternatives, scattered there by dfl_logprob_rows behind every verify's posterior
         self.logprobs = ops.check_logprobs(logprobs)
@@ -233,6 +245,13 @@ class DecodeSession:
         self.native = isinstance(target, NativeTarget)
         self.lp = (ops.logprob_sink(1, self.output_ids.shape[1], self.logprobs, dev) if self.logprobs is not None else None)
         self._lpkw = {} if self.lp is None else dict(logprobs=self.lp)
+        # the penalty state: the table row dfl_penalty_count keeps (prompt flags + output counts of everything committed),
+        # the three values and the buffer the verify writes its penalised rows into
+        self.pen = None
+        if pen is not None:
+            self.pen = SimpleNamespace(table=ops.penalty_state(1, target.V, dev), r=pen[0], a=pen[1], f=pen[2],
+                                       logits=torch.zeros(16, target.V, dtype=torch.bfloat16, device=dev))
+            self._lpkw = dict(self._lpkw, penalties=self.pen)
         self.tcache = (target.new_cache(self.max_length + 2 * self.max_bs) if self.native
                        else _new_target_cache(target))
         self.use_draft = self.max_bs > 1
@@ -295,7 +314,9 @@ class DecodeSession:
                               past_key_values=self.tcache, use_cache=True, logits_to_keep=1,
                               output_hidden_states=self.use_draft)
         self.output_ids[:, :self.n_in] = self.input_ids
-        if self._tseed is not None:   # the first new token draws position n_in
+        if self.pen is not None:
+            self._first_token_penalised(out.logits[0, -1:])
+        elif self._tseed is not None:   # the first new token draws position n_in
             self.output_ids[:, self.n_in:self.n_in + 1] = _draw_rows(out.logits[:, -1:], self.temperature, self._tseed,
                                                                      self.n_in, self._filter)
         else:
@@ -305,6 +326,26 @@ class DecodeSession:
                              self.lp, pos_base=self.n_in)
         if self.use_draft:
             self.target_hidden = _taps(out.hidden_states, self.model.target_layer_ids)
+
+    def _first_token_penalised(self, row: torch.Tensor) -> None:
+        """The first new token under penalties: the prompt is counted into a cleared table row, the prompt's last-row
+        logits are penalised by it, the token is their argmax or the seeded draw at position n_in over them, and it is
+        counted as output."""
+        p, n = self.pen, self.n_in
+        ops.penalty_count(p.table, self.output_ids, lo=0, hi=n, as_prompt=True, clear=True)
+        first = self.output_ids[0, n:n + 1]
+        z = ops.penalty_rows(row.to(torch.bfloat16).contiguous(), p.table, repetition_penalty=p.r, presence_penalty=p.a,
+                             frequency_penalty=p.f, out_ids=first)
+        if self._tseed is not None:
+            first.copy_(_draw_rows(z.unsqueeze(0), self.temperature, self._tseed, n, self._filter)[0])
+        ops.penalty_count(p.table, self.output_ids, lo=n, hi=n + 1)
+
+    def _count_committed(self) -> None:
+        """Right behind an accept launch: what it committed, output_ids(S, START] of the draft record it has just
+        written, goes into the penalty table — once per cycle, eager or replayed."""
+        if self.pen is not None:
+            ops.penalty_count(self.pen.table, self.output_ids, dyn=self.dyn, lo_word=ops.DYN_S, hi_word=ops.DYN_START,
+                              lo=1, hi=1)
 
     def _mark(self, key, which):
         if self.events is not None and self.record_events:
@@ -440,6 +481,7 @@ class DecodeSession:
         ops.accept_commit(blk[0], posterior[0].contiguous(), bs, self.output_ids[0], self.dyn, self.stop_t,
                           self.result, rearm=(self.block[0], self.max_bs, self.mask_token_id),
                           dyn_t=self.tcache.dyn if (self.native and self._fixed is not None) else None)
+        self._count_committed()
         self._armed = True
         # the record now holds the next draft forward's S / tau / pos0 / start — if that cycle was a cached draft cycle
         # on this record (bs > 1, one draft step) and keeps the block size
@@ -551,6 +593,7 @@ class DecodeSession:
                                taps_out=self.taps_buf, dyn_lengths=True, seed=self._tseed, **self._fkw, **self._lpkw)
             ops.accept_commit(self.block[0, :bs], post[0].contiguous(), bs, self.output_ids[0], self.dyn, self.stop_t,
                               self.result, rearm=(self.block[0], self.max_bs, self.mask_token_id), dyn_t=self.tcache.dyn)
+            self._count_committed()
 
         graphs = {bs: (capture_graph(lambda: draft(bs)), capture_graph(lambda: verify_accept(bs))) for bs in sizes}
         # The graphs hold RAW device pointers: keep alive every tensor whose address they hold and that this session does
@@ -559,7 +602,8 @@ class DecodeSession:
                        (m._rope, t._rope, getattr(m, "ws", None), getattr(t, "ws", None), getattr(t, "_taps", None),
                         self.lm_wp, self.lm_wp8, self.embed_w, getattr(t, "lm_wp", None),
                         t.fp8_tensors() if self.native else (),    # (an fp8 target's codes and scale vectors)
-                        getattr(t, "_nuc_logits", None)))          # (the logits a filtered or logprobs verify materialises)
+                        getattr(t, "_nuc_logits", None),           # (the logits a filtered, logprobs or penalised verify materialises)
+                        self.pen))                                 # (the penalty table and the penalised rows: the session's own)
 
     def _tables_moved(self, rec: _Replay) -> bool:
         """A shared draft model / NativeTarget replaces its RoPE table when another caller needs more positions
@@ -699,12 +743,14 @@ def run_decode(model, target, input_ids: torch.Tensor, *, mask_token_id: int, ma
                draft_steps: int = 1, collect_profile: bool = False, scheduler=None,
                draft_temperature: float = 0.0, draft_token_hook: Optional[Callable] = None,
                max_block_size: Optional[int] = None, sampler: str = "torch", seed: Optional[int] = None,
-               top_k: int = 0, top_p: float = 1.0, logprobs: Optional[int] = None) -> SimpleNamespace:
+               top_k: int = 0, top_p: float = 1.0, logprobs: Optional[int] = None, repetition_penalty: float = 1.0,
+               presence_penalty: float = 0.0, frequency_penalty: float = 0.0) -> SimpleNamespace:
     s = DecodeSession(model, target, input_ids, mask_token_id=mask_token_id, max_new_tokens=max_new_tokens,
                       max_block_size=max_block_size or block_size, stop_token_ids=stop_token_ids,
                       temperature=temperature, draft_temperature=draft_temperature,
                       draft_token_hook=draft_token_hook, sampler=sampler, seed=seed, top_k=top_k, top_p=top_p,
-                      logprobs=logprobs)
+                      logprobs=logprobs, repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
+                      frequency_penalty=frequency_penalty)
     t_prefill = cuda_time()
     s.prefill()
     time_to_first_token = cuda_time() - t_prefill
@@ -870,8 +916,13 @@ def dflash_generate(model, target, input_ids: torch.Tensor, mask_token_id: int, 
                     block_size: int, stop_token_ids, temperature: float = 0.0, collect_profile: bool = False,
                     draft_steps: int = 1, draft_token_hook=None, sampler: str = "torch",
                     seed: Optional[int] = None, top_k: int = 0, top_p: float = 1.0,
-                    logprobs: Optional[int] = None) -> SimpleNamespace:
+                    logprobs: Optional[int] = None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
+                    frequency_penalty: float = 0.0) -> SimpleNamespace:
     """benchmark.py:44-55 signature; returns the namespace of :242-251 (+ replayed_cycles).
+    repetition_penalty r / presence_penalty a / frequency_penalty f (1.0 / 0.0 / 0.0: off; need a NativeTarget, blocks of
+    <= 16 rows, and sampler="device" at T > 0): the vLLM / OpenAI penalties on the target's logits, history = the prompt
+    and everything emitted so far, the draft tokens in front of a verify row included.  The draft's
+    proposals stay unpenalised.
     logprobs (None: off; needs a NativeTarget): 0 adds the field `logprobs` fp32 [num_output_tokens], the
     log-probability of every generated token under the target's RAW distribution (log_softmax of its logits at T = 1,
     unfiltered, whatever temperature and filter drew the token); 1..8 add `top_logprob_ids` / `top_logprobs`
@@ -882,11 +933,13 @@ def dflash_generate(model, target, input_ids: torch.Tensor, mask_token_id: int, 
     if getattr(model, "wide_hidden", False):
         return _generate_wide_hidden(model, target, input_ids, mask_token_id, max_new_tokens, block_size, stop_token_ids,
                                      temperature, collect_profile, draft_steps, draft_token_hook, sampler, seed, top_k, top_p,
-                                     logprobs)
+                                     logprobs, (repetition_penalty, presence_penalty, frequency_penalty))
     r = run_decode(model, target, input_ids, mask_token_id=mask_token_id, max_new_tokens=max_new_tokens,
                    block_size=block_size, stop_token_ids=stop_token_ids, temperature=temperature, clamp_tail=True,
                    draft_steps=draft_steps, collect_profile=collect_profile, draft_token_hook=draft_token_hook,
-                   sampler=sampler, seed=seed, top_k=top_k, top_p=top_p, logprobs=logprobs)
+                   sampler=sampler, seed=seed, top_k=top_k, top_p=top_p, logprobs=logprobs,
+                   repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
+                   frequency_penalty=frequency_penalty)
     return SimpleNamespace(output_ids=r.output_ids, num_input_tokens=r.num_input_tokens,
                            num_output_tokens=r.num_output_tokens, time_to_first_token=r.time_to_first_token,
                            time_per_output_token=r.time_per_output_token, acceptance_lengths=r.acceptance_lengths,
@@ -897,7 +950,7 @@ def dflash_generate(model, target, input_ids: torch.Tensor, mask_token_id: int, 
 
 def _generate_wide_hidden(model, target, input_ids, mask_token_id, max_new_tokens, block_size, stop_token_ids, temperature,
                           collect_profile=False, draft_steps=1, draft_token_hook=None, sampler="torch",
-                          seed=None, top_k=0, top_p=1.0, logprobs=None) -> SimpleNamespace:
+                          seed=None, top_k=0, top_p=1.0, logprobs=None, penalties=(1.0, 0.0, 0.0)) -> SimpleNamespace:
     """hidden_size > 4096: the request runs as a group of ONE through the ragged-batch kernels (their GEMMs cut K over
     workgroups; the single-request kernels keep a whole K = hidden row slice per workgroup).  Same loop semantics
     (benchmark.py:44-251, tail clamp included); no per-cycle profile, one draft step per cycle."""
@@ -911,18 +964,23 @@ def _generate_wide_hidden(model, target, input_ids, mask_token_id, max_new_token
     hook = (lambda r, blk, start, call: draft_token_hook(blk, start, call)) if draft_token_hook else None
     return dflash_generate_batch(model, target, [input_ids], mask_token_id, max_new_tokens, block_size, stop_token_ids,
                                  temperature, draft_token_hook=hook, group_size=1, hook_block_view=True, sampler=sampler,
-                                 seed=None if seed is None else [seed], top_k=top_k, top_p=top_p, logprobs=logprobs)[0]
+                                 seed=None if seed is None else [seed], top_k=top_k, top_p=top_p, logprobs=logprobs,
+                                 repetition_penalty=penalties[0], presence_penalty=penalties[1],
+                                 frequency_penalty=penalties[2])[0]
 
 
 def dflash_generate_policy(*, model, target, input_ids: torch.Tensor, mask_token_id: int, max_new_tokens: int,
                            stop_token_ids, temperature: float, fixed_block_size: Optional[int] = None,
                            scheduler=None, draft_token_hook=None, sampler: str = "torch",
                            seed: Optional[int] = None, top_k: int = 0, top_p: float = 1.0,
-                           logprobs: Optional[int] = None) -> SimpleNamespace:
+                           logprobs: Optional[int] = None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
+                           frequency_penalty: float = 0.0) -> SimpleNamespace:
     """benchmark_dynamic_schedule.py:260-272 signature; returns the namespace of :425-434 (+ replayed_cycles).
     logprobs: as dflash_generate (the fields logprobs / top_logprob_ids / top_logprobs; None when off).
     sampler / seed: as dflash_generate; the draft's own T > 0 draw uses the same seed on a stream of its own.
-    top_k / top_p: as dflash_generate (the target's draw; the draft's own draw stays unfiltered)."""
+    top_k / top_p: as dflash_generate (the target's draw; the draft's own draw stays unfiltered).
+    repetition_penalty / presence_penalty / frequency_penalty: as dflash_generate (the target's rows; the draft's own
+    draw stays unpenalised)."""
     if fixed_block_size is None and scheduler is None:
         raise ValueError("Either fixed_block_size or scheduler must be provided.")
     max_bs = fixed_block_size if fixed_block_size is not None else max(scheduler.candidates)
@@ -931,7 +989,8 @@ def dflash_generate_policy(*, model, target, input_ids: torch.Tensor, mask_token
                    block_size=max_bs, stop_token_ids=stop_token_ids, temperature=temperature, clamp_tail=True,
                    scheduler=sched, draft_temperature=temperature, max_block_size=max_bs,
                    draft_token_hook=draft_token_hook, sampler=sampler, seed=seed, top_k=top_k, top_p=top_p,
-                   logprobs=logprobs)
+                   logprobs=logprobs, repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
+                   frequency_penalty=frequency_penalty)
     if fixed_block_size is not None:
         for row in r.cycle_trace:
             for k in ("tau_hat", "cycle_hat", "score_hat", "current_block_size", "adl_lgen_hat", "adl_lacc_hat",

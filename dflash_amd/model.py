@@ -663,15 +663,20 @@ class DFlashDraftModel:
     @torch.inference_mode()
     def spec_generate(self, target, input_ids: torch.LongTensor, max_new_tokens: int, stop_token_ids,
                       temperature: float, draft_token_hook=None, sampler: str = "torch",
-                      seed: Optional[int] = None, top_k: int = 0, top_p: float = 1.0) -> torch.LongTensor:
-        """model/dflash.py:192-277.  sampler / seed / top_k / top_p: as dflash_generate."""
+                      seed: Optional[int] = None, top_k: int = 0, top_p: float = 1.0, repetition_penalty: float = 1.0,
+                      presence_penalty: float = 0.0, frequency_penalty: float = 0.0) -> torch.LongTensor:
+        """model/dflash.py:192-277.  sampler / seed / top_k / top_p: as dflash_generate (DESIGN.md section 8);
+        repetition_penalty / presence_penalty / frequency_penalty likewise (section 13)."""
+        pen = dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
+                   frequency_penalty=frequency_penalty)
         from .generate import _generate_wide_hidden, run_decode
         if self.wide_hidden:    # (ids are the same with or without the harness form's tail clamp)
             return _generate_wide_hidden(self, target, input_ids, self.mask_token_id, max_new_tokens, self.block_size,
                                          stop_token_ids, temperature, draft_token_hook=draft_token_hook, sampler=sampler,
-                                         seed=seed, top_k=top_k, top_p=top_p).output_ids
+                                         seed=seed, top_k=top_k, top_p=top_p,
+                                         penalties=tuple(pen.values())).output_ids
         r = run_decode(self, target, input_ids, mask_token_id=self.mask_token_id, max_new_tokens=max_new_tokens,
                        block_size=self.block_size, stop_token_ids=stop_token_ids, temperature=temperature,
                        clamp_tail=False, draft_token_hook=draft_token_hook, sampler=sampler, seed=seed, top_k=top_k,
-                       top_p=top_p)
+                       top_p=top_p, **pen)
         return r.output_ids

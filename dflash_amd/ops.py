@@ -680,6 +680,112 @@ def logprob_rows(logits: torch.Tensor, ids: torch.Tensor, sink, *, ids_off: int 
                                  _p(tlp, F32, "sink.top_lp"), length, length, _stream()), "dfl_logprob_rows")
 
 
+def check_penalties(repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0):
+    """Validate one request's (repetition_penalty r > 0, presence_penalty a, frequency_penalty f), all finite; the
+    tuple (r, a, f) of floats, or None when all three are neutral (1.0, 0.0, 0.0): the path without penalties."""
+    import math
+    r, a, f = float(repetition_penalty), float(presence_penalty), float(frequency_penalty)
+    if not (math.isfinite(r) and r > 0.0):
+        raise ValueError(f"dflash_amd: repetition_penalty must be a finite value > 0 (1.0 = off), got {repetition_penalty!r}")
+    if not math.isfinite(a):
+        raise ValueError(f"dflash_amd: presence_penalty must be finite (0.0 = off), got {presence_penalty!r}")
+    if not math.isfinite(f):
+        raise ValueError(f"dflash_amd: frequency_penalty must be finite (0.0 = off), got {frequency_penalty!r}")
+    return None if (r == 1.0 and a == 0.0 and f == 0.0) else (r, a, f)
+
+
+def penalty_state(slots: int, V: int, device) -> torch.Tensor:
+    """The penalty table int32 [slots, V], zeroed: per request slot and token, bit 31 = seen in the
+    prompt, bits 0..30 = occurrences in the output.  Kept by penalty_count, read by penalty_rows."""
+    if V < 8 or V % 8:
+        raise ValueError(f"dflash_amd: penalties need a vocabulary that is a multiple of 8, got {V}")
+    return torch.zeros(slots, V, dtype=I32, device=device)
+
+
+def penalty_count(table: torch.Tensor, ids: torch.Tensor, *, lo: int = 0, hi: int = 0, dyn=None, lo_word: int = 0,
+                  hi_word: int = 0, as_prompt: bool = False, clear: bool = False) -> None:
+    """Add ids[s, lo':hi'] to row s of the penalty table for every slot s (dfl_penalty_count; table int32 [slots, V] or
+    [V], ids int64 [slots, n] or [n]).  dyn None: lo' = lo, hi' = hi.  dyn (int32 length records, one per slot): lo' =
+    dyn[s][lo_word] + lo, hi' = dyn[s][hi_word] + hi, and a slot whose BS word is 0 is skipped whole.  as_prompt: set the
+    prompt flag (bit 31) instead of counting; clear: zero the row first, in the same launch."""
+    if table.dim() == 1:
+        table = table.unsqueeze(0)
+    if ids.dim() == 1:
+        ids = ids.unsqueeze(0)
+    assert table.dim() == 2 and table.stride(1) == 1 and ids.dim() == 2 and ids.stride(1) == 1
+    slots, V = table.shape
+    assert ids.shape[0] >= slots or slots == 1, "ids: one row per slot"
+    if ids.dtype != I64 or not ids.is_cuda or table.dtype != I32 or not table.is_cuda:
+        raise TypeError("dflash_amd: penalty_count takes an int32 GPU table and int64 GPU ids")
+    if dyn is not None:
+        assert dyn.numel() >= 8 * slots
+    check(lib().dfl_penalty_count(table.data_ptr(), table.stride(0), V, slots, ids.data_ptr(), ids.stride(0), ids.shape[1],
+                                  _p(dyn, I32, "dyn"), lo_word, hi_word, lo, hi, int(as_prompt), int(clear), _stream()),
+          "dfl_penalty_count")
+
+
+def penalty_rows(logits: torch.Tensor, table: torch.Tensor, *, repetition_penalty=1.0, presence_penalty=0.0,
+                 frequency_penalty=0.0, block=None, out: Optional[torch.Tensor] = None, row0: int = 0,
+                 nrows: Optional[int] = None, dyn=None, nrows_dyn_word: int = -1, tiles_per_req: int = 1,
+                 out_ids: Optional[torch.Tensor] = None, out_off: int = 0) -> torch.Tensor:
+    """Penalised logits (dfl_penalty_rows) of materialised bf16 logits [rows <= 16, V] (one tile) or
+    [tiles, 16, V], unit inner stride; returns `out` (same shape and strides; None: a new buffer; the logits themselves:
+    in place).  table int32 [slots, V] or [V]; block int64 [slots, >= the rows of a request] or 1-D for one slot
+    (None: no in-block tokens): row m of tile j of slot q sees block[q, 1 : 16 j + m + 1] on top of table row q.
+    The three penalties: a host value, or a device fp32 tensor indexed by slot.  Rows of a tile as in
+    sample_rows_nucleus.  out_ids (int64, [tiles, n] or [n]): the penalised rows' argmax at out_ids[t, out_off + m - row0]."""
+    assert logits.dim() in (2, 3) and logits.stride(-1) == 1 and logits.is_cuda and logits.dtype == BF16
+    if logits.dim() == 2:
+        assert logits.shape[0] <= 16, "one tile holds at most 16 rows"
+        tiles, tile_rows, tile_stride = 1, logits.shape[0], 16 * logits.stride(0)
+    else:
+        assert logits.shape[1] == 16
+        tiles, tile_rows, tile_stride = logits.shape[0], 16, logits.stride(0)
+    V, ld = logits.shape[-1], logits.stride(-2)
+    if nrows is None:
+        nrows = tile_rows - row0
+    assert 0 <= row0 and row0 + nrows <= tile_rows or nrows_dyn_word >= 0 and tile_rows == 16
+    n_out = 16 - row0 if nrows_dyn_word >= 0 else nrows
+    if out is None:
+        out = torch.empty_strided(logits.shape, logits.stride(), dtype=BF16, device=logits.device)
+    assert out.shape == logits.shape and out.stride() == logits.stride() and out.dtype == BF16 and out.is_cuda, "out"
+    if table.dim() == 1:
+        table = table.unsqueeze(0)
+    slots = (tiles + tiles_per_req - 1) // tiles_per_req
+    assert table.dim() == 2 and table.stride(1) == 1 and table.shape == (table.shape[0], V) and table.shape[0] >= slots
+    if table.dtype != I32 or not table.is_cuda:
+        raise TypeError("dflash_amd: the penalty table must be an int32 GPU tensor")
+    blk_stride = 0
+    if block is not None:
+        if block.dtype != I64 or not block.is_cuda:
+            raise TypeError("dflash_amd: block must be an int64 GPU tensor")
+        assert block.stride(-1) == 1 and block.shape[-1] >= 16 * (tiles_per_req - 1) + row0 + n_out, "block"
+        assert block.dim() == 2 and block.shape[0] >= slots or block.dim() == 1 and slots == 1, "block"
+        blk_stride = block.stride(0) if block.dim() == 2 else 0
+    out_stride = 0
+    if out_ids is not None:
+        assert out_ids.stride(-1) == 1 and out_ids.shape[-1] >= out_off + n_out, "out_ids"
+        assert out_ids.dim() == 2 and out_ids.shape[0] >= tiles or out_ids.dim() == 1 and tiles == 1, "out_ids"
+        out_stride = out_ids.stride(0) if out_ids.dim() == 2 else 0
+    if dyn is not None:
+        assert dyn.numel() >= 8 * tiles
+
+    def dev_or_host(v, name, neutral):
+        if torch.is_tensor(v):
+            assert v.numel() >= slots, name
+            return _p(v, F32, name), neutral
+        return None, float(v)
+
+    r_p, r_v = dev_or_host(repetition_penalty, "repetition_penalty", 1.0)
+    a_p, a_v = dev_or_host(presence_penalty, "presence_penalty", 0.0)
+    f_p, f_v = dev_or_host(frequency_penalty, "frequency_penalty", 0.0)
+    check(lib().dfl_penalty_rows(logits.data_ptr(), out.data_ptr(), ld, tile_stride, tiles, V, row0, nrows,
+                                 _p(dyn, I32, "dyn"), nrows_dyn_word, tiles_per_req, table.data_ptr(), table.stride(0),
+                                 None if block is None else block.data_ptr(), blk_stride, r_p, r_v, a_p, a_v, f_p, f_v,
+                                 _p(out_ids, I64, "out_ids"), out_stride, out_off, _stream()), "dfl_penalty_rows")
+    return out
+
+
 def gemm_resid(wp, x, N: int, K: int, h_io: torch.Tensor, *, add_residual: bool, ss_out=None, tap=None,
                dyn=None) -> None:
     """h_io [16, >=N] bf16 (unit inner stride) updated in place; tap: optional [16, *] view

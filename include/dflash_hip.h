@@ -499,6 +499,50 @@ int dfl_logprob_rows(const void *logits, int64_t ld, int64_t tile_stride, int ti
                      const int64_t *ids, int64_t ids_stride, int ids_off, int n_top, float *lp_out, int64_t *top_ids_out,
                      float *top_lp_out, int64_t lp_stride, int lp_len, void *stream);
 
+/* Repetition / presence / frequency penalties.  The state is one table row per request slot,
+ * int32 [slots][table_stride >= V]: bit 31 = the token occurs in the PROMPT, bits 0..30 = its occurrences in the OUTPUT.
+ * V is a multiple of 8, at most 155648; table rows start on 16 bytes (table_stride a multiple of 4).
+ *
+ * dfl_penalty_count adds a range of ids to the rows of slots 0 .. slots-1, one workgroup per slot: slot s takes
+ * ids[s * ids_stride + i] (int64) for i in [lo', hi'), clamped into [0, ids_len), where
+ *   dyn == NULL: lo' = lo, hi' = hi;
+ *   dyn != NULL: lo' = dyn[s][lo_word] + lo, hi' = dyn[s][hi_word] + hi, and a slot whose DFL_DYN_BS word is 0 is IDLE:
+ *                it is skipped whole (not cleared either), the rule of dfl_accept_commit_batch — a parked slot is not
+ *                counted twice.  Behind an accept launch, lo_word = DFL_DYN_S, hi_word = DFL_DYN_START, lo = hi = 1 is
+ *                exactly what that launch committed: output_ids(S, START].
+ * as_prompt != 0: bit 31 is set (integer atomic or); else the count goes up by 1 per occurrence (integer atomic add).
+ * clear != 0: the slot's row is zeroed first, inside the same launch, before its adds.  Ids outside [0, V) are not
+ * counted and never indexed.  Integer adds only: the result does not depend on the order they land in. */
+int dfl_penalty_count(int32_t *table, int64_t table_stride, int V, int slots, const int64_t *ids, int64_t ids_stride,
+                      int ids_len, const int32_t *dyn, int lo_word, int hi_word, int lo, int hi, int as_prompt, int clear,
+                      void *stream);
+
+/* Penalised logits of a verify's rows: reads materialised bf16 logits laid out as tiles [tiles][16][V] — rows, tiles, dyn /
+ * nrows_dyn_word / tiles_per_req exactly as dfl_sample_rows_nucleus takes them (ld and tile_stride in elements, multiples
+ * of 8, rows on 16 bytes) — and writes `out`, same layout; out may be the logits themselves.  Rows past a tile's valid
+ * count return at once and write nothing.  Row m of tile t (tile j = t % tiles_per_req of slot q = t / tiles_per_req) is
+ * penalised by table row q plus the block's own tokens block_ids[q * block_stride + 1 .. 16 j + m] (int64; NULL: none):
+ *   seen(v) = the table word of v is not 0, or v is among those tokens
+ *   c(v)    = bits 0..30 of the table word + the occurrences of v among those tokens
+ * and, x being the bf16 logit widened to fp32, in fp32 IEEE operations each rounded once:
+ *   y1 = seen ? (x > 0 ? x / r : x * r) : x        (a true, correctly rounded division; -0 takes x * r)
+ *   y2 = y1 - (c > 0 ? a : 0)
+ *   y3 = fmaf(-f, float(c), y2)
+ *   z  = y3 rounded to bf16, nearest even
+ * +-inf go through the same operations; a NaN keeps its bits.  With r = 1, a = 0, f = 0 every z is x bit for bit.  Block
+ * ids outside [0, V) are ignored.  r / a / f: device fp32 arrays indexed by q, or NULL for the host value beside them
+ * (the way top_k_dev / top_k work).  Host values are validated (r finite and > 0, a and f finite); device values are
+ * not: a device r that is not > 0 or not finite reads as 1, a non-finite a or f reads as 0, so every bit pattern is defined.
+ * out_ids (optional, int64): out_ids[t * out_stride + out_off + (m - row0)] = the penalised row's argmax, the lowest
+ * column among those equal to the maximum over the values that are not NaN (-0 == +0); 0 for a row of NaNs.  On rows
+ * without NaN these are the ids of dfl_argmax; greedy rows need no further launch, a sampled row's id is overwritten
+ * by the draw behind it.  No floating-point atomics: the same inputs give the same bits, eager or replayed. */
+int dfl_penalty_rows(const void *logits, void *out, int64_t ld, int64_t tile_stride, int tiles, int V, int row0, int nrows,
+                     const int32_t *dyn, int nrows_dyn_word, int tiles_per_req, const int32_t *table, int64_t table_stride,
+                     const int64_t *block_ids, int64_t block_stride, const float *r_dev, float r, const float *a_dev,
+                     float a, const float *f_dev, float f, int64_t *out_ids, int64_t out_stride, int out_off,
+                     void *stream);
+
 /* Acceptance scan + commit + bonus token + stop test + length bookkeeping in one
  * wavefront (model/dflash.py:258-268):
  *   acc = #leading i with block[i+1] == posterior[i]           (0..bs-1)
