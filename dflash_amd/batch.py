@@ -55,15 +55,24 @@ class BatchedDecoder:
                  out_len: int, mask_token_id: int, stop_token_ids=None, max_splits: int = 32,
                  temperature: float = 0.0, tiles_per_request: int = 1, sampler: str = "torch",
                  draft_temperature: float = 0.0, filtering: bool = False, request_temperature: bool = False,
-                 logprobs: Optional[int] = None, penalties: bool = False):
+                 logprobs: Optional[int] = None, penalties: bool = False, logit_bias: bool = False):
         """logprobs = N (None: off; fixed here, it fixes the captured launch sequence): every verify materialises its
         logits and dfl_logprob_rows scatters the log-probability of each committed token, and the top N alternatives, to
         the token's position in the slot's row of self.lp.
         penalties (fixed here for the same reason): requests may carry repetition / presence / frequency penalties
         (admit); every verify materialises its logits, dfl_penalty_rows writes each slot's penalised rows and their
         argmax, the draw runs over the penalised rows, and dfl_penalty_count keeps the slots' table rows behind the
-        accept launch.  A slot with neutral values gets the ids of a decoder built without it."""
+        accept launch.  A slot with neutral values gets the ids of a decoder built without it.
+        logit_bias (fixed here for the same reason): requests may carry logit_bias / allowed_token_ids / banned_token_ids
+        / min_tokens (admit); every verify materialises its logits and dfl_logit_bias_rows writes each slot's biased rows
+        and their argmax from the slot's table row and min_pos, ahead of the penalties and the draw.
+        A slot with neutral values has a zero row and min_pos = 0 and gets the ids of a decoder built without it."""
         logprobs = ops.check_logprobs(logprobs)
+        if logit_bias and tiles_per_request != 1:
+            raise NotImplementedError("logit_bias takes blocks of <= 16 rows (tiles_per_request = 1)")
+        if logit_bias and temperature >= 1e-5 and sampler != "device":
+            raise ValueError("logit_bias at T > 0 needs sampler='device' (sampler='torch' is the reference's multinomial "
+                             "over the raw logits)")
         if penalties and tiles_per_request != 1:
             raise NotImplementedError("penalties take blocks of <= 16 rows (tiles_per_request = 1)")
         if penalties and temperature >= 1e-5 and sampler != "device":
@@ -144,10 +153,17 @@ class BatchedDecoder:
             self.pen_table = ops.penalty_state(NREQ, target.V, dev)
             self.pen_r, self.pen_a, self.pen_f = torch.ones(NREQ, dtype=F32, device=dev), z(NREQ, dt=F32), z(NREQ, dt=F32)
             self._pen_logits = z(MT, 16, target.V)
-        if self.filtering or self.lp is not None or self.penalties:
+        # logit bias: one dense fp32 table row and one min_pos per request slot, rewritten whole on every admission, and
+        # the buffer of the biased rows
+        self.logit_bias = bool(logit_bias)
+        if self.logit_bias:
+            self.lb = ops.logit_bias_state(NREQ, target.V, dev)
+            self._lb_logits = z(MT, 16, target.V)
+        if self.filtering or self.lp is not None or self.penalties or self.logit_bias:
             self._logits = z(MT, 16, target.V)
         self.output_ids = torch.full((NREQ, out_len), self.mask_id, dtype=I64, device=dev)
         self.stop_t = torch.tensor(stop_token_ids, dtype=I64, device=dev) if stop_token_ids else None
+        self.stop_token_ids = list(stop_token_ids) if stop_token_ids else None
         # ---- draft scratch
         self.nqkv_d = c.q_dim + 2 * c.kv_dim
         self.nkv_all = Ld * 2 * c.kv_dim
@@ -223,7 +239,7 @@ class BatchedDecoder:
 
     # ------------------------------------------------------------------ admission
     def _admit_prefill(self, r: int, input_ids: torch.Tensor, temperature: float, seed: Optional[int], top_k=0,
-                       top_p=1.0, penalties=(1.0, 0.0, 0.0)):
+                       top_p=1.0, penalties=(1.0, 0.0, 0.0), bias=None):
         """The launches both admissions share: target prefill into slot r's cache, the first token, the prompt's context
         rows into the draft cache except the last <= 16.  Returns (P, first token [1, 1] on the device, tapped rows
         [P, fc_in], the seed written for the slot or None)."""
@@ -233,6 +249,10 @@ class BatchedDecoder:
             raise ValueError("admit: penalties need a decoder built with penalties=True")
         if pen is not None and temperature >= 1e-5 and self.sampler != "device":
             raise ValueError("admit: penalties at T > 0 need sampler='device'")
+        lb = self.check_bias(**bias) if bias else None
+        if lb is not None and temperature >= 1e-5 and self.sampler != "device":
+            raise ValueError("admit: logit_bias / allowed_token_ids / banned_token_ids / min_tokens at T > 0 need "
+                             "sampler='device'")
         flt = None
         if ops.check_filter(top_k, top_p) and temperature >= 1e-5:
             if not self.filtering:
@@ -253,12 +273,18 @@ class BatchedDecoder:
         tc = _View(self.tk[r], self.tv[r], None, self.max_rows)
         out = t.prefill(input_ids, tc, output_hidden_states=True, tap_layers=self.model.target_layer_ids)
         first_logits = out.logits[:, -1:]
+        if self.logit_bias:   # the slot's whole table row and min_pos = P + min_tokens are rewritten, whatever ran in the
+            # slot before (neutral values: zeros and 0); the prompt's last row predicts position P and takes them
+            ops.logit_bias_set(self.lb, r, lb[0] if lb else None, P + lb[1] if (lb and lb[1]) else 0)
+            first_logits = ops.logit_bias_rows(out.logits[0, -1:].to(BF16).contiguous(), self.lb.bias[r:r + 1],
+                                               min_pos=self.lb.min_pos[r:r + 1], stop_ids=self.stop_t,
+                                               pos_base=P).unsqueeze(0)
         if self.penalties:   # the slot's table row starts from the prompt alone, whatever ran in the slot before; the
             # first token comes from the prompt's last row penalised by it (no block in front of it)
             pr, pa, pf = pen or (1.0, 0.0, 0.0)
             tab = self.pen_table[r:r + 1]
             ops.penalty_count(tab, input_ids, lo=0, hi=P, as_prompt=True, clear=True)
-            first_logits = ops.penalty_rows(out.logits[0, -1:].to(BF16).contiguous(), tab, repetition_penalty=pr,
+            first_logits = ops.penalty_rows(first_logits[0, -1:].to(BF16).contiguous(), tab, repetition_penalty=pr,
                                             presence_penalty=pa, frequency_penalty=pf).unsqueeze(0)
         sd = None
         if self.sampler == "device" and (temperature >= 1e-5 or self.temperature >= 1e-5):
@@ -287,10 +313,23 @@ class BatchedDecoder:
             m.prefill_context(dc, th[:P - n_tail], 0)
         return P, first, th, sd
 
+    def check_bias(self, logit_bias=None, allowed_token_ids=None, banned_token_ids=None, min_tokens=0):
+        """ops.check_logit_bias of one request's values against this decoder's vocabulary and stop ids: None (neutral),
+        or (b fp32 [V] on the host, min_tokens).  Values that are not neutral need a decoder built with logit_bias=True."""
+        if logit_bias is None and allowed_token_ids is None and banned_token_ids is None and min_tokens == 0:
+            return None
+        lb = ops.check_logit_bias(self.target.V, logit_bias, allowed_token_ids, banned_token_ids, min_tokens,
+                                  self.stop_token_ids)
+        if lb is not None and not self.logit_bias:
+            raise ValueError("logit_bias / allowed_token_ids / banned_token_ids / min_tokens need a decoder built with "
+                             "logit_bias=True")
+        return lb
+
     @torch.inference_mode()
     def admit(self, r: int, input_ids: torch.Tensor, temperature: float = 0.0, seed: Optional[int] = None,
               top_k: int = 0, top_p: float = 1.0, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
-              frequency_penalty: float = 0.0) -> None:
+              frequency_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None, banned_token_ids=None,
+              min_tokens: int = 0) -> None:
         """Prefill request r (model/dflash.py:218-229): target prefill through the wrapped
         model, K/V into the group cache, first token sampled, the prompt's context rows
         projected into the draft cache except the last <= 16, which become the first
@@ -299,9 +338,13 @@ class BatchedDecoder:
         (otherwise those are drawn at the decoder's).
         top_k / top_p: the request's filter (a decoder built with filtering=True), written into the slot's device words.
         repetition_penalty / presence_penalty / frequency_penalty: the request's penalties (a decoder built with
-        penalties=True), likewise; the slot's table row is cleared and re-counted from this prompt."""
+        penalties=True), likewise; the slot's table row is cleared and re-counted from this prompt.
+        logit_bias / allowed_token_ids / banned_token_ids / min_tokens: the request's own (a decoder built with
+        logit_bias=True); the slot's whole bias row and min_pos are rewritten."""
         P, first, th, sd = self._admit_prefill(r, input_ids, temperature, seed, top_k, top_p,
-                                               (repetition_penalty, presence_penalty, frequency_penalty))
+                                               (repetition_penalty, presence_penalty, frequency_penalty),
+                                               dict(logit_bias=logit_bias, allowed_token_ids=allowed_token_ids,
+                                                    banned_token_ids=banned_token_ids, min_tokens=min_tokens))
         self.output_ids[r].fill_(self.mask_id)
         self.output_ids[r, :P] = input_ids[0]
         if sd is not None:
@@ -325,7 +368,8 @@ class BatchedDecoder:
     @torch.inference_mode()
     def admit_fused(self, r: int, input_ids: torch.Tensor, temperature: float = 0.0, seed: Optional[int] = None,
                     top_k: int = 0, top_p: float = 1.0, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
-                    frequency_penalty: float = 0.0) -> None:
+                    frequency_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None, banned_token_ids=None,
+                    min_tokens: int = 0) -> None:
         """`admit` with the slot re-armed by ONE launch (dfl_admit_slot) instead of a dozen small writes: ids, first
         token, block, context tile, both length records and the seed are written on the device from device-resident
         inputs, so that after the prefill launches the admission reads nothing back and copies nothing from the host —
@@ -336,7 +380,9 @@ class BatchedDecoder:
         if not 0 <= r < self.R:
             raise ValueError(f"admit_fused: slot {r} outside 0..{self.R - 1}")
         P, first, th, sd = self._admit_prefill(r, input_ids, temperature, seed, top_k, top_p,
-                                               (repetition_penalty, presence_penalty, frequency_penalty))
+                                               (repetition_penalty, presence_penalty, frequency_penalty),
+                                               dict(logit_bias=logit_bias, allowed_token_ids=allowed_token_ids,
+                                                    banned_token_ids=banned_token_ids, min_tokens=min_tokens))
         n_tail = min(16, P)
         ops.admit_slot(r, input_ids[0].contiguous(), first.reshape(1), self.output_ids, self.block, self.post, self.result,
                        th[P - n_tail:], self.d["taps"], self.dyn_d, self.dyn_t, self.BW, self.mask_id,
@@ -456,16 +502,26 @@ class BatchedDecoder:
         st.finish(t.norm)
         lm = self._t_head()
         lg = self._logits if self.lp is not None else None   # logprobs: every head below materialises its logits
-        if self.penalties:   # materialise; each slot's penalised rows and their argmax (what a greedy slot keeps); the
-            # draw over the penalised rows at the slot's seed / top_k / top_p / invT; logprobs below read the raw rows
+        if self.penalties or self.logit_bias:
+            # materialise; each slot's biased rows (row m predicts position POS0 + m + 1), then its penalised rows, each
+            # launch with the rows' argmax (what a greedy slot keeps); the draw over the last of them at the slot's seed /
+            # top_k / top_p / invT; logprobs below read the raw rows
             ops.gemm_argmax_batch(lm, s["xn"], R, t.V, H, 0, 16, self.gws, self.post.view(-1, 16), 0, dyn_t,
                                   nrows_dyn_word=ops.DYN_BS, logits=self._logits)
-            ops.penalty_rows(self._logits[:R], self.pen_table, repetition_penalty=self.pen_r, presence_penalty=self.pen_a,
-                             frequency_penalty=self.pen_f, block=self.block, out=self._pen_logits[:R], dyn=dyn_t,
-                             nrows_dyn_word=ops.DYN_BS, out_ids=self.post.view(-1, 16))
+            rows = self._logits[:R]
+            if self.logit_bias:
+                ops.logit_bias_rows(rows, self.lb.bias, min_pos=self.lb.min_pos, stop_ids=self.stop_t,
+                                    out=self._lb_logits[:R], dyn=dyn_t, nrows_dyn_word=ops.DYN_BS, pos_word=ops.DYN_POS0,
+                                    pos_add=1, out_ids=self.post.view(-1, 16))
+                rows = self._lb_logits[:R]
+            if self.penalties:
+                ops.penalty_rows(rows, self.pen_table, repetition_penalty=self.pen_r, presence_penalty=self.pen_a,
+                                 frequency_penalty=self.pen_f, block=self.block, out=self._pen_logits[:R], dyn=dyn_t,
+                                 nrows_dyn_word=ops.DYN_BS, out_ids=self.post.view(-1, 16))
+                rows = self._pen_logits[:R]
             if self.request_temperature or self.temperature >= 1e-5:
                 tkw = dict(inv_t=self.inv_ts) if self.request_temperature else dict(temperature=self.temperature)
-                ops.sample_rows_nucleus(self._pen_logits[:R], seed=self.seeds, top_k=self.top_k, top_p=self.top_p,
+                ops.sample_rows_nucleus(rows, seed=self.seeds, top_k=self.top_k, top_p=self.top_p,
                                         dyn=dyn_t, nrows_dyn_word=ops.DYN_BS, pos_word=ops.DYN_POS0, pos_add=1,
                                         tiles_per_req=TPR, out=self.post.view(-1, 16), **tkw)
         elif self.request_temperature and self.filtering:   # greedy slots keep the argmax ids the first launch wrote
@@ -672,13 +728,47 @@ def _prompt_penalties(repetition_penalty, presence_penalty, frequency_penalty, n
     return pens, any(ops.check_penalties(*p) is not None for p in pens)
 
 
+def _prompt_bias(target, logit_bias, allowed_token_ids, banned_token_ids, min_tokens, n: int, stop_token_ids):
+    """(the four keywords per prompt as dicts, whether any prompt is not neutral; target.V is read only for a prompt whose
+    keywords are given).  logit_bias: None or one mapping for every prompt, or a sequence of n (mapping or None).
+    allowed_token_ids / banned_token_ids: None or one sequence of ids for every prompt, or a sequence of n (sequence of
+    ids or None).  min_tokens: an int, or one per prompt."""
+    from collections.abc import Mapping
+
+    def is_id(v):
+        return isinstance(v, int) or (torch.is_tensor(v) and v.dim() == 0) or (hasattr(v, "__index__")
+                                                                             and not hasattr(v, "__len__"))
+
+    def per_prompt(v, one, name):
+        if one(v):
+            return [v] * n
+        v = list(v)
+        if len(v) != n:
+            raise ValueError(f"{name}: one value, or one per prompt")
+        return v
+
+    lbs = per_prompt(logit_bias, lambda v: v is None or isinstance(v, Mapping), "logit_bias")
+    ids_one = lambda v: v is None or all(is_id(x) for x in v)  # noqa: E731
+    als = per_prompt(allowed_token_ids, ids_one, "allowed_token_ids")
+    bns = per_prompt(banned_token_ids, ids_one, "banned_token_ids")
+    mts = per_prompt(min_tokens, lambda v: not hasattr(v, "__len__"), "min_tokens")
+    kws = [dict(logit_bias=lbs[i], allowed_token_ids=als[i], banned_token_ids=bns[i], min_tokens=mts[i]) for i in range(n)]
+    on = False
+    for kw in kws:
+        if not (kw["logit_bias"] is None and kw["allowed_token_ids"] is None and kw["banned_token_ids"] is None
+                and kw["min_tokens"] == 0):
+            on = ops.check_logit_bias(target.V, stop_token_ids=stop_token_ids, **kw) is not None or on
+    return kws, on
+
+
 @torch.inference_mode()
 def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_ids: Sequence[torch.Tensor],
                           mask_token_id: int, max_new_tokens: int, block_size: int, stop_token_ids,
                           temperature=0.0, draft_token_hook: Optional[Callable] = None,
                           group_size: int = MAX_GROUP, hook_block_view: bool = False, sampler: str = "torch",
                           seed=None, top_k=0, top_p=1.0, logprobs: Optional[int] = None, repetition_penalty=1.0,
-                          presence_penalty=0.0, frequency_penalty=0.0) -> list:
+                          presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, allowed_token_ids=None,
+                          banned_token_ids=None, min_tokens=0) -> list:
     """`dflash_generate` (benchmark.py:44-251) for a list of prompts: requests run in
     groups of `group_size` <= 4 (<= 2 with block sizes of 17..32 rows) that share the weight stream; returns one namespace per
     prompt with the fields of benchmark.py:242-251 (timing fields are the group's).
@@ -691,9 +781,14 @@ def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_i
     a decoder built with request_temperature=True ("Per-request temperature").
     logprobs: as dflash_generate, for every prompt (the fields logprobs / top_logprob_ids / top_logprobs; None when off).
     repetition_penalty / presence_penalty / frequency_penalty: as dflash_generate; a scalar, or one value per prompt.
-    The decoders are built with penalties=True when any prompt is not neutral (blocks of <= 16 rows)."""
+    The decoders are built with penalties=True when any prompt is not neutral (blocks of <= 16 rows).
+    logit_bias / allowed_token_ids / banned_token_ids / min_tokens: as dflash_generate; one value for every prompt, or a
+    sequence with one value (or None) per prompt.  The decoders are built with logit_bias=True when any prompt is not
+    neutral (blocks of <= 16 rows)."""
     logprobs = ops.check_logprobs(logprobs)
     pens, penalties = _prompt_penalties(repetition_penalty, presence_penalty, frequency_penalty, len(input_ids))
+    biases, logit_bias_on = _prompt_bias(target, logit_bias, allowed_token_ids, banned_token_ids, min_tokens,
+                                         len(input_ids), stop_token_ids)
     temps, per_request = _prompt_temperatures(temperature, len(input_ids), sampler)
     seeds = _prompt_seeds(sampler, seed, len(input_ids), any(t >= 1e-5 for t in temps))
     top_ks, top_ps, filtering = _prompt_filters(top_k, top_p, len(input_ids), temps, sampler)
@@ -701,6 +796,8 @@ def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_i
         raise NotImplementedError("the batched loop takes blocks of 1..16 rows (one tile per request) or 17..32 rows (two)")
     if penalties and block_size > 16:
         raise NotImplementedError("penalties take blocks of <= 16 rows")
+    if logit_bias_on and block_size > 16:
+        raise NotImplementedError("logit_bias / allowed_token_ids / banned_token_ids / min_tokens take blocks of <= 16 rows")
     tpr = 1 if block_size <= 16 else 2      # blocks of 17..32 rows: a request takes two of the group's four tiles
     group_size = min(group_size, MAX_GROUP // tpr)
     n = len(input_ids)
@@ -714,12 +811,12 @@ def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_i
                              out_len=pmax + max_new_tokens + 16 * tpr, mask_token_id=mask_token_id,
                              stop_token_ids=stop_token_ids, temperature=max(temps[i] for i in idx), tiles_per_request=tpr,
                              sampler=sampler, filtering=filtering, request_temperature=per_request, logprobs=logprobs,
-                             penalties=penalties)
+                             penalties=penalties, logit_bias=logit_bias_on)
         t0 = cuda_time()
         for r, p in enumerate(prompts):
             pr, pa, pf = pens[idx[r]]
             dec.admit(r, p, temps[idx[r]], seed=seeds[idx[r]], top_k=top_ks[idx[r]], top_p=top_ps[idx[r]],
-                      repetition_penalty=pr, presence_penalty=pa, frequency_penalty=pf)
+                      repetition_penalty=pr, presence_penalty=pa, frequency_penalty=pf, **biases[idx[r]])
         ttft = cuda_time() - t0
         taus = [[] for _ in idx]
         # (hook_block_view: the hook sees the block as the single-request loop hands it over, bs slots; default: the

@@ -15,7 +15,8 @@ from typing import Callable, Optional, Sequence, Union
 import torch
 
 from . import ops
-from .batch import MAX_GROUP, BatchedDecoder, _prompt_filters, _prompt_penalties, _prompt_seeds, _prompt_temperatures
+from .batch import (MAX_GROUP, BatchedDecoder, _prompt_bias, _prompt_filters, _prompt_penalties, _prompt_seeds,
+                    _prompt_temperatures)
 from .generate import NO_LOGPROBS, _kept_cols, _trim, cuda_time, logprob_fields
 from .slots import SlotLoop
 
@@ -59,7 +60,7 @@ class _DecoderDriver:
         ids = p.input_ids if p.input_ids.is_cuda else p.input_ids.to(self.dec.dev)
         self.dec.admit_fused(slot, ids, p.temperature, seed=p.seed, top_k=p.top_k, top_p=p.top_p,
                              repetition_penalty=p.penalties[0], presence_penalty=p.penalties[1],
-                             frequency_penalty=p.penalties[2])
+                             frequency_penalty=p.penalties[2], **p.bias)
         t1 = cuda_time()
         p.ttft, p.t_admitted = t1 - t0, t1
         self.stats["admit_s"] += t1 - t0
@@ -120,12 +121,12 @@ class BatchEngine:
     cycle runs eagerly, the decoder is captured ONCE and every later cycle of the engine's life is a replay, across
     admissions.  A precondition of the capture that does not hold raises here, nothing is swallowed."""
 
-    filtering, request_temperature, temperature, penalties = False, False, 0.0, False
+    filtering, request_temperature, temperature, penalties, logit_bias = False, False, 0.0, False, False
 
     def __init__(self, model, target, *, slots: int = MAX_GROUP, max_rows: int, out_len: int, mask_token_id: int,
                  block_size: int = 16, stop_token_ids=None, temperature: float = 0.0, sampler: str = "torch",
                  graph: Optional[bool] = None, filtering: bool = False, request_temperature: bool = False,
-                 logprobs: Optional[int] = None, penalties: bool = False):
+                 logprobs: Optional[int] = None, penalties: bool = False, logit_bias: bool = False):
         """logprobs = N (None: off): every result carries logprobs / top_logprob_ids / top_logprobs as dflash_generate
         returns them; fixed here, one capture per engine — there is no per-request switch.
         filtering: requests may carry top_k / top_p (submit); fixed here because it fixes the captured launch sequence
@@ -134,7 +135,10 @@ class BatchEngine:
         weight pass and the one capture; fixed here for the same reason, needs sampler='device' (DESIGN.md section 8,
         "Per-request temperature").  `temperature` is then the default of submit.
         penalties: requests may carry repetition / presence / frequency penalties (submit); fixed here because it fixes
-        the captured launch sequence.  Neutral requests of such an engine emit the same ids."""
+        the captured launch sequence.  Neutral requests of such an engine emit the same ids.
+        logit_bias: requests may carry logit_bias / allowed_token_ids / banned_token_ids / min_tokens (submit); fixed
+        here for the same reason.  A slot's table row and min_pos are rewritten whole on every
+        admission: nothing of the slot's previous request survives, and neutral requests emit the same ids."""
         if not 1 <= block_size <= 32:
             raise ValueError("block_size is 1..32")
         if block_size > BLOCK_ROWS:
@@ -152,8 +156,9 @@ class BatchEngine:
         self.dec = BatchedDecoder(model, target, slots, max_rows=max_rows, out_len=out_len, mask_token_id=mask_token_id,
                                   stop_token_ids=stop_token_ids, temperature=temperature, sampler=sampler,
                                   filtering=filtering, request_temperature=request_temperature, logprobs=logprobs,
-                                  penalties=penalties)
+                                  penalties=penalties, logit_bias=logit_bias)
         self.filtering, self.temperature, self.penalties = bool(filtering), float(temperature), bool(penalties)
+        self.logit_bias = bool(logit_bias)
         self.request_temperature = bool(request_temperature)
         self.stats = dict(group_cycles=0, live_slot_cycles=0, admissions=0, replayed_cycles=0, admit_s=0.0, captures=0,
                           graph=self.use_graph)
@@ -166,7 +171,8 @@ class BatchEngine:
     def submit(self, input_ids: torch.Tensor, max_new_tokens: int, *, seed: Optional[int] = None,
                draft_token_hook: Optional[Callable] = None, top_k: int = 0, top_p: float = 1.0,
                temperature: Optional[float] = None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
-               frequency_penalty: float = 0.0) -> int:
+               frequency_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None, banned_token_ids=None,
+               min_tokens: int = 0) -> int:
         """Queue a request; returns its id (ids count up in submission order).  draft_token_hook(block_view, start,
         call): `call` counts from 0 at the request's admission; the view has the cycle's block size.
         top_k / top_p: the request's own filter on its T > 0 draws (an engine built with filtering=True); accepted and
@@ -174,10 +180,17 @@ class BatchEngine:
         temperature: the request's own (None: the engine's); a value that differs from the engine's needs an engine built
         with request_temperature=True.
         repetition_penalty / presence_penalty / frequency_penalty: the request's own (an engine built with
-        penalties=True; 1.0 / 0.0 / 0.0: off)."""
+        penalties=True; 1.0 / 0.0 / 0.0: off).
+        logit_bias / allowed_token_ids / banned_token_ids / min_tokens: the request's own (an engine built with
+        logit_bias=True; None / None / None / 0: off), validated here."""
         pen = ops.check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
         if pen is not None and not self.penalties:
             raise ValueError("submit: penalties need an engine built with penalties=True")
+        bias = dict(logit_bias=logit_bias, allowed_token_ids=allowed_token_ids, banned_token_ids=banned_token_ids,
+                    min_tokens=min_tokens)
+        if (logit_bias is None and allowed_token_ids is None and banned_token_ids is None and min_tokens == 0) \
+                or self.dec.check_bias(**bias) is None:   # (raises on a bad value, and on a request an unflagged engine cannot serve)
+            bias = {}
         if input_ids.dim() != 2 or input_ids.shape[0] != 1:
             raise ValueError("submit: input_ids must be a [1, P] tensor")
         T = self.temperature if temperature is None else float(temperature)
@@ -190,7 +203,7 @@ class BatchEngine:
         req = self.loop.submit(input_ids.shape[1], int(max_new_tokens),
                                SimpleNamespace(input_ids=input_ids, seed=seed, hook=draft_token_hook, result=None,
                                                ttft=0.0, t_admitted=0.0, top_k=int(top_k), top_p=float(top_p),
-                                               temperature=T, penalties=pen or (1.0, 0.0, 0.0)))
+                                               temperature=T, penalties=pen or (1.0, 0.0, 0.0), bias=bias))
         return req.rid
 
     @torch.inference_mode()
@@ -215,7 +228,8 @@ def dflash_generate_stream(model, target, input_ids: Sequence[torch.Tensor], mas
                            temperature=0.0, *, slots: int = MAX_GROUP, draft_token_hook: Optional[Callable] = None,
                            sampler: str = "torch", seed=None, top_k=0, top_p=1.0,
                            logprobs: Optional[int] = None, repetition_penalty=1.0, presence_penalty=0.0,
-                           frequency_penalty=0.0) -> list:
+                           frequency_penalty=0.0, logit_bias=None, allowed_token_ids=None, banned_token_ids=None,
+                           min_tokens=0) -> list:
     """`dflash_generate_batch` with slot refill: one namespace per prompt with the fields of benchmark.py:242-251, each
     request emitting what its own `dflash_generate` run emits.  max_new_tokens: one int or one per prompt.
     draft_token_hook(request_index, block_view, start, call).  seed as in dflash_generate_batch (an int s gives prompt i
@@ -223,7 +237,9 @@ def dflash_generate_stream(model, target, input_ids: Sequence[torch.Tensor], mas
     time, admission to last token, over its tokens.  top_k / top_p: a scalar or one value per prompt.
     temperature: one float, or one value per prompt (values that differ: sampler="device", an engine built with
     request_temperature=True).  logprobs: as dflash_generate, for every prompt.
-    repetition_penalty / presence_penalty / frequency_penalty: a scalar or one value per prompt."""
+    repetition_penalty / presence_penalty / frequency_penalty: a scalar or one value per prompt.
+    logit_bias / allowed_token_ids / banned_token_ids / min_tokens: one value for every prompt, or a sequence with one
+    value (or None) per prompt."""
     n = len(input_ids)
     mnt = [int(max_new_tokens)] * n if isinstance(max_new_tokens, int) else [int(x) for x in max_new_tokens]
     if len(mnt) != n:
@@ -235,14 +251,16 @@ def dflash_generate_stream(model, target, input_ids: Sequence[torch.Tensor], mas
     seeds = _prompt_seeds(sampler, seed, n, any(t >= 1e-5 for t in temps))
     top_ks, top_ps, filtering = _prompt_filters(top_k, top_p, n, temps, sampler)
     pens, penalties = _prompt_penalties(repetition_penalty, presence_penalty, frequency_penalty, n)
+    biases, logit_bias_on = _prompt_bias(target, logit_bias, allowed_token_ids, banned_token_ids, min_tokens, n,
+                                         stop_token_ids)
     need = max([p.shape[1] + k for p, k in zip(input_ids, mnt)] + [1])
     eng = BatchEngine(model, target, slots=max(1, min(slots, max(n, 1))), max_rows=need + 3 * BLOCK_ROWS,
                       out_len=need + BLOCK_ROWS, mask_token_id=mask_token_id, block_size=block_size,
                       stop_token_ids=stop_token_ids, temperature=max(temps, default=0.0), sampler=sampler, filtering=filtering,
-                      request_temperature=per_request, logprobs=logprobs, penalties=penalties)
+                      request_temperature=per_request, logprobs=logprobs, penalties=penalties, logit_bias=logit_bias_on)
     for i, p in enumerate(input_ids):
         hook = (lambda blk, start, call, i=i: draft_token_hook(i, blk, start, call)) if draft_token_hook else None
         eng.submit(p, mnt[i], seed=seeds[i], draft_token_hook=hook, top_k=top_ks[i], top_p=top_ps[i],
                    temperature=temps[i], repetition_penalty=pens[i][0], presence_penalty=pens[i][1],
-                   frequency_penalty=pens[i][2])
+                   frequency_penalty=pens[i][2], **biases[i])
     return eng.run()

@@ -186,6 +186,18 @@ def logprob_fields(sink, row: int, cols: torch.Tensor) -> dict:
 NO_LOGPROBS = dict(logprobs=None, top_logprob_ids=None, top_logprobs=None)
 
 
+def _vocab_of(target) -> int:
+    """The vocabulary the logit-bias keywords are validated against: a NativeTarget's V, else the wrapped model's
+    config.vocab_size (only to tell neutral values from a request such a target cannot serve)."""
+    v = getattr(target, "V", None)
+    if v is None:
+        v = getattr(getattr(target, "config", None), "vocab_size", None)
+    if v is None:
+        raise ValueError("logit_bias / allowed_token_ids / banned_token_ids / min_tokens need a dflash_amd.NativeTarget "
+                         "(the kernel reads the verify's materialised logits)")
+    return int(v)
+
+
 class DecodeSession:
     """State of one request between cycles (what the reference keeps in local
     variables of its while-loop, model/dflash.py:206-233)."""
@@ -194,8 +206,25 @@ class DecodeSession:
                  max_block_size: int, stop_token_ids, temperature: float, draft_temperature: float = 0.0,
                  draft_token_hook: Optional[Callable] = None, sampler: str = "torch", seed: Optional[int] = None,
                  top_k: int = 0, top_p: float = 1.0, logprobs: Optional[int] = None, repetition_penalty: float = 1.0,
-                 presence_penalty: float = 0.0, frequency_penalty: float = 0.0):
+                 presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None,
+                 banned_token_ids=None, min_tokens: int = 0):
         from .target import NativeTarget
+        # logit_bias / allowed_token_ids / banned_token_ids / min_tokens on the TARGET's rows; all
+        # neutral: None, and every launch below is the one enqueued without the keywords
+        lb = None
+        if not (logit_bias is None and allowed_token_ids is None and banned_token_ids is None and min_tokens == 0):
+            lb = ops.check_logit_bias(_vocab_of(target), logit_bias, allowed_token_ids, banned_token_ids, min_tokens,
+                                      stop_token_ids)
+        if lb is not None:
+            if not isinstance(target, NativeTarget):
+                raise ValueError("logit_bias / allowed_token_ids / banned_token_ids / min_tokens need a "
+                                 "dflash_amd.NativeTarget (the kernel reads the verify's materialised logits)")
+            if temperature >= 1e-5 and sampler != "device":
+                raise ValueError("logit_bias / allowed_token_ids / banned_token_ids / min_tokens at T > 0 need "
+                                 "sampler='device' (sampler='torch' is the reference's multinomial over the raw logits)")
+            if int(max_block_size) > 16:
+                raise NotImplementedError("logit_bias / allowed_token_ids / banned_token_ids / min_tokens take blocks of "
+                                          "<= 16 rows (the 17..32-row verify is not covered)")
         # repetition / presence / frequency penalties on the TARGET's rows; all three neutral:
         # None, and every launch below is the one enqueued without the keywords
         pen = ops.check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
@@ -269,6 +298,15 @@ class DecodeSession:
             if self.lm_wp8 is None:
                 self.lm_wp8 = model.packed_lm_head_fp8(target.lm_head)
         self.stop_t = torch.tensor(stop_token_ids, dtype=torch.long, device=dev) if stop_token_ids else None
+        # the logit-bias state: the dense table row and min_pos = n_in + min_tokens (written once: a session is one
+        # request), the stop ids the accept launch takes, and the buffer the verify writes its biased rows into
+        self.lb = None
+        if lb is not None:
+            self.lb = ops.logit_bias_state(1, target.V, dev)
+            ops.logit_bias_set(self.lb, 0, lb[0], self.n_in + lb[1] if lb[1] else 0)
+            self.lb.stop = self.stop_t
+            self.lb.logits = torch.zeros(16, target.V, dtype=torch.bfloat16, device=dev)
+            self._lpkw = dict(self._lpkw, logit_bias=self.lb)
         # the reference scans the whole buffer, mask slots included (model/dflash.py:265-268)
         self.stop_always = stop_token_ids is not None and mask_token_id in stop_token_ids
         # the accept result {acc, new start, stop, cycle}: pinned host memory the kernel writes with one 16-byte store and
@@ -314,8 +352,8 @@ class DecodeSession:
                               past_key_values=self.tcache, use_cache=True, logits_to_keep=1,
                               output_hidden_states=self.use_draft)
         self.output_ids[:, :self.n_in] = self.input_ids
-        if self.pen is not None:
-            self._first_token_penalised(out.logits[0, -1:])
+        if self.pen is not None or self.lb is not None:
+            self._first_token_processed(out.logits[0, -1:])
         elif self._tseed is not None:   # the first new token draws position n_in
             self.output_ids[:, self.n_in:self.n_in + 1] = _draw_rows(out.logits[:, -1:], self.temperature, self._tseed,
                                                                      self.n_in, self._filter)
@@ -327,18 +365,24 @@ class DecodeSession:
         if self.use_draft:
             self.target_hidden = _taps(out.hidden_states, self.model.target_layer_ids)
 
-    def _first_token_penalised(self, row: torch.Tensor) -> None:
-        """The first new token under penalties: the prompt is counted into a cleared table row, the prompt's last-row
-        logits are penalised by it, the token is their argmax or the seeded draw at position n_in over them, and it is
-        counted as output."""
-        p, n = self.pen, self.n_in
-        ops.penalty_count(p.table, self.output_ids, lo=0, hi=n, as_prompt=True, clear=True)
+    def _first_token_processed(self, row: torch.Tensor) -> None:
+        """The first new token under logit bias and / or penalties.  The prompt's last-row logits predict position n_in:
+        they take the bias row (and lose the stop ids under min_tokens >= 1); under penalties the prompt is counted into a
+        cleared table row and the rows are penalised by it; the token is their argmax or the seeded draw at position
+        n_in over them, and it is counted as output."""
+        p, lb, n = self.pen, self.lb, self.n_in
         first = self.output_ids[0, n:n + 1]
-        z = ops.penalty_rows(row.to(torch.bfloat16).contiguous(), p.table, repetition_penalty=p.r, presence_penalty=p.a,
-                             frequency_penalty=p.f, out_ids=first)
+        z = row.to(torch.bfloat16).contiguous()
+        if lb is not None:
+            z = ops.logit_bias_rows(z, lb.bias, min_pos=lb.min_pos, stop_ids=lb.stop, pos_base=n, out_ids=first)
+        if p is not None:
+            ops.penalty_count(p.table, self.output_ids, lo=0, hi=n, as_prompt=True, clear=True)
+            z = ops.penalty_rows(z, p.table, repetition_penalty=p.r, presence_penalty=p.a, frequency_penalty=p.f,
+                                 out_ids=first)
         if self._tseed is not None:
             first.copy_(_draw_rows(z.unsqueeze(0), self.temperature, self._tseed, n, self._filter)[0])
-        ops.penalty_count(p.table, self.output_ids, lo=n, hi=n + 1)
+        if p is not None:
+            ops.penalty_count(p.table, self.output_ids, lo=n, hi=n + 1)
 
     def _count_committed(self) -> None:
         """Right behind an accept launch: what it committed, output_ids(S, START] of the draft record it has just
@@ -603,7 +647,8 @@ class DecodeSession:
                         self.lm_wp, self.lm_wp8, self.embed_w, getattr(t, "lm_wp", None),
                         t.fp8_tensors() if self.native else (),    # (an fp8 target's codes and scale vectors)
                         getattr(t, "_nuc_logits", None),           # (the logits a filtered, logprobs or penalised verify materialises)
-                        self.pen))                                 # (the penalty table and the penalised rows: the session's own)
+                        self.pen,                                  # (the penalty table and the penalised rows: the session's own)
+                        self.lb))                                  # (the bias table, min_pos and the biased rows likewise)
 
     def _tables_moved(self, rec: _Replay) -> bool:
         """A shared draft model / NativeTarget replaces its RoPE table when another caller needs more positions
@@ -744,13 +789,15 @@ def run_decode(model, target, input_ids: torch.Tensor, *, mask_token_id: int, ma
                draft_temperature: float = 0.0, draft_token_hook: Optional[Callable] = None,
                max_block_size: Optional[int] = None, sampler: str = "torch", seed: Optional[int] = None,
                top_k: int = 0, top_p: float = 1.0, logprobs: Optional[int] = None, repetition_penalty: float = 1.0,
-               presence_penalty: float = 0.0, frequency_penalty: float = 0.0) -> SimpleNamespace:
+               presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None,
+               banned_token_ids=None, min_tokens: int = 0) -> SimpleNamespace:
     s = DecodeSession(model, target, input_ids, mask_token_id=mask_token_id, max_new_tokens=max_new_tokens,
                       max_block_size=max_block_size or block_size, stop_token_ids=stop_token_ids,
                       temperature=temperature, draft_temperature=draft_temperature,
                       draft_token_hook=draft_token_hook, sampler=sampler, seed=seed, top_k=top_k, top_p=top_p,
                       logprobs=logprobs, repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
-                      frequency_penalty=frequency_penalty)
+                      frequency_penalty=frequency_penalty, logit_bias=logit_bias, allowed_token_ids=allowed_token_ids,
+                      banned_token_ids=banned_token_ids, min_tokens=min_tokens)
     t_prefill = cuda_time()
     s.prefill()
     time_to_first_token = cuda_time() - t_prefill
@@ -917,8 +964,13 @@ def dflash_generate(model, target, input_ids: torch.Tensor, mask_token_id: int, 
                     draft_steps: int = 1, draft_token_hook=None, sampler: str = "torch",
                     seed: Optional[int] = None, top_k: int = 0, top_p: float = 1.0,
                     logprobs: Optional[int] = None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
-                    frequency_penalty: float = 0.0) -> SimpleNamespace:
+                    frequency_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None, banned_token_ids=None,
+                    min_tokens: int = 0) -> SimpleNamespace:
     """benchmark.py:44-55 signature; returns the namespace of :242-251 (+ replayed_cycles).
+    logit_bias ({id: bias}, finite or -inf) / allowed_token_ids / banned_token_ids / min_tokens (None / None / None / 0:
+    off; need a NativeTarget, blocks of <= 16 rows, and sampler="device" at T > 0): the OpenAI / vLLM controls on the
+    target's logits, applied before the penalties; no stop id is emitted before min_tokens tokens are out (DESIGN.md
+    section 14).  The draft's proposals stay unprocessed.
     repetition_penalty r / presence_penalty a / frequency_penalty f (1.0 / 0.0 / 0.0: off; need a NativeTarget, blocks of
     <= 16 rows, and sampler="device" at T > 0): the vLLM / OpenAI penalties on the target's logits, history = the prompt
     and everything emitted so far, the draft tokens in front of a verify row included.  The draft's
@@ -933,13 +985,16 @@ def dflash_generate(model, target, input_ids: torch.Tensor, mask_token_id: int, 
     if getattr(model, "wide_hidden", False):
         return _generate_wide_hidden(model, target, input_ids, mask_token_id, max_new_tokens, block_size, stop_token_ids,
                                      temperature, collect_profile, draft_steps, draft_token_hook, sampler, seed, top_k, top_p,
-                                     logprobs, (repetition_penalty, presence_penalty, frequency_penalty))
+                                     logprobs, (repetition_penalty, presence_penalty, frequency_penalty),
+                                     dict(logit_bias=logit_bias, allowed_token_ids=allowed_token_ids,
+                                          banned_token_ids=banned_token_ids, min_tokens=min_tokens))
     r = run_decode(model, target, input_ids, mask_token_id=mask_token_id, max_new_tokens=max_new_tokens,
                    block_size=block_size, stop_token_ids=stop_token_ids, temperature=temperature, clamp_tail=True,
                    draft_steps=draft_steps, collect_profile=collect_profile, draft_token_hook=draft_token_hook,
                    sampler=sampler, seed=seed, top_k=top_k, top_p=top_p, logprobs=logprobs,
                    repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
-                   frequency_penalty=frequency_penalty)
+                   frequency_penalty=frequency_penalty, logit_bias=logit_bias, allowed_token_ids=allowed_token_ids,
+                   banned_token_ids=banned_token_ids, min_tokens=min_tokens)
     return SimpleNamespace(output_ids=r.output_ids, num_input_tokens=r.num_input_tokens,
                            num_output_tokens=r.num_output_tokens, time_to_first_token=r.time_to_first_token,
                            time_per_output_token=r.time_per_output_token, acceptance_lengths=r.acceptance_lengths,
@@ -950,7 +1005,8 @@ def dflash_generate(model, target, input_ids: torch.Tensor, mask_token_id: int, 
 
 def _generate_wide_hidden(model, target, input_ids, mask_token_id, max_new_tokens, block_size, stop_token_ids, temperature,
                           collect_profile=False, draft_steps=1, draft_token_hook=None, sampler="torch",
-                          seed=None, top_k=0, top_p=1.0, logprobs=None, penalties=(1.0, 0.0, 0.0)) -> SimpleNamespace:
+                          seed=None, top_k=0, top_p=1.0, logprobs=None, penalties=(1.0, 0.0, 0.0),
+                          bias=None) -> SimpleNamespace:
     """hidden_size > 4096: the request runs as a group of ONE through the ragged-batch kernels (their GEMMs cut K over
     workgroups; the single-request kernels keep a whole K = hidden row slice per workgroup).  Same loop semantics
     (benchmark.py:44-251, tail clamp included); no per-cycle profile, one draft step per cycle."""
@@ -966,7 +1022,16 @@ def _generate_wide_hidden(model, target, input_ids, mask_token_id, max_new_token
                                  temperature, draft_token_hook=hook, group_size=1, hook_block_view=True, sampler=sampler,
                                  seed=None if seed is None else [seed], top_k=top_k, top_p=top_p, logprobs=logprobs,
                                  repetition_penalty=penalties[0], presence_penalty=penalties[1],
-                                 frequency_penalty=penalties[2])[0]
+                                 frequency_penalty=penalties[2], **_one_prompt_bias(bias))[0]
+
+
+def _one_prompt_bias(bias) -> dict:
+    """A single request's logit-bias keywords in the per-prompt form dflash_generate_batch takes (lists are values
+    there: one per prompt)."""
+    if not bias:
+        return {}
+    return dict(logit_bias=[bias["logit_bias"]], allowed_token_ids=[bias["allowed_token_ids"]],
+                banned_token_ids=[bias["banned_token_ids"]], min_tokens=bias["min_tokens"])
 
 
 def dflash_generate_policy(*, model, target, input_ids: torch.Tensor, mask_token_id: int, max_new_tokens: int,
@@ -974,13 +1039,14 @@ def dflash_generate_policy(*, model, target, input_ids: torch.Tensor, mask_token
                            scheduler=None, draft_token_hook=None, sampler: str = "torch",
                            seed: Optional[int] = None, top_k: int = 0, top_p: float = 1.0,
                            logprobs: Optional[int] = None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
-                           frequency_penalty: float = 0.0) -> SimpleNamespace:
+                           frequency_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None, banned_token_ids=None,
+                           min_tokens: int = 0) -> SimpleNamespace:
     """benchmark_dynamic_schedule.py:260-272 signature; returns the namespace of :425-434 (+ replayed_cycles).
     logprobs: as dflash_generate (the fields logprobs / top_logprob_ids / top_logprobs; None when off).
     sampler / seed: as dflash_generate; the draft's own T > 0 draw uses the same seed on a stream of its own.
     top_k / top_p: as dflash_generate (the target's draw; the draft's own draw stays unfiltered).
     repetition_penalty / presence_penalty / frequency_penalty: as dflash_generate (the target's rows; the draft's own
-    draw stays unpenalised)."""
+    draw stays unpenalised).  logit_bias / allowed_token_ids / banned_token_ids / min_tokens: likewise."""
     if fixed_block_size is None and scheduler is None:
         raise ValueError("Either fixed_block_size or scheduler must be provided.")
     max_bs = fixed_block_size if fixed_block_size is not None else max(scheduler.candidates)
@@ -990,7 +1056,8 @@ def dflash_generate_policy(*, model, target, input_ids: torch.Tensor, mask_token
                    scheduler=sched, draft_temperature=temperature, max_block_size=max_bs,
                    draft_token_hook=draft_token_hook, sampler=sampler, seed=seed, top_k=top_k, top_p=top_p,
                    logprobs=logprobs, repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
-                   frequency_penalty=frequency_penalty)
+                   frequency_penalty=frequency_penalty, logit_bias=logit_bias, allowed_token_ids=allowed_token_ids,
+                   banned_token_ids=banned_token_ids, min_tokens=min_tokens)
     if fixed_block_size is not None:
         for row in r.cycle_trace:
             for k in ("tau_hat", "cycle_hat", "score_hat", "current_block_size", "adl_lgen_hat", "adl_lacc_hat",

@@ -786,6 +786,144 @@ def penalty_rows(logits: torch.Tensor, table: torch.Tensor, *, repetition_penalt
     return out
 
 
+def check_logit_bias(V: int, logit_bias=None, allowed_token_ids=None, banned_token_ids=None, min_tokens=0,
+                     stop_token_ids=None):
+    """Validate one request's logit_bias ({id: bias}, finite or -inf), allowed_token_ids (non-empty), banned_token_ids
+    and min_tokens (int >= 0) for a vocabulary of V.  None when everything is neutral: no / empty
+    mapping and lists, a mapping of zeros, min_tokens == 0 or no stop ids — the path without the feature.  Otherwise
+    (b, min_tokens): b a host fp32 tensor [V] with -inf where a token is not allowed, banned or biased by -inf, the bias
+    (or 0) elsewhere; min_tokens 0 when there is no stop id to suppress."""
+    import math
+    import operator
+
+    def ids_of(seq, name):
+        out = []
+        for v in seq:
+            try:
+                i = operator.index(v)
+            except TypeError:
+                raise ValueError(f"dflash_amd: {name}: {v!r} is not a token id") from None
+            if not 0 <= i < V:
+                raise ValueError(f"dflash_amd: {name}: id {i} outside [0, {V})")
+            out.append(i)
+        return out
+
+    try:
+        mt = operator.index(min_tokens)
+    except TypeError:
+        raise ValueError(f"dflash_amd: min_tokens must be an integer >= 0, got {min_tokens!r}") from None
+    if mt < 0:
+        raise ValueError(f"dflash_amd: min_tokens must be an integer >= 0, got {min_tokens!r}")
+    stops = [int(s) for s in (stop_token_ids if stop_token_ids is not None else ())]
+    if not stops:
+        mt = 0      # nothing to suppress
+    b = torch.zeros(V, dtype=F32)
+    for k, v in (logit_bias or {}).items():
+        i = ids_of([int(k) if isinstance(k, str) else k], "logit_bias")[0]
+        v = float(v)
+        if math.isnan(v) or v == math.inf or (v != -math.inf and abs(v) > 3.4028234663852886e38):
+            raise ValueError(f"dflash_amd: logit_bias[{i}] = {v!r}: a bias is finite in fp32, or -inf for a ban")
+        b[i] = v
+    if allowed_token_ids is not None:
+        allowed = ids_of(allowed_token_ids, "allowed_token_ids")
+        if not allowed:
+            raise ValueError("dflash_amd: allowed_token_ids is empty (None: no allow list)")
+        keep = torch.zeros(V, dtype=torch.bool)
+        keep[torch.tensor(allowed, dtype=I64)] = True
+        b[~keep] = -math.inf
+    if banned_token_ids is not None:
+        banned = ids_of(banned_token_ids, "banned_token_ids")
+        if banned:
+            b[torch.tensor(banned, dtype=I64)] = -math.inf
+    live = b > -math.inf
+    if mt > 0:
+        for s in stops:
+            if 0 <= s < V:
+                live[s] = False
+    if not bool(live.any()):
+        raise ValueError("dflash_amd: logit_bias / allowed_token_ids / banned_token_ids / min_tokens leave no token finite")
+    if mt == 0 and not bool((b != 0).any()):
+        return None
+    return b, mt
+
+
+def logit_bias_state(slots: int, V: int, device) -> SimpleNamespace:
+    """The logit-bias state: .bias fp32 [slots, V], zeroed — one dense table row per request slot —
+    and .min_pos int32 [slots], zeroed (0: min_tokens off).  Written by logit_bias_set, read by logit_bias_rows."""
+    if V < 8 or V % 8:
+        raise ValueError(f"dflash_amd: logit bias needs a vocabulary that is a multiple of 8, got {V}")
+    return SimpleNamespace(bias=torch.zeros(slots, V, dtype=F32, device=device),
+                           min_pos=torch.zeros(slots, dtype=I32, device=device))
+
+
+def logit_bias_set(state, slot: int, b, min_pos: int = 0) -> None:
+    """Rewrite slot's whole table row (b: a host or device fp32 [V], None: zeros) and its min_pos: nothing of the slot's
+    previous request survives.  Admission only, plain copies."""
+    if not 0 <= slot < state.bias.shape[0]:
+        raise ValueError(f"dflash_amd: logit_bias_set: slot {slot} outside 0..{state.bias.shape[0] - 1}")
+    if b is None:
+        state.bias[slot].zero_()
+    else:
+        b = torch.as_tensor(b, dtype=F32)
+        if b.shape != (state.bias.shape[1],):
+            raise ValueError(f"dflash_amd: logit_bias_set: b has shape {tuple(b.shape)}, the table row ({state.bias.shape[1]},)")
+        state.bias[slot].copy_(b)
+    state.min_pos[slot:slot + 1].fill_(int(min_pos))
+
+
+def logit_bias_rows(logits: torch.Tensor, bias: torch.Tensor, *, min_pos=0, stop_ids: Optional[torch.Tensor] = None,
+                    out: Optional[torch.Tensor] = None, row0: int = 0, nrows: Optional[int] = None, dyn=None,
+                    nrows_dyn_word: int = -1, pos_word: int = -1, pos_base: int = 0, pos_add: int = 0,
+                    tiles_per_req: int = 1, out_ids: Optional[torch.Tensor] = None, out_off: int = 0) -> torch.Tensor:
+    """Biased logits (dfl_logit_bias_rows) of materialised bf16 logits [rows <= 16, V] (one tile) or
+    [tiles, 16, V], unit inner stride; returns `out` (same shape and strides; None: a new buffer; the logits themselves:
+    in place).  bias fp32 [slots, V] or [V]: row m of tile j of slot q takes table row q and predicts position
+    (dyn[t][pos_word] if pos_word >= 0 else pos_base) + pos_add + 16 j + m; while that is < min_pos (a host int, or a
+    device int32 tensor indexed by slot) the stop_ids (device int64, the accept launch's list) are set to -inf.  Rows of a
+    tile as in sample_rows_nucleus.  out_ids (int64, [tiles, n] or [n]): the rows' argmax at out_ids[t, out_off + m - row0]."""
+    assert logits.dim() in (2, 3) and logits.stride(-1) == 1 and logits.is_cuda and logits.dtype == BF16
+    if logits.dim() == 2:
+        assert logits.shape[0] <= 16, "one tile holds at most 16 rows"
+        tiles, tile_rows, tile_stride = 1, logits.shape[0], 16 * logits.stride(0)
+    else:
+        assert logits.shape[1] == 16
+        tiles, tile_rows, tile_stride = logits.shape[0], 16, logits.stride(0)
+    V, ld = logits.shape[-1], logits.stride(-2)
+    if nrows is None:
+        nrows = tile_rows - row0
+    assert 0 <= row0 and row0 + nrows <= tile_rows or nrows_dyn_word >= 0 and tile_rows == 16
+    n_out = 16 - row0 if nrows_dyn_word >= 0 else nrows
+    if out is None:
+        out = torch.empty_strided(logits.shape, logits.stride(), dtype=BF16, device=logits.device)
+    assert out.shape == logits.shape and out.stride() == logits.stride() and out.dtype == BF16 and out.is_cuda, "out"
+    if bias.dim() == 1:
+        bias = bias.unsqueeze(0)
+    slots = (tiles + tiles_per_req - 1) // tiles_per_req
+    assert bias.dim() == 2 and bias.stride(1) == 1 and bias.shape == (bias.shape[0], V) and bias.shape[0] >= slots
+    if bias.dtype != F32 or not bias.is_cuda:
+        raise TypeError("dflash_amd: the logit-bias table must be an fp32 GPU tensor")
+    mp_p, mp_v = None, 0
+    if torch.is_tensor(min_pos):
+        assert min_pos.numel() >= slots, "min_pos"
+        mp_p = _p(min_pos, I32, "min_pos")
+    else:
+        mp_v = int(min_pos)
+    n_stop = 0 if stop_ids is None else stop_ids.numel()
+    out_stride = 0
+    if out_ids is not None:
+        assert out_ids.stride(-1) == 1 and out_ids.shape[-1] >= out_off + n_out, "out_ids"
+        assert out_ids.dim() == 2 and out_ids.shape[0] >= tiles or out_ids.dim() == 1 and tiles == 1, "out_ids"
+        out_stride = out_ids.stride(0) if out_ids.dim() == 2 else 0
+    if dyn is not None:
+        assert dyn.numel() >= 8 * tiles
+    check(lib().dfl_logit_bias_rows(logits.data_ptr(), out.data_ptr(), ld, tile_stride, tiles, V, row0, nrows,
+                                    _p(dyn, I32, "dyn"), nrows_dyn_word, tiles_per_req, bias.data_ptr(), bias.stride(0),
+                                    mp_p, mp_v, _p(stop_ids, I64, "stop_ids") if n_stop else None, n_stop, pos_word,
+                                    pos_base, pos_add, _p(out_ids, I64, "out_ids"), out_stride, out_off, _stream()),
+          "dfl_logit_bias_rows")
+    return out
+
+
 def gemm_resid(wp, x, N: int, K: int, h_io: torch.Tensor, *, add_residual: bool, ss_out=None, tap=None,
                dyn=None) -> None:
     """h_io [16, >=N] bf16 (unit inner stride) updated in place; tap: optional [16, *] view

@@ -795,7 +795,7 @@ class NativeTarget:
     def verify(self, block_ids: torch.Tensor, start: int, cache: TargetKVCache, *, tap_layers: Sequence[int] = (),
                temperature: float = 0.0, logits_out: Optional[torch.Tensor] = None,
                taps_out: Optional[torch.Tensor] = None, dyn_lengths: bool = False, seed: Optional[int] = None,
-               top_k: int = 0, top_p: float = 1.0, logprobs=None, penalties=None):
+               top_k: int = 0, top_p: float = 1.0, logprobs=None, penalties=None, logit_bias=None):
         """block_ids int64 [bs] at positions start..start+bs-1 (cache rows alike), bs <= 32.
         Returns (posterior ids int64 [1, bs], taps bf16 [32, len(tap_layers)*H] or None).
         K/V of all bs rows are written; the caller crops to what it accepts.
@@ -822,13 +822,24 @@ class NativeTarget:
         the raw logits, dfl_penalty_rows writes the penalised rows into .logits — row j by the table plus the block's own
         block_ids[1 .. j] — and their argmax into the posterior; at temperature > 0 (seeded) dfl_sample_rows_nucleus then
         draws over the penalised rows (filters off: the plain seeded draw).  logprobs stay those of the raw rows
-        (DESIGN.md section 13)."""
+        (DESIGN.md section 13).
+        logit_bias: a state object (DecodeSession makes one: .bias fp32 [1, V] and .min_pos, written by
+        ops.logit_bias_set, .stop int64 stop ids on the device or None, .logits bf16 [16, V]; None: off, and nothing here
+        changes).  Blocks of <= 16 rows: behind the head launch dfl_logit_bias_rows writes the biased rows into .logits —
+        row j predicts position start + j + 1, start from the record's POS0 word under dyn_lengths, and loses the stop
+        ids while that is < min_pos — and their argmax into the posterior; the penalties, then the draw, run over those
+        rows; logprobs stay those of the raw rows."""
         bs = block_ids.numel()
         if penalties is not None:
             if bs > 16:
                 raise NotImplementedError("NativeTarget.verify: penalties take blocks of <= 16 rows")
             if temperature >= 1e-5 and seed is None:
                 raise ValueError("penalties at temperature > 0 need the seeded draw (seed=...)")
+        if logit_bias is not None:
+            if bs > 16:
+                raise NotImplementedError("NativeTarget.verify: logit_bias takes blocks of <= 16 rows")
+            if temperature >= 1e-5 and seed is None:
+                raise ValueError("logit_bias at temperature > 0 needs the seeded draw (seed=...)")
         flt = None
         if ops.check_filter(top_k, top_p) and temperature >= 1e-5:
             if seed is None:
@@ -906,19 +917,28 @@ class NativeTarget:
                 ops.logprob_rows(logits[16 * t:16 * t + 16], ids[16 * t:], logprobs, nrows=min(16, bs - 16 * t), dyn=dt,
                                  pos_word=ops.DYN_POS0 if dyn_lengths else -1, pos_base=start, pos_add=16 * t + 1)
 
-        if penalties is not None:   # one tile: raw logits, penalised rows + their argmax, the draw over them, logprobs of the raw rows
+        if penalties is not None or logit_bias is not None:
+            # one tile: raw logits; biased rows + their argmax; penalised rows + their argmax; the draw over the last of
+            # them; logprobs of the raw rows.  Row m predicts position start + m + 1, start from the record when replayed
             pen, dt = penalties, tiles[0][1]
+            pos = dict(pos_word=ops.DYN_POS0 if dyn_lengths else -1, pos_base=start, pos_add=1)
             if logits is None:
                 logits = self._nucleus_logits()
             if temperature < 1e-5 and self.x13 and not w8:
                 head = ops.bf16x13_twin(head, self.V, H, "lm_head") or head
             ops.gemm_argmax(head, fin[0], self.V, H, 0, bs, ws["argmax_ws"], post, 0, dyn=dt, logits=logits[:16])
-            ops.penalty_rows(logits[:16], pen.table, repetition_penalty=pen.r, presence_penalty=pen.a,
-                             frequency_penalty=pen.f, block=block_ids, out=pen.logits, nrows=bs, out_ids=post[:16])
-            if temperature >= 1e-5:   # row m predicts position start + m + 1, start from the record when replayed
-                ops.sample_rows_nucleus(pen.logits, seed=seed, temperature=temperature, nrows=bs, dyn=dt,
-                                        pos_word=ops.DYN_POS0 if dyn_lengths else -1, pos_base=start, pos_add=1,
-                                        out=post[:16], **(flt or dict(top_k=0, top_p=1.0)))
+            rows = logits[:16]
+            if logit_bias is not None:
+                ops.logit_bias_rows(rows, logit_bias.bias, min_pos=logit_bias.min_pos, stop_ids=logit_bias.stop,
+                                    out=logit_bias.logits, nrows=bs, dyn=dt, out_ids=post[:16], **pos)
+                rows = logit_bias.logits
+            if pen is not None:
+                ops.penalty_rows(rows, pen.table, repetition_penalty=pen.r, presence_penalty=pen.a,
+                                 frequency_penalty=pen.f, block=block_ids, out=pen.logits, nrows=bs, out_ids=post[:16])
+                rows = pen.logits
+            if temperature >= 1e-5:
+                ops.sample_rows_nucleus(rows, seed=seed, temperature=temperature, nrows=bs, dyn=dt,
+                                        out=post[:16], **pos, **(flt or dict(top_k=0, top_p=1.0)))
             if logprobs is not None:
                 lp_rows(post)
             cache.length = start + bs

@@ -543,6 +543,28 @@ int dfl_penalty_rows(const void *logits, void *out, int64_t ld, int64_t tile_str
                      float a, const float *f_dev, float f, int64_t *out_ids, int64_t out_stride, int out_off,
                      void *stream);
 
+/* Logit bias, token allow / ban lists and min_tokens.  The state is one dense table row per
+ * request slot, fp32 [slots][bias_stride >= V] (rows on 16 bytes, bias_stride a multiple of 4), and one int32 min_pos per
+ * slot.  logits / out / ld / tile_stride / tiles / V / row0 / nrows / dyn / nrows_dyn_word / tiles_per_req / out_ids /
+ * out_stride / out_off exactly as dfl_penalty_rows takes them; out may be the logits themselves; rows past a tile's valid
+ * count return at once and write nothing.  Row m of tile t (tile j = t % tiles_per_req of slot q = t / tiles_per_req)
+ * predicts position
+ *   p = (pos_word >= 0 ? dyn[t][pos_word] : pos_base) + pos_add + 16 j + m        (the rule of dfl_logprob_rows)
+ * and, x being the bf16 logit widened to fp32 and b = bias[q * bias_stride + v]:
+ *   z = (b == 0)    ? x           the bits of x copied: -0 stays -0, a NaN keeps its bits
+ *     : (b == -inf) ? -inf        whatever x is
+ *     :               x + b in fp32, rounded to bf16 nearest even (a NaN x keeps its bits)
+ *   if p < min_pos[q]:  z[s] = -inf for every s among stop_ids[0 .. n_stop) that lies in [0, V)
+ * min_pos: min_pos_dev[q] (device int32 by slot), or the host value when min_pos_dev is NULL; 0 is off.  A stop id outside
+ * [0, V) is ignored and never indexed; n_stop <= 64.  Table values are not validated: a NaN or +inf reads as 0, so every
+ * bit pattern is defined.  out_ids (optional): the processed row's argmax by the rule of dfl_penalty_rows; a fully
+ * banned row gives 0.  No floating-point atomics: the same inputs give the same bits, eager or replayed. */
+int dfl_logit_bias_rows(const void *logits, void *out, int64_t ld, int64_t tile_stride, int tiles, int V, int row0,
+                        int nrows, const int32_t *dyn, int nrows_dyn_word, int tiles_per_req, const float *bias,
+                        int64_t bias_stride, const int32_t *min_pos_dev, int min_pos, const int64_t *stop_ids, int n_stop,
+                        int pos_word, int pos_base, int pos_add, int64_t *out_ids, int64_t out_stride, int out_off,
+                        void *stream);
+
 /* Acceptance scan + commit + bonus token + stop test + length bookkeeping in one
  * wavefront (model/dflash.py:258-268):
  *   acc = #leading i with block[i+1] == posterior[i]           (0..bs-1)
