@@ -55,8 +55,14 @@ class BatchedDecoder:
                  out_len: int, mask_token_id: int, stop_token_ids=None, max_splits: int = 32,
                  temperature: float = 0.0, tiles_per_request: int = 1, sampler: str = "torch",
                  draft_temperature: float = 0.0, filtering: bool = False, request_temperature: bool = False,
-                 logprobs: Optional[int] = None, penalties: bool = False, logit_bias: bool = False):
-        """logprobs = N (None: off; fixed here, it fixes the captured launch sequence): every verify materialises its
+                 logprobs: Optional[int] = None, penalties: bool = False, logit_bias: bool = False,
+                 grammar_states: int = 0):
+        """grammar_states = N (0: off; fixed here, it fixes the captured launch sequence and the pool's address): a pool
+        of N automaton rows that add_grammar fills; requests may carry a grammar handle (admit); every verify
+        materialises its logits and dfl_grammar_rows masks each slot's rows by the state their prefix of the block
+        reaches, between the logit bias and the penalties, and dfl_grammar_advance steps the slots' states behind the
+        accept launch.  A slot without a grammar gets the ids of a decoder built without it.
+        logprobs = N (None: off; fixed here, it fixes the captured launch sequence): every verify materialises its
         logits and dfl_logprob_rows scatters the log-probability of each committed token, and the top N alternatives, to
         the token's position in the slot's row of self.lp.
         penalties (fixed here for the same reason): requests may carry repetition / presence / frequency penalties
@@ -68,6 +74,14 @@ class BatchedDecoder:
         and their argmax from the slot's table row and min_pos, ahead of the penalties and the draw.
         A slot with neutral values has a zero row and min_pos = 0 and gets the ids of a decoder built without it."""
         logprobs = ops.check_logprobs(logprobs)
+        grammar_states = int(grammar_states)
+        if grammar_states < 0:
+            raise ValueError(f"grammar_states must be >= 0 (0: off), got {grammar_states}")
+        if grammar_states and tiles_per_request != 1:
+            raise NotImplementedError("grammar takes blocks of <= 16 rows (tiles_per_request = 1)")
+        if grammar_states and temperature >= 1e-5 and sampler != "device":
+            raise ValueError("grammar at T > 0 needs sampler='device' (sampler='torch' is the reference's multinomial over "
+                             "the raw logits)")
         if logit_bias and tiles_per_request != 1:
             raise NotImplementedError("logit_bias takes blocks of <= 16 rows (tiles_per_request = 1)")
         if logit_bias and temperature >= 1e-5 and sampler != "device":
@@ -159,7 +173,14 @@ class BatchedDecoder:
         if self.logit_bias:
             self.lb = ops.logit_bias_state(NREQ, target.V, dev)
             self._lb_logits = z(MT, 16, target.V)
-        if self.filtering or self.lp is not None or self.penalties or self.logit_bias:
+        # grammar: the pool (its storage never moves: one capture serves every grammar loaded later), base / state per
+        # request slot (-1 / -1: no grammar), the grammars loaded so far (handle -> (base, dfa)) and the masked rows
+        self.grammar = None
+        if grammar_states:
+            self.grammar = ops.grammar_state(NREQ, grammar_states, target.V, dev)
+            self._grammars = []
+            self._gr_logits = z(MT, 16, target.V)
+        if self.filtering or self.lp is not None or self.penalties or self.logit_bias or self.grammar is not None:
             self._logits = z(MT, 16, target.V)
         self.output_ids = torch.full((NREQ, out_len), self.mask_id, dtype=I64, device=dev)
         self.stop_t = torch.tensor(stop_token_ids, dtype=I64, device=dev) if stop_token_ids else None
@@ -239,11 +260,14 @@ class BatchedDecoder:
 
     # ------------------------------------------------------------------ admission
     def _admit_prefill(self, r: int, input_ids: torch.Tensor, temperature: float, seed: Optional[int], top_k=0,
-                       top_p=1.0, penalties=(1.0, 0.0, 0.0), bias=None):
+                       top_p=1.0, penalties=(1.0, 0.0, 0.0), bias=None, grammar=None):
         """The launches both admissions share: target prefill into slot r's cache, the first token, the prompt's context
         rows into the draft cache except the last <= 16.  Returns (P, first token [1, 1] on the device, tapped rows
         [P, fc_in], the seed written for the slot or None)."""
         m, t = self.model, self.target
+        gr = self.check_grammar_handle(grammar)
+        if gr is not None and temperature >= 1e-5 and self.sampler != "device":
+            raise ValueError("admit: grammar at T > 0 needs sampler='device'")
         pen = ops.check_penalties(*penalties)
         if pen is not None and not self.penalties:
             raise ValueError("admit: penalties need a decoder built with penalties=True")
@@ -253,6 +277,8 @@ class BatchedDecoder:
         if lb is not None and temperature >= 1e-5 and self.sampler != "device":
             raise ValueError("admit: logit_bias / allowed_token_ids / banned_token_ids / min_tokens at T > 0 need "
                              "sampler='device'")
+        if gr is not None and lb is not None:   # a reachable state whose legal tokens this request's bias bans all
+            ops.check_grammar(gr[1], t.V, lb[0])
         flt = None
         if ops.check_filter(top_k, top_p) and temperature >= 1e-5:
             if not self.filtering:
@@ -279,6 +305,12 @@ class BatchedDecoder:
             first_logits = ops.logit_bias_rows(out.logits[0, -1:].to(BF16).contiguous(), self.lb.bias[r:r + 1],
                                                min_pos=self.lb.min_pos[r:r + 1], stop_ids=self.stop_t,
                                                pos_base=P).unsqueeze(0)
+        if self.grammar is not None:   # the slot's base and state are rewritten, whatever ran in the slot before (no
+            # grammar: -1 / -1, the rows pass unmasked); the prompt's last row is masked by the start state (no walk)
+            ops.grammar_set(self.grammar, r, gr[0] if gr else None, gr[1].start if gr else 0)
+            one = SimpleNamespace(table=self.grammar.table, base=self.grammar.base[r:r + 1],
+                                  state=self.grammar.state[r:r + 1])
+            first_logits = ops.grammar_rows(first_logits[0, -1:].to(BF16).contiguous(), one).unsqueeze(0)
         if self.penalties:   # the slot's table row starts from the prompt alone, whatever ran in the slot before; the
             # first token comes from the prompt's last row penalised by it (no block in front of it)
             pr, pa, pf = pen or (1.0, 0.0, 0.0)
@@ -298,6 +330,8 @@ class BatchedDecoder:
             self.pen_r[r:r + 1].fill_(pr)
             self.pen_a[r:r + 1].fill_(pa)
             self.pen_f[r:r + 1].fill_(pf)
+        if self.grammar is not None:   # the first token is output: the slot's state steps over it
+            ops.grammar_advance(one, first.reshape(1, 1), lo=0, hi=1)
         if self.lp is not None:   # the first token's value, from the prompt's last-row logits: nothing is read back
             sink = SimpleNamespace(**{**vars(self.lp), "slot": r})
             ops.logprob_rows(out.logits[0, -1:].to(BF16).contiguous(), first.reshape(1), sink, pos_base=P)
@@ -325,11 +359,50 @@ class BatchedDecoder:
                              "logit_bias=True")
         return lb
 
+    grammar = None   # (the state of a decoder built with grammar_states > 0)
+
+    def add_grammar(self, dfa) -> int:
+        """Validate a TokenDFA (ops.check_grammar) and copy its table into the pool's next free rows; returns the handle
+        admit takes.  ValueError when the decoder was built without a pool or the pool is full.  The pool's address is
+        fixed, so a captured cycle serves grammars loaded after the capture."""
+        if self.grammar is None:
+            raise ValueError("add_grammar needs a decoder built with grammar_states > 0")
+        base = ops.grammar_load(self.grammar, dfa)
+        self._grammars.append((base, dfa))
+        return len(self._grammars) - 1
+
+    def check_grammar_handle(self, handle):
+        """(base, dfa) of a handle add_grammar returned; None for None."""
+        if handle is None:
+            return None
+        if self.grammar is None:
+            raise ValueError("grammar needs a decoder built with grammar_states > 0")
+        if isinstance(handle, bool) or not isinstance(handle, int) or not 0 <= handle < len(self._grammars):
+            raise ValueError(f"grammar: {handle!r} is no handle add_grammar returned")
+        return self._grammars[handle]
+
+    def grammar_state_of(self, r: int, ids: torch.Tensor, n_in: int):
+        """The result field grammar_state of slot r's request: the state after the generated tokens ids[n_in:] (1-D, as
+        returned), walked by dfl_grammar_advance from the grammar's start; -1 where one is illegal or the slot's own state
+        was violated; None when the slot has no grammar (DecodeSession.finish_grammar has the reasons)."""
+        if self.grammar is None:
+            return None
+        base, st = int(self.grammar.base[r]), int(self.grammar.state[r])
+        if base < 0:
+            return None
+        if st < 0:
+            return -1
+        start = next(d.start for b, d in self._grammars if b == base)
+        g = SimpleNamespace(table=self.grammar.table, base=self.grammar.base[r:r + 1],
+                            state=torch.full((1,), int(start), dtype=I32, device=self.dev))
+        ops.grammar_advance(g, ids.contiguous(), lo=n_in, hi=ids.shape[0])
+        return int(g.state.item())
+
     @torch.inference_mode()
     def admit(self, r: int, input_ids: torch.Tensor, temperature: float = 0.0, seed: Optional[int] = None,
               top_k: int = 0, top_p: float = 1.0, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
               frequency_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None, banned_token_ids=None,
-              min_tokens: int = 0) -> None:
+              min_tokens: int = 0, grammar=None) -> None:
         """Prefill request r (model/dflash.py:218-229): target prefill through the wrapped
         model, K/V into the group cache, first token sampled, the prompt's context rows
         projected into the draft cache except the last <= 16, which become the first
@@ -340,11 +413,13 @@ class BatchedDecoder:
         repetition_penalty / presence_penalty / frequency_penalty: the request's penalties (a decoder built with
         penalties=True), likewise; the slot's table row is cleared and re-counted from this prompt.
         logit_bias / allowed_token_ids / banned_token_ids / min_tokens: the request's own (a decoder built with
-        logit_bias=True); the slot's whole bias row and min_pos are rewritten."""
+        logit_bias=True); the slot's whole bias row and min_pos are rewritten.
+        grammar: a handle add_grammar returned (None: no grammar, the slot's rows pass unmasked); the slot's base and
+        state are rewritten."""
         P, first, th, sd = self._admit_prefill(r, input_ids, temperature, seed, top_k, top_p,
                                                (repetition_penalty, presence_penalty, frequency_penalty),
                                                dict(logit_bias=logit_bias, allowed_token_ids=allowed_token_ids,
-                                                    banned_token_ids=banned_token_ids, min_tokens=min_tokens))
+                                                    banned_token_ids=banned_token_ids, min_tokens=min_tokens), grammar)
         self.output_ids[r].fill_(self.mask_id)
         self.output_ids[r, :P] = input_ids[0]
         if sd is not None:
@@ -369,7 +444,7 @@ class BatchedDecoder:
     def admit_fused(self, r: int, input_ids: torch.Tensor, temperature: float = 0.0, seed: Optional[int] = None,
                     top_k: int = 0, top_p: float = 1.0, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
                     frequency_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None, banned_token_ids=None,
-                    min_tokens: int = 0) -> None:
+                    min_tokens: int = 0, grammar=None) -> None:
         """`admit` with the slot re-armed by ONE launch (dfl_admit_slot) instead of a dozen small writes: ids, first
         token, block, context tile, both length records and the seed are written on the device from device-resident
         inputs, so that after the prefill launches the admission reads nothing back and copies nothing from the host —
@@ -382,7 +457,7 @@ class BatchedDecoder:
         P, first, th, sd = self._admit_prefill(r, input_ids, temperature, seed, top_k, top_p,
                                                (repetition_penalty, presence_penalty, frequency_penalty),
                                                dict(logit_bias=logit_bias, allowed_token_ids=allowed_token_ids,
-                                                    banned_token_ids=banned_token_ids, min_tokens=min_tokens))
+                                                    banned_token_ids=banned_token_ids, min_tokens=min_tokens), grammar)
         n_tail = min(16, P)
         ops.admit_slot(r, input_ids[0].contiguous(), first.reshape(1), self.output_ids, self.block, self.post, self.result,
                        th[P - n_tail:], self.d["taps"], self.dyn_d, self.dyn_t, self.BW, self.mask_id,
@@ -502,8 +577,9 @@ class BatchedDecoder:
         st.finish(t.norm)
         lm = self._t_head()
         lg = self._logits if self.lp is not None else None   # logprobs: every head below materialises its logits
-        if self.penalties or self.logit_bias:
-            # materialise; each slot's biased rows (row m predicts position POS0 + m + 1), then its penalised rows, each
+        if self.penalties or self.logit_bias or self.grammar is not None:
+            # materialise; each slot's biased rows (row m predicts position POS0 + m + 1), then its grammar-masked rows
+            # (row m by the slot's state walked through block[1 .. m]), then its penalised rows, each
             # launch with the rows' argmax (what a greedy slot keeps); the draw over the last of them at the slot's seed /
             # top_k / top_p / invT; logprobs below read the raw rows
             ops.gemm_argmax_batch(lm, s["xn"], R, t.V, H, 0, 16, self.gws, self.post.view(-1, 16), 0, dyn_t,
@@ -514,6 +590,10 @@ class BatchedDecoder:
                                     out=self._lb_logits[:R], dyn=dyn_t, nrows_dyn_word=ops.DYN_BS, pos_word=ops.DYN_POS0,
                                     pos_add=1, out_ids=self.post.view(-1, 16))
                 rows = self._lb_logits[:R]
+            if self.grammar is not None:
+                ops.grammar_rows(rows, self.grammar, block=self.block, out=self._gr_logits[:R], dyn=dyn_t,
+                                 nrows_dyn_word=ops.DYN_BS, out_ids=self.post.view(-1, 16))
+                rows = self._gr_logits[:R]
             if self.penalties:
                 ops.penalty_rows(rows, self.pen_table, repetition_penalty=self.pen_r, presence_penalty=self.pen_a,
                                  frequency_penalty=self.pen_f, block=self.block, out=self._pen_logits[:R], dyn=dyn_t,
@@ -568,6 +648,9 @@ class BatchedDecoder:
         if self.penalties:   # what the launch committed, output_ids(S, START] of each live slot; a parked slot is idle
             ops.penalty_count(self.pen_table[:self.R], self.output_ids, dyn=self.dyn_d, lo_word=ops.DYN_S,
                               hi_word=ops.DYN_START, lo=1, hi=1)
+        if self.grammar is not None:   # the same range steps each live slot's automaton state
+            ops.grammar_advance(self.grammar, self.output_ids, slots=self.R, dyn=self.dyn_d, lo_word=ops.DYN_S,
+                                hi_word=ops.DYN_START, lo=1, hi=1)
 
     def accept(self, launch: bool = True) -> list:
         """Acceptance scan + commit + rollback bookkeeping of all requests (:258-268) and
@@ -761,6 +844,31 @@ def _prompt_bias(target, logit_bias, allowed_token_ids, banned_token_ids, min_to
     return kws, on
 
 
+def _prompt_grammars(grammar, n: int) -> list:
+    """One TokenDFA (or None) per prompt: None or one TokenDFA for every prompt, or a sequence of n (TokenDFA or None)."""
+    if grammar is None or hasattr(grammar, "next"):
+        return [grammar] * n
+    g = list(grammar)
+    if len(g) != n:
+        raise ValueError("grammar: one TokenDFA, or one per prompt")
+    return g
+
+
+def _load_grammars(dec, dfas) -> list:
+    """The handles of `dfas` (TokenDFA or None each) in decoder / engine `dec`, every distinct automaton loaded once."""
+    seen, out = {}, []
+    for d in dfas:
+        if d is not None and id(d) not in seen:
+            seen[id(d)] = dec.add_grammar(d)
+        out.append(None if d is None else seen[id(d)])
+    return out
+
+
+def _pool_rows(dfas) -> int:
+    """The pool rows the distinct (validated) automata among `dfas` need (0: none given)."""
+    return sum(int(d.next.shape[0]) for d in {id(d): d for d in dfas if d is not None}.values())
+
+
 @torch.inference_mode()
 def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_ids: Sequence[torch.Tensor],
                           mask_token_id: int, max_new_tokens: int, block_size: int, stop_token_ids,
@@ -768,7 +876,7 @@ def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_i
                           group_size: int = MAX_GROUP, hook_block_view: bool = False, sampler: str = "torch",
                           seed=None, top_k=0, top_p=1.0, logprobs: Optional[int] = None, repetition_penalty=1.0,
                           presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, allowed_token_ids=None,
-                          banned_token_ids=None, min_tokens=0) -> list:
+                          banned_token_ids=None, min_tokens=0, grammar=None) -> list:
     """`dflash_generate` (benchmark.py:44-251) for a list of prompts: requests run in
     groups of `group_size` <= 4 (<= 2 with block sizes of 17..32 rows) that share the weight stream; returns one namespace per
     prompt with the fields of benchmark.py:242-251 (timing fields are the group's).
@@ -784,8 +892,15 @@ def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_i
     The decoders are built with penalties=True when any prompt is not neutral (blocks of <= 16 rows).
     logit_bias / allowed_token_ids / banned_token_ids / min_tokens: as dflash_generate; one value for every prompt, or a
     sequence with one value (or None) per prompt.  The decoders are built with logit_bias=True when any prompt is not
-    neutral (blocks of <= 16 rows)."""
+    neutral (blocks of <= 16 rows).
+    grammar: as dflash_generate; one TokenDFA for every prompt, or a sequence with one (or None) per prompt.  Each group's
+    decoder gets a pool of exactly its prompts' automata (blocks of <= 16 rows); the results carry `grammar_state`."""
     logprobs = ops.check_logprobs(logprobs)
+    dfas = _prompt_grammars(grammar, len(input_ids))
+    for d in {id(d): d for d in dfas if d is not None}.values():
+        ops.check_grammar(d, target.V)
+    if _pool_rows(dfas) and block_size > 16:
+        raise NotImplementedError("grammar takes blocks of <= 16 rows")
     pens, penalties = _prompt_penalties(repetition_penalty, presence_penalty, frequency_penalty, len(input_ids))
     biases, logit_bias_on = _prompt_bias(target, logit_bias, allowed_token_ids, banned_token_ids, min_tokens,
                                          len(input_ids), stop_token_ids)
@@ -811,12 +926,15 @@ def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_i
                              out_len=pmax + max_new_tokens + 16 * tpr, mask_token_id=mask_token_id,
                              stop_token_ids=stop_token_ids, temperature=max(temps[i] for i in idx), tiles_per_request=tpr,
                              sampler=sampler, filtering=filtering, request_temperature=per_request, logprobs=logprobs,
-                             penalties=penalties, logit_bias=logit_bias_on)
+                             penalties=penalties, logit_bias=logit_bias_on,
+                             grammar_states=_pool_rows([dfas[i] for i in idx]))
+        handles = _load_grammars(dec, [dfas[i] for i in idx])
         t0 = cuda_time()
         for r, p in enumerate(prompts):
             pr, pa, pf = pens[idx[r]]
             dec.admit(r, p, temps[idx[r]], seed=seeds[idx[r]], top_k=top_ks[idx[r]], top_p=top_ps[idx[r]],
-                      repetition_penalty=pr, presence_penalty=pa, frequency_penalty=pf, **biases[idx[r]])
+                      repetition_penalty=pr, presence_penalty=pa, frequency_penalty=pf, **biases[idx[r]],
+                      grammar=handles[r])
         ttft = cuda_time() - t0
         taus = [[] for _ in idx]
         # (hook_block_view: the hook sees the block as the single-request loop hands it over, bs slots; default: the
@@ -857,7 +975,8 @@ def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_i
                 dec.lp, r, _kept_cols(dec.output_ids[r:r + 1], max_len[r], mask_token_id, stop_token_ids, dec.n_in[r])[dec.n_in[r]:])
             results[i] = SimpleNamespace(output_ids=ids.clone(), num_input_tokens=dec.n_in[r], num_output_tokens=n_out,
                                          time_to_first_token=ttft, time_per_output_token=decode_s / max(1, n_out),
-                                         acceptance_lengths=taus[r], cycle_trace=[], profile_summary=None, **lpf)
+                                         acceptance_lengths=taus[r], cycle_trace=[], profile_summary=None,
+                                         grammar_state=dec.grammar_state_of(r, ids[0], dec.n_in[r]), **lpf)
         del dec
     return results
 

@@ -15,8 +15,8 @@ from typing import Callable, Optional, Sequence, Union
 import torch
 
 from . import ops
-from .batch import (MAX_GROUP, BatchedDecoder, _prompt_bias, _prompt_filters, _prompt_penalties, _prompt_seeds,
-                    _prompt_temperatures)
+from .batch import (MAX_GROUP, BatchedDecoder, _load_grammars, _pool_rows, _prompt_bias, _prompt_filters,
+                    _prompt_grammars, _prompt_penalties, _prompt_seeds, _prompt_temperatures)
 from .generate import NO_LOGPROBS, _kept_cols, _trim, cuda_time, logprob_fields
 from .slots import SlotLoop
 
@@ -60,7 +60,7 @@ class _DecoderDriver:
         ids = p.input_ids if p.input_ids.is_cuda else p.input_ids.to(self.dec.dev)
         self.dec.admit_fused(slot, ids, p.temperature, seed=p.seed, top_k=p.top_k, top_p=p.top_p,
                              repetition_penalty=p.penalties[0], presence_penalty=p.penalties[1],
-                             frequency_penalty=p.penalties[2], **p.bias)
+                             frequency_penalty=p.penalties[2], **p.bias, grammar=p.grammar)
         t1 = cuda_time()
         p.ttft, p.t_admitted = t1 - t0, t1
         self.stats["admit_s"] += t1 - t0
@@ -111,7 +111,8 @@ class _DecoderDriver:
                                    time_to_first_token=p.ttft, time_per_output_token=decode_s / max(1, n_out),
                                    acceptance_lengths=req.taus, cycle_trace=[], profile_summary=None,
                                    request_id=req.rid, slot=slot, admitted_step=req.admitted_step,
-                                   finished_step=req.finished_step, **lpf)
+                                   finished_step=req.finished_step,
+                                   grammar_state=d.grammar_state_of(slot, ids[0], req.n_in), **lpf)
 
 
 class BatchEngine:
@@ -126,8 +127,13 @@ class BatchEngine:
     def __init__(self, model, target, *, slots: int = MAX_GROUP, max_rows: int, out_len: int, mask_token_id: int,
                  block_size: int = 16, stop_token_ids=None, temperature: float = 0.0, sampler: str = "torch",
                  graph: Optional[bool] = None, filtering: bool = False, request_temperature: bool = False,
-                 logprobs: Optional[int] = None, penalties: bool = False, logit_bias: bool = False):
-        """logprobs = N (None: off): every result carries logprobs / top_logprob_ids / top_logprobs as dflash_generate
+                 logprobs: Optional[int] = None, penalties: bool = False, logit_bias: bool = False,
+                 grammar_states: int = 0):
+        """grammar_states = N (0: off): a pool of N automaton rows; add_grammar loads a TokenDFA into it and returns the
+        handle submit takes.  Fixed here because it fixes the captured launch sequence; the pool's
+        address is fixed too, so the one capture serves grammars loaded later.  Requests without a grammar emit the same
+        ids; results carry `grammar_state`.
+        logprobs = N (None: off): every result carries logprobs / top_logprob_ids / top_logprobs as dflash_generate
         returns them; fixed here, one capture per engine — there is no per-request switch.
         filtering: requests may carry top_k / top_p (submit); fixed here because it fixes the captured launch sequence
         ("Filtered draw").  Unfiltered requests of such an engine emit the same ids.
@@ -156,7 +162,7 @@ class BatchEngine:
         self.dec = BatchedDecoder(model, target, slots, max_rows=max_rows, out_len=out_len, mask_token_id=mask_token_id,
                                   stop_token_ids=stop_token_ids, temperature=temperature, sampler=sampler,
                                   filtering=filtering, request_temperature=request_temperature, logprobs=logprobs,
-                                  penalties=penalties, logit_bias=logit_bias)
+                                  penalties=penalties, logit_bias=logit_bias, grammar_states=grammar_states)
         self.filtering, self.temperature, self.penalties = bool(filtering), float(temperature), bool(penalties)
         self.logit_bias = bool(logit_bias)
         self.request_temperature = bool(request_temperature)
@@ -172,7 +178,7 @@ class BatchEngine:
                draft_token_hook: Optional[Callable] = None, top_k: int = 0, top_p: float = 1.0,
                temperature: Optional[float] = None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
                frequency_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None, banned_token_ids=None,
-               min_tokens: int = 0) -> int:
+               min_tokens: int = 0, grammar=None) -> int:
         """Queue a request; returns its id (ids count up in submission order).  draft_token_hook(block_view, start,
         call): `call` counts from 0 at the request's admission; the view has the cycle's block size.
         top_k / top_p: the request's own filter on its T > 0 draws (an engine built with filtering=True); accepted and
@@ -182,7 +188,10 @@ class BatchEngine:
         repetition_penalty / presence_penalty / frequency_penalty: the request's own (an engine built with
         penalties=True; 1.0 / 0.0 / 0.0: off).
         logit_bias / allowed_token_ids / banned_token_ids / min_tokens: the request's own (an engine built with
-        logit_bias=True; None / None / None / 0: off), validated here."""
+        logit_bias=True; None / None / None / 0: off), validated here.
+        grammar: a handle add_grammar returned (None: no grammar; an engine built with grammar_states > 0)."""
+        if grammar is not None:   # (raises on a handle this engine did not return, and on an engine without a pool)
+            self.dec.check_grammar_handle(grammar)
         pen = ops.check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
         if pen is not None and not self.penalties:
             raise ValueError("submit: penalties need an engine built with penalties=True")
@@ -203,8 +212,14 @@ class BatchEngine:
         req = self.loop.submit(input_ids.shape[1], int(max_new_tokens),
                                SimpleNamespace(input_ids=input_ids, seed=seed, hook=draft_token_hook, result=None,
                                                ttft=0.0, t_admitted=0.0, top_k=int(top_k), top_p=float(top_p),
-                                               temperature=T, penalties=pen or (1.0, 0.0, 0.0), bias=bias))
+                                               temperature=T, penalties=pen or (1.0, 0.0, 0.0), bias=bias,
+                                               grammar=grammar))
         return req.rid
+
+    def add_grammar(self, dfa) -> int:
+        """Load a TokenDFA into the engine's pool; the handle submit(..., grammar=handle) takes.  ValueError when the pool
+        is full or the engine was built with grammar_states = 0."""
+        return self.dec.add_grammar(dfa)
 
     @torch.inference_mode()
     def step(self) -> list:
@@ -229,7 +244,7 @@ def dflash_generate_stream(model, target, input_ids: Sequence[torch.Tensor], mas
                            sampler: str = "torch", seed=None, top_k=0, top_p=1.0,
                            logprobs: Optional[int] = None, repetition_penalty=1.0, presence_penalty=0.0,
                            frequency_penalty=0.0, logit_bias=None, allowed_token_ids=None, banned_token_ids=None,
-                           min_tokens=0) -> list:
+                           min_tokens=0, grammar=None) -> list:
     """`dflash_generate_batch` with slot refill: one namespace per prompt with the fields of benchmark.py:242-251, each
     request emitting what its own `dflash_generate` run emits.  max_new_tokens: one int or one per prompt.
     draft_token_hook(request_index, block_view, start, call).  seed as in dflash_generate_batch (an int s gives prompt i
@@ -239,7 +254,11 @@ def dflash_generate_stream(model, target, input_ids: Sequence[torch.Tensor], mas
     request_temperature=True).  logprobs: as dflash_generate, for every prompt.
     repetition_penalty / presence_penalty / frequency_penalty: a scalar or one value per prompt.
     logit_bias / allowed_token_ids / banned_token_ids / min_tokens: one value for every prompt, or a sequence with one
-    value (or None) per prompt."""
+    value (or None) per prompt.
+    grammar: one TokenDFA for every prompt, or a sequence with one (or None) per prompt."""
+    dfas = _prompt_grammars(grammar, len(input_ids))
+    for d in {id(d): d for d in dfas if d is not None}.values():
+        ops.check_grammar(d, target.V)
     n = len(input_ids)
     mnt = [int(max_new_tokens)] * n if isinstance(max_new_tokens, int) else [int(x) for x in max_new_tokens]
     if len(mnt) != n:
@@ -257,10 +276,12 @@ def dflash_generate_stream(model, target, input_ids: Sequence[torch.Tensor], mas
     eng = BatchEngine(model, target, slots=max(1, min(slots, max(n, 1))), max_rows=need + 3 * BLOCK_ROWS,
                       out_len=need + BLOCK_ROWS, mask_token_id=mask_token_id, block_size=block_size,
                       stop_token_ids=stop_token_ids, temperature=max(temps, default=0.0), sampler=sampler, filtering=filtering,
-                      request_temperature=per_request, logprobs=logprobs, penalties=penalties, logit_bias=logit_bias_on)
+                      request_temperature=per_request, logprobs=logprobs, penalties=penalties, logit_bias=logit_bias_on,
+                      grammar_states=_pool_rows(dfas))
+    handles = _load_grammars(eng, dfas)
     for i, p in enumerate(input_ids):
         hook = (lambda blk, start, call, i=i: draft_token_hook(i, blk, start, call)) if draft_token_hook else None
         eng.submit(p, mnt[i], seed=seeds[i], draft_token_hook=hook, top_k=top_ks[i], top_p=top_ps[i],
                    temperature=temps[i], repetition_penalty=pens[i][0], presence_penalty=pens[i][1],
-                   frequency_penalty=pens[i][2], **biases[i])
+                   frequency_penalty=pens[i][2], **biases[i], grammar=handles[i])
     return eng.run()

@@ -207,8 +207,19 @@ class DecodeSession:
                  draft_token_hook: Optional[Callable] = None, sampler: str = "torch", seed: Optional[int] = None,
                  top_k: int = 0, top_p: float = 1.0, logprobs: Optional[int] = None, repetition_penalty: float = 1.0,
                  presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None,
-                 banned_token_ids=None, min_tokens: int = 0):
+                 banned_token_ids=None, min_tokens: int = 0, grammar=None):
         from .target import NativeTarget
+        # grammar: a TokenDFA the emitted tokens must walk; None: every launch below is the one
+        # enqueued without the keyword
+        if grammar is not None:
+            if not isinstance(target, NativeTarget):
+                raise ValueError("grammar needs a dflash_amd.NativeTarget (the kernel reads the verify's materialised "
+                                 "logits)")
+            if temperature >= 1e-5 and sampler != "device":
+                raise ValueError("grammar at T > 0 needs sampler='device' (sampler='torch' is the reference's multinomial "
+                                 "over the raw logits)")
+            if int(max_block_size) > 16:
+                raise NotImplementedError("grammar takes blocks of <= 16 rows (the 17..32-row verify is not covered)")
         # logit_bias / allowed_token_ids / banned_token_ids / min_tokens on the TARGET's rows; all
         # neutral: None, and every launch below is the one enqueued without the keywords
         lb = None
@@ -307,6 +318,17 @@ class DecodeSession:
             self.lb.stop = self.stop_t
             self.lb.logits = torch.zeros(16, target.V, dtype=torch.bfloat16, device=dev)
             self._lpkw = dict(self._lpkw, logit_bias=self.lb)
+        # the grammar state: a pool of exactly the automaton's rows at base 0 (validated against the bias row: a reachable
+        # state whose legal tokens are all banned is refused here), the slot's state, and the buffer the verify writes its
+        # masked rows into
+        self.gr = None
+        if grammar is not None:
+            ops.check_grammar(grammar, target.V, None if lb is None else lb[0])
+            self.gr = ops.grammar_state(1, grammar.next.shape[0], target.V, dev)
+            self.gr.start = int(grammar.start)
+            ops.grammar_set(self.gr, 0, ops.grammar_load(self.gr, grammar), self.gr.start)
+            self.gr.logits = torch.zeros(16, target.V, dtype=torch.bfloat16, device=dev)
+            self._lpkw = dict(self._lpkw, grammar=self.gr)
         # the reference scans the whole buffer, mask slots included (model/dflash.py:265-268)
         self.stop_always = stop_token_ids is not None and mask_token_id in stop_token_ids
         # the accept result {acc, new start, stop, cycle}: pinned host memory the kernel writes with one 16-byte store and
@@ -352,7 +374,7 @@ class DecodeSession:
                               past_key_values=self.tcache, use_cache=True, logits_to_keep=1,
                               output_hidden_states=self.use_draft)
         self.output_ids[:, :self.n_in] = self.input_ids
-        if self.pen is not None or self.lb is not None:
+        if self.pen is not None or self.lb is not None or self.gr is not None:
             self._first_token_processed(out.logits[0, -1:])
         elif self._tseed is not None:   # the first new token draws position n_in
             self.output_ids[:, self.n_in:self.n_in + 1] = _draw_rows(out.logits[:, -1:], self.temperature, self._tseed,
@@ -369,12 +391,15 @@ class DecodeSession:
         """The first new token under logit bias and / or penalties.  The prompt's last-row logits predict position n_in:
         they take the bias row (and lose the stop ids under min_tokens >= 1); under penalties the prompt is counted into a
         cleared table row and the rows are penalised by it; the token is their argmax or the seeded draw at position
-        n_in over them, and it is counted as output."""
-        p, lb, n = self.pen, self.lb, self.n_in
+        n_in over them, and it is counted as output.  Under a grammar the rows are masked by the start state (the
+        single-row form: no walk) between the two, and the state advances over the token."""
+        p, lb, gr, n = self.pen, self.lb, self.gr, self.n_in
         first = self.output_ids[0, n:n + 1]
         z = row.to(torch.bfloat16).contiguous()
         if lb is not None:
             z = ops.logit_bias_rows(z, lb.bias, min_pos=lb.min_pos, stop_ids=lb.stop, pos_base=n, out_ids=first)
+        if gr is not None:
+            z = ops.grammar_rows(z, gr, out_ids=first)
         if p is not None:
             ops.penalty_count(p.table, self.output_ids, lo=0, hi=n, as_prompt=True, clear=True)
             z = ops.penalty_rows(z, p.table, repetition_penalty=p.r, presence_penalty=p.a, frequency_penalty=p.f,
@@ -383,13 +408,18 @@ class DecodeSession:
             first.copy_(_draw_rows(z.unsqueeze(0), self.temperature, self._tseed, n, self._filter)[0])
         if p is not None:
             ops.penalty_count(p.table, self.output_ids, lo=n, hi=n + 1)
+        if gr is not None:
+            ops.grammar_advance(gr, self.output_ids, lo=n, hi=n + 1)
 
     def _count_committed(self) -> None:
         """Right behind an accept launch: what it committed, output_ids(S, START] of the draft record it has just
-        written, goes into the penalty table — once per cycle, eager or replayed."""
+        written, goes into the penalty table and steps the grammar state — once per cycle, eager or replayed."""
         if self.pen is not None:
             ops.penalty_count(self.pen.table, self.output_ids, dyn=self.dyn, lo_word=ops.DYN_S, hi_word=ops.DYN_START,
                               lo=1, hi=1)
+        if self.gr is not None:
+            ops.grammar_advance(self.gr, self.output_ids, dyn=self.dyn, lo_word=ops.DYN_S, hi_word=ops.DYN_START,
+                                lo=1, hi=1)
 
     def _mark(self, key, which):
         if self.events is not None and self.record_events:
@@ -648,7 +678,8 @@ class DecodeSession:
                         t.fp8_tensors() if self.native else (),    # (an fp8 target's codes and scale vectors)
                         getattr(t, "_nuc_logits", None),           # (the logits a filtered, logprobs or penalised verify materialises)
                         self.pen,                                  # (the penalty table and the penalised rows: the session's own)
-                        self.lb))                                  # (the bias table, min_pos and the biased rows likewise)
+                        self.lb,                                   # (the bias table, min_pos and the biased rows likewise)
+                        self.gr))                                  # (the grammar pool, base / state and the masked rows likewise)
 
     def _tables_moved(self, rec: _Replay) -> bool:
         """A shared draft model / NativeTarget replaces its RoPE table when another caller needs more positions
@@ -781,6 +812,20 @@ class DecodeSession:
         cols = _kept_cols(self.output_ids, self.max_length, self.mask_token_id, self.stop_token_ids, self.n_in)
         return logprob_fields(self.lp, 0, cols[self.n_in:])
 
+    def finish_grammar(self, output_ids: torch.Tensor) -> Optional[int]:
+        """The result field grammar_state: the automaton's state after the generated tokens finish() returned, walked by
+        dfl_grammar_advance from start; -1 where one of them is illegal or the slot's own state was violated; None with
+        the grammar off.  (The slot's own state runs on over what an accept launch committed behind a stop id or past
+        max_length — tokens the trim drops — so it is not the state after what is returned.)"""
+        if self.gr is None:
+            return None
+        if int(self.gr.state.item()) < 0:
+            return -1
+        g = SimpleNamespace(table=self.gr.table, base=self.gr.base,
+                            state=torch.full((1,), self.gr.start, dtype=torch.int32, device=self.dev))
+        ops.grammar_advance(g, output_ids[0].contiguous(), lo=self.n_in, hi=output_ids.shape[1])
+        return int(g.state.item())
+
 
 @torch.inference_mode()
 def run_decode(model, target, input_ids: torch.Tensor, *, mask_token_id: int, max_new_tokens: int,
@@ -790,14 +835,14 @@ def run_decode(model, target, input_ids: torch.Tensor, *, mask_token_id: int, ma
                max_block_size: Optional[int] = None, sampler: str = "torch", seed: Optional[int] = None,
                top_k: int = 0, top_p: float = 1.0, logprobs: Optional[int] = None, repetition_penalty: float = 1.0,
                presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None,
-               banned_token_ids=None, min_tokens: int = 0) -> SimpleNamespace:
+               banned_token_ids=None, min_tokens: int = 0, grammar=None) -> SimpleNamespace:
     s = DecodeSession(model, target, input_ids, mask_token_id=mask_token_id, max_new_tokens=max_new_tokens,
                       max_block_size=max_block_size or block_size, stop_token_ids=stop_token_ids,
                       temperature=temperature, draft_temperature=draft_temperature,
                       draft_token_hook=draft_token_hook, sampler=sampler, seed=seed, top_k=top_k, top_p=top_p,
                       logprobs=logprobs, repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
                       frequency_penalty=frequency_penalty, logit_bias=logit_bias, allowed_token_ids=allowed_token_ids,
-                      banned_token_ids=banned_token_ids, min_tokens=min_tokens)
+                      banned_token_ids=banned_token_ids, min_tokens=min_tokens, grammar=grammar)
     t_prefill = cuda_time()
     s.prefill()
     time_to_first_token = cuda_time() - t_prefill
@@ -908,7 +953,7 @@ def run_decode(model, target, input_ids: torch.Tensor, *, mask_token_id: int, ma
                            acceptance_lengths=taus, used_block_sizes=used_bs, l_gen=lgens,
                            cycle_trace=cycle_trace, profile_summary=profile_summary, replayed_cycles=replayed,
                            replayed_flags=replayed_flags,
-                           seed=s.seed, **s.finish_logprobs())
+                           seed=s.seed, grammar_state=s.finish_grammar(output_ids), **s.finish_logprobs())
 
 
 def _draft_ids(model, hid_frag, lm_wp, bs, blk, draft_temperature, keep_logits=None, seed=None, dyn=None, start=None,
@@ -965,8 +1010,13 @@ def dflash_generate(model, target, input_ids: torch.Tensor, mask_token_id: int, 
                     seed: Optional[int] = None, top_k: int = 0, top_p: float = 1.0,
                     logprobs: Optional[int] = None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
                     frequency_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None, banned_token_ids=None,
-                    min_tokens: int = 0) -> SimpleNamespace:
+                    min_tokens: int = 0, grammar=None) -> SimpleNamespace:
     """benchmark.py:44-55 signature; returns the namespace of :242-251 (+ replayed_cycles).
+    grammar (a dflash_amd.TokenDFA; None: off; needs a NativeTarget, blocks of <= 16 rows, and sampler="device" at
+    T > 0): the emitted tokens walk the automaton from its start state — every verify row is masked by the state its
+    own prefix of the block reaches, between the logit bias and the penalties.  The result's
+    `grammar_state` is the state after the returned tokens (-1: violated; None when off).  The draft's proposals stay
+    unconstrained.
     logit_bias ({id: bias}, finite or -inf) / allowed_token_ids / banned_token_ids / min_tokens (None / None / None / 0:
     off; need a NativeTarget, blocks of <= 16 rows, and sampler="device" at T > 0): the OpenAI / vLLM controls on the
     target's logits, applied before the penalties; no stop id is emitted before min_tokens tokens are out (DESIGN.md
@@ -983,6 +1033,8 @@ def dflash_generate(model, target, input_ids: torch.Tensor, mask_token_id: int, 
     however the request runs, and the cycles can be replayed from hipGraphs; seed=None draws one from torch's RNG.
     top_k / top_p (0 / 1.0: off) restrict the target's seeded draw (section 8, "Filtered draw"); sampler="device" only."""
     if getattr(model, "wide_hidden", False):
+        if grammar is not None:
+            raise NotImplementedError("grammar: hidden_size > 4096 runs through the ragged batch, which takes no grammar")
         return _generate_wide_hidden(model, target, input_ids, mask_token_id, max_new_tokens, block_size, stop_token_ids,
                                      temperature, collect_profile, draft_steps, draft_token_hook, sampler, seed, top_k, top_p,
                                      logprobs, (repetition_penalty, presence_penalty, frequency_penalty),
@@ -994,13 +1046,13 @@ def dflash_generate(model, target, input_ids: torch.Tensor, mask_token_id: int, 
                    sampler=sampler, seed=seed, top_k=top_k, top_p=top_p, logprobs=logprobs,
                    repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
                    frequency_penalty=frequency_penalty, logit_bias=logit_bias, allowed_token_ids=allowed_token_ids,
-                   banned_token_ids=banned_token_ids, min_tokens=min_tokens)
+                   banned_token_ids=banned_token_ids, min_tokens=min_tokens, grammar=grammar)
     return SimpleNamespace(output_ids=r.output_ids, num_input_tokens=r.num_input_tokens,
                            num_output_tokens=r.num_output_tokens, time_to_first_token=r.time_to_first_token,
                            time_per_output_token=r.time_per_output_token, acceptance_lengths=r.acceptance_lengths,
                            cycle_trace=r.cycle_trace, profile_summary=r.profile_summary,
                            replayed_cycles=r.replayed_cycles, logprobs=r.logprobs, top_logprob_ids=r.top_logprob_ids,
-                           top_logprobs=r.top_logprobs)
+                           top_logprobs=r.top_logprobs, grammar_state=r.grammar_state)
 
 
 def _generate_wide_hidden(model, target, input_ids, mask_token_id, max_new_tokens, block_size, stop_token_ids, temperature,
@@ -1040,8 +1092,9 @@ def dflash_generate_policy(*, model, target, input_ids: torch.Tensor, mask_token
                            seed: Optional[int] = None, top_k: int = 0, top_p: float = 1.0,
                            logprobs: Optional[int] = None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
                            frequency_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None, banned_token_ids=None,
-                           min_tokens: int = 0) -> SimpleNamespace:
+                           min_tokens: int = 0, grammar=None) -> SimpleNamespace:
     """benchmark_dynamic_schedule.py:260-272 signature; returns the namespace of :425-434 (+ replayed_cycles).
+    grammar: as dflash_generate (the target's rows; the draft's own draw stays unconstrained; `grammar_state`).
     logprobs: as dflash_generate (the fields logprobs / top_logprob_ids / top_logprobs; None when off).
     sampler / seed: as dflash_generate; the draft's own T > 0 draw uses the same seed on a stream of its own.
     top_k / top_p: as dflash_generate (the target's draw; the draft's own draw stays unfiltered).
@@ -1057,7 +1110,7 @@ def dflash_generate_policy(*, model, target, input_ids: torch.Tensor, mask_token
                    draft_token_hook=draft_token_hook, sampler=sampler, seed=seed, top_k=top_k, top_p=top_p,
                    logprobs=logprobs, repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
                    frequency_penalty=frequency_penalty, logit_bias=logit_bias, allowed_token_ids=allowed_token_ids,
-                   banned_token_ids=banned_token_ids, min_tokens=min_tokens)
+                   banned_token_ids=banned_token_ids, min_tokens=min_tokens, grammar=grammar)
     if fixed_block_size is not None:
         for row in r.cycle_trace:
             for k in ("tau_hat", "cycle_hat", "score_hat", "current_block_size", "adl_lgen_hat", "adl_lacc_hat",
@@ -1068,7 +1121,7 @@ def dflash_generate_policy(*, model, target, input_ids: torch.Tensor, mask_token
                            time_per_output_token=r.time_per_output_token, acceptance_lengths=r.acceptance_lengths,
                            used_block_sizes=r.used_block_sizes, cycle_trace=r.cycle_trace,
                            replayed_cycles=r.replayed_cycles, logprobs=r.logprobs, top_logprob_ids=r.top_logprob_ids,
-                           top_logprobs=r.top_logprobs)
+                           top_logprobs=r.top_logprobs, grammar_state=r.grammar_state)
 
 
 class _Fixed:

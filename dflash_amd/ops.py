@@ -924,6 +924,179 @@ def logit_bias_rows(logits: torch.Tensor, bias: torch.Tensor, *, min_pos=0, stop
     return out
 
 
+I16 = torch.int16
+
+
+def check_grammar(dfa, V: int, logit_bias_row=None) -> None:
+    """Validate a TokenDFA for a vocabulary of V: next an int16 numpy array [S, V], 1 <= S <= 32767,
+    V % 8 == 0, successors in [-1, S), start in [0, S), and every state reachable from start has a legal token —
+    where logit_bias_row (fp32 [V], the row check_logit_bias returns) is given, one that it does not ban."""
+    import numpy as np
+    import operator
+    nxt = getattr(dfa, "next", None)
+    if not isinstance(nxt, np.ndarray) or nxt.dtype != np.int16 or nxt.ndim != 2:
+        raise ValueError("dflash_amd: grammar: TokenDFA.next must be an int16 numpy array [S, V]")
+    S, Vd = nxt.shape
+    if not 1 <= S <= 32767:
+        raise ValueError(f"dflash_amd: grammar: {S} states, 1..32767 fit the int16 table")
+    if Vd != int(V) or Vd < 8 or Vd % 8:
+        raise ValueError(f"dflash_amd: grammar: the table has {Vd} columns, the vocabulary {V} (a multiple of 8)")
+    if int(nxt.min()) < -1 or int(nxt.max()) >= S:
+        raise ValueError(f"dflash_amd: grammar: a successor lies outside [-1, {S})")
+    try:
+        start = operator.index(dfa.start)
+    except TypeError:
+        raise ValueError(f"dflash_amd: grammar: start {dfa.start!r} is not a state") from None
+    if not 0 <= start < S:
+        raise ValueError(f"dflash_amd: grammar: start {start} outside [0, {S})")
+    open_cols = None
+    if logit_bias_row is not None:
+        b = torch.as_tensor(logit_bias_row, dtype=F32).cpu().numpy()
+        if b.shape != (Vd,):
+            raise ValueError(f"dflash_amd: grammar: the bias row has shape {b.shape}, the vocabulary ({Vd},)")
+        open_cols = b > -np.inf
+    reached = np.zeros(S, dtype=bool)
+    reached[start] = True
+    frontier = np.array([start])
+    while frontier.size:
+        rows = nxt[frontier]
+        legal = rows >= 0
+        dead = ~legal.any(axis=1)
+        if dead.any():
+            raise ValueError(f"dflash_amd: grammar: state {int(frontier[dead][0])} is reachable from start {start} and has "
+                             f"no legal token")
+        if open_cols is not None:
+            shut = ~(legal & open_cols[None, :]).any(axis=1)
+            if shut.any():
+                raise ValueError(f"dflash_amd: grammar: every legal token of reachable state {int(frontier[shut][0])} is "
+                                 f"banned by logit_bias / allowed_token_ids / banned_token_ids")
+        succ = np.unique(rows[legal])
+        frontier = succ[~reached[succ]]
+        reached[frontier] = True
+
+
+def grammar_state(slots: int, pool_states: int, V: int, device) -> SimpleNamespace:
+    """The grammar state: .table int16 [pool_states, V], the pool, all -1 (no token legal) until
+    grammar_load writes a grammar's rows; .base int32 [slots] (-1: the slot has no grammar) and .state int32 [slots]
+    (relative to base; -1: violated), written by grammar_set; .used: the pool rows handed out so far (host)."""
+    if V < 8 or V % 8:
+        raise ValueError(f"dflash_amd: a grammar needs a vocabulary that is a multiple of 8, got {V}")
+    if pool_states < 1 or slots < 1:
+        raise ValueError(f"dflash_amd: grammar_state: slots={slots} pool_states={pool_states}")
+    return SimpleNamespace(table=torch.full((pool_states, V), -1, dtype=I16, device=device),
+                           base=torch.full((slots,), -1, dtype=I32, device=device),
+                           state=torch.full((slots,), -1, dtype=I32, device=device), used=0)
+
+
+def grammar_load(state, dfa, logit_bias_row=None) -> int:
+    """Validate dfa (check_grammar) and copy its table into the next free pool rows; returns their base.  ValueError when
+    the pool has fewer rows left than the grammar has states.  The pool's storage never moves."""
+    pool, V = state.table.shape
+    check_grammar(dfa, V, logit_bias_row)
+    S = dfa.next.shape[0]
+    if state.used + S > pool:
+        raise ValueError(f"dflash_amd: the grammar pool is full: {S} states asked, {pool - state.used} of {pool} rows free")
+    base = state.used
+    import numpy as np
+    state.table[base:base + S].copy_(torch.from_numpy(np.ascontiguousarray(dfa.next)))
+    state.used = base + S
+    return base
+
+
+def grammar_set(state, slot: int, base, start: int = 0) -> None:
+    """Slot's grammar: base (a value grammar_load returned; None or < 0: no grammar, the slot's rows pass unmasked) and
+    its state, start.  Admission only, plain fills."""
+    if not 0 <= slot < state.base.shape[0]:
+        raise ValueError(f"dflash_amd: grammar_set: slot {slot} outside 0..{state.base.shape[0] - 1}")
+    if base is None or base < 0:
+        base, start = -1, -1
+    elif not (base < state.table.shape[0] and 0 <= start < state.table.shape[0] - base):
+        raise ValueError(f"dflash_amd: grammar_set: base {base} / start {start} outside the pool of {state.table.shape[0]}")
+    state.base[slot:slot + 1].fill_(int(base))
+    state.state[slot:slot + 1].fill_(int(start))
+
+
+def _grammar_pool(state):
+    t = state.table
+    if t.dtype != I16 or not t.is_cuda or state.base.dtype != I32 or state.state.dtype != I32:
+        raise TypeError("dflash_amd: the grammar pool must be an int16 GPU tensor, base / state int32")
+    assert t.dim() == 2 and t.stride(1) == 1 and state.base.is_cuda and state.state.is_cuda
+    assert state.base.is_contiguous() and state.state.is_contiguous()
+    return t
+
+
+def grammar_rows(logits: torch.Tensor, state, *, block=None, out: Optional[torch.Tensor] = None, row0: int = 0,
+                 nrows: Optional[int] = None, dyn=None, nrows_dyn_word: int = -1, tiles_per_req: int = 1,
+                 out_ids: Optional[torch.Tensor] = None, out_off: int = 0) -> torch.Tensor:
+    """Grammar-masked logits (dfl_grammar_rows) of materialised bf16 logits [rows <= 16, V] (one
+    tile) or [tiles, 16, V], unit inner stride; returns `out` (same shape and strides; None: a new buffer; the logits
+    themselves: in place).  state: a grammar_state.  block int64 [slots, >= the rows of a request] or 1-D for one slot:
+    row m of slot q walks state[q] through block[q, 1 : m + 1] and masks by where it arrives, or is copied unchanged
+    when the walk dies; None: no walk, the single-row form for a first token.  Rows of a tile as in penalty_rows.
+    out_ids: the rows' argmax at out_ids[t, out_off + m - row0].  tiles_per_req = 2 (17..32-row blocks) is refused."""
+    if tiles_per_req != 1:
+        raise NotImplementedError("dflash_amd: grammar_rows takes one tile per request (blocks of <= 16 rows)")
+    assert logits.dim() in (2, 3) and logits.stride(-1) == 1 and logits.is_cuda and logits.dtype == BF16
+    if logits.dim() == 2:
+        assert logits.shape[0] <= 16, "one tile holds at most 16 rows"
+        tiles, tile_rows, tile_stride = 1, logits.shape[0], 16 * logits.stride(0)
+    else:
+        assert logits.shape[1] == 16
+        tiles, tile_rows, tile_stride = logits.shape[0], 16, logits.stride(0)
+    V, ld = logits.shape[-1], logits.stride(-2)
+    if nrows is None:
+        nrows = tile_rows - row0
+    assert 0 <= row0 and row0 + nrows <= tile_rows or nrows_dyn_word >= 0 and tile_rows == 16
+    n_out = 16 - row0 if nrows_dyn_word >= 0 else nrows
+    if out is None:
+        out = torch.empty_strided(logits.shape, logits.stride(), dtype=BF16, device=logits.device)
+    assert out.shape == logits.shape and out.stride() == logits.stride() and out.dtype == BF16 and out.is_cuda, "out"
+    table = _grammar_pool(state)
+    assert table.shape[1] == V and state.base.numel() >= tiles and state.state.numel() >= tiles, "one base / state per slot"
+    blk_stride = 0
+    if block is not None:
+        if block.dtype != I64 or not block.is_cuda:
+            raise TypeError("dflash_amd: block must be an int64 GPU tensor")
+        assert block.stride(-1) == 1 and block.shape[-1] >= row0 + n_out, "block"
+        assert block.dim() == 2 and block.shape[0] >= tiles or block.dim() == 1 and tiles == 1, "block"
+        blk_stride = block.stride(0) if block.dim() == 2 else 0
+    out_stride = 0
+    if out_ids is not None:
+        assert out_ids.stride(-1) == 1 and out_ids.shape[-1] >= out_off + n_out, "out_ids"
+        assert out_ids.dim() == 2 and out_ids.shape[0] >= tiles or out_ids.dim() == 1 and tiles == 1, "out_ids"
+        out_stride = out_ids.stride(0) if out_ids.dim() == 2 else 0
+    if dyn is not None:
+        assert dyn.numel() >= 8 * tiles
+    check(lib().dfl_grammar_rows(logits.data_ptr(), out.data_ptr(), ld, tile_stride, tiles, V, row0, nrows,
+                                 _p(dyn, I32, "dyn"), nrows_dyn_word, 1, table.data_ptr(), table.stride(0), table.shape[0],
+                                 state.base.data_ptr(), state.state.data_ptr(),
+                                 None if block is None else block.data_ptr(), blk_stride, _p(out_ids, I64, "out_ids"),
+                                 out_stride, out_off, _stream()), "dfl_grammar_rows")
+    return out
+
+
+def grammar_advance(state, ids: torch.Tensor, *, lo: int = 0, hi: int = 0, dyn=None, lo_word: int = 0,
+                    hi_word: int = 0, slots: Optional[int] = None) -> None:
+    """Step every slot's state over ids[s, lo':hi'] (dfl_grammar_advance; ids int64 [slots, n] or [n]); the range and the
+    idle-slot rule as penalty_count takes them.  An illegal id, or one outside the vocabulary, leaves -1, which stays.
+    slots: the first `slots` of the state's slots (None: all)."""
+    table = _grammar_pool(state)
+    if ids.dim() == 1:
+        ids = ids.unsqueeze(0)
+    if slots is None:
+        slots = state.base.numel()
+    assert 0 <= slots <= state.base.numel() == state.state.numel(), "slots"
+    assert ids.dim() == 2 and ids.stride(1) == 1 and (ids.shape[0] >= slots or slots == 1), "ids: one row per slot"
+    if ids.dtype != I64 or not ids.is_cuda:
+        raise TypeError("dflash_amd: grammar_advance takes int64 GPU ids")
+    if dyn is not None:
+        assert dyn.numel() >= 8 * slots
+    check(lib().dfl_grammar_advance(table.data_ptr(), table.stride(0), table.shape[0], table.shape[1],
+                                    state.base.data_ptr(), state.state.data_ptr(), slots, ids.data_ptr(), ids.stride(0),
+                                    ids.shape[1], _p(dyn, I32, "dyn"), lo_word, hi_word, lo, hi, _stream()),
+          "dfl_grammar_advance")
+
+
 def gemm_resid(wp, x, N: int, K: int, h_io: torch.Tensor, *, add_residual: bool, ss_out=None, tap=None,
                dyn=None) -> None:
     """h_io [16, >=N] bf16 (unit inner stride) updated in place; tap: optional [16, *] view

@@ -795,7 +795,7 @@ class NativeTarget:
     def verify(self, block_ids: torch.Tensor, start: int, cache: TargetKVCache, *, tap_layers: Sequence[int] = (),
                temperature: float = 0.0, logits_out: Optional[torch.Tensor] = None,
                taps_out: Optional[torch.Tensor] = None, dyn_lengths: bool = False, seed: Optional[int] = None,
-               top_k: int = 0, top_p: float = 1.0, logprobs=None, penalties=None, logit_bias=None):
+               top_k: int = 0, top_p: float = 1.0, logprobs=None, penalties=None, logit_bias=None, grammar=None):
         """block_ids int64 [bs] at positions start..start+bs-1 (cache rows alike), bs <= 32.
         Returns (posterior ids int64 [1, bs], taps bf16 [32, len(tap_layers)*H] or None).
         K/V of all bs rows are written; the caller crops to what it accepts.
@@ -828,8 +828,19 @@ class NativeTarget:
         changes).  Blocks of <= 16 rows: behind the head launch dfl_logit_bias_rows writes the biased rows into .logits —
         row j predicts position start + j + 1, start from the record's POS0 word under dyn_lengths, and loses the stop
         ids while that is < min_pos — and their argmax into the posterior; the penalties, then the draw, run over those
-        rows; logprobs stay those of the raw rows."""
+        rows; logprobs stay those of the raw rows.
+        grammar: an ops.grammar_state with .logits bf16 [16, V] beside it (DecodeSession makes one; None: off, and
+        nothing here changes).  Blocks of <= 16 rows: behind dfl_logit_bias_rows and in front of dfl_penalty_rows,
+        dfl_grammar_rows writes the masked rows into .logits — row j walks the slot's state through block_ids[1 .. j] and
+        sets what is illegal where it arrives to -inf; a row whose walk dies is copied — and their argmax into the
+        posterior; the penalties, then the draw, run over those rows; logprobs stay those of the raw rows (DESIGN.md
+        section 15)."""
         bs = block_ids.numel()
+        if grammar is not None:
+            if bs > 16:
+                raise NotImplementedError("NativeTarget.verify: a grammar takes blocks of <= 16 rows")
+            if temperature >= 1e-5 and seed is None:
+                raise ValueError("a grammar at temperature > 0 needs the seeded draw (seed=...)")
         if penalties is not None:
             if bs > 16:
                 raise NotImplementedError("NativeTarget.verify: penalties take blocks of <= 16 rows")
@@ -917,9 +928,10 @@ class NativeTarget:
                 ops.logprob_rows(logits[16 * t:16 * t + 16], ids[16 * t:], logprobs, nrows=min(16, bs - 16 * t), dyn=dt,
                                  pos_word=ops.DYN_POS0 if dyn_lengths else -1, pos_base=start, pos_add=16 * t + 1)
 
-        if penalties is not None or logit_bias is not None:
-            # one tile: raw logits; biased rows + their argmax; penalised rows + their argmax; the draw over the last of
-            # them; logprobs of the raw rows.  Row m predicts position start + m + 1, start from the record when replayed
+        if penalties is not None or logit_bias is not None or grammar is not None:
+            # one tile: raw logits; biased rows + their argmax; grammar-masked rows + their argmax (masking commutes with
+            # both neighbours: neither turns -inf finite); penalised rows + their argmax; the draw over the last of them;
+            # logprobs of the raw rows.  Row m predicts position start + m + 1, start from the record when replayed
             pen, dt = penalties, tiles[0][1]
             pos = dict(pos_word=ops.DYN_POS0 if dyn_lengths else -1, pos_base=start, pos_add=1)
             if logits is None:
@@ -932,6 +944,9 @@ class NativeTarget:
                 ops.logit_bias_rows(rows, logit_bias.bias, min_pos=logit_bias.min_pos, stop_ids=logit_bias.stop,
                                     out=logit_bias.logits, nrows=bs, dyn=dt, out_ids=post[:16], **pos)
                 rows = logit_bias.logits
+            if grammar is not None:
+                ops.grammar_rows(rows, grammar, block=block_ids, out=grammar.logits, nrows=bs, dyn=dt, out_ids=post[:16])
+                rows = grammar.logits
             if pen is not None:
                 ops.penalty_rows(rows, pen.table, repetition_penalty=pen.r, presence_penalty=pen.a,
                                  frequency_penalty=pen.f, block=block_ids, out=pen.logits, nrows=bs, out_ids=post[:16])

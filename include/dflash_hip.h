@@ -565,6 +565,39 @@ int dfl_logit_bias_rows(const void *logits, void *out, int64_t ld, int64_t tile_
                         int pos_word, int pos_base, int pos_add, int64_t *out_ids, int64_t out_stride, int out_off,
                         void *stream);
 
+/* Grammar-constrained decoding: a token automaton.  The state is a POOL, int16
+ * [pool_states][table_stride >= V] (rows on 16 bytes, table_stride a multiple of 8), holding several grammars at different
+ * base rows: table[(base + s) * table_stride + v] >= 0 is the state, relative to base, after token v in state s; < 0: v is
+ * illegal in s.  Per slot two int32 values: base[slot], the grammar's first pool row (< 0: the slot has no grammar), and
+ * state[slot], relative to base (-1: violated, sticky).  Every row offset (base + s) * table_stride is formed in 64 bits.
+ * A state or successor with base + s >= pool_states reads as violated and is never indexed.
+ *
+ * dfl_grammar_rows: logits / out / ld / tile_stride / tiles / V / row0 / nrows / dyn / nrows_dyn_word / tiles_per_req /
+ * block_ids / block_stride / out_ids / out_stride / out_off exactly as dfl_penalty_rows takes them; out may be the logits
+ * themselves; rows past a tile's valid count return at once and write nothing.  Row m of tile t (tile j = t %
+ * tiles_per_req of slot q = t / tiles_per_req) starts from s = state[q] and walks the block's own tokens
+ * block_ids[q * block_stride + 1 .. 16 j + m] (int64; NULL: no walk — the single-row form for a first token):
+ *   s <- table[(base[q] + s) * table_stride + id], and the row is DEAD once base[q] < 0, s < 0, or an id is outside [0, V)
+ *   live: z[v] = table[(base[q] + s) * table_stride + v] < 0 ? -inf : x[v]      (the bits of x copied; a NaN keeps its bits)
+ *   dead: z = x
+ * A dead row is never committed by the accept rule: row m is compared, or used as the bonus, only when block[1 .. m] were
+ * all accepted, each of them picked from a live row.  out_ids (optional): the row's argmax by the rule of
+ * dfl_penalty_rows; a row that is all -inf gives 0.  No floating-point atomics: the same inputs give the same bits, eager
+ * or replayed. */
+int dfl_grammar_rows(const void *logits, void *out, int64_t ld, int64_t tile_stride, int tiles, int V, int row0, int nrows,
+                     const int32_t *dyn, int nrows_dyn_word, int tiles_per_req, const int16_t *table, int64_t table_stride,
+                     int pool_states, const int32_t *base, const int32_t *state, const int64_t *block_ids,
+                     int64_t block_stride, int64_t *out_ids, int64_t out_stride, int out_off, void *stream);
+
+/* dfl_grammar_advance walks what was committed: one wave per slot 0 .. slots-1, one lane stepping state[s] over
+ * ids[s * ids_stride + i] (int64) for i in [lo', hi') — ids / ids_stride / ids_len / dyn / lo_word / hi_word / lo / hi
+ * exactly as dfl_penalty_count takes them (behind an accept launch: DFL_DYN_S, DFL_DYN_START, 1, 1 is output_ids(S,
+ * START]).  An illegal step or an id outside [0, V) stores -1.  A slot whose DFL_DYN_BS word is 0, whose base is < 0, whose
+ * state is < 0 or whose range is empty is left alone.  Plain vector stores. */
+int dfl_grammar_advance(const int16_t *table, int64_t table_stride, int pool_states, int V, const int32_t *base,
+                        int32_t *state, int slots, const int64_t *ids, int64_t ids_stride, int ids_len, const int32_t *dyn,
+                        int lo_word, int hi_word, int lo, int hi, void *stream);
+
 /* Acceptance scan + commit + bonus token + stop test + length bookkeeping in one
  * wavefront (model/dflash.py:258-268):
  *   acc = #leading i with block[i+1] == posterior[i]           (0..bs-1)
