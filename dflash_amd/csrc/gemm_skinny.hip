@@ -221,10 +221,19 @@ constexpr int gemm_fr(int MT, bool CHUNKED) { return CHUNKED ? 4 : (MT == 1 ? 8 
 // (16 c + w) * 4 .. + 3 — quad 16 c + w of the tile.  An item is that ONE quad (the request of k_moe_gate_up: SG, NB, L0,
 // L1; 13 VGPRs in flight against 16), its meta pair is pair (t * nch + c) * 16 + w, and the chunk's activation fragments
 // go behind the quad as in the bf16 form.
-template <int MT, bool CHUNKED, int EPI, bool NORM, bool W8 = false, bool W13 = false>
+// UNC (the W13 gate/up + SiLU launch only): the item loop requests the next item UNCONDITIONALLY — past the last item a
+// dummy whose descriptor holds zero bytes and whose meta load reads pair 0 — so that hipcc counts the loads in flight
+// exactly.  Behind the loop's `if (i + 1 < nitems)` it counts from the merged state, as if the request had not been made:
+// the first decode of an item then waits at vmcnt(3) / (1) / (0), i.e. for five of the eight words of the item the wave
+// has JUST asked for and, before its last k-steps, for all of it.  The bf16 form has the same waits and loses little (its
+// process step is 8 MFMAs); the 13-bit form puts 8 x 19 VALU of decode per item into that window.  Unconditional, the
+// waits are vmcnt(15) .. (8): an item's decode starts as its own words land, with the whole next item still in flight.
+// Same requests in the same order, same fragments, same MFMAs, same finish(): the conditional loop's bits.
+template <int MT, bool CHUNKED, int EPI, bool NORM, bool W8 = false, bool W13 = false, bool UNC = false>
 __device__ __forceinline__ void gemm_body(const GemmArgs &a, const SampleArgs &sa) {
   GSTAMP(0);
   static_assert(!W13 || (MT == 1 && !W8), "W13: the single-tile bf16 kernels only");
+  static_assert(!UNC || (W13 && !CHUNKED && EPI == EPI_SILU), "unconditional item requests: the W13 gate/up launch only");
   static_assert(!W13 || !CHUNKED || (EPI == EPI_RESID && !NORM), "W13, K-chunked: the residual launch only");
   constexpr int FR = gemm_fr(MT, CHUNKED);
   constexpr int NW = W13 ? (CHUNKED ? 3 : 6) : (W8 ? FR / 2 : FR);  // 16-byte weight words per item and lane
@@ -604,7 +613,14 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &a, const SampleArgs &s
       }
       // (requesting unconditionally — a zero-length dummy past the last item, so that hipcc can count the loads in
       // flight — was tried twice in this 16-wave kernel, rounds 2 and 3: 20.4 -> 20.8 us on down_proj; not kept)
-      if (i + 1 < nitems) load_item(wB, scB, exB, xB, tile_of(jn), cn, half_of(jn));
+      // (... and in the 13-bit gate/up launch, where the decode sits in the wait: kept, UNC above)
+      if constexpr (UNC) {
+        const bool live = i + 1 < nitems;
+        load_w13(wB, exB, live ? tile_of(jn) : 0, ks0_of(0), live ? nf0 : 0, -1);
+        __builtin_amdgcn_sched_barrier(0);
+      } else if (i + 1 < nitems) {
+        load_item(wB, scB, exB, xB, tile_of(jn), cn, half_of(jn));
+      }
       process(wA, scA, exA, xA, tile_of(j), c, j);
       if (i == 0) GSTAMP(4);
       if (i + 1 >= nitems) break;
@@ -613,7 +629,14 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &a, const SampleArgs &s
         c2 = 0;
         ++j2;
       }
-      if (i + 2 < nitems) load_item(wA, scA, exA, xA, tile_of(j2), c2, half_of(j2));
+      if constexpr (UNC) {
+        const bool live = i + 2 < nitems;
+        __builtin_amdgcn_sched_barrier(0);
+        load_w13(wA, exA, live ? tile_of(j2) : 0, ks0_of(0), live ? nf0 : 0, -1);
+        __builtin_amdgcn_sched_barrier(0);
+      } else if (i + 2 < nitems) {
+        load_item(wA, scA, exA, xA, tile_of(j2), c2, half_of(j2));
+      }
       process(wB, scB, exB, xB, tile_of(jn), cn, jn);
       if (i + 2 >= nitems) break;
       j = j2;
@@ -659,7 +682,7 @@ __global__ __launch_bounds__(1024) void k_gemm_w8(GEMM_HEAD_PARAMS, GemmArgs res
 // the W13 form (lossless 13-bit bf16, gemm_body): gate/up + SiLU and lm_head + argmax, the two launches it pays for
 template <int EPI, bool NORM>
 __global__ __launch_bounds__(1024) void k_gemm_w13(GEMM_HEAD_PARAMS, GemmArgs rest) {
-  gemm_body<1, false, EPI, NORM, false, true>(with_head<false, NORM>(rest, GEMM_HEAD_NAMES), SampleArgs{});
+  gemm_body<1, false, EPI, NORM, false, true, EPI == EPI_SILU>(with_head<false, NORM>(rest, GEMM_HEAD_NAMES), SampleArgs{});
 }
 
 // ... and its K-chunked form (down_proj, fc: K a multiple of 2048 above 4096), one quad per item
