@@ -56,8 +56,13 @@ class BatchedDecoder:
                  temperature: float = 0.0, tiles_per_request: int = 1, sampler: str = "torch",
                  draft_temperature: float = 0.0, filtering: bool = False, request_temperature: bool = False,
                  logprobs: Optional[int] = None, penalties: bool = False, logit_bias: bool = False,
-                 grammar_states: int = 0):
-        """grammar_states = N (0: off; fixed here, it fixes the captured launch sequence and the pool's address): a pool
+                 grammar_states: int = 0, constrain_draft: bool = False):
+        """constrain_draft (fixed here for the same reason as grammar_states: it fixes the captured launch sequence; needs
+        grammar_states > 0 or logit_bias, one tile per request and a greedy draft): the draft's head launch materialises
+        its logits and ONE dfl_grammar_draft_rows launch over all tiles re-picks every slot's draft tokens under its
+        automaton and its bans ("The draft under the grammar").  A slot without a grammar and
+        without bans keeps its argmax ids.
+        grammar_states = N (0: off; fixed here, it fixes the captured launch sequence and the pool's address): a pool
         of N automaton rows that add_grammar fills; requests may carry a grammar handle (admit); every verify
         materialises its logits and dfl_grammar_rows masks each slot's rows by the state their prefix of the block
         reaches, between the logit bias and the penalties, and dfl_grammar_advance steps the slots' states behind the
@@ -82,6 +87,15 @@ class BatchedDecoder:
         if grammar_states and temperature >= 1e-5 and sampler != "device":
             raise ValueError("grammar at T > 0 needs sampler='device' (sampler='torch' is the reference's multinomial over "
                              "the raw logits)")
+        if constrain_draft:
+            if not (grammar_states or logit_bias):
+                raise ValueError("constrain_draft needs something to constrain by: a decoder built with grammar_states > 0 "
+                                 "or logit_bias=True")
+            if tiles_per_request != 1:
+                raise NotImplementedError("constrain_draft takes blocks of <= 16 rows (tiles_per_request = 1)")
+            if draft_temperature >= 1e-5:
+                raise NotImplementedError("constrain_draft takes a greedy draft (a sampled draft draws in the head "
+                                          "launch's epilogue, before the pick)")
         if logit_bias and tiles_per_request != 1:
             raise NotImplementedError("logit_bias takes blocks of <= 16 rows (tiles_per_request = 1)")
         if logit_bias and temperature >= 1e-5 and sampler != "device":
@@ -182,6 +196,9 @@ class BatchedDecoder:
             self._gr_logits = z(MT, 16, target.V)
         if self.filtering or self.lp is not None or self.penalties or self.logit_bias or self.grammar is not None:
             self._logits = z(MT, 16, target.V)
+        # constrain_draft: the draft head's materialised logits, read by the pick launch right behind it
+        self.constrain_draft = bool(constrain_draft)
+        self._cd_logits = z(MT, 16, target.V) if self.constrain_draft else None
         self.output_ids = torch.full((NREQ, out_len), self.mask_id, dtype=I64, device=dev)
         self.stop_t = torch.tensor(stop_token_ids, dtype=I64, device=dev) if stop_token_ids else None
         self.stop_token_ids = list(stop_token_ids) if stop_token_ids else None
@@ -554,7 +571,13 @@ class BatchedDecoder:
         elif self.TPR == 1:
             lm = self._lm8() or self.lm_wp
             ops.gemm_argmax_batch(lm, s["xn"], R, c.vocab_size, c.hidden_size, 1, 15, self.gws, self.block, 1,
-                                  self.dyn_tt, nrows_dyn_word=ops.DYN_BS)
+                                  self.dyn_tt, nrows_dyn_word=ops.DYN_BS, logits=self._cd_logits)
+            if self.constrain_draft:
+                # every slot's block[1:BS] re-picked under its automaton and its bans, from the state dfl_grammar_advance
+                # left behind the last accept launch (a run-ahead head is enqueued behind _accept_launch: the new state);
+                # in front of the hook.  A slot with base < 0 and a bias row without bans keeps the argmax ids
+                ops.grammar_draft_rows(self._cd_logits[:R], self.grammar, bias=self.lb.bias if self.logit_bias else None,
+                                       block=self.block, dyn=self.dyn_tt, nrows_dyn_word=ops.DYN_BS)
         else:   # row 0 of a request's SECOND tile is a draft row: all 16 rows of every tile, row 0 of the block dropped here
             lm = self._lm8() or self.lm_wp
             ops.gemm_argmax_batch(lm, s["xn"], R, c.vocab_size, c.hidden_size, 0, 16, self.gws, self.ids_tmp, 0,
@@ -876,7 +899,7 @@ def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_i
                           group_size: int = MAX_GROUP, hook_block_view: bool = False, sampler: str = "torch",
                           seed=None, top_k=0, top_p=1.0, logprobs: Optional[int] = None, repetition_penalty=1.0,
                           presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, allowed_token_ids=None,
-                          banned_token_ids=None, min_tokens=0, grammar=None) -> list:
+                          banned_token_ids=None, min_tokens=0, grammar=None, constrain_draft: bool = False) -> list:
     """`dflash_generate` (benchmark.py:44-251) for a list of prompts: requests run in
     groups of `group_size` <= 4 (<= 2 with block sizes of 17..32 rows) that share the weight stream; returns one namespace per
     prompt with the fields of benchmark.py:242-251 (timing fields are the group's).
@@ -894,7 +917,9 @@ def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_i
     sequence with one value (or None) per prompt.  The decoders are built with logit_bias=True when any prompt is not
     neutral (blocks of <= 16 rows).
     grammar: as dflash_generate; one TokenDFA for every prompt, or a sequence with one (or None) per prompt.  Each group's
-    decoder gets a pool of exactly its prompts' automata (blocks of <= 16 rows); the results carry `grammar_state`."""
+    decoder gets a pool of exactly its prompts' automata (blocks of <= 16 rows); the results carry `grammar_state`.
+    constrain_draft: as dflash_generate (ValueError when no prompt has a grammar or a not-neutral logit-bias keyword); a
+    prompt without a grammar and without bans keeps its argmax draft."""
     logprobs = ops.check_logprobs(logprobs)
     dfas = _prompt_grammars(grammar, len(input_ids))
     for d in {id(d): d for d in dfas if d is not None}.values():
@@ -904,6 +929,11 @@ def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_i
     pens, penalties = _prompt_penalties(repetition_penalty, presence_penalty, frequency_penalty, len(input_ids))
     biases, logit_bias_on = _prompt_bias(target, logit_bias, allowed_token_ids, banned_token_ids, min_tokens,
                                          len(input_ids), stop_token_ids)
+    if constrain_draft and not (_pool_rows(dfas) or logit_bias_on):
+        raise ValueError("constrain_draft needs something to constrain by: a grammar, allowed_token_ids, banned_token_ids "
+                         "or a logit_bias")
+    if constrain_draft and block_size > 16:
+        raise NotImplementedError("constrain_draft takes blocks of <= 16 rows")
     temps, per_request = _prompt_temperatures(temperature, len(input_ids), sampler)
     seeds = _prompt_seeds(sampler, seed, len(input_ids), any(t >= 1e-5 for t in temps))
     top_ks, top_ps, filtering = _prompt_filters(top_k, top_p, len(input_ids), temps, sampler)
@@ -927,7 +957,9 @@ def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_i
                              stop_token_ids=stop_token_ids, temperature=max(temps[i] for i in idx), tiles_per_request=tpr,
                              sampler=sampler, filtering=filtering, request_temperature=per_request, logprobs=logprobs,
                              penalties=penalties, logit_bias=logit_bias_on,
-                             grammar_states=_pool_rows([dfas[i] for i in idx]))
+                             grammar_states=_pool_rows([dfas[i] for i in idx]),
+                             # (a group none of whose prompts has anything to constrain by runs the plain launches)
+                             constrain_draft=bool(constrain_draft) and bool(logit_bias_on or _pool_rows([dfas[i] for i in idx])))
         handles = _load_grammars(dec, [dfas[i] for i in idx])
         t0 = cuda_time()
         for r, p in enumerate(prompts):

@@ -128,8 +128,12 @@ class BatchEngine:
                  block_size: int = 16, stop_token_ids=None, temperature: float = 0.0, sampler: str = "torch",
                  graph: Optional[bool] = None, filtering: bool = False, request_temperature: bool = False,
                  logprobs: Optional[int] = None, penalties: bool = False, logit_bias: bool = False,
-                 grammar_states: int = 0):
-        """grammar_states = N (0: off): a pool of N automaton rows; add_grammar loads a TokenDFA into it and returns the
+                 grammar_states: int = 0, constrain_draft: bool = False):
+        """constrain_draft: every slot's draft tokens are re-picked under its grammar and its bans right behind the draft's
+        head launch ("The draft under the grammar"); fixed here because it fixes the captured
+        launch sequence; needs grammar_states > 0 or logit_bias=True (ValueError).  The emitted ids do not change; a
+        request without a grammar and without bans keeps its argmax draft.
+        grammar_states = N (0: off): a pool of N automaton rows; add_grammar loads a TokenDFA into it and returns the
         handle submit takes.  Fixed here because it fixes the captured launch sequence; the pool's
         address is fixed too, so the one capture serves grammars loaded later.  Requests without a grammar emit the same
         ids; results carry `grammar_state`.
@@ -162,7 +166,8 @@ class BatchEngine:
         self.dec = BatchedDecoder(model, target, slots, max_rows=max_rows, out_len=out_len, mask_token_id=mask_token_id,
                                   stop_token_ids=stop_token_ids, temperature=temperature, sampler=sampler,
                                   filtering=filtering, request_temperature=request_temperature, logprobs=logprobs,
-                                  penalties=penalties, logit_bias=logit_bias, grammar_states=grammar_states)
+                                  penalties=penalties, logit_bias=logit_bias, grammar_states=grammar_states,
+                                  constrain_draft=constrain_draft)
         self.filtering, self.temperature, self.penalties = bool(filtering), float(temperature), bool(penalties)
         self.logit_bias = bool(logit_bias)
         self.request_temperature = bool(request_temperature)
@@ -244,7 +249,7 @@ def dflash_generate_stream(model, target, input_ids: Sequence[torch.Tensor], mas
                            sampler: str = "torch", seed=None, top_k=0, top_p=1.0,
                            logprobs: Optional[int] = None, repetition_penalty=1.0, presence_penalty=0.0,
                            frequency_penalty=0.0, logit_bias=None, allowed_token_ids=None, banned_token_ids=None,
-                           min_tokens=0, grammar=None) -> list:
+                           min_tokens=0, grammar=None, constrain_draft: bool = False) -> list:
     """`dflash_generate_batch` with slot refill: one namespace per prompt with the fields of benchmark.py:242-251, each
     request emitting what its own `dflash_generate` run emits.  max_new_tokens: one int or one per prompt.
     draft_token_hook(request_index, block_view, start, call).  seed as in dflash_generate_batch (an int s gives prompt i
@@ -255,7 +260,8 @@ def dflash_generate_stream(model, target, input_ids: Sequence[torch.Tensor], mas
     repetition_penalty / presence_penalty / frequency_penalty: a scalar or one value per prompt.
     logit_bias / allowed_token_ids / banned_token_ids / min_tokens: one value for every prompt, or a sequence with one
     value (or None) per prompt.
-    grammar: one TokenDFA for every prompt, or a sequence with one (or None) per prompt."""
+    grammar: one TokenDFA for every prompt, or a sequence with one (or None) per prompt.
+    constrain_draft: as dflash_generate_batch."""
     dfas = _prompt_grammars(grammar, len(input_ids))
     for d in {id(d): d for d in dfas if d is not None}.values():
         ops.check_grammar(d, target.V)
@@ -277,7 +283,7 @@ def dflash_generate_stream(model, target, input_ids: Sequence[torch.Tensor], mas
                       out_len=need + BLOCK_ROWS, mask_token_id=mask_token_id, block_size=block_size,
                       stop_token_ids=stop_token_ids, temperature=max(temps, default=0.0), sampler=sampler, filtering=filtering,
                       request_temperature=per_request, logprobs=logprobs, penalties=penalties, logit_bias=logit_bias_on,
-                      grammar_states=_pool_rows(dfas))
+                      grammar_states=_pool_rows(dfas), constrain_draft=constrain_draft)
     handles = _load_grammars(eng, dfas)
     for i, p in enumerate(input_ids):
         hook = (lambda blk, start, call, i=i: draft_token_hook(i, blk, start, call)) if draft_token_hook else None

@@ -207,7 +207,7 @@ class DecodeSession:
                  draft_token_hook: Optional[Callable] = None, sampler: str = "torch", seed: Optional[int] = None,
                  top_k: int = 0, top_p: float = 1.0, logprobs: Optional[int] = None, repetition_penalty: float = 1.0,
                  presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None,
-                 banned_token_ids=None, min_tokens: int = 0, grammar=None):
+                 banned_token_ids=None, min_tokens: int = 0, grammar=None, constrain_draft: bool = False):
         from .target import NativeTarget
         # grammar: a TokenDFA the emitted tokens must walk; None: every launch below is the one
         # enqueued without the keyword
@@ -358,6 +358,21 @@ class DecodeSession:
         self.record_events = True  # False: record nothing new, but still hand a run-ahead draft's pairs to self.events
         self.host_times = None  # a list: cycle() appends (seconds enqueueing launches, seconds polling for the result)
         self.draft_logits = None  # set to a bf16 [32, V] buffer to have the draft's logits materialised into it
+        # constrain_draft: every greedy draft head below materialises its logits and dfl_grammar_draft_rows re-picks the
+        # block's draft tokens under the automaton and the bans ("The draft under the grammar").
+        # Off: every launch is the one enqueued without the keyword.  Only the bans of the bias row are read, and only
+        # where it has one: a row of finite biases alone leaves nothing to constrain by
+        self.constrain = bool(constrain_draft)
+        if self.constrain:
+            if draft_temperature >= 1e-5:
+                raise NotImplementedError("constrain_draft takes a greedy draft (a sampled draft draws in the head launch's "
+                                          "epilogue, before the pick)")
+            bans = lb is not None and bool(torch.isneginf(lb[0]).any())
+            if grammar is None and not bans:
+                raise ValueError("constrain_draft needs something to constrain by: a grammar, allowed_token_ids, "
+                                 "banned_token_ids or a logit_bias of -inf")
+            self._cd_bias = self.lb.bias if bans else None
+            self.draft_logits = torch.zeros(16, target.V, dtype=torch.bfloat16, device=dev)
         # the tapped rows live here from a verify to the next draft (own buffer: several
         # sessions may be interleaved on one NativeTarget)
         self.taps_buf = (torch.zeros(32, len(model.target_layer_ids) * model.config.hidden_size, dtype=torch.bfloat16,
@@ -431,6 +446,13 @@ class DecodeSession:
         """The e4m3 lm_head for the draft's greedy unmask, or None (a bf16 model, or fp8_stream switched off)."""
         return self.lm_wp8 if self.model.fp8_stream else None
 
+    def _constrain_draft(self, bs) -> None:
+        """Right behind a greedy draft head launch, in front of the hook: block[1:bs] re-picked row by row from the head's
+        materialised logits, each the best token that is legal in the state reached over the picks before it.  The
+        slot's state is read, never written: it moves in _count_committed alone."""
+        if self.constrain:
+            ops.grammar_draft_rows(self.draft_logits[:16], self.gr, bias=self._cd_bias, block=self.block[0], nrows=bs)
+
     def _draft_ahead(self, bs) -> None:
         """The draft forward of the cycle AFTER the one whose accept kernel has just been enqueued (model/dflash.py:237-247
         of the next loop iteration): lengths from the device record, context rows = the verify's tap buffer (valid count
@@ -445,6 +467,9 @@ class DecodeSession:
         if ev:
             ev[2].record()
         _draft_ids(m, hid, self.lm_wp, bs, self.block[:, :bs], 0.0, self.draft_logits, lm_wp8=self._lm8())
+        # (cycle() enqueues this draft behind _count_committed: the state the pick reads is the one AFTER the advance
+        # over what the accept launch has just committed — the state the next verify's rows start from)
+        self._constrain_draft(bs)
         if ev:
             ev[3].record()
             ev[1].record()
@@ -489,6 +514,7 @@ class DecodeSession:
             self._mark("lm_head", 0)
             _draft_ids(m, hid, self.lm_wp, bs, blk, self.draft_temperature, self.draft_logits, seed=self._dseed,
                        dyn=self.dcache.dyn, start=self.start, lm_wp8=self._lm8())
+            self._constrain_draft(bs)
             self._mark("lm_head", 1)
             return self._call_hook(blk)
         # benchmark.py:112-142: k full passes, each re-embedding the whole block, no draft
@@ -503,7 +529,9 @@ class DecodeSession:
                 c2, p0 = ctx[ctx_len - 16:], p0 + ctx_len - 16
             hid = m.draft_block(tmp, th_rows=c2, tau=c2.shape[0], bs=bs, pos0=p0, block_ids=blk[0],
                                 embed=self.embed_w, append=False)
-            _draft_ids(m, hid, self.lm_wp, bs, blk, 0.0, lm_wp8=self._lm8())
+            _draft_ids(m, hid, self.lm_wp, bs, blk, 0.0, self.draft_logits if self.constrain else None,
+                       lm_wp8=self._lm8())
+            self._constrain_draft(bs)
             self._call_hook(blk)
 
     @torch.inference_mode()
@@ -661,6 +689,7 @@ class DecodeSession:
                                 embed=self.embed_w, dyn_ready=True, s_bound=bound)
             _draft_ids(m, hid, self.lm_wp, bs, self.block[:, :bs], self.draft_temperature, self.draft_logits,
                        seed=self._dseed, dyn=self.dcache.dyn, lm_wp8=self._lm8())
+            self._constrain_draft(bs)
 
         def verify_accept(bs):   # (a T > 0 draw takes its positions from the target record's POS0 word: fresh every replay)
             post, _ = t.verify(self.block[0, :bs], bound, self.tcache, temperature=self.temperature, tap_layers=tl,
@@ -835,14 +864,16 @@ def run_decode(model, target, input_ids: torch.Tensor, *, mask_token_id: int, ma
                max_block_size: Optional[int] = None, sampler: str = "torch", seed: Optional[int] = None,
                top_k: int = 0, top_p: float = 1.0, logprobs: Optional[int] = None, repetition_penalty: float = 1.0,
                presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None,
-               banned_token_ids=None, min_tokens: int = 0, grammar=None) -> SimpleNamespace:
+               banned_token_ids=None, min_tokens: int = 0, grammar=None,
+               constrain_draft: bool = False) -> SimpleNamespace:
     s = DecodeSession(model, target, input_ids, mask_token_id=mask_token_id, max_new_tokens=max_new_tokens,
                       max_block_size=max_block_size or block_size, stop_token_ids=stop_token_ids,
                       temperature=temperature, draft_temperature=draft_temperature,
                       draft_token_hook=draft_token_hook, sampler=sampler, seed=seed, top_k=top_k, top_p=top_p,
                       logprobs=logprobs, repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
                       frequency_penalty=frequency_penalty, logit_bias=logit_bias, allowed_token_ids=allowed_token_ids,
-                      banned_token_ids=banned_token_ids, min_tokens=min_tokens, grammar=grammar)
+                      banned_token_ids=banned_token_ids, min_tokens=min_tokens, grammar=grammar,
+                      constrain_draft=constrain_draft)
     t_prefill = cuda_time()
     s.prefill()
     time_to_first_token = cuda_time() - t_prefill
@@ -1010,13 +1041,18 @@ def dflash_generate(model, target, input_ids: torch.Tensor, mask_token_id: int, 
                     seed: Optional[int] = None, top_k: int = 0, top_p: float = 1.0,
                     logprobs: Optional[int] = None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
                     frequency_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None, banned_token_ids=None,
-                    min_tokens: int = 0, grammar=None) -> SimpleNamespace:
+                    min_tokens: int = 0, grammar=None, constrain_draft: bool = False) -> SimpleNamespace:
     """benchmark.py:44-55 signature; returns the namespace of :242-251 (+ replayed_cycles).
     grammar (a dflash_amd.TokenDFA; None: off; needs a NativeTarget, blocks of <= 16 rows, and sampler="device" at
     T > 0): the emitted tokens walk the automaton from its start state — every verify row is masked by the state its
     own prefix of the block reaches, between the logit bias and the penalties.  The result's
     `grammar_state` is the state after the returned tokens (-1: violated; None when off).  The draft's proposals stay
-    unconstrained.
+    unconstrained unless constrain_draft is set.
+    constrain_draft (False: off, the launches of before; needs a grammar or a ban — allowed_token_ids, banned_token_ids,
+    a logit_bias of -inf —, else ValueError; a greedy draft): each draft token is the draft's best choice among the
+    tokens the request could emit at that point of the block — one launch behind the draft's head picks row by row
+    under the automaton and the bans ("The draft under the grammar").  The emitted ids do not
+    change, only the acceptance lengths.
     logit_bias ({id: bias}, finite or -inf) / allowed_token_ids / banned_token_ids / min_tokens (None / None / None / 0:
     off; need a NativeTarget, blocks of <= 16 rows, and sampler="device" at T > 0): the OpenAI / vLLM controls on the
     target's logits, applied before the penalties; no stop id is emitted before min_tokens tokens are out (DESIGN.md
@@ -1039,14 +1075,16 @@ def dflash_generate(model, target, input_ids: torch.Tensor, mask_token_id: int, 
                                      temperature, collect_profile, draft_steps, draft_token_hook, sampler, seed, top_k, top_p,
                                      logprobs, (repetition_penalty, presence_penalty, frequency_penalty),
                                      dict(logit_bias=logit_bias, allowed_token_ids=allowed_token_ids,
-                                          banned_token_ids=banned_token_ids, min_tokens=min_tokens))
+                                          banned_token_ids=banned_token_ids, min_tokens=min_tokens),
+                                     constrain_draft=constrain_draft)
     r = run_decode(model, target, input_ids, mask_token_id=mask_token_id, max_new_tokens=max_new_tokens,
                    block_size=block_size, stop_token_ids=stop_token_ids, temperature=temperature, clamp_tail=True,
                    draft_steps=draft_steps, collect_profile=collect_profile, draft_token_hook=draft_token_hook,
                    sampler=sampler, seed=seed, top_k=top_k, top_p=top_p, logprobs=logprobs,
                    repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
                    frequency_penalty=frequency_penalty, logit_bias=logit_bias, allowed_token_ids=allowed_token_ids,
-                   banned_token_ids=banned_token_ids, min_tokens=min_tokens, grammar=grammar)
+                   banned_token_ids=banned_token_ids, min_tokens=min_tokens, grammar=grammar,
+                   constrain_draft=constrain_draft)
     return SimpleNamespace(output_ids=r.output_ids, num_input_tokens=r.num_input_tokens,
                            num_output_tokens=r.num_output_tokens, time_to_first_token=r.time_to_first_token,
                            time_per_output_token=r.time_per_output_token, acceptance_lengths=r.acceptance_lengths,
@@ -1058,7 +1096,7 @@ def dflash_generate(model, target, input_ids: torch.Tensor, mask_token_id: int, 
 def _generate_wide_hidden(model, target, input_ids, mask_token_id, max_new_tokens, block_size, stop_token_ids, temperature,
                           collect_profile=False, draft_steps=1, draft_token_hook=None, sampler="torch",
                           seed=None, top_k=0, top_p=1.0, logprobs=None, penalties=(1.0, 0.0, 0.0),
-                          bias=None) -> SimpleNamespace:
+                          bias=None, constrain_draft=False) -> SimpleNamespace:
     """hidden_size > 4096: the request runs as a group of ONE through the ragged-batch kernels (their GEMMs cut K over
     workgroups; the single-request kernels keep a whole K = hidden row slice per workgroup).  Same loop semantics
     (benchmark.py:44-251, tail clamp included); no per-cycle profile, one draft step per cycle."""
@@ -1074,7 +1112,8 @@ def _generate_wide_hidden(model, target, input_ids, mask_token_id, max_new_token
                                  temperature, draft_token_hook=hook, group_size=1, hook_block_view=True, sampler=sampler,
                                  seed=None if seed is None else [seed], top_k=top_k, top_p=top_p, logprobs=logprobs,
                                  repetition_penalty=penalties[0], presence_penalty=penalties[1],
-                                 frequency_penalty=penalties[2], **_one_prompt_bias(bias))[0]
+                                 frequency_penalty=penalties[2], **_one_prompt_bias(bias),
+                                 constrain_draft=constrain_draft)[0]
 
 
 def _one_prompt_bias(bias) -> dict:
@@ -1092,9 +1131,11 @@ def dflash_generate_policy(*, model, target, input_ids: torch.Tensor, mask_token
                            seed: Optional[int] = None, top_k: int = 0, top_p: float = 1.0,
                            logprobs: Optional[int] = None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
                            frequency_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None, banned_token_ids=None,
-                           min_tokens: int = 0, grammar=None) -> SimpleNamespace:
+                           min_tokens: int = 0, grammar=None, constrain_draft: bool = False) -> SimpleNamespace:
     """benchmark_dynamic_schedule.py:260-272 signature; returns the namespace of :425-434 (+ replayed_cycles).
     grammar: as dflash_generate (the target's rows; the draft's own draw stays unconstrained; `grammar_state`).
+    constrain_draft: as dflash_generate; this loop drafts at the request's temperature, so it needs temperature = 0
+    (NotImplementedError for a sampled draft).
     logprobs: as dflash_generate (the fields logprobs / top_logprob_ids / top_logprobs; None when off).
     sampler / seed: as dflash_generate; the draft's own T > 0 draw uses the same seed on a stream of its own.
     top_k / top_p: as dflash_generate (the target's draw; the draft's own draw stays unfiltered).
@@ -1110,7 +1151,8 @@ def dflash_generate_policy(*, model, target, input_ids: torch.Tensor, mask_token
                    draft_token_hook=draft_token_hook, sampler=sampler, seed=seed, top_k=top_k, top_p=top_p,
                    logprobs=logprobs, repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
                    frequency_penalty=frequency_penalty, logit_bias=logit_bias, allowed_token_ids=allowed_token_ids,
-                   banned_token_ids=banned_token_ids, min_tokens=min_tokens, grammar=grammar)
+                   banned_token_ids=banned_token_ids, min_tokens=min_tokens, grammar=grammar,
+                   constrain_draft=constrain_draft)
     if fixed_block_size is not None:
         for row in r.cycle_trace:
             for k in ("tau_hat", "cycle_hat", "score_hat", "current_block_size", "adl_lgen_hat", "adl_lacc_hat",

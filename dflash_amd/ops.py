@@ -1075,6 +1075,59 @@ def grammar_rows(logits: torch.Tensor, state, *, block=None, out: Optional[torch
     return out
 
 
+def grammar_draft_rows(logits: torch.Tensor, state=None, *, bias: Optional[torch.Tensor] = None, block: torch.Tensor,
+                       nrows: Optional[int] = None, dyn=None, nrows_dyn_word: int = -1, tiles_per_req: int = 1) -> None:
+    """The draft's block tokens picked under the automaton (dfl_grammar_draft_rows): logits bf16
+    [rows <= 16, V] (one slot) or [tiles, 16, V], row m predicting block slot m, as the draft's head launch materialised
+    them; block int64 [slots, >= 16] or 1-D for one slot, block[q, 1:n] holding that launch's argmax.  Slot q walks
+    state[q] (a grammar_state; None: the ban-only form) row by row: block[q, m] <- the lowest legal column among the
+    maxima over the legal, non-NaN columns of row m, legal = a successor >= 0 in the state reached over block[q, 1:m]
+    and not banned (bias fp32 [slots, V] or [V], the logit-bias table: -inf is a ban, finite values are ignored; None:
+    the grammar-only form).  The walk stops, and the ids from there on stay, at a violated state, a row without such a
+    column, or a successor outside the pool.  n = nrows (None: the logits' rows), or dyn[t][nrows_dyn_word].  The
+    state is only read.  tiles_per_req = 2 (17..32-row blocks) is refused."""
+    if tiles_per_req != 1:
+        raise NotImplementedError("dflash_amd: grammar_draft_rows takes one tile per request (blocks of <= 16 rows)")
+    if state is None and bias is None:
+        raise ValueError("dflash_amd: grammar_draft_rows needs a grammar state or a bias table to constrain by")
+    assert logits.dim() in (2, 3) and logits.stride(-1) == 1 and logits.is_cuda and logits.dtype == BF16
+    if logits.dim() == 2:
+        assert logits.shape[0] <= 16, "one tile holds at most 16 rows"
+        tiles, tile_rows, tile_stride = 1, logits.shape[0], 16 * logits.stride(0)
+    else:
+        assert logits.shape[1] == 16
+        tiles, tile_rows, tile_stride = logits.shape[0], 16, logits.stride(0)
+    V, ld = logits.shape[-1], logits.stride(-2)
+    if nrows is None:
+        nrows = tile_rows
+    assert 0 <= nrows <= tile_rows or nrows_dyn_word >= 0 and tile_rows == 16
+    n_out = 16 if nrows_dyn_word >= 0 else nrows
+    t_p, t_stride, t_rows, b_p, s_p = None, 0, 0, None, None
+    if state is not None:
+        table = _grammar_pool(state)
+        assert table.shape[1] == V and state.base.numel() >= tiles and state.state.numel() >= tiles, "one base / state per slot"
+        t_p, t_stride, t_rows, b_p, s_p = table.data_ptr(), table.stride(0), table.shape[0], state.base.data_ptr(), state.state.data_ptr()
+    bias_p, bias_stride = None, 0
+    if bias is not None:
+        if bias.dim() == 1:
+            bias = bias.unsqueeze(0)
+        assert bias.dim() == 2 and bias.stride(1) == 1 and bias.shape == (bias.shape[0], V) and bias.shape[0] >= tiles
+        if bias.dtype != F32 or not bias.is_cuda:
+            raise TypeError("dflash_amd: the logit-bias table must be an fp32 GPU tensor")
+        bias_p, bias_stride = bias.data_ptr(), bias.stride(0)
+    if block.dtype != I64 or not block.is_cuda:
+        raise TypeError("dflash_amd: block must be an int64 GPU tensor")
+    assert block.stride(-1) == 1 and block.shape[-1] >= n_out, "block"
+    assert block.dim() == 2 and block.shape[0] >= tiles or block.dim() == 1 and tiles == 1, "block"
+    blk_stride = block.stride(0) if block.dim() == 2 else 0
+    assert tiles == 1 or blk_stride >= 16, "block: one row of >= 16 ids per slot"
+    if dyn is not None:
+        assert dyn.numel() >= 8 * tiles
+    check(lib().dfl_grammar_draft_rows(logits.data_ptr(), ld, tile_stride, tiles, V, nrows, _p(dyn, I32, "dyn"),
+                                       nrows_dyn_word, t_p, t_stride, t_rows, b_p, s_p, bias_p, bias_stride,
+                                       block.data_ptr(), blk_stride, _stream()), "dfl_grammar_draft_rows")
+
+
 def grammar_advance(state, ids: torch.Tensor, *, lo: int = 0, hi: int = 0, dyn=None, lo_word: int = 0,
                     hi_word: int = 0, slots: Optional[int] = None) -> None:
     """Step every slot's state over ids[s, lo':hi'] (dfl_grammar_advance; ids int64 [slots, n] or [n]); the range and the

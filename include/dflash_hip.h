@@ -598,6 +598,29 @@ int dfl_grammar_advance(const int16_t *table, int64_t table_stride, int pool_sta
                         int32_t *state, int slots, const int64_t *ids, int64_t ids_stride, int ids_len, const int32_t *dyn,
                         int lo_word, int hi_word, int lo, int hi, void *stream);
 
+/* dfl_grammar_draft_rows: the draft's block tokens picked under the automaton ("The draft under
+ * the grammar").  logits / ld / tile_stride / tiles / V / dyn / nrows_dyn_word and the pool as dfl_grammar_rows takes
+ * them, ONE tile per slot (tile t is slot t); nrows (0..16) is the block size n, or dyn[t][nrows_dyn_word] when
+ * nrows_dyn_word >= 0.  Row m of the bf16 logits predicts block slot m; block_ids[t * block_stride + 1 .. n-1] (int64)
+ * hold the head launch's plain argmax on entry.  One 1024-thread workgroup per slot walks the rows in order:
+ *   s = state[t]                         (base[t] < 0 or table == NULL: no grammar, every column grammar-legal)
+ *   for m = 1 .. n-1:
+ *     legal(v) = (no grammar or table[(base[t] + s) * table_stride + v] >= 0) and (bias == NULL or bias[t][v] != -inf)
+ *     grammar and s < 0 (or base + s >= pool_states): stop
+ *     c = the lowest legal column among those whose logit is maximal over the legal, non-NaN columns; none: stop
+ *     block_ids[t * block_stride + m] = c
+ *     grammar: s = table[(base[t] + s) * table_stride + c], a successor outside the pool: stop
+ * "stop" leaves the ids from there on as they were.  -0 == +0; a legal -inf wins only when every legal column is -inf or
+ * NaN.  bias (fp32 [tiles][bias_stride >= V], rows on 16 bytes; NULL: the grammar-only form): the logit-bias table, of
+ * which only the bans (-inf) are read.  table == NULL (with bias): the ban-only form, rows independent of each other.  A
+ * slot with neither a grammar nor a bias table, an idle slot (n < 2) and row 0 are left untouched.  state is only read.
+ * Every pool offset is formed in 64 bits.  No atomics, plain vector stores: the same inputs give the same bits, eager or
+ * replayed. */
+int dfl_grammar_draft_rows(const void *logits, int64_t ld, int64_t tile_stride, int tiles, int V, int nrows,
+                           const int32_t *dyn, int nrows_dyn_word, const int16_t *table, int64_t table_stride,
+                           int pool_states, const int32_t *base, const int32_t *state, const float *bias,
+                           int64_t bias_stride, int64_t *block_ids, int64_t block_stride, void *stream);
+
 /* Acceptance scan + commit + bonus token + stop test + length bookkeeping in one
  * wavefront (model/dflash.py:258-268):
  *   acc = #leading i with block[i+1] == posterior[i]           (0..bs-1)
