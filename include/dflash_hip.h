@@ -297,7 +297,9 @@ int dfl_attn_fused(const float *qkv, int nsplit, int64_t split_stride, int ld, i
  * query tile's frag16 output lies out_tile_stride bf16 elements after the first.
  * Lengths: dyn == NULL -> the immediates S, tau, bs, pos0; else they are read from dyn and S is the caller's
  * upper bound on dyn[S] (it sizes the key splits, as kv_len_max does for dfl_attn_fused).
- * ws: dfl_attn_head_ws_bytes(n_q, max_splits, q_tiles) bytes, ZEROED once (arrival tickets, left zero). */
+ * ws: dfl_attn_head_ws_bytes(n_q, max_splits, q_tiles) bytes, ZEROED once (arrival tickets, left zero).  Only the tickets
+ * need the zeros: the split partials in front of them may hold anything.  The figure, like dfl_attn_fused_ws_bytes and
+ * dfl_attn_fused_batch_ws_bytes, ends in 64 bytes of slack behind the last ticket: an upper bound, not a tight size. */
 int64_t dfl_attn_head_ws_bytes(int n_q, int max_splits, int q_tiles);
 int dfl_attn_head(const void *xq, int64_t ldq, int q_col, int k_col, int v_col, const void *xc, int64_t ldc,
                   int ck_col, int cv_col, int n_q, int n_kv, const void *q_norm_w, const void *k_norm_w, float eps,
@@ -697,7 +699,11 @@ int dfl_prefill_attn(const void *q_rows, int64_t ldq, int q_col, const void *kca
  *                           [P][8]; then (one workgroup) per-expert counts cnt and tile offsets, the work list items =
  *                           (expert, first gathered tile, tiles <= 4) with n_items[0] = items, [1] = tiles, posmap
  *                           [P][8] = gathered row of each pair, src_row / row_w [gathered row] = its source row (-1:
- *                           padding) and routing weight (bf16 value, as float)
+ *                           padding) and routing weight (bf16 value, as float).  WHICH gathered row of its expert's tiles
+ *                           a (row, slot) pair gets is decided by the order integer atomics land in: posmap, src_row,
+ *                           row_w and the row order of xg / act_g / out32 may differ from launch to launch on the same
+ *                           inputs; pair_e / pair_w / cnt / tile_off / n_items and what dfl_prefill_moe_combine leaves
+ *                           in h (each row's slots added in slot order) do not
  *   dfl_prefill_moe_gather  the source rows' normalised fragments into the gathered tiles xg (zero for padding rows)
  *   dfl_prefill_moe_gemm_silu   act_g = silu(xg Wg_e^T) * (xg Wu_e^T) per expert (gate/up interleaved as dfl_pack_weight_gateup);
  *                               with src_row (and 1 KiB of zeros for padding rows) `xg` is the UNGATHERED x_frag and the
