@@ -347,7 +347,8 @@ class NativeTarget:
     def check_config(cfg, weight_format: str = "bf16", expert_format: str = "bf16") -> None:
         """Architectures the kernels do not cover are rejected loudly, before any launch (the reference is shape-agnostic:
         model/dflash.py:36,42-56 take head_dim, attention_bias and sliding_window from the config; no BASELINE config
-        needs them): head_dim != 128, biased projections, sliding-window attention layers.  weight_format: an unknown
+        needs them): head_dim != 128, biased projections, sliding-window attention layers, a sparse-MoE target (num_experts)
+        whose hidden_size exceeds 4096 or is no multiple of 32.  weight_format: an unknown
         one is a ValueError; "fp8_e4m3" refuses a sparse-MoE target (its experts take expert_format instead) and hidden,
         intermediate or q widths that are not multiples of 64 (the packed e4m3 layout holds k-step pairs).
         expert_format: an unknown one is a ValueError; "fp8_e4m3" needs a sparse-MoE config (num_experts) whose hidden_size
@@ -365,6 +366,10 @@ class NativeTarget:
         lt = getattr(cfg, "layer_types", None) or ()
         if any(t == "sliding_attention" for t in lt) and getattr(cfg, "sliding_window", None):
             raise NotImplementedError("NativeTarget: sliding-window attention layers are not supported; keep the HF target")
+        if getattr(cfg, "num_experts", 0) and (cfg.hidden_size > 4096 or cfg.hidden_size % 32):
+            # (the experts' gate/up launch covers one K pass of 16 waves x 8 k-steps of 32: dfl_gemm_silu_mul_experts)
+            raise NotImplementedError(f"NativeTarget: the sparse-MoE expert kernels cover hidden_size <= 4096 in multiples "
+                                      f"of 32 (got {cfg.hidden_size}); keep the HF target")
         if weight_format == "fp8_e4m3":
             if getattr(cfg, "num_experts", 0) or getattr(cfg, "num_local_experts", 0):
                 raise NotImplementedError("NativeTarget: fp8_e4m3 weights are not supported for sparse-MoE targets (the "

@@ -149,6 +149,24 @@ def check_plan(pair_e, pair_w, E: int, tpi: int, cnt, tile_off, n_items, items, 
     return dict(cnt=want_cnt, tiles=tiles, tile_off=want_off, n_items=want_n, items=want_items)
 
 
+FLT_MAX = 3.4028234663852886e38
+
+
+def expert_act_ref(x, gate_e, up_e, fp32_range: bool = False):
+    """One expert's gate/up stage in fp64 with the kernels' rounding points (tf:modeling_qwen3.py:82 — the two Linear
+    outputs are bf16, silu is rounded, the product is rounded again): bf16(bf16(silu(bf16(gate_e x))) * bf16(up_e x)).
+    x [rows, H], gate_e / up_e [I, H] hold bf16 values in fp64; returns [rows, I] bf16 values in fp64.
+    fp32_range: the model evaluates silu in fp32, where exp(-g) overflows for g < -88.72 and g / (1 + inf) is -0 in any
+    fp32 evaluation (torch's included), while fp64 still holds |silu| <= 89 e^-89 = 2e-37: those elements are -0 here
+    too.  For a comparison in bf16 steps; a bound relative to the sums' magnitude does not see the difference."""
+    gb, ub = rbf(x @ gate_e.T), rbf(x @ up_e.T)
+    ex = torch.exp(-gb)
+    silu = gb / (1.0 + ex)
+    if fp32_range:
+        silu = torch.where(ex > FLT_MAX, torch.full_like(silu, -0.0), silu)
+    return rbf(rbf(silu) * ub)
+
+
 def moe_rows_ref(x, gate, up, down, pair_e, pair_w):
     """The routed MLP rows of given pairs, expert by expert in fp64 with the roundings of k_pgemm's epilogues:
     out[m, r] = w[m, r] * down_e(bf16(bf16(silu(bf16(gate_e x_m))) * bf16(up_e x_m))), e = pair_e[m, r].
@@ -163,8 +181,7 @@ def moe_rows_ref(x, gate, up, down, pair_e, pair_w):
         m, r = torch.nonzero(pair_e.to(x.device) == e, as_tuple=True)
         if m.numel() == 0:
             continue
-        gb, ub = rbf(x[m] @ gate[e].T), rbf(x[m] @ up[e].T)
-        act = rbf(rbf(gb / (1.0 + torch.exp(-gb))) * ub)
+        act = expert_act_ref(x[m], gate[e], up[e])
         out[m, r] = w[m, r][:, None] * (act @ down[e].T)
         mag[m, r] = act.abs() @ down[e].abs().T
     return out, mag

@@ -61,3 +61,26 @@ def test_rejects_unsupported_architectures_before_any_launch():
     hf = types.SimpleNamespace(config=types.SimpleNamespace(**{**base, "attention_bias": True}))
     with pytest.raises(NotImplementedError, match="bias"):
         NativeTarget(hf)        # never reaches hf.lm_head / the device
+
+
+def test_rejects_moe_widths_the_expert_kernels_do_not_cover():
+    """The experts' gate/up launch (dfl_gemm_silu_mul_experts) covers one K pass of at most 4096 in k-steps of 32: a
+    sparse-MoE config beyond that is refused by check_config, not by the first verify.  Hidden 4096 (Qwen3-235B-A22B)
+    passes; dense configs of the refused widths are not this check's business."""
+    import types
+    from dflash_amd.target import NativeTarget
+
+    def cfg(hidden, heads, **kw):
+        return types.SimpleNamespace(num_attention_heads=heads, hidden_size=hidden, head_dim=128, attention_bias=False,
+                                     mlp_bias=False, layer_types=["full_attention"] * 2, sliding_window=None, **kw)
+    moe = dict(num_experts=128, num_experts_per_tok=8, moe_intermediate_size=1536)
+    NativeTarget.check_config(cfg(4096, 64, **moe))
+    NativeTarget.check_config(cfg(2048, 32, **moe))
+    for hidden in (5120, 2064):
+        with pytest.raises(NotImplementedError, match=r"hidden_size <= 4096 in multiples of 32.*keep the HF target"):
+            NativeTarget.check_config(cfg(hidden, 16, **moe))
+        NativeTarget.check_config(cfg(hidden, 16))                   # dense: unaffected
+        NativeTarget.check_config(cfg(hidden, 16, num_experts=0))
+    hf = types.SimpleNamespace(config=cfg(5120, 40, **moe))
+    with pytest.raises(NotImplementedError, match="4096"):
+        NativeTarget(hf)        # never reaches the wrapped model's weights or the device

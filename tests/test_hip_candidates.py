@@ -279,9 +279,28 @@ def test_native_candidate_pass_on_moe_target_equals_single_verifies(shared_pass,
     kernel on the same fragments as the single verify, so no near-tie can flip.  True (the default from three tiles on):
     the 48 rows go through ONE pass over the experts (the prefill's grouped kernels); the router logits then come from the
     batch GEMM (another fp32 summation order), a near-tie at the k-th place may flip for a row, and the max bar is wider."""
+    _candidate_pass_vs_single_verifies(_moe_target(), shared_pass, C, taps=[0, 2], kv_layer=3)
+
+
+def _wide_moe_target():
+    """Two layers of Qwen3-235B-A22B's hidden width (4096; 8 q / 2 kv heads, 16 experts of 256, top-4): past 2048 the
+    experts' gate/up goes through dfl_gemm_silu_mul_experts (tests/test_hip_moe_wide.py)."""
+    import test_hip_moe as TM
+    return TM._moe_hf(hidden=4096, heads=8, kv=2, layers=2, seed=TM.WIDE_SEED)
+
+
+@pytest.mark.parametrize("C", [1, 3])
+@pytest.mark.parametrize("shared_pass", [False, True])
+def test_native_candidate_pass_on_wide_moe_target_equals_single_verifies(shared_pass, C):
+    """The same at hidden 4096: the per-tile branch with the general gate/up launch (C = 1, and C = 3 with the shared
+    pass off) and the shared pass with the grouped kernels at K = 4096 and N = 4096 and the batch router GEMM at
+    K = 4096, against single verifies at the bars of the narrow target."""
+    _candidate_pass_vs_single_verifies(_wide_moe_target(), shared_pass, C, taps=[0], kv_layer=1)
+
+
+def _candidate_pass_vs_single_verifies(hf, shared_pass, C, taps, kv_layer):
     from dflash_amd import NativeTarget
     from dflash_amd.candidates import NativeCandidateVerifier
-    hf = _moe_target()
     nt = NativeTarget(hf)
     nt.moe_shared_pass = shared_pass
     g = torch.Generator().manual_seed(16)
@@ -291,7 +310,6 @@ def test_native_candidate_pass_on_moe_target_equals_single_verifies(shared_pass,
     cands[:, 0] = cands[0, 0].clone()
     cache = nt.new_cache(160)
     nt.prefill(prompt, cache)
-    taps = [0, 2]
     ver = NativeCandidateVerifier(nt, len(taps))
     ver.part_h.fill_(float("nan"))      # stale shares must never be read
     post = ver.verify(cands, P, cache, taps).clone()
@@ -304,7 +322,7 @@ def test_native_candidate_pass_on_moe_target_equals_single_verifies(shared_pass,
         _, th = nt.verify(cands[c], P, c2, tap_layers=taps, logits_out=logits)
         H.assert_ids_match_where_safe(f"MoE candidate {c} posterior", post[c], logits[:bs].float())
         H.assert_close(f"MoE candidate {c} taps", ver.taps[c], th[:16], max_rel=6e-2 if shared_pass else H.MAX_REL)
-        H.assert_close(f"MoE candidate {c} staged K l3", ver.stage_k[3, c, :, :bs], c2.k[3][:, P:P + bs],
+        H.assert_close(f"MoE candidate {c} staged K l{kv_layer}", ver.stage_k[kv_layer, c, :, :bs], c2.k[kv_layer][:, P:P + bs],
                        max_rel=6e-2 if shared_pass else H.KV_MAX_REL)
 
 

@@ -217,9 +217,9 @@ def _normed(K, seed, nss=None):
     return h, _partials(h, nss or K // 16), nw, xn
 
 
-def _source(ops, kind, K, vw, nv, seed):
+def _source(ops, kind, K, vw, nv, seed, nss=None):
     """(row source, the rows the GEMM must see as fp32 [16, K]).  Rows >= nv of a plain or normalised source hold
-    nonzero data that the kernel must treat as zero."""
+    nonzero data that the kernel must treat as zero.  nss: partial sums of squares of a normalised source (K / 16)."""
     if kind == "frag":
         x = _small_ints((16, K), _cuda_gen(seed))
         return ops.rows_frag(_frag(x)), x.float()
@@ -227,8 +227,8 @@ def _source(ops, kind, K, vw, nv, seed):
         x = _small_ints((16, K), _cuda_gen(seed))
         src, xs = ops.rows_plain(x, vw), x.float()
     else:
-        h, ss, nw, xs = _normed(K, seed)
-        src, xs = ops.rows_normed(h, ss, K // 16, nw, 0.0, vw), xs.float()
+        h, ss, nw, xs = _normed(K, seed, nss)
+        src, xs = ops.rows_normed(h, ss, nss or K // 16, nw, 0.0, vw), xs.float()
     xs = xs.clone()
     xs[nv:] = 0
     return src, xs
