@@ -31,7 +31,7 @@ class RowsBatch(C.Structure):
 
 _rb = C.POINTER(RowsBatch)
 
-W_BF16, W_E4M3, W_BF16X13 = 0, 1, 2   # DFL_W_BF16, DFL_W_E4M3, DFL_W_BF16X13
+W_BF16, W_E4M3, W_BF16X13, W_MXFP4 = 0, 1, 2, 3   # DFL_W_BF16, DFL_W_E4M3, DFL_W_BF16X13, DFL_W_MXFP4
 
 
 class Weight(C.Structure):

@@ -40,7 +40,8 @@ void dfl_set_error(const char *fmt, ...);
 // the two, a bf16 weight with a scale vector.  (e4m3 codes WITHOUT one are refused where each entry point checks its
 // pointers.)  After it, w->format == DFL_W_E4M3 selects the W8 instantiation.  DFL_W_BF16X13 is "neither of the two" here:
 // dfl_gemm_silu_mul, dfl_gemm_argmax and dfl_moe_gate_up, the three entry points that take it, look for it before they
-// call this.
+// call this.  DFL_W_MXFP4 likewise: dfl_gemm_resid, dfl_gemm_silu_mul and dfl_gemm_argmax look for it first, every other
+// entry point refuses it here.
 inline bool weight_ok(const char *who, const dfl_weight *w) {
   if (!w)
     dfl_set_error("%s: null weight descriptor", who);

@@ -75,6 +75,42 @@ __device__ __forceinline__ bf16x8 weight_frag(const bf16x8 (&wr)[NW], int f) {
     return wr[f];
 }
 
+// ---- W4: weights stored as OCP MXFP4 — e2m1 codes, one e8m0 scale per 32 consecutive k of a row (DFL_W_MXFP4) ----
+// Codes [N/16][K/128][64 lanes][16 B]: lane l (column l & 15, kq = l >> 4) holds in dword d of its 16-byte word the 8 codes
+// of k-step 4 j + d (k = 128 j + 32 d + 8 kq ..), low nibble first — so one 16-byte load per lane is still one contiguous
+// 1 KiB wave request and carries FOUR MFMA A-fragments, and one k-step fragment of one column is exactly one MX block.
+// Scales behind the codes: e8m0 bytes [N/16][K/128][16 columns][4 B], one dword per (column, 128-k group), byte d the scale
+// of k-step 4 j + d.
+// The W4 form of load_ksteps: the wave's NF k-steps (NF % 4 == 0) as NF/4 weight loads and NF/4 scale dwords, both through
+// descriptors that clip at the wave's share `nf` (k-steps, % 4 == 0): a clipped read is code 0 under scale code 0, i.e. +0.
+// The scale dwords are requested IN FRONT of the words they scale (a wave's loads return in order: the first conversion
+// then waits for one small request and one word).  The raw words stay in flight as they are — a quarter of the bf16
+// form's registers; w4_frag turns dword f & 3 into the fragment of k-step f right in front of its MFMA.
+template <int NF, int AUX = 2>
+__device__ __forceinline__ void load_ksteps_w4(bf16x8 (&wr)[NF / 4], uint32_t (&sc)[2], const bf16x8 *first,
+                                               const char *first_scale, int nf, int l, int half = -1) {
+  static_assert(NF % 4 == 0 && NF <= 8, "W4: a wave's share is a whole number of 4-k-step words (at most two)");
+  const int nw = nf < 0 ? 0 : nf >> 2;
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(first_scale), 0, nw * 64, 0x00020000);
+  const bool mine = half < 0 || ((l >> 3) & 1) == half;
+  const int voff4 = mine ? (l & 15) * 4 : 0x40000000;
+#pragma unroll
+  for (int q = 0; q < NF / 4; ++q) sc[q] = __builtin_amdgcn_raw_buffer_load_b32(rs, voff4 + q * 64, 0, AUX);
+  load_ksteps<NF / 4, AUX>(wr, first, nw, l, half);
+}
+
+// the 8 e2m1 codes in dword d (0..3) of one 16-byte word, times 2^(scale byte d - 127) -> bf16x8 (exact: the block scale
+// rides in the conversion, so the launch has no epilogue multiply)
+__device__ __forceinline__ bf16x8 w4_frag(bf16x8 raw, uint32_t scales, int d) {
+  const uint32_t q = __builtin_bit_cast(u32x4, raw)[d];
+  const float s = __builtin_bit_cast(float, ((scales >> (8 * d)) & 0xffu) << 23);
+  const bf16x2 a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, s, 0);
+  const bf16x2 b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, s, 1);
+  const bf16x2 c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, s, 2);
+  const bf16x2 e = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, s, 3);
+  return (bf16x8){a[0], a[1], b[0], b[1], c[0], c[1], e[0], e[1]};
+}
+
 // ---- W13: bf16 weights stored losslessly in 13 bits (DFL_W_BF16X13, dflash_hip.h) ----
 // A bf16 is L = bits[7:0] (e0, m6..m0) and H = bits[15:8] (s, e7..e1).  Per packed 16-column tile, hb = max(0, max(H & 0x7f)
 // - 15); a weight keeps L, its sign and a 4-bit code c: c = 0 <=> (H & 0x7f) == 0, c = 1..15 <=> (H & 0x7f) == hb + c.

@@ -21,6 +21,8 @@
 //     loops over K chunks itself so that the epilogue sees finished sums.
 //   * W8 (k_gemm_w8, the draft's optional fp8 weights): the same kernel over e4m3 codes, one byte per weight, two
 //     k-steps per 16-byte word, converted to bf16 in registers; one fp32 scale per output row on the fp32 sum.
+//   * W4 (k_gemm_w4, the draft's optional MXFP4 weights): the same kernel over e2m1 codes, four k-steps per 16-byte word,
+//     each dword converted to a bf16 fragment with its block's e8m0 scale applied in the conversion; no epilogue multiply.
 // MFMA utilisation is a few percent by construction; the roofline is HBM: every launch
 // costs ~3.6 us + bytes / 6.5 TB/s (scripts/bench_gemm.py).
 #include "gemm_rows.h"
@@ -229,14 +231,19 @@ constexpr int gemm_fr(int MT, bool CHUNKED) { return CHUNKED ? 4 : (MT == 1 ? 8 
 // process step is 8 MFMAs); the 13-bit form puts 8 x 19 VALU of decode per item into that window.  Unconditional, the
 // waits are vmcnt(15) .. (8): an item's decode starts as its own words land, with the whole next item still in flight.
 // Same requests in the same order, same fragments, same MFMAs, same finish(): the conditional loop's bits.
-template <int MT, bool CHUNKED, int EPI, bool NORM, bool W8 = false, bool W13 = false, bool UNC = false>
+// W4 (k_gemm_w4; DFL_W_MXFP4): the weights are e2m1 codes, FOUR k-steps per 16-byte word, with one e8m0 scale per k-step and
+// column (gemm_rows.h): a quarter as many loads per item, the item's scale dwords requested WITH its words (item 0's in the
+// prologue, never behind the K loop), each dword converted into its fragment — block scale included — in front of its
+// MFMA; no epilogue multiply.  A wave's share is whole words (nfr % 4 == 0).  Everything else is the bf16 form's.
+template <int MT, bool CHUNKED, int EPI, bool NORM, bool W8 = false, bool W13 = false, bool UNC = false, bool W4 = false>
 __device__ __forceinline__ void gemm_body(const GemmArgs &a, const SampleArgs &sa) {
   GSTAMP(0);
   static_assert(!W13 || (MT == 1 && !W8), "W13: the single-tile bf16 kernels only");
+  static_assert(!W4 || (MT == 1 && !W8 && !W13), "W4: the single-tile kernels only, one format per kernel");
   static_assert(!UNC || (W13 && !CHUNKED && EPI == EPI_SILU), "unconditional item requests: the W13 gate/up launch only");
   static_assert(!W13 || !CHUNKED || (EPI == EPI_RESID && !NORM), "W13, K-chunked: the residual launch only");
   constexpr int FR = gemm_fr(MT, CHUNKED);
-  constexpr int NW = W13 ? (CHUNKED ? 3 : 6) : (W8 ? FR / 2 : FR);  // 16-byte weight words per item and lane
+  constexpr int NW = W13 ? (CHUNKED ? 3 : 6) : (W8 ? FR / 2 : (W4 ? FR / 4 : FR));  // 16-byte weight words per item and lane
   // red[buf][wave][mt][256]: lane l owns floats 4l..4l+3 (its MFMA D regs)
   __shared__ float red[2][16][MT][256];
   __shared__ float ssred[NORM ? MT : 1][16][16];
@@ -272,7 +279,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &a, const SampleArgs &s
 
   bf16x8 wA[NW], wB[NW];
   float scA = 1.f, scB = 1.f;  // W8: the scale of this thread's column (tid & 15) of the item in wA / wB
-  W13Extra exA{}, exB{};       // W13: the item's sign words and its {base, patch} pair
+  W13Extra exA{}, exB{};       // W13: the item's sign words and its {base, patch} pair; W4: sg = the item's scale dwords
   bf16x8 xA[MT][FR], xB[MT][FR];
   bf16x8 xr[MT][FR];  // activations of the (single) chunk stay in registers for the launch
 
@@ -343,8 +350,17 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &a, const SampleArgs &s
       ex.meta = w13_meta(reinterpret_cast<const u32x2 *>(a.wscale), nf > 0 ? t : 0, w);  // (nothing fetched: any valid pair)
     }
   };
+  // W4: the wave's words ks0 / 4 .. of tile t and, WITH that request, their scale dwords (a.wscale = the scale region)
+  auto load_w4 = [&](bf16x8(&wr)[NW], W13Extra &ex, int t, int ks0, int nf, int half) {
+    if constexpr (W4) {
+      const size_t word = (size_t)t * (a.KS >> 2) + (ks0 >> 2);
+      load_ksteps_w4<FR>(wr, ex.sg, a.wp + word * 64, reinterpret_cast<const char *>(a.wscale) + word * 64, nf, l, half);
+    }
+  };
   auto load_item = [&](bf16x8(&wr)[NW], float &sc, W13Extra &ex, bf16x8(&xb)[MT][FR], int t, int c, int half) {
-    if constexpr (W13)
+    if constexpr (W4)
+      load_w4(wr, ex, t, ks0_of(c), nf_of(c), half);
+    else if constexpr (W13)
       load_w13(wr, ex, t, ks0_of(c), nf_of(c), half, c);
     else if constexpr (W8)
       load_w8(wr, sc, t, ks0_of(c), nf_of(c), half);
@@ -446,6 +462,8 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &a, const SampleArgs &s
           wf = w13_frag(wr, ex.sg[0], ex.meta, f, l);
         else if constexpr (W13)
           wf = w13_frag(wr, ex, f, l);
+        else if constexpr (W4)
+          wf = w4_frag(wr[f >> 2], ex.sg[f >> 2], f & 3);
         else
           wf = weight_frag<W8>(wr, f);
         acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, xv, acc[mt], 0, 0, 0);
@@ -538,7 +556,9 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &a, const SampleArgs &s
     // load_ksteps clips at the wave's share through the buffer descriptor instead (zero weights, no traffic), and
     // activations past the share are zero as well.  (The expert list of an MoE launch is a dependent scalar load: that
     // launch asks for its first weights once it knows the tile.)
-    if constexpr (W13)
+    if constexpr (W4)
+      load_w4(wA, exA, SILU ? 2 * (int)blockIdx.x : first_tile, ks0_of(0), first_live ? nf0 : 0, first_half);
+    else if constexpr (W13)
       load_w13(wA, exA, SILU ? 2 * (int)blockIdx.x : first_tile, ks0_of(0), first_live ? nf0 : 0, first_half);
     else if constexpr (W8)
       load_w8(wA, scA, SILU ? 2 * (int)blockIdx.x : first_tile, ks0_of(0), first_live ? nf0 : 0, first_half);
@@ -588,7 +608,9 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &a, const SampleArgs &s
     }
   } else {
     // chunked kernels build their activation fragments per item: item 0's behind the weights already requested
-    if constexpr (W8)
+    if constexpr (W4)
+      load_w4(wA, exA, first_tile, ks0_of(0), first_live ? nf0 : 0, first_half);
+    else if constexpr (W8)
       load_w8(wA, scA, first_tile, ks0_of(0), first_live ? nf0 : 0, first_half);
     else if constexpr (W13)
       load_w13(wA, exA, first_tile, ks0_of(0), first_live ? nf0 : 0, first_half, 0);
@@ -691,6 +713,12 @@ __global__ __launch_bounds__(1024) void k_gemm_w13c(GEMM_HEAD_PARAMS, GemmArgs r
   gemm_body<1, true, EPI, false, false, true>(with_head<true, false>(rest, GEMM_HEAD_NAMES), SampleArgs{});
 }
 
+// the W4 form (MXFP4 codes with their block scales, gemm_body): the draft's gate/up, lm_head and residual launches
+template <bool CHUNKED, int EPI, bool NORM>
+__global__ __launch_bounds__(1024) void k_gemm_w4(GEMM_HEAD_PARAMS, GemmArgs rest) {
+  gemm_body<1, CHUNKED, EPI, NORM, false, false, false, true>(with_head<CHUNKED, NORM>(rest, GEMM_HEAD_NAMES), SampleArgs{});
+}
+
 template <bool NORM>
 __global__ __launch_bounds__(1024) void k_gemm_s(GEMM_HEAD_PARAMS, GemmArgs rest, SampleArgs sa) {
   gemm_body<1, false, EPI_SAMPLE, NORM>(with_head<false, NORM>(rest, GEMM_HEAD_NAMES), sa);
@@ -760,6 +788,34 @@ bool launch_gemm_w13(const char *who, GemmArgs &a, const dfl_weight *w, int N, d
     hipLaunchKernelGGL((k_gemm_w13<EPI, true>), grid, dim3(1024), 0, stream, GEMM_HEAD_OF(h), a);
   else
     hipLaunchKernelGGL((k_gemm_w13<EPI, false>), grid, dim3(1024), 0, stream, GEMM_HEAD_OF(h), a);
+  return true;
+}
+
+// The W4 launch of dfl_gemm_resid / dfl_gemm_silu_mul / dfl_gemm_argmax (DFL_W_MXFP4, dflash_hip.h).  a.wp is the weight's
+// first byte and N its packed rows: the scale region starts N * K / 2 bytes in.  K % 128 == 0, and every wave's share is
+// whole 4-k-step words (the callers round nfr up, as the W8 form rounds to even).
+template <bool CHUNKED, int EPI>
+bool launch_gemm_w4(const char *who, GemmArgs &a, const dfl_weight *w, int N, dim3 grid, hipStream_t stream) {
+  if (w->scale) {
+    dfl_set_error("%s: a DFL_W_MXFP4 weight takes no scale vector (the block scales follow the codes)", who);
+    return false;
+  }
+  if (a.KS % 4 || a.nfr % 4 || a.nfr > 8) {
+    dfl_set_error("%s: DFL_W_MXFP4 needs K %% 128 == 0 and whole 4-k-step words per wave (K=%d, %d k-steps per wave)", who,
+                  a.KS * 32, a.nfr);
+    return false;
+  }
+  a.wscale = reinterpret_cast<const float *>(reinterpret_cast<const char *>(w->wp) + (int64_t)N * a.KS * 16);
+  a.gx = (int)grid.x;
+  GemmHead h;
+  if (!gemm_head<CHUNKED>(h, a)) return false;
+  if constexpr (!CHUNKED) {
+    if (a.src[0].mode == 2) {
+      hipLaunchKernelGGL((k_gemm_w4<false, EPI, true>), grid, dim3(1024), 0, stream, GEMM_HEAD_OF(h), a);
+      return true;
+    }
+  }
+  hipLaunchKernelGGL((k_gemm_w4<CHUNKED, EPI, false>), grid, dim3(1024), 0, stream, GEMM_HEAD_OF(h), a);
   return true;
 }
 
@@ -980,11 +1036,12 @@ extern "C" int dfl_gemm_f32(const void *wp, const dfl_rows *x0, const dfl_rows *
 // with one fp32 scale per packed row (w->scale), K % 64 == 0, and every wave's share (nfr) is rounded up to whole k-step
 // pairs.
 namespace {
-template <bool W8, bool W13 = false>
+template <bool W8, bool W13 = false, bool W4 = false>
 int gemm_silu_mul_impl(const char *who, const dfl_weight *w, const dfl_rows *x, int I, int K, void *act_frag,
                        const int32_t *dyn, void *stream) {
   DFL_REQUIRE(w->wp && act_frag && (!W8 || w->scale), "%s: null pointer", who);
-  DFL_REQUIRE(I > 0 && K > 0 && I % 16 == 0 && K % (W8 ? 64 : 32) == 0, "%s: need I%%16==0, K%%%d==0", who, W8 ? 64 : 32);
+  DFL_REQUIRE(I > 0 && K > 0 && I % 16 == 0 && K % (W4 ? 128 : W8 ? 64 : 32) == 0, "%s: need I%%16==0, K%%%d==0", who,
+              W4 ? 128 : W8 ? 64 : 32);
   const int KS = K / 32;
   DFL_REQUIRE(KS <= 16 * 8, "%s: K=%d needs a K split, which the fused activation cannot take", who, K);
   GemmArgs a{};
@@ -996,9 +1053,12 @@ int gemm_silu_mul_impl(const char *who, const dfl_weight *w, const dfl_rows *x, 
   a.ntiles = 2 * (I / 16);
   a.nfr = (KS + 15) / 16;
   if (W8) a.nfr += a.nfr & 1;
+  if (W4) a.nfr = (a.nfr + 3) & ~3;
   a.nch = 1;
   a.act = (bf16_t *)act_frag;
-  if constexpr (W13) {
+  if constexpr (W4) {
+    if (!launch_gemm_w4<false, EPI_SILU>(who, a, w, 2 * I, dim3(grid_x_for(I / 16), 1), (hipStream_t)stream)) return DFL_EINVAL;
+  } else if constexpr (W13) {
     if (!launch_gemm_w13<EPI_SILU>(who, a, w, 2 * I, dim3(grid_x_for(I / 16), 1), (hipStream_t)stream)) return DFL_EINVAL;
   } else if (!launch_gemm<1, false, EPI_SILU, W8>(a, dim3(grid_x_for(I / 16), 1), (hipStream_t)stream)) {
     return DFL_EINVAL;
@@ -1013,6 +1073,8 @@ extern "C" int dfl_gemm_silu_mul(const dfl_weight *w_gateup, const dfl_rows *x, 
   const char *who = "dfl_gemm_silu_mul";
   if (w_gateup && w_gateup->format == DFL_W_BF16X13)  // (weight_ok knows the two formats every entry point takes)
     return gemm_silu_mul_impl<false, true>(who, w_gateup, x, I, K, act_frag, dyn, stream);
+  if (w_gateup && w_gateup->format == DFL_W_MXFP4)
+    return gemm_silu_mul_impl<false, false, true>(who, w_gateup, x, I, K, act_frag, dyn, stream);
   if (!weight_ok(who, w_gateup)) return DFL_EINVAL;
   return w_gateup->format == DFL_W_BF16 ? gemm_silu_mul_impl<false>(who, w_gateup, x, I, K, act_frag, dyn, stream)
                                         : gemm_silu_mul_impl<true>(who, w_gateup, x, I, K, act_frag, dyn, stream);
@@ -1059,10 +1121,10 @@ namespace {
 int gemm_argmax_impl(const char *who, const dfl_weight *w, const dfl_rows *x, int V, int K, int row0, int nrows,
                      const int32_t *dyn, int nrows_dyn_word, void *ws, int64_t *out_ids, int out_off, void *logits,
                      float *margin_out, hipEvent_t ev0, hipEvent_t ev1, void *stream, const SampleArgs *smp = nullptr) {
-  const bool w8 = w->format == DFL_W_E4M3, w13 = w->format == DFL_W_BF16X13;
+  const bool w8 = w->format == DFL_W_E4M3, w13 = w->format == DFL_W_BF16X13, w4 = w->format == DFL_W_MXFP4;
   DFL_REQUIRE(w->wp && ws && out_ids && (!w8 || w->scale), "%s: null pointer", who);
-  DFL_REQUIRE(V > 0 && K > 0 && V % 16 == 0 && K % (w8 ? 64 : 32) == 0, "%s: need V%%16==0, K%%%d==0 (V=%d K=%d)", who,
-              w8 ? 64 : 32, V, K);
+  DFL_REQUIRE(V > 0 && K > 0 && V % 16 == 0 && K % (w4 ? 128 : w8 ? 64 : 32) == 0, "%s: need V%%16==0, K%%%d==0 (V=%d K=%d)", who,
+              w4 ? 128 : w8 ? 64 : 32, V, K);
   DFL_REQUIRE(row0 >= 0 && nrows >= 0 && row0 + nrows <= 16, "%s: rows [%d,%d) outside the 16-row tile", who, row0,
               row0 + nrows);
   const int KS = K / 32;
@@ -1075,6 +1137,7 @@ int gemm_argmax_impl(const char *who, const dfl_weight *w, const dfl_rows *x, in
   a.ntiles = V / 16;
   a.nfr = (KS + 15) / 16;
   if (w8) a.nfr += a.nfr & 1;
+  if (w4) a.nfr = (a.nfr + 3) & ~3;
   a.wscale = w->scale;
   a.nch = 1;
   a.row0 = row0;
@@ -1103,6 +1166,8 @@ int gemm_argmax_impl(const char *who, const dfl_weight *w, const dfl_rows *x, in
       hipLaunchKernelGGL(k_gemm_s<false>, dim3(gx, 1), dim3(1024), 0, (hipStream_t)stream, GEMM_HEAD_OF(h), a, *smp);
   } else if (w13) {
     if (!launch_gemm_w13<EPI_ARGMAX>(who, a, w, V, dim3(gx, 1), (hipStream_t)stream)) return DFL_EINVAL;
+  } else if (w4) {
+    if (!launch_gemm_w4<false, EPI_ARGMAX>(who, a, w, V, dim3(gx, 1), (hipStream_t)stream)) return DFL_EINVAL;
   } else if (w8) {
     if (!launch_gemm<1, false, EPI_ARGMAX, true>(a, dim3(gx, 1), (hipStream_t)stream)) return DFL_EINVAL;
   } else {
@@ -1120,7 +1185,7 @@ extern "C" int dfl_gemm_argmax(const dfl_weight *w, const dfl_rows *x, int V, in
                                const int32_t *dyn, int nrows_dyn_word, void *ws, int64_t *out_ids, int out_off,
                                void *logits, float *margin_out, void *ev_start, void *ev_end, void *stream) {
   const char *who = "dfl_gemm_argmax";
-  if (!(w && w->format == DFL_W_BF16X13) && !weight_ok(who, w)) return DFL_EINVAL;
+  if (!(w && (w->format == DFL_W_BF16X13 || w->format == DFL_W_MXFP4)) && !weight_ok(who, w)) return DFL_EINVAL;
   return gemm_argmax_impl(who, w, x, V, K, row0, nrows, dyn, nrows_dyn_word, ws, out_ids, out_off, logits, margin_out,
                           (hipEvent_t)ev_start, (hipEvent_t)ev_end, stream);
 }
@@ -1143,12 +1208,12 @@ extern "C" int dfl_gemm_sample(const dfl_weight *w, const dfl_rows *x, int V, in
 
 
 namespace {
-template <bool W8, bool W13 = false>
+template <bool W8, bool W13 = false, bool W4 = false>
 int gemm_resid_impl(const char *who, const dfl_weight *w, const dfl_rows *x, int N, int K, void *h_io, int64_t ldh,
                     int add_residual, void *tap, int64_t ldtap, float *ss_out, const int32_t *dyn, void *stream) {
   DFL_REQUIRE(w->wp && h_io && (!W8 || w->scale), "%s: null pointer", who);
-  DFL_REQUIRE(N > 0 && K > 0 && N % 16 == 0 && K % (W8 ? 64 : 32) == 0, "%s: need N%%16==0, K%%%d==0 (N=%d K=%d)", who,
-              W8 ? 64 : 32, N, K);
+  DFL_REQUIRE(N > 0 && K > 0 && N % 16 == 0 && K % (W4 ? 128 : W8 ? 64 : 32) == 0, "%s: need N%%16==0, K%%%d==0 (N=%d K=%d)", who,
+              W4 ? 128 : W8 ? 64 : 32, N, K);
   DFL_REQUIRE(ldh >= N && (!tap || ldtap >= N), "%s: row strides shorter than N", who);
   const int KS = K / 32;
   GemmArgs a{};
@@ -1171,13 +1236,20 @@ int gemm_resid_impl(const char *who, const dfl_weight *w, const dfl_rows *x, int
   if (KS <= 16 * 8) {  // the whole K fits the 16 waves x 8 steps of one pass
     a.nfr = (KS + 15) / 16;
     if (W8) a.nfr += a.nfr & 1;
+    if (W4) a.nfr = (a.nfr + 3) & ~3;
     a.nch = 1;
-    if (!launch_gemm<1, false, EPI_RESID, W8>(a, grid, (hipStream_t)stream)) return DFL_EINVAL;
+    if constexpr (W4) {
+      if (!launch_gemm_w4<false, EPI_RESID>(who, a, w, N, grid, (hipStream_t)stream)) return DFL_EINVAL;
+    } else if (!launch_gemm<1, false, EPI_RESID, W8>(a, grid, (hipStream_t)stream)) {
+      return DFL_EINVAL;
+    }
   } else {  // walk K in chunks of 16 waves x 4 steps inside the workgroup
     DFL_REQUIRE(a.src[0].mode != 2, "%s: a normalised source needs K <= 4096", who);
     a.nfr = 4;
     a.nch = (KS + 63) / 64;  // 64 k-steps per chunk: 16 waves x 4
-    if constexpr (W13) {  // (dfl_gemm_resid: K is a whole number of chunks, no scale; whole tiles only — KS > 128 above)
+    if constexpr (W4) {
+      if (!launch_gemm_w4<true, EPI_RESID>(who, a, w, N, grid, (hipStream_t)stream)) return DFL_EINVAL;
+    } else if constexpr (W13) {  // (dfl_gemm_resid: K is a whole number of chunks, no scale; whole tiles only — KS > 128 above)
       a.wscale = reinterpret_cast<const float *>(reinterpret_cast<const char *>(w->wp) + w13_quads_bytes(N, K));
       a.gx = (int)grid.x;
       GemmHead h;
@@ -1201,6 +1273,8 @@ extern "C" int dfl_gemm_resid(const dfl_weight *w, const dfl_rows *x, int N, int
     DFL_REQUIRE(!w->scale, "%s: a DFL_W_BF16X13 weight takes no scale vector (the bases and patch words follow the codes)", who);
     return gemm_resid_impl<false, true>(who, w, x, N, K, h_io, ldh, add_residual, tap, ldtap, ss_out, dyn, stream);
   }
+  if (w && w->format == DFL_W_MXFP4)
+    return gemm_resid_impl<false, false, true>(who, w, x, N, K, h_io, ldh, add_residual, tap, ldtap, ss_out, dyn, stream);
   if (!weight_ok(who, w)) return DFL_EINVAL;
   return w->format == DFL_W_BF16
              ? gemm_resid_impl<false>(who, w, x, N, K, h_io, ldh, add_residual, tap, ldtap, ss_out, dyn, stream)

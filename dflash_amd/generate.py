@@ -308,6 +308,8 @@ class DecodeSession:
             self.lm_wp8 = getattr(target, "lm_wp8", None) if self.native else None
             if self.lm_wp8 is None:
                 self.lm_wp8 = model.packed_lm_head_fp8(target.lm_head)
+        elif self.use_draft and getattr(model, "w4", None) is not None:   # an mxfp4 draft: its own 4-bit copy of the head
+            self.lm_wp8 = model.packed_lm_head_mxfp4(target.lm_head)
         self.stop_t = torch.tensor(stop_token_ids, dtype=torch.long, device=dev) if stop_token_ids else None
         # the logit-bias state: the dense table row and min_pos = n_in + min_tokens (written once: a session is one
         # request), the stop ids the accept launch takes, and the buffer the verify writes its biased rows into
@@ -443,7 +445,10 @@ class DecodeSession:
             self.events.setdefault(key, [None, None])[which] = e
 
     def _lm8(self):
-        """The e4m3 lm_head for the draft's greedy unmask, or None (a bf16 model, or fp8_stream switched off)."""
+        """The e4m3 (an mxfp4 draft: the 4-bit) lm_head for the draft's greedy unmask, or None (a bf16 model, or fp8_stream /
+        mxfp4_stream switched off)."""
+        if isinstance(self.lm_wp8, ops.Mxfp4Weight):
+            return self.lm_wp8 if self.model.mxfp4_stream else None
         return self.lm_wp8 if self.model.fp8_stream else None
 
     def _constrain_draft(self, bs) -> None:
@@ -1002,6 +1007,7 @@ def _draft_ids(model, hid_frag, lm_wp, bs, blk, draft_temperature, keep_logits=N
     if draft_temperature < 1e-5:
         from .model import WideRows
         wide = isinstance(hid_frag, WideRows)   # (both tiles in one ragged-batch lm_head pass)
+        # (an mxfp4 draft's 4-bit head: the single 16-row tile only — streams_fp8_tiles() is False for it)
         wp = lm_wp8 if lm_wp8 is not None and (model.streams_fp8_tiles() if wide else bs <= 16) else lm_wp
         model.draft_tokens(hid_frag, wp, bs, blk[0], logits=keep_logits)
         return

@@ -73,7 +73,8 @@ class WideRows:
         return self.tiles
 
 
-WEIGHT_FORMATS = ("bf16", "fp8_e4m3")
+WEIGHT_FORMATS = ("bf16", "fp8_e4m3", "mxfp4")
+TARGET_WEIGHT_FORMATS = ("bf16", "fp8_e4m3")   # NativeTarget: the 4-bit format is the draft's alone (it only proposes)
 
 
 class DFlashDraftModel:
@@ -88,7 +89,14 @@ class DFlashDraftModel:
         codes, which the draft forward streams at one byte per weight: a single request's block, the ragged batch and
         the engine.  The draft's format never touches the target, so committed tokens stay the target's
         own (a target may be quantised on its own: NativeTarget(weight_format=...)); what the quantisation does to the
-        acceptance length of a trained checkpoint is NOT measured — hence off by default."""
+        acceptance length of a trained checkpoint is NOT measured — hence off by default.
+        "mxfp4": every Linear weight of the draft is quantised at load time to OCP MXFP4 — e2m1 codes with one e8m0 scale
+        per 32 consecutive k of a row (ops.quantize_mxfp4_rows).  ONE quantised model again:
+        `self.w` holds the dequantised values (exact in bf16), `self.w4` the packed 4-bit twins, which a single
+        request's block of <= 16 rows streams at 4.25 bits per weight (streams_mxfp4); a sampled draft's lm_head, the
+        ragged batch and the engine, wider blocks, prefill and attn_impl="fused" compute the same model from self.w.  stream_format is ignored (the 13-bit twins are for bf16 weights).  The draft only proposes: committed
+        tokens stay the target's own, but the effect of a 4-bit draft on the acceptance length of a trained checkpoint is
+        NOT measured — hence off by default."""
         if weight_format not in WEIGHT_FORMATS:
             raise ValueError(f"weight_format must be one of {WEIGHT_FORMATS}, got {weight_format!r}")
         self.weight_format = weight_format
@@ -111,6 +119,8 @@ class DFlashDraftModel:
         self.dtype = BF16
         if weight_format == "fp8_e4m3" and any(k % 64 for k in (c.hidden_size, c.intermediate_size, c.fc_in, c.q_dim)):
             raise NotImplementedError("fp8_e4m3 weights need hidden, intermediate, fc input and q widths % 64 == 0")
+        if weight_format == "mxfp4" and any(k % 128 for k in (c.hidden_size, c.intermediate_size, c.fc_in, c.q_dim)):
+            raise NotImplementedError("mxfp4 weights need hidden, intermediate, fc input and q widths % 128 == 0")
         self.w: Optional[dict] = None
         self.gu13: list = []             # stream_format="auto": per layer, the 13-bit twin of w["layers"][i]["gu"] or None
         self.down13: list = []           # ... and of w["layers"][i]["down"]
@@ -118,10 +128,13 @@ class DFlashDraftModel:
         self.w8: Optional[dict] = None   # fp8_e4m3: ops.Fp8Weight twins of the matrices in self.w (same keys)
         # fp8_e4m3 only: False = run everything on the dequantised bf16 copy (the second implementation the tests compare)
         self.fp8_stream = True
+        self.w4: Optional[dict] = None   # mxfp4: ops.Mxfp4Weight twins of the matrices in self.w (same keys)
+        self.mxfp4_stream = True         # mxfp4 only: False = everything on the dequantised bf16 copy (second implementation)
         self._ws = None
         self.rows: Optional[RowStack] = None   # the block's layer stack on the single-request kernels (made with _ws)
         self._lm_head_cache = {}
         self._lm_head_cache8 = {}
+        self._lm_head_cache4 = {}
         self._tile_layers = {}   # tile_layers(): qkv_parts -> layer dicts with the e4m3 twins
         self._row_layers = {}    # row_layers(): streams e4m3 -> layer dicts with the e4m3 / 13-bit twins
         self._rope = None
@@ -160,12 +173,16 @@ class DFlashDraftModel:
 
         fp8 = self.weight_format == "fp8_e4m3"
         w8 = {"layers": []} if fp8 else None
+        mx4 = self.weight_format == "mxfp4"
+        w4 = {"layers": []} if mx4 else None
 
         def mat(name, store, key):
             """A Linear weight on the device: as loaded, or (fp8) its dequantised values, the codes packed into `store`."""
             m = dev(name)
             if fp8:
                 m, store[key] = ops.quantize_keep_fp8(m)
+            elif mx4:
+                m, store[key] = ops.quantize_keep_mxfp4(m)
             return m
 
         top8 = {}
@@ -173,6 +190,9 @@ class DFlashDraftModel:
              "norm": dev("norm.weight"), "layers": []}
         if fp8:
             w8["fc"] = ops.pack_weight_fp8(*top8.pop("fc"))
+        elif mx4:
+            w4["fc"] = ops.pack_weight_mxfp4(*top8.pop("fc"))
+        kv4 = []   # mxfp4: the layers' k and v codes and scale codes, for the context K/V matrix of all layers
         gu13, down13 = [], []
         for i in range(c.num_hidden_layers):
             p = f"layers.{i}."
@@ -183,6 +203,9 @@ class DFlashDraftModel:
             o, down = mat(p + "self_attn.o_proj.weight", l8, "o"), mat(p + "mlp.down_proj.weight", l8, "down")
             if fp8:
                 w8["layers"].append(ops.pack_layer_fp8(l8))
+            elif mx4:
+                w4["layers"].append(ops.pack_layer_mxfp4(l8))
+                kv4 += [l8["k"], l8["v"]]
             del l8
             w["layers"].append({
                 "qkv": ops.pack_weight(qkv),
@@ -209,9 +232,13 @@ class DFlashDraftModel:
                 torch.cat([l8["qkv"].wp[c.q_dim * c.hidden_size:] for l8 in w8["layers"]]).contiguous(),
                 torch.cat([l8["qkv"].scale[c.q_dim:] for l8 in w8["layers"]]).contiguous(),
                 c.num_hidden_layers * nkv2, c.hidden_size)
+        if mx4:   # packed on its own: rows in w["kv_all"]'s order (the scale region of a packed qkv is no plain slice)
+            w4["kv_all"] = ops.pack_weight_mxfp4(torch.cat([q[0] for q in kv4]), torch.cat([q[1] for q in kv4]))
+        del kv4
         torch.cuda.synchronize(self.device)
         self.w = w
         self.w8 = w8
+        self.w4 = w4
         self.gu13, self.down13 = gu13, down13
         # fc's 13-bit twin for the <= 16-row block (draft_block), or None where plain bf16 stays
         self.fc13 = ops.bf16x13_twin(w["fc"], c.hidden_size, c.fc_in, "fc") if self.x13 else None
@@ -306,6 +333,24 @@ class DFlashDraftModel:
             self._lm_head_cache8[key] = ops.pack_weight_fp8(q, sc)
         return self._lm_head_cache8[key]
 
+    def packed_lm_head_mxfp4(self, lm_head) -> ops.Mxfp4Weight:
+        """The target's lm_head weight quantised to MXFP4 and packed for streaming (the DRAFT's greedy unmask of <= 16
+        rows only: the target keeps its bf16 copy); cached per weight tensor as packed_lm_head."""
+        wt = lm_head.weight if hasattr(lm_head, "weight") else lm_head
+        key = (wt.data_ptr(), tuple(wt.shape), wt._version)
+        if key not in self._lm_head_cache4:
+            self._lm_head_cache4.clear()
+            q = ops.quantize_mxfp4_rows(wt.detach().to(device=self.device, dtype=BF16).contiguous())
+            self._lm_head_cache4[key] = ops.pack_weight_mxfp4(*q)
+        return self._lm_head_cache4[key]
+
+    def streams_mxfp4(self, bs: int) -> bool:
+        """Whether draft_block streams the 4-bit twins for a block of `bs` rows: an mxfp4 model, one 16-row tile, the head
+        attention stage, o_proj not fused, no wide hidden (the conditions of streams_fp8).  Every other path computes
+        the same quantised model from self.w."""
+        return (getattr(self, "w4", None) is not None and self.mxfp4_stream and bs <= 16 and self.attn_impl == "head"
+                and not self.fuse_oproj and not self.wide_hidden)
+
     def streams_fp8(self, bs: int) -> bool:
         """Whether draft_block streams the e4m3 codes for a block of `bs` rows: an fp8 model, one 16-row tile, the head
         attention stage, o_proj not fused.  Every other path computes the same quantised model from self.w."""
@@ -328,10 +373,11 @@ class DFlashDraftModel:
 
     def row_layers(self, bs: int) -> list:
         """The layer dicts RowStack.run takes for a block of `bs` rows: self.w's, with the four matrices replaced by
-        their e4m3 twins when streams_fp8(bs), else gate/up and down by their 13-bit twins where the layer has them
-        (gu13, down13)."""
-        fp8 = self.streams_fp8(bs)
-        return ops.row_layers(self.w["layers"], self.w8["layers"] if fp8 else None, self.gu13, fp8, self._row_layers,
+        their e4m3 twins when streams_fp8(bs) or their 4-bit twins when streams_mxfp4(bs) (a model has one of the two at
+        most), else gate/up and down by their 13-bit twins where the layer has them (gu13, down13)."""
+        fp8, mx4 = self.streams_fp8(bs), self.streams_mxfp4(bs)
+        twins = self.w8["layers"] if fp8 else self.w4["layers"] if mx4 else None
+        return ops.row_layers(self.w["layers"], twins, self.gu13, fp8 or mx4, self._row_layers,
                               getattr(self, "down13", None))
 
     # ------------------------------------------------------------------ kernels
@@ -489,7 +535,8 @@ class DFlashDraftModel:
             ops.set_dyn2(cache.dyn, S, tau, bs, pos0)
         dyn = cache.dyn[:8]
         tiles = [(t, cache.dyn[8 * t:8 * t + 8]) for t in range((bs + 15) // 16)]
-        top = self.w8 if self.streams_fp8(bs) else w   # fc and kv_all, the matrices outside the layers: as row_layers(bs)
+        # fc and kv_all, the matrices outside the layers: as row_layers(bs)
+        top = self.w8 if self.streams_fp8(bs) else self.w4 if self.streams_mxfp4(bs) else w
         if tau > 0:
             # fc straight off the tap rows; hidden_norm is applied by each layer's qkv GEMM (:177)
             fc = top["fc"]
@@ -566,7 +613,8 @@ class DFlashDraftModel:
                      sample: Optional[dict] = None) -> None:
         """block_ids[1:bs] <- argmax(lm_head(hidden[1:bs])) (model/dflash.py:238,245,247).
         hid_frag: what draft_block returned (one row source per 16-row tile; a single source = one tile).
-        lm_head_wp: the packed bf16 lm_head, or (greedy only: sample is None) an ops.Fp8Weight of it.  A bf16 head's
+        lm_head_wp: the packed bf16 lm_head, or (greedy only: sample is None) an ops.Fp8Weight of it or (greedy, <= 16
+        rows) an ops.Mxfp4Weight.  A bf16 head's
         single-tile argmax launch streams its 13-bit twin where stream_format="auto" has one (shared with the target).
         logits (bf16 [16 * tiles, V]) / margins (fp32 [>= bs]): margins[j] <- top-1 minus top-2 draft
         logit of block slot j >= 1, the reference's per-position confidence

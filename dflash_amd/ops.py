@@ -10,7 +10,7 @@ from typing import NamedTuple, Optional
 
 import torch
 
-from ._lib import W_BF16, W_BF16X13, W_E4M3, Rows, Weight, check, lib
+from ._lib import W_BF16, W_BF16X13, W_E4M3, W_MXFP4, Rows, Weight, check, lib
 
 BF16, F32, I32, I64 = torch.bfloat16, torch.float32, torch.int32, torch.int64
 DYN_S, DYN_TAU, DYN_BS, DYN_POS0, DYN_START, DYN_STOP, DYN_CYCLE = range(7)
@@ -192,7 +192,7 @@ def tile_layers(layers: list, layers8: list, qkv_parts: bool, cache: dict) -> li
 
 def row_layers(layers: list, layers8, gu13: list, fp8: bool, cache: dict, down13=None) -> list:
     """The layer dicts RowStack.run takes — the one format choice of the single-request path.  fp8: `layers` with qkv / o /
-    gu / down replaced by their e4m3 twins in layers8; else with gu / down replaced by their 13-bit twins where gu13[i] /
+    gu / down replaced by their quantised twins in layers8 (an fp8 model's e4m3 codes, an mxfp4 model's 4-bit ones); else with gu / down replaced by their 13-bit twins where gu13[i] /
     down13[i] is not None (a layer with neither, an MoE layer among them, passes through as it is).  Built once per form
     and kept in `cache`."""
     if fp8 not in cache:
@@ -321,6 +321,103 @@ def bf16x13_report() -> dict:
             "patched_items": sum(v[4]["patched"] for v in live), "refused_items": sum(v[4]["refused"] for v in live)}
 
 
+# ---- mxfp4: OCP Microscaling e2m1 codes with one e8m0 scale per 32 consecutive k of a row ----
+E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)   # magnitudes of codes 0..7; bit 3 of a code is the sign
+MX_BLOCK = 32
+MX_EXP_MIN, MX_EXP_MAX = -120, 120     # scale codes 7..247 (code = exponent + 127)
+
+
+class Mxfp4Weight(NamedTuple):
+    """A packed MXFP4 weight (pack_weight_mxfp4 / pack_weight_gateup_mxfp4): gemm_resid / gemm_silu_mul / gemm_argmax
+    take one in place of a packed bf16 weight (K % 128 == 0)."""
+    data: torch.Tensor    # uint8: codes [N/16][K/128][64 lanes][16 B], then e8m0 scales [N/16][K/128][16 columns][4 B]
+    N: int
+    K: int
+
+
+def quantize_mxfp4_rows(w: torch.Tensor):
+    """[N, K] weight (K % 32 == 0) -> (codes uint8 [N, K/2], scale_codes uint8 [N, K/32]).  Per block of 32 consecutive k
+    of a row: scale = 2^e, e = ceil(log2(amax / 6)) clamped to [-120, 120] (0 for an all-zero block), scale code e + 127;
+    q = round-to-nearest-even of w / scale onto the e2m1 grid {0, .5, 1, 1.5, 2, 3, 4, 6} with sign (a value that rounds to
+    zero is stored as +0).  The ceil rule keeps amax / scale <= 6: nothing is clamped at +-6 except by the exponent clamp.
+    Element 2 i of a row is the LOW nibble of byte i.  Thresholds, no cast to a torch fp4 type; runs on w's device."""
+    if w.dim() != 2 or w.shape[1] % MX_BLOCK:
+        raise ValueError(f"dflash_amd: quantize_mxfp4_rows takes [N, K] with K % {MX_BLOCK} == 0, got {tuple(w.shape)}")
+    wf = w.detach().float()
+    if not bool(torch.isfinite(wf).all()):
+        raise ValueError("dflash_amd: quantize_mxfp4_rows: the weight holds a non-finite value")
+    n, k = wf.shape
+    blk = wf.view(n, k // MX_BLOCK, MX_BLOCK)
+    amax = blk.abs().amax(dim=2)
+    # amax = m * 2^ea with m in [0.5, 1): 6 * 2^e >= amax  <=>  2^(e - ea) >= m / 6, and m / 6 <= 1/8 exactly when m <= 0.75
+    m, ea = torch.frexp(amax)
+    e = torch.where(m <= 0.75, ea - 3, ea - 2)
+    e = torch.where(amax == 0, torch.zeros_like(e), e).clamp_(MX_EXP_MIN, MX_EXP_MAX)
+    a = torch.ldexp(blk.abs(), -e.unsqueeze(2))        # |w| / scale, exact (a power of two)
+    # round to nearest, ties to the even code: midpoints .25 .75 1.25 1.75 2.5 3.5 5 between codes 0..7
+    mag = ((a > 0.25).to(U8) + (a >= 0.75).to(U8) + (a > 1.25).to(U8) + (a >= 1.75).to(U8) + (a > 2.5).to(U8)
+           + (a >= 3.5).to(U8) + (a > 5.0).to(U8))
+    code = torch.where((blk < 0) & (mag != 0), mag | 8, mag).view(n, k // 2, 2)
+    codes = (code[..., 0] | (code[..., 1] << 4)).contiguous()
+    return codes, (e + 127).to(U8).contiguous()
+
+
+def dequantize_mxfp4_rows(codes: torch.Tensor, scale_codes: torch.Tensor) -> torch.Tensor:
+    """e2m1 value * 2^(scale code - 127) as bf16 [N, K]: exact (at most two significant bits, exponents -121 .. 122)."""
+    n, k2 = codes.shape
+    c = torch.stack([codes & 15, codes >> 4], dim=2).view(n, 2 * k2).long()
+    lut = torch.tensor(E2M1_VALUES + tuple(-v for v in E2M1_VALUES), dtype=F32, device=codes.device)
+    e = (scale_codes.to(I32) - 127).repeat_interleave(MX_BLOCK, dim=1)
+    return torch.ldexp(lut[c], e).to(BF16)
+
+
+def _mxfp4_check(codes, scale_codes):
+    n, k = codes.shape[0], codes.shape[1] * 2
+    if codes.dtype != U8 or scale_codes.dtype != U8 or tuple(scale_codes.shape) != (n, k // MX_BLOCK) or n % 16 or k % 128:
+        raise ValueError(f"dflash_amd: mxfp4 codes uint8 [N, K/2] and scale codes uint8 [N, K/32] with N % 16 == 0 and "
+                         f"K % 128 == 0 (got {tuple(codes.shape)}, {tuple(scale_codes.shape)})")
+    return n, k
+
+
+def pack_weight_mxfp4(codes: torch.Tensor, scale_codes: torch.Tensor) -> Mxfp4Weight:
+    """quantize_mxfp4_rows' output for an [N, K] weight -> Mxfp4Weight in the DFL_W_MXFP4 layout (include/dflash_hip.h):
+    a byte permutation, tensor ops on the codes' device.  N % 16 == 0, K % 128 == 0; N * K / 2 + N * K / 32 bytes."""
+    n, k = _mxfp4_check(codes, scale_codes)
+    # row byte 64 j + 16 d + 4 kq + b holds k = 128 j + 32 d + 8 kq + 2 b ..: [t][column][j][d][kq][b] -> [t][j][kq][column][d][b]
+    cp = codes.view(n // 16, 16, k // 128, 4, 4, 4).permute(0, 2, 4, 1, 3, 5).reshape(-1)
+    sp = scale_codes.view(n // 16, 16, k // 128, 4).permute(0, 2, 1, 3).reshape(-1)    # [t][j][column][d]
+    return Mxfp4Weight(torch.cat([cp, sp]).contiguous(), n, k)
+
+
+def pack_weight_gateup_mxfp4(gate_codes: torch.Tensor, gate_scales: torch.Tensor, up_codes: torch.Tensor,
+                             up_scales: torch.Tensor) -> Mxfp4Weight:
+    """gate / up codes [I, K/2] and scale codes [I, K/32] -> one Mxfp4Weight of 2I rows, tiles interleaved (gate tile p, up
+    tile p) as pack_weight_gateup, codes and scales alike."""
+    i, k = _mxfp4_check(gate_codes, gate_scales)
+    if (i, k) != _mxfp4_check(up_codes, up_scales):
+        raise ValueError("dflash_amd: gate and up must have one shape")
+
+    def weave(g, u):
+        return torch.stack([g.view(i // 16, 16, -1), u.view(i // 16, 16, -1)], dim=1).reshape(2 * i, -1)
+
+    return pack_weight_mxfp4(weave(gate_codes, up_codes), weave(gate_scales, up_scales))
+
+
+def quantize_keep_mxfp4(m: torch.Tensor):
+    """The load step of an mxfp4 model for one Linear weight [N, K]: (the dequantised values as bf16 — what every path
+    without a 4-bit kernel computes with —, (codes, scale codes) for pack_weight_mxfp4 / pack_layer_mxfp4)."""
+    q = quantize_mxfp4_rows(m)
+    return dequantize_mxfp4_rows(*q), q
+
+
+def pack_layer_mxfp4(l4: dict) -> dict:
+    """A dense layer's (codes, scale codes) by projection — q, k, v, o, gate, up, down — -> its four Mxfp4Weights, laid
+    out as the layer's packed bf16 weights are: q/k/v as one matrix, gate/up interleaved."""
+    return {"qkv": pack_weight_mxfp4(torch.cat([l4[k][0] for k in "qkv"]), torch.cat([l4[k][1] for k in "qkv"])),
+            "o": pack_weight_mxfp4(*l4["o"]), "gu": pack_weight_gateup_mxfp4(*l4["gate"], *l4["up"]),
+            "down": pack_weight_mxfp4(*l4["down"])}
+
+
 def check_stream_format(stream_format: str) -> bool:
     """True for "auto" (the 13-bit twins where they apply), False for "bf16"."""
     if stream_format not in STREAM_FORMATS:
@@ -329,12 +426,17 @@ def check_stream_format(stream_format: str) -> bool:
 
 
 def _w(wp, N: int, K: int, name: str) -> Weight:
-    """The dfl_weight of a launch: a packed bf16 tensor, or an Fp8Weight / a Bf16x13Weight of the launch's N x K.  Read
+    """The dfl_weight of a launch: a packed bf16 tensor, or an Fp8Weight / a Bf16x13Weight / an Mxfp4Weight of the launch's
+    N x K (the C side refuses a format the entry point does not take).  Read
     on the host during the call only; the caller's references keep the tensors alive."""
     if isinstance(wp, Bf16x13Weight):
         if (wp.N, wp.K) != (N, K):
             raise ValueError(f"dflash_amd: {name} is a bf16x13 weight of {wp.N} x {wp.K}, the launch asks for {N} x {K}")
         return Weight(_p(wp.data, U8, name), None, W_BF16X13)
+    if isinstance(wp, Mxfp4Weight):
+        if (wp.N, wp.K) != (N, K):
+            raise ValueError(f"dflash_amd: {name} is an mxfp4 weight of {wp.N} x {wp.K}, the launch asks for {N} x {K}")
+        return Weight(_p(wp.data, U8, name), None, W_MXFP4)
     if not isinstance(wp, Fp8Weight):
         return Weight(_p(wp, BF16, name), None, W_BF16)
     if (wp.N, wp.K) != (N, K):

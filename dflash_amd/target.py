@@ -24,7 +24,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import ops
-from .model import WEIGHT_FORMATS, _rope_tables
+from .model import TARGET_WEIGHT_FORMATS as WEIGHT_FORMATS, _rope_tables
 from .row_stack import RowStack
 from .tile_stack import TileStack, gemm_ws
 from .utils import sample

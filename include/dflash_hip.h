@@ -118,8 +118,27 @@ typedef struct dfl_rows {
  *     chunk c wave w owns k-steps (16 c + w) * 4 .. + 3 — quad 16 c + w of the tile — so an ITEM is (tile, chunk, wave),
  *     one quad.  meta = uint32 [N / 16][nch][16][2]: the pair of (t, c, w) at index (t * nch + c) * 16 + w (nch = 1 gives
  *     the formula above), the base repeated per (chunk, wave), the patch word's k-step field 0..3.
- * The packer is dflash_amd.ops.pack_weight_bf16x13 (tensor ops over the packed bf16 weight, once at load). */
-enum { DFL_W_BF16 = 0, DFL_W_E4M3 = 1, DFL_W_BF16X13 = 2 };
+ * The packer is dflash_amd.ops.pack_weight_bf16x13 (tensor ops over the packed bf16 weight, once at load).
+ * ---- DFL_W_MXFP4: OCP Microscaling MXFP4, weight-only (W4A16) ----
+ * Taken by dfl_gemm_resid (any K % 128 == 0, the K-chunked form included), dfl_gemm_silu_mul and dfl_gemm_argmax ONLY;
+ * every other entry point refuses it as an unknown format.  An element is an e2m1 code (bit 3 sign, bits 2:0 the magnitudes
+ * 0, .5, 1, 1.5, 2, 3, 4, 6) and every 32 consecutive k of a row share one e8m0 scale code s: the weight is e2m1 * 2^(s - 127).
+ * The kernels convert code pairs to bf16 with the block scale applied in the conversion (exact), run the same bf16 MFMA
+ * on the same bf16 activations and have no epilogue multiply: Linear output = bf16(sum_k x[m][k] * w[n][k]), every rounding
+ * point where the bf16 form has it.  One MFMA k-step of one column is 32 consecutive k: a k-step fragment is one MX block.
+ * wp points at ONE buffer of N * K / 2 + N * K / 32 bytes (scale must be NULL): the codes, then the scales.
+ *   codes  [N/16][K/128][64 lanes][16 B]: lane l is column 16 t + (l & 15), kq = l >> 4; dword d (0..3) of the lane's 16-byte
+ *     word holds k-step 4 j + d: its 8 codes are those of k = 128 j + 32 d + 8 kq .. + 7, two per byte in k order, the LOW
+ *     nibble first.
+ *   scales e8m0 bytes [N/16][K/128][16 columns][4 B] at byte offset N * K / 2: one dword per (column, 128-k group), byte d
+ *     the scale of k-step 4 j + d (k = 128 j + 32 d ..).  The kernel forms the fp32 multiplier as code << 23.
+ *   Tiles t in dfl_pack_weight order, or (dfl_gemm_silu_mul, N = 2 I) in dfl_pack_weight_gateup order — gate tile p, up tile
+ *     p interleaved — codes and scales alike.
+ * Scale codes 7..247 (exponents -120..120); anything else is undefined, as other unvalidated device data.
+ * K % 128 == 0; a wave's share is a whole number of 4-k-step words (the launcher rounds it up, as the e4m3 form rounds to
+ * even).  DFL_EINVAL, by the entry point's name: K % 128 != 0, a non-NULL scale.
+ * Quantiser and packers: dflash_amd.ops.quantize_mxfp4_rows / pack_weight_mxfp4 / pack_weight_gateup_mxfp4 (tensor ops). */
+enum { DFL_W_BF16 = 0, DFL_W_E4M3 = 1, DFL_W_BF16X13 = 2, DFL_W_MXFP4 = 3 };
 typedef struct dfl_weight {
   const void *wp;      /* packed weight: dfl_pack_weight[_gateup] (bf16) or dfl_pack_weight[_gateup]_fp8 (codes) */
   const float *scale;  /* DFL_W_E4M3: fp32 scale per packed row, in packed tile order; DFL_W_BF16: must be NULL */
@@ -171,7 +190,8 @@ int dfl_gemm_f32(const void *wp, const dfl_rows *x0, const dfl_rows *x1, int mt,
  * (tf:...modeling_qwen3.py:82 inner expression).  w_gateup from dfl_pack_weight_gateup[_fp8].
  * K/32 <= 128 (no K split: the activation needs the finished sums).  e4m3: gate and up sums are scaled separately,
  * each before its bf16 rounding.  DFL_W_BF16X13 (of the dfl_pack_weight_gateup layout, N = 2 I): K = 2048 or 4096, scale
- * NULL; anything else is refused by name.  Same bits as DFL_W_BF16. */
+ * NULL; anything else is refused by name.  Same bits as DFL_W_BF16.  DFL_W_MXFP4 (gate/up tile order, N = 2 I): K % 128
+ * == 0, scale NULL; gate and up blocks carry their own scales. */
 int dfl_gemm_silu_mul(const dfl_weight *w_gateup, const dfl_rows *x, int I, int K, void *act_frag, const int32_t *dyn,
                       void *stream);
 
@@ -188,7 +208,8 @@ int dfl_gemm_silu_mul(const dfl_weight *w_gateup, const dfl_rows *x, int I, int 
  * ev_start / ev_end (each optional): hipEvent_t recorded on `stream` right before and right after the GEMM launch (the
  * argmax finish launch comes behind ev_end): bench.py times the lm_head kernel itself with them (roofline.achieved).
  * e4m3: ids, logits and margins over bf16(sum * scale).  DFL_W_BF16X13: K = 2048 or 4096, scale NULL; same bits as
- * DFL_W_BF16 (dfl_gemm_sample does not take it). */
+ * DFL_W_BF16 (dfl_gemm_sample does not take it).  DFL_W_MXFP4: K % 128 == 0, scale NULL; ids, logits and margins over
+ * bf16(sum) of the dequantised weights (dfl_gemm_sample refuses it). */
 int64_t dfl_argmax_ws_bytes(void);
 int dfl_gemm_argmax(const dfl_weight *w, const dfl_rows *x, int V, int K, int row0, int nrows, const int32_t *dyn,
                     int nrows_dyn_word, void *ws, int64_t *out_ids, int out_off, void *logits, float *margin_out,
@@ -212,7 +233,8 @@ int dfl_gemm_sample(const dfl_weight *w, const dfl_rows *x, int V, int K, int ro
  *   ss_out[n/16][m] <- sum over the tile's 16 columns of h_new^2 (optional; feeds the
  *   mode-2 row source of the next GEMM, so the RMSNorm is no launch of its own).
  * Any K: beyond 4096 the workgroup walks K in chunks itself (x must then be mode 0/1).
- * DFL_W_BF16X13: K > 4096 and K % 2048 == 0 only (the K-chunked form), scale NULL; same bits as DFL_W_BF16. */
+ * DFL_W_BF16X13: K > 4096 and K % 2048 == 0 only (the K-chunked form), scale NULL; same bits as DFL_W_BF16.
+ * DFL_W_MXFP4: any K % 128 == 0 (both forms, half tiles included), scale NULL. */
 int dfl_gemm_resid(const dfl_weight *w, const dfl_rows *x, int N, int K, void *h_io, int64_t ldh, int add_residual,
                    void *tap, int64_t ldtap, float *ss_out, const int32_t *dyn, void *stream);
 
