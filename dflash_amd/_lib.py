@@ -70,6 +70,7 @@ SIGNATURES = {
                               _p, _i64, _i, _p]),
     "dfl_logit_bias_rows": (_i, [_p, _p, _i64, _i64, _i, _i, _i, _i, _p, _i, _i, _p, _i64, _p, _i, _p, _i, _i, _i, _i,
                                  _p, _i64, _i, _p]),
+    "dfl_min_p_rows": (_i, [_p, _p, _i64, _i64, _i, _i, _i, _i, _p, _i, _i, _p, _f, _p, _f, _p, _i64, _i, _p]),
     "dfl_grammar_rows": (_i, [_p, _p, _i64, _i64, _i, _i, _i, _i, _p, _i, _i, _p, _i64, _i, _p, _p, _p, _i64, _p, _i64, _i,
                               _p]),
     "dfl_grammar_advance": (_i, [_p, _i64, _i, _i, _p, _p, _i, _p, _i64, _i, _p, _i, _i, _i, _i, _p]),

@@ -56,8 +56,13 @@ class BatchedDecoder:
                  temperature: float = 0.0, tiles_per_request: int = 1, sampler: str = "torch",
                  draft_temperature: float = 0.0, filtering: bool = False, request_temperature: bool = False,
                  logprobs: Optional[int] = None, penalties: bool = False, logit_bias: bool = False,
-                 grammar_states: int = 0, constrain_draft: bool = False):
-        """constrain_draft (fixed here for the same reason as grammar_states: it fixes the captured launch sequence; needs
+                 grammar_states: int = 0, constrain_draft: bool = False, min_p: bool = False):
+        """min_p (fixed here for the same reason as filtering: it fixes the captured launch sequence): requests may
+        carry a min_p (admit); every sampling verify materialises its logits and, directly in front of the draw,
+        dfl_min_p_rows writes each slot's rows masked by its own ln(min_p), read by address from log_min_ps beside
+        inv_ts, into a buffer of their own.  A slot at 0 (-inf) has its rows copied and gets the
+        ids of a decoder built without it; a greedy decoder enqueues nothing new.
+        constrain_draft (fixed here for the same reason as grammar_states: it fixes the captured launch sequence; needs
         grammar_states > 0 or logit_bias, one tile per request and a greedy draft): the draft's head launch materialises
         its logits and ONE dfl_grammar_draft_rows launch over all tiles re-picks every slot's draft tokens under its
         automaton and its bans ("The draft under the grammar").  A slot without a grammar and
@@ -105,6 +110,9 @@ class BatchedDecoder:
             raise NotImplementedError("penalties take blocks of <= 16 rows (tiles_per_request = 1)")
         if penalties and temperature >= 1e-5 and sampler != "device":
             raise ValueError("penalties at T > 0 need sampler='device' (sampler='torch' is the reference's multinomial over "
+                             "the raw logits)")
+        if min_p and temperature >= 1e-5 and sampler != "device":
+            raise ValueError("min_p at T > 0 needs sampler='device' (sampler='torch' is the reference's multinomial over "
                              "the raw logits)")
         if not isinstance(target, NativeTarget):
             raise TypeError("BatchedDecoder needs a dflash_amd.NativeTarget (see module docstring)")
@@ -194,7 +202,16 @@ class BatchedDecoder:
             self.grammar = ops.grammar_state(NREQ, grammar_states, target.V, dev)
             self._grammars = []
             self._gr_logits = z(MT, 16, target.V)
-        if self.filtering or self.lp is not None or self.penalties or self.logit_bias or self.grammar is not None:
+        # min_p: one fp32 L = ln(min_p) per request slot beside inv_ts (-inf: off), rewritten on every admission and read
+        # by address, and the buffer of the masked rows; min_p_on: the decoder samples, so the launch is enqueued at all
+        self.min_p = bool(min_p)
+        self.min_p_on = self.min_p and (self.temperature >= 1e-5 or self.request_temperature)
+        if self.min_p:
+            self.log_min_ps = torch.full((NREQ,), float("-inf"), dtype=F32, device=dev)
+        if self.min_p_on:
+            self._mp_logits = z(MT, 16, target.V)
+        if (self.filtering or self.lp is not None or self.penalties or self.logit_bias or self.grammar is not None
+                or self.min_p_on):
             self._logits = z(MT, 16, target.V)
         # constrain_draft: the draft head's materialised logits, read by the pick launch right behind it
         self.constrain_draft = bool(constrain_draft)
@@ -277,7 +294,7 @@ class BatchedDecoder:
 
     # ------------------------------------------------------------------ admission
     def _admit_prefill(self, r: int, input_ids: torch.Tensor, temperature: float, seed: Optional[int], top_k=0,
-                       top_p=1.0, penalties=(1.0, 0.0, 0.0), bias=None, grammar=None):
+                       top_p=1.0, penalties=(1.0, 0.0, 0.0), bias=None, grammar=None, min_p=None):
         """The launches both admissions share: target prefill into slot r's cache, the first token, the prompt's context
         rows into the draft cache except the last <= 16.  Returns (P, first token [1, 1] on the device, tapped rows
         [P, fc_in], the seed written for the slot or None)."""
@@ -301,6 +318,11 @@ class BatchedDecoder:
             if not self.filtering:
                 raise ValueError("admit: top_k / top_p need a decoder built with filtering=True (and sampler='device')")
             flt = dict(top_k=int(top_k), top_p=float(top_p))
+        mp = ops.check_min_p(min_p)
+        if mp is not None and not self.min_p:
+            raise ValueError("admit: min_p needs a decoder built with min_p=True")
+        if mp is not None and temperature >= 1e-5 and self.sampler != "device":
+            raise ValueError("admit: min_p at T > 0 needs sampler='device'")
         if input_ids.shape[0] != 1 or not input_ids.is_cuda:
             raise ValueError("admit: input_ids must be a [1, P] GPU tensor")
         P = input_ids.shape[1]
@@ -335,9 +357,15 @@ class BatchedDecoder:
             ops.penalty_count(tab, input_ids, lo=0, hi=P, as_prompt=True, clear=True)
             first_logits = ops.penalty_rows(first_logits[0, -1:].to(BF16).contiguous(), tab, repetition_penalty=pr,
                                             presence_penalty=pa, frequency_penalty=pf).unsqueeze(0)
+        if self.min_p:   # the slot's L for every later token, rewritten on every admission (-inf: off)
+            self.log_min_ps[r:r + 1].fill_(ops.min_p_log(mp))
         sd = None
         if self.sampler == "device" and (temperature >= 1e-5 or self.temperature >= 1e-5):
             sd = resolve_seed("device", seed)
+            if mp is not None and temperature >= 1e-5:   # the floor directly in front of the first token's draw
+                first_logits = ops.min_p_rows(first_logits[0, -1:].to(BF16).contiguous(), min_p=mp,
+                                              temperature=temperature).unsqueeze(0)
+                flt = flt or dict(top_k=0, top_p=1.0)
             first = (_draw_rows(first_logits, temperature, sd, P, flt) if temperature >= 1e-5
                      else sample(first_logits, 0.0))
         else:
@@ -419,7 +447,7 @@ class BatchedDecoder:
     def admit(self, r: int, input_ids: torch.Tensor, temperature: float = 0.0, seed: Optional[int] = None,
               top_k: int = 0, top_p: float = 1.0, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
               frequency_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None, banned_token_ids=None,
-              min_tokens: int = 0, grammar=None) -> None:
+              min_tokens: int = 0, grammar=None, min_p=None) -> None:
         """Prefill request r (model/dflash.py:218-229): target prefill through the wrapped
         model, K/V into the group cache, first token sampled, the prompt's context rows
         projected into the draft cache except the last <= 16, which become the first
@@ -432,11 +460,14 @@ class BatchedDecoder:
         logit_bias / allowed_token_ids / banned_token_ids / min_tokens: the request's own (a decoder built with
         logit_bias=True); the slot's whole bias row and min_pos are rewritten.
         grammar: a handle add_grammar returned (None: no grammar, the slot's rows pass unmasked); the slot's base and
-        state are rewritten."""
+        state are rewritten.
+        min_p: the request's own (None / 0: off; a decoder built with min_p=True, else ValueError); the slot's
+        ln(min_p) is rewritten."""
         P, first, th, sd = self._admit_prefill(r, input_ids, temperature, seed, top_k, top_p,
                                                (repetition_penalty, presence_penalty, frequency_penalty),
                                                dict(logit_bias=logit_bias, allowed_token_ids=allowed_token_ids,
-                                                    banned_token_ids=banned_token_ids, min_tokens=min_tokens), grammar)
+                                                    banned_token_ids=banned_token_ids, min_tokens=min_tokens), grammar,
+                                               min_p)
         self.output_ids[r].fill_(self.mask_id)
         self.output_ids[r, :P] = input_ids[0]
         if sd is not None:
@@ -461,7 +492,7 @@ class BatchedDecoder:
     def admit_fused(self, r: int, input_ids: torch.Tensor, temperature: float = 0.0, seed: Optional[int] = None,
                     top_k: int = 0, top_p: float = 1.0, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
                     frequency_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None, banned_token_ids=None,
-                    min_tokens: int = 0, grammar=None) -> None:
+                    min_tokens: int = 0, grammar=None, min_p=None) -> None:
         """`admit` with the slot re-armed by ONE launch (dfl_admit_slot) instead of a dozen small writes: ids, first
         token, block, context tile, both length records and the seed are written on the device from device-resident
         inputs, so that after the prefill launches the admission reads nothing back and copies nothing from the host —
@@ -474,7 +505,8 @@ class BatchedDecoder:
         P, first, th, sd = self._admit_prefill(r, input_ids, temperature, seed, top_k, top_p,
                                                (repetition_penalty, presence_penalty, frequency_penalty),
                                                dict(logit_bias=logit_bias, allowed_token_ids=allowed_token_ids,
-                                                    banned_token_ids=banned_token_ids, min_tokens=min_tokens), grammar)
+                                                    banned_token_ids=banned_token_ids, min_tokens=min_tokens), grammar,
+                                               min_p)
         n_tail = min(16, P)
         ops.admit_slot(r, input_ids[0].contiguous(), first.reshape(1), self.output_ids, self.block, self.post, self.result,
                        th[P - n_tail:], self.d["taps"], self.dyn_d, self.dyn_t, self.BW, self.mask_id,
@@ -600,7 +632,7 @@ class BatchedDecoder:
         st.finish(t.norm)
         lm = self._t_head()
         lg = self._logits if self.lp is not None else None   # logprobs: every head below materialises its logits
-        if self.penalties or self.logit_bias or self.grammar is not None:
+        if self.penalties or self.logit_bias or self.grammar is not None or self.min_p_on:
             # materialise; each slot's biased rows (row m predicts position POS0 + m + 1), then its grammar-masked rows
             # (row m by the slot's state walked through block[1 .. m]), then its penalised rows, each
             # launch with the rows' argmax (what a greedy slot keeps); the draw over the last of them at the slot's seed /
@@ -624,6 +656,11 @@ class BatchedDecoder:
                 rows = self._pen_logits[:R]
             if self.request_temperature or self.temperature >= 1e-5:
                 tkw = dict(inv_t=self.inv_ts) if self.request_temperature else dict(temperature=self.temperature)
+                if self.min_p_on:   # directly in front of the draw: each slot's rows under its own L (-inf: copied), at
+                    # the invT the draw uses; the masked rows go to a buffer of their own
+                    ops.min_p_rows(rows, log_min_p=self.log_min_ps, out=self._mp_logits[:R], dyn=dyn_t,
+                                   nrows_dyn_word=ops.DYN_BS, tiles_per_req=TPR, **tkw)
+                    rows = self._mp_logits[:R]
                 ops.sample_rows_nucleus(rows, seed=self.seeds, top_k=self.top_k, top_p=self.top_p,
                                         dyn=dyn_t, nrows_dyn_word=ops.DYN_BS, pos_word=ops.DYN_POS0, pos_add=1,
                                         tiles_per_req=TPR, out=self.post.view(-1, 16), **tkw)
@@ -822,6 +859,24 @@ def _prompt_filters(top_k, top_p, n: int, temperature, sampler: str):
     return [int(k) for k in ks], [float(p) for p in ps], filtering
 
 
+def _prompt_min_p(min_p, n: int, temperature, sampler: str):
+    """(min_p per prompt: a float in (0, 1] or None, whether any prompt floors a sampled draw) from None, a scalar or one
+    value (or None) per prompt; temperature: one float, or the list _prompt_temperatures returns."""
+    if min_p is None or isinstance(min_p, (bool, int, float)) or not hasattr(min_p, "__len__"):
+        mps = [min_p] * n
+    else:
+        mps = list(min_p)
+        if len(mps) != n:
+            raise ValueError("min_p: a scalar or one value per prompt")
+    mps = [ops.check_min_p(v) for v in mps]
+    ts = [temperature] * n if isinstance(temperature, (int, float)) else list(temperature)
+    on = any(v is not None and t >= 1e-5 for v, t in zip(mps, ts))
+    if on and sampler != "device":
+        raise ValueError("min_p at T > 0 needs sampler='device' (sampler='torch' is the reference's multinomial over the "
+                         "raw logits)")
+    return mps, on
+
+
 def _prompt_penalties(repetition_penalty, presence_penalty, frequency_penalty, n: int):
     """((r, a, f) per prompt, whether any prompt is not neutral) from scalars or one value per prompt."""
     cols = []
@@ -899,7 +954,8 @@ def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_i
                           group_size: int = MAX_GROUP, hook_block_view: bool = False, sampler: str = "torch",
                           seed=None, top_k=0, top_p=1.0, logprobs: Optional[int] = None, repetition_penalty=1.0,
                           presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, allowed_token_ids=None,
-                          banned_token_ids=None, min_tokens=0, grammar=None, constrain_draft: bool = False) -> list:
+                          banned_token_ids=None, min_tokens=0, grammar=None, constrain_draft: bool = False,
+                          min_p=None) -> list:
     """`dflash_generate` (benchmark.py:44-251) for a list of prompts: requests run in
     groups of `group_size` <= 4 (<= 2 with block sizes of 17..32 rows) that share the weight stream; returns one namespace per
     prompt with the fields of benchmark.py:242-251 (timing fields are the group's).
@@ -919,7 +975,9 @@ def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_i
     grammar: as dflash_generate; one TokenDFA for every prompt, or a sequence with one (or None) per prompt.  Each group's
     decoder gets a pool of exactly its prompts' automata (blocks of <= 16 rows); the results carry `grammar_state`.
     constrain_draft: as dflash_generate (ValueError when no prompt has a grammar or a not-neutral logit-bias keyword); a
-    prompt without a grammar and without bans keeps its argmax draft."""
+    prompt without a grammar and without bans keeps its argmax draft.
+    min_p: as dflash_generate; a scalar, or one value (or None) per prompt.  The decoders are built with min_p=True when
+    any prompt floors a sampled draw (blocks of up to 32 rows); a prompt at 0 gets the ids of a run without it."""
     logprobs = ops.check_logprobs(logprobs)
     dfas = _prompt_grammars(grammar, len(input_ids))
     for d in {id(d): d for d in dfas if d is not None}.values():
@@ -937,6 +995,7 @@ def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_i
     temps, per_request = _prompt_temperatures(temperature, len(input_ids), sampler)
     seeds = _prompt_seeds(sampler, seed, len(input_ids), any(t >= 1e-5 for t in temps))
     top_ks, top_ps, filtering = _prompt_filters(top_k, top_p, len(input_ids), temps, sampler)
+    min_ps, min_p_on = _prompt_min_p(min_p, len(input_ids), temps, sampler)
     if not 1 <= block_size <= 32:
         raise NotImplementedError("the batched loop takes blocks of 1..16 rows (one tile per request) or 17..32 rows (two)")
     if penalties and block_size > 16:
@@ -956,7 +1015,7 @@ def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_i
                              out_len=pmax + max_new_tokens + 16 * tpr, mask_token_id=mask_token_id,
                              stop_token_ids=stop_token_ids, temperature=max(temps[i] for i in idx), tiles_per_request=tpr,
                              sampler=sampler, filtering=filtering, request_temperature=per_request, logprobs=logprobs,
-                             penalties=penalties, logit_bias=logit_bias_on,
+                             penalties=penalties, logit_bias=logit_bias_on, min_p=min_p_on,
                              grammar_states=_pool_rows([dfas[i] for i in idx]),
                              # (a group none of whose prompts has anything to constrain by runs the plain launches)
                              constrain_draft=bool(constrain_draft) and bool(logit_bias_on or _pool_rows([dfas[i] for i in idx])))
@@ -966,7 +1025,7 @@ def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_i
             pr, pa, pf = pens[idx[r]]
             dec.admit(r, p, temps[idx[r]], seed=seeds[idx[r]], top_k=top_ks[idx[r]], top_p=top_ps[idx[r]],
                       repetition_penalty=pr, presence_penalty=pa, frequency_penalty=pf, **biases[idx[r]],
-                      grammar=handles[r])
+                      grammar=handles[r], min_p=min_ps[idx[r]] if min_p_on else None)
         ttft = cuda_time() - t0
         taus = [[] for _ in idx]
         # (hook_block_view: the hook sees the block as the single-request loop hands it over, bs slots; default: the

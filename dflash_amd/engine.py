@@ -16,7 +16,7 @@ import torch
 
 from . import ops
 from .batch import (MAX_GROUP, BatchedDecoder, _load_grammars, _pool_rows, _prompt_bias, _prompt_filters,
-                    _prompt_grammars, _prompt_penalties, _prompt_seeds, _prompt_temperatures)
+                    _prompt_grammars, _prompt_min_p, _prompt_penalties, _prompt_seeds, _prompt_temperatures)
 from .generate import NO_LOGPROBS, _kept_cols, _trim, cuda_time, logprob_fields
 from .slots import SlotLoop
 
@@ -60,7 +60,7 @@ class _DecoderDriver:
         ids = p.input_ids if p.input_ids.is_cuda else p.input_ids.to(self.dec.dev)
         self.dec.admit_fused(slot, ids, p.temperature, seed=p.seed, top_k=p.top_k, top_p=p.top_p,
                              repetition_penalty=p.penalties[0], presence_penalty=p.penalties[1],
-                             frequency_penalty=p.penalties[2], **p.bias, grammar=p.grammar)
+                             frequency_penalty=p.penalties[2], **p.bias, grammar=p.grammar, min_p=p.min_p)
         t1 = cuda_time()
         p.ttft, p.t_admitted = t1 - t0, t1
         self.stats["admit_s"] += t1 - t0
@@ -123,13 +123,17 @@ class BatchEngine:
     admissions.  A precondition of the capture that does not hold raises here, nothing is swallowed."""
 
     filtering, request_temperature, temperature, penalties, logit_bias = False, False, 0.0, False, False
+    min_p = False
 
     def __init__(self, model, target, *, slots: int = MAX_GROUP, max_rows: int, out_len: int, mask_token_id: int,
                  block_size: int = 16, stop_token_ids=None, temperature: float = 0.0, sampler: str = "torch",
                  graph: Optional[bool] = None, filtering: bool = False, request_temperature: bool = False,
                  logprobs: Optional[int] = None, penalties: bool = False, logit_bias: bool = False,
-                 grammar_states: int = 0, constrain_draft: bool = False):
-        """constrain_draft: every slot's draft tokens are re-picked under its grammar and its bans right behind the draft's
+                 grammar_states: int = 0, constrain_draft: bool = False, min_p: bool = False):
+        """min_p: requests may carry a min_p (submit); fixed here because it fixes the captured launch sequence
+        (DESIGN.md section 18).  A slot's ln(min_p) is rewritten on every admission and read by address by the captured
+        launch; requests at 0 emit the same ids, and a greedy engine enqueues nothing new.
+        constrain_draft: every slot's draft tokens are re-picked under its grammar and its bans right behind the draft's
         head launch ("The draft under the grammar"); fixed here because it fixes the captured
         launch sequence; needs grammar_states > 0 or logit_bias=True (ValueError).  The emitted ids do not change; a
         request without a grammar and without bans keeps its argmax draft.
@@ -167,7 +171,8 @@ class BatchEngine:
                                   stop_token_ids=stop_token_ids, temperature=temperature, sampler=sampler,
                                   filtering=filtering, request_temperature=request_temperature, logprobs=logprobs,
                                   penalties=penalties, logit_bias=logit_bias, grammar_states=grammar_states,
-                                  constrain_draft=constrain_draft)
+                                  constrain_draft=constrain_draft, min_p=min_p)
+        self.min_p = bool(min_p)
         self.filtering, self.temperature, self.penalties = bool(filtering), float(temperature), bool(penalties)
         self.logit_bias = bool(logit_bias)
         self.request_temperature = bool(request_temperature)
@@ -183,7 +188,7 @@ class BatchEngine:
                draft_token_hook: Optional[Callable] = None, top_k: int = 0, top_p: float = 1.0,
                temperature: Optional[float] = None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
                frequency_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None, banned_token_ids=None,
-               min_tokens: int = 0, grammar=None) -> int:
+               min_tokens: int = 0, grammar=None, min_p=None) -> int:
         """Queue a request; returns its id (ids count up in submission order).  draft_token_hook(block_view, start,
         call): `call` counts from 0 at the request's admission; the view has the cycle's block size.
         top_k / top_p: the request's own filter on its T > 0 draws (an engine built with filtering=True); accepted and
@@ -194,7 +199,10 @@ class BatchEngine:
         penalties=True; 1.0 / 0.0 / 0.0: off).
         logit_bias / allowed_token_ids / banned_token_ids / min_tokens: the request's own (an engine built with
         logit_bias=True; None / None / None / 0: off), validated here.
-        grammar: a handle add_grammar returned (None: no grammar; an engine built with grammar_states > 0)."""
+        grammar: a handle add_grammar returned (None: no grammar; an engine built with grammar_states > 0).
+        min_p: the request's own (None / 0: off; an engine built with min_p=True, else ValueError); it does nothing on a
+        request whose own temperature is 0."""
+        mp = ops.check_min_p(min_p)
         if grammar is not None:   # (raises on a handle this engine did not return, and on an engine without a pool)
             self.dec.check_grammar_handle(grammar)
         pen = ops.check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
@@ -213,12 +221,16 @@ class BatchEngine:
                              "request_temperature=True")
         if ops.check_filter(top_k, top_p) and T >= 1e-5 and not self.filtering:
             raise ValueError("submit: top_k / top_p need an engine built with filtering=True")
+        if mp is not None and not self.min_p:
+            raise ValueError("submit: min_p needs an engine built with min_p=True")
+        if mp is not None and T >= 1e-5 and self.dec.sampler != "device":
+            raise ValueError("submit: min_p at T > 0 needs sampler='device'")
         check_fit(input_ids.shape[1], int(max_new_tokens), self.dec.max_rows, self.dec.out_len)
         req = self.loop.submit(input_ids.shape[1], int(max_new_tokens),
                                SimpleNamespace(input_ids=input_ids, seed=seed, hook=draft_token_hook, result=None,
                                                ttft=0.0, t_admitted=0.0, top_k=int(top_k), top_p=float(top_p),
                                                temperature=T, penalties=pen or (1.0, 0.0, 0.0), bias=bias,
-                                               grammar=grammar))
+                                               grammar=grammar, min_p=mp))
         return req.rid
 
     def add_grammar(self, dfa) -> int:
@@ -249,7 +261,7 @@ def dflash_generate_stream(model, target, input_ids: Sequence[torch.Tensor], mas
                            sampler: str = "torch", seed=None, top_k=0, top_p=1.0,
                            logprobs: Optional[int] = None, repetition_penalty=1.0, presence_penalty=0.0,
                            frequency_penalty=0.0, logit_bias=None, allowed_token_ids=None, banned_token_ids=None,
-                           min_tokens=0, grammar=None, constrain_draft: bool = False) -> list:
+                           min_tokens=0, grammar=None, constrain_draft: bool = False, min_p=None) -> list:
     """`dflash_generate_batch` with slot refill: one namespace per prompt with the fields of benchmark.py:242-251, each
     request emitting what its own `dflash_generate` run emits.  max_new_tokens: one int or one per prompt.
     draft_token_hook(request_index, block_view, start, call).  seed as in dflash_generate_batch (an int s gives prompt i
@@ -261,7 +273,8 @@ def dflash_generate_stream(model, target, input_ids: Sequence[torch.Tensor], mas
     logit_bias / allowed_token_ids / banned_token_ids / min_tokens: one value for every prompt, or a sequence with one
     value (or None) per prompt.
     grammar: one TokenDFA for every prompt, or a sequence with one (or None) per prompt.
-    constrain_draft: as dflash_generate_batch."""
+    constrain_draft: as dflash_generate_batch.
+    min_p: a scalar, or one value (or None) per prompt."""
     dfas = _prompt_grammars(grammar, len(input_ids))
     for d in {id(d): d for d in dfas if d is not None}.values():
         ops.check_grammar(d, target.V)
@@ -275,6 +288,7 @@ def dflash_generate_stream(model, target, input_ids: Sequence[torch.Tensor], mas
     temps, per_request = _prompt_temperatures(temperature, n, sampler)
     seeds = _prompt_seeds(sampler, seed, n, any(t >= 1e-5 for t in temps))
     top_ks, top_ps, filtering = _prompt_filters(top_k, top_p, n, temps, sampler)
+    min_ps, min_p_on = _prompt_min_p(min_p, n, temps, sampler)
     pens, penalties = _prompt_penalties(repetition_penalty, presence_penalty, frequency_penalty, n)
     biases, logit_bias_on = _prompt_bias(target, logit_bias, allowed_token_ids, banned_token_ids, min_tokens, n,
                                          stop_token_ids)
@@ -283,11 +297,12 @@ def dflash_generate_stream(model, target, input_ids: Sequence[torch.Tensor], mas
                       out_len=need + BLOCK_ROWS, mask_token_id=mask_token_id, block_size=block_size,
                       stop_token_ids=stop_token_ids, temperature=max(temps, default=0.0), sampler=sampler, filtering=filtering,
                       request_temperature=per_request, logprobs=logprobs, penalties=penalties, logit_bias=logit_bias_on,
-                      grammar_states=_pool_rows(dfas), constrain_draft=constrain_draft)
+                      grammar_states=_pool_rows(dfas), constrain_draft=constrain_draft, min_p=min_p_on)
     handles = _load_grammars(eng, dfas)
     for i, p in enumerate(input_ids):
         hook = (lambda blk, start, call, i=i: draft_token_hook(i, blk, start, call)) if draft_token_hook else None
         eng.submit(p, mnt[i], seed=seeds[i], draft_token_hook=hook, top_k=top_ks[i], top_p=top_ps[i],
                    temperature=temps[i], repetition_penalty=pens[i][0], presence_penalty=pens[i][1],
-                   frequency_penalty=pens[i][2], **biases[i], grammar=handles[i])
+                   frequency_penalty=pens[i][2], **biases[i], grammar=handles[i],
+                   min_p=min_ps[i] if min_p_on else None)
     return eng.run()

@@ -207,8 +207,19 @@ class DecodeSession:
                  draft_token_hook: Optional[Callable] = None, sampler: str = "torch", seed: Optional[int] = None,
                  top_k: int = 0, top_p: float = 1.0, logprobs: Optional[int] = None, repetition_penalty: float = 1.0,
                  presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None,
-                 banned_token_ids=None, min_tokens: int = 0, grammar=None, constrain_draft: bool = False):
+                 banned_token_ids=None, min_tokens: int = 0, grammar=None, constrain_draft: bool = False, min_p=None):
         from .target import NativeTarget
+        # min_p on the TARGET's rows, directly in front of its draw; None / 0, or T = 0 (the
+        # maximum is always kept): None, and every launch below is the one enqueued without the keyword
+        self._mp = ops.check_min_p(min_p)
+        if temperature < 1e-5:
+            self._mp = None
+        if self._mp is not None:
+            if not isinstance(target, NativeTarget):
+                raise ValueError("min_p needs a dflash_amd.NativeTarget (the kernel reads the verify's materialised logits)")
+            if sampler != "device":
+                raise ValueError("min_p at T > 0 needs sampler='device' (sampler='torch' is the reference's multinomial "
+                                 "over the raw logits)")
         # grammar: a TokenDFA the emitted tokens must walk; None: every launch below is the one
         # enqueued without the keyword
         if grammar is not None:
@@ -285,6 +296,8 @@ class DecodeSession:
         self.native = isinstance(target, NativeTarget)
         self.lp = (ops.logprob_sink(1, self.output_ids.shape[1], self.logprobs, dev) if self.logprobs is not None else None)
         self._lpkw = {} if self.lp is None else dict(logprobs=self.lp)
+        if self._mp is not None:
+            self._lpkw = dict(self._lpkw, min_p=self._mp)
         # the penalty state: the table row dfl_penalty_count keeps (prompt flags + output counts of everything committed),
         # the three values and the buffer the verify writes its penalised rows into
         self.pen = None
@@ -391,7 +404,7 @@ class DecodeSession:
                               past_key_values=self.tcache, use_cache=True, logits_to_keep=1,
                               output_hidden_states=self.use_draft)
         self.output_ids[:, :self.n_in] = self.input_ids
-        if self.pen is not None or self.lb is not None or self.gr is not None:
+        if self.pen is not None or self.lb is not None or self.gr is not None or self._mp is not None:
             self._first_token_processed(out.logits[0, -1:])
         elif self._tseed is not None:   # the first new token draws position n_in
             self.output_ids[:, self.n_in:self.n_in + 1] = _draw_rows(out.logits[:, -1:], self.temperature, self._tseed,
@@ -405,7 +418,8 @@ class DecodeSession:
             self.target_hidden = _taps(out.hidden_states, self.model.target_layer_ids)
 
     def _first_token_processed(self, row: torch.Tensor) -> None:
-        """The first new token under logit bias and / or penalties.  The prompt's last-row logits predict position n_in:
+        """The first new token under logit bias, a grammar, penalties and / or min_p (the floor goes directly in front of
+        the draw).  The prompt's last-row logits predict position n_in:
         they take the bias row (and lose the stop ids under min_tokens >= 1); under penalties the prompt is counted into a
         cleared table row and the rows are penalised by it; the token is their argmax or the seeded draw at position
         n_in over them, and it is counted as output.  Under a grammar the rows are masked by the start state (the
@@ -421,8 +435,12 @@ class DecodeSession:
             ops.penalty_count(p.table, self.output_ids, lo=0, hi=n, as_prompt=True, clear=True)
             z = ops.penalty_rows(z, p.table, repetition_penalty=p.r, presence_penalty=p.a, frequency_penalty=p.f,
                                  out_ids=first)
+        flt = self._filter
+        if self._mp is not None:   # (T > 0 and seeded) the floor goes directly in front of the draw; filters off: the plain draw
+            z = ops.min_p_rows(z, min_p=self._mp, temperature=self.temperature)
+            flt = flt or dict(top_k=0, top_p=1.0)
         if self._tseed is not None:
-            first.copy_(_draw_rows(z.unsqueeze(0), self.temperature, self._tseed, n, self._filter)[0])
+            first.copy_(_draw_rows(z.unsqueeze(0), self.temperature, self._tseed, n, flt)[0])
         if p is not None:
             ops.penalty_count(p.table, self.output_ids, lo=n, hi=n + 1)
         if gr is not None:
@@ -711,6 +729,7 @@ class DecodeSession:
                         self.lm_wp, self.lm_wp8, self.embed_w, getattr(t, "lm_wp", None),
                         t.fp8_tensors() if self.native else (),    # (an fp8 target's codes and scale vectors)
                         getattr(t, "_nuc_logits", None),           # (the logits a filtered, logprobs or penalised verify materialises)
+                        getattr(t, "_mp_logits", None),            # (the rows a verify with min_p masks for its draw)
                         self.pen,                                  # (the penalty table and the penalised rows: the session's own)
                         self.lb,                                   # (the bias table, min_pos and the biased rows likewise)
                         self.gr))                                  # (the grammar pool, base / state and the masked rows likewise)
@@ -870,7 +889,7 @@ def run_decode(model, target, input_ids: torch.Tensor, *, mask_token_id: int, ma
                top_k: int = 0, top_p: float = 1.0, logprobs: Optional[int] = None, repetition_penalty: float = 1.0,
                presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None,
                banned_token_ids=None, min_tokens: int = 0, grammar=None,
-               constrain_draft: bool = False) -> SimpleNamespace:
+               constrain_draft: bool = False, min_p=None) -> SimpleNamespace:
     s = DecodeSession(model, target, input_ids, mask_token_id=mask_token_id, max_new_tokens=max_new_tokens,
                       max_block_size=max_block_size or block_size, stop_token_ids=stop_token_ids,
                       temperature=temperature, draft_temperature=draft_temperature,
@@ -878,7 +897,7 @@ def run_decode(model, target, input_ids: torch.Tensor, *, mask_token_id: int, ma
                       logprobs=logprobs, repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
                       frequency_penalty=frequency_penalty, logit_bias=logit_bias, allowed_token_ids=allowed_token_ids,
                       banned_token_ids=banned_token_ids, min_tokens=min_tokens, grammar=grammar,
-                      constrain_draft=constrain_draft)
+                      constrain_draft=constrain_draft, min_p=min_p)
     t_prefill = cuda_time()
     s.prefill()
     time_to_first_token = cuda_time() - t_prefill
@@ -1047,8 +1066,12 @@ def dflash_generate(model, target, input_ids: torch.Tensor, mask_token_id: int, 
                     seed: Optional[int] = None, top_k: int = 0, top_p: float = 1.0,
                     logprobs: Optional[int] = None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
                     frequency_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None, banned_token_ids=None,
-                    min_tokens: int = 0, grammar=None, constrain_draft: bool = False) -> SimpleNamespace:
+                    min_tokens: int = 0, grammar=None, constrain_draft: bool = False, min_p=None) -> SimpleNamespace:
     """benchmark.py:44-55 signature; returns the namespace of :242-251 (+ replayed_cycles).
+    min_p (None / 0: off; a float in (0, 1]; needs a NativeTarget and sampler="device" at T > 0, does nothing at T = 0):
+    the target's draw keeps token v only if p_v >= min_p * p_max on its tempered, processed distribution — one launch
+    directly in front of every target draw, behind the logit bias, the grammar and the penalties; top_p takes its mass
+    over what min_p kept; blocks of up to 32 rows.  The draft's proposals stay unfiltered.
     grammar (a dflash_amd.TokenDFA; None: off; needs a NativeTarget, blocks of <= 16 rows, and sampler="device" at
     T > 0): the emitted tokens walk the automaton from its start state — every verify row is masked by the state its
     own prefix of the block reaches, between the logit bias and the penalties.  The result's
@@ -1082,7 +1105,7 @@ def dflash_generate(model, target, input_ids: torch.Tensor, mask_token_id: int, 
                                      logprobs, (repetition_penalty, presence_penalty, frequency_penalty),
                                      dict(logit_bias=logit_bias, allowed_token_ids=allowed_token_ids,
                                           banned_token_ids=banned_token_ids, min_tokens=min_tokens),
-                                     constrain_draft=constrain_draft)
+                                     constrain_draft=constrain_draft, min_p=min_p)
     r = run_decode(model, target, input_ids, mask_token_id=mask_token_id, max_new_tokens=max_new_tokens,
                    block_size=block_size, stop_token_ids=stop_token_ids, temperature=temperature, clamp_tail=True,
                    draft_steps=draft_steps, collect_profile=collect_profile, draft_token_hook=draft_token_hook,
@@ -1090,7 +1113,7 @@ def dflash_generate(model, target, input_ids: torch.Tensor, mask_token_id: int, 
                    repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
                    frequency_penalty=frequency_penalty, logit_bias=logit_bias, allowed_token_ids=allowed_token_ids,
                    banned_token_ids=banned_token_ids, min_tokens=min_tokens, grammar=grammar,
-                   constrain_draft=constrain_draft)
+                   constrain_draft=constrain_draft, min_p=min_p)
     return SimpleNamespace(output_ids=r.output_ids, num_input_tokens=r.num_input_tokens,
                            num_output_tokens=r.num_output_tokens, time_to_first_token=r.time_to_first_token,
                            time_per_output_token=r.time_per_output_token, acceptance_lengths=r.acceptance_lengths,
@@ -1102,7 +1125,7 @@ def dflash_generate(model, target, input_ids: torch.Tensor, mask_token_id: int, 
 def _generate_wide_hidden(model, target, input_ids, mask_token_id, max_new_tokens, block_size, stop_token_ids, temperature,
                           collect_profile=False, draft_steps=1, draft_token_hook=None, sampler="torch",
                           seed=None, top_k=0, top_p=1.0, logprobs=None, penalties=(1.0, 0.0, 0.0),
-                          bias=None, constrain_draft=False) -> SimpleNamespace:
+                          bias=None, constrain_draft=False, min_p=None) -> SimpleNamespace:
     """hidden_size > 4096: the request runs as a group of ONE through the ragged-batch kernels (their GEMMs cut K over
     workgroups; the single-request kernels keep a whole K = hidden row slice per workgroup).  Same loop semantics
     (benchmark.py:44-251, tail clamp included); no per-cycle profile, one draft step per cycle."""
@@ -1119,7 +1142,7 @@ def _generate_wide_hidden(model, target, input_ids, mask_token_id, max_new_token
                                  seed=None if seed is None else [seed], top_k=top_k, top_p=top_p, logprobs=logprobs,
                                  repetition_penalty=penalties[0], presence_penalty=penalties[1],
                                  frequency_penalty=penalties[2], **_one_prompt_bias(bias),
-                                 constrain_draft=constrain_draft)[0]
+                                 constrain_draft=constrain_draft, min_p=min_p)[0]
 
 
 def _one_prompt_bias(bias) -> dict:
@@ -1137,8 +1160,10 @@ def dflash_generate_policy(*, model, target, input_ids: torch.Tensor, mask_token
                            seed: Optional[int] = None, top_k: int = 0, top_p: float = 1.0,
                            logprobs: Optional[int] = None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
                            frequency_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None, banned_token_ids=None,
-                           min_tokens: int = 0, grammar=None, constrain_draft: bool = False) -> SimpleNamespace:
+                           min_tokens: int = 0, grammar=None, constrain_draft: bool = False,
+                           min_p=None) -> SimpleNamespace:
     """benchmark_dynamic_schedule.py:260-272 signature; returns the namespace of :425-434 (+ replayed_cycles).
+    min_p: as dflash_generate (the target's draw; the draft's own draw stays unfiltered).
     grammar: as dflash_generate (the target's rows; the draft's own draw stays unconstrained; `grammar_state`).
     constrain_draft: as dflash_generate; this loop drafts at the request's temperature, so it needs temperature = 0
     (NotImplementedError for a sampled draft).
@@ -1158,7 +1183,7 @@ def dflash_generate_policy(*, model, target, input_ids: torch.Tensor, mask_token
                    logprobs=logprobs, repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
                    frequency_penalty=frequency_penalty, logit_bias=logit_bias, allowed_token_ids=allowed_token_ids,
                    banned_token_ids=banned_token_ids, min_tokens=min_tokens, grammar=grammar,
-                   constrain_draft=constrain_draft)
+                   constrain_draft=constrain_draft, min_p=min_p)
     if fixed_block_size is not None:
         for row in r.cycle_trace:
             for k in ("tau_hat", "cycle_hat", "score_hat", "current_block_size", "adl_lgen_hat", "adl_lacc_hat",

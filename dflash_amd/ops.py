@@ -1026,6 +1026,81 @@ def logit_bias_rows(logits: torch.Tensor, bias: torch.Tensor, *, min_pos=0, stop
     return out
 
 
+def check_min_p(min_p) -> Optional[float]:
+    """Validate one request's min_p: None or 0 is off and returns None; a float in (0, 1] is
+    returned as a float.  A bool, a NaN or anything else raises ValueError."""
+    if min_p is None:
+        return None
+    if isinstance(min_p, (bool, str, bytes)) or torch.is_tensor(min_p):
+        raise ValueError(f"dflash_amd: min_p must be None or a number in [0, 1] (0 = off), got {min_p!r}")
+    try:
+        v = float(min_p)
+    except (TypeError, ValueError):
+        raise ValueError(f"dflash_amd: min_p must be None or a number in [0, 1] (0 = off), got {min_p!r}") from None
+    if not 0.0 <= v <= 1.0:     # a NaN fails both comparisons
+        raise ValueError(f"dflash_amd: min_p must be inside [0, 1] (0 = off), got {min_p!r}")
+    return v if v > 0.0 else None
+
+
+def min_p_log(min_p) -> float:
+    """float32(ln(min_p)) computed on the host, the L of dfl_min_p_rows; -inf for None / 0 (off)."""
+    import math
+    import numpy as np
+    v = check_min_p(min_p)
+    return -math.inf if v is None else float(np.float32(math.log(v)))
+
+
+def min_p_rows(logits: torch.Tensor, *, min_p=None, log_min_p: Optional[torch.Tensor] = None,
+               temperature: Optional[float] = None, inv_t: Optional[torch.Tensor] = None,
+               out: Optional[torch.Tensor] = None, row0: int = 0, nrows: Optional[int] = None, dyn=None,
+               nrows_dyn_word: int = -1, tiles_per_req: int = 1, kept: Optional[torch.Tensor] = None,
+               kept_off: int = 0) -> torch.Tensor:
+    """min_p-masked logits (dfl_min_p_rows) of materialised bf16 logits [rows <= 16, V] (one tile)
+    or [tiles, 16, V], unit inner stride; returns `out` (same shape and strides; None: a new buffer; the logits
+    themselves: in place).  Column v of a row stays iff (x_v - max) * invT >= ln(min_p) or x_v is the row's maximum; the
+    others become -inf.  Give min_p (a host value, check_min_p) or log_min_p (a device fp32 tensor of float32(ln(min_p))
+    per request slot, -inf: off), and temperature (a host value > 0) or inv_t (a device fp32 tensor of invT per slot; a
+    slot whose value is not > 0 is greedy: its rows are copied).  Rows of a tile as in sample_rows_nucleus.  kept (int32,
+    [tiles, n] or [n]): the number of columns the rule kept at kept[t, kept_off + m - row0]; a copied row reports V."""
+    assert logits.dim() in (2, 3) and logits.stride(-1) == 1 and logits.is_cuda and logits.dtype == BF16
+    if logits.dim() == 2:
+        assert logits.shape[0] <= 16, "one tile holds at most 16 rows"
+        tiles, tile_rows, tile_stride = 1, logits.shape[0], 16 * logits.stride(0)
+    else:
+        assert logits.shape[1] == 16
+        tiles, tile_rows, tile_stride = logits.shape[0], 16, logits.stride(0)
+    V, ld = logits.shape[-1], logits.stride(-2)
+    if nrows is None:
+        nrows = tile_rows - row0
+    assert 0 <= row0 and row0 + nrows <= tile_rows or nrows_dyn_word >= 0 and tile_rows == 16
+    n_out = 16 - row0 if nrows_dyn_word >= 0 else nrows
+    if out is None:
+        out = torch.empty_strided(logits.shape, logits.stride(), dtype=BF16, device=logits.device)
+    assert out.shape == logits.shape and out.stride() == logits.stride() and out.dtype == BF16 and out.is_cuda, "out"
+    slots = (tiles + tiles_per_req - 1) // tiles_per_req
+    if (min_p is None) == (log_min_p is None):
+        raise ValueError("min_p_rows: give either min_p or log_min_p")
+    if (temperature is None) == (inv_t is None):
+        raise ValueError("min_p_rows: give either temperature or inv_t")
+    if log_min_p is not None:
+        assert torch.is_tensor(log_min_p) and log_min_p.numel() >= slots, "log_min_p"
+    if inv_t is not None:
+        assert torch.is_tensor(inv_t) and inv_t.numel() >= slots, "inv_t"
+    kept_stride = 0
+    if kept is not None:
+        assert kept.stride(-1) == 1 and kept.shape[-1] >= kept_off + n_out, "kept"
+        assert kept.dim() == 2 and kept.shape[0] >= tiles or kept.dim() == 1 and tiles == 1, "kept"
+        kept_stride = kept.stride(0) if kept.dim() == 2 else 0
+    if dyn is not None:
+        assert dyn.numel() >= 8 * tiles
+    check(lib().dfl_min_p_rows(logits.data_ptr(), out.data_ptr(), ld, tile_stride, tiles, V, row0, nrows,
+                               _p(dyn, I32, "dyn"), nrows_dyn_word, tiles_per_req, _p(log_min_p, F32, "log_min_p"),
+                               0.0 if log_min_p is not None else min_p_log(min_p),
+                               _p(inv_t, F32, "inv_t"), 0.0 if inv_t is not None else inv_temperature(temperature),
+                               _p(kept, I32, "kept"), kept_stride, kept_off, _stream()), "dfl_min_p_rows")
+    return out
+
+
 I16 = torch.int16
 
 

@@ -134,6 +134,7 @@ class NativeTarget:
         self._wide = None
         self._wide_seed = None    # int64 [1]: the seed of an fp8 target's sampled wide head (dfl_gemm_sample_batch on e4m3 codes)
         self._nuc_logits = None   # bf16 [32, V], made on the first filtered verify (top_k / top_p)
+        self._mp_logits = None    # bf16 [32, V], made on the first verify with min_p
         self.moe_pair_kernel = True   # MoE gate/up at K <= 2048 through dfl_moe_gate_up (False: the general kernel)
         self.moe_shared_pass = True   # three or four tiles (ragged batch, candidates): one pass over the experts they share
         self.moe_shared_min = 2       # tiles from which the shared pass is taken (30B-A3B layer: 2 tiles 291 -> 216 us, 4: 576 -> 241)
@@ -712,8 +713,15 @@ class NativeTarget:
             self._nuc_logits = torch.zeros(32, self.V, dtype=BF16, device=self._dev)
         return self._nuc_logits
 
+    def _min_p_logits(self) -> torch.Tensor:
+        """bf16 [32, V]: the min_p-masked rows the draw reads (kept: a captured cycle replays into it); the raw rows stay
+        where the head launch wrote them, for logprobs."""
+        if self._mp_logits is None:
+            self._mp_logits = torch.zeros(32, self.V, dtype=BF16, device=self._dev)
+        return self._mp_logits
+
     def _verify_wide(self, block_ids, start, cache, bs, tap_layers, taps, logits_out, temperature, cos, sin, seed=None,
-                     flt=None, logprobs=None):
+                     flt=None, logprobs=None, mp=None):
         """Blocks of 17..32 rows in ONE pass over the weights: the two 16-row tiles go through the ragged-batch
         GEMMs (tile_stack.TileStack, R = 2) as if they were two requests, and through ONE attention launch per layer with
         two query tiles on the request's single cache.  Same lines as verify(): model/dflash.py:249-257."""
@@ -773,7 +781,12 @@ class NativeTarget:
         ops.gemm_argmax_batch(self.tile_head(), s["xn"], R, self.V, H, 0, 16, gws, post.view(2, 16), 0, dyn2,
                               nrows_dyn_word=ops.DYN_BS, logits=lv)
         if flt is not None:   # the filtered draw, host-position form: tile t row m -> start + 16 t + m + 1
-            ops.sample_rows_nucleus(logits.view(2, 16, self.V), seed=seed, temperature=temperature, dyn=dyn2,
+            rows = logits
+            if mp is not None:
+                rows = ops.min_p_rows(logits.view(2, 16, self.V), min_p=mp, temperature=temperature,
+                                      out=self._min_p_logits().view(2, 16, self.V), dyn=dyn2,
+                                      nrows_dyn_word=ops.DYN_BS, tiles_per_req=2)
+            ops.sample_rows_nucleus(rows.view(2, 16, self.V), seed=seed, temperature=temperature, dyn=dyn2,
                                     nrows_dyn_word=ops.DYN_BS, pos_base=start, pos_add=1, tiles_per_req=2,
                                     out=post.view(2, 16), **flt)
             posterior = post[:bs].unsqueeze(0)
@@ -800,7 +813,8 @@ class NativeTarget:
     def verify(self, block_ids: torch.Tensor, start: int, cache: TargetKVCache, *, tap_layers: Sequence[int] = (),
                temperature: float = 0.0, logits_out: Optional[torch.Tensor] = None,
                taps_out: Optional[torch.Tensor] = None, dyn_lengths: bool = False, seed: Optional[int] = None,
-               top_k: int = 0, top_p: float = 1.0, logprobs=None, penalties=None, logit_bias=None, grammar=None):
+               top_k: int = 0, top_p: float = 1.0, logprobs=None, penalties=None, logit_bias=None, grammar=None,
+               min_p=None):
         """block_ids int64 [bs] at positions start..start+bs-1 (cache rows alike), bs <= 32.
         Returns (posterior ids int64 [1, bs], taps bf16 [32, len(tap_layers)*H] or None).
         K/V of all bs rows are written; the caller crops to what it accepts.
@@ -839,8 +853,22 @@ class NativeTarget:
         dfl_grammar_rows writes the masked rows into .logits — row j walks the slot's state through block_ids[1 .. j] and
         sets what is illegal where it arrives to -inf; a row whose walk dies is copied — and their argmax into the
         posterior; the penalties, then the draw, run over those rows; logprobs stay those of the raw rows (DESIGN.md
-        section 15)."""
+        section 15).
+        min_p (with seed, temperature > 0; None / 0: off, and nothing here changes; at temperature 0 it does nothing,
+        the maximum is always kept): directly in front of the draw dfl_min_p_rows writes the rows with every column
+        below min_p times the top token's probability set to -inf into a buffer of the target's own, and
+        dfl_sample_rows_nucleus draws over those (filters off: the plain seeded draw); blocks of up to 32 rows;
+        logprobs stay those of the raw rows; a logits_out given with it has a row stride of V, as that buffer has
+        (ValueError otherwise)."""
         bs = block_ids.numel()
+        mp = ops.check_min_p(min_p)
+        if temperature < 1e-5:
+            mp = None
+        if mp is not None and seed is None:
+            raise ValueError("min_p at temperature > 0 needs the seeded draw (seed=...)")
+        if mp is not None and logits_out is not None and (logits_out.dim() != 2 or logits_out.stride(0) != self.V):
+            raise ValueError("min_p needs logits_out with a row stride of V: the masked rows go to a buffer of the "
+                             "target's own, laid out like the rows they are made from")
         if grammar is not None:
             if bs > 16:
                 raise NotImplementedError("NativeTarget.verify: a grammar takes blocks of <= 16 rows")
@@ -861,6 +889,8 @@ class NativeTarget:
             if seed is None:
                 raise ValueError("top_k / top_p at temperature > 0 need the seeded draw (seed=...)")
             flt = dict(top_k=int(top_k), top_p=float(top_p))
+        if mp is not None and flt is None:   # the draw over the masked rows: filters off is the plain seeded draw
+            flt = dict(top_k=0, top_p=1.0)
         if self.wide_hidden:
             raise NotImplementedError("NativeTarget.verify: hidden > 4096 runs through the ragged-batch path "
                                       "(dflash_generate / dflash_generate_batch / BatchedDecoder)")
@@ -903,7 +933,7 @@ class NativeTarget:
         head = self.lm_wp8 if w8 else self.lm_wp
         if len(tiles) == 2 and self.wide_one_pass and self.attn_impl == "head":
             return self._verify_wide(block_ids, start, cache, bs, tap_layers, taps, logits_out, temperature, cos, sin, seed,
-                                     flt, logprobs)
+                                     flt, logprobs, mp)
         rs = self.rows
         for t, dt in tiles:
             ops.embed_rows(self.embed, block_ids[16 * t:], rs.h_tiles[t], H, rs.ss_emb[16 * t:], dt, ops.DYN_BS)
@@ -956,6 +986,8 @@ class NativeTarget:
                 ops.penalty_rows(rows, pen.table, repetition_penalty=pen.r, presence_penalty=pen.a,
                                  frequency_penalty=pen.f, block=block_ids, out=pen.logits, nrows=bs, out_ids=post[:16])
                 rows = pen.logits
+            if mp is not None:
+                rows = ops.min_p_rows(rows, min_p=mp, temperature=temperature, out=self._min_p_logits()[:16], nrows=bs)
             if temperature >= 1e-5:
                 ops.sample_rows_nucleus(rows, seed=seed, temperature=temperature, nrows=bs, dyn=dt,
                                         out=post[:16], **pos, **(flt or dict(top_k=0, top_p=1.0)))
@@ -970,7 +1002,11 @@ class NativeTarget:
                 n = min(16, bs - 16 * t)
                 ops.gemm_argmax(head, fin[t], self.V, H, 0, n, ws["argmax_ws"], post, 16 * t, dyn=dt,
                                 logits=logits[16 * t:16 * t + 16])
-                ops.sample_rows_nucleus(logits[16 * t:16 * t + 16], seed=seed, temperature=temperature, nrows=n, dyn=dt,
+                rows = logits[16 * t:16 * t + 16]
+                if mp is not None:
+                    rows = ops.min_p_rows(rows, min_p=mp, temperature=temperature,
+                                          out=self._min_p_logits()[16 * t:16 * t + 16], nrows=n)
+                ops.sample_rows_nucleus(rows, seed=seed, temperature=temperature, nrows=n, dyn=dt,
                                         pos_word=ops.DYN_POS0 if dyn_lengths else -1, pos_base=start, pos_add=16 * t + 1,
                                         out=post[16 * t:16 * t + 16], **flt)
             if logprobs is not None:

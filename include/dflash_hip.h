@@ -589,6 +589,27 @@ int dfl_logit_bias_rows(const void *logits, void *out, int64_t ld, int64_t tile_
                         int pos_word, int pos_base, int pos_add, int64_t *out_ids, int64_t out_stride, int out_off,
                         void *stream);
 
+/* min_p: a probability floor relative to the top token.  logits / out / ld / tile_stride / tiles /
+ * V / row0 / nrows / dyn / nrows_dyn_word / tiles_per_req exactly as dfl_penalty_rows takes them; out may be the logits
+ * themselves; rows past a tile's valid count return at once and write nothing.  Row m of tile t belongs to slot
+ * q = t / tiles_per_req.  L = log_min_p_dev[q] and invT = inv_t_dev[q] (device fp32 by slot), or the host values beside
+ * them when the array is NULL; L = float32(ln(min_p)) from the host, -inf for min_p = 0.  x being the row's bf16 logits
+ * widened to fp32, in fp32 IEEE operations each rounded once, never contracted:
+ *   m   = max over the entries of x that are not NaN                  (-0 == +0)
+ *   d_v = (x_v - m) * invT
+ *   z_v = (x_v == m or d_v >= L) ? x_v : -inf                         (the bits of x copied; a NaN x_v keeps its bits too)
+ * which is exp(invT (x_v - m)) >= min_p, p_v >= min_p * p_max on the tempered distribution.  The maximum is always kept:
+ * the row's argmax (lowest column on ties) does not move.  A row is copied whole, bit for bit, when its slot is off
+ * (L is -inf, > 0 or NaN), when its slot is greedy (invT not > 0) or when m is not finite (+inf, or no entry that is not
+ * NaN or -inf).  Host values are validated (log_min_p <= 0, -inf allowed; inv_t in (0, 1e5]); device values are not: every
+ * bit pattern is defined above.  kept_out (optional, int32): kept_out[t * kept_stride + kept_off + (m - row0)] = the
+ * number of columns with x_v == m or d_v >= L (a NaN is not counted); a row that is copied whole reports V.  No atomics:
+ * the same inputs give the same bits, eager or replayed. */
+int dfl_min_p_rows(const void *logits, void *out, int64_t ld, int64_t tile_stride, int tiles, int V, int row0, int nrows,
+                   const int32_t *dyn, int nrows_dyn_word, int tiles_per_req, const float *log_min_p_dev, float log_min_p,
+                   const float *inv_t_dev, float inv_t, int32_t *kept_out, int64_t kept_stride, int kept_off,
+                   void *stream);
+
 /* Grammar-constrained decoding: a token automaton.  The state is a POOL, int16
  * [pool_states][table_stride >= V] (rows on 16 bytes, table_stride a multiple of 8), holding several grammars at different
  * base rows: table[(base + s) * table_stride + v] >= 0 is the state, relative to base, after token v in state s; < 0: v is
