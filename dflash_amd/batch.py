@@ -28,6 +28,7 @@ import torch
 from . import ops
 from .generate import (NO_LOGPROBS, _bf16_table, _draw_rows, _kept_cols, _taps, _trim, capture_graph, cuda_time,
                        logprob_fields, resolve_seed)
+from .logits_stage import LogitsStage, check_features
 from .model import DFlashDraftModel
 from .target import NativeTarget
 from .tile_stack import TileStack, gemm_ws
@@ -57,41 +58,23 @@ class BatchedDecoder:
                  draft_temperature: float = 0.0, filtering: bool = False, request_temperature: bool = False,
                  logprobs: Optional[int] = None, penalties: bool = False, logit_bias: bool = False,
                  grammar_states: int = 0, constrain_draft: bool = False, min_p: bool = False):
-        """min_p (fixed here for the same reason as filtering: it fixes the captured launch sequence): requests may
-        carry a min_p (admit); every sampling verify materialises its logits and, directly in front of the draw,
-        dfl_min_p_rows writes each slot's rows masked by its own ln(min_p), read by address from log_min_ps beside
-        inv_ts, into a buffer of their own.  A slot at 0 (-inf) has its rows copied and gets the
-        ids of a decoder built without it; a greedy decoder enqueues nothing new.
-        constrain_draft (fixed here for the same reason as grammar_states: it fixes the captured launch sequence; needs
-        grammar_states > 0 or logit_bias, one tile per request and a greedy draft): the draft's head launch materialises
-        its logits and ONE dfl_grammar_draft_rows launch over all tiles re-picks every slot's draft tokens under its
-        automaton and its bans ("The draft under the grammar").  A slot without a grammar and
-        without bans keeps its argmax ids.
-        grammar_states = N (0: off; fixed here, it fixes the captured launch sequence and the pool's address): a pool
-        of N automaton rows that add_grammar fills; requests may carry a grammar handle (admit); every verify
-        materialises its logits and dfl_grammar_rows masks each slot's rows by the state their prefix of the block
-        reaches, between the logit bias and the penalties, and dfl_grammar_advance steps the slots' states behind the
-        accept launch.  A slot without a grammar gets the ids of a decoder built without it.
-        logprobs = N (None: off; fixed here, it fixes the captured launch sequence): every verify materialises its
-        logits and dfl_logprob_rows scatters the log-probability of each committed token, and the top N alternatives, to
-        the token's position in the slot's row of self.lp.
-        penalties (fixed here for the same reason): requests may carry repetition / presence / frequency penalties
-        (admit); every verify materialises its logits, dfl_penalty_rows writes each slot's penalised rows and their
-        argmax, the draw runs over the penalised rows, and dfl_penalty_count keeps the slots' table rows behind the
-        accept launch.  A slot with neutral values gets the ids of a decoder built without it.
-        logit_bias (fixed here for the same reason): requests may carry logit_bias / allowed_token_ids / banned_token_ids
-        / min_tokens (admit); every verify materialises its logits and dfl_logit_bias_rows writes each slot's biased rows
-        and their argmax from the slot's table row and min_pos, ahead of the penalties and the draw.
-        A slot with neutral values has a zero row and min_pos = 0 and gets the ids of a decoder built without it."""
+        """filtering / logprobs / penalties / logit_bias / grammar_states / min_p: which row processors the verify runs
+        between its head launch and the posterior (logits_stage.LogitsStage has the order, what each reads and the
+        DESIGN.md sections).  Fixed here: they fix the captured launch sequence and the addresses it reads.  Requests
+        carry their own values (admit); a slot at the neutral values gets the ids of a decoder built without the
+        feature, and a greedy decoder enqueues neither min_p nor a draw.  grammar_states = N: a pool of N automaton rows
+        that add_grammar fills.
+        constrain_draft (fixed here for the same reason; needs grammar_states > 0 or logit_bias, one tile per request and
+        a greedy draft): the draft's head launch materialises its logits and ONE dfl_grammar_draft_rows launch over all
+        tiles re-picks every slot's draft tokens under its automaton and its bans ("The draft under
+        the grammar").  A slot without a grammar and without bans keeps its argmax ids."""
         logprobs = ops.check_logprobs(logprobs)
         grammar_states = int(grammar_states)
         if grammar_states < 0:
             raise ValueError(f"grammar_states must be >= 0 (0: off), got {grammar_states}")
-        if grammar_states and tiles_per_request != 1:
-            raise NotImplementedError("grammar takes blocks of <= 16 rows (tiles_per_request = 1)")
-        if grammar_states and temperature >= 1e-5 and sampler != "device":
-            raise ValueError("grammar at T > 0 needs sampler='device' (sampler='torch' is the reference's multinomial over "
-                             "the raw logits)")
+        on = dict(min_p=min_p, grammar=grammar_states, logit_bias=logit_bias, penalties=penalties, filter=filtering)
+        check_features([f for f, v in on.items() if v], sampling=temperature >= 1e-5, seeded=sampler == "device",
+                       wide=tiles_per_request != 1)
         if constrain_draft:
             if not (grammar_states or logit_bias):
                 raise ValueError("constrain_draft needs something to constrain by: a decoder built with grammar_states > 0 "
@@ -101,19 +84,6 @@ class BatchedDecoder:
             if draft_temperature >= 1e-5:
                 raise NotImplementedError("constrain_draft takes a greedy draft (a sampled draft draws in the head "
                                           "launch's epilogue, before the pick)")
-        if logit_bias and tiles_per_request != 1:
-            raise NotImplementedError("logit_bias takes blocks of <= 16 rows (tiles_per_request = 1)")
-        if logit_bias and temperature >= 1e-5 and sampler != "device":
-            raise ValueError("logit_bias at T > 0 needs sampler='device' (sampler='torch' is the reference's multinomial "
-                             "over the raw logits)")
-        if penalties and tiles_per_request != 1:
-            raise NotImplementedError("penalties take blocks of <= 16 rows (tiles_per_request = 1)")
-        if penalties and temperature >= 1e-5 and sampler != "device":
-            raise ValueError("penalties at T > 0 need sampler='device' (sampler='torch' is the reference's multinomial over "
-                             "the raw logits)")
-        if min_p and temperature >= 1e-5 and sampler != "device":
-            raise ValueError("min_p at T > 0 needs sampler='device' (sampler='torch' is the reference's multinomial over "
-                             "the raw logits)")
         if not isinstance(target, NativeTarget):
             raise TypeError("BatchedDecoder needs a dflash_amd.NativeTarget (see module docstring)")
         if tiles_per_request not in (1, 2):
@@ -125,9 +95,6 @@ class BatchedDecoder:
         if draft_temperature >= 1e-5 and sampler != "device":
             raise NotImplementedError("a sampled draft in the ragged batch needs sampler='device'")
         resolve_seed(sampler, None, needed=False)   # (validates the name)
-        if filtering and temperature >= 1e-5 and sampler != "device":
-            raise ValueError("top_k / top_p at T > 0 need sampler='device' (sampler='torch' is the reference's unfiltered "
-                             "multinomial)")
         if request_temperature and sampler != "device":
             raise ValueError("request_temperature needs sampler='device': a slot's temperature is read by the seeded draw "
                              "on the device")
@@ -179,45 +146,26 @@ class BatchedDecoder:
         # then only the default of admit(): the verify runs the _t launch forms whatever it is.
         self.request_temperature = bool(request_temperature)
         self.inv_ts = z(NREQ, dt=F32) if self.request_temperature else None
-        self.filtering = bool(filtering) and (self.temperature >= 1e-5 or self.request_temperature)
-        self.top_k, self.top_p = z(NREQ, dt=I32), torch.ones(NREQ, dtype=F32, device=dev)
-        self.lp = ops.logprob_sink(NREQ, out_len, logprobs, dev) if logprobs is not None else None
-        # penalties: one table row per request slot (bit 31: seen in the prompt, bits 0..30: occurrences in the output),
-        # the slots' three values beside their seeds, and the buffer of the penalised rows (the raw ones stay for logprobs)
-        self.penalties = bool(penalties)
-        if self.penalties:
-            self.pen_table = ops.penalty_state(NREQ, target.V, dev)
-            self.pen_r, self.pen_a, self.pen_f = torch.ones(NREQ, dtype=F32, device=dev), z(NREQ, dt=F32), z(NREQ, dt=F32)
-            self._pen_logits = z(MT, 16, target.V)
-        # logit bias: one dense fp32 table row and one min_pos per request slot, rewritten whole on every admission, and
-        # the buffer of the biased rows
-        self.logit_bias = bool(logit_bias)
-        if self.logit_bias:
-            self.lb = ops.logit_bias_state(NREQ, target.V, dev)
-            self._lb_logits = z(MT, 16, target.V)
-        # grammar: the pool (its storage never moves: one capture serves every grammar loaded later), base / state per
-        # request slot (-1 / -1: no grammar), the grammars loaded so far (handle -> (base, dfa)) and the masked rows
-        self.grammar = None
-        if grammar_states:
-            self.grammar = ops.grammar_state(NREQ, grammar_states, target.V, dev)
-            self._grammars = []
-            self._gr_logits = z(MT, 16, target.V)
-        # min_p: one fp32 L = ln(min_p) per request slot beside inv_ts (-inf: off), rewritten on every admission and read
-        # by address, and the buffer of the masked rows; min_p_on: the decoder samples, so the launch is enqueued at all
-        self.min_p = bool(min_p)
-        self.min_p_on = self.min_p and (self.temperature >= 1e-5 or self.request_temperature)
-        if self.min_p:
-            self.log_min_ps = torch.full((NREQ,), float("-inf"), dtype=F32, device=dev)
-        if self.min_p_on:
-            self._mp_logits = z(MT, 16, target.V)
-        if (self.filtering or self.lp is not None or self.penalties or self.logit_bias or self.grammar is not None
-                or self.min_p_on):
-            self._logits = z(MT, 16, target.V)
+        sampling = self.temperature >= 1e-5 or self.request_temperature
+        self.filtering = bool(filtering) and sampling
+        self.stop_t = torch.tensor(stop_token_ids, dtype=I64, device=dev) if stop_token_ids else None
+        # the row processors' state and buffers, one slot per request slot, values read by address (None: nothing is on);
+        # the flags say what the decoder was built with (admit refuses a request that asks for more)
+        self.penalties, self.logit_bias, self.min_p = bool(penalties), bool(logit_bias), bool(min_p)
+        self.stage, self.grammar, self.lp = None, None, None
+        if self.filtering or logprobs is not None or penalties or logit_bias or grammar_states or min_p:
+            self.stage = LogitsStage(NREQ, target.V, dev, tiles=MT, device_values=True, out_len=out_len, logprobs=logprobs,
+                                     penalties=penalties, logit_bias=logit_bias, grammar_states=grammar_states,
+                                     min_p=min_p, filtering=filtering, sampling=sampling,
+                                     stop_ids=self.stop_t)
+            self.grammar, self.lp, self._grammars = self.stage.gr, self.stage.lp, []
+            self.pen_table = self.stage.pen_table   # (None without penalties)
+            if self.stage.materialises:   # where every head launch of such a decoder materialises its logits
+                self._logits = self.stage.raw.view(MT, 16, target.V)
         # constrain_draft: the draft head's materialised logits, read by the pick launch right behind it
         self.constrain_draft = bool(constrain_draft)
         self._cd_logits = z(MT, 16, target.V) if self.constrain_draft else None
         self.output_ids = torch.full((NREQ, out_len), self.mask_id, dtype=I64, device=dev)
-        self.stop_t = torch.tensor(stop_token_ids, dtype=I64, device=dev) if stop_token_ids else None
         self.stop_token_ids = list(stop_token_ids) if stop_token_ids else None
         # ---- draft scratch
         self.nqkv_d = c.q_dim + 2 * c.kv_dim
@@ -300,29 +248,19 @@ class BatchedDecoder:
         [P, fc_in], the seed written for the slot or None)."""
         m, t = self.model, self.target
         gr = self.check_grammar_handle(grammar)
-        if gr is not None and temperature >= 1e-5 and self.sampler != "device":
-            raise ValueError("admit: grammar at T > 0 needs sampler='device'")
         pen = ops.check_penalties(*penalties)
-        if pen is not None and not self.penalties:
-            raise ValueError("admit: penalties need a decoder built with penalties=True")
-        if pen is not None and temperature >= 1e-5 and self.sampler != "device":
-            raise ValueError("admit: penalties at T > 0 need sampler='device'")
         lb = self.check_bias(**bias) if bias else None
-        if lb is not None and temperature >= 1e-5 and self.sampler != "device":
-            raise ValueError("admit: logit_bias / allowed_token_ids / banned_token_ids / min_tokens at T > 0 need "
-                             "sampler='device'")
         if gr is not None and lb is not None:   # a reachable state whose legal tokens this request's bias bans all
             ops.check_grammar(gr[1], t.V, lb[0])
         flt = None
         if ops.check_filter(top_k, top_p) and temperature >= 1e-5:
-            if not self.filtering:
-                raise ValueError("admit: top_k / top_p need a decoder built with filtering=True (and sampler='device')")
             flt = dict(top_k=int(top_k), top_p=float(top_p))
         mp = ops.check_min_p(min_p)
-        if mp is not None and not self.min_p:
-            raise ValueError("admit: min_p needs a decoder built with min_p=True")
-        if mp is not None and temperature >= 1e-5 and self.sampler != "device":
-            raise ValueError("admit: min_p at T > 0 needs sampler='device'")
+        on = dict(min_p=mp is not None, grammar=gr is not None, logit_bias=lb is not None, penalties=pen is not None,
+                  filter=flt is not None)
+        check_features([f for f, v in on.items() if v], where="admit: ", sampling=temperature >= 1e-5,
+                       seeded=self.sampler == "device",
+                       built=dict(min_p=self.min_p, penalties=self.penalties, filter=self.filtering))
         if input_ids.shape[0] != 1 or not input_ids.is_cuda:
             raise ValueError("admit: input_ids must be a [1, P] GPU tensor")
         P = input_ids.shape[1]
@@ -337,52 +275,17 @@ class BatchedDecoder:
             self.embed_w = _bf16_table(t.model.embed_tokens.weight, self.dev)
         tc = _View(self.tk[r], self.tv[r], None, self.max_rows)
         out = t.prefill(input_ids, tc, output_hidden_states=True, tap_layers=self.model.target_layer_ids)
-        first_logits = out.logits[:, -1:]
-        if self.logit_bias:   # the slot's whole table row and min_pos = P + min_tokens are rewritten, whatever ran in the
-            # slot before (neutral values: zeros and 0); the prompt's last row predicts position P and takes them
-            ops.logit_bias_set(self.lb, r, lb[0] if lb else None, P + lb[1] if (lb and lb[1]) else 0)
-            first_logits = ops.logit_bias_rows(out.logits[0, -1:].to(BF16).contiguous(), self.lb.bias[r:r + 1],
-                                               min_pos=self.lb.min_pos[r:r + 1], stop_ids=self.stop_t,
-                                               pos_base=P).unsqueeze(0)
-        if self.grammar is not None:   # the slot's base and state are rewritten, whatever ran in the slot before (no
-            # grammar: -1 / -1, the rows pass unmasked); the prompt's last row is masked by the start state (no walk)
-            ops.grammar_set(self.grammar, r, gr[0] if gr else None, gr[1].start if gr else 0)
-            one = SimpleNamespace(table=self.grammar.table, base=self.grammar.base[r:r + 1],
-                                  state=self.grammar.state[r:r + 1])
-            first_logits = ops.grammar_rows(first_logits[0, -1:].to(BF16).contiguous(), one).unsqueeze(0)
-        if self.penalties:   # the slot's table row starts from the prompt alone, whatever ran in the slot before; the
-            # first token comes from the prompt's last row penalised by it (no block in front of it)
-            pr, pa, pf = pen or (1.0, 0.0, 0.0)
-            tab = self.pen_table[r:r + 1]
-            ops.penalty_count(tab, input_ids, lo=0, hi=P, as_prompt=True, clear=True)
-            first_logits = ops.penalty_rows(first_logits[0, -1:].to(BF16).contiguous(), tab, repetition_penalty=pr,
-                                            presence_penalty=pa, frequency_penalty=pf).unsqueeze(0)
-        if self.min_p:   # the slot's L for every later token, rewritten on every admission (-inf: off)
-            self.log_min_ps[r:r + 1].fill_(ops.min_p_log(mp))
         sd = None
         if self.sampler == "device" and (temperature >= 1e-5 or self.temperature >= 1e-5):
             sd = resolve_seed("device", seed)
-            if mp is not None and temperature >= 1e-5:   # the floor directly in front of the first token's draw
-                first_logits = ops.min_p_rows(first_logits[0, -1:].to(BF16).contiguous(), min_p=mp,
-                                              temperature=temperature).unsqueeze(0)
-                flt = flt or dict(top_k=0, top_p=1.0)
-            first = (_draw_rows(first_logits, temperature, sd, P, flt) if temperature >= 1e-5
-                     else sample(first_logits, 0.0))
+        if self.stage is not None:   # the slot's values, rewritten whatever ran in the slot before, and the first token
+            first = self.stage.admit(r, out.logits[0, -1:], input_ids, P, temperature=temperature, seed=sd, penalties=pen,
+                                     bias=(lb[0], P + lb[1] if lb[1] else 0) if lb else None,
+                                     grammar=(gr[0], gr[1].start) if gr else None, min_p=mp, flt=flt)
+        elif sd is not None and temperature >= 1e-5:
+            first = _draw_rows(out.logits[:, -1:], temperature, sd, P)
         else:
-            first = sample(first_logits, temperature)
-        if self.penalties:   # the first token is output; the slot's three values, re-armed on every admission
-            ops.penalty_count(tab, first.reshape(1, 1), lo=0, hi=1)
-            self.pen_r[r:r + 1].fill_(pr)
-            self.pen_a[r:r + 1].fill_(pa)
-            self.pen_f[r:r + 1].fill_(pf)
-        if self.grammar is not None:   # the first token is output: the slot's state steps over it
-            ops.grammar_advance(one, first.reshape(1, 1), lo=0, hi=1)
-        if self.lp is not None:   # the first token's value, from the prompt's last-row logits: nothing is read back
-            sink = SimpleNamespace(**{**vars(self.lp), "slot": r})
-            ops.logprob_rows(out.logits[0, -1:].to(BF16).contiguous(), first.reshape(1), sink, pos_base=P)
-        # the slot's filter, re-armed on every admission (0 / 1.0: off); two small fills, admissions are never captured
-        self.top_k[r:r + 1].fill_(flt["top_k"] if flt else 0)
-        self.top_p[r:r + 1].fill_(flt["top_p"] if flt else 1.0)
+            first = sample(out.logits[:, -1:], temperature)
         if self.request_temperature:   # the slot's invT for every later token; 0: greedy
             self.inv_ts[r:r + 1].fill_(ops.inv_temperature(temperature) if temperature >= 1e-5 else 0.0)
         th = _taps(out.hidden_states, m.target_layer_ids)[0]          # [P, fc_in]
@@ -608,7 +511,7 @@ class BatchedDecoder:
                 # every slot's block[1:BS] re-picked under its automaton and its bans, from the state dfl_grammar_advance
                 # left behind the last accept launch (a run-ahead head is enqueued behind _accept_launch: the new state);
                 # in front of the hook.  A slot with base < 0 and a bias row without bans keeps the argmax ids
-                ops.grammar_draft_rows(self._cd_logits[:R], self.grammar, bias=self.lb.bias if self.logit_bias else None,
+                ops.grammar_draft_rows(self._cd_logits[:R], self.grammar, bias=self.stage.lb.bias if self.logit_bias else None,
                                        block=self.block, dyn=self.dyn_tt, nrows_dyn_word=ops.DYN_BS)
         else:   # row 0 of a request's SECOND tile is a draft row: all 16 rows of every tile, row 0 of the block dropped here
             lm = self._lm8() or self.lm_wp
@@ -631,45 +534,20 @@ class BatchedDecoder:
                tap_layers=self.model.target_layer_ids, moe=t.moe_mlp_tiles)
         st.finish(t.norm)
         lm = self._t_head()
+        stage = self.stage
         lg = self._logits if self.lp is not None else None   # logprobs: every head below materialises its logits
-        if self.penalties or self.logit_bias or self.grammar is not None or self.min_p_on:
-            # materialise; each slot's biased rows (row m predicts position POS0 + m + 1), then its grammar-masked rows
-            # (row m by the slot's state walked through block[1 .. m]), then its penalised rows, each
-            # launch with the rows' argmax (what a greedy slot keeps); the draw over the last of them at the slot's seed /
-            # top_k / top_p / invT; logprobs below read the raw rows
+        # tile j row m of a slot predicts (and, if accepted, commits at) position POS0 + 16 j + m + 1
+        where = dict(dyn=dyn_t, nrows_dyn_word=ops.DYN_BS, pos=dict(pos_word=ops.DYN_POS0, pos_add=1), tiles_per_req=TPR)
+        if stage is not None and stage.processes:
+            # materialise, then the stage's launches over every slot's rows at its own values; a greedy slot keeps the
+            # argmax ids the launches before the draw wrote
             ops.gemm_argmax_batch(lm, s["xn"], R, t.V, H, 0, 16, self.gws, self.post.view(-1, 16), 0, dyn_t,
                                   nrows_dyn_word=ops.DYN_BS, logits=self._logits)
-            rows = self._logits[:R]
-            if self.logit_bias:
-                ops.logit_bias_rows(rows, self.lb.bias, min_pos=self.lb.min_pos, stop_ids=self.stop_t,
-                                    out=self._lb_logits[:R], dyn=dyn_t, nrows_dyn_word=ops.DYN_BS, pos_word=ops.DYN_POS0,
-                                    pos_add=1, out_ids=self.post.view(-1, 16))
-                rows = self._lb_logits[:R]
-            if self.grammar is not None:
-                ops.grammar_rows(rows, self.grammar, block=self.block, out=self._gr_logits[:R], dyn=dyn_t,
-                                 nrows_dyn_word=ops.DYN_BS, out_ids=self.post.view(-1, 16))
-                rows = self._gr_logits[:R]
-            if self.penalties:
-                ops.penalty_rows(rows, self.pen_table, repetition_penalty=self.pen_r, presence_penalty=self.pen_a,
-                                 frequency_penalty=self.pen_f, block=self.block, out=self._pen_logits[:R], dyn=dyn_t,
-                                 nrows_dyn_word=ops.DYN_BS, out_ids=self.post.view(-1, 16))
-                rows = self._pen_logits[:R]
+            draw = None
             if self.request_temperature or self.temperature >= 1e-5:
-                tkw = dict(inv_t=self.inv_ts) if self.request_temperature else dict(temperature=self.temperature)
-                if self.min_p_on:   # directly in front of the draw: each slot's rows under its own L (-inf: copied), at
-                    # the invT the draw uses; the masked rows go to a buffer of their own
-                    ops.min_p_rows(rows, log_min_p=self.log_min_ps, out=self._mp_logits[:R], dyn=dyn_t,
-                                   nrows_dyn_word=ops.DYN_BS, tiles_per_req=TPR, **tkw)
-                    rows = self._mp_logits[:R]
-                ops.sample_rows_nucleus(rows, seed=self.seeds, top_k=self.top_k, top_p=self.top_p,
-                                        dyn=dyn_t, nrows_dyn_word=ops.DYN_BS, pos_word=ops.DYN_POS0, pos_add=1,
-                                        tiles_per_req=TPR, out=self.post.view(-1, 16), **tkw)
-        elif self.request_temperature and self.filtering:   # greedy slots keep the argmax ids the first launch wrote
-            ops.gemm_argmax_batch(lm, s["xn"], R, t.V, H, 0, 16, self.gws, self.post.view(-1, 16), 0, dyn_t,
-                                  nrows_dyn_word=ops.DYN_BS, logits=self._logits)
-            ops.sample_rows_nucleus(self._logits[:R], seed=self.seeds, top_k=self.top_k, top_p=self.top_p,
-                                    inv_t=self.inv_ts, dyn=dyn_t, nrows_dyn_word=ops.DYN_BS, pos_word=ops.DYN_POS0,
-                                    pos_add=1, tiles_per_req=TPR, out=self.post.view(-1, 16))
+                draw = dict(seed=self.seeds, **(dict(inv_t=self.inv_ts) if self.request_temperature
+                                                else dict(temperature=self.temperature)))
+            stage.rows(self._logits[:R], self.block, self.post.view(-1, 16), draw=draw, **where)
         elif self.request_temperature:   # the fused draw at each slot's own invT; a greedy slot takes the plain argmax
             ops.gemm_sample_batch(lm, s["xn"], R, t.V, H, 0, 16, self.gws, self.post.view(-1, 16), 0, dyn_t,
                                   seeds=self.seeds, inv_ts=self.inv_ts, pos_word=ops.DYN_POS0, pos_add=1,
@@ -677,12 +555,6 @@ class BatchedDecoder:
         elif self.temperature < 1e-5:
             ops.gemm_argmax_batch(lm, s["xn"], R, t.V, H, 0, 16, self.gws, self.post.view(-1, 16), 0, dyn_t,
                                   nrows_dyn_word=ops.DYN_BS, logits=lg)
-        elif self.filtering:   # materialise, then the filtered draw: tile j row m -> start + 16 j + m + 1
-            ops.gemm_argmax_batch(lm, s["xn"], R, t.V, H, 0, 16, self.gws, self.post.view(-1, 16), 0, dyn_t,
-                                  nrows_dyn_word=ops.DYN_BS, logits=self._logits)
-            ops.sample_rows_nucleus(self._logits[:R], seed=self.seeds, top_k=self.top_k, top_p=self.top_p,
-                                    temperature=self.temperature, dyn=dyn_t, nrows_dyn_word=ops.DYN_BS,
-                                    pos_word=ops.DYN_POS0, pos_add=1, tiles_per_req=TPR, out=self.post.view(-1, 16))
         elif self.sampler == "device":   # the seeded draw in the lm_head epilogue: tile j row m -> start + 16 j + m + 1
             ops.gemm_sample_batch(lm, s["xn"], R, t.V, H, 0, 16, self.gws, self.post.view(-1, 16), 0, dyn_t,
                                   seeds=self.seeds, temperature=self.temperature, pos_word=ops.DYN_POS0, pos_add=1,
@@ -696,21 +568,15 @@ class BatchedDecoder:
             ops.gemm_argmax_batch(lm, s["xn"], R, t.V, H, 0, 16, self.gws, self.post, 0, dyn_t,
                                   nrows_dyn_word=ops.DYN_BS, logits=self._logits)
             self.post[:R] = sample(self._logits[:R], self.temperature)
-        if self.lp is not None:   # behind whichever branch wrote the posterior, before the accept launch moves POS0:
-            # tile j row m of a slot commits (if accepted) at position POS0 + 16 j + m + 1
-            ops.logprob_rows(self._logits[:R], self.post.view(-1, 16), self.lp, dyn=dyn_t, nrows_dyn_word=ops.DYN_BS,
-                             pos_word=ops.DYN_POS0, pos_add=1, tiles_per_req=TPR)
+        if self.lp is not None:   # behind whichever branch wrote the posterior, before the accept launch moves POS0
+            stage.logprobs(self._logits[:R], self.post.view(-1, 16), **where)
 
     def _accept_launch(self) -> None:
         ops.accept_commit_batch(self.block, self.post, self.R, self.output_ids, self.dyn_d, self.dyn_t, self.stop_t,
                                 self.result, rearm_mask_id=self.mask_id, tiles_per_req=self.TPR,
                                 dyn_d_tiles=self.dyn_dt, dyn_t_tiles=self.dyn_tt)
-        if self.penalties:   # what the launch committed, output_ids(S, START] of each live slot; a parked slot is idle
-            ops.penalty_count(self.pen_table[:self.R], self.output_ids, dyn=self.dyn_d, lo_word=ops.DYN_S,
-                              hi_word=ops.DYN_START, lo=1, hi=1)
-        if self.grammar is not None:   # the same range steps each live slot's automaton state
-            ops.grammar_advance(self.grammar, self.output_ids, slots=self.R, dyn=self.dyn_d, lo_word=ops.DYN_S,
-                                hi_word=ops.DYN_START, lo=1, hi=1)
+        if self.stage is not None:
+            self.stage.commit(self.output_ids, self.dyn_d, self.R)
 
     def accept(self, launch: bool = True) -> list:
         """Acceptance scan + commit + rollback bookkeeping of all requests (:258-268) and

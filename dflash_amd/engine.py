@@ -18,6 +18,7 @@ from . import ops
 from .batch import (MAX_GROUP, BatchedDecoder, _load_grammars, _pool_rows, _prompt_bias, _prompt_filters,
                     _prompt_grammars, _prompt_min_p, _prompt_penalties, _prompt_seeds, _prompt_temperatures)
 from .generate import NO_LOGPROBS, _kept_cols, _trim, cuda_time, logprob_fields
+from .logits_stage import check_features
 from .slots import SlotLoop
 
 BLOCK_ROWS = 16   # rows of a slot's tile: the margins below are the ones dflash_generate_batch sizes its decoder with
@@ -130,29 +131,16 @@ class BatchEngine:
                  graph: Optional[bool] = None, filtering: bool = False, request_temperature: bool = False,
                  logprobs: Optional[int] = None, penalties: bool = False, logit_bias: bool = False,
                  grammar_states: int = 0, constrain_draft: bool = False, min_p: bool = False):
-        """min_p: requests may carry a min_p (submit); fixed here because it fixes the captured launch sequence
-        (DESIGN.md section 18).  A slot's ln(min_p) is rewritten on every admission and read by address by the captured
-        launch; requests at 0 emit the same ids, and a greedy engine enqueues nothing new.
-        constrain_draft: every slot's draft tokens are re-picked under its grammar and its bans right behind the draft's
-        head launch ("The draft under the grammar"); fixed here because it fixes the captured
-        launch sequence; needs grammar_states > 0 or logit_bias=True (ValueError).  The emitted ids do not change; a
-        request without a grammar and without bans keeps its argmax draft.
-        grammar_states = N (0: off): a pool of N automaton rows; add_grammar loads a TokenDFA into it and returns the
-        handle submit takes.  Fixed here because it fixes the captured launch sequence; the pool's
-        address is fixed too, so the one capture serves grammars loaded later.  Requests without a grammar emit the same
-        ids; results carry `grammar_state`.
-        logprobs = N (None: off): every result carries logprobs / top_logprob_ids / top_logprobs as dflash_generate
-        returns them; fixed here, one capture per engine — there is no per-request switch.
-        filtering: requests may carry top_k / top_p (submit); fixed here because it fixes the captured launch sequence
-        ("Filtered draw").  Unfiltered requests of such an engine emit the same ids.
-        request_temperature: requests may carry their own temperature (submit), greedy and sampled ones sharing the
-        weight pass and the one capture; fixed here for the same reason, needs sampler='device' (DESIGN.md section 8,
-        "Per-request temperature").  `temperature` is then the default of submit.
-        penalties: requests may carry repetition / presence / frequency penalties (submit); fixed here because it fixes
-        the captured launch sequence.  Neutral requests of such an engine emit the same ids.
-        logit_bias: requests may carry logit_bias / allowed_token_ids / banned_token_ids / min_tokens (submit); fixed
-        here for the same reason.  A slot's table row and min_pos are rewritten whole on every
-        admission: nothing of the slot's previous request survives, and neutral requests emit the same ids."""
+        """filtering / request_temperature / logprobs / penalties / logit_bias / grammar_states / constrain_draft / min_p:
+        as BatchedDecoder takes them — what requests may carry (submit); fixed here because they fix the one captured
+        launch sequence of the engine's life (logits_stage.LogitsStage has the row processors' order and the DESIGN.md
+        sections).  A slot's values are rewritten whole on every admission and read by address by the captured launches:
+        nothing of the slot's previous request survives, and requests at the neutral values emit the same ids.
+        logprobs = N: every result carries logprobs / top_logprob_ids / top_logprobs; there is no per-request switch.
+        grammar_states = N: add_grammar loads a TokenDFA into the pool and returns the handle submit takes; the pool's
+        address is fixed, so the one capture serves grammars loaded later; results carry `grammar_state`.
+        request_temperature: greedy and sampled requests share the weight pass and the capture; needs sampler='device';
+        `temperature` is then the default of submit."""
         if not 1 <= block_size <= 32:
             raise ValueError("block_size is 1..32")
         if block_size > BLOCK_ROWS:
@@ -206,8 +194,6 @@ class BatchEngine:
         if grammar is not None:   # (raises on a handle this engine did not return, and on an engine without a pool)
             self.dec.check_grammar_handle(grammar)
         pen = ops.check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
-        if pen is not None and not self.penalties:
-            raise ValueError("submit: penalties need an engine built with penalties=True")
         bias = dict(logit_bias=logit_bias, allowed_token_ids=allowed_token_ids, banned_token_ids=banned_token_ids,
                     min_tokens=min_tokens)
         if (logit_bias is None and allowed_token_ids is None and banned_token_ids is None and min_tokens == 0) \
@@ -219,12 +205,10 @@ class BatchEngine:
         if T != self.temperature and not self.request_temperature:
             raise ValueError("submit: a temperature other than the engine's needs an engine built with "
                              "request_temperature=True")
-        if ops.check_filter(top_k, top_p) and T >= 1e-5 and not self.filtering:
-            raise ValueError("submit: top_k / top_p need an engine built with filtering=True")
-        if mp is not None and not self.min_p:
-            raise ValueError("submit: min_p needs an engine built with min_p=True")
-        if mp is not None and T >= 1e-5 and self.dec.sampler != "device":
-            raise ValueError("submit: min_p at T > 0 needs sampler='device'")
+        on = dict(min_p=mp is not None, penalties=pen is not None, filter=ops.check_filter(top_k, top_p) and T >= 1e-5)
+        check_features([f for f, v in on.items() if v], where="submit: ", sampling=T >= 1e-5, owner="engine",
+                       seeded=mp is None or T < 1e-5 or self.dec.sampler == "device",   # (the rest: at the admission)
+                       built=dict(min_p=self.min_p, penalties=self.penalties, filter=self.filtering))
         check_fit(input_ids.shape[1], int(max_new_tokens), self.dec.max_rows, self.dec.out_len)
         req = self.loop.submit(input_ids.shape[1], int(max_new_tokens),
                                SimpleNamespace(input_ids=input_ids, seed=seed, hook=draft_token_hook, result=None,

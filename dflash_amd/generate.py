@@ -25,6 +25,7 @@ from typing import Callable, NamedTuple, Optional
 import torch
 
 from . import ops
+from .logits_stage import LogitsStage, check_features, draw_rows as _draw_rows
 from .utils import extract_context_feature, sample
 
 _TABLES = {}
@@ -136,20 +137,6 @@ def resolve_filter(top_k, top_p, temperature: float, sampler: str) -> Optional[d
     return dict(top_k=int(top_k), top_p=float(top_p))
 
 
-def _draw_rows(logits: torch.Tensor, temperature: float, seed: int, pos0: int, flt: Optional[dict] = None) -> torch.Tensor:
-    """The device sampler over materialised logits [1, T, V]: row j draws position pos0 + j (stream TARGET); flt: the
-    top_k / top_p of the filtered draw, one launch per 16-row tile."""
-    _, t, v = logits.shape
-    rows = logits.reshape(t, v)
-    if flt is None:
-        return ops.sample_rows(rows, seed=seed, temperature=temperature, pos0=pos0).view(1, t)
-    out = torch.empty(t, dtype=torch.long, device=logits.device)
-    for r0 in range(0, t, 16):
-        ops.sample_rows_nucleus(rows[r0:r0 + 16], seed=seed, temperature=temperature, pos_base=pos0 + r0, out=out[r0:r0 + 16],
-                                **flt)
-    return out.view(1, t)
-
-
 def _trim(output_ids, max_length, mask_token_id, stop_token_ids, n_in):
     """model/dflash.py:269-275."""
     output_ids = output_ids[:, :max_length]
@@ -209,60 +196,22 @@ class DecodeSession:
                  presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None,
                  banned_token_ids=None, min_tokens: int = 0, grammar=None, constrain_draft: bool = False, min_p=None):
         from .target import NativeTarget
-        # min_p on the TARGET's rows, directly in front of its draw; None / 0, or T = 0 (the
-        # maximum is always kept): None, and every launch below is the one enqueued without the keyword
-        self._mp = ops.check_min_p(min_p)
-        if temperature < 1e-5:
-            self._mp = None
-        if self._mp is not None:
-            if not isinstance(target, NativeTarget):
-                raise ValueError("min_p needs a dflash_amd.NativeTarget (the kernel reads the verify's materialised logits)")
-            if sampler != "device":
-                raise ValueError("min_p at T > 0 needs sampler='device' (sampler='torch' is the reference's multinomial "
-                                 "over the raw logits)")
-        # grammar: a TokenDFA the emitted tokens must walk; None: every launch below is the one
-        # enqueued without the keyword
-        if grammar is not None:
-            if not isinstance(target, NativeTarget):
-                raise ValueError("grammar needs a dflash_amd.NativeTarget (the kernel reads the verify's materialised "
-                                 "logits)")
-            if temperature >= 1e-5 and sampler != "device":
-                raise ValueError("grammar at T > 0 needs sampler='device' (sampler='torch' is the reference's multinomial "
-                                 "over the raw logits)")
-            if int(max_block_size) > 16:
-                raise NotImplementedError("grammar takes blocks of <= 16 rows (the 17..32-row verify is not covered)")
-        # logit_bias / allowed_token_ids / banned_token_ids / min_tokens on the TARGET's rows; all
-        # neutral: None, and every launch below is the one enqueued without the keywords
+        # The row processors on the TARGET's rows (logits_stage.LogitsStage has the order and the DESIGN.md sections).
+        # Bad values are refused first; min_p at T = 0 keeps the maximum and is off; every feature at its neutral value
+        # leaves every launch below the one enqueued without the keyword
+        mp = ops.check_min_p(min_p) if temperature >= 1e-5 else (ops.check_min_p(min_p) and None)
         lb = None
         if not (logit_bias is None and allowed_token_ids is None and banned_token_ids is None and min_tokens == 0):
             lb = ops.check_logit_bias(_vocab_of(target), logit_bias, allowed_token_ids, banned_token_ids, min_tokens,
                                       stop_token_ids)
-        if lb is not None:
-            if not isinstance(target, NativeTarget):
-                raise ValueError("logit_bias / allowed_token_ids / banned_token_ids / min_tokens need a "
-                                 "dflash_amd.NativeTarget (the kernel reads the verify's materialised logits)")
-            if temperature >= 1e-5 and sampler != "device":
-                raise ValueError("logit_bias / allowed_token_ids / banned_token_ids / min_tokens at T > 0 need "
-                                 "sampler='device' (sampler='torch' is the reference's multinomial over the raw logits)")
-            if int(max_block_size) > 16:
-                raise NotImplementedError("logit_bias / allowed_token_ids / banned_token_ids / min_tokens take blocks of "
-                                          "<= 16 rows (the 17..32-row verify is not covered)")
-        # repetition / presence / frequency penalties on the TARGET's rows; all three neutral:
-        # None, and every launch below is the one enqueued without the keywords
         pen = ops.check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
-        if pen is not None:
-            if not isinstance(target, NativeTarget):
-                raise ValueError("penalties need a dflash_amd.NativeTarget (the kernel reads the verify's materialised logits)")
-            if temperature >= 1e-5 and sampler != "device":
-                raise ValueError("penalties at T > 0 need sampler='device' (sampler='torch' is the reference's multinomial "
-                                 "over the raw logits)")
-            if int(max_block_size) > 16:
-                raise NotImplementedError("penalties take blocks of <= 16 rows (the 17..32-row verify is not covered)")
         # logprobs = N (None: off): per position of output_ids the log-probability of the committed token and the top N
-        # alternatives, scattered there by dfl_logprob_rows behind every verify's posterior
+        # alternatives
         self.logprobs = ops.check_logprobs(logprobs)
-        if self.logprobs is not None and not isinstance(target, NativeTarget):
-            raise ValueError("logprobs needs a dflash_amd.NativeTarget (the kernel reads the verify's materialised logits)")
+        on = dict(min_p=mp is not None, grammar=grammar is not None, logit_bias=lb is not None, penalties=pen is not None,
+                  logprobs=self.logprobs is not None)
+        check_features([f for f, v in on.items() if v], native=isinstance(target, NativeTarget),
+                       sampling=temperature >= 1e-5, seeded=sampler == "device", wide=int(max_block_size) > 16)
         dev = model.device
         if not input_ids.is_cuda:
             raise RuntimeError("dflash_amd: input_ids must be on the GPU")
@@ -284,7 +233,6 @@ class DecodeSession:
         # top_k / top_p restrict the TARGET's draw (the draft's own draw stays unfiltered: the target's draw alone
         # decides what is emitted); None: the fused unfiltered epilogue
         self._filter = resolve_filter(top_k, top_p, temperature, sampler)
-        self._fkw = {} if self._filter is None else self._filter
         # T > 0 cycles can be replayed only with the device sampler (the torch draw consumes host RNG state)
         self.replay_sampling_ok = sampler == "device" or (temperature < 1e-5 and draft_temperature < 1e-5)
         self.stop_token_ids = stop_token_ids
@@ -294,17 +242,6 @@ class DecodeSession:
         self.output_ids = torch.full((1, self.max_length + self.max_bs), mask_token_id, dtype=torch.long, device=dev)
         self.position_ids = torch.arange(self.output_ids.shape[1], device=dev).unsqueeze(0)
         self.native = isinstance(target, NativeTarget)
-        self.lp = (ops.logprob_sink(1, self.output_ids.shape[1], self.logprobs, dev) if self.logprobs is not None else None)
-        self._lpkw = {} if self.lp is None else dict(logprobs=self.lp)
-        if self._mp is not None:
-            self._lpkw = dict(self._lpkw, min_p=self._mp)
-        # the penalty state: the table row dfl_penalty_count keeps (prompt flags + output counts of everything committed),
-        # the three values and the buffer the verify writes its penalised rows into
-        self.pen = None
-        if pen is not None:
-            self.pen = SimpleNamespace(table=ops.penalty_state(1, target.V, dev), r=pen[0], a=pen[1], f=pen[2],
-                                       logits=torch.zeros(16, target.V, dtype=torch.bfloat16, device=dev))
-            self._lpkw = dict(self._lpkw, penalties=self.pen)
         self.tcache = (target.new_cache(self.max_length + 2 * self.max_bs) if self.native
                        else _new_target_cache(target))
         self.use_draft = self.max_bs > 1
@@ -324,26 +261,29 @@ class DecodeSession:
         elif self.use_draft and getattr(model, "w4", None) is not None:   # an mxfp4 draft: its own 4-bit copy of the head
             self.lm_wp8 = model.packed_lm_head_mxfp4(target.lm_head)
         self.stop_t = torch.tensor(stop_token_ids, dtype=torch.long, device=dev) if stop_token_ids else None
-        # the logit-bias state: the dense table row and min_pos = n_in + min_tokens (written once: a session is one
-        # request), the stop ids the accept launch takes, and the buffer the verify writes its biased rows into
-        self.lb = None
-        if lb is not None:
-            self.lb = ops.logit_bias_state(1, target.V, dev)
-            ops.logit_bias_set(self.lb, 0, lb[0], self.n_in + lb[1] if lb[1] else 0)
-            self.lb.stop = self.stop_t
-            self.lb.logits = torch.zeros(16, target.V, dtype=torch.bfloat16, device=dev)
-            self._lpkw = dict(self._lpkw, logit_bias=self.lb)
-        # the grammar state: a pool of exactly the automaton's rows at base 0 (validated against the bias row: a reachable
-        # state whose legal tokens are all banned is refused here), the slot's state, and the buffer the verify writes its
-        # masked rows into
-        self.gr = None
-        if grammar is not None:
-            ops.check_grammar(grammar, target.V, None if lb is None else lb[0])
-            self.gr = ops.grammar_state(1, grammar.next.shape[0], target.V, dev)
-            self.gr.start = int(grammar.start)
-            ops.grammar_set(self.gr, 0, ops.grammar_load(self.gr, grammar), self.gr.start)
-            self.gr.logits = torch.zeros(16, target.V, dtype=torch.bfloat16, device=dev)
-            self._lpkw = dict(self._lpkw, grammar=self.gr)
+        # the row processors' state and buffers, slot 0 of a stage of its own (None: nothing is on, and verify is called
+        # without it); the slot's values go in with the first token (prefill).  A grammar's pool is exactly the
+        # automaton's rows at base 0, validated against the bias row: a reachable state whose legal tokens are all banned
+        # is refused here
+        self.stage, self._vkw = None, {}
+        if any(on.values()) or (self.native and self._filter is not None):
+            if grammar is not None:
+                ops.check_grammar(grammar, target.V, None if lb is None else lb[0])
+            self.stage = LogitsStage(1, target.V, dev, tiles=2 if self.max_bs > 16 else 1, out_len=self.output_ids.shape[1],
+                                     logprobs=self.logprobs, penalties=pen is not None, logit_bias=lb is not None,
+                                     grammar_states=grammar.next.shape[0] if grammar is not None else 0,
+                                     min_p=mp is not None, filtering=self._filter is not None,
+                                     sampling=temperature >= 1e-5, stop_ids=self.stop_t)
+            self._vkw = dict(stage=self.stage)
+            self._gr_start = int(grammar.start) if grammar is not None else None
+            self._admit = dict(penalties=pen, min_p=mp, flt=self._filter,
+                               bias=(lb[0], self.n_in + lb[1] if lb[1] else 0) if lb is not None else None,
+                               grammar=(self.stage.load_grammar(grammar), self._gr_start) if grammar is not None else None)
+        # what the session's own code and its observers read of the stage: the logprob sink, the penalty table, the
+        # grammar state (None each where the feature is off)
+        st = self.stage
+        self.lp, self.gr = (st.lp, st.gr) if st is not None else (None, None)
+        self.pen = SimpleNamespace(table=st.pen_table) if st is not None and st.pen_table is not None else None
         # the reference scans the whole buffer, mask slots included (model/dflash.py:265-268)
         self.stop_always = stop_token_ids is not None and mask_token_id in stop_token_ids
         # the accept result {acc, new start, stop, cycle}: pinned host memory the kernel writes with one 16-byte store and
@@ -386,7 +326,7 @@ class DecodeSession:
             if grammar is None and not bans:
                 raise ValueError("constrain_draft needs something to constrain by: a grammar, allowed_token_ids, "
                                  "banned_token_ids or a logit_bias of -inf")
-            self._cd_bias = self.lb.bias if bans else None
+            self._cd_bias = self.stage.lb.bias if bans else None
             self.draft_logits = torch.zeros(16, target.V, dtype=torch.bfloat16, device=dev)
         # the tapped rows live here from a verify to the next draft (own buffer: several
         # sessions may be interleaved on one NativeTarget)
@@ -404,57 +344,16 @@ class DecodeSession:
                               past_key_values=self.tcache, use_cache=True, logits_to_keep=1,
                               output_hidden_states=self.use_draft)
         self.output_ids[:, :self.n_in] = self.input_ids
-        if self.pen is not None or self.lb is not None or self.gr is not None or self._mp is not None:
-            self._first_token_processed(out.logits[0, -1:])
+        if self.stage is not None:   # the first new token through the stage's chain, from the prompt's last-row logits
+            self.stage.admit(0, out.logits[0, -1:], self.output_ids, self.n_in, temperature=self.temperature,
+                             seed=self._tseed, first=self.output_ids[0, self.n_in:self.n_in + 1], **self._admit)
         elif self._tseed is not None:   # the first new token draws position n_in
             self.output_ids[:, self.n_in:self.n_in + 1] = _draw_rows(out.logits[:, -1:], self.temperature, self._tseed,
                                                                      self.n_in, self._filter)
         else:
             self.output_ids[:, self.n_in:self.n_in + 1] = sample(out.logits, self.temperature)
-        if self.lp is not None:   # the first new token, from the prompt's last-row logits
-            ops.logprob_rows(out.logits[0, -1:].to(torch.bfloat16).contiguous(), self.output_ids[0, self.n_in:self.n_in + 1],
-                             self.lp, pos_base=self.n_in)
         if self.use_draft:
             self.target_hidden = _taps(out.hidden_states, self.model.target_layer_ids)
-
-    def _first_token_processed(self, row: torch.Tensor) -> None:
-        """The first new token under logit bias, a grammar, penalties and / or min_p (the floor goes directly in front of
-        the draw).  The prompt's last-row logits predict position n_in:
-        they take the bias row (and lose the stop ids under min_tokens >= 1); under penalties the prompt is counted into a
-        cleared table row and the rows are penalised by it; the token is their argmax or the seeded draw at position
-        n_in over them, and it is counted as output.  Under a grammar the rows are masked by the start state (the
-        single-row form: no walk) between the two, and the state advances over the token."""
-        p, lb, gr, n = self.pen, self.lb, self.gr, self.n_in
-        first = self.output_ids[0, n:n + 1]
-        z = row.to(torch.bfloat16).contiguous()
-        if lb is not None:
-            z = ops.logit_bias_rows(z, lb.bias, min_pos=lb.min_pos, stop_ids=lb.stop, pos_base=n, out_ids=first)
-        if gr is not None:
-            z = ops.grammar_rows(z, gr, out_ids=first)
-        if p is not None:
-            ops.penalty_count(p.table, self.output_ids, lo=0, hi=n, as_prompt=True, clear=True)
-            z = ops.penalty_rows(z, p.table, repetition_penalty=p.r, presence_penalty=p.a, frequency_penalty=p.f,
-                                 out_ids=first)
-        flt = self._filter
-        if self._mp is not None:   # (T > 0 and seeded) the floor goes directly in front of the draw; filters off: the plain draw
-            z = ops.min_p_rows(z, min_p=self._mp, temperature=self.temperature)
-            flt = flt or dict(top_k=0, top_p=1.0)
-        if self._tseed is not None:
-            first.copy_(_draw_rows(z.unsqueeze(0), self.temperature, self._tseed, n, flt)[0])
-        if p is not None:
-            ops.penalty_count(p.table, self.output_ids, lo=n, hi=n + 1)
-        if gr is not None:
-            ops.grammar_advance(gr, self.output_ids, lo=n, hi=n + 1)
-
-    def _count_committed(self) -> None:
-        """Right behind an accept launch: what it committed, output_ids(S, START] of the draft record it has just
-        written, goes into the penalty table and steps the grammar state — once per cycle, eager or replayed."""
-        if self.pen is not None:
-            ops.penalty_count(self.pen.table, self.output_ids, dyn=self.dyn, lo_word=ops.DYN_S, hi_word=ops.DYN_START,
-                              lo=1, hi=1)
-        if self.gr is not None:
-            ops.grammar_advance(self.gr, self.output_ids, dyn=self.dyn, lo_word=ops.DYN_S, hi_word=ops.DYN_START,
-                                lo=1, hi=1)
 
     def _mark(self, key, which):
         if self.events is not None and self.record_events:
@@ -472,7 +371,7 @@ class DecodeSession:
     def _constrain_draft(self, bs) -> None:
         """Right behind a greedy draft head launch, in front of the hook: block[1:bs] re-picked row by row from the head's
         materialised logits, each the best token that is legal in the state reached over the picks before it.  The
-        slot's state is read, never written: it moves in _count_committed alone."""
+        slot's state is read, never written: it moves in the stage's commit alone."""
         if self.constrain:
             ops.grammar_draft_rows(self.draft_logits[:16], self.gr, bias=self._cd_bias, block=self.block[0], nrows=bs)
 
@@ -490,7 +389,7 @@ class DecodeSession:
         if ev:
             ev[2].record()
         _draft_ids(m, hid, self.lm_wp, bs, self.block[:, :bs], 0.0, self.draft_logits, lm_wp8=self._lm8())
-        # (cycle() enqueues this draft behind _count_committed: the state the pick reads is the one AFTER the advance
+        # (cycle() enqueues this draft behind the stage's commit: the state the pick reads is the one AFTER the advance
         # over what the accept launch has just committed — the state the next verify's rows start from)
         self._constrain_draft(bs)
         if ev:
@@ -585,7 +484,7 @@ class DecodeSession:
             posterior, taps = self.target.verify(
                 blk[0], start, self.tcache, temperature=self.temperature,
                 tap_layers=self.model.target_layer_ids if (want_hidden and self.use_draft) else (),
-                taps_out=self.taps_buf, seed=self._tseed, **self._fkw, **self._lpkw)
+                taps_out=self.taps_buf, seed=self._tseed, **self._vkw)
             self._mark("target", 1)
         else:
             out = self.target(blk, position_ids=self.position_ids[:, start:start + bs],
@@ -606,7 +505,8 @@ class DecodeSession:
         ops.accept_commit(blk[0], posterior[0].contiguous(), bs, self.output_ids[0], self.dyn, self.stop_t,
                           self.result, rearm=(self.block[0], self.max_bs, self.mask_token_id),
                           dyn_t=self.tcache.dyn if (self.native and self._fixed is not None) else None)
-        self._count_committed()
+        if self.stage is not None:
+            self.stage.commit(self.output_ids, self.dyn)
         self._armed = True
         # the record now holds the next draft forward's S / tau / pos0 / start — if that cycle was a cached draft cycle
         # on this record (bs > 1, one draft step) and keeps the block size
@@ -716,10 +616,11 @@ class DecodeSession:
 
         def verify_accept(bs):   # (a T > 0 draw takes its positions from the target record's POS0 word: fresh every replay)
             post, _ = t.verify(self.block[0, :bs], bound, self.tcache, temperature=self.temperature, tap_layers=tl,
-                               taps_out=self.taps_buf, dyn_lengths=True, seed=self._tseed, **self._fkw, **self._lpkw)
+                               taps_out=self.taps_buf, dyn_lengths=True, seed=self._tseed, **self._vkw)
             ops.accept_commit(self.block[0, :bs], post[0].contiguous(), bs, self.output_ids[0], self.dyn, self.stop_t,
                               self.result, rearm=(self.block[0], self.max_bs, self.mask_token_id), dyn_t=self.tcache.dyn)
-            self._count_committed()
+            if self.stage is not None:
+                self.stage.commit(self.output_ids, self.dyn)
 
         graphs = {bs: (capture_graph(lambda: draft(bs)), capture_graph(lambda: verify_accept(bs))) for bs in sizes}
         # The graphs hold RAW device pointers: keep alive every tensor whose address they hold and that this session does
@@ -728,11 +629,7 @@ class DecodeSession:
                        (m._rope, t._rope, getattr(m, "ws", None), getattr(t, "ws", None), getattr(t, "_taps", None),
                         self.lm_wp, self.lm_wp8, self.embed_w, getattr(t, "lm_wp", None),
                         t.fp8_tensors() if self.native else (),    # (an fp8 target's codes and scale vectors)
-                        getattr(t, "_nuc_logits", None),           # (the logits a filtered, logprobs or penalised verify materialises)
-                        getattr(t, "_mp_logits", None),            # (the rows a verify with min_p masks for its draw)
-                        self.pen,                                  # (the penalty table and the penalised rows: the session's own)
-                        self.lb,                                   # (the bias table, min_pos and the biased rows likewise)
-                        self.gr))                                  # (the grammar pool, base / state and the masked rows likewise)
+                        self.stage))   # (the row processors' state and every buffer their launches read or write)
 
     def _tables_moved(self, rec: _Replay) -> bool:
         """A shared draft model / NativeTarget replaces its RoPE table when another caller needs more positions
@@ -875,7 +772,7 @@ class DecodeSession:
         if int(self.gr.state.item()) < 0:
             return -1
         g = SimpleNamespace(table=self.gr.table, base=self.gr.base,
-                            state=torch.full((1,), self.gr.start, dtype=torch.int32, device=self.dev))
+                            state=torch.full((1,), self._gr_start, dtype=torch.int32, device=self.dev))
         ops.grammar_advance(g, output_ids[0].contiguous(), lo=self.n_in, hi=output_ids.shape[1])
         return int(g.state.item())
 

@@ -24,6 +24,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import ops
+from .logits_stage import LogitsStage
 from .model import TARGET_WEIGHT_FORMATS as WEIGHT_FORMATS, _rope_tables
 from .row_stack import RowStack
 from .tile_stack import TileStack, gemm_ws
@@ -133,8 +134,8 @@ class NativeTarget:
         self.wide_one_pass = True
         self._wide = None
         self._wide_seed = None    # int64 [1]: the seed of an fp8 target's sampled wide head (dfl_gemm_sample_batch on e4m3 codes)
-        self._nuc_logits = None   # bf16 [32, V], made on the first filtered verify (top_k / top_p)
-        self._mp_logits = None    # bf16 [32, V], made on the first verify with min_p
+        self._kw_bufs = {}        # the buffers of a verify that is given the row processors as keywords, not as a stage
+        self._nuc_logits = None   # the stage buffer the last verify materialised its raw rows into (what a test reads back)
         self.moe_pair_kernel = True   # MoE gate/up at K <= 2048 through dfl_moe_gate_up (False: the general kernel)
         self.moe_shared_pass = True   # three or four tiles (ragged batch, candidates): one pass over the experts they share
         self.moe_shared_min = 2       # tiles from which the shared pass is taken (30B-A3B layer: 2 tiles 291 -> 216 us, 4: 576 -> 241)
@@ -707,21 +708,8 @@ class NativeTarget:
         return 1
 
     # ---- the verify forward on the kernels
-    def _nucleus_logits(self) -> torch.Tensor:
-        """bf16 [32, V]: where a filtered verify materialises its logits (kept: a captured cycle replays into it)."""
-        if self._nuc_logits is None:
-            self._nuc_logits = torch.zeros(32, self.V, dtype=BF16, device=self._dev)
-        return self._nuc_logits
-
-    def _min_p_logits(self) -> torch.Tensor:
-        """bf16 [32, V]: the min_p-masked rows the draw reads (kept: a captured cycle replays into it); the raw rows stay
-        where the head launch wrote them, for logprobs."""
-        if self._mp_logits is None:
-            self._mp_logits = torch.zeros(32, self.V, dtype=BF16, device=self._dev)
-        return self._mp_logits
-
     def _verify_wide(self, block_ids, start, cache, bs, tap_layers, taps, logits_out, temperature, cos, sin, seed=None,
-                     flt=None, logprobs=None, mp=None):
+                     stage=None):
         """Blocks of 17..32 rows in ONE pass over the weights: the two 16-row tiles go through the ragged-batch
         GEMMs (tile_stack.TileStack, R = 2) as if they were two requests, and through ONE attention launch per layer with
         two query tiles on the request's single cache.  Same lines as verify(): model/dflash.py:249-257."""
@@ -749,14 +737,17 @@ class NativeTarget:
                taps=None if taps is None else taps.view(2, 16, -1), tap_layers=tap_layers, moe=self.moe_mlp_tiles)
         st.finish(self.norm)
         post = ws["post"]
-        if logprobs is not None and logits_out is None:   # the head launch below materialises the block's logits
-            logits_out = self._nucleus_logits()
+        if stage is not None and stage.materialises and logits_out is None:   # the head launch below materialises the block's logits
+            logits_out = self._nuc_logits = stage.raw
+        # tile j row m -> position start + 16 j + m + 1, both tiles of the one request
+        where = dict(dyn=dyn2, nrows_dyn_word=ops.DYN_BS, pos=dict(pos_base=start, pos_add=1), tiles_per_req=2)
 
-        def lp_rows(logits, ids):   # tile j row m -> position start + 16 j + m + 1, both tiles of the one request
-            ops.logprob_rows(logits.view(2, 16, self.V), ids.view(2, 16), logprobs, dyn=dyn2, nrows_dyn_word=ops.DYN_BS,
-                             pos_base=start, pos_add=1, tiles_per_req=2)
+        def lp_rows(logits, ids):
+            if stage is not None and stage.lp is not None:
+                stage.logprobs(logits.view(2, 16, self.V), ids.view(2, 16), **where)
 
-        if flt is None and temperature >= 1e-5 and seed is not None and self.streams_fp8_tiles():
+        process = stage is not None and stage.processes
+        if not process and temperature >= 1e-5 and seed is not None and self.streams_fp8_tiles():
             # an fp8 target: the seeded draw in the e4m3 ring head's epilogue (tile j row m -> POS0 + 16 j + m + 1; the
             # record is rewritten here: verify() rewrites it only when the block size changes, and POS0 must be this
             # cycle's `start`) — the ids of sample_rows over the same launch's logits
@@ -768,34 +759,24 @@ class NativeTarget:
                                   seeds=self._wide_seed, temperature=temperature, pos_word=ops.DYN_POS0, pos_add=1,
                                   tiles_per_req=2, nrows_dyn_word=ops.DYN_BS,
                                   logits=None if logits_out is None else logits_out.view(2, 16, self.V))
-            if logprobs is not None:
-                lp_rows(logits_out, post)
+            lp_rows(logits_out, post)
             cache.length = start + bs
             return post[:bs].unsqueeze(0), taps
         logits = logits_out
-        if flt is not None and logits is None:
-            logits = self._nucleus_logits()
-        elif temperature >= 1e-5:
+        if not process and temperature >= 1e-5:
             logits = torch.empty(32, self.V, dtype=BF16, device=self._dev)
         lv = None if logits is None else logits.view(2, 16, self.V)
         ops.gemm_argmax_batch(self.tile_head(), s["xn"], R, self.V, H, 0, 16, gws, post.view(2, 16), 0, dyn2,
                               nrows_dyn_word=ops.DYN_BS, logits=lv)
-        if flt is not None:   # the filtered draw, host-position form: tile t row m -> start + 16 t + m + 1
-            rows = logits
-            if mp is not None:
-                rows = ops.min_p_rows(logits.view(2, 16, self.V), min_p=mp, temperature=temperature,
-                                      out=self._min_p_logits().view(2, 16, self.V), dyn=dyn2,
-                                      nrows_dyn_word=ops.DYN_BS, tiles_per_req=2)
-            ops.sample_rows_nucleus(rows.view(2, 16, self.V), seed=seed, temperature=temperature, dyn=dyn2,
-                                    nrows_dyn_word=ops.DYN_BS, pos_base=start, pos_add=1, tiles_per_req=2,
-                                    out=post.view(2, 16), **flt)
+        if process:   # (blocks of 17..32 rows: min_p and the filtered draw; the processors that read the block were refused)
+            stage.rows(lv, None, post.view(2, 16), draw=dict(seed=seed, temperature=temperature), **where)
             posterior = post[:bs].unsqueeze(0)
         elif temperature >= 1e-5 and seed is not None:   # the seeded draw over the materialised rows: row j -> start + j + 1
             ops.sample_rows(logits[:bs], seed=seed, temperature=temperature, pos0=start + 1, out=post[:bs])
             posterior = post[:bs].unsqueeze(0)
         else:
             posterior = post[:bs].unsqueeze(0) if temperature < 1e-5 else sample(logits[:bs].unsqueeze(0), temperature)
-        if logprobs is not None:
+        if stage is not None and stage.lp is not None:
             ids = post
             if posterior.data_ptr() != post.data_ptr():   # the host draw: its ids, padded to the two tiles
                 ids = torch.zeros(32, dtype=torch.int64, device=self._dev)
@@ -814,7 +795,7 @@ class NativeTarget:
                temperature: float = 0.0, logits_out: Optional[torch.Tensor] = None,
                taps_out: Optional[torch.Tensor] = None, dyn_lengths: bool = False, seed: Optional[int] = None,
                top_k: int = 0, top_p: float = 1.0, logprobs=None, penalties=None, logit_bias=None, grammar=None,
-               min_p=None):
+               min_p=None, stage=None):
         """block_ids int64 [bs] at positions start..start+bs-1 (cache rows alike), bs <= 32.
         Returns (posterior ids int64 [1, bs], taps bf16 [32, len(tap_layers)*H] or None).
         K/V of all bs rows are written; the caller crops to what it accepts.
@@ -829,68 +810,20 @@ class NativeTarget:
         seed (temperature > 0): the seeded Gumbel-max draw in the lm_head epilogue instead of softmax + multinomial —
         row j draws position start + j + 1, start from the record's POS0 word under dyn_lengths (DESIGN.md section 8);
         no logits are written unless logits_out is given.
-        top_k / top_p (with seed, temperature > 0): the filtered draw (section 8, "Filtered draw") — the lm_head launch
-        materialises the block's logits and dfl_sample_rows_nucleus writes the posterior, positions as above.
-        logprobs: an ops.logprob_sink (None: off, and nothing here changes).  The head launch then materialises the
-        block's logits — into logits_out or the target's own buffer — and dfl_logprob_rows, behind whichever launch wrote
-        the posterior, scatters log_softmax(raw logits)[posterior[j]] (T = 1, unfiltered, whatever drew the token) and
-        the sink's n_top alternatives to position start + j + 1 of the sink's row `slot`; start
-        from the record's POS0 word under dyn_lengths.
-        penalties: a state object (DecodeSession makes one: .table int32 [1, V] kept by ops.penalty_count, .r / .a / .f,
-        .logits bf16 [16, V]; None: off, and nothing here changes).  Blocks of <= 16 rows: the head launch materialises
-        the raw logits, dfl_penalty_rows writes the penalised rows into .logits — row j by the table plus the block's own
-        block_ids[1 .. j] — and their argmax into the posterior; at temperature > 0 (seeded) dfl_sample_rows_nucleus then
-        draws over the penalised rows (filters off: the plain seeded draw).  logprobs stay those of the raw rows
-        (DESIGN.md section 13).
-        logit_bias: a state object (DecodeSession makes one: .bias fp32 [1, V] and .min_pos, written by
-        ops.logit_bias_set, .stop int64 stop ids on the device or None, .logits bf16 [16, V]; None: off, and nothing here
-        changes).  Blocks of <= 16 rows: behind the head launch dfl_logit_bias_rows writes the biased rows into .logits —
-        row j predicts position start + j + 1, start from the record's POS0 word under dyn_lengths, and loses the stop
-        ids while that is < min_pos — and their argmax into the posterior; the penalties, then the draw, run over those
-        rows; logprobs stay those of the raw rows.
-        grammar: an ops.grammar_state with .logits bf16 [16, V] beside it (DecodeSession makes one; None: off, and
-        nothing here changes).  Blocks of <= 16 rows: behind dfl_logit_bias_rows and in front of dfl_penalty_rows,
-        dfl_grammar_rows writes the masked rows into .logits — row j walks the slot's state through block_ids[1 .. j] and
-        sets what is illegal where it arrives to -inf; a row whose walk dies is copied — and their argmax into the
-        posterior; the penalties, then the draw, run over those rows; logprobs stay those of the raw rows (DESIGN.md
-        section 15).
-        min_p (with seed, temperature > 0; None / 0: off, and nothing here changes; at temperature 0 it does nothing,
-        the maximum is always kept): directly in front of the draw dfl_min_p_rows writes the rows with every column
-        below min_p times the top token's probability set to -inf into a buffer of the target's own, and
-        dfl_sample_rows_nucleus draws over those (filters off: the plain seeded draw); blocks of up to 32 rows;
-        logprobs stay those of the raw rows; a logits_out given with it has a row stride of V, as that buffer has
-        (ValueError otherwise)."""
+        stage: a logits_stage.LogitsStage (None: off, and nothing here changes) — the row processors between the head
+        launch and the posterior, in the order its docstring gives.  The head launch then materialises the block's
+        logits, into logits_out or the stage's own buffer, and the stage's launches write the posterior; row m predicts
+        position start + m + 1, start from the record's POS0 word under dyn_lengths.  A stage with logprobs alone
+        leaves the head launches below as they are and reads the rows they materialise.
+        top_k / top_p / logprobs / penalties / logit_bias / grammar / min_p: the same asked by keyword, for a caller
+        that keeps the state objects itself (LogitsStage.of_keywords); their buffers are this target's."""
         bs = block_ids.numel()
-        mp = ops.check_min_p(min_p)
-        if temperature < 1e-5:
-            mp = None
-        if mp is not None and seed is None:
-            raise ValueError("min_p at temperature > 0 needs the seeded draw (seed=...)")
-        if mp is not None and logits_out is not None and (logits_out.dim() != 2 or logits_out.stride(0) != self.V):
-            raise ValueError("min_p needs logits_out with a row stride of V: the masked rows go to a buffer of the "
-                             "target's own, laid out like the rows they are made from")
-        if grammar is not None:
-            if bs > 16:
-                raise NotImplementedError("NativeTarget.verify: a grammar takes blocks of <= 16 rows")
-            if temperature >= 1e-5 and seed is None:
-                raise ValueError("a grammar at temperature > 0 needs the seeded draw (seed=...)")
-        if penalties is not None:
-            if bs > 16:
-                raise NotImplementedError("NativeTarget.verify: penalties take blocks of <= 16 rows")
-            if temperature >= 1e-5 and seed is None:
-                raise ValueError("penalties at temperature > 0 need the seeded draw (seed=...)")
-        if logit_bias is not None:
-            if bs > 16:
-                raise NotImplementedError("NativeTarget.verify: logit_bias takes blocks of <= 16 rows")
-            if temperature >= 1e-5 and seed is None:
-                raise ValueError("logit_bias at temperature > 0 needs the seeded draw (seed=...)")
-        flt = None
-        if ops.check_filter(top_k, top_p) and temperature >= 1e-5:
-            if seed is None:
-                raise ValueError("top_k / top_p at temperature > 0 need the seeded draw (seed=...)")
-            flt = dict(top_k=int(top_k), top_p=float(top_p))
-        if mp is not None and flt is None:   # the draw over the masked rows: filters off is the plain seeded draw
-            flt = dict(top_k=0, top_p=1.0)
+        own = stage is None
+        if own:
+            stage = LogitsStage.of_keywords(self.V, temperature, top_k=top_k, top_p=top_p, logprobs=logprobs,
+                                            penalties=penalties, logit_bias=logit_bias, grammar=grammar, min_p=min_p)
+        if stage is not None:
+            stage.check_block(bs, temperature, seed, logits_out)
         if self.wide_hidden:
             raise NotImplementedError("NativeTarget.verify: hidden > 4096 runs through the ragged-batch path "
                                       "(dflash_generate / dflash_generate_batch / BatchedDecoder)")
@@ -931,9 +864,11 @@ class NativeTarget:
                 taps = self._taps[key]
         w8 = self.streams_fp8(bs)
         head = self.lm_wp8 if w8 else self.lm_wp
+        if own and stage is not None:
+            stage.device, stage._bufs = self._dev, self._kw_bufs
         if len(tiles) == 2 and self.wide_one_pass and self.attn_impl == "head":
             return self._verify_wide(block_ids, start, cache, bs, tap_layers, taps, logits_out, temperature, cos, sin, seed,
-                                     flt, logprobs, mp)
+                                     stage)
         rs = self.rows
         for t, dt in tiles:
             ops.embed_rows(self.embed, block_ids[16 * t:], rs.h_tiles[t], H, rs.ss_emb[16 * t:], dt, ops.DYN_BS)
@@ -955,62 +890,27 @@ class NativeTarget:
                      taps=taps, tap_layers=tap_layers, moe=self._moe_mlp, gu_events=self.gu_events)
         post = ws["post"]
         logits = logits_out
-        if logprobs is not None and logits is None and (flt is not None or seed is not None or temperature < 1e-5):
-            logits = self._nucleus_logits()   # (the host draw below materialises into a buffer of its own)
+        process = stage is not None and stage.processes
+        if stage is not None and logits is None and (process or stage.lp is not None and (seed is not None or temperature < 1e-5)):
+            logits = self._nuc_logits = stage.raw   # (the host draw below materialises into a buffer of its own)
 
-        def lp_rows(ids):   # behind the launches that wrote the posterior: tile t row m -> position start + 16 t + m + 1
-            for t, dt in tiles:
-                ops.logprob_rows(logits[16 * t:16 * t + 16], ids[16 * t:], logprobs, nrows=min(16, bs - 16 * t), dyn=dt,
-                                 pos_word=ops.DYN_POS0 if dyn_lengths else -1, pos_base=start, pos_add=16 * t + 1)
+        if stage is not None:
+            def pos(t):   # tile t row m predicts position start + 16 t + m + 1, start from the record when replayed
+                return dict(pos_word=ops.DYN_POS0 if dyn_lengths else -1, pos_base=start, pos_add=16 * t + 1)
 
-        if penalties is not None or logit_bias is not None or grammar is not None:
-            # one tile: raw logits; biased rows + their argmax; grammar-masked rows + their argmax (masking commutes with
-            # both neighbours: neither turns -inf finite); penalised rows + their argmax; the draw over the last of them;
-            # logprobs of the raw rows.  Row m predicts position start + m + 1, start from the record when replayed
-            pen, dt = penalties, tiles[0][1]
-            pos = dict(pos_word=ops.DYN_POS0 if dyn_lengths else -1, pos_base=start, pos_add=1)
-            if logits is None:
-                logits = self._nucleus_logits()
+            def lp_rows(ids):   # behind the launches that wrote the posterior
+                for t, dt in tiles:
+                    stage.logprobs(logits[16 * t:16 * t + 16], ids[16 * t:], pos=pos(t), nrows=min(16, bs - 16 * t), dyn=dt)
+
+        if process:   # per tile: the head launch materialises the raw rows, the stage's launches write the posterior
             if temperature < 1e-5 and self.x13 and not w8:
                 head = ops.bf16x13_twin(head, self.V, H, "lm_head") or head
-            ops.gemm_argmax(head, fin[0], self.V, H, 0, bs, ws["argmax_ws"], post, 0, dyn=dt, logits=logits[:16])
-            rows = logits[:16]
-            if logit_bias is not None:
-                ops.logit_bias_rows(rows, logit_bias.bias, min_pos=logit_bias.min_pos, stop_ids=logit_bias.stop,
-                                    out=logit_bias.logits, nrows=bs, dyn=dt, out_ids=post[:16], **pos)
-                rows = logit_bias.logits
-            if grammar is not None:
-                ops.grammar_rows(rows, grammar, block=block_ids, out=grammar.logits, nrows=bs, dyn=dt, out_ids=post[:16])
-                rows = grammar.logits
-            if pen is not None:
-                ops.penalty_rows(rows, pen.table, repetition_penalty=pen.r, presence_penalty=pen.a,
-                                 frequency_penalty=pen.f, block=block_ids, out=pen.logits, nrows=bs, out_ids=post[:16])
-                rows = pen.logits
-            if mp is not None:
-                rows = ops.min_p_rows(rows, min_p=mp, temperature=temperature, out=self._min_p_logits()[:16], nrows=bs)
-            if temperature >= 1e-5:
-                ops.sample_rows_nucleus(rows, seed=seed, temperature=temperature, nrows=bs, dyn=dt,
-                                        out=post[:16], **pos, **(flt or dict(top_k=0, top_p=1.0)))
-            if logprobs is not None:
-                lp_rows(post)
-            cache.length = start + bs
-            return post[:bs].unsqueeze(0), taps
-        if flt is not None:
-            if logits is None:
-                logits = self._nucleus_logits()
-            for t, dt in tiles:   # tile t row m predicts position start + 16 t + m + 1, start from the record when replayed
-                n = min(16, bs - 16 * t)
-                ops.gemm_argmax(head, fin[t], self.V, H, 0, n, ws["argmax_ws"], post, 16 * t, dyn=dt,
-                                logits=logits[16 * t:16 * t + 16])
-                rows = logits[16 * t:16 * t + 16]
-                if mp is not None:
-                    rows = ops.min_p_rows(rows, min_p=mp, temperature=temperature,
-                                          out=self._min_p_logits()[16 * t:16 * t + 16], nrows=n)
-                ops.sample_rows_nucleus(rows, seed=seed, temperature=temperature, nrows=n, dyn=dt,
-                                        pos_word=ops.DYN_POS0 if dyn_lengths else -1, pos_base=start, pos_add=16 * t + 1,
-                                        out=post[16 * t:16 * t + 16], **flt)
-            if logprobs is not None:
-                lp_rows(post)
+            draw = dict(seed=seed, temperature=temperature) if temperature >= 1e-5 else None
+            for t, dt in tiles:
+                n, raw = min(16, bs - 16 * t), logits[16 * t:16 * t + 16]
+                ops.gemm_argmax(head, fin[t], self.V, H, 0, n, ws["argmax_ws"], post, 16 * t, dyn=dt, logits=raw)
+                stage.rows(raw, block_ids, post[16 * t:16 * t + 16], draw=draw, pos=pos(t), tile=t, nrows=n, dyn=dt)
+            lp_rows(post)
             cache.length = start + bs
             return post[:bs].unsqueeze(0), taps
         if temperature >= 1e-5 and seed is not None:
@@ -1019,7 +919,7 @@ class NativeTarget:
                                 seed=seed, temperature=temperature, pos_dyn=dt if dyn_lengths else None,
                                 pos_word=ops.DYN_POS0, pos_base=start, pos_add=16 * t + 1, dyn=dt,
                                 logits=None if logits is None else logits[16 * t:16 * t + 16])
-            if logprobs is not None:
+            if stage is not None:
                 lp_rows(post)
             cache.length = start + bs
             return post[:bs].unsqueeze(0), taps
@@ -1034,7 +934,7 @@ class NativeTarget:
             posterior = post[:bs].unsqueeze(0)
         else:
             posterior = sample(logits[:bs].unsqueeze(0), temperature)
-        if logprobs is not None:
+        if stage is not None:
             lp_rows(posterior[0].contiguous())
         cache.length = start + bs
         return posterior, taps
