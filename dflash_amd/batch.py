@@ -26,8 +26,8 @@ from typing import Callable, Optional, Sequence
 import torch
 
 from . import ops
-from .generate import (NO_LOGPROBS, _bf16_table, _draw_rows, _kept_cols, _taps, _trim, capture_graph, cuda_time,
-                       logprob_fields, resolve_seed)
+from .generate import (NO_LOGPROBS, _bf16_table, _draw_rows, _kept_cols, _taps, _trim, capture_graph, check_couple_draft,
+                       cuda_time, logprob_fields, resolve_seed)
 from .logits_stage import LogitsStage, check_features
 from .model import DFlashDraftModel
 from .target import NativeTarget
@@ -57,7 +57,8 @@ class BatchedDecoder:
                  temperature: float = 0.0, tiles_per_request: int = 1, sampler: str = "torch",
                  draft_temperature: float = 0.0, filtering: bool = False, request_temperature: bool = False,
                  logprobs: Optional[int] = None, penalties: bool = False, logit_bias: bool = False,
-                 grammar_states: int = 0, constrain_draft: bool = False, min_p: bool = False):
+                 grammar_states: int = 0, constrain_draft: bool = False, min_p: bool = False,
+                 couple_draft: bool = False):
         """filtering / logprobs / penalties / logit_bias / grammar_states / min_p: which row processors the verify runs
         between its head launch and the posterior (logits_stage.LogitsStage has the order, what each reads and the
         DESIGN.md sections).  Fixed here: they fix the captured launch sequence and the addresses it reads.  Requests
@@ -67,8 +68,19 @@ class BatchedDecoder:
         constrain_draft (fixed here for the same reason; needs grammar_states > 0 or logit_bias, one tile per request and
         a greedy draft): the draft's head launch materialises its logits and ONE dfl_grammar_draft_rows launch over all
         tiles re-picks every slot's draft tokens under its automaton and its bans ("The draft under
-        the grammar").  A slot without a grammar and without bans keeps its argmax ids."""
+        the grammar").  A slot without a grammar and without bans keeps its argmax ids.
+        couple_draft (fixed here for the same reason; sampler="device" where anything samples): the draft's head launch is
+        dfl_gemm_sample_batch on stream TARGET with each slot's seed and the TARGET's invT (the per-slot array with
+        request_temperature: a greedy slot keeps the plain argmax), position base = the draft record's START word — every
+        slot's draft token j is picked under the noise the verify draws that position with.  The
+        bf16 lm_head for this launch, also in an fp8 draft.  With constrain_draft the pick is the noise form.  A decoder
+        in which nothing samples enqueues the launches of before."""
         logprobs = ops.check_logprobs(logprobs)
+        draft_temperature = check_couple_draft(couple_draft, temperature, draft_temperature if draft_temperature >= 1e-5
+                                               else None, sampler)
+        self.couple = bool(couple_draft) and (temperature >= 1e-5 or bool(request_temperature))
+        if self.couple:
+            draft_temperature = 0.0   # the draft counts as greedy below: only its head launch differs
         grammar_states = int(grammar_states)
         if grammar_states < 0:
             raise ValueError(f"grammar_states must be >= 0 (0: off), got {grammar_states}")
@@ -496,7 +508,20 @@ class BatchedDecoder:
         m, c, R = self.model, self.cfg, self.NT
         self.side_d.stack.finish(m.w["norm"])   # last down_proj + final norm
         s = self.side_d.stack.src
-        if self.draft_temperature >= 1e-5:   # sampled draft (policy loop): slot j of the block draws start + j
+        if self.couple:   # coupled draft: slot j under the noise the verify draws position START + j with (section 20)
+            row0, out, off = (1, self.block, 1) if self.TPR == 1 else (0, self.ids_tmp, 0)
+            inv = dict(inv_ts=self.inv_ts) if self.request_temperature else dict(temperature=self.temperature)
+            ops.gemm_sample_batch(self.lm_wp, s["xn"], R, c.vocab_size, c.hidden_size, row0, 16 - row0, self.gws, out, off,
+                                  self.dyn_tt, seeds=self.seeds, stream=ops.RNG_TARGET, pos_word=ops.DYN_START, pos_add=0,
+                                  tiles_per_req=self.TPR, nrows_dyn_word=ops.DYN_BS, logits=self._cd_logits, **inv)
+            if self.TPR == 2:
+                self.block[:, 1:].copy_(self.ids_tmp.view(-1, self.BW)[:, 1:])
+            if self.constrain_draft:   # the noise form of the pick below: the perturbed maximum over the legal columns
+                ops.grammar_draft_sample_rows(self._cd_logits[:R], self.grammar,
+                                              bias=self.stage.lb.bias if self.logit_bias else None, block=self.block,
+                                              dyn=self.dyn_tt, nrows_dyn_word=ops.DYN_BS, seeds=self.seeds,
+                                              pos_dyn_word=ops.DYN_START, **inv)
+        elif self.draft_temperature >= 1e-5:   # sampled draft (policy loop): slot j of the block draws start + j
             row0, out, off = (1, self.block, 1) if self.TPR == 1 else (0, self.ids_tmp, 0)
             ops.gemm_sample_batch(self.lm_wp, s["xn"], R, c.vocab_size, c.hidden_size, row0, 16 - row0, self.gws, out, off,
                                   self.dyn_tt, seeds=self.seeds, temperature=self.draft_temperature, stream=ops.RNG_DRAFT,
@@ -821,7 +846,7 @@ def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_i
                           seed=None, top_k=0, top_p=1.0, logprobs: Optional[int] = None, repetition_penalty=1.0,
                           presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, allowed_token_ids=None,
                           banned_token_ids=None, min_tokens=0, grammar=None, constrain_draft: bool = False,
-                          min_p=None) -> list:
+                          min_p=None, couple_draft: bool = False) -> list:
     """`dflash_generate` (benchmark.py:44-251) for a list of prompts: requests run in
     groups of `group_size` <= 4 (<= 2 with block sizes of 17..32 rows) that share the weight stream; returns one namespace per
     prompt with the fields of benchmark.py:242-251 (timing fields are the group's).
@@ -843,7 +868,8 @@ def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_i
     constrain_draft: as dflash_generate (ValueError when no prompt has a grammar or a not-neutral logit-bias keyword); a
     prompt without a grammar and without bans keeps its argmax draft.
     min_p: as dflash_generate; a scalar, or one value (or None) per prompt.  The decoders are built with min_p=True when
-    any prompt floors a sampled draw (blocks of up to 32 rows); a prompt at 0 gets the ids of a run without it."""
+    any prompt floors a sampled draw (blocks of up to 32 rows); a prompt at 0 gets the ids of a run without it.
+    couple_draft: as dflash_generate, for every prompt at its own temperature (a prompt at 0 keeps its greedy draft)."""
     logprobs = ops.check_logprobs(logprobs)
     dfas = _prompt_grammars(grammar, len(input_ids))
     for d in {id(d): d for d in dfas if d is not None}.values():
@@ -884,7 +910,8 @@ def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_i
                              penalties=penalties, logit_bias=logit_bias_on, min_p=min_p_on,
                              grammar_states=_pool_rows([dfas[i] for i in idx]),
                              # (a group none of whose prompts has anything to constrain by runs the plain launches)
-                             constrain_draft=bool(constrain_draft) and bool(logit_bias_on or _pool_rows([dfas[i] for i in idx])))
+                             constrain_draft=bool(constrain_draft) and bool(logit_bias_on or _pool_rows([dfas[i] for i in idx])),
+                             couple_draft=couple_draft)
         handles = _load_grammars(dec, [dfas[i] for i in idx])
         t0 = cuda_time()
         for r, p in enumerate(prompts):

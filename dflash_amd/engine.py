@@ -130,8 +130,10 @@ class BatchEngine:
                  block_size: int = 16, stop_token_ids=None, temperature: float = 0.0, sampler: str = "torch",
                  graph: Optional[bool] = None, filtering: bool = False, request_temperature: bool = False,
                  logprobs: Optional[int] = None, penalties: bool = False, logit_bias: bool = False,
-                 grammar_states: int = 0, constrain_draft: bool = False, min_p: bool = False):
-        """filtering / request_temperature / logprobs / penalties / logit_bias / grammar_states / constrain_draft / min_p:
+                 grammar_states: int = 0, constrain_draft: bool = False, min_p: bool = False,
+                 couple_draft: bool = False):
+        """filtering / request_temperature / logprobs / penalties / logit_bias / grammar_states / constrain_draft / min_p /
+        couple_draft:
         as BatchedDecoder takes them — what requests may carry (submit); fixed here because they fix the one captured
         launch sequence of the engine's life (logits_stage.LogitsStage has the row processors' order and the DESIGN.md
         sections).  A slot's values are rewritten whole on every admission and read by address by the captured launches:
@@ -159,7 +161,7 @@ class BatchEngine:
                                   stop_token_ids=stop_token_ids, temperature=temperature, sampler=sampler,
                                   filtering=filtering, request_temperature=request_temperature, logprobs=logprobs,
                                   penalties=penalties, logit_bias=logit_bias, grammar_states=grammar_states,
-                                  constrain_draft=constrain_draft, min_p=min_p)
+                                  constrain_draft=constrain_draft, min_p=min_p, couple_draft=couple_draft)
         self.min_p = bool(min_p)
         self.filtering, self.temperature, self.penalties = bool(filtering), float(temperature), bool(penalties)
         self.logit_bias = bool(logit_bias)
@@ -245,7 +247,8 @@ def dflash_generate_stream(model, target, input_ids: Sequence[torch.Tensor], mas
                            sampler: str = "torch", seed=None, top_k=0, top_p=1.0,
                            logprobs: Optional[int] = None, repetition_penalty=1.0, presence_penalty=0.0,
                            frequency_penalty=0.0, logit_bias=None, allowed_token_ids=None, banned_token_ids=None,
-                           min_tokens=0, grammar=None, constrain_draft: bool = False, min_p=None) -> list:
+                           min_tokens=0, grammar=None, constrain_draft: bool = False, min_p=None,
+                           couple_draft: bool = False) -> list:
     """`dflash_generate_batch` with slot refill: one namespace per prompt with the fields of benchmark.py:242-251, each
     request emitting what its own `dflash_generate` run emits.  max_new_tokens: one int or one per prompt.
     draft_token_hook(request_index, block_view, start, call).  seed as in dflash_generate_batch (an int s gives prompt i
@@ -257,7 +260,7 @@ def dflash_generate_stream(model, target, input_ids: Sequence[torch.Tensor], mas
     logit_bias / allowed_token_ids / banned_token_ids / min_tokens: one value for every prompt, or a sequence with one
     value (or None) per prompt.
     grammar: one TokenDFA for every prompt, or a sequence with one (or None) per prompt.
-    constrain_draft: as dflash_generate_batch.
+    constrain_draft: as dflash_generate_batch.  couple_draft: likewise.
     min_p: a scalar, or one value (or None) per prompt."""
     dfas = _prompt_grammars(grammar, len(input_ids))
     for d in {id(d): d for d in dfas if d is not None}.values():
@@ -281,7 +284,8 @@ def dflash_generate_stream(model, target, input_ids: Sequence[torch.Tensor], mas
                       out_len=need + BLOCK_ROWS, mask_token_id=mask_token_id, block_size=block_size,
                       stop_token_ids=stop_token_ids, temperature=max(temps, default=0.0), sampler=sampler, filtering=filtering,
                       request_temperature=per_request, logprobs=logprobs, penalties=penalties, logit_bias=logit_bias_on,
-                      grammar_states=_pool_rows(dfas), constrain_draft=constrain_draft, min_p=min_p_on)
+                      grammar_states=_pool_rows(dfas), constrain_draft=constrain_draft, min_p=min_p_on,
+                      couple_draft=couple_draft)
     handles = _load_grammars(eng, dfas)
     for i, p in enumerate(input_ids):
         hook = (lambda blk, start, call, i=i: draft_token_hook(i, blk, start, call)) if draft_token_hook else None

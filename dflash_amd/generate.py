@@ -137,6 +137,21 @@ def resolve_filter(top_k, top_p, temperature: float, sampler: str) -> Optional[d
     return dict(top_k=int(top_k), top_p=float(top_p))
 
 
+def check_couple_draft(couple_draft, temperature: float, draft_temperature: Optional[float], sampler: str) -> float:
+    """Validate couple_draft against the request and return the draft temperature to run with
+    (0.0: a greedy draft).  A coupled draft shares the target's seeded noise: sampler="torch" has none at T > 0, and a
+    draft temperature of its own contradicts invT = the target's."""
+    dt = 0.0 if draft_temperature is None else float(draft_temperature)
+    if not couple_draft:
+        return dt
+    if draft_temperature is not None and dt != float(temperature):
+        raise ValueError(f"couple_draft draws the draft at the target's temperature: draft_temperature={draft_temperature!r} "
+                         f"differs from temperature={temperature!r}")
+    if temperature >= 1e-5 and sampler != "device":
+        raise ValueError("couple_draft at T > 0 needs sampler='device' (sampler='torch' has no seeded noise to share)")
+    return dt
+
+
 def _trim(output_ids, max_length, mask_token_id, stop_token_ids, n_in):
     """model/dflash.py:269-275."""
     output_ids = output_ids[:, :max_length]
@@ -190,12 +205,21 @@ class DecodeSession:
     variables of its while-loop, model/dflash.py:206-233)."""
 
     def __init__(self, model, target, input_ids: torch.Tensor, *, mask_token_id: int, max_new_tokens: int,
-                 max_block_size: int, stop_token_ids, temperature: float, draft_temperature: float = 0.0,
+                 max_block_size: int, stop_token_ids, temperature: float, draft_temperature: Optional[float] = None,
                  draft_token_hook: Optional[Callable] = None, sampler: str = "torch", seed: Optional[int] = None,
                  top_k: int = 0, top_p: float = 1.0, logprobs: Optional[int] = None, repetition_penalty: float = 1.0,
                  presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None,
-                 banned_token_ids=None, min_tokens: int = 0, grammar=None, constrain_draft: bool = False, min_p=None):
+                 banned_token_ids=None, min_tokens: int = 0, grammar=None, constrain_draft: bool = False, min_p=None,
+                 couple_draft: bool = False):
         from .target import NativeTarget
+        # couple_draft (DESIGN.md section 20): at T > 0 every draft token is the argmax of the DRAFT's logits under the
+        # noise the TARGET's verify will draw that position with (stream TARGET, the request's seed, the target's invT).
+        # The draft then counts as greedy everywhere below — run-ahead, constrain_draft, the fixed-size capture — and only
+        # its head launch differs.  At T = 0, or off: every launch is the one enqueued without the keyword
+        draft_temperature = check_couple_draft(couple_draft, temperature, draft_temperature, sampler)
+        self.couple = bool(couple_draft) and temperature >= 1e-5
+        if self.couple:
+            draft_temperature = 0.0
         # The row processors on the TARGET's rows (logits_stage.LogitsStage has the order and the DESIGN.md sections).
         # Bad values are refused first; min_p at T = 0 keeps the maximum and is off; every feature at its neutral value
         # leaves every launch below the one enqueued without the keyword
@@ -230,6 +254,8 @@ class DecodeSession:
         self.seed = resolve_seed(sampler, seed, needed=temperature >= 1e-5 or draft_temperature >= 1e-5)
         self._tseed = self.seed if (self.seed is not None and temperature >= 1e-5) else None
         self._dseed = self.seed if (self.seed is not None and draft_temperature >= 1e-5) else None
+        self._couple = dict(seed=self._tseed, temperature=temperature) if self.couple else None
+        self._cseed = (torch.tensor([ops.seed_i64(self._tseed)], dtype=torch.long, device=dev) if self.couple else None)
         # top_k / top_p restrict the TARGET's draw (the draft's own draw stays unfiltered: the target's draw alone
         # decides what is emitted); None: the fused unfiltered epilogue
         self._filter = resolve_filter(top_k, top_p, temperature, sampler)
@@ -368,11 +394,20 @@ class DecodeSession:
             return self.lm_wp8 if self.model.mxfp4_stream else None
         return self.lm_wp8 if self.model.fp8_stream else None
 
-    def _constrain_draft(self, bs) -> None:
+    def _constrain_draft(self, bs, start: Optional[int] = None) -> None:
         """Right behind a greedy draft head launch, in front of the hook: block[1:bs] re-picked row by row from the head's
         materialised logits, each the best token that is legal in the state reached over the picks before it.  The
-        slot's state is read, never written: it moves in the stage's commit alone."""
-        if self.constrain:
+        slot's state is read, never written: it moves in the stage's commit alone.
+        A coupled draft: the noise form — the perturbed maximum over the legal columns, slot j under the noise of position
+        START + j (the draft record's word, as the head launch read it; `start`: the host value, where no record is armed)."""
+        if not self.constrain:
+            return
+        if self.couple:
+            ops.grammar_draft_sample_rows(self.draft_logits[:16], self.gr, bias=self._cd_bias, block=self.block[0], nrows=bs,
+                                          seeds=self._cseed, temperature=self.temperature, dyn=self.dcache.dyn,
+                                          pos_dyn_word=-1 if start is not None else ops.DYN_START,
+                                          pos_base=0 if start is None else int(start))
+        else:
             ops.grammar_draft_rows(self.draft_logits[:16], self.gr, bias=self._cd_bias, block=self.block[0], nrows=bs)
 
     def _draft_ahead(self, bs) -> None:
@@ -388,7 +423,8 @@ class DecodeSession:
                             block_ids=self.block[0], embed=self.embed_w, dyn_ready=True, s_bound=self.start + self.max_bs)
         if ev:
             ev[2].record()
-        _draft_ids(m, hid, self.lm_wp, bs, self.block[:, :bs], 0.0, self.draft_logits, lm_wp8=self._lm8())
+        _draft_ids(m, hid, self.lm_wp, bs, self.block[:, :bs], 0.0, self.draft_logits, dyn=self.dcache.dyn,
+                   lm_wp8=self._lm8(), couple=self._couple)
         # (cycle() enqueues this draft behind the stage's commit: the state the pick reads is the one AFTER the advance
         # over what the accept launch has just committed — the state the next verify's rows start from)
         self._constrain_draft(bs)
@@ -435,7 +471,7 @@ class DecodeSession:
             self._dyn_bs = None   # until the accept of this cycle has re-armed the record
             self._mark("lm_head", 0)
             _draft_ids(m, hid, self.lm_wp, bs, blk, self.draft_temperature, self.draft_logits, seed=self._dseed,
-                       dyn=self.dcache.dyn, start=self.start, lm_wp8=self._lm8())
+                       dyn=self.dcache.dyn, start=self.start, lm_wp8=self._lm8(), couple=self._couple)
             self._constrain_draft(bs)
             self._mark("lm_head", 1)
             return self._call_hook(blk)
@@ -452,8 +488,8 @@ class DecodeSession:
             hid = m.draft_block(tmp, th_rows=c2, tau=c2.shape[0], bs=bs, pos0=p0, block_ids=blk[0],
                                 embed=self.embed_w, append=False)
             _draft_ids(m, hid, self.lm_wp, bs, blk, 0.0, self.draft_logits if self.constrain else None,
-                       lm_wp8=self._lm8())
-            self._constrain_draft(bs)
+                       start=self.start, lm_wp8=self._lm8(), couple=self._couple)   # (no record: the host's start)
+            self._constrain_draft(bs, start=self.start)
             self._call_hook(blk)
 
     @torch.inference_mode()
@@ -580,9 +616,10 @@ class DecodeSession:
         if not sizes or sizes[0] < 2 or sizes[-1] > 16:
             return "needs block sizes in 2..16"
         # The one asymmetry: the fixed form's draft is the NEXT cycle's, enqueued before the host has this cycle's result,
-        # and a run-ahead draft is only ever greedy (cycle() launches none at a draft temperature: capture()'s
-        # `_ahead == bs` could never hold).  The sized form drafts inside its own cycle, after the host has written the
-        # records, so its draft may sample (the draw takes the block start from the record's START word).
+        # and a run-ahead draft is only ever greedy or coupled (cycle() launches none at a draft temperature: capture()'s
+        # `_ahead == bs` could never hold; a coupled draft reads START from the record the accept launch re-armed).
+        # The sized form drafts inside its own cycle, after the host has written the records, so its draft may sample
+        # (the draw takes the block start from the record's START word).
         if ahead and self.draft_temperature >= 1e-5:
             return "needs a greedy draft (the next cycle's draft runs ahead of the accept result)"
         if self._replay_bound(sizes[-1]) < self.start:
@@ -611,7 +648,7 @@ class DecodeSession:
             hid = m.draft_block(self.dcache, th_rows=self.taps_buf[:16], tau=16, bs=bs, pos0=bound, block_ids=self.block[0],
                                 embed=self.embed_w, dyn_ready=True, s_bound=bound)
             _draft_ids(m, hid, self.lm_wp, bs, self.block[:, :bs], self.draft_temperature, self.draft_logits,
-                       seed=self._dseed, dyn=self.dcache.dyn, lm_wp8=self._lm8())
+                       seed=self._dseed, dyn=self.dcache.dyn, lm_wp8=self._lm8(), couple=self._couple)
             self._constrain_draft(bs)
 
         def verify_accept(bs):   # (a T > 0 draw takes its positions from the target record's POS0 word: fresh every replay)
@@ -781,12 +818,12 @@ class DecodeSession:
 def run_decode(model, target, input_ids: torch.Tensor, *, mask_token_id: int, max_new_tokens: int,
                block_size: int, stop_token_ids, temperature: float, clamp_tail: bool,
                draft_steps: int = 1, collect_profile: bool = False, scheduler=None,
-               draft_temperature: float = 0.0, draft_token_hook: Optional[Callable] = None,
+               draft_temperature: Optional[float] = None, draft_token_hook: Optional[Callable] = None,
                max_block_size: Optional[int] = None, sampler: str = "torch", seed: Optional[int] = None,
                top_k: int = 0, top_p: float = 1.0, logprobs: Optional[int] = None, repetition_penalty: float = 1.0,
                presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None,
                banned_token_ids=None, min_tokens: int = 0, grammar=None,
-               constrain_draft: bool = False, min_p=None) -> SimpleNamespace:
+               constrain_draft: bool = False, min_p=None, couple_draft: bool = False) -> SimpleNamespace:
     s = DecodeSession(model, target, input_ids, mask_token_id=mask_token_id, max_new_tokens=max_new_tokens,
                       max_block_size=max_block_size or block_size, stop_token_ids=stop_token_ids,
                       temperature=temperature, draft_temperature=draft_temperature,
@@ -794,7 +831,7 @@ def run_decode(model, target, input_ids: torch.Tensor, *, mask_token_id: int, ma
                       logprobs=logprobs, repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
                       frequency_penalty=frequency_penalty, logit_bias=logit_bias, allowed_token_ids=allowed_token_ids,
                       banned_token_ids=banned_token_ids, min_tokens=min_tokens, grammar=grammar,
-                      constrain_draft=constrain_draft, min_p=min_p)
+                      constrain_draft=constrain_draft, min_p=min_p, couple_draft=couple_draft)
     t_prefill = cuda_time()
     s.prefill()
     time_to_first_token = cuda_time() - t_prefill
@@ -909,7 +946,7 @@ def run_decode(model, target, input_ids: torch.Tensor, *, mask_token_id: int, ma
 
 
 def _draft_ids(model, hid_frag, lm_wp, bs, blk, draft_temperature, keep_logits=None, seed=None, dyn=None, start=None,
-               lm_wp8=None):
+               lm_wp8=None, couple=None):
     """blk[0, 1:bs] <- draft tokens.  Greedy (every loop but the policy one at T>0):
     fused lm_head GEMM + argmax.  benchmark_dynamic_schedule.py:342 samples the draft
     with the temperature: then the logits are materialised by the same GEMM and the
@@ -919,7 +956,15 @@ def _draft_ids(model, hid_frag, lm_wp, bs, blk, draft_temperature, keep_logits=N
     starts at `start` draws position start + j, extra = start); dyn: the draft cache's record, whose START word holds
     that start on the device (what a captured graph reads).
     lm_wp8 (an fp8 draft model): the e4m3 lm_head, taken by the greedy unmask — of a block of <= 16 rows, or of a
-    17..32-row block that went through the tile stack; a sampled draft keeps the bf16 copy."""
+    17..32-row block that went through the tile stack; a sampled draft keeps the bf16 copy.
+    couple (dict(seed, temperature): the request's seed and the TARGET's temperature): the coupled
+    draw — the same epilogue on stream TARGET, slot j under the noise verify row j - 1 will draw position start + j with;
+    the bf16 head, as every sampled draft."""
+    if couple is not None:
+        model.draft_tokens(hid_frag, lm_wp, bs, blk[0], logits=keep_logits,
+                           sample=dict(seed=couple["seed"], temperature=couple["temperature"], dyn=dyn, start=start,
+                                       stream=ops.RNG_TARGET))
+        return
     if draft_temperature < 1e-5:
         from .model import WideRows
         wide = isinstance(hid_frag, WideRows)   # (both tiles in one ragged-batch lm_head pass)
@@ -963,8 +1008,14 @@ def dflash_generate(model, target, input_ids: torch.Tensor, mask_token_id: int, 
                     seed: Optional[int] = None, top_k: int = 0, top_p: float = 1.0,
                     logprobs: Optional[int] = None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
                     frequency_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None, banned_token_ids=None,
-                    min_tokens: int = 0, grammar=None, constrain_draft: bool = False, min_p=None) -> SimpleNamespace:
+                    min_tokens: int = 0, grammar=None, constrain_draft: bool = False, min_p=None,
+                    couple_draft: bool = False) -> SimpleNamespace:
     """benchmark.py:44-55 signature; returns the namespace of :242-251 (+ replayed_cycles).
+    couple_draft (False: off, the launches of before; at T > 0 needs sampler="device", else ValueError; at T = 0 it does
+    nothing): every draft token is picked under the noise the target's verify will draw that position with — Gumbel-max
+    coupling, DESIGN.md section 20.  The emitted ids do not change (the target's draw decides every token as before),
+    only the acceptance lengths.  The draft's head reads the bf16 lm_head for this launch, also in an fp8 / mxfp4 draft.
+    With constrain_draft the pick under the automaton is the perturbed maximum over the legal tokens.
     min_p (None / 0: off; a float in (0, 1]; needs a NativeTarget and sampler="device" at T > 0, does nothing at T = 0):
     the target's draw keeps token v only if p_v >= min_p * p_max on its tempered, processed distribution — one launch
     directly in front of every target draw, behind the logit bias, the grammar and the penalties; top_p takes its mass
@@ -1002,7 +1053,7 @@ def dflash_generate(model, target, input_ids: torch.Tensor, mask_token_id: int, 
                                      logprobs, (repetition_penalty, presence_penalty, frequency_penalty),
                                      dict(logit_bias=logit_bias, allowed_token_ids=allowed_token_ids,
                                           banned_token_ids=banned_token_ids, min_tokens=min_tokens),
-                                     constrain_draft=constrain_draft, min_p=min_p)
+                                     constrain_draft=constrain_draft, min_p=min_p, couple_draft=couple_draft)
     r = run_decode(model, target, input_ids, mask_token_id=mask_token_id, max_new_tokens=max_new_tokens,
                    block_size=block_size, stop_token_ids=stop_token_ids, temperature=temperature, clamp_tail=True,
                    draft_steps=draft_steps, collect_profile=collect_profile, draft_token_hook=draft_token_hook,
@@ -1010,7 +1061,7 @@ def dflash_generate(model, target, input_ids: torch.Tensor, mask_token_id: int, 
                    repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
                    frequency_penalty=frequency_penalty, logit_bias=logit_bias, allowed_token_ids=allowed_token_ids,
                    banned_token_ids=banned_token_ids, min_tokens=min_tokens, grammar=grammar,
-                   constrain_draft=constrain_draft, min_p=min_p)
+                   constrain_draft=constrain_draft, min_p=min_p, couple_draft=couple_draft)
     return SimpleNamespace(output_ids=r.output_ids, num_input_tokens=r.num_input_tokens,
                            num_output_tokens=r.num_output_tokens, time_to_first_token=r.time_to_first_token,
                            time_per_output_token=r.time_per_output_token, acceptance_lengths=r.acceptance_lengths,
@@ -1022,7 +1073,7 @@ def dflash_generate(model, target, input_ids: torch.Tensor, mask_token_id: int, 
 def _generate_wide_hidden(model, target, input_ids, mask_token_id, max_new_tokens, block_size, stop_token_ids, temperature,
                           collect_profile=False, draft_steps=1, draft_token_hook=None, sampler="torch",
                           seed=None, top_k=0, top_p=1.0, logprobs=None, penalties=(1.0, 0.0, 0.0),
-                          bias=None, constrain_draft=False, min_p=None) -> SimpleNamespace:
+                          bias=None, constrain_draft=False, min_p=None, couple_draft=False) -> SimpleNamespace:
     """hidden_size > 4096: the request runs as a group of ONE through the ragged-batch kernels (their GEMMs cut K over
     workgroups; the single-request kernels keep a whole K = hidden row slice per workgroup).  Same loop semantics
     (benchmark.py:44-251, tail clamp included); no per-cycle profile, one draft step per cycle."""
@@ -1039,7 +1090,7 @@ def _generate_wide_hidden(model, target, input_ids, mask_token_id, max_new_token
                                  seed=None if seed is None else [seed], top_k=top_k, top_p=top_p, logprobs=logprobs,
                                  repetition_penalty=penalties[0], presence_penalty=penalties[1],
                                  frequency_penalty=penalties[2], **_one_prompt_bias(bias),
-                                 constrain_draft=constrain_draft, min_p=min_p)[0]
+                                 constrain_draft=constrain_draft, min_p=min_p, couple_draft=couple_draft)[0]
 
 
 def _one_prompt_bias(bias) -> dict:
@@ -1058,8 +1109,10 @@ def dflash_generate_policy(*, model, target, input_ids: torch.Tensor, mask_token
                            logprobs: Optional[int] = None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
                            frequency_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None, banned_token_ids=None,
                            min_tokens: int = 0, grammar=None, constrain_draft: bool = False,
-                           min_p=None) -> SimpleNamespace:
+                           min_p=None, couple_draft: bool = False) -> SimpleNamespace:
     """benchmark_dynamic_schedule.py:260-272 signature; returns the namespace of :425-434 (+ replayed_cycles).
+    couple_draft: as dflash_generate; here it REPLACES this loop's own draw on the DRAFT stream (whose acceptance,
+    sum p_i q_i, is the lowest of the three drafts), and constrain_draft then works at T > 0.
     min_p: as dflash_generate (the target's draw; the draft's own draw stays unfiltered).
     grammar: as dflash_generate (the target's rows; the draft's own draw stays unconstrained; `grammar_state`).
     constrain_draft: as dflash_generate; this loop drafts at the request's temperature, so it needs temperature = 0
@@ -1080,7 +1133,7 @@ def dflash_generate_policy(*, model, target, input_ids: torch.Tensor, mask_token
                    logprobs=logprobs, repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
                    frequency_penalty=frequency_penalty, logit_bias=logit_bias, allowed_token_ids=allowed_token_ids,
                    banned_token_ids=banned_token_ids, min_tokens=min_tokens, grammar=grammar,
-                   constrain_draft=constrain_draft, min_p=min_p)
+                   constrain_draft=constrain_draft, min_p=min_p, couple_draft=couple_draft)
     if fixed_block_size is not None:
         for row in r.cycle_trace:
             for k in ("tau_hat", "cycle_hat", "score_hat", "current_block_size", "adl_lgen_hat", "adl_lacc_hat",

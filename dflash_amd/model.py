@@ -620,8 +620,11 @@ class DFlashDraftModel:
         logit of block slot j >= 1, the reference's per-position confidence
         (benchmark_candidate_solutions.py:296-302).
         sample (the device sampler): dict(seed, temperature, dyn, start) — slot j draws the seeded
-        stream-DRAFT noise of position start + j (extra = start), start from dyn's START word when dyn is given."""
+        stream-DRAFT noise of position start + j (extra = start), start from dyn's START word when dyn is given.
+        sample["stream"] (default ops.RNG_DRAFT): ops.RNG_TARGET is the coupled draft — the noise
+        the target's verify row j - 1 draws position start + j with (extra = 0; temperature: the target's)."""
         c, ws = self.config, self._workspace()
+        rng = ops.RNG_DRAFT if sample is None else int(sample.get("stream", ops.RNG_DRAFT))
         if isinstance(hid_frag, WideRows):   # both tiles in one lm_head pass (ragged-batch GEMM, R = 2)
             if margins is not None:
                 raise NotImplementedError("top-2 margins are computed for blocks of <= 16 rows")
@@ -638,7 +641,7 @@ class DFlashDraftModel:
                     raise ValueError("a sampled draft of more than 16 rows needs the block start on the host")
                 st = int(sample["start"])
                 ops.sample_rows(logits.view(-1, c.vocab_size)[:bs], seed=sample["seed"], temperature=sample["temperature"],
-                                pos0=st, stream=ops.RNG_DRAFT, extra=st, out=ids.view(-1)[:bs])
+                                pos0=st, stream=rng, extra=st if rng == ops.RNG_DRAFT else 0, out=ids.view(-1)[:bs])
             block_ids[1:bs].copy_(ids.view(-1)[1:bs])
             return
         srcs = hid_frag if isinstance(hid_frag, (list, tuple)) else [hid_frag]
@@ -652,7 +655,7 @@ class DFlashDraftModel:
                 if dyn is None and sample.get("start") is None:
                     raise ValueError("a sampled draft needs the block start: a length record or the host value")
                 ops.gemm_sample(lm_head_wp, x, c.vocab_size, c.hidden_size, row0, nrows, ws["argmax_ws"], block_ids,
-                                16 * t + row0, seed=sample["seed"], temperature=sample["temperature"], stream=ops.RNG_DRAFT,
+                                16 * t + row0, seed=sample["seed"], temperature=sample["temperature"], stream=rng,
                                 pos_dyn=dyn, pos_word=ops.DYN_START, pos_base=int(sample.get("start") or 0),
                                 pos_add=16 * t, logits=None if logits is None else logits[16 * t:16 * t + 16],
                                 margins=margins)
@@ -714,11 +717,13 @@ class DFlashDraftModel:
                       seed: Optional[int] = None, top_k: int = 0, top_p: float = 1.0, repetition_penalty: float = 1.0,
                       presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None,
                       allowed_token_ids=None, banned_token_ids=None, min_tokens: int = 0,
-                      grammar=None, constrain_draft: bool = False, min_p=None) -> torch.LongTensor:
+                      grammar=None, constrain_draft: bool = False, min_p=None,
+                      couple_draft: bool = False) -> torch.LongTensor:
         """model/dflash.py:192-277.  sampler / seed / top_k / top_p: as dflash_generate; min_p
         likewise (section 18);
         repetition_penalty / presence_penalty / frequency_penalty likewise (section 13); logit_bias / allowed_token_ids /
-        banned_token_ids / min_tokens likewise (section 14); grammar and constrain_draft likewise (section 15)."""
+        banned_token_ids / min_tokens likewise (section 14); grammar and constrain_draft likewise (section 15); couple_draft likewise
+        (section 20)."""
         bias = dict(logit_bias=logit_bias, allowed_token_ids=allowed_token_ids, banned_token_ids=banned_token_ids,
                     min_tokens=min_tokens)
         pen = dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
@@ -731,9 +736,11 @@ class DFlashDraftModel:
                                          stop_token_ids, temperature, draft_token_hook=draft_token_hook, sampler=sampler,
                                          seed=seed, top_k=top_k, top_p=top_p,
                                          penalties=tuple(pen.values()), bias=bias,
-                                         constrain_draft=constrain_draft, min_p=min_p).output_ids
+                                         constrain_draft=constrain_draft, min_p=min_p,
+                                         couple_draft=couple_draft).output_ids
         r = run_decode(self, target, input_ids, mask_token_id=self.mask_token_id, max_new_tokens=max_new_tokens,
                        block_size=self.block_size, stop_token_ids=stop_token_ids, temperature=temperature,
                        clamp_tail=False, draft_token_hook=draft_token_hook, sampler=sampler, seed=seed, top_k=top_k,
-                       top_p=top_p, **pen, **bias, grammar=grammar, constrain_draft=constrain_draft, min_p=min_p)
+                       top_p=top_p, **pen, **bias, grammar=grammar, constrain_draft=constrain_draft, min_p=min_p,
+                       couple_draft=couple_draft)
         return r.output_ids

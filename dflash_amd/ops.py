@@ -1263,6 +1263,39 @@ def grammar_draft_rows(logits: torch.Tensor, state=None, *, bias: Optional[torch
     the grammar-only form).  The walk stops, and the ids from there on stay, at a violated state, a row without such a
     column, or a successor outside the pool.  n = nrows (None: the logits' rows), or dyn[t][nrows_dyn_word].  The
     state is only read.  tiles_per_req = 2 (17..32-row blocks) is refused."""
+    args = _grammar_draft_args(logits, state, bias, block, nrows, dyn, nrows_dyn_word, tiles_per_req)
+    check(lib().dfl_grammar_draft_rows(*args, _stream()), "dfl_grammar_draft_rows")
+
+
+def grammar_draft_sample_rows(logits: torch.Tensor, state=None, *, bias: Optional[torch.Tensor] = None, block: torch.Tensor,
+                              seeds: torch.Tensor, temperature: Optional[float] = None,
+                              inv_ts: Optional[torch.Tensor] = None, pos_dyn_word: int = -1, pos_base: int = 0,
+                              nrows: Optional[int] = None, dyn=None, nrows_dyn_word: int = -1,
+                              tiles_per_req: int = 1) -> None:
+    """grammar_draft_rows under the target's noise (dfl_grammar_draft_sample_rows): block[q, m] <-
+    the lowest legal column among the maxima of fmaf(logit, invT, g(seeds[q], RNG_TARGET, base_q + m, v, 0)) over the
+    legal columns of row m — what the coupled draft head drew, restricted to what the request can emit.  seeds: int64
+    [slots] on the device.  Either `temperature` (one host value) or inv_ts (device fp32 [slots]; a slot whose value is
+    not > 0 gets grammar_draft_rows' plain pick).  base_q = dyn[q][pos_dyn_word] (the draft record's DYN_START) when
+    pos_dyn_word >= 0, else pos_base."""
+    if (temperature is None) == (inv_ts is None):
+        raise ValueError("grammar_draft_sample_rows: give either temperature or inv_ts")
+    args = _grammar_draft_args(logits, state, bias, block, nrows, dyn, nrows_dyn_word, tiles_per_req)
+    tiles = args[3]
+    if seeds.dtype != I64 or not seeds.is_cuda or seeds.numel() < tiles:
+        raise TypeError("dflash_amd: seeds must be an int64 GPU tensor with one seed per slot")
+    if inv_ts is not None and (inv_ts.dtype != F32 or not inv_ts.is_cuda or inv_ts.numel() < tiles):
+        raise TypeError("dflash_amd: inv_ts must be an fp32 GPU tensor with one value per slot")
+    if pos_dyn_word >= 0:
+        assert dyn is not None and dyn.numel() >= 8 * tiles, "pos_dyn_word needs the records"
+    check(lib().dfl_grammar_draft_sample_rows(*args, seeds.data_ptr(),
+                                              0.0 if inv_ts is not None else inv_temperature(temperature),
+                                              _p(inv_ts, F32, "inv_ts"), pos_dyn_word, int(pos_base), _stream()),
+          "dfl_grammar_draft_sample_rows")
+
+
+def _grammar_draft_args(logits, state, bias, block, nrows, dyn, nrows_dyn_word, tiles_per_req) -> tuple:
+    """The arguments dfl_grammar_draft_rows and its noise form share, validated."""
     if tiles_per_req != 1:
         raise NotImplementedError("dflash_amd: grammar_draft_rows takes one tile per request (blocks of <= 16 rows)")
     if state is None and bias is None:
@@ -1300,9 +1333,8 @@ def grammar_draft_rows(logits: torch.Tensor, state=None, *, bias: Optional[torch
     assert tiles == 1 or blk_stride >= 16, "block: one row of >= 16 ids per slot"
     if dyn is not None:
         assert dyn.numel() >= 8 * tiles
-    check(lib().dfl_grammar_draft_rows(logits.data_ptr(), ld, tile_stride, tiles, V, nrows, _p(dyn, I32, "dyn"),
-                                       nrows_dyn_word, t_p, t_stride, t_rows, b_p, s_p, bias_p, bias_stride,
-                                       block.data_ptr(), blk_stride, _stream()), "dfl_grammar_draft_rows")
+    return (logits.data_ptr(), ld, tile_stride, tiles, V, nrows, _p(dyn, I32, "dyn"), nrows_dyn_word, t_p, t_stride, t_rows,
+            b_p, s_p, bias_p, bias_stride, block.data_ptr(), blk_stride)
 
 
 def grammar_advance(state, ids: torch.Tensor, *, lo: int = 0, hi: int = 0, dyn=None, lo_word: int = 0,

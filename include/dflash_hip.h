@@ -666,6 +666,21 @@ int dfl_grammar_draft_rows(const void *logits, int64_t ld, int64_t tile_stride, 
                            int pool_states, const int32_t *base, const int32_t *state, const float *bias,
                            int64_t bias_stride, int64_t *block_ids, int64_t block_stride, void *stream);
 
+/* dfl_grammar_draft_sample_rows: the noise form of dfl_grammar_draft_rows ("The coupled draft under
+ * a grammar").  Every argument up to block_stride, the walk, the stops and what is left untouched are the sibling's; the
+ * quantity compared over the legal columns of row m of slot t is
+ *   key(v) = fmaf(bf16 logit[v], invT_t, g(seeds[t], DFL_RNG_TARGET, p = base_t + m, v, extra = 0))      (dfl_rng.h)
+ * — the noise the target's verify row m - 1 draws position base_t + m with — and c is the lowest legal column among
+ * those whose key is maximal over the legal columns with a non-NaN key.  base_t = dyn[t][pos_dyn_word] when
+ * pos_dyn_word >= 0 (the draft record's DFL_DYN_START), else pos_base.  seeds: int64 [tiles].  invT_t = inv_ts[t] (fp32
+ * [tiles]) when inv_ts is given, else inv_t; a slot whose invT is not > 0 (0, negative, NaN) compares the logits
+ * themselves: the sibling's pick, bit for bit.  Philox is called once per four columns, only where one of them is legal. */
+int dfl_grammar_draft_sample_rows(const void *logits, int64_t ld, int64_t tile_stride, int tiles, int V, int nrows,
+                                  const int32_t *dyn, int nrows_dyn_word, const int16_t *table, int64_t table_stride,
+                                  int pool_states, const int32_t *base, const int32_t *state, const float *bias,
+                                  int64_t bias_stride, int64_t *block_ids, int64_t block_stride, const int64_t *seeds,
+                                  float inv_t, const float *inv_ts, int pos_dyn_word, int pos_base, void *stream);
+
 /* Acceptance scan + commit + bonus token + stop test + length bookkeeping in one
  * wavefront (model/dflash.py:258-268):
  *   acc = #leading i with block[i+1] == posterior[i]           (0..bs-1)
