@@ -16,8 +16,10 @@ from .model import DFlashDraftModel, DFlashKVCache
 from .generate import dflash_generate, dflash_generate_policy
 from .target import NativeTarget
 from .candidates import dflash_generate_candidate_solutions
-from .grammar import TokenDFA
+from .grammar import ByteGrammar, TokenDFA, Vocabulary, compile_grammar
+from .json_schema import json_schema_regex
+from .regex import ByteDFA, compile_regex
 
-__all__ = ["TokenDFA","DFlashConfig", "DFlashDraftModel", "DFlashKVCache", "EWMAPerformanceScheduler",
+__all__ = ["TokenDFA", "ByteDFA", "ByteGrammar", "Vocabulary", "compile_regex", "json_schema_regex", "compile_grammar","DFlashConfig", "DFlashDraftModel", "DFlashKVCache", "EWMAPerformanceScheduler",
            "build_target_layer_ids", "extract_context_feature", "sample", "dflash_generate",
            "dflash_generate_policy", "NativeTarget", "dflash_generate_candidate_solutions"]

@@ -77,6 +77,8 @@ SIGNATURES = {
     "dfl_grammar_draft_rows": (_i, [_p, _i64, _i64, _i, _i, _i, _p, _i, _p, _i64, _i, _p, _p, _p, _i64, _p, _i64, _p]),
     "dfl_grammar_draft_sample_rows": (_i, [_p, _i64, _i64, _i, _i, _i, _p, _i, _p, _i64, _i, _p, _p, _p, _i64, _p, _i64, _p, _f,
                                            _p, _i, _i, _p]),
+    "dfl_grammar_lift": (_i, [_p, _i64, _i, _i, _i, _p, _i, _p, _i64, _p, _p, _p, _i, _p]),
+    "dfl_grammar_reach": (_i, [_p, _i64, _i, _i, _i, _i, _p, _p, _p, _p]),
     "dfl_norm_pack": (_i, [_p, _i, _i64, _i, _i, _p, _p, _p, _p, _p, _i64, _p, _f, _p, _i, _p, _i, _p]),
     "dfl_qknorm_rope_append": (_i, [_p, _i, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _f, _p, _p, _i, _p, _p, _p, _i, _p,
                                     _i, _i, _p]),

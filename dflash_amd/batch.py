@@ -263,7 +263,10 @@ class BatchedDecoder:
         pen = ops.check_penalties(*penalties)
         lb = self.check_bias(**bias) if bias else None
         if gr is not None and lb is not None:   # a reachable state whose legal tokens this request's bias bans all
-            ops.check_grammar(gr[1], t.V, lb[0])
+            if ops.is_byte_grammar(gr[1]):   # a ByteGrammar: its table exists on the device only
+                ops.grammar_reach_check(self.grammar, gr[0], gr[1].num_states, gr[1].start, lb[0])
+            else:
+                ops.check_grammar(gr[1], t.V, lb[0])
         flt = None
         if ops.check_filter(top_k, top_p) and temperature >= 1e-5:
             flt = dict(top_k=int(top_k), top_p=float(top_p))
@@ -322,11 +325,14 @@ class BatchedDecoder:
     grammar = None   # (the state of a decoder built with grammar_states > 0)
 
     def add_grammar(self, dfa) -> int:
-        """Validate a TokenDFA (ops.check_grammar) and copy its table into the pool's next free rows; returns the handle
+        """Validate a TokenDFA (ops.check_grammar) and copy its table into the pool's next free rows — a ByteGrammar is lifted
+        there on the device instead (ops.grammar_load); returns the handle
         admit takes.  ValueError when the decoder was built without a pool or the pool is full.  The pool's address is
         fixed, so a captured cycle serves grammars loaded after the capture."""
         if self.grammar is None:
             raise ValueError("add_grammar needs a decoder built with grammar_states > 0")
+        if ops.is_byte_grammar(dfa) and dfa.num_states > ops.LIFT_MAX_STATES:   # too large to lift: the host's table
+            dfa = dfa.to_token_dfa()
         base = ops.grammar_load(self.grammar, dfa)
         self._grammars.append((base, dfa))
         return len(self._grammars) - 1
@@ -815,7 +821,7 @@ def _prompt_bias(target, logit_bias, allowed_token_ids, banned_token_ids, min_to
 
 def _prompt_grammars(grammar, n: int) -> list:
     """One TokenDFA (or None) per prompt: None or one TokenDFA for every prompt, or a sequence of n (TokenDFA or None)."""
-    if grammar is None or hasattr(grammar, "next"):
+    if grammar is None or hasattr(grammar, "next") or hasattr(grammar, "char_next"):
         return [grammar] * n
     g = list(grammar)
     if len(g) != n:
@@ -835,7 +841,7 @@ def _load_grammars(dec, dfas) -> list:
 
 def _pool_rows(dfas) -> int:
     """The pool rows the distinct (validated) automata among `dfas` need (0: none given)."""
-    return sum(int(d.next.shape[0]) for d in {id(d): d for d in dfas if d is not None}.values())
+    return sum(int(d.num_states) for d in {id(d): d for d in dfas if d is not None}.values())
 
 
 @torch.inference_mode()

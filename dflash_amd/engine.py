@@ -220,8 +220,9 @@ class BatchEngine:
         return req.rid
 
     def add_grammar(self, dfa) -> int:
-        """Load a TokenDFA into the engine's pool; the handle submit(..., grammar=handle) takes.  ValueError when the pool
-        is full or the engine was built with grammar_states = 0."""
+        """Load a TokenDFA, or a ByteGrammar (lifted on the device), into the engine's pool; the
+        handle submit(..., grammar=handle) takes.  ValueError when the pool is full or the engine was built with
+        grammar_states = 0."""
         return self.dec.add_grammar(dfa)
 
     @torch.inference_mode()

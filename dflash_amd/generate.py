@@ -297,14 +297,16 @@ class DecodeSession:
                 ops.check_grammar(grammar, target.V, None if lb is None else lb[0])
             self.stage = LogitsStage(1, target.V, dev, tiles=2 if self.max_bs > 16 else 1, out_len=self.output_ids.shape[1],
                                      logprobs=self.logprobs, penalties=pen is not None, logit_bias=lb is not None,
-                                     grammar_states=grammar.next.shape[0] if grammar is not None else 0,
+                                     grammar_states=grammar.num_states if grammar is not None else 0,
                                      min_p=mp is not None, filtering=self._filter is not None,
                                      sampling=temperature >= 1e-5, stop_ids=self.stop_t)
             self._vkw = dict(stage=self.stage)
             self._gr_start = int(grammar.start) if grammar is not None else None
             self._admit = dict(penalties=pen, min_p=mp, flt=self._filter,
                                bias=(lb[0], self.n_in + lb[1] if lb[1] else 0) if lb is not None else None,
-                               grammar=(self.stage.load_grammar(grammar), self._gr_start) if grammar is not None else None)
+                               grammar=(self.stage.load_grammar(grammar, lb[0] if lb is not None and ops.is_byte_grammar(grammar)
+                                                                 else None), self._gr_start)
+                               if grammar is not None else None)
         # what the session's own code and its observers read of the stage: the logprob sink, the penalty table, the
         # grammar state (None each where the feature is off)
         st = self.stage
@@ -1020,7 +1022,7 @@ def dflash_generate(model, target, input_ids: torch.Tensor, mask_token_id: int, 
     the target's draw keeps token v only if p_v >= min_p * p_max on its tempered, processed distribution — one launch
     directly in front of every target draw, behind the logit bias, the grammar and the penalties; top_p takes its mass
     over what min_p kept; blocks of up to 32 rows.  The draft's proposals stay unfiltered.
-    grammar (a dflash_amd.TokenDFA; None: off; needs a NativeTarget, blocks of <= 16 rows, and sampler="device" at
+    grammar (a dflash_amd.TokenDFA or ByteGrammar; None: off; needs a NativeTarget, blocks of <= 16 rows, and sampler="device" at
     T > 0): the emitted tokens walk the automaton from its start state — every verify row is masked by the state its
     own prefix of the block reaches, between the logit bias and the penalties.  The result's
     `grammar_state` is the state after the returned tokens (-1: violated; None when off).  The draft's proposals stay

@@ -1110,6 +1110,15 @@ def check_grammar(dfa, V: int, logit_bias_row=None) -> None:
     where logit_bias_row (fp32 [V], the row check_logit_bias returns) is given, one that it does not ban."""
     import numpy as np
     import operator
+    if is_byte_grammar(dfa):   # the host-side checks only: reachability is checked on the loaded rows (grammar_load)
+        S, Vd = dfa.num_states, dfa.vocab_size
+        if not 1 <= S <= 32767:
+            raise ValueError(f"dflash_amd: grammar: {S} states, 1..32767 fit the int16 table")
+        if Vd != int(V) or Vd < 8 or Vd % 8:
+            raise ValueError(f"dflash_amd: grammar: the vocabulary has {Vd} tokens, the model's {V} (a multiple of 8)")
+        if not 0 <= dfa.start < S:
+            raise ValueError(f"dflash_amd: grammar: start {dfa.start} outside [0, {S})")
+        return
     nxt = getattr(dfa, "next", None)
     if not isinstance(nxt, np.ndarray) or nxt.dtype != np.int16 or nxt.ndim != 2:
         raise ValueError("dflash_amd: grammar: TokenDFA.next must be an int16 numpy array [S, V]")
@@ -1165,19 +1174,108 @@ def grammar_state(slots: int, pool_states: int, V: int, device) -> SimpleNamespa
                            state=torch.full((slots,), -1, dtype=I32, device=device), used=0)
 
 
+LIFT_MAX_STATES = 4096   # dfl_grammar_lift / dfl_grammar_reach: the largest automaton lifted and checked on the device
+
+
+def is_byte_grammar(g) -> bool:
+    return hasattr(g, "char_next") and hasattr(g, "vocabulary")
+
+
 def grammar_load(state, dfa, logit_bias_row=None) -> int:
-    """Validate dfa (check_grammar) and copy its table into the next free pool rows; returns their base.  ValueError when
-    the pool has fewer rows left than the grammar has states.  The pool's storage never moves."""
+    """Validate dfa (check_grammar) and put its table into the next free pool rows; returns their base.  A TokenDFA's
+    table is copied; a ByteGrammar is lifted on the device (grammar_lift) and its reachability is checked on the rows
+    just written (grammar_reach_check: on failure the rows are filled back with -1 and `used` stays) — above
+    LIFT_MAX_STATES states it loads as its to_token_dfa().  ValueError when the pool has fewer rows left than the
+    grammar has states.  The pool's storage never moves."""
     pool, V = state.table.shape
     check_grammar(dfa, V, logit_bias_row)
-    S = dfa.next.shape[0]
+    if is_byte_grammar(dfa) and dfa.num_states > LIFT_MAX_STATES:
+        dfa = dfa.to_token_dfa()
+        check_grammar(dfa, V, logit_bias_row)
+    S = dfa.num_states if is_byte_grammar(dfa) else dfa.next.shape[0]
     if state.used + S > pool:
         raise ValueError(f"dflash_amd: the grammar pool is full: {S} states asked, {pool - state.used} of {pool} rows free")
     base = state.used
-    import numpy as np
-    state.table[base:base + S].copy_(torch.from_numpy(np.ascontiguousarray(dfa.next)))
+    if is_byte_grammar(dfa):
+        grammar_lift(state, dfa, base)
+        try:
+            grammar_reach_check(state, base, S, dfa.start, logit_bias_row)
+        except ValueError:
+            state.table[base:base + S].fill_(-1)
+            raise
+    else:
+        import numpy as np
+        state.table[base:base + S].copy_(torch.from_numpy(np.ascontiguousarray(dfa.next)))
     state.used = base + S
     return base
+
+
+def grammar_lift(state, grammar, base: int) -> None:
+    """dfl_grammar_lift: pool rows [base, base + grammar.num_states) of state.table from a
+    ByteGrammar's byte automaton and its Vocabulary's device buffers — TokenDFA.from_bytes' table, entry for entry.  Only
+    the automaton ([Sc, 256] int16), the accepting flags and, once per vocabulary and device, the byte strings cross the
+    bus."""
+    import numpy as np
+    table = _grammar_pool(state)
+    dev = table.device
+    data, off, eos = grammar.vocabulary.device_buffers(dev)
+    Sc = grammar.num_states
+    if off.numel() != table.shape[1] + 1:
+        raise ValueError(f"dflash_amd: grammar_lift: the vocabulary has {off.numel() - 1} tokens, the pool {table.shape[1]}")
+    acc = np.zeros(Sc, dtype=np.uint8)
+    acc[list(grammar.accepting)] = 1
+    dfa = torch.from_numpy(grammar.char_next).to(dev)
+    acc_t = torch.from_numpy(acc).to(dev)
+    n_eos = len(grammar.vocabulary.eos_ids)
+    check(lib().dfl_grammar_lift(table.data_ptr(), table.stride(0), table.shape[0], table.shape[1], int(base),
+                                 _p(dfa, I16, "dfa"), Sc, _p(data, U8, "token bytes"), data.numel(),
+                                 _p(off, I32, "token offsets"), _p(acc_t, U8, "accepting"),
+                                 _p(eos, I32, "eos ids") if n_eos else None, n_eos, _stream()), "dfl_grammar_lift")
+
+
+def grammar_reach(state, base: int, S: int, logit_bias_row=None):
+    """dfl_grammar_reach over pool rows [base, base + S): (adj uint8 [S, S], any_legal uint8 [S]) on the device.
+    adj[s, t] = 1 iff a legal token that logit_bias_row (fp32 [V]; -inf: banned) does not ban leads from s to t;
+    any_legal[s] = 1 iff s has a legal token at all."""
+    table = _grammar_pool(state)
+    V = table.shape[1]
+    bias = None
+    if logit_bias_row is not None:
+        bias = torch.as_tensor(logit_bias_row, dtype=F32).to(table.device).contiguous()
+        if bias.shape != (V,):
+            raise ValueError(f"dflash_amd: grammar: the bias row has shape {tuple(bias.shape)}, the vocabulary ({V},)")
+    adj = torch.empty((S, S), dtype=U8, device=table.device)
+    any_legal = torch.empty((S,), dtype=U8, device=table.device)
+    check(lib().dfl_grammar_reach(table.data_ptr(), table.stride(0), table.shape[0], V, int(base), int(S),
+                                  _p(bias, F32, "bias row"), adj.data_ptr(), any_legal.data_ptr(), _stream()),
+          "dfl_grammar_reach")
+    return adj, any_legal
+
+
+def grammar_reach_check(state, base: int, S: int, start: int, logit_bias_row=None) -> None:
+    """check_grammar's reachability check on loaded rows: grammar_reach, its two results copied back, and a breadth-first
+    search from start over adj.  The same two ValueErrors: a reachable state without a legal token, a reachable state
+    whose legal tokens the bias row bans all.  (The search follows the tokens that can be emitted — legal and not banned
+    — where check_grammar follows every legal one.)"""
+    adj, any_legal = grammar_reach(state, base, S, logit_bias_row)
+    adj, any_legal = adj.cpu().numpy().astype(bool), any_legal.cpu().numpy().astype(bool)
+    reached = [False] * S
+    reached[start] = True
+    frontier = [start]
+    while frontier:
+        nxt = []
+        for s in frontier:
+            if not any_legal[s]:
+                raise ValueError(f"dflash_amd: grammar: state {s} is reachable from start {start} and has no legal token")
+            succ = adj[s].nonzero()[0]
+            if not succ.size:
+                raise ValueError(f"dflash_amd: grammar: every legal token of reachable state {s} is "
+                                 f"banned by logit_bias / allowed_token_ids / banned_token_ids")
+            for t in succ.tolist():
+                if not reached[t]:
+                    reached[t] = True
+                    nxt.append(t)
+        frontier = sorted(nxt)
 
 
 def grammar_set(state, slot: int, base, start: int = 0) -> None:

@@ -681,6 +681,31 @@ int dfl_grammar_draft_sample_rows(const void *logits, int64_t ld, int64_t tile_s
                                   int64_t bias_stride, int64_t *block_ids, int64_t block_stride, const int64_t *seeds,
                                   float inv_t, const float *inv_ts, int pos_dyn_word, int pos_base, void *stream);
 
+/* dfl_grammar_lift: a byte automaton lifted to the pool's token rows on the device.  dfa: int16
+ * [Sc][256] on the device (16-byte aligned), dfa[s * 256 + b] the state after byte b in state s, < 0 (or >= Sc): dead.
+ * tok_bytes (uint8, n_bytes of them) holds the vocabulary's byte strings back to back, token v being
+ * tok_bytes[tok_off[v] .. tok_off[v + 1]) (tok_off int32 [V + 1]; a token whose range is empty, reversed or outside the
+ * buffer is illegal everywhere).  accepting: uint8 [Sc], nonzero = accepting.  eos_ids: int32 [n_eos] (NULL with
+ * n_eos = 0).  Writes rows [base, base + Sc) of the pool, columns [0, V):
+ *   table[(base + s) * table_stride + v] = the state where walking token v's bytes from s ends (relative to base), -1 if
+ *                                          the walk dies or the token is empty
+ *   v an eos id:                           s where accepting[s], -1 elsewhere (whatever its bytes give)
+ * Columns >= V and every other row are not touched.  Refused (DFL_EINVAL, nothing launched): a null pointer, V % 8, Sc
+ * outside 1..4096, base < 0 or base + Sc > pool_states, table_stride < V or not a multiple of 8, rows off 16 bytes.
+ * Plain 16-byte vector stores, no atomics; every pool offset is formed in 64 bits. */
+int dfl_grammar_lift(int16_t *table, int64_t table_stride, int pool_states, int V, int base, const int16_t *dfa, int Sc,
+                     const uint8_t *tok_bytes, int64_t n_bytes, const int32_t *tok_off, const uint8_t *accepting,
+                     const int32_t *eos_ids, int n_eos, void *stream);
+
+/* dfl_grammar_reach: which states a loaded grammar's states lead to.  Reads pool rows [base, base + S), 1 <= S <= 4096,
+ * columns [0, V); bias (optional, fp32 [V]): a column holding -inf is banned.  Writes, whole,
+ *   adj uint8 [S][S]:    adj[s * S + t] = 1 iff some token v with table[(base + s) * table_stride + v] = t that is not
+ *                        banned exists, else 0
+ *   any_legal uint8 [S]: 1 iff row s has a legal token at all (banned or not)
+ * The same refusals as dfl_grammar_lift.  Byte stores of a value that does not depend on the order of the threads. */
+int dfl_grammar_reach(const int16_t *table, int64_t table_stride, int pool_states, int V, int base, int S,
+                      const float *bias, uint8_t *adj, uint8_t *any_legal, void *stream);
+
 /* Acceptance scan + commit + bonus token + stop test + length bookkeeping in one
  * wavefront (model/dflash.py:258-268):
  *   acc = #leading i with block[i+1] == posterior[i]           (0..bs-1)
