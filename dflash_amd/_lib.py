@@ -145,6 +145,7 @@ SIGNATURES = {
     "dfl_accept_commit_batch": (_i, [_p, _i64, _p, _i64, _i, _p, _i64, _i64, _p, _p, _p, _i, _p, _p, _i64, _i, _p, _p, _p]),
     "dfl_admit_slot": (_i, [_i, _i, _p, _i, _p, _p, _i64, _i64, _p, _p, _i, _p, _p, _i64, _i, _p, _i, _p, _p, _i, _p, _i64,
                             _i64, _p]),
+    "dfl_stop_seq_rows": (_i, [_p, _i64, _p, _i64, _p, _i64, _i64, _p, _i, _i, _p, _p, _p, _p, _p, _p]),
 }
 
 _lib = None

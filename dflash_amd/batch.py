@@ -26,7 +26,8 @@ from typing import Callable, Optional, Sequence
 import torch
 
 from . import ops
-from .generate import (NO_LOGPROBS, _bf16_table, _draw_rows, _kept_cols, _taps, _trim, capture_graph, check_couple_draft,
+from .generate import (NO_LOGPROBS, _bf16_table, _draw_rows, _kept_cols, _stop_hit, _taps, _trim, capture_graph, check_couple_draft,
+                       first_token_stop,
                        cuda_time, logprob_fields, resolve_seed)
 from .logits_stage import LogitsStage, check_features
 from .model import DFlashDraftModel
@@ -58,8 +59,11 @@ class BatchedDecoder:
                  draft_temperature: float = 0.0, filtering: bool = False, request_temperature: bool = False,
                  logprobs: Optional[int] = None, penalties: bool = False, logit_bias: bool = False,
                  grammar_states: int = 0, constrain_draft: bool = False, min_p: bool = False,
-                 couple_draft: bool = False):
-        """filtering / logprobs / penalties / logit_bias / grammar_states / min_p: which row processors the verify runs
+                 couple_draft: bool = False, stop_sequences: bool = False):
+        """stop_sequences (fixed here: it fixes the captured launch sequence): dfl_stop_seq_rows directly in front of every
+        accept launch, over every slot's own table of stop sequences (admit(..., stop_sequences=...); DESIGN.md section
+        22).  Off: the launches of before, nothing allocated, and a request that carries sequences is refused.
+        filtering / logprobs / penalties / logit_bias / grammar_states / min_p: which row processors the verify runs
         between its head launch and the posterior (logits_stage.LogitsStage has the order, what each reads and the
         DESIGN.md sections).  Fixed here: they fix the captured launch sequence and the addresses it reads.  Requests
         carry their own values (admit); a slot at the neutral values gets the ids of a decoder built without the
@@ -179,6 +183,9 @@ class BatchedDecoder:
         self._cd_logits = z(MT, 16, target.V) if self.constrain_draft else None
         self.output_ids = torch.full((NREQ, out_len), self.mask_id, dtype=I64, device=dev)
         self.stop_token_ids = list(stop_token_ids) if stop_token_ids else None
+        # stop sequences: one table row and one hit record per request slot, read by address (None: off)
+        self.sq = ops.stop_seq_state(NREQ, dev) if stop_sequences else None
+        self.stop_seqs = [None] * NREQ   # host mirror: the slot's sequences as admitted (the trim needs their lengths)
         # ---- draft scratch
         self.nqkv_d = c.q_dim + 2 * c.kv_dim
         self.nkv_all = Ld * 2 * c.kv_dim
@@ -322,6 +329,32 @@ class BatchedDecoder:
                              "logit_bias=True")
         return lb
 
+    def check_stop_sequences(self, stop_sequences):
+        """ops.check_stop_sequences of one request's value against this decoder's vocabulary and mask id: None (none), or
+        the list of lists.  A request that carries sequences needs a decoder built with stop_sequences=True."""
+        if stop_sequences is None:
+            return None
+        seqs = ops.check_stop_sequences(stop_sequences, self.target.V, self.mask_id)
+        if seqs is not None and getattr(self, "sq", None) is None:
+            raise ValueError("stop_sequences need a decoder built with stop_sequences=True")
+        return seqs
+
+    def _admit_stop(self, r: int, P: int, seqs, min_tokens) -> None:
+        """Behind the slot's records: its table rows rewritten whole (nothing of the previous request survives), then the
+        first token — produced before any accept launch runs — through the same launch over a one-row block
+        (generate.first_token_stop), its stop word ORed into the slot's draft-form record on the device."""
+        self.stop_seqs[r] = seqs
+        if self.sq is None:
+            return
+        mt = int(min_tokens) if seqs else 0
+        ops.stop_seq_set(self.sq, r, seqs, first_pos=P, min_end=P + mt if mt > 0 else 0)
+        if seqs:
+            first_token_stop(self.sq, r, self.output_ids[r], P, dyn_row=self.dyn_d[r])
+
+    def stop_hit(self, r: int, include: bool = True):
+        """Slot r's hit record as _trim / _kept_cols take it (read with the ids, at the end of the request), or None."""
+        return _stop_hit(self.sq, r, self.stop_seqs[r], include)
+
     grammar = None   # (the state of a decoder built with grammar_states > 0)
 
     def add_grammar(self, dfa) -> int:
@@ -368,7 +401,7 @@ class BatchedDecoder:
     def admit(self, r: int, input_ids: torch.Tensor, temperature: float = 0.0, seed: Optional[int] = None,
               top_k: int = 0, top_p: float = 1.0, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
               frequency_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None, banned_token_ids=None,
-              min_tokens: int = 0, grammar=None, min_p=None) -> None:
+              min_tokens: int = 0, grammar=None, min_p=None, stop_sequences=None) -> None:
         """Prefill request r (model/dflash.py:218-229): target prefill through the wrapped
         model, K/V into the group cache, first token sampled, the prompt's context rows
         projected into the draft cache except the last <= 16, which become the first
@@ -383,7 +416,10 @@ class BatchedDecoder:
         grammar: a handle add_grammar returned (None: no grammar, the slot's rows pass unmasked); the slot's base and
         state are rewritten.
         min_p: the request's own (None / 0: off; a decoder built with min_p=True, else ValueError); the slot's
-        ln(min_p) is rewritten."""
+        ln(min_p) is rewritten.
+        stop_sequences: the request's own (None: none; a decoder built with stop_sequences=True, else ValueError); the
+        slot's table rows and hit record are rewritten.  A request's own stop IDS are sequences of length 1 given here."""
+        seqs = self.check_stop_sequences(stop_sequences)
         P, first, th, sd = self._admit_prefill(r, input_ids, temperature, seed, top_k, top_p,
                                                (repetition_penalty, presence_penalty, frequency_penalty),
                                                dict(logit_bias=logit_bias, allowed_token_ids=allowed_token_ids,
@@ -408,12 +444,13 @@ class BatchedDecoder:
                 self.dyn_dt[t0 + j] = torch.tensor([S + 16 * j, n_tail if j == 0 else 0, 0, S + 16 * j, P, 0, 0, 0], dtype=I32)
                 self.dyn_tt[t0 + j] = torch.tensor([P, 0, 16, P, P, 0, 0, 0], dtype=I32)
         self.start[r], self.n_in[r], self.live[r], self.hook_calls[r], self.bs[r] = P, P, True, 0, BW
+        self._admit_stop(r, P, seqs, min_tokens)
 
     @torch.inference_mode()
     def admit_fused(self, r: int, input_ids: torch.Tensor, temperature: float = 0.0, seed: Optional[int] = None,
                     top_k: int = 0, top_p: float = 1.0, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
                     frequency_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None, banned_token_ids=None,
-                    min_tokens: int = 0, grammar=None, min_p=None) -> None:
+                    min_tokens: int = 0, grammar=None, min_p=None, stop_sequences=None) -> None:
         """`admit` with the slot re-armed by ONE launch (dfl_admit_slot) instead of a dozen small writes: ids, first
         token, block, context tile, both length records and the seed are written on the device from device-resident
         inputs, so that after the prefill launches the admission reads nothing back and copies nothing from the host —
@@ -423,6 +460,7 @@ class BatchedDecoder:
             raise NotImplementedError("admit_fused re-arms one 16-row tile per request; use admit() with tiles_per_request=2")
         if not 0 <= r < self.R:
             raise ValueError(f"admit_fused: slot {r} outside 0..{self.R - 1}")
+        seqs = self.check_stop_sequences(stop_sequences)
         P, first, th, sd = self._admit_prefill(r, input_ids, temperature, seed, top_k, top_p,
                                                (repetition_penalty, presence_penalty, frequency_penalty),
                                                dict(logit_bias=logit_bias, allowed_token_ids=allowed_token_ids,
@@ -433,6 +471,7 @@ class BatchedDecoder:
                        th[P - n_tail:], self.d["taps"], self.dyn_d, self.dyn_t, self.BW, self.mask_id,
                        seeds=self.seeds if sd is not None else None, seed=ops.seed_i64(sd) if sd is not None else 0)
         self.start[r], self.n_in[r], self.live[r], self.hook_calls[r], self.bs[r] = P, P, True, 0, self.BW
+        self._admit_stop(r, P, seqs, min_tokens)
 
     def park(self, r: int) -> None:
         """Request r is finished: its tile stays in the launches but does no work."""
@@ -603,6 +642,8 @@ class BatchedDecoder:
             stage.logprobs(self._logits[:R], self.post.view(-1, 16), **where)
 
     def _accept_launch(self) -> None:
+        if self.sq is not None:   # every slot's stop sequences over what the accept launch is about to commit
+            ops.stop_seq_rows(self.block, self.post, self.output_ids, self.dyn_d, self.sq, slots=self.R)
         ops.accept_commit_batch(self.block, self.post, self.R, self.output_ids, self.dyn_d, self.dyn_t, self.stop_t,
                                 self.result, rearm_mask_id=self.mask_id, tiles_per_req=self.TPR,
                                 dyn_d_tiles=self.dyn_dt, dyn_t_tiles=self.dyn_tt)
@@ -774,6 +815,24 @@ def _prompt_min_p(min_p, n: int, temperature, sampler: str):
     return mps, on
 
 
+def _prompt_stop_sequences(stop_sequences, n: int, target, mask_token_id: int) -> list:
+    """The stop sequences per prompt (ops.check_stop_sequences: a list of lists of ints, or None) from None, one list of
+    sequences for every prompt, or a list of n entries each of which is None or a list of SEQUENCES (its first element
+    is itself a list / tuple / tensor).  A flat list of n lists of ids is therefore one list for every prompt.  target.V
+    is read only where sequences are given."""
+    def is_seq(v):
+        return isinstance(v, (list, tuple)) or (torch.is_tensor(v) and v.dim() >= 1)
+
+    if stop_sequences is None:
+        return [None] * n
+    vals, V = list(stop_sequences), target.V
+    per_prompt = len(vals) == n and any(v is None or (is_seq(v) and len(v) > 0 and is_seq(v[0])) for v in vals) \
+        and all(v is None or is_seq(v) for v in vals)
+    if not per_prompt:
+        vals = [vals] * n
+    return [ops.check_stop_sequences(v, V, mask_token_id) for v in vals]
+
+
 def _prompt_penalties(repetition_penalty, presence_penalty, frequency_penalty, n: int):
     """((r, a, f) per prompt, whether any prompt is not neutral) from scalars or one value per prompt."""
     cols = []
@@ -852,7 +911,8 @@ def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_i
                           seed=None, top_k=0, top_p=1.0, logprobs: Optional[int] = None, repetition_penalty=1.0,
                           presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, allowed_token_ids=None,
                           banned_token_ids=None, min_tokens=0, grammar=None, constrain_draft: bool = False,
-                          min_p=None, couple_draft: bool = False) -> list:
+                          min_p=None, couple_draft: bool = False, stop_sequences=None,
+                          include_stop_sequence: bool = True) -> list:
     """`dflash_generate` (benchmark.py:44-251) for a list of prompts: requests run in
     groups of `group_size` <= 4 (<= 2 with block sizes of 17..32 rows) that share the weight stream; returns one namespace per
     prompt with the fields of benchmark.py:242-251 (timing fields are the group's).
@@ -875,7 +935,12 @@ def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_i
     prompt without a grammar and without bans keeps its argmax draft.
     min_p: as dflash_generate; a scalar, or one value (or None) per prompt.  The decoders are built with min_p=True when
     any prompt floors a sampled draw (blocks of up to 32 rows); a prompt at 0 gets the ids of a run without it.
-    couple_draft: as dflash_generate, for every prompt at its own temperature (a prompt at 0 keeps its greedy draft)."""
+    couple_draft: as dflash_generate, for every prompt at its own temperature (a prompt at 0 keeps its greedy draft).
+    stop_sequences / include_stop_sequence: as dflash_generate; one list of sequences for every prompt, or a list with one
+    list (or None) per prompt.  The decoders are built with stop_sequences=True when any prompt carries one; the
+    results carry `stop_sequence`."""
+    stops = _prompt_stop_sequences(stop_sequences, len(input_ids), target, mask_token_id)
+    stops_on = any(s is not None for s in stops)
     logprobs = ops.check_logprobs(logprobs)
     dfas = _prompt_grammars(grammar, len(input_ids))
     for d in {id(d): d for d in dfas if d is not None}.values():
@@ -917,14 +982,14 @@ def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_i
                              grammar_states=_pool_rows([dfas[i] for i in idx]),
                              # (a group none of whose prompts has anything to constrain by runs the plain launches)
                              constrain_draft=bool(constrain_draft) and bool(logit_bias_on or _pool_rows([dfas[i] for i in idx])),
-                             couple_draft=couple_draft)
+                             couple_draft=couple_draft, stop_sequences=stops_on)
         handles = _load_grammars(dec, [dfas[i] for i in idx])
         t0 = cuda_time()
         for r, p in enumerate(prompts):
             pr, pa, pf = pens[idx[r]]
             dec.admit(r, p, temps[idx[r]], seed=seeds[idx[r]], top_k=top_ks[idx[r]], top_p=top_ps[idx[r]],
                       repetition_penalty=pr, presence_penalty=pa, frequency_penalty=pf, **biases[idx[r]],
-                      grammar=handles[r], min_p=min_ps[idx[r]] if min_p_on else None)
+                      grammar=handles[r], min_p=min_ps[idx[r]] if min_p_on else None, stop_sequences=stops[idx[r]])
         ttft = cuda_time() - t0
         taus = [[] for _ in idx]
         # (hook_block_view: the hook sees the block as the single-request loop hands it over, bs slots; default: the
@@ -943,7 +1008,7 @@ def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_i
                 if dec.live[r]:
                     dec.set_block_size(r, max(1, min(block_size, max_len[r] - dec.start[r])))
             # run-ahead draft: only while no live request can finish or hit its tail clamp on this cycle's result
-            ahead = (stop_token_ids is None and not stop_always
+            ahead = (stop_token_ids is None and not stops_on and not stop_always
                      and all(dec.start[r] + 2 * block_size <= max_len[r] for r in range(len(idx)) if dec.live[r]))
             if first:   # the clock restarts after the first draft, before its verify (benchmark.py:145-147)
                 first = False
@@ -959,14 +1024,16 @@ def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_i
                     dec.park(r)
         decode_s = cuda_time() - t1
         for r, i in enumerate(idx):
-            ids = _trim(dec.output_ids[r:r + 1], max_len[r], mask_token_id, stop_token_ids, dec.n_in[r])
+            hit, which = dec.stop_hit(r, include_stop_sequence), []
+            ids = _trim(dec.output_ids[r:r + 1], max_len[r], mask_token_id, stop_token_ids, dec.n_in[r], hit)
             n_out = ids.shape[1] - dec.n_in[r]
-            lpf = NO_LOGPROBS if dec.lp is None else logprob_fields(
-                dec.lp, r, _kept_cols(dec.output_ids[r:r + 1], max_len[r], mask_token_id, stop_token_ids, dec.n_in[r])[dec.n_in[r]:])
+            cols = _kept_cols(dec.output_ids[r:r + 1], max_len[r], mask_token_id, stop_token_ids, dec.n_in[r], hit, which)
+            lpf = NO_LOGPROBS if dec.lp is None else logprob_fields(dec.lp, r, cols[dec.n_in[r]:])
             results[i] = SimpleNamespace(output_ids=ids.clone(), num_input_tokens=dec.n_in[r], num_output_tokens=n_out,
                                          time_to_first_token=ttft, time_per_output_token=decode_s / max(1, n_out),
                                          acceptance_lengths=taus[r], cycle_trace=[], profile_summary=None,
-                                         grammar_state=dec.grammar_state_of(r, ids[0], dec.n_in[r]), **lpf)
+                                         grammar_state=dec.grammar_state_of(r, ids[0], dec.n_in[r]),
+                                         stop_sequence=which[0] if which else None, **lpf)
         del dec
     return results
 
@@ -975,7 +1042,8 @@ def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_i
 def dflash_generate_policy_batch(*, model: DFlashDraftModel, target: NativeTarget, input_ids: Sequence[torch.Tensor],
                                  mask_token_id: int, max_new_tokens: int, stop_token_ids, temperature: float,
                                  schedulers: Sequence, draft_token_hook: Optional[Callable] = None,
-                                 group_size: int = MAX_GROUP, sampler: str = "torch", seed=None) -> list:
+                                 group_size: int = MAX_GROUP, sampler: str = "torch", seed=None, stop_sequences=None,
+                                 include_stop_sequence: bool = True) -> list:
     """`dflash_generate_policy` (benchmark_dynamic_schedule.py:260-434) for a list of prompts, the requests of a group
     sharing the weight stream: every request has its OWN scheduler (schedulers[i], e.g. an EWMAPerformanceScheduler) and
     therefore its own block size per cycle — the kernels read each request's size from its length record, so a group
@@ -984,7 +1052,10 @@ def dflash_generate_policy_batch(*, model: DFlashDraftModel, target: NativeTarge
     Block sizes <= 16 (one tile per request); T = 0 (the reference samples the draft with T too, :342 — a per-request
     RNG stream over a shared launch has no counterpart in it): both raise NotImplementedError otherwise — except with
     sampler="device" (seed as in dflash_generate_batch), whose per-request seeded draws of target AND draft are what
-    dflash_generate_policy(..., sampler="device") draws for that request."""
+    dflash_generate_policy(..., sampler="device") draws for that request.
+    stop_sequences / include_stop_sequence: as dflash_generate_batch (the field `stop_sequence`)."""
+    stops = _prompt_stop_sequences(stop_sequences, len(input_ids), target, mask_token_id)
+    stops_on = any(s is not None for s in stops)
     if temperature >= 1e-5 and sampler != "device":
         raise NotImplementedError("the batched policy loop samples at T > 0 with sampler='device' only; or run the requests "
                                   "through dflash_generate_policy")
@@ -1006,11 +1077,12 @@ def dflash_generate_policy_batch(*, model: DFlashDraftModel, target: NativeTarge
         max_len = [p.shape[1] + max_new_tokens for p in prompts]
         dec = BatchedDecoder(model, target, len(idx), max_rows=pmax + max_new_tokens + 3 * 16,
                              out_len=pmax + max_new_tokens + 16, mask_token_id=mask_token_id,
-                             stop_token_ids=stop_token_ids, temperature=T, sampler=sampler, draft_temperature=T)
+                             stop_token_ids=stop_token_ids, temperature=T, sampler=sampler, draft_temperature=T,
+                             stop_sequences=stops_on)
         stop_t = dec.stop_t
         t0 = cuda_time()
         for r, p in enumerate(prompts):
-            dec.admit(r, p, T, seed=seeds[idx[r]])
+            dec.admit(r, p, T, seed=seeds[idx[r]], stop_sequences=stops[idx[r]])
         ttft = cuda_time() - t0
         R = len(idx)
         taus, used, traces, cyc = [[] for _ in idx], [[] for _ in idx], [[] for _ in idx], [0] * R
@@ -1068,10 +1140,13 @@ def dflash_generate_policy_batch(*, model: DFlashDraftModel, target: NativeTarge
                     dec.park(r)
         decode_s = cuda_time() - t1
         for r, i in enumerate(idx):
-            ids = _trim(dec.output_ids[r:r + 1], max_len[r], mask_token_id, stop_token_ids, dec.n_in[r])
+            hit, which = dec.stop_hit(r, include_stop_sequence), []
+            ids = dec.output_ids[r:r + 1][:, _kept_cols(dec.output_ids[r:r + 1], max_len[r], mask_token_id, stop_token_ids,
+                                                        dec.n_in[r], hit, which)]
             n_out = ids.shape[1] - dec.n_in[r]
             results[i] = SimpleNamespace(output_ids=ids.clone(), num_input_tokens=dec.n_in[r], num_output_tokens=n_out,
                                          time_to_first_token=ttft, time_per_output_token=decode_s / max(1, n_out),
-                                         acceptance_lengths=taus[r], used_block_sizes=used[r], cycle_trace=traces[r])
+                                         acceptance_lengths=taus[r], used_block_sizes=used[r], cycle_trace=traces[r],
+                                         stop_sequence=which[0] if which else None)
         del dec
     return results

@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libdflash_hip.so")
-SOURCES = ["dfl_common.hip", "gemm_skinny.hip", "gemm_batch.hip", "rows.hip", "attn_block.hip", "attn_head.hip", "accept.hip", "nucleus.hip", "logprobs.hip", "penalties.hip", "logit_bias.hip", "min_p.hip", "grammar.hip", "grammar_draft.hip", "grammar_lift.hip", "candidates.hip", "moe.hip", "prefill.hip"]
+SOURCES = ["dfl_common.hip", "gemm_skinny.hip", "gemm_batch.hip", "rows.hip", "attn_block.hip", "attn_head.hip", "accept.hip", "nucleus.hip", "logprobs.hip", "penalties.hip", "logit_bias.hip", "min_p.hip", "grammar.hip", "grammar_draft.hip", "grammar_lift.hip", "stop_seq.hip", "candidates.hip", "moe.hip", "prefill.hip"]
 HEADERS = [os.path.join(CSRC, "dfl_common.h"), os.path.join(CSRC, "dfl_rng.h"), os.path.join(CSRC, "gemm_rows.h"), os.path.join(CSRC, "gemm_ring.h"), os.path.join(CSRC, "moe_route.h"),
            os.path.join(HERE, "..", "include", "dflash_hip.h")]
 # kernarg preload: gfx950 delivers up to 14 leading scalar / pointer kernel arguments in SGPRs at wave start (the hot

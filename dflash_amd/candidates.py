@@ -287,9 +287,12 @@ def dflash_generate_candidate_solutions(model, target, input_ids: torch.Tensor, 
                                         adaptive_budgets=(1, 4, 8), adaptive_accept_thresholds=(0.85, 0.65),
                                         adaptive_warmup_cycles: int = 2, adaptive_probe_interval: int = 5,
                                         temperature: float = 0.0, collect_profile: bool = False,
-                                        draft_token_hook=None) -> SimpleNamespace:
+                                        draft_token_hook=None, stop_sequences=None) -> SimpleNamespace:
     """benchmark_candidate_solutions.py:416-741: signature (plus the test hook), cycle_trace rows, candidate_summary
-    and timing fields of the reference."""
+    and timing fields of the reference.  stop_sequences: refused (this loop has an accept launch of its own)."""
+    if stop_sequences is not None:
+        raise NotImplementedError("stop_sequences: the multi-candidate verify loop commits through dfl_candidate_select, "
+                                  "which no stop-sequence launch stands in front of (DESIGN.md section 22)")
     if temperature >= 1e-5:
         raise ValueError("benchmark_candidate_solutions.py currently supports only temperature=0.0")   # :438-439
     if block_size > 32:

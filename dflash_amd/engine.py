@@ -16,7 +16,8 @@ import torch
 
 from . import ops
 from .batch import (MAX_GROUP, BatchedDecoder, _load_grammars, _pool_rows, _prompt_bias, _prompt_filters,
-                    _prompt_grammars, _prompt_min_p, _prompt_penalties, _prompt_seeds, _prompt_temperatures)
+                    _prompt_grammars, _prompt_min_p, _prompt_penalties, _prompt_seeds, _prompt_stop_sequences,
+                    _prompt_temperatures)
 from .generate import NO_LOGPROBS, _kept_cols, _trim, cuda_time, logprob_fields
 from .logits_stage import check_features
 from .slots import SlotLoop
@@ -59,9 +60,13 @@ class _DecoderDriver:
         p = req.payload
         t0 = cuda_time()
         ids = p.input_ids if p.input_ids.is_cuda else p.input_ids.to(self.dec.dev)
+        bias = dict(p.bias)
+        if p.stop_sequences:   # (no stop sequence matches before min_tokens tokens are out, bias keywords or not)
+            bias.setdefault("min_tokens", p.min_tokens)
         self.dec.admit_fused(slot, ids, p.temperature, seed=p.seed, top_k=p.top_k, top_p=p.top_p,
                              repetition_penalty=p.penalties[0], presence_penalty=p.penalties[1],
-                             frequency_penalty=p.penalties[2], **p.bias, grammar=p.grammar, min_p=p.min_p)
+                             frequency_penalty=p.penalties[2], **bias, grammar=p.grammar, min_p=p.min_p,
+                             stop_sequences=p.stop_sequences)
         t1 = cuda_time()
         p.ttft, p.t_admitted = t1 - t0, t1
         self.stats["admit_s"] += t1 - t0
@@ -100,20 +105,23 @@ class _DecoderDriver:
 
     def retire(self, slot: int, req) -> None:
         d, p = self.dec, req.payload
-        ids = _trim(d.output_ids[slot:slot + 1], req.max_len, d.mask_id, self.stop_token_ids, req.n_in).clone()
+        # (the slot's hit record is read here, with the ids: the next admission rewrites it)
+        hit, which = d.stop_hit(slot, p.include_stop), []
+        cols = _kept_cols(d.output_ids[slot:slot + 1], req.max_len, d.mask_id, self.stop_token_ids, req.n_in, hit, which)
+        ids = _trim(d.output_ids[slot:slot + 1], req.max_len, d.mask_id, self.stop_token_ids, req.n_in, hit).clone()
         n_out = ids.shape[1] - req.n_in
         decode_s = cuda_time() - p.t_admitted
         self.hooks[slot] = None
         # logprobs: the positions the ids keep, [n_in, n_in + n_out) of the slot's row — each written by THIS request (its
         # admission, then the cycle that committed the position), so nothing of the slot's previous request shows
-        lpf = NO_LOGPROBS if d.lp is None else logprob_fields(
-            d.lp, slot, _kept_cols(d.output_ids[slot:slot + 1], req.max_len, d.mask_id, self.stop_token_ids, req.n_in)[req.n_in:])
+        lpf = NO_LOGPROBS if d.lp is None else logprob_fields(d.lp, slot, cols[req.n_in:])
         p.result = SimpleNamespace(output_ids=ids, num_input_tokens=req.n_in, num_output_tokens=n_out,
                                    time_to_first_token=p.ttft, time_per_output_token=decode_s / max(1, n_out),
                                    acceptance_lengths=req.taus, cycle_trace=[], profile_summary=None,
                                    request_id=req.rid, slot=slot, admitted_step=req.admitted_step,
                                    finished_step=req.finished_step,
-                                   grammar_state=d.grammar_state_of(slot, ids[0], req.n_in), **lpf)
+                                   grammar_state=d.grammar_state_of(slot, ids[0], req.n_in),
+                                   stop_sequence=which[0] if which else None, **lpf)
 
 
 class BatchEngine:
@@ -131,8 +139,10 @@ class BatchEngine:
                  graph: Optional[bool] = None, filtering: bool = False, request_temperature: bool = False,
                  logprobs: Optional[int] = None, penalties: bool = False, logit_bias: bool = False,
                  grammar_states: int = 0, constrain_draft: bool = False, min_p: bool = False,
-                 couple_draft: bool = False):
-        """filtering / request_temperature / logprobs / penalties / logit_bias / grammar_states / constrain_draft / min_p /
+                 couple_draft: bool = False, stop_sequences: bool = False):
+        """stop_sequences: as BatchedDecoder takes it — requests may carry their own stop sequences (submit), matched on
+        the device in front of every accept launch; results carry `stop_sequence`.
+        filtering / request_temperature / logprobs / penalties / logit_bias / grammar_states / constrain_draft / min_p /
         couple_draft:
         as BatchedDecoder takes them — what requests may carry (submit); fixed here because they fix the one captured
         launch sequence of the engine's life (logits_stage.LogitsStage has the row processors' order and the DESIGN.md
@@ -161,7 +171,8 @@ class BatchEngine:
                                   stop_token_ids=stop_token_ids, temperature=temperature, sampler=sampler,
                                   filtering=filtering, request_temperature=request_temperature, logprobs=logprobs,
                                   penalties=penalties, logit_bias=logit_bias, grammar_states=grammar_states,
-                                  constrain_draft=constrain_draft, min_p=min_p, couple_draft=couple_draft)
+                                  constrain_draft=constrain_draft, min_p=min_p, couple_draft=couple_draft,
+                                  stop_sequences=stop_sequences)
         self.min_p = bool(min_p)
         self.filtering, self.temperature, self.penalties = bool(filtering), float(temperature), bool(penalties)
         self.logit_bias = bool(logit_bias)
@@ -170,7 +181,8 @@ class BatchEngine:
                           graph=self.use_graph)
         driver = _DecoderDriver(self.dec, self.stats, self.use_graph, float(temperature), stop_token_ids)
         stop_always = stop_token_ids is not None and mask_token_id in stop_token_ids
-        self.loop = SlotLoop(driver, slots, block_size, may_stop=stop_token_ids is not None, stop_always=stop_always,
+        self.loop = SlotLoop(driver, slots, block_size, may_stop=stop_token_ids is not None or bool(stop_sequences),
+                             stop_always=stop_always,
                              stats=self.stats)
         self._pending: list = []   # results of requests finished since the last run()
 
@@ -178,7 +190,8 @@ class BatchEngine:
                draft_token_hook: Optional[Callable] = None, top_k: int = 0, top_p: float = 1.0,
                temperature: Optional[float] = None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
                frequency_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None, banned_token_ids=None,
-               min_tokens: int = 0, grammar=None, min_p=None) -> int:
+               min_tokens: int = 0, grammar=None, min_p=None, stop_sequences=None,
+               include_stop_sequence: bool = True) -> int:
         """Queue a request; returns its id (ids count up in submission order).  draft_token_hook(block_view, start,
         call): `call` counts from 0 at the request's admission; the view has the cycle's block size.
         top_k / top_p: the request's own filter on its T > 0 draws (an engine built with filtering=True); accepted and
@@ -191,7 +204,11 @@ class BatchEngine:
         logit_bias=True; None / None / None / 0: off), validated here.
         grammar: a handle add_grammar returned (None: no grammar; an engine built with grammar_states > 0).
         min_p: the request's own (None / 0: off; an engine built with min_p=True, else ValueError); it does nothing on a
-        request whose own temperature is 0."""
+        request whose own temperature is 0.
+        stop_sequences: the request's own (None: none; an engine built with stop_sequences=True, else ValueError),
+        validated here; a request's own stop IDS are sequences of length 1.  include_stop_sequence=False cuts the matched
+        ids off the result as well."""
+        seqs = None if stop_sequences is None else self.dec.check_stop_sequences(stop_sequences)
         mp = ops.check_min_p(min_p)
         if grammar is not None:   # (raises on a handle this engine did not return, and on an engine without a pool)
             self.dec.check_grammar_handle(grammar)
@@ -216,7 +233,8 @@ class BatchEngine:
                                SimpleNamespace(input_ids=input_ids, seed=seed, hook=draft_token_hook, result=None,
                                                ttft=0.0, t_admitted=0.0, top_k=int(top_k), top_p=float(top_p),
                                                temperature=T, penalties=pen or (1.0, 0.0, 0.0), bias=bias,
-                                               grammar=grammar, min_p=mp))
+                                               grammar=grammar, min_p=mp, stop_sequences=seqs,
+                                               include_stop=bool(include_stop_sequence), min_tokens=int(min_tokens)))
         return req.rid
 
     def add_grammar(self, dfa) -> int:
@@ -249,7 +267,8 @@ def dflash_generate_stream(model, target, input_ids: Sequence[torch.Tensor], mas
                            logprobs: Optional[int] = None, repetition_penalty=1.0, presence_penalty=0.0,
                            frequency_penalty=0.0, logit_bias=None, allowed_token_ids=None, banned_token_ids=None,
                            min_tokens=0, grammar=None, constrain_draft: bool = False, min_p=None,
-                           couple_draft: bool = False) -> list:
+                           couple_draft: bool = False, stop_sequences=None,
+                           include_stop_sequence: bool = True) -> list:
     """`dflash_generate_batch` with slot refill: one namespace per prompt with the fields of benchmark.py:242-251, each
     request emitting what its own `dflash_generate` run emits.  max_new_tokens: one int or one per prompt.
     draft_token_hook(request_index, block_view, start, call).  seed as in dflash_generate_batch (an int s gives prompt i
@@ -262,7 +281,9 @@ def dflash_generate_stream(model, target, input_ids: Sequence[torch.Tensor], mas
     value (or None) per prompt.
     grammar: one TokenDFA for every prompt, or a sequence with one (or None) per prompt.
     constrain_draft: as dflash_generate_batch.  couple_draft: likewise.
-    min_p: a scalar, or one value (or None) per prompt."""
+    min_p: a scalar, or one value (or None) per prompt.
+    stop_sequences / include_stop_sequence: as dflash_generate_batch."""
+    stops = _prompt_stop_sequences(stop_sequences, len(input_ids), target, mask_token_id)
     dfas = _prompt_grammars(grammar, len(input_ids))
     for d in {id(d): d for d in dfas if d is not None}.values():
         ops.check_grammar(d, target.V)
@@ -286,12 +307,13 @@ def dflash_generate_stream(model, target, input_ids: Sequence[torch.Tensor], mas
                       stop_token_ids=stop_token_ids, temperature=max(temps, default=0.0), sampler=sampler, filtering=filtering,
                       request_temperature=per_request, logprobs=logprobs, penalties=penalties, logit_bias=logit_bias_on,
                       grammar_states=_pool_rows(dfas), constrain_draft=constrain_draft, min_p=min_p_on,
-                      couple_draft=couple_draft)
+                      couple_draft=couple_draft, stop_sequences=any(s is not None for s in stops))
     handles = _load_grammars(eng, dfas)
     for i, p in enumerate(input_ids):
         hook = (lambda blk, start, call, i=i: draft_token_hook(i, blk, start, call)) if draft_token_hook else None
         eng.submit(p, mnt[i], seed=seeds[i], draft_token_hook=hook, top_k=top_ks[i], top_p=top_ps[i],
                    temperature=temps[i], repetition_penalty=pens[i][0], presence_penalty=pens[i][1],
                    frequency_penalty=pens[i][2], **biases[i], grammar=handles[i],
-                   min_p=min_ps[i] if min_p_on else None)
+                   min_p=min_ps[i] if min_p_on else None, stop_sequences=stops[i],
+                   include_stop_sequence=include_stop_sequence)
     return eng.run()

@@ -152,8 +152,10 @@ def check_couple_draft(couple_draft, temperature: float, draft_temperature: Opti
     return dt
 
 
-def _trim(output_ids, max_length, mask_token_id, stop_token_ids, n_in):
-    """model/dflash.py:269-275."""
+def _trim(output_ids, max_length, mask_token_id, stop_token_ids, n_in, stop_hit=None):
+    """model/dflash.py:269-275.  stop_hit (the stop sequences' (e, k, L, include) of _stop_hit, or None): see _kept_cols."""
+    if stop_hit is not None:
+        return output_ids[:, _kept_cols(output_ids, max_length, mask_token_id, stop_token_ids, n_in, stop_hit)]
     output_ids = output_ids[:, :max_length]
     output_ids = output_ids[:, output_ids[0] != mask_token_id]
     if stop_token_ids is not None:
@@ -164,15 +166,33 @@ def _trim(output_ids, max_length, mask_token_id, stop_token_ids, n_in):
     return output_ids
 
 
-def _kept_cols(output_ids, max_length, mask_token_id, stop_token_ids, n_in):
-    """The columns of output_ids that _trim keeps, as indices: what trims a per-position buffer exactly as the ids."""
+def _kept_cols(output_ids, max_length, mask_token_id, stop_token_ids, n_in, stop_hit=None, which=None):
+    """The columns of output_ids that _trim keeps, as indices: what trims a per-position buffer exactly as the ids.
+    stop_hit = (e, k, L, include): a stop sequence of L ids (index k) matched with its last id at position e (DESIGN.md
+    section 22).  The cut is at the earlier of the first stop id and e; where the sequence decides (e is kept and not
+    behind the first stop id), include=False drops the window's L ids too and `which` (a list, optional) receives k."""
     cols = (output_ids[0, :max_length] != mask_token_id).nonzero(as_tuple=True)[0]
+    cut = None
     if stop_token_ids is not None:
         st = torch.tensor(stop_token_ids, device=output_ids.device)
         idx = torch.isin(output_ids[0, cols][n_in:], st).nonzero(as_tuple=True)[0]
         if idx.numel() > 0:
-            cols = cols[: n_in + idx[0] + 1]
-    return cols
+            cut = n_in + int(idx[0]) + 1
+    if stop_hit is not None and cols.numel() > 0:
+        e, k, L, include = stop_hit
+        if 0 <= e <= int(cols[-1]) and (cut is None or e <= int(cols[cut - 1])):
+            cut = int((cols <= (e if include else e - L)).sum())
+            if which is not None:
+                which.append(k)
+    return cols if cut is None else cols[:cut]
+
+
+def _stop_hit(state, slot: int, seqs, include: bool):
+    """The slot's hit record read back as _kept_cols takes it (with the ids, at the end of the request), or None."""
+    if state is None or not seqs:
+        return None
+    e, k = state.hit[slot].tolist()
+    return (e, k, len(seqs[k]), bool(include)) if e >= 0 and 0 <= k < len(seqs) else None
 
 
 def logprob_fields(sink, row: int, cols: torch.Tensor) -> dict:
@@ -200,6 +220,25 @@ def _vocab_of(target) -> int:
     return int(v)
 
 
+def first_token_stop(state, slot: int, ids_row: torch.Tensor, n_in: int, dyn_row: Optional[torch.Tensor] = None) -> bool:
+    """The first new token (position n_in of ids_row, produced by admission before any accept launch runs) against the
+    slot's stop sequences: dfl_stop_seq_rows over a one-row block — a record of its own with START = n_in - 1, whose one
+    committed token is the "posterior" ids_row[n_in] — so a length-1 sequence equal to the first token stops the request
+    as a stop id does.  dyn_row (the ragged batch: the slot's draft-form record): the stop word is ORed into it on the
+    device and nothing is read back (returns False); None: the stop word is read back and returned."""
+    rec = torch.zeros(8, dtype=torch.int32, device=ids_row.device)
+    rec[ops.DYN_START] = n_in - 1
+    one = SimpleNamespace(seq_ids=state.seq_ids[slot:slot + 1], seq_len=state.seq_len[slot:slot + 1],
+                          first_pos=state.first_pos[slot:slot + 1], min_end=state.min_end[slot:slot + 1],
+                          hit=state.hit[slot:slot + 1])
+    first = ids_row[n_in:n_in + 1]
+    ops.stop_seq_rows(first, first, ids_row, rec, one, bs=1)
+    if dyn_row is not None:
+        dyn_row[ops.DYN_STOP] |= rec[ops.DYN_STOP]
+        return False
+    return bool(rec[ops.DYN_STOP].item())
+
+
 class DecodeSession:
     """State of one request between cycles (what the reference keeps in local
     variables of its while-loop, model/dflash.py:206-233)."""
@@ -210,8 +249,14 @@ class DecodeSession:
                  top_k: int = 0, top_p: float = 1.0, logprobs: Optional[int] = None, repetition_penalty: float = 1.0,
                  presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None,
                  banned_token_ids=None, min_tokens: int = 0, grammar=None, constrain_draft: bool = False, min_p=None,
-                 couple_draft: bool = False):
+                 couple_draft: bool = False, stop_sequences=None, include_stop_sequence: bool = True):
         from .target import NativeTarget
+        # stop_sequences: multi-token stops matched on the device by one launch in front of every
+        # accept launch; None / empty: the launches of before, nothing allocated.  Bad values are refused first
+        self.stop_seqs = (ops.check_stop_sequences(stop_sequences, _vocab_of(target), mask_token_id)
+                          if stop_sequences is not None else None)
+        self.include_stop = bool(include_stop_sequence)
+        self._min_tokens = int(min_tokens) if self.stop_seqs else 0
         # couple_draft: at T > 0 every draft token is the argmax of the DRAFT's logits under the
         # noise the TARGET's verify will draw that position with (stream TARGET, the request's seed, the target's invT).
         # The draft then counts as greedy everywhere below — run-ahead, constrain_draft, the fixed-size capture — and only
@@ -287,6 +332,10 @@ class DecodeSession:
         elif self.use_draft and getattr(model, "w4", None) is not None:   # an mxfp4 draft: its own 4-bit copy of the head
             self.lm_wp8 = model.packed_lm_head_mxfp4(target.lm_head)
         self.stop_t = torch.tensor(stop_token_ids, dtype=torch.long, device=dev) if stop_token_ids else None
+        # the stop sequences' tables and hit record, slot 0 of a state of its own (None: off); written in prefill()
+        self.sq = ops.stop_seq_state(1, dev) if self.stop_seqs else None
+        self._hit = None   # the hit record as finish() read it: (e, k, L, include) or None
+        self.stop_sequence = None
         # the row processors' state and buffers, slot 0 of a stage of its own (None: nothing is on, and verify is called
         # without it); the slot's values go in with the first token (prefill).  A grammar's pool is exactly the
         # automaton's rows at base 0, validated against the bias row: a reachable state whose legal tokens are all banned
@@ -382,6 +431,15 @@ class DecodeSession:
             self.output_ids[:, self.n_in:self.n_in + 1] = sample(out.logits, self.temperature)
         if self.use_draft:
             self.target_hidden = _taps(out.hidden_states, self.model.target_layer_ids)
+        if self.sq is not None:
+            ops.stop_seq_set(self.sq, 0, self.stop_seqs, first_pos=self.n_in,
+                             min_end=self.n_in + self._min_tokens if self._min_tokens > 0 else 0)
+            self.stopped = first_token_stop(self.sq, 0, self.output_ids[0], self.n_in)
+
+    def _stop_seq(self, blk_row, post_row, bs) -> None:
+        """Directly in front of an accept launch: the slot's stop sequences over what that launch is about to commit."""
+        if self.sq is not None:
+            ops.stop_seq_rows(blk_row, post_row, self.output_ids[0], self.dyn, self.sq, bs=bs)
 
     def _mark(self, key, which):
         if self.events is not None and self.record_events:
@@ -540,7 +598,9 @@ class DecodeSession:
             # a stopped session is terminal, run_decode leaves the loop on it)
             ops.set_dyn(self.dyn, 0, 0, bs, start)  # start word = pos0 + tau = start
         self._arm_result()
-        ops.accept_commit(blk[0], posterior[0].contiguous(), bs, self.output_ids[0], self.dyn, self.stop_t,
+        post0 = posterior[0].contiguous()
+        self._stop_seq(blk[0], post0, bs)
+        ops.accept_commit(blk[0], post0, bs, self.output_ids[0], self.dyn, self.stop_t,
                           self.result, rearm=(self.block[0], self.max_bs, self.mask_token_id),
                           dyn_t=self.tcache.dyn if (self.native and self._fixed is not None) else None)
         if self.stage is not None:
@@ -656,7 +716,9 @@ class DecodeSession:
         def verify_accept(bs):   # (a T > 0 draw takes its positions from the target record's POS0 word: fresh every replay)
             post, _ = t.verify(self.block[0, :bs], bound, self.tcache, temperature=self.temperature, tap_layers=tl,
                                taps_out=self.taps_buf, dyn_lengths=True, seed=self._tseed, **self._vkw)
-            ops.accept_commit(self.block[0, :bs], post[0].contiguous(), bs, self.output_ids[0], self.dyn, self.stop_t,
+            post0 = post[0].contiguous()
+            self._stop_seq(self.block[0, :bs], post0, bs)
+            ops.accept_commit(self.block[0, :bs], post0, bs, self.output_ids[0], self.dyn, self.stop_t,
                               self.result, rearm=(self.block[0], self.max_bs, self.mask_token_id), dyn_t=self.tcache.dyn)
             if self.stage is not None:
                 self.stage.commit(self.output_ids, self.dyn)
@@ -668,7 +730,8 @@ class DecodeSession:
                        (m._rope, t._rope, getattr(m, "ws", None), getattr(t, "ws", None), getattr(t, "_taps", None),
                         self.lm_wp, self.lm_wp8, self.embed_w, getattr(t, "lm_wp", None),
                         t.fp8_tensors() if self.native else (),    # (an fp8 target's codes and scale vectors)
-                        self.stage))   # (the row processors' state and every buffer their launches read or write)
+                        self.stage,    # (the row processors' state and every buffer their launches read or write)
+                        self.sq))      # (the stop sequences' tables and hit record)
 
     def _tables_moved(self, rec: _Replay) -> bool:
         """A shared draft model / NativeTarget replaces its RoPE table when another caller needs more positions
@@ -791,21 +854,31 @@ class DecodeSession:
         return self._commit(res, bs, start, self.taps_buf, replayed=True)
 
     def finish(self) -> torch.Tensor:
-        return _trim(self.output_ids, self.max_length, self.mask_token_id, self.stop_token_ids, self.n_in)
+        """The returned ids; with stop sequences the hit record is read here, once, and `stop_sequence` set: the index of
+        the sequence that ended the request, None where it ended otherwise."""
+        self._hit = _stop_hit(self.sq, 0, self.stop_seqs, self.include_stop)
+        if self._hit is None:
+            return _trim(self.output_ids, self.max_length, self.mask_token_id, self.stop_token_ids, self.n_in)
+        which = []
+        cols = _kept_cols(self.output_ids, self.max_length, self.mask_token_id, self.stop_token_ids, self.n_in, self._hit,
+                          which)
+        self.stop_sequence = which[0] if which else None
+        return self.output_ids[:, cols]
 
     def finish_logprobs(self) -> dict:
         """The result fields logprobs / top_logprob_ids / top_logprobs, trimmed exactly as finish() trims the ids (all
         None with logprobs off)."""
         if self.lp is None:
             return dict(NO_LOGPROBS)
-        cols = _kept_cols(self.output_ids, self.max_length, self.mask_token_id, self.stop_token_ids, self.n_in)
+        cols = _kept_cols(self.output_ids, self.max_length, self.mask_token_id, self.stop_token_ids, self.n_in, self._hit)
         return logprob_fields(self.lp, 0, cols[self.n_in:])
 
     def finish_grammar(self, output_ids: torch.Tensor) -> Optional[int]:
         """The result field grammar_state: the automaton's state after the generated tokens finish() returned, walked by
         dfl_grammar_advance from start; -1 where one of them is illegal or the slot's own state was violated; None with
-        the grammar off.  (The slot's own state runs on over what an accept launch committed behind a stop id or past
-        max_length — tokens the trim drops — so it is not the state after what is returned.)"""
+        the grammar off.  (The slot's own state runs on over what an accept launch committed behind a stop id, behind a
+        matched stop sequence or past max_length — tokens the trim drops, which dfl_penalty_count and dfl_grammar_advance
+        still count — so it is not the state after what is returned.)"""
         if self.gr is None:
             return None
         if int(self.gr.state.item()) < 0:
@@ -825,7 +898,8 @@ def run_decode(model, target, input_ids: torch.Tensor, *, mask_token_id: int, ma
                top_k: int = 0, top_p: float = 1.0, logprobs: Optional[int] = None, repetition_penalty: float = 1.0,
                presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None,
                banned_token_ids=None, min_tokens: int = 0, grammar=None,
-               constrain_draft: bool = False, min_p=None, couple_draft: bool = False) -> SimpleNamespace:
+               constrain_draft: bool = False, min_p=None, couple_draft: bool = False, stop_sequences=None,
+               include_stop_sequence: bool = True) -> SimpleNamespace:
     s = DecodeSession(model, target, input_ids, mask_token_id=mask_token_id, max_new_tokens=max_new_tokens,
                       max_block_size=max_block_size or block_size, stop_token_ids=stop_token_ids,
                       temperature=temperature, draft_temperature=draft_temperature,
@@ -833,7 +907,8 @@ def run_decode(model, target, input_ids: torch.Tensor, *, mask_token_id: int, ma
                       logprobs=logprobs, repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
                       frequency_penalty=frequency_penalty, logit_bias=logit_bias, allowed_token_ids=allowed_token_ids,
                       banned_token_ids=banned_token_ids, min_tokens=min_tokens, grammar=grammar,
-                      constrain_draft=constrain_draft, min_p=min_p, couple_draft=couple_draft)
+                      constrain_draft=constrain_draft, min_p=min_p, couple_draft=couple_draft,
+                      stop_sequences=stop_sequences, include_stop_sequence=include_stop_sequence)
     t_prefill = cuda_time()
     s.prefill()
     time_to_first_token = cuda_time() - t_prefill
@@ -848,7 +923,7 @@ def run_decode(model, target, input_ids: torch.Tensor, *, mask_token_id: int, ma
     replay = os.environ.get("DFL_GRAPH", "1") != "0" and s.replay_uncovered(sizes, ahead=scheduler is None) is None
     cyc = replayed = 0
     replayed_flags = []
-    while s.start < s.max_length:
+    while s.start < s.max_length and not s.stopped:   # (stopped before a cycle: the first token ended a stop sequence)
         cycle_t0 = cuda_time() if scheduler is not None else None
         if collect_profile:
             s.events = {}
@@ -944,7 +1019,8 @@ def run_decode(model, target, input_ids: torch.Tensor, *, mask_token_id: int, ma
                            acceptance_lengths=taus, used_block_sizes=used_bs, l_gen=lgens,
                            cycle_trace=cycle_trace, profile_summary=profile_summary, replayed_cycles=replayed,
                            replayed_flags=replayed_flags,
-                           seed=s.seed, grammar_state=s.finish_grammar(output_ids), **s.finish_logprobs())
+                           seed=s.seed, grammar_state=s.finish_grammar(output_ids), stop_sequence=s.stop_sequence,
+                           **s.finish_logprobs())
 
 
 def _draft_ids(model, hid_frag, lm_wp, bs, blk, draft_temperature, keep_logits=None, seed=None, dyn=None, start=None,
@@ -1011,8 +1087,14 @@ def dflash_generate(model, target, input_ids: torch.Tensor, mask_token_id: int, 
                     logprobs: Optional[int] = None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
                     frequency_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None, banned_token_ids=None,
                     min_tokens: int = 0, grammar=None, constrain_draft: bool = False, min_p=None,
-                    couple_draft: bool = False) -> SimpleNamespace:
+                    couple_draft: bool = False, stop_sequences=None, include_stop_sequence: bool = True) -> SimpleNamespace:
     """benchmark.py:44-55 signature; returns the namespace of :242-251 (+ replayed_cycles).
+    stop_sequences (None: off, the launches of before; up to 8 sequences of 1..16 token ids, a bare int counting as a
+    sequence of one): the request ends with the first committed token that completes one of them — matched on the device
+    in front of every accept launch, over committed tokens only, across cycle boundaries, never inside the prompt and
+    not before min_tokens tokens are out.  include_stop_sequence (True, as stop ids stay in the
+    output; False: the matched ids are cut off too, the OpenAI behaviour).  The result's `stop_sequence` is the index of
+    the sequence that ended the request, None where it ended otherwise.  Any target, native or wrapped.
     couple_draft (False: off, the launches of before; at T > 0 needs sampler="device", else ValueError; at T = 0 it does
     nothing): every draft token is picked under the noise the target's verify will draw that position with — Gumbel-max
     coupling, DESIGN.md section 20.  The emitted ids do not change (the target's draw decides every token as before),
@@ -1055,10 +1137,11 @@ def dflash_generate(model, target, input_ids: torch.Tensor, mask_token_id: int, 
                                      logprobs, (repetition_penalty, presence_penalty, frequency_penalty),
                                      dict(logit_bias=logit_bias, allowed_token_ids=allowed_token_ids,
                                           banned_token_ids=banned_token_ids, min_tokens=min_tokens),
-                                     constrain_draft=constrain_draft, min_p=min_p, couple_draft=couple_draft)
+                                     constrain_draft=constrain_draft, min_p=min_p, couple_draft=couple_draft,
+                                     stop_sequences=stop_sequences, include_stop_sequence=include_stop_sequence)
     r = run_decode(model, target, input_ids, mask_token_id=mask_token_id, max_new_tokens=max_new_tokens,
                    block_size=block_size, stop_token_ids=stop_token_ids, temperature=temperature, clamp_tail=True,
-                   draft_steps=draft_steps, collect_profile=collect_profile, draft_token_hook=draft_token_hook,
+                   stop_sequences=stop_sequences, include_stop_sequence=include_stop_sequence, draft_steps=draft_steps, collect_profile=collect_profile, draft_token_hook=draft_token_hook,
                    sampler=sampler, seed=seed, top_k=top_k, top_p=top_p, logprobs=logprobs,
                    repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
                    frequency_penalty=frequency_penalty, logit_bias=logit_bias, allowed_token_ids=allowed_token_ids,
@@ -1069,13 +1152,14 @@ def dflash_generate(model, target, input_ids: torch.Tensor, mask_token_id: int, 
                            time_per_output_token=r.time_per_output_token, acceptance_lengths=r.acceptance_lengths,
                            cycle_trace=r.cycle_trace, profile_summary=r.profile_summary,
                            replayed_cycles=r.replayed_cycles, logprobs=r.logprobs, top_logprob_ids=r.top_logprob_ids,
-                           top_logprobs=r.top_logprobs, grammar_state=r.grammar_state)
+                           top_logprobs=r.top_logprobs, grammar_state=r.grammar_state, stop_sequence=r.stop_sequence)
 
 
 def _generate_wide_hidden(model, target, input_ids, mask_token_id, max_new_tokens, block_size, stop_token_ids, temperature,
                           collect_profile=False, draft_steps=1, draft_token_hook=None, sampler="torch",
                           seed=None, top_k=0, top_p=1.0, logprobs=None, penalties=(1.0, 0.0, 0.0),
-                          bias=None, constrain_draft=False, min_p=None, couple_draft=False) -> SimpleNamespace:
+                          bias=None, constrain_draft=False, min_p=None, couple_draft=False, stop_sequences=None,
+                          include_stop_sequence=True) -> SimpleNamespace:
     """hidden_size > 4096: the request runs as a group of ONE through the ragged-batch kernels (their GEMMs cut K over
     workgroups; the single-request kernels keep a whole K = hidden row slice per workgroup).  Same loop semantics
     (benchmark.py:44-251, tail clamp included); no per-cycle profile, one draft step per cycle."""
@@ -1092,7 +1176,8 @@ def _generate_wide_hidden(model, target, input_ids, mask_token_id, max_new_token
                                  seed=None if seed is None else [seed], top_k=top_k, top_p=top_p, logprobs=logprobs,
                                  repetition_penalty=penalties[0], presence_penalty=penalties[1],
                                  frequency_penalty=penalties[2], **_one_prompt_bias(bias),
-                                 constrain_draft=constrain_draft, min_p=min_p, couple_draft=couple_draft)[0]
+                                 constrain_draft=constrain_draft, min_p=min_p, couple_draft=couple_draft,
+                                 stop_sequences=stop_sequences, include_stop_sequence=include_stop_sequence)[0]
 
 
 def _one_prompt_bias(bias) -> dict:
@@ -1111,8 +1196,10 @@ def dflash_generate_policy(*, model, target, input_ids: torch.Tensor, mask_token
                            logprobs: Optional[int] = None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
                            frequency_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None, banned_token_ids=None,
                            min_tokens: int = 0, grammar=None, constrain_draft: bool = False,
-                           min_p=None, couple_draft: bool = False) -> SimpleNamespace:
+                           min_p=None, couple_draft: bool = False, stop_sequences=None,
+                           include_stop_sequence: bool = True) -> SimpleNamespace:
     """benchmark_dynamic_schedule.py:260-272 signature; returns the namespace of :425-434 (+ replayed_cycles).
+    stop_sequences / include_stop_sequence: as dflash_generate (the field `stop_sequence`).
     couple_draft: as dflash_generate; here it REPLACES this loop's own draw on the DRAFT stream (whose acceptance,
     sum p_i q_i, is the lowest of the three drafts), and constrain_draft then works at T > 0.
     min_p: as dflash_generate (the target's draw; the draft's own draw stays unfiltered).
@@ -1131,6 +1218,7 @@ def dflash_generate_policy(*, model, target, input_ids: torch.Tensor, mask_token
     r = run_decode(model, target, input_ids, mask_token_id=mask_token_id, max_new_tokens=max_new_tokens,
                    block_size=max_bs, stop_token_ids=stop_token_ids, temperature=temperature, clamp_tail=True,
                    scheduler=sched, draft_temperature=temperature, max_block_size=max_bs,
+                   stop_sequences=stop_sequences, include_stop_sequence=include_stop_sequence,
                    draft_token_hook=draft_token_hook, sampler=sampler, seed=seed, top_k=top_k, top_p=top_p,
                    logprobs=logprobs, repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
                    frequency_penalty=frequency_penalty, logit_bias=logit_bias, allowed_token_ids=allowed_token_ids,
@@ -1146,7 +1234,7 @@ def dflash_generate_policy(*, model, target, input_ids: torch.Tensor, mask_token
                            time_per_output_token=r.time_per_output_token, acceptance_lengths=r.acceptance_lengths,
                            used_block_sizes=r.used_block_sizes, cycle_trace=r.cycle_trace,
                            replayed_cycles=r.replayed_cycles, logprobs=r.logprobs, top_logprob_ids=r.top_logprob_ids,
-                           top_logprobs=r.top_logprobs, grammar_state=r.grammar_state)
+                           top_logprobs=r.top_logprobs, grammar_state=r.grammar_state, stop_sequence=r.stop_sequence)
 
 
 class _Fixed:

@@ -718,12 +718,13 @@ class DFlashDraftModel:
                       presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None,
                       allowed_token_ids=None, banned_token_ids=None, min_tokens: int = 0,
                       grammar=None, constrain_draft: bool = False, min_p=None,
-                      couple_draft: bool = False) -> torch.LongTensor:
+                      couple_draft: bool = False, stop_sequences=None,
+                      include_stop_sequence: bool = True) -> torch.LongTensor:
         """model/dflash.py:192-277.  sampler / seed / top_k / top_p: as dflash_generate; min_p
         likewise (section 18);
         repetition_penalty / presence_penalty / frequency_penalty likewise (section 13); logit_bias / allowed_token_ids /
         banned_token_ids / min_tokens likewise (section 14); grammar and constrain_draft likewise (section 15); couple_draft likewise
-        (section 20)."""
+        (section 20); stop_sequences / include_stop_sequence likewise (section 22; any target, native or wrapped)."""
         bias = dict(logit_bias=logit_bias, allowed_token_ids=allowed_token_ids, banned_token_ids=banned_token_ids,
                     min_tokens=min_tokens)
         pen = dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
@@ -737,10 +738,12 @@ class DFlashDraftModel:
                                          seed=seed, top_k=top_k, top_p=top_p,
                                          penalties=tuple(pen.values()), bias=bias,
                                          constrain_draft=constrain_draft, min_p=min_p,
-                                         couple_draft=couple_draft).output_ids
+                                         couple_draft=couple_draft, stop_sequences=stop_sequences,
+                                         include_stop_sequence=include_stop_sequence).output_ids
         r = run_decode(self, target, input_ids, mask_token_id=self.mask_token_id, max_new_tokens=max_new_tokens,
                        block_size=self.block_size, stop_token_ids=stop_token_ids, temperature=temperature,
                        clamp_tail=False, draft_token_hook=draft_token_hook, sampler=sampler, seed=seed, top_k=top_k,
                        top_p=top_p, **pen, **bias, grammar=grammar, constrain_draft=constrain_draft, min_p=min_p,
-                       couple_draft=couple_draft)
+                       couple_draft=couple_draft, stop_sequences=stop_sequences,
+                       include_stop_sequence=include_stop_sequence)
         return r.output_ids

@@ -1773,6 +1773,115 @@ def accept_commit(block_ids, posterior, bs: int, output_ids, dyn, stop_ids=None,
                                   int(n), int(mask_id), _p(dyn_t, I32, "dyn_t"), _stream()), "dfl_accept_commit")
 
 
+# ---- stop sequences (csrc/stop_seq.hip)
+STOP_SEQS, STOP_SEQ_LEN = 8, 16   # DFL_STOP_SEQS, DFL_STOP_SEQ_LEN
+
+
+def check_stop_sequences(seqs, V: int, mask_token_id: Optional[int] = None):
+    """Normalise one request's stop sequences to a list of lists of ints (a bare int: a sequence of length 1); None for
+    None or an empty list — the path without the feature.  ValueError, before anything touches the GPU: an empty
+    sequence, more than 8 sequences, a sequence longer than 16, an id outside [0, V), the mask id inside a sequence."""
+    import operator
+    if seqs is None:
+        return None
+    if isinstance(seqs, (str, bytes)) or not hasattr(seqs, "__iter__"):
+        raise ValueError(f"dflash_amd: stop_sequences must be a list of token-id sequences, got {seqs!r}")
+    out = []
+    for k, s in enumerate(seqs):
+        if torch.is_tensor(s):
+            s = s.tolist()
+        if isinstance(s, (str, bytes)):
+            raise ValueError(f"dflash_amd: stop_sequences[{k}]: {s!r} is text; token ids are what is matched")
+        if not hasattr(s, "__iter__"):
+            s = [s]
+        ids = []
+        for v in s:
+            try:
+                i = operator.index(v)
+            except TypeError:
+                raise ValueError(f"dflash_amd: stop_sequences[{k}]: {v!r} is not a token id") from None
+            if not 0 <= i < V:
+                raise ValueError(f"dflash_amd: stop_sequences[{k}]: id {i} outside [0, {V})")
+            if mask_token_id is not None and i == int(mask_token_id):
+                raise ValueError(f"dflash_amd: stop_sequences[{k}] holds the mask id {i}, which is never committed")
+            ids.append(i)
+        if not ids:
+            raise ValueError(f"dflash_amd: stop_sequences[{k}] is empty")
+        if len(ids) > STOP_SEQ_LEN:
+            raise ValueError(f"dflash_amd: stop_sequences[{k}] has {len(ids)} ids, more than {STOP_SEQ_LEN}")
+        out.append(ids)
+    if len(out) > STOP_SEQS:
+        raise ValueError(f"dflash_amd: {len(out)} stop sequences, more than {STOP_SEQS}")
+    return out or None
+
+
+def stop_seq_state(slots: int, device) -> SimpleNamespace:
+    """The stop-sequence state, one row per request slot: .seq_ids int32 [slots, 8, 16], .seq_len
+    int32 [slots, 8] (0: unused), .first_pos / .min_end int32 [slots], .hit int32 [slots, 2] ({-1, -1}: no match yet).
+    Written by stop_seq_set, read (hit: written) by stop_seq_rows."""
+    if slots < 1:
+        raise ValueError(f"dflash_amd: stop_seq_state: slots={slots} < 1")
+    return SimpleNamespace(seq_ids=torch.zeros(slots, STOP_SEQS, STOP_SEQ_LEN, dtype=I32, device=device),
+                           seq_len=torch.zeros(slots, STOP_SEQS, dtype=I32, device=device),
+                           first_pos=torch.zeros(slots, dtype=I32, device=device),
+                           min_end=torch.zeros(slots, dtype=I32, device=device),
+                           hit=torch.full((slots, 2), -1, dtype=I32, device=device))
+
+
+def stop_seq_set(state, slot: int, seqs, first_pos: int = 0, min_end: int = 0) -> None:
+    """Rewrite slot's rows whole: its sequences (a list of lists of ints as check_stop_sequences returns it; None: none),
+    first_pos (the first position a window may cover: the prompt's length), min_end (no match ends before it; 0: off)
+    and hit <- {-1, -1}: nothing of the slot's previous request survives.  Admission only, plain copies."""
+    slots = state.seq_len.shape[0]
+    if not 0 <= slot < slots:
+        raise ValueError(f"dflash_amd: stop_seq_set: slot {slot} outside 0..{slots - 1}")
+    seqs = seqs or []
+    if len(seqs) > STOP_SEQS or any(not 1 <= len(s) <= STOP_SEQ_LEN for s in seqs):
+        raise ValueError("dflash_amd: stop_seq_set: at most 8 sequences of 1..16 ids (check_stop_sequences)")
+    ids = torch.zeros(STOP_SEQS, STOP_SEQ_LEN, dtype=I32)
+    lens = torch.zeros(STOP_SEQS, dtype=I32)
+    for k, s in enumerate(seqs):
+        ids[k, :len(s)] = torch.tensor(s, dtype=I32)
+        lens[k] = len(s)
+    state.seq_ids[slot].copy_(ids)
+    state.seq_len[slot].copy_(lens)
+    state.first_pos[slot:slot + 1].fill_(int(first_pos))
+    state.min_end[slot:slot + 1].fill_(int(min_end))
+    state.hit[slot].fill_(-1)
+
+
+def stop_seq_rows(block: torch.Tensor, posterior: torch.Tensor, output_ids: torch.Tensor, dyn: torch.Tensor, state,
+                  bs: Optional[int] = None, slots: Optional[int] = None, output_len: Optional[int] = None) -> None:
+    """Match every slot's stop sequences over the tokens the accept launch behind this one is about to commit
+    (dfl_stop_seq_rows): block / posterior int64 [slots, >= bs] (or 1-D for one slot), output_ids int64 [slots, n] (or
+    1-D), dyn the int32 length records [slots, 8] the accept launch reads (the ragged batch: dyn_d).  bs None: every
+    slot's own DFL_DYN_BS word.  slots None: all of the state's.  A match ORs 1 into the slot's stop word and, the first
+    time, stores {end position, sequence index} in state.hit."""
+    if block.dim() == 1:
+        block, posterior = block.unsqueeze(0), posterior.unsqueeze(0)
+    if output_ids.dim() == 1:
+        output_ids = output_ids.unsqueeze(0)
+    if slots is None:
+        slots = state.seq_len.shape[0]
+    assert 1 <= slots <= state.seq_len.shape[0], "slots"
+    assert block.dim() == 2 and posterior.dim() == 2 and output_ids.dim() == 2
+    assert block.stride(1) == 1 and posterior.stride(1) == 1 and output_ids.stride(1) == 1
+    assert block.shape[0] >= slots and posterior.shape[0] >= slots and output_ids.shape[0] >= slots, "one row per slot"
+    assert dyn.numel() >= 8 * slots and dyn.is_contiguous(), "dyn"
+    assert state.seq_ids.is_contiguous() and state.seq_len.is_contiguous() and state.hit.is_contiguous()
+    out_len = output_ids.shape[1] if output_len is None else int(output_len)
+    assert 1 <= out_len <= output_ids.shape[1]
+    # (one slot: its row's length stands for the stride, which nothing is addressed by)
+    one = slots == 1
+    check(lib().dfl_stop_seq_rows(_p(block, I64, "block"), block.shape[1] if one else block.stride(0),
+                                  _p(posterior, I64, "posterior"), posterior.shape[1] if one else posterior.stride(0),
+                                  _p(output_ids, I64, "output_ids"), output_ids.shape[1] if one else output_ids.stride(0),
+                                  out_len, _p(dyn, I32, "dyn"), slots, -1 if bs is None else int(bs),
+                                  _p(state.seq_ids, I32, "seq_ids"), _p(state.seq_len, I32, "seq_len"),
+                                  _p(state.first_pos, I32, "first_pos"), _p(state.min_end, I32, "min_end"),
+                                  _p(state.hit, I32, "hit"), _stream()), "dfl_stop_seq_rows")
+
+
 # ---- ragged batch of requests (include/dflash_hip.h, second half) ---------------------------
 from ._lib import RowsBatch  # noqa: E402
 

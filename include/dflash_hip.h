@@ -991,6 +991,33 @@ int dfl_admit_slot(int r, int n_slots, const int64_t *prompt_ids, int P, const i
                    const void *tail_rows, int64_t ld_tail, int n_tail, void *taps, int fc_in, int32_t *dyn_d,
                    int32_t *dyn_t, int bs, int64_t *seeds, int64_t seed, int64_t mask_id, void *stream);
 
+/* Stop sequences: per-slot, multi-token stops matched in front of the accept launch, over
+ * exactly the tokens that launch is about to commit.  One wavefront per slot s = 0 .. slots-1; rows of slot s at
+ * block_ids + s * blk_stride, posterior + s * post_stride, output_ids + s * out_stride (int64), its record at
+ * dyn + s * DFL_DYN_WORDS (for the ragged batch: the draft-form record dyn_d, whose stop word the accept launch copies
+ * and publishes), its tables at
+ *   seq_ids   int32 [slots][DFL_STOP_SEQS][DFL_STOP_SEQ_LEN]      seq_len  int32 [slots][DFL_STOP_SEQS], 0 = unused
+ *   first_pos int32 [slots]   min_end  int32 [slots]               hit      int32 [slots][2], {-1, -1} = none yet
+ * bs >= 0: the block size of every slot; bs < 0: the record's DFL_DYN_BS word (cut to min(32, blk_stride, post_stride):
+ * nothing past a row is read).  With start = dyn[DFL_DYN_START] and acc = the leading i < bs - 1 with
+ * block_ids[i + 1] == posterior[i] (the accept launch's ballot), the newly committed ids are those of positions
+ * start + 1 .. start + acc + 1 = block_ids[1 .. acc] then posterior[acc]; position start and everything before it is
+ * read from output_ids (never below index 0, never at or past output_len).  For every end position e in that range and
+ * every sequence k with length L_k > 0 (a stored length is taken into 0..16), the window [e - L_k + 1, e] MATCHES when it
+ * equals seq_ids[s][k][0 .. L_k), e - L_k + 1 >= max(first_pos[s], 0) and e >= min_end[s].  Of all matches the smallest e
+ * wins, at equal e the smallest k; then dyn[DFL_DYN_STOP] |= 1 and, only while hit[s] is still {-1, -1}, hit[s] <- {e, k}.
+ * A slot with block size 0 or with every L_k == 0 is left untouched, and so is everything of a slot without a match.
+ * Nothing but the stop word and hit is written, with plain vector stores; the logits are never read.
+ * DFL_EINVAL, nothing launched: a null pointer, slots < 1, bs > 32, blk_stride or post_stride below max(bs, 1),
+ * output_len < 1, out_stride < output_len.  bs == 0 launches nothing and returns DFL_OK. */
+#define DFL_STOP_SEQS 8
+#define DFL_STOP_SEQ_LEN 16
+#define DFL_STOP_SEQ_MAX_BS 32
+int dfl_stop_seq_rows(const int64_t *block_ids, int64_t blk_stride, const int64_t *posterior, int64_t post_stride,
+                      const int64_t *output_ids, int64_t out_stride, int64_t output_len, int32_t *dyn, int slots, int bs,
+                      const int32_t *seq_ids, const int32_t *seq_len, const int32_t *first_pos, const int32_t *min_end,
+                      int32_t *hit, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
