@@ -287,7 +287,8 @@ int dfl_qknorm_rope_append(const float *qkv, int nsplit, int64_t split_stride, i
  * (the draft, is_causal=False, model/dflash.py:86-99).  causal = 1: query row j sees
  * cache rows <= S + tau + j (the target's verify forward over the same block).  MFMA QK^T / PV, K/V tiles
  * staged in LDS, split over the key axis with a log-sum-exp merge.
- * ws: dfl_attn_ws_bytes(n_q, max_splits) bytes.  out: frag16 [n_q*128/8][16][8]. */
+ * ws: dfl_attn_ws_bytes(n_q, max_splits) bytes.  out: frag16 [n_q*128/8][16][8].
+ * GQA group n_q / n_kv: 1..8 (one wave per query head of the group); anything else is DFL_EINVAL, nothing launched. */
 int64_t dfl_attn_ws_bytes(int n_q, int max_splits);
 int dfl_block_attn(const void *q, const void *kcache, const void *vcache, int cache_rows, int n_q, int n_kv,
                    float scale, int causal, const int32_t *dyn, int kv_len_max, void *ws, int max_splits,
@@ -299,7 +300,9 @@ int dfl_block_attn(const void *q, const void *kcache, const void *vcache, int ca
  * dfl_qknorm_rope_append + dfl_block_attn (V rows bit-identical, K up to rare 1-ulp flips); the key axis is
  * split over workgroups and merged by the last one to arrive.  tau + bs <= 32 new rows.
  * ws: dfl_attn_fused_ws_bytes(n_q, n_kv, max_splits) bytes, ZEROED once by the caller
- * (it holds the arrival tickets, which every launch leaves at zero again). */
+ * (it holds the arrival tickets, which every launch leaves at zero again).
+ * GQA group n_q / n_kv: 1, 2, 4 or 8 (dfl_attn_fused_batch likewise); anything else is DFL_EINVAL, nothing launched.
+ * dfl_attn_head and its forms and dfl_prefill_attn take any n_q % n_kv == 0. */
 int64_t dfl_attn_fused_ws_bytes(int n_q, int n_kv, int max_splits);
 int dfl_attn_fused(const float *qkv, int nsplit, int64_t split_stride, int ld, int q_col, int k_col, int v_col,
                    int ctx_row0, int blk_row0, int n_q, int n_kv, const void *q_norm_w, const void *k_norm_w,

@@ -61,18 +61,20 @@ def prefill_visibility(P: int) -> torch.Tensor:
     return decode_visibility(0, 0, P, True)
 
 
-def attention_ref(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, vis: torch.Tensor, scale: float = SCALE):
+def attention_ref(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, vis: torch.Tensor, scale: float = SCALE, kv_of=None):
     """Plain fp64 softmax attention with GQA and an explicit visibility mask.  q [rows, n_q, 128], k / v
-    [n_kv, keys, 128], vis [rows, keys] -> (out fp64 [rows, n_q, 128], largest weight of each row fp64 [rows, n_q])."""
+    [n_kv, keys, 128], vis [rows, keys] -> (out fp64 [rows, n_q, 128], largest weight of each row fp64 [rows, n_q]).
+    kv_of (the CPU mutants of test_attn_keys_cpu only): the kv head of query head h, for h // G."""
     rows, n_q, _ = q.shape
     G = n_q // k.shape[0]
+    kv_of = kv_of or (lambda h: h // G)
     out = torch.empty(rows, n_q, D, dtype=F64)
     top = torch.empty(rows, n_q, dtype=F64)
     for h in range(n_q):
-        sc = (q[:, h].double() @ k[h // G].double().T) * scale
+        sc = (q[:, h].double() @ k[kv_of(h)].double().T) * scale
         sc = sc.masked_fill(~vis, float("-inf"))
         p = torch.softmax(sc, dim=-1)
-        out[:, h] = p @ v[h // G].double()
+        out[:, h] = p @ v[kv_of(h)].double()
         top[:, h] = p.max(dim=-1).values
     return out, top
 
@@ -213,7 +215,9 @@ def _patterns(bs: int, causal: bool, prefill: bool):
 def needle_slot_keys(S, tau, bs, causal, G, prefill=False) -> list:
     """Per launch an int64 [bs, G] table: the key (row j, head g of the kv group) probes, -1: none.  Slot k = launch * G
     + g: the first slots walk the block rows by pattern (the causal diagonal first), the others share out the cached
-    and context positions; at most MAX_LAUNCHES launches (the positions are thinned evenly beyond that)."""
+    and context positions, and once those run out the slots left in a launch walk the block rows again (a group
+    larger than the slots there are to fill: every launch still probes every head); at most MAX_LAUNCHES launches (the
+    positions are thinned evenly beyond that)."""
     pats = _patterns(bs, causal, prefill)
     free = [] if prefill else probe_positions(S, tau)
     cap = MAX_LAUNCHES * G * bs - len(pats) * bs
@@ -223,8 +227,8 @@ def needle_slot_keys(S, tau, bs, causal, G, prefill=False) -> list:
     while k < len(pats) or nxt < len(free):
         tab = torch.full((bs, G), -1, dtype=torch.long)
         for g in range(G):
-            if k < len(pats):
-                blk = pats[k]
+            if k < len(pats) or nxt >= len(free):       # nothing left for this slot: the block rows again, so that every
+                blk = pats[k % len(pats)]               # launch probes EVERY head of the group (G > the slots there are)
                 tab[:, g] = torch.where(blk >= 0, S + tau + blk, blk)
             for j in range(bs):
                 if tab[j, g] < 0 and nxt < len(free):
@@ -241,6 +245,7 @@ def needle_problem(S, tau, bs, causal, n_q, n_kv, slot_keys: torch.Tensor, seed=
     n = S + tau + bs
     g = _gen(seed)
     v = _randn_bf16((n_kv, n, D), g)
+    v[v == 0] = 1.0     # an element that is exactly 0 cannot come back bit-equal: the other keys' 2^-65 weights show beside it
     k = torch.zeros(n_kv, n, D, dtype=BF16)
     q = torch.zeros(bs, n_q, D, dtype=BF16)
     codes = _pairs(seed)
