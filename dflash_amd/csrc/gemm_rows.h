@@ -111,6 +111,23 @@ __device__ __forceinline__ bf16x8 w4_frag(bf16x8 raw, uint32_t scales, int d) {
   return (bf16x8){a[0], a[1], b[0], b[1], c[0], c[1], e[0], e[1]};
 }
 
+// The expert kernels' item (moe_w4.hip): NT 16-byte words per lane — 1 KiB wave words — that lie `stride` words apart (the
+// same word of NT consecutive tiles), each with its 64-byte scale line at the same stride in lines, through ONE descriptor
+// for the words and one for the scales.  The first n (0..NT) words are inside the descriptors; the others, and all of a dead
+// item (n = 0), read code 0 under scale code 0.  load_ksteps_w4's rule of issue: every scale dword in front of its word.
+template <int NT, int AUX = 2>
+__device__ __forceinline__ void load_words_w4(bf16x8 (&wr)[NT], uint32_t (&sc)[NT], const bf16x8 *first, const char *first_scale,
+                                              int n, int stride, int l) {
+  const int span = n > 0 ? (n - 1) * stride + 1 : 0;
+  const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16x8 *>(first), 0, span * 1024, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(first_scale), 0, span * 64, 0x00020000);
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    sc[t] = __builtin_amdgcn_raw_buffer_load_b32(rs, (l & 15) * 4, t * stride * 64, AUX);
+    wr[t] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rw, l * 16, t * stride * 1024, AUX));
+  }
+}
+
 // ---- W13: bf16 weights stored losslessly in 13 bits (DFL_W_BF16X13, dflash_hip.h) ----
 // A bf16 is L = bits[7:0] (e0, m6..m0) and H = bits[15:8] (s, e7..e1).  Per packed 16-column tile, hb = max(0, max(H & 0x7f)
 // - 15); a weight keeps L, its sign and a 4-bit code c: c = 0 <=> (H & 0x7f) == 0, c = 1..15 <=> (H & 0x7f) == hb + c.

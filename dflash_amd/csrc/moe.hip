@@ -643,12 +643,22 @@ int moe_gate_up_impl(const char *who, const dfl_weight *w, const void *x_frag, i
 }
 }  // namespace
 
+// The DFL_W_MXFP4 forms of the two expert launches (moe_w4.hip: kernels and argument structs of their own, so the
+// instantiations in this file do not change by an instruction)
+int dfl_moe_gate_up_w4(const char *who, const dfl_weight *w, const void *x_frag, int E, int I, int K, void *act_frag,
+                       const int32_t *list, const int32_t *n_active, const int32_t *dyn, int valid_word, void *stream);
+int dfl_moe_down_w4(const char *who, const dfl_weight *w, int64_t wp_expert_stride, const void *act_frag,
+                    int64_t act_expert_stride, const void *wt, const int32_t *list, const int32_t *n_active, int E, int N, int I,
+                    int nsplit, float *out, void *stream);
+
 extern "C" int dfl_moe_gate_up(const dfl_weight *w_gateup, const void *x_frag, int E, int I, int K, void *act_frag,
                                const int32_t *list, const int32_t *n_active, const int32_t *dyn, int valid_word,
                                void *stream) {
   const char *who = "dfl_moe_gate_up";
   if (w_gateup && w_gateup->format == DFL_W_BF16X13)  // (weight_ok knows the two formats every entry point takes)
     return moe_gate_up_impl<false, true>(who, w_gateup, x_frag, E, I, K, act_frag, list, n_active, dyn, valid_word, stream);
+  if (w_gateup && w_gateup->format == DFL_W_MXFP4)
+    return dfl_moe_gate_up_w4(who, w_gateup, x_frag, E, I, K, act_frag, list, n_active, dyn, valid_word, stream);
   if (!weight_ok(who, w_gateup)) return DFL_EINVAL;
   return w_gateup->format == DFL_W_BF16
              ? moe_gate_up_impl<false>(who, w_gateup, x_frag, E, I, K, act_frag, list, n_active, dyn, valid_word, stream)
@@ -767,6 +777,8 @@ extern "C" int dfl_moe_down(const dfl_weight *w_down, int64_t wp_expert_stride, 
                             int64_t act_expert_stride, const void *wt, const int32_t *list, const int32_t *n_active, int E,
                             int N, int I, int nsplit, float *out, void *stream) {
   const char *who = "dfl_moe_down";
+  if (w_down && w_down->format == DFL_W_MXFP4)
+    return dfl_moe_down_w4(who, w_down, wp_expert_stride, act_frag, act_expert_stride, wt, list, n_active, E, N, I, nsplit, out, stream);
   if (!weight_ok(who, w_down)) return DFL_EINVAL;
   return w_down->format == DFL_W_BF16 ? moe_down_impl<false>(who, w_down, wp_expert_stride, act_frag, act_expert_stride, wt,
                                                              list, n_active, E, N, I, nsplit, out, stream)

@@ -403,6 +403,38 @@ def pack_weight_gateup_mxfp4(gate_codes: torch.Tensor, gate_scales: torch.Tensor
     return pack_weight_mxfp4(weave(gate_codes, up_codes), weave(gate_scales, up_scales))
 
 
+class Mxfp4Experts(NamedTuple):
+    """One MoE layer's expert weights of one kind as MXFP4 (pack_experts_mxfp4): expert e's packed codes in row e, the e8m0
+    scales an array of their own.  moe_gate_up (K <= 2048) / moe_down take one in place of the packed bf16 [E, .] tensor."""
+    wp: torch.Tensor      # uint8 [E, N * K / 2]: per expert the code region of pack_weight_gateup_mxfp4 (N = 2I) / pack_weight_mxfp4
+    sc: torch.Tensor      # uint8 [E, N * K / 32]: per expert that layout's scale region ([tiles][K/128][16 columns][4 B])
+    E: int
+    N: int                # output rows per expert: 2 * I (gate/up) or the hidden width (down)
+    K: int
+
+
+def pack_experts_mxfp4(codes: torch.Tensor, scales: torch.Tensor, gateup: bool) -> Mxfp4Experts:
+    """codes uint8 [E, N, K/2] and scale codes uint8 [E, N, K/32] (quantize_mxfp4_rows of the [E * N, K] view) -> Mxfp4Experts.
+    gateup: N = 2I with rows 0 .. I-1 the gate and I .. 2I-1 the up projection (HF's fused gate_up_proj), tiles interleaved;
+    else a plain [N, K] weight per expert (down_proj).  Byte permutations, one expert at a time, on the codes' device."""
+    e, n, k2 = codes.shape
+    k = 2 * k2
+    if codes.dtype != U8 or scales.dtype != U8 or tuple(scales.shape) != (e, n, k // MX_BLOCK):
+        raise ValueError(f"dflash_amd: pack_experts_mxfp4 takes uint8 [E, N, K/2] and [E, N, K/32], got {tuple(codes.shape)}, "
+                         f"{tuple(scales.shape)}")
+    wp = torch.empty(e, n * k2, dtype=U8, device=codes.device)
+    sc = torch.empty(e, n * k // MX_BLOCK, dtype=U8, device=codes.device)
+    for j in range(e):
+        if gateup:
+            i = n // 2
+            w4 = pack_weight_gateup_mxfp4(codes[j, :i], scales[j, :i], codes[j, i:], scales[j, i:])
+        else:
+            w4 = pack_weight_mxfp4(codes[j], scales[j])
+        wp[j].copy_(w4.data[:n * k2])
+        sc[j].copy_(w4.data[n * k2:])
+    return Mxfp4Experts(wp, sc, e, n, k)
+
+
 def quantize_keep_mxfp4(m: torch.Tensor):
     """The load step of an mxfp4 model for one Linear weight [N, K]: (the dequantised values as bf16 — what every path
     without a 4-bit kernel computes with —, (codes, scale codes) for pack_weight_mxfp4 / pack_layer_mxfp4)."""
@@ -445,8 +477,13 @@ def _w(wp, N: int, K: int, name: str) -> Weight:
 
 
 def _we(wp, E: int, N: int, K: int, name: str):
-    """_w for one MoE layer's experts: packed bf16 [E, .] or an Fp8Experts of E x N x K.  Returns the descriptor and the
+    """_w for one MoE layer's experts: packed bf16 [E, .], an Fp8Experts or an Mxfp4Experts of E x N x K.  Returns the descriptor and the
     tensor whose rows are the experts (its stride(0): bf16 elements, or bytes of codes, between them)."""
+    if isinstance(wp, Mxfp4Experts):
+        if (wp.E, wp.N, wp.K) != (E, N, K):
+            raise ValueError(f"dflash_amd: {name} holds mxfp4 experts of {wp.E} x {wp.N} x {wp.K}, the launch asks for "
+                             f"{E} x {N} x {K}")
+        return Weight(_p(wp.wp, U8, name), _p(wp.sc, U8, name + ".sc"), W_MXFP4), wp.wp   # (the scale codes ride in `scale`)
     if not isinstance(wp, Fp8Experts):
         assert wp.dim() == 2 and wp.is_contiguous()
         return Weight(_p(wp, BF16, name), None, W_BF16), wp
@@ -1714,14 +1751,14 @@ def gemm_silu_mul_experts(wp_gu: torch.Tensor, x, E: int, I: int, K: int, act: t
 def moe_gate_up(wp_gu: torch.Tensor, x_frag: torch.Tensor, E: int, I: int, K: int, act: torch.Tensor, lst: torch.Tensor,
                 n_active: torch.Tensor, dyn=None, valid_word: int = -1) -> None:
     """gemm_silu_mul_experts for K <= 2048 from frag16 rows: one LDS meeting per (gate, up) tile pair.  wp_gu: packed
-    bf16 [E, 2*I*K], an Fp8Experts, or (K = 2048) the Bf16x13Weight of that packed tensor as ONE matrix of E * 2I x K
+    bf16 [E, 2*I*K], an Fp8Experts, an Mxfp4Experts (K % 128 == 0), or (K = 2048) the Bf16x13Weight of that packed tensor as ONE matrix of E * 2I x K
     (pack_weight_bf16x13: the experts' tiles back to back) — the same bits as the packed tensor gives."""
     assert act.dim() == 2 and act.is_contiguous() and act.shape[1] == 16 * I and x_frag.numel() >= 16 * K
     if isinstance(wp_gu, Bf16x13Weight):
         w = _w(wp_gu, E * 2 * I, K, "wp_gu")
     else:
         w, rows = _we(wp_gu, E, 2 * I, K, "wp_gu")
-        assert rows.shape[1] == 2 * I * K
+        assert rows.shape[1] == (I * K if isinstance(wp_gu, Mxfp4Experts) else 2 * I * K)
     check(lib().dfl_moe_gate_up(w, _p(x_frag, BF16, "x_frag"), E, I, K, _p(act, BF16, "act"), _p(lst, I32, "list"),
                                 _p(n_active, I32, "n_active"), _p(dyn, I32, "dyn"), valid_word, _stream()),
           "dfl_moe_gate_up")
@@ -1729,7 +1766,7 @@ def moe_gate_up(wp_gu: torch.Tensor, x_frag: torch.Tensor, E: int, I: int, K: in
 
 def moe_down(wp_down: torch.Tensor, act: torch.Tensor, wt: torch.Tensor, lst: torch.Tensor, n_active: torch.Tensor, E: int,
              N: int, I: int, nsplit: int, out: torch.Tensor) -> None:
-    """wp_down bf16 [E, N*I] packed per expert, or an Fp8Experts; out fp32 [nsplit, 16, N]."""
+    """wp_down bf16 [E, N*I] packed per expert, an Fp8Experts, or an Mxfp4Experts (I % 128 == 0); out fp32 [nsplit, 16, N]."""
     assert act.dim() == 2 and act.is_contiguous()
     assert out.dtype == F32 and out.is_contiguous() and out.numel() >= nsplit * 16 * N
     w, rows = _we(wp_down, E, N, I, "wp_down")

@@ -25,7 +25,7 @@ import torch
 
 from . import ops
 from .logits_stage import LogitsStage
-from .model import TARGET_WEIGHT_FORMATS as WEIGHT_FORMATS, _rope_tables
+from .model import EXPERT_FORMATS, TARGET_WEIGHT_FORMATS as WEIGHT_FORMATS, _rope_tables
 from .row_stack import RowStack
 from .tile_stack import TileStack, gemm_ws
 from .utils import sample
@@ -112,6 +112,13 @@ class NativeTarget:
         `self.experts8[i]` holds layer i's codes and scales (ops.Fp8Experts; None for a dense layer), which the <= 16-row
         verify, the per-tile expert branch and the shared pass over 2..4 tiles stream while `self.expert_stream` is True
         ("The experts"; the native MoE prefill reads the copy).  What weight-only e4m3 does to a real MoE checkpoint's routing and outputs is NOT measured.
+        expert_format="mxfp4": the same for OCP MXFP4 (ops.quantize_mxfp4_rows: e2m1 codes, one power-of-two scale per 32
+        consecutive k of a row; hidden and moe_intermediate sizes % 128 == 0) — both expert tensors of hf_model are
+        overwritten with the dequantised values, lw["gu_e"] / lw["down_e"] stay their packed bf16 copy, and
+        `self.experts4[i]` (ops.Mxfp4Experts; lw["gu_e4"] / lw["down_e4"]) holds the codes and block scales, which the
+        <= 16-row verify and the per-tile expert branch stream while `self.expert_stream` is True; the shared pass over
+        2..4 tiles, the prefill and gate/up at hidden > 2048 read the copy ("The experts").  What
+        weight-only MXFP4 does to a real MoE checkpoint's routing and outputs is NOT measured.
         attn_impl: "head" = dfl_attn_head on finished bf16 q/k/v rows (round 2, default); "fused" = the
         round-1 stage (fp32 K-split partials -> dfl_attn_fused), kept for A/B measurement and as a second
         implementation the tests compare against.
@@ -149,6 +156,8 @@ class NativeTarget:
         # fp8 experts only: False = the bf16 expert kernels on the dequantised copy (the second implementation the tests compare)
         self.expert_stream = True
         self.experts8 = [] if e8 else None   # per layer: {"gu_e", "down_e"} ops.Fp8Experts twins, None for a dense layer
+        e4 = expert_format == "mxfp4"
+        self.experts4 = [] if e4 else None   # per layer: {"gu_e", "down_e"} ops.Mxfp4Experts twins, None for a dense layer
         # fp8_e4m3 only: False = the bf16 kernels on the dequantised copy (the second implementation the tests compare)
         self.fp8_stream = True
         self.layers8 = [] if fp8 else None   # per layer: ops.Fp8Weight twins of qkv / o / gu / down in self.layers
@@ -249,10 +258,21 @@ class NativeTarget:
                         del q, sc
                     self.experts8.append(x8)
                     lw["gu_e8"], lw["down_e8"] = x8["gu_e"], x8["down_e"]   # (the layer dict is what moe_mlp_tiles is handed)
+                if e4:   # MXFP4 codes + block scales; the model's own tensors and what is packed below become the dequantised values
+                    x4 = {}
+                    for key, name, t in (("gu_e", "mlp.experts.gate_up_proj", gup), ("down_e", "mlp.experts.down_proj", dwn)):
+                        q, sc = ops.quantize_mxfp4_rows(t.view(-1, t.shape[2]))
+                        t.copy_(ops.dequantize_mxfp4_rows(q, sc).view_as(t))
+                        with torch.no_grad():
+                            sd[p + name].copy_(t)
+                        x4[key] = ops.pack_experts_mxfp4(q.view(*t.shape[:2], -1), sc.view(*t.shape[:2], -1), gateup=key == "gu_e")
+                        del q, sc
+                    self.experts4.append(x4)
+                    lw["gu_e4"], lw["down_e4"] = x4["gu_e"], x4["down_e"]
                 lw["gu_e"] = torch.stack([ops.pack_weight_gateup(gup[e, :Ie].contiguous(), gup[e, Ie:].contiguous())
                                           for e in range(self.E)])
                 lw["down_e"] = torch.stack([ops.pack_weight(dwn[e].contiguous()) for e in range(self.E)])
-                if self.x13 and not e8 and self.H == 2048:   # the experts' gate/up as ONE tall matrix in 13 bits
+                if self.x13 and not e8 and not e4 and self.H == 2048:   # the experts' gate/up as ONE tall matrix in 13 bits
                     g13 = ops.bf16x13_twin(lw["gu_e"], self.E * 2 * Ie, self.H, "experts_gateup")
                     if g13 is not None:   # (None: the kind is off or the packer refused the matrix — plain bf16 stays)
                         lw["gu_e13"] = g13   # (held by the layer dict: a captured verify reads it for the target's lifetime)
@@ -277,6 +297,8 @@ class NativeTarget:
                     down13 = ops.bf16x13_twin(lw["down"], self.H, self.I, "down")
                 if e8:
                     self.experts8.append(None)
+                if e4:
+                    self.experts4.append(None)
             if fp8:
                 if "gate" not in l8:
                     raise NotImplementedError("NativeTarget: fp8_e4m3 needs dense MLP layers")
@@ -354,11 +376,11 @@ class NativeTarget:
         one is a ValueError; "fp8_e4m3" refuses a sparse-MoE target (its experts take expert_format instead) and hidden,
         intermediate or q widths that are not multiples of 64 (the packed e4m3 layout holds k-step pairs).
         expert_format: an unknown one is a ValueError; "fp8_e4m3" needs a sparse-MoE config (num_experts) whose hidden_size
-        and moe_intermediate_size are multiples of 64."""
+        and moe_intermediate_size are multiples of 64; "mxfp4" one whose two widths are multiples of 128 (a 4-k-step word)."""
         if weight_format not in WEIGHT_FORMATS:
             raise ValueError(f"NativeTarget: weight_format must be one of {WEIGHT_FORMATS}, got {weight_format!r}")
-        if expert_format not in WEIGHT_FORMATS:
-            raise ValueError(f"NativeTarget: expert_format must be one of {WEIGHT_FORMATS}, got {expert_format!r}")
+        if expert_format not in EXPERT_FORMATS:
+            raise ValueError(f"NativeTarget: expert_format must be one of {EXPERT_FORMATS}, got {expert_format!r}")
         n_q = cfg.num_attention_heads
         hd = getattr(cfg, "head_dim", None) or cfg.hidden_size // n_q
         if hd != 128:
@@ -389,6 +411,16 @@ class NativeTarget:
             bad = {k: v for k, v in widths.items() if not v or v % 64}
             if bad:
                 raise NotImplementedError(f"NativeTarget: fp8_e4m3 experts need hidden and moe_intermediate widths % 64 == 0 "
+                                          f"(got {bad})")
+
+        if expert_format == "mxfp4":
+            if not getattr(cfg, "num_experts", 0):
+                raise NotImplementedError("NativeTarget: expert_format='mxfp4' needs a sparse-MoE target (Qwen3-MoE expert "
+                                          "layout); the 4-bit format has no dense target form")
+            widths = dict(hidden_size=cfg.hidden_size, moe_intermediate_size=getattr(cfg, "moe_intermediate_size", 0))
+            bad = {k: v for k, v in widths.items() if not v or v % 128}
+            if bad:
+                raise NotImplementedError(f"NativeTarget: mxfp4 experts need hidden and moe_intermediate widths % 128 == 0 "
                                           f"(got {bad})")
 
     # ---- HF-compatible surface (the reference loop can still drive the wrapped model)
@@ -448,15 +480,21 @@ class NativeTarget:
             ws += [w8 for l8 in self.layers8 for w8 in l8.values()] + [self.lm_wp8]
         if self.experts8 is not None:
             ws += [x8 for l8 in self.experts8 if l8 is not None for x8 in l8.values()]
-        return tuple(t for w8 in ws for t in (w8.wp, w8.scale))
+        ts = [t for w8 in ws for t in (w8.wp, w8.scale)]
+        if self.experts4 is not None:   # (an mxfp4-expert target's codes and block scales)
+            ts += [t for l4 in self.experts4 if l4 is not None for x4 in l4.values() for t in (x4.wp, x4.sc)]
+        return tuple(ts)
 
     def expert_weights(self, lw: dict) -> tuple:
         """(gate/up, down) weights of an MoE layer (its dict in self.layers) for the two expert launches on <= 16 rows:
         the e4m3 codes (ops.Fp8Experts) of an fp8-expert target while expert_stream is set — gate/up only where the pair
         kernel runs (hidden <= 2048, moe_pair_kernel): dfl_gemm_silu_mul_experts has no W8 form — else the packed bf16
         copy; of a bf16 target under stream_format="auto", gate/up is the layer's 13-bit twin (lw["gu_e13"], hidden 2048)
-        where the pair kernel runs and the packer took the matrix: the same bits from 13/16 of the bytes."""
+        where the pair kernel runs and the packer took the matrix: the same bits from 13/16 of the bytes.  An mxfp4-expert
+        target (ops.Mxfp4Experts) as the fp8 one; the shared pass over 2..4 tiles and the prefill read its bf16 copy."""
         pair = self.H <= 2048 and self.moe_pair_kernel
+        if "gu_e4" in lw and self.expert_stream:   # an mxfp4-expert target: the 4-bit codes, gate/up where the pair kernel runs
+            return (lw["gu_e4"] if pair else lw["gu_e"]), lw["down_e4"]
         if "gu_e8" not in lw or not self.expert_stream:
             return (lw["gu_e13"] if (pair and "gu_e13" in lw) else lw["gu_e"]), lw["down_e"]
         return (lw["gu_e8"] if pair else lw["gu_e"]), lw["down_e8"]

@@ -120,13 +120,14 @@ typedef struct dfl_rows {
  *     the formula above), the base repeated per (chunk, wave), the patch word's k-step field 0..3.
  * The packer is dflash_amd.ops.pack_weight_bf16x13 (tensor ops over the packed bf16 weight, once at load).
  * ---- DFL_W_MXFP4: OCP Microscaling MXFP4, weight-only (W4A16) ----
- * Taken by dfl_gemm_resid (any K % 128 == 0, the K-chunked form included), dfl_gemm_silu_mul and dfl_gemm_argmax ONLY;
- * every other entry point refuses it as an unknown format.  An element is an e2m1 code (bit 3 sign, bits 2:0 the magnitudes
+ * Taken by dfl_gemm_resid (any K % 128 == 0, the K-chunked form included), dfl_gemm_silu_mul and dfl_gemm_argmax, and — with
+ * the scales as an array of their own, see the two entry points — by dfl_moe_gate_up and dfl_moe_down; every other entry
+ * point refuses it as an unknown format.  An element is an e2m1 code (bit 3 sign, bits 2:0 the magnitudes
  * 0, .5, 1, 1.5, 2, 3, 4, 6) and every 32 consecutive k of a row share one e8m0 scale code s: the weight is e2m1 * 2^(s - 127).
  * The kernels convert code pairs to bf16 with the block scale applied in the conversion (exact), run the same bf16 MFMA
  * on the same bf16 activations and have no epilogue multiply: Linear output = bf16(sum_k x[m][k] * w[n][k]), every rounding
  * point where the bf16 form has it.  One MFMA k-step of one column is 32 consecutive k: a k-step fragment is one MX block.
- * wp points at ONE buffer of N * K / 2 + N * K / 32 bytes (scale must be NULL): the codes, then the scales.
+ * Dense entry points: wp points at ONE buffer of N * K / 2 + N * K / 32 bytes (scale must be NULL): the codes, then the scales.
  *   codes  [N/16][K/128][64 lanes][16 B]: lane l is column 16 t + (l & 15), kq = l >> 4; dword d (0..3) of the lane's 16-byte
  *     word holds k-step 4 j + d: its 8 codes are those of k = 128 j + 32 d + 8 kq .. + 7, two per byte in k order, the LOW
  *     nibble first.
@@ -141,7 +142,8 @@ typedef struct dfl_rows {
 enum { DFL_W_BF16 = 0, DFL_W_E4M3 = 1, DFL_W_BF16X13 = 2, DFL_W_MXFP4 = 3 };
 typedef struct dfl_weight {
   const void *wp;      /* packed weight: dfl_pack_weight[_gateup] (bf16) or dfl_pack_weight[_gateup]_fp8 (codes) */
-  const float *scale;  /* DFL_W_E4M3: fp32 scale per packed row, in packed tile order; DFL_W_BF16: must be NULL */
+  const float *scale;  /* DFL_W_E4M3: fp32 scale per packed row, in packed tile order; DFL_W_BF16: must be NULL; DFL_W_MXFP4
+                        * through dfl_moe_gate_up / dfl_moe_down: the experts' e8m0 scale array, reinterpreted (else NULL) */
   int32_t format;
 } dfl_weight;
 
@@ -454,7 +456,16 @@ int dfl_gemm_silu_mul_experts(const void *wp_gateup, int64_t wp_expert_stride, c
  * pack_weight_bf16x13 of the [E][2*I*K] tensor as it stands): the quads of all E * 2*I / 16 tiles, expert after expert
  * in dfl_pack_weight_gateup order, then the {base, patch} pairs of all tiles.  Wave w's four k-steps of a tile are quad
  * w of that tile, so an item streams one quad of the gate tile and one of the up tile and rebuilds the bf16 form's
- * fragments in registers: the same bits as the DFL_W_BF16 launch on the same weights, from 13/16 of the bytes. */
+ * fragments in registers: the same bits as the DFL_W_BF16 launch on the same weights, from 13/16 of the bytes.
+ * DFL_W_MXFP4 (both launches): per expert the codes in the dense format's tile layout [tiles][K/128][64 lanes][16 B] — for
+ * dfl_moe_gate_up in dfl_pack_weight_gateup order (gate tile p, up tile p), N = 2 I, the experts back to back at I * K bytes;
+ * for dfl_moe_down (K = I) expert e at wp + e * wp_expert_stride BYTES of codes (>= N * I / 2, % 16 == 0).  The e8m0 scales are
+ * an array of their own, [E][tiles][K/128][16 columns] dwords (byte d = k-step 4 j + d: per tile the dense format's scale
+ * region), whose address travels in the descriptor's `scale` field, reinterpreted; it must be 64-byte aligned.  The same
+ * items as the bf16 launches — a wave's four k-steps of a tile are ONE 16-byte word — with the block scale applied in the
+ * conversion and no epilogue multiply: the bits of the DFL_W_BF16 launch on the dequantised weights.
+ * DFL_EINVAL by the entry point's name, nothing launched: scale NULL (the message names format 3) or not 64-byte aligned;
+ * K % 128 != 0 or K > 2048 (dfl_moe_gate_up); I % 128 != 0 or expert strides too short (dfl_moe_down). */
 int dfl_moe_gate_up(const dfl_weight *w_gateup, const void *x_frag, int E, int I, int K, void *act_frag, const int32_t *list,
                     const int32_t *n_active, const int32_t *dyn, int valid_word, void *stream);
 int dfl_moe_down(const dfl_weight *w_down, int64_t wp_expert_stride, const void *act_frag, int64_t act_expert_stride,

@@ -13,7 +13,7 @@ import torch
 out = os.path.join(ROOT, "gpurun_out", "dbg")
 os.makedirs(out, exist_ok=True)
 so = os.path.join(out, "libdbg_moe.so")
-src = [os.path.join(ROOT, "dflash_amd", "csrc", f) for f in ("moe.hip", "dfl_common.hip")]
+src = [os.path.join(ROOT, "dflash_amd", "csrc", f) for f in ("moe.hip", "moe_w4.hip", "dfl_common.hip")]   # (moe.hip dispatches its MXFP4 forms into moe_w4.hip)
 subprocess.run([_hipcc(), *FLAGS, "-shared", "-DDFL_MOE_STAMPS",
                 "-I", os.path.join(ROOT, "include"), "-o", so, *src], check=True)
 from dflash_amd import _lib, ops
