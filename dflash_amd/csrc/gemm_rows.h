@@ -354,6 +354,17 @@ __device__ __forceinline__ void build_x(const RowSrc &s, const int (&ks)[NF], co
 }
 
 // ---- host side ----
+// What every expert entry point (moe_w4.hip, moe_w4_shared.hip) asks of a DFL_W_MXFP4 descriptor before anything else: its e8m0 scale array, through `scale`
+inline bool w4_scales_ok(const char *who, const dfl_weight *w) {
+  if (!w->scale)
+    dfl_set_error("%s: format 3 (DFL_W_MXFP4) experts take their e8m0 scale array through `scale`: it is NULL", who);
+  else if (((uintptr_t)w->scale & 63) != 0)
+    dfl_set_error("%s: the DFL_W_MXFP4 scale array must be 64-byte aligned", who);
+  else
+    return true;
+  return false;
+}
+
 inline int pick_ksplit_min(int KS, int fr_max) { return (KS + 16 * fr_max - 1) / (16 * fr_max); }
 
 // Workgroups along x for `ngroups` tile groups when the K axis is cut `ksplit` ways: at

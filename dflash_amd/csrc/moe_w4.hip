@@ -216,17 +216,6 @@ __global__ __launch_bounds__(1024) void k_moe_down_w4(MoeDownArgs4 a) {
   }
 }
 
-// What both expert entry points ask of a DFL_W_MXFP4 descriptor before anything else: its e8m0 scale array, through `scale`
-inline bool w4_scales_ok(const char *who, const dfl_weight *w) {
-  if (!w->scale)
-    dfl_set_error("%s: format 3 (DFL_W_MXFP4) experts take their e8m0 scale array through `scale`: it is NULL", who);
-  else if (((uintptr_t)w->scale & 63) != 0)
-    dfl_set_error("%s: the DFL_W_MXFP4 scale array must be 64-byte aligned", who);
-  else
-    return true;
-  return false;
-}
-
 }  // namespace
 
 int dfl_moe_gate_up_w4(const char *who, const dfl_weight *w, const void *x_frag, int E, int I, int K, void *act_frag,

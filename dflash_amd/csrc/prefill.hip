@@ -1029,10 +1029,22 @@ extern "C" int dfl_prefill_moe_gemm_down(const void *wp_down_e, int64_t w_expert
                                   max_items, H, I, row_w, out32, rows_per_item, stream);
 }
 
+// The DFL_W_MXFP4 forms of the two dfl_weight entry points (moe_w4_shared.hip: kernels and argument structs of their own,
+// so every k_pgemm instantiation stays as it is)
+int dfl_moe_grouped_gate_up_w4(const char *who, const dfl_weight *w, int64_t w_expert_stride, const void *xg, const int32_t *items,
+                               const int32_t *n_items, int max_items, int I, int K, void *act_g, int rows_per_item,
+                               const int32_t *src_row, const void *zeros_1k, void *stream);
+int dfl_moe_grouped_down_w4(const char *who, const dfl_weight *w, int64_t w_expert_stride, const void *act_g, const int32_t *items,
+                            const int32_t *n_items, int max_items, int H, int I, const float *row_w, float *out32,
+                            int rows_per_item, void *stream);
+
 extern "C" int dfl_moe_grouped_gate_up(const dfl_weight *w_gateup_e, int64_t w_expert_stride, const void *xg,
                                        const int32_t *items, const int32_t *n_items, int max_items, int I, int K, void *act_g,
                                        int rows_per_item, const int32_t *src_row, const void *zeros_1k, void *stream) {
   const char *who = "dfl_moe_grouped_gate_up";
+  if (w_gateup_e && w_gateup_e->format == DFL_W_MXFP4)  // (weight_ok knows the two formats every entry point takes)
+    return dfl_moe_grouped_gate_up_w4(who, w_gateup_e, w_expert_stride, xg, items, n_items, max_items, I, K, act_g, rows_per_item,
+                                      src_row, zeros_1k, stream);
   if (!grouped_weight_ok(who, w_gateup_e)) return DFL_EINVAL;
   return w_gateup_e->format == DFL_W_BF16
              ? grouped_gate_up_impl<false>(who, w_gateup_e->wp, nullptr, w_expert_stride, xg, items, n_items, max_items, I, K,
@@ -1045,6 +1057,9 @@ extern "C" int dfl_moe_grouped_down(const dfl_weight *w_down_e, int64_t w_expert
                                     const int32_t *n_items, int max_items, int H, int I, const float *row_w, float *out32,
                                     int rows_per_item, void *stream) {
   const char *who = "dfl_moe_grouped_down";
+  if (w_down_e && w_down_e->format == DFL_W_MXFP4)
+    return dfl_moe_grouped_down_w4(who, w_down_e, w_expert_stride, act_g, items, n_items, max_items, H, I, row_w, out32,
+                                   rows_per_item, stream);
   if (!grouped_weight_ok(who, w_down_e)) return DFL_EINVAL;
   return w_down_e->format == DFL_W_BF16
              ? grouped_down_impl<false>(who, w_down_e->wp, nullptr, w_expert_stride, act_g, items, n_items, max_items, H, I,

@@ -405,7 +405,8 @@ def pack_weight_gateup_mxfp4(gate_codes: torch.Tensor, gate_scales: torch.Tensor
 
 class Mxfp4Experts(NamedTuple):
     """One MoE layer's expert weights of one kind as MXFP4 (pack_experts_mxfp4): expert e's packed codes in row e, the e8m0
-    scales an array of their own.  moe_gate_up (K <= 2048) / moe_down take one in place of the packed bf16 [E, .] tensor."""
+    scales an array of their own.  moe_gate_up (K <= 2048) / moe_down and moe_grouped_gate_up (any K) / moe_grouped_down take
+    one in place of the packed bf16 [E, .] tensor."""
     wp: torch.Tensor      # uint8 [E, N * K / 2]: per expert the code region of pack_weight_gateup_mxfp4 (N = 2I) / pack_weight_mxfp4
     sc: torch.Tensor      # uint8 [E, N * K / 32]: per expert that layout's scale region ([tiles][K/128][16 columns][4 B])
     E: int
@@ -2259,12 +2260,14 @@ def prefill_moe_route(rlog: torch.Tensor, P: int, sc: dict, norm_topk: bool = Tr
 
 def moe_grouped_gate_up(wp_gu, x_frag: torch.Tensor, sc: dict, K: int, *, gather: bool) -> None:
     """The grouped gate/up + SiLU launch over the work list in the scratch `sc` (prefill_moe_route): act_g <- silu(x Wg_e^T)
-    * (x Wu_e^T) per item.  wp_gu: packed bf16 [E, 2*I*K], or an Fp8Experts (dfl_moe_grouped_gate_up's e4m3 form: any K,
-    unlike moe_gate_up).  gather: x_frag holds the UNGATHERED row tiles and the gather happens in the kernel's addresses
-    (src_row); else x_frag is the gathered copy (sc["xg"])."""
+    * (x Wu_e^T) per item.  wp_gu: packed bf16 [E, 2*I*K], an Fp8Experts (dfl_moe_grouped_gate_up's e4m3 form: any K,
+    unlike moe_gate_up) or an Mxfp4Experts (the 4-bit kernel of csrc/moe_w4_shared.hip: K % 128 == 0, any K, I % 32 == 0;
+    the bits of the bf16 launch on the dequantised weights).  gather: x_frag holds the UNGATHERED row tiles and the gather
+    happens in the kernel's addresses (src_row); else x_frag is the gathered copy (sc["xg"])."""
     E, I = sc["E"], sc["I"]
     w, rows = _we(wp_gu, E, 2 * I, K, "wp_gu")
-    assert rows.shape == (E, 2 * I * K) and x_frag.is_cuda and x_frag.dtype == BF16
+    per = I * K if isinstance(wp_gu, Mxfp4Experts) else 2 * I * K    # (mxfp4: two codes per byte)
+    assert rows.shape == (E, per) and x_frag.is_cuda and x_frag.dtype == BF16
     check(lib().dfl_moe_grouped_gate_up(w, rows.stride(0), x_frag.data_ptr(), _p(sc["items"], I32, "items"),
                                         _p(sc["n_items"], I32, "n_items"), sc["max_items"], I, K, _p(sc["act_g"], BF16, "act_g"),
                                         sc["rows_per_item"], _p(sc["src_row"], I32, "src_row") if gather else None,
@@ -2274,10 +2277,11 @@ def moe_grouped_gate_up(wp_gu, x_frag: torch.Tensor, sc: dict, K: int, *, gather
 
 def moe_grouped_down(wp_down, sc: dict, N: int) -> None:
     """The grouped down projection over the same work list: out32[gathered row] <- row_w * (act_g Wd_e^T), fp32.
-    wp_down: packed bf16 [E, N*I], or an Fp8Experts."""
+    wp_down: packed bf16 [E, N*I], an Fp8Experts, or an Mxfp4Experts (I % 128 == 0, N % 16 == 0)."""
     E, I = sc["E"], sc["I"]
     w, rows = _we(wp_down, E, N, I, "wp_down")
-    assert rows.shape == (E, N * I) and sc["out32"].shape[1] == N
+    per = N * I // 2 if isinstance(wp_down, Mxfp4Experts) else N * I
+    assert rows.shape == (E, per) and sc["out32"].shape[1] == N
     check(lib().dfl_moe_grouped_down(w, rows.stride(0), _p(sc["act_g"], BF16, "act_g"), _p(sc["items"], I32, "items"),
                                      _p(sc["n_items"], I32, "n_items"), sc["max_items"], N, I, _p(sc["row_w"], F32, "row_w"),
                                      _p(sc["out32"], F32, "out32"), sc["rows_per_item"], _stream()),

@@ -116,8 +116,9 @@ class NativeTarget:
         consecutive k of a row; hidden and moe_intermediate sizes % 128 == 0) — both expert tensors of hf_model are
         overwritten with the dequantised values, lw["gu_e"] / lw["down_e"] stay their packed bf16 copy, and
         `self.experts4[i]` (ops.Mxfp4Experts; lw["gu_e4"] / lw["down_e4"]) holds the codes and block scales, which the
-        <= 16-row verify and the per-tile expert branch stream while `self.expert_stream` is True; the shared pass over
-        2..4 tiles, the prefill and gate/up at hidden > 2048 read the copy ("The experts").  What
+        <= 16-row verify, the per-tile expert branch and the shared pass over 2..4 tiles (ragged batch, engine, wide blocks,
+        candidate verifier) stream while `self.expert_stream` is True; the prefill, and the per-tile gate/up at hidden > 2048,
+        read the copy ("The experts" and "The shared pass").  What
         weight-only MXFP4 does to a real MoE checkpoint's routing and outputs is NOT measured.
         attn_impl: "head" = dfl_attn_head on finished bf16 q/k/v rows (round 2, default); "fused" = the
         round-1 stage (fp32 K-split partials -> dfl_attn_fused), kept for A/B measurement and as a second
@@ -723,7 +724,8 @@ class NativeTarget:
         gathered like prompt rows (dfl_prefill_moe_*, csrc/prefill.hip), so that an expert several tiles picked is
         streamed once (four tiles of 16 rows x top-8 touch nearly all of 128 experts: one pass over them instead of four
         over ~80 each).  Same rounding points as the per-tile kernels; the rows' fp32 sums land as ONE share in `part`.
-        An fp8-expert target streams the codes here too while expert_stream is set (ops.moe_grouped_gate_up / _down).
+        An fp8- or mxfp4-expert target streams the codes here too while expert_stream is set (ops.moe_grouped_gate_up /
+        _down; mxfp4: the kernels of csrc/moe_w4_shared.hip).
         Rows beyond a tile's valid count are routed too (zero fragments) and ignored by the norm launch that follows."""
         H, P = self.H, R * 16
         if self._moe_sh is None:
@@ -736,11 +738,11 @@ class NativeTarget:
         ops.gemm_resid_batch(lw["router_p"], ops.brows_frag(xn), R, sh["rlog"].shape[2], H, sh["rlog"], add_residual=False,
                              ws=sh["gws"], dyn=dyn)
         ops.prefill_moe_route(sh["rlog"].view(64, -1), P, sc, self.norm_topk)
-        # fp8 experts: both grouped launches stream the codes (the grouped form has no K <= 2048 limit, so gate/up too at
-        # any hidden width); else, or with expert_stream off, the packed bf16 copy
-        e8 = "gu_e8" in lw and self.expert_stream
-        ops.moe_grouped_gate_up(lw["gu_e8"] if e8 else lw["gu_e"], xn, sc, H, gather=True)
-        ops.moe_grouped_down(lw["down_e8"] if e8 else lw["down_e"], sc, H)
+        # fp8 / mxfp4 experts: both grouped launches stream the codes (the grouped forms have no K <= 2048 limit, so gate/up
+        # too at any hidden width); else, or with expert_stream off, the packed bf16 copy
+        fmt = next((f for f in ("8", "4") if "gu_e" + f in lw and self.expert_stream), "")
+        ops.moe_grouped_gate_up(lw["gu_e" + fmt], xn, sc, H, gather=True)
+        ops.moe_grouped_down(lw["down_e" + fmt], sc, H)
         ops.check(L.dfl_prefill_moe_combine(sc["out32"].data_ptr(), sc["posmap"].data_ptr(), P, H, self.top_k, None, 0, None, 0,
                                             part.data_ptr(), st), "dfl_prefill_moe_combine")
         return 1

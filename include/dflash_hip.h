@@ -840,7 +840,17 @@ int dfl_prefill_moe_combine(const float *out32, const int32_t *posmap, int P, in
  * power-of-two scales bit-equal to the bf16 launch on q * scale.
  * w_expert_stride: elements of the weight's format between experts; it must be N * K.  N % 128 == 0, K % 64 == 0,
  * rows_per_item 64 or 128, src_row and zeros_1k together or neither; DFL_EINVAL, nothing launched, on any of these, on
- * the descriptor errors of dfl_weight and on scales that are not 64-byte aligned. */
+ * the descriptor errors of dfl_weight and on scales that are not 64-byte aligned.
+ * DFL_W_MXFP4 (kernels of their own, csrc/moe_w4_shared.hip; DESIGN.md section 17, "The shared pass"): exactly
+ * dfl_moe_gate_up's / dfl_moe_down's operand — expert e's codes [tiles][K/128][64 lanes][16 B] at wp + e * w_expert_stride
+ * BYTES (gate/up tiles interleaved), w_expert_stride == N * K / 2; the e8m0 scales through `scale` as
+ * [E][tiles][K/128][16 columns] dwords, 64-byte aligned.  Waves own two adjacent column tiles and walk K, the codes go
+ * HBM -> registers -> MFMA with the block scale in the conversion, the item's <= 4 row tiles stream through an LDS ring;
+ * the same k-steps in the same order into every accumulator and no scale multiply: the bits of the DFL_W_BF16 launch on
+ * the dequantised weights.  An item of 5..8 tiles (rows_per_item 128) takes two passes.  K % 128 == 0 (gate/up; no upper
+ * limit), I % 32 == 0 (gate/up) / I % 128 == 0 (down), N % 16 == 0; x_frag / act_g within 2 GiB of their base; zeros_1k is
+ * required with src_row but not read (padding rows are clipped reads).  Refused first: scale == NULL, then a misaligned
+ * scale array, then the shapes, the stride, rows_per_item, null pointers, src_row without zeros_1k or the reverse. */
 int dfl_moe_grouped_gate_up(const dfl_weight *w_gateup_e, int64_t w_expert_stride, const void *xg, const int32_t *items,
                             const int32_t *n_items, int max_items, int I, int K, void *act_g, int rows_per_item,
                             const int32_t *src_row, const void *zeros_1k, void *stream);
