@@ -247,8 +247,12 @@ class BatchedDecoder:
             self.events.setdefault(key, [None, None])[which] = e
 
     def _lm8(self):
-        """The e4m3 lm_head of the greedy draft head, or None where the draft does not stream its codes; packed on first
-        use (0.6 GB at 8B shapes: not for a model that never reads it)."""
+        """The e4m3 (an mxfp4 draft: the 4-bit) lm_head of the greedy draft head, or None where the draft does not stream
+        its codes; packed on first use (0.6 / 0.33 GB at 8B shapes: not for a model that never reads it)."""
+        if self.model.streams_mxfp4_tiles():
+            if self.lm_wp8 is None:
+                self.lm_wp8 = self.model.packed_lm_head_mxfp4(self.target.lm_head)
+            return self.lm_wp8
         if not self.model.streams_fp8_tiles():
             return None
         if self.lm_wp8 is None:   # (an fp8 target's own codes where it has them: one e4m3 copy serves both)
@@ -538,9 +542,10 @@ class BatchedDecoder:
                              dyn=dyn_d)
         ops.norm_frag_batch(d["ctxh"], R, m.w["hidden_norm"], eps, st.xn, dyn_d, ops.DYN_TAU)
         # an fp8 draft: the context K/V weights and the layers' gate/up, o, down — and q/k/v where
-        # it leaves K parts — stream their e4m3 codes; fc (a plain-row source) reads the dequantised copy
-        fp8 = m.streams_fp8_tiles()
-        ops.gemm_f32_batch(m.w8["kv_all"] if fp8 else self.kv_all, st.src["xn"], R, self.nkv_all, H, d["part_kv"], dyn_d)
+        # it leaves K parts — stream their e4m3 codes; fc (a plain-row source) reads the dequantised copy.  An mxfp4 draft
+        # (section 17, "The batch forms"): the same launches on its 4-bit twins, the K-part ones per matrix where their K fits
+        kv_twin = m.kv_all_tiles()
+        ops.gemm_f32_batch(self.kv_all if kv_twin is None else kv_twin, st.src["xn"], R, self.nkv_all, H, d["part_kv"], dyn_d)
         ops.kv_append_batch(kv=d["part_kv"], nsplit=ops.batch_ksplit(H), split_stride=MT * 16 * self.nkv_all,
                             ld=self.nkv_all, k_col=0, v_col=c.kv_dim, col_layer_stride=2 * c.kv_dim,
                             n_layers=c.num_hidden_layers, R=R, n_kv=c.num_key_value_heads, k_norm_w=self.k_norm_all,

@@ -637,6 +637,16 @@ bool fp8_ring_ok(const char *who, const dfl_rows_batch *x, int K) {
 
 }  // namespace
 
+// The DFL_W_MXFP4 forms of the three dfl_weight entry points below (gemm_batch_w4.hip: kernels and argument structs of
+// their own; DESIGN.md section 17, "The batch forms").  The argmax one launches its ring only: the finish is the one here.
+int dfl_gemm_f32_batch_w4(const char *who, const dfl_weight *w, const dfl_rows_batch *x, int R, int N, int K, float *out,
+                          const int32_t *dyn, void *stream);
+int dfl_gemm_silu_mul_batch_w4(const char *who, const dfl_weight *w, const dfl_rows_batch *x, int R, int I, int K, void *act_frag,
+                               int64_t act_stride, const int32_t *dyn, void *stream);
+int dfl_gemm_argmax_batch_w4(const char *who, const dfl_weight *w, const dfl_rows_batch *x, int R, int V, int K, int row0, int nrows,
+                             const int32_t *dyn, int nrows_dyn_word, float *best_val, int *best_idx, void *logits,
+                             int64_t logits_stride, int *ncand, void *stream);
+
 extern "C" int dfl_batch_ksplit(int K) { return batch_ksplit(K); }
 extern "C" int dfl_batch_tiles(int R) { return mt_of(R); }
 
@@ -648,6 +658,8 @@ extern "C" int dfl_gemm_f32_batch(const dfl_weight *w, const dfl_rows_batch *x, 
                                   const int32_t *dyn, void *stream) {
   const char *who = "dfl_gemm_f32_batch";
   GemmBArgs a{};
+  if (w && w->format == DFL_W_MXFP4)  // (weight_ok knows the two formats every entry point takes)
+    return dfl_gemm_f32_batch_w4(who, w, x, R, N, K, out, dyn, stream);
   if (!weight_ok(who, w)) return DFL_EINVAL;
   const bool w8 = w->format == DFL_W_E4M3;
   DFL_REQUIRE(out, "%s: null pointer", who);
@@ -679,6 +691,8 @@ extern "C" int dfl_gemm_silu_mul_batch(const dfl_weight *w_gateup, const dfl_row
                                        void *stream) {
   const char *who = "dfl_gemm_silu_mul_batch";
   GemmBArgs a{};
+  if (w_gateup && w_gateup->format == DFL_W_MXFP4)  // (the ring form only, no workspace)
+    return dfl_gemm_silu_mul_batch_w4(who, w_gateup, x, R, I, K, act_frag, act_stride, dyn, stream);
   if (!weight_ok(who, w_gateup)) return DFL_EINVAL;
   const bool w8 = w_gateup->format == DFL_W_E4M3;
   DFL_REQUIRE(act_frag && (w8 || ws), "%s: null pointer", who);  // (ws is the slab form's: the e4m3 ring takes none)
@@ -774,6 +788,19 @@ extern "C" int dfl_gemm_argmax_batch(const dfl_weight *w, const dfl_rows_batch *
                                      void *stream) {
   const char *who = "dfl_gemm_argmax_batch";
   GemmBArgs a{};
+  if (w && w->format == DFL_W_MXFP4) {  // the 4-bit ring, then the finish below over its one candidate per workgroup
+    const bool have = ws && out_ids;  // (refused there, behind the descriptor's own checks: the NULL scale comes first)
+    float *bv = have ? (float *)((char *)ws + WS_TICKETS) : nullptr;
+    int *bi = have ? (int *)((char *)ws + WS_TICKETS + WS_CAND * sizeof(float)) : nullptr;
+    int ncand = 0;
+    const int rc = dfl_gemm_argmax_batch_w4(who, w, x, R, V, K, row0, nrows, dyn, nrows_dyn_word, bv, bi, logits, logits_stride,
+                                            &ncand, stream);
+    if (rc != DFL_OK) return rc;
+    hipLaunchKernelGGL(k_argmax_finish_b, dim3(16, R), dim3(64), 0, (hipStream_t)stream, bv, bi, ncand, mt_of(R), row0, nrows, dyn,
+                       nrows_dyn_word, out_ids, out_stride, out_off);
+    DFL_CHECK_LAUNCH(who);
+    return DFL_OK;
+  }
   if (!weight_ok(who, w)) return DFL_EINVAL;
   const bool w8 = w->format == DFL_W_E4M3;
   DFL_REQUIRE(ws && out_ids, "%s: null pointer", who);

@@ -1046,8 +1046,8 @@ def _draft_ids(model, hid_frag, lm_wp, bs, blk, draft_temperature, keep_logits=N
     if draft_temperature < 1e-5:
         from .model import WideRows
         wide = isinstance(hid_frag, WideRows)   # (both tiles in one ragged-batch lm_head pass)
-        # (an mxfp4 draft's 4-bit head: the single 16-row tile only — streams_fp8_tiles() is False for it)
-        wp = lm_wp8 if lm_wp8 is not None and (model.streams_fp8_tiles() if wide else bs <= 16) else lm_wp
+        tiles = model.streams_fp8_tiles() or model.streams_mxfp4_tiles()
+        wp = lm_wp8 if lm_wp8 is not None and (tiles if wide else bs <= 16) else lm_wp
         model.draft_tokens(hid_frag, wp, bs, blk[0], logits=keep_logits)
         return
     if seed is not None:

@@ -93,9 +93,12 @@ class DFlashDraftModel:
         acceptance length of a trained checkpoint is NOT measured — hence off by default.
         "mxfp4": every Linear weight of the draft is quantised at load time to OCP MXFP4 — e2m1 codes with one e8m0 scale
         per 32 consecutive k of a row (ops.quantize_mxfp4_rows).  ONE quantised model again:
-        `self.w` holds the dequantised values (exact in bf16), `self.w4` the packed 4-bit twins, which a single
-        request's block of <= 16 rows streams at 4.25 bits per weight (streams_mxfp4); a sampled draft's lm_head, the
-        ragged batch and the engine, wider blocks, prefill and attn_impl="fused" compute the same model from self.w.  stream_format is ignored (the 13-bit twins are for bf16 weights).  The draft only proposes: committed
+        `self.w` holds the dequantised values (exact in bf16), `self.w4` the packed 4-bit twins, streamed at 4.25 bits
+        per weight by a single request's block of <= 16 rows (streams_mxfp4) and by the tile-stack paths — the ragged
+        batch, the engine, a 17..32-row block (streams_mxfp4_tiles: gate/up and the greedy lm_head always; o_proj,
+        down_proj, q/k/v as parts and the context K/V where ops.mxfp4_parts_ok takes the matrix's K, bit for bit the bf16
+        launches on self.w); a sampled or coupled draft head, fc, prefill, the candidate loop, hidden > 4096 and
+        attn_impl="fused" compute the same model from self.w.  stream_format is ignored (the 13-bit twins are for bf16 weights).  The draft only proposes: committed
         tokens stay the target's own, but the effect of a 4-bit draft on the acceptance length of a trained checkpoint is
         NOT measured — hence off by default."""
         if weight_format not in WEIGHT_FORMATS:
@@ -136,7 +139,7 @@ class DFlashDraftModel:
         self._lm_head_cache = {}
         self._lm_head_cache8 = {}
         self._lm_head_cache4 = {}
-        self._tile_layers = {}   # tile_layers(): qkv_parts -> layer dicts with the e4m3 twins
+        self._tile_layers = {}   # tile_layers(): qkv_parts -> layer dicts with the e4m3 / 4-bit twins
         self._row_layers = {}    # row_layers(): streams e4m3 -> layer dicts with the e4m3 / 13-bit twins
         self._rope = None
         # "head": dfl_attn_head on finished bf16 q/k/v rows (round 2); "fused": round-1 stage on fp32 partials
@@ -335,8 +338,9 @@ class DFlashDraftModel:
         return self._lm_head_cache8[key]
 
     def packed_lm_head_mxfp4(self, lm_head) -> ops.Mxfp4Weight:
-        """The target's lm_head weight quantised to MXFP4 and packed for streaming (the DRAFT's greedy unmask of <= 16
-        rows only: the target keeps its bf16 copy); cached per weight tensor as packed_lm_head."""
+        """The target's lm_head weight quantised to MXFP4 and packed for streaming (the DRAFT's greedy unmask only — one
+        request's block, the ragged batch, the engine: the target keeps its bf16 copy); cached per weight tensor as
+        packed_lm_head."""
         wt = lm_head.weight if hasattr(lm_head, "weight") else lm_head
         key = (wt.data_ptr(), tuple(wt.shape), wt._version)
         if key not in self._lm_head_cache4:
@@ -365,12 +369,32 @@ class DFlashDraftModel:
         K parts; fc, q/k/v as finished rows and a sampled lm_head read self.w."""
         return self.w8 is not None and self.fp8_stream and self.attn_impl == "head"
 
+    def streams_mxfp4_tiles(self) -> bool:
+        """Whether the tile-stack paths (streams_fp8_tiles) stream the 4-bit twins: an mxfp4 model, mxfp4_stream, the
+        head attention stage, no wide hidden.  There gate/up and the greedy lm_head take the codes, and o_proj,
+        down_proj, q/k/v as parts and the context K/V where ops.mxfp4_parts_ok holds for the matrix's K; everything else
+        reads self.w ("The batch forms")."""
+        return (getattr(self, "w4", None) is not None and self.mxfp4_stream and self.attn_impl == "head"
+                and not self.wide_hidden)
+
     def tile_layers(self, qkv_parts: bool) -> list:
         """The layer dicts TileStack.run takes: self.w's, with gu / o / down — and qkv, where the caller runs
-        qkv="parts" — replaced by their e4m3 twins when streams_fp8_tiles()."""
-        if not self.streams_fp8_tiles():
-            return self.w["layers"]
-        return ops.tile_layers(self.w["layers"], self.w8["layers"], qkv_parts, self._tile_layers)
+        qkv="parts" — replaced by their e4m3 twins when streams_fp8_tiles(), by their 4-bit twins when
+        streams_mxfp4_tiles() (o / down / qkv per matrix: ops.tile_layers)."""
+        if self.streams_fp8_tiles():
+            return ops.tile_layers(self.w["layers"], self.w8["layers"], qkv_parts, self._tile_layers)
+        if self.streams_mxfp4_tiles():
+            return ops.tile_layers(self.w["layers"], self.w4["layers"], qkv_parts, self._tile_layers)
+        return self.w["layers"]
+
+    def kv_all_tiles(self):
+        """The context K/V matrix of all layers for the tile-stack paths' gemm_f32_batch: the e4m3 or (where the launch takes
+        K = hidden) the 4-bit twin when the model streams, else None — the caller's bf16 copy."""
+        if self.streams_fp8_tiles():
+            return self.w8["kv_all"]
+        if self.streams_mxfp4_tiles() and ops.mxfp4_parts_ok(self.config.hidden_size):
+            return self.w4["kv_all"]
+        return None
 
     def row_layers(self, bs: int) -> list:
         """The layer dicts RowStack.run takes for a block of `bs` rows: self.w's, with the four matrices replaced by
@@ -614,8 +638,8 @@ class DFlashDraftModel:
                      sample: Optional[dict] = None) -> None:
         """block_ids[1:bs] <- argmax(lm_head(hidden[1:bs])) (model/dflash.py:238,245,247).
         hid_frag: what draft_block returned (one row source per 16-row tile; a single source = one tile).
-        lm_head_wp: the packed bf16 lm_head, or (greedy only: sample is None) an ops.Fp8Weight of it or (greedy, <= 16
-        rows) an ops.Mxfp4Weight.  A bf16 head's
+        lm_head_wp: the packed bf16 lm_head, or (greedy only: sample is None) an ops.Fp8Weight or an ops.Mxfp4Weight
+        of it.  A bf16 head's
         single-tile argmax launch streams its 13-bit twin where stream_format="auto" has one (shared with the target).
         logits (bf16 [16 * tiles, V]) / margins (fp32 [>= bs]): margins[j] <- top-1 minus top-2 draft
         logit of block slot j >= 1, the reference's per-position confidence

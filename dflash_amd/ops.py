@@ -182,11 +182,16 @@ def pack_layer_fp8(l8: dict) -> dict:
 
 
 def tile_layers(layers: list, layers8: list, qkv_parts: bool, cache: dict) -> list:
-    """The layer dicts TileStack.run takes where it streams e4m3 codes: `layers` with gu / o / down — and qkv, where the
-    caller runs qkv="parts" — replaced by their twins in layers8.  Built once per form and kept in `cache`."""
+    """The layer dicts TileStack.run takes where it streams e4m3 or 4-bit codes: `layers` with gu / o / down — and qkv,
+    where the caller runs qkv="parts" — replaced by their twins in layers8.  An Mxfp4Weight twin of o / down / qkv only
+    where the K-part launch takes its K (mxfp4_parts_ok), else that matrix stays the bf16 copy; gu always (the ring
+    form).  Built once per form and kept in `cache`."""
     if qkv_parts not in cache:
         keys = ("gu", "o", "down") + (("qkv",) if qkv_parts else ())
-        cache[qkv_parts] = [{**lw, **{k: l8[k] for k in keys}} for lw, l8 in zip(layers, layers8)]
+
+        def takes(k, t):
+            return k == "gu" or not isinstance(t, Mxfp4Weight) or mxfp4_parts_ok(t.K)
+        cache[qkv_parts] = [{**lw, **{k: l8[k] for k in keys if takes(k, l8[k])}} for lw, l8 in zip(layers, layers8)]
     return cache[qkv_parts]
 
 
@@ -329,7 +334,8 @@ MX_EXP_MIN, MX_EXP_MAX = -120, 120     # scale codes 7..247 (code = exponent + 1
 
 class Mxfp4Weight(NamedTuple):
     """A packed MXFP4 weight (pack_weight_mxfp4 / pack_weight_gateup_mxfp4): gemm_resid / gemm_silu_mul / gemm_argmax
-    take one in place of a packed bf16 weight (K % 128 == 0)."""
+    take one in place of a packed bf16 weight (K % 128 == 0), and so do the ragged batch's gemm_silu_mul_batch /
+    gemm_argmax_batch (K >= 256, frag16 sources) and gemm_f32_batch (mxfp4_parts_ok(K))."""
     data: torch.Tensor    # uint8: codes [N/16][K/128][64 lanes][16 B], then e8m0 scales [N/16][K/128][16 columns][4 B]
     N: int
     K: int
@@ -451,6 +457,17 @@ def pack_layer_mxfp4(l4: dict) -> dict:
             "down": pack_weight_mxfp4(*l4["down"])}
 
 
+def mxfp4_parts_ok(K: int) -> bool:
+    """Whether gemm_f32_batch takes an Mxfp4Weight of this K: the bf16 launch's share per wave, ceil(K / 32 / (8 * K
+    parts)) k-steps with ceil(K / 2048) K parts, is a whole number of 4-k-step words — the 4-bit launch then gives every
+    wave the k-steps of the bf16 one (K = 1024 and every multiple of 2048; not 512, 2560, 3072, 5120)."""
+    if K <= 0 or K % 128:
+        return False
+    ks = K // 32
+    parts = (ks + 63) // 64
+    return parts <= 16 and -(-ks // (8 * parts)) % 4 == 0
+
+
 def check_stream_format(stream_format: str) -> bool:
     """True for "auto" (the 13-bit twins where they apply), False for "bf16"."""
     if stream_format not in STREAM_FORMATS:
@@ -458,9 +475,10 @@ def check_stream_format(stream_format: str) -> bool:
     return stream_format == "auto"
 
 
-def _w(wp, N: int, K: int, name: str) -> Weight:
+def _w(wp, N: int, K: int, name: str, batch: bool = False) -> Weight:
     """The dfl_weight of a launch: a packed bf16 tensor, or an Fp8Weight / a Bf16x13Weight / an Mxfp4Weight of the launch's
-    N x K (the C side refuses a format the entry point does not take).  Read
+    N x K (the C side refuses a format the entry point does not take).  batch (the ragged-batch GEMMs): an Mxfp4Weight's
+    scale region — behind the N * K / 2 bytes of codes — goes through `scale`, as the expert forms' array does.  Read
     on the host during the call only; the caller's references keep the tensors alive."""
     if isinstance(wp, Bf16x13Weight):
         if (wp.N, wp.K) != (N, K):
@@ -469,7 +487,8 @@ def _w(wp, N: int, K: int, name: str) -> Weight:
     if isinstance(wp, Mxfp4Weight):
         if (wp.N, wp.K) != (N, K):
             raise ValueError(f"dflash_amd: {name} is an mxfp4 weight of {wp.N} x {wp.K}, the launch asks for {N} x {K}")
-        return Weight(_p(wp.data, U8, name), None, W_MXFP4)
+        base = _p(wp.data, U8, name)
+        return Weight(base, base + N * K // 2 if batch else None, W_MXFP4)
     if not isinstance(wp, Fp8Weight):
         return Weight(_p(wp, BF16, name), None, W_BF16)
     if (wp.N, wp.K) != (N, K):
@@ -1972,15 +1991,17 @@ def gemm_batch_ws(N: int, K: int, device) -> torch.Tensor:
 
 def gemm_f32_batch(wp, x: BatchRowSource, R: int, N: int, K: int, out: torch.Tensor, dyn) -> None:
     assert out.numel() >= batch_ksplit(K) * batch_tiles(R) * 16 * N
-    # (an Fp8Weight: every K part comes out scaled, the launch that sums them takes it as it is)
-    check(lib().dfl_gemm_f32_batch(_w(wp, N, K, "wp"), x.ref, R, N, K, _p(out, F32, "out"), _p(dyn, I32, "dyn"),
+    # (an Fp8Weight: every K part comes out scaled, the launch that sums them takes it as it is; an Mxfp4Weight:
+    # where mxfp4_parts_ok(K), the bits of the bf16 launch on the dequantised weights)
+    check(lib().dfl_gemm_f32_batch(_w(wp, N, K, "wp", batch=True), x.ref, R, N, K, _p(out, F32, "out"), _p(dyn, I32, "dyn"),
                                    _stream()), "dfl_gemm_f32_batch")
 
 
 def gemm_silu_mul_batch(wp_gu, x: BatchRowSource, R: int, I: int, K: int, act: torch.Tensor, ws, dyn) -> None:
     assert act.dim() == 2 and act.shape[1] >= 16 * I and act.shape[0] >= batch_tiles(R)
-    # (an Fp8Weight runs the ring form only, here and in the two below: a plain-row source is an error, not a fall-back)
-    check(lib().dfl_gemm_silu_mul_batch(_w(wp_gu, 2 * I, K, "wp_gu"), x.ref, R, I, K, _p(act, BF16, "act"), act.stride(0),
+    # (an Fp8Weight or an Mxfp4Weight runs the ring form only, here and in gemm_argmax_batch: a plain-row source is an
+    # error, not a fall-back; gemm_sample_batch refuses an Mxfp4Weight)
+    check(lib().dfl_gemm_silu_mul_batch(_w(wp_gu, 2 * I, K, "wp_gu", batch=True), x.ref, R, I, K, _p(act, BF16, "act"), act.stride(0),
                                         _p(ws), _p(dyn, I32, "dyn"), _stream()), "dfl_gemm_silu_mul_batch")
 
 
@@ -2010,7 +2031,7 @@ def gemm_argmax_batch(wp, x: BatchRowSource, R: int, V: int, K: int, row0: int, 
     if logits is not None:
         assert logits.dim() == 3 and logits.shape[1] == 16 and logits.shape[2] == V and logits.is_contiguous()
         lp, lst = _p(logits, BF16, "logits"), logits.stride(0)
-    check(lib().dfl_gemm_argmax_batch(_w(wp, V, K, "wp"), x.ref, R, V, K, row0, nrows, _p(dyn, I32, "dyn"),
+    check(lib().dfl_gemm_argmax_batch(_w(wp, V, K, "wp", batch=True), x.ref, R, V, K, row0, nrows, _p(dyn, I32, "dyn"),
                                       nrows_dyn_word, _p(ws), out_ids.data_ptr(), out_ids.stride(0), out_off, lp, lst,
                                       _stream()), "dfl_gemm_argmax_batch")
 

@@ -121,7 +121,8 @@ typedef struct dfl_rows {
  * The packer is dflash_amd.ops.pack_weight_bf16x13 (tensor ops over the packed bf16 weight, once at load).
  * ---- DFL_W_MXFP4: OCP Microscaling MXFP4, weight-only (W4A16) ----
  * Taken by dfl_gemm_resid (any K % 128 == 0, the K-chunked form included), dfl_gemm_silu_mul and dfl_gemm_argmax, and — with
- * the scales as an array of their own, see the two entry points — by dfl_moe_gate_up and dfl_moe_down; every other entry
+ * the scales as an array of their own, see the two entry points — by dfl_moe_gate_up and dfl_moe_down, and with the scale
+ * region through `scale` by dfl_gemm_f32_batch, dfl_gemm_silu_mul_batch and dfl_gemm_argmax_batch; every other entry
  * point refuses it as an unknown format.  An element is an e2m1 code (bit 3 sign, bits 2:0 the magnitudes
  * 0, .5, 1, 1.5, 2, 3, 4, 6) and every 32 consecutive k of a row share one e8m0 scale code s: the weight is e2m1 * 2^(s - 127).
  * The kernels convert code pairs to bf16 with the block scale applied in the conversion (exact), run the same bf16 MFMA
@@ -894,6 +895,20 @@ int64_t dfl_gemm_batch_ws_bytes(int N, int K);
  * output (the launch that sums the parts is untouched).  dfl_gemm_silu_mul_batch, dfl_gemm_argmax_batch and
  * dfl_gemm_sample_batch run e4m3 in the ring form only: -22 for a source that is not frag16 (mode 0), never a quiet
  * fall-back to the slab form or to the bf16 kernels. */
+/* DFL_W_MXFP4 in dfl_gemm_f32_batch, dfl_gemm_silu_mul_batch and dfl_gemm_argmax_batch (kernels of their own,
+ * csrc/gemm_batch_w4.hip; DESIGN.md section 17, "The batch forms"): argument for argument the bf16 contract, and bit for bit
+ * the bf16 launch's output on the dequantised weights — every accumulator receives the k-steps its bf16 counterpart receives,
+ * in order, and every cross-wave sum runs in the bf16 form's order.  wp: the codes of the dense layout above (gate/up tile
+ * order for dfl_gemm_silu_mul_batch); `scale`: that layout's e8m0 region, 64-byte aligned — for the dense blob wp + N * K / 2
+ * (the single-request entry points take the blob with scale NULL; here, as in the expert forms, it is passed).  Refused with
+ * -22 by the entry point's name, nothing launched, in this order: a NULL scale ("format 3 ... it is NULL"); a misaligned one;
+ * a NULL weight or row source, R outside 1..4, N % 16 != 0, K % 128 != 0; then
+ *   dfl_gemm_silu_mul_batch, dfl_gemm_argmax_batch (ring form only, no slab fall-back; ws is not read by the former): a
+ *     source that is not frag16 (mode 0, frag_stride % 8 == 0), K < 256;
+ *   dfl_gemm_f32_batch: a K whose bf16 share per wave nfr = ceil(K / 32 / (8 * dfl_batch_ksplit(K))) is not a multiple of 4
+ *     (taken: K = 1024 and every multiple of 2048; not 512, 2560, 3072, 5120) — the share is never rounded up, which would
+ *     move k-steps between waves; mode 2 sources as in the bf16 form.
+ * dfl_gemm_sample_batch and dfl_gemm_resid_batch do not take the format. */
 /* dfl_gemm_f32 for R requests: out[c][r*16+m][n], c < dfl_batch_ksplit(K) partial sums
  * (out holds ksplit * dfl_batch_tiles(R) * 16 * N floats). */
 int dfl_gemm_f32_batch(const dfl_weight *w, const dfl_rows_batch *x, int R, int N, int K, float *out, const int32_t *dyn,
