@@ -250,8 +250,8 @@ class BatchedDecoder:
         """The e4m3 (an mxfp4 draft: the 4-bit) lm_head of the greedy draft head, or None where the draft does not stream
         its codes; packed on first use (0.6 / 0.33 GB at 8B shapes: not for a model that never reads it)."""
         if self.model.streams_mxfp4_tiles():
-            if self.lm_wp8 is None:
-                self.lm_wp8 = self.model.packed_lm_head_mxfp4(self.target.lm_head)
+            if self.lm_wp8 is None:   # (an mxfp4 target's own 4-bit head where it has one: one copy serves both)
+                self.lm_wp8 = getattr(self.target, "lm_wp4", None) or self.model.packed_lm_head_mxfp4(self.target.lm_head)
             return self.lm_wp8
         if not self.model.streams_fp8_tiles():
             return None
@@ -260,8 +260,14 @@ class BatchedDecoder:
         return self.lm_wp8
 
     def _t_head(self):
-        """The verify's lm_head: an fp8 target that streams takes its e4m3 codes, else the shared packed bf16 copy."""
-        return self.target.lm_wp8 if self.target.streams_fp8_tiles() else self.lm_wp
+        """The verify's lm_head: an fp8 target that streams takes its e4m3 codes; an mxfp4 target that streams its 4-bit
+        codes under the greedy ring argmax head (a decoder with any T > 0 launch keeps bf16: the sampled ring head has no
+        4-bit form); else the shared packed bf16 copy."""
+        t = self.target
+        if t.streams_fp8_tiles():
+            return t.lm_wp8
+        greedy = not self.request_temperature and self.temperature < 1e-5
+        return t.lm_wp4 if (greedy and t.streams_mxfp4_tiles()) else self.lm_wp
 
     # ------------------------------------------------------------------ admission
     def _admit_prefill(self, r: int, input_ids: torch.Tensor, temperature: float, seed: Optional[int], top_k=0,

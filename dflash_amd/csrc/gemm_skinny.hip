@@ -730,6 +730,16 @@ __global__ __launch_bounds__(1024) void k_gemm_s_w8(GEMM_HEAD_PARAMS, GemmArgs r
   gemm_body<1, false, EPI_SAMPLE, NORM, true>(with_head<false, NORM>(rest, GEMM_HEAD_NAMES), sa);
 }
 
+// ... and its W4 form (dfl_gemm_sample on MXFP4 codes; the dense target's and the draft's sampled lm_head): raw 16-byte
+// words of four k-steps, each item's e8m0 dwords requested in front of its words (item 0's in the prologue), the block
+// scale inside the fragment — so the perturbation lands on bf16(sum), the rounding point of k_gemm_s, with no epilogue
+// multiply.  Built without packed fp32 instructions (the normalised source's rstd * weight products are scalar multiplies).
+template <bool NORM>
+__attribute__((target("no-packed-fp32-ops"))) __global__ __launch_bounds__(1024) void k_gemm_s_w4(GEMM_HEAD_PARAMS, GemmArgs rest,
+                                                                                                   SampleArgs sa) {
+  gemm_body<1, false, EPI_SAMPLE, NORM, false, false, false, true>(with_head<false, NORM>(rest, GEMM_HEAD_NAMES), sa);
+}
+
 // the instantiation for this launch's row sources (a normalised source needs the NORM kernels)
 template <int MT, bool CHUNKED, int EPI, bool W8 = false>
 bool launch_gemm(GemmArgs &a, dim3 grid, hipStream_t stream) {
@@ -1160,6 +1170,11 @@ int gemm_argmax_impl(const char *who, const dfl_weight *w, const dfl_rows *x, in
         hipLaunchKernelGGL(k_gemm_s_w8<true>, dim3(gx, 1), dim3(1024), 0, (hipStream_t)stream, GEMM_HEAD_OF(h), a, *smp);
       else
         hipLaunchKernelGGL(k_gemm_s_w8<false>, dim3(gx, 1), dim3(1024), 0, (hipStream_t)stream, GEMM_HEAD_OF(h), a, *smp);
+    } else if (w4) {  // (K % 128, the scale region and its alignment are checked by now; nfr % 4 == 0: whole words per wave)
+      if (a.src[0].mode == 2)
+        hipLaunchKernelGGL(k_gemm_s_w4<true>, dim3(gx, 1), dim3(1024), 0, (hipStream_t)stream, GEMM_HEAD_OF(h), a, *smp);
+      else
+        hipLaunchKernelGGL(k_gemm_s_w4<false>, dim3(gx, 1), dim3(1024), 0, (hipStream_t)stream, GEMM_HEAD_OF(h), a, *smp);
     } else if (a.src[0].mode == 2)
       hipLaunchKernelGGL(k_gemm_s<true>, dim3(gx, 1), dim3(1024), 0, (hipStream_t)stream, GEMM_HEAD_OF(h), a, *smp);
     else
@@ -1195,7 +1210,13 @@ extern "C" int dfl_gemm_sample(const dfl_weight *w, const dfl_rows *x, int V, in
                                void *logits, float *margin_out, uint64_t seed, float inv_t, int rng_stream,
                                const int32_t *pos_dyn, int pos_word, int pos_base, int pos_add, void *stream) {
   const char *who = "dfl_gemm_sample";
-  if (!weight_ok(who, w)) return DFL_EINVAL;
+  if (w && w->format == DFL_W_MXFP4) {  // the batch forms' convention: `scale` is the blob's e8m0 region (wp + V * K / 2)
+    DFL_REQUIRE(w->scale, "%s: format 3 (DFL_W_MXFP4) takes its e8m0 scale region through `scale` here, as the batch forms do: it is NULL",
+                who);
+    DFL_REQUIRE(((uintptr_t)w->scale & 63) == 0, "%s: the DFL_W_MXFP4 scale region must be 64-byte aligned", who);
+  } else if (!weight_ok(who, w)) {
+    return DFL_EINVAL;
+  }
   DFL_REQUIRE(w->wp && (w->format == DFL_W_BF16 || w->scale) && ws && out_ids, "%s: null pointer", who);
   DFL_REQUIRE(inv_t > 0.f && inv_t <= 1e5f, "%s: inv_t=%g outside (0, 1e5]", who, (double)inv_t);
   DFL_REQUIRE(rng_stream == (int)DFL_RNG_TARGET || rng_stream == (int)DFL_RNG_DRAFT, "%s: unknown stream %d", who,

@@ -329,8 +329,11 @@ class DecodeSession:
             self.lm_wp8 = getattr(target, "lm_wp8", None) if self.native else None
             if self.lm_wp8 is None:
                 self.lm_wp8 = model.packed_lm_head_fp8(target.lm_head)
-        elif self.use_draft and getattr(model, "w4", None) is not None:   # an mxfp4 draft: its own 4-bit copy of the head
-            self.lm_wp8 = model.packed_lm_head_mxfp4(target.lm_head)
+        elif self.use_draft and getattr(model, "w4", None) is not None:
+            # an mxfp4 draft: the mxfp4 target's own 4-bit head where it has one (ONE copy serves both), else packed here
+            self.lm_wp8 = getattr(target, "lm_wp4", None) if self.native else None
+            if self.lm_wp8 is None:
+                self.lm_wp8 = model.packed_lm_head_mxfp4(target.lm_head)
         self.stop_t = torch.tensor(stop_token_ids, dtype=torch.long, device=dev) if stop_token_ids else None
         # the stop sequences' tables and hit record, slot 0 of a state of its own (None: off); written in prefill()
         self.sq = ops.stop_seq_state(1, dev) if self.stop_seqs else None
@@ -730,6 +733,7 @@ class DecodeSession:
                        (m._rope, t._rope, getattr(m, "ws", None), getattr(t, "ws", None), getattr(t, "_taps", None),
                         self.lm_wp, self.lm_wp8, self.embed_w, getattr(t, "lm_wp", None),
                         t.fp8_tensors() if self.native else (),    # (an fp8 target's codes and scale vectors)
+                        t.mxfp4_tensors() if self.native else (),  # (an mxfp4 target's code blobs)
                         self.stage,    # (the row processors' state and every buffer their launches read or write)
                         self.sq))      # (the stop sequences' tables and hit record)
 

@@ -75,7 +75,7 @@ class WideRows:
 
 WEIGHT_FORMATS = ("bf16", "fp8_e4m3", "mxfp4")
 EXPERT_FORMATS = ("bf16", "fp8_e4m3", "mxfp4")          # NativeTarget's expert_format: a sparse-MoE target's expert weights
-TARGET_WEIGHT_FORMATS = ("bf16", "fp8_e4m3")   # NativeTarget: the 4-bit format is the draft's alone (it only proposes)
+TARGET_WEIGHT_FORMATS = ("bf16", "fp8_e4m3", "mxfp4")   # NativeTarget (dense; a sparse-MoE target quantises its experts: EXPERT_FORMATS)
 
 
 class DFlashDraftModel:

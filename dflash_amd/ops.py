@@ -333,8 +333,8 @@ MX_EXP_MIN, MX_EXP_MAX = -120, 120     # scale codes 7..247 (code = exponent + 1
 
 
 class Mxfp4Weight(NamedTuple):
-    """A packed MXFP4 weight (pack_weight_mxfp4 / pack_weight_gateup_mxfp4): gemm_resid / gemm_silu_mul / gemm_argmax
-    take one in place of a packed bf16 weight (K % 128 == 0), and so do the ragged batch's gemm_silu_mul_batch /
+    """A packed MXFP4 weight (pack_weight_mxfp4 / pack_weight_gateup_mxfp4): gemm_resid / gemm_silu_mul / gemm_argmax /
+    gemm_sample take one in place of a packed bf16 weight (K % 128 == 0), and so do the ragged batch's gemm_silu_mul_batch /
     gemm_argmax_batch (K >= 256, frag16 sources) and gemm_f32_batch (mxfp4_parts_ok(K))."""
     data: torch.Tensor    # uint8: codes [N/16][K/128][64 lanes][16 B], then e8m0 scales [N/16][K/128][16 columns][4 B]
     N: int
@@ -477,7 +477,7 @@ def check_stream_format(stream_format: str) -> bool:
 
 def _w(wp, N: int, K: int, name: str, batch: bool = False) -> Weight:
     """The dfl_weight of a launch: a packed bf16 tensor, or an Fp8Weight / a Bf16x13Weight / an Mxfp4Weight of the launch's
-    N x K (the C side refuses a format the entry point does not take).  batch (the ragged-batch GEMMs): an Mxfp4Weight's
+    N x K (the C side refuses a format the entry point does not take).  batch (the ragged-batch GEMMs, gemm_sample): an Mxfp4Weight's
     scale region — behind the N * K / 2 bytes of codes — goes through `scale`, as the expert forms' array does.  Read
     on the host during the call only; the caller's references keep the tensors alive."""
     if isinstance(wp, Bf16x13Weight):
@@ -665,13 +665,14 @@ def gemm_sample(wp, x, V: int, K: int, row0: int, nrows: int, ws, out_ids: torch
                 pos_base: int = 0, pos_add: int = 0, dyn=None, nrows_dyn_word: int = -1,
                 logits: Optional[torch.Tensor] = None, margins: Optional[torch.Tensor] = None) -> None:
     """gemm_argmax with the seeded Gumbel-max draw at `temperature` (dfl_gemm_sample): tile row m draws position
-    (pos_dyn[pos_word] if pos_dyn is given, else pos_base) + pos_add + m.  wp: packed bf16, or an Fp8Weight
-    (the draw over bf16(sum * scale))."""
+    (pos_dyn[pos_word] if pos_dyn is given, else pos_base) + pos_add + m.  wp: packed bf16, an Fp8Weight (the draw over
+    bf16(sum * scale)) or an Mxfp4Weight (K % 128 == 0; the draw over bf16(sum) of the dequantised weights — its e8m0
+    region, behind the codes of the blob, goes through the descriptor's `scale` as in the batch forms)."""
     if logits is not None:
         assert logits.numel() >= 16 * V
     if margins is not None:
         assert margins.numel() >= out_off + nrows
-    check(lib().dfl_gemm_sample(_w(wp, V, K, "wp"), _src(x).ref, V, K, row0, nrows, _p(dyn, I32, "dyn"), nrows_dyn_word,
+    check(lib().dfl_gemm_sample(_w(wp, V, K, "wp", batch=True), _src(x).ref, V, K, row0, nrows, _p(dyn, I32, "dyn"), nrows_dyn_word,
                                 _p(ws), _p(out_ids, I64, "out_ids"), out_off, _p(logits, BF16, "logits"),
                                 _p(margins, F32, "margins"), _seed64(seed), inv_temperature(temperature), stream,
                                 _p(pos_dyn, I32, "pos_dyn"), pos_word, pos_base, pos_add, _stream()), "dfl_gemm_sample")

@@ -78,6 +78,12 @@ class _Weight:
         self.weight = w
 
 
+class Mxfp4TargetRefused(NotImplementedError, ValueError):
+    """weight_format="mxfp4" on a config the dense 4-bit target does not cover (a sparse-MoE target, widths that are no
+    multiples of 128 or missing): not implemented for that config, and for it no valid value of weight_format — a caller
+    that catches either kind sees it.  (Until the dense target took the format, every config got the ValueError.)"""
+
+
 class NativeTarget:
     def __init__(self, hf_model, max_splits: int = 32, attn_impl: str = "head", keep_hf: bool = True,
                  prefill: str = "native", weight_format: str = "bf16", expert_format: str = "bf16",
@@ -102,6 +108,19 @@ class NativeTarget:
         weight ("The target").  Norm weights and the embedding gather stay bf16.  What weight-only
         e4m3 does to a real checkpoint's outputs, or to the acceptance length of a draft trained on the bf16 target, is
         NOT measured — hence off by default.
+        weight_format="mxfp4" (a dense target; hidden, intermediate and q widths % 128 == 0): the same scheme in OCP MXFP4
+        — e2m1 codes with one power-of-two scale per 32 consecutive k of a row (ops.quantize_mxfp4_rows; W4A16).  Again the
+        quantised target IS the model and THE CALLER'S hf_model IS MODIFIED: q/k/v, o_proj, gate, up and down of every
+        layer and the lm_head are overwritten in place with the dequantised values before anything is packed (with tied
+        embeddings the table then holds the dequantised head); quantising those values again gives the same values, so
+        a second NativeTarget or packed_lm_head_mxfp4 of the overwritten head holds the same model.  `self.layers` is the
+        packed bf16 copy, `self.layers4` / `self.lm_wp4` the ops.Mxfp4Weight twins, which the verify streams at 0.53 bytes
+        per weight while `self.mxfp4_stream` is True: a block of <= 16 rows entirely (streams_mxfp4; the sampled head
+        through dfl_gemm_sample's 4-bit form), the tile-stack paths where the launch takes the matrix's K
+        (streams_mxfp4_tiles; their T > 0 heads stay bf16).  Prefill, attn_impl="fused", fuse_oproj, two-pass wide blocks,
+        the candidate loop and hidden > 4096 read the copy.  stream_format is ignored (no 13-bit twins).  What weight-only
+        MXFP4 does to a real checkpoint's outputs or to a trained draft's acceptance length is NOT measured — off by
+        default ("The target").
         expert_format: "bf16" (default), or "fp8_e4m3" for a sparse-MoE target (weight_format stays "bf16": at the MoE
         targets' hidden widths the dense projections are at their launch floors; the bytes are the experts'): every MoE
         layer's mlp.experts.gate_up_proj ([E, 2I, H] as E * 2I rows of H) and mlp.experts.down_proj ([E, H, I] as E * H
@@ -163,7 +182,12 @@ class NativeTarget:
         self.fp8_stream = True
         self.layers8 = [] if fp8 else None   # per layer: ops.Fp8Weight twins of qkv / o / gu / down in self.layers
         self.lm_wp8 = None                   # the e4m3 lm_head (ops.Fp8Weight)
-        self._tile_layers = {}               # tile_layers(): qkv_parts -> layer dicts with the e4m3 twins
+        mx4 = weight_format == "mxfp4"
+        # mxfp4 only: False = the bf16 kernels on the dequantised copy (the second implementation the tests compare)
+        self.mxfp4_stream = True
+        self.layers4 = [] if mx4 else None   # per layer: ops.Mxfp4Weight twins of qkv / o / gu / down in self.layers
+        self.lm_wp4 = None                   # the 4-bit lm_head (ops.Mxfp4Weight)
+        self._tile_layers = {}               # tile_layers(): qkv_parts -> layer dicts with the e4m3 / 4-bit twins
         self._row_layers = {}                # row_layers(): streams e4m3 -> layer dicts with the e4m3 / 13-bit twins
         self.hf = hf_model
         self.model = hf_model.model
@@ -217,16 +241,19 @@ class NativeTarget:
             """A Linear weight: as loaded, or (fp8) its dequantised values q * scale — written back over the wrapped
             model's own tensor — with the codes and scales kept in `store`."""
             m = w(name)
-            if fp8:
-                m, store[key] = ops.quantize_keep_fp8(m)
+            if fp8 or mx4:
+                m, store[key] = ops.quantize_keep_fp8(m) if fp8 else ops.quantize_keep_mxfp4(m)
                 with torch.no_grad():
                     sd[name].copy_(m)   # (the state dict's tensors are the parameters' storage; exact in any float dtype)
             return m
 
-        if fp8:   # the head first: with tied embeddings self.embed, read below, is then the dequantised head
+        if fp8 or mx4:   # the head first: with tied embeddings self.embed, read below, is then the dequantised head
             h8 = {}
             mat("lm_head.weight", h8, "lm")
-            self.lm_wp8 = ops.pack_weight_fp8(*h8.pop("lm"))
+            if fp8:
+                self.lm_wp8 = ops.pack_weight_fp8(*h8.pop("lm"))
+            else:
+                self.lm_wp4 = ops.pack_weight_mxfp4(*h8.pop("lm"))
         self.layers = []
         self.gu13 = []   # stream_format="auto": per layer, the 13-bit twin of a dense layer's gate/up or None
         self.down13 = []   # ... and of its down_proj (the K-chunked form: intermediate size a multiple of 2048 above 4096)
@@ -304,6 +331,8 @@ class NativeTarget:
                 if "gate" not in l8:
                     raise NotImplementedError("NativeTarget: fp8_e4m3 needs dense MLP layers")
                 self.layers8.append(ops.pack_layer_fp8(l8))
+            if mx4:   # (check_config has refused a sparse-MoE config: every layer is dense)
+                self.layers4.append(ops.pack_layer_mxfp4(l8))
             self.layers.append(lw)
             self.gu13.append(gu13)
             self.down13.append(down13)
@@ -375,13 +404,27 @@ class NativeTarget:
         needs them): head_dim != 128, biased projections, sliding-window attention layers, a sparse-MoE target (num_experts)
         whose hidden_size exceeds 4096 or is no multiple of 32.  weight_format: an unknown
         one is a ValueError; "fp8_e4m3" refuses a sparse-MoE target (its experts take expert_format instead) and hidden,
-        intermediate or q widths that are not multiples of 64 (the packed e4m3 layout holds k-step pairs).
+        intermediate or q widths that are not multiples of 64 (the packed e4m3 layout holds k-step pairs); "mxfp4" refuses
+        a sparse-MoE target the same way, pointing at expert_format, and those widths where they are missing or no
+        multiples of 128 — with Mxfp4TargetRefused, a NotImplementedError that is a ValueError too, checked with the name.
         expert_format: an unknown one is a ValueError; "fp8_e4m3" needs a sparse-MoE config (num_experts) whose hidden_size
         and moe_intermediate_size are multiples of 64; "mxfp4" one whose two widths are multiples of 128 (a 4-k-step word)."""
         if weight_format not in WEIGHT_FORMATS:
             raise ValueError(f"NativeTarget: weight_format must be one of {WEIGHT_FORMATS}, got {weight_format!r}")
         if expert_format not in EXPERT_FORMATS:
             raise ValueError(f"NativeTarget: expert_format must be one of {EXPERT_FORMATS}, got {expert_format!r}")
+        if weight_format == "mxfp4":   # with the format's name: is it a value THIS config can take?  (Mxfp4TargetRefused)
+            if getattr(cfg, "num_experts", 0) or getattr(cfg, "num_local_experts", 0):
+                raise Mxfp4TargetRefused("NativeTarget: weight_format='mxfp4' is the dense target's; a sparse-MoE target takes "
+                                         "its 4-bit weights through expert_format='mxfp4' (weight_format stays 'bf16')")
+            heads, hidden = getattr(cfg, "num_attention_heads", None), getattr(cfg, "hidden_size", None)
+            head_dim = getattr(cfg, "head_dim", None) or (hidden // heads if hidden and heads else None)
+            widths = dict(hidden_size=hidden, intermediate_size=getattr(cfg, "intermediate_size", None),
+                          q_width=heads * head_dim if heads and head_dim else None)
+            bad = {k: v for k, v in widths.items() if not v or v % 128}
+            if bad:
+                raise Mxfp4TargetRefused(f"NativeTarget: weight_format='mxfp4' needs hidden, intermediate and q widths % 128 == 0 "
+                                         f"(a 4-k-step word; got {bad})")
         n_q = cfg.num_attention_heads
         hd = getattr(cfg, "head_dim", None) or cfg.hidden_size // n_q
         if hd != 128:
@@ -417,7 +460,7 @@ class NativeTarget:
         if expert_format == "mxfp4":
             if not getattr(cfg, "num_experts", 0):
                 raise NotImplementedError("NativeTarget: expert_format='mxfp4' needs a sparse-MoE target (Qwen3-MoE expert "
-                                          "layout); the 4-bit format has no dense target form")
+                                          "layout); a dense target takes weight_format='mxfp4'")
             widths = dict(hidden_size=cfg.hidden_size, moe_intermediate_size=getattr(cfg, "moe_intermediate_size", 0))
             bad = {k: v for k, v in widths.items() if not v or v % 128}
             if bad:
@@ -460,18 +503,45 @@ class NativeTarget:
         return (self.layers8 is not None and self.fp8_stream and self.attn_impl == "head"
                 and min(self.H, self.I, self.q_dim) >= 256)   # (the ring and K-part W8 forms take K >= 256)
 
+    def streams_mxfp4(self, bs: int = 16) -> bool:
+        """Whether verify() streams the 4-bit twins for a block of `bs` rows: an mxfp4 target, mxfp4_stream, one 16-row
+        tile, the head attention stage, o_proj not fused, no wide hidden (the draft's streams_mxfp4).  A 17..32-row block
+        in one pass is a tile-stack path (streams_mxfp4_tiles); in two passes it reads self.layers."""
+        return (self.layers4 is not None and self.mxfp4_stream and bs <= 16 and self.attn_impl == "head"
+                and not self.fuse_oproj and not self.wide_hidden)
+
+    def streams_mxfp4_tiles(self) -> bool:
+        """The same for the tile-stack paths — _verify_wide, the ragged batch and engine: gate/up and the greedy lm_head
+        take the codes (the ring forms, K = hidden >= 256), and o_proj, down_proj and q/k/v as parts where
+        ops.mxfp4_parts_ok holds for the matrix's K; everything else, a T > 0 head among it, reads the bf16 copy
+        ("The target")."""
+        return (self.layers4 is not None and self.mxfp4_stream and self.attn_impl == "head" and not self.wide_hidden
+                and self.H >= 256)
+
     def tile_layers(self, qkv_parts: bool) -> list:
         """The layer dicts TileStack.run takes: self.layers, with gu / o / down — and qkv, where the caller runs
-        qkv="parts" — replaced by their e4m3 twins when streams_fp8_tiles()."""
-        if not self.streams_fp8_tiles():
-            return self.layers
-        return ops.tile_layers(self.layers, self.layers8, qkv_parts, self._tile_layers)
+        qkv="parts" — replaced by their e4m3 twins when streams_fp8_tiles(), by their 4-bit twins when
+        streams_mxfp4_tiles() (o / down / qkv per matrix: ops.tile_layers)."""
+        if self.streams_fp8_tiles():
+            return ops.tile_layers(self.layers, self.layers8, qkv_parts, self._tile_layers)
+        if self.streams_mxfp4_tiles():
+            return ops.tile_layers(self.layers, self.layers4, qkv_parts, self._tile_layers)
+        return self.layers
 
     def row_layers(self, bs: int) -> list:
         """The layer dicts RowStack.run takes for a block of `bs` rows: self.layers, with the four matrices replaced by
-        their e4m3 twins when streams_fp8(bs), else a dense layer's gate/up and down by their 13-bit twins where it has
-        them (gu13, down13)."""
-        return ops.row_layers(self.layers, self.layers8, self.gu13, self.streams_fp8(bs), self._row_layers, self.down13)
+        their e4m3 twins when streams_fp8(bs) or their 4-bit twins when streams_mxfp4(bs) (a target has one of the two at
+        most), else a dense layer's gate/up and down by their 13-bit twins where it has them (gu13, down13)."""
+        fp8, mx4 = self.streams_fp8(bs), self.streams_mxfp4(bs)
+        return ops.row_layers(self.layers, self.layers8 if fp8 else self.layers4, self.gu13, fp8 or mx4, self._row_layers,
+                              self.down13)
+
+    def mxfp4_tensors(self) -> tuple:
+        """Every code blob of an mxfp4 target (empty otherwise): what a captured graph of the verify holds raw pointers
+        to (DecodeSession's keep-alive tuple, the engine's capture key)."""
+        if self.layers4 is None:
+            return ()
+        return tuple(w4.data for l4 in self.layers4 for w4 in l4.values()) + (self.lm_wp4.data,)
 
     def fp8_tensors(self) -> tuple:
         """Every e4m3 code tensor and scale vector of an fp8 target and of fp8 experts (empty for bf16): what a captured
@@ -500,9 +570,13 @@ class NativeTarget:
             return (lw["gu_e13"] if (pair and "gu_e13" in lw) else lw["gu_e"]), lw["down_e"]
         return (lw["gu_e8"] if pair else lw["gu_e"]), lw["down_e8"]
 
-    def tile_head(self):
-        """The lm_head of the tile-stack paths: the e4m3 codes when streams_fp8_tiles(), else the packed bf16 copy."""
-        return self.lm_wp8 if self.streams_fp8_tiles() else self.lm_wp
+    def tile_head(self, greedy: bool = True):
+        """The lm_head of the tile-stack paths: the e4m3 codes when streams_fp8_tiles(); the 4-bit codes when
+        streams_mxfp4_tiles() and the launch is the greedy ring argmax head (a T > 0 head — the sampled ring head or the
+        two-step draw — has no 4-bit form: bf16); else the packed bf16 copy."""
+        if self.streams_fp8_tiles():
+            return self.lm_wp8
+        return self.lm_wp4 if (greedy and self.streams_mxfp4_tiles()) else self.lm_wp
 
     def new_cache(self, max_rows: Optional[int] = None) -> TargetKVCache:
         if max_rows is None:
@@ -806,7 +880,7 @@ class NativeTarget:
         if not process and temperature >= 1e-5:
             logits = torch.empty(32, self.V, dtype=BF16, device=self._dev)
         lv = None if logits is None else logits.view(2, 16, self.V)
-        ops.gemm_argmax_batch(self.tile_head(), s["xn"], R, self.V, H, 0, 16, gws, post.view(2, 16), 0, dyn2,
+        ops.gemm_argmax_batch(self.tile_head(greedy=temperature < 1e-5), s["xn"], R, self.V, H, 0, 16, gws, post.view(2, 16), 0, dyn2,
                               nrows_dyn_word=ops.DYN_BS, logits=lv)
         if process:   # (blocks of 17..32 rows: min_p and the filtered draw; the processors that read the block were refused)
             stage.rows(lv, None, post.view(2, 16), draw=dict(seed=seed, temperature=temperature), **where)
@@ -903,7 +977,8 @@ class NativeTarget:
                     self._taps[key] = torch.zeros(32, key * H, dtype=BF16, device=self._dev)
                 taps = self._taps[key]
         w8 = self.streams_fp8(bs)
-        head = self.lm_wp8 if w8 else self.lm_wp
+        # (an mxfp4 target that streams: the 4-bit head under every launch below — greedy, materialising, sampled)
+        head = self.lm_wp8 if w8 else self.lm_wp4 if self.streams_mxfp4(bs) else self.lm_wp
         if own and stage is not None:
             stage.device, stage._bufs = self._dev, self._kw_bufs
         if len(tiles) == 2 and self.wide_one_pass and self.attn_impl == "head":

@@ -122,7 +122,7 @@ typedef struct dfl_rows {
  * ---- DFL_W_MXFP4: OCP Microscaling MXFP4, weight-only (W4A16) ----
  * Taken by dfl_gemm_resid (any K % 128 == 0, the K-chunked form included), dfl_gemm_silu_mul and dfl_gemm_argmax, and — with
  * the scales as an array of their own, see the two entry points — by dfl_moe_gate_up and dfl_moe_down, and with the scale
- * region through `scale` by dfl_gemm_f32_batch, dfl_gemm_silu_mul_batch and dfl_gemm_argmax_batch; every other entry
+ * region through `scale` by dfl_gemm_sample, dfl_gemm_f32_batch, dfl_gemm_silu_mul_batch and dfl_gemm_argmax_batch; every other entry
  * point refuses it as an unknown format.  An element is an e2m1 code (bit 3 sign, bits 2:0 the magnitudes
  * 0, .5, 1, 1.5, 2, 3, 4, 6) and every 32 consecutive k of a row share one e8m0 scale code s: the weight is e2m1 * 2^(s - 127).
  * The kernels convert code pairs to bf16 with the block scale applied in the conversion (exact), run the same bf16 MFMA
@@ -212,7 +212,7 @@ int dfl_gemm_silu_mul(const dfl_weight *w_gateup, const dfl_rows *x, int I, int 
  * argmax finish launch comes behind ev_end): bench.py times the lm_head kernel itself with them (roofline.achieved).
  * e4m3: ids, logits and margins over bf16(sum * scale).  DFL_W_BF16X13: K = 2048 or 4096, scale NULL; same bits as
  * DFL_W_BF16 (dfl_gemm_sample does not take it).  DFL_W_MXFP4: K % 128 == 0, scale NULL; ids, logits and margins over
- * bf16(sum) of the dequantised weights (dfl_gemm_sample refuses it). */
+ * bf16(sum) of the dequantised weights (dfl_gemm_sample takes it with the scale region through `scale`, see there). */
 int64_t dfl_argmax_ws_bytes(void);
 int dfl_gemm_argmax(const dfl_weight *w, const dfl_rows *x, int V, int K, int row0, int nrows, const int32_t *dyn,
                     int nrows_dyn_word, void *ws, int64_t *out_ids, int out_off, void *logits, float *margin_out,
@@ -224,7 +224,13 @@ int dfl_gemm_argmax(const dfl_weight *w, const dfl_rows *x, int V, int K, int ro
  * stream)).  Tile row m draws position p = base + pos_add + m with base = pos_dyn[pos_word] (a device length record, so
  * a captured graph draws fresh positions on every replay) or, pos_dyn NULL, base = pos_base.  rng_stream 0 (TARGET):
  * extra = 0; 1 (DRAFT): extra = base.  Everything else as dfl_gemm_argmax; margin_out is the perturbed top-2 gap.
- * e4m3: the draw perturbs bf16(sum * scale[n]), the logit dfl_gemm_argmax materialises for the same weight. */
+ * e4m3: the draw perturbs bf16(sum * scale[n]), the logit dfl_gemm_argmax materialises for the same weight.
+ * DFL_W_MXFP4 (K % 128 == 0, K <= 4096): the batch forms' descriptor convention — wp the codes of the dense layout,
+ * `scale` that layout's e8m0 region, wp + V * K / 2 for the dense blob, 64-byte aligned (dfl_gemm_argmax takes the same
+ * blob with scale NULL).  The block scales ride in the conversion, so the draw perturbs bf16(sum) of the dequantised
+ * weights — the rounding point of the bf16 form and the logit dfl_gemm_argmax materialises for the same weight; positions,
+ * streams, workspace, `logits` and the rows past nrows as the bf16 form has them.  DFL_EINVAL, nothing launched: a NULL
+ * scale (refused as format 3 without its region), a misaligned one, K % 128 != 0, K > 4096. */
 int dfl_gemm_sample(const dfl_weight *w, const dfl_rows *x, int V, int K, int row0, int nrows, const int32_t *dyn,
                     int nrows_dyn_word, void *ws, int64_t *out_ids, int out_off, void *logits, float *margin_out,
                     uint64_t seed, float inv_t, int rng_stream, const int32_t *pos_dyn, int pos_word, int pos_base,
