@@ -116,6 +116,7 @@ SIGNATURES = {
     "dfl_prefill_pack_rows": (_i, [_p, _i64, _i, _i, _p, _p]),
     "dfl_prefill_qk_rope": (_i, [_p, _i64, _i, _i, _i, _i, _i, _i, _p, _p, _f, _p, _p, _i, _i, _p, _p, _i, _i, _p]),
     "dfl_prefill_attn": (_i, [_p, _i64, _i, _p, _p, _i, _i, _i, _i, _f, _p, _p]),
+    "dfl_prefill_logprobs": (_i, [_p, _p, _i, _i, _i, _p, _i, _p, _p, _p]),
     "dfl_prefill_moe_max_tiles": (_i64, [_i, _i, _i]),
     "dfl_prefill_moe_max_items": (_i64, [_i, _i, _i]),
     "dfl_prefill_moe_route": (_i, [_p, _i64, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p]),

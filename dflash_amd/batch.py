@@ -28,7 +28,7 @@ import torch
 from . import ops
 from .generate import (NO_LOGPROBS, _bf16_table, _draw_rows, _kept_cols, _stop_hit, _taps, _trim, capture_graph, check_couple_draft,
                        first_token_stop,
-                       cuda_time, logprob_fields, resolve_seed)
+                       cuda_time, check_prompt_logprobs, logprob_fields, resolve_seed)
 from .logits_stage import LogitsStage, check_features
 from .model import DFlashDraftModel
 from .target import NativeTarget
@@ -234,6 +234,7 @@ class BatchedDecoder:
         self.n_in = [0] * R
         self.live = [False] * R
         self.hook_calls = [0] * R
+        self.prompt_lp = [None] * R   # per slot: the prompt_logprobs of the request admitted last (None: not asked for)
         self.bs = [self.BW] * R
         self.events = None  # set to a dict to have cycle() record (start, end) event pairs per phase
         self._ahead, self._ahead_ev = False, None   # a run-ahead draft is in flight (cycle(ahead_ok=True))
@@ -271,7 +272,7 @@ class BatchedDecoder:
 
     # ------------------------------------------------------------------ admission
     def _admit_prefill(self, r: int, input_ids: torch.Tensor, temperature: float, seed: Optional[int], top_k=0,
-                       top_p=1.0, penalties=(1.0, 0.0, 0.0), bias=None, grammar=None, min_p=None):
+                       top_p=1.0, penalties=(1.0, 0.0, 0.0), bias=None, grammar=None, min_p=None, prompt_logprobs=False):
         """The launches both admissions share: target prefill into slot r's cache, the first token, the prompt's context
         rows into the draft cache except the last <= 16.  Returns (P, first token [1, 1] on the device, tapped rows
         [P, fc_in], the seed written for the slot or None)."""
@@ -306,7 +307,10 @@ class BatchedDecoder:
             self._lm8()
             self.embed_w = _bf16_table(t.model.embed_tokens.weight, self.dev)
         tc = _View(self.tk[r], self.tv[r], None, self.max_rows)
-        out = t.prefill(input_ids, tc, output_hidden_states=True, tap_layers=self.model.target_layer_ids)
+        plp = ops.check_prompt_logprobs(prompt_logprobs)   # (off: the prefill's launches of before; section 23)
+        out = t.prefill(input_ids, tc, output_hidden_states=True, tap_layers=self.model.target_layer_ids,
+                        **(dict(prompt_logprobs=True) if plp else {}))
+        self.prompt_lp[r] = out.prompt_logprobs if plp else None
         sd = None
         if self.sampler == "device" and (temperature >= 1e-5 or self.temperature >= 1e-5):
             sd = resolve_seed("device", seed)
@@ -411,7 +415,7 @@ class BatchedDecoder:
     def admit(self, r: int, input_ids: torch.Tensor, temperature: float = 0.0, seed: Optional[int] = None,
               top_k: int = 0, top_p: float = 1.0, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
               frequency_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None, banned_token_ids=None,
-              min_tokens: int = 0, grammar=None, min_p=None, stop_sequences=None) -> None:
+              min_tokens: int = 0, grammar=None, min_p=None, stop_sequences=None, prompt_logprobs=False) -> None:
         """Prefill request r (model/dflash.py:218-229): target prefill through the wrapped
         model, K/V into the group cache, first token sampled, the prompt's context rows
         projected into the draft cache except the last <= 16, which become the first
@@ -428,13 +432,15 @@ class BatchedDecoder:
         min_p: the request's own (None / 0: off; a decoder built with min_p=True, else ValueError); the slot's
         ln(min_p) is rewritten.
         stop_sequences: the request's own (None: none; a decoder built with stop_sequences=True, else ValueError); the
-        slot's table rows and hit record are rewritten.  A request's own stop IDS are sequences of length 1 given here."""
+        slot's table rows and hit record are rewritten.  A request's own stop IDS are sequences of length 1 given here.
+        prompt_logprobs (False: off; True: as NativeTarget.prefill): the slot's self.prompt_lp[r] is the prompt's fp32
+        [P - 1] tensor until the slot's next admission (None when off)."""
         seqs = self.check_stop_sequences(stop_sequences)
         P, first, th, sd = self._admit_prefill(r, input_ids, temperature, seed, top_k, top_p,
                                                (repetition_penalty, presence_penalty, frequency_penalty),
                                                dict(logit_bias=logit_bias, allowed_token_ids=allowed_token_ids,
                                                     banned_token_ids=banned_token_ids, min_tokens=min_tokens), grammar,
-                                               min_p)
+                                               min_p, prompt_logprobs)
         self.output_ids[r].fill_(self.mask_id)
         self.output_ids[r, :P] = input_ids[0]
         if sd is not None:
@@ -460,7 +466,7 @@ class BatchedDecoder:
     def admit_fused(self, r: int, input_ids: torch.Tensor, temperature: float = 0.0, seed: Optional[int] = None,
                     top_k: int = 0, top_p: float = 1.0, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
                     frequency_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None, banned_token_ids=None,
-                    min_tokens: int = 0, grammar=None, min_p=None, stop_sequences=None) -> None:
+                    min_tokens: int = 0, grammar=None, min_p=None, stop_sequences=None, prompt_logprobs=False) -> None:
         """`admit` with the slot re-armed by ONE launch (dfl_admit_slot) instead of a dozen small writes: ids, first
         token, block, context tile, both length records and the seed are written on the device from device-resident
         inputs, so that after the prefill launches the admission reads nothing back and copies nothing from the host —
@@ -475,7 +481,7 @@ class BatchedDecoder:
                                                (repetition_penalty, presence_penalty, frequency_penalty),
                                                dict(logit_bias=logit_bias, allowed_token_ids=allowed_token_ids,
                                                     banned_token_ids=banned_token_ids, min_tokens=min_tokens), grammar,
-                                               min_p)
+                                               min_p, prompt_logprobs)
         n_tail = min(16, P)
         ops.admit_slot(r, input_ids[0].contiguous(), first.reshape(1), self.output_ids, self.block, self.post, self.result,
                        th[P - n_tail:], self.d["taps"], self.dyn_d, self.dyn_t, self.BW, self.mask_id,
@@ -923,7 +929,7 @@ def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_i
                           presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, allowed_token_ids=None,
                           banned_token_ids=None, min_tokens=0, grammar=None, constrain_draft: bool = False,
                           min_p=None, couple_draft: bool = False, stop_sequences=None,
-                          include_stop_sequence: bool = True) -> list:
+                          include_stop_sequence: bool = True, prompt_logprobs=False) -> list:
     """`dflash_generate` (benchmark.py:44-251) for a list of prompts: requests run in
     groups of `group_size` <= 4 (<= 2 with block sizes of 17..32 rows) that share the weight stream; returns one namespace per
     prompt with the fields of benchmark.py:242-251 (timing fields are the group's).
@@ -949,10 +955,12 @@ def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_i
     couple_draft: as dflash_generate, for every prompt at its own temperature (a prompt at 0 keeps its greedy draft).
     stop_sequences / include_stop_sequence: as dflash_generate; one list of sequences for every prompt, or a list with one
     list (or None) per prompt.  The decoders are built with stop_sequences=True when any prompt carries one; the
-    results carry `stop_sequence`."""
+    results carry `stop_sequence`.
+    prompt_logprobs: as dflash_generate, for every prompt (the field `prompt_logprobs`; None when off)."""
     stops = _prompt_stop_sequences(stop_sequences, len(input_ids), target, mask_token_id)
     stops_on = any(s is not None for s in stops)
     logprobs = ops.check_logprobs(logprobs)
+    prompt_logprobs = check_prompt_logprobs(prompt_logprobs, target)
     dfas = _prompt_grammars(grammar, len(input_ids))
     for d in {id(d): d for d in dfas if d is not None}.values():
         ops.check_grammar(d, target.V)
@@ -1000,7 +1008,8 @@ def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_i
             pr, pa, pf = pens[idx[r]]
             dec.admit(r, p, temps[idx[r]], seed=seeds[idx[r]], top_k=top_ks[idx[r]], top_p=top_ps[idx[r]],
                       repetition_penalty=pr, presence_penalty=pa, frequency_penalty=pf, **biases[idx[r]],
-                      grammar=handles[r], min_p=min_ps[idx[r]] if min_p_on else None, stop_sequences=stops[idx[r]])
+                      grammar=handles[r], min_p=min_ps[idx[r]] if min_p_on else None, stop_sequences=stops[idx[r]],
+                      prompt_logprobs=prompt_logprobs)
         ttft = cuda_time() - t0
         taus = [[] for _ in idx]
         # (hook_block_view: the hook sees the block as the single-request loop hands it over, bs slots; default: the
@@ -1044,7 +1053,7 @@ def dflash_generate_batch(model: DFlashDraftModel, target: NativeTarget, input_i
                                          time_to_first_token=ttft, time_per_output_token=decode_s / max(1, n_out),
                                          acceptance_lengths=taus[r], cycle_trace=[], profile_summary=None,
                                          grammar_state=dec.grammar_state_of(r, ids[0], dec.n_in[r]),
-                                         stop_sequence=which[0] if which else None, **lpf)
+                                         stop_sequence=which[0] if which else None, prompt_logprobs=dec.prompt_lp[r], **lpf)
         del dec
     return results
 

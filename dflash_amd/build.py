@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libdflash_hip.so")
-SOURCES = ["dfl_common.hip", "gemm_skinny.hip", "gemm_batch.hip", "gemm_batch_w4.hip", "rows.hip", "attn_block.hip", "attn_head.hip", "accept.hip", "nucleus.hip", "logprobs.hip", "penalties.hip", "logit_bias.hip", "min_p.hip", "grammar.hip", "grammar_draft.hip", "grammar_lift.hip", "stop_seq.hip", "candidates.hip", "moe.hip", "moe_w4.hip", "moe_w4_shared.hip", "prefill.hip"]
+SOURCES = ["dfl_common.hip", "gemm_skinny.hip", "gemm_batch.hip", "gemm_batch_w4.hip", "rows.hip", "attn_block.hip", "attn_head.hip", "accept.hip", "nucleus.hip", "logprobs.hip", "penalties.hip", "logit_bias.hip", "min_p.hip", "grammar.hip", "grammar_draft.hip", "grammar_lift.hip", "stop_seq.hip", "candidates.hip", "moe.hip", "moe_w4.hip", "moe_w4_shared.hip", "prefill.hip", "prompt_logprobs.hip"]
 HEADERS = [os.path.join(CSRC, "dfl_common.h"), os.path.join(CSRC, "dfl_rng.h"), os.path.join(CSRC, "gemm_rows.h"), os.path.join(CSRC, "gemm_ring.h"), os.path.join(CSRC, "moe_route.h"),
            os.path.join(HERE, "..", "include", "dflash_hip.h")]
 # kernarg preload: gfx950 delivers up to 14 leading scalar / pointer kernel arguments in SGPRs at wave start (the hot
@@ -21,9 +21,10 @@ HEADERS = [os.path.join(CSRC, "dfl_common.h"), os.path.join(CSRC, "dfl_rng.h"), 
 # The diagnostic builds under scripts/ compile with these flags too, so a stamped build measures the product's code.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",
          "-mllvm", "-amdgpu-kernarg-preload-count=14"]
-# per source, on top of FLAGS.  moe_w4.hip, moe_w4_shared.hip, gemm_batch_w4.hip: no packed fp32 instructions (v_pk_fma_f32 and kin) in their kernels
+# per source, on top of FLAGS.  moe_w4.hip, moe_w4_shared.hip, gemm_batch_w4.hip, prompt_logprobs.hip: no packed fp32 instructions (v_pk_fma_f32 and kin) in their kernels
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-EXTRA_FLAGS = {"moe_w4.hip": _NO_PK_F32, "moe_w4_shared.hip": _NO_PK_F32, "gemm_batch_w4.hip": _NO_PK_F32}
+EXTRA_FLAGS = {"moe_w4.hip": _NO_PK_F32, "moe_w4_shared.hip": _NO_PK_F32, "gemm_batch_w4.hip": _NO_PK_F32,
+               "prompt_logprobs.hip": _NO_PK_F32}
 
 
 def _hipcc() -> str:

@@ -18,7 +18,7 @@ from . import ops
 from .batch import (MAX_GROUP, BatchedDecoder, _load_grammars, _pool_rows, _prompt_bias, _prompt_filters,
                     _prompt_grammars, _prompt_min_p, _prompt_penalties, _prompt_seeds, _prompt_stop_sequences,
                     _prompt_temperatures)
-from .generate import NO_LOGPROBS, _kept_cols, _trim, cuda_time, logprob_fields
+from .generate import NO_LOGPROBS, _kept_cols, _trim, check_prompt_logprobs, cuda_time, logprob_fields
 from .logits_stage import check_features
 from .slots import SlotLoop
 
@@ -66,7 +66,8 @@ class _DecoderDriver:
         self.dec.admit_fused(slot, ids, p.temperature, seed=p.seed, top_k=p.top_k, top_p=p.top_p,
                              repetition_penalty=p.penalties[0], presence_penalty=p.penalties[1],
                              frequency_penalty=p.penalties[2], **bias, grammar=p.grammar, min_p=p.min_p,
-                             stop_sequences=p.stop_sequences)
+                             stop_sequences=p.stop_sequences, prompt_logprobs=p.prompt_logprobs)
+        p.prompt_lp = self.dec.prompt_lp[slot]   # (kept with the request: the slot's next admission replaces the decoder's)
         t1 = cuda_time()
         p.ttft, p.t_admitted = t1 - t0, t1
         self.stats["admit_s"] += t1 - t0
@@ -121,7 +122,7 @@ class _DecoderDriver:
                                    request_id=req.rid, slot=slot, admitted_step=req.admitted_step,
                                    finished_step=req.finished_step,
                                    grammar_state=d.grammar_state_of(slot, ids[0], req.n_in),
-                                   stop_sequence=which[0] if which else None, **lpf)
+                                   stop_sequence=which[0] if which else None, prompt_logprobs=p.prompt_lp, **lpf)
 
 
 class BatchEngine:
@@ -191,7 +192,7 @@ class BatchEngine:
                temperature: Optional[float] = None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
                frequency_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None, banned_token_ids=None,
                min_tokens: int = 0, grammar=None, min_p=None, stop_sequences=None,
-               include_stop_sequence: bool = True) -> int:
+               include_stop_sequence: bool = True, prompt_logprobs=False) -> int:
         """Queue a request; returns its id (ids count up in submission order).  draft_token_hook(block_view, start,
         call): `call` counts from 0 at the request's admission; the view has the cycle's block size.
         top_k / top_p: the request's own filter on its T > 0 draws (an engine built with filtering=True); accepted and
@@ -207,7 +208,10 @@ class BatchEngine:
         request whose own temperature is 0.
         stop_sequences: the request's own (None: none; an engine built with stop_sequences=True, else ValueError),
         validated here; a request's own stop IDS are sequences of length 1.  include_stop_sequence=False cuts the matched
-        ids off the result as well."""
+        ids off the result as well.
+        prompt_logprobs (False: off; True: as dflash_generate): the request's result carries `prompt_logprobs` (None when
+        off); any engine — the pass belongs to the request's own prefill at its admission."""
+        plp = ops.check_prompt_logprobs(prompt_logprobs)
         seqs = None if stop_sequences is None else self.dec.check_stop_sequences(stop_sequences)
         mp = ops.check_min_p(min_p)
         if grammar is not None:   # (raises on a handle this engine did not return, and on an engine without a pool)
@@ -234,7 +238,8 @@ class BatchEngine:
                                                ttft=0.0, t_admitted=0.0, top_k=int(top_k), top_p=float(top_p),
                                                temperature=T, penalties=pen or (1.0, 0.0, 0.0), bias=bias,
                                                grammar=grammar, min_p=mp, stop_sequences=seqs,
-                                               include_stop=bool(include_stop_sequence), min_tokens=int(min_tokens)))
+                                               include_stop=bool(include_stop_sequence), min_tokens=int(min_tokens),
+                                               prompt_logprobs=plp, prompt_lp=None))
         return req.rid
 
     def add_grammar(self, dfa) -> int:
@@ -268,7 +273,7 @@ def dflash_generate_stream(model, target, input_ids: Sequence[torch.Tensor], mas
                            frequency_penalty=0.0, logit_bias=None, allowed_token_ids=None, banned_token_ids=None,
                            min_tokens=0, grammar=None, constrain_draft: bool = False, min_p=None,
                            couple_draft: bool = False, stop_sequences=None,
-                           include_stop_sequence: bool = True) -> list:
+                           include_stop_sequence: bool = True, prompt_logprobs=False) -> list:
     """`dflash_generate_batch` with slot refill: one namespace per prompt with the fields of benchmark.py:242-251, each
     request emitting what its own `dflash_generate` run emits.  max_new_tokens: one int or one per prompt.
     draft_token_hook(request_index, block_view, start, call).  seed as in dflash_generate_batch (an int s gives prompt i
@@ -282,7 +287,9 @@ def dflash_generate_stream(model, target, input_ids: Sequence[torch.Tensor], mas
     grammar: one TokenDFA for every prompt, or a sequence with one (or None) per prompt.
     constrain_draft: as dflash_generate_batch.  couple_draft: likewise.
     min_p: a scalar, or one value (or None) per prompt.
-    stop_sequences / include_stop_sequence: as dflash_generate_batch."""
+    stop_sequences / include_stop_sequence: as dflash_generate_batch.
+    prompt_logprobs: as dflash_generate, for every prompt."""
+    prompt_logprobs = check_prompt_logprobs(prompt_logprobs, target)
     stops = _prompt_stop_sequences(stop_sequences, len(input_ids), target, mask_token_id)
     dfas = _prompt_grammars(grammar, len(input_ids))
     for d in {id(d): d for d in dfas if d is not None}.values():
@@ -315,5 +322,5 @@ def dflash_generate_stream(model, target, input_ids: Sequence[torch.Tensor], mas
                    temperature=temps[i], repetition_penalty=pens[i][0], presence_penalty=pens[i][1],
                    frequency_penalty=pens[i][2], **biases[i], grammar=handles[i],
                    min_p=min_ps[i] if min_p_on else None, stop_sequences=stops[i],
-                   include_stop_sequence=include_stop_sequence)
+                   include_stop_sequence=include_stop_sequence, prompt_logprobs=prompt_logprobs)
     return eng.run()

@@ -208,6 +208,18 @@ def logprob_fields(sink, row: int, cols: torch.Tensor) -> dict:
 NO_LOGPROBS = dict(logprobs=None, top_logprob_ids=None, top_logprobs=None)
 
 
+def check_prompt_logprobs(prompt_logprobs, target, where: str = "") -> bool:
+    """The `prompt_logprobs` keyword of the generate entry points, before anything touches the GPU: ops.check_prompt_logprobs
+    (True / False; top-N per prompt position is NotImplementedError), and a target that is no NativeTarget is refused in
+    check_features' words."""
+    from .target import NativeTarget
+    on = ops.check_prompt_logprobs(prompt_logprobs)
+    if on and not isinstance(target, NativeTarget):
+        raise ValueError(f"{where}prompt_logprobs needs a dflash_amd.NativeTarget (the kernel reads the native prefill's "
+                         f"final rows)")
+    return on
+
+
 def _vocab_of(target) -> int:
     """The vocabulary the logit-bias keywords are validated against: a NativeTarget's V, else the wrapped model's
     config.vocab_size (only to tell neutral values from a request such a target cannot serve)."""
@@ -249,8 +261,13 @@ class DecodeSession:
                  top_k: int = 0, top_p: float = 1.0, logprobs: Optional[int] = None, repetition_penalty: float = 1.0,
                  presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None,
                  banned_token_ids=None, min_tokens: int = 0, grammar=None, constrain_draft: bool = False, min_p=None,
-                 couple_draft: bool = False, stop_sequences=None, include_stop_sequence: bool = True):
+                 couple_draft: bool = False, stop_sequences=None, include_stop_sequence: bool = True,
+                 prompt_logprobs=False):
         from .target import NativeTarget
+        # prompt_logprobs: the prompt tokens' own log-probabilities from the target's prefill; off:
+        # the prefill enqueues the launches of before
+        self.prompt_lp = check_prompt_logprobs(prompt_logprobs, target)
+        self.prompt_logprobs = None
         # stop_sequences: multi-token stops matched on the device by one launch in front of every
         # accept launch; None / empty: the launches of before, nothing allocated.  Bad values are refused first
         self.stop_seqs = (ops.check_stop_sequences(stop_sequences, _vocab_of(target), mask_token_id)
@@ -418,7 +435,9 @@ class DecodeSession:
         """model/dflash.py:218-229."""
         if self.native:
             out = self.target.prefill(self.input_ids, self.tcache, output_hidden_states=self.use_draft,
-                                      tap_layers=self.model.target_layer_ids if self.use_draft else None)
+                                      tap_layers=self.model.target_layer_ids if self.use_draft else None,
+                                      **(dict(prompt_logprobs=True) if self.prompt_lp else {}))
+            self.prompt_logprobs = getattr(out, "prompt_logprobs", None)
         else:
             out = self.target(self.input_ids, position_ids=self.position_ids[:, :self.n_in],
                               past_key_values=self.tcache, use_cache=True, logits_to_keep=1,
@@ -903,7 +922,7 @@ def run_decode(model, target, input_ids: torch.Tensor, *, mask_token_id: int, ma
                presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None,
                banned_token_ids=None, min_tokens: int = 0, grammar=None,
                constrain_draft: bool = False, min_p=None, couple_draft: bool = False, stop_sequences=None,
-               include_stop_sequence: bool = True) -> SimpleNamespace:
+               include_stop_sequence: bool = True, prompt_logprobs=False) -> SimpleNamespace:
     s = DecodeSession(model, target, input_ids, mask_token_id=mask_token_id, max_new_tokens=max_new_tokens,
                       max_block_size=max_block_size or block_size, stop_token_ids=stop_token_ids,
                       temperature=temperature, draft_temperature=draft_temperature,
@@ -912,7 +931,8 @@ def run_decode(model, target, input_ids: torch.Tensor, *, mask_token_id: int, ma
                       frequency_penalty=frequency_penalty, logit_bias=logit_bias, allowed_token_ids=allowed_token_ids,
                       banned_token_ids=banned_token_ids, min_tokens=min_tokens, grammar=grammar,
                       constrain_draft=constrain_draft, min_p=min_p, couple_draft=couple_draft,
-                      stop_sequences=stop_sequences, include_stop_sequence=include_stop_sequence)
+                      stop_sequences=stop_sequences, include_stop_sequence=include_stop_sequence,
+                      prompt_logprobs=prompt_logprobs)
     t_prefill = cuda_time()
     s.prefill()
     time_to_first_token = cuda_time() - t_prefill
@@ -1024,7 +1044,7 @@ def run_decode(model, target, input_ids: torch.Tensor, *, mask_token_id: int, ma
                            cycle_trace=cycle_trace, profile_summary=profile_summary, replayed_cycles=replayed,
                            replayed_flags=replayed_flags,
                            seed=s.seed, grammar_state=s.finish_grammar(output_ids), stop_sequence=s.stop_sequence,
-                           **s.finish_logprobs())
+                           prompt_logprobs=s.prompt_logprobs, **s.finish_logprobs())
 
 
 def _draft_ids(model, hid_frag, lm_wp, bs, blk, draft_temperature, keep_logits=None, seed=None, dyn=None, start=None,
@@ -1091,8 +1111,13 @@ def dflash_generate(model, target, input_ids: torch.Tensor, mask_token_id: int, 
                     logprobs: Optional[int] = None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
                     frequency_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None, banned_token_ids=None,
                     min_tokens: int = 0, grammar=None, constrain_draft: bool = False, min_p=None,
-                    couple_draft: bool = False, stop_sequences=None, include_stop_sequence: bool = True) -> SimpleNamespace:
+                    couple_draft: bool = False, stop_sequences=None, include_stop_sequence: bool = True,
+                    prompt_logprobs=False) -> SimpleNamespace:
     """benchmark.py:44-55 signature; returns the namespace of :242-251 (+ replayed_cycles).
+    prompt_logprobs (False: off, the launches of before; True needs a NativeTarget with the native prefill): the result's
+    `prompt_logprobs` is fp32 [num_input_tokens - 1], entry i the log-probability of prompt token i + 1 given tokens
+    0 .. i under the target's raw distribution — one fused lm_head + log-softmax pass over the prefill rows, no logits
+    written.  Top-N per prompt position (an integer N > 0) is NotImplementedError.  Off: None.
     stop_sequences (None: off, the launches of before; up to 8 sequences of 1..16 token ids, a bare int counting as a
     sequence of one): the request ends with the first committed token that completes one of them — matched on the device
     in front of every accept launch, over committed tokens only, across cycle boundaries, never inside the prompt and
@@ -1142,7 +1167,8 @@ def dflash_generate(model, target, input_ids: torch.Tensor, mask_token_id: int, 
                                      dict(logit_bias=logit_bias, allowed_token_ids=allowed_token_ids,
                                           banned_token_ids=banned_token_ids, min_tokens=min_tokens),
                                      constrain_draft=constrain_draft, min_p=min_p, couple_draft=couple_draft,
-                                     stop_sequences=stop_sequences, include_stop_sequence=include_stop_sequence)
+                                     stop_sequences=stop_sequences, include_stop_sequence=include_stop_sequence,
+                                     prompt_logprobs=prompt_logprobs)
     r = run_decode(model, target, input_ids, mask_token_id=mask_token_id, max_new_tokens=max_new_tokens,
                    block_size=block_size, stop_token_ids=stop_token_ids, temperature=temperature, clamp_tail=True,
                    stop_sequences=stop_sequences, include_stop_sequence=include_stop_sequence, draft_steps=draft_steps, collect_profile=collect_profile, draft_token_hook=draft_token_hook,
@@ -1150,20 +1176,21 @@ def dflash_generate(model, target, input_ids: torch.Tensor, mask_token_id: int, 
                    repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
                    frequency_penalty=frequency_penalty, logit_bias=logit_bias, allowed_token_ids=allowed_token_ids,
                    banned_token_ids=banned_token_ids, min_tokens=min_tokens, grammar=grammar,
-                   constrain_draft=constrain_draft, min_p=min_p, couple_draft=couple_draft)
+                   constrain_draft=constrain_draft, min_p=min_p, couple_draft=couple_draft, prompt_logprobs=prompt_logprobs)
     return SimpleNamespace(output_ids=r.output_ids, num_input_tokens=r.num_input_tokens,
                            num_output_tokens=r.num_output_tokens, time_to_first_token=r.time_to_first_token,
                            time_per_output_token=r.time_per_output_token, acceptance_lengths=r.acceptance_lengths,
                            cycle_trace=r.cycle_trace, profile_summary=r.profile_summary,
                            replayed_cycles=r.replayed_cycles, logprobs=r.logprobs, top_logprob_ids=r.top_logprob_ids,
-                           top_logprobs=r.top_logprobs, grammar_state=r.grammar_state, stop_sequence=r.stop_sequence)
+                           top_logprobs=r.top_logprobs, grammar_state=r.grammar_state, stop_sequence=r.stop_sequence,
+                           prompt_logprobs=r.prompt_logprobs)
 
 
 def _generate_wide_hidden(model, target, input_ids, mask_token_id, max_new_tokens, block_size, stop_token_ids, temperature,
                           collect_profile=False, draft_steps=1, draft_token_hook=None, sampler="torch",
                           seed=None, top_k=0, top_p=1.0, logprobs=None, penalties=(1.0, 0.0, 0.0),
                           bias=None, constrain_draft=False, min_p=None, couple_draft=False, stop_sequences=None,
-                          include_stop_sequence=True) -> SimpleNamespace:
+                          include_stop_sequence=True, prompt_logprobs=False) -> SimpleNamespace:
     """hidden_size > 4096: the request runs as a group of ONE through the ragged-batch kernels (their GEMMs cut K over
     workgroups; the single-request kernels keep a whole K = hidden row slice per workgroup).  Same loop semantics
     (benchmark.py:44-251, tail clamp included); no per-cycle profile, one draft step per cycle."""
@@ -1181,7 +1208,8 @@ def _generate_wide_hidden(model, target, input_ids, mask_token_id, max_new_token
                                  repetition_penalty=penalties[0], presence_penalty=penalties[1],
                                  frequency_penalty=penalties[2], **_one_prompt_bias(bias),
                                  constrain_draft=constrain_draft, min_p=min_p, couple_draft=couple_draft,
-                                 stop_sequences=stop_sequences, include_stop_sequence=include_stop_sequence)[0]
+                                 stop_sequences=stop_sequences, include_stop_sequence=include_stop_sequence,
+                                 prompt_logprobs=prompt_logprobs)[0]
 
 
 def _one_prompt_bias(bias) -> dict:
@@ -1201,8 +1229,9 @@ def dflash_generate_policy(*, model, target, input_ids: torch.Tensor, mask_token
                            frequency_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None, banned_token_ids=None,
                            min_tokens: int = 0, grammar=None, constrain_draft: bool = False,
                            min_p=None, couple_draft: bool = False, stop_sequences=None,
-                           include_stop_sequence: bool = True) -> SimpleNamespace:
+                           include_stop_sequence: bool = True, prompt_logprobs=False) -> SimpleNamespace:
     """benchmark_dynamic_schedule.py:260-272 signature; returns the namespace of :425-434 (+ replayed_cycles).
+    prompt_logprobs: as dflash_generate (the field `prompt_logprobs`; None when off).
     stop_sequences / include_stop_sequence: as dflash_generate (the field `stop_sequence`).
     couple_draft: as dflash_generate; here it REPLACES this loop's own draw on the DRAFT stream (whose acceptance,
     sum p_i q_i, is the lowest of the three drafts), and constrain_draft then works at T > 0.
@@ -1227,7 +1256,7 @@ def dflash_generate_policy(*, model, target, input_ids: torch.Tensor, mask_token
                    logprobs=logprobs, repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
                    frequency_penalty=frequency_penalty, logit_bias=logit_bias, allowed_token_ids=allowed_token_ids,
                    banned_token_ids=banned_token_ids, min_tokens=min_tokens, grammar=grammar,
-                   constrain_draft=constrain_draft, min_p=min_p, couple_draft=couple_draft)
+                   constrain_draft=constrain_draft, min_p=min_p, couple_draft=couple_draft, prompt_logprobs=prompt_logprobs)
     if fixed_block_size is not None:
         for row in r.cycle_trace:
             for k in ("tau_hat", "cycle_hat", "score_hat", "current_block_size", "adl_lgen_hat", "adl_lacc_hat",
@@ -1238,7 +1267,8 @@ def dflash_generate_policy(*, model, target, input_ids: torch.Tensor, mask_token
                            time_per_output_token=r.time_per_output_token, acceptance_lengths=r.acceptance_lengths,
                            used_block_sizes=r.used_block_sizes, cycle_trace=r.cycle_trace,
                            replayed_cycles=r.replayed_cycles, logprobs=r.logprobs, top_logprob_ids=r.top_logprob_ids,
-                           top_logprobs=r.top_logprobs, grammar_state=r.grammar_state, stop_sequence=r.stop_sequence)
+                           top_logprobs=r.top_logprobs, grammar_state=r.grammar_state, stop_sequence=r.stop_sequence,
+                           prompt_logprobs=r.prompt_logprobs)
 
 
 class _Fixed:

@@ -14,7 +14,7 @@ from __future__ import annotations
 
 import json
 import os
-from typing import Optional
+from typing import Optional, Tuple, Union
 
 import torch
 
@@ -744,12 +744,15 @@ class DFlashDraftModel:
                       allowed_token_ids=None, banned_token_ids=None, min_tokens: int = 0,
                       grammar=None, constrain_draft: bool = False, min_p=None,
                       couple_draft: bool = False, stop_sequences=None,
-                      include_stop_sequence: bool = True) -> torch.LongTensor:
+                      include_stop_sequence: bool = True,
+                      prompt_logprobs=False) -> Union[torch.LongTensor, Tuple[torch.LongTensor, torch.Tensor]]:
         """model/dflash.py:192-277.  sampler / seed / top_k / top_p: as dflash_generate; min_p
         likewise (section 18);
         repetition_penalty / presence_penalty / frequency_penalty likewise (section 13); logit_bias / allowed_token_ids /
         banned_token_ids / min_tokens likewise (section 14); grammar and constrain_draft likewise (section 15); couple_draft likewise
-        (section 20); stop_sequences / include_stop_sequence likewise (section 22; any target, native or wrapped)."""
+        (section 20); stop_sequences / include_stop_sequence likewise (section 22; any target, native or wrapped).
+        prompt_logprobs=True (section 23; a NativeTarget): returns (output_ids, prompt_logprobs fp32 [P - 1]) instead of
+        the ids alone."""
         bias = dict(logit_bias=logit_bias, allowed_token_ids=allowed_token_ids, banned_token_ids=banned_token_ids,
                     min_tokens=min_tokens)
         pen = dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
@@ -758,17 +761,18 @@ class DFlashDraftModel:
         if self.wide_hidden:    # (ids are the same with or without the harness form's tail clamp)
             if grammar is not None:
                 raise NotImplementedError("grammar: hidden_size > 4096 runs through the ragged batch, which takes no grammar")
-            return _generate_wide_hidden(self, target, input_ids, self.mask_token_id, max_new_tokens, self.block_size,
+            r = _generate_wide_hidden(self, target, input_ids, self.mask_token_id, max_new_tokens, self.block_size,
                                          stop_token_ids, temperature, draft_token_hook=draft_token_hook, sampler=sampler,
                                          seed=seed, top_k=top_k, top_p=top_p,
                                          penalties=tuple(pen.values()), bias=bias,
                                          constrain_draft=constrain_draft, min_p=min_p,
                                          couple_draft=couple_draft, stop_sequences=stop_sequences,
-                                         include_stop_sequence=include_stop_sequence).output_ids
+                                         include_stop_sequence=include_stop_sequence, prompt_logprobs=prompt_logprobs)
+            return (r.output_ids, r.prompt_logprobs) if r.prompt_logprobs is not None else r.output_ids
         r = run_decode(self, target, input_ids, mask_token_id=self.mask_token_id, max_new_tokens=max_new_tokens,
                        block_size=self.block_size, stop_token_ids=stop_token_ids, temperature=temperature,
                        clamp_tail=False, draft_token_hook=draft_token_hook, sampler=sampler, seed=seed, top_k=top_k,
                        top_p=top_p, **pen, **bias, grammar=grammar, constrain_draft=constrain_draft, min_p=min_p,
                        couple_draft=couple_draft, stop_sequences=stop_sequences,
-                       include_stop_sequence=include_stop_sequence)
-        return r.output_ids
+                       include_stop_sequence=include_stop_sequence, prompt_logprobs=prompt_logprobs)
+        return (r.output_ids, r.prompt_logprobs) if r.prompt_logprobs is not None else r.output_ids

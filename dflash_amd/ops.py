@@ -2254,6 +2254,56 @@ def prefill_attn(qkv: torch.Tensor, P: int, q_col: int, kcache, vcache, n_q: int
           "dfl_prefill_attn")
 
 
+# ---- prompt logprobs (csrc/prompt_logprobs.hip)
+def check_prompt_logprobs(prompt_logprobs) -> bool:
+    """The `prompt_logprobs` keyword of prefill / the generate entry points: False / None / 0 is off, True is on (the
+    scored token's log-probability per prompt position); top-N alternatives per prompt position (an integer N > 0, or
+    anything above 1) are not built."""
+    if prompt_logprobs is None or prompt_logprobs is False or (type(prompt_logprobs) is int and prompt_logprobs == 0):
+        return False
+    if prompt_logprobs is True:
+        return True
+    if isinstance(prompt_logprobs, int):
+        raise NotImplementedError(f"dflash_amd: prompt_logprobs={prompt_logprobs!r}: top-N alternatives per prompt position "
+                                  "are not supported; pass prompt_logprobs=True for the prompt tokens' own log-probabilities")
+    raise ValueError(f"dflash_amd: prompt_logprobs must be a bool, got {prompt_logprobs!r}")
+
+
+def prefill_logprobs_nsplit(rows: int, V: int) -> int:
+    """Strips of 128-column blocks per 128-row block: the grid fills 256 CUs at two workgroups each (512 workgroups over
+    the row blocks), at least one column block per strip."""
+    nrb, ncb = (rows + 127) // 128, (V + 127) // 128
+    return max(1, min(ncb, 512 // nrb))
+
+
+_plp_ws: dict = {}   # device -> the partials of prefill_logprobs (grown, never shrunk; stream-ordered like every scratch here)
+
+
+def prefill_logprobs(wp, xf, rows: int, V: int, K: int, targets: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[m] = log_softmax(bf16(x[m] . W^T))[targets[m]] for m < rows (dfl_prefill_logprobs): wp the packed bf16 head
+    [V, K], xf the final-normed rows as frag16 tiles (prefill_norm_pack), targets int64 [>= rows].  fp32 [rows]; NaN
+    where a target is outside [0, V).  No logits are written: the workspace is 16 bytes per (row, strip)."""
+    if rows < 1 or V <= 0 or V % 16 or K <= 0 or K % 64:
+        raise ValueError(f"dflash_amd: prefill_logprobs needs rows >= 1, V % 16 == 0, K % 64 == 0 (rows={rows} V={V} K={K})")
+    Pp = (rows + 127) // 128 * 128
+    if wp.numel() != V * K or xf.numel() < Pp * K:
+        raise ValueError(f"dflash_amd: prefill_logprobs: wp holds {wp.numel()} values (V*K = {V * K}), x_frag {xf.numel()} "
+                         f"(needs {Pp * K})")
+    if targets.dtype != I64 or targets.dim() != 1 or targets.numel() < rows:
+        raise TypeError("dflash_amd: targets must be an int64 vector of at least `rows` ids")
+    if out is None:
+        out = torch.empty(rows, dtype=F32, device=xf.device)
+    if out.numel() < rows:
+        raise ValueError("dflash_amd: out holds fewer than `rows` values")
+    nsplit = prefill_logprobs_nsplit(rows, V)
+    ws = _plp_ws.get(xf.device)
+    if ws is None or ws.numel() < nsplit * Pp * 4:
+        ws = _plp_ws[xf.device] = torch.empty(nsplit * Pp * 4, dtype=F32, device=xf.device)
+    check(lib().dfl_prefill_logprobs(_p(wp, BF16, "wp"), _p(xf, BF16, "x_frag"), rows, V, K, _p(targets, I64, "targets"),
+                                     nsplit, _p(ws, F32, "ws"), _p(out, F32, "out"), _stream()), "dfl_prefill_logprobs")
+    return out
+
+
 # ---- sparse-MoE MLP of the prefill (csrc/prefill.hip: k_pmoe_*, the grouped k_pgemm) ----------------------------
 def prefill_moe_scratch(P: int, H: int, I: int, E: int, top_k: int, router_cols: int, device) -> dict:
     """Caller-owned scratch of dfl_prefill_moe_* for P prompt rows (sizes in include/dflash_hip.h)."""

@@ -597,18 +597,35 @@ class NativeTarget:
     # ---- prefill (model/dflash.py:218-225)
     @torch.inference_mode()
     def prefill(self, input_ids: torch.Tensor, cache: TargetKVCache, output_hidden_states: bool = True,
-                tap_layers: Optional[Sequence[int]] = None):
+                tap_layers: Optional[Sequence[int]] = None, prompt_logprobs=False):
         """Returns an object with `.logits` [1, 1, V] (last prompt row, logits_to_keep = 1) and `.hidden_states`
         (indexable like HF's tuple).  tap_layers: keep only hidden_states[l + 1] for these layers (the draft's taps,
-        model/utils.py:16-25) instead of all of them."""
+        model/utils.py:16-25) instead of all of them.
+        prompt_logprobs=True (the native prefill only): the object gains `.prompt_logprobs`, fp32 [P - 1] — entry i is the
+        log-probability of prompt token i + 1 given tokens 0 .. i under the raw distribution (T = 1, unfiltered; HF's
+        logits[:, :-1].log_softmax(-1) gathered at input_ids[:, 1:]), from one fused lm_head + log-softmax pass that
+        writes no logits.  An fp8 / mxfp4 target scores with the bf16 copy of its head: the
+        quantised model's own values."""
         P = input_ids.shape[1]
         if P > cache.max_rows:
             raise ValueError("target KV cache too small for the prompt")
+        plp = ops.check_prompt_logprobs(prompt_logprobs)
+        if plp and not self.native_prefill:
+            raise ValueError("prompt_logprobs needs the native prefill: this target runs the wrapped model's forward "
+                             "(prefill='hf', or widths the prefill kernels do not take)")
         if self.native_prefill:
-            return self._prefill_native(input_ids, cache, output_hidden_states, tap_layers)
+            return self._prefill_native(input_ids, cache, output_hidden_states, tap_layers, plp)
         return self._prefill_hf(input_ids, cache, output_hidden_states)
 
-    def _prefill_native(self, input_ids, cache, output_hidden_states, tap_layers):
+    @torch.inference_mode()
+    def score(self, input_ids: torch.Tensor, cache: Optional[TargetKVCache] = None) -> torch.Tensor:
+        """Log-probabilities of a text under the target, fp32 [P - 1] (prefill(..., prompt_logprobs=True) and nothing
+        else: no taps kept): perplexity, ranking the continuations of a multiple-choice item."""
+        if cache is None:
+            cache = self.new_cache(input_ids.shape[1])
+        return self.prefill(input_ids, cache, output_hidden_states=False, prompt_logprobs=True).prompt_logprobs
+
+    def _prefill_native(self, input_ids, cache, output_hidden_states, tap_layers, prompt_logprobs=False):
         """The prompt rows on the kernels: per layer RMSNorm -> frag16 tiles, q/k/v GEMM (bf16 rows), q/k-norm + RoPE +
         cache write, causal attention over the prompt (k_pattn: one wave per head and 16-row query tile), o_proj +
         residual, RMSNorm, gate/up + SiLU,
@@ -691,7 +708,18 @@ class NativeTarget:
         # (hidden_states[L], HF's final-normed state, is not kept: nothing on the path reads it — model/utils.py:16-25
         # taps layer OUTPUTS, and build_target_layer_ids never picks the last layer)
         cache.length = P
-        return SimpleNamespace(logits=logits, hidden_states=_HiddenStates(kept, self.L + 1) if output_hidden_states else None)
+        out = SimpleNamespace(logits=logits, hidden_states=_HiddenStates(kept, self.L + 1) if output_hidden_states else None)
+        return self._prompt_logprobs(out, input_ids, h, xf) if prompt_logprobs else out
+
+    def _prompt_logprobs(self, out, input_ids, h, xf):
+        """out.prompt_logprobs from the prefill's final residual rows h: final norm -> frag16 tiles, then rows 0 .. P - 2
+        against the tokens that follow them through the head without a logit written.  P == 1: empty, no launch."""
+        P = input_ids.shape[1]
+        out.prompt_logprobs = torch.empty(P - 1, dtype=torch.float32, device=self._dev)
+        if P > 1:
+            ops.prefill_norm_pack(h, P, self.H, self.norm, self.eps, xf)
+            ops.prefill_logprobs(self.lm_wp, xf, P - 1, self.V, self.H, input_ids[0, 1:].contiguous(), out.prompt_logprobs)
+        return out
 
     def _prefill_hf(self, input_ids, cache, output_hidden_states):
         """Through the wrapped model, K/V copied into the preallocated cache (odd widths, prefill="hf")."""

@@ -793,6 +793,20 @@ int dfl_prefill_qk_rope(void *qkv_rows, int64_t ld, int P, int q_col, int k_col,
 int dfl_prefill_attn(const void *q_rows, int64_t ldq, int q_col, const void *kcache, const void *vcache, int cache_rows,
                      int P, int n_q, int n_kv, float scale, void *out_frag, void *stream);
 
+/* Prompt logprobs: the lm_head over `rows` prefill rows with a log-softmax epilogue; no logit is
+ * ever written.  wp_head: the packed head [V/16][K/32][64][8] (dfl_pack_weight); x_frag: the final-normed rows as frag16
+ * tiles, dfl_prefill_rows_padded(rows) / 16 of them (what dfl_prefill_norm_pack writes); targets int64 [rows].
+ *   z_m[v] = float(bf16(sum_k W[v][k] x[m][k]))      fp32 MFMA sums, ONE rounding: the logit the head launches materialise
+ *   out[m] = z_m[targets[m]] - ln(sum_v exp(z_m[v]))   fp32, T = 1, raw and unfiltered (dfl_logprob_rows's definition)
+ * for m < rows; NaN where targets[m] is outside [0, V); out[m] for m >= rows is not written (out: float [rows]).
+ * Two launches: the strips (each 128-row block x each of nsplit strips of 128-column blocks keeps a running maximum and
+ * sum per row) and the finish over the partials.  ws: float [nsplit][dfl_prefill_rows_padded(rows)][4] = (maximum, sum
+ * of exp(z - maximum), target logit or -inf, 0) per (strip, row), 16-byte aligned; every element is written before it is
+ * read.  1 <= nsplit <= ceil(V / 128).  V % 16 == 0, K % 64 == 0, rows >= 1; anything else returns DFL_EINVAL and
+ * launches nothing. */
+int dfl_prefill_logprobs(const void *wp_head, const void *x_frag, int rows, int V, int K, const int64_t *targets, int nsplit,
+                         float *ws, float *out, void *stream);
+
 /* Sparse-MoE MLP of the prefill: Qwen3MoeSparseMoeBlock over the P prompt rows of one layer of an MoE target
  * (tf:models/qwen3_moe/modeling_qwen3_moe.py: Qwen3MoeTopKRouter.forward + Qwen3MoeExperts.forward; the reference
  * reaches it through the HF forward of model/dflash.py:218-225, a Python loop over the experts).  The layer's
