@@ -31,7 +31,7 @@ from .generate import (NO_LOGPROBS, _bf16_table, _draw_rows, _kept_cols, _stop_h
                        cuda_time, check_prompt_logprobs, logprob_fields, resolve_seed)
 from .logits_stage import LogitsStage, check_features
 from .model import DFlashDraftModel
-from .target import NativeTarget
+from .target import NativeTarget, refuse_kv_format
 from .tile_stack import TileStack, gemm_ws
 from .utils import sample
 
@@ -79,6 +79,7 @@ class BatchedDecoder:
         slot's draft token j is picked under the noise the verify draws that position with.  The
         bf16 lm_head for this launch, also in an fp8 draft.  With constrain_draft the pick is the noise form.  A decoder
         in which nothing samples enqueues the launches of before."""
+        refuse_kv_format(target, "BatchedDecoder")
         logprobs = ops.check_logprobs(logprobs)
         draft_temperature = check_couple_draft(couple_draft, temperature, draft_temperature if draft_temperature >= 1e-5
                                                else None, sampler)

@@ -13,8 +13,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libdflash_hip.so")
-SOURCES = ["dfl_common.hip", "gemm_skinny.hip", "gemm_batch.hip", "gemm_batch_w4.hip", "rows.hip", "attn_block.hip", "attn_head.hip", "accept.hip", "nucleus.hip", "logprobs.hip", "penalties.hip", "logit_bias.hip", "min_p.hip", "grammar.hip", "grammar_draft.hip", "grammar_lift.hip", "stop_seq.hip", "candidates.hip", "moe.hip", "moe_w4.hip", "moe_w4_shared.hip", "prefill.hip", "prompt_logprobs.hip"]
-HEADERS = [os.path.join(CSRC, "dfl_common.h"), os.path.join(CSRC, "dfl_rng.h"), os.path.join(CSRC, "gemm_rows.h"), os.path.join(CSRC, "gemm_ring.h"), os.path.join(CSRC, "moe_route.h"),
+SOURCES = ["dfl_common.hip", "gemm_skinny.hip", "gemm_batch.hip", "gemm_batch_w4.hip", "rows.hip", "attn_block.hip", "attn_head.hip", "attn_head_kv8.hip", "accept.hip", "nucleus.hip", "logprobs.hip", "penalties.hip", "logit_bias.hip", "min_p.hip", "grammar.hip", "grammar_draft.hip", "grammar_lift.hip", "stop_seq.hip", "candidates.hip", "moe.hip", "moe_w4.hip", "moe_w4_shared.hip", "prefill.hip", "prompt_logprobs.hip"]
+HEADERS = [os.path.join(CSRC, "dfl_common.h"), os.path.join(CSRC, "dfl_rng.h"), os.path.join(CSRC, "gemm_rows.h"), os.path.join(CSRC, "attn_head.h"), os.path.join(CSRC, "gemm_ring.h"), os.path.join(CSRC, "moe_route.h"),
            os.path.join(HERE, "..", "include", "dflash_hip.h")]
 # kernarg preload: gfx950 delivers up to 14 leading scalar / pointer kernel arguments in SGPRs at wave start (the hot
 # kernels keep what their first memory request needs there: csrc/gemm_skinny.hip, "the head of the launch arguments").

@@ -210,9 +210,10 @@ class NativeCandidateVerifier:
     MT = 4
 
     def __init__(self, target, n_taps: int, max_splits: int = 32):
-        from .target import NativeTarget
+        from .target import NativeTarget, refuse_kv_format
         if not isinstance(target, NativeTarget):
             raise TypeError("NativeCandidateVerifier needs a dflash_amd.NativeTarget")
+        refuse_kv_format(target, "NativeCandidateVerifier")
         t, MT = target, self.MT
         self.t, self.max_splits = t, max_splits
         dev = t.device

@@ -15,6 +15,7 @@ from typing import Callable, Optional, Sequence, Union
 import torch
 
 from . import ops
+from .target import refuse_kv_format
 from .batch import (MAX_GROUP, BatchedDecoder, _load_grammars, _pool_rows, _prompt_bias, _prompt_filters,
                     _prompt_grammars, _prompt_min_p, _prompt_penalties, _prompt_seeds, _prompt_stop_sequences,
                     _prompt_temperatures)
@@ -154,6 +155,7 @@ class BatchEngine:
         address is fixed, so the one capture serves grammars loaded later; results carry `grammar_state`.
         request_temperature: greedy and sampled requests share the weight pass and the capture; needs sampler='device';
         `temperature` is then the default of submit."""
+        refuse_kv_format(target, "BatchEngine")
         if not 1 <= block_size <= 32:
             raise ValueError("block_size is 1..32")
         if block_size > BLOCK_ROWS:

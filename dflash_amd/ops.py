@@ -1614,6 +1614,58 @@ def attn_head(*, xq: torch.Tensor, q_col: int, k_col: int, v_col: int, n_q: int,
         _p(out_frag, BF16, "out_frag"), out_tile_stride, _stream()), "dfl_attn_head")
 
 
+# ---- e4m3 KV cache (csrc/attn_head_kv8.hip, DESIGN.md section 24)
+KV_FORMATS = ("bf16", "fp8_e4m3")
+
+
+def quantize_kv_rows(x: torch.Tensor):
+    """[..., 128] post-norm, post-RoPE K or V rows -> (codes uint8 [..., 128], scale fp32 [...]): quantize_fp8_rows' rule
+    per row — scale = 2^ceil(log2(amax / 448)), 1 for an all-zero row — with the scale kept at 2^-64 or above, codes the
+    round-to-nearest-even of x / scale.  dequantize_kv_rows of the result is exact in bf16, and quantising that again
+    returns the same codes and scales."""
+    q, scale = quantize_fp8_rows(x.reshape(-1, x.shape[-1]))
+    low = scale < 2.0 ** -64
+    if bool(low.any()):   # (|x| / 2^-64 <= 448 there: no clamp needed)
+        scale = torch.where(low, torch.full_like(scale, 2.0 ** -64), scale)
+        q = torch.where(low[:, None], (x.reshape(q.shape).float() / scale[:, None]).to(torch.float8_e4m3fn).view(U8), q)
+    return q.view(x.shape), scale.view(x.shape[:-1])
+
+
+def dequantize_kv_rows(q: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """codes * scale as bf16 [..., 128]: what every attention of a kv_format="fp8_e4m3" target sees."""
+    return (q.view(torch.float8_e4m3fn).float() * scale[..., None].float()).to(BF16)
+
+
+def _kv8(kcodes, vcodes, k_scale, v_scale):
+    assert kcodes.shape == vcodes.shape and kcodes.dim() == 3 and kcodes.shape[2] == 128
+    assert k_scale.shape == v_scale.shape == kcodes.shape[:2]
+    return _p(kcodes, U8, "kcodes"), _p(vcodes, U8, "vcodes"), _p(k_scale, F32, "k_scale"), _p(v_scale, F32, "v_scale")
+
+
+def kv_quant_rows(k_rows: torch.Tensor, v_rows: torch.Tensor, P: int, kcodes, vcodes, k_scale, v_scale, row0: int) -> None:
+    """One layer's bf16 K and V rows [n_kv, >= P, 128] -> codes and scales at cache rows [row0, row0 + P) of
+    kcodes / vcodes uint8 [n_kv, rows, 128] and k_scale / v_scale fp32 [n_kv, rows]; the rows become code * scale in place."""
+    assert k_rows.shape == v_rows.shape and k_rows.dim() == 3 and k_rows.shape[2] == 128 and k_rows.shape[0] == kcodes.shape[0]
+    check(lib().dfl_kv_quant_rows(_p(k_rows, BF16, "k_rows"), _p(v_rows, BF16, "v_rows"), k_rows.shape[1], P, k_rows.shape[0],
+                                  *_kv8(kcodes, vcodes, k_scale, v_scale), kcodes.shape[1], row0, _stream()), "dfl_kv_quant_rows")
+
+
+def attn_head_kv8(*, xq: torch.Tensor, q_col: int, k_col: int, v_col: int, n_q: int, n_kv: int, q_norm_w, k_norm_w, eps,
+                  cos_tab, sin_tab, kcache, vcache, k_scale, v_scale, scale: float, causal: bool, S: int, bs: int, pos0: int,
+                  ws, max_splits: int, out_frag: torch.Tensor, tau: int = 0, dyn: Optional[torch.Tensor] = None,
+                  q_tiles: int = 1, out_tile_stride: int = 0) -> None:
+    """attn_head over an e4m3 cache: kcache / vcache uint8 [n_kv, rows, 128] codes, k_scale / v_scale fp32 [n_kv, rows]
+    (rows % 4 == 0).  No context rows."""
+    assert xq.is_cuda and xq.dtype == BF16 and xq.dim() == 2 and xq.stride(1) == 1 and xq.shape[0] >= min(bs, 16 * q_tiles)
+    if tau != 0:
+        raise ValueError("attn_head_kv8 takes no context rows (tau must be 0)")
+    check(lib().dfl_attn_head_kv8(
+        xq.data_ptr(), xq.stride(0), q_col, k_col, v_col, n_q, n_kv, _p(q_norm_w, BF16, "q_norm_w"),
+        _p(k_norm_w, BF16, "k_norm_w"), eps, _p(cos_tab, BF16, "cos"), _p(sin_tab, BF16, "sin"), cos_tab.shape[0],
+        *_kv8(kcache, vcache, k_scale, v_scale), kcache.shape[1], scale, int(causal), _p(dyn, I32, "dyn"), S, bs, pos0,
+        q_tiles, _p(ws), max_splits, _p(out_frag, BF16, "out_frag"), out_tile_stride, _stream()), "dfl_attn_head_kv8")
+
+
 ATTN_OPROJ_SYNC_WORDS = 1056   # DFL_ATTN_OPROJ_SYNC_WORDS: 32 counter replicas on their own lines + bookkeeping
 ATTN_OPROJ_FAIL_WORD = 1025
 

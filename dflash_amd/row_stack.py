@@ -64,7 +64,8 @@ class RowStack:
         """The layers over the block's `bs` rows in h (embedded, their sums of squares in ss_emb).  tiles: [(t, the
         tile's length record)].  Returns the row sources of the final-normed rows, one per tile.
         attn: what the attention launch takes per call — cos_tab, sin_tab, kcache / vcache (indexed by layer here),
-        causal, S, tau, pos0, dyn (or None) and, for the draft, xc: the context rows' K/V of all layers (or None).
+        causal, S, tau, pos0, dyn (or None) and, for the draft, xc: the context rows' K/V of all layers (or None); a
+        target with an e4m3 cache adds k_scale / v_scale (indexed by layer), and the launch is ops.attn_head_kv8.
         fuse_oproj: attention + o_proj in one launch where its range allows (one tile, q_dim <= 4096).
         attend(i, lw, x1): the round-1 "fused" stage in place of q/k/v + attention, from the sources x1 to frag16 rows
         in attn[0].
@@ -95,7 +96,10 @@ class RowStack:
                           vcache=attn["vcache"][i])
                 if xc is not None:
                     kw.update(xc=xc, ck_col=i * 2 * self.kv_dim, cv_col=i * 2 * self.kv_dim + self.kv_dim)
-                if fuse_o:
+                if "k_scale" in attn:
+                    ops.attn_head_kv8(**kw, k_scale=attn["k_scale"][i], v_scale=attn["v_scale"][i], out_frag=self.attn,
+                                      q_tiles=len(tiles), out_tile_stride=self.attn.stride(0))
+                elif fuse_o:
                     ops.attn_head_oproj(**kw, attn_frag=self.attn[0], wo=lw["o"], H=H, h_io=hs[0], ss_out=self.ss_h[0],
                                         sync=self.sync)
                 else:

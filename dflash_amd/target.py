@@ -34,11 +34,24 @@ BF16 = torch.bfloat16
 
 
 class TargetKVCache:
-    """Preallocated target KV: [layer][kv head][rows][128] bf16; crop = counter."""
+    """Preallocated target KV: [layer][kv head][rows][128] bf16; crop = counter.
+    kv_format="fp8_e4m3": k / v hold OCP e4m3 codes (uint8, same shape) and k_scale / v_scale one power-of-two fp32 scale
+    per [layer][kv head][row] (ops.quantize_kv_rows; 264 bytes per row and head instead of 512); the tensors' row count
+    is max_rows rounded up to a multiple of 4 (the attention stage loads four rows' scales at a time)."""
 
-    def __init__(self, n_layers, n_kv, max_rows, device):
+    def __init__(self, n_layers, n_kv, max_rows, device, kv_format: str = "bf16"):
+        if kv_format not in ops.KV_FORMATS:
+            raise ValueError(f"TargetKVCache: kv_format must be one of {ops.KV_FORMATS}, got {kv_format!r}")
         self.max_rows = int(max_rows)
-        self.k = torch.zeros(n_layers, n_kv, self.max_rows, 128, dtype=BF16, device=device)
+        self.kv_format = kv_format
+        self.k_scale = self.v_scale = None
+        if kv_format == "fp8_e4m3":
+            rows = (self.max_rows + 3) // 4 * 4
+            self.k = torch.zeros(n_layers, n_kv, rows, 128, dtype=torch.uint8, device=device)
+            self.k_scale = torch.ones(n_layers, n_kv, rows, dtype=torch.float32, device=device)
+            self.v_scale = torch.ones_like(self.k_scale)
+        else:
+            self.k = torch.zeros(n_layers, n_kv, self.max_rows, 128, dtype=BF16, device=device)
         self.v = torch.zeros_like(self.k)
         self.dyn = torch.zeros(16, dtype=torch.int32, device=device)   # one length record per 16-row block tile
         self.length = 0
@@ -84,11 +97,32 @@ class Mxfp4TargetRefused(NotImplementedError, ValueError):
     that catches either kind sees it.  (Until the dense target took the format, every config got the ValueError.)"""
 
 
+def refuse_kv_format(target, who: str) -> None:
+    """The paths that read a target's cache through kernels without an e4m3 form refuse a kv_format target by name."""
+    if getattr(target, "kv8", False):
+        raise NotImplementedError(f"{who}: a NativeTarget(kv_format='fp8_e4m3') is not supported here (the ragged-batch and "
+                                  f"candidate attention stages read a bf16 cache); use dflash_generate / DecodeSession")
+
+
 class NativeTarget:
+    kv_format, kv8 = "bf16", False   # (the cache format; set per instance by __init__)
+
     def __init__(self, hf_model, max_splits: int = 32, attn_impl: str = "head", keep_hf: bool = True,
                  prefill: str = "native", weight_format: str = "bf16", expert_format: str = "bf16",
-                 stream_format: str = "auto"):
-        """stream_format: "auto" (default): a bf16 target's verify of <= 16 block rows streams each dense layer's gate/up
+                 stream_format: str = "auto", kv_format: str = "bf16"):
+        """kv_format: "bf16" (default), or "fp8_e4m3": the target's KV cache holds OCP e4m3 codes with one power-of-two
+        fp32 scale per (row, kv head), K and V separately (ops.quantize_kv_rows on the post-norm, post-RoPE rows; 264
+        bytes per row and head instead of 512).  The quantised-KV target IS the model: every attention it runs — the
+        prefill, the verify over cached rows and over the block's own new rows — sees exactly code * scale, so its
+        outputs do not depend on how the tokens were cut into prefill and blocks, and a speculative run emits what this
+        target alone emits.  The prefill goes through a one-layer bf16 scratch and dfl_kv_quant_rows, the verify through
+        dfl_attn_head_kv8 (blocks of 17..32 rows in one pass or two).  Needs the native prefill and
+        attn_impl="head" (refused here); fuse_oproj and prefill_attn="sdpa" are attributes set after construction, so
+        they are refused where they would act — by verify() and prefill(); BatchedDecoder, BatchEngine and
+        NativeCandidateVerifier refuse such a target when they are built.  The draft's
+        own cache stays bf16.  What e4m3 K/V does to a real checkpoint's outputs or to a trained draft's acceptance
+        length is NOT measured — off by default.
+        stream_format: "auto" (default): a bf16 target's verify of <= 16 block rows streams each dense layer's gate/up
         and, at temperature 0, the lm_head from a lossless 13-bit copy (ops.pack_weight_bf16x13)
         wherever the layout covers the shape (hidden 2048 or 4096) and the packer takes the matrix: the same bits out,
         13/16 of the bytes in.  The plain packed weights stay resident for every other path (prefill, wide blocks, the
@@ -168,9 +202,14 @@ class NativeTarget:
         self.moe_shared_min = 2       # tiles from which the shared pass is taken (30B-A3B layer: 2 tiles 291 -> 216 us, 4: 576 -> 241)
         self._moe_sh = None
         cfg = hf_model.config
-        self.check_config(cfg, weight_format, expert_format)   # (before anything touches the device: a rejected architecture never launches a kernel)
+        self.check_config(cfg, weight_format, expert_format, kv_format=kv_format)   # (before anything touches the device: a rejected architecture never launches a kernel)
         self.weight_format = weight_format
         self.expert_format = expert_format
+        self.kv_format = kv_format
+        self.kv8 = kv_format == "fp8_e4m3"
+        if self.kv8 and attn_impl != "head":
+            raise NotImplementedError("NativeTarget: kv_format='fp8_e4m3' with attn_impl='fused' is not implemented (the "
+                                      "round-1 stage reads a bf16 cache)")
         fp8 = weight_format == "fp8_e4m3"
         e8 = expert_format == "fp8_e4m3"
         # fp8 experts only: False = the bf16 expert kernels on the dequantised copy (the second implementation the tests compare)
@@ -377,6 +416,9 @@ class NativeTarget:
         dense_ok = all("gu_e" in lw for lw in self.layers) or self.I % 64 == 0   # (a dense MLP layer needs I % 64)
         self.native_prefill = (prefill == "native" and (q_dim + 2 * kv_dim) % 128 == 0 and self.H % 128 == 0 and dense_ok
                                and q_dim % 64 == 0 and (not self.is_moe or self.Ie % 64 == 0))
+        if self.kv8 and not self.native_prefill:
+            raise NotImplementedError("NativeTarget: kv_format='fp8_e4m3' needs the native prefill (prefill='native', widths "
+                                      "% 128, FFN widths % 64): the wrapped model's forward attends unquantised K/V")
         self.prefill_attn = "native"   # "sdpa": the causal attention core of the prefill through torch (round-3 first form)
         self._rotary = getattr(hf_model.model, "rotary_emb", None)
         if not keep_hf:
@@ -398,7 +440,7 @@ class NativeTarget:
         torch.cuda.synchronize(dev)
 
     @staticmethod
-    def check_config(cfg, weight_format: str = "bf16", expert_format: str = "bf16") -> None:
+    def check_config(cfg, weight_format: str = "bf16", expert_format: str = "bf16", *, kv_format: str = "bf16") -> None:
         """Architectures the kernels do not cover are rejected loudly, before any launch (the reference is shape-agnostic:
         model/dflash.py:36,42-56 take head_dim, attention_bias and sliding_window from the config; no BASELINE config
         needs them): head_dim != 128, biased projections, sliding-window attention layers, a sparse-MoE target (num_experts)
@@ -408,7 +450,10 @@ class NativeTarget:
         a sparse-MoE target the same way, pointing at expert_format, and those widths where they are missing or no
         multiples of 128 — with Mxfp4TargetRefused, a NotImplementedError that is a ValueError too, checked with the name.
         expert_format: an unknown one is a ValueError; "fp8_e4m3" needs a sparse-MoE config (num_experts) whose hidden_size
-        and moe_intermediate_size are multiples of 64; "mxfp4" one whose two widths are multiples of 128 (a 4-k-step word)."""
+        and moe_intermediate_size are multiples of 64; "mxfp4" one whose two widths are multiples of 128 (a 4-k-step word).
+        kv_format: an unknown one is a ValueError."""
+        if kv_format not in ops.KV_FORMATS:
+            raise ValueError(f"NativeTarget: kv_format must be one of {ops.KV_FORMATS}, got {kv_format!r}")
         if weight_format not in WEIGHT_FORMATS:
             raise ValueError(f"NativeTarget: weight_format must be one of {WEIGHT_FORMATS}, got {weight_format!r}")
         if expert_format not in EXPERT_FORMATS:
@@ -581,7 +626,16 @@ class NativeTarget:
     def new_cache(self, max_rows: Optional[int] = None) -> TargetKVCache:
         if max_rows is None:
             raise ValueError("NativeTarget.new_cache needs max_rows (prompt + new tokens + block)")
-        return TargetKVCache(self.L, self.n_kv, max_rows, self._dev)
+        return TargetKVCache(self.L, self.n_kv, max_rows, self._dev, kv_format=self.kv_format)
+
+    def _check_cache(self, cache) -> None:
+        if getattr(cache, "kv_format", "bf16") != self.kv_format:
+            raise ValueError(f"NativeTarget(kv_format={self.kv_format!r}) was given a {getattr(cache, 'kv_format', 'bf16')!r} "
+                             f"cache; build it with new_cache()")
+
+    def _kv_scales(self, cache) -> dict:
+        """What the attention launches of a kv_format target take beside the cache (RowStack.run's attn dict)."""
+        return dict(k_scale=cache.k_scale, v_scale=cache.v_scale) if self.kv8 else {}
 
     def _rope_tab(self, need: int):
         if self._rope is None or self._rope[0].shape[0] < need:
@@ -609,6 +663,7 @@ class NativeTarget:
         P = input_ids.shape[1]
         if P > cache.max_rows:
             raise ValueError("target KV cache too small for the prompt")
+        self._check_cache(cache)
         plp = ops.check_prompt_logprobs(prompt_logprobs)
         if plp and not self.native_prefill:
             raise ValueError("prompt_logprobs needs the native prefill: this target runs the wrapped model's forward "
@@ -642,6 +697,11 @@ class NativeTarget:
                             logits=z(16, self.V), ids=torch.zeros(16, dtype=torch.int64, device=dev))
         pf = self._pf
         h, xf, qkv, act, attn = pf["h"], pf["xf"], pf["qkv"], pf["act"], pf["attn"]
+        if self.kv8:   # one layer's K / V rows in bf16, reused by every layer: quantised into the cache, attended dequantised
+            if self.prefill_attn != "native":
+                raise NotImplementedError("NativeTarget: kv_format='fp8_e4m3' with prefill_attn='sdpa' is not implemented")
+            if "kv8_k" not in pf or pf["kv8_k"].shape[1] < Pp:
+                pf["kv8_k"], pf["kv8_v"] = (torch.zeros(self.n_kv, Pp, 128, dtype=BF16, device=dev) for _ in range(2))
         h.zero_()
         torch.index_select(self.embed, 0, input_ids[0], out=h[:P])
         cos, sin = self._rope_tab(P + 64)
@@ -656,10 +716,13 @@ class NativeTarget:
         for i, lw in enumerate(self.layers):
             ops.prefill_norm_pack(h, P, H, lw["ln1"], self.eps, xf)
             ops.prefill_gemm_rows(lw["qkv"], xf, P, nqkv, H, qkv)
+            kl, vl = (pf["kv8_k"], pf["kv8_v"]) if self.kv8 else (cache.k[i], cache.v[i])
             ops.prefill_qk_rope(qkv, P, 0, q_dim, q_dim + kv_dim, self.n_q, self.n_kv, lw["q_norm"], lw["k_norm"], self.eps,
-                                cos, sin, 0, cache.k[i], cache.v[i], 0)
+                                cos, sin, 0, kl, vl, 0)
+            if self.kv8:
+                ops.kv_quant_rows(kl, vl, P, cache.k[i], cache.v[i], cache.k_scale[i], cache.v_scale[i], 0)
             if self.prefill_attn == "native":   # csrc/prefill.hip:k_pattn, straight into o_proj's frag16 operand
-                ops.prefill_attn(qkv, P, 0, cache.k[i], cache.v[i], self.n_q, self.n_kv, 128 ** -0.5, xf)
+                ops.prefill_attn(qkv, P, 0, kl, vl, self.n_q, self.n_kv, 128 ** -0.5, xf)
             else:                               # torch SDPA on the same rows (second implementation: tests, A/B)
                 q = qkv[:P, :q_dim].view(P, self.n_q, 128).transpose(0, 1).unsqueeze(0)
                 o = F.scaled_dot_product_attention(q, cache.k[i][:, :P].unsqueeze(0), cache.v[i][:, :P].unsqueeze(0),
@@ -869,11 +932,14 @@ class NativeTarget:
         ops.embed_rows_batch(self.embed, self._wide_ids, R, st.h, H, rs.ss_emb.view(2, 16), dyn2, ops.DYN_BS)
 
         def attend(i, lw):
-            ops.attn_head(xq=rs.xq, q_col=0, k_col=self.q_dim, v_col=self.q_dim + self.kv_dim, n_q=self.n_q,
-                          n_kv=self.n_kv, q_norm_w=lw["q_norm"], k_norm_w=lw["k_norm"], eps=self.eps, cos_tab=cos,
-                          sin_tab=sin, kcache=cache.k[i], vcache=cache.v[i], scale=128 ** -0.5, causal=True, S=start,
-                          tau=0, bs=bs, pos0=start, ws=rs.head_ws, max_splits=self.max_splits, out_frag=rs.attn,
-                          q_tiles=2, out_tile_stride=rs.attn.stride(0))
+            kw = dict(xq=rs.xq, q_col=0, k_col=self.q_dim, v_col=self.q_dim + self.kv_dim, n_q=self.n_q, n_kv=self.n_kv,
+                      q_norm_w=lw["q_norm"], k_norm_w=lw["k_norm"], eps=self.eps, cos_tab=cos, sin_tab=sin, kcache=cache.k[i],
+                      vcache=cache.v[i], scale=128 ** -0.5, causal=True, S=start, tau=0, bs=bs, pos0=start, ws=rs.head_ws,
+                      max_splits=self.max_splits, out_frag=rs.attn, q_tiles=2, out_tile_stride=rs.attn.stride(0))
+            if self.kv8:
+                ops.attn_head_kv8(**kw, k_scale=cache.k_scale[i], v_scale=cache.v_scale[i])
+            else:
+                ops.attn_head(**kw)
 
         st.run(self.tile_layers(qkv_parts=False), R, dyn2, attend, qkv="rows",
                taps=None if taps is None else taps.view(2, 16, -1), tap_layers=tap_layers, moe=self.moe_mlp_tiles)
@@ -960,6 +1026,10 @@ class NativeTarget:
         top_k / top_p / logprobs / penalties / logit_bias / grammar / min_p: the same asked by keyword, for a caller
         that keeps the state objects itself (LogitsStage.of_keywords); their buffers are this target's."""
         bs = block_ids.numel()
+        self._check_cache(cache)
+        if self.kv8 and (self.fuse_oproj or self.attn_impl != "head"):
+            raise NotImplementedError("NativeTarget: kv_format='fp8_e4m3' runs the plain 'head' attention stage only "
+                                      "(no fuse_oproj, no attn_impl='fused')")
         own = stage is None
         if own:
             stage = LogitsStage.of_keywords(self.V, temperature, top_k=top_k, top_p=top_p, logprobs=logprobs,
@@ -1029,7 +1099,7 @@ class NativeTarget:
         fin = rs.run(self.row_layers(bs), tiles, bs=bs, fuse_oproj=self.fuse_oproj,
                      attend=None if self.attn_impl == "head" else attend,
                      attn=dict(cos_tab=cos, sin_tab=sin, kcache=cache.k, vcache=cache.v, causal=True, S=start, tau=0,
-                               pos0=start, dyn=dyn if dyn_lengths else None),
+                               pos0=start, dyn=dyn if dyn_lengths else None, **self._kv_scales(cache)),
                      taps=taps, tap_layers=tap_layers, moe=self._moe_mlp, gu_events=self.gu_events)
         post = ws["post"]
         logits = logits_out

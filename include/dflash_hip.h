@@ -341,6 +341,25 @@ int dfl_attn_head(const void *xq, int64_t ldq, int q_col, int k_col, int v_col, 
                   float scale, int causal, const int32_t *dyn, int S, int tau, int bs, int pos0, int q_tiles,
                   void *ws, int max_splits, void *out_frag, int64_t out_tile_stride, void *stream);
 
+/* e4m3 KV cache (csrc/attn_head_kv8.hip).  The format: codes uint8 [kv head][cache_rows][128] for K
+ * and for V (OCP e4m3fn), scales float [kv head][cache_rows] for K and for V — 264 bytes per row and head instead of 512.
+ * A row of 128 post-norm, post-RoPE bf16 values has scale = 2^ceil(log2(amax / 448)), not below 2^-64, 1 for an all-zero
+ * row; its codes are the round-to-nearest-even of x / scale; code * scale is an exact bf16.  cache_rows % 4 == 0, codes
+ * and scales 16-byte aligned.
+ * dfl_attn_head_kv8: dfl_attn_head over such a cache — no context rows (tau = 0), q_tiles in {1, 2}, one query head per
+ * workgroup at every length; lengths as immediates (dyn == NULL) or from dyn with S their bound; same ws.  Every key
+ * the stage sees — cached, or one of this launch's own new rows — is exactly code * scale, so its result is dfl_attn_head's
+ * on the dequantised cache; the new rows' codes and scales are appended at rows S.. .
+ * dfl_kv_quant_rows: one layer's bf16 rows k_rows / v_rows [n_kv][src_rows][128], the first P of each head -> codes and
+ * scales at cache rows [row0, row0 + P), and the dequantised values back in place. */
+int dfl_attn_head_kv8(const void *xq, int64_t ldq, int q_col, int k_col, int v_col, int n_q, int n_kv, const void *q_norm_w,
+                      const void *k_norm_w, float eps, const void *cos_tab, const void *sin_tab, int max_pos, void *kcodes,
+                      void *vcodes, float *k_scale, float *v_scale, int cache_rows, float scale, int causal,
+                      const int32_t *dyn, int S, int bs, int pos0, int q_tiles, void *ws, int max_splits, void *out_frag,
+                      int64_t out_tile_stride, void *stream);
+int dfl_kv_quant_rows(void *k_rows, void *v_rows, int src_rows, int P, int n_kv, void *kcodes, void *vcodes, float *k_scale,
+                      float *v_scale, int cache_rows, int row0, void *stream);
+
 /* dfl_attn_head (q_tiles = 1) AND the o_proj + residual GEMM that follows it (model/dflash.py:101,140; for the
  * target tf:modeling_qwen3.py o_proj) in ONE launch: besides the attention workgroups the grid carries one workgroup
  * per 16-column tile of o_proj, which pulls its weight slice into registers while the attention runs (the stage
